@@ -24,6 +24,10 @@ of a diagnostic build, profiles/, same staleness rule).  `parity` is max |rgb - 
 the JAX reference cannot run here) on the same 1024-ray batch by BASELINE.md's protocol: 8 threads and all granted host
 cores, 3 warm-up + 10 timed passes each, median (`cpu_baseline.runs` holds both, `value` the all-cores run).
 `image.ms_per_image_to_host` adds the one device-to-host copy of the gathered keys to the device-complete image time.
+
+`--dump-outputs DIR` writes what the last timed step rendered (rank 0: every output array render_rays hands its
+caller, float32, well under 1 MB) as DIR/<key>.npy.  Inputs and weights are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -339,6 +343,8 @@ def main():
     ap.add_argument("--profile-mode", type=int, default=3,
                     help="HIP events in the timed region: 0 none, 1 every stage, 2 around the dominant kernel of every step, "
                          "3 around the dominant kernel of every 8th step (default: the events of mode 2 cost 2 %% of a step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<key>.npy (rank 0)")
     args = ap.parse_args()
     if args.profile_mode == 3 and args.steps < 16:
         args.profile_mode = 2            # too few steps to sample: events on every step
@@ -444,6 +450,12 @@ def main():
             el = float(t.item())
         run_s.append(el)
     elapsed = sorted(run_s)[len(run_s) // 2]
+    # the last timed step's outputs, copied before the passes below overwrite the output buffers
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = outs[(args.steps - 1) % nstr]
+        dumped = {k: v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+                  for k, v in last.items()}
     if dist is not None:
         # rendered pixels of all ranks, gathered once (image granularity), outside the step loop
         pix = torch.cat([out["rgb"], out["acc"][:, None]], dim=1)
@@ -569,6 +581,10 @@ def main():
         res["cpu_baseline"] = None
     # parity of what was timed: batch 0 of the timed loop against the fp32 oracle (256 of its rays: seconds on the host)
     res["parity"] = secondary("parity", parity_block, cfg, weights, rank, first)
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in dumped.items():
+            np.save(os.path.join(args.dump_outputs, f"{k}.npy"), v)
     sys.stdout.flush()
     os.dup2(json_fd, 1)
     os.close(json_fd)
