@@ -1112,10 +1112,8 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
     F.direct = h->fused_direct;
     // mode 3: the one-wavefront-per-ray form.  Builds with the split-MFMA shader (RC_SPLIT_MFMA) run it for mode 1 as well:
     // the two-wave kernel was unstable with the split form in every layer (rc_dev_mlp.h INSTABILITY; cause not found)
-    // (RC_TEAM_SPLIT=1 in the environment puts the two-wave kernel back under the split form: the configuration
-    // for diagnosis: with the density MLPs fp32, as they are now, tools/stress_repeat.py has not shown a differing launch there)
-    static const bool team_split = getenv("RC_TEAM_SPLIT") && getenv("RC_TEAM_SPLIT")[0] == '1';
-    F.team = (h->fused_mode == 1 && (!kRcSplit || team_split)) ? 1 : 0;
+    // (a split build compiles the two-wave kernel only under -DRC_TEAM_SPLIT_DIAG, for diagnosis: rc_pack_host.h RC_TEAM_KERNEL)
+    F.team = (h->fused_mode == 1 && RC_TEAM_KERNEL) ? 1 : 0;
     F.stagger_cycles = h->fused_stagger;
     F.prio_mode = h->fused_prio;
     if (A.export_samples) {

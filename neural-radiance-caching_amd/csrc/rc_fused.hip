@@ -589,12 +589,14 @@ void rc_launch_fused(const RcFusedLaunch& L, hipStream_t stream) {
     return;
   }
 #endif
+#if RC_TEAM_KERNEL
   if (L.team) {
     a.stagger_cycles = L.stagger_cycles;
     a.prio_mode = L.prio_mode;
     rc_launch_fused_team(a, L.out.ptr[RC_OUT_NORMALS] != nullptr, stream);
     return;
   }
+#endif
   if (L.out.ptr[RC_OUT_NORMALS]) hipLaunchKernelGGL(k_cache_fused<true>, grid, block, lds, stream, a);
   else hipLaunchKernelGGL(k_cache_fused<false>, grid, block, lds, stream, a);
 }

@@ -1,8 +1,8 @@
 // Fused cache forward for primary rays, TWO wavefronts per ray and TWO workgroups per CU: the plain cache pass of
 // BASELINE configs 1, 2, 4 in builds with the fp32-MFMA shader (RC_SPLIT_MFMA=0).  The default build runs the shader on
 // the bf16 pipe (rc_dev_mlp.h, split form) and the one-wavefront-per-ray kernel of rc_fused.hip for this pass too: the
-// kernel was unstable with the split form in every layer (INSTABILITY there; RC_TEAM_SPLIT=1 puts it back for
-// diagnosis).  rc_fused.hip is also the transient front end and the material stage's export.
+// kernel was unstable with the split form in every layer (INSTABILITY there; split builds compile this file only with
+// -DRC_TEAM_SPLIT_DIAG, for diagnosis: rc_pack_host.h RC_TEAM_KERNEL).  rc_fused.hip is also the transient front end and the material stage's export.
 //
 // Why: with one wavefront per ray a 1024-ray batch is one wave per SIMD, and everything a wave waits for -- the
 // texture-address unit working through 10 752 divergent lane requests per ray (the gather phases run at the CU's ~1
@@ -26,6 +26,8 @@
 #include "rc_fused_common.h"
 #include <type_traits>
 #include <utility>
+
+#if RC_TEAM_KERNEL
 
 using namespace rcdev;
 using namespace rcfused;
@@ -870,3 +872,5 @@ void rc_launch_fused_team(const RcFusedArgs& a, bool grad, hipStream_t stream) {
   if (grad) hipLaunchKernelGGL(k_cache_fused_team<true>, grid, block, lds, stream, b);
   else hipLaunchKernelGGL(k_cache_fused_team<false>, grid, block, lds, stream, b);
 }
+
+#endif  // RC_TEAM_KERNEL

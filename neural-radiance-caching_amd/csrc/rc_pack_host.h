@@ -64,6 +64,15 @@ RC_HD inline bool rc_cell_corner(int N, int64_t i, int64_t* entry) {
 #define RC_SPLIT_MFMA 1
 #endif
 constexpr bool kRcSplit = RC_SPLIT_MFMA != 0;
+// The two-wave kernel k_cache_fused_team (rc_fused2.hip) is built where the shader is the fp32 MFMA chain.  Its split form
+// shares a SIMD between waves of two workgroups, the configuration rc_dev_mlp.h INSTABILITY calls unstable, so a split
+// build compiles it only for diagnosis (`make diag DIAG_STAMPS= DIAG_EXTRA=-DRC_TEAM_SPLIT_DIAG`); elsewhere rc_set_fused(1) runs the
+// one-wave kernel (tests/test_code_objects.py holds every bf16-MFMA kernel of the product to the whole register file).
+#if !RC_SPLIT_MFMA || defined(RC_TEAM_SPLIT_DIAG)
+#define RC_TEAM_KERNEL 1
+#else
+#define RC_TEAM_KERNEL 0
+#endif
 // fragments of a weight layer / of a dot_out block (NO outputs over NT hidden tiles + NO bias fragments; padded to whole
 // 1-KiB pieces in the split form so that every layer behind it starts on one)
 constexpr int rc_lfr(int ks, int nt) { return kRcSplit ? ((ks + 7) / 8) * nt * 12 : ks * nt; }

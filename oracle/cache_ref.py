@@ -232,13 +232,15 @@ def model_env_map_rgb(weights, cfg, viewdirs):
 # ----------------------------------------------------------------------------
 # Cache shader (NeRFMLP, passive branch)
 # ----------------------------------------------------------------------------
-def cache_shader(weights, cfg, rays, sres, exec_dead_envmap=False):
+def cache_shader(weights, cfg, rays, sres, exec_dead_envmap=False, app=None):
     """BaseShader.__call__ -> predict_appearance -> _predict_appearance_passive
-    (shading.py:276-339, nerf.py:561-689, 940-1090)."""
+    (shading.py:276-339, nerf.py:561-689, 940-1090).  `app`: appearance-grid features given instead of looked up
+    (tests evaluate the shader alone on another implementation's inputs)."""
     means = sres["means"]
     viewdirs = rays["viewdirs"]
-    app = hashgrid_ref.hash_encoding(weights, f"{P}Cache/Shader/appearance_grid", cfg.appearance_grid,
-                                     mathx.contract_radius(means, cfg.contract_radius))
+    if app is None:
+        app = hashgrid_ref.hash_encoding(weights, f"{P}Cache/Shader/appearance_grid", cfg.appearance_grid,
+                                         mathx.contract_radius(means, cfg.contract_radius))
     feature = torch.cat([sres["feature"], app], dim=-1)                    # shading.py:156-220
     bottleneck = dense(weights, "Cache/Shader/bottleneck_layer", feature)  # nerf.py:394-396
     roughness = mathx.softplus(dense(weights, "Cache/Shader/roughness_layer", feature) + cfg.roughness_bias)

@@ -88,13 +88,16 @@ def zero_invalid_bins(cfg, rays, means, diffuse, specular):
     return torch.where(kill, z, diffuse), torch.where(kill, z, specular)
 
 
-def transient_shader(weights, cfg, rays, sres, occ=None):
-    """predict_appearance -> _predict_appearance_active for the primary pass of the cornell cache."""
+def transient_shader(weights, cfg, rays, sres, occ=None, app=None):
+    """predict_appearance -> _predict_appearance_active for the primary pass of the cornell cache.  `app`:
+    appearance-grid features given instead of looked up (tests evaluate the shader alone on another implementation's
+    inputs)."""
     t = cfg.transient
     means = sres["means"]
     viewdirs = rays["viewdirs"]
-    app = hashgrid_ref.hash_encoding(weights, f"{P}{SH}/appearance_grid", cfg.appearance_grid,
-                                     mathx.contract_radius(means, cfg.contract_radius))
+    if app is None:
+        app = hashgrid_ref.hash_encoding(weights, f"{P}{SH}/appearance_grid", cfg.appearance_grid,
+                                         mathx.contract_radius(means, cfg.contract_radius))
     feature = torch.cat([sres["feature"], app], dim=-1)
     bottleneck = dense(weights, f"{SH}/bottleneck_layer", feature)
     roughness = mathx.softplus(dense(weights, f"{SH}/roughness_layer", feature) + cfg.roughness_bias)
@@ -165,7 +168,7 @@ def transient_shader(weights, cfg, rays, sres, occ=None):
         n_dot_l_rgb=n_dot_l * ones, light_radiance_rgb=light_radiance_mult * ones,
         irradiance_rgb=n_dot_l * light_radiance_before_occ / pymath.pi * ones,
         ray_dists=torch.linalg.norm(rays["origins"][..., None, :] - means, dim=-1, keepdim=True),
-        light_dists=light_dists, roughness=roughness,
+        light_dists=light_dists, roughness=roughness, tint_ibrdf=tint * ibrdf,
     )
     for k, v in sres.items():
         out.setdefault(k, v)

@@ -240,7 +240,8 @@ def test_two_wave_fused_kernel_equals_the_one_wave_kernel(rc, n, jitter_seed):
     without requesting the analytic normals (the GRAD / non-GRAD instantiations).
     A library built with the split-form shader (rc_mlp_arithmetic() == 1, the default) runs the one-wave kernel for mode 1
     as well: there the comparison is of that kernel with itself; it compares the two kernels in a
-    RC_SPLIT_MFMA=0 build (RC_HIP_LIBRARY) -- run that way in round 4: 129 passed."""
+    RC_SPLIT_MFMA=0 build (RC_HIP_LIBRARY).  The real comparison runs in every GPU suite run: tests/test_gpu_f32_build.py
+    runs this module against that build (make variant-f32) in a child process."""
     rays = nrc_amd.synthetic_rays(n, seed=900 + n)
     rnd = None if jitter_seed is None else {"jitter": common.jitters(n, seed=jitter_seed)}
     for outputs in (None, ["rgb", "acc", "distance_median", "normals_pred"]):
