@@ -281,9 +281,18 @@ int rc_hashgrid_lookup(rc_handle* h, int32_t grid_id, const float* points, int64
 int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64_t n, int32_t num_bins,
                         int32_t num_samples, const float* jitter, float* out, void* stream);
 
-/* -- introspection for tests / profiling: named internal buffers of the last rc_render_rays
- * ("sdist0", "tdist2", "density1", "weights2", "shade_rgb", ...).  Returns RC_ERR_INVALID_ARG
- * for unknown names.  count = number of float32 elements. */
+/* -- introspection for tests / profiling: a named workspace buffer as the last call that used its set left it.
+ * name = [prefix]<buffer>.  Prefix: none = set 0 (rc_render_rays on the first caller stream, rc_render_material,
+ * rc_render_transient), "p1:" .. "p3:" = the sets of rc_render_rays on further caller streams, "s:" = the batched
+ * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward.
+ * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
+ * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
+ * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
+ * "acc_sel", "feat_sel", "hbuf_sel", "normals_sel", "density_sel"; "t_irr", "t_slf", "tshade" (set 0 of a time-resolved
+ * handle).  Set 0 only: "m_*", "l_*", "sec_*" (rc_render_material), "sh_*" (rc_render_transient with occlusions).
+ * "t:": "feat", "dfeat", "a1", "a2", "d1", "d2", "fe", "graw", "density", "partial".
+ * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
+ * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
 /* Per-stage device time (ms, hipEvents recorded on the launch stream), averaged over the calls
  * issued since profiling was last (re)enabled (ring of 16).  mode 0 off, 1 every stage,

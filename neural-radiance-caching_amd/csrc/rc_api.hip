@@ -44,6 +44,66 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+// Device copies of the packed weights and of the derived tables (repack).
+enum RawLayer { RAW_MAT_BOTTLENECK, RAW_MAT_BRDF, RAW_LIGHT_0, RAW_LIGHT_1, RAW_LIGHT_OUT, RAW_COUNT };
+const char* const kRawPaths[RAW_COUNT] = {"params/MaterialShader/bottleneck_layer", "params/MaterialShader/pred_brdf_layer",
+                                          "params/LightSampler/layers_0", "params/LightSampler/layers_1",
+                                          "params/LightSampler/output_layer"};
+struct Packs {
+  DevBuf dens[RC_MAX_LEVELS], train[RC_MAX_LEVELS];
+  DevBuf shader, fused, fused_front, envmap, t_shader, t_bins, t_taps;
+  DevBuf pair[RC_MAX_GRID_LEVELS];       // level-2 density + appearance tables interleaved (cell tables on dense levels)
+  DevBuf cell[2][RC_MAX_GRID_LEVELS];    // dense levels of proposal grids 0 / 1 as cell tables
+  DevBuf rec[3][RC_MAX_GRID_LEVELS];     // hashed levels of grids 0-2 as cell records (kLevelHRec)
+  struct { DevBuf kernel, bias; } raw[RAW_COUNT];   // material / light-sampler layers on the Flax layout
+};
+
+// Workspace buffer: device pointer, capacity in bytes, element count of the last request (rc_workspace_ptr).
+struct WsBuf { float* p = nullptr; size_t bytes = 0; int64_t count = 0; };
+// One set of rc_render_rays' launch-per-stage buffers (ensure_workspace).
+struct RenderWs {
+  WsBuf sdist[RC_MAX_LEVELS], tdist[RC_MAX_LEVELS], means[RC_MAX_LEVELS], feat[RC_MAX_LEVELS], density[RC_MAX_LEVELS],
+      weights[RC_MAX_LEVELS];
+  WsBuf hbuf, normals_pred, normals_grad, jac, app, shade, debug, env_rgb, rgb_noenv, acc_ws, inds, src_idx, filt_weight, acc_sel;
+  WsBuf feat_sel, hbuf_sel, normals_sel, density_sel;   // lean resampling pass: the picked samples only
+  WsBuf t_irr, t_slf, tshade;                          // time-resolved cache: set 0 only
+};
+// Set 0 only: rc_render_material's buffers and the shadow rays of rc_render_transient.
+struct ExtraWs {
+  WsBuf m_pts, m_nrm, m_feat, m_mat, m_feat_all, m_mat_all, l_feat, l_vmf, l_vmf_logit, sec_origins, sec_dirs, sec_near,
+      sec_far, sec_lights, sec_samples, m_local_view, sec_rgb, sec_acc, sec_env;
+  WsBuf sh_origins, sh_dirs, sh_near, sh_far, sh_normals, sh_lights, sh_acc;
+};
+// rc_density_backward.
+struct TrainWs { WsBuf feat, dfeat, a1, a2, d1, d2, fe, graw, density, partial; };
+
+// Every workspace buffer by name, for rc_workspace_ptr ("<name>", per-level buffers "<name><level>") and rc_destroy.
+struct WsName {
+  const char* name;
+  WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
+  constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
+  constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
+  constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
+  constexpr WsName(const char* s, WsBuf TrainWs::*m) : name(s), t(m) {}
+};
+namespace wsn {
+using R = RenderWs; using X = ExtraWs; using T = TrainWs;
+#define WS(S, m) WsName(#m, &S::m)
+constexpr WsName kTable[] = {
+    WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
+    WS(R, normals_grad), WS(R, jac), WS(R, app), WS(R, shade), WS(R, debug), WS(R, env_rgb), WS(R, rgb_noenv), WS(R, acc_ws),
+    WS(R, inds), WS(R, src_idx), WS(R, filt_weight), WS(R, acc_sel), WS(R, feat_sel), WS(R, hbuf_sel), WS(R, normals_sel),
+    WS(R, density_sel), WS(R, t_irr), WS(R, t_slf), WS(R, tshade),
+    WS(X, m_pts), WS(X, m_nrm), WS(X, m_feat), WS(X, m_mat), WS(X, m_feat_all), WS(X, m_mat_all), WS(X, l_feat), WS(X, l_vmf),
+    WS(X, l_vmf_logit), WS(X, sec_origins), WS(X, sec_dirs), WS(X, sec_near), WS(X, sec_far), WS(X, sec_lights),
+    WS(X, sec_samples), WS(X, m_local_view), WS(X, sec_rgb), WS(X, sec_acc), WS(X, sec_env), WS(X, sh_origins), WS(X, sh_dirs),
+    WS(X, sh_near), WS(X, sh_far), WS(X, sh_normals), WS(X, sh_lights), WS(X, sh_acc),
+    WS(T, feat), WS(T, dfeat), WS(T, a1), WS(T, a2), WS(T, d1), WS(T, d2), WS(T, fe), WS(T, graw), WS(T, density), WS(T, partial)};
+#undef WS
+constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += e.lv ? RC_MAX_LEVELS : 1; return n; }
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T), "the table lists every workspace buffer");
+}  // namespace wsn
+
 constexpr int kEvSlots = 16;
 
 // Everything that is baked into the kernel arguments of one rc_render_rays call.
@@ -81,22 +141,20 @@ struct rc_handle {
   bool have_envmap = false;
   bool have_material = false;
   // packed MFMA fragments (device)
-  std::map<std::string, DevBuf> packs;
+  Packs packs;
   DevBuf ide_table;
-  // workspace (ws_prefix selects the slot: "" / "p1:".. one per caller stream so that independent
-  // batches enqueued on different streams overlap; "s:" batched secondary trace of the material stage)
-  std::string ws_prefix;
-  // Who used a workspace set last.  Sets 0-3 serve rc_render_rays (one per caller stream, least recently used one taken
-  // over when a fifth stream shows up); set 0 also serves rc_render_material / rc_render_transient (with its "s:"
-  // companion for their batched secondary trace); set 4 ("t:") serves rc_density_backward.  A call whose stream differs
-  // from the set's previous user first waits for that user's last call (event), so two streams never run on one set at
-  // the same time.
+  // Workspace sets.  ws[0..3] serve rc_render_rays, one per caller stream so that independent batches enqueued on
+  // different streams overlap (the least recently used one is taken over when a fifth stream shows up); ws[0] also serves
+  // rc_render_material / rc_render_transient, with ws_x and with ws_sec for their batched secondary trace; ws_train serves
+  // rc_density_backward.  groups[0..3] / groups[4] record who used a render set / the train set last: a call whose stream
+  // differs from the set's previous user first waits for that user's last call (event), so two streams never run on one
+  // set at the same time.
+  RenderWs ws[4], ws_sec;
+  ExtraWs ws_x;
+  TrainWs ws_train;
   struct WsGroup { hipStream_t stream = nullptr; bool used = false; hipEvent_t done = nullptr; uint64_t last_use = 0; };
   WsGroup groups[5];
   uint64_t use_clock = 0;
-  int64_t ws_rays = 0;
-  std::map<std::string, DevBuf> ws;
-  std::map<std::string, int64_t> ws_count;
   // profiling: ring of event sets, one set per render call (slot = call % kEvSlots)
   // mode 0 off, 1 every stage, 2 only the dominant kernel (cache shader), 3 like 2 on every 8th call
   int profiling = 0;
@@ -109,7 +167,6 @@ struct rc_handle {
   rc_transient_config tcfg{};
   float light_power = 0.0f;
   bool have_light_power = false;
-  DevBuf taps;
   int n_taps = 0;
   // fused per-ray kernel for the plain cache pass (fused_mode: 0 never, 1 whenever eligible)
   int fused_mode = 1;
@@ -284,15 +341,31 @@ std::vector<float> pad_stream(std::vector<float> v) {
   return v;
 }
 
-int upload(rc_handle* h, const std::string& key, const std::vector<float>& v) {
-  DevBuf& b = h->packs[key];
-  if (b.bytes != v.size() * sizeof(float)) {
+// (Re)allocate a pack to exactly `floats` elements.
+int pack_alloc(rc_handle* h, DevBuf& b, size_t floats) {
+  if (b.bytes != floats * sizeof(float)) {
     if (b.p) RC_HIP(h, hipFree(b.p));
-    RC_HIP(h, hipMalloc((void**)&b.p, v.size() * sizeof(float)));
-    b.bytes = v.size() * sizeof(float);
+    b = DevBuf{};
+    RC_HIP(h, hipMalloc((void**)&b.p, floats * sizeof(float)));
+    b.bytes = floats * sizeof(float);
   }
+  return RC_OK;
+}
+int upload(rc_handle* h, DevBuf& b, const std::vector<float>& v) {
+  if (int rc = pack_alloc(h, b, v.size())) return rc;
   RC_HIP(h, hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice));
   return RC_OK;
+}
+template <class Buf> void free_buf(Buf& b) { if (b.p) (void)hipFree(b.p); b = Buf{}; }
+void free_packs(Packs& P) {
+  for (DevBuf* b : {&P.shader, &P.fused, &P.fused_front, &P.envmap, &P.t_shader, &P.t_bins, &P.t_taps}) free_buf(*b);
+  for (int l = 0; l < RC_MAX_LEVELS; ++l) { free_buf(P.dens[l]); free_buf(P.train[l]); }
+  for (int l = 0; l < RC_MAX_GRID_LEVELS; ++l) {
+    free_buf(P.pair[l]);
+    for (int g = 0; g < 2; ++g) free_buf(P.cell[g][l]);
+    for (int g = 0; g < 3; ++g) free_buf(P.rec[g][l]);
+  }
+  for (auto& r : P.raw) { free_buf(r.kernel); free_buf(r.bias); }
 }
 
 const HostLayer* need(rc_handle* h, const std::string& path, std::string& missing) {
@@ -337,28 +410,13 @@ int build_fused_tables(rc_handle* h) {
     for (int l = 0; l < h->grids[2].dev.num_levels; ++l) {
       if (h->grids[2].dev.lvl[l].dense) continue;          // dense levels: cell tables below
       const size_t entries = h->grids[2].dev.lvl[l].entries;
-      DevBuf& b = h->packs["pair_" + std::to_string(l)];
-      const size_t bytes = entries * 8 * sizeof(float);
-      if (b.bytes != bytes) {
-        if (b.p) RC_HIP(h, hipFree(b.p));
-        RC_HIP(h, hipMalloc((void**)&b.p, bytes));
-        b.bytes = bytes;
-      }
+      DevBuf& b = h->packs.pair[l];
+      if ((rc = pack_alloc(h, b, entries * 8))) return rc;
       RC_HIP(h, hipMemcpy2D(b.p, 32, h->grids[2].dev.lvl[l].table, 16, 16, entries, hipMemcpyDeviceToDevice));
       RC_HIP(h, hipMemcpy2D(b.p + 4, 32, h->grids[3].dev.lvl[l].table, 16, 16, entries, hipMemcpyDeviceToDevice));
     }
     // dense levels as cell tables (the 8 corners of every cell of the zero-padded volume side by side):
     // proposal grids 0 / 1: 8 floats per cell; level-2 pair: 8 x [density 4 | appearance 4] per cell
-    auto cells = [&](const std::string& key, size_t floats, float** out) -> int {
-      DevBuf& b = h->packs[key];
-      if (b.bytes != floats * sizeof(float)) {
-        if (b.p) RC_HIP(h, hipFree(b.p));
-        RC_HIP(h, hipMalloc((void**)&b.p, floats * sizeof(float)));
-        b.bytes = floats * sizeof(float);
-      }
-      *out = b.p;
-      return RC_OK;
-    };
     for (int g = 0; g < 3; ++g)
       for (int l = 0; l < h->grids[g].dev.num_levels; ++l) {
         const RcGridLevel& L = h->grids[g].dev.lvl[l];
@@ -371,21 +429,21 @@ int build_fused_tables(rc_handle* h) {
           if (l < kRcFusedDenseLevels + nrl && L.mask != 0) {
             const int F = h->grids[g].dev.num_features;
             const size_t nrec = (size_t)(L.size + 1) * (L.size + 1) * (L.size + 1);
-            float* dst = nullptr;
-            if ((rc = cells("rec" + std::to_string(g) + "_" + std::to_string(l), nrec * 8 * F, &dst))) return rc;
+            if ((rc = pack_alloc(h, h->packs.rec[g][l], nrec * 8 * F))) return rc;
+            float* dst = h->packs.rec[g][l].p;
             rc_launch_build_hrec(L.table, L.size, L.mask, F, dst, nullptr);
             h->grids[g].dev.lvl[l].rec = dst;
           }
           continue;
         }
         const size_t ncell = (size_t)(L.size + 3) * (L.size + 3) * (L.size + 3);
-        float* dst = nullptr;
+        DevBuf& b = g < 2 ? h->packs.cell[g][l] : h->packs.pair[l];      // the level-2 pair: replaces the flat pair table
+        if ((rc = pack_alloc(h, b, ncell * (g < 2 ? 8 : 64)))) return rc;
+        float* dst = b.p;
         if (g < 2) {
-          if ((rc = cells("cell" + std::to_string(g) + "_" + std::to_string(l), ncell * 8, &dst))) return rc;
           rc_launch_build_cells(L.table, L.size, 1, dst, 1, 0, nullptr);
           h->grids[g].dev.lvl[l].cell = dst;       // the launch-per-stage gather reads it as well
         } else {
-          if ((rc = cells("pair_" + std::to_string(l), ncell * 64, &dst))) return rc;      // replaces the flat pair table
           rc_launch_build_cells(L.table, L.size, 4, dst, 8, 0, nullptr);
           rc_launch_build_cells(h->grids[3].dev.lvl[l].table, L.size, 4, dst, 8, 4, nullptr);
         }
@@ -395,20 +453,27 @@ int build_fused_tables(rc_handle* h) {
   return RC_OK;
 }
 
-// The per-batch launch descriptor of the fused plan with every pointer and constant that only changes with the weights.
-void build_fused_template(rc_handle* h) {
+// What the fused plan and its FRONT variant share: grids, derived tables and the constants of the proposal sampler.
+RcFusedLaunch fused_front_end(rc_handle* h) {
   const rc_config& c = h->cfg;
   RcFusedLaunch F{};
   for (int l = 0; l < 3; ++l) F.num_samples[l] = c.num_samples[l];
   for (int g = 0; g < 4; ++g) F.grid[g] = &h->grids[g].dev;
-  for (int l = 0; l < h->grids[2].dev.num_levels; ++l) F.pair_table[l] = h->packs["pair_" + std::to_string(l)].p;
+  for (int l = 0; l < h->grids[2].dev.num_levels; ++l) F.pair_table[l] = h->packs.pair[l].p;
   for (int g = 0; g < 2; ++g)
     for (int l = 0; l < h->grids[g].dev.num_levels; ++l)
-      F.cell_table[g][l] = h->grids[g].dev.lvl[l].dense ? h->packs["cell" + std::to_string(g) + "_" + std::to_string(l)].p
+      F.cell_table[g][l] = h->grids[g].dev.lvl[l].dense ? h->packs.cell[g][l].p
                                                         : h->grids[g].dev.lvl[l].rec;      // cell records of a kLevelHRec level, or NULL
-  F.wstream = h->packs["fused"].p; F.ide_coef = h->ide_table.p;
   F.anneal = c.anneal; F.padding = c.resample_padding; F.density_bias = c.density_bias;
   F.contract_radius = c.contract_radius; F.bg = c.bg_intensity;
+  return F;
+}
+
+// The per-batch launch descriptor of the fused plan with every pointer and constant that only changes with the weights.
+void build_fused_template(rc_handle* h) {
+  const rc_config& c = h->cfg;
+  RcFusedLaunch F = fused_front_end(h);
+  F.wstream = h->packs.fused.p; F.ide_coef = h->ide_table.p;
   for (int i = 0; i < 3; ++i) F.pct[i] = c.percentiles[i];
   F.roughness_bias = c.roughness_bias; F.irradiance_bias = c.irradiance_bias; F.ambient_bias = c.ambient_irradiance_bias;
   F.rgb_max = c.rgb_max; F.slf_ambient_bias = c.slf_ambient_bias;
@@ -452,6 +517,13 @@ int repack(rc_handle* h) {
   std::string missing;
   const rc_config& c = h->cfg;
   std::vector<float> fused_parts[4];
+  if (!h->ide_table.p) {      // directional-encoding coefficients of the cache shaders (both kinds of handle)
+    RcIdeTable tb;
+    build_ide_table(tb);
+    RC_HIP(h, hipMalloc((void**)&h->ide_table.p, sizeof(tb)));
+    h->ide_table.bytes = sizeof(tb);
+    RC_HIP(h, hipMemcpy(h->ide_table.p, &tb, sizeof(tb), hipMemcpyHostToDevice));
+  }
   // all grids of the cache path must be loaded
   for (int g = 0; g < 4; ++g)
     for (size_t l = 0; l < h->grids[g].sizes.size(); ++l)
@@ -486,7 +558,7 @@ int repack(rc_handle* h) {
       append(stream, pack_f32(sb, {tile_full(&w0t, 0, 0, false)}));
     }
     if (l < 3) fused_parts[l] = stream;
-    int rc = upload(h, "dens_" + std::to_string(l), pad_stream(stream));
+    int rc = upload(h, h->packs.dens[l], pad_stream(stream));
     if (rc) return rc;
   }
   if (h->transient) {
@@ -503,7 +575,7 @@ int repack(rc_handle* h) {
     ok = ok && (int)(stream.size() / 64) == off[3];
     h->fused_front_ok = ok;
     if (ok) {
-      int rc = upload(h, "fused_front", pad_stream(stream));
+      int rc = upload(h, h->packs.fused_front, pad_stream(stream));
       if (rc) return rc;
       if ((rc = build_fused_tables(h))) return rc;
     }
@@ -562,7 +634,7 @@ int repack(rc_handle* h) {
                              tile_full(lb, 3, 0, false)}));
     append(stream, pack_dot({Col{la, 0}, Col{la, 1}, Col{la, 2}}, 4));
     fused_parts[3] = stream;
-    int rc = upload(h, "shader", pad_stream(stream));
+    int rc = upload(h, h->packs.shader, pad_stream(stream));
     if (rc) return rc;
   }
   {
@@ -580,7 +652,7 @@ int repack(rc_handle* h) {
     ok = ok && (int)(stream.size() / 64) == nf;
     h->fused_ok = ok;
     if (ok) {
-      int rc = upload(h, "fused", pad_stream(stream));
+      int rc = upload(h, h->packs.fused, pad_stream(stream));
       if (rc) return rc;
       if ((rc = build_fused_tables(h))) return rc;
     }
@@ -615,32 +687,24 @@ int repack(rc_handle* h) {
       append(stream, pack(s, {tile_full(eb, 0, 256), tile_full(eb, 1, 256), tile_full(eb, 2, 256), tile_full(eb, 3, 256)}));
       s.clear(); steps_acc(s, 4, 0); step_bias(s);
       append(stream, pack(s, {tile_by_reg({Col{eo, 0}, Col{eo, 1}, Col{eo, 2}})}));
-      int rc = upload(h, "envmap", pad_stream(stream));
+      int rc = upload(h, h->packs.envmap, pad_stream(stream));
       if (rc) return rc;
     }
   }
   {
     // material / light heads run as plain per-point kernels on the Flax layout
     h->have_material = true;
-    for (const char* pth : {"params/MaterialShader/bottleneck_layer", "params/MaterialShader/pred_brdf_layer",
-                            "params/LightSampler/layers_0", "params/LightSampler/layers_1", "params/LightSampler/output_layer"}) {
+    for (int i = 0; i < RAW_COUNT; ++i) {
       std::string miss;
-      const HostLayer* L = need(h, pth, miss);
+      const HostLayer* L = need(h, kRawPaths[i], miss);
       if (!L) { h->have_material = false; continue; }
-      int rc = upload(h, std::string("raw:") + pth + "/kernel", L->kernel);
+      int rc = upload(h, h->packs.raw[i].kernel, L->kernel);
       if (rc) return rc;
-      if ((rc = upload(h, std::string("raw:") + pth + "/bias", L->bias))) return rc;
+      if ((rc = upload(h, h->packs.raw[i].bias, L->bias))) return rc;
     }
     for (int g = 4; g < 6; ++g)
       for (size_t l = 0; l < h->grids[g].sizes.size(); ++l)
         if (!h->grids[g].loaded[l]) h->have_material = false;
-  }
-  if (!h->ide_table.p) {
-    RcIdeTable tb;
-    build_ide_table(tb);
-    RC_HIP(h, hipMalloc((void**)&h->ide_table.p, sizeof(tb)));
-    h->ide_table.bytes = sizeof(tb);
-    RC_HIP(h, hipMemcpy(h->ide_table.p, &tb, sizeof(tb), hipMemcpyHostToDevice));
   }
   if (h->fused_ok) build_fused_template(h);
   h->packed_dirty = false;
@@ -652,68 +716,83 @@ int repack(rc_handle* h) {
 // ---------------------------------------------------------------------------------------------
 void drop_graphs(rc_handle* h);
 
-int ws_alloc(rc_handle* h, const std::string& name0, int64_t count) {
-  const std::string name = h->ws_prefix + name0;
-  DevBuf& b = h->ws[name];
+int ws_alloc(rc_handle* h, WsBuf& b, int64_t count) {
   const size_t bytes = (size_t)count * sizeof(float);
   if (b.bytes < bytes) {
     // captured graphs have workspace pointers baked into their kernel arguments: none survives a reallocation
     // (whichever entry point grew the buffer), so this is the one place that invalidates them
     drop_graphs(h);
     if (b.p) RC_HIP(h, hipFree(b.p));
+    b = WsBuf{};
     RC_HIP(h, hipMalloc((void**)&b.p, bytes));
     b.bytes = bytes;
   }
-  h->ws_count[name] = count;
+  b.count = count;
   return RC_OK;
 }
-float* W(rc_handle* h, const std::string& name) { return h->ws[h->ws_prefix + name].p; }
 
-int ensure_workspace(rc_handle* h, int64_t n) {
+int ensure_workspace(rc_handle* h, RenderWs& w, int64_t n) {
   // ws_alloc only (re)allocates when a buffer is too small and always records the current element
   // count, so after the largest batch has been seen this is allocation-free.
   const rc_config& c = h->cfg;
   int rc;
   for (int l = 0; l < c.num_levels; ++l) {
     const int64_t S = c.num_samples[l];
-    const std::string L = std::to_string(l);
     const int LF = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
-    if ((rc = ws_alloc(h, "sdist" + L, n * (S + 1)))) return rc;
-    if ((rc = ws_alloc(h, "tdist" + L, n * (S + 1)))) return rc;
-    if ((rc = ws_alloc(h, "means" + L, 3 * n * S))) return rc;
-    if ((rc = ws_alloc(h, "feat" + L, (int64_t)LF * n * S))) return rc;
-    if ((rc = ws_alloc(h, "density" + L, n * S))) return rc;
-    if ((rc = ws_alloc(h, "weights" + L, n * S))) return rc;
+    if ((rc = ws_alloc(h, w.sdist[l], n * (S + 1))) || (rc = ws_alloc(h, w.tdist[l], n * (S + 1))) ||
+        (rc = ws_alloc(h, w.means[l], 3 * n * S)) || (rc = ws_alloc(h, w.feat[l], (int64_t)LF * n * S)) ||
+        (rc = ws_alloc(h, w.density[l], n * S)) || (rc = ws_alloc(h, w.weights[l], n * S)))
+      return rc;
   }
   const int64_t S2 = c.num_samples[c.num_levels - 1];
   const int64_t np = n * S2;
-  if ((rc = ws_alloc(h, "hbuf", ((np + 31) / 32) * 32 * 64))) return rc;
-  if ((rc = ws_alloc(h, "normals_pred", 3 * np))) return rc;
-  if ((rc = ws_alloc(h, "normals_grad", 3 * np))) return rc;
-  if ((rc = ws_alloc(h, "jac", 3 * 32 * np))) return rc;
-  if ((rc = ws_alloc(h, "app", 32 * np))) return rc;
-  if ((rc = ws_alloc(h, "shade", RC_SHADE_CH * np))) return rc;
-  if ((rc = ws_alloc(h, "debug", 32 * ((np + 31) / 32) + 64))) return rc;
-  if ((rc = ws_alloc(h, "env_rgb", 3 * n))) return rc;
-  if ((rc = ws_alloc(h, "rgb_noenv", 3 * n))) return rc;
-  if ((rc = ws_alloc(h, "acc_ws", n))) return rc;
-  if ((rc = ws_alloc(h, "inds", n))) return rc;
-  if ((rc = ws_alloc(h, "src_idx", n))) return rc;
-  if ((rc = ws_alloc(h, "filt_weight", n))) return rc;
-  if ((rc = ws_alloc(h, "acc_sel", n))) return rc;
+  if ((rc = ws_alloc(h, w.hbuf, ((np + 31) / 32) * 32 * 64)) || (rc = ws_alloc(h, w.normals_pred, 3 * np)) ||
+      (rc = ws_alloc(h, w.normals_grad, 3 * np)) || (rc = ws_alloc(h, w.jac, 3 * 32 * np)) || (rc = ws_alloc(h, w.app, 32 * np)) ||
+      (rc = ws_alloc(h, w.shade, RC_SHADE_CH * np)) || (rc = ws_alloc(h, w.debug, 32 * ((np + 31) / 32) + 64)) ||
+      (rc = ws_alloc(h, w.env_rgb, 3 * n)) || (rc = ws_alloc(h, w.rgb_noenv, 3 * n)) || (rc = ws_alloc(h, w.acc_ws, n)) ||
+      (rc = ws_alloc(h, w.inds, n)) || (rc = ws_alloc(h, w.src_idx, n)) || (rc = ws_alloc(h, w.filt_weight, n)) ||
+      (rc = ws_alloc(h, w.acc_sel, n)))
+    return rc;
   // lean resampling pass: last-level features / hidden vector / predicted normals of the picked samples only
-  if ((rc = ws_alloc(h, "feat_sel", 32 * n))) return rc;
-  if ((rc = ws_alloc(h, "hbuf_sel", ((n + 31) / 32) * 32 * 64))) return rc;
-  if ((rc = ws_alloc(h, "normals_sel", 3 * n))) return rc;
-  if ((rc = ws_alloc(h, "density_sel", n))) return rc;
-  if (h->transient && h->ws_prefix.empty()) {
+  if ((rc = ws_alloc(h, w.feat_sel, 32 * n)) || (rc = ws_alloc(h, w.hbuf_sel, ((n + 31) / 32) * 32 * 64)) ||
+      (rc = ws_alloc(h, w.normals_sel, 3 * n)) || (rc = ws_alloc(h, w.density_sel, n)))
+    return rc;
+  if (h->transient && &w == &h->ws[0]) {
     const int64_t tiles = (np + 31) / 32;
-    if ((rc = ws_alloc(h, "t_irr", tiles * 32 * 64))) return rc;
-    if ((rc = ws_alloc(h, "t_slf", tiles * 64 * 64))) return rc;
-    if ((rc = ws_alloc(h, "tshade", (int64_t)RC_TS_COUNT * np))) return rc;
+    if ((rc = ws_alloc(h, w.t_irr, tiles * 32 * 64)) || (rc = ws_alloc(h, w.t_slf, tiles * 64 * 64)) ||
+        (rc = ws_alloc(h, w.tshade, (int64_t)RC_TS_COUNT * np)))
+      return rc;
   }
-  if (n > h->ws_rays) h->ws_rays = n;
   return RC_OK;
+}
+
+void free_workspace(rc_handle* h) {
+  for (const WsName& e : wsn::kTable) {
+    for (RenderWs* r : {&h->ws[0], &h->ws[1], &h->ws[2], &h->ws[3], &h->ws_sec}) {
+      if (e.r) free_buf(r->*e.r);
+      if (e.lv) for (WsBuf& b : r->*e.lv) free_buf(b);
+    }
+    if (e.x) free_buf(h->ws_x.*e.x);
+    if (e.t) free_buf(h->ws_train.*e.t);
+  }
+}
+
+// rc_workspace_ptr: "[p1:|p2:|p3:|s:|t:]<name>[level]" -> the buffer (nullptr for an unknown name)
+WsBuf* ws_find(rc_handle* h, const char* name) {
+  const char* colon = strchr(name, ':');
+  const std::string pre = colon ? std::string(name, colon + 1) : "", leaf = colon ? colon + 1 : name;
+  const char* const kPre[6] = {"", "p1:", "p2:", "p3:", "s:", "t:"};
+  int set = -1;      // 0-3 rc_render_rays' sets (0 with the extras), 4 the secondary set, 5 the train set
+  for (int i = 0; i < 6; ++i) if (pre == kPre[i]) set = i;
+  RenderWs* r = set < 0 || set == 5 ? nullptr : (set == 4 ? &h->ws_sec : &h->ws[set]);
+  for (const WsName& e : wsn::kTable) {
+    const size_t k = strlen(e.name);
+    if (leaf.compare(0, k, e.name) != 0) continue;
+    if (leaf.size() == k && ((e.r && r) || (e.x && set == 0) || (e.t && set == 5)))
+      return e.r ? &(r->*e.r) : e.x ? &(h->ws_x.*e.x) : &(h->ws_train.*e.t);
+    if (e.lv && r && leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels) return &(r->*e.lv)[leaf[k] - '0'];
+  }
+  return nullptr;
 }
 
 // roctx ranges around the stages (tracing), for `rocprofv3 --marker-trace`.  The marker library is resolved at run
@@ -771,6 +850,10 @@ int ws_leave(rc_handle* h, int g, hipStream_t st) {
   RC_HIP(h, hipEventRecord(h->groups[g].done, st));
   return RC_OK;
 }
+struct WsLeave {      // an entry point's every exit records the "done" event of the set it entered
+  rc_handle* h; int g; hipStream_t st; bool on;
+  ~WsLeave() { if (on) (void)ws_leave(h, g, st); }
+};
 // Workspace set of rc_render_rays for caller stream `st`: its own, else a free one, else the least recently used.
 int ws_pick(rc_handle* h, hipStream_t st) {
   int free_i = -1, lru = 0;
@@ -872,10 +955,9 @@ void rc_destroy(rc_handle* h) {
   try {
   (void)hipSetDevice(h->device);
   for (auto& g : h->grids)
-    for (auto& t : g.tables)
-      if (t.p) (void)hipFree(t.p);
-  for (auto& kv : h->packs) if (kv.second.p) (void)hipFree(kv.second.p);
-  for (auto& kv : h->ws) if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& t : g.tables) free_buf(t);
+  free_packs(h->packs);
+  free_workspace(h);
   if (h->ide_table.p) (void)hipFree(h->ide_table.p);
   drop_graphs(h);
   for (auto& G : h->groups) if (G.done) (void)hipEventDestroy(G.done);
@@ -1032,10 +1114,10 @@ int rc_stage_times_ms(rc_handle* h, float* out_ms, int32_t n) {
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count) {
   RC_TRY
   if (!h || !name || !ptr || !count) return RC_ERR_INVALID_ARG;
-  auto it = h->ws.find(name);
-  if (it == h->ws.end()) return fail(h, RC_ERR_INVALID_ARG, std::string("rc_workspace_ptr: unknown buffer ") + name);
-  *ptr = it->second.p;
-  *count = h->ws_count[name];
+  const WsBuf* b = ws_find(h, name);
+  if (!b || !b->p) return fail(h, RC_ERR_INVALID_ARG, std::string("rc_workspace_ptr: unknown buffer ") + name);
+  *ptr = b->p;
+  *count = b->count;
   return RC_OK;
   RC_CATCH(h)
 }
@@ -1087,10 +1169,10 @@ struct RenderArgs {
   bool* env_released = nullptr;    // set when the launch plan taken had the spot (the caller releases the EnvMap itself otherwise)
 };
 
-void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, hipStream_t st);
+void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st);
 
-// Enqueue the whole launch sequence on `st` (also used under stream capture).
-void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
+// Enqueue the whole launch sequence on `st` (also used under stream capture) with workspace set `w`.
+void enqueue_all(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st) {
   const rc_config& c = h->cfg;
   const int NL = c.num_levels;
   const int64_t n = A.n;
@@ -1103,8 +1185,7 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
                     !A.out.ptr[RC_OUT_NORMALS];
   const int slot = A.slot;
   if (A.fused) {
-    // everything of the launch that only changes when weights are (re)packed was resolved then (fused_template): no
-    // string keys, no map lookups on the per-batch path
+    // everything of the launch that only changes when weights are (re)packed was resolved then (build_fused_template)
     RcFusedLaunch F = h->fused_tmpl;
     F.rays = A.rays; F.n = n;
     for (int l = 0; l < 3; ++l) F.jitter[l] = rnd ? rnd->jitter[l] : nullptr;
@@ -1117,10 +1198,8 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
     F.stagger_cycles = h->fused_stagger;
     F.prio_mode = h->fused_prio;
     if (A.export_samples) {
-      const std::string L2 = std::to_string(NL - 1);
       F.export_samples = 1;
-      F.f_tdist = W(h, "tdist" + L2); F.f_density = W(h, "density" + L2); F.f_means = W(h, "means" + L2);
-      F.f_normals_pred = W(h, "normals_pred");
+      F.f_tdist = w.tdist[NL - 1].p; F.f_density = w.density[NL - 1].p; F.f_means = w.means[NL - 1].p; F.f_normals_pred = w.normals_pred.p;
     }
     // profiling: the single launch is reported as the "shader" stage, every other stage as 0
     for (int i = 0; i <= ST_SHADER; ++i) stage_mark(h, slot, i, st);
@@ -1132,46 +1211,34 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
   if (A.tout && h->fused_front_ok && h->fused_mode != 0 && !secondary && !resample && !A.weights_only) {
     // time-resolved cache on primary rays: the whole proposal sampler + appearance lookup as ONE launch (the FRONT
     // variant of the fused kernel), results in the workspace buffers the stages behind it read
-    const std::string L2 = std::to_string(NL - 1);
-    RcFusedLaunch F{};
+    RcFusedLaunch F = fused_front_end(h);
     F.rays = A.rays; F.n = n;
-    for (int l = 0; l < 3; ++l) { F.jitter[l] = rnd ? rnd->jitter[l] : nullptr; F.num_samples[l] = c.num_samples[l]; }
-    for (int g = 0; g < 4; ++g) F.grid[g] = &h->grids[g].dev;
-    for (int l = 0; l < h->grids[2].dev.num_levels; ++l) F.pair_table[l] = h->packs["pair_" + std::to_string(l)].p;
-    for (int g = 0; g < 2; ++g)
-      for (int l = 0; l < h->grids[g].dev.num_levels; ++l)
-        F.cell_table[g][l] = h->grids[g].dev.lvl[l].dense ? h->packs["cell" + std::to_string(g) + "_" + std::to_string(l)].p
-                                                        : h->grids[g].dev.lvl[l].rec;      // cell records of a kLevelHRec level, or NULL
-    F.wstream = h->packs["fused_front"].p; F.ide_coef = nullptr;
-    F.anneal = c.anneal; F.padding = c.resample_padding; F.density_bias = c.density_bias;
-    F.contract_radius = c.contract_radius; F.bg = c.bg_intensity;
-    memset(&F.out, 0, sizeof(F.out));
+    for (int l = 0; l < 3; ++l) F.jitter[l] = rnd ? rnd->jitter[l] : nullptr;
+    F.wstream = h->packs.fused_front.p;
     F.front = 1;
     F.want_grad = (A.out.ptr[RC_OUT_NORMALS] != nullptr || A.force_grad) ? 1 : 0;
     F.use_raydist = 1; F.raydist_p = c.raydist_p; F.raydist_premult = c.raydist_premult;   // TransientNeRFModel (see below)
-    F.f_tdist = W(h, "tdist" + L2); F.f_density = W(h, "density" + L2); F.f_means = W(h, "means" + L2);
-    F.f_normals_pred = W(h, "normals_pred"); F.f_normals_grad = W(h, "normals_grad"); F.f_hbuf = W(h, "hbuf"); F.f_app = W(h, "app");
+    F.f_tdist = w.tdist[NL - 1].p; F.f_density = w.density[NL - 1].p; F.f_means = w.means[NL - 1].p;
+    F.f_normals_pred = w.normals_pred.p; F.f_normals_grad = w.normals_grad.p; F.f_hbuf = w.hbuf.p; F.f_app = w.app.p;
     rc_launch_fused(F, st);
-    enqueue_transient_tail(h, A, st);
+    enqueue_transient_tail(h, A, w, st);
     return;
   }
   for (int l = 0; l < NL; ++l) {
-    const std::string L = std::to_string(l), Lp = std::to_string(l - 1);
     const int S = c.num_samples[l];
     const int64_t np = n * S;
     RcSampleArgs sa{};
     sa.origins = rays->origins; sa.directions = rays->directions; sa.viewdirs = rays->viewdirs;
     sa.near = rays->near; sa.far = rays->far; sa.normals = rays->normals; sa.n_rays = n;
     if (l > 0) {
-      sa.prev_sdist = W(h, "sdist" + Lp); sa.prev_tdist = W(h, "tdist" + Lp); sa.prev_density = W(h, "density" + Lp);
-      sa.P = c.num_samples[l - 1];
-      sa.prev_weights = W(h, "weights" + Lp);
+      sa.prev_sdist = w.sdist[l - 1].p; sa.prev_tdist = w.tdist[l - 1].p; sa.prev_density = w.density[l - 1].p;
+      sa.P = c.num_samples[l - 1]; sa.prev_weights = w.weights[l - 1].p;
     } else {
       sa.P = 1;
     }
     sa.S = S;
     sa.jitter = rnd ? rnd->jitter[l] : nullptr;
-    sa.sdist = W(h, "sdist" + L); sa.tdist = W(h, "tdist" + L); sa.means = W(h, "means" + L);
+    sa.sdist = w.sdist[l].p; sa.tdist = w.tdist[l].p; sa.means = w.means[l].p;
     sa.anneal = c.anneal; sa.padding = c.resample_padding;
     sa.secondary = secondary ? 1 : 0;
     sa.use_raydist = (secondary || h->transient) ? 1 : 0;     // TransientNeRFModel: use_raydist_for_secondary_only = False
@@ -1185,8 +1252,8 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
     const bool level_kernel = h->fused_mode != 0 && !h->profiling && rc_level_supported(h->grids[l].dev) && !want_grad &&
                               (l < NL - 1 || (lean && !A.tout));
     RcLevelArgs la{};
-    la.grid = &h->grids[l].dev; la.means = W(h, "means" + L); la.n = np; la.wstream = h->packs["dens_" + L].p;
-    la.density_bias = c.density_bias; la.contract_radius = c.contract_radius; la.density = W(h, "density" + L);
+    la.grid = &h->grids[l].dev; la.means = w.means[l].p; la.n = np; la.wstream = h->packs.dens[l].p;
+    la.density_bias = c.density_bias; la.contract_radius = c.contract_radius; la.density = w.density[l].p;
     // (one ray per wave pays from ~100 rays per CU on: measured break-even of the whole pass near 32 k rays, +27 us at 1-4 k)
     if (level_kernel && (h->fused_mode == 1 || h->fused_mode == 3) && n >= 24576 && rc_level_ray_supported(h->grids[l].dev, S)) {
       roctx_stage(l == 0 ? "level0 (sample+grid+mlp)" : (l == 1 ? "level1 (sample+grid+mlp)" : "level2 (sample+grid+mlp)"));
@@ -1210,36 +1277,31 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
       rc_launch_level(la, st);
       continue;
     }
-    rc_launch_hashgrid(h->grids[l].dev, W(h, "means" + L), 1, np, W(h, "feat" + L), 1, np, c.contract_radius,
-                       want_grad ? W(h, "jac") : nullptr, st);
+    rc_launch_hashgrid(h->grids[l].dev, w.means[l].p, 1, np, w.feat[l].p, 1, np, c.contract_radius, want_grad ? w.jac.p : nullptr, st);
 
     RcDensityMlpArgs da{};
-    da.feat = W(h, "feat" + L); da.n = np; da.ld = np;
+    da.feat = w.feat[l].p; da.n = np; da.ld = np;
     da.K = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
-    da.wstream = h->packs["dens_" + L].p;
-    da.means = W(h, "means" + L);
+    da.wstream = h->packs.dens[l].p; da.means = w.means[l].p;
     da.density_bias = c.density_bias; da.contract_radius = c.contract_radius; da.bbox = h->grids[l].cfg.bbox;
-    da.last = (l == NL - 1) ? 1 : 0;
-    da.density = W(h, "density" + L);
+    da.last = (l == NL - 1) ? 1 : 0; da.density = w.density[l].p;
     // lean resampling pass: the hidden feature / predicted normals are only needed at the ONE sample per ray picked
     // below, so they are not written for all of them here (256 + 12 bytes per sample) but recomputed for the picks
-    da.hbuf = (da.last && !lean) ? W(h, "hbuf") : nullptr;
-    da.normals_pred = (da.last && !lean) ? W(h, "normals_pred") : nullptr;
-    da.jac = want_grad ? W(h, "jac") : nullptr;
-    da.normals_grad = want_grad ? W(h, "normals_grad") : nullptr;
+    da.hbuf = (da.last && !lean) ? w.hbuf.p : nullptr;
+    da.normals_pred = (da.last && !lean) ? w.normals_pred.p : nullptr;
+    da.jac = want_grad ? w.jac.p : nullptr; da.normals_grad = want_grad ? w.normals_grad.p : nullptr;
     stage_mark(h, slot, ST_MLP0 + 3 * l, st);
     rc_launch_density_mlp(da, st);
   }
-  const std::string LL = std::to_string(NL - 1);
   const int S2 = c.num_samples[NL - 1];
   const int64_t np2 = n * S2;
   if (A.weights_only) {
     // weights_only=True (models.py:944-982): no shader; only acc = sum of the last level's weights is consumed
     RcCompositeArgs ca{};
     ca.directions = rays->directions; ca.origins = rays->origins; ca.lights = rays->lights; ca.n_rays = n; ca.S = S2;
-    ca.tdist = W(h, "tdist" + LL); ca.density = W(h, "density" + LL); ca.means = W(h, "means" + LL);
-    ca.normals_pred = W(h, "normals_pred"); ca.normals_grad = nullptr;
-    ca.shade = W(h, "shade"); ca.Sf = S2; ca.weights = W(h, "weights" + LL);
+    ca.tdist = w.tdist[NL - 1].p; ca.density = w.density[NL - 1].p; ca.means = w.means[NL - 1].p;
+    ca.normals_pred = w.normals_pred.p; ca.normals_grad = nullptr;
+    ca.shade = w.shade.p; ca.Sf = S2; ca.weights = w.weights[NL - 1].p;
     ca.bg = 0.0f;
     ca.pct[0] = c.percentiles[0]; ca.pct[1] = c.percentiles[1]; ca.pct[2] = c.percentiles[2];
     ca.out = A.out;
@@ -1250,13 +1312,12 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
   const int32_t* src = nullptr;
   if (resample) {
     RcResampleArgs ra{};
-    ra.n_rays = n; ra.S = S2; ra.tdist = W(h, "tdist" + LL); ra.density = W(h, "density" + LL);
+    ra.n_rays = n; ra.S = S2; ra.tdist = w.tdist[NL - 1].p; ra.density = w.density[NL - 1].p;
     ra.directions = rays->directions; ra.gumbel = rnd->gumbel; ra.inds_in = rnd->resample_inds;
-    ra.inds_out = (int32_t*)W(h, "inds"); ra.filt_weight = W(h, "filt_weight"); ra.weights = W(h, "weights" + LL);
-    ra.acc_out = W(h, "acc_sel");
-    ra.src_out = (int32_t*)W(h, "src_idx");
+    ra.inds_out = (int32_t*)w.inds.p; ra.filt_weight = w.filt_weight.p; ra.weights = w.weights[NL - 1].p;
+    ra.acc_out = w.acc_sel.p; ra.src_out = (int32_t*)w.src_idx.p;
     rc_launch_resample(ra, st);
-    src = (const int32_t*)W(h, "src_idx");
+    src = (const int32_t*)w.src_idx.p;
   }
   const int64_t nsh = resample ? n : np2;
   bool pair_lookup = false;
@@ -1270,77 +1331,68 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, hipStream_t st) {
     if (pair_lookup) {
       RcPairTables pt{};
       for (int l = 0; l < h->grids[2].dev.num_levels; ++l) pt.t[l] = h->fused_tmpl.pair_table[l];
-      rc_launch_hashgrid_pair(h->grids[2].dev, pt, W(h, "means" + LL), src, np2, n, W(h, "feat_sel"), W(h, "app"), n, c.contract_radius, st);
+      rc_launch_hashgrid_pair(h->grids[2].dev, pt, w.means[NL - 1].p, src, np2, n, w.feat_sel.p, w.app.p, n, c.contract_radius, st);
     } else {
-      rc_launch_hashgrid_src(h->grids[l2].dev, W(h, "means" + LL), 1, src, np2, n, W(h, "feat_sel"), 1, n, c.contract_radius,
-                             nullptr, st);
+      rc_launch_hashgrid_src(h->grids[l2].dev, w.means[NL - 1].p, 1, src, np2, n, w.feat_sel.p, 1, n, c.contract_radius, nullptr, st);
     }
     RcDensityMlpArgs ds{};
-    ds.feat = W(h, "feat_sel"); ds.n = n; ds.ld = n; ds.K = K2; ds.wstream = h->packs["dens_" + LL].p;
-    ds.means = W(h, "means" + LL); ds.src = src; ds.n_src = np2;
+    ds.feat = w.feat_sel.p; ds.n = n; ds.ld = n; ds.K = K2; ds.wstream = h->packs.dens[NL - 1].p;
+    ds.means = w.means[NL - 1].p; ds.src = src; ds.n_src = np2;
     ds.density_bias = c.density_bias; ds.contract_radius = c.contract_radius; ds.bbox = h->grids[l2].cfg.bbox;
-    ds.last = 1; ds.density = W(h, "density_sel"); ds.hbuf = W(h, "hbuf_sel"); ds.normals_pred = W(h, "normals_sel");
+    ds.last = 1; ds.density = w.density_sel.p; ds.hbuf = w.hbuf_sel.p; ds.normals_pred = w.normals_sel.p;
     rc_launch_density_mlp(ds, st);
   }
   stage_mark(h, slot, ST_GRID_APP, st);
   if (!pair_lookup)
-    rc_launch_hashgrid_src(h->grids[3].dev, W(h, "means" + LL), 1, src, np2, nsh, W(h, "app"), 1, nsh,
-                           c.contract_radius, nullptr, st);
+    rc_launch_hashgrid_src(h->grids[3].dev, w.means[NL - 1].p, 1, src, np2, nsh, w.app.p, 1, nsh, c.contract_radius, nullptr, st);
   if (A.tout) {
-    enqueue_transient_tail(h, A, st);
+    enqueue_transient_tail(h, A, w, st);
     return;
   }
   stage_mark(h, slot, ST_SHADER, st);
   {
     RcShaderArgs s{};
     s.n = nsh; s.n_src = lean ? n : np2; s.src = lean ? nullptr : src; s.samples_per_ray = resample ? 1 : S2;
-    s.hbuf = W(h, lean ? "hbuf_sel" : "hbuf"); s.app = W(h, "app");
-    s.normals_pred = W(h, lean ? "normals_sel" : "normals_pred"); s.viewdirs = rays->viewdirs;
-    s.wstream = h->packs["shader"].p; s.ide_coef = h->ide_table.p;
+    s.hbuf = (lean ? w.hbuf_sel : w.hbuf).p; s.app = w.app.p;
+    s.normals_pred = (lean ? w.normals_sel : w.normals_pred).p; s.viewdirs = rays->viewdirs;
+    s.wstream = h->packs.shader.p; s.ide_coef = h->ide_table.p;
     s.roughness_bias = c.roughness_bias; s.irradiance_bias = c.irradiance_bias; s.ambient_bias = c.ambient_irradiance_bias;
     s.rgb_max = c.rgb_max; s.slf_ambient_bias = c.slf_ambient_bias;
-    s.shade = W(h, "shade");
-    s.debug = W(h, "debug");
+    s.shade = w.shade.p; s.debug = w.debug.p;
     rc_launch_shader(s, st);
   }
   stage_mark(h, slot, ST_COMPOSITE, st);
   {
     RcCompositeArgs ca{};
     ca.directions = rays->directions; ca.origins = rays->origins; ca.lights = rays->lights; ca.n_rays = n; ca.S = S2;
-    ca.tdist = W(h, "tdist" + LL); ca.density = W(h, "density" + LL); ca.means = W(h, "means" + LL);
-    ca.normals_pred = lean ? nullptr : W(h, "normals_pred");
-    ca.normals_grad = A.out.ptr[RC_OUT_NORMALS] ? W(h, "normals_grad") : nullptr;
-    ca.shade = W(h, "shade"); ca.Sf = resample ? 1 : S2;
-    ca.inds = resample ? (const int32_t*)W(h, "inds") : nullptr;
-    ca.filt_weight = resample ? W(h, "filt_weight") : nullptr;
-    ca.weights = W(h, "weights" + LL);
+    ca.tdist = w.tdist[NL - 1].p; ca.density = w.density[NL - 1].p; ca.means = w.means[NL - 1].p;
+    ca.normals_pred = lean ? nullptr : w.normals_pred.p;
+    ca.normals_grad = A.out.ptr[RC_OUT_NORMALS] ? w.normals_grad.p : nullptr;
+    ca.shade = w.shade.p; ca.Sf = resample ? 1 : S2;
+    ca.inds = resample ? (const int32_t*)w.inds.p : nullptr; ca.filt_weight = resample ? w.filt_weight.p : nullptr;
+    ca.weights = w.weights[NL - 1].p;
     ca.bg = secondary ? 0.0f : c.bg_intensity;
     ca.pct[0] = c.percentiles[0]; ca.pct[1] = c.percentiles[1]; ca.pct[2] = c.percentiles[2];
     ca.out = A.out;
-    if (secondary) {
-      ca.out.ptr[RC_OUT_RGB] = W(h, "rgb_noenv");
-      ca.out.ptr[RC_OUT_ACC] = W(h, "acc_ws");
-    }
+    if (secondary) { ca.out.ptr[RC_OUT_RGB] = w.rgb_noenv.p; ca.out.ptr[RC_OUT_ACC] = w.acc_ws.p; }
     // one resampled sample per ray and nothing but rgb / acc wanted (the batched secondary trace): the weights and their
     // sum are k_resample's, one thread per ray finishes (17 -> 3 us for 32 768 rays; same bits)
     bool pick_only = resample;
     for (int id = 0; id < RC_OUT_COUNT && pick_only; ++id)
       if (ca.out.ptr[id] && id != RC_OUT_RGB && id != RC_OUT_ACC) pick_only = false;
-    if (pick_only) rc_launch_composite_pick(n, W(h, "shade"), W(h, "filt_weight"), W(h, "acc_sel"), ca.bg, ca.out.ptr[RC_OUT_RGB], ca.out.ptr[RC_OUT_ACC], st);
+    if (pick_only) rc_launch_composite_pick(n, w.shade.p, w.filt_weight.p, w.acc_sel.p, ca.bg, ca.out.ptr[RC_OUT_RGB], ca.out.ptr[RC_OUT_ACC], st);
     else rc_launch_composite(ca, st);
   }
   if (secondary) {
     const bool use_env = !(A.mask & RC_PASS_NO_ENVMAP);
     if (use_env) {
       RcEnvMapArgs ea{};
-      ea.n = n; ea.viewdirs = rays->viewdirs; ea.wstream = h->packs["envmap"].p;
-      ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = W(h, "env_rgb");
+      ea.n = n; ea.viewdirs = rays->viewdirs; ea.wstream = h->packs.envmap.p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = w.env_rgb.p;
       rc_launch_envmap(ea, st);
     }
     hipLaunchKernelGGL(k_env_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
-                       (const float*)W(h, "rgb_noenv"), (const float*)W(h, "acc_ws"),
-                       use_env ? (const float*)W(h, "env_rgb") : (const float*)nullptr, A.out.ptr[RC_OUT_RGB],
-                       A.out.ptr[RC_OUT_ACC], A.out.ptr[RC_OUT_ENV_MAP_RGB], A.out.ptr[RC_OUT_RGB_NO_ENV]);
+                       (const float*)w.rgb_noenv.p, (const float*)w.acc_ws.p, use_env ? (const float*)w.env_rgb.p : (const float*)nullptr,
+                       A.out.ptr[RC_OUT_RGB], A.out.ptr[RC_OUT_ACC], A.out.ptr[RC_OUT_ENV_MAP_RGB], A.out.ptr[RC_OUT_RGB_NO_ENV]);
   }
   stage_mark(h, slot, ST_COUNT, st);
 }
@@ -1377,19 +1429,12 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
   // one workspace set per caller stream (up to 4): calls on different streams do not share buffers.  The fused kernel
   // keeps every intermediate on chip: no workspace, no set.
   const int ws_slot = fused ? 0 : ws_pick(h, st);
-  struct PrefixGuard {
-    rc_handle* h;
-    ~PrefixGuard() { h->ws_prefix = ""; }
-  } guard{h};
-  h->ws_prefix = ws_slot == 0 ? "" : "p" + std::to_string(ws_slot) + ":";
+  RenderWs& w = h->ws[ws_slot];
   if (!fused) {
     if ((rc = ws_enter(h, ws_slot, st))) return rc;
-    if ((rc = ensure_workspace(h, n))) return rc;      // a reallocation drops the captured graphs (ws_alloc)
+    if ((rc = ensure_workspace(h, w, n))) return rc;      // a reallocation drops the captured graphs (ws_alloc)
   }
-  struct LeaveGuard {                                  // every exit below records the set's "done" event
-    rc_handle* h; int slot; hipStream_t st; bool on;
-    ~LeaveGuard() { if (on) (void)ws_leave(h, slot, st); }
-  } leave{h, ws_slot, st, !fused};
+  WsLeave leave{h, ws_slot, st, !fused};
   rc_shader_prepare();
 
   RenderArgs A{};
@@ -1411,7 +1456,7 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
   // event records are not replayable graph nodes: profile eagerly.  The fused plan is ONE launch: a plain launch
   // queues back to back with the previous one (gap < 1 us), the replay of a one-node graph leaves ~5 us between them.
   if (h->graph_mode == 0 || h->profiling || fused) {
-    enqueue_all(h, A, st);
+    enqueue_all(h, A, w, st);
     RC_HIP(h, hipGetLastError());
     return RC_OK;
   }
@@ -1434,7 +1479,7 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
   h->last_key = key;
   h->have_last_key = true;
   if (!capture) {
-    enqueue_all(h, A, st);
+    enqueue_all(h, A, w, st);
     RC_HIP(h, hipGetLastError());
     return RC_OK;
   }
@@ -1444,13 +1489,13 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
   GraphEntry e;
   e.key = key;
   RC_HIP(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-  enqueue_all(h, A, h->cap_stream);
+  enqueue_all(h, A, w, h->cap_stream);
   hipError_t ce = hipStreamEndCapture(h->cap_stream, &e.graph);
   if (ce != hipSuccess || !e.graph) {
     // capture unsupported for this sequence: fall back to eager launches for good
     (void)hipGetLastError();
     h->graph_mode = 0;
-    enqueue_all(h, A, st);
+    enqueue_all(h, A, w, st);
     RC_HIP(h, hipGetLastError());
     return RC_OK;
   }
@@ -1573,28 +1618,20 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   const int NL = c.num_levels;
   const int S2 = c.num_samples[NL - 1];
   const int64_t np2 = n * S2, nsec = n * (Ks + Kd);
-  h->ws_prefix = "";
-  if ((rc = ws_enter(h, 0, st))) return rc;             // shares workspace set 0 (and "s:") with the other entry points
-  struct LeaveGuard {
-    rc_handle* h; hipStream_t st;
-    ~LeaveGuard() { (void)ws_leave(h, 0, st); }
-  } leave{h, st};
-  if ((rc = ensure_workspace(h, n))) return rc;
-  if ((rc = ws_alloc(h, "m_pts", 3 * n)) || (rc = ws_alloc(h, "m_nrm", 3 * n)) || (rc = ws_alloc(h, "m_feat", 32 * n)) ||
-      (rc = ws_alloc(h, "m_mat", RC_MAT_CH * n)) || (rc = ws_alloc(h, "m_feat_all", 32 * np2)) ||
-      (rc = ws_alloc(h, "m_mat_all", RC_MAT_CH * np2)) || (rc = ws_alloc(h, "l_feat", 32 * n)) ||
-      (rc = ws_alloc(h, "l_vmf", (int64_t)128 * RC_VMF_CH * n)) || (rc = ws_alloc(h, "l_vmf_logit", (int64_t)128 * n)) || (rc = ws_alloc(h, "sec_origins", 3 * nsec)) ||
-      (rc = ws_alloc(h, "sec_dirs", 3 * nsec)) || (rc = ws_alloc(h, "sec_near", nsec)) || (rc = ws_alloc(h, "sec_far", nsec)) ||
-      (rc = ws_alloc(h, "sec_lights", 3 * nsec)) || (rc = ws_alloc(h, "sec_samples", RC_SMP_CH * nsec)) ||
-      (rc = ws_alloc(h, "m_local_view", 3 * n)) || (rc = ws_alloc(h, "sec_rgb", 3 * nsec)) ||
-      (rc = ws_alloc(h, "sec_acc", nsec)) || (rc = ws_alloc(h, "sec_env", 3 * nsec)))
+  RenderWs& w = h->ws[0];
+  ExtraWs& x = h->ws_x;
+  if ((rc = ws_enter(h, 0, st))) return rc;             // shares workspace set 0 (and the secondary set) with the other entry points
+  WsLeave leave{h, 0, st, true};
+  if ((rc = ensure_workspace(h, w, n))) return rc;
+  if ((rc = ws_alloc(h, x.m_pts, 3 * n)) || (rc = ws_alloc(h, x.m_nrm, 3 * n)) || (rc = ws_alloc(h, x.m_feat, 32 * n)) ||
+      (rc = ws_alloc(h, x.m_mat, RC_MAT_CH * n)) || (rc = ws_alloc(h, x.m_feat_all, 32 * np2)) || (rc = ws_alloc(h, x.m_mat_all, RC_MAT_CH * np2)) ||
+      (rc = ws_alloc(h, x.l_feat, 32 * n)) || (rc = ws_alloc(h, x.l_vmf, (int64_t)128 * RC_VMF_CH * n)) ||
+      (rc = ws_alloc(h, x.l_vmf_logit, (int64_t)128 * n)) || (rc = ws_alloc(h, x.sec_origins, 3 * nsec)) || (rc = ws_alloc(h, x.sec_dirs, 3 * nsec)) ||
+      (rc = ws_alloc(h, x.sec_near, nsec)) || (rc = ws_alloc(h, x.sec_far, nsec)) || (rc = ws_alloc(h, x.sec_lights, 3 * nsec)) ||
+      (rc = ws_alloc(h, x.sec_samples, RC_SMP_CH * nsec)) || (rc = ws_alloc(h, x.m_local_view, 3 * n)) || (rc = ws_alloc(h, x.sec_rgb, 3 * nsec)) ||
+      (rc = ws_alloc(h, x.sec_acc, nsec)) || (rc = ws_alloc(h, x.sec_env, 3 * nsec)) || (rc = ensure_workspace(h, h->ws_sec, nsec)))
     return rc;
-  h->ws_prefix = "s:";
-  rc = ensure_workspace(h, nsec);
-  h->ws_prefix = "";
-  if (rc) return rc;
   rc_shader_prepare();
-  const std::string LL = std::to_string(NL - 1);
 
   // 1. cache pass on the primary rays (all samples shaded) -> cache_out
   RenderArgs A{};
@@ -1604,20 +1641,19 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   // steps 2-3 below; bitwise the launch-per-stage pass (tests/test_gpu_parity.py)
   A.fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && !h->profiling && c.num_samples[NL - 1] == 32;
   A.export_samples = A.fused;
-  enqueue_all(h, A, st);
+  enqueue_all(h, A, w, st);
 
   // 2. one shading sample per ray (MaterialModel.resample_render, models.py:1430-1439)
   {
     RcResampleArgs ra{};
-    ra.n_rays = n; ra.S = S2; ra.tdist = W(h, "tdist" + LL); ra.density = W(h, "density" + LL);
+    ra.n_rays = n; ra.S = S2; ra.tdist = w.tdist[NL - 1].p; ra.density = w.density[NL - 1].p;
     ra.directions = rays->directions; ra.gumbel = mr->gumbel; ra.inds_in = mr->resample_inds;
-    ra.inds_out = (int32_t*)W(h, "inds"); ra.filt_weight = W(h, "filt_weight"); ra.weights = W(h, "weights" + LL);
-    ra.src_out = (int32_t*)W(h, "src_idx");
+    ra.inds_out = (int32_t*)w.inds.p; ra.filt_weight = w.filt_weight.p; ra.weights = w.weights[NL - 1].p; ra.src_out = (int32_t*)w.src_idx.p;
     // position and predicted normal of the picked sample = the shading point
-    ra.means = W(h, "means" + LL); ra.normals = W(h, "normals_pred"); ra.pts_out = W(h, "m_pts"); ra.nrm_out = W(h, "m_nrm");
+    ra.means = w.means[NL - 1].p; ra.normals = w.normals_pred.p; ra.pts_out = x.m_pts.p; ra.nrm_out = x.m_nrm.p;
     rc_launch_resample(ra, st);
   }
-  auto raw = [&](const char* path, const char* leaf) { return h->packs[std::string("raw:") + path + "/" + leaf].p; };
+  const auto& raw = h->packs.raw;
   // Side stream: the material-only composite over all samples (step 3b) and the EnvMap along the secondary rays (step 6b)
   // feed only the outputs / the final integration, so they leave the critical path sampler -> trace -> integrate and
   // fill the gaps of its latency-bound kernels.  Forked from and joined to the caller's stream with events: to the
@@ -1625,7 +1661,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   { int rcs = ensure_side_stream(h); if (rcs) return rcs; }
   hipStream_t side = h->side_stream;
   // Whatever way this function is left once work has been forked onto the side stream, the caller's stream is joined
-  // to it again BEFORE the workspace set is released (declared after LeaveGuard: destroyed first): an early error
+  // to it again BEFORE the workspace set is released (declared after `leave`: destroyed first): an early error
   // return must not leave side-stream kernels writing mat_out / sec_env behind a caller that believes `st` orders
   // everything of the call.
   struct SideJoin {
@@ -1641,19 +1677,19 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   roctx_stage("material: heads + light sampler");
   {
     RcMatHeadArgs ma{};
-    ma.w0 = raw("params/MaterialShader/bottleneck_layer", "kernel"); ma.b0 = raw("params/MaterialShader/bottleneck_layer", "bias");
-    ma.w1 = raw("params/MaterialShader/pred_brdf_layer", "kernel"); ma.b1 = raw("params/MaterialShader/pred_brdf_layer", "bias");
+    ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
+    ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
     ma.min_roughness = c.min_roughness;
     RcLightHeadArgs la{};
-    la.n = n; la.feat = W(h, "l_feat");
-    la.w0 = raw("params/LightSampler/layers_0", "kernel"); la.b0 = raw("params/LightSampler/layers_0", "bias");
-    la.w1 = raw("params/LightSampler/layers_1", "kernel"); la.b1 = raw("params/LightSampler/layers_1", "bias");
-    la.w2 = raw("params/LightSampler/output_layer", "kernel"); la.b2 = raw("params/LightSampler/output_layer", "bias");
-    la.pts = W(h, "m_pts"); la.noise = mr->vmf_noise; la.vmf_scale = c.vmf_scale; la.vmf = W(h, "l_vmf"); la.vmf_logit = W(h, "l_vmf_logit");
+    la.n = n; la.feat = x.l_feat.p;
+    la.w0 = raw[RAW_LIGHT_0].kernel.p; la.b0 = raw[RAW_LIGHT_0].bias.p;
+    la.w1 = raw[RAW_LIGHT_1].kernel.p; la.b1 = raw[RAW_LIGHT_1].bias.p;
+    la.w2 = raw[RAW_LIGHT_OUT].kernel.p; la.b2 = raw[RAW_LIGHT_OUT].bias.p;
+    la.pts = x.m_pts.p; la.noise = mr->vmf_noise; la.vmf_scale = c.vmf_scale; la.vmf = x.l_vmf.p; la.vmf_logit = x.l_vmf_logit.p;
     // caller's stream, the critical path: both grids at the shading points in one launch, both heads in one launch (as
     // four launches on two streams the BRDF sampler waited ~12 us for the event behind the light head)
-    rc_launch_hashgrid_two(h->grids[4].dev, h->grids[5].dev, W(h, "m_pts"), n, W(h, "m_feat"), W(h, "l_feat"), c.contract_radius, st);
-    ma.n = n; ma.feat = W(h, "m_feat"); ma.mat = W(h, "m_mat");
+    rc_launch_hashgrid_two(h->grids[4].dev, h->grids[5].dev, x.m_pts.p, n, x.m_feat.p, x.l_feat.p, c.contract_radius, st);
+    ma.n = n; ma.feat = x.m_feat.p; ma.mat = x.m_mat.p;
     rc_launch_shading_heads(ma, la, st);
   }
   // 5. BRDF importance sampling -> secondary rays
@@ -1661,14 +1697,13 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   {
     RcBrdfSampleArgs sa{};
     sa.n = n; sa.Ks = Ks; sa.Kd = Kd; sa.Kc = Kc;
-    sa.pts = W(h, "m_pts"); sa.nrm = W(h, "m_nrm"); sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
-    sa.mat = W(h, "m_mat"); sa.vmf = W(h, "l_vmf"); sa.vmf_logit = W(h, "l_vmf_logit");
+    sa.pts = x.m_pts.p; sa.nrm = x.m_nrm.p; sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
+    sa.mat = x.m_mat.p; sa.vmf = x.l_vmf.p; sa.vmf_logit = x.l_vmf_logit.p;
     sa.spec_u1 = mr->spec_u1; sa.spec_u2 = mr->spec_u2; sa.cos_u1 = mr->cos_u1; sa.cos_u2 = mr->cos_u2;
     sa.vmf_lobe = mr->vmf_lobe; sa.vmf_v = mr->vmf_v; sa.vmf_tmp = mr->vmf_tmp; sa.vmf_lobe_gumbel = mr->vmf_lobe_gumbel;
     sa.normal_eps = c.secondary_normal_eps; sa.near = c.secondary_near; sa.far = c.secondary_far;
-    sa.sec_origins = W(h, "sec_origins"); sa.sec_dirs = W(h, "sec_dirs"); sa.sec_near = W(h, "sec_near");
-    sa.sec_far = W(h, "sec_far"); sa.sec_lights = W(h, "sec_lights"); sa.samples = W(h, "sec_samples");
-    sa.local_view = W(h, "m_local_view");
+    sa.sec_origins = x.sec_origins.p; sa.sec_dirs = x.sec_dirs.p; sa.sec_near = x.sec_near.p; sa.sec_far = x.sec_far.p;
+    sa.sec_lights = x.sec_lights.p; sa.samples = x.sec_samples.p; sa.local_view = x.m_local_view.p;
     rc_launch_brdf_sample(sa, st);
   }
   // 3b. side stream: the material head on ALL samples and the material-only composite (outputs only).  Forked HERE, behind
@@ -1680,13 +1715,13 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
     RC_HIP(h, hipStreamWaitEvent(side, h->ev_side[0], 0));
     side_join.forked = true;
     RcMatHeadArgs ma{};
-    ma.w0 = raw("params/MaterialShader/bottleneck_layer", "kernel"); ma.b0 = raw("params/MaterialShader/bottleneck_layer", "bias");
-    ma.w1 = raw("params/MaterialShader/pred_brdf_layer", "kernel"); ma.b1 = raw("params/MaterialShader/pred_brdf_layer", "bias");
+    ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
+    ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
     ma.min_roughness = c.min_roughness;
-    rc_launch_hashgrid(h->grids[4].dev, W(h, "means" + LL), 1, np2, W(h, "m_feat_all"), 0, 32, c.contract_radius, nullptr, side);
-    ma.n = np2; ma.feat = W(h, "m_feat_all"); ma.mat = W(h, "m_mat_all");
+    rc_launch_hashgrid(h->grids[4].dev, w.means[NL - 1].p, 1, np2, x.m_feat_all.p, 0, 32, c.contract_radius, nullptr, side);
+    ma.n = np2; ma.feat = x.m_feat_all.p; ma.mat = x.m_mat_all.p;
     rc_launch_material_head(ma, side);
-    rc_launch_material_composite_all(n, S2, W(h, "weights" + LL), W(h, "m_mat_all"), mat_out->ptr[RC_MOUT_MATERIAL_ALBEDO],
+    rc_launch_material_composite_all(n, S2, w.weights[NL - 1].p, x.m_mat_all.p, mat_out->ptr[RC_MOUT_MATERIAL_ALBEDO],
                                      mat_out->ptr[RC_MOUT_MATERIAL_ROUGHNESS], mat_out->ptr[RC_MOUT_MATERIAL_METALNESS],
                                      mat_out->ptr[RC_MOUT_MATERIAL_F_0], c.default_F_0, side);
   }
@@ -1694,8 +1729,8 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   //    ref_rays.normals = None since MaterialMLP.shadow_eps_indirect = False) + EnvMap along the same rays
   {
     RenderArgs B{};
-    B.rays.origins = W(h, "sec_origins"); B.rays.directions = W(h, "sec_dirs"); B.rays.viewdirs = W(h, "sec_dirs");
-    B.rays.near = W(h, "sec_near"); B.rays.far = W(h, "sec_far"); B.rays.lights = W(h, "sec_lights"); B.rays.normals = nullptr;
+    B.rays.origins = x.sec_origins.p; B.rays.directions = x.sec_dirs.p; B.rays.viewdirs = x.sec_dirs.p;
+    B.rays.near = x.sec_near.p; B.rays.far = x.sec_far.p; B.rays.lights = x.sec_lights.p; B.rays.normals = nullptr;
     B.have_rnd = true;
     for (int l = 0; l < RC_MAX_LEVELS; ++l) B.rnd.jitter[l] = mr->sec_jitter[l];
     B.rnd.gumbel = mr->sec_gumbel; B.rnd.resample_inds = mr->sec_resample_inds;
@@ -1711,10 +1746,9 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
     }
     B.s_bounds = h->sec_sbounds;
     memset(&B.out, 0, sizeof(B.out));
-    B.out.ptr[RC_OUT_RGB] = W(h, "sec_rgb"); B.out.ptr[RC_OUT_ACC] = W(h, "sec_acc");
-    float* sec_dirs = W(h, "sec_dirs"); float* sec_env = W(h, "sec_env");
+    B.out.ptr[RC_OUT_RGB] = x.sec_rgb.p; B.out.ptr[RC_OUT_ACC] = x.sec_acc.p;
     RcEnvMapArgs ea{};
-    ea.n = nsec; ea.viewdirs = sec_dirs; ea.wstream = h->packs["envmap"].p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = sec_env;
+    ea.n = nsec; ea.viewdirs = x.sec_dirs.p; ea.wstream = h->packs.envmap.p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = x.sec_env.p;
     // 6b. EnvMap of the secondary directions, on the side stream.  It is MFMA-bound and keeps a CU's LDS to itself, as the
     // level kernels of the trace do: next to a level kernel it only gets the CUs that kernel's persistent workgroups
     // leave.  Beside the first two levels (F = 1: bound by their own instruction issue) every CU it takes is a CU they
@@ -1736,9 +1770,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
       RC_HIP(h, hipEventRecord(h->ev_side[2], side));
       env_released = true;
     }
-    h->ws_prefix = "s:";
-    enqueue_all(h, B, st);
-    h->ws_prefix = "";
+    enqueue_all(h, B, h->ws_sec, st);
     if (!env_released) {
       // the trace took a launch plan without that spot (per-stage profiling on, a grid layout the level kernels do not
       // cover): the EnvMap behind the trace
@@ -1755,10 +1787,9 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   {
     RcMatIntegrateArgs ia{};
     ia.n = n; ia.Ks = Ks; ia.Kd = Kd; ia.S = S2;
-    ia.mat = W(h, "m_mat"); ia.samples = W(h, "sec_samples"); ia.local_view = W(h, "m_local_view");
-    ia.sec_rgb = W(h, "sec_rgb"); ia.sec_acc = W(h, "sec_acc"); ia.sec_env = W(h, "sec_env");
-    ia.weights = W(h, "weights" + LL); ia.filt_weight = W(h, "filt_weight");
-    ia.pts = W(h, "m_pts"); ia.nrm = W(h, "m_nrm"); ia.origins = rays->origins; ia.lights = rays->lights;
+    ia.mat = x.m_mat.p; ia.samples = x.sec_samples.p; ia.local_view = x.m_local_view.p; ia.sec_rgb = x.sec_rgb.p;
+    ia.sec_acc = x.sec_acc.p; ia.sec_env = x.sec_env.p; ia.weights = w.weights[NL - 1].p; ia.filt_weight = w.filt_weight.p;
+    ia.pts = x.m_pts.p; ia.nrm = x.m_nrm.p; ia.origins = rays->origins; ia.lights = rays->lights;
     ia.f0 = c.default_F_0; ia.rgb_max = c.rgb_max; ia.bg = c.bg_intensity;
     ia.out = *mat_out;
     rc_launch_material_integrate(ia, st);

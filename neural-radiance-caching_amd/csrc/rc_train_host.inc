@@ -66,7 +66,7 @@ int pack_train_stream(rc_handle* h, int level) {
   std::vector<Step> sb; steps_acc(sb, 2, 0);
   append(stream, pack_f32(sb, {tile_full(&w1t, 0, 0, false), tile_full(&w1t, 1, 0, false)}));
   append(stream, pack_f32(sb, {tile_full(&w0t, 0, 0, false)}));
-  return upload(h, "train_" + std::to_string(level), pad_stream(stream));
+  return upload(h, h->packs.train[level], pad_stream(stream));
 }
 
 }  // namespace
@@ -121,25 +121,15 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
     h->train_gen[level] = h->layers_gen;
   }
   const int64_t ld = (n + 63) / 64 * 64;
-  const std::string saved = h->ws_prefix;
-  if ((rc = ws_enter(h, 4, st))) return rc;             // the "t:" workspace set: ordered against its previous user
-  struct LeaveGuard {
-    rc_handle* h; hipStream_t st;
-    ~LeaveGuard() { (void)ws_leave(h, 4, st); }
-  } leave{h, st};
-  h->ws_prefix = "t:";
+  if ((rc = ws_enter(h, 4, st))) return rc;             // the train workspace set: ordered against its previous user
+  WsLeave leave{h, 4, st, true};
+  TrainWs& t = h->ws_train;
   const int nwaves = rc_wgrad_waves(n);
-  rc = ws_alloc(h, "feat", (int64_t)K * ld);
-  if (!rc) rc = ws_alloc(h, "dfeat", (int64_t)K * ld);
-  if (!rc) rc = ws_alloc(h, "a1", n * 64);
-  if (!rc) rc = ws_alloc(h, "a2", n * 64);
-  if (!rc) rc = ws_alloc(h, "d2", n * 64);
-  if (!rc) rc = ws_alloc(h, "d1", n * 64);
-  if (!rc) rc = ws_alloc(h, "fe", n * 32);
-  if (!rc) rc = ws_alloc(h, "graw", n);
-  if (!rc) rc = ws_alloc(h, "density", n);
-  if (!rc) rc = ws_alloc(h, "partial", rc_wgrad_partial_floats(nwaves));
-  if (rc) { h->ws_prefix = saved; return rc; }
+  if ((rc = ws_alloc(h, t.feat, (int64_t)K * ld)) || (rc = ws_alloc(h, t.dfeat, (int64_t)K * ld)) || (rc = ws_alloc(h, t.a1, n * 64)) ||
+      (rc = ws_alloc(h, t.a2, n * 64)) || (rc = ws_alloc(h, t.d2, n * 64)) || (rc = ws_alloc(h, t.d1, n * 64)) ||
+      (rc = ws_alloc(h, t.fe, n * 32)) || (rc = ws_alloc(h, t.graw, n)) || (rc = ws_alloc(h, t.density, n)) ||
+      (rc = ws_alloc(h, t.partial, rc_wgrad_partial_floats(nwaves))))
+    return rc;
 
   if (!h->train_stream[0]) {
     bool ok = true;
@@ -151,10 +141,7 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
     }
   }
   (void)rc_train_prepare();
-  float* const feat = W(h, "feat"); float* const dfeat = W(h, "dfeat"); float* const a1 = W(h, "a1"); float* const a2 = W(h, "a2");
-  float* const d2 = W(h, "d2"); float* const d1 = W(h, "d1"); float* const fe = W(h, "fe"); float* const graw = W(h, "graw");
-  float* const dens = density_out ? density_out : W(h, "density"); float* const partial = W(h, "partial");
-  const float* const wstream = h->packs["train_" + std::to_string(level)].p;
+  const float* const wstream = h->packs.train[level].p;
   const std::vector<GradSeg> segs = density_grad_segments(h, level);
 
   // The whole call as launches on `q` (the caller's stream, or the capture stream of the graph below).
@@ -164,17 +151,17 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
   // otherwise hold every CU until they have drained), the LDS-accumulated levels of an F = 4 grid on a second one; both
   // forked from and joined to `q` with events, so to the caller everything of the call is ordered on its stream.
   auto enqueue = [&](hipStream_t q) {
-    rc_launch_hashgrid(gs.dev, points, 0, n, feat, 1, ld, h->cfg.contract_radius, nullptr, q);
+    rc_launch_hashgrid(gs.dev, points, 0, n, t.feat.p, 1, ld, h->cfg.contract_radius, nullptr, q);
     RcDensityBwdArgs b{};
-    b.feat = feat; b.n = n; b.ld = ld; b.K = K; b.wstream = wstream;
+    b.feat = t.feat.p; b.n = n; b.ld = ld; b.K = K; b.wstream = wstream;
     b.points = points; b.density_bias = h->cfg.density_bias; b.contract_radius = h->cfg.contract_radius; b.bbox = gs.cfg.bbox;
     b.d_density = d_density; b.d_feature = d_feature;
-    b.density = dens; b.graw = graw;
-    b.a1 = a1; b.a2 = a2; b.d2 = d2; b.d1 = d1; b.fe = fe; b.dfeat = dfeat;
+    b.density = density_out ? density_out : t.density.p; b.graw = t.graw.p;
+    b.a1 = t.a1.p; b.a2 = t.a2.p; b.d2 = t.d2.p; b.d1 = t.d1.p; b.fe = t.fe.p; b.dfeat = t.dfeat.p;
     rc_launch_density_bwd(b, q);
 
     RcWgradArgs w{};
-    w.a1 = a1; w.d2 = d2; w.fe = fe; w.d1 = d1; w.a2 = a2; w.graw = graw; w.n = n; w.partial = partial;
+    w.a1 = t.a1.p; w.d2 = t.d2.p; w.fe = t.fe.p; w.d1 = t.d1.p; w.a2 = t.a2.p; w.graw = t.graw.p; w.n = n; w.partial = t.partial.p;
     // F = 1 grids: k_wgrad beside k_grid_scatter_sliced (-25 us per call).  F = 4 grids: no fork -- beside k_grid_scatter<4>
     // the weight gradients stretch to the scatter's own length (0.194 ms per call on one stream, 0.198 forked), and a call
     // that forks TWO helper streams was measured at 0.37 ms in a process that had run the material stage before it
@@ -189,7 +176,7 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
     RcGridScatterArgs sa{};
     sa.grid = gs.dev;
     for (size_t l = 0; l < gs.sizes.size(); ++l) sa.gtable[l] = grads + segs[l].offset;
-    sa.points = points; sa.n = n; sa.ld = ld; sa.dfeat = dfeat; sa.contract_radius = h->cfg.contract_radius;
+    sa.points = points; sa.n = n; sa.ld = ld; sa.dfeat = t.dfeat.p; sa.contract_radius = h->cfg.contract_radius;
     rc_launch_grid_scatter(sa, q, h->train_stream[1], forked && nfork == 2);
     if (forked) {       // join (before the workspace set is released)
       for (int i = 0; i < nfork; ++i)
@@ -201,7 +188,6 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
   // (Replaying the call as one hipGraph -- fork and join captured -- was tried against its ~140 us of host time per call:
   // 0.28-0.40 ms per call instead of 0.16-0.20, a three-branch graph launches slower than its six plain launches.)
   enqueue(st);
-  h->ws_prefix = saved;
   RC_HIP(h, hipGetLastError());
   return RC_OK;
   RC_CATCH(h)

@@ -94,7 +94,7 @@ int repack_transient(rc_handle* h) {
                              tile_full(lb, 3, 0, false)}));
     if ((int)(stream.size() / 64) != rc_transient_shader_frags())
       return fail(h, RC_ERR_INVALID_ARG, "internal: transient shader stream length mismatch");
-    int rc = upload(h, "t_shader", pad_stream(stream));
+    int rc = upload(h, h->packs.t_shader, pad_stream(stream));
     if (rc) return rc;
   }
   {
@@ -126,7 +126,7 @@ int repack_transient(rc_handle* h) {
     }
     if ((int)(stream.size() / 64) != rc_transient_bins_frags())
       return fail(h, RC_ERR_INVALID_ARG, "internal: transient bins stream length mismatch");
-    int rc = upload(h, "t_bins", pad_stream(stream));
+    int rc = upload(h, h->packs.t_bins, pad_stream(stream));
     if (rc) return rc;
   }
   {
@@ -146,16 +146,9 @@ int repack_transient(rc_handle* h) {
     }
     h->n_taps = (int)taps.size();
     if (h->n_taps) {
-      int rc = upload(h, "t_taps", taps);
+      int rc = upload(h, h->packs.t_taps, taps);
       if (rc) return rc;
     }
-  }
-  if (!h->ide_table.p) {
-    RcIdeTable tb;
-    build_ide_table(tb);
-    RC_HIP(h, hipMalloc((void**)&h->ide_table.p, sizeof(tb)));
-    h->ide_table.bytes = sizeof(tb);
-    RC_HIP(h, hipMemcpy(h->ide_table.p, &tb, sizeof(tb), hipMemcpyHostToDevice));
   }
   h->fused_ok = false;
   h->packed_dirty = false;
@@ -163,11 +156,11 @@ int repack_transient(rc_handle* h) {
 }
 
 // After the proposal sampler and the appearance-grid lookup: shader, per-bin heads + compositing, scalar composites.
-void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, hipStream_t st) {
+// `w` is workspace set 0 (the shadow rays use its extras and the secondary set).
+void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st) {
   const rc_config& c = h->cfg;
   const rc_transient_config& t = h->tcfg;
   const int NL = c.num_levels;
-  const std::string LL = std::to_string(NL - 1);
   const int S2 = c.num_samples[NL - 1];
   const int64_t n = A.n, np2 = n * S2;
   const rc_transient_outputs& o = *A.tout;
@@ -177,11 +170,9 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, hipStream_t st) {
     // this kernel also leaves the alpha-compositing weights of the last level in the workspace for the bins kernel
     RcCompositeArgs ca{};
     ca.directions = A.rays.directions; ca.origins = A.rays.origins; ca.lights = A.rays.lights; ca.n_rays = n; ca.S = S2;
-    ca.tdist = W(h, "tdist" + LL); ca.density = W(h, "density" + LL); ca.means = W(h, "means" + LL);
-    ca.normals_pred = W(h, "normals_pred");
-    ca.normals_grad = A.out.ptr[RC_OUT_NORMALS] ? W(h, "normals_grad") : nullptr;
-    ca.shade = W(h, "shade"); ca.Sf = S2; ca.inds = nullptr; ca.filt_weight = nullptr;
-    ca.weights = W(h, "weights" + LL);
+    ca.tdist = w.tdist[NL - 1].p; ca.density = w.density[NL - 1].p; ca.means = w.means[NL - 1].p; ca.normals_pred = w.normals_pred.p;
+    ca.normals_grad = A.out.ptr[RC_OUT_NORMALS] ? w.normals_grad.p : nullptr;
+    ca.shade = w.shade.p; ca.Sf = S2; ca.inds = nullptr; ca.filt_weight = nullptr; ca.weights = w.weights[NL - 1].p;
     ca.bg = 0.0f;
     ca.pct[0] = c.percentiles[0]; ca.pct[1] = c.percentiles[1]; ca.pct[2] = c.percentiles[2];
     ca.out = A.out;
@@ -191,12 +182,12 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, hipStream_t st) {
   if (t.use_occlusions) {
     // _compute_occlusions: n * S2 shadow rays through the secondary-ray sampler, weights only
     const int64_t nsec = np2;
+    const ExtraWs& x = h->ws_x;
     RcShadowRayArgs sr{};
-    sr.n = np2; sr.samples_per_ray = S2; sr.means = W(h, "means" + LL); sr.normals = W(h, "normals_grad");
-    sr.lights = A.rays.lights;
+    sr.n = np2; sr.samples_per_ray = S2; sr.means = w.means[NL - 1].p; sr.normals = w.normals_grad.p; sr.lights = A.rays.lights;
     sr.normal_eps = c.secondary_normal_eps; sr.shadow_near = t.shadow_near; sr.shadow_far = t.shadow_far; sr.light_near = t.light_near;
-    sr.origins = W(h, "sh_origins"); sr.dirs = W(h, "sh_dirs"); sr.near = W(h, "sh_near"); sr.far = W(h, "sh_far");
-    sr.out_normals = W(h, "sh_normals"); sr.out_lights = W(h, "sh_lights");
+    sr.origins = x.sh_origins.p; sr.dirs = x.sh_dirs.p; sr.near = x.sh_near.p; sr.far = x.sh_far.p;
+    sr.out_normals = x.sh_normals.p; sr.out_lights = x.sh_lights.p;
     rc_launch_shadow_rays(sr, st);
     RenderArgs B{};
     B.rays.origins = sr.origins; B.rays.directions = sr.dirs; B.rays.viewdirs = sr.dirs; B.rays.near = sr.near; B.rays.far = sr.far;
@@ -205,38 +196,34 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, hipStream_t st) {
     if (A.shadow_rnd) B.rnd = *A.shadow_rnd;
     B.n = nsec; B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY; B.slot = -1; B.fused = false; B.weights_only = true;
     memset(&B.out, 0, sizeof(B.out));
-    float* sh_acc = W(h, "sh_acc");
-    B.out.ptr[RC_OUT_ACC] = sh_acc;
-    h->ws_prefix = "s:";
-    enqueue_all(h, B, st);
-    h->ws_prefix = "";
-    occ = sh_acc;
+    B.out.ptr[RC_OUT_ACC] = x.sh_acc.p;
+    enqueue_all(h, B, h->ws_sec, st);
+    occ = x.sh_acc.p;
   }
   stage_mark(h, A.slot, ST_SHADER, st);
   {
     RcTransShaderArgs s{};
     s.n = np2; s.samples_per_ray = S2;
-    s.hbuf = W(h, "hbuf"); s.app = W(h, "app"); s.means = W(h, "means" + LL); s.normals = W(h, "normals_pred");
+    s.hbuf = w.hbuf.p; s.app = w.app.p; s.means = w.means[NL - 1].p; s.normals = w.normals_pred.p;
     s.origins = A.rays.origins; s.viewdirs = A.rays.viewdirs; s.lights = A.rays.lights; s.cam_origins = A.cam_origins;
     s.occ = occ; s.occ_threshold = t.occ_threshold;
-    s.wstream = h->packs["t_shader"].p; s.ide_coef = h->ide_table.p;
+    s.wstream = h->packs.t_shader.p; s.ide_coef = h->ide_table.p;
     s.roughness_bias = c.roughness_bias; s.albedo_bias = t.albedo_bias; s.brdf_bias = t.brdf_bias; s.rgb_max = t.rgb_max;
     s.contract_radius = c.contract_radius;
     s.light_power = h->light_power; s.light_near = t.light_near; s.use_falloff = t.use_falloff; s.light_zero = t.light_zero;
-    s.irr_feat = W(h, "t_irr"); s.slf_feat = W(h, "t_slf"); s.tshade = W(h, "tshade");
+    s.irr_feat = w.t_irr.p; s.slf_feat = w.t_slf.p; s.tshade = w.tshade.p;
     rc_launch_transient_shader(s, st);
   }
   {
     RcTransBinsArgs b{};
-    b.n_rays = n;
-    b.wstream = h->packs["t_bins"].p;
-    b.slf_feat = W(h, "t_slf"); b.irr_feat = W(h, "t_irr"); b.tshade = W(h, "tshade"); b.weights = W(h, "weights" + LL);
+    b.n_rays = n; b.wstream = h->packs.t_bins.p;
+    b.slf_feat = w.t_slf.p; b.irr_feat = w.t_irr.p; b.tshade = w.tshade.p; b.weights = w.weights[NL - 1].p;
     b.exposure = t.exposure_time; b.shift = t.transient_shift;
     b.max_dists = (float)((double)(t.n_bins - 1) * (double)t.exposure_time);       // render_utils.py:1730
     b.irradiance_bias = t.irradiance_bias; b.slf_rgb_bias = t.slf_rgb_bias; b.indirect_scale = t.indirect_scale;
     b.rgb_max = t.rgb_max; b.light_near = t.light_near;
     b.bin_zero_threshold_light = t.bin_zero_threshold_light; b.light_zero = t.light_zero;
-    b.n_taps = h->n_taps; b.taps = h->n_taps ? h->packs["t_taps"].p : nullptr;
+    b.n_taps = h->n_taps; b.taps = h->n_taps ? h->packs.t_taps.p : nullptr;
     b.out_rgb = o.ptr[RC_TOUT_RGB]; b.out_direct = o.ptr[RC_TOUT_TRANSIENT_DIRECT_VIZ]; b.out_indirect = o.ptr[RC_TOUT_TRANSIENT_INDIRECT_VIZ];
     b.out_ti_diffuse = o.ptr[RC_TOUT_TRANSIENT_INDIRECT_DIFFUSE]; b.out_ti_specular = o.ptr[RC_TOUT_TRANSIENT_INDIRECT_SPECULAR];
     b.out_direct_rgb = o.ptr[RC_TOUT_DIRECT_RGB]; b.out_indirect_rgb = o.ptr[RC_TOUT_INDIRECT_RGB];
@@ -285,23 +272,17 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   hipStream_t st = (hipStream_t)stream_v;
   int rc;
   if (h->packed_dirty && (rc = repack(h))) return rc;
-  h->ws_prefix = "";
-  if ((rc = ws_enter(h, 0, st))) return rc;             // workspace set 0 (and "s:"): ordered against its previous user
-  struct LeaveGuard {
-    rc_handle* h; hipStream_t st;
-    ~LeaveGuard() { (void)ws_leave(h, 0, st); }
-  } leave{h, st};
-  if ((rc = ensure_workspace(h, n))) return rc;
+  RenderWs& w = h->ws[0];
+  ExtraWs& x = h->ws_x;
+  if ((rc = ws_enter(h, 0, st))) return rc;             // workspace set 0 (and the secondary set): ordered against its previous user
+  WsLeave leave{h, 0, st, true};
+  if ((rc = ensure_workspace(h, w, n))) return rc;
   if (h->tcfg.use_occlusions) {
     const int64_t nsec = n * h->cfg.num_samples[h->cfg.num_levels - 1];
-    if ((rc = ws_alloc(h, "sh_origins", 3 * nsec)) || (rc = ws_alloc(h, "sh_dirs", 3 * nsec)) || (rc = ws_alloc(h, "sh_near", nsec)) ||
-        (rc = ws_alloc(h, "sh_far", nsec)) || (rc = ws_alloc(h, "sh_normals", 3 * nsec)) || (rc = ws_alloc(h, "sh_lights", 3 * nsec)) ||
-        (rc = ws_alloc(h, "sh_acc", nsec)))
+    if ((rc = ws_alloc(h, x.sh_origins, 3 * nsec)) || (rc = ws_alloc(h, x.sh_dirs, 3 * nsec)) || (rc = ws_alloc(h, x.sh_near, nsec)) ||
+        (rc = ws_alloc(h, x.sh_far, nsec)) || (rc = ws_alloc(h, x.sh_normals, 3 * nsec)) || (rc = ws_alloc(h, x.sh_lights, 3 * nsec)) ||
+        (rc = ws_alloc(h, x.sh_acc, nsec)) || (rc = ensure_workspace(h, h->ws_sec, nsec)))
       return rc;
-    h->ws_prefix = "s:";
-    rc = ensure_workspace(h, nsec);
-    h->ws_prefix = "";
-    if (rc) return rc;
   }
   rc_shader_prepare();
   RenderArgs A{};
@@ -322,7 +303,7 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   A.out.ptr[RC_OUT_NORMALS_PRED] = out->ptr[RC_TOUT_NORMALS_PRED];
   A.out.ptr[RC_OUT_RAY_DISTS] = out->ptr[RC_TOUT_RAY_DISTS];
   A.out.ptr[RC_OUT_LIGHT_DISTS] = out->ptr[RC_TOUT_LIGHT_DISTS];
-  enqueue_all(h, A, st);
+  enqueue_all(h, A, w, st);
   RC_HIP(h, hipGetLastError());
   return RC_OK;
   RC_CATCH(h)

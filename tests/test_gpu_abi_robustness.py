@@ -97,6 +97,38 @@ def test_material_and_cache_calls_from_two_streams_share_set_zero():
             assert torch.equal(got_m[k], want_m[k]), k
 
 
+def test_workspace_names_resolve_every_set():
+    """rc_workspace_ptr beyond set 0: a "p1:" name after a render on a second caller stream (its own set, the same values
+    as set 0 for the same rays), a "t:" name after rc_density_backward, a set no call has used, and unknown names, which
+    come back as RC_ERR_INVALID_ARG."""
+    from nrc_amd import rc_ext
+    rc = _staged_rc(common.weights_np())
+    rc.set_graph_mode(0)
+    n = 256
+    fields = {k: rc._dev(v) for k, v in nrc_amd.synthetic_rays(n, seed=21).hot_fields().items() if v is not None}
+    rc.render_rays(fields, None, **STAGED)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        rc.render_rays(fields, None, **STAGED)
+    torch.cuda.synchronize()
+    for name, count in (("density2", n * 32), ("tdist0", n * 65), ("weights2", n * 32)):
+        p1 = rc.workspace("p1:" + name)
+        assert p1.size == count, name
+        assert np.array_equal(p1, rc.workspace(name)), name
+    pts = np.random.default_rng(3).uniform(-1.0, 1.0, size=(n, 3)).astype(np.float32)
+    rc.density_backward(0, pts, np.ones(n, np.float32))
+    torch.cuda.synchronize()
+    K = 6                                      # proposal grid 0: 6 levels of 1 feature
+    feat = rc.workspace("t:feat")
+    ld = (n + 63) // 64 * 64
+    assert feat.size == K * ld and rc.workspace("t:graw").size == n
+    np.testing.assert_allclose(feat.reshape(K, ld)[:, :n].T, rc.hashgrid_lookup(0, pts).cpu().numpy(), rtol=1e-6, atol=1e-7)
+    for name in ("p2:density2", "shade_rgb", "density", "density3", "t:sdist0", "p1:m_mat", "q1:inds"):
+        with pytest.raises(rc_ext.RcError) as e:
+            rc.workspace(name)
+        assert e.value.code == -1, name
+
+
 def test_errors_come_back_as_codes():
     from nrc_amd import rc_ext
     rc = rc_ext.RadianceCache(nrc_amd.hotdog_config(), 0)
