@@ -284,13 +284,17 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
 /* -- introspection for tests / profiling: a named workspace buffer as the last call that used its set left it.
  * name = [prefix]<buffer>.  Prefix: none = set 0 (rc_render_rays on the first caller stream, rc_render_material,
  * rc_render_transient), "p1:" .. "p3:" = the sets of rc_render_rays on further caller streams, "s:" = the batched
- * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward.
+ * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
+ * "i:" = rc_interlevel_backward.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
  * "acc_sel", "feat_sel", "hbuf_sel", "normals_sel", "density_sel"; "t_irr", "t_slf", "tshade" (set 0 of a time-resolved
  * handle).  Set 0 only: "m_*", "l_*", "sec_*" (rc_render_material), "sh_*" (rc_render_transient with occlusions).
  * "t:": "feat", "dfeat", "a1", "a2", "d1", "d2", "fe", "graw", "density", "partial".
+ * "i:": the training forward's per-level "sdist", "tdist", "means", "feat", "density", "weights" (levels 0 .. num_levels-1,
+ * as above), and per proposal level 0 .. num_levels-2 "d_density" (d loss / d density, [n][S]) and "points" (the
+ * means as [n S][3], the points of that level's density backward); "loss_ray" ([num_levels-1][n] per-ray sums).
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -474,6 +478,31 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
 int rc_hashgrid_grad_layout(rc_handle* h, int32_t grid_id, rc_grad_segment* segs, int32_t capacity, int32_t* count, int64_t* total);
 int rc_hashgrid_backward(rc_handle* h, int32_t grid_id, const float* points, int64_t n, const float* d_features, float* grads,
                          int32_t apply_contraction, void* stream);
+
+/* Spline interlevel loss of the proposal samplers and the exact gradients of both proposal networks
+ * (loss_utils.spline_interlevel_loss, internal/loss_utils.py:74-104, with ProposalVolumeSampler.stop_level_grad,
+ * sampling.py:354-355: each proposal level's loss reaches only its own density).  One call:
+ *   1. the training forward: the three sampler levels (sampling + grid lookup + density MLP; no shader) of rc_render_rays'
+ *      launch plan, with the caller's jitter (rnd->jitter; rnd NULL = the deterministic sampler) and `anneal`
+ *      (the train-time clip(bias(train_frac / anneal_end, anneal_slope), 0, anneal_clip), sampling.py:326-335; the
+ *      handle's rc_config.anneal is the render-time value), on a workspace set of its own ("i:");
+ *   2. per proposal level l < num_levels-1: the last level's weights * lossmult blurred by blurs[l] and resampled onto
+ *      level l's intervals (stepfun.blur_and_resample_weights, stepfun.py:463-483; linspline.py:95-222), the term
+ *      losses[l] = mults[l] * mean over the n x S_l samples of max(0, w_blur - wp)^2 / (wp + 1e-5), wp = weights_l *
+ *      lossmult, and its d / d density_l through compute_alpha_weights (render.py:134-169);
+ *   3. per proposal level whose grads[l] is not NULL: rc_density_backward of that level at the forward's own sample
+ *      means with that d_density, ACCUMULATED into grads[l] (layout rc_density_grad_layout(l)).
+ * rays: origins, directions, viewdirs, near, far as for rc_render_rays.  lossmult: [n] device floats or NULL (1).
+ * mults, blurs: HOST arrays of num_levels-1 floats (the hotdog gin: mults (0.01, 0.01), blurs (0.03, 0.003);
+ * configs/ngp_yobo.gin:245-247).  losses: DEVICE array of num_levels-1 floats, written (bitwise reproducible).
+ * The mean is over the local batch; a data-parallel trainer all-reduces (averages) grads afterwards, as pmean.
+ * Scaling by (not finetune_cache) (train_utils.py:3193-3202) is the caller's.  Everything is ordered on `stream`.
+ * The last level must have <= 32 intervals, the proposal levels <= 64 (RC_ERR_UNSUPPORTED otherwise); the time-resolved
+ * cache handle is unsupported.  n == 0 returns RC_OK and writes nothing.
+ * Buffers of the call: rc_workspace_ptr "i:" names. */
+int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                           float anneal, const float* mults, const float* blurs, float* const* grads, float* losses,
+                           void* stream);
 
 #ifdef __cplusplus
 }

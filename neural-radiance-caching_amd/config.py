@@ -156,6 +156,22 @@ class RenderConfig:
         return len(self.sampling_strategy)
 
 
+@dataclasses.dataclass(frozen=True)
+class InterlevelConfig:
+    """Training-time constants of the proposal samplers' spline interlevel loss (hotdog cache stage).  Kept apart from
+    RenderConfig: nothing here reaches the render path."""
+    # Config.use_spline_interlevel_loss = True; interlevel_loss_mults / _blurs: configs/ngp_yobo.gin:245-247,
+    # nerf_ngp_yobo.gin:62-64 (one value per proposal level)
+    mults: Tuple[float, ...] = (0.01, 0.01)
+    blurs: Tuple[float, ...] = (0.03, 0.003)
+    # ProposalVolumeSampler anneal schedule: anneal_slope / anneal_end defaults (internal/sampling.py:71-72),
+    # anneal_clip = 0.4 (nerf_ngp_yobo_hotdog.gin:5); anneal = clip(bias(train_frac / anneal_end, anneal_slope), 0,
+    # anneal_clip) (sampling.py:326-335)
+    anneal_slope: float = 10.0
+    anneal_end: float = 1.0
+    anneal_clip: float = 0.4
+
+
 def hotdog_config(**overrides) -> RenderConfig:
     """configs/nerf_ngp_yobo_hotdog.gin resolved at render time (train=False)."""
     return dataclasses.replace(RenderConfig(), **overrides)

@@ -76,18 +76,24 @@ struct ExtraWs {
 };
 // rc_density_backward.
 struct TrainWs { WsBuf feat, dfeat, a1, a2, d1, d2, fe, graw, density, partial; };
+// rc_interlevel_backward, beside its RenderWs (the training forward): per proposal level d loss / d density and the
+// sample means as points [n S][3]; the per-ray loss sums.
+struct InterlevelWs { WsBuf d_density[RC_MAX_LEVELS], points[RC_MAX_LEVELS]; WsBuf loss_ray; };
 
 // Every workspace buffer by name, for rc_workspace_ptr ("<name>", per-level buffers "<name><level>") and rc_destroy.
 struct WsName {
   const char* name;
   WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
+  WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
   constexpr WsName(const char* s, WsBuf TrainWs::*m) : name(s), t(m) {}
+  constexpr WsName(const char* s, WsBuf InterlevelWs::*m) : name(s), i(m) {}
+  constexpr WsName(const char* s, WsBuf (InterlevelWs::*m)[RC_MAX_LEVELS]) : name(s), ilv(m) {}
 };
 namespace wsn {
-using R = RenderWs; using X = ExtraWs; using T = TrainWs;
+using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -98,10 +104,11 @@ constexpr WsName kTable[] = {
     WS(X, l_vmf_logit), WS(X, sec_origins), WS(X, sec_dirs), WS(X, sec_near), WS(X, sec_far), WS(X, sec_lights),
     WS(X, sec_samples), WS(X, m_local_view), WS(X, sec_rgb), WS(X, sec_acc), WS(X, sec_env), WS(X, sh_origins), WS(X, sh_dirs),
     WS(X, sh_near), WS(X, sh_far), WS(X, sh_normals), WS(X, sh_lights), WS(X, sh_acc),
-    WS(T, feat), WS(T, dfeat), WS(T, a1), WS(T, a2), WS(T, d1), WS(T, d2), WS(T, fe), WS(T, graw), WS(T, density), WS(T, partial)};
+    WS(T, feat), WS(T, dfeat), WS(T, a1), WS(T, a2), WS(T, d1), WS(T, d2), WS(T, fe), WS(T, graw), WS(T, density), WS(T, partial),
+    WS(I, d_density), WS(I, points), WS(I, loss_ray)};
 #undef WS
-constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += e.lv ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T), "the table lists every workspace buffer");
+constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I), "the table lists every workspace buffer");
 }  // namespace wsn
 
 constexpr int kEvSlots = 16;
@@ -146,14 +153,15 @@ struct rc_handle {
   // Workspace sets.  ws[0..3] serve rc_render_rays, one per caller stream so that independent batches enqueued on
   // different streams overlap (the least recently used one is taken over when a fifth stream shows up); ws[0] also serves
   // rc_render_material / rc_render_transient, with ws_x and with ws_sec for their batched secondary trace; ws_train serves
-  // rc_density_backward.  groups[0..3] / groups[4] record who used a render set / the train set last: a call whose stream
-  // differs from the set's previous user first waits for that user's last call (event), so two streams never run on one
-  // set at the same time.
-  RenderWs ws[4], ws_sec;
+  // rc_density_backward; ws_il + ws_ilx serve rc_interlevel_backward.  groups[0..3] / groups[4] / groups[5] record who used
+  // a render set / the train set / the interlevel set last: a call whose stream differs from the set's previous user first
+  // waits for that user's last call (event), so two streams never run on one set at the same time.
+  RenderWs ws[4], ws_sec, ws_il;
   ExtraWs ws_x;
   TrainWs ws_train;
+  InterlevelWs ws_ilx;
   struct WsGroup { hipStream_t stream = nullptr; bool used = false; hipEvent_t done = nullptr; uint64_t last_use = 0; };
-  WsGroup groups[5];
+  WsGroup groups[6];
   uint64_t use_clock = 0;
   // profiling: ring of event sets, one set per render call (slot = call % kEvSlots)
   // mode 0 off, 1 every stage, 2 only the dominant kernel (cache shader), 3 like 2 on every 8th call
@@ -768,29 +776,33 @@ int ensure_workspace(rc_handle* h, RenderWs& w, int64_t n) {
 
 void free_workspace(rc_handle* h) {
   for (const WsName& e : wsn::kTable) {
-    for (RenderWs* r : {&h->ws[0], &h->ws[1], &h->ws[2], &h->ws[3], &h->ws_sec}) {
+    for (RenderWs* r : {&h->ws[0], &h->ws[1], &h->ws[2], &h->ws[3], &h->ws_sec, &h->ws_il}) {
       if (e.r) free_buf(r->*e.r);
       if (e.lv) for (WsBuf& b : r->*e.lv) free_buf(b);
     }
     if (e.x) free_buf(h->ws_x.*e.x);
     if (e.t) free_buf(h->ws_train.*e.t);
+    if (e.i) free_buf(h->ws_ilx.*e.i);
+    if (e.ilv) for (WsBuf& b : h->ws_ilx.*e.ilv) free_buf(b);
   }
 }
 
-// rc_workspace_ptr: "[p1:|p2:|p3:|s:|t:]<name>[level]" -> the buffer (nullptr for an unknown name)
+// rc_workspace_ptr: "[p1:|p2:|p3:|s:|t:|i:]<name>[level]" -> the buffer (nullptr for an unknown name)
 WsBuf* ws_find(rc_handle* h, const char* name) {
   const char* colon = strchr(name, ':');
   const std::string pre = colon ? std::string(name, colon + 1) : "", leaf = colon ? colon + 1 : name;
-  const char* const kPre[6] = {"", "p1:", "p2:", "p3:", "s:", "t:"};
-  int set = -1;      // 0-3 rc_render_rays' sets (0 with the extras), 4 the secondary set, 5 the train set
-  for (int i = 0; i < 6; ++i) if (pre == kPre[i]) set = i;
-  RenderWs* r = set < 0 || set == 5 ? nullptr : (set == 4 ? &h->ws_sec : &h->ws[set]);
+  const char* const kPre[7] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:"};
+  int set = -1;      // 0-3 rc_render_rays' sets (0 with the extras), 4 the secondary set, 5 the train set, 6 the interlevel set
+  for (int i = 0; i < 7; ++i) if (pre == kPre[i]) set = i;
+  RenderWs* r = set < 0 || set == 5 ? nullptr : (set == 6 ? &h->ws_il : set == 4 ? &h->ws_sec : &h->ws[set]);
   for (const WsName& e : wsn::kTable) {
     const size_t k = strlen(e.name);
     if (leaf.compare(0, k, e.name) != 0) continue;
-    if (leaf.size() == k && ((e.r && r) || (e.x && set == 0) || (e.t && set == 5)))
-      return e.r ? &(r->*e.r) : e.x ? &(h->ws_x.*e.x) : &(h->ws_train.*e.t);
-    if (e.lv && r && leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels) return &(r->*e.lv)[leaf[k] - '0'];
+    if (leaf.size() == k && ((e.r && r) || (e.x && set == 0) || (e.t && set == 5) || (e.i && set == 6)))
+      return e.r ? &(r->*e.r) : e.x ? &(h->ws_x.*e.x) : e.t ? &(h->ws_train.*e.t) : &(h->ws_ilx.*e.i);
+    const bool digit = leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels;
+    if (e.lv && r && digit) return &(r->*e.lv)[leaf[k] - '0'];
+    if (e.ilv && set == 6 && digit && leaf[k] < '0' + h->cfg.num_levels - 1) return &(h->ws_ilx.*e.ilv)[leaf[k] - '0'];
   }
   return nullptr;
 }
@@ -1160,6 +1172,9 @@ struct RenderArgs {
   rc_rays rays; rc_randoms rnd; bool have_rnd; int64_t n; uint32_t mask; rc_outputs out; int slot; bool fused;
   const rc_transient_outputs* tout = nullptr; const float* cam_origins = nullptr;
   const rc_randoms* shadow_rnd = nullptr; bool weights_only = false; bool force_grad = false;
+  // rc_interlevel_backward's training forward: the sampler levels only (sdist / tdist / means / density / weights of every
+  // level in the workspace, nothing behind them), resampling at `anneal` (< 0: the config's render-time value)
+  bool sampler_only = false; float anneal = -1.0f;
   bool export_samples = false;     // fused plan: leave tdist / density / means / normals_pred of the last level in the workspace
   const float* s_bounds = nullptr; // secondary rays with ONE (near, far): power-ladder bounds computed once (RcSampleArgs)
   // material stage: the EnvMap of the trace's directions is released on `env_side` when the LAST proposal level is
@@ -1239,7 +1254,7 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st)
     sa.S = S;
     sa.jitter = rnd ? rnd->jitter[l] : nullptr;
     sa.sdist = w.sdist[l].p; sa.tdist = w.tdist[l].p; sa.means = w.means[l].p;
-    sa.anneal = c.anneal; sa.padding = c.resample_padding;
+    sa.anneal = A.anneal >= 0.0f ? A.anneal : c.anneal; sa.padding = c.resample_padding;
     sa.secondary = secondary ? 1 : 0;
     sa.use_raydist = (secondary || h->transient) ? 1 : 0;     // TransientNeRFModel: use_raydist_for_secondary_only = False
     sa.raydist_p = c.raydist_p; sa.raydist_premult = c.raydist_premult;
@@ -1287,12 +1302,13 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st)
     da.last = (l == NL - 1) ? 1 : 0; da.density = w.density[l].p;
     // lean resampling pass: the hidden feature / predicted normals are only needed at the ONE sample per ray picked
     // below, so they are not written for all of them here (256 + 12 bytes per sample) but recomputed for the picks
-    da.hbuf = (da.last && !lean) ? w.hbuf.p : nullptr;
-    da.normals_pred = (da.last && !lean) ? w.normals_pred.p : nullptr;
+    da.hbuf = (da.last && !lean && !A.sampler_only) ? w.hbuf.p : nullptr;
+    da.normals_pred = (da.last && !lean && !A.sampler_only) ? w.normals_pred.p : nullptr;
     da.jac = want_grad ? w.jac.p : nullptr; da.normals_grad = want_grad ? w.normals_grad.p : nullptr;
     stage_mark(h, slot, ST_MLP0 + 3 * l, st);
     rc_launch_density_mlp(da, st);
   }
+  if (A.sampler_only) return;
   const int S2 = c.num_samples[NL - 1];
   const int64_t np2 = n * S2;
   if (A.weights_only) {
@@ -1803,3 +1819,4 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 
 #include "rc_transient_host.inc"
 #include "rc_train_host.inc"
+#include "rc_interlevel_host.inc"

@@ -1,0 +1,227 @@
+// Spline interlevel loss of the proposal samplers and its gradient with respect to every proposal level's density
+// (DESIGN.md §4.6).
+//
+// Replaces, per proposal level l, loss_utils.spline_interlevel_loss (internal/loss_utils.py:74-104):
+//   c, w   = sdist and weights * lossmult of the LAST level (the target; stop_gradient on the blurred result)
+//   w_blur = blur_and_resample_weights(cp = sdist_l, c, w, blur_l)             (stepfun.py:463-483)
+//          = diff(interpolate_integral(cp, compute_integral(blur_stepfun(c, weight_to_pdf(c, w), blur_l))))
+//   loss_l = mult_l * mean(max(0, w_blur - wp)^2 / (wp + 1e-5)),  wp = weights_l * lossmult
+// and the backward of that mean through compute_alpha_weights (render.py:134-169) to d loss_l / d density_l.  sdist
+// carries no gradient across levels (ProposalVolumeSampler.stop_level_grad, sampling.py:354-355), so this is the
+// whole gradient of the term up to the density; rc_density_backward takes it from there.
+//
+// One wave per ray (S_l <= 64 intervals on the proposal levels, S_last <= 32 on the target: its 2 (S_last + 1)
+// dilated knots are merged by rank, no sort):
+//   weights      alpha_weight of rc_dev_sample.h on every level: the samplers' own arithmetic
+//   blur_stepfun (linspline.py:187-222)  ts_lo = min(minus_eps(t), t - h), ts_hi = max(plus_eps(t), t + h) are each
+//                sorted, so the stable argsort of [ts_lo, ts_hi] is a merge: lo_j has rank j + #{hi < lo_j}, hi_j has
+//                rank j + #{lo <= hi_j} (a tie puts the lo knot first, as the stable sort of the concatenation does).
+//                dyp is gathered with idx[:-2]: the derivative of a knot of rank >= 2 S_last is dropped.  Double
+//                cumsum on two wave scans.
+//   compute_integral / interpolate_integral (linspline.py:95-141): queries clipped to [t_0, minus_eps(t_last)],
+//                searchsorted side='right' by binary search in LDS.
+//   backward     g_k = d loss / d weights_k;  x = density * |delta|;  d L / d x_k = g_k T_{k+1} - sum_{i>k} g_i w_i
+//                (a reverse wave scan);  d L / d density_k = d L / d x_k * |delta_k|.
+// The per-ray loss sums go to loss_ray[level][ray]; k_interlevel_reduce adds them in a fixed order (bitwise stable).
+#include <hip/hip_runtime.h>
+
+#include "rc_dev_sample.h"
+
+using namespace rcdev;
+
+namespace {
+
+constexpr int kIlWaves = 4;                 // rays (waves) per workgroup
+// LDS floats per wave: s knots of the target [65], dilated lo / hi [2 x 65], merged knots tp [66], dyp [64],
+// blurred pdf yp [66], integral offsets c [65], integrated queries acc [65], query knots [65]
+constexpr int kIlT = 0, kIlLo = 68, kIlHi = 136, kIlTp = 204, kIlDyp = 272, kIlYp = 340, kIlC = 408, kIlAcc = 476,
+              kIlQ = 544, kIlFloats = 612;
+
+__device__ __forceinline__ float minus_eps(float x) { return fabsf(x) < RC_TINY ? -RC_TINY : nextafterf(x, -INFINITY); }
+__device__ __forceinline__ float plus_eps(float x) { return fabsf(x) < RC_TINY ? RC_TINY : nextafterf(x, INFINITY); }
+
+// Number of entries of s[0..m-1] (sorted ascending) that are < x  (searchsorted side='left').
+__device__ __forceinline__ int lower_bound(const float* s, int m, float x) {
+  int lo = 0, hi = m;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (s[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ float shfl_f(float v, int src) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
+}
+
+__global__ void __launch_bounds__(64 * kIlWaves) k_interlevel_bwd(RcInterlevelArgs a) {
+  __shared__ float lds_all[kIlWaves * kIlFloats];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t ray = (int64_t)blockIdx.x * kIlWaves + wave;
+  if (ray >= a.n) return;                   // wave-uniform; nothing below synchronises beyond the wave
+  float* lds = lds_all + wave * kIlFloats;
+  float* s_t = lds + kIlT;
+  float* s_lo = lds + kIlLo;
+  float* s_hi = lds + kIlHi;
+  float* s_tp = lds + kIlTp;
+  float* s_dyp = lds + kIlDyp;
+  float* s_yp = lds + kIlYp;
+  float* s_c = lds + kIlC;
+  float* s_acc = lds + kIlAcc;
+  float* s_q = lds + kIlQ;
+
+  const int NL = a.num_levels, L2 = NL - 1;
+  const float dx = a.directions[3 * ray], dy = a.directions[3 * ray + 1], dz = a.directions[3 * ray + 2];
+  const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);      // as sample_level_ray
+  const float lm = a.lossmult ? a.lossmult[ray] : 1.0f;
+
+  // --- the target: weights * lossmult of the last level on its s knots -> weight_to_pdf (stepfun.py:75-79)
+  const int S2 = a.S[L2];
+  const bool act2 = lane < S2;
+  const float* td2 = a.tdist[L2] + ray * (S2 + 1);
+  const float w2 = alpha_weight(act2 ? a.density[L2][ray * S2 + lane] : 0.0f, act2 ? td2[lane] : 0.0f,
+                                act2 ? td2[lane + 1] : 0.0f, dnorm, act2, lane) * lm;
+  if (lane <= S2) s_t[lane] = a.sdist[L2][ray * (S2 + 1) + lane];
+  lds_sync_wave();
+  float pdf = 0.0f;                         // safe_div (math.py:133-140) where td >= tiny, else 0
+  if (act2) {
+    const float d = s_t[lane + 1] - s_t[lane];
+    pdf = d < RC_TINY ? 0.0f : fminf(fmaxf(w2 / d, -RC_FMAX), RC_FMAX);
+  }
+  // ys0 = [0, pdf, 0]: lane j <= S2 needs pdf_{j-1}
+  const float pdf_left = shfl_f(pdf, (lane + 63) & 63);      // every lane takes part in the permute
+  const float pdf_prev = lane == 0 ? 0.0f : pdf_left;
+  const int M = 2 * (S2 + 1);               // dilated knots
+
+  for (int l = 0; l < L2; ++l) {
+    const float h = a.blur[l];
+    // --- blur_stepfun: dilated knots, merged by rank
+    float dyv = 0.0f, lo = 0.0f, hi = 0.0f;
+    if (lane <= S2) {
+      const float t = s_t[lane];
+      lo = fminf(minus_eps(t), t - h);
+      hi = fmaxf(plus_eps(t), t + h);
+      s_lo[lane] = lo; s_hi[lane] = hi;
+      dyv = ((lane < S2 ? pdf : 0.0f) - pdf_prev) / (hi - lo);
+    }
+    lds_sync_wave();
+    if (lane <= S2) {
+      const int rlo = lane + lower_bound(s_hi, S2 + 1, lo);
+      const int rhi = lane + upper_bound(s_lo, S2 + 1, hi);
+      s_tp[rlo] = lo; s_tp[rhi] = hi;
+      if (rlo < M - 2) s_dyp[rlo] = dyv;
+      if (rhi < M - 2) s_dyp[rhi] = -dyv;
+    }
+    lds_sync_wave();
+    // yp[r + 1] = cumsum(diff(tp)[:-1] * cumsum(dyp)), r < M - 2 (<= 64 lanes); yp[0] = yp[M - 1] = 0
+    const bool ra = lane < M - 2;
+    const float cdy = wave_scan_incl(ra ? s_dyp[lane] : 0.0f, lane);
+    const float dtp = ra ? s_tp[lane + 1] - s_tp[lane] : 0.0f;
+    const float yp = wave_scan_incl(dtp * cdy, lane);
+    if (ra) s_yp[lane + 1] = yp;
+    if (lane == 0) { s_yp[0] = 0.0f; s_yp[M - 1] = 0.0f; }
+    lds_sync_wave();
+    // compute_integral: c[0] = 0, c[r + 1] = 0.5 * cumsum(dt[:-1] * (yp[:-2] + yp[1:-1]))[r], r < M - 2
+    const float e = ra ? dtp * (s_yp[lane] + s_yp[lane + 1]) : 0.0f;
+    const float cs = wave_scan_incl(e, lane);
+    if (ra) s_c[lane + 1] = 0.5f * cs;
+    if (lane == 0) s_c[0] = 0.0f;
+    // the query knots: this level's sdist
+    const int S = a.S[l];
+    const float* sd = a.sdist[l] + ray * (S + 1);
+    s_q[lane] = lane <= S ? sd[lane] : 0.0f;
+    if (lane + 64 <= S) s_q[lane + 64] = sd[lane + 64];
+    lds_sync_wave();
+    // interpolate_integral at the S + 1 query knots
+    const float tmin = s_tp[0], tmax = minus_eps(s_tp[M - 1]);
+    for (int q = lane; q <= S; q += 64) {
+      const float tq = fminf(fmaxf(s_q[q], tmin), tmax);
+      const int i0 = min(max(upper_bound(s_tp, M, tq) - 1, 0), M - 2);
+      const float t0 = s_tp[i0];
+      const float av = (s_yp[i0 + 1] - s_yp[i0]) / fmaxf(RC_EPS * RC_EPS, 2.0f * (s_tp[i0 + 1] - t0));
+      const float bv = s_yp[i0], cv = s_c[i0];
+      const float d = tq - t0;
+      s_acc[q] = av * (d * d) + bv * d + cv;
+    }
+    lds_sync_wave();
+    // --- the truncated chi-squared term and d loss / d wp
+    const bool act = lane < S;
+    const float* tdl = a.tdist[l] + ray * (S + 1);
+    const float t0 = act ? tdl[lane] : 0.0f, t1 = act ? tdl[lane + 1] : 0.0f;
+    const float dens = act ? a.density[l][ray * S + lane] : 0.0f;
+    const float w = alpha_weight(dens, t0, t1, dnorm, act, lane);
+    const float wb = act ? fmaxf(0.0f, s_acc[lane + 1] - s_acc[lane]) : 0.0f;
+    const float wp = w * lm;
+    const float m = fmaxf(0.0f, wb - wp);
+    const float den = wp + 1e-5f;
+    const float term = act ? m * m / den : 0.0f;
+    const float ray_loss = wave_sum(term);
+    if (lane == 0) a.loss_ray[(int64_t)l * a.n + ray] = ray_loss;
+    const float g_wp = act ? a.coef[l] * (-(2.0f * m) / den - (m * m) / (den * den)) : 0.0f;
+    const float g = g_wp * lm;
+    // --- compute_alpha_weights backward: x = density * |delta|, T_{k+1} = exp(-cumsum(x)_k)
+    const float adelta = act ? fabsf((t1 - t0) * dnorm) : 0.0f;
+    const float x = act ? dens * adelta : 0.0f;
+    const float tnext = expf(-wave_scan_incl(x, lane));
+    // sum_{i>k} g_i w_i: inclusive scan over the reversed lanes, read back one lane further
+    const float gw = act ? g * w : 0.0f;
+    const float rev = wave_scan_incl(shfl_f(gw, 63 - lane), lane);
+    const float rev_next = shfl_f(rev, (62 - lane) & 63);
+    const float after = lane < 63 ? rev_next : 0.0f;
+    const float dx_k = g * tnext - after;
+    if (act) a.d_density[l][ray * S + lane] = dx_k * adelta;
+    lds_sync_wave();                        // the next level rewrites this wave's LDS
+  }
+}
+
+// losses[l] = mult_l * (sum of loss_ray[l] / (n S_l)), summed in a fixed order: one workgroup per level, a strided
+// partial per thread (double), a tree through LDS.
+__global__ void __launch_bounds__(256) k_interlevel_reduce(const float* loss_ray, int64_t n, RcInterlevelReduce r, float* losses) {
+  __shared__ double part[256];
+  const int l = blockIdx.x;
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)loss_ray[(int64_t)l * n + i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) part[threadIdx.x] += part[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) losses[l] = r.mult[l] * (float)(part[0] / r.count[l]);
+}
+
+// SoA means [3][np] -> AoS points [np][3] (rc_density_backward's layout), an exact copy
+__global__ void k_points_aos(const float* __restrict__ soa, int64_t np, float* __restrict__ aos) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  aos[3 * i] = soa[i];
+  aos[3 * i + 1] = soa[np + i];
+  aos[3 * i + 2] = soa[2 * np + i];
+}
+
+}  // namespace
+
+bool rc_interlevel_supported(int num_levels, const int* S) {
+  if (num_levels < 2 || num_levels > RC_MAX_LEVELS) return false;
+  if (S[num_levels - 1] < 2 || S[num_levels - 1] > 32) return false;
+  for (int l = 0; l < num_levels - 1; ++l)
+    if (S[l] < 1 || S[l] > 64) return false;
+  return true;
+}
+
+void rc_launch_interlevel_bwd(const RcInterlevelArgs& a, hipStream_t stream) {
+  if (a.n <= 0) return;
+  const unsigned blocks = (unsigned)((a.n + kIlWaves - 1) / kIlWaves);
+  hipLaunchKernelGGL(k_interlevel_bwd, dim3(blocks), dim3(64 * kIlWaves), 0, stream, a);
+}
+
+void rc_launch_interlevel_reduce(const float* loss_ray, int64_t n, int levels, const RcInterlevelReduce& r, float* losses,
+                                 hipStream_t stream) {
+  if (n <= 0 || levels <= 0) return;
+  hipLaunchKernelGGL(k_interlevel_reduce, dim3(levels), dim3(256), 0, stream, loss_ray, n, r, losses);
+}
+
+void rc_launch_points_aos(const float* soa, int64_t np, float* aos, hipStream_t stream) {
+  if (np <= 0) return;
+  hipLaunchKernelGGL(k_points_aos, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, soa, np, aos);
+}

@@ -1,0 +1,95 @@
+// Host side of rc_interlevel_backward (rc_interlevel.hip); included by rc_api.hip after rc_train_host.inc.
+//
+// One call = the training forward (enqueue_all's sampler levels on the interlevel workspace set ws_il, the caller's jitter
+// and anneal) -> k_interlevel_bwd (losses' per-ray sums, d loss / d density of every proposal level) ->
+// k_interlevel_reduce (the losses, fixed order) -> per proposal level with a gradient buffer: the means copied from the
+// workspace's SoA [3][n S] into the AoS [n S][3] rc_density_backward takes (an exact copy: the backward evaluates the
+// forward's points; 24 bytes per sample moved, against the ~2 KB per sample the density backward itself moves), then
+// rc_density_backward of that level.
+
+int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                           float anneal, const float* mults, const float* blurs, float* const* grads, float* losses,
+                           void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const rc_config& c = h->cfg;
+  const int NL = c.num_levels;
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: negative n_rays");
+  if (!rays || !mults || !blurs) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: null rays/mults/blurs");
+  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: anneal must be finite and >= 0");
+  for (int l = 0; l < NL - 1; ++l) {
+    if (!std::isfinite(mults[l])) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: mults must be finite");
+    if (!(blurs[l] >= 0.0f) || !std::isfinite(blurs[l])) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: blurs must be finite and >= 0");
+  }
+  if (n == 0) return RC_OK;
+  if (!losses) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: null losses");
+  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
+    return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: origins/directions/viewdirs/near/far are required");
+  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_interlevel_backward: not available on a time-resolved cache handle");
+  if (!rc_interlevel_supported(NL, c.num_samples))
+    return fail(h, RC_ERR_UNSUPPORTED, "rc_interlevel_backward: needs >= 2 levels, <= 64 samples per proposal level, <= 32 on the last");
+  RoctxScope roctx_call("rc_interlevel_backward");
+  RC_HIP(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream_v;
+  int rc;
+  if (h->packed_dirty) {
+    drop_graphs(h);
+    if ((rc = repack(h))) return rc;
+  }
+  if ((rc = ws_enter(h, 5, st))) return rc;             // the interlevel set: ordered against its previous user
+  WsLeave leave{h, 5, st, true};
+  RenderWs& w = h->ws_il;
+  InterlevelWs& x = h->ws_ilx;
+  for (int l = 0; l < NL; ++l) {
+    const int64_t S = c.num_samples[l];
+    const int LF = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
+    if ((rc = ws_alloc(h, w.sdist[l], n * (S + 1))) || (rc = ws_alloc(h, w.tdist[l], n * (S + 1))) ||
+        (rc = ws_alloc(h, w.means[l], 3 * n * S)) || (rc = ws_alloc(h, w.feat[l], (int64_t)LF * n * S)) ||
+        (rc = ws_alloc(h, w.density[l], n * S)) || (rc = ws_alloc(h, w.weights[l], n * S)))
+      return rc;
+    if (l < NL - 1) {
+      if ((rc = ws_alloc(h, x.d_density[l], n * S))) return rc;
+      if (grads && grads[l] && (rc = ws_alloc(h, x.points[l], 3 * n * S))) return rc;
+    }
+  }
+  if ((rc = ws_alloc(h, x.loss_ray, (int64_t)(NL - 1) * n))) return rc;
+
+  // 1. the training forward: rc_render_rays' own sampler loop, stopped behind the last level's density
+  RenderArgs A{};
+  A.rays = *rays;
+  A.have_rnd = rnd != nullptr;
+  if (rnd) A.rnd = *rnd;
+  A.n = n; A.mask = RC_PASS_CACHE; A.slot = -1; A.fused = false;
+  A.sampler_only = true; A.anneal = anneal;
+  enqueue_all(h, A, w, st);
+
+  // 2. the loss and d loss / d density of every proposal level
+  RcInterlevelArgs ia{};
+  ia.n = n; ia.num_levels = NL; ia.directions = rays->directions; ia.lossmult = lossmult; ia.loss_ray = x.loss_ray.p;
+  RcInterlevelReduce rr{};
+  for (int l = 0; l < NL; ++l) {
+    ia.S[l] = c.num_samples[l];
+    ia.sdist[l] = w.sdist[l].p; ia.tdist[l] = w.tdist[l].p; ia.density[l] = w.density[l].p;
+    if (l < NL - 1) {
+      const double count = (double)n * c.num_samples[l];
+      ia.blur[l] = blurs[l];
+      ia.coef[l] = (float)((double)mults[l] / count);      // jnp.mean: 1 / (n S) per sample, times the mult
+      ia.d_density[l] = x.d_density[l].p;
+      rr.mult[l] = mults[l]; rr.count[l] = count;
+    }
+  }
+  rc_launch_interlevel_bwd(ia, st);
+  rc_launch_interlevel_reduce(x.loss_ray.p, n, NL - 1, rr, losses, st);
+  RC_HIP(h, hipGetLastError());
+
+  // 3. the density backward of each proposal level at the forward's sample means
+  for (int l = 0; l < NL - 1; ++l) {
+    if (!grads || !grads[l]) continue;
+    const int64_t np = n * c.num_samples[l];
+    rc_launch_points_aos(w.means[l].p, np, x.points[l].p, st);
+    if ((rc = rc_density_backward(h, l, x.points[l].p, np, x.d_density[l].p, nullptr, grads[l], nullptr, stream_v))) return rc;
+  }
+  RC_HIP(h, hipGetLastError());
+  return RC_OK;
+  RC_CATCH(h)
+}

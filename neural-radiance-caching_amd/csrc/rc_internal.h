@@ -443,6 +443,28 @@ struct RcGridScatterArgs {
 void rc_launch_grid_scatter(const RcGridScatterArgs& a, hipStream_t stream, hipStream_t small_stream = nullptr, bool use_small_stream = false);
 bool rc_train_prepare();     // LDS opt-in of the scatter kernels (call once outside any stream capture)
 
+// Spline interlevel loss and d loss / d density of the proposal levels (rc_interlevel.hip)
+struct RcInterlevelArgs {
+  int64_t n;                               // rays
+  int num_levels;                          // sampler levels; the last is the target, 0 .. num_levels - 2 get a loss
+  int S[RC_MAX_LEVELS];                    // intervals per level
+  const float* sdist[RC_MAX_LEVELS];       // [n][S + 1]
+  const float* tdist[RC_MAX_LEVELS];       // [n][S + 1]
+  const float* density[RC_MAX_LEVELS];     // [n][S]
+  const float* directions;                 // [n][3]
+  const float* lossmult;                   // [n] or nullptr (1)
+  float blur[RC_MAX_LEVELS];               // halfwidth per proposal level
+  float coef[RC_MAX_LEVELS];               // mult / (n S) per proposal level: d loss / d (per-sample term)
+  float* d_density[RC_MAX_LEVELS];         // [n][S] per proposal level, written
+  float* loss_ray;                         // [num_levels - 1][n] per-ray sums of the per-sample terms, written
+};
+struct RcInterlevelReduce { float mult[RC_MAX_LEVELS]; double count[RC_MAX_LEVELS]; };
+bool rc_interlevel_supported(int num_levels, const int* S);
+void rc_launch_interlevel_bwd(const RcInterlevelArgs& a, hipStream_t stream);
+void rc_launch_interlevel_reduce(const float* loss_ray, int64_t n, int levels, const RcInterlevelReduce& r, float* losses,
+                                 hipStream_t stream);
+void rc_launch_points_aos(const float* soa, int64_t np, float* aos, hipStream_t stream);
+
 // Random fill (rc_prng.hip)
 enum { RC_PRNG_BITS = 0, RC_PRNG_UNIFORM = 1, RC_PRNG_NORMAL = 2, RC_PRNG_GUMBEL = 3 };
 struct RcPrngArgs {

@@ -151,7 +151,7 @@ EXPORTS = (
     "rc_hashgrid_lookup", "rc_sample_intervals", "rc_workspace_ptr", "rc_set_profiling", "rc_stage_count",
     "rc_stage_name", "rc_stage_times_ms", "rc_set_graph_mode", "rc_set_fused", "rc_render_material", "rc_set_transient", "rc_render_transient", "rc_cast_rays",
     "rc_prng_fill", "rc_density_grad_size", "rc_density_grad_layout", "rc_density_backward",
-    "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs",
+    "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs", "rc_interlevel_backward",
 )
 
 _LIB = None
@@ -246,6 +246,10 @@ def load_library():
     lib.rc_density_backward.restype = C.c_int
     lib.rc_hashgrid_grad_layout.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     lib.rc_hashgrid_grad_layout.restype = C.c_int
+    lib.rc_interlevel_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms), C.c_float,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.c_void_p,
+                                           C.c_void_p]
+    lib.rc_interlevel_backward.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -630,6 +634,61 @@ class RadianceCache:
                                                  stream))
         self._keep = [pts, dd, df]
         return grads, dens
+
+    def interlevel_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, mults=(0.01, 0.01),
+                            blurs=(0.03, 0.003), lossmult=None, grads=None, levels=None):
+        """rc_interlevel_backward: the spline interlevel loss of the proposal levels on a batch of rays and its gradient
+        w.r.t. the hash-grid tables and density MLP of each proposal level (loss_utils.spline_interlevel_loss).
+        jitters: per-level [n] sampler jitter (None = the deterministic sampler); anneal: the train-time resampling
+        exponent (train.anneal_at); lossmult: [n] or None (1).  grads: per proposal level a flat float32 cuda buffer
+        (density_grad_layout(level)), accumulated into; a missing one is allocated zeroed.  levels: the proposal levels
+        whose backward runs (default all); the others get no gradient (None in the result).
+        Returns (flat buffers, losses [num_levels - 1] cuda tensor)."""
+        torch = self._torch
+        r, held, n = self._rays_struct(rays)
+        nprop = self.cfg.num_levels - 1
+        levels = tuple(range(nprop)) if levels is None else tuple(levels)
+        if len(mults) != nprop or len(blurs) != nprop:
+            raise ValueError(f"mults and blurs need {nprop} values")
+        rnd_p = None
+        if jitters is not None:
+            rnd = rc_randoms()
+            for l, j in enumerate(jitters):
+                if j is not None:
+                    t = self._dev(j).reshape(-1)
+                    if t.shape[0] != n:
+                        raise ValueError(f"jitter of level {l} has {t.shape[0]} values, expected {n}")
+                    held[f"jit{l}"] = t
+                    rnd.jitter[l] = t.data_ptr()
+            rnd_p = C.byref(rnd)
+        lm = None
+        if lossmult is not None:
+            lm = self._dev(lossmult).reshape(-1)
+            if lm.shape[0] != n:
+                raise ValueError("lossmult must have one value per ray")
+            held["lossmult"] = lm
+        flats = list(grads) if grads is not None else [None] * nprop
+        ptrs = (C.c_void_p * nprop)()
+        for l in range(nprop):
+            if l not in levels:
+                flats[l] = None
+                continue
+            total = int(self.lib.rc_density_grad_size(self._h, l))
+            if total < 0:
+                self._check(total)
+            if flats[l] is None:
+                flats[l] = torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
+            elif flats[l].numel() != total or flats[l].dtype != torch.float32 or not flats[l].is_cuda or not flats[l].is_contiguous():
+                raise ValueError(f"grads[{l}] must be a contiguous float32 cuda tensor of {total} elements")
+            ptrs[l] = flats[l].data_ptr()
+        losses = torch.zeros(max(nprop, 1), dtype=torch.float32, device=f"cuda:{self.device}")
+        m = (C.c_float * nprop)(*[float(v) for v in mults])
+        b = (C.c_float * nprop)(*[float(v) for v in blurs])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.rc_interlevel_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n, rnd_p,
+                                                    float(anneal), m, b, ptrs, losses.data_ptr(), stream))
+        self._keep = [held]
+        return flats, losses
 
     def prng_fill(self, key, shape, mode: str = "uniform", minval: float = 0.0, maxval: float = 1.0):
         """rc_prng_fill: the tensor jax.random.{bits,uniform,normal,gumbel}(key, shape) of the reference's pinned jax

@@ -11,13 +11,20 @@ model followed by `jax.lax.pmean(grad, "batch")` across devices and the optimize
     (torch.distributed; backend "nccl" = RCCL over xGMI on the GPUs, "gloo" in the CPU tests).  The buffers are the
     bucket: ~45-180 MB per level, large enough to run the xGMI ring at its per-link bound, no per-tensor launches.
 
-The loss, the shader's backward and the optimizer are not part of this row.
+  * `interlevel_grads(rc, rays, jitters, train_frac)` -> the spline interlevel loss of the proposal samplers
+    (loss_utils.spline_interlevel_loss) and the exact gradients of both proposal networks, in one device call
+    (rc_interlevel_backward: training forward, loss backward to the densities, density backward of levels 0 and 1);
+  * `anneal_at(train_frac)` -> the train-time resampling exponent of the proposal sampler.
+
+The data loss, the shader's backward and the optimizer are not part of this row.
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List
+from typing import Dict, Iterable, List, Optional
 
 import numpy as np
+
+from .config import InterlevelConfig
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -47,3 +54,27 @@ def allreduce_grads(buffers: Iterable, average: bool = True, group=None) -> List
         if average:
             b.div_(world)
     return buffers
+
+
+def anneal_at(train_frac: float, cfg: InterlevelConfig = InterlevelConfig()) -> float:
+    """clip(bias(train_frac / anneal_end, anneal_slope), 0, anneal_clip), bias(x, s) = s x / ((s - 1) x + 1)
+    (Schlick's bias, internal/sampling.py:326-335).  anneal_at(1) = 0.4 = RenderConfig.anneal."""
+    x = float(train_frac) / cfg.anneal_end
+    s = cfg.anneal_slope
+    return float(min(max((s * x) / ((s - 1.0) * x + 1.0), 0.0), cfg.anneal_clip))
+
+
+def interlevel_grads(rc, rays, jitters, train_frac: float, lossmult=None, flats: Optional[List] = None,
+                     cfg: InterlevelConfig = InterlevelConfig(), levels=None):
+    """The spline interlevel loss of a batch and its gradients (rc_interlevel_backward).
+    rays: the ray dict of render_rays; jitters: per-level [n] sampler jitter (None = deterministic); train_frac sets
+    the anneal; lossmult: [n] or None; flats: per proposal level a flat gradient buffer to accumulate into (allocated
+    zeroed when None).  -> ({level: {tensor name: gradient view}}, flats, losses [num_levels - 1]) -- the flats are what
+    allreduce_grads averages across ranks; each rank's losses are its local batch mean."""
+    flats, losses = rc.interlevel_backward(rays, jitters, anneal_at(train_frac, cfg), cfg.mults, cfg.blurs, lossmult,
+                                           flats, levels)
+    grads = {}
+    for level, flat in enumerate(flats):
+        if flat is not None:
+            grads[level] = grads_as_dict(flat, rc.density_grad_layout(level)[0])
+    return grads, flats, losses
