@@ -285,7 +285,7 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * name = [prefix]<buffer>.  Prefix: none = set 0 (rc_render_rays on the first caller stream, rc_render_material,
  * rc_render_transient), "p1:" .. "p3:" = the sets of rc_render_rays on further caller streams, "s:" = the batched
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
- * "i:" = rc_interlevel_backward.
+ * "i:" = rc_interlevel_backward, "d:" = rc_data_backward.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -295,6 +295,11 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "i:": the training forward's per-level "sdist", "tdist", "means", "feat", "density", "weights" (levels 0 .. num_levels-1,
  * as above), and per proposal level 0 .. num_levels-2 "d_density" (d loss / d density, [n][S]) and "points" (the
  * means as [n S][3], the points of that level's density backward); "loss_ray" ([num_levels-1][n] per-ray sums).
+ * "d:": the training forward's buffers (the render-set names above) and "rgb" ([n][3] ray colour), "loss_ray" ([n]),
+ * "d_density" ([n S]), "d_rgbs" ([n S][3]), "points" ([n S][3]); of the last sample chunk of the shader backward
+ * (row-major per sample): "f96", "heads", "p3" (pred_raw), "ib_in", "x328", "s0", "s1", "sb", "i1", "i2", "io", "so", their
+ * gradients "dheads", "dio", "dso", "dsb", "dx328", "ds1", "ds0", "di2", "di1", "dib_in", "db128", "dp3", "df96", and
+ * "dfeat" ([C][64] d loss / d feature64), "dapp" ([C][32]), "part", "ones".
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -503,6 +508,29 @@ int rc_hashgrid_backward(rc_handle* h, int32_t grid_id, const float* points, int
 int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
                            float anneal, const float* mults, const float* blurs, float* const* grads, float* losses,
                            void* stream);
+
+/* Data loss of the cache pass and the exact gradients of the parameters it reaches (train_utils.compute_data_loss,
+ * internal/train_utils.py:402-528, loss_type 'charb' for the cache stage):
+ *   loss = mult * mean over the n x 3 channels of lossmult * sqrt((rgb - gt)^2 + charb_padding^2),
+ *   rgb  = the level-2 composite sum w rgb_s + max(0, 1 - acc) bg (render.py:172-247), no sRGB conversion.
+ * sdist carries no gradient (sampling.py:354-355): the loss reaches MLP_<num_levels-1> and Cache/Shader only.  One call:
+ *   1. the training forward: rc_render_rays' launch-per-stage cache pass (the rc_set_fused(0) plan; no analytic normals)
+ *      with the caller's jitter and `anneal` (as rc_interlevel_backward) on a workspace set of its own ("d:");
+ *   2. the loss (written to `loss`, a DEVICE float; bitwise reproducible) and d loss / d density, d loss / d rgb_s;
+ *   3-5. only when density_grads or shader_grads is given: the shader's recompute and backward, its weight gradients
+ *      (fixed reduction order), d feature += W_n^T d pred_raw, rc_density_backward of the last level into density_grads
+ *      (layout rc_density_grad_layout(num_levels-1)) and rc_hashgrid_backward of the appearance grid into its segment of
+ *      shader_grads (layout rc_shader_grad_layout).  Both are ACCUMULATED into.
+ * gt_rgb: [n,3] device; lossmult: [n] device or NULL (1).  Cache/Shader/EnvMap, SurfaceLightField/output_rgba_layer and
+ * the model-level Cache/EnvMap get an exact 0 and are not in the layout.  The reference counts the term twice ("main"
+ * and "cache_main", models.py:2065-2071); this call returns one copy, scaled by `mult`.  Everything is ordered on
+ * `stream`.  The last level must have <= 32 intervals (RC_ERR_UNSUPPORTED otherwise); the time-resolved cache handle is
+ * unsupported.  n == 0 returns RC_OK and writes nothing.  Buffers of the call: rc_workspace_ptr "d:" names. */
+int64_t rc_shader_grad_size(rc_handle* h);
+int rc_shader_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count);
+int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, const float* lossmult, int64_t n,
+                     const rc_randoms* rnd, float anneal, float charb_padding, float mult, float* density_grads,
+                     float* shader_grads, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

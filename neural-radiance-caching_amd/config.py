@@ -172,6 +172,16 @@ class InterlevelConfig:
     anneal_clip: float = 0.4
 
 
+@dataclasses.dataclass(frozen=True)
+class DataLossConfig:
+    """Training-time constants of the cache stage's data loss (train_utils.compute_data_loss, loss_type 'charb').
+    charb_padding: Config.charb_padding (internal/configs.py:330); loss_weight: MaterialModel.cache_loss_weight
+    (configs/ngp_yobo.gin:36); data_loss_mult: Config.data_loss_mult (ngp_yobo.gin:456)."""
+    charb_padding: float = 1e-3
+    loss_weight: float = 1.0
+    data_loss_mult: float = 1.0
+
+
 def hotdog_config(**overrides) -> RenderConfig:
     """configs/nerf_ngp_yobo_hotdog.gin resolved at render time (train=False)."""
     return dataclasses.replace(RenderConfig(), **overrides)

@@ -79,21 +79,30 @@ struct TrainWs { WsBuf feat, dfeat, a1, a2, d1, d2, fe, graw, density, partial; 
 // rc_interlevel_backward, beside its RenderWs (the training forward): per proposal level d loss / d density and the
 // sample means as points [n S][3]; the per-ray loss sums.
 struct InterlevelWs { WsBuf d_density[RC_MAX_LEVELS], points[RC_MAX_LEVELS]; WsBuf loss_ray; };
+// rc_data_backward, beside its RenderWs (the training forward): the ray rgb, per-ray loss sums, per-sample d loss / d
+// density and d loss / d rgb_s, the means as points [n S][3]; then one sample chunk of the shader backward
+// (rc_data_host.inc: recompute activations, their gradients, the weight-gradient K-slices and a column of ones).
+struct DataWs {
+  WsBuf rgb, loss_ray, d_density, d_rgbs, points;
+  WsBuf f96, heads, p3, ib_in, x328, s0, s1, sb, i1, i2, io, so;
+  WsBuf dheads, dio, dso, dsb, dx328, ds1, ds0, di2, di1, dib_in, db128, dp3, df96, dfeat, dapp, part, ones;
+};
 
 // Every workspace buffer by name, for rc_workspace_ptr ("<name>", per-level buffers "<name><level>") and rc_destroy.
 struct WsName {
   const char* name;
   WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
-  WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr;
+  WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr; WsBuf DataWs::*d = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
   constexpr WsName(const char* s, WsBuf TrainWs::*m) : name(s), t(m) {}
   constexpr WsName(const char* s, WsBuf InterlevelWs::*m) : name(s), i(m) {}
   constexpr WsName(const char* s, WsBuf (InterlevelWs::*m)[RC_MAX_LEVELS]) : name(s), ilv(m) {}
+  constexpr WsName(const char* s, WsBuf DataWs::*m) : name(s), d(m) {}
 };
 namespace wsn {
-using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs;
+using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -105,10 +114,14 @@ constexpr WsName kTable[] = {
     WS(X, sec_samples), WS(X, m_local_view), WS(X, sec_rgb), WS(X, sec_acc), WS(X, sec_env), WS(X, sh_origins), WS(X, sh_dirs),
     WS(X, sh_near), WS(X, sh_far), WS(X, sh_normals), WS(X, sh_lights), WS(X, sh_acc),
     WS(T, feat), WS(T, dfeat), WS(T, a1), WS(T, a2), WS(T, d1), WS(T, d2), WS(T, fe), WS(T, graw), WS(T, density), WS(T, partial),
-    WS(I, d_density), WS(I, points), WS(I, loss_ray)};
+    WS(I, d_density), WS(I, points), WS(I, loss_ray),
+    WS(D, rgb), WS(D, loss_ray), WS(D, d_density), WS(D, d_rgbs), WS(D, points), WS(D, f96), WS(D, heads), WS(D, p3),
+    WS(D, ib_in), WS(D, x328), WS(D, s0), WS(D, s1), WS(D, sb), WS(D, i1), WS(D, i2), WS(D, io), WS(D, so), WS(D, dheads),
+    WS(D, dio), WS(D, dso), WS(D, dsb), WS(D, dx328), WS(D, ds1), WS(D, ds0), WS(D, di2), WS(D, di1), WS(D, dib_in),
+    WS(D, db128), WS(D, dp3), WS(D, df96), WS(D, dfeat), WS(D, dapp), WS(D, part), WS(D, ones)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I), "the table lists every workspace buffer");
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D), "the table lists every workspace buffer");
 }  // namespace wsn
 
 constexpr int kEvSlots = 16;
@@ -145,6 +158,8 @@ struct rc_handle {
   bool packed_dirty = true;
   uint64_t layers_gen = 1;                   // bumped whenever a dense layer is (re)loaded
   uint64_t train_gen[RC_MAX_LEVELS] = {};    // layers_gen the training stream of a level was packed at
+  uint64_t data_gen = 0;                     // layers_gen data_w was uploaded at
+  DevBuf data_w;                             // rc_data_backward: the shader's dense layers on the Flax layout
   bool have_envmap = false;
   bool have_material = false;
   // packed MFMA fragments (device)
@@ -153,15 +168,17 @@ struct rc_handle {
   // Workspace sets.  ws[0..3] serve rc_render_rays, one per caller stream so that independent batches enqueued on
   // different streams overlap (the least recently used one is taken over when a fifth stream shows up); ws[0] also serves
   // rc_render_material / rc_render_transient, with ws_x and with ws_sec for their batched secondary trace; ws_train serves
-  // rc_density_backward; ws_il + ws_ilx serve rc_interlevel_backward.  groups[0..3] / groups[4] / groups[5] record who used
-  // a render set / the train set / the interlevel set last: a call whose stream differs from the set's previous user first
-  // waits for that user's last call (event), so two streams never run on one set at the same time.
-  RenderWs ws[4], ws_sec, ws_il;
+  // rc_density_backward; ws_il + ws_ilx serve rc_interlevel_backward; ws_d + ws_dx serve rc_data_backward.  groups[0..3] /
+  // groups[4] / groups[5] / groups[6] record who used a render set / the train set / the interlevel set / the data set
+  // last: a call whose stream differs from the set's previous user first waits for that user's last call (event), so two
+  // streams never run on one set at the same time.
+  RenderWs ws[4], ws_sec, ws_il, ws_d;
   ExtraWs ws_x;
   TrainWs ws_train;
   InterlevelWs ws_ilx;
+  DataWs ws_dx;
   struct WsGroup { hipStream_t stream = nullptr; bool used = false; hipEvent_t done = nullptr; uint64_t last_use = 0; };
-  WsGroup groups[6];
+  WsGroup groups[7];
   uint64_t use_clock = 0;
   // profiling: ring of event sets, one set per render call (slot = call % kEvSlots)
   // mode 0 off, 1 every stage, 2 only the dominant kernel (cache shader), 3 like 2 on every 8th call
@@ -776,7 +793,7 @@ int ensure_workspace(rc_handle* h, RenderWs& w, int64_t n) {
 
 void free_workspace(rc_handle* h) {
   for (const WsName& e : wsn::kTable) {
-    for (RenderWs* r : {&h->ws[0], &h->ws[1], &h->ws[2], &h->ws[3], &h->ws_sec, &h->ws_il}) {
+    for (RenderWs* r : {&h->ws[0], &h->ws[1], &h->ws[2], &h->ws[3], &h->ws_sec, &h->ws_il, &h->ws_d}) {
       if (e.r) free_buf(r->*e.r);
       if (e.lv) for (WsBuf& b : r->*e.lv) free_buf(b);
     }
@@ -784,22 +801,24 @@ void free_workspace(rc_handle* h) {
     if (e.t) free_buf(h->ws_train.*e.t);
     if (e.i) free_buf(h->ws_ilx.*e.i);
     if (e.ilv) for (WsBuf& b : h->ws_ilx.*e.ilv) free_buf(b);
+    if (e.d) free_buf(h->ws_dx.*e.d);
   }
 }
 
-// rc_workspace_ptr: "[p1:|p2:|p3:|s:|t:|i:]<name>[level]" -> the buffer (nullptr for an unknown name)
+// rc_workspace_ptr: "[p1:|p2:|p3:|s:|t:|i:|d:]<name>[level]" -> the buffer (nullptr for an unknown name)
 WsBuf* ws_find(rc_handle* h, const char* name) {
   const char* colon = strchr(name, ':');
   const std::string pre = colon ? std::string(name, colon + 1) : "", leaf = colon ? colon + 1 : name;
-  const char* const kPre[7] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:"};
-  int set = -1;      // 0-3 rc_render_rays' sets (0 with the extras), 4 the secondary set, 5 the train set, 6 the interlevel set
-  for (int i = 0; i < 7; ++i) if (pre == kPre[i]) set = i;
-  RenderWs* r = set < 0 || set == 5 ? nullptr : (set == 6 ? &h->ws_il : set == 4 ? &h->ws_sec : &h->ws[set]);
+  const char* const kPre[8] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:"};
+  int set = -1;      // 0-3 rc_render_rays' sets (0 with the extras), 4 the secondary set, 5 the train set, 6 the interlevel set,
+                     // 7 the data-loss set
+  for (int i = 0; i < 8; ++i) if (pre == kPre[i]) set = i;
+  RenderWs* r = set < 0 || set == 5 ? nullptr : (set == 7 ? &h->ws_d : set == 6 ? &h->ws_il : set == 4 ? &h->ws_sec : &h->ws[set]);
   for (const WsName& e : wsn::kTable) {
     const size_t k = strlen(e.name);
     if (leaf.compare(0, k, e.name) != 0) continue;
-    if (leaf.size() == k && ((e.r && r) || (e.x && set == 0) || (e.t && set == 5) || (e.i && set == 6)))
-      return e.r ? &(r->*e.r) : e.x ? &(h->ws_x.*e.x) : e.t ? &(h->ws_train.*e.t) : &(h->ws_ilx.*e.i);
+    if (leaf.size() == k && ((e.r && r) || (e.x && set == 0) || (e.t && set == 5) || (e.i && set == 6) || (e.d && set == 7)))
+      return e.r ? &(r->*e.r) : e.x ? &(h->ws_x.*e.x) : e.t ? &(h->ws_train.*e.t) : e.i ? &(h->ws_ilx.*e.i) : &(h->ws_dx.*e.d);
     const bool digit = leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels;
     if (e.lv && r && digit) return &(r->*e.lv)[leaf[k] - '0'];
     if (e.ilv && set == 6 && digit && leaf[k] < '0' + h->cfg.num_levels - 1) return &(h->ws_ilx.*e.ilv)[leaf[k] - '0'];
@@ -971,6 +990,7 @@ void rc_destroy(rc_handle* h) {
   free_packs(h->packs);
   free_workspace(h);
   if (h->ide_table.p) (void)hipFree(h->ide_table.p);
+  free_buf(h->data_w);
   drop_graphs(h);
   for (auto& G : h->groups) if (G.done) (void)hipEventDestroy(G.done);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -1820,3 +1840,4 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_transient_host.inc"
 #include "rc_train_host.inc"
 #include "rc_interlevel_host.inc"
+#include "rc_data_host.inc"

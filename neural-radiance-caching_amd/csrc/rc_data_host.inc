@@ -1,0 +1,294 @@
+// Host side of rc_data_backward (rc_data.hip); included by rc_api.hip after rc_interlevel_host.inc.
+//
+// One call = the training forward (enqueue_all's launch-per-stage cache pass on the data set ws_d, the caller's jitter and
+// anneal) -> k_data_loss_bwd (per-ray charb sums, d loss / d density and d loss / d rgb_s of every last-level sample) ->
+// k_interlevel_reduce (the loss, fixed order) -> with a gradient buffer, per chunk of kDataChunk samples: the shader
+// recompute and backward as dense layers on k_gemm, their weight gradients (K = the chunk's samples, fixed slices),
+// d feature64 += W_n^T d pred_raw, rc_density_backward of the last level and rc_hashgrid_backward of the appearance grid.
+
+namespace {
+
+constexpr int64_t kDataChunk = 32768;      // samples per chunk of the shader backward (bounds its workspace)
+constexpr int64_t kDataKSlice = 1024;      // samples per K slice of a weight gradient
+
+// The dense layers of the shader layout (pred_normals_layer first, the appearance tables between it and the rest).
+enum { DL_PRED, DL_BOTT, DL_ROUGH, DL_AMB, DL_TINT, DL_IRR, DL_I0, DL_I1, DL_IO, DL_S0, DL_S1, DL_S2, DL_SB, DL_SO, DL_COUNT };
+struct DataLayer { const char* name; int in, out; };
+constexpr DataLayer kDataLayers[DL_COUNT] = {
+    {"pred_normals_layer", 64, 3},           {"bottleneck_layer", 96, 128},     {"roughness_layer", 96, 1},
+    {"ambient_irradiance_layer", 96, 3},     {"tint_layer", 96, 3},             {"irradiance_layer", 96, 3},
+    {"integrated_brdf_layers_0", 129, 64},   {"integrated_brdf_layers_1", 64, 64}, {"output_integrated_brdf_layer", 64, 1},
+    {"SurfaceLightField/layer_0", 200, 128}, {"SurfaceLightField/layer_1", 128, 128}, {"SurfaceLightField/layer_2", 128, 128},
+    {"SurfaceLightField/layer_bottleneck", 328, 128}, {"SurfaceLightField/output_ambient_rgb_layer", 128, 3}};
+
+std::string data_layer_path(rc_handle* h, int i) {
+  return i == DL_PRED ? "params/Cache/Sampler/MLP_" + std::to_string(h->cfg.num_levels - 1) + "/pred_normals_layer"
+                      : std::string("params/Cache/Shader/") + kDataLayers[i].name;
+}
+
+// Segments of the shader gradient buffer; kernel_seg[i] = index of layer i's kernel segment (its bias follows).
+std::vector<GradSeg> shader_grad_segments(rc_handle* h, int* kernel_seg = nullptr, int64_t* app_off = nullptr) {
+  std::vector<GradSeg> v;
+  int64_t off = 0;
+  for (int i = 0; i < DL_COUNT; ++i) {
+    if (i == DL_BOTT) {
+      if (app_off) *app_off = off;
+      for (const GradSeg& g : grid_grad_segments(h->grids[3], off)) v.push_back(g);
+    }
+    if (kernel_seg) kernel_seg[i] = (int)v.size();
+    const std::string base = data_layer_path(h, i);
+    GradSeg k{}; k.name = base + "/kernel"; k.offset = off; k.size = (int64_t)kDataLayers[i].in * kDataLayers[i].out; k.ndim = 2;
+    k.shape[0] = kDataLayers[i].in; k.shape[1] = kDataLayers[i].out; off += k.size; v.push_back(k);
+    GradSeg b{}; b.name = base + "/bias"; b.offset = off; b.size = kDataLayers[i].out; b.ndim = 1; b.shape[0] = kDataLayers[i].out;
+    off += b.size; v.push_back(b);
+  }
+  return v;
+}
+
+// data_w: every layer's kernel [in, out] then bias, in layer order; offsets into it
+int64_t data_w_offset(int i) {
+  int64_t o = 0;
+  for (int k = 0; k < i; ++k) o += (int64_t)kDataLayers[k].in * kDataLayers[k].out + kDataLayers[k].out;
+  return o;
+}
+
+int upload_data_weights(rc_handle* h) {
+  std::string missing;
+  std::vector<float> v;
+  for (int i = 0; i < DL_COUNT; ++i) {
+    const HostLayer* L = need(h, data_layer_path(h, i), missing);
+    if (!L) continue;
+    if (L->in != kDataLayers[i].in || L->out != kDataLayers[i].out)
+      return fail(h, RC_ERR_UNSUPPORTED, "rc_data_backward: unexpected shape of " + data_layer_path(h, i));
+    v.insert(v.end(), L->kernel.begin(), L->kernel.end());
+    v.insert(v.end(), L->bias.begin(), L->bias.end());
+  }
+  if (!missing.empty()) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: " + missing);
+  return upload(h, h->data_w, v);
+}
+
+}  // namespace
+
+int64_t rc_shader_grad_size(rc_handle* h) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_shader_grad_size: not available on a time-resolved cache handle");
+  const std::vector<GradSeg> v = shader_grad_segments(h);
+  return v.back().offset + v.back().size;
+  RC_CATCH(h)
+}
+
+int rc_shader_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  if (!count) return fail(h, RC_ERR_INVALID_ARG, "rc_shader_grad_layout: null count");
+  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_shader_grad_layout: not available on a time-resolved cache handle");
+  const std::vector<GradSeg> v = shader_grad_segments(h);
+  *count = (int32_t)v.size();
+  if (!segs) return RC_OK;
+  if (capacity < (int32_t)v.size()) return fail(h, RC_ERR_INVALID_ARG, "rc_shader_grad_layout: capacity too small");
+  for (size_t i = 0; i < v.size(); ++i) {
+    memset(&segs[i], 0, sizeof(rc_grad_segment));
+    snprintf(segs[i].name, sizeof(segs[i].name), "%s", v[i].name.c_str());
+    segs[i].offset = v[i].offset; segs[i].size = v[i].size; segs[i].ndim = v[i].ndim;
+    for (int d = 0; d < 4; ++d) segs[i].shape[d] = v[i].shape[d];
+  }
+  return RC_OK;
+  RC_CATCH(h)
+}
+
+int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, const float* lossmult, int64_t n,
+                     const rc_randoms* rnd, float anneal, float charb_padding, float mult, float* density_grads,
+                     float* shader_grads, float* loss, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const rc_config& c = h->cfg;
+  const int NL = c.num_levels;
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: negative n_rays");
+  if (!rays) return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: null rays");
+  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: anneal must be finite and >= 0");
+  if (!std::isfinite(charb_padding) || !std::isfinite(mult)) return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: charb_padding and mult must be finite");
+  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_data_backward: not available on a time-resolved cache handle");
+  if (n == 0) return RC_OK;
+  if (!gt_rgb || !loss) return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: null gt_rgb/loss");
+  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
+    return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: origins/directions/viewdirs/near/far are required");
+  const int S2 = c.num_samples[NL - 1];
+  if (S2 < 1 || S2 > 32) return fail(h, RC_ERR_UNSUPPORTED, "rc_data_backward: needs <= 32 samples on the last level");
+  if (h->grids[NL - 1].dev.num_levels * h->grids[NL - 1].dev.num_features != 32 ||
+      h->grids[3].dev.num_levels * h->grids[3].dev.num_features != 32)
+    return fail(h, RC_ERR_UNSUPPORTED, "rc_data_backward: needs 32 features on the last density grid and the appearance grid");
+  RoctxScope roctx_call("rc_data_backward");
+  RC_HIP(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream_v;
+  int rc;
+  if (h->packed_dirty) {
+    drop_graphs(h);
+    if ((rc = repack(h))) return rc;
+  }
+  const bool grads = density_grads || shader_grads;
+  if (grads && h->data_gen != h->layers_gen) {
+    if ((rc = upload_data_weights(h))) return rc;
+    h->data_gen = h->layers_gen;
+  }
+  if ((rc = ws_enter(h, 6, st))) return rc;             // the data set: ordered against its previous user
+  WsLeave leave{h, 6, st, true};
+  RenderWs& w = h->ws_d;
+  DataWs& x = h->ws_dx;
+  const int64_t np = n * S2;
+  if ((rc = ensure_workspace(h, w, n)) || (rc = ws_alloc(h, x.rgb, 3 * n)) || (rc = ws_alloc(h, x.loss_ray, n)) ||
+      (rc = ws_alloc(h, x.d_density, np)) || (rc = ws_alloc(h, x.d_rgbs, 3 * np)))
+    return rc;
+
+  // 1. the training forward: rc_render_rays' launch-per-stage cache pass, no analytic normals
+  RenderArgs A{};
+  A.rays = *rays;
+  A.have_rnd = rnd != nullptr;
+  if (rnd) A.rnd = *rnd;
+  A.n = n; A.mask = RC_PASS_CACHE; A.slot = -1; A.fused = false; A.anneal = anneal;
+  A.out.ptr[RC_OUT_RGB] = x.rgb.p;
+  enqueue_all(h, A, w, st);
+
+  // 2. the charb term, d loss / d rgb_s and d loss / d density
+  RcDataLossArgs la{};
+  la.n = n; la.S = S2; la.rgb = x.rgb.p; la.gt = gt_rgb; la.lossmult = lossmult;
+  la.weights = w.weights[NL - 1].p; la.density = w.density[NL - 1].p; la.tdist = w.tdist[NL - 1].p; la.shade = w.shade.p;
+  la.directions = rays->directions; la.bg = c.bg_intensity; la.padding = charb_padding;
+  la.coef = (float)((double)mult / (3.0 * (double)n));
+  la.loss_ray = x.loss_ray.p; la.d_density = x.d_density.p; la.d_rgbs = x.d_rgbs.p;
+  rc_launch_data_loss_bwd(la, st);
+  RcInterlevelReduce rr{};
+  rr.mult[0] = mult; rr.count[0] = 3.0 * (double)n;
+  rc_launch_interlevel_reduce(x.loss_ray.p, n, 1, rr, loss, st);
+  RC_HIP(h, hipGetLastError());
+  if (!grads) return RC_OK;
+
+  // 3-5. the shader backward, chunk by chunk
+  const int64_t CH = np < kDataChunk ? np : kDataChunk;
+  const int64_t nslices = (CH + kDataKSlice - 1) / kDataKSlice;
+  struct { WsBuf* b; int64_t per; } bufs[] = {
+      {&x.f96, 96}, {&x.heads, 10}, {&x.p3, 3}, {&x.ib_in, 129}, {&x.x328, 328}, {&x.s0, 128}, {&x.s1, 128}, {&x.sb, 128},
+      {&x.i1, 64}, {&x.i2, 64}, {&x.io, 1}, {&x.so, 3}, {&x.dheads, 10}, {&x.dio, 1}, {&x.dso, 3}, {&x.dsb, 128},
+      {&x.dx328, 328}, {&x.ds1, 128}, {&x.ds0, 128}, {&x.di2, 64}, {&x.di1, 64}, {&x.dib_in, 129}, {&x.db128, 128},
+      {&x.dp3, 3}, {&x.df96, 96}, {&x.dfeat, 64}, {&x.dapp, 32}};
+  for (auto& e : bufs)
+    if ((rc = ws_alloc(h, *e.b, CH * e.per))) return rc;
+  if ((rc = ws_alloc(h, x.part, nslices * 328 * 128)) || (rc = ws_alloc(h, x.ones, 1)) || (rc = ws_alloc(h, x.points, 3 * np)))
+    return rc;
+  RC_HIP(h, hipMemsetD32Async((hipDeviceptr_t)x.ones.p, 0x3f800000, 1, st));     // 1.0f: the A operand of a bias gradient
+  rc_launch_points_aos(w.means[NL - 1].p, np, x.points.p, st);
+  int kseg[DL_COUNT];
+  int64_t app_off = 0;
+  const std::vector<GradSeg> segs = shader_grad_segments(h, kseg, &app_off);
+  const float* W = h->data_w.p;
+  auto Wk = [&](int l) { return W + data_w_offset(l); };
+  auto Wb = [&](int l) { return W + data_w_offset(l) + (int64_t)kDataLayers[l].in * kDataLayers[l].out; };
+
+  for (int64_t c0 = 0; c0 < np; c0 += CH) {
+    const int64_t C = np - c0 < CH ? np - c0 : CH;
+    // Y[:, j0 ..] = X W (+ b); X [C][in] row stride ldx, Y row stride ldy
+    auto fwd = [&](int l, const float* X, int64_t ldx, float* Y, int64_t ldy, bool relu) {
+      RcGemmArgs g{};
+      g.M = (int)C; g.N = kDataLayers[l].out; g.K = kDataLayers[l].in;
+      g.a = X; g.sai = ldx; g.sak = 1; g.b = Wk(l); g.sbk = kDataLayers[l].out; g.sbj = 1;
+      g.c = Y; g.sci = ldy; g.scj = 1; g.bias = Wb(l); g.relu = relu ? 1 : 0; g.kslice = g.K;
+      rc_launch_gemm(g, 1, st);
+    };
+    // dX[:, cols j0 .. j0 + nj) (+)= dY W^T, zero where mask <= 0 (the forward's ReLU output)
+    auto bwd = [&](int l, const float* dY, int64_t ldy, float* dX, int64_t ldx, int j0, int nj, const float* mask, int64_t ldm,
+                   bool accumulate) {
+      RcGemmArgs g{};
+      g.M = (int)C; g.N = nj; g.K = kDataLayers[l].out;
+      g.a = dY; g.sai = ldy; g.sak = 1; g.b = Wk(l) + (int64_t)j0 * kDataLayers[l].out; g.sbk = 1; g.sbj = kDataLayers[l].out;
+      g.c = dX + j0; g.sci = ldx; g.scj = 1; g.mask = mask ? mask + j0 : nullptr; g.smi = ldm; g.smj = 1;
+      g.accumulate = accumulate ? 1 : 0; g.kslice = g.K;
+      rc_launch_gemm(g, 1, st);
+    };
+    // grads[kernel] += X^T dY, grads[bias] += column sums of dY: K = the chunk's samples in fixed slices
+    auto wgrad = [&](int l, const float* X, int64_t ldx, const float* dY, int64_t ldy) {
+      const int in = kDataLayers[l].in, out = kDataLayers[l].out;
+      const int64_t Z = (C + kDataKSlice - 1) / kDataKSlice;
+      for (int pass = 0; pass < 2; ++pass) {
+        RcGemmArgs g{};
+        g.M = pass == 0 ? in : 1; g.N = out; g.K = C;
+        g.a = pass == 0 ? X : x.ones.p; g.sai = pass == 0 ? 1 : 0; g.sak = pass == 0 ? ldx : 0;
+        g.b = dY; g.sbk = ldy; g.sbj = 1; g.c = x.part.p; g.sci = out; g.scj = 1;
+        g.kslice = kDataKSlice; g.spart = (int64_t)g.M * out;
+        rc_launch_gemm(g, (int)Z, st);
+        rc_launch_sum_parts(x.part.p, (int)Z, g.spart, shader_grads + segs[kseg[l] + pass].offset, st);
+      }
+    };
+    RcShaderBwdArgs sa{};
+    sa.C = C; sa.c0 = c0; sa.np = np; sa.S = S2;
+    sa.hbuf = w.hbuf.p; sa.app = w.app.p; sa.viewdirs = rays->viewdirs;
+    sa.ide = reinterpret_cast<const RcIdeTable*>(h->ide_table.p);
+    sa.roughness_bias = c.roughness_bias; sa.ambient_bias = c.ambient_irradiance_bias; sa.irradiance_bias = c.irradiance_bias;
+    sa.slf_ambient_bias = c.slf_ambient_bias; sa.rgb_max = c.rgb_max; sa.d_rgbs = x.d_rgbs.p;
+    sa.f96 = x.f96.p; sa.heads = x.heads.p; sa.p3 = x.p3.p; sa.ib_in = x.ib_in.p; sa.x328 = x.x328.p; sa.io = x.io.p; sa.so = x.so.p;
+    sa.dheads = x.dheads.p; sa.dio = x.dio.p; sa.dso = x.dso.p; sa.dib_in = x.dib_in.p; sa.dx328 = x.dx328.p;
+    sa.db128 = x.db128.p; sa.dp3 = x.dp3.p;
+
+    // recompute: feature96, heads, pred_raw, bottleneck, IDE, integrated BRDF, SLF
+    rc_launch_shader_stage(sa, 0, st);
+    fwd(DL_ROUGH, x.f96.p, 96, x.heads.p + 0, 10, false);
+    fwd(DL_AMB, x.f96.p, 96, x.heads.p + 1, 10, false);
+    fwd(DL_TINT, x.f96.p, 96, x.heads.p + 4, 10, false);
+    fwd(DL_IRR, x.f96.p, 96, x.heads.p + 7, 10, false);
+    fwd(DL_PRED, x.f96.p, 96, x.p3.p, 3, false);
+    fwd(DL_BOTT, x.f96.p, 96, x.x328.p + 128, 328, false);
+    fwd(DL_BOTT, x.f96.p, 96, x.ib_in.p, 129, false);
+    rc_launch_shader_stage(sa, 1, st);
+    fwd(DL_I0, x.ib_in.p, 129, x.i1.p, 64, true);
+    fwd(DL_I1, x.i1.p, 64, x.i2.p, 64, true);
+    fwd(DL_IO, x.i2.p, 64, x.io.p, 1, false);
+    fwd(DL_S0, x.x328.p + 128, 328, x.s0.p, 128, true);
+    fwd(DL_S1, x.s0.p, 128, x.s1.p, 128, true);
+    fwd(DL_S2, x.s1.p, 128, x.x328.p, 328, true);
+    fwd(DL_SB, x.x328.p, 328, x.sb.p, 128, true);
+    fwd(DL_SO, x.sb.p, 128, x.so.p, 3, false);
+    // backward
+    rc_launch_shader_stage(sa, 2, st);
+    bwd(DL_SO, x.dso.p, 3, x.dsb.p, 128, 0, 128, x.sb.p, 128, false);
+    bwd(DL_SB, x.dsb.p, 128, x.dx328.p, 328, 0, 128, x.x328.p, 328, false);
+    bwd(DL_SB, x.dsb.p, 128, x.dx328.p, 328, 128, 200, nullptr, 0, false);
+    bwd(DL_S2, x.dx328.p, 328, x.ds1.p, 128, 0, 128, x.s1.p, 128, false);
+    bwd(DL_S1, x.ds1.p, 128, x.ds0.p, 128, 0, 128, x.s0.p, 128, false);
+    bwd(DL_S0, x.ds0.p, 128, x.dx328.p + 128, 328, 0, 200, nullptr, 0, true);
+    bwd(DL_IO, x.dio.p, 1, x.di2.p, 64, 0, 64, x.i2.p, 64, false);
+    bwd(DL_I1, x.di2.p, 64, x.di1.p, 64, 0, 64, x.i1.p, 64, false);
+    bwd(DL_I0, x.di1.p, 64, x.dib_in.p, 129, 0, 129, nullptr, 0, false);
+    rc_launch_shader_stage(sa, 3, st);
+    bwd(DL_BOTT, x.db128.p, 128, x.df96.p, 96, 0, 96, nullptr, 0, false);
+    bwd(DL_ROUGH, x.dheads.p + 0, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
+    bwd(DL_AMB, x.dheads.p + 1, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
+    bwd(DL_TINT, x.dheads.p + 4, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
+    bwd(DL_IRR, x.dheads.p + 7, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
+    bwd(DL_PRED, x.dp3.p, 3, x.df96.p, 96, 0, 64, nullptr, 0, true);
+    rc_launch_split_feature(x.df96.p, C, x.dfeat.p, x.dapp.p, st);
+    RC_HIP(h, hipGetLastError());
+    if (shader_grads) {
+      wgrad(DL_PRED, x.f96.p, 96, x.dp3.p, 3);
+      wgrad(DL_BOTT, x.f96.p, 96, x.db128.p, 128);
+      wgrad(DL_ROUGH, x.f96.p, 96, x.dheads.p + 0, 10);
+      wgrad(DL_AMB, x.f96.p, 96, x.dheads.p + 1, 10);
+      wgrad(DL_TINT, x.f96.p, 96, x.dheads.p + 4, 10);
+      wgrad(DL_IRR, x.f96.p, 96, x.dheads.p + 7, 10);
+      wgrad(DL_I0, x.ib_in.p, 129, x.di1.p, 64);
+      wgrad(DL_I1, x.i1.p, 64, x.di2.p, 64);
+      wgrad(DL_IO, x.i2.p, 64, x.dio.p, 1);
+      wgrad(DL_S0, x.x328.p + 128, 328, x.ds0.p, 128);
+      wgrad(DL_S1, x.s0.p, 128, x.ds1.p, 128);
+      wgrad(DL_S2, x.s1.p, 128, x.dx328.p, 328);
+      wgrad(DL_SB, x.x328.p, 328, x.dsb.p, 128);
+      wgrad(DL_SO, x.sb.p, 128, x.dso.p, 3);
+      RC_HIP(h, hipGetLastError());
+      if ((rc = rc_hashgrid_backward(h, 3, x.points.p + 3 * c0, C, x.dapp.p, shader_grads + app_off, 1, stream_v))) return rc;
+    }
+    if (density_grads &&
+        (rc = rc_density_backward(h, NL - 1, x.points.p + 3 * c0, C, x.d_density.p + c0, x.dfeat.p, density_grads, nullptr, stream_v)))
+      return rc;
+  }
+  RC_HIP(h, hipGetLastError());
+  return RC_OK;
+  RC_CATCH(h)
+}

@@ -465,6 +465,46 @@ void rc_launch_interlevel_reduce(const float* loss_ray, int64_t n, int levels, c
                                  hipStream_t stream);
 void rc_launch_points_aos(const float* soa, int64_t np, float* aos, hipStream_t stream);
 
+// Data loss of the cache pass and the shader backward (rc_data.hip)
+struct RcDataLossArgs {
+  int64_t n; int S;                        // rays, last-level intervals (<= 32)
+  const float* rgb;                        // [n][3] the composite
+  const float* gt;                         // [n][3]
+  const float* lossmult;                   // [n] or nullptr (1)
+  const float* weights, * density, * tdist, * shade, * directions;   // the training forward's last level
+  float bg, padding, coef;                 // background, charb padding, mult / (3 n)
+  float* loss_ray;                         // [n] per-ray sums of lossmult * charb, written
+  float* d_density;                        // [n S] written
+  float* d_rgbs;                           // [n S][3] d L / d rgb_s, written
+};
+// C(i, j) (+)= sum_k A(i, k) B(k, j) (+ bias[j]), then ReLU, then zero where mask(i, j) <= 0.  A(i, k) = a[i sai + k sak],
+// B(k, j) = b[k sbk + j sbj], C(i, j) = c[i sci + j scj] (+ z spart for K slice z of kslice values).
+struct RcGemmArgs {
+  int M, N; int64_t K;
+  const float* a; int64_t sai, sak;
+  const float* b; int64_t sbk, sbj;
+  float* c; int64_t sci, scj;
+  const float* bias;
+  const float* mask; int64_t smi, smj;
+  int relu, accumulate;
+  int64_t kslice, spart;
+};
+// One chunk of C samples (global index c0 + p) of the shader backward: row-major per-sample buffers.
+struct RcShaderBwdArgs {
+  int64_t C, c0, np; int S;
+  const float* hbuf, * app, * viewdirs;    // the training forward (hbuf: accumulator order, app: [32][np])
+  const RcIdeTable* ide;
+  float roughness_bias, ambient_bias, irradiance_bias, slf_ambient_bias, rgb_max;
+  const float* d_rgbs;                     // [np][3]
+  float* f96, * heads, * p3, * ib_in, * x328, * io, * so;                     // recompute
+  float* dheads, * dio, * dso, * dib_in, * dx328, * db128, * dp3;             // gradients
+};
+void rc_launch_data_loss_bwd(const RcDataLossArgs& a, hipStream_t st);
+void rc_launch_gemm(const RcGemmArgs& a, int kparts, hipStream_t st);
+void rc_launch_sum_parts(const float* part, int nparts, int64_t count, float* out, hipStream_t st);
+void rc_launch_shader_stage(const RcShaderBwdArgs& a, int which, hipStream_t st);   // 0 stage, 1 glue fwd, 2 out bwd, 3 glue bwd
+void rc_launch_split_feature(const float* df96, int64_t C, float* dfeat, float* dapp, hipStream_t st);
+
 // Random fill (rc_prng.hip)
 enum { RC_PRNG_BITS = 0, RC_PRNG_UNIFORM = 1, RC_PRNG_NORMAL = 2, RC_PRNG_GUMBEL = 3 };
 struct RcPrngArgs {

@@ -152,6 +152,7 @@ EXPORTS = (
     "rc_stage_name", "rc_stage_times_ms", "rc_set_graph_mode", "rc_set_fused", "rc_render_material", "rc_set_transient", "rc_render_transient", "rc_cast_rays",
     "rc_prng_fill", "rc_density_grad_size", "rc_density_grad_layout", "rc_density_backward",
     "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs", "rc_interlevel_backward",
+    "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward",
 )
 
 _LIB = None
@@ -250,6 +251,13 @@ def load_library():
                                            C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.c_void_p,
                                            C.c_void_p]
     lib.rc_interlevel_backward.restype = C.c_int
+    lib.rc_shader_grad_size.argtypes = [C.c_void_p]
+    lib.rc_shader_grad_size.restype = C.c_int64
+    lib.rc_shader_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.rc_shader_grad_layout.restype = C.c_int
+    lib.rc_data_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
+                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_data_backward.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -573,6 +581,19 @@ class RadianceCache:
             self._check(total)
         return out, total
 
+    def shader_grad_layout(self):
+        """rc_shader_grad_layout: [(tensor name, offset, shape)] of the gradient buffer of the data loss's shader side
+        (MLP_<last>/pred_normals_layer, the appearance-grid tables, the Cache/Shader dense layers), and its size."""
+        cnt = C.c_int32()
+        self._check(self.lib.rc_shader_grad_layout(self._h, None, 0, C.byref(cnt)))
+        segs = (rc_grad_segment * cnt.value)()
+        self._check(self.lib.rc_shader_grad_layout(self._h, segs, cnt.value, C.byref(cnt)))
+        out = [(s.name.decode(), int(s.offset), tuple(int(v) for v in s.shape[: s.ndim])) for s in segs]
+        total = int(self.lib.rc_shader_grad_size(self._h))
+        if total < 0:
+            self._check(total)
+        return out, total
+
     def hashgrid_grad_layout(self, grid_id: int):
         """rc_hashgrid_grad_layout: [(tensor name, offset, shape)] of the table-gradient buffer of a grid, and its size."""
         cnt, total = C.c_int32(), C.c_int64()
@@ -689,6 +710,62 @@ class RadianceCache:
                                                     float(anneal), m, b, ptrs, losses.data_ptr(), stream))
         self._keep = [held]
         return flats, losses
+
+    def _jitter_struct(self, jitters, held, n):
+        if jitters is None:
+            return None
+        rnd = rc_randoms()
+        for l, j in enumerate(jitters):
+            if j is not None:
+                t = self._dev(j).reshape(-1)
+                if t.shape[0] != n:
+                    raise ValueError(f"jitter of level {l} has {t.shape[0]} values, expected {n}")
+                held[f"jit{l}"] = t
+                rnd.jitter[l] = t.data_ptr()
+        held["rnd"] = rnd
+        return C.byref(rnd)
+
+    def data_backward(self, rays: Dict[str, object], rgb, jitters=None, anneal: float = 0.4, lossmult=None,
+                      charb_padding: float = 1e-3, mult: float = 1.0, grads=None):
+        """rc_data_backward: the charb data loss of the cache pass against target colours `rgb` [n, 3] and its
+        gradient w.r.t. the last density level (density_grad_layout(num_levels - 1)) and the shader side
+        (shader_grad_layout).  jitters / anneal as interlevel_backward; lossmult: [n] or None (1).  grads: (density
+        flat, shader flat) to accumulate into, either None (allocated zeroed); grads=False computes the loss only.
+        Returns ((density flat, shader flat), loss [1] cuda tensor); one copy of the term (the reference adds it twice)."""
+        torch = self._torch
+        r, held, n = self._rays_struct(rays)
+        rnd_p = self._jitter_struct(jitters, held, n)
+        gt = self._dev(rgb).reshape(-1, 3).contiguous()
+        if gt.shape[0] != n:
+            raise ValueError("rgb must be [n, 3]")
+        held["gt"] = gt
+        lm = None
+        if lossmult is not None:
+            lm = self._dev(lossmult).reshape(-1)
+            if lm.shape[0] != n:
+                raise ValueError("lossmult must have one value per ray")
+            held["lossmult"] = lm
+        flats = [None, None]
+        if grads is not False:
+            sizes = (int(self.lib.rc_density_grad_size(self._h, self.cfg.num_levels - 1)), int(self.lib.rc_shader_grad_size(self._h)))
+            given = list(grads) if grads is not None else [None, None]
+            for i, total in enumerate(sizes):
+                if total < 0:
+                    self._check(total)
+                f = given[i]
+                if f is None:
+                    f = torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
+                elif f.numel() != total or f.dtype != torch.float32 or not f.is_cuda or not f.is_contiguous():
+                    raise ValueError(f"grads[{i}] must be a contiguous float32 cuda tensor of {total} elements")
+                flats[i] = f
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.rc_data_backward(self._h, C.byref(r), gt.data_ptr(), None if lm is None else lm.data_ptr(), n,
+                                              rnd_p, float(anneal), float(charb_padding), float(mult),
+                                              None if flats[0] is None else flats[0].data_ptr(),
+                                              None if flats[1] is None else flats[1].data_ptr(), loss.data_ptr(), stream))
+        self._keep = [held]
+        return (flats[0], flats[1]), loss
 
     def prng_fill(self, key, shape, mode: str = "uniform", minval: float = 0.0, maxval: float = 1.0):
         """rc_prng_fill: the tensor jax.random.{bits,uniform,normal,gumbel}(key, shape) of the reference's pinned jax

@@ -14,9 +14,14 @@ model followed by `jax.lax.pmean(grad, "batch")` across devices and the optimize
   * `interlevel_grads(rc, rays, jitters, train_frac)` -> the spline interlevel loss of the proposal samplers
     (loss_utils.spline_interlevel_loss) and the exact gradients of both proposal networks, in one device call
     (rc_interlevel_backward: training forward, loss backward to the densities, density backward of levels 0 and 1);
-  * `anneal_at(train_frac)` -> the train-time resampling exponent of the proposal sampler.
+  * `anneal_at(train_frac)` -> the train-time resampling exponent of the proposal sampler;
+  * `data_grads(rc, rays, rgb, jitters, train_frac)` -> the charb data loss of the cache pass
+    (train_utils.compute_data_loss) and the exact gradients of the last density level (MLP_2) and the shader side
+    (pred_normals_layer, appearance grid, Cache/Shader layers), in one device call (rc_data_backward: training forward,
+    loss backward through the compositing, shader recompute + backward, density and appearance-grid backward).
 
-The data loss, the shader's backward and the optimizer are not part of this row.
+A first-order cache-stage step is `interlevel_grads` + `data_grads` + an optimizer of the caller's choice.  The
+normal losses (second derivatives) and the optimizer are not part of this row.
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ from typing import Dict, Iterable, List, Optional
 
 import numpy as np
 
-from .config import InterlevelConfig
+from .config import DataLossConfig, InterlevelConfig
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -78,3 +83,61 @@ def interlevel_grads(rc, rays, jitters, train_frac: float, lossmult=None, flats:
         if flat is not None:
             grads[level] = grads_as_dict(flat, rc.density_grad_layout(level)[0])
     return grads, flats, losses
+
+
+# The shader side of the data loss's gradient (rc_shader_grad_layout): [(name, (in, out))] of the dense layers, with the
+# appearance-grid tables (rc_hashgrid_grad_layout(3)) between pred_normals_layer and the Cache/Shader layers.
+SHADER_DENSE_LAYERS = (
+    ("Cache/Shader/bottleneck_layer", (96, 128)),
+    ("Cache/Shader/roughness_layer", (96, 1)),
+    ("Cache/Shader/ambient_irradiance_layer", (96, 3)),
+    ("Cache/Shader/tint_layer", (96, 3)),
+    ("Cache/Shader/irradiance_layer", (96, 3)),
+    ("Cache/Shader/integrated_brdf_layers_0", (129, 64)),
+    ("Cache/Shader/integrated_brdf_layers_1", (64, 64)),
+    ("Cache/Shader/output_integrated_brdf_layer", (64, 1)),
+    ("Cache/Shader/SurfaceLightField/layer_0", (200, 128)),
+    ("Cache/Shader/SurfaceLightField/layer_1", (128, 128)),
+    ("Cache/Shader/SurfaceLightField/layer_2", (128, 128)),
+    ("Cache/Shader/SurfaceLightField/layer_bottleneck", (328, 128)),
+    ("Cache/Shader/SurfaceLightField/output_ambient_rgb_layer", (128, 3)),
+)
+
+
+def shader_grad_layout(cfg, appearance_tables):
+    """Python mirror of rc_shader_grad_layout: [(name, offset, shape)] and the total size.  appearance_tables: the
+    [(name, shape)] of the appearance grid's tables in level order (rc_hashgrid_grad_layout(3))."""
+    out, off = [], 0
+
+    def add(name, shape):
+        nonlocal off
+        out.append((name, off, tuple(shape)))
+        off += int(np.prod(shape))
+
+    def dense(path, shape):
+        add(f"params/{path}/kernel", shape)
+        add(f"params/{path}/bias", (shape[1],))
+
+    dense(f"Cache/Sampler/MLP_{cfg.num_levels - 1}/pred_normals_layer", (64, 3))
+    for name, shape in appearance_tables:
+        add(name, shape)
+    for path, shape in SHADER_DENSE_LAYERS:
+        dense(path, shape)
+    return out, off
+
+
+def data_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, flats=None, cfg: DataLossConfig = DataLossConfig(),
+               anneal_cfg: InterlevelConfig = InterlevelConfig()):
+    """The cache pass's charb data loss of a batch against target colours rgb [n, 3] and its gradients
+    (rc_data_backward).  jitters: per-level [n] sampler jitter (None = deterministic); train_frac sets the anneal
+    (anneal_at); lossmult: [n] or None; flats: (density flat, shader flat) to accumulate into (allocated zeroed when
+    None).  -> ({"MLP_2": {name: view}, "Shader": {name: view}}, flats, loss [1]) -- the flats are what allreduce_grads
+    averages across ranks; loss is the local batch's term, one copy (the reference adds it under "main" and
+    "cache_main")."""
+    mult = cfg.loss_weight * cfg.data_loss_mult
+    flats, loss = rc.data_backward(rays, rgb, jitters, anneal_at(train_frac, anneal_cfg), lossmult, cfg.charb_padding,
+                                   mult, flats)
+    last = rc.cfg.num_levels - 1
+    grads = {f"MLP_{last}": grads_as_dict(flats[0], rc.density_grad_layout(last)[0]),
+             "Shader": grads_as_dict(flats[1], rc.shader_grad_layout()[0])}
+    return grads, list(flats), loss

@@ -1,0 +1,338 @@
+"""rc_data_backward on the GPU: the cache pass's charb data loss and the gradients of MLP_2 and the shader side, against
+the torch restatement (tests/data_loss_ref.py) and the fp64 density-backward oracle."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import common
+import data_loss_ref as dr
+import nrc_amd
+from nrc_amd import train
+from oracle import cache_ref, hashgrid_ref, mathx, train_ref
+
+CFG = nrc_amd.hotdog_config()
+S2 = CFG.sampling_strategy[-1][2]
+L2 = CFG.num_levels - 1
+RC_ERR_UNSUPPORTED = -5
+
+pytestmark = pytest.mark.gpu
+
+
+def _case(n, seed=5):
+    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
+    rays = {k: v for k, v in rays.items() if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
+    jit = [j.reshape(-1) for j in common.jitters(n, seed=seed + 1)]
+    rng = np.random.Generator(np.random.PCG64(seed + 2))
+    gt = rng.uniform(0.0, 1.0, size=(n, 3)).astype(np.float32)
+    return rays, jit, gt
+
+
+def _lossmult(n, seed=9):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
+    lm[::7] = 0.0
+    return lm
+
+
+def _hidden(hbuf, np_):
+    """hbuf (k_density_mlp's accumulator order per 32-point tile) -> [np, 64] in the reference's column order."""
+    tiles = (np_ + 31) // 32
+    hb = hbuf[: tiles * 2048].reshape(tiles, 2, 16, 2, 32)          # tile, t, r, h, point
+    t, r, h = np.meshgrid(np.arange(2), np.arange(16), np.arange(2), indexing="ij")
+    col = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h
+    out = np.empty((tiles, 32, 64), np.float32)
+    out[:, :, col.reshape(-1)] = hb.reshape(tiles, 64, 32).transpose(0, 2, 1)
+    return out.reshape(-1, 64)[:np_]
+
+
+def _buffers(rc, n):
+    g = lambda name, count: rc.workspace("d:" + name)[:count]
+    np_ = n * S2
+    return dict(
+        density=g(f"density{L2}", np_).reshape(n, S2), tdist=g(f"tdist{L2}", n * (S2 + 1)).reshape(n, S2 + 1),
+        weights=g(f"weights{L2}", np_).reshape(n, S2), means=g(f"means{L2}", 3 * np_).reshape(3, np_).T.copy(),
+        h64=_hidden(g("hbuf", ((np_ + 31) // 32) * 2048), np_).reshape(n, S2, 64),
+        app=g("app", 32 * np_).reshape(32, np_).T.reshape(n, S2, 32).copy(),
+        normals_pred=g("normals_pred", 3 * np_), shade=g("shade", 15 * np_), rgb=g("rgb", 3 * n).reshape(n, 3),
+        d_density=g("d_density", np_).reshape(n, S2))
+
+
+def _restated(w, b, rays, gt, lm, dtype, mult=1.0):
+    t = lambda a: torch.from_numpy(np.asarray(a)).to(dtype)
+    h64 = t(b["h64"]).requires_grad_(True)
+    app = t(b["app"]).requires_grad_(True)
+    dens = t(b["density"]).requires_grad_(True)
+    taps = {}
+    loss, _ = dr.data_loss(w, CFG, h64, app, dens, t(b["tdist"]), t(rays["directions"]), t(rays["viewdirs"]), t(gt), t(lm),
+                           mult=mult, taps=taps)
+    loss.backward()
+    return float(loss.detach()), dict(d_density=dens.grad, dfeat=h64.grad, dapp=app.grad, dp3=taps["pred_raw"].grad)
+
+
+def _bound(got, ref64, ref32, floor):
+    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
+    return err, 3.0 * err32 + floor
+
+
+def test_kernel_against_restatement():
+    """Loss, d density, d feature64, d app32 and d pred_raw within 3x the fp32 restatement's distance from fp64 (plus a
+    small floor), on the HIP forward's d: buffers, lossmult with zeros."""
+    rc = common.make_rc()
+    n = 1000
+    rays, jit, gt = _case(n)
+    lm = _lossmult(n)
+    (_, _), loss = rc.data_backward(rays, gt, jit, 0.4, lm)
+    loss = float(loss.cpu())
+    b = _buffers(rc, n)
+    np_ = n * S2
+    got = dict(d_density=b["d_density"], dfeat=rc.workspace("d:dfeat")[: np_ * 64].reshape(n, S2, 64),
+               dapp=rc.workspace("d:dapp")[: np_ * 32].reshape(n, S2, 32), dp3=rc.workspace("d:dp3")[: np_ * 3].reshape(n, S2, 3))
+    l64, g64 = _restated(common.weights_torch(dtype=torch.float64), b, rays, gt, lm, torch.float64)
+    l32, g32 = _restated(common.weights_torch(dtype=torch.float32), b, rays, gt, lm, torch.float32)
+    err, tol = _bound(np.float64(loss), l64, l32, 1e-6 * l64)
+    assert err <= tol, ("loss", loss, l64, l32)
+    for k in ("d_density", "dfeat", "dapp", "dp3"):
+        r64, r32 = g64[k].numpy(), g32[k].double().numpy()
+        scale = float(np.abs(r64).max())
+        assert scale > 0, k
+        err, tol = _bound(got[k].astype(np.float64), r64, r32, 2e-5 * scale)
+        assert err <= tol, (k, err, tol, scale)
+    assert np.all(b["d_density"][lm == 0.0] == 0.0)
+    assert np.all(got["dfeat"][lm == 0.0] == 0.0)
+
+
+def test_layout_matches_the_python_mirror():
+    rc = common.make_rc()
+    tables, _ = rc.hashgrid_grad_layout(3)
+    ref, total = train.shader_grad_layout(CFG, [(name, shape) for name, _, shape in tables])
+    got, gtotal = rc.shader_grad_layout()
+    assert got == ref and gtotal == total
+
+
+def _oracle_chain(w, means, tdist, directions, viewdirs, gt):
+    """The data loss in fp64 from the sample means on: level-2 density grid -> density MLP (density, hidden vector),
+    appearance grid, shader, composite, charb (oracle hashgrid_ref / cache_ref pieces + tests/data_loss_ref.py)."""
+    n = means.shape[0]
+    warped = mathx.contract_radius(means, CFG.contract_radius)
+    x = hashgrid_ref.hash_encoding(w, f"params/Cache/Sampler/MLP_{L2}/density_grid", CFG.proposal_grids[L2], warped)
+    h = torch.relu(cache_ref.dense(w, f"Cache/Sampler/MLP_{L2}/density_layers_0", x))
+    h = torch.relu(cache_ref.dense(w, f"Cache/Sampler/MLP_{L2}/density_layers_1", h))
+    raw = cache_ref.dense(w, f"Cache/Sampler/MLP_{L2}/output_density_layer", h)[..., 0]
+    valid = ((warped > -CFG.proposal_grids[L2].bbox) & (warped < CFG.proposal_grids[L2].bbox)).all(dim=-1)
+    density = torch.where(valid, mathx.safe_exp(raw + CFG.density_bias), torch.zeros_like(raw))
+    app = hashgrid_ref.hash_encoding(w, "params/Cache/Shader/appearance_grid", CFG.appearance_grid, warped)
+    loss, _ = dr.data_loss(w, CFG, h, app, density, tdist, directions, viewdirs, gt, torch.ones(n, dtype=means.dtype))
+    return loss
+
+
+def test_whole_chain_against_oracle():
+    """Every tensor of both layouts -- both grids' tables included -- against fp64 autograd of the whole chain from the
+    HIP forward's sample means, relative to each tensor's scale.  More than 1 024 rays, so the shader backward runs two
+    chunks (the second with its own points offset).  Rays with a level-2 sample within 3e-5 of a density-MLP ReLU kink
+    (where fp32 and fp64 may take different sides) are left out, as in test_gpu_interlevel: each ray's forward is
+    independent of the others, so the subset's buffers are the same bits."""
+    rc = common.make_rc()
+    n0 = 8192
+    rays, jit, gt = _case(n0, seed=21)
+    rc.data_backward(rays, gt, jit, 0.4, grads=False)
+    means = _buffers(rc, n0)["means"]
+    m = train_ref.relu_margin(common.weights_torch(dtype=torch.float64), CFG, L2, torch.from_numpy(means).double())
+    keep = np.nonzero((m.numpy().reshape(n0, S2) > 3e-5).all(axis=1))[0][:1200]
+    assert len(keep) == 1200, len(keep)        # 38 400 samples: two chunks of the shader backward
+    rays = {k: np.ascontiguousarray(v[keep]) for k, v in rays.items()}
+    jit, gt, n = [np.ascontiguousarray(j[keep]) for j in jit], np.ascontiguousarray(gt[keep]), len(keep)
+    g, flats, _ = train.data_grads(rc, rays, gt, jit, 1.0)
+    b = _buffers(rc, n)
+    ref = {}
+    for dt in (torch.float64, torch.float32):
+        w = {k: v.clone().requires_grad_(True) for k, v in common.weights_torch(dtype=dt).items()}
+        t = lambda a: torch.from_numpy(np.asarray(a)).to(dt)
+        _oracle_chain(w, t(b["means"]).reshape(n, S2, 3), t(b["tdist"]), t(rays["directions"]), t(rays["viewdirs"]),
+                      t(gt)).backward()
+        ref[dt] = {k: v.grad for k, v in w.items() if v.grad is not None}
+    tables = 0
+    for part in (f"MLP_{L2}", "Shader"):
+        for name, v in g[part].items():
+            a = v.cpu().double().numpy()
+            assert name in ref[torch.float64], name
+            r, r32 = ref[torch.float64][name].numpy(), ref[torch.float32][name].double().numpy()
+            scale = float(np.abs(r).max())
+            assert scale > 0, name
+            # a table entry sums the contributions of many samples: the sum cancels, so its fp32 error is measured by
+            # the fp32 oracle's own distance from fp64, not by the entry's size
+            err, err32 = float(np.abs(a - r).max()), float(np.abs(r32 - r).max())
+            assert err <= 3.0 * err32 + 2e-3 * scale, (name, err, err32, scale)
+            if "_grid/" in name:
+                # the same entries are touched, up to corners whose trilinear weight is 0 in one precision only (a sample
+                # on a cell face: the float32 cell fraction is off by ~ resolution x eps, up to 2.4e-4 on the 2048 level);
+                # their values are held by the bound above
+                tables += 1
+                only = (a != 0.0) != (r != 0.0)
+                assert np.count_nonzero(only) <= 1e-4 * np.count_nonzero(r), (name, np.count_nonzero(only))
+    assert tables == len(rc.hashgrid_grad_layout(L2)[0]) + len(rc.hashgrid_grad_layout(3)[0])
+
+
+def test_recompute_matches_the_forward():
+    """The backward's fp32 recompute of the last sample chunk (pred_raw -> normals, the per-sample rgb from its heads,
+    integrated-BRDF logit and SLF logits) against what the forward stored for the same samples: pins the hbuf column
+    mapping, the appearance layout and the chunk offset.  The bound allows for the forward's split-bf16 shader layers."""
+    rc = common.make_rc()
+    n = 1500                                       # 48 000 samples: two chunks, the second starts at sample 32 768
+    rays, jit, gt = _case(n, seed=13)
+    rc.data_backward(rays, gt, jit, 0.4)
+    np_, c0 = n * S2, 32768
+    C = np_ - c0
+    p3 = rc.workspace("d:p3")[: 3 * C].reshape(C, 3).astype(np.float64)
+    nrm = -p3 / np.linalg.norm(p3, axis=1, keepdims=True)
+    stored = rc.workspace("d:normals_pred")[: 3 * np_].reshape(3, np_).T[c0:]
+    assert float(np.abs(nrm - stored).max()) <= 1e-4, float(np.abs(nrm - stored).max())
+    heads = rc.workspace("d:heads")[: 10 * C].reshape(C, 10).astype(np.float64)
+    io = rc.workspace("d:io")[:C].astype(np.float64)
+    so = rc.workspace("d:so")[: 3 * C].reshape(C, 3).astype(np.float64)
+    sp = lambda v: np.logaddexp(v, 0.0)
+    sig = lambda v: 1.0 / (1.0 + np.exp(-v))
+    ad = np.clip(sp(heads[:, 1:4] + CFG.ambient_irradiance_bias), 0.0, CFG.rgb_max)
+    tint = sig(heads[:, 4:7])
+    irr = np.clip(sp(heads[:, 7:10] + CFG.irradiance_bias), 0.0, CFG.rgb_max)
+    ibrdf = sig(io + np.log(3.0))[:, None]
+    amb = np.maximum(sp(so + CFG.slf_ambient_bias), 0.0)
+    rgb = ad + irr + np.clip(tint * ibrdf * amb, 0.0, CFG.rgb_max)
+    shade = rc.workspace("d:shade")[: 15 * np_].reshape(15, np_)[0:3, c0:].T
+    err = float((np.abs(rgb - shade) / np.maximum(1.0, np.abs(shade))).max())
+    assert err <= 2e-4, err
+
+
+def test_forward_matches_the_render_workspace():
+    """The training forward's buffers are bitwise those of a launch-per-stage render at anneal 0.4, on both plan forms."""
+    for n in (1000, 24577):
+        rays, jit, gt = _case(n, seed=11)
+        rc = common.make_rc()
+        rc.data_backward(rays, gt, jit, 0.4, grads=False)
+        torch.cuda.synchronize()
+        rc.set_fused(False)
+        out = rc.render_rays(rays, {"jitter": jit}, outputs=["rgb"])
+        torch.cuda.synchronize()
+        np_ = n * S2
+        for name, cnt in [(f"{k}{l}", None) for l in range(L2 + 1) for k in ("sdist", "tdist", "means", "density", "weights")] + \
+                         [("hbuf", ((np_ + 31) // 32) * 2048), ("normals_pred", 3 * np_), ("shade", 15 * np_)]:
+            a, b = rc.workspace("d:" + name), rc.workspace(name)
+            if cnt is not None:
+                a, b = a[:cnt], b[:cnt]
+            assert a.shape == b.shape and np.array_equal(a, b), (n, name)
+        rgb = out["rgb"]
+        rgb = rgb.cpu().numpy() if hasattr(rgb, "cpu") else np.asarray(rgb)
+        assert np.array_equal(rc.workspace("d:rgb")[: 3 * n].reshape(n, 3), rgb.reshape(n, 3)), n
+        if n == 1000:
+            rc.interlevel_backward(rays, jit, 0.4, levels=())
+            for l in range(L2 + 1):
+                for k in ("sdist", "tdist", "means", "density"):
+                    assert np.array_equal(rc.workspace(f"i:{k}{l}"), rc.workspace(f"d:{k}{l}")), (k, l)
+
+
+def _mlp_part(rc, flat, which):
+    layout = rc.density_grad_layout(L2)[0] if which == 0 else rc.shader_grad_layout()[0]
+    keep = [(o, int(np.prod(s))) for name, o, s in layout if "grid" not in name]
+    return torch.cat([flat[o:o + c] for o, c in keep])
+
+
+def test_semantics():
+    rc = common.make_rc()
+    n = 777
+    rays, jit, gt = _case(n, seed=31)
+    lm = _lossmult(n, seed=32)
+    f1, l1 = rc.data_backward(rays, gt, jit, 0.3, lm)
+    f1 = [f.clone() for f in f1]
+    l1 = l1.clone()
+    f2, l2 = rc.data_backward(rays, gt, jit, 0.3, lm)
+    assert torch.equal(l1, l2)                                   # bitwise stable
+    for i in range(2):
+        assert torch.equal(_mlp_part(rc, f1[i], i), _mlp_part(rc, f2[i], i))
+        assert float(f1[i].abs().max()) > 0
+    f3, l3 = rc.data_backward(rays, gt, jit, 0.3, lm, mult=2.0)  # linear in mult
+    for i in range(2):
+        ref = 2 * f1[i].cpu().numpy()
+        np.testing.assert_allclose(f3[i].cpu().numpy(), ref, rtol=1e-5, atol=1e-6 * float(np.abs(ref).max()))
+    np.testing.assert_allclose(l3.cpu().numpy(), 2 * l1.cpu().numpy(), rtol=1e-6)
+    acc = [f.clone() for f in f1]                                # accumulates; MLP parts bitwise 2x
+    rc.data_backward(rays, gt, jit, 0.3, lm, grads=acc)
+    for i in range(2):
+        assert torch.equal(_mlp_part(rc, acc[i], i), 2 * _mlp_part(rc, f1[i], i))
+    fz, lz = rc.data_backward(rays, gt, jit, 0.3, lm, grads=False)   # NULL buffers: the loss only
+    assert fz == (None, None) and torch.equal(lz, l1)
+    empty = {k: v[:0] for k, v in rays.items()}                 # n = 0
+    fe, le = rc.data_backward(empty, gt[:0], [j[:0] for j in jit], 0.4)
+    assert float(le.abs().max()) == 0.0 and all(float(f.abs().max()) == 0.0 for f in fe)
+
+
+def test_bad_arguments():
+    rc = common.make_rc()
+    n = 64
+    rays, _, gt = _case(n)
+    r, held, _ = rc._rays_struct(rays)
+    g = torch.from_numpy(gt).cuda()
+    loss = torch.zeros(1, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    call = lambda rays_p=C.byref(r), gt_p=g.data_ptr(), nn=n, anneal=0.4, pad=1e-3, mult=1.0, out=loss.data_ptr(): \
+        rc.lib.rc_data_backward(rc._h, rays_p, gt_p, None, nn, None, anneal, pad, mult, None, None, out, stream)
+    assert call() == 0
+    for kw in (dict(rays_p=None), dict(gt_p=None), dict(nn=-1), dict(anneal=float("nan")), dict(anneal=-0.1),
+               dict(pad=float("inf")), dict(mult=float("nan")), dict(out=None)):
+        assert call(**kw) == -1, kw
+        assert rc.lib.rc_last_error(rc._h), kw
+    del held
+    torch.cuda.synchronize()
+    # more than 32 last-level intervals
+    from nrc_amd import rc_ext
+    rc64 = rc_ext.RadianceCache(nrc_amd.hotdog_config(sampling_strategy=CFG.sampling_strategy[:-1] + ((2, 2, 64),)), 0)
+    rc64.load_weights(common.weights_np())
+    r2, held2, _ = rc64._rays_struct(rays)
+    assert rc64.lib.rc_data_backward(rc64._h, C.byref(r2), g.data_ptr(), None, n, None, 0.4, 1e-3, 1.0, None, None,
+                                     loss.data_ptr(), stream) == RC_ERR_UNSUPPORTED
+    del held2
+    torch.cuda.synchronize()
+    # the time-resolved cache handle
+    tr = rc_ext.RadianceCache(nrc_amd.cornell_transient_config(), 0)
+    tr.load_weights(common.weights_transient_np())
+    r3, held3, _ = tr._rays_struct(rays)
+    assert tr.lib.rc_data_backward(tr._h, C.byref(r3), g.data_ptr(), None, n, None, 0.4, 1e-3, 1.0, None, None,
+                                   loss.data_ptr(), stream) == RC_ERR_UNSUPPORTED
+    assert b"time-resolved" in tr.lib.rc_last_error(tr._h)
+    assert tr.lib.rc_shader_grad_size(tr._h) == RC_ERR_UNSUPPORTED
+    del held3
+    torch.cuda.synchronize()
+
+
+def test_training_loop_reduces_the_loss():
+    """Adam on MLP_2 + Shader driven by data_grads + interlevel_grads + load_weights, fitting colours rendered by a
+    second weight set on a fixed batch."""
+    rc = common.make_rc()
+    n = 2048
+    rays, jit, _ = _case(n, seed=41)
+    from nrc_amd import rc_ext
+    target = rc_ext.RadianceCache(CFG, 0)
+    target.load_weights(common.weights_np(seed=2))
+    target.set_fused(False)
+    gt = target.render_rays(rays, {"jitter": jit}, outputs=["rgb"])["rgb"]
+    gt = torch.as_tensor(np.asarray(gt.cpu() if hasattr(gt, "cpu") else gt)).reshape(n, 3).contiguous()
+    names = [name for name, _, _ in rc.density_grad_layout(L2)[0]] + [name for name, _, _ in rc.shader_grad_layout()[0]]
+    params = {k: torch.from_numpy(v).cuda() for k, v in common.weights_np().items() if k in names}
+    assert len(params) == len(names)
+    opt = torch.optim.Adam(params.values(), lr=LOOP_LR)
+    hist = []
+    for step in range(LOOP_STEPS):
+        g, _, loss = train.data_grads(rc, rays, gt, jit, 1.0)
+        train.interlevel_grads(rc, rays, jit, 1.0)
+        hist.append(float(loss))
+        for part in g.values():
+            for name, v in part.items():
+                params[name].grad = v.clone()
+        opt.step()
+        rc.load_weights(params)
+    assert min(hist[-3:]) < LOOP_DROP * hist[0], hist
+
+
+# Adam at 1e-3 on every parameter of MLP_2 and the shader side: -93 % in 40 steps on this batch when the loop was tried
+# out (0.0205 -> 0.0014, not monotone over the first steps); the 0.5 bound leaves wide margin
+LOOP_LR, LOOP_STEPS, LOOP_DROP = 1e-3, 40, 0.5
