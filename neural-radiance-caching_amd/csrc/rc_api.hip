@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "rc_internal.h"
@@ -88,6 +89,30 @@ struct DataWs {
   WsBuf dheads, dio, dso, dsb, dx328, ds1, ds0, di2, di1, dib_in, db128, dp3, df96, dfeat, dapp, part, ones;
 };
 
+// Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
+// different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
+// serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
+// WS_TRAIN serves rc_density_backward (TrainWs only), WS_INTERLEVEL rc_interlevel_backward, WS_DATA rc_data_backward.
+enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_COUNT };
+// rc_workspace_ptr's "<prefix><name>" for each set
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:"};
+
+struct WsSet {
+  RenderWs r;
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs> x;   // the set's extra buffers (ws_extra)
+  // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
+  // (event), so two streams never run on one set at the same time (WsUse)
+  hipStream_t stream = nullptr;
+  bool used = false;
+  hipEvent_t done = nullptr;
+  uint64_t last_use = 0;
+};
+// The extra buffers of a set, of the kind its entry point uses (fixed by that entry point's first call).
+template <class X> X& ws_extra(WsSet& s) {
+  if (X* p = std::get_if<X>(&s.x)) return *p;
+  return s.x.template emplace<X>();
+}
+
 // Every workspace buffer by name, for rc_workspace_ptr ("<name>", per-level buffers "<name><level>") and rc_destroy.
 struct WsName {
   const char* name;
@@ -100,6 +125,20 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf InterlevelWs::*m) : name(s), i(m) {}
   constexpr WsName(const char* s, WsBuf (InterlevelWs::*m)[RC_MAX_LEVELS]) : name(s), ilv(m) {}
   constexpr WsName(const char* s, WsBuf DataWs::*m) : name(s), d(m) {}
+  // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
+  WsBuf* in(WsSet& s, int l) const {
+    if (l < 0) {
+      if (r) return &(s.r.*r);
+      if (x) return one(s, x);
+      if (t) return one(s, t);
+      if (i) return one(s, i);
+      return d ? one(s, d) : nullptr;
+    }
+    if (lv) return &(s.r.*lv)[l];
+    InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
+    return p ? &(p->*ilv)[l] : nullptr;
+  }
+  template <class X> static WsBuf* one(WsSet& s, WsBuf X::*m) { X* p = std::get_if<X>(&s.x); return p ? &(p->*m) : nullptr; }
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs;
@@ -165,20 +204,7 @@ struct rc_handle {
   // packed MFMA fragments (device)
   Packs packs;
   DevBuf ide_table;
-  // Workspace sets.  ws[0..3] serve rc_render_rays, one per caller stream so that independent batches enqueued on
-  // different streams overlap (the least recently used one is taken over when a fifth stream shows up); ws[0] also serves
-  // rc_render_material / rc_render_transient, with ws_x and with ws_sec for their batched secondary trace; ws_train serves
-  // rc_density_backward; ws_il + ws_ilx serve rc_interlevel_backward; ws_d + ws_dx serve rc_data_backward.  groups[0..3] /
-  // groups[4] / groups[5] / groups[6] record who used a render set / the train set / the interlevel set / the data set
-  // last: a call whose stream differs from the set's previous user first waits for that user's last call (event), so two
-  // streams never run on one set at the same time.
-  RenderWs ws[4], ws_sec, ws_il, ws_d;
-  ExtraWs ws_x;
-  TrainWs ws_train;
-  InterlevelWs ws_ilx;
-  DataWs ws_dx;
-  struct WsGroup { hipStream_t stream = nullptr; bool used = false; hipEvent_t done = nullptr; uint64_t last_use = 0; };
-  WsGroup groups[7];
+  WsSet ws[WS_COUNT];                        // workspace sets (WsSetId)
   uint64_t use_clock = 0;
   // profiling: ring of event sets, one set per render call (slot = call % kEvSlots)
   // mode 0 off, 1 every stage, 2 only the dominant kernel (cache shader), 3 like 2 on every 8th call
@@ -213,10 +239,10 @@ struct rc_handle {
   float* sec_sbounds = nullptr;            // power-ladder image of the secondary rays' (near, far): constants of the config
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_side[4] = {nullptr, nullptr, nullptr, nullptr};
-  // rc_density_backward: weight gradients ([0]) and the LDS-accumulated table levels ([1]) beside the scatter of the other
-  // levels on the caller's stream (highest priority; events: fork, join [0], join [1])
-  hipStream_t train_stream[2] = {nullptr, nullptr};
-  hipEvent_t ev_train[3] = {nullptr, nullptr, nullptr};
+  // rc_density_backward: the weight gradients beside the table-gradient scatter on the caller's stream (highest priority;
+  // events: fork, join)
+  hipStream_t train_stream = nullptr;
+  hipEvent_t ev_train[2] = {nullptr, nullptr};
   std::vector<GraphEntry> graphs;
   RenderKey last_key{};
   bool have_last_key = false;
@@ -508,11 +534,11 @@ void build_fused_template(rc_handle* h) {
 // The handle's side stream (work that only feeds a call's outputs, forked from / joined to the caller's stream with events)
 // at the lowest priority: the kernels on the caller's stream -- the critical path -- get the CUs first.
 // Helper streams are per PROCESS and device, created together by the first rc_create and never destroyed: [0] lowest
-// priority (the material stage's side work), [1], [2] highest priority (rc_density_backward).  Measured on this runtime
-// (ROCm 7.2, profiles/r04_helper_streams.txt): with streams that come and go with their handles, whichever multi-stream
-// call ran SECOND in a process was slow -- every kernel of the call +50 us or 2-3x, ~100 us of host time between calls:
-// bench.py's train line after its material line 0.20 -> 0.37 ms per level-2 call, the other order the material stage
-// 1.39 -> 1.95 ms.  Sharing the streams across handles did not cure it, creating all of them before any work did.
+// priority (the material stage's side work), [1], [2] highest priority ([1]: rc_density_backward; [2]: no user now, still
+// created with the others).  Measured on this runtime (ROCm 7.2, profiles/r04_helper_streams.txt): with streams that come
+// and go with their handles, whichever multi-stream call ran SECOND in a process was slow -- every kernel of the call
+// +50 us or 2-3x, ~100 us of host time between calls: bench.py's train line after its material line 0.20 -> 0.37 ms per
+// level-2 call, the other order the material stage 1.39 -> 1.95 ms.  Sharing the streams across handles did not cure it, creating all of them before any work did.
 // Handles are driven by one host thread per GPU; every call forks from and joins to the caller's stream with the
 // handle's own events, so sharing the streams only orders the helper work of two handles.
 hipStream_t rc_helper_stream(int which) {
@@ -756,72 +782,67 @@ int ws_alloc(rc_handle* h, WsBuf& b, int64_t count) {
   return RC_OK;
 }
 
+// Requests in order; the first failure is returned.
+struct WsReq { WsBuf& b; int64_t count; };
+int ws_alloc(rc_handle* h, std::initializer_list<WsReq> reqs) {
+  for (const WsReq& q : reqs)
+    if (int rc = ws_alloc(h, q.b, q.count)) return rc;
+  return RC_OK;
+}
+
+// The proposal sampler's buffers of level l in set `w`.
+int ws_sampler_level(rc_handle* h, RenderWs& w, int l, int64_t n) {
+  const int64_t S = h->cfg.num_samples[l];
+  const int LF = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
+  return ws_alloc(h, {{w.sdist[l], n * (S + 1)}, {w.tdist[l], n * (S + 1)}, {w.means[l], 3 * n * S}, {w.feat[l], (int64_t)LF * n * S},
+                      {w.density[l], n * S}, {w.weights[l], n * S}});
+}
+
 int ensure_workspace(rc_handle* h, RenderWs& w, int64_t n) {
   // ws_alloc only (re)allocates when a buffer is too small and always records the current element
   // count, so after the largest batch has been seen this is allocation-free.
   const rc_config& c = h->cfg;
   int rc;
-  for (int l = 0; l < c.num_levels; ++l) {
-    const int64_t S = c.num_samples[l];
-    const int LF = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
-    if ((rc = ws_alloc(h, w.sdist[l], n * (S + 1))) || (rc = ws_alloc(h, w.tdist[l], n * (S + 1))) ||
-        (rc = ws_alloc(h, w.means[l], 3 * n * S)) || (rc = ws_alloc(h, w.feat[l], (int64_t)LF * n * S)) ||
-        (rc = ws_alloc(h, w.density[l], n * S)) || (rc = ws_alloc(h, w.weights[l], n * S)))
-      return rc;
-  }
+  for (int l = 0; l < c.num_levels; ++l)
+    if ((rc = ws_sampler_level(h, w, l, n))) return rc;
   const int64_t S2 = c.num_samples[c.num_levels - 1];
   const int64_t np = n * S2;
-  if ((rc = ws_alloc(h, w.hbuf, ((np + 31) / 32) * 32 * 64)) || (rc = ws_alloc(h, w.normals_pred, 3 * np)) ||
-      (rc = ws_alloc(h, w.normals_grad, 3 * np)) || (rc = ws_alloc(h, w.jac, 3 * 32 * np)) || (rc = ws_alloc(h, w.app, 32 * np)) ||
-      (rc = ws_alloc(h, w.shade, RC_SHADE_CH * np)) || (rc = ws_alloc(h, w.debug, 32 * ((np + 31) / 32) + 64)) ||
-      (rc = ws_alloc(h, w.env_rgb, 3 * n)) || (rc = ws_alloc(h, w.rgb_noenv, 3 * n)) || (rc = ws_alloc(h, w.acc_ws, n)) ||
-      (rc = ws_alloc(h, w.inds, n)) || (rc = ws_alloc(h, w.src_idx, n)) || (rc = ws_alloc(h, w.filt_weight, n)) ||
-      (rc = ws_alloc(h, w.acc_sel, n)))
+  if ((rc = ws_alloc(h, {{w.hbuf, ((np + 31) / 32) * 32 * 64}, {w.normals_pred, 3 * np}, {w.normals_grad, 3 * np}, {w.jac, 3 * 32 * np},
+                         {w.app, 32 * np}, {w.shade, RC_SHADE_CH * np}, {w.debug, 32 * ((np + 31) / 32) + 64}, {w.env_rgb, 3 * n},
+                         {w.rgb_noenv, 3 * n}, {w.acc_ws, n}, {w.inds, n}, {w.src_idx, n}, {w.filt_weight, n}, {w.acc_sel, n}})))
     return rc;
   // lean resampling pass: last-level features / hidden vector / predicted normals of the picked samples only
-  if ((rc = ws_alloc(h, w.feat_sel, 32 * n)) || (rc = ws_alloc(h, w.hbuf_sel, ((n + 31) / 32) * 32 * 64)) ||
-      (rc = ws_alloc(h, w.normals_sel, 3 * n)) || (rc = ws_alloc(h, w.density_sel, n)))
+  if ((rc = ws_alloc(h, {{w.feat_sel, 32 * n}, {w.hbuf_sel, ((n + 31) / 32) * 32 * 64}, {w.normals_sel, 3 * n}, {w.density_sel, n}})))
     return rc;
-  if (h->transient && &w == &h->ws[0]) {
+  if (h->transient && &w == &h->ws[WS_RENDER0].r) {
     const int64_t tiles = (np + 31) / 32;
-    if ((rc = ws_alloc(h, w.t_irr, tiles * 32 * 64)) || (rc = ws_alloc(h, w.t_slf, tiles * 64 * 64)) ||
-        (rc = ws_alloc(h, w.tshade, (int64_t)RC_TS_COUNT * np)))
-      return rc;
+    return ws_alloc(h, {{w.t_irr, tiles * 32 * 64}, {w.t_slf, tiles * 64 * 64}, {w.tshade, (int64_t)RC_TS_COUNT * np}});
   }
   return RC_OK;
 }
 
 void free_workspace(rc_handle* h) {
-  for (const WsName& e : wsn::kTable) {
-    for (RenderWs* r : {&h->ws[0], &h->ws[1], &h->ws[2], &h->ws[3], &h->ws_sec, &h->ws_il, &h->ws_d}) {
-      if (e.r) free_buf(r->*e.r);
-      if (e.lv) for (WsBuf& b : r->*e.lv) free_buf(b);
-    }
-    if (e.x) free_buf(h->ws_x.*e.x);
-    if (e.t) free_buf(h->ws_train.*e.t);
-    if (e.i) free_buf(h->ws_ilx.*e.i);
-    if (e.ilv) for (WsBuf& b : h->ws_ilx.*e.ilv) free_buf(b);
-    if (e.d) free_buf(h->ws_dx.*e.d);
-  }
+  for (WsSet& s : h->ws)
+    for (const WsName& e : wsn::kTable)
+      for (int l = -1; l < RC_MAX_LEVELS; ++l)
+        if (WsBuf* b = e.in(s, l)) free_buf(*b);
 }
 
-// rc_workspace_ptr: "[p1:|p2:|p3:|s:|t:|i:|d:]<name>[level]" -> the buffer (nullptr for an unknown name)
+// rc_workspace_ptr: "<set prefix><name>[level]" -> the buffer (nullptr for an unknown name)
 WsBuf* ws_find(rc_handle* h, const char* name) {
   const char* colon = strchr(name, ':');
   const std::string pre = colon ? std::string(name, colon + 1) : "", leaf = colon ? colon + 1 : name;
-  const char* const kPre[8] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:"};
-  int set = -1;      // 0-3 rc_render_rays' sets (0 with the extras), 4 the secondary set, 5 the train set, 6 the interlevel set,
-                     // 7 the data-loss set
-  for (int i = 0; i < 8; ++i) if (pre == kPre[i]) set = i;
-  RenderWs* r = set < 0 || set == 5 ? nullptr : (set == 7 ? &h->ws_d : set == 6 ? &h->ws_il : set == 4 ? &h->ws_sec : &h->ws[set]);
+  int set = 0;
+  while (set < WS_COUNT && pre != kWsPrefix[set]) ++set;
+  if (set == WS_COUNT) return nullptr;
+  WsSet& s = h->ws[set];
   for (const WsName& e : wsn::kTable) {
     const size_t k = strlen(e.name);
     if (leaf.compare(0, k, e.name) != 0) continue;
-    if (leaf.size() == k && ((e.r && r) || (e.x && set == 0) || (e.t && set == 5) || (e.i && set == 6) || (e.d && set == 7)))
-      return e.r ? &(r->*e.r) : e.x ? &(h->ws_x.*e.x) : e.t ? &(h->ws_train.*e.t) : e.i ? &(h->ws_ilx.*e.i) : &(h->ws_dx.*e.d);
-    const bool digit = leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels;
-    if (e.lv && r && digit) return &(r->*e.lv)[leaf[k] - '0'];
-    if (e.ilv && set == 6 && digit && leaf[k] < '0' + h->cfg.num_levels - 1) return &(h->ws_ilx.*e.ilv)[leaf[k] - '0'];
+    WsBuf* b = nullptr;
+    if (leaf.size() == k) b = e.in(s, -1);
+    else if (leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels - (e.ilv ? 1 : 0)) b = e.in(s, leaf[k] - '0');
+    if (b) return b;
   }
   return nullptr;
 }
@@ -870,28 +891,27 @@ void stage_mark(rc_handle* h, int slot, int idx, hipStream_t s) {
   (void)hipEventRecord(h->ev[slot][idx], s);
 }
 
-int ws_enter(rc_handle* h, int g, hipStream_t st) {
-  rc_handle::WsGroup& G = h->groups[g];
-  if (!G.done) RC_HIP(h, hipEventCreateWithFlags(&G.done, hipEventDisableTiming));
-  if (G.used && G.stream != st) RC_HIP(h, hipStreamWaitEvent(st, G.done, 0));
-  G.stream = st; G.used = true; G.last_use = ++h->use_clock;
-  return RC_OK;
-}
-int ws_leave(rc_handle* h, int g, hipStream_t st) {
-  RC_HIP(h, hipEventRecord(h->groups[g].done, st));
-  return RC_OK;
-}
-struct WsLeave {      // an entry point's every exit records the "done" event of the set it entered
-  rc_handle* h; int g; hipStream_t st; bool on;
-  ~WsLeave() { if (on) (void)ws_leave(h, g, st); }
+// One entry point's use of a workspace set on stream `st`: entering orders it behind the set's previous user on another
+// stream; every exit of the scope then records the set's "done" event.  `rc`: the status of the entry (on = false: the
+// call uses no set).
+struct WsUse {
+  rc_handle* h; WsSet& s; hipStream_t st; bool on; int rc;
+  WsUse(rc_handle* h_, int set, hipStream_t st_, bool on_ = true) : h(h_), s(h_->ws[set]), st(st_), on(on_), rc(on ? enter() : RC_OK) {}
+  ~WsUse() { if (on && rc == RC_OK) (void)hipEventRecord(s.done, st); }
+  int enter() {
+    if (!s.done) RC_HIP(h, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    if (s.used && s.stream != st) RC_HIP(h, hipStreamWaitEvent(st, s.done, 0));
+    s.stream = st; s.used = true; s.last_use = ++h->use_clock;
+    return RC_OK;
+  }
 };
 // Workspace set of rc_render_rays for caller stream `st`: its own, else a free one, else the least recently used.
 int ws_pick(rc_handle* h, hipStream_t st) {
   int free_i = -1, lru = 0;
-  for (int i = 0; i < 4; ++i) {
-    if (h->groups[i].used && h->groups[i].stream == st) return i;
-    if (!h->groups[i].used && free_i < 0) free_i = i;
-    if (h->groups[i].last_use < h->groups[lru].last_use) lru = i;
+  for (int i = WS_RENDER0; i <= WS_RENDER3; ++i) {
+    if (h->ws[i].used && h->ws[i].stream == st) return i;
+    if (!h->ws[i].used && free_i < 0) free_i = i;
+    if (h->ws[i].last_use < h->ws[lru].last_use) lru = i;
   }
   return free_i >= 0 ? free_i : lru;
 }
@@ -903,6 +923,20 @@ void drop_graphs(rc_handle* h) {
   }
   h->graphs.clear();
   h->have_last_key = false;
+}
+
+// The ray fields every ray-taking entry point requires.
+int check_rays(rc_handle* h, const rc_rays* rays, const char* who) {
+  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
+    return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": origins/directions/viewdirs/near/far are required");
+  return RC_OK;
+}
+
+// Repack the weights if a load changed them (captured graphs hold the old packs' pointers: dropped first).
+int ensure_packed(rc_handle* h) {
+  if (!h->packed_dirty) return RC_OK;
+  drop_graphs(h);
+  return repack(h);
 }
 
 // Secondary rays: rgb += env * (1 - acc) (Model._composite_env_map, internal/models.py:423-460).
@@ -992,7 +1026,7 @@ void rc_destroy(rc_handle* h) {
   if (h->ide_table.p) (void)hipFree(h->ide_table.p);
   free_buf(h->data_w);
   drop_graphs(h);
-  for (auto& G : h->groups) if (G.done) (void)hipEventDestroy(G.done);
+  for (WsSet& s : h->ws) if (s.done) (void)hipEventDestroy(s.done);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
   // side_stream / train_stream belong to the process (rc_helper_stream)
   if (h->sec_sbounds) (void)hipFree(h->sec_sbounds);
@@ -1442,8 +1476,8 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
   if (!rays || !out) return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: null rays/outputs");
   if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: negative n_rays");
   if (n == 0) return RC_OK;
-  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: origins/directions/viewdirs/near/far are required");
+  int rc;
+  if ((rc = check_rays(h, rays, "rc_render_rays"))) return rc;
   RoctxScope roctx_call("rc_render_rays");
   if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_rays: this handle renders the time-resolved cache (rc_render_transient)");
   if (!(pass_mask & RC_PASS_CACHE)) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_rays: pass_mask must include RC_PASS_CACHE");
@@ -1454,23 +1488,17 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
     return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: resampling needs rc_randoms.gumbel or .resample_inds");
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
-  int rc;
-  if (h->packed_dirty) {
-    drop_graphs(h);
-    if ((rc = repack(h))) return rc;
-  }
+  if ((rc = ensure_packed(h))) return rc;
   if (secondary && !(pass_mask & RC_PASS_NO_ENVMAP) && !h->have_envmap)
     return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/* (secondary rays composite the model-level EnvMap)");
   const bool fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && pass_mask == RC_PASS_CACHE;
   // one workspace set per caller stream (up to 4): calls on different streams do not share buffers.  The fused kernel
   // keeps every intermediate on chip: no workspace, no set.
-  const int ws_slot = fused ? 0 : ws_pick(h, st);
-  RenderWs& w = h->ws[ws_slot];
-  if (!fused) {
-    if ((rc = ws_enter(h, ws_slot, st))) return rc;
-    if ((rc = ensure_workspace(h, w, n))) return rc;      // a reallocation drops the captured graphs (ws_alloc)
-  }
-  WsLeave leave{h, ws_slot, st, !fused};
+  const int ws_slot = fused ? WS_RENDER0 : ws_pick(h, st);
+  RenderWs& w = h->ws[ws_slot].r;
+  WsUse use(h, ws_slot, st, !fused);
+  if ((rc = use.rc)) return rc;
+  if (!fused && (rc = ensure_workspace(h, w, n))) return rc;      // a reallocation drops the captured graphs (ws_alloc)
   rc_shader_prepare();
 
   RenderArgs A{};
@@ -1626,8 +1654,8 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   if (!rays || !mr || !cache_out || !mat_out) return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: null argument");
   if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: negative n_rays");
   if (n == 0) return RC_OK;
-  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: origins/directions/viewdirs/near/far are required");
+  int rc;
+  if ((rc = check_rays(h, rays, "rc_render_material"))) return rc;
   const rc_config& c = h->cfg;
   const int Ks = (int)lround(K * (1.0 - (double)c.diffuse_sample_fraction));
   const int Kd = (int)lround(K * (double)c.diffuse_sample_fraction);
@@ -1644,28 +1672,24 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
                                        "sec_gumbel or sec_resample_inds (secondary trace)");
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
-  int rc;
-  if (h->packed_dirty) {
-    drop_graphs(h);
-    if ((rc = repack(h))) return rc;
-  }
+  if ((rc = ensure_packed(h))) return rc;
   if (!h->have_material) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/MaterialShader/* or params/LightSampler/*");
   if (!h->have_envmap) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/*");
   const int NL = c.num_levels;
   const int S2 = c.num_samples[NL - 1];
   const int64_t np2 = n * S2, nsec = n * (Ks + Kd);
-  RenderWs& w = h->ws[0];
-  ExtraWs& x = h->ws_x;
-  if ((rc = ws_enter(h, 0, st))) return rc;             // shares workspace set 0 (and the secondary set) with the other entry points
-  WsLeave leave{h, 0, st, true};
+  WsUse use(h, WS_RENDER0, st);          // shares set 0 (and the secondary set) with the other entry points
+  if ((rc = use.rc)) return rc;
+  RenderWs& w = use.s.r;
+  ExtraWs& x = ws_extra<ExtraWs>(use.s);
+  RenderWs& ws_sec = h->ws[WS_SECONDARY].r;
   if ((rc = ensure_workspace(h, w, n))) return rc;
-  if ((rc = ws_alloc(h, x.m_pts, 3 * n)) || (rc = ws_alloc(h, x.m_nrm, 3 * n)) || (rc = ws_alloc(h, x.m_feat, 32 * n)) ||
-      (rc = ws_alloc(h, x.m_mat, RC_MAT_CH * n)) || (rc = ws_alloc(h, x.m_feat_all, 32 * np2)) || (rc = ws_alloc(h, x.m_mat_all, RC_MAT_CH * np2)) ||
-      (rc = ws_alloc(h, x.l_feat, 32 * n)) || (rc = ws_alloc(h, x.l_vmf, (int64_t)128 * RC_VMF_CH * n)) ||
-      (rc = ws_alloc(h, x.l_vmf_logit, (int64_t)128 * n)) || (rc = ws_alloc(h, x.sec_origins, 3 * nsec)) || (rc = ws_alloc(h, x.sec_dirs, 3 * nsec)) ||
-      (rc = ws_alloc(h, x.sec_near, nsec)) || (rc = ws_alloc(h, x.sec_far, nsec)) || (rc = ws_alloc(h, x.sec_lights, 3 * nsec)) ||
-      (rc = ws_alloc(h, x.sec_samples, RC_SMP_CH * nsec)) || (rc = ws_alloc(h, x.m_local_view, 3 * n)) || (rc = ws_alloc(h, x.sec_rgb, 3 * nsec)) ||
-      (rc = ws_alloc(h, x.sec_acc, nsec)) || (rc = ws_alloc(h, x.sec_env, 3 * nsec)) || (rc = ensure_workspace(h, h->ws_sec, nsec)))
+  if ((rc = ws_alloc(h, {{x.m_pts, 3 * n}, {x.m_nrm, 3 * n}, {x.m_feat, 32 * n}, {x.m_mat, RC_MAT_CH * n}, {x.m_feat_all, 32 * np2},
+                         {x.m_mat_all, RC_MAT_CH * np2}, {x.l_feat, 32 * n}, {x.l_vmf, (int64_t)128 * RC_VMF_CH * n},
+                         {x.l_vmf_logit, (int64_t)128 * n}, {x.sec_origins, 3 * nsec}, {x.sec_dirs, 3 * nsec}, {x.sec_near, nsec},
+                         {x.sec_far, nsec}, {x.sec_lights, 3 * nsec}, {x.sec_samples, RC_SMP_CH * nsec}, {x.m_local_view, 3 * n},
+                         {x.sec_rgb, 3 * nsec}, {x.sec_acc, nsec}, {x.sec_env, 3 * nsec}})) ||
+      (rc = ensure_workspace(h, ws_sec, nsec)))
     return rc;
   rc_shader_prepare();
 
@@ -1697,7 +1721,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   { int rcs = ensure_side_stream(h); if (rcs) return rcs; }
   hipStream_t side = h->side_stream;
   // Whatever way this function is left once work has been forked onto the side stream, the caller's stream is joined
-  // to it again BEFORE the workspace set is released (declared after `leave`: destroyed first): an early error
+  // to it again BEFORE the workspace set is released (declared after `use`: destroyed first): an early error
   // return must not leave side-stream kernels writing mat_out / sec_env behind a caller that believes `st` orders
   // everything of the call.
   struct SideJoin {
@@ -1806,7 +1830,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
       RC_HIP(h, hipEventRecord(h->ev_side[2], side));
       env_released = true;
     }
-    enqueue_all(h, B, h->ws_sec, st);
+    enqueue_all(h, B, ws_sec, st);
     if (!env_released) {
       // the trace took a launch plan without that spot (per-stage profiling on, a grid layout the level kernels do not
       // cover): the EnvMap behind the trace

@@ -1,7 +1,7 @@
 // Host side of rc_data_backward (rc_data.hip); included by rc_api.hip after rc_interlevel_host.inc.
 //
-// One call = the training forward (enqueue_all's launch-per-stage cache pass on the data set ws_d, the caller's jitter and
-// anneal) -> k_data_loss_bwd (per-ray charb sums, d loss / d density and d loss / d rgb_s of every last-level sample) ->
+// One call = the training forward (enqueue_all's launch-per-stage cache pass on the workspace set WS_DATA, the caller's
+// jitter and anneal) -> k_data_loss_bwd (per-ray charb sums, d loss / d density and d loss / d rgb_s of every last-level sample) ->
 // k_interlevel_reduce (the loss, fixed order) -> with a gradient buffer, per chunk of kDataChunk samples: the shader
 // recompute and backward as dense layers on k_gemm, their weight gradients (K = the chunk's samples, fixed slices),
 // d feature64 += W_n^T d pred_raw, rc_density_backward of the last level and rc_hashgrid_backward of the appearance grid.
@@ -36,11 +36,7 @@ std::vector<GradSeg> shader_grad_segments(rc_handle* h, int* kernel_seg = nullpt
       for (const GradSeg& g : grid_grad_segments(h->grids[3], off)) v.push_back(g);
     }
     if (kernel_seg) kernel_seg[i] = (int)v.size();
-    const std::string base = data_layer_path(h, i);
-    GradSeg k{}; k.name = base + "/kernel"; k.offset = off; k.size = (int64_t)kDataLayers[i].in * kDataLayers[i].out; k.ndim = 2;
-    k.shape[0] = kDataLayers[i].in; k.shape[1] = kDataLayers[i].out; off += k.size; v.push_back(k);
-    GradSeg b{}; b.name = base + "/bias"; b.offset = off; b.size = kDataLayers[i].out; b.ndim = 1; b.shape[0] = kDataLayers[i].out;
-    off += b.size; v.push_back(b);
+    dense_grad_segments(v, off, data_layer_path(h, i), kDataLayers[i].in, kDataLayers[i].out);
   }
   return v;
 }
@@ -73,8 +69,7 @@ int64_t rc_shader_grad_size(rc_handle* h) {
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
   if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_shader_grad_size: not available on a time-resolved cache handle");
-  const std::vector<GradSeg> v = shader_grad_segments(h);
-  return v.back().offset + v.back().size;
+  return grad_size(shader_grad_segments(h));
   RC_CATCH(h)
 }
 
@@ -83,17 +78,7 @@ int rc_shader_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity,
   if (!h) return RC_ERR_INVALID_ARG;
   if (!count) return fail(h, RC_ERR_INVALID_ARG, "rc_shader_grad_layout: null count");
   if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_shader_grad_layout: not available on a time-resolved cache handle");
-  const std::vector<GradSeg> v = shader_grad_segments(h);
-  *count = (int32_t)v.size();
-  if (!segs) return RC_OK;
-  if (capacity < (int32_t)v.size()) return fail(h, RC_ERR_INVALID_ARG, "rc_shader_grad_layout: capacity too small");
-  for (size_t i = 0; i < v.size(); ++i) {
-    memset(&segs[i], 0, sizeof(rc_grad_segment));
-    snprintf(segs[i].name, sizeof(segs[i].name), "%s", v[i].name.c_str());
-    segs[i].offset = v[i].offset; segs[i].size = v[i].size; segs[i].ndim = v[i].ndim;
-    for (int d = 0; d < 4; ++d) segs[i].shape[d] = v[i].shape[d];
-  }
-  return RC_OK;
+  return copy_segments(h, shader_grad_segments(h), segs, capacity, count, "rc_shader_grad_layout");
   RC_CATCH(h)
 }
 
@@ -111,8 +96,8 @@ int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, con
   if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_data_backward: not available on a time-resolved cache handle");
   if (n == 0) return RC_OK;
   if (!gt_rgb || !loss) return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: null gt_rgb/loss");
-  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_data_backward: origins/directions/viewdirs/near/far are required");
+  int rc;
+  if ((rc = check_rays(h, rays, "rc_data_backward"))) return rc;
   const int S2 = c.num_samples[NL - 1];
   if (S2 < 1 || S2 > 32) return fail(h, RC_ERR_UNSUPPORTED, "rc_data_backward: needs <= 32 samples on the last level");
   if (h->grids[NL - 1].dev.num_levels * h->grids[NL - 1].dev.num_features != 32 ||
@@ -121,23 +106,18 @@ int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, con
   RoctxScope roctx_call("rc_data_backward");
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
-  int rc;
-  if (h->packed_dirty) {
-    drop_graphs(h);
-    if ((rc = repack(h))) return rc;
-  }
+  if ((rc = ensure_packed(h))) return rc;
   const bool grads = density_grads || shader_grads;
   if (grads && h->data_gen != h->layers_gen) {
     if ((rc = upload_data_weights(h))) return rc;
     h->data_gen = h->layers_gen;
   }
-  if ((rc = ws_enter(h, 6, st))) return rc;             // the data set: ordered against its previous user
-  WsLeave leave{h, 6, st, true};
-  RenderWs& w = h->ws_d;
-  DataWs& x = h->ws_dx;
+  WsUse use(h, WS_DATA, st);
+  if ((rc = use.rc)) return rc;
+  RenderWs& w = use.s.r;
+  DataWs& x = ws_extra<DataWs>(use.s);
   const int64_t np = n * S2;
-  if ((rc = ensure_workspace(h, w, n)) || (rc = ws_alloc(h, x.rgb, 3 * n)) || (rc = ws_alloc(h, x.loss_ray, n)) ||
-      (rc = ws_alloc(h, x.d_density, np)) || (rc = ws_alloc(h, x.d_rgbs, 3 * np)))
+  if ((rc = ensure_workspace(h, w, n)) || (rc = ws_alloc(h, {{x.rgb, 3 * n}, {x.loss_ray, n}, {x.d_density, np}, {x.d_rgbs, 3 * np}})))
     return rc;
 
   // 1. the training forward: rc_render_rays' launch-per-stage cache pass, no analytic normals
@@ -166,14 +146,12 @@ int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, con
   // 3-5. the shader backward, chunk by chunk
   const int64_t CH = np < kDataChunk ? np : kDataChunk;
   const int64_t nslices = (CH + kDataKSlice - 1) / kDataKSlice;
-  struct { WsBuf* b; int64_t per; } bufs[] = {
-      {&x.f96, 96}, {&x.heads, 10}, {&x.p3, 3}, {&x.ib_in, 129}, {&x.x328, 328}, {&x.s0, 128}, {&x.s1, 128}, {&x.sb, 128},
-      {&x.i1, 64}, {&x.i2, 64}, {&x.io, 1}, {&x.so, 3}, {&x.dheads, 10}, {&x.dio, 1}, {&x.dso, 3}, {&x.dsb, 128},
-      {&x.dx328, 328}, {&x.ds1, 128}, {&x.ds0, 128}, {&x.di2, 64}, {&x.di1, 64}, {&x.dib_in, 129}, {&x.db128, 128},
-      {&x.dp3, 3}, {&x.df96, 96}, {&x.dfeat, 64}, {&x.dapp, 32}};
-  for (auto& e : bufs)
-    if ((rc = ws_alloc(h, *e.b, CH * e.per))) return rc;
-  if ((rc = ws_alloc(h, x.part, nslices * 328 * 128)) || (rc = ws_alloc(h, x.ones, 1)) || (rc = ws_alloc(h, x.points, 3 * np)))
+  if ((rc = ws_alloc(h, {{x.f96, CH * 96}, {x.heads, CH * 10}, {x.p3, CH * 3}, {x.ib_in, CH * 129}, {x.x328, CH * 328},
+                         {x.s0, CH * 128}, {x.s1, CH * 128}, {x.sb, CH * 128}, {x.i1, CH * 64}, {x.i2, CH * 64}, {x.io, CH * 1},
+                         {x.so, CH * 3}, {x.dheads, CH * 10}, {x.dio, CH * 1}, {x.dso, CH * 3}, {x.dsb, CH * 128},
+                         {x.dx328, CH * 328}, {x.ds1, CH * 128}, {x.ds0, CH * 128}, {x.di2, CH * 64}, {x.di1, CH * 64},
+                         {x.dib_in, CH * 129}, {x.db128, CH * 128}, {x.dp3, CH * 3}, {x.df96, CH * 96}, {x.dfeat, CH * 64},
+                         {x.dapp, CH * 32}, {x.part, nslices * 328 * 128}, {x.ones, 1}, {x.points, 3 * np}})))
     return rc;
   RC_HIP(h, hipMemsetD32Async((hipDeviceptr_t)x.ones.p, 0x3f800000, 1, st));     // 1.0f: the A operand of a bias gradient
   rc_launch_points_aos(w.means[NL - 1].p, np, x.points.p, st);

@@ -1,6 +1,6 @@
 // Host side of rc_interlevel_backward (rc_interlevel.hip); included by rc_api.hip after rc_train_host.inc.
 //
-// One call = the training forward (enqueue_all's sampler levels on the interlevel workspace set ws_il, the caller's jitter
+// One call = the training forward (enqueue_all's sampler levels on the workspace set WS_INTERLEVEL, the caller's jitter
 // and anneal) -> k_interlevel_bwd (losses' per-ray sums, d loss / d density of every proposal level) ->
 // k_interlevel_reduce (the losses, fixed order) -> per proposal level with a gradient buffer: the means copied from the
 // workspace's SoA [3][n S] into the AoS [n S][3] rc_density_backward takes (an exact copy: the backward evaluates the
@@ -23,30 +23,22 @@ int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossm
   }
   if (n == 0) return RC_OK;
   if (!losses) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: null losses");
-  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: origins/directions/viewdirs/near/far are required");
+  int rc;
+  if ((rc = check_rays(h, rays, "rc_interlevel_backward"))) return rc;
   if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_interlevel_backward: not available on a time-resolved cache handle");
   if (!rc_interlevel_supported(NL, c.num_samples))
     return fail(h, RC_ERR_UNSUPPORTED, "rc_interlevel_backward: needs >= 2 levels, <= 64 samples per proposal level, <= 32 on the last");
   RoctxScope roctx_call("rc_interlevel_backward");
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
-  int rc;
-  if (h->packed_dirty) {
-    drop_graphs(h);
-    if ((rc = repack(h))) return rc;
-  }
-  if ((rc = ws_enter(h, 5, st))) return rc;             // the interlevel set: ordered against its previous user
-  WsLeave leave{h, 5, st, true};
-  RenderWs& w = h->ws_il;
-  InterlevelWs& x = h->ws_ilx;
+  if ((rc = ensure_packed(h))) return rc;
+  WsUse use(h, WS_INTERLEVEL, st);
+  if ((rc = use.rc)) return rc;
+  RenderWs& w = use.s.r;
+  InterlevelWs& x = ws_extra<InterlevelWs>(use.s);
   for (int l = 0; l < NL; ++l) {
     const int64_t S = c.num_samples[l];
-    const int LF = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
-    if ((rc = ws_alloc(h, w.sdist[l], n * (S + 1))) || (rc = ws_alloc(h, w.tdist[l], n * (S + 1))) ||
-        (rc = ws_alloc(h, w.means[l], 3 * n * S)) || (rc = ws_alloc(h, w.feat[l], (int64_t)LF * n * S)) ||
-        (rc = ws_alloc(h, w.density[l], n * S)) || (rc = ws_alloc(h, w.weights[l], n * S)))
-      return rc;
+    if ((rc = ws_sampler_level(h, w, l, n))) return rc;
     if (l < NL - 1) {
       if ((rc = ws_alloc(h, x.d_density[l], n * S))) return rc;
       if (grads && grads[l] && (rc = ws_alloc(h, x.points[l], 3 * n * S))) return rc;

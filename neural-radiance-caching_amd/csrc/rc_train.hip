@@ -518,7 +518,6 @@ bool rc_train_prepare() {
   const uint64_t bit = 1ull << (dev & 63);
   if (rc_first_use_on_device(prepared)) {
     const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_scatter_sliced<1>), hipFuncAttributeMaxDynamicSharedMemorySize, kSliceFloats * 4) == hipSuccess &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_scatter_sliced<4>), hipFuncAttributeMaxDynamicSharedMemorySize, kSliceFloats * 4) == hipSuccess &&
                     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_scatter_small<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess &&
                     hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grid_scatter_small<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
     if (ok) good.fetch_or(bit);
@@ -526,17 +525,13 @@ bool rc_train_prepare() {
   return (good.load() & bit) != 0;
 }
 
-void rc_launch_grid_scatter(const RcGridScatterArgs& a, hipStream_t stream, hipStream_t small_stream, bool use_small_stream) {
-  const hipStream_t sst = use_small_stream ? small_stream : stream;
+void rc_launch_grid_scatter(const RcGridScatterArgs& a, hipStream_t stream) {
   if (a.n <= 0) return;
   const int G = a.grid.num_features == 4 ? 4 : 2;
   dim3 grid((unsigned)((a.n * G + 255) / 256), (unsigned)a.grid.num_levels), block(256);
-  static const bool sliced_on = !(getenv("RC_SCATTER_SLICED") && getenv("RC_SCATTER_SLICED")[0] == '0');
   const int F = a.grid.num_features;
   uint32_t sliced_levels = 0;
-  // RC_SCATTER_SLICED=4: also the dense levels of an F = 4 grid (experiment: measured slower, below)
-  static const bool sliced_f4 = getenv("RC_SCATTER_SLICED") && getenv("RC_SCATTER_SLICED")[0] == '4';
-  if ((F == 1 || (F == 4 && sliced_f4)) && sliced_on && rc_train_prepare()) {
+  if (F == 1 && rc_train_prepare()) {
     // through k_grid_scatter_sliced: every level of an F = 1 grid (power-of-two hash tables).  The dense levels of an F = 4
     // grid (4-32 adds per row at 32 768 samples) were tried too: 37 slices, every point walked once per slice with four
     // LDS adds per corner -- the level-2 call went from 0.199 to 0.280 ms; they stay with k_grid_scatter<4> / _small<4>.
@@ -545,7 +540,7 @@ void rc_launch_grid_scatter(const RcGridScatterArgs& a, hipStream_t stream, hipS
     for (int l = 0; l < a.grid.num_levels; ++l) {
       const RcGridLevel& L = a.grid.lvl[l];
       const int64_t floats = (int64_t)L.entries * F;
-      const bool take = floats % 64 == 0 && (L.dense ? floats <= (1 << 20) : (F == 1 && L.mask != 0));
+      const bool take = floats % 64 == 0 && (L.dense ? floats <= (1 << 20) : L.mask != 0);
       if (!take) continue;
       sliced_levels |= 1u << l;
       plan.nslice[l] = (int)((floats + kSliceFloats - 1) / kSliceFloats);
@@ -566,36 +561,25 @@ void rc_launch_grid_scatter(const RcGridScatterArgs& a, hipStream_t stream, hipS
         wg += plan.nslice[l] * plan.nparts[l];
       }
       for (int l = a.grid.num_levels; l <= RC_MAX_GRID_LEVELS; ++l) plan.wg_base[l] = wg;
-      const bool all = sliced_levels == (1u << a.grid.num_levels) - 1u;
-      const hipStream_t q = all ? stream : sst;      // beside the other levels' scatter when there are any
-      if (F == 4) hipLaunchKernelGGL(k_grid_scatter_sliced<4>, dim3((unsigned)wg), dim3(kSliceThreads), kSliceFloats * 4, q, a, plan);
-      else hipLaunchKernelGGL(k_grid_scatter_sliced<1>, dim3((unsigned)wg), dim3(kSliceThreads), kSliceFloats * 4, q, a, plan);
-      if (all) return;
+      hipLaunchKernelGGL(k_grid_scatter_sliced<1>, dim3((unsigned)wg), dim3(kSliceThreads), kSliceFloats * 4, stream, a, plan);
+      if (sliced_levels == (1u << a.grid.num_levels) - 1u) return;
     }
   }
   RcGridScatterArgs b = a;
   b.level0 = 0;
   b.lds_levels = sliced_levels;
-  // experiment switches (timing only): RC_SCATTER_SKIP = bit mask of levels whose gradient is NOT computed;
-  // RC_SCATTER_LDS_MAX = largest table (floats) summed in LDS (default 32768 = 128 KiB: 16^3 at F = 1 | 4, 32^3 at F = 1)
-  static const unsigned skip_levels = getenv("RC_SCATTER_SKIP") ? (unsigned)strtoul(getenv("RC_SCATTER_SKIP"), nullptr, 0) : 0u;
-  static const int64_t lds_max = getenv("RC_SCATTER_LDS_MAX") ? atoll(getenv("RC_SCATTER_LDS_MAX")) : 32768;
+  constexpr int64_t kLdsMax = 32768;      // largest table (floats) summed in LDS (128 KiB: 16^3 at F = 1 | 4, 32^3 at F = 1)
   for (int l = 0; l < a.grid.num_levels; ++l) {
     const RcGridLevel& L = a.grid.lvl[l];
     if ((sliced_levels >> l) & 1u) continue;
-    if ((skip_levels >> l) & 1u) { b.lds_levels |= 1u << l; continue; }
-    if (!L.dense || (int64_t)L.entries * a.grid.num_features > lds_max) continue;
+    if (!L.dense || (int64_t)L.entries * a.grid.num_features > kLdsMax) continue;
     const int lds = (int)L.entries * a.grid.num_features * (int)sizeof(float);
     if (lds > 65536 && !rc_train_prepare()) continue;       // no LDS opt-in: the level goes through the global scatter
     b.lds_levels |= 1u << l;
     int wgs = (int)((a.n + 255) / 256);            // one table flush per workgroup: at most one per CU
-    if (wgs > 256) wgs = 256;
-    if (lds > 65536) {                              // beyond the default LDS limit
-      static const int wg_big = getenv("RC_SCATTER_BIG_WGS") ? atoi(getenv("RC_SCATTER_BIG_WGS")) : 256;
-      if (wgs > wg_big) wgs = wg_big;               // (experiment knob; 16 ... 256 workgroups measured: 256 is the fastest)
-    }
-    if (a.grid.num_features == 4) hipLaunchKernelGGL((k_grid_scatter_small<4>), dim3(wgs), dim3(256), lds, sst, b, l);
-    else hipLaunchKernelGGL((k_grid_scatter_small<1>), dim3(wgs), dim3(256), lds, sst, b, l);
+    if (wgs > 256) wgs = 256;                       // (beyond the default LDS limit 16 ... 256 workgroups measured: 256 is the fastest)
+    if (a.grid.num_features == 4) hipLaunchKernelGGL((k_grid_scatter_small<4>), dim3(wgs), dim3(256), lds, stream, b, l);
+    else hipLaunchKernelGGL((k_grid_scatter_small<1>), dim3(wgs), dim3(256), lds, stream, b, l);
   }
   const RcGridScatterArgs& a2 = b;
   if (a.grid.num_features == 4) hipLaunchKernelGGL((k_grid_scatter<4>), grid, block, 0, stream, a2);

@@ -1,4 +1,5 @@
-// Host side of the training backward of one level's density field (rc_train.hip); included by rc_api.hip.
+// Host side of the training backward of one level's density field (rc_train.hip); included by rc_api.hip.  Also the
+// gradient-buffer layouts (GradSeg, dense_grad_segments, copy_segments) that rc_data_host.inc builds on.
 
 namespace {
 
@@ -25,23 +26,42 @@ std::vector<GradSeg> grid_grad_segments(const GridState& gs, int64_t& off) {
   return v;
 }
 
+// dense layer `path`: kernel [in, out], then bias [out]
+void dense_grad_segments(std::vector<GradSeg>& v, int64_t& off, const std::string& path, int in, int out) {
+  GradSeg k{}; k.name = path + "/kernel"; k.offset = off; k.size = (int64_t)in * out; k.ndim = 2; k.shape[0] = in; k.shape[1] = out;
+  off += k.size; v.push_back(k);
+  GradSeg b{}; b.name = path + "/bias"; b.offset = off; b.size = out; b.ndim = 1; b.shape[0] = out;
+  off += b.size; v.push_back(b);
+}
+
+// floats of a gradient buffer
+int64_t grad_size(const std::vector<GradSeg>& v) { return v.back().offset + v.back().size; }
+
 std::vector<GradSeg> density_grad_segments(rc_handle* h, int level) {
   const GridState& gs = h->grids[level];
-  const int F = gs.cfg.num_features;
   int64_t off = 0;
   std::vector<GradSeg> v = grid_grad_segments(gs, off);
-  const int K = (int)gs.sizes.size() * F;
+  const int K = (int)gs.sizes.size() * gs.cfg.num_features;
   const std::string base = "params/Cache/Sampler/MLP_" + std::to_string(level);
-  auto dense = [&](const std::string& name, int in, int out) {
-    GradSeg k{}; k.name = base + "/" + name + "/kernel"; k.offset = off; k.size = (int64_t)in * out; k.ndim = 2; k.shape[0] = in; k.shape[1] = out;
-    off += k.size; v.push_back(k);
-    GradSeg b{}; b.name = base + "/" + name + "/bias"; b.offset = off; b.size = out; b.ndim = 1; b.shape[0] = out;
-    off += b.size; v.push_back(b);
-  };
-  dense("density_layers_0", K, 64);
-  dense("density_layers_1", 64, 64);
-  dense("output_density_layer", 64, 1);
+  dense_grad_segments(v, off, base + "/density_layers_0", K, 64);
+  dense_grad_segments(v, off, base + "/density_layers_1", 64, 64);
+  dense_grad_segments(v, off, base + "/output_density_layer", 64, 1);
   return v;
+}
+
+// rc_*_grad_layout: the segments into the caller's array
+int copy_segments(rc_handle* h, const std::vector<GradSeg>& v, rc_grad_segment* segs, int32_t capacity, int32_t* count, const char* who) {
+  if (!count) return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": null count");
+  *count = (int32_t)v.size();
+  if (!segs) return RC_OK;
+  if (capacity < (int32_t)v.size()) return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": capacity too small");
+  for (size_t i = 0; i < v.size(); ++i) {
+    memset(&segs[i], 0, sizeof(rc_grad_segment));
+    snprintf(segs[i].name, sizeof(segs[i].name), "%s", v[i].name.c_str());
+    segs[i].offset = v[i].offset; segs[i].size = v[i].size; segs[i].ndim = v[i].ndim;
+    for (int d = 0; d < 4; ++d) segs[i].shape[d] = v[i].shape[d];
+  }
+  return RC_OK;
 }
 
 // Stream of k_density_bwd: the forward fragments of every level followed by W1^T, W0^T.
@@ -75,8 +95,7 @@ int64_t rc_density_grad_size(rc_handle* h, int32_t level) {
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
   if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, "rc_density_grad_size: bad level");
-  const std::vector<GradSeg> v = density_grad_segments(h, level);
-  return v.back().offset + v.back().size;
+  return grad_size(density_grad_segments(h, level));
   RC_CATCH(h)
 }
 
@@ -84,18 +103,7 @@ int rc_density_grad_layout(rc_handle* h, int32_t level, rc_grad_segment* segs, i
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
   if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, "rc_density_grad_layout: bad level");
-  if (!count) return fail(h, RC_ERR_INVALID_ARG, "rc_density_grad_layout: null count");
-  const std::vector<GradSeg> v = density_grad_segments(h, level);
-  *count = (int32_t)v.size();
-  if (!segs) return RC_OK;
-  if (capacity < (int32_t)v.size()) return fail(h, RC_ERR_INVALID_ARG, "rc_density_grad_layout: capacity too small");
-  for (size_t i = 0; i < v.size(); ++i) {
-    memset(&segs[i], 0, sizeof(rc_grad_segment));
-    snprintf(segs[i].name, sizeof(segs[i].name), "%s", v[i].name.c_str());
-    segs[i].offset = v[i].offset; segs[i].size = v[i].size; segs[i].ndim = v[i].ndim;
-    for (int d = 0; d < 4; ++d) segs[i].shape[d] = v[i].shape[d];
-  }
-  return RC_OK;
+  return copy_segments(h, density_grad_segments(h, level), segs, capacity, count, "rc_density_grad_layout");
   RC_CATCH(h)
 }
 
@@ -121,22 +129,20 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
     h->train_gen[level] = h->layers_gen;
   }
   const int64_t ld = (n + 63) / 64 * 64;
-  if ((rc = ws_enter(h, 4, st))) return rc;             // the train workspace set: ordered against its previous user
-  WsLeave leave{h, 4, st, true};
-  TrainWs& t = h->ws_train;
+  WsUse use(h, WS_TRAIN, st);
+  if ((rc = use.rc)) return rc;
+  TrainWs& t = ws_extra<TrainWs>(use.s);
   const int nwaves = rc_wgrad_waves(n);
-  if ((rc = ws_alloc(h, t.feat, (int64_t)K * ld)) || (rc = ws_alloc(h, t.dfeat, (int64_t)K * ld)) || (rc = ws_alloc(h, t.a1, n * 64)) ||
-      (rc = ws_alloc(h, t.a2, n * 64)) || (rc = ws_alloc(h, t.d2, n * 64)) || (rc = ws_alloc(h, t.d1, n * 64)) ||
-      (rc = ws_alloc(h, t.fe, n * 32)) || (rc = ws_alloc(h, t.graw, n)) || (rc = ws_alloc(h, t.density, n)) ||
-      (rc = ws_alloc(h, t.partial, rc_wgrad_partial_floats(nwaves))))
+  if ((rc = ws_alloc(h, {{t.feat, (int64_t)K * ld}, {t.dfeat, (int64_t)K * ld}, {t.a1, n * 64}, {t.a2, n * 64}, {t.d2, n * 64},
+                         {t.d1, n * 64}, {t.fe, n * 32}, {t.graw, n}, {t.density, n}, {t.partial, rc_wgrad_partial_floats(nwaves)}})))
     return rc;
 
-  if (!h->train_stream[0]) {
-    bool ok = true;
-    for (int i = 0; i < 2; ++i) { h->train_stream[i] = rc_helper_stream(1 + i); ok = ok && h->train_stream[i]; }
+  if (!h->train_stream) {
+    h->train_stream = rc_helper_stream(1);
+    bool ok = h->train_stream != nullptr;
     for (hipEvent_t& e : h->ev_train) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
-      for (hipStream_t& s : h->train_stream) s = nullptr;
+      h->train_stream = nullptr;
       for (hipEvent_t& e : h->ev_train) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     }
   }
@@ -146,10 +152,10 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
 
   // The whole call as launches on `q` (the caller's stream, or the capture stream of the graph below).
   // The weight gradients (k_wgrad + k_grad_reduce: matrix cores, 40 us) and the table gradients (memory-side atomics) both
-  // read what k_density_bwd left and write disjoint segments of `grads`: the former run on a stream of the handle's own
-  // beside the scatter (highest priority and launched first: k_wgrad is one workgroup per CU, the scatter's threads would
-  // otherwise hold every CU until they have drained), the LDS-accumulated levels of an F = 4 grid on a second one; both
-  // forked from and joined to `q` with events, so to the caller everything of the call is ordered on its stream.
+  // read what k_density_bwd left and write disjoint segments of `grads`: for an F = 1 grid the former run on a stream of the
+  // handle's own beside the scatter (highest priority and launched first: k_wgrad is one workgroup per CU, the scatter's
+  // threads would otherwise hold every CU until they have drained), forked from and joined to `q` with events, so to the
+  // caller everything of the call is ordered on its stream.
   auto enqueue = [&](hipStream_t q) {
     rc_launch_hashgrid(gs.dev, points, 0, n, t.feat.p, 1, ld, h->cfg.contract_radius, nullptr, q);
     RcDensityBwdArgs b{};
@@ -164,25 +170,20 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
     w.a1 = t.a1.p; w.d2 = t.d2.p; w.fe = t.fe.p; w.d1 = t.d1.p; w.a2 = t.a2.p; w.graw = t.graw.p; w.n = n; w.partial = t.partial.p;
     // F = 1 grids: k_wgrad beside k_grid_scatter_sliced (-25 us per call).  F = 4 grids: no fork -- beside k_grid_scatter<4>
     // the weight gradients stretch to the scatter's own length (0.194 ms per call on one stream, 0.198 forked), and a call
-    // that forks TWO helper streams was measured at 0.37 ms in a process that had run the material stage before it
-    // (every kernel of the call 2-3x slower, 100 us of host time between calls; RC_TRAIN_FORK=2 brings that form back).
-    static const bool fork2 = getenv("RC_TRAIN_FORK") && getenv("RC_TRAIN_FORK")[0] == '2';
-    const int nfork = F == 4 ? (fork2 ? 2 : 0) : 1;
-    static const bool no_fork = getenv("RC_TRAIN_FORK") && getenv("RC_TRAIN_FORK")[0] == '0';      // experiment: everything on q
-    bool forked = !no_fork && nfork > 0 && h->train_stream[0] && hipEventRecord(h->ev_train[0], q) == hipSuccess;
-    for (int i = 0; i < nfork && forked; ++i) forked = hipStreamWaitEvent(h->train_stream[i], h->ev_train[0], 0) == hipSuccess;
-    rc_launch_wgrad(w, K, grads + segs[gs.sizes.size()].offset, forked ? h->train_stream[0] : q);
+    // that forked TWO helper streams (the second one for the LDS-accumulated levels) was measured at 0.37 ms in a process
+    // that had run the material stage before it (every kernel of the call 2-3x slower, 100 us of host time between calls).
+    const bool forked = F != 4 && h->train_stream && hipEventRecord(h->ev_train[0], q) == hipSuccess &&
+                        hipStreamWaitEvent(h->train_stream, h->ev_train[0], 0) == hipSuccess;
+    rc_launch_wgrad(w, K, grads + segs[gs.sizes.size()].offset, forked ? h->train_stream : q);
 
     RcGridScatterArgs sa{};
     sa.grid = gs.dev;
     for (size_t l = 0; l < gs.sizes.size(); ++l) sa.gtable[l] = grads + segs[l].offset;
     sa.points = points; sa.n = n; sa.ld = ld; sa.dfeat = t.dfeat.p; sa.contract_radius = h->cfg.contract_radius;
-    rc_launch_grid_scatter(sa, q, h->train_stream[1], forked && nfork == 2);
-    if (forked) {       // join (before the workspace set is released)
-      for (int i = 0; i < nfork; ++i)
-        if (hipEventRecord(h->ev_train[1 + i], h->train_stream[i]) != hipSuccess || hipStreamWaitEvent(q, h->ev_train[1 + i], 0) != hipSuccess)
-          (void)hipStreamSynchronize(h->train_stream[i]);
-    }
+    rc_launch_grid_scatter(sa, q);
+    if (forked &&       // join (before the workspace set is released)
+        (hipEventRecord(h->ev_train[1], h->train_stream) != hipSuccess || hipStreamWaitEvent(q, h->ev_train[1], 0) != hipSuccess))
+      (void)hipStreamSynchronize(h->train_stream);
   };
 
   // (Replaying the call as one hipGraph -- fork and join captured -- was tried against its ~140 us of host time per call:
@@ -196,22 +197,6 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
 // ---------------------------------------------------------------------------------------------------------
 // rc_hashgrid_backward: the transpose of rc_hashgrid_lookup for any of the handle's grids
 // ---------------------------------------------------------------------------------------------------------
-namespace {
-int copy_segments(rc_handle* h, const std::vector<GradSeg>& v, rc_grad_segment* segs, int32_t capacity, int32_t* count, const char* who) {
-  if (!count) return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": null count");
-  *count = (int32_t)v.size();
-  if (!segs) return RC_OK;
-  if (capacity < (int32_t)v.size()) return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": capacity too small");
-  for (size_t i = 0; i < v.size(); ++i) {
-    memset(&segs[i], 0, sizeof(rc_grad_segment));
-    snprintf(segs[i].name, sizeof(segs[i].name), "%s", v[i].name.c_str());
-    segs[i].offset = v[i].offset; segs[i].size = v[i].size; segs[i].ndim = v[i].ndim;
-    for (int d = 0; d < 4; ++d) segs[i].shape[d] = v[i].shape[d];
-  }
-  return RC_OK;
-}
-}  // namespace
-
 int rc_hashgrid_grad_layout(rc_handle* h, int32_t grid_id, rc_grad_segment* segs, int32_t capacity, int32_t* count, int64_t* total) {
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;

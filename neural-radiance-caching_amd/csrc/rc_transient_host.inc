@@ -182,7 +182,7 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipS
   if (t.use_occlusions) {
     // _compute_occlusions: n * S2 shadow rays through the secondary-ray sampler, weights only
     const int64_t nsec = np2;
-    const ExtraWs& x = h->ws_x;
+    const ExtraWs& x = ws_extra<ExtraWs>(h->ws[WS_RENDER0]);
     RcShadowRayArgs sr{};
     sr.n = np2; sr.samples_per_ray = S2; sr.means = w.means[NL - 1].p; sr.normals = w.normals_grad.p; sr.lights = A.rays.lights;
     sr.normal_eps = c.secondary_normal_eps; sr.shadow_near = t.shadow_near; sr.shadow_far = t.shadow_far; sr.light_near = t.light_near;
@@ -197,7 +197,7 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipS
     B.n = nsec; B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY; B.slot = -1; B.fused = false; B.weights_only = true;
     memset(&B.out, 0, sizeof(B.out));
     B.out.ptr[RC_OUT_ACC] = x.sh_acc.p;
-    enqueue_all(h, B, h->ws_sec, st);
+    enqueue_all(h, B, h->ws[WS_SECONDARY].r, st);
     occ = x.sh_acc.p;
   }
   stage_mark(h, A.slot, ST_SHADER, st);
@@ -265,23 +265,22 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   if (!rays || !out) return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: null rays/outputs");
   if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: negative n_rays");
   if (n == 0) return RC_OK;
-  if (!rays->origins || !rays->directions || !rays->viewdirs || !rays->near || !rays->far)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: origins/directions/viewdirs/near/far are required");
+  int rc;
+  if ((rc = check_rays(h, rays, "rc_render_transient"))) return rc;
   if (!rays->lights || !cam_origins) return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: lights and cam_origins are required");
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
-  int rc;
-  if (h->packed_dirty && (rc = repack(h))) return rc;
-  RenderWs& w = h->ws[0];
-  ExtraWs& x = h->ws_x;
-  if ((rc = ws_enter(h, 0, st))) return rc;             // workspace set 0 (and the secondary set): ordered against its previous user
-  WsLeave leave{h, 0, st, true};
+  if ((rc = ensure_packed(h))) return rc;
+  WsUse use(h, WS_RENDER0, st);          // set 0 (and the secondary set) of the other entry points
+  if ((rc = use.rc)) return rc;
+  RenderWs& w = use.s.r;
+  ExtraWs& x = ws_extra<ExtraWs>(use.s);
   if ((rc = ensure_workspace(h, w, n))) return rc;
   if (h->tcfg.use_occlusions) {
     const int64_t nsec = n * h->cfg.num_samples[h->cfg.num_levels - 1];
-    if ((rc = ws_alloc(h, x.sh_origins, 3 * nsec)) || (rc = ws_alloc(h, x.sh_dirs, 3 * nsec)) || (rc = ws_alloc(h, x.sh_near, nsec)) ||
-        (rc = ws_alloc(h, x.sh_far, nsec)) || (rc = ws_alloc(h, x.sh_normals, 3 * nsec)) || (rc = ws_alloc(h, x.sh_lights, 3 * nsec)) ||
-        (rc = ws_alloc(h, x.sh_acc, nsec)) || (rc = ensure_workspace(h, h->ws_sec, nsec)))
+    if ((rc = ws_alloc(h, {{x.sh_origins, 3 * nsec}, {x.sh_dirs, 3 * nsec}, {x.sh_near, nsec}, {x.sh_far, nsec},
+                           {x.sh_normals, 3 * nsec}, {x.sh_lights, 3 * nsec}, {x.sh_acc, nsec}})) ||
+        (rc = ensure_workspace(h, h->ws[WS_SECONDARY].r, nsec)))
       return rc;
   }
   rc_shader_prepare();

@@ -411,20 +411,7 @@ class RadianceCache:
         normals.  Returns dict name -> torch cuda tensor ([n,3] or [n]).  Passing the dict returned by
         an earlier call as `out` reuses its buffers (same pointers -> the captured hipGraph is replayed)."""
         torch = self._torch
-        r = rc_rays()
-        held = {}
-        n = None
-        for k in ("origins", "directions", "viewdirs", "near", "far", "lights", "normals"):
-            v = rays.get(k)
-            if v is None:
-                continue
-            t = self._dev(v)
-            t = t.reshape(-1, 3) if k not in ("near", "far") else t.reshape(-1)
-            held[k] = t
-            setattr(r, k, t.data_ptr())
-            n = t.shape[0] if n is None else n
-            if t.shape[0] != n:
-                raise ValueError(f"ray field {k} has {t.shape[0]} rows, expected {n}")
+        r, held, n = self._rays_struct(rays)
         rnd_p = None
         if randoms is not None:
             rnd = rc_randoms()
@@ -568,39 +555,59 @@ class RadianceCache:
                 raise ValueError(f"ray field {k} has {t.shape[0]} rows, expected {n}")
         return r, held, n
 
+    def _segments(self, query, args, tail=()):
+        """The two calls of an rc_*_grad_layout query (count, then the segments): [(tensor name, offset, shape)]."""
+        cnt = C.c_int32()
+        self._check(query(self._h, *args, None, 0, C.byref(cnt), *tail))
+        segs = (rc_grad_segment * cnt.value)()
+        self._check(query(self._h, *args, segs, cnt.value, C.byref(cnt), *tail))
+        return [(s.name.decode(), int(s.offset), tuple(int(v) for v in s.shape[: s.ndim])) for s in segs]
+
+    def _grad_size(self, level=None):
+        """rc_density_grad_size(level), or rc_shader_grad_size for level None (fixed by the config: asked once)."""
+        sizes = self.__dict__.setdefault("_grad_sizes", {})
+        total = sizes.get(level)
+        if total is None:
+            lib = self.lib
+            total = int(lib.rc_shader_grad_size(self._h) if level is None else lib.rc_density_grad_size(self._h, level))
+            if total < 0:
+                self._check(total)
+            sizes[level] = total
+        return total
+
+    def _grad_buffer(self, flat, total, what="grads"):
+        """A flat gradient buffer of `total` floats: `flat` checked, or a zeroed one when it is None."""
+        torch = self._torch
+        if flat is None:
+            return torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
+        if flat.numel() != total or flat.dtype != torch.float32 or not flat.is_cuda or not flat.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 cuda tensor of {total} elements")
+        return flat
+
+    def _lossmult(self, lossmult, held, n):
+        """Per-ray loss weights [n] (kept alive in `held`), or None."""
+        if lossmult is None:
+            return None
+        lm = self._dev(lossmult).reshape(-1)
+        if lm.shape[0] != n:
+            raise ValueError("lossmult must have one value per ray")
+        held["lossmult"] = lm
+        return lm
+
     def density_grad_layout(self, level: int):
         """rc_density_grad_layout: [(tensor name, offset, shape)] of the gradient buffer of proposal level `level`
         (the reference's parameter-tree names), and its total size in floats."""
-        cnt = C.c_int32()
-        self._check(self.lib.rc_density_grad_layout(self._h, level, None, 0, C.byref(cnt)))
-        segs = (rc_grad_segment * cnt.value)()
-        self._check(self.lib.rc_density_grad_layout(self._h, level, segs, cnt.value, C.byref(cnt)))
-        out = [(s.name.decode(), int(s.offset), tuple(int(v) for v in s.shape[: s.ndim])) for s in segs]
-        total = int(self.lib.rc_density_grad_size(self._h, level))
-        if total < 0:
-            self._check(total)
-        return out, total
+        return self._segments(self.lib.rc_density_grad_layout, (level,)), self._grad_size(level)
 
     def shader_grad_layout(self):
         """rc_shader_grad_layout: [(tensor name, offset, shape)] of the gradient buffer of the data loss's shader side
         (MLP_<last>/pred_normals_layer, the appearance-grid tables, the Cache/Shader dense layers), and its size."""
-        cnt = C.c_int32()
-        self._check(self.lib.rc_shader_grad_layout(self._h, None, 0, C.byref(cnt)))
-        segs = (rc_grad_segment * cnt.value)()
-        self._check(self.lib.rc_shader_grad_layout(self._h, segs, cnt.value, C.byref(cnt)))
-        out = [(s.name.decode(), int(s.offset), tuple(int(v) for v in s.shape[: s.ndim])) for s in segs]
-        total = int(self.lib.rc_shader_grad_size(self._h))
-        if total < 0:
-            self._check(total)
-        return out, total
+        return self._segments(self.lib.rc_shader_grad_layout, ()), self._grad_size()
 
     def hashgrid_grad_layout(self, grid_id: int):
         """rc_hashgrid_grad_layout: [(tensor name, offset, shape)] of the table-gradient buffer of a grid, and its size."""
-        cnt, total = C.c_int32(), C.c_int64()
-        self._check(self.lib.rc_hashgrid_grad_layout(self._h, grid_id, None, 0, C.byref(cnt), C.byref(total)))
-        segs = (rc_grad_segment * cnt.value)()
-        self._check(self.lib.rc_hashgrid_grad_layout(self._h, grid_id, segs, cnt.value, C.byref(cnt), C.byref(total)))
-        return [(s.name.decode(), int(s.offset), tuple(int(v) for v in s.shape[: s.ndim])) for s in segs], int(total.value)
+        total = C.c_int64()
+        return self._segments(self.lib.rc_hashgrid_grad_layout, (grid_id,), (C.byref(total),)), int(total.value)
 
     def hashgrid_backward(self, grid_id: int, points, d_features, grads=None, apply_contraction: bool = True):
         """rc_hashgrid_backward: scatter d L / d features [n, L*F] (the layout hashgrid_lookup returns) into the tables'
@@ -609,11 +616,7 @@ class RadianceCache:
         pts = self._dev(points).reshape(-1, 3).contiguous()
         n = pts.shape[0]
         df = self._dev(d_features).reshape(n, -1).contiguous()
-        _, total = self.hashgrid_grad_layout(grid_id)
-        if grads is None:
-            grads = torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
-        elif grads.numel() != total or grads.dtype != torch.float32 or not grads.is_cuda or not grads.is_contiguous():
-            raise ValueError(f"grads must be a contiguous float32 cuda tensor of {total} elements")
+        grads = self._grad_buffer(grads, self.hashgrid_grad_layout(grid_id)[1])
         g = self.cfg_grid(grid_id)
         if df.shape[1] != g.out_dim:
             raise ValueError(f"d_features must have {g.out_dim} columns")
@@ -637,17 +640,7 @@ class RadianceCache:
         df = None
         if d_feature is not None:
             df = self._dev(d_feature).reshape(n, 64).contiguous()
-        sizes = self.__dict__.setdefault("_grad_sizes", {})        # the layout is fixed by the config: asked once per level
-        total = sizes.get(level)
-        if total is None:
-            total = int(self.lib.rc_density_grad_size(self._h, level))
-            if total < 0:
-                self._check(total)
-            sizes[level] = total
-        if grads is None:
-            grads = torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
-        elif grads.numel() != total or grads.dtype != torch.float32 or not grads.is_cuda or not grads.is_contiguous():
-            raise ValueError(f"grads must be a contiguous float32 cuda tensor of {total} elements")
+        grads = self._grad_buffer(grads, self._grad_size(level))
         dens = torch.empty(n, dtype=torch.float32, device=f"cuda:{self.device}")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rc_density_backward(self._h, level, pts.data_ptr(), n, dd.data_ptr(),
@@ -671,36 +664,15 @@ class RadianceCache:
         levels = tuple(range(nprop)) if levels is None else tuple(levels)
         if len(mults) != nprop or len(blurs) != nprop:
             raise ValueError(f"mults and blurs need {nprop} values")
-        rnd_p = None
-        if jitters is not None:
-            rnd = rc_randoms()
-            for l, j in enumerate(jitters):
-                if j is not None:
-                    t = self._dev(j).reshape(-1)
-                    if t.shape[0] != n:
-                        raise ValueError(f"jitter of level {l} has {t.shape[0]} values, expected {n}")
-                    held[f"jit{l}"] = t
-                    rnd.jitter[l] = t.data_ptr()
-            rnd_p = C.byref(rnd)
-        lm = None
-        if lossmult is not None:
-            lm = self._dev(lossmult).reshape(-1)
-            if lm.shape[0] != n:
-                raise ValueError("lossmult must have one value per ray")
-            held["lossmult"] = lm
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
         flats = list(grads) if grads is not None else [None] * nprop
         ptrs = (C.c_void_p * nprop)()
         for l in range(nprop):
             if l not in levels:
                 flats[l] = None
                 continue
-            total = int(self.lib.rc_density_grad_size(self._h, l))
-            if total < 0:
-                self._check(total)
-            if flats[l] is None:
-                flats[l] = torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
-            elif flats[l].numel() != total or flats[l].dtype != torch.float32 or not flats[l].is_cuda or not flats[l].is_contiguous():
-                raise ValueError(f"grads[{l}] must be a contiguous float32 cuda tensor of {total} elements")
+            flats[l] = self._grad_buffer(flats[l], self._grad_size(l), f"grads[{l}]")
             ptrs[l] = flats[l].data_ptr()
         losses = torch.zeros(max(nprop, 1), dtype=torch.float32, device=f"cuda:{self.device}")
         m = (C.c_float * nprop)(*[float(v) for v in mults])
@@ -739,25 +711,12 @@ class RadianceCache:
         if gt.shape[0] != n:
             raise ValueError("rgb must be [n, 3]")
         held["gt"] = gt
-        lm = None
-        if lossmult is not None:
-            lm = self._dev(lossmult).reshape(-1)
-            if lm.shape[0] != n:
-                raise ValueError("lossmult must have one value per ray")
-            held["lossmult"] = lm
+        lm = self._lossmult(lossmult, held, n)
         flats = [None, None]
         if grads is not False:
-            sizes = (int(self.lib.rc_density_grad_size(self._h, self.cfg.num_levels - 1)), int(self.lib.rc_shader_grad_size(self._h)))
             given = list(grads) if grads is not None else [None, None]
-            for i, total in enumerate(sizes):
-                if total < 0:
-                    self._check(total)
-                f = given[i]
-                if f is None:
-                    f = torch.zeros(total, dtype=torch.float32, device=f"cuda:{self.device}")
-                elif f.numel() != total or f.dtype != torch.float32 or not f.is_cuda or not f.is_contiguous():
-                    raise ValueError(f"grads[{i}] must be a contiguous float32 cuda tensor of {total} elements")
-                flats[i] = f
+            for i, level in enumerate((self.cfg.num_levels - 1, None)):
+                flats[i] = self._grad_buffer(given[i], self._grad_size(level), f"grads[{i}]")
         loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rc_data_backward(self._h, C.byref(r), gt.data_ptr(), None if lm is None else lm.data_ptr(), n,
