@@ -40,11 +40,14 @@ def jitters(n, levels=3, seed=7):
     return [rng.uniform(size=(n, 1)).astype(np.float32) for _ in range(levels)]
 
 
-def oracle_cache(n_rays, dtype=torch.float32, jitter_seed=None, density_shift=0.0, seed=20200823, **kw):
-    cfg = nrc_amd.hotdog_config()
+def oracle_cache(n_rays, dtype=torch.float32, jitter_seed=None, density_shift=0.0, seed=20200823, cfg=None, weights=None,
+                 **kw):
+    """The cache-only render of the oracle; `cfg` / `weights` (numpy dict) default to the hotdog config and weights_np."""
+    cfg = nrc_amd.hotdog_config() if cfg is None else cfg
     rays = nrc_amd.synthetic_rays(n_rays, seed=seed)
     jit = None if jitter_seed is None else [torch.from_numpy(j) for j in jitters(n_rays, seed=jitter_seed)]
-    return cache_ref.material_model_cache_only(weights_torch(density_shift), cfg, rays_torch(rays, dtype), jit, **kw)
+    w = weights_torch(density_shift) if weights is None else to_torch(weights)
+    return cache_ref.material_model_cache_only(w, cfg, rays_torch(rays, dtype), jit, **kw)
 
 
 def rays_dict_torch(rays: dict, dtype=torch.float32):
@@ -88,13 +91,14 @@ def oracle_transient(n_rays, jitter_seed=None, seed=20200823, smooth=False, dtyp
     cfg = nrc_amd.cornell_transient_config(use_occlusions=occlusions)
     rays = nrc_amd.synthetic_transient_rays(n_rays, seed=seed)
     jit = None if jitter_seed is None else [torch.from_numpy(j).to(dtype) for j in jitters(n_rays, seed=jitter_seed)]
-    sj = None if shadow_jitter_seed is None else [torch.from_numpy(j).to(dtype) for j in shadow_jitters(n_rays * 32, shadow_jitter_seed)]
+    sj =None if shadow_jitter_seed is None else [torch.from_numpy(j).to(dtype) for j in shadow_jitters(n_rays * 32, shadow_jitter_seed)]
     return transient_ref.transient_forward(to_torch(weights_transient_np(smooth, density_shift), dtype), cfg, rays_torch(rays, dtype), jit, sj)
 
 
-def make_rc(density_shift=0.0):
-    """GPU handle with the synthetic hotdog weights loaded (gpu tests only)."""
+def make_rc(density_shift=0.0, cfg=None, weights=None):
+    """GPU handle with the synthetic hotdog weights loaded (gpu tests only); `cfg` / `weights` replace the hotdog
+    config and its weights_np(density_shift)."""
     from nrc_amd import rc_ext
-    rc = rc_ext.RadianceCache(nrc_amd.hotdog_config(), 0)
-    rc.load_weights(weights_np(density_shift))
+    rc = rc_ext.RadianceCache(nrc_amd.hotdog_config() if cfg is None else cfg, 0)
+    rc.load_weights(weights_np(density_shift) if weights is None else weights)
     return rc
