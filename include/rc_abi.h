@@ -285,7 +285,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * name = [prefix]<buffer>.  Prefix: none = set 0 (rc_render_rays on the first caller stream, rc_render_material,
  * rc_render_transient), "p1:" .. "p3:" = the sets of rc_render_rays on further caller streams, "s:" = the batched
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
- * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer.
+ * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
+ * "o:" = rc_adam_update / rc_load_params_flat.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -305,6 +306,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "d_pred" ([n S][3] d loss / d pred_raw), "points" ([n S][3]); of the last sample chunk: "h64" ([C][64] hidden vectors in
  * the reference's column order), "dfeat" ([C][64] d loss / d feature64), "part", "ones"; rc_density_regularizer's
  * "reg_part" (per-table partial sums, doubles).
+ * "o:": "part" (per-tile sums of g^2 of the norm clip, doubles), "norm" ([1] the global norm), "mult" ([1] the clip
+ * multiplier), "stage" (the dense segments of rc_load_params_flat gathered when they are not contiguous).
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -574,6 +577,60 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
  * ACCUMULATED into each table's segment of it (layout rc_density_grad_layout(level)); the MLP segments are untouched.
  * Ordered on `stream`; the time-resolved cache handle is unsupported. */
 int rc_density_regularizer(rc_handle* h, int32_t level, float mult, float* density_grads, float* loss, void* stream);
+
+/* ---- the optimizer step of the cache stage -------------------------------------------------------
+ * rc_adam_update: what train_step does with the gradients after pmean (internal/train_utils.py:3154-3161):
+ * tree_map(nan_to_num) (NaN -> 0, +-inf -> +-FLT_MAX), clip_gradients (train_utils.py:1274-1298: clip by value when
+ * grad_max_val > 0, then by the global norm when grad_max_norm > 0, mult = min(1, grad_max_norm / (FLT_EPSILON + norm)),
+ * norm = sqrt(sum g^2) over ALL buffers of the call -- pass one top-level module per call), then optax.adam
+ * (scale_by_adam with eps_root = 0, scale_by_learning_rate) and apply_updates, per element in float32:
+ *   mu = (1-b1) g + b1 mu;  nu = (1-b2) (g g) + b2 nu;  p = p + ((mu / bc1) / (sqrt(nu / bc2) + eps)) * (-lr)
+ * with the scalars of the element's group.  ONE launch over all buffers (two more with the norm clip: per-tile sums of
+ * g^2 in double and a fixed-order reduce that leaves the multiplier on the device, rc_workspace_ptr "o:mult" / "o:norm";
+ * bitwise reproducible).  Dense: every element moves every step.  zero_grads != 0 writes g = 0 afterwards, so the next
+ * step's backward calls can accumulate into the same buffers.  Everything is ordered on `stream`; no host sync.
+ *   bufs[k]: DEVICE float32 arrays of n elements each, 16-byte aligned; the HOST arrays seg_offset / seg_size /
+ *            seg_group (nseg entries) cover [0, n) in order without gaps (a gradient layout's segments, each with the
+ *            optimizer group of its tensor); at most RC_ADAM_MAX_BUFFERS buffers and 32 runs of consecutive segments
+ *            of one group over all of them.
+ *   step:    HOST struct.  Per group g < ngroups: lr at this step's count t (the caller's schedule), the decays, 1 - b
+ *            rounded from the caller's (double) value as optax does, eps, and the bias corrections 1 - b^(t+1). */
+#define RC_ADAM_MAX_BUFFERS 8
+#define RC_ADAM_MAX_GROUPS 8
+typedef struct {
+  float* params;
+  float* grads;
+  float* mu;
+  float* nu;
+  int64_t n;
+  int32_t nseg;
+  const int64_t* seg_offset;
+  const int64_t* seg_size;
+  const int32_t* seg_group;
+} rc_adam_buffer;
+typedef struct {
+  int32_t ngroups;
+  float lr[RC_ADAM_MAX_GROUPS];
+  float b1[RC_ADAM_MAX_GROUPS], b2[RC_ADAM_MAX_GROUPS];
+  float one_minus_b1[RC_ADAM_MAX_GROUPS], one_minus_b2[RC_ADAM_MAX_GROUPS];
+  float eps[RC_ADAM_MAX_GROUPS];
+  float bias_correction1[RC_ADAM_MAX_GROUPS], bias_correction2[RC_ADAM_MAX_GROUPS];
+  float grad_max_val;          /* <= 0: off */
+  float grad_max_norm;         /* <= 0: off */
+  int32_t zero_grads;
+} rc_adam_step;
+int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const rc_adam_step* step, void* stream);
+
+/* rc_load_params_flat: rc_load_weights of every tensor of one gradient layout, from a DEVICE buffer in that layout
+ * (layout = density level l: rc_density_grad_layout(l); RC_LAYOUT_SHADER: rc_shader_grad_layout).  The grid tables
+ * are copied device to device into the handle's table buffers, ordered on `stream`; the dense-layer segments go to
+ * the host in ONE copy (gathered on the device first when they are not contiguous), after which the call waits for
+ * `stream` (the host repack needs them).  The derived tables (cell tables, level-2 pairs, cell records) and packs are
+ * marked stale and captured graphs dropped, as rc_load_weights does: the next render or backward call on any stream
+ * computes bitwise what it would after rc_load_weights of the same tensors.  The time-resolved cache handle is
+ * unsupported. */
+#define RC_LAYOUT_SHADER (-1)
+int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void* stream);
 
 #ifdef __cplusplus
 }

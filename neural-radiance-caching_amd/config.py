@@ -211,6 +211,85 @@ class GeometryLossConfig:
     density_grid_mult: float = 1.0
 
 
+@dataclasses.dataclass(frozen=True)
+class ExtraOptParams:
+    """One entry of Config.extra_opt_params (configs/ngp_yobo.gin:59-115): the Adam of the tensors whose path holds
+    `prefix` as a whole element, and its schedule; the _material values replace the others when a material stage trains
+    (engine/trainer.py:362-366)."""
+    prefix: str
+    lr_init: float
+    lr_final: float
+    lr_delay_steps: int
+    lr_init_material: float
+    lr_final_material: float
+    lr_delay_steps_material: int
+
+
+@dataclasses.dataclass(frozen=True)
+class OptimizerConfig:
+    """The optimizer of the hotdog cache stage (train_utils.create_optimizer, internal/train_utils.py:3834-3934) with
+    the values the gin chain resolves to, before the trainer's scaling (applied by `groups()` as
+    engine/trainer.py:209-236 and :337-368 apply it)."""
+    # Config.adam_beta1 / adam_beta2 / adam_eps (configs/ngp_yobo.gin:18-20)
+    b1: float = 0.9
+    b2: float = 0.99
+    eps: float = 1e-15
+    # the main Adam: Config.lr_init / lr_final / lr_delay_steps / lr_delay_mult (ngp_yobo.gin:44-47), Config.max_steps
+    # (ngp_yobo.gin:57); lr_delay_mult and max_steps serve every group (no group of the gin overrides them)
+    lr_init: float = 0.01
+    lr_final: float = 1e-3
+    lr_delay_steps: int = 2500
+    lr_delay_mult: float = 1e-8
+    max_steps: int = 25000
+    # Config.extra_opt_params in gin order (ngp_yobo.gin:59-115): folded one after another, the last prefix on a path wins
+    extra_opt_params: Tuple[ExtraOptParams, ...] = (
+        ExtraOptParams("Cache", 0.01, 1e-4, 2500, 0.002, 2e-5, 0),
+        ExtraOptParams("SurfaceLightField", 0.01, 1e-4, 2500, 0.002, 2e-5, 0),
+        ExtraOptParams("LightSampler", 0.01, 1e-4, 2500, 0.002, 2e-5, 0),
+        ExtraOptParams("SurfaceLightFieldMem", 0.01, 1e-4, 2500, 0.01, 1e-4, 0),
+        ExtraOptParams("EnvMap", 5e-4, 5e-6, 2500, 0.002, 2e-5, 0),
+        ExtraOptParams("MaterialShader", 5e-4, 5e-6, 2500, 0.002, 2e-5, 0),
+    )
+    # Config.grad_max_val / grad_max_norm (ngp_yobo.gin:53-54): both clips off for hotdog
+    grad_max_val: float = 0.0
+    grad_max_norm: float = 0.0
+    # the trainer's scaling (engine/trainer.py:209-236): scale_factor = base_batch_size // ((batch_size *
+    # grad_accum_steps) // secondary_grad_accum_steps) (ngp_yobo.gin:6, :52-57); lr_factor = Config.lr_factor *
+    # lr_factor_mult (ngp_yobo.gin:15, internal/configs.py:267); Config.train_length_mult (ngp_yobo.gin:16)
+    base_batch_size: int = 65536
+    batch_size: int = 65536
+    grad_accum_steps: int = 1
+    secondary_grad_accum_steps: int = 1
+    lr_factor: float = 1.0
+    train_length_mult: int = 1
+    # a material stage trains (use_material and not from_scratch): the _material values (trainer.py:362-366)
+    material: bool = False
+
+    @property
+    def scale_factor(self) -> int:
+        return self.base_batch_size // ((self.batch_size * self.grad_accum_steps) // self.secondary_grad_accum_steps)
+
+    def scaled_steps(self, steps: int) -> int:
+        return (steps * self.scale_factor) // self.train_length_mult
+
+    def scaled_lr(self, lr: float) -> float:
+        return (lr / self.scale_factor) * self.lr_factor
+
+    def groups(self):
+        """[(group name, dict(lr_init, lr_final, max_steps, lr_delay_steps, lr_delay_mult))]: "main" first, then
+        the extra_opt_params prefixes in gin order, each schedule as the trainer hands it to create_optimizer."""
+        max_steps = self.scaled_steps(self.max_steps)
+        out = [("main", dict(lr_init=self.scaled_lr(self.lr_init), lr_final=self.scaled_lr(self.lr_final),
+                             max_steps=max_steps, lr_delay_steps=self.scaled_steps(self.lr_delay_steps),
+                             lr_delay_mult=self.lr_delay_mult))]
+        for e in self.extra_opt_params:
+            li, lf, ld = ((e.lr_init_material, e.lr_final_material, e.lr_delay_steps_material) if self.material
+                          else (e.lr_init, e.lr_final, e.lr_delay_steps))
+            out.append((e.prefix, dict(lr_init=self.scaled_lr(li), lr_final=self.scaled_lr(lf), max_steps=max_steps,
+                                       lr_delay_steps=self.scaled_steps(ld), lr_delay_mult=self.lr_delay_mult)))
+        return out
+
+
 def hotdog_config(**overrides) -> RenderConfig:
     """configs/nerf_ngp_yobo_hotdog.gin resolved at render time (train=False)."""
     return dataclasses.replace(RenderConfig(), **overrides)

@@ -92,19 +92,22 @@ struct DataWs {
 // d density and d loss / d pred_raw, the means as points [n S][3]; one sample chunk of the hidden vectors h64 and
 // d feature64, the weight-gradient K-slices and a column of ones; rc_density_regularizer's per-table partial sums.
 struct GeometryWs { WsBuf loss_ray, d_density, d_pred, points, h64, dfeat, part, ones, reg_part; };
+// rc_adam_update: the per-tile sums of g^2 (doubles), the norm and the clip multiplier; rc_load_params_flat: the dense
+// segments of a layout gathered for the one copy to the host.
+struct OptimWs { WsBuf part, norm, mult, stage; };
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
 // serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
 // WS_TRAIN serves rc_density_backward (TrainWs only), WS_INTERLEVEL rc_interlevel_backward, WS_DATA rc_data_backward,
-// WS_GEOMETRY rc_geometry_backward and rc_density_regularizer.
-enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_COUNT };
+// WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat.
+enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -123,7 +126,7 @@ struct WsName {
   const char* name;
   WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
   WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr; WsBuf DataWs::*d = nullptr;
-  WsBuf GeometryWs::*g = nullptr;
+  WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -132,6 +135,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf (InterlevelWs::*m)[RC_MAX_LEVELS]) : name(s), ilv(m) {}
   constexpr WsName(const char* s, WsBuf DataWs::*m) : name(s), d(m) {}
   constexpr WsName(const char* s, WsBuf GeometryWs::*m) : name(s), g(m) {}
+  constexpr WsName(const char* s, WsBuf OptimWs::*m) : name(s), o(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -140,7 +144,8 @@ struct WsName {
       if (t) return one(s, t);
       if (i) return one(s, i);
       if (d) return one(s, d);
-      return g ? one(s, g) : nullptr;
+      if (g) return one(s, g);
+      return o ? one(s, o) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -149,7 +154,7 @@ struct WsName {
   template <class X> static WsBuf* one(WsSet& s, WsBuf X::*m) { X* p = std::get_if<X>(&s.x); return p ? &(p->*m) : nullptr; }
 };
 namespace wsn {
-using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs;
+using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -167,10 +172,10 @@ constexpr WsName kTable[] = {
     WS(D, dio), WS(D, dso), WS(D, dsb), WS(D, dx328), WS(D, ds1), WS(D, ds0), WS(D, di2), WS(D, di1), WS(D, dib_in),
     WS(D, db128), WS(D, dp3), WS(D, df96), WS(D, dfeat), WS(D, dapp), WS(D, part), WS(D, ones),
     WS(G, loss_ray), WS(G, d_density), WS(G, d_pred), WS(G, points), WS(G, h64), WS(G, dfeat), WS(G, part), WS(G, ones),
-    WS(G, reg_part)};
+    WS(G, reg_part), WS(O, part), WS(O, norm), WS(O, mult), WS(O, stage)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G), "the table lists every workspace buffer");
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O), "the table lists every workspace buffer");
 }  // namespace wsn
 
 constexpr int kEvSlots = 16;
@@ -211,6 +216,8 @@ struct rc_handle {
   DevBuf data_w;                             // rc_data_backward: the shader's dense layers on the Flax layout
   uint64_t geom_gen = 0;                     // layers_gen geom_w was uploaded at
   DevBuf geom_w;                             // rc_geometry_backward: pred_normals_layer kernel [64][3] + bias [3]
+  float* pinned = nullptr;                   // rc_load_params_flat: page-locked landing buffer of the dense segments
+  size_t pinned_bytes = 0;
   bool have_envmap = false;
   bool have_material = false;
   // packed MFMA fragments (device)
@@ -1038,6 +1045,7 @@ void rc_destroy(rc_handle* h) {
   if (h->ide_table.p) (void)hipFree(h->ide_table.p);
   free_buf(h->data_w);
   free_buf(h->geom_w);
+  if (h->pinned) (void)hipHostFree(h->pinned);
   drop_graphs(h);
   for (WsSet& s : h->ws) if (s.done) (void)hipEventDestroy(s.done);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
@@ -1882,3 +1890,4 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_interlevel_host.inc"
 #include "rc_data_host.inc"
 #include "rc_geometry_host.inc"
+#include "rc_optim_host.inc"

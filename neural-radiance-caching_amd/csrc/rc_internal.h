@@ -526,6 +526,25 @@ int rc_grid_l2_blocks();                   // partial sums per table of rc_launc
 void rc_launch_grid_l2_bwd(const float* x, int64_t count, float gscale, float* grad, double* part, hipStream_t st);
 void rc_launch_grid_l2_reduce(const double* part, const RcGridL2Reduce& r, float* loss, hipStream_t st);
 
+// The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
+constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
+struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };
+struct RcAdamGroup { float lr, b1, b2, omb1, omb2, eps, bc1, bc2; };   // omb = 1 - b (rounded from the caller's double)
+struct RcAdamArgs {
+  RcAdamBuf buf[kRcAdamMaxBufs];
+  int nbuf;
+  int64_t run_end[kRcAdamMaxRuns];        // exclusive end of run r within its buffer
+  int run_group[kRcAdamMaxRuns];
+  RcAdamGroup group[kRcAdamMaxGroups];
+  float max_val;                          // > 0: clip by value
+  const float* mult;                      // the norm-clip multiplier on the device, or nullptr (no clip by norm)
+  int zero_grads;
+};
+int64_t rc_adam_tile();                   // floats per workgroup tile of k_adam / k_adam_sumsq
+void rc_launch_adam(const RcAdamArgs& a, int64_t blocks, hipStream_t st);
+void rc_launch_adam_norm(const RcAdamArgs& a, int64_t blocks, float max_norm, double* part, float* mult, float* norm,
+                         hipStream_t st);
+
 // Random fill (rc_prng.hip)
 enum { RC_PRNG_BITS = 0, RC_PRNG_UNIFORM = 1, RC_PRNG_NORMAL = 2, RC_PRNG_GUMBEL = 3 };
 struct RcPrngArgs {

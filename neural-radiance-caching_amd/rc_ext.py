@@ -151,6 +151,22 @@ class rc_geometry_loss(C.Structure):
                                          "pred_normal_mult", "pred_normal_w_grad_weight", "pred_normal_reverse_mult")]
 
 
+RC_ADAM_MAX_GROUPS = 8
+RC_LAYOUT_SHADER = -1
+
+
+class rc_adam_buffer(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
+                ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
+
+
+class rc_adam_step(C.Structure):
+    _fields_ = ([("ngroups", C.c_int32)]
+                + [(k, C.c_float * RC_ADAM_MAX_GROUPS) for k in ("lr", "b1", "b2", "one_minus_b1", "one_minus_b2", "eps",
+                                                                 "bias_correction1", "bias_correction2")]
+                + [("grad_max_val", C.c_float), ("grad_max_norm", C.c_float), ("zero_grads", C.c_int32)])
+
+
 EXPORTS = (
     "rc_create", "rc_destroy", "rc_last_error", "rc_abi_version", "rc_mlp_arithmetic", "rc_load_weights", "rc_render_rays", "rc_render_chunks",
     "rc_hashgrid_lookup", "rc_sample_intervals", "rc_workspace_ptr", "rc_set_profiling", "rc_stage_count",
@@ -158,6 +174,7 @@ EXPORTS = (
     "rc_prng_fill", "rc_density_grad_size", "rc_density_grad_layout", "rc_density_backward",
     "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs", "rc_interlevel_backward",
     "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward", "rc_geometry_backward", "rc_density_regularizer",
+    "rc_adam_update", "rc_load_params_flat",
 )
 
 _LIB = None
@@ -268,6 +285,10 @@ def load_library():
     lib.rc_geometry_backward.restype = C.c_int
     lib.rc_density_regularizer.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rc_density_regularizer.restype = C.c_int
+    lib.rc_adam_update.argtypes = [C.c_void_p, C.POINTER(rc_adam_buffer), C.c_int32, C.POINTER(rc_adam_step), C.c_void_p]
+    lib.rc_adam_update.restype = C.c_int
+    lib.rc_load_params_flat.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.rc_load_params_flat.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -322,6 +343,29 @@ def transient_config_to_c(t) -> rc_transient_config:
               "brdf_bias", "irradiance_bias", "slf_rgb_bias", "occ_threshold", "shadow_near", "shadow_far"):
         setattr(c, k, float(getattr(t, k)))
     return c
+
+
+class AdamTable:
+    """The rc_adam_buffer array of a fixed set of flat buffers, built once (the segment arrays stay alive with it)."""
+
+    def __init__(self, buffers):
+        if not 1 <= len(buffers) <= 8:
+            raise ValueError("1 to 8 buffers per rc_adam_update call")
+        self.bufs = (rc_adam_buffer * len(buffers))()
+        self._keep = []
+        for i, (p, g, m, v, segs) in enumerate(buffers):
+            n = p.numel()
+            for t in (p, g, m, v):
+                if t.numel() != n or not t.is_cuda or not t.is_contiguous() or str(t.dtype) != "torch.float32":
+                    raise ValueError("params, grads, mu, nu: contiguous float32 cuda tensors of one size")
+            off = np.ascontiguousarray([s[0] for s in segs], dtype=np.int64)
+            size = np.ascontiguousarray([s[1] for s in segs], dtype=np.int64)
+            grp = np.ascontiguousarray([s[2] for s in segs], dtype=np.int32)
+            self._keep += [p, g, m, v, off, size, grp]
+            b = self.bufs[i]
+            b.params, b.grads, b.mu, b.nu = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+            b.n, b.nseg = n, len(segs)
+            b.seg_offset, b.seg_size, b.seg_group = off.ctypes.data, size.ctypes.data, grp.ctypes.data
 
 
 class RcError(RuntimeError):
@@ -782,6 +826,42 @@ class RadianceCache:
         self._check(self.lib.rc_density_regularizer(self._h, int(level), float(mult),
                                                     None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
         return flat, loss
+
+    # -- optimizer ------------------------------------------------------------------------------
+    def adam_update(self, buffers, step: Dict[str, object], stream_handle=None):
+        """rc_adam_update: one launch of the Adam step over flat buffers (plus two with the norm clip).
+        buffers: [(params, grads, mu, nu, segments)] -- contiguous float32 cuda tensors of one size each and
+        segments = [(offset, size, group)] covering the buffer in order (AdamTable builds them once);
+        step: per-group lists lr, b1, b2, one_minus_b1, one_minus_b2, eps, bias_correction1, bias_correction2
+        (float32 values of the reference's expressions, nrc_amd.train.adam_scalars) and grad_max_val, grad_max_norm,
+        zero_grads.  Ordered on the current stream."""
+        table = buffers if isinstance(buffers, AdamTable) else AdamTable(buffers)
+        st = rc_adam_step()
+        st.ngroups = len(step["lr"])
+        if not 1 <= st.ngroups <= RC_ADAM_MAX_GROUPS:
+            raise ValueError(f"1 to {RC_ADAM_MAX_GROUPS} groups")
+        for k in ("lr", "b1", "b2", "one_minus_b1", "one_minus_b2", "eps", "bias_correction1", "bias_correction2"):
+            arr = getattr(st, k)
+            for g, v in enumerate(step[k]):
+                arr[g] = float(v)
+        st.grad_max_val = float(step.get("grad_max_val", 0.0))
+        st.grad_max_norm = float(step.get("grad_max_norm", 0.0))
+        st.zero_grads = int(bool(step.get("zero_grads", False)))
+        stream = self._torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), stream))
+
+    def load_params_flat(self, layout, params, stream_handle=None):
+        """rc_load_params_flat: load every tensor of one gradient layout (a density level, or "shader") from a flat
+        float32 cuda buffer in that layout -- table copies ordered on the current stream, the dense layers in one copy
+        to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
+        same tensors, bitwise."""
+        torch = self._torch
+        lay = RC_LAYOUT_SHADER if layout == "shader" else int(layout)
+        total = self._grad_size(None if lay == RC_LAYOUT_SHADER else lay)
+        if params.numel() != total or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
+            raise ValueError(f"params must be a contiguous float32 cuda tensor of {total} elements")
+        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        self._check(self.lib.rc_load_params_flat(self._h, lay, params.data_ptr(), stream))
 
     def prng_fill(self, key, shape, mode: str = "uniform", minval: float = 0.0, maxval: float = 1.0):
         """rc_prng_fill: the tensor jax.random.{bits,uniform,normal,gumbel}(key, shape) of the reference's pinned jax

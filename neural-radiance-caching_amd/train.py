@@ -32,8 +32,18 @@ model followed by `jax.lax.pmean(grad, "batch")` across devices and the optimize
 These terms are all first order here (the analytic normals are stop-gradiented where they appear).  The
 predicted-normal terms follow that first-order reading; whether it matches the reference is not settled (DESIGN.md,
 Oddities: train_utils.py:1060-1070 passes gt="normals_pred", pred="normals" to the forward term, and
-nerf_ngp_yobo.gin:57 disables the analytic normals).  A cache-stage step
-is `cache_stage_grads` + an optimizer of the caller's choice; the optimizer is not part of this row.
+nerf_ngp_yobo.gin:57 disables the analytic normals).
+
+The optimizer:
+
+  * `learning_rate_decay(step, ...)` -> math.learning_rate_decay (internal/math.py:356-409) in float32;
+    `param_group(name, cfg)` -> which of create_optimizer's chained Adams (train_utils.py:3834-3934) updates a tensor;
+    `adam_scalars(count, cfg)` -> the per-group float32 scalars of one step;
+  * `CacheStageOptimizer(rc, cfg)` -> flat params / mu / nu in the four gradient layouts, one rc_adam_update per step
+    (nan_to_num, clip_gradients, optax.adam, apply_updates) and the stream-ordered refresh of the handle
+    (rc_load_params_flat per layout);
+  * `cache_stage_step(rc, opt, rays, rgb, jitters)` -> one reference train step (train_utils.py:3128-3161) of the
+    cache stage: cache_stage_grads into the optimizer's gradient buffers, the pmean, the update.
 """
 from __future__ import annotations
 
@@ -42,7 +52,7 @@ from typing import Dict, Iterable, List, Optional
 
 import numpy as np
 
-from .config import DataLossConfig, GeometryLossConfig, InterlevelConfig
+from .config import DataLossConfig, GeometryLossConfig, InterlevelConfig, OptimizerConfig
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -240,3 +250,164 @@ def cache_stage_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, 
     losses.update({f"cache_main_{k}": v for k, v in main.items()})
     losses["regularizer/density_grid"] = reg[0]
     return flats, losses
+
+
+# ---- the optimizer ---------------------------------------------------------------------------------------------------
+
+def learning_rate_decay(step, lr_init: float, lr_final: float, max_steps: int, lr_delay_steps: int = 0,
+                        lr_delay_mult: float = 1.0) -> np.float32:
+    """math.learning_rate_decay (internal/math.py:356-409) as jax evaluates it on optax's int32 count, in float32:
+    delay_rate * log_lerp(step / max_steps, lr_init, lr_final), log_lerp(t, a, b) = exp(clip(t, 0, 1) (log b - log a)
+    + log a), delay_rate = mult + (1 - mult) sin(pi/2 clip(step / delay_steps, 0, 1)) when delay_steps > 0, else 1."""
+    f = np.float32
+    if lr_init == 0.0 and lr_final == 0.0:
+        return f(0.0)
+    if lr_init <= 0 or lr_final <= 0:
+        raise ValueError(f"Interpolants {lr_init} and {lr_final} must be positive.")
+    if lr_delay_steps > 0:
+        x = np.clip(f(step) / f(lr_delay_steps), f(0), f(1))
+        delay_rate = f(lr_delay_mult) + f(1 - lr_delay_mult) * np.sin(f(0.5 * np.pi) * x)
+    else:
+        delay_rate = f(1.0)
+    lv0, lv1 = np.log(f(lr_init)), np.log(f(lr_final))
+    t = np.clip(f(step) / f(max_steps), f(0), f(1))
+    return f(delay_rate * np.exp(t * (lv1 - lv0) + lv0))
+
+
+def train_frac_at(step: int, max_steps: int) -> float:
+    """clip(step / (max_steps - 1), 0, 1) (engine/trainer.py:2116-2126): what the anneal and the normal-loss ease read."""
+    return float(min(max(step / (max_steps - 1), 0.0), 1.0))
+
+
+def param_group(name: str, cfg: OptimizerConfig = OptimizerConfig()) -> str:
+    """The Adam that updates tensor `name` ("params/Cache/..." or "Cache/..."): create_optimizer folds each
+    extra_opt_params prefix in as chain(masked(tx_prev, prefix not in path), masked(adam_prefix, prefix in path)) with
+    path.split("/") matched element by element, and optax.masked passes masked-out updates through, so the LAST listed
+    prefix on the path wins; "main" when none is on it."""
+    parts = name.split("/")
+    if parts and parts[0] == "params":
+        parts = parts[1:]
+    group = "main"
+    for e in cfg.extra_opt_params:
+        if e.prefix in parts:
+            group = e.prefix
+    return group
+
+
+def adam_scalars(count: int, cfg: OptimizerConfig = OptimizerConfig(), zero_grads: bool = True):
+    """The rc_adam_step of the step at optax count `count` (before the update), per group of cfg.groups(): lr(count),
+    the decays, 1 - b rounded from the double (optax's (1 - decay) * g on a float32 array), eps, and the bias
+    corrections 1 - b^(count+1) in float32; the clip thresholds."""
+    f = np.float32
+    out = {k: [] for k in ("lr", "b1", "b2", "one_minus_b1", "one_minus_b2", "eps", "bias_correction1",
+                           "bias_correction2")}
+    for _, sched in cfg.groups():
+        out["lr"].append(learning_rate_decay(count, **sched))
+        out["b1"].append(f(cfg.b1))
+        out["b2"].append(f(cfg.b2))
+        out["one_minus_b1"].append(f(1.0 - cfg.b1))
+        out["one_minus_b2"].append(f(1.0 - cfg.b2))
+        out["eps"].append(f(cfg.eps))
+        out["bias_correction1"].append(f(1) - np.power(f(cfg.b1), f(count + 1)))
+        out["bias_correction2"].append(f(1) - np.power(f(cfg.b2), f(count + 1)))
+    out.update(grad_max_val=cfg.grad_max_val, grad_max_norm=cfg.grad_max_norm, zero_grads=zero_grads)
+    return out
+
+
+class CacheStageOptimizer:
+    """The cache stage's optimizer state on the device: flat params, mu, nu and gradient buffers in the layouts
+    rc.density_grad_layout(l) (l = 0 .. num_levels-1) and rc.shader_grad_layout() ("shader"), and the optax count.
+    step() = one rc_adam_update over the four buffers (nan_to_num, clip_gradients, the chained Adams), then
+    rc_load_params_flat per layout: the handle renders the updated parameters, ordered on the current stream."""
+
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
+        import torch
+        from . import rc_ext
+
+        self.rc, self.cfg, self._rc_ext = rc, cfg, rc_ext
+        self.keys = list(range(rc.cfg.num_levels)) + ["shader"]
+        self.layouts = {k: (rc.shader_grad_layout() if k == "shader" else rc.density_grad_layout(k)) for k in self.keys}
+        self.group_names = [g for g, _ in cfg.groups()]
+        dev = f"cuda:{rc.device}"
+        z = lambda k: torch.zeros(self.layouts[k][1], dtype=torch.float32, device=dev)
+        self.params = {k: z(k) for k in self.keys}
+        self.mu = {k: z(k) for k in self.keys}
+        self.nu = {k: z(k) for k in self.keys}
+        self.grads = {k: z(k) for k in self.keys}
+        self.segments = {k: [(off, int(np.prod(shape)), self.group_names.index(param_group(name, cfg)))
+                             for name, off, shape in self.layouts[k][0]] for k in self.keys}
+        self._table = self._adam_table(self.grads)
+        self.count = 0
+
+    def _adam_table(self, grads):
+        return self._rc_ext.AdamTable([(self.params[k], grads[k], self.mu[k], self.nu[k], self.segments[k])
+                                       for k in self.keys])
+
+    def names(self):
+        return [name for k in self.keys for name, _, _ in self.layouts[k][0]]
+
+    def init_from(self, weights: Dict[str, object], count: int = 0):
+        """Parameters from a {"params/...": array} dict (weights.py, checkpoint.load_params); zero moments and
+        gradients; the optax count; the handle refreshed."""
+        import torch
+        for k in self.keys:
+            for name, off, shape in self.layouts[k][0]:
+                if name not in weights:
+                    raise KeyError(f"init_from: {name} missing")
+                w = weights[name]
+                t = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+                if tuple(t.shape) != tuple(shape):
+                    raise ValueError(f"init_from: {name} has shape {tuple(t.shape)}, expected {shape}")
+                self.params[k][off: off + int(np.prod(shape))].copy_(t.reshape(-1))
+            self.mu[k].zero_()
+            self.nu[k].zero_()
+            self.grads[k].zero_()
+        self.count = int(count)
+        self.refresh()
+
+    def refresh(self):
+        """rc_load_params_flat of every layout (ordered on the current stream)."""
+        for k in self.keys:
+            self.rc.load_params_flat(k, self.params[k])
+
+    def step(self, flats=None, zero_grads: bool = True):
+        """One update from the gradients `flats` ({key: flat buffer}; None = the optimizer's own gradient buffers,
+        which cache_stage_step fills), then the refresh; `zero_grads` leaves the gradient buffers zeroed."""
+        table = self._table if flats is None or all(flats[k] is self.grads[k] for k in self.keys) else \
+            self._adam_table({k: flats[k] for k in self.keys})
+        self.rc.adam_update(table, adam_scalars(self.count, self.cfg, zero_grads))
+        self.count += 1
+        self.refresh()
+
+    def params_dict(self) -> Dict[str, object]:
+        """{"params/...": view of the flat parameters}: what checkpoint.save_params and load_weights accept."""
+        return {name: v for k in self.keys for name, v in grads_as_dict(self.params[k], self.layouts[k][0]).items()}
+
+    def state_dict(self):
+        """params, mu, nu (copies of the flat buffers by layout key) and the count: training stops and resumes on it."""
+        c = lambda d: {str(k): v.detach().clone() for k, v in d.items()}
+        return {"count": int(self.count), "params": c(self.params), "mu": c(self.mu), "nu": c(self.nu)}
+
+    def load_state_dict(self, sd):
+        for k in self.keys:
+            self.params[k].copy_(sd["params"][str(k)])
+            self.mu[k].copy_(sd["mu"][str(k)])
+            self.nu[k].copy_(sd["nu"][str(k)])
+            self.grads[k].zero_()
+        self.count = int(sd["count"])
+        self.refresh()
+
+
+def cache_stage_step(rc, opt: CacheStageOptimizer, rays, rgb, jitters, lossmult=None, group=None,
+                     geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
+                     interlevel_cfg: InterlevelConfig = InterlevelConfig()):
+    """One train step of the cache stage (train_utils.py:3128-3161): train_frac from opt.count
+    (trainer.py:2116-2126), cache_stage_grads into the optimizer's zeroed gradient buffers, the pmean over `group`
+    when torch.distributed runs (allreduce_grads), then opt.step() (nan_to_num, clip_gradients, the Adams, the handle's
+    refresh).  -> the losses dict of cache_stage_grads (the local batch's values)."""
+    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
+    flats, losses = cache_stage_grads(rc, rays, rgb, jitters, tf, lossmult, dict(opt.grads), geometry_cfg, data_cfg,
+                                      interlevel_cfg)
+    allreduce_grads([flats[k] for k in opt.keys], group=group)
+    opt.step({k: flats[k] for k in opt.keys})
+    return losses
