@@ -286,7 +286,7 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * rc_render_transient), "p1:" .. "p3:" = the sets of rc_render_rays on further caller streams, "s:" = the batched
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
- * "o:" = rc_adam_update / rc_load_params_flat.
+ * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -308,6 +308,11 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "reg_part" (per-table partial sums, doubles).
  * "o:": "part" (per-tile sums of g^2 of the norm clip, doubles), "norm" ([1] the global norm), "mult" ([1] the clip
  * multiplier), "stage" (the dense segments of rc_load_params_flat gathered when they are not contiguous).
+ * "ls:": "cache_rgb" ([n][3]), "cache_acc" ([n]) (the primary pass's composite, not read), "h0", "h1" ([n][64] the light
+ * head's hidden layers, recomputed), "vp" ([n][640] its vmf_params), "dvp" ([n][640] d loss / d vmf_params), "dh1",
+ * "dh0" ([n][64]), "dfeat" ([n][32] d loss / d light-grid features), "loss_ray" ([n] per-ray sums), "part" (weight-gradient
+ * K slices), "ones", "reg_part" (rc_light_regularizer's per-table partial sums, doubles).  The forward's own buffers
+ * keep their set-0 / "s:" names ("m_pts", "m_nrm", "l_feat", "l_vmf", "l_vmf_logit", "sec_dirs", "sec_samples", "sec_rgb").
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -622,7 +627,8 @@ typedef struct {
 int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const rc_adam_step* step, void* stream);
 
 /* rc_load_params_flat: rc_load_weights of every tensor of one gradient layout, from a DEVICE buffer in that layout
- * (layout = density level l: rc_density_grad_layout(l); RC_LAYOUT_SHADER: rc_shader_grad_layout).  The grid tables
+ * (layout = density level l: rc_density_grad_layout(l); RC_LAYOUT_SHADER: rc_shader_grad_layout; RC_LAYOUT_LIGHT:
+ * rc_light_grad_layout).  The grid tables
  * are copied device to device into the handle's table buffers, ordered on `stream`; the dense-layer segments go to
  * the host in ONE copy (gathered on the device first when they are not contiguous), after which the call waits for
  * `stream` (the host repack needs them).  The derived tables (cell tables, level-2 pairs, cell records) and packs are
@@ -630,7 +636,53 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
  * computes bitwise what it would after rc_load_weights of the same tensors.  The time-resolved cache handle is
  * unsupported. */
 #define RC_LAYOUT_SHADER (-1)
+#define RC_LAYOUT_LIGHT (-2)   /* rc_light_grad_layout */
 int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void* stream);
+
+/* ---- the light sampler's own loss -----------------------------------------------------------------
+ * light_sampling (train_utils.light_sampling_loss, internal/train_utils.py:1985-2067 -> render_utils.vmf_loss_fn,
+ * internal/inverse_render/render_utils.py:1493-1547) and its exact first-order gradient of the params/LightSampler tensors.
+ * Per suffix s of the batched secondary trace (indirect_specular: the Ks GGX rays, indirect_diffuse: the Kd cosine + vMF
+ * rays), over the n x K_s samples:
+ *   L_s  = mean of (f - l) sg(f - l) w (lossmult_r / K_s) / max(pdf, 1e-2)       (the reference divides by K_s twice)
+ *   f    = srgb(max(|radiance_in|, 1e-5)), radiance_in = nan_to_num(the trace's rgb), |.| the 2-norm (no gradient)
+ *   l    = srgb(max(sum_j safe_exp(logit_j) eval_vmf(d, l2_normalize(mean_j, grad_eps = 1e-5), kappa_j), 1e-5))
+ *   w    = clip(weight, 0, 10), 0 where d . n <= 0 (n = the shading point's normals_to_use)
+ *   loss = mult (L_spec + L_diff) / 2, srgb = image.linear_to_srgb when linear_to_srgb != 0, else the identity.
+ * mean_j, kappa_j, logit_j: get_vmfs of the light head at the shading point (vmf_scale, the caller's vmf_noise and the
+ * point itself are constants).  Everything else the loss reads is stop-gradiented: the gradient reaches only the
+ * LightSampler parameters.  One call:
+ *   1. rc_render_material's forward with the same rnd / mrnd / num_secondary_samples (the primary cache pass, the shading
+ *      point's pick, the shading heads, BRDF importance sampling, the batched secondary trace; no integration, no EnvMap,
+ *      no material-only composite) on rc_render_material's workspace sets (set 0 and "s:"): m_pts, l_vmf, l_vmf_logit,
+ *      sec_dirs, sec_samples and sec_rgb are bitwise what rc_render_material leaves there for the same inputs;
+ *   2. the light head's recompute (h0, h1, vmf_params), the loss (DEVICE float, written; fixed reduction order, bitwise
+ *      reproducible) and, when light_grads is given, d loss / d vmf_params;
+ *   3. only when light_grads is given: the three dense layers' backward (weight gradients reduced over fixed slices of
+ *      points: bitwise reproducible) and rc_hashgrid_backward of the light grid (grid 5, contracted) at the shading
+ *      points; ACCUMULATED into light_grads (layout rc_light_grad_layout).  NULL: the loss only.
+ * lossmult: [n] device or NULL (1).  The mean is over the local batch; a data-parallel trainer averages light_grads.
+ * Argument checks, the num_secondary_samples split and the refusals are rc_render_material's (missing material or light
+ * weights: RC_ERR_MISSING_WEIGHT; the EnvMap is not needed); the time-resolved cache handle is unsupported.  n == 0
+ * returns RC_OK and writes nothing.  Everything is ordered on `stream`.  Buffers of the call: set-0 / "s:" / "ls:" names.
+ * Not covered: the gradient the LightSampler receives from the material data loss through the vMF-sampled directions. */
+typedef struct {
+  float mult;                  /* the extra loss's multiplier (trainer.gin: 1.0) */
+  int32_t linear_to_srgb;      /* Config.light_sampling_linear_to_srgb (ngp_yobo.gin: True) */
+} rc_light_sampling_loss;
+/* The light layout: params/LightSampler/light_grid tables in level order (as rc_hashgrid_grad_layout(5)), then layers_0,
+ * layers_1 and output_layer, kernel [in, out] then bias [out] each. */
+int64_t rc_light_grad_size(rc_handle* h);
+int rc_light_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count);
+int rc_light_sampling_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                               const rc_material_randoms* mrnd, int32_t num_secondary_samples,
+                               const rc_light_sampling_loss* cfg, float* light_grads, float* loss, void* stream);
+/* param_regularizer_loss for 'light_grid' (train_utils.py:1169-1214; nerf_ngp_yobo.gin:47-51, (mult, jnp.mean, 2, 1)):
+ * loss = mult * sum over the light grid's tables of 0.5 * mean(x^2), written to `loss` (DEVICE float; fixed reduction
+ * order); when light_grads is given, mult * x / numel(table) is ACCUMULATED into each table's segment of it (layout
+ * rc_light_grad_layout); the MLP segments are untouched.  Ordered on `stream`; the time-resolved cache handle is
+ * unsupported.  Buffers: "ls:reg_part". */
+int rc_light_regularizer(rc_handle* h, float mult, float* light_grads, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

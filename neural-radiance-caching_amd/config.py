@@ -212,6 +212,22 @@ class GeometryLossConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class LightSamplingConfig:
+    """Training-time constants of the light sampler's own loss and its grid regularizer (the material_light_from_scratch
+    stage, hotdog)."""
+    # the light_sampling extra loss of the stage: "main" mult 1.0, start_frac 0.0 (configs/trainer.gin:345-349)
+    mult: float = 1.0
+    start_frac: float = 0.0
+    # Config.light_sampling_linear_to_srgb (configs/ngp_yobo.gin:443)
+    linear_to_srgb: bool = True
+    # the stage's num_secondary_samples 4 (configs/trainer.gin:327, material_light_from_scratch) times Trainer.sample_factor 2
+    # (engine/trainer.py:86, :300)
+    num_secondary_samples: int = 8
+    # Config.param_regularizers 'light_grid': (1.0, jnp.mean, 2, 1) (nerf_ngp_yobo.gin:47-51)
+    light_grid_mult: float = 1.0
+
+
+@dataclasses.dataclass(frozen=True)
 class ExtraOptParams:
     """One entry of Config.extra_opt_params (configs/ngp_yobo.gin:59-115): the Adam of the tensors whose path holds
     `prefix` as a whole element, and its schedule; the _material values replace the others when a material stage trains

@@ -95,19 +95,25 @@ struct GeometryWs { WsBuf loss_ray, d_density, d_pred, points, h64, dfeat, part,
 // rc_adam_update: the per-tile sums of g^2 (doubles), the norm and the clip multiplier; rc_load_params_flat: the dense
 // segments of a layout gathered for the one copy to the host.
 struct OptimWs { WsBuf part, norm, mult, stage; };
+// rc_light_sampling_backward (its forward on set 0 and WS_SECONDARY): the primary pass's composite (not read), the light
+// head's recompute and its gradients, the per-point loss sums, the weight-gradient K slices and a column of ones;
+// rc_light_regularizer's per-table partial sums.
+struct LightWs { WsBuf cache_rgb, cache_acc, h0, h1, vp, dvp, dh1, dh0, dfeat, loss_ray, part, ones, reg_part; };
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
 // serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
 // WS_TRAIN serves rc_density_backward (TrainWs only), WS_INTERLEVEL rc_interlevel_backward, WS_DATA rc_data_backward,
-// WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat.
-enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM, WS_COUNT };
+// WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat, WS_LIGHT
+// the buffers of rc_light_sampling_backward's own (its forward runs on WS_RENDER0 + WS_SECONDARY) and rc_light_regularizer.
+enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
+               WS_LIGHT, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -126,7 +132,7 @@ struct WsName {
   const char* name;
   WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
   WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr; WsBuf DataWs::*d = nullptr;
-  WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr;
+  WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -136,6 +142,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf DataWs::*m) : name(s), d(m) {}
   constexpr WsName(const char* s, WsBuf GeometryWs::*m) : name(s), g(m) {}
   constexpr WsName(const char* s, WsBuf OptimWs::*m) : name(s), o(m) {}
+  constexpr WsName(const char* s, WsBuf LightWs::*m) : name(s), ls(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -145,7 +152,8 @@ struct WsName {
       if (i) return one(s, i);
       if (d) return one(s, d);
       if (g) return one(s, g);
-      return o ? one(s, o) : nullptr;
+      if (o) return one(s, o);
+      return ls ? one(s, ls) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -155,6 +163,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
+using L = LightWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -172,10 +181,13 @@ constexpr WsName kTable[] = {
     WS(D, dio), WS(D, dso), WS(D, dsb), WS(D, dx328), WS(D, ds1), WS(D, ds0), WS(D, di2), WS(D, di1), WS(D, dib_in),
     WS(D, db128), WS(D, dp3), WS(D, df96), WS(D, dfeat), WS(D, dapp), WS(D, part), WS(D, ones),
     WS(G, loss_ray), WS(G, d_density), WS(G, d_pred), WS(G, points), WS(G, h64), WS(G, dfeat), WS(G, part), WS(G, ones),
-    WS(G, reg_part), WS(O, part), WS(O, norm), WS(O, mult), WS(O, stage)};
+    WS(G, reg_part), WS(O, part), WS(O, norm), WS(O, mult), WS(O, stage),
+    WS(L, cache_rgb), WS(L, cache_acc), WS(L, h0), WS(L, h1), WS(L, vp), WS(L, dvp), WS(L, dh1), WS(L, dh0), WS(L, dfeat),
+    WS(L, loss_ray), WS(L, part), WS(L, ones), WS(L, reg_part)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O), "the table lists every workspace buffer");
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L),
+              "the table lists every workspace buffer");
 }  // namespace wsn
 
 constexpr int kEvSlots = 16;
@@ -1668,6 +1680,148 @@ int rc_render_chunks(rc_handle* h, const rc_rays* rays, int64_t chunk, int64_t n
   return RC_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// rc_render_material's forward, shared with rc_light_sampling_backward (rc_light_host.inc): the argument checks behind
+// the entry point's own, the workspace, and steps 1-2 (the primary cache pass, the shading point), 3a-4 (the shading
+// heads), 5 (BRDF importance sampling) and the arguments of step 6 (the batched secondary trace).  Each step launches
+// what rc_render_material launched before, in the same order.
+struct MatSplit { int Ks, Kd, Kc; };
+
+int material_check(rc_handle* h, const rc_rays* rays, const rc_material_randoms* mr, int32_t K, const char* who, MatSplit& sp) {
+  int rc;
+  const std::string w = who;
+  if ((rc = check_rays(h, rays, who))) return rc;
+  const rc_config& c = h->cfg;
+  sp.Ks = (int)lround(K * (1.0 - (double)c.diffuse_sample_fraction));
+  sp.Kd = (int)lround(K * (double)c.diffuse_sample_fraction);
+  sp.Kc = (int)lround(0.5 * sp.Kd);
+  const int Ks = sp.Ks, Kd = sp.Kd, Kc = sp.Kc;
+  if (K < 2 || Ks < 1 || Kd < 2 || Kc < 1 || Kd - Kc < 1 || Ks + Kd > 64)
+    return fail(h, RC_ERR_UNSUPPORTED, w + ": num_secondary_samples must give 1 <= Ks, 2 <= Kd, Ks + Kd <= 64");
+  if (c.num_vmf != 128) return fail(h, RC_ERR_UNSUPPORTED, w + ": num_vmf must be 128");
+  if (!mr->vmf_noise || !mr->spec_u1 || !mr->spec_u2 || !mr->cos_u1 || !mr->cos_u2 || !mr->vmf_v || !mr->vmf_tmp ||
+      !(mr->vmf_lobe || mr->vmf_lobe_gumbel))
+    return fail(h, RC_ERR_INVALID_ARG, w + ": every sampler member of rc_material_randoms is required "
+                                           "(vmf_lobe or vmf_lobe_gumbel)");
+  if (!(mr->gumbel || mr->resample_inds) || !(mr->sec_gumbel || mr->sec_resample_inds))
+    return fail(h, RC_ERR_INVALID_ARG, w + ": the categorical picks need gumbel or resample_inds (primary) and "
+                                           "sec_gumbel or sec_resample_inds (secondary trace)");
+  return RC_OK;
+}
+
+int material_workspace(rc_handle* h, RenderWs& w, ExtraWs& x, RenderWs& ws_sec, int64_t n, const MatSplit& sp) {
+  const rc_config& c = h->cfg;
+  const int64_t np2 = n * c.num_samples[c.num_levels - 1], nsec = n * (sp.Ks + sp.Kd);
+  int rc;
+  if ((rc = ensure_workspace(h, w, n))) return rc;
+  if ((rc = ws_alloc(h, {{x.m_pts, 3 * n}, {x.m_nrm, 3 * n}, {x.m_feat, 32 * n}, {x.m_mat, RC_MAT_CH * n}, {x.m_feat_all, 32 * np2},
+                         {x.m_mat_all, RC_MAT_CH * np2}, {x.l_feat, 32 * n}, {x.l_vmf, (int64_t)128 * RC_VMF_CH * n},
+                         {x.l_vmf_logit, (int64_t)128 * n}, {x.sec_origins, 3 * nsec}, {x.sec_dirs, 3 * nsec}, {x.sec_near, nsec},
+                         {x.sec_far, nsec}, {x.sec_lights, 3 * nsec}, {x.sec_samples, RC_SMP_CH * nsec}, {x.m_local_view, 3 * n},
+                         {x.sec_rgb, 3 * nsec}, {x.sec_acc, nsec}, {x.sec_env, 3 * nsec}})) ||
+      (rc = ensure_workspace(h, ws_sec, nsec)))
+    return rc;
+  return RC_OK;
+}
+
+// 1. cache pass on the primary rays (all samples shaded) -> cache_out; 2. one shading sample per ray
+void material_primary(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd, const rc_material_randoms* mr,
+                      const rc_outputs* cache_out, RenderWs& w, ExtraWs& x, hipStream_t st) {
+  const rc_config& c = h->cfg;
+  const int NL = c.num_levels;
+  const int S2 = c.num_samples[NL - 1];
+  RenderArgs A{};
+  A.rays = *rays; A.have_rnd = rnd != nullptr; if (rnd) A.rnd = *rnd;
+  A.n = n; A.mask = RC_PASS_CACHE; A.out = *cache_out; A.slot = -1;
+  // the fused kernel when the handle runs it (rc_set_fused mode 1): one launch, its per-sample results exported for
+  // steps 2-3 below; bitwise the launch-per-stage pass (tests/test_gpu_parity.py)
+  A.fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && !h->profiling && c.num_samples[NL - 1] == 32;
+  A.export_samples = A.fused;
+  enqueue_all(h, A, w, st);
+
+  // 2. one shading sample per ray (MaterialModel.resample_render, models.py:1430-1439)
+  RcResampleArgs ra{};
+  ra.n_rays = n; ra.S = S2; ra.tdist = w.tdist[NL - 1].p; ra.density = w.density[NL - 1].p;
+  ra.directions = rays->directions; ra.gumbel = mr->gumbel; ra.inds_in = mr->resample_inds;
+  ra.inds_out = (int32_t*)w.inds.p; ra.filt_weight = w.filt_weight.p; ra.weights = w.weights[NL - 1].p; ra.src_out = (int32_t*)w.src_idx.p;
+  // position and predicted normal of the picked sample = the shading point
+  ra.means = w.means[NL - 1].p; ra.normals = w.normals_pred.p; ra.pts_out = x.m_pts.p; ra.nrm_out = x.m_nrm.p;
+  rc_launch_resample(ra, st);
+}
+
+// 3a. material head and 4. light sampler (128 vMF lobes) at the shading point: one lookup launch + one head launch on the
+// caller's stream
+void material_heads(rc_handle* h, int64_t n, const rc_material_randoms* mr, ExtraWs& x, hipStream_t st) {
+  const rc_config& c = h->cfg;
+  const auto& raw = h->packs.raw;
+  roctx_stage("material: heads + light sampler");
+  RcMatHeadArgs ma{};
+  ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
+  ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
+  ma.min_roughness = c.min_roughness;
+  RcLightHeadArgs la{};
+  la.n = n; la.feat = x.l_feat.p;
+  la.w0 = raw[RAW_LIGHT_0].kernel.p; la.b0 = raw[RAW_LIGHT_0].bias.p;
+  la.w1 = raw[RAW_LIGHT_1].kernel.p; la.b1 = raw[RAW_LIGHT_1].bias.p;
+  la.w2 = raw[RAW_LIGHT_OUT].kernel.p; la.b2 = raw[RAW_LIGHT_OUT].bias.p;
+  la.pts = x.m_pts.p; la.noise = mr->vmf_noise; la.vmf_scale = c.vmf_scale; la.vmf = x.l_vmf.p; la.vmf_logit = x.l_vmf_logit.p;
+  // caller's stream, the critical path: both grids at the shading points in one launch, both heads in one launch (as
+  // four launches on two streams the BRDF sampler waited ~12 us for the event behind the light head)
+  rc_launch_hashgrid_two(h->grids[4].dev, h->grids[5].dev, x.m_pts.p, n, x.m_feat.p, x.l_feat.p, c.contract_radius, st);
+  ma.n = n; ma.feat = x.m_feat.p; ma.mat = x.m_mat.p;
+  rc_launch_shading_heads(ma, la, st);
+}
+
+// 5. BRDF importance sampling -> secondary rays
+void material_brdf_sample(rc_handle* h, const rc_rays* rays, int64_t n, const rc_material_randoms* mr, const MatSplit& sp,
+                          ExtraWs& x, hipStream_t st) {
+  const rc_config& c = h->cfg;
+  roctx_stage("material: brdf sample");
+  RcBrdfSampleArgs sa{};
+  sa.n = n; sa.Ks = sp.Ks; sa.Kd = sp.Kd; sa.Kc = sp.Kc;
+  sa.pts = x.m_pts.p; sa.nrm = x.m_nrm.p; sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
+  sa.mat = x.m_mat.p; sa.vmf = x.l_vmf.p; sa.vmf_logit = x.l_vmf_logit.p;
+  sa.spec_u1 = mr->spec_u1; sa.spec_u2 = mr->spec_u2; sa.cos_u1 = mr->cos_u1; sa.cos_u2 = mr->cos_u2;
+  sa.vmf_lobe = mr->vmf_lobe; sa.vmf_v = mr->vmf_v; sa.vmf_tmp = mr->vmf_tmp; sa.vmf_lobe_gumbel = mr->vmf_lobe_gumbel;
+  sa.normal_eps = c.secondary_normal_eps; sa.near = c.secondary_near; sa.far = c.secondary_far;
+  sa.sec_origins = x.sec_origins.p; sa.sec_dirs = x.sec_dirs.p; sa.sec_near = x.sec_near.p; sa.sec_far = x.sec_far.p;
+  sa.sec_lights = x.sec_lights.p; sa.samples = x.sec_samples.p; sa.local_view = x.m_local_view.p;
+  rc_launch_brdf_sample(sa, st);
+}
+
+// 6. the arguments of the ONE batched secondary trace through the cache (is_secondary, resample, use_env_map=False;
+//    ref_rays.normals = None since MaterialMLP.shadow_eps_indirect = False) -> sec_rgb, sec_acc
+int material_trace_args(rc_handle* h, const rc_material_randoms* mr, int64_t nsec, ExtraWs& x, hipStream_t st, RenderArgs& B) {
+  const rc_config& c = h->cfg;
+  B = RenderArgs{};
+  B.rays.origins = x.sec_origins.p; B.rays.directions = x.sec_dirs.p; B.rays.viewdirs = x.sec_dirs.p;
+  B.rays.near = x.sec_near.p; B.rays.far = x.sec_far.p; B.rays.lights = x.sec_lights.p; B.rays.normals = nullptr;
+  B.have_rnd = true;
+  for (int l = 0; l < RC_MAX_LEVELS; ++l) B.rnd.jitter[l] = mr->sec_jitter[l];
+  B.rnd.gumbel = mr->sec_gumbel; B.rnd.resample_inds = mr->sec_resample_inds;
+  B.n = nsec; B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY | RC_PASS_NO_ENVMAP; B.slot = -1;
+  // every secondary ray of this trace has the same (near, far) (k_brdf_sample writes the two constants): the
+  // power-ladder image of the pair is computed once instead of by each of the 3 x 32 768 sampler waves
+  // ... and once per handle: the five inputs are constants of the configuration (same device function, a buffer of
+  // the handle's own; 5 us + a 6 us gap in every step before)
+  if (!h->sec_sbounds) {
+    RC_HIP(h, hipMalloc((void**)&h->sec_sbounds, 2 * sizeof(float)));
+    rc_launch_ladder_bounds(c.secondary_near, c.secondary_far, c.env_map_distance, c.raydist_p, c.raydist_premult, h->sec_sbounds, st);
+    RC_HIP(h, hipStreamSynchronize(st));       // later calls may come on other streams
+  }
+  B.s_bounds = h->sec_sbounds;
+  memset(&B.out, 0, sizeof(B.out));
+  B.out.ptr[RC_OUT_RGB] = x.sec_rgb.p; B.out.ptr[RC_OUT_ACC] = x.sec_acc.p;
+  return RC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd,
                        const rc_material_randoms* mr, int32_t K, const rc_outputs* cache_out,
                        const rc_mat_outputs* mat_out, void* stream_v) {
@@ -1679,21 +1833,10 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: negative n_rays");
   if (n == 0) return RC_OK;
   int rc;
-  if ((rc = check_rays(h, rays, "rc_render_material"))) return rc;
+  MatSplit sp;
+  if ((rc = material_check(h, rays, mr, K, "rc_render_material", sp))) return rc;
   const rc_config& c = h->cfg;
-  const int Ks = (int)lround(K * (1.0 - (double)c.diffuse_sample_fraction));
-  const int Kd = (int)lround(K * (double)c.diffuse_sample_fraction);
-  const int Kc = (int)lround(0.5 * Kd);
-  if (K < 2 || Ks < 1 || Kd < 2 || Kc < 1 || Kd - Kc < 1 || Ks + Kd > 64)
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_render_material: num_secondary_samples must give 1 <= Ks, 2 <= Kd, Ks + Kd <= 64");
-  if (c.num_vmf != 128) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_material: num_vmf must be 128");
-  if (!mr->vmf_noise || !mr->spec_u1 || !mr->spec_u2 || !mr->cos_u1 || !mr->cos_u2 || !mr->vmf_v || !mr->vmf_tmp ||
-      !(mr->vmf_lobe || mr->vmf_lobe_gumbel))
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: every sampler member of rc_material_randoms is required "
-                                       "(vmf_lobe or vmf_lobe_gumbel)");
-  if (!(mr->gumbel || mr->resample_inds) || !(mr->sec_gumbel || mr->sec_resample_inds))
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: the categorical picks need gumbel or resample_inds (primary) and "
-                                       "sec_gumbel or sec_resample_inds (secondary trace)");
+  const int Ks = sp.Ks, Kd = sp.Kd;
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
@@ -1707,36 +1850,11 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   RenderWs& w = use.s.r;
   ExtraWs& x = ws_extra<ExtraWs>(use.s);
   RenderWs& ws_sec = h->ws[WS_SECONDARY].r;
-  if ((rc = ensure_workspace(h, w, n))) return rc;
-  if ((rc = ws_alloc(h, {{x.m_pts, 3 * n}, {x.m_nrm, 3 * n}, {x.m_feat, 32 * n}, {x.m_mat, RC_MAT_CH * n}, {x.m_feat_all, 32 * np2},
-                         {x.m_mat_all, RC_MAT_CH * np2}, {x.l_feat, 32 * n}, {x.l_vmf, (int64_t)128 * RC_VMF_CH * n},
-                         {x.l_vmf_logit, (int64_t)128 * n}, {x.sec_origins, 3 * nsec}, {x.sec_dirs, 3 * nsec}, {x.sec_near, nsec},
-                         {x.sec_far, nsec}, {x.sec_lights, 3 * nsec}, {x.sec_samples, RC_SMP_CH * nsec}, {x.m_local_view, 3 * n},
-                         {x.sec_rgb, 3 * nsec}, {x.sec_acc, nsec}, {x.sec_env, 3 * nsec}})) ||
-      (rc = ensure_workspace(h, ws_sec, nsec)))
-    return rc;
+  if ((rc = material_workspace(h, w, x, ws_sec, n, sp))) return rc;
   rc_shader_prepare();
 
-  // 1. cache pass on the primary rays (all samples shaded) -> cache_out
-  RenderArgs A{};
-  A.rays = *rays; A.have_rnd = rnd != nullptr; if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = RC_PASS_CACHE; A.out = *cache_out; A.slot = -1;
-  // the fused kernel when the handle runs it (rc_set_fused mode 1): one launch, its per-sample results exported for
-  // steps 2-3 below; bitwise the launch-per-stage pass (tests/test_gpu_parity.py)
-  A.fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && !h->profiling && c.num_samples[NL - 1] == 32;
-  A.export_samples = A.fused;
-  enqueue_all(h, A, w, st);
-
-  // 2. one shading sample per ray (MaterialModel.resample_render, models.py:1430-1439)
-  {
-    RcResampleArgs ra{};
-    ra.n_rays = n; ra.S = S2; ra.tdist = w.tdist[NL - 1].p; ra.density = w.density[NL - 1].p;
-    ra.directions = rays->directions; ra.gumbel = mr->gumbel; ra.inds_in = mr->resample_inds;
-    ra.inds_out = (int32_t*)w.inds.p; ra.filt_weight = w.filt_weight.p; ra.weights = w.weights[NL - 1].p; ra.src_out = (int32_t*)w.src_idx.p;
-    // position and predicted normal of the picked sample = the shading point
-    ra.means = w.means[NL - 1].p; ra.normals = w.normals_pred.p; ra.pts_out = x.m_pts.p; ra.nrm_out = x.m_nrm.p;
-    rc_launch_resample(ra, st);
-  }
+  // 1. cache pass on the primary rays (all samples shaded) -> cache_out; 2. one shading sample per ray
+  material_primary(h, rays, n, rnd, mr, cache_out, w, x, st);
   const auto& raw = h->packs.raw;
   // Side stream: the material-only composite over all samples (step 3b) and the EnvMap along the secondary rays (step 6b)
   // feed only the outputs / the final integration, so they leave the critical path sampler -> trace -> integrate and
@@ -1756,40 +1874,10 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
         (void)hipStreamSynchronize(side);
     }
   } side_join{h, st, side, false};
-  // 3a. material head and 4. light sampler (128 vMF lobes) at the shading point: one lookup launch + one head launch on the
-  // caller's stream
-  roctx_stage("material: heads + light sampler");
-  {
-    RcMatHeadArgs ma{};
-    ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
-    ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
-    ma.min_roughness = c.min_roughness;
-    RcLightHeadArgs la{};
-    la.n = n; la.feat = x.l_feat.p;
-    la.w0 = raw[RAW_LIGHT_0].kernel.p; la.b0 = raw[RAW_LIGHT_0].bias.p;
-    la.w1 = raw[RAW_LIGHT_1].kernel.p; la.b1 = raw[RAW_LIGHT_1].bias.p;
-    la.w2 = raw[RAW_LIGHT_OUT].kernel.p; la.b2 = raw[RAW_LIGHT_OUT].bias.p;
-    la.pts = x.m_pts.p; la.noise = mr->vmf_noise; la.vmf_scale = c.vmf_scale; la.vmf = x.l_vmf.p; la.vmf_logit = x.l_vmf_logit.p;
-    // caller's stream, the critical path: both grids at the shading points in one launch, both heads in one launch (as
-    // four launches on two streams the BRDF sampler waited ~12 us for the event behind the light head)
-    rc_launch_hashgrid_two(h->grids[4].dev, h->grids[5].dev, x.m_pts.p, n, x.m_feat.p, x.l_feat.p, c.contract_radius, st);
-    ma.n = n; ma.feat = x.m_feat.p; ma.mat = x.m_mat.p;
-    rc_launch_shading_heads(ma, la, st);
-  }
+  // 3a. material head and 4. light sampler (128 vMF lobes) at the shading point
+  material_heads(h, n, mr, x, st);
   // 5. BRDF importance sampling -> secondary rays
-  roctx_stage("material: brdf sample");
-  {
-    RcBrdfSampleArgs sa{};
-    sa.n = n; sa.Ks = Ks; sa.Kd = Kd; sa.Kc = Kc;
-    sa.pts = x.m_pts.p; sa.nrm = x.m_nrm.p; sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
-    sa.mat = x.m_mat.p; sa.vmf = x.l_vmf.p; sa.vmf_logit = x.l_vmf_logit.p;
-    sa.spec_u1 = mr->spec_u1; sa.spec_u2 = mr->spec_u2; sa.cos_u1 = mr->cos_u1; sa.cos_u2 = mr->cos_u2;
-    sa.vmf_lobe = mr->vmf_lobe; sa.vmf_v = mr->vmf_v; sa.vmf_tmp = mr->vmf_tmp; sa.vmf_lobe_gumbel = mr->vmf_lobe_gumbel;
-    sa.normal_eps = c.secondary_normal_eps; sa.near = c.secondary_near; sa.far = c.secondary_far;
-    sa.sec_origins = x.sec_origins.p; sa.sec_dirs = x.sec_dirs.p; sa.sec_near = x.sec_near.p; sa.sec_far = x.sec_far.p;
-    sa.sec_lights = x.sec_lights.p; sa.samples = x.sec_samples.p; sa.local_view = x.m_local_view.p;
-    rc_launch_brdf_sample(sa, st);
-  }
+  material_brdf_sample(h, rays, n, mr, sp, x, st);
   // 3b. side stream: the material head on ALL samples and the material-only composite (outputs only).  Forked HERE, behind
   // the BRDF sampler: beside the small latency-bound kernels above they doubled those kernels' times (heads 18 -> 35 us,
   // sampler 19 -> 33 us); beside the first level of the trace they fit into what its workgroups leave of a CU (no LDS /
@@ -1812,25 +1900,8 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   // 6. ONE batched secondary trace through the cache (is_secondary, resample, use_env_map=False;
   //    ref_rays.normals = None since MaterialMLP.shadow_eps_indirect = False) + EnvMap along the same rays
   {
-    RenderArgs B{};
-    B.rays.origins = x.sec_origins.p; B.rays.directions = x.sec_dirs.p; B.rays.viewdirs = x.sec_dirs.p;
-    B.rays.near = x.sec_near.p; B.rays.far = x.sec_far.p; B.rays.lights = x.sec_lights.p; B.rays.normals = nullptr;
-    B.have_rnd = true;
-    for (int l = 0; l < RC_MAX_LEVELS; ++l) B.rnd.jitter[l] = mr->sec_jitter[l];
-    B.rnd.gumbel = mr->sec_gumbel; B.rnd.resample_inds = mr->sec_resample_inds;
-    B.n = nsec; B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY | RC_PASS_NO_ENVMAP; B.slot = -1;
-    // every secondary ray of this trace has the same (near, far) (k_brdf_sample writes the two constants): the
-    // power-ladder image of the pair is computed once instead of by each of the 3 x 32 768 sampler waves
-    // ... and once per handle: the five inputs are constants of the configuration (same device function, a buffer of
-    // the handle's own; 5 us + a 6 us gap in every step before)
-    if (!h->sec_sbounds) {
-      RC_HIP(h, hipMalloc((void**)&h->sec_sbounds, 2 * sizeof(float)));
-      rc_launch_ladder_bounds(c.secondary_near, c.secondary_far, c.env_map_distance, c.raydist_p, c.raydist_premult, h->sec_sbounds, st);
-      RC_HIP(h, hipStreamSynchronize(st));       // later calls may come on other streams
-    }
-    B.s_bounds = h->sec_sbounds;
-    memset(&B.out, 0, sizeof(B.out));
-    B.out.ptr[RC_OUT_RGB] = x.sec_rgb.p; B.out.ptr[RC_OUT_ACC] = x.sec_acc.p;
+    RenderArgs B;
+    if ((rc = material_trace_args(h, mr, nsec, x, st, B))) return rc;
     RcEnvMapArgs ea{};
     ea.n = nsec; ea.viewdirs = x.sec_dirs.p; ea.wstream = h->packs.envmap.p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = x.sec_env.p;
     // 6b. EnvMap of the secondary directions, on the side stream.  It is MFMA-bound and keeps a CU's LDS to itself, as the
@@ -1890,4 +1961,5 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_interlevel_host.inc"
 #include "rc_data_host.inc"
 #include "rc_geometry_host.inc"
+#include "rc_light_host.inc"
 #include "rc_optim_host.inc"

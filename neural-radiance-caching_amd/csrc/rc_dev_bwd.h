@@ -1,4 +1,4 @@
-// Device pieces shared by the loss backwards (rc_interlevel.hip, rc_data.hip, rc_geometry.hip): the reverse wave scan
+// Device pieces shared by the loss backwards (rc_interlevel.hip, rc_data.hip, rc_geometry.hip, rc_light.hip): the reverse wave scan
 // of compute_alpha_weights, ref_utils.l2_normalize's override_gradient and the column order of k_density_mlp's hbuf.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +34,23 @@ __device__ __forceinline__ void l2_normalize_bwd(float px, float py, float pz, f
     dpx = ux / d; dpy = uy / d; dpz = uz / d;
     if (s > RC_EPS) {
       const float k = (ux * px + uy * py + uz * pz) / (d * d * d);
+      dpx -= k * px; dpy -= k * py; dpz -= k * pz;
+    }
+  }
+}
+
+// The same backward for any grad_eps (vmf_loss_fn: 1e-5), with jnp.maximum's tie rule: at |p|^2 == grad_eps half the
+// gradient reaches the squared norm.
+__device__ __forceinline__ void l2_normalize_bwd_eps(float px, float py, float pz, float ux, float uy, float uz, float grad_eps,
+                                                     float& dpx, float& dpy, float& dpz) {
+  const float s = px * px + py * py + pz * pz;
+  dpx = 0.0f; dpy = 0.0f; dpz = 0.0f;
+  if (!(s < RC_TINY)) {
+    const float d = sqrtf(fmaxf(grad_eps, s));
+    dpx = ux / d; dpy = uy / d; dpz = uz / d;
+    if (s >= grad_eps) {
+      float k = (ux * px + uy * py + uz * pz) / (d * d * d);
+      if (s == grad_eps) k = 0.5f * k;
       dpx -= k * px; dpy -= k * py; dpz -= k * pz;
     }
   }

@@ -526,6 +526,23 @@ int rc_grid_l2_blocks();                   // partial sums per table of rc_launc
 void rc_launch_grid_l2_bwd(const float* x, int64_t count, float gscale, float* grad, double* part, hipStream_t st);
 void rc_launch_grid_l2_reduce(const double* part, const RcGridL2Reduce& r, float* loss, hipStream_t st);
 
+// The light sampler's own loss (rc_light.hip)
+struct RcLightLossArgs {
+  int64_t n; int Ks, Kd;                   // shading points, secondary samples per suffix
+  const float* vp;                         // [n][640] the light head's vmf_params
+  const float* noise;                      // [n][128][3] the vMF mean noise
+  const float* pts, * nrm;                 // [n][3] shading point, normals_to_use
+  const float* sec_dirs, * sec_rgb;        // [n Ks | n Kd][3] the batched trace's directions and colours
+  const float* samples;                    // [n][Ks + Kd][RC_SMP_CH] local direction, pdf, MIS weight
+  const float* lossmult;                   // [n] or nullptr (1)
+  float vmf_scale;
+  int srgb;                                // linear_to_srgb on f and the likelihood
+  float coef_spec, coef_diff;              // mult / 2 / (n K_s): d loss / d (per-sample term)
+  float* loss_ray;                         // [n] per-point sum over s of (sum of the terms) / K_s, written
+  float* dvp;                              // [n][640] d loss / d vmf_params, written, or nullptr (loss only)
+};
+void rc_launch_light_sampling_loss_bwd(const RcLightLossArgs& a, hipStream_t st);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

@@ -153,6 +153,11 @@ class rc_geometry_loss(C.Structure):
 
 RC_ADAM_MAX_GROUPS = 8
 RC_LAYOUT_SHADER = -1
+RC_LAYOUT_LIGHT = -2
+
+
+class rc_light_sampling_loss(C.Structure):
+    _fields_ = [("mult", C.c_float), ("linear_to_srgb", C.c_int32)]
 
 
 class rc_adam_buffer(C.Structure):
@@ -174,7 +179,8 @@ EXPORTS = (
     "rc_prng_fill", "rc_density_grad_size", "rc_density_grad_layout", "rc_density_backward",
     "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs", "rc_interlevel_backward",
     "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward", "rc_geometry_backward", "rc_density_regularizer",
-    "rc_adam_update", "rc_load_params_flat",
+    "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
+    "rc_light_regularizer",
 )
 
 _LIB = None
@@ -289,6 +295,16 @@ def load_library():
     lib.rc_adam_update.restype = C.c_int
     lib.rc_load_params_flat.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.rc_load_params_flat.restype = C.c_int
+    lib.rc_light_grad_size.argtypes = [C.c_void_p]
+    lib.rc_light_grad_size.restype = C.c_int64
+    lib.rc_light_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.rc_light_grad_layout.restype = C.c_int
+    lib.rc_light_sampling_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
+                                               C.POINTER(rc_material_randoms), C.c_int32, C.POINTER(rc_light_sampling_loss),
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_light_sampling_backward.restype = C.c_int
+    lib.rc_light_regularizer.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_light_regularizer.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -623,7 +639,8 @@ class RadianceCache:
         total = sizes.get(level)
         if total is None:
             lib = self.lib
-            total = int(lib.rc_shader_grad_size(self._h) if level is None else lib.rc_density_grad_size(self._h, level))
+            total = int(lib.rc_shader_grad_size(self._h) if level is None else
+                        lib.rc_light_grad_size(self._h) if level == "light" else lib.rc_density_grad_size(self._h, level))
             if total < 0:
                 self._check(total)
             sizes[level] = total
@@ -827,6 +844,45 @@ class RadianceCache:
                                                     None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
         return flat, loss
 
+    def light_grad_layout(self):
+        """rc_light_grad_layout: [(tensor name, offset, shape)] of the LightSampler gradient buffer (the light_grid tables,
+        then layers_0, layers_1, output_layer), and its size in floats."""
+        return self._segments(self.lib.rc_light_grad_layout, ()), self._grad_size("light")
+
+    def light_sampling_backward(self, rays: Dict[str, object], randoms: Dict[str, object], num_secondary_samples: int = None,
+                                lossmult=None, mult: float = 1.0, linear_to_srgb: bool = True, grad=None,
+                                stream_handle=None):
+        """rc_light_sampling_backward: render_material's forward with the same rays / randoms / num_secondary_samples
+        (up to the secondary trace), the light_sampling loss (vmf_loss_fn over both suffixes) and its gradient w.r.t.
+        the LightSampler parameters (light_grad_layout).  grad: flat buffer to accumulate into (allocated zeroed when
+        None); grad=False computes the loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
+        torch = self._torch
+        K = num_secondary_samples or self.cfg.num_secondary_samples
+        r, held, n = self._rays_struct(rays)
+        rnd, mr = self._material_randoms(randoms, n, K, held)
+        lm = self._lossmult(lossmult, held, n)
+        cfg = rc_light_sampling_loss(mult=float(mult), linear_to_srgb=int(bool(linear_to_srgb)))
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("light"))
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        self._check(self.lib.rc_light_sampling_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n,
+                                                        C.byref(rnd), C.byref(mr), K, C.byref(cfg),
+                                                        None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
+        self._keep = [held]
+        return flat, loss
+
+    def light_regularizer(self, mult: float, grad=None):
+        """rc_light_regularizer: mult * sum over the light grid's tables of 0.5 * mean(x^2) (param_regularizer_loss,
+        'light_grid').  grad: flat buffer of light_grad_layout to accumulate mult * x / numel into (allocated zeroed when
+        None); grad=False computes the loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
+        torch = self._torch
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("light"))
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.rc_light_regularizer(self._h, float(mult), None if flat is None else flat.data_ptr(),
+                                                  loss.data_ptr(), stream))
+        return flat, loss
+
     # -- optimizer ------------------------------------------------------------------------------
     def adam_update(self, buffers, step: Dict[str, object], stream_handle=None):
         """rc_adam_update: one launch of the Adam step over flat buffers (plus two with the norm clip).
@@ -851,13 +907,13 @@ class RadianceCache:
         self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), stream))
 
     def load_params_flat(self, layout, params, stream_handle=None):
-        """rc_load_params_flat: load every tensor of one gradient layout (a density level, or "shader") from a flat
+        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader" or "light") from a flat
         float32 cuda buffer in that layout -- table copies ordered on the current stream, the dense layers in one copy
         to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
         same tensors, bitwise."""
         torch = self._torch
-        lay = RC_LAYOUT_SHADER if layout == "shader" else int(layout)
-        total = self._grad_size(None if lay == RC_LAYOUT_SHADER else lay)
+        lay = RC_LAYOUT_SHADER if layout == "shader" else RC_LAYOUT_LIGHT if layout == "light" else int(layout)
+        total = self._grad_size(None if lay == RC_LAYOUT_SHADER else "light" if lay == RC_LAYOUT_LIGHT else lay)
         if params.numel() != total or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
             raise ValueError(f"params must be a contiguous float32 cuda tensor of {total} elements")
         stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
@@ -985,16 +1041,10 @@ class RadianceCache:
         self._keep = [held]
         return res
 
-    def render_material(self, rays: Dict[str, object], randoms: Dict[str, object], num_secondary_samples: int = None):
-        """Material stage (rc_render_material).  randoms: dict with the keys of
-        oracle-compatible `draw_randoms` (jitter[3], gumbel, vmf_noise, spec_u1/u2, cos_u1/u2, vmf_lobe, vmf_v,
-        vmf_tmp, spec_jitter[3], spec_gumbel, diff_jitter[3], diff_gumbel) and optionally the categorical picks
-        themselves (resample_inds [n]; spec_resample_inds [n*Ks] + diff_resample_inds [n*Kd]), which replace the draws.
-        Returns (cache_outputs, material_outputs) as dicts of cuda tensors."""
+    def _material_randoms(self, randoms, n, K, held):
+        """The rc_randoms / rc_material_randoms of render_material and light_sampling_backward (device copies kept in
+        `held`)."""
         torch = self._torch
-        K = num_secondary_samples or self.cfg.num_secondary_samples
-        r, held, n = self._rays_struct(rays)
-        dev = f"cuda:{self.device}"
         rnd = rc_randoms()
         if randoms.get("jitter") is not None:
             for l, j in enumerate(randoms["jitter"]):
@@ -1039,6 +1089,18 @@ class RadianceCache:
             held["s_inds"] = torch.cat([self._dev(randoms["spec_resample_inds"], torch.int32).reshape(-1),
                                         self._dev(randoms["diff_resample_inds"], torch.int32).reshape(-1)])
             mr.sec_resample_inds = held["s_inds"].data_ptr()
+        return rnd, mr
+
+    def render_material(self, rays: Dict[str, object], randoms: Dict[str, object], num_secondary_samples: int = None):
+        """Material stage (rc_render_material).  randoms: dict with the keys of
+        oracle-compatible `draw_randoms` (jitter[3], gumbel, vmf_noise, spec_u1/u2, cos_u1/u2, vmf_lobe, vmf_v,
+        vmf_tmp, spec_jitter[3], spec_gumbel, diff_jitter[3], diff_gumbel) and optionally the categorical picks
+        themselves (resample_inds [n]; spec_resample_inds [n*Ks] + diff_resample_inds [n*Kd]), which replace the draws.
+        Returns (cache_outputs, material_outputs) as dicts of cuda tensors."""
+        torch = self._torch
+        K = num_secondary_samples or self.cfg.num_secondary_samples
+        r, held, n = self._rays_struct(rays)
+        rnd, mr = self._material_randoms(randoms, n, K, held)
         cout, mout = rc_outputs(), rc_mat_outputs()
         cres, mres = {}, {}
         c_items = [(i, nm, width) for i, (nm, width) in enumerate(OUTPUTS) if nm not in ("env_map_rgb", "rgb_no_env")]

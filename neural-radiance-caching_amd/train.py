@@ -44,6 +44,16 @@ The optimizer:
     (rc_load_params_flat per layout);
   * `cache_stage_step(rc, opt, rays, rgb, jitters)` -> one reference train step (train_utils.py:3128-3161) of the
     cache stage: cache_stage_grads into the optimizer's gradient buffers, the pmean, the update.
+
+The light sampler, first piece of the material_light_from_scratch stage:
+
+  * `light_sampling_grads(rc, rays, randoms, train_frac)` -> the light_sampling loss (train_utils.light_sampling_loss ->
+    render_utils.vmf_loss_fn) and the light_grid regularizer with their exact gradients of the LightSampler parameters
+    (rc_light_sampling_backward: the material forward up to the secondary trace, the loss backward, the light head's
+    backward and the light grid's scatter; rc_light_regularizer);
+  * `LightSamplerOptimizer(rc, cfg)` / `light_sampler_step(...)` -> the same optimizer state and step on the one light
+    layout (group "LightSampler").  The LightSampler's gradient from the material data loss (through the vMF-sampled
+    directions) is not part of these.
 """
 from __future__ import annotations
 
@@ -52,7 +62,7 @@ from typing import Dict, Iterable, List, Optional
 
 import numpy as np
 
-from .config import DataLossConfig, GeometryLossConfig, InterlevelConfig, OptimizerConfig
+from .config import DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, OptimizerConfig
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -410,4 +420,58 @@ def cache_stage_step(rc, opt: CacheStageOptimizer, rays, rgb, jitters, lossmult=
                                       interlevel_cfg)
     allreduce_grads([flats[k] for k in opt.keys], group=group)
     opt.step({k: flats[k] for k in opt.keys})
+    return losses
+
+
+# ---- the light sampler ---------------------------------------------------------------------------------------------
+
+def light_sampling_grads(rc, rays, randoms, train_frac: float, lossmult=None, flat=None,
+                         cfg: LightSamplingConfig = LightSamplingConfig()):
+    """The light sampler's own loss on a batch and its gradient: the light_sampling extra loss
+    (train_utils.py:1985-2067, active from cfg.start_frac of training) and param_regularizer_loss for 'light_grid', both
+    accumulated into `flat` (layout rc.light_grad_layout(); allocated zeroed when None).  randoms: render_material's.
+    -> (flat, losses) with losses keyed like the reference's losses_flat ("light_sampling", "regularizer/light_grid"),
+    0-d cuda tensors (the local batch's values)."""
+    mult = cfg.mult if train_frac >= cfg.start_frac else 0.0
+    flat, loss = rc.light_sampling_backward(rays, randoms, cfg.num_secondary_samples, lossmult, mult, cfg.linear_to_srgb,
+                                            flat)
+    flat, reg = rc.light_regularizer(cfg.light_grid_mult, flat)
+    return flat, {"light_sampling": loss[0], "regularizer/light_grid": reg[0]}
+
+
+class LightSamplerOptimizer(CacheStageOptimizer):
+    """The LightSampler's optimizer state on the device: flat params, mu, nu and gradients in the layout
+    rc.light_grad_layout() (key "light") and the optax count.  Every tensor is in param_group "LightSampler"; clip_gradients
+    takes its norm per top-level module, so a step is ONE rc_adam_update over this buffer, then rc_load_params_flat
+    (RC_LAYOUT_LIGHT).  init_from / params_dict / state_dict / load_state_dict as CacheStageOptimizer."""
+
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
+        import torch
+        from . import rc_ext
+
+        self.rc, self.cfg, self._rc_ext = rc, cfg, rc_ext
+        self.keys = ["light"]
+        self.layouts = {"light": rc.light_grad_layout()}
+        self.group_names = [g for g, _ in cfg.groups()]
+        dev = f"cuda:{rc.device}"
+        z = lambda k: torch.zeros(self.layouts[k][1], dtype=torch.float32, device=dev)
+        self.params = {k: z(k) for k in self.keys}
+        self.mu = {k: z(k) for k in self.keys}
+        self.nu = {k: z(k) for k in self.keys}
+        self.grads = {k: z(k) for k in self.keys}
+        self.segments = {k: [(off, int(np.prod(shape)), self.group_names.index(param_group(name, cfg)))
+                             for name, off, shape in self.layouts[k][0]] for k in self.keys}
+        self._table = self._adam_table(self.grads)
+        self.count = 0
+
+
+def light_sampler_step(rc, opt: LightSamplerOptimizer, rays, randoms, lossmult=None, group=None,
+                       cfg: LightSamplingConfig = LightSamplingConfig()):
+    """One train step of the light sampler on its own loss: train_frac from opt.count, light_sampling_grads into the
+    optimizer's zeroed gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().
+    -> the losses dict of light_sampling_grads."""
+    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
+    flat, losses = light_sampling_grads(rc, rays, randoms, tf, lossmult, opt.grads["light"], cfg)
+    allreduce_grads([flat], group=group)
+    opt.step({"light": flat})
     return losses
