@@ -286,7 +286,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * rc_render_transient), "p1:" .. "p3:" = the sets of rc_render_rays on further caller streams, "s:" = the batched
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
- * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer.
+ * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
+ * "ms:" = rc_material_smoothness_backward / rc_material_regularizer.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -313,6 +314,12 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "dh0" ([n][64]), "dfeat" ([n][32] d loss / d light-grid features), "loss_ray" ([n] per-ray sums), "part" (weight-gradient
  * K slices), "ones", "reg_part" (rc_light_regularizer's per-table partial sums, doubles).  The forward's own buffers
  * keep their set-0 / "s:" names ("m_pts", "m_nrm", "l_feat", "l_vmf", "l_vmf_logit", "sec_dirs", "sec_samples", "sec_rgb").
+ * "ms:": "cache_rgb" ([n][3]), "cache_acc" ([n]) (the primary pass's composite, not read), "pts" ([2n][3] the shading
+ * points x, then x' = x + noise_scale nu), "feat" ([2n][32] their material-grid features),
+ * "mat_p" ([n][5] the material at x', before nan_to_num), "loss_ray" ([n] per-point sums), "loss_part" (per-workgroup
+ * loss sums, doubles), "dfeat" ([2n][32] d loss / d features), "part" (per-workgroup partials of the dense layers'
+ * gradients), "reg_part" (rc_material_regularizer's per-table partial sums, doubles).  The forward's own buffers keep
+ * their set-0 names ("m_pts", "m_nrm", "m_mat", "filt_weight").
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -628,7 +635,7 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
 
 /* rc_load_params_flat: rc_load_weights of every tensor of one gradient layout, from a DEVICE buffer in that layout
  * (layout = density level l: rc_density_grad_layout(l); RC_LAYOUT_SHADER: rc_shader_grad_layout; RC_LAYOUT_LIGHT:
- * rc_light_grad_layout).  The grid tables
+ * rc_light_grad_layout; RC_LAYOUT_MATERIAL: rc_material_grad_layout).  The grid tables
  * are copied device to device into the handle's table buffers, ordered on `stream`; the dense-layer segments go to
  * the host in ONE copy (gathered on the device first when they are not contiguous), after which the call waits for
  * `stream` (the host repack needs them).  The derived tables (cell tables, level-2 pairs, cell records) and packs are
@@ -637,6 +644,7 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
  * unsupported. */
 #define RC_LAYOUT_SHADER (-1)
 #define RC_LAYOUT_LIGHT (-2)   /* rc_light_grad_layout */
+#define RC_LAYOUT_MATERIAL (-3)   /* rc_material_grad_layout */
 int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void* stream);
 
 /* ---- the light sampler's own loss -----------------------------------------------------------------
@@ -683,6 +691,51 @@ int rc_light_sampling_backward(rc_handle* h, const rc_rays* rays, const float* l
  * rc_light_grad_layout); the MLP segments are untouched.  Ordered on `stream`; the time-resolved cache handle is
  * unsupported.  Buffers: "ls:reg_part". */
 int rc_light_regularizer(rc_handle* h, float mult, float* light_grads, float* loss, void* stream);
+
+/* ---- the material network's smoothness loss ------------------------------------------------------
+ * material_smoothness (train_utils.material_smoothness_loss, internal/train_utils.py:2505-2700, with the hotdog values
+ * configs/nerf_ngp_yobo.gin:400-408) and its exact first-order gradient of the params/MaterialShader tensors.  With x the
+ * shading point of each ray (rc_render_material's pick, weight w = filt_weight), x' = x + noise_scale nu (stopped),
+ * m = material_mlp (material grid -> bottleneck_layer -> pred_brdf_layer -> albedo, roughness, metalness) and
+ * m' = nan_to_num(m at x'), lambda = lossmult_r w (no gradient):
+ *   loss = mult (weight_albedo mean_{n x 3} |(a - a') / max(1e-6, max(a, a'))| lambda      (tensoir_albedo; else |a - a'|)
+ *                + weight_other mean_n |r - r'| lambda + weight_other mean_n |m_metal - m_metal'| lambda)
+ * Both evaluations carry parameter gradients; nothing reaches the geometry.  JAX rules: max ties split the gradient,
+ * d|x|/dx = +1 at 0.  One call:
+ *   1. rc_render_material's steps 1-2 (the primary cache pass, the shading point's pick) with the same rnd / mrnd (only
+ *      mrnd's gumbel / resample_inds are read) on set 0, and its material lookup and head at the shading points:
+ *      m_pts, filt_weight and m_mat are bitwise what rc_render_material leaves there for the same inputs (no light head,
+ *      no BRDF sampling, no secondary trace; the material features go to "ms:feat", not to m_feat);
+ *   2. the loss (DEVICE float, written; fixed reduction order, bitwise reproducible);
+ *   3. only when material_grads is given: the exact gradient, ACCUMULATED into material_grads (layout
+ *      rc_material_grad_layout): the dense segments reduced over fixed per-workgroup partials (bitwise reproducible),
+ *      the material grid's tables through rc_hashgrid_backward at the 2n points.  NULL: the loss only.
+ * noise: [n][3] device floats (nu ~ N(0, 1)).  lossmult: [n] device or NULL (1).  The mean is over the local batch; a
+ * data-parallel trainer averages material_grads.  Missing material weights: RC_ERR_MISSING_WEIGHT; the time-resolved
+ * cache handle is unsupported.  n == 0 returns RC_OK and writes nothing.  Everything is ordered on `stream`.  Buffers of
+ * the call: set-0 / "ms:" names.
+ * Not covered: the material data loss's gradient (the Disney-GGX integration). */
+typedef struct {
+  float mult;                  /* the extra loss's multiplier (trainer.gin: 1.0) */
+  float weight_albedo;         /* Config.material_smoothness_weight_albedo (nerf_ngp_yobo.gin: 1e-4) */
+  float weight_other;          /* Config.material_smoothness_weight_other (nerf_ngp_yobo.gin: 1e-4) */
+  float noise;                 /* Config.material_smoothness_noise (nerf_ngp_yobo.gin: 0.01) */
+  int32_t tensoir_albedo;      /* Config.material_smoothness_tensoir_albedo (nerf_ngp_yobo.gin: True) */
+} rc_material_smoothness_loss;
+/* The material layout: params/MaterialShader/material_grid tables in level order (as rc_hashgrid_grad_layout(4)), then
+ * bottleneck_layer and pred_brdf_layer, kernel [in, out] then bias [out] each. */
+int64_t rc_material_grad_size(rc_handle* h);
+int rc_material_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count);
+int rc_material_smoothness_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                                    const rc_material_randoms* mrnd, const float* noise, const rc_material_smoothness_loss* cfg,
+                                    float* material_grads, float* loss, void* stream);
+/* param_regularizer_loss for 'material_grid' (train_utils.py:1169-1234; nerf_ngp_yobo.gin:47-51, (1.0, jnp.mean, 2, 1)):
+ * loss = mult * sum over the material grid's tables of 0.5 * mean(x^2), written to `loss` (DEVICE float; fixed
+ * reduction order); when material_grads is given, mult * x / numel(table) is ACCUMULATED into each table's segment of
+ * it (layout rc_material_grad_layout); the MLP segments are untouched.  The reference's ease factor for the prefix
+ * "material" is 1 in the material stages (use_material_weight_ease = False) and is the caller's (folded into mult).
+ * Ordered on `stream`; the time-resolved cache handle is unsupported.  Buffers: "ms:reg_part". */
+int rc_material_regularizer(rc_handle* h, float mult, float* material_grads, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

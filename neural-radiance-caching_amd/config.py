@@ -228,6 +228,34 @@ class LightSamplingConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class MaterialSmoothnessConfig:
+    """Training-time constants of the material network's smoothness loss, its grid regularizer and the stage's other
+    extra loss (the material_light_from_scratch stage, hotdog)."""
+    # the material_smoothness extra loss of the stage: "main" mult 1.0, start_frac 0.0 (configs/trainer.gin:340-344)
+    mult: float = 1.0
+    start_frac: float = 0.0
+    # Config.material_smoothness_* (configs/nerf_ngp_yobo.gin:400-408, ngp_yobo.gin:432)
+    l1_loss: bool = True                   # :400
+    tensoir_albedo: bool = True            # :401
+    noise: float = 0.01                    # :402
+    weight_albedo: float = 1e-4            # :403
+    weight_other: float = 1e-4             # :404
+    irradiance_weight: bool = False        # :408
+    albedo_stopgrad: bool = False          # ngp_yobo.gin:432
+    # Config.param_regularizers 'material_grid': (1.0, jnp.mean, 2, 1) (nerf_ngp_yobo.gin:47-51); the ease factor of the
+    # prefix "material" is 1 in the material stages (use_material_weight_ease = False, engine/trainer.py:518-536)
+    material_grid_mult: float = 1.0
+    material_grid_ease: float = 1.0
+    # the material_ray_sampler extra loss: "main" mult 1.0 (trainer.gin:334-338) times its four term mults, all 0
+    # (nerf_ngp_yobo.gin:52-53, internal/configs.py:531-534 defaults)
+    ray_sampler_mult: float = 1.0
+    ray_sampler_interlevel_mult: float = 0.0
+    ray_sampler_distortion_mult: float = 0.0
+    ray_sampler_orientation_mult: float = 0.0
+    ray_sampler_normal_mult: float = 0.0
+
+
+@dataclasses.dataclass(frozen=True)
 class ExtraOptParams:
     """One entry of Config.extra_opt_params (configs/ngp_yobo.gin:59-115): the Adam of the tensors whose path holds
     `prefix` as a whole element, and its schedule; the _material values replace the others when a material stage trains

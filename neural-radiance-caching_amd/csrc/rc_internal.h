@@ -543,6 +543,31 @@ struct RcLightLossArgs {
 };
 void rc_launch_light_sampling_loss_bwd(const RcLightLossArgs& a, hipStream_t st);
 
+// The material network's smoothness loss (rc_material_bwd.hip)
+constexpr int kRcMatSmoothParts = 32 * 128 + 128 + 128 * 10 + 10;   // floats of one workgroup's weight-gradient partial
+struct RcMatSmoothArgs {
+  int64_t n;                               // shading points
+  const float* feat_x, * feat_p;           // [n][32] material-grid features at x and at x'
+  const float* w0, * b0, * w1, * b1;       // bottleneck_layer [32][128], [128]; pred_brdf_layer [128][10], [10]
+  float min_roughness;
+  const float* filt_weight;                // [n] the shading sample's weight
+  const float* lossmult;                   // [n] or nullptr (1)
+  int tensoir;                             // material_smoothness_tensoir_albedo
+  float wa, wo;                            // weight_albedo / 3, weight_other: the per-point loss sum
+  float ga, go;                            // mult weight_albedo / (3 n), mult weight_other / n: d loss / d |term|
+  float* mat_x, * mat_p;                   // [n][RC_MAT_CH] the materials at x (bitwise m_mat) and at x', written
+  float* loss_ray;                         // [n] per-point loss sums, written
+  float* dfeat;                            // [2n][32] d loss / d features (x, then x'), written when part is given
+  float* part;                             // [rc_mat_smooth_blocks(n)][kRcMatSmoothParts] or nullptr (loss only)
+  double* loss_part;                       // [rc_mat_smooth_blocks(n)] per-workgroup loss sums, written
+};
+int rc_mat_smooth_blocks(int64_t n);
+void rc_launch_material_smoothness_points(const float* pts, const float* noise, float scale, int64_t n, float* out,
+                                          hipStream_t st);
+void rc_launch_material_smoothness_bwd(const RcMatSmoothArgs& a, hipStream_t st);
+// loss = mult * sum / n (fixed order); with grads: grads (the layout's four dense segments) += the partials, fixed order
+void rc_launch_material_smoothness_reduce(const RcMatSmoothArgs& a, float* grads, float mult, float* loss, hipStream_t st);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

@@ -331,3 +331,36 @@ def material_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
     out["vmf_tmp"] = uniform(kt, (n_rays, Kl))
     out["diff_jitter"], out["diff_gumbel"] = trace_randoms(kc_diff, Kd)
     return out
+
+
+# the extra losses of the material stage in _compute_extra_losses' dict order (internal/train_utils.py:3620-3632); each
+# enabled one takes one split of the key (:3648)
+EXTRA_LOSS_ORDER = ("emission", "residual_albedo", "direct_indirect_consistency", "light_sampling",
+                    "material_surface_light_field", "material_smoothness", "geometry_smoothness", "material_correlation",
+                    "material_ray_sampler", "maximum_radiance", "normalize_weight")
+# material_light_from_scratch's extra losses (configs/trainer.gin:333-350)
+MATERIAL_STAGE_EXTRA_LOSSES = ("material_ray_sampler", "material_smoothness", "light_sampling")
+
+
+def extra_loss_keys(cur_key, enabled: Sequence[str] = MATERIAL_STAGE_EXTRA_LOSSES) -> Dict[str, np.ndarray]:
+    """The key each enabled extra loss receives from _compute_extra_losses (train_utils.py:3648: rng, cur_key =
+    random.split(cur_key), in EXTRA_LOSS_ORDER)."""
+    out = {}
+    key = as_key(cur_key)
+    for name in EXTRA_LOSS_ORDER:
+        if name in enabled:
+            k = split(key)
+            out[name], key = k[0], k[1]
+    return out
+
+
+def material_smoothness_noise(loss_key, n_points: int) -> np.ndarray:
+    """nu of material_smoothness_loss (train_utils.py:2530-2574) from the key the loss receives: three splits (:2530 the
+    resample pick, :2541 the cache_shader pick, :2566 the noise), then normal(rng, [n, 3]) (:2568).  The perturbed
+    shading pass's key (:2574) is not drawn from here (material_only, shading_only: the material head draws nothing).
+    The order against a jax run is unverified (no jax here)."""
+    key = as_key(loss_key)
+    _, key = random_split(key)      # :2530
+    _, key = random_split(key)      # :2541
+    rng, _ = random_split(key)      # :2566
+    return normal(rng, (int(n_points), 3))

@@ -154,10 +154,16 @@ class rc_geometry_loss(C.Structure):
 RC_ADAM_MAX_GROUPS = 8
 RC_LAYOUT_SHADER = -1
 RC_LAYOUT_LIGHT = -2
+RC_LAYOUT_MATERIAL = -3
 
 
 class rc_light_sampling_loss(C.Structure):
     _fields_ = [("mult", C.c_float), ("linear_to_srgb", C.c_int32)]
+
+
+class rc_material_smoothness_loss(C.Structure):
+    _fields_ = [("mult", C.c_float), ("weight_albedo", C.c_float), ("weight_other", C.c_float), ("noise", C.c_float),
+                ("tensoir_albedo", C.c_int32)]
 
 
 class rc_adam_buffer(C.Structure):
@@ -180,7 +186,8 @@ EXPORTS = (
     "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs", "rc_interlevel_backward",
     "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward", "rc_geometry_backward", "rc_density_regularizer",
     "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
-    "rc_light_regularizer",
+    "rc_light_regularizer", "rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
+    "rc_material_regularizer",
 )
 
 _LIB = None
@@ -305,6 +312,17 @@ def load_library():
     lib.rc_light_sampling_backward.restype = C.c_int
     lib.rc_light_regularizer.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rc_light_regularizer.restype = C.c_int
+    lib.rc_material_grad_size.argtypes = [C.c_void_p]
+    lib.rc_material_grad_size.restype = C.c_int64
+    lib.rc_material_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.rc_material_grad_layout.restype = C.c_int
+    lib.rc_material_smoothness_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64,
+                                                    C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_void_p,
+                                                    C.POINTER(rc_material_smoothness_loss), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
+    lib.rc_material_smoothness_backward.restype = C.c_int
+    lib.rc_material_regularizer.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_material_regularizer.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -640,7 +658,9 @@ class RadianceCache:
         if total is None:
             lib = self.lib
             total = int(lib.rc_shader_grad_size(self._h) if level is None else
-                        lib.rc_light_grad_size(self._h) if level == "light" else lib.rc_density_grad_size(self._h, level))
+                        lib.rc_light_grad_size(self._h) if level == "light" else
+                        lib.rc_material_grad_size(self._h) if level == "material" else
+                        lib.rc_density_grad_size(self._h, level))
             if total < 0:
                 self._check(total)
             sizes[level] = total
@@ -907,13 +927,15 @@ class RadianceCache:
         self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), stream))
 
     def load_params_flat(self, layout, params, stream_handle=None):
-        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader" or "light") from a flat
+        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light" or "material")
+        from a flat
         float32 cuda buffer in that layout -- table copies ordered on the current stream, the dense layers in one copy
         to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
         same tensors, bitwise."""
         torch = self._torch
-        lay = RC_LAYOUT_SHADER if layout == "shader" else RC_LAYOUT_LIGHT if layout == "light" else int(layout)
-        total = self._grad_size(None if lay == RC_LAYOUT_SHADER else "light" if lay == RC_LAYOUT_LIGHT else lay)
+        named = {"shader": RC_LAYOUT_SHADER, "light": RC_LAYOUT_LIGHT, "material": RC_LAYOUT_MATERIAL}
+        lay = named[layout] if layout in named else int(layout)
+        total = self._grad_size({RC_LAYOUT_SHADER: None, RC_LAYOUT_LIGHT: "light", RC_LAYOUT_MATERIAL: "material"}.get(lay, lay))
         if params.numel() != total or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
             raise ValueError(f"params must be a contiguous float32 cuda tensor of {total} elements")
         stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
@@ -1040,6 +1062,72 @@ class RadianceCache:
         self._check(self.lib.rc_render_transient(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, shadow_p, C.byref(cout), stream))
         self._keep = [held]
         return res
+
+    def material_grad_layout(self):
+        """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid
+        tables, then bottleneck_layer, pred_brdf_layer), and its size in floats."""
+        return self._segments(self.lib.rc_material_grad_layout, ()), self._grad_size("material")
+
+    def _shading_randoms(self, randoms, held):
+        """The rc_randoms / rc_material_randoms of material_smoothness_backward: the primary pass's jitter and the shading
+        point's pick (gumbel or resample_inds) of render_material's randoms; the sampler members stay NULL."""
+        torch = self._torch
+        rnd = rc_randoms()
+        if randoms.get("jitter") is not None:
+            for l, j in enumerate(randoms["jitter"]):
+                held[f"jit{l}"] = self._dev(j).reshape(-1)
+                rnd.jitter[l] = held[f"jit{l}"].data_ptr()
+        mr = rc_material_randoms()
+        if randoms.get("resample_inds") is not None:
+            held["m_inds"] = self._dev(randoms["resample_inds"], torch.int32).reshape(-1)
+            mr.resample_inds = held["m_inds"].data_ptr()
+        elif randoms.get("gumbel") is not None:
+            held["m_gumbel"] = self._dev(randoms["gumbel"])
+            mr.gumbel = held["m_gumbel"].data_ptr()
+        return rnd, mr
+
+    def material_smoothness_backward(self, rays: Dict[str, object], randoms: Dict[str, object], noise, lossmult=None,
+                                     mult: float = 1.0, weight_albedo: float = 1e-4, weight_other: float = 1e-4,
+                                     noise_scale: float = 0.01, tensoir_albedo: bool = True, grad=None,
+                                     stream_handle=None):
+        """rc_material_smoothness_backward: render_material's primary pass and shading point with the same rays /
+        randoms (jitter, gumbel or resample_inds), the material_smoothness loss at x and x' = x + noise_scale * noise
+        (noise: [n, 3], N(0, 1)) and its gradient w.r.t. the MaterialShader parameters (material_grad_layout).  grad: flat
+        buffer to accumulate into (allocated zeroed when None); grad=False computes the loss only.
+        Returns (grad flat or None, loss [1] cuda tensor)."""
+        torch = self._torch
+        r, held, n = self._rays_struct(rays)
+        rnd, mr = self._shading_randoms(randoms, held)
+        lm = self._lossmult(lossmult, held, n)
+        nz = self._dev(noise).reshape(-1)
+        if nz.numel() != 3 * n:
+            raise ValueError("noise must hold [n, 3] values")
+        held["ms_noise"] = nz
+        cfg = rc_material_smoothness_loss(mult=float(mult), weight_albedo=float(weight_albedo),
+                                          weight_other=float(weight_other), noise=float(noise_scale),
+                                          tensoir_albedo=int(bool(tensoir_albedo)))
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("material"))
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        self._check(self.lib.rc_material_smoothness_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n,
+                                                             C.byref(rnd), C.byref(mr), nz.data_ptr(), C.byref(cfg),
+                                                             None if flat is None else flat.data_ptr(), loss.data_ptr(),
+                                                             stream))
+        self._keep = [held]
+        return flat, loss
+
+    def material_regularizer(self, mult: float, grad=None):
+        """rc_material_regularizer: mult * sum over the material grid's tables of 0.5 * mean(x^2) (param_regularizer_loss,
+        'material_grid', the ease factor folded into mult).  grad: flat buffer of material_grad_layout to accumulate
+        mult * x / numel into (allocated zeroed when None); grad=False computes the loss only.
+        Returns (grad flat or None, loss [1] cuda tensor)."""
+        torch = self._torch
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("material"))
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.rc_material_regularizer(self._h, float(mult), None if flat is None else flat.data_ptr(),
+                                                     loss.data_ptr(), stream))
+        return flat, loss
 
     def _material_randoms(self, randoms, n, K, held):
         """The rc_randoms / rc_material_randoms of render_material and light_sampling_backward (device copies kept in

@@ -54,6 +54,16 @@ The light sampler, first piece of the material_light_from_scr
   * `LightSamplerOptimizer(rc, cfg)` / `light_sampler_step(...)` -> the same optimizer state and step on the one light
     layout (group "LightSampler").  The LightSampler's gradient from the material data loss (through the vMF-sampled
     directions) is not part of these.
+
+The material network, second piece of that stage:
+
+  * `material_smoothness_grads(rc, rays, randoms, noise, train_frac)` -> the material_smoothness loss
+    (train_utils.material_smoothness_loss), the material_grid regularizer and material_ray_sampler (identically 0 for
+    hotdog) with the exact gradients of the MaterialShader parameters (rc_material_smoothness_backward: the primary pass
+    and shading point, both material evaluations and the head's backward in one kernel, the material grid's scatter;
+    rc_material_regularizer);
+  * `MaterialOptimizer(rc, cfg)` / `material_step(...)` -> the optimizer state and step on the material layout (group
+    "MaterialShader").  The material data loss's gradient (the Disney-GGX integration) is not part of these.
 """
 from __future__ import annotations
 
@@ -62,7 +72,8 @@ from typing import Dict, Iterable, List, Optional
 
 import numpy as np
 
-from .config import DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, OptimizerConfig
+from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaterialSmoothnessConfig,
+                     OptimizerConfig)
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -474,4 +485,78 @@ def light_sampler_step(rc, opt: LightSamplerOptimizer, rays, randoms, lossmult=N
     flat, losses = light_sampling_grads(rc, rays, randoms, tf, lossmult, opt.grads["light"], cfg)
     allreduce_grads([flat], group=group)
     opt.step({"light": flat})
+    return losses
+
+
+# ---- the material network ------------------------------------------------------------------------------------------
+
+def material_ray_sampler_loss(cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig(), interlevel=0.0, distortion=0.0,
+                              orientation=0.0, normal=0.0) -> float:
+    """train_utils.material_ray_sampler_loss (internal/train_utils.py:2273-2351) times its "main" mult, given the values
+    of its four terms on the reference rays: interlevel * interlevel_mult + distortion * normal_mult * distortion_mult
+    + orientation * orientation_mult + (predicted normal + reverse) * normal_mult.  Every term mult is 0 for hotdog
+    (nerf_ngp_yobo.gin:52-53, configs.py:531-534), so the loss is identically 0 and no backward is needed."""
+    total = (interlevel * cfg.ray_sampler_interlevel_mult
+             + distortion * cfg.ray_sampler_normal_mult * cfg.ray_sampler_distortion_mult
+             + orientation * cfg.ray_sampler_orientation_mult + normal * cfg.ray_sampler_normal_mult)
+    return cfg.ray_sampler_mult * total
+
+
+def material_smoothness_grads(rc, rays, randoms, noise, train_frac: float, lossmult=None, flat=None,
+                              cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig()):
+    """The material network's own losses on a batch and their gradient: the material_smoothness extra
+    loss (train_utils.py:2505-2700, active from cfg.start_frac of training) and param_regularizer_loss for
+    'material_grid', both accumulated into `flat` (layout rc.material_grad_layout(); allocated zeroed when None), and
+    material_ray_sampler (0: no gradient).  randoms: render_material's (jitter, gumbel or resample_inds are read); noise:
+    [n, 3] N(0, 1) (prng.material_smoothness_noise).  -> (flat, losses) with losses keyed like the reference's
+    losses_flat ("material_smoothness", "regularizer/material_grid", "material_ray_sampler"), 0-d cuda tensors (the local
+    batch's values)."""
+    import torch
+
+    if not (cfg.l1_loss and not cfg.irradiance_weight and not cfg.albedo_stopgrad):
+        raise NotImplementedError("material_smoothness: only the l1 form without irradiance weight or albedo stopgrad")
+    mult = cfg.mult if train_frac >= cfg.start_frac else 0.0
+    flat, loss = rc.material_smoothness_backward(rays, randoms, noise, lossmult, mult, cfg.weight_albedo, cfg.weight_other,
+                                                 cfg.noise, cfg.tensoir_albedo, flat)
+    flat, reg = rc.material_regularizer(cfg.material_grid_mult * cfg.material_grid_ease, flat)
+    zero = torch.zeros((), dtype=torch.float32, device=loss.device) + material_ray_sampler_loss(cfg)
+    return flat, {"material_smoothness": loss[0], "regularizer/material_grid": reg[0], "material_ray_sampler": zero}
+
+
+class MaterialOptimizer(CacheStageOptimizer):
+    """The MaterialShader's optimizer state on the device: flat params, mu, nu and gradients in the layout
+    rc.material_grad_layout() (key "material") and the optax count.  Every tensor is in param_group "MaterialShader";
+    clip_gradients takes its norm per top-level module, so a step is ONE rc_adam_update over this buffer, then
+    rc_load_params_flat (RC_LAYOUT_MATERIAL).  init_from / params_dict / state_dict / load_state_dict as
+    CacheStageOptimizer."""
+
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
+        import torch
+        from . import rc_ext
+
+        self.rc, self.cfg, self._rc_ext = rc, cfg, rc_ext
+        self.keys = ["material"]
+        self.layouts = {"material": rc.material_grad_layout()}
+        self.group_names = [g for g, _ in cfg.groups()]
+        dev = f"cuda:{rc.device}"
+        z = lambda k: torch.zeros(self.layouts[k][1], dtype=torch.float32, device=dev)
+        self.params = {k: z(k) for k in self.keys}
+        self.mu = {k: z(k) for k in self.keys}
+        self.nu = {k: z(k) for k in self.keys}
+        self.grads = {k: z(k) for k in self.keys}
+        self.segments = {k: [(off, int(np.prod(shape)), self.group_names.index(param_group(name, cfg)))
+                             for name, off, shape in self.layouts[k][0]] for k in self.keys}
+        self._table = self._adam_table(self.grads)
+        self.count = 0
+
+
+def material_step(rc, opt: MaterialOptimizer, rays, randoms, noise, lossmult=None, group=None,
+                  cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig()):
+    """One train step of the material network on its own losses: train_frac from opt.count, material_smoothness_grads
+    into the optimizer's zeroed gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().
+    -> the losses dict of material_smoothness_grads."""
+    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
+    flat, losses = material_smoothness_grads(rc, rays, randoms, noise, tf, lossmult, opt.grads["material"], cfg)
+    allreduce_grads([flat], group=group)
+    opt.step({"material": flat})
     return losses

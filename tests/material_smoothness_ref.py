@@ -1,0 +1,94 @@
+"""Torch restatement of the material network's smoothness loss with JAX's differentiation rules, for the
+CPU and GPU tests of rc_material_smoothness_backward.
+
+  material_smoothness  internal/train_utils.py:2505-2700 with the hotdog values (configs/nerf_ngp_yobo.gin:400-408,
+                       ngp_yobo.gin:432): l1, tensoir albedo, no irradiance weight, no albedo stopgrad
+  material head        oracle.material_ref.material_mlp (material grid, bottleneck_layer, pred_brdf_layer, the heads)
+  lambda               lossmult_r * sg(w) (:2601-2607), w the shading sample's weight
+
+JAX rules restated here (jax 0.4.16, read from the source, not run): jnp.abs' JVP is select(x >= 0, g, -g) (+1 at 0;
+torch's sign gives 0 there); jnp.maximum gives half the gradient to each side on a tie; jnp.nan_to_num passes the
+gradient unchanged where the value is finite."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from oracle import material_ref
+
+P = "params/"
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def jabs(x):
+    """jnp.abs with jax's JVP: d|x|/dx = +1 at x = 0 (torch.abs would give 0)."""
+    return torch.where(x >= 0, x, -x)
+
+
+def jmaximum(u, v):
+    """jnp.maximum(u, v) of two traced arrays: the larger side takes the gradient, half each on a tie."""
+    return torch.where(u > v, u, torch.where(u < v, v, 0.5 * (u + v)))
+
+
+def jmax_const(c: float, x):
+    """jnp.maximum(c, x) with a constant c: the gradient passes where x > c, half of it where x == c."""
+    out = torch.where(x > c, x, torch.full_like(x, c))
+    return out + torch.where(x == c, 0.5 * (x - x.detach()), torch.zeros_like(x))
+
+
+def nan_to_num(x):
+    """jnp.nan_to_num: nan -> 0, +-inf -> +-float32 max; the gradient passes unchanged where x is finite."""
+    fixed = torch.nan_to_num(x.detach(), nan=0.0, posinf=F32_MAX, neginf=-F32_MAX)
+    return torch.where(torch.isfinite(x), x, fixed)
+
+
+def material(weights, cfg, pts):
+    """(albedo [n, 3], roughness [n], metalness [n]) of material_mlp at pts [n, 3]."""
+    m = material_ref.material_mlp(weights, cfg, pts)
+    return m["albedo"], m["roughness"][..., 0], m["metalness"][..., 0]
+
+
+def smoothness_loss(mx, mp, lam, mult: float = 1.0, weight_albedo: float = 1e-4, weight_other: float = 1e-4,
+                    tensoir: bool = True):
+    """material_smoothness from the materials at x (mx) and x' (mp, before nan_to_num) and lambda [n] (not stopped here:
+    the caller passes lossmult * w.detach())."""
+    (a, r, m), (ap, rp, mpm) = mx, tuple(nan_to_num(t) for t in mp)
+    d = a - ap
+    if tensoir:
+        d = d / jmax_const(1e-6, jmaximum(a, ap))
+    loss = weight_albedo * (jabs(d) * lam[:, None]).mean()
+    loss = loss + weight_other * (jabs(r - rp) * lam).mean()
+    loss = loss + weight_other * (jabs(m - mpm) * lam).mean()
+    return mult * loss
+
+
+def chain_loss(weights, cfg, x, xp, lossmult, w, mult: float = 1.0, weight_albedo: float = 1e-4, weight_other: float = 1e-4,
+               tensoir: bool = True):
+    """The whole loss at the shading points x and x' (both stop-gradiented) with lambda = lossmult * sg(w)."""
+    lam = lossmult * w.detach()
+    return smoothness_loss(material(weights, cfg, x.detach()), material(weights, cfg, xp.detach()), lam, mult,
+                           weight_albedo, weight_other, tensoir)
+
+
+def loop_loss(mx, mp, lam, mult=1.0, weight_albedo=1e-4, weight_other=1e-4, tensoir=True):
+    """The reference expression as plain loops over points and channels (floats)."""
+    a, r, m = (np.asarray(t, np.float64) for t in mx)
+    ap, rp, mpm = (np.nan_to_num(np.asarray(t, np.float64), nan=0.0, posinf=F32_MAX, neginf=-F32_MAX) for t in mp)
+    lam = np.asarray(lam, np.float64)
+    n = len(lam)
+    alb = 0.0
+    for i in range(n):
+        for c in range(3):
+            d = a[i, c] - ap[i, c]
+            if tensoir:
+                d = d / max(1e-6, max(a[i, c], ap[i, c]))
+            alb += abs(d) * lam[i]
+    rough = sum(abs(r[i] - rp[i]) * lam[i] for i in range(n))
+    metal = sum(abs(m[i] - mpm[i]) * lam[i] for i in range(n))
+    return mult * (weight_albedo * alb / (3 * n) + weight_other * rough / n + weight_other * metal / n)
+
+
+def material_layout(cfg):
+    """The material layout's (name, shape) in order: material_grid tables, then bottleneck_layer, pred_brdf_layer."""
+    from nrc_amd import weights as W
+    return [(k, tuple(v)) for k, v in W.param_shapes(cfg, ("material",)).items() if k.startswith(f"{P}MaterialShader/")]
