@@ -287,7 +287,7 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
- * "ms:" = rc_material_smoothness_backward / rc_material_regularizer.
+ * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -714,7 +714,7 @@ int rc_light_regularizer(rc_handle* h, float mult, float* light_grads, float* lo
  * data-parallel trainer averages material_grads.  Missing material weights: RC_ERR_MISSING_WEIGHT; the time-resolved
  * cache handle is unsupported.  n == 0 returns RC_OK and writes nothing.  Everything is ordered on `stream`.  Buffers of
  * the call: set-0 / "ms:" names.
- * Not covered: the material data loss's gradient (the Disney-GGX integration). */
+ * The material data loss: rc_material_data_backward. */
 typedef struct {
   float mult;                  /* the extra loss's multiplier (trainer.gin: 1.0) */
   float weight_albedo;         /* Config.material_smoothness_weight_albedo (nerf_ngp_yobo.gin: 1e-4) */
@@ -736,6 +736,47 @@ int rc_material_smoothness_backward(rc_handle* h, const rc_rays* rays, const flo
  * "material" is 1 in the material stages (use_material_weight_ease = False) and is the caller's (folded into mult).
  * Ordered on `stream`; the time-resolved cache handle is unsupported.  Buffers: "ms:reg_part". */
 int rc_material_regularizer(rc_handle* h, float mult, float* material_grads, float* loss, void* stream);
+
+/* ---- the material stage's data loss --------------------------------------------------------------
+ * The "data" term of the material_light_from_scratch stage: train_utils.compute_data_loss on the MaterialIntegrator's
+ * rgb (internal/train_utils.py:402-528) with loss_type 'rawnerf_transient_unbiased', which _select_data_loss_function
+ * maps to compute_unbiased_loss_rawnerf (:173-197), and its exact gradient of the params/MaterialShader tensors.  With
+ * rgb = w sh_rgb + max(0, 1 - acc) bg (rc_render_material's "rgb"), c = the primary cache pass's rgb (the rendering's
+ * "cache_rgb", which _get_rgb_clip_for_rawnerf reads first), gt_c = clip(c, 0, clip_val) (or clip(gt, 0, clip_val) when
+ * use_gt_rawnerf), then clip(max(., gt), 0, clip_val) when use_combined_rawnerf, then its norm over the channels when
+ * use_norm_rawnerf, s = 1 / (sg(gt_c) ** exponent + eps) per ray and channel, lossmult_rc = 0 where gt > thresh:
+ *   loss = weight * mult * mean_{n x 3}(lossmult * 2 (rgb - gt) sg(rgb - gt) s)
+ * The gradient is the one of the reference's Trainer.stopgrad = True reading (MaterialMLP.stopgrad_rays =
+ * stopgrad_samples = True): path (a), through the material grid, bottleneck_layer, pred_brdf_layer, the heads, F0, GGX D,
+ * Smith G (k = a / 2), Lambert, the clip of radiance * lobe, the means over the samples and rgb; every input of the
+ * integration read from the secondary trace (directions, pdf, MIS weight, cache radiance, acc, EnvMap radiance), w and
+ * the primary geometry are constants.  Not covered: the default hotdog reading's path (b) (roughness -> GGX-sampled
+ * direction), and the gradients of the Cache, EnvMap and LightSampler through this loss.  One call:
+ *   1. rc_render_material itself with the same rnd / mrnd / num_secondary_samples (set 0, "s:"): its buffers are
+ *      bitwise what a plain rc_render_material call leaves; its primary composite goes to "md:cache_rgb" / "md:cache_acc";
+ *   2. the loss (DEVICE float, written; fixed reduction order, bitwise reproducible); "md:rgb" = the rebuilt rgb, bitwise
+ *      rc_render_material's;
+ *   3. only when material_grads is given: the gradient, ACCUMULATED into material_grads (layout rc_material_grad_layout):
+ *      the dense segments reduced over fixed per-workgroup partials (bitwise reproducible), the material grid's tables
+ *      through rc_hashgrid_backward at the shading points.  NULL: the loss only.
+ * gt_rgb: [n][3] device floats.  lossmult: [n] device or NULL (1); a caller with masks folds them in (mask_lossmult).
+ * The mean is over the local batch; a data-parallel trainer averages material_grads.  Missing material or EnvMap weights:
+ * RC_ERR_MISSING_WEIGHT; the time-resolved cache handle is unsupported.  n == 0 returns RC_OK and writes nothing.
+ * Everything is ordered on `stream`.  Buffers of the call: set-0 / "s:" / "md:" names. */
+typedef struct {
+  float mult;                  /* Config.data_loss_mult (ngp_yobo.gin: 1.0) */
+  float weight;                /* MaterialModel.loss_weight (nerf_ngp_yobo.gin: 0.1) times material_loss_weight_ease (1) */
+  float exponent;              /* Config.rawnerf_exponent_material (nerf_ngp_yobo.gin: 1) */
+  float eps;                   /* Config.rawnerf_eps_material (nerf_ngp_yobo.gin: 1e-2) */
+  float clip_val;              /* compute_unbiased_loss_rawnerf's clip_val (1e4) */
+  float thresh;                /* Config.loss_thresh (configs.py: 1e6) */
+  int32_t use_gt_rawnerf;      /* Config.use_gt_rawnerf (configs.py: False) */
+  int32_t use_combined_rawnerf; /* Config.use_combined_rawnerf (configs.py: True) */
+  int32_t use_norm_rawnerf;    /* Config.use_norm_rawnerf (configs.py: False) */
+} rc_material_data_loss;
+int rc_material_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, const float* lossmult, int64_t n,
+                              const rc_randoms* rnd, const rc_material_randoms* mrnd, int32_t num_secondary_samples,
+                              const rc_material_data_loss* cfg, float* material_grads, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

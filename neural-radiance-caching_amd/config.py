@@ -256,6 +256,50 @@ class MaterialSmoothnessConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class MaterialDataLossConfig:
+    """Training-time constants of the material stage's data loss: the "data" term of the MaterialIntegrator's output
+    "main" (train_utils.compute_data_loss, internal/train_utils.py:402-528, via loss_fn :3005-3080 and
+    _compute_integrator_losses :3325-3345; hotdog is not use_transient).  _select_data_loss_function (:664-669) maps the
+    loss type to compute_unbiased_loss_rawnerf (:173-197), per ray and channel (Oddities)."""
+    # MaterialModel.loss / loss_weight (configs/nerf_ngp_yobo.gin:427-428, over ngp_yobo.gin:32-33)
+    loss_type: str = "rawnerf_transient_unbiased"
+    loss_weight: float = 0.1
+    # Config.data_loss_mult (ngp_yobo.gin:456), applied in loss_fn (train_utils.py:2917)
+    data_loss_mult: float = 1.0
+    # material_loss_weight_ease (train_utils.py:2990, 3012): 1 in the material stages
+    # (use_material_weight_ease = False, engine/trainer.py:518-536)
+    material_loss_weight_ease: float = 1.0
+    # Config.rawnerf_exponent_material / rawnerf_eps_material (nerf_ngp_yobo.gin:437, 440), is_material (:3019-3021)
+    exponent: float = 1.0
+    eps: float = 1e-2
+    # compute_unbiased_loss_rawnerf's default clip_val (train_utils.py:173; compute_data_loss passes none)
+    clip_val: float = 1e4
+    # Config.loss_thresh (internal/configs.py:447): gt > thresh zeroes lossmult
+    loss_thresh: float = 1e6
+    # Config.use_gt_rawnerf / use_combined_rawnerf / use_norm_rawnerf (configs.py:587-590; no gin overrides;
+    # use_combined_rawnerf_material, configs.py:589, is read nowhere)
+    use_gt_rawnerf: bool = False
+    use_combined_rawnerf: bool = True
+    use_norm_rawnerf: bool = False
+    # Config.use_loss_clip (configs.py:446): skipped for an "unbiased" loss type (train_utils.py:466)
+    use_loss_clip: bool = False
+    # Config.mask_lossmult (nerf_ngp_yobo.gin:369): False, but an "unbiased" type multiplies lossmult by the masks
+    # anyway (train_utils.py:447-451); batch.masks None -> ones.  The caller folds masks into lossmult.
+    mask_lossmult: bool = False
+    # _filter_rays_by_normal (train_utils.py:3550-3597): ones_like of both comparisons times rays.lossmult, and
+    # filter_retroreflective = False (configs.py:594): lossmult unchanged whatever filter_normals_thresh (1.01, :596) and
+    # material_loss_radius (2.0, nerf_ngp_yobo.gin:475) are
+    filter_normals_thresh: float = 1.01
+    # the stage's num_secondary_samples 4 (configs/trainer.gin:327) times Trainer.sample_factor 2 (engine/trainer.py:86)
+    num_secondary_samples: int = 8
+
+    @property
+    def weight(self) -> float:
+        """The loss's factor in losses_flat["data"]: loss_weight * material_loss_weight_ease."""
+        return self.loss_weight * self.material_loss_weight_ease
+
+
+@dataclasses.dataclass(frozen=True)
 class ExtraOptParams:
     """One entry of Config.extra_opt_params (configs/ngp_yobo.gin:59-115): the Adam of the tensors whose path holds
     `prefix` as a whole element, and its schedule; the _material values replace the others when a material stage trains

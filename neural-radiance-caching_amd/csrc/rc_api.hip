@@ -103,6 +103,10 @@ struct LightWs { WsBuf cache_rgb, cache_acc, h0, h1, vp, dvp, dh1, dh0, dfeat, l
 // features of both evaluations, the materials at x', the per-point and per-workgroup loss sums, d loss / d features, the
 // per-workgroup weight-gradient partials; rc_material_regularizer's per-table partial sums.
 struct MaterialWs { WsBuf cache_rgb, cache_acc, pts, feat, mat_p, loss_ray, loss_part, dfeat, part, reg_part; };
+// rc_material_data_backward (its forward is rc_render_material on set 0 and WS_SECONDARY): the primary pass's composite
+// ("cache_rgb" is read by the loss), the rebuilt rgb, the per-point loss sums and d loss / d material, d loss / d features,
+// the per-workgroup weight-gradient partials and loss sums.
+struct MatDataWs { WsBuf cache_rgb, cache_acc, rgb, loss_ray, dmat, dfeat, part, loss_part; };
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
@@ -110,15 +114,16 @@ struct MaterialWs { WsBuf cache_rgb, cache_acc, pts, feat, mat_p, loss_ray, loss
 // WS_TRAIN serves rc_density_backward (TrainWs only), WS_INTERLEVEL rc_interlevel_backward, WS_DATA rc_data_backward,
 // WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat, WS_LIGHT
 // the buffers of rc_light_sampling_backward's own (its forward runs on WS_RENDER0 + WS_SECONDARY) and rc_light_regularizer,
-// WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer.
+// WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer,
+// WS_MATDATA those of rc_material_data_backward (its forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY).
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -138,7 +143,7 @@ struct WsName {
   WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
   WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr; WsBuf DataWs::*d = nullptr;
   WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
-  WsBuf MaterialWs::*ms = nullptr;
+  WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -150,6 +155,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf OptimWs::*m) : name(s), o(m) {}
   constexpr WsName(const char* s, WsBuf LightWs::*m) : name(s), ls(m) {}
   constexpr WsName(const char* s, WsBuf MaterialWs::*m) : name(s), ms(m) {}
+  constexpr WsName(const char* s, WsBuf MatDataWs::*m) : name(s), md(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -161,7 +167,8 @@ struct WsName {
       if (g) return one(s, g);
       if (o) return one(s, o);
       if (ls) return one(s, ls);
-      return ms ? one(s, ms) : nullptr;
+      if (ms) return one(s, ms);
+      return md ? one(s, md) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -171,7 +178,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -193,10 +200,12 @@ constexpr WsName kTable[] = {
     WS(L, cache_rgb), WS(L, cache_acc), WS(L, h0), WS(L, h1), WS(L, vp), WS(L, dvp), WS(L, dh1), WS(L, dh0), WS(L, dfeat),
     WS(L, loss_ray), WS(L, part), WS(L, ones), WS(L, reg_part),
     WS(M, cache_rgb), WS(M, cache_acc), WS(M, pts), WS(M, feat), WS(M, mat_p), WS(M, loss_ray), WS(M, loss_part), WS(M, dfeat),
-    WS(M, part), WS(M, reg_part)};
+    WS(M, part), WS(M, reg_part),
+    WS(MD, cache_rgb), WS(MD, cache_acc), WS(MD, rgb), WS(MD, loss_ray), WS(MD, dmat), WS(MD, dfeat), WS(MD, part),
+    WS(MD, loss_part)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -1973,4 +1982,5 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_geometry_host.inc"
 #include "rc_light_host.inc"
 #include "rc_material_bwd_host.inc"
+#include "rc_material_data_host.inc"
 #include "rc_optim_host.inc"

@@ -567,6 +567,45 @@ void rc_launch_material_smoothness_points(const float* pts, const float* noise, 
 void rc_launch_material_smoothness_bwd(const RcMatSmoothArgs& a, hipStream_t st);
 // loss = mult * sum / n (fixed order); with grads: grads (the layout's four dense segments) += the partials, fixed order
 void rc_launch_material_smoothness_reduce(const RcMatSmoothArgs& a, float* grads, float mult, float* loss, hipStream_t st);
+// the same reduction for any caller of material_head_bwd: nparts (<= 1024) partials of kRcMatSmoothParts floats and
+// per-workgroup loss sums; loss = mult * (sum) / count
+void rc_launch_material_partials_reduce(const float* part, int nparts, const double* loss_part, float* grads, float mult,
+                                        double count, float* loss, hipStream_t st);
+
+// The material stage's data loss (rc_material_data.hip)
+struct RcMatDataArgs {
+  int64_t n; int32_t Ks, Kd, S;
+  // rc_render_material's step-7 inputs (set 0), read as k_material_integrate reads them
+  const float* mat; const float* samples; const float* local_view;
+  const float* sec_rgb; const float* sec_acc; const float* sec_env;
+  const float* weights;                    // [n][S] unfiltered weights of the primary rays
+  const float* filt_weight;                // [n]
+  float f0, rgb_max, bg;
+  // the loss
+  const float* gt;                         // [n][3]
+  const float* lossmult;                   // [n] or nullptr (1)
+  const float* cache_rgb;                  // [n][3] the primary cache pass's rgb (the rendering's "cache_rgb")
+  float exponent, eps, clip_val, thresh;
+  int use_gt, use_combined, use_norm;
+  float coef;                              // weight * data_loss_mult / (3 n): d loss / d (per-element term)
+  float* rgb;                              // [n][3] the rebuilt rgb, written
+  float* loss_ray;                         // [n] per-point sums over the channels of lossmult 2 d sg(d) s, written
+  float* dmat;                             // [n][5] d loss / d (albedo rgb, roughness, metalness), written, or nullptr
+};
+void rc_launch_material_data_bwd(const RcMatDataArgs& a, hipStream_t st);
+struct RcMatDataHeadArgs {
+  int64_t n;
+  const float* feat;                       // [n][32] material-grid features at the shading points (m_feat)
+  const float* w0, * b0, * w1, * b1;
+  float min_roughness;
+  const float* dmat;                       // [n][5] or nullptr (loss only)
+  const float* loss_ray;                   // [n]
+  float* dfeat;                            // [n][32] d loss / d features, written when part is given
+  float* part;                             // [rc_mat_data_blocks(n)][kRcMatSmoothParts] or nullptr (loss only)
+  double* loss_part;                       // [rc_mat_data_blocks(n)] per-workgroup loss sums, written
+};
+int rc_mat_data_blocks(int64_t n);
+void rc_launch_material_data_head_bwd(const RcMatDataHeadArgs& a, hipStream_t st);
 
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;

@@ -166,6 +166,12 @@ class rc_material_smoothness_loss(C.Structure):
                 ("tensoir_albedo", C.c_int32)]
 
 
+class rc_material_data_loss(C.Structure):
+    _fields_ = [("mult", C.c_float), ("weight", C.c_float), ("exponent", C.c_float), ("eps", C.c_float),
+                ("clip_val", C.c_float), ("thresh", C.c_float), ("use_gt_rawnerf", C.c_int32),
+                ("use_combined_rawnerf", C.c_int32), ("use_norm_rawnerf", C.c_int32)]
+
+
 class rc_adam_buffer(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
                 ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
@@ -187,7 +193,7 @@ EXPORTS = (
     "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward", "rc_geometry_backward", "rc_density_regularizer",
     "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
     "rc_light_regularizer", "rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
-    "rc_material_regularizer",
+    "rc_material_regularizer", "rc_material_data_backward",
 )
 
 _LIB = None
@@ -323,6 +329,10 @@ def load_library():
     lib.rc_material_smoothness_backward.restype = C.c_int
     lib.rc_material_regularizer.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rc_material_regularizer.restype = C.c_int
+    lib.rc_material_data_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_int32,
+                                              C.POINTER(rc_material_data_loss), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_material_data_backward.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -1127,6 +1137,40 @@ class RadianceCache:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rc_material_regularizer(self._h, float(mult), None if flat is None else flat.data_ptr(),
                                                      loss.data_ptr(), stream))
+        return flat, loss
+
+    def material_data_backward(self, rays: Dict[str, object], randoms: Dict[str, object], gt_rgb,
+                               num_secondary_samples: int = None, lossmult=None, cfg=None, grad=None, stream_handle=None):
+        """rc_material_data_backward: render_material with the same rays / randoms / num_secondary_samples, the material
+        stage's data loss against gt_rgb ([n, 3]) with the constants of cfg (config.MaterialDataLossConfig) and its
+        gradient w.r.t. the MaterialShader parameters (material_grad_layout; the Trainer.stopgrad = True reading,
+        DESIGN.md §4.12).  grad: flat buffer to accumulate into (allocated zeroed when None); grad=False computes the
+        loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
+        from .config import MaterialDataLossConfig
+
+        torch = self._torch
+        cfg = MaterialDataLossConfig() if cfg is None else cfg
+        K = num_secondary_samples or self.cfg.num_secondary_samples
+        r, held, n = self._rays_struct(rays)
+        rnd, mr = self._material_randoms(randoms, n, K, held)
+        lm = self._lossmult(lossmult, held, n)
+        gt = self._dev(gt_rgb).reshape(-1)
+        if gt.numel() != 3 * n:
+            raise ValueError("gt_rgb must hold [n, 3] values")
+        held["md_gt"] = gt
+        c = rc_material_data_loss(mult=float(cfg.data_loss_mult), weight=float(cfg.weight), exponent=float(cfg.exponent),
+                                  eps=float(cfg.eps), clip_val=float(cfg.clip_val), thresh=float(cfg.loss_thresh),
+                                  use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
+                                  use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)),
+                                  use_norm_rawnerf=int(bool(cfg.use_norm_rawnerf)))
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("material"))
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        self._check(self.lib.rc_material_data_backward(self._h, C.byref(r), gt.data_ptr(),
+                                                       None if lm is None else lm.data_ptr(), n, C.byref(rnd), C.byref(mr),
+                                                       K, C.byref(c), None if flat is None else flat.data_ptr(),
+                                                       loss.data_ptr(), stream))
+        self._keep = [held]
         return flat, loss
 
     def _material_randoms(self, randoms, n, K, held):

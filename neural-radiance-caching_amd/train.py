@@ -72,8 +72,8 @@ from typing import Dict, Iterable, List, Optional
 
 import numpy as np
 
-from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaterialSmoothnessConfig,
-                     OptimizerConfig)
+from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaterialDataLossConfig,
+                     MaterialSmoothnessConfig, OptimizerConfig)
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -557,6 +557,45 @@ def material_step(rc, opt: MaterialOptimizer, rays, randoms, noise, lossmult=Non
     -> the losses dict of material_smoothness_grads."""
     tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
     flat, losses = material_smoothness_grads(rc, rays, randoms, noise, tf, lossmult, opt.grads["material"], cfg)
+    allreduce_grads([flat], group=group)
+    opt.step({"material": flat})
+    return losses
+
+
+def material_data_grads(rc, rays, randoms, gt_rgb, lossmult=None, flat=None,
+                        cfg: MaterialDataLossConfig = MaterialDataLossConfig()):
+    """The material stage's data loss on a batch and its MaterialShader gradient: compute_data_loss of
+    the MaterialIntegrator's rgb against gt_rgb ([n, 3]) times loss_weight, material_loss_weight_ease and data_loss_mult,
+    accumulated into `flat` (layout rc.material_grad_layout(); allocated zeroed when None).  The gradient is the
+    Trainer.stopgrad = True reading (path (a)); the Cache, EnvMap and LightSampler get none from this call.  randoms:
+    render_material's.  -> (flat, {"data": 0-d cuda tensor}), the key of the reference's losses_flat."""
+    if cfg.loss_type != "rawnerf_transient_unbiased" or cfg.use_loss_clip:
+        raise NotImplementedError("material data loss: only the rawnerf unbiased form without loss clip")
+    flat, loss = rc.material_data_backward(rays, randoms, gt_rgb, cfg.num_secondary_samples, lossmult, cfg, flat)
+    return flat, {"data": loss[0]}
+
+
+def material_stage_grads(rc, rays, randoms, gt_rgb, noise, train_frac: float, lossmult=None, flat=None,
+                         data_cfg: MaterialDataLossConfig = MaterialDataLossConfig(),
+                         smooth_cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig()):
+    """Every loss of the material stage that reaches params/MaterialShader, accumulated into one flat buffer: the data
+    loss (material_data_grads) and material_smoothness_grads (material_smoothness, regularizer/material_grid,
+    material_ray_sampler).  -> (flat, losses) keyed like losses_flat."""
+    flat, losses = material_data_grads(rc, rays, randoms, gt_rgb, lossmult, flat, data_cfg)
+    flat, more = material_smoothness_grads(rc, rays, randoms, noise, train_frac, lossmult, flat, smooth_cfg)
+    losses.update(more)
+    return flat, losses
+
+
+def material_stage_step(rc, opt: MaterialOptimizer, rays, randoms, gt_rgb, noise, lossmult=None, group=None,
+                        data_cfg: MaterialDataLossConfig = MaterialDataLossConfig(),
+                        smooth_cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig()):
+    """One train step of the material network on the stage's losses: train_frac from opt.count, material_stage_grads into
+    the optimizer's zeroed gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().
+    -> the losses dict of material_stage_grads."""
+    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
+    flat, losses = material_stage_grads(rc, rays, randoms, gt_rgb, noise, tf, lossmult, opt.grads["material"], data_cfg,
+                                        smooth_cfg)
     allreduce_grads([flat], group=group)
     opt.step({"material": flat})
     return losses
