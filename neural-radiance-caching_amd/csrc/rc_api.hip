@@ -82,7 +82,8 @@ struct TrainWs { WsBuf feat, dfeat, a1, a2, d1, d2, fe, graw, density, partial; 
 struct InterlevelWs { WsBuf d_density[RC_MAX_LEVELS], points[RC_MAX_LEVELS]; WsBuf loss_ray; };
 // rc_data_backward, beside its RenderWs (the training forward): the ray rgb, per-ray loss sums, per-sample d loss / d
 // density and d loss / d rgb_s, the means as points [n S][3]; then one sample chunk of the shader backward
-// (rc_data_host.inc: recompute activations, their gradients, the weight-gradient K-slices and a column of ones).
+// (rc_data_host.inc; rc_train_host.inc's dense-layer helpers: recompute activations, their gradients, the weight-gradient
+// K-slices and a column of ones).
 struct DataWs {
   WsBuf rgb, loss_ray, d_density, d_rgbs, points;
   WsBuf f96, heads, p3, ib_in, x328, s0, s1, sb, i1, i2, io, so;

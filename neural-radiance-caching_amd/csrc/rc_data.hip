@@ -36,8 +36,6 @@ namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 // d clip(y, lo, hi) / d y under jnp.clip = minimum(maximum(y, lo), hi) with the balanced tie rule
 __device__ __forceinline__ float clip_grad(float y, float lo, float hi) {
   const float a = y > lo ? 1.0f : (y == lo ? 0.5f : 0.0f);

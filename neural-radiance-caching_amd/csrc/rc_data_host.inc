@@ -1,52 +1,12 @@
-// Host side of rc_data_backward (rc_data.hip); included by rc_api.hip after rc_interlevel_host.inc.
+// Host side of rc_data_backward (rc_data.hip); included by rc_api.hip.
 //
 // One call = the training forward (enqueue_all's launch-per-stage cache pass on the workspace set WS_DATA, the caller's
 // jitter and anneal) -> k_data_loss_bwd (per-ray charb sums, d loss / d density and d loss / d rgb_s of every last-level sample) ->
 // k_interlevel_reduce (the loss, fixed order) -> with a gradient buffer, per chunk of kDataChunk samples: the shader
-// recompute and backward as dense layers on k_gemm, their weight gradients (K = the chunk's samples, fixed slices),
+// recompute and backward as dense layers on k_gemm (rc_train_host.inc), their weight gradients (K = the chunk's samples),
 // d feature64 += W_n^T d pred_raw, rc_density_backward of the last level and rc_hashgrid_backward of the appearance grid.
 
 namespace {
-
-constexpr int64_t kDataChunk = 32768;      // samples per chunk of the shader backward (bounds its workspace)
-constexpr int64_t kDataKSlice = 1024;      // samples per K slice of a weight gradient
-
-// The dense layers of the shader layout (pred_normals_layer first, the appearance tables between it and the rest).
-enum { DL_PRED, DL_BOTT, DL_ROUGH, DL_AMB, DL_TINT, DL_IRR, DL_I0, DL_I1, DL_IO, DL_S0, DL_S1, DL_S2, DL_SB, DL_SO, DL_COUNT };
-struct DataLayer { const char* name; int in, out; };
-constexpr DataLayer kDataLayers[DL_COUNT] = {
-    {"pred_normals_layer", 64, 3},           {"bottleneck_layer", 96, 128},     {"roughness_layer", 96, 1},
-    {"ambient_irradiance_layer", 96, 3},     {"tint_layer", 96, 3},             {"irradiance_layer", 96, 3},
-    {"integrated_brdf_layers_0", 129, 64},   {"integrated_brdf_layers_1", 64, 64}, {"output_integrated_brdf_layer", 64, 1},
-    {"SurfaceLightField/layer_0", 200, 128}, {"SurfaceLightField/layer_1", 128, 128}, {"SurfaceLightField/layer_2", 128, 128},
-    {"SurfaceLightField/layer_bottleneck", 328, 128}, {"SurfaceLightField/output_ambient_rgb_layer", 128, 3}};
-
-std::string data_layer_path(rc_handle* h, int i) {
-  return i == DL_PRED ? "params/Cache/Sampler/MLP_" + std::to_string(h->cfg.num_levels - 1) + "/pred_normals_layer"
-                      : std::string("params/Cache/Shader/") + kDataLayers[i].name;
-}
-
-// Segments of the shader gradient buffer; kernel_seg[i] = index of layer i's kernel segment (its bias follows).
-std::vector<GradSeg> shader_grad_segments(rc_handle* h, int* kernel_seg = nullptr, int64_t* app_off = nullptr) {
-  std::vector<GradSeg> v;
-  int64_t off = 0;
-  for (int i = 0; i < DL_COUNT; ++i) {
-    if (i == DL_BOTT) {
-      if (app_off) *app_off = off;
-      for (const GradSeg& g : grid_grad_segments(h->grids[3], off)) v.push_back(g);
-    }
-    if (kernel_seg) kernel_seg[i] = (int)v.size();
-    dense_grad_segments(v, off, data_layer_path(h, i), kDataLayers[i].in, kDataLayers[i].out);
-  }
-  return v;
-}
-
-// data_w: every layer's kernel [in, out] then bias, in layer order; offsets into it
-int64_t data_w_offset(int i) {
-  int64_t o = 0;
-  for (int k = 0; k < i; ++k) o += (int64_t)kDataLayers[k].in * kDataLayers[k].out + kDataLayers[k].out;
-  return o;
-}
 
 int upload_data_weights(rc_handle* h) {
   std::string missing;
@@ -64,23 +24,6 @@ int upload_data_weights(rc_handle* h) {
 }
 
 }  // namespace
-
-int64_t rc_shader_grad_size(rc_handle* h) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_shader_grad_size: not available on a time-resolved cache handle");
-  return grad_size(shader_grad_segments(h));
-  RC_CATCH(h)
-}
-
-int rc_shader_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (!count) return fail(h, RC_ERR_INVALID_ARG, "rc_shader_grad_layout: null count");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_shader_grad_layout: not available on a time-resolved cache handle");
-  return copy_segments(h, shader_grad_segments(h), segs, capacity, count, "rc_shader_grad_layout");
-  RC_CATCH(h)
-}
 
 int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, const float* lossmult, int64_t n,
                      const rc_randoms* rnd, float anneal, float charb_padding, float mult, float* density_grads,
@@ -158,44 +101,15 @@ int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, con
   int kseg[DL_COUNT];
   int64_t app_off = 0;
   const std::vector<GradSeg> segs = shader_grad_segments(h, kseg, &app_off);
-  const float* W = h->data_w.p;
-  auto Wk = [&](int l) { return W + data_w_offset(l); };
-  auto Wb = [&](int l) { return W + data_w_offset(l) + (int64_t)kDataLayers[l].in * kDataLayers[l].out; };
+  Dense L[DL_COUNT];                     // h->data_w: every layer's kernel then bias, in layer order
+  for (int64_t l = 0, at = 0; l < DL_COUNT; ++l) {
+    const int in = kDataLayers[l].in, out = kDataLayers[l].out;
+    L[l] = Dense{in, out, h->data_w.p + at, h->data_w.p + at + in * out};
+    at += in * out + out;
+  }
 
   for (int64_t c0 = 0; c0 < np; c0 += CH) {
     const int64_t C = np - c0 < CH ? np - c0 : CH;
-    // Y[:, j0 ..] = X W (+ b); X [C][in] row stride ldx, Y row stride ldy
-    auto fwd = [&](int l, const float* X, int64_t ldx, float* Y, int64_t ldy, bool relu) {
-      RcGemmArgs g{};
-      g.M = (int)C; g.N = kDataLayers[l].out; g.K = kDataLayers[l].in;
-      g.a = X; g.sai = ldx; g.sak = 1; g.b = Wk(l); g.sbk = kDataLayers[l].out; g.sbj = 1;
-      g.c = Y; g.sci = ldy; g.scj = 1; g.bias = Wb(l); g.relu = relu ? 1 : 0; g.kslice = g.K;
-      rc_launch_gemm(g, 1, st);
-    };
-    // dX[:, cols j0 .. j0 + nj) (+)= dY W^T, zero where mask <= 0 (the forward's ReLU output)
-    auto bwd = [&](int l, const float* dY, int64_t ldy, float* dX, int64_t ldx, int j0, int nj, const float* mask, int64_t ldm,
-                   bool accumulate) {
-      RcGemmArgs g{};
-      g.M = (int)C; g.N = nj; g.K = kDataLayers[l].out;
-      g.a = dY; g.sai = ldy; g.sak = 1; g.b = Wk(l) + (int64_t)j0 * kDataLayers[l].out; g.sbk = 1; g.sbj = kDataLayers[l].out;
-      g.c = dX + j0; g.sci = ldx; g.scj = 1; g.mask = mask ? mask + j0 : nullptr; g.smi = ldm; g.smj = 1;
-      g.accumulate = accumulate ? 1 : 0; g.kslice = g.K;
-      rc_launch_gemm(g, 1, st);
-    };
-    // grads[kernel] += X^T dY, grads[bias] += column sums of dY: K = the chunk's samples in fixed slices
-    auto wgrad = [&](int l, const float* X, int64_t ldx, const float* dY, int64_t ldy) {
-      const int in = kDataLayers[l].in, out = kDataLayers[l].out;
-      const int64_t Z = (C + kDataKSlice - 1) / kDataKSlice;
-      for (int pass = 0; pass < 2; ++pass) {
-        RcGemmArgs g{};
-        g.M = pass == 0 ? in : 1; g.N = out; g.K = C;
-        g.a = pass == 0 ? X : x.ones.p; g.sai = pass == 0 ? 1 : 0; g.sak = pass == 0 ? ldx : 0;
-        g.b = dY; g.sbk = ldy; g.sbj = 1; g.c = x.part.p; g.sci = out; g.scj = 1;
-        g.kslice = kDataKSlice; g.spart = (int64_t)g.M * out;
-        rc_launch_gemm(g, (int)Z, st);
-        rc_launch_sum_parts(x.part.p, (int)Z, g.spart, shader_grads + segs[kseg[l] + pass].offset, st);
-      }
-    };
     RcShaderBwdArgs sa{};
     sa.C = C; sa.c0 = c0; sa.np = np; sa.S = S2;
     sa.hbuf = w.hbuf.p; sa.app = w.app.p; sa.viewdirs = rays->viewdirs;
@@ -208,43 +122,46 @@ int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, con
 
     // recompute: feature96, heads, pred_raw, bottleneck, IDE, integrated BRDF, SLF
     rc_launch_shader_stage(sa, 0, st);
-    fwd(DL_ROUGH, x.f96.p, 96, x.heads.p + 0, 10, false);
-    fwd(DL_AMB, x.f96.p, 96, x.heads.p + 1, 10, false);
-    fwd(DL_TINT, x.f96.p, 96, x.heads.p + 4, 10, false);
-    fwd(DL_IRR, x.f96.p, 96, x.heads.p + 7, 10, false);
-    fwd(DL_PRED, x.f96.p, 96, x.p3.p, 3, false);
-    fwd(DL_BOTT, x.f96.p, 96, x.x328.p + 128, 328, false);
-    fwd(DL_BOTT, x.f96.p, 96, x.ib_in.p, 129, false);
+    dense_fwd(L[DL_ROUGH], C, x.f96.p, 96, x.heads.p + 0, 10, false, st);
+    dense_fwd(L[DL_AMB], C, x.f96.p, 96, x.heads.p + 1, 10, false, st);
+    dense_fwd(L[DL_TINT], C, x.f96.p, 96, x.heads.p + 4, 10, false, st);
+    dense_fwd(L[DL_IRR], C, x.f96.p, 96, x.heads.p + 7, 10, false, st);
+    dense_fwd(L[DL_PRED], C, x.f96.p, 96, x.p3.p, 3, false, st);
+    dense_fwd(L[DL_BOTT], C, x.f96.p, 96, x.x328.p + 128, 328, false, st);
+    dense_fwd(L[DL_BOTT], C, x.f96.p, 96, x.ib_in.p, 129, false, st);
     rc_launch_shader_stage(sa, 1, st);
-    fwd(DL_I0, x.ib_in.p, 129, x.i1.p, 64, true);
-    fwd(DL_I1, x.i1.p, 64, x.i2.p, 64, true);
-    fwd(DL_IO, x.i2.p, 64, x.io.p, 1, false);
-    fwd(DL_S0, x.x328.p + 128, 328, x.s0.p, 128, true);
-    fwd(DL_S1, x.s0.p, 128, x.s1.p, 128, true);
-    fwd(DL_S2, x.s1.p, 128, x.x328.p, 328, true);
-    fwd(DL_SB, x.x328.p, 328, x.sb.p, 128, true);
-    fwd(DL_SO, x.sb.p, 128, x.so.p, 3, false);
+    dense_fwd(L[DL_I0], C, x.ib_in.p, 129, x.i1.p, 64, true, st);
+    dense_fwd(L[DL_I1], C, x.i1.p, 64, x.i2.p, 64, true, st);
+    dense_fwd(L[DL_IO], C, x.i2.p, 64, x.io.p, 1, false, st);
+    dense_fwd(L[DL_S0], C, x.x328.p + 128, 328, x.s0.p, 128, true, st);
+    dense_fwd(L[DL_S1], C, x.s0.p, 128, x.s1.p, 128, true, st);
+    dense_fwd(L[DL_S2], C, x.s1.p, 128, x.x328.p, 328, true, st);
+    dense_fwd(L[DL_SB], C, x.x328.p, 328, x.sb.p, 128, true, st);
+    dense_fwd(L[DL_SO], C, x.sb.p, 128, x.so.p, 3, false, st);
     // backward
     rc_launch_shader_stage(sa, 2, st);
-    bwd(DL_SO, x.dso.p, 3, x.dsb.p, 128, 0, 128, x.sb.p, 128, false);
-    bwd(DL_SB, x.dsb.p, 128, x.dx328.p, 328, 0, 128, x.x328.p, 328, false);
-    bwd(DL_SB, x.dsb.p, 128, x.dx328.p, 328, 128, 200, nullptr, 0, false);
-    bwd(DL_S2, x.dx328.p, 328, x.ds1.p, 128, 0, 128, x.s1.p, 128, false);
-    bwd(DL_S1, x.ds1.p, 128, x.ds0.p, 128, 0, 128, x.s0.p, 128, false);
-    bwd(DL_S0, x.ds0.p, 128, x.dx328.p + 128, 328, 0, 200, nullptr, 0, true);
-    bwd(DL_IO, x.dio.p, 1, x.di2.p, 64, 0, 64, x.i2.p, 64, false);
-    bwd(DL_I1, x.di2.p, 64, x.di1.p, 64, 0, 64, x.i1.p, 64, false);
-    bwd(DL_I0, x.di1.p, 64, x.dib_in.p, 129, 0, 129, nullptr, 0, false);
+    dense_dx(L[DL_SO], C, x.dso.p, 3, x.dsb.p, 128, 0, 128, x.sb.p, false, st);
+    dense_dx(L[DL_SB], C, x.dsb.p, 128, x.dx328.p, 328, 0, 128, x.x328.p, false, st);
+    dense_dx(L[DL_SB], C, x.dsb.p, 128, x.dx328.p, 328, 128, 200, nullptr, false, st);
+    dense_dx(L[DL_S2], C, x.dx328.p, 328, x.ds1.p, 128, 0, 128, x.s1.p, false, st);
+    dense_dx(L[DL_S1], C, x.ds1.p, 128, x.ds0.p, 128, 0, 128, x.s0.p, false, st);
+    dense_dx(L[DL_S0], C, x.ds0.p, 128, x.dx328.p + 128, 328, 0, 200, nullptr, true, st);
+    dense_dx(L[DL_IO], C, x.dio.p, 1, x.di2.p, 64, 0, 64, x.i2.p, false, st);
+    dense_dx(L[DL_I1], C, x.di2.p, 64, x.di1.p, 64, 0, 64, x.i1.p, false, st);
+    dense_dx(L[DL_I0], C, x.di1.p, 64, x.dib_in.p, 129, 0, 129, nullptr, false, st);
     rc_launch_shader_stage(sa, 3, st);
-    bwd(DL_BOTT, x.db128.p, 128, x.df96.p, 96, 0, 96, nullptr, 0, false);
-    bwd(DL_ROUGH, x.dheads.p + 0, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
-    bwd(DL_AMB, x.dheads.p + 1, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
-    bwd(DL_TINT, x.dheads.p + 4, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
-    bwd(DL_IRR, x.dheads.p + 7, 10, x.df96.p, 96, 0, 96, nullptr, 0, true);
-    bwd(DL_PRED, x.dp3.p, 3, x.df96.p, 96, 0, 64, nullptr, 0, true);
+    dense_dx(L[DL_BOTT], C, x.db128.p, 128, x.df96.p, 96, 0, 96, nullptr, false, st);
+    dense_dx(L[DL_ROUGH], C, x.dheads.p + 0, 10, x.df96.p, 96, 0, 96, nullptr, true, st);
+    dense_dx(L[DL_AMB], C, x.dheads.p + 1, 10, x.df96.p, 96, 0, 96, nullptr, true, st);
+    dense_dx(L[DL_TINT], C, x.dheads.p + 4, 10, x.df96.p, 96, 0, 96, nullptr, true, st);
+    dense_dx(L[DL_IRR], C, x.dheads.p + 7, 10, x.df96.p, 96, 0, 96, nullptr, true, st);
+    dense_dx(L[DL_PRED], C, x.dp3.p, 3, x.df96.p, 96, 0, 64, nullptr, true, st);
     rc_launch_split_feature(x.df96.p, C, x.dfeat.p, x.dapp.p, st);
     RC_HIP(h, hipGetLastError());
     if (shader_grads) {
+      auto wgrad = [&](int l, const float* X, int64_t ldx, const float* dY, int64_t ldy) {
+        dense_wgrad(L[l], C, X, ldx, dY, ldy, x.ones.p, x.part.p, shader_grads, &segs[kseg[l]], st);
+      };
       wgrad(DL_PRED, x.f96.p, 96, x.dp3.p, 3);
       wgrad(DL_BOTT, x.f96.p, 96, x.db128.p, 128);
       wgrad(DL_ROUGH, x.f96.p, 96, x.dheads.p + 0, 10);

@@ -1,5 +1,6 @@
 // Device pieces shared by the loss backwards (rc_interlevel.hip, rc_data.hip, rc_geometry.hip, rc_light.hip): the reverse wave scan
-// of compute_alpha_weights, ref_utils.l2_normalize's override_gradient and the column order of k_density_mlp's hbuf.
+// of compute_alpha_weights, ref_utils.l2_normalize's override_gradient, the column order of k_density_mlp's hbuf and a few
+// scalar helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,13 @@
 
 namespace rcdev {
 
+__device__ __forceinline__ float readlane_f(float v, int l) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
+// nan_to_num: NaN -> 0, +-inf -> +-FLT_MAX
+__device__ __forceinline__ float fix_nan(float v) { return v != v ? 0.0f : fminf(fmaxf(v, -RC_FMAX), RC_FMAX); }
 __device__ __forceinline__ float shfl_f(float v, int src) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
 }

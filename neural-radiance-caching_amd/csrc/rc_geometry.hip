@@ -30,10 +30,6 @@ using namespace rcdev;
 
 namespace {
 
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ float fix_nan(float v) { return v != v ? 0.0f : fminf(fmaxf(v, -RC_FMAX), RC_FMAX); }
 __device__ __forceinline__ float sgn_ge(float x) { return x >= 0.0f ? 1.0f : -1.0f; }     // lax.abs' JVP factor
 
 __global__ void __launch_bounds__(256) k_geometry_loss_bwd(RcGeometryLossArgs a) {

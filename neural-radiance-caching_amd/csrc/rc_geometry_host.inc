@@ -1,5 +1,4 @@
-// Host side of rc_geometry_backward and rc_density_regularizer (rc_geometry.hip); included by rc_api.hip after
-// rc_data_host.inc.
+// Host side of rc_geometry_backward and rc_density_regularizer (rc_geometry.hip); included by rc_api.hip.
 //
 // One rc_geometry_backward call = the training forward (enqueue_all's sampler levels with the last level's hidden vector,
 // predicted and analytic normals, on the workspace set WS_GEOMETRY, the caller's jitter and anneal; no shader) ->
@@ -107,31 +106,14 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
   rc_launch_points_aos(w.means[NL - 1].p, np, x.points.p, st);
   int kseg[DL_COUNT];
   const std::vector<GradSeg> segs = shader_grad_segments(h, kseg);
-  const float* Wn = h->geom_w.p;
+  const Dense Wn{64, 3, h->geom_w.p, nullptr};
   for (int64_t c0 = 0; c0 < np; c0 += CH) {
     const int64_t C = np - c0 < CH ? np - c0 : CH;
     const float* dp = x.d_pred.p + 3 * c0;
     rc_launch_stage_hidden(w.hbuf.p, c0, C, x.h64.p, st);
-    if (shader_grads) {
-      // grads[kernel] += h64^T d pred_raw, grads[bias] += column sums of d pred_raw, in fixed K slices
-      const int64_t Z = (C + kDataKSlice - 1) / kDataKSlice;
-      for (int pass = 0; pass < 2; ++pass) {
-        RcGemmArgs g{};
-        g.M = pass == 0 ? 64 : 1; g.N = 3; g.K = C;
-        g.a = pass == 0 ? x.h64.p : x.ones.p; g.sai = pass == 0 ? 1 : 0; g.sak = pass == 0 ? 64 : 0;
-        g.b = dp; g.sbk = 3; g.sbj = 1; g.c = x.part.p; g.sci = 3; g.scj = 1;
-        g.kslice = kDataKSlice; g.spart = (int64_t)g.M * 3;
-        rc_launch_gemm(g, (int)Z, st);
-        rc_launch_sum_parts(x.part.p, (int)Z, g.spart, shader_grads + segs[kseg[DL_PRED] + pass].offset, st);
-      }
-    }
+    if (shader_grads) dense_wgrad(Wn, C, x.h64.p, 64, dp, 3, x.ones.p, x.part.p, shader_grads, &segs[kseg[DL_PRED]], st);
     if (density_grads) {
-      // d feature64 = d pred_raw W_n^T
-      RcGemmArgs g{};
-      g.M = (int)C; g.N = 64; g.K = 3;
-      g.a = dp; g.sai = 3; g.sak = 1; g.b = Wn; g.sbk = 1; g.sbj = 3;
-      g.c = x.dfeat.p; g.sci = 64; g.scj = 1; g.kslice = g.K;
-      rc_launch_gemm(g, 1, st);
+      dense_dx(Wn, C, dp, 3, x.dfeat.p, 64, 0, 64, nullptr, false, st);     // d feature64 = d pred_raw W_n^T
       RC_HIP(h, hipGetLastError());
       if ((rc = rc_density_backward(h, NL - 1, x.points.p + 3 * c0, C, x.d_density.p + c0, x.dfeat.p, density_grads, nullptr, stream_v)))
         return rc;
@@ -146,35 +128,6 @@ int rc_density_regularizer(rc_handle* h, int32_t level, float mult, float* densi
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
   if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, "rc_density_regularizer: bad level");
-  if (!std::isfinite(mult)) return fail(h, RC_ERR_INVALID_ARG, "rc_density_regularizer: mult must be finite");
-  if (!loss) return fail(h, RC_ERR_INVALID_ARG, "rc_density_regularizer: null loss");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_density_regularizer: not available on a time-resolved cache handle");
-  const GridState& gs = h->grids[level];
-  const int T = (int)gs.sizes.size();
-  if (T < 1 || T > RC_MAX_GRID_LEVELS) return fail(h, RC_ERR_UNSUPPORTED, "rc_density_regularizer: unexpected grid levels");
-  for (int t = 0; t < T; ++t)
-    if (!gs.loaded[t]) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: " + gs.prefix + "/" + level_name(gs.cfg, gs.sizes, gs.sizes[t]));
-  RC_HIP(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream_v;
-  WsUse use(h, WS_GEOMETRY, st);
-  int rc;
-  if ((rc = use.rc)) return rc;
-  GeometryWs& x = ws_extra<GeometryWs>(use.s);
-  const int B = rc_grid_l2_blocks();
-  if ((rc = ws_alloc(h, x.reg_part, 2 * (int64_t)T * B))) return rc;     // doubles
-  double* part = reinterpret_cast<double*>(x.reg_part.p);
-  int64_t off = 0;
-  const std::vector<GradSeg> segs = grid_grad_segments(gs, off);     // the tables lead the level's density layout
-  RcGridL2Reduce rr{};
-  rr.mult = mult; rr.tables = T;
-  for (int t = 0; t < T; ++t) {
-    const int64_t count = segs[t].size;
-    rr.count[t] = count;
-    rc_launch_grid_l2_bwd(gs.dev.lvl[t].table, count, (float)((double)mult / (double)count),
-                          density_grads ? density_grads + segs[t].offset : nullptr, part + (int64_t)t * B, st);
-  }
-  rc_launch_grid_l2_reduce(part, rr, loss, st);
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
+  return grid_l2_regularizer<GeometryWs>(h, level, WS_GEOMETRY, mult, density_grads, loss, stream_v, "rc_density_regularizer");
   RC_CATCH(h)
 }

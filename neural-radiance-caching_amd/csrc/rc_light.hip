@@ -29,21 +29,15 @@ namespace {
 
 constexpr float kPi = 3.14159265358979323846f;
 
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
 // the wave's sum, lane 0's order, on every lane
 __device__ __forceinline__ float wave_total(float v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
   return readlane_f(v, 0);
 }
-__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 // d max(x, c) / d x and d min(x, c) / d x with the balanced tie rule
 __device__ __forceinline__ float max_grad(float x, float c) { return x > c ? 1.0f : (x == c ? 0.5f : 0.0f); }
 __device__ __forceinline__ float min_grad(float x, float c) { return x < c ? 1.0f : (x == c ? 0.5f : 0.0f); }
-__device__ __forceinline__ float fix_nan(float v) { return v != v ? 0.0f : fminf(fmaxf(v, -RC_FMAX), RC_FMAX); }
 
 // image.linear_to_srgb (internal/image.py:192-200) and its derivative
 __device__ __forceinline__ float srgb(float x) {

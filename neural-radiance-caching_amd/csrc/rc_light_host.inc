@@ -1,45 +1,10 @@
-// Host side of rc_light_sampling_backward and rc_light_regularizer (rc_light.hip) and the light layout; included by
-// rc_api.hip after rc_geometry_host.inc (rc_optim_host.inc's rc_load_params_flat reads light_grad_segments).
+// Host side of rc_light_sampling_backward and rc_light_regularizer (rc_light.hip); included by rc_api.hip.
 //
 // One rc_light_sampling_backward call = rc_render_material's forward up to the batched secondary trace (material_* in
 // rc_api.hip, on set 0 and WS_SECONDARY) -> the light head's recompute on k_gemm (h0, h1, vmf_params; "ls:" buffers) ->
 // k_light_sampling_loss_bwd (per-point loss sums, d loss / d vmf_params) -> k_interlevel_reduce (the loss, fixed order) ->
 // with a gradient buffer: the three dense layers' backward on k_gemm (input gradients masked by ReLU', weight gradients
 // over fixed K slices of points, added up by k_sum_parts in slice order) and rc_hashgrid_backward of the light grid.
-
-namespace {
-
-constexpr int kLightGrid = 5;                  // the handle's grid id of params/LightSampler/light_grid
-constexpr int kLightWidth = 32;                // the light head's input: the light grid's features (RcLightHeadArgs)
-
-// params/LightSampler: light_grid tables in level order, then layers_0, layers_1, output_layer (kernel, bias each)
-std::vector<GradSeg> light_grad_segments(rc_handle* h) {
-  const GridState& gs = h->grids[kLightGrid];
-  int64_t off = 0;
-  std::vector<GradSeg> v = grid_grad_segments(gs, off);
-  dense_grad_segments(v, off, "params/LightSampler/layers_0", (int)gs.sizes.size() * gs.cfg.num_features, 64);
-  dense_grad_segments(v, off, "params/LightSampler/layers_1", 64, 64);
-  dense_grad_segments(v, off, "params/LightSampler/output_layer", 64, 5 * h->cfg.num_vmf);
-  return v;
-}
-
-}  // namespace
-
-int64_t rc_light_grad_size(rc_handle* h) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (h->grids[kLightGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, "rc_light_grad_size: no light grid");
-  return grad_size(light_grad_segments(h));
-  RC_CATCH(h)
-}
-
-int rc_light_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (h->grids[kLightGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, "rc_light_grad_layout: no light grid");
-  return copy_segments(h, light_grad_segments(h), segs, capacity, count, "rc_light_grad_layout");
-  RC_CATCH(h)
-}
 
 int rc_light_sampling_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
                                const rc_material_randoms* mr, int32_t K, const rc_light_sampling_loss* cfg,
@@ -100,18 +65,12 @@ int rc_light_sampling_backward(rc_handle* h, const rc_rays* rays, const float* l
   // 2. the light head's recompute: h0 = relu(feat W0 + b0), h1 = relu(h0 W1 + b1), vp = h1 W2 + b2 (row-major per point)
   roctx_stage("light sampling: loss");
   const auto& raw = h->packs.raw;
-  const float* Wl[3] = {raw[RAW_LIGHT_0].kernel.p, raw[RAW_LIGHT_1].kernel.p, raw[RAW_LIGHT_OUT].kernel.p};
-  const float* bl[3] = {raw[RAW_LIGHT_0].bias.p, raw[RAW_LIGHT_1].bias.p, raw[RAW_LIGHT_OUT].bias.p};
-  const int din[3] = {kLightWidth, 64, 64}, dout[3] = {64, 64, 640};
+  const Dense L[3] = {{kLightWidth, 64, raw[RAW_LIGHT_0].kernel.p, raw[RAW_LIGHT_0].bias.p},
+                      {64, 64, raw[RAW_LIGHT_1].kernel.p, raw[RAW_LIGHT_1].bias.p},
+                      {64, 640, raw[RAW_LIGHT_OUT].kernel.p, raw[RAW_LIGHT_OUT].bias.p}};
   const float* xin[3] = {x.l_feat.p, y.h0.p, y.h1.p};
   float* yout[3] = {y.h0.p, y.h1.p, y.vp.p};
-  for (int l = 0; l < 3; ++l) {
-    RcGemmArgs g{};
-    g.M = (int)n; g.N = dout[l]; g.K = din[l];
-    g.a = xin[l]; g.sai = din[l]; g.sak = 1; g.b = Wl[l]; g.sbk = dout[l]; g.sbj = 1;
-    g.c = yout[l]; g.sci = dout[l]; g.scj = 1; g.bias = bl[l]; g.relu = l < 2; g.kslice = g.K;
-    rc_launch_gemm(g, 1, st);
-  }
+  for (int l = 0; l < 3; ++l) dense_fwd(L[l], n, xin[l], L[l].in, yout[l], L[l].out, l < 2, st);
   // 3. the loss and d loss / d vmf_params
   RcLightLossArgs la{};
   la.n = n; la.Ks = sp.Ks; la.Kd = sp.Kd;
@@ -137,22 +96,8 @@ int rc_light_sampling_backward(rc_handle* h, const rc_rays* rays, const float* l
   float* dxl[3] = {y.dfeat.p, y.dh0.p, y.dh1.p};
   const float* hmask[3] = {nullptr, y.h0.p, y.h1.p};           // ReLU' of the layer's input
   for (int l = 2; l >= 0; --l) {
-    for (int pass = 0; pass < 2; ++pass) {
-      RcGemmArgs g{};
-      g.M = pass == 0 ? din[l] : 1; g.N = dout[l]; g.K = n;
-      g.a = pass == 0 ? xin[l] : y.ones.p; g.sai = pass == 0 ? 1 : 0; g.sak = pass == 0 ? din[l] : 0;
-      g.b = dyl[l]; g.sbk = dout[l]; g.sbj = 1; g.c = y.part.p; g.sci = dout[l]; g.scj = 1;
-      g.kslice = kDataKSlice; g.spart = (int64_t)g.M * dout[l];
-      rc_launch_gemm(g, (int)Z, st);
-      rc_launch_sum_parts(y.part.p, (int)Z, g.spart, light_grads + segs[T + 2 * l + pass].offset, st);
-    }
-    // d input = dY W^T (zero where the input's ReLU was off)
-    RcGemmArgs g{};
-    g.M = (int)n; g.N = din[l]; g.K = dout[l];
-    g.a = dyl[l]; g.sai = dout[l]; g.sak = 1; g.b = Wl[l]; g.sbk = 1; g.sbj = dout[l];
-    g.c = dxl[l]; g.sci = din[l]; g.scj = 1; g.kslice = g.K;
-    g.mask = hmask[l]; g.smi = din[l]; g.smj = 1;
-    rc_launch_gemm(g, 1, st);
+    dense_wgrad(L[l], n, xin[l], L[l].in, dyl[l], L[l].out, y.ones.p, y.part.p, light_grads, &segs[T + 2 * l], st);
+    dense_dx(L[l], n, dyl[l], L[l].out, dxl[l], L[l].in, 0, L[l].in, hmask[l], false, st);     // zero where the input's ReLU was off
   }
   RC_HIP(h, hipGetLastError());
   // 5. the light grid's tables (contracted shading points), at the head of the layout
@@ -163,35 +108,6 @@ int rc_light_sampling_backward(rc_handle* h, const rc_rays* rays, const float* l
 int rc_light_regularizer(rc_handle* h, float mult, float* light_grads, float* loss, void* stream_v) {
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
-  if (!std::isfinite(mult)) return fail(h, RC_ERR_INVALID_ARG, "rc_light_regularizer: mult must be finite");
-  if (!loss) return fail(h, RC_ERR_INVALID_ARG, "rc_light_regularizer: null loss");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_light_regularizer: not available on a time-resolved cache handle");
-  const GridState& gs = h->grids[kLightGrid];
-  const int T = (int)gs.sizes.size();
-  if (T < 1 || T > RC_MAX_GRID_LEVELS) return fail(h, RC_ERR_UNSUPPORTED, "rc_light_regularizer: unexpected grid levels");
-  for (int t = 0; t < T; ++t)
-    if (!gs.loaded[t]) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: " + gs.prefix + "/" + level_name(gs.cfg, gs.sizes, gs.sizes[t]));
-  RC_HIP(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream_v;
-  WsUse use(h, WS_LIGHT, st);
-  int rc;
-  if ((rc = use.rc)) return rc;
-  LightWs& y = ws_extra<LightWs>(use.s);
-  const int B = rc_grid_l2_blocks();
-  if ((rc = ws_alloc(h, y.reg_part, 2 * (int64_t)T * B))) return rc;     // doubles
-  double* part = reinterpret_cast<double*>(y.reg_part.p);
-  int64_t off = 0;
-  const std::vector<GradSeg> segs = grid_grad_segments(gs, off);     // the tables lead the light layout
-  RcGridL2Reduce rr{};
-  rr.mult = mult; rr.tables = T;
-  for (int t = 0; t < T; ++t) {
-    const int64_t count = segs[t].size;
-    rr.count[t] = count;
-    rc_launch_grid_l2_bwd(gs.dev.lvl[t].table, count, (float)((double)mult / (double)count),
-                          light_grads ? light_grads + segs[t].offset : nullptr, part + (int64_t)t * B, st);
-  }
-  rc_launch_grid_l2_reduce(part, rr, loss, st);
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
+  return grid_l2_regularizer<LightWs>(h, kLightGrid, WS_LIGHT, mult, light_grads, loss, stream_v, "rc_light_regularizer");
   RC_CATCH(h)
 }

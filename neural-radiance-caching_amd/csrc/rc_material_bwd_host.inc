@@ -1,5 +1,4 @@
-// Host side of rc_material_smoothness_backward and rc_material_regularizer (rc_material_bwd.hip) and the material layout;
-// included by rc_api.hip after rc_light_host.inc (rc_optim_host.inc's rc_load_params_flat reads material_grad_segments).
+// Host side of rc_material_smoothness_backward and rc_material_regularizer (rc_material_bwd.hip); included by rc_api.hip.
 //
 // One rc_material_smoothness_backward call = rc_render_material's steps 1-2 (material_primary in rc_api.hip, on set 0) ->
 // k_material_smoothness_points (x, x' = x + noise_scale nu; "ms:pts") -> one material-grid lookup over the 2n points
@@ -7,41 +6,6 @@
 // m(x) into m_mat, the loss terms and per-workgroup loss sums, with a gradient buffer the head's backward, d loss /
 // d features and per-workgroup partials of the dense gradients) -> k_material_smoothness_reduce (the loss; the partials
 // in workgroup order) -> with a gradient buffer: rc_hashgrid_backward of the material grid at the 2n points.
-
-namespace {
-
-constexpr int kMaterialGrid = 4;               // the handle's grid id of params/MaterialShader/material_grid
-constexpr int kMaterialWidth = 32;             // the material head's input: the material grid's features (RcMatHeadArgs)
-
-// params/MaterialShader: material_grid tables in level order, then bottleneck_layer, pred_brdf_layer (kernel, bias each)
-std::vector<GradSeg> material_grad_segments(rc_handle* h) {
-  const GridState& gs = h->grids[kMaterialGrid];
-  int64_t off = 0;
-  std::vector<GradSeg> v = grid_grad_segments(gs, off);
-  const auto inv = dense_inventory(h->cfg, nullptr);
-  const auto& bott = inv.at("params/MaterialShader/bottleneck_layer");
-  dense_grad_segments(v, off, "params/MaterialShader/bottleneck_layer", bott.first, bott.second);
-  dense_grad_segments(v, off, "params/MaterialShader/pred_brdf_layer", bott.second, 10);
-  return v;
-}
-
-}  // namespace
-
-int64_t rc_material_grad_size(rc_handle* h) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (h->grids[kMaterialGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, "rc_material_grad_size: no material grid");
-  return grad_size(material_grad_segments(h));
-  RC_CATCH(h)
-}
-
-int rc_material_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (h->grids[kMaterialGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, "rc_material_grad_layout: no material grid");
-  return copy_segments(h, material_grad_segments(h), segs, capacity, count, "rc_material_grad_layout");
-  RC_CATCH(h)
-}
 
 int rc_material_smoothness_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
                                     const rc_material_randoms* mr, const float* noise, const rc_material_smoothness_loss* cfg,
@@ -129,35 +93,7 @@ int rc_material_smoothness_backward(rc_handle* h, const rc_rays* rays, const flo
 int rc_material_regularizer(rc_handle* h, float mult, float* material_grads, float* loss, void* stream_v) {
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
-  if (!std::isfinite(mult)) return fail(h, RC_ERR_INVALID_ARG, "rc_material_regularizer: mult must be finite");
-  if (!loss) return fail(h, RC_ERR_INVALID_ARG, "rc_material_regularizer: null loss");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_material_regularizer: not available on a time-resolved cache handle");
-  const GridState& gs = h->grids[kMaterialGrid];
-  const int T = (int)gs.sizes.size();
-  if (T < 1 || T > RC_MAX_GRID_LEVELS) return fail(h, RC_ERR_UNSUPPORTED, "rc_material_regularizer: unexpected grid levels");
-  for (int t = 0; t < T; ++t)
-    if (!gs.loaded[t]) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: " + gs.prefix + "/" + level_name(gs.cfg, gs.sizes, gs.sizes[t]));
-  RC_HIP(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream_v;
-  WsUse use(h, WS_MATERIAL, st);
-  int rc;
-  if ((rc = use.rc)) return rc;
-  MaterialWs& y = ws_extra<MaterialWs>(use.s);
-  const int B = rc_grid_l2_blocks();
-  if ((rc = ws_alloc(h, y.reg_part, 2 * (int64_t)T * B))) return rc;     // doubles
-  double* part = reinterpret_cast<double*>(y.reg_part.p);
-  int64_t off = 0;
-  const std::vector<GradSeg> segs = grid_grad_segments(gs, off);     // the tables lead the material layout
-  RcGridL2Reduce rr{};
-  rr.mult = mult; rr.tables = T;
-  for (int t = 0; t < T; ++t) {
-    const int64_t count = segs[t].size;
-    rr.count[t] = count;
-    rc_launch_grid_l2_bwd(gs.dev.lvl[t].table, count, (float)((double)mult / (double)count),
-                          material_grads ? material_grads + segs[t].offset : nullptr, part + (int64_t)t * B, st);
-  }
-  rc_launch_grid_l2_reduce(part, rr, loss, st);
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
+  return grid_l2_regularizer<MaterialWs>(h, kMaterialGrid, WS_MATERIAL, mult, material_grads, loss, stream_v,
+                                         "rc_material_regularizer");
   RC_CATCH(h)
 }

@@ -1,5 +1,4 @@
-// Host side of rc_material_data_backward (rc_material_data.hip); included by rc_api.hip after rc_material_bwd_host.inc
-// (material_grad_segments, kMaterialGrid, kMaterialWidth).
+// Host side of rc_material_data_backward (rc_material_data.hip); included by rc_api.hip.
 //
 // One call = rc_render_material itself (every step, kernels and launch order unchanged; its primary composite to
 // "md:cache_rgb" / "md:cache_acc", its "rgb" not written) -> k_material_data_bwd (the integration's recompute, the rebuilt

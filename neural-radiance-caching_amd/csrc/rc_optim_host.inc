@@ -1,4 +1,4 @@
-// Host side of rc_adam_update (rc_optim.hip) and rc_load_params_flat; included by rc_api.hip after rc_material_bwd_host.inc.
+// Host side of rc_adam_update (rc_optim.hip) and rc_load_params_flat; included by rc_api.hip.
 //
 // rc_adam_update: the call's buffers and their segments -> runs (consecutive segments of one group) and the tile table of
 // k_adam -> with the norm clip, k_adam_sumsq + k_adam_norm on the workspace set WS_OPTIM -> k_adam.  rc_load_params_flat:
@@ -91,14 +91,9 @@ int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void*
       (layout < 0 || layout >= h->cfg.num_levels))
     return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: layout must be a density level, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT "
                                        "or RC_LAYOUT_MATERIAL");
-  if (layout == RC_LAYOUT_LIGHT && h->grids[kLightGrid].sizes.empty())
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_load_params_flat: no light grid");
-  if (layout == RC_LAYOUT_MATERIAL && h->grids[kMaterialGrid].sizes.empty())
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_load_params_flat: no material grid");
-  const std::vector<GradSeg> segs = layout == RC_LAYOUT_SHADER     ? shader_grad_segments(h)
-                                    : layout == RC_LAYOUT_LIGHT    ? light_grad_segments(h)
-                                    : layout == RC_LAYOUT_MATERIAL ? material_grad_segments(h)
-                                                                   : density_grad_segments(h, layout);
+  int rc;
+  if ((rc = layout_check(h, layout, "rc_load_params_flat"))) return rc;
+  const std::vector<GradSeg> segs = layout_segments(h, layout);
   const auto inv = dense_inventory(h->cfg, nullptr);
   // classify: grid table (grid, level) or dense layer (checked against the inventory)
   struct Dst { int g = -1, l = -1; };
@@ -122,7 +117,6 @@ int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void*
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   WsUse use(h, WS_OPTIM, st);
-  int rc;
   if ((rc = use.rc)) return rc;
   OptimWs& x = ws_extra<OptimWs>(use.s);
   // 1. the tables, device to device on the caller's stream

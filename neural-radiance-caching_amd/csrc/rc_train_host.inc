@@ -1,5 +1,7 @@
-// Host side of the training backward of one level's density field (rc_train.hip); included by rc_api.hip.  Also the
-// gradient-buffer layouts (GradSeg, dense_grad_segments, copy_segments) that rc_data_host.inc builds on.
+// Host side of the training backward of one level's density field (rc_train.hip); included by rc_api.hip before the other
+// training files.  Also what those files share: the gradient-buffer layouts (GradSeg, one builder per layout,
+// layout_segments, behind every rc_*_grad_size / rc_*_grad_layout and rc_load_params_flat), the dense layers on k_gemm
+// (dense_fwd, dense_dx, dense_wgrad) and the body of the three grid-L2 regularizers.
 
 namespace {
 
@@ -49,6 +51,90 @@ std::vector<GradSeg> density_grad_segments(rc_handle* h, int level) {
   return v;
 }
 
+// The dense layers of the shader layout (pred_normals_layer first, the appearance tables between it and the rest).
+enum { DL_PRED, DL_BOTT, DL_ROUGH, DL_AMB, DL_TINT, DL_IRR, DL_I0, DL_I1, DL_IO, DL_S0, DL_S1, DL_S2, DL_SB, DL_SO, DL_COUNT };
+struct DataLayer { const char* name; int in, out; };
+constexpr DataLayer kDataLayers[DL_COUNT] = {
+    {"pred_normals_layer", 64, 3},           {"bottleneck_layer", 96, 128},     {"roughness_layer", 96, 1},
+    {"ambient_irradiance_layer", 96, 3},     {"tint_layer", 96, 3},             {"irradiance_layer", 96, 3},
+    {"integrated_brdf_layers_0", 129, 64},   {"integrated_brdf_layers_1", 64, 64}, {"output_integrated_brdf_layer", 64, 1},
+    {"SurfaceLightField/layer_0", 200, 128}, {"SurfaceLightField/layer_1", 128, 128}, {"SurfaceLightField/layer_2", 128, 128},
+    {"SurfaceLightField/layer_bottleneck", 328, 128}, {"SurfaceLightField/output_ambient_rgb_layer", 128, 3}};
+
+std::string data_layer_path(rc_handle* h, int i) {
+  return i == DL_PRED ? "params/Cache/Sampler/MLP_" + std::to_string(h->cfg.num_levels - 1) + "/pred_normals_layer"
+                      : std::string("params/Cache/Shader/") + kDataLayers[i].name;
+}
+
+// Segments of the shader gradient buffer; kernel_seg[i] = index of layer i's kernel segment (its bias follows).
+std::vector<GradSeg> shader_grad_segments(rc_handle* h, int* kernel_seg = nullptr, int64_t* app_off = nullptr) {
+  std::vector<GradSeg> v;
+  int64_t off = 0;
+  for (int i = 0; i < DL_COUNT; ++i) {
+    if (i == DL_BOTT) {
+      if (app_off) *app_off = off;
+      for (const GradSeg& g : grid_grad_segments(h->grids[3], off)) v.push_back(g);
+    }
+    if (kernel_seg) kernel_seg[i] = (int)v.size();
+    dense_grad_segments(v, off, data_layer_path(h, i), kDataLayers[i].in, kDataLayers[i].out);
+  }
+  return v;
+}
+
+constexpr int kLightGrid = 5;                  // the handle's grid id of params/LightSampler/light_grid
+constexpr int kLightWidth = 32;                // the light head's input: the light grid's features (RcLightHeadArgs)
+constexpr int kMaterialGrid = 4;               // the handle's grid id of params/MaterialShader/material_grid
+constexpr int kMaterialWidth = 32;             // the material head's input: the material grid's features (RcMatHeadArgs)
+
+// params/LightSampler: light_grid tables in level order, then layers_0, layers_1, output_layer (kernel, bias each)
+std::vector<GradSeg> light_grad_segments(rc_handle* h) {
+  const GridState& gs = h->grids[kLightGrid];
+  int64_t off = 0;
+  std::vector<GradSeg> v = grid_grad_segments(gs, off);
+  dense_grad_segments(v, off, "params/LightSampler/layers_0", (int)gs.sizes.size() * gs.cfg.num_features, 64);
+  dense_grad_segments(v, off, "params/LightSampler/layers_1", 64, 64);
+  dense_grad_segments(v, off, "params/LightSampler/output_layer", 64, 5 * h->cfg.num_vmf);
+  return v;
+}
+
+// params/MaterialShader: material_grid tables in level order, then bottleneck_layer, pred_brdf_layer (kernel, bias each)
+std::vector<GradSeg> material_grad_segments(rc_handle* h) {
+  const GridState& gs = h->grids[kMaterialGrid];
+  int64_t off = 0;
+  std::vector<GradSeg> v = grid_grad_segments(gs, off);
+  const auto inv = dense_inventory(h->cfg, nullptr);
+  const auto& bott = inv.at("params/MaterialShader/bottleneck_layer");
+  dense_grad_segments(v, off, "params/MaterialShader/bottleneck_layer", bott.first, bott.second);
+  dense_grad_segments(v, off, "params/MaterialShader/pred_brdf_layer", bott.second, 10);
+  return v;
+}
+
+// Layout ids of the ABI: a density level >= 0, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, RC_LAYOUT_MATERIAL.  `who`'s check that
+// the handle has the layout (a density export maps a negative level to kNoLayout, so that it names no other layout).
+constexpr int kNoLayout = INT32_MIN;
+int layout_check(rc_handle* h, int layout, const std::string& who) {
+  if (layout == RC_LAYOUT_SHADER) {
+    if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
+  } else if (layout == RC_LAYOUT_LIGHT) {
+    if (h->grids[kLightGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, who + ": no light grid");
+  } else if (layout == RC_LAYOUT_MATERIAL) {
+    if (h->grids[kMaterialGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, who + ": no material grid");
+  } else if (layout < 0 || layout >= h->cfg.num_levels) {
+    return fail(h, RC_ERR_INVALID_ARG, who + ": bad level");
+  }
+  return RC_OK;
+}
+
+// the segments of a layout that passed layout_check
+std::vector<GradSeg> layout_segments(rc_handle* h, int layout) {
+  switch (layout) {
+    case RC_LAYOUT_SHADER: return shader_grad_segments(h);
+    case RC_LAYOUT_LIGHT: return light_grad_segments(h);
+    case RC_LAYOUT_MATERIAL: return material_grad_segments(h);
+    default: return density_grad_segments(h, layout);
+  }
+}
+
 // rc_*_grad_layout: the segments into the caller's array
 int copy_segments(rc_handle* h, const std::vector<GradSeg>& v, rc_grad_segment* segs, int32_t capacity, int32_t* count, const char* who) {
   if (!count) return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": null count");
@@ -61,6 +147,107 @@ int copy_segments(rc_handle* h, const std::vector<GradSeg>& v, rc_grad_segment* 
     segs[i].offset = v[i].offset; segs[i].size = v[i].size; segs[i].ndim = v[i].ndim;
     for (int d = 0; d < 4; ++d) segs[i].shape[d] = v[i].shape[d];
   }
+  return RC_OK;
+}
+
+// The bodies of rc_*_grad_size and rc_*_grad_layout.
+int64_t layout_grad_size(rc_handle* h, int layout, const char* who) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  int rc;
+  if ((rc = layout_check(h, layout, who))) return rc;
+  return grad_size(layout_segments(h, layout));
+  RC_CATCH(h)
+}
+
+int layout_grad_layout(rc_handle* h, int layout, rc_grad_segment* segs, int32_t capacity, int32_t* count, const char* who) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  // rc_shader_grad_layout checks `count` before the handle's kind, the others after it (copy_segments)
+  if (layout == RC_LAYOUT_SHADER && !count) return fail(h, RC_ERR_INVALID_ARG, std::string(who) + ": null count");
+  int rc;
+  if ((rc = layout_check(h, layout, who))) return rc;
+  return copy_segments(h, layout_segments(h, layout), segs, capacity, count, who);
+  RC_CATCH(h)
+}
+
+// Dense layers on k_gemm, M rows (points or samples) each; X, Y, dX, dY row-major with row strides ld*.
+constexpr int64_t kDataChunk = 32768;      // samples per chunk of a shader backward (bounds its workspace)
+constexpr int64_t kDataKSlice = 1024;      // rows per K slice of a weight gradient
+
+struct Dense { int in, out; const float* w; const float* b; };    // kernel [in, out], bias [out]
+
+// Y = X W + b, ReLU'd when `relu`
+void dense_fwd(const Dense& L, int64_t M, const float* X, int64_t ldx, float* Y, int64_t ldy, bool relu, hipStream_t st) {
+  RcGemmArgs g{};
+  g.M = (int)M; g.N = L.out; g.K = L.in;
+  g.a = X; g.sai = ldx; g.sak = 1; g.b = L.w; g.sbk = L.out; g.sbj = 1;
+  g.c = Y; g.sci = ldy; g.scj = 1; g.bias = L.b; g.relu = relu ? 1 : 0; g.kslice = g.K;
+  rc_launch_gemm(g, 1, st);
+}
+
+// dX[:, j0 .. j0 + nj) (+)= dY W^T, zero where mask <= 0 (the forward's ReLU output, row stride ldx like dX)
+void dense_dx(const Dense& L, int64_t M, const float* dY, int64_t ldy, float* dX, int64_t ldx, int j0, int nj, const float* mask,
+              bool accumulate, hipStream_t st) {
+  RcGemmArgs g{};
+  g.M = (int)M; g.N = nj; g.K = L.out;
+  g.a = dY; g.sai = ldy; g.sak = 1; g.b = L.w + (int64_t)j0 * L.out; g.sbk = 1; g.sbj = L.out;
+  g.c = dX + j0; g.sci = ldx; g.scj = 1; g.mask = mask ? mask + j0 : nullptr; g.smi = ldx; g.smj = 1;
+  g.accumulate = accumulate ? 1 : 0; g.kslice = g.K;
+  rc_launch_gemm(g, 1, st);
+}
+
+// grads[kb[0]] += X^T dY, grads[kb[1]] += column sums of dY (kb: the layer's kernel segment, its bias segment after it):
+// K = the M rows in fixed slices of kDataKSlice, their partials in `part` added up by k_sum_parts in slice order; `ones`:
+// a 1.0f, the A operand of the bias pass
+void dense_wgrad(const Dense& L, int64_t M, const float* X, int64_t ldx, const float* dY, int64_t ldy, const float* ones,
+                 float* part, float* grads, const GradSeg* kb, hipStream_t st) {
+  const int64_t Z = (M + kDataKSlice - 1) / kDataKSlice;
+  for (int pass = 0; pass < 2; ++pass) {
+    RcGemmArgs g{};
+    g.M = pass == 0 ? L.in : 1; g.N = L.out; g.K = M;
+    g.a = pass == 0 ? X : ones; g.sai = pass == 0 ? 1 : 0; g.sak = pass == 0 ? ldx : 0;
+    g.b = dY; g.sbk = ldy; g.sbj = 1; g.c = part; g.sci = L.out; g.scj = 1;
+    g.kslice = kDataKSlice; g.spart = (int64_t)g.M * L.out;
+    rc_launch_gemm(g, (int)Z, st);
+    rc_launch_sum_parts(part, (int)Z, g.spart, grads + kb[pass].offset, st);
+  }
+}
+
+// rc_{density,light,material}_regularizer after the export's own checks: mult * sum over the tables of grid `grid` of
+// 0.5 * mean(x^2) into `loss`, and mult * x / numel added into the layout `grads` (whose head is the grid's tables), on
+// the workspace set `set` (X: its extra buffers, reg_part the per-table partial sums).
+template <class X>
+int grid_l2_regularizer(rc_handle* h, int grid, int set, float mult, float* grads, float* loss, void* stream_v, const std::string& who) {
+  if (!std::isfinite(mult)) return fail(h, RC_ERR_INVALID_ARG, who + ": mult must be finite");
+  if (!loss) return fail(h, RC_ERR_INVALID_ARG, who + ": null loss");
+  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
+  const GridState& gs = h->grids[grid];
+  const int T = (int)gs.sizes.size();
+  if (T < 1 || T > RC_MAX_GRID_LEVELS) return fail(h, RC_ERR_UNSUPPORTED, who + ": unexpected grid levels");
+  for (int t = 0; t < T; ++t)
+    if (!gs.loaded[t]) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: " + gs.prefix + "/" + level_name(gs.cfg, gs.sizes, gs.sizes[t]));
+  RC_HIP(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream_v;
+  WsUse use(h, set, st);
+  int rc;
+  if ((rc = use.rc)) return rc;
+  X& y = ws_extra<X>(use.s);
+  const int B = rc_grid_l2_blocks();
+  if ((rc = ws_alloc(h, y.reg_part, 2 * (int64_t)T * B))) return rc;     // doubles
+  double* part = reinterpret_cast<double*>(y.reg_part.p);
+  int64_t off = 0;
+  const std::vector<GradSeg> segs = grid_grad_segments(gs, off);
+  RcGridL2Reduce rr{};
+  rr.mult = mult; rr.tables = T;
+  for (int t = 0; t < T; ++t) {
+    const int64_t count = segs[t].size;
+    rr.count[t] = count;
+    rc_launch_grid_l2_bwd(gs.dev.lvl[t].table, count, (float)((double)mult / (double)count),
+                          grads ? grads + segs[t].offset : nullptr, part + (int64_t)t * B, st);
+  }
+  rc_launch_grid_l2_reduce(part, rr, loss, st);
+  RC_HIP(h, hipGetLastError());
   return RC_OK;
 }
 
@@ -92,19 +279,23 @@ int pack_train_stream(rc_handle* h, int level) {
 }  // namespace
 
 int64_t rc_density_grad_size(rc_handle* h, int32_t level) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, "rc_density_grad_size: bad level");
-  return grad_size(density_grad_segments(h, level));
-  RC_CATCH(h)
+  return layout_grad_size(h, level < 0 ? kNoLayout : level, "rc_density_grad_size");
 }
+int64_t rc_shader_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_SHADER, "rc_shader_grad_size"); }
+int64_t rc_light_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_LIGHT, "rc_light_grad_size"); }
+int64_t rc_material_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_MATERIAL, "rc_material_grad_size"); }
 
 int rc_density_grad_layout(rc_handle* h, int32_t level, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, "rc_density_grad_layout: bad level");
-  return copy_segments(h, density_grad_segments(h, level), segs, capacity, count, "rc_density_grad_layout");
-  RC_CATCH(h)
+  return layout_grad_layout(h, level < 0 ? kNoLayout : level, segs, capacity, count, "rc_density_grad_layout");
+}
+int rc_shader_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  return layout_grad_layout(h, RC_LAYOUT_SHADER, segs, capacity, count, "rc_shader_grad_layout");
+}
+int rc_light_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  return layout_grad_layout(h, RC_LAYOUT_LIGHT, segs, capacity, count, "rc_light_grad_layout");
+}
+int rc_material_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  return layout_grad_layout(h, RC_LAYOUT_MATERIAL, segs, capacity, count, "rc_material_grad_layout");
 }
 
 int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_t n, const float* d_density,

@@ -196,6 +196,16 @@ EXPORTS = (
     "rc_material_regularizer", "rc_material_data_backward",
 )
 
+# Gradient layouts by key -- a density level (int), "shader", "light", "material": the C functions of its size and of its
+# segments (a density level is their first argument) and its RC_LAYOUT_* id (rc_load_params_flat; a level is its own).
+_GRAD_LAYOUTS = {
+    int: ("rc_density_grad_size", "rc_density_grad_layout", None),
+    "shader": ("rc_shader_grad_size", "rc_shader_grad_layout", RC_LAYOUT_SHADER),
+    "light": ("rc_light_grad_size", "rc_light_grad_layout", RC_LAYOUT_LIGHT),
+    "material": ("rc_material_grad_size", "rc_material_grad_layout", RC_LAYOUT_MATERIAL),
+}
+_LAYOUT_KEYS = {row[2]: key for key, row in _GRAD_LAYOUTS.items() if key is not int}
+
 _LIB = None
 _RAY_FIELDS = ("origins", "directions", "viewdirs", "near", "far", "lights", "normals")
 
@@ -661,20 +671,28 @@ class RadianceCache:
         self._check(query(self._h, *args, segs, cnt.value, C.byref(cnt), *tail))
         return [(s.name.decode(), int(s.offset), tuple(int(v) for v in s.shape[: s.ndim])) for s in segs]
 
-    def _grad_size(self, level=None):
-        """rc_density_grad_size(level), or rc_shader_grad_size for level None (fixed by the config: asked once)."""
+    def _layout_fn(self, key, which):
+        """(C function, leading arguments) of gradient layout `key`'s size (which=0) or segments (which=1) query."""
+        if isinstance(key, str):
+            return getattr(self.lib, _GRAD_LAYOUTS[key][which]), ()
+        return getattr(self.lib, _GRAD_LAYOUTS[int][which]), (key,)
+
+    def _grad_size(self, key):
+        """Floats of gradient layout `key` (_GRAD_LAYOUTS; fixed by the config: asked once)."""
         sizes = self.__dict__.setdefault("_grad_sizes", {})
-        total = sizes.get(level)
+        total = sizes.get(key)
         if total is None:
-            lib = self.lib
-            total = int(lib.rc_shader_grad_size(self._h) if level is None else
-                        lib.rc_light_grad_size(self._h) if level == "light" else
-                        lib.rc_material_grad_size(self._h) if level == "material" else
-                        lib.rc_density_grad_size(self._h, level))
+            fn, args = self._layout_fn(key, 0)
+            total = int(fn(self._h, *args))
             if total < 0:
                 self._check(total)
-            sizes[level] = total
+            sizes[key] = total
         return total
+
+    def _grad_layout(self, key):
+        """[(tensor name, offset, shape)] of gradient layout `key` and its size in floats."""
+        fn, args = self._layout_fn(key, 1)
+        return self._segments(fn, args), self._grad_size(key)
 
     def _grad_buffer(self, flat, total, what="grads"):
         """A flat gradient buffer of `total` floats: `flat` checked, or a zeroed one when it is None."""
@@ -684,6 +702,22 @@ class RadianceCache:
         if flat.numel() != total or flat.dtype != torch.float32 or not flat.is_cuda or not flat.is_contiguous():
             raise ValueError(f"{what} must be a contiguous float32 cuda tensor of {total} elements")
         return flat
+
+    def _loss_prologue(self, key, grad, stream_handle=None):
+        """The head of a loss call with one gradient buffer: the buffer of layout `key` (None for grad=False; `grad`
+        checked, or allocated zeroed when None), the zeroed float32 loss tensor [1] and the stream (the current one when
+        stream_handle is None)."""
+        torch = self._torch
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size(key))
+        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        return flat, loss, stream
+
+    def _regularizer(self, fn, key, args, grad):
+        """rc_{density,light,material}_regularizer: fn(handle, *args, grad flat, loss, stream) -> (grad flat or None, loss)."""
+        flat, loss, stream = self._loss_prologue(key, grad)
+        self._check(fn(self._h, *args, None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
+        return flat, loss
 
     def _lossmult(self, lossmult, held, n):
         """Per-ray loss weights [n] (kept alive in `held`), or None."""
@@ -698,12 +732,12 @@ class RadianceCache:
     def density_grad_layout(self, level: int):
         """rc_density_grad_layout: [(tensor name, offset, shape)] of the gradient buffer of proposal level `level`
         (the reference's parameter-tree names), and its total size in floats."""
-        return self._segments(self.lib.rc_density_grad_layout, (level,)), self._grad_size(level)
+        return self._grad_layout(level)
 
     def shader_grad_layout(self):
         """rc_shader_grad_layout: [(tensor name, offset, shape)] of the gradient buffer of the data loss's shader side
         (MLP_<last>/pred_normals_layer, the appearance-grid tables, the Cache/Shader dense layers), and its size."""
-        return self._segments(self.lib.rc_shader_grad_layout, ()), self._grad_size()
+        return self._grad_layout("shader")
 
     def hashgrid_grad_layout(self, grid_id: int):
         """rc_hashgrid_grad_layout: [(tensor name, offset, shape)] of the table-gradient buffer of a grid, and its size."""
@@ -816,7 +850,7 @@ class RadianceCache:
         flats = [None, None]
         if grads is not False:
             given = list(grads) if grads is not None else [None, None]
-            for i, level in enumerate((self.cfg.num_levels - 1, None)):
+            for i, level in enumerate((self.cfg.num_levels - 1, "shader")):
                 flats[i] = self._grad_buffer(given[i], self._grad_size(level), f"grads[{i}]")
         loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -849,7 +883,7 @@ class RadianceCache:
         flats = [None, None]
         if grads is not False:
             given = list(grads) if grads is not None else [None, None]
-            for i, level in enumerate((self.cfg.num_levels - 1, None)):
+            for i, level in enumerate((self.cfg.num_levels - 1, "shader")):
                 flats[i] = self._grad_buffer(given[i], self._grad_size(level), f"grads[{i}]")
         losses = torch.zeros(4, dtype=torch.float32, device=f"cuda:{self.device}")
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -866,18 +900,12 @@ class RadianceCache:
         (param_regularizer_loss, 'density_grid').  grad: flat buffer of density_grad_layout(level) to accumulate
         mult * x / numel into (allocated zeroed when None); grad=False computes the loss only.
         Returns (grad flat or None, loss [1] cuda tensor)."""
-        torch = self._torch
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size(level))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_density_regularizer(self._h, int(level), float(mult),
-                                                    None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
-        return flat, loss
+        return self._regularizer(self.lib.rc_density_regularizer, level, (int(level), float(mult)), grad)
 
     def light_grad_layout(self):
         """rc_light_grad_layout: [(tensor name, offset, shape)] of the LightSampler gradient buffer (the light_grid tables,
         then layers_0, layers_1, output_layer), and its size in floats."""
-        return self._segments(self.lib.rc_light_grad_layout, ()), self._grad_size("light")
+        return self._grad_layout("light")
 
     def light_sampling_backward(self, rays: Dict[str, object], randoms: Dict[str, object], num_secondary_samples: int = None,
                                 lossmult=None, mult: float = 1.0, linear_to_srgb: bool = True, grad=None,
@@ -886,15 +914,12 @@ class RadianceCache:
         (up to the secondary trace), the light_sampling loss (vmf_loss_fn over both suffixes) and its gradient w.r.t.
         the LightSampler parameters (light_grad_layout).  grad: flat buffer to accumulate into (allocated zeroed when
         None); grad=False computes the loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
-        torch = self._torch
         K = num_secondary_samples or self.cfg.num_secondary_samples
         r, held, n = self._rays_struct(rays)
         rnd, mr = self._material_randoms(randoms, n, K, held)
         lm = self._lossmult(lossmult, held, n)
         cfg = rc_light_sampling_loss(mult=float(mult), linear_to_srgb=int(bool(linear_to_srgb)))
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("light"))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        flat, loss, stream = self._loss_prologue("light", grad, stream_handle=stream_handle)
         self._check(self.lib.rc_light_sampling_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n,
                                                         C.byref(rnd), C.byref(mr), K, C.byref(cfg),
                                                         None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
@@ -905,13 +930,7 @@ class RadianceCache:
         """rc_light_regularizer: mult * sum over the light grid's tables of 0.5 * mean(x^2) (param_regularizer_loss,
         'light_grid').  grad: flat buffer of light_grad_layout to accumulate mult * x / numel into (allocated zeroed when
         None); grad=False computes the loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
-        torch = self._torch
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("light"))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_light_regularizer(self._h, float(mult), None if flat is None else flat.data_ptr(),
-                                                  loss.data_ptr(), stream))
-        return flat, loss
+        return self._regularizer(self.lib.rc_light_regularizer, "light", (float(mult),), grad)
 
     # -- optimizer ------------------------------------------------------------------------------
     def adam_update(self, buffers, step: Dict[str, object], stream_handle=None):
@@ -943,9 +962,9 @@ class RadianceCache:
         to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
         same tensors, bitwise."""
         torch = self._torch
-        named = {"shader": RC_LAYOUT_SHADER, "light": RC_LAYOUT_LIGHT, "material": RC_LAYOUT_MATERIAL}
-        lay = named[layout] if layout in named else int(layout)
-        total = self._grad_size({RC_LAYOUT_SHADER: None, RC_LAYOUT_LIGHT: "light", RC_LAYOUT_MATERIAL: "material"}.get(lay, lay))
+        key = layout if isinstance(layout, str) else _LAYOUT_KEYS.get(int(layout), int(layout))
+        lay = _GRAD_LAYOUTS[key][2] if isinstance(key, str) else key
+        total = self._grad_size(key)
         if params.numel() != total or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
             raise ValueError(f"params must be a contiguous float32 cuda tensor of {total} elements")
         stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
@@ -1076,7 +1095,7 @@ class RadianceCache:
     def material_grad_layout(self):
         """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid
         tables, then bottleneck_layer, pred_brdf_layer), and its size in floats."""
-        return self._segments(self.lib.rc_material_grad_layout, ()), self._grad_size("material")
+        return self._grad_layout("material")
 
     def _shading_randoms(self, randoms, held):
         """The rc_randoms / rc_material_randoms of material_smoothness_backward: the primary pass's jitter and the shading
@@ -1105,7 +1124,6 @@ class RadianceCache:
         (noise: [n, 3], N(0, 1)) and its gradient w.r.t. the MaterialShader parameters (material_grad_layout).  grad: flat
         buffer to accumulate into (allocated zeroed when None); grad=False computes the loss only.
         Returns (grad flat or None, loss [1] cuda tensor)."""
-        torch = self._torch
         r, held, n = self._rays_struct(rays)
         rnd, mr = self._shading_randoms(randoms, held)
         lm = self._lossmult(lossmult, held, n)
@@ -1116,9 +1134,7 @@ class RadianceCache:
         cfg = rc_material_smoothness_loss(mult=float(mult), weight_albedo=float(weight_albedo),
                                           weight_other=float(weight_other), noise=float(noise_scale),
                                           tensoir_albedo=int(bool(tensoir_albedo)))
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("material"))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        flat, loss, stream = self._loss_prologue("material", grad, stream_handle=stream_handle)
         self._check(self.lib.rc_material_smoothness_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n,
                                                              C.byref(rnd), C.byref(mr), nz.data_ptr(), C.byref(cfg),
                                                              None if flat is None else flat.data_ptr(), loss.data_ptr(),
@@ -1131,13 +1147,7 @@ class RadianceCache:
         'material_grid', the ease factor folded into mult).  grad: flat buffer of material_grad_layout to accumulate
         mult * x / numel into (allocated zeroed when None); grad=False computes the loss only.
         Returns (grad flat or None, loss [1] cuda tensor)."""
-        torch = self._torch
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("material"))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_material_regularizer(self._h, float(mult), None if flat is None else flat.data_ptr(),
-                                                     loss.data_ptr(), stream))
-        return flat, loss
+        return self._regularizer(self.lib.rc_material_regularizer, "material", (float(mult),), grad)
 
     def material_data_backward(self, rays: Dict[str, object], randoms: Dict[str, object], gt_rgb,
                                num_secondary_samples: int = None, lossmult=None, cfg=None, grad=None, stream_handle=None):
@@ -1148,7 +1158,6 @@ class RadianceCache:
         loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
         from .config import MaterialDataLossConfig
 
-        torch = self._torch
         cfg = MaterialDataLossConfig() if cfg is None else cfg
         K = num_secondary_samples or self.cfg.num_secondary_samples
         r, held, n = self._rays_struct(rays)
@@ -1163,9 +1172,7 @@ class RadianceCache:
                                   use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
                                   use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)),
                                   use_norm_rawnerf=int(bool(cfg.use_norm_rawnerf)))
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("material"))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        flat, loss, stream = self._loss_prologue("material", grad, stream_handle=stream_handle)
         self._check(self.lib.rc_material_data_backward(self._h, C.byref(r), gt.data_ptr(),
                                                        None if lm is None else lm.data_ptr(), n, C.byref(rnd), C.byref(mr),
                                                        K, C.byref(c), None if flat is None else flat.data_ptr(),

@@ -339,15 +339,16 @@ class CacheStageOptimizer:
     """The cache stage's optimizer state on the device: flat params, mu, nu and gradient buffers in the layouts
     rc.density_grad_layout(l) (l = 0 .. num_levels-1) and rc.shader_grad_layout() ("shader"), and the optax count.
     step() = one rc_adam_update over the four buffers (nan_to_num, clip_gradients, the chained Adams), then
-    rc_load_params_flat per layout: the handle renders the updated parameters, ordered on the current stream."""
+    rc_load_params_flat per layout: the handle renders the updated parameters, ordered on the current stream.
+    `keys` (the subclasses'): other gradient layouts of the handle ("light", "material") instead of the cache stage's."""
 
-    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig(), keys=None):
         import torch
         from . import rc_ext
 
         self.rc, self.cfg, self._rc_ext = rc, cfg, rc_ext
-        self.keys = list(range(rc.cfg.num_levels)) + ["shader"]
-        self.layouts = {k: (rc.shader_grad_layout() if k == "shader" else rc.density_grad_layout(k)) for k in self.keys}
+        self.keys = list(range(rc.cfg.num_levels)) + ["shader"] if keys is None else list(keys)
+        self.layouts = {k: rc._grad_layout(k) for k in self.keys}
         self.group_names = [g for g, _ in cfg.groups()]
         dev = f"cuda:{rc.device}"
         z = lambda k: torch.zeros(self.layouts[k][1], dtype=torch.float32, device=dev)
@@ -419,6 +420,18 @@ class CacheStageOptimizer:
         self.refresh()
 
 
+def _train_step(opt: CacheStageOptimizer, group, grads):
+    """The body of the *_step functions: train_frac from opt.count, grads(train_frac) -> ({key: flat buffer}, or the one
+    flat buffer of a single-layout optimizer; losses), the pmean over `group` (allreduce_grads), opt.step().  -> losses."""
+    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
+    flats, losses = grads(tf)
+    if not isinstance(flats, dict):
+        flats = {opt.keys[0]: flats}
+    allreduce_grads([flats[k] for k in opt.keys], group=group)
+    opt.step({k: flats[k] for k in opt.keys})
+    return losses
+
+
 def cache_stage_step(rc, opt: CacheStageOptimizer, rays, rgb, jitters, lossmult=None, group=None,
                      geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
                      interlevel_cfg: InterlevelConfig = InterlevelConfig()):
@@ -426,12 +439,8 @@ def cache_stage_step(rc, opt: CacheStageOptimizer, rays, rgb, jitters, lossmult=
     (trainer.py:2116-2126), cache_stage_grads into the optimizer's zeroed gradient buffers, the pmean over `group`
     when torch.distributed runs (allreduce_grads), then opt.step() (nan_to_num, clip_gradients, the Adams, the handle's
     refresh).  -> the losses dict of cache_stage_grads (the local batch's values)."""
-    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
-    flats, losses = cache_stage_grads(rc, rays, rgb, jitters, tf, lossmult, dict(opt.grads), geometry_cfg, data_cfg,
-                                      interlevel_cfg)
-    allreduce_grads([flats[k] for k in opt.keys], group=group)
-    opt.step({k: flats[k] for k in opt.keys})
-    return losses
+    return _train_step(opt, group, lambda tf: cache_stage_grads(rc, rays, rgb, jitters, tf, lossmult, dict(opt.grads),
+                                                                geometry_cfg, data_cfg, interlevel_cfg))
 
 
 # ---- the light sampler ---------------------------------------------------------------------------------------------
@@ -457,23 +466,7 @@ class LightSamplerOptimizer(CacheStageOptimizer):
     (RC_LAYOUT_LIGHT).  init_from / params_dict / state_dict / load_state_dict as CacheStageOptimizer."""
 
     def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
-        import torch
-        from . import rc_ext
-
-        self.rc, self.cfg, self._rc_ext = rc, cfg, rc_ext
-        self.keys = ["light"]
-        self.layouts = {"light": rc.light_grad_layout()}
-        self.group_names = [g for g, _ in cfg.groups()]
-        dev = f"cuda:{rc.device}"
-        z = lambda k: torch.zeros(self.layouts[k][1], dtype=torch.float32, device=dev)
-        self.params = {k: z(k) for k in self.keys}
-        self.mu = {k: z(k) for k in self.keys}
-        self.nu = {k: z(k) for k in self.keys}
-        self.grads = {k: z(k) for k in self.keys}
-        self.segments = {k: [(off, int(np.prod(shape)), self.group_names.index(param_group(name, cfg)))
-                             for name, off, shape in self.layouts[k][0]] for k in self.keys}
-        self._table = self._adam_table(self.grads)
-        self.count = 0
+        super().__init__(rc, cfg, ["light"])
 
 
 def light_sampler_step(rc, opt: LightSamplerOptimizer, rays, randoms, lossmult=None, group=None,
@@ -481,11 +474,7 @@ def light_sampler_step(rc, opt: LightSamplerOptimizer, rays, randoms, lossmult=N
     """One train step of the light sampler on its own loss: train_frac from opt.count, light_sampling_grads into the
     optimizer's zeroed gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().
     -> the losses dict of light_sampling_grads."""
-    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
-    flat, losses = light_sampling_grads(rc, rays, randoms, tf, lossmult, opt.grads["light"], cfg)
-    allreduce_grads([flat], group=group)
-    opt.step({"light": flat})
-    return losses
+    return _train_step(opt, group, lambda tf: light_sampling_grads(rc, rays, randoms, tf, lossmult, opt.grads["light"], cfg))
 
 
 # ---- the material network ------------------------------------------------------------------------------------------
@@ -531,23 +520,7 @@ class MaterialOptimizer(CacheStageOptimizer):
     CacheStageOptimizer."""
 
     def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
-        import torch
-        from . import rc_ext
-
-        self.rc, self.cfg, self._rc_ext = rc, cfg, rc_ext
-        self.keys = ["material"]
-        self.layouts = {"material": rc.material_grad_layout()}
-        self.group_names = [g for g, _ in cfg.groups()]
-        dev = f"cuda:{rc.device}"
-        z = lambda k: torch.zeros(self.layouts[k][1], dtype=torch.float32, device=dev)
-        self.params = {k: z(k) for k in self.keys}
-        self.mu = {k: z(k) for k in self.keys}
-        self.nu = {k: z(k) for k in self.keys}
-        self.grads = {k: z(k) for k in self.keys}
-        self.segments = {k: [(off, int(np.prod(shape)), self.group_names.index(param_group(name, cfg)))
-                             for name, off, shape in self.layouts[k][0]] for k in self.keys}
-        self._table = self._adam_table(self.grads)
-        self.count = 0
+        super().__init__(rc, cfg, ["material"])
 
 
 def material_step(rc, opt: MaterialOptimizer, rays, randoms, noise, lossmult=None, group=None,
@@ -555,11 +528,8 @@ def material_step(rc, opt: MaterialOptimizer, rays, randoms, noise, lossmult=Non
     """One train step of the material network on its own losses: train_frac from opt.count, material_smoothness_grads
     into the optimizer's zeroed gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().
     -> the losses dict of material_smoothness_grads."""
-    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
-    flat, losses = material_smoothness_grads(rc, rays, randoms, noise, tf, lossmult, opt.grads["material"], cfg)
-    allreduce_grads([flat], group=group)
-    opt.step({"material": flat})
-    return losses
+    return _train_step(opt, group, lambda tf: material_smoothness_grads(rc, rays, randoms, noise, tf, lossmult,
+                                                                        opt.grads["material"], cfg))
 
 
 def material_data_grads(rc, rays, randoms, gt_rgb, lossmult=None, flat=None,
@@ -593,9 +563,5 @@ def material_stage_step(rc, opt: MaterialOptimizer, rays, randoms, gt_rgb, noise
     """One train step of the material network on the stage's losses: train_frac from opt.count, material_stage_grads into
     the optimizer's zeroed gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().
     -> the losses dict of material_stage_grads."""
-    tf = train_frac_at(opt.count, opt.cfg.scaled_steps(opt.cfg.max_steps))
-    flat, losses = material_stage_grads(rc, rays, randoms, gt_rgb, noise, tf, lossmult, opt.grads["material"], data_cfg,
-                                        smooth_cfg)
-    allreduce_grads([flat], group=group)
-    opt.step({"material": flat})
-    return losses
+    return _train_step(opt, group, lambda tf: material_stage_grads(rc, rays, randoms, gt_rgb, noise, tf, lossmult,
+                                                                   opt.grads["material"], data_cfg, smooth_cfg))

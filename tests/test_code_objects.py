@@ -89,12 +89,18 @@ def code_objects(lib_path, tmp_path):
     return kernels
 
 
+_PRODUCT = []
+
+
 @pytest.fixture(scope="module")
 def product(tmp_path_factory):
-    import __graft_entry__ as g
-    g.build()
-    from nrc_amd import rc_ext
-    return code_objects(rc_ext.library_path(), tmp_path_factory.mktemp("product"))
+    # built and extracted once per session: the per-entry-point modules (test_*_code_objects.py) import this fixture
+    if not _PRODUCT:
+        import __graft_entry__ as g
+        g.build()
+        from nrc_amd import rc_ext
+        _PRODUCT.append(code_objects(rc_ext.library_path(), tmp_path_factory.mktemp("product")))
+    return _PRODUCT[0]
 
 
 @pytest.fixture(scope="module")
@@ -128,3 +134,53 @@ def test_fp32_variant_has_no_bf16_mfma(variant_f32):
     bf16 = {f'{v["base"]} {k[1]} ({k[0]})': sum("bf16" in op for op in v["mfma"]) for k, v in variant_f32.items()
             if any("bf16" in op for op in v["mfma"])}
     assert not bf16, bf16
+
+
+# The training entry points' code, one row per tests/test_<entry>_code_objects.py: its exports (in the library and in
+# rc_ext.EXPORTS), its exact kernel set, the kernels with no MFMA at all and the MFMA opcode a kernel must contain.  Every
+# kernel of a row uses no scratch and no bf16 MFMA: the split-bf16 form is fenced to the forward shaders, the backwards
+# run in fp32.
+TRAINING = {
+    "data": (("rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward"),
+             {"k_data_loss_bwd", "k_gemm", "k_sum_parts", "k_stage_feature", "k_shader_glue_fwd", "k_shader_out_bwd",
+              "k_shader_glue_bwd", "k_split_feature"},
+             set(), {"k_gemm": "v_mfma_f32_32x32x2_f32"}),
+    "geometry": (("rc_geometry_backward", "rc_density_regularizer"),
+                 {"k_geometry_loss_bwd", "k_stage_hidden", "k_grid_l2_bwd", "k_grid_l2_reduce"}, set(), {}),
+    "light": (("rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward", "rc_light_regularizer"),
+              {"k_light_sampling_loss_bwd", "k_gemm", "k_sum_parts", "k_grid_l2_bwd", "k_grid_l2_reduce"}, set(), {}),
+    "material": (("rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
+                  "rc_material_regularizer"),
+                 {"k_material_smoothness_points", "k_material_smoothness_bwd", "k_material_smoothness_reduce",
+                  "k_grid_l2_bwd", "k_grid_l2_reduce"},
+                 {"k_material_smoothness_bwd", "k_material_smoothness_reduce"}, {}),
+    "material_data": (("rc_material_data_backward",), {"k_material_data_bwd", "k_material_data_head_bwd"},
+                      {"k_material_data_bwd", "k_material_data_head_bwd"}, {}),
+    # streaming element-wise code with 16-byte loads and stores
+    "optimizer": (("rc_adam_update", "rc_load_params_flat"), {"k_adam", "k_adam_sumsq", "k_adam_norm"},
+                  {"k_adam", "k_adam_sumsq", "k_adam_norm"}, {}),
+}
+
+
+def check_training_exports(entry):
+    import ctypes
+
+    from nrc_amd import rc_ext
+
+    lib = ctypes.CDLL(rc_ext.library_path())
+    for name in TRAINING[entry][0]:
+        assert hasattr(lib, name), name
+        assert name in rc_ext.EXPORTS, name
+
+
+def check_training_kernels(product, entry):
+    _, kernels, no_mfma, has_op = TRAINING[entry]
+    ks = {v["base"]: v for v in product.values() if v["base"] in kernels}
+    assert set(ks) == kernels, sorted(set(ks))
+    for name, v in ks.items():
+        assert v["scratch"] == 0, (name, v["scratch"])
+        assert not any("bf16" in op for op in v["mfma"]), name
+        if name in no_mfma:
+            assert not v["mfma"], (name, v["mfma"])
+    for name, op in has_op.items():
+        assert op in ks[name]["mfma"], (name, op)
