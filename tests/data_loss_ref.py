@@ -6,7 +6,7 @@
   composite sum w rgb_s + max(0, 1 - acc) bg                                         render.py:172-247
   L = mult * mean_{n x 3}(lossmult * sqrt((rgb - gt)^2 + padding^2))                 train_utils.py:402-528
 
-built on oracle.cache_ref / oracle.mathx, with the two JAX derivative rules torch does not share written out:
+built on oracle.cache_ref / oracle.mathx, with the two JAX derivative rules torch does not share (tests/jax_rules.py):
   * jnp.maximum / jnp.clip pass half of the gradient to each side at a tie (lax.max's balanced-eq JVP);
   * ref_utils.l2_normalize's override_gradient: the backward divides by sqrt(max(float32 eps, |x|^2)).
 """
@@ -16,38 +16,24 @@ import math
 
 import torch
 
+from jax_rules import l2_normalize, value_with_grad_of  # noqa: F401  (l2_normalize at its default grad_eps, float32 eps)
 from oracle import cache_ref, mathx
 
 P = "params/"
 
 
-def _value_with_grad_of(value, surrogate):
-    """value in the forward pass, the gradient of `surrogate` in the backward pass (math.override_gradient)."""
-    return value.detach() + (surrogate - surrogate.detach())
-
-
 def maximum(x, lo):
     """jnp.maximum(x, lo) with scalar lo: the gradient is 1/2 at x == lo."""
-    return _value_with_grad_of(torch.clamp(x, min=lo), 0.5 * (x + lo + torch.abs(x - lo)))
+    return value_with_grad_of(torch.clamp(x, min=lo), 0.5 * (x + lo + torch.abs(x - lo)))
 
 
 def minimum(x, hi):
-    return _value_with_grad_of(torch.clamp(x, max=hi), 0.5 * (x + hi - torch.abs(x - hi)))
+    return value_with_grad_of(torch.clamp(x, max=hi), 0.5 * (x + hi - torch.abs(x - hi)))
 
 
 def clip(x, lo, hi):
     """jnp.clip = minimum(maximum(x, lo), hi)."""
     return minimum(maximum(x, lo), hi)
-
-
-def l2_normalize(x):
-    """ref_utils.l2_normalize: forward x / sqrt(max(tiny, |x|^2)), backward through x / sqrt(max(eps, |x|^2)), zero where
-    |x|^2 < tiny."""
-    denom_sq = (x * x).sum(-1, keepdim=True)
-    val = x / torch.sqrt(torch.clamp(denom_sq, min=mathx.TINY))
-    grad = x / torch.sqrt(torch.clamp(denom_sq, min=mathx.EPS))
-    out = _value_with_grad_of(val, grad)
-    return torch.where(denom_sq < mathx.TINY, torch.zeros_like(out), out)
 
 
 def normals_pred(weights, cfg, h64):

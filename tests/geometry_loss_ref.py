@@ -10,12 +10,12 @@ test module).
   reverse      the same with w' = stop_gradient(w)                                    train_utils.py:1073-1093
   n^ = normals_pred = nan_to_num(-l2_normalize(pred_raw))                              geometry.py:467-471
 
-JAX rules written out where torch differs (jax 0.4.16, jax/_src/lax/lax.py and jax/_src/numpy):
+JAX rules where torch differs (jax 0.4.16, jax/_src/lax/lax.py and jax/_src/numpy; written out in tests/jax_rules.py):
   * lax.abs: the JVP is select(x >= 0, g, -g) (`_abs_jvp_rule`), so the derivative is +1 at 0; torch's is 0 there;
   * jnp.minimum(0, y)^2: lax.min's balanced JVP passes half of the gradient at the tie, times 2 min(0, y) = 0: zero
     derivative at the tie either way;
   * ref_utils.l2_normalize's override_gradient: the backward divides by sqrt(max(float32 eps, |x|^2))
-    (data_loss_ref.l2_normalize);
+    (jax_rules.l2_normalize);
   * jnp.nan_to_num: `where(isnan(x), 0, clip(x, min, max))`-shaped, so the gradient passes where x is finite;
   * each ray's + 1e-5 sits inside the outer abs: it is part of the value, and enters the gradient only through the
     sign select of that abs.
@@ -24,13 +24,8 @@ from __future__ import annotations
 
 import torch
 
-import data_loss_ref as dr
+from jax_rules import jabs, l2_normalize
 from oracle import mathx
-
-
-def jabs(x):
-    """jnp.abs with lax.abs' JVP: derivative +1 at 0."""
-    return dr._value_with_grad_of(x.abs(), torch.where(x >= 0, x, -x))
 
 
 def stopgrad_with_weight(x, weight):
@@ -44,7 +39,7 @@ def stopgrad_with_weight(x, weight):
 
 def normals_from_raw(raw):
     """nan_to_num(-l2_normalize(pred_raw)) with l2_normalize's override gradient."""
-    return mathx.nan_to_num(-dr.l2_normalize(raw))
+    return mathx.nan_to_num(-l2_normalize(raw))
 
 
 def distortion(c, w):

@@ -15,36 +15,15 @@ import math
 import numpy as np
 import torch
 
+from jax_rules import FLT_EPS, TINY, jmax, jmin, l2_normalize  # noqa: F401
 from oracle import cache_ref, hashgrid_ref, mathx
 
 P = "params/"
-FLT_EPS = float(np.finfo(np.float32).eps)
-TINY = float(np.finfo(np.float32).tiny)
-
-
-def jmax(x, c: float):
-    """jnp.maximum(x, c): the gradient passes where x > c, half of it where x == c."""
-    out = torch.where(x > c, x, torch.full_like(x, c))
-    return out + torch.where(x == c, 0.5 * (x - x.detach()), torch.zeros_like(x))
-
-
-def jmin(x, c: float):
-    out = torch.where(x < c, x, torch.full_like(x, c))
-    return out + torch.where(x == c, 0.5 * (x - x.detach()), torch.zeros_like(x))
 
 
 def safe_exp(x):
     """inverse_render.math.safe_exp: exp(minimum(x, 80)); no custom JVP."""
     return torch.exp(jmin(x, 80.0))
-
-
-def l2_normalize(x, grad_eps: float = FLT_EPS):
-    """ref_utils.l2_normalize: forward x / sqrt(max(tiny, |x|^2)), backward through x / sqrt(max(grad_eps, |x|^2))."""
-    s = (x * x).sum(-1, keepdim=True)
-    val = x / torch.sqrt(torch.clamp(s, min=TINY))
-    grad = x / torch.sqrt(jmax(s, max(TINY, grad_eps)))
-    out = val.detach() + (grad - grad.detach())
-    return torch.where(s < TINY, torch.zeros_like(out), out)
 
 
 def eval_vmf(x, means, kappa):

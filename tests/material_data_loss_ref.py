@@ -22,32 +22,16 @@ import math
 import numpy as np
 import torch
 
+from jax_rules import F32_MAX, jmaximum, jminimum, nan_to_num  # noqa: F401
 from oracle import material_ref
 
 EPS = 1.1920929e-07          # jnp.finfo(float32).eps, the RC_EPS floors of get_lobe
 DENOM_EPS = 1e-5             # render_utils.DENOMINATOR_EPS
-F32_MAX = float(np.finfo(np.float32).max)
-
-
-def jmaximum(u, v):
-    """jnp.maximum(u, v): the larger side takes the gradient, half each on a tie."""
-    return torch.where(u > v, u, torch.where(u < v, v, 0.5 * (u + v)))
-
-
-def jminimum(u, v):
-    """jnp.minimum(u, v): the smaller side takes the gradient, half each on a tie."""
-    return torch.where(u < v, u, torch.where(u > v, v, 0.5 * (u + v)))
 
 
 def jclip(x, lo: float, hi: float):
     """jnp.clip(x, lo, hi) = minimum(maximum(x, lo), hi) with constant bounds."""
     return jminimum(jmaximum(x, torch.full_like(x, lo)), torch.full_like(x, hi))
-
-
-def nan_to_num(x):
-    """jnp.nan_to_num: nan -> 0, +-inf -> +-float32 max; the gradient passes unchanged where x is finite."""
-    fixed = torch.nan_to_num(x.detach(), nan=0.0, posinf=F32_MAX, neginf=-F32_MAX)
-    return torch.where(torch.isfinite(x), x, fixed)
 
 
 def rgb_clip(cache_rgb, gt, clip_val=1e4, use_gt=False, use_combined=True, use_norm=False):

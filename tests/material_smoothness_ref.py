@@ -6,40 +6,17 @@ CPU and GPU tests of rc_material_smoothness_backward.
   material head        oracle.material_ref.material_mlp (material grid, bottleneck_layer, pred_brdf_layer, the heads)
   lambda               lossmult_r * sg(w) (:2601-2607), w the shading sample's weight
 
-JAX rules restated here (jax 0.4.16, read from the source, not run): jnp.abs' JVP is select(x >= 0, g, -g) (+1 at 0;
+JAX rules used here (tests/jax_rules.py; jax 0.4.16, read from the source, not run): jnp.abs' JVP is select(x >= 0, g, -g) (+1 at 0;
 torch's sign gives 0 there); jnp.maximum gives half the gradient to each side on a tie; jnp.nan_to_num passes the
 gradient unchanged where the value is finite."""
 from __future__ import annotations
 
 import numpy as np
-import torch
 
+from jax_rules import F32_MAX, jabs, jmax_const, jmaximum, nan_to_num  # noqa: F401
 from oracle import material_ref
 
 P = "params/"
-F32_MAX = float(np.finfo(np.float32).max)
-
-
-def jabs(x):
-    """jnp.abs with jax's JVP: d|x|/dx = +1 at x = 0 (torch.abs would give 0)."""
-    return torch.where(x >= 0, x, -x)
-
-
-def jmaximum(u, v):
-    """jnp.maximum(u, v) of two traced arrays: the larger side takes the gradient, half each on a tie."""
-    return torch.where(u > v, u, torch.where(u < v, v, 0.5 * (u + v)))
-
-
-def jmax_const(c: float, x):
-    """jnp.maximum(c, x) with a constant c: the gradient passes where x > c, half of it where x == c."""
-    out = torch.where(x > c, x, torch.full_like(x, c))
-    return out + torch.where(x == c, 0.5 * (x - x.detach()), torch.zeros_like(x))
-
-
-def nan_to_num(x):
-    """jnp.nan_to_num: nan -> 0, +-inf -> +-float32 max; the gradient passes unchanged where x is finite."""
-    fixed = torch.nan_to_num(x.detach(), nan=0.0, posinf=F32_MAX, neginf=-F32_MAX)
-    return torch.where(torch.isfinite(x), x, fixed)
 
 
 def material(weights, cfg, pts):

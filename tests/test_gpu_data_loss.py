@@ -8,6 +8,7 @@ import torch
 
 import common
 import data_loss_ref as dr
+import loss_cases as lc
 import nrc_amd
 from nrc_amd import train
 from oracle import cache_ref, hashgrid_ref, mathx, train_ref
@@ -21,42 +22,11 @@ pytestmark = pytest.mark.gpu
 
 
 def _case(n, seed=5):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rays = {k: v for k, v in rays.items() if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-    jit = [j.reshape(-1) for j in common.jitters(n, seed=seed + 1)]
-    rng = np.random.Generator(np.random.PCG64(seed + 2))
-    gt = rng.uniform(0.0, 1.0, size=(n, 3)).astype(np.float32)
-    return rays, jit, gt
-
-
-def _lossmult(n, seed=9):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
-    lm[::7] = 0.0
-    return lm
-
-
-def _hidden(hbuf, np_):
-    """hbuf (k_density_mlp's accumulator order per 32-point tile) -> [np, 64] in the reference's column order."""
-    tiles = (np_ + 31) // 32
-    hb = hbuf[: tiles * 2048].reshape(tiles, 2, 16, 2, 32)          # tile, t, r, h, point
-    t, r, h = np.meshgrid(np.arange(2), np.arange(16), np.arange(2), indexing="ij")
-    col = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h
-    out = np.empty((tiles, 32, 64), np.float32)
-    out[:, :, col.reshape(-1)] = hb.reshape(tiles, 64, 32).transpose(0, 2, 1)
-    return out.reshape(-1, 64)[:np_]
+    return (*lc.cache_case(n, seed), lc.uniform_gt(n, seed + 2))
 
 
 def _buffers(rc, n):
-    g = lambda name, count: rc.workspace("d:" + name)[:count]
-    np_ = n * S2
-    return dict(
-        density=g(f"density{L2}", np_).reshape(n, S2), tdist=g(f"tdist{L2}", n * (S2 + 1)).reshape(n, S2 + 1),
-        weights=g(f"weights{L2}", np_).reshape(n, S2), means=g(f"means{L2}", 3 * np_).reshape(3, np_).T.copy(),
-        h64=_hidden(g("hbuf", ((np_ + 31) // 32) * 2048), np_).reshape(n, S2, 64),
-        app=g("app", 32 * np_).reshape(32, np_).T.reshape(n, S2, 32).copy(),
-        normals_pred=g("normals_pred", 3 * np_), shade=g("shade", 15 * np_), rgb=g("rgb", 3 * n).reshape(n, 3),
-        d_density=g("d_density", np_).reshape(n, S2))
+    return lc.buffers(rc, "d:", n, ("density", "tdist", "means", "h64", "app", "d_density"))
 
 
 def _restated(w, b, rays, gt, lm, dtype, mult=1.0):
@@ -71,18 +41,13 @@ def _restated(w, b, rays, gt, lm, dtype, mult=1.0):
     return float(loss.detach()), dict(d_density=dens.grad, dfeat=h64.grad, dapp=app.grad, dp3=taps["pred_raw"].grad)
 
 
-def _bound(got, ref64, ref32, floor):
-    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
-    return err, 3.0 * err32 + floor
-
-
 def test_kernel_against_restatement():
     """Loss, d density, d feature64, d app32 and d pred_raw within 3x the fp32 restatement's distance from fp64 (plus a
     small floor), on the HIP forward's d: buffers, lossmult with zeros."""
     rc = common.make_rc()
     n = 1000
     rays, jit, gt = _case(n)
-    lm = _lossmult(n)
+    lm = lc.lossmult(n)
     (_, _), loss = rc.data_backward(rays, gt, jit, 0.4, lm)
     loss = float(loss.cpu())
     b = _buffers(rc, n)
@@ -91,13 +56,13 @@ def test_kernel_against_restatement():
                dapp=rc.workspace("d:dapp")[: np_ * 32].reshape(n, S2, 32), dp3=rc.workspace("d:dp3")[: np_ * 3].reshape(n, S2, 3))
     l64, g64 = _restated(common.weights_torch(dtype=torch.float64), b, rays, gt, lm, torch.float64)
     l32, g32 = _restated(common.weights_torch(dtype=torch.float32), b, rays, gt, lm, torch.float32)
-    err, tol = _bound(np.float64(loss), l64, l32, 1e-6 * l64)
+    err, tol = lc.bound(np.float64(loss), l64, l32, 1e-6 * l64)
     assert err <= tol, ("loss", loss, l64, l32)
     for k in ("d_density", "dfeat", "dapp", "dp3"):
         r64, r32 = g64[k].numpy(), g32[k].double().numpy()
         scale = float(np.abs(r64).max())
         assert scale > 0, k
-        err, tol = _bound(got[k].astype(np.float64), r64, r32, 2e-5 * scale)
+        err, tol = lc.bound(got[k].astype(np.float64), r64, r32, 2e-5 * scale)
         assert err <= tol, (k, err, tol, scale)
     assert np.all(b["d_density"][lm == 0.0] == 0.0)
     assert np.all(got["dfeat"][lm == 0.0] == 0.0)
@@ -231,24 +196,18 @@ def test_forward_matches_the_render_workspace():
                     assert np.array_equal(rc.workspace(f"i:{k}{l}"), rc.workspace(f"d:{k}{l}")), (k, l)
 
 
-def _mlp_part(rc, flat, which):
-    layout = rc.density_grad_layout(L2)[0] if which == 0 else rc.shader_grad_layout()[0]
-    keep = [(o, int(np.prod(s))) for name, o, s in layout if "grid" not in name]
-    return torch.cat([flat[o:o + c] for o, c in keep])
-
-
 def test_semantics():
     rc = common.make_rc()
     n = 777
     rays, jit, gt = _case(n, seed=31)
-    lm = _lossmult(n, seed=32)
+    lm = lc.lossmult(n, seed=32)
     f1, l1 = rc.data_backward(rays, gt, jit, 0.3, lm)
     f1 = [f.clone() for f in f1]
     l1 = l1.clone()
     f2, l2 = rc.data_backward(rays, gt, jit, 0.3, lm)
     assert torch.equal(l1, l2)                                   # bitwise stable
     for i in range(2):
-        assert torch.equal(_mlp_part(rc, f1[i], i), _mlp_part(rc, f2[i], i))
+        assert torch.equal(lc.mlp_part(rc, f1[i], i), lc.mlp_part(rc, f2[i], i))
         assert float(f1[i].abs().max()) > 0
     f3, l3 = rc.data_backward(rays, gt, jit, 0.3, lm, mult=2.0)  # linear in mult
     for i in range(2):
@@ -258,7 +217,7 @@ def test_semantics():
     acc = [f.clone() for f in f1]                                # accumulates; MLP parts bitwise 2x
     rc.data_backward(rays, gt, jit, 0.3, lm, grads=acc)
     for i in range(2):
-        assert torch.equal(_mlp_part(rc, acc[i], i), 2 * _mlp_part(rc, f1[i], i))
+        assert torch.equal(lc.mlp_part(rc, acc[i], i), 2 * lc.mlp_part(rc, f1[i], i))
     fz, lz = rc.data_backward(rays, gt, jit, 0.3, lm, grads=False)   # NULL buffers: the loss only
     assert fz == (None, None) and torch.equal(lz, l1)
     empty = {k: v[:0] for k, v in rays.items()}                 # n = 0
@@ -317,19 +276,13 @@ def test_training_loop_reduces_the_loss():
     gt = target.render_rays(rays, {"jitter": jit}, outputs=["rgb"])["rgb"]
     gt = torch.as_tensor(np.asarray(gt.cpu() if hasattr(gt, "cpu") else gt)).reshape(n, 3).contiguous()
     names = [name for name, _, _ in rc.density_grad_layout(L2)[0]] + [name for name, _, _ in rc.shader_grad_layout()[0]]
-    params = {k: torch.from_numpy(v).cuda() for k, v in common.weights_np().items() if k in names}
-    assert len(params) == len(names)
-    opt = torch.optim.Adam(params.values(), lr=LOOP_LR)
-    hist = []
-    for step in range(LOOP_STEPS):
+
+    def grads():
         g, _, loss = train.data_grads(rc, rays, gt, jit, 1.0)
         train.interlevel_grads(rc, rays, jit, 1.0)
-        hist.append(float(loss))
-        for part in g.values():
-            for name, v in part.items():
-                params[name].grad = v.clone()
-        opt.step()
-        rc.load_weights(params)
+        return float(loss), {name: v for part in g.values() for name, v in part.items()}
+
+    hist = lc.adam_loop(rc, names, LOOP_LR, LOOP_STEPS, grads)
     assert min(hist[-3:]) < LOOP_DROP * hist[0], hist
 
 

@@ -9,6 +9,7 @@ import torch
 import common
 import data_loss_ref as dr
 import geometry_loss_ref as gr
+import loss_cases as lc
 import nrc_amd
 from nrc_amd import rc_ext, train
 from oracle import cache_ref, hashgrid_ref, mathx, train_ref
@@ -22,39 +23,8 @@ TERMS = train.geometry_terms(1.0)
 pytestmark = pytest.mark.gpu
 
 
-def _case(n, seed=5):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rays = {k: v for k, v in rays.items() if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-    jit = [j.reshape(-1) for j in common.jitters(n, seed=seed + 1)]
-    return rays, jit
-
-
-def _lossmult(n, seed=9):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
-    lm[::7] = 0.0
-    return lm
-
-
-def _hidden(hbuf, np_):
-    tiles = (np_ + 31) // 32
-    hb = hbuf[: tiles * 2048].reshape(tiles, 2, 16, 2, 32)
-    t, r, h = np.meshgrid(np.arange(2), np.arange(16), np.arange(2), indexing="ij")
-    col = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h
-    out = np.empty((tiles, 32, 64), np.float32)
-    out[:, :, col.reshape(-1)] = hb.reshape(tiles, 64, 32).transpose(0, 2, 1)
-    return out.reshape(-1, 64)[:np_]
-
-
 def _buffers(rc, n):
-    g = lambda name, count: rc.workspace("g:" + name)[:count]
-    np_ = n * S2
-    soa = lambda name: g(name, 3 * np_).reshape(3, np_).T.reshape(n, S2, 3).copy()
-    return dict(means=g(f"means{L2}", 3 * np_).reshape(3, np_).T.copy(),
-                density=g(f"density{L2}", np_).reshape(n, S2), tdist=g(f"tdist{L2}", n * (S2 + 1)).reshape(n, S2 + 1),
-                weights=g(f"weights{L2}", np_).reshape(n, S2), normals_pred=soa("normals_pred"),
-                normals=soa("normals_grad"), h64=_hidden(g("hbuf", ((np_ + 31) // 32) * 2048), np_).reshape(n, S2, 64),
-                d_density=g("d_density", np_).reshape(n, S2), d_pred=g("d_pred", 3 * np_).reshape(n, S2, 3))
+    return lc.buffers(rc, "g:", n, ("means", "density", "tdist", "normals_grad", "h64", "d_density", "d_pred"))
 
 
 def _restated(w, b, rays, lm, dtype):
@@ -65,15 +35,9 @@ def _restated(w, b, rays, lm, dtype):
     raw = (t(b["h64"]) @ kern + bias).detach().requires_grad_(True)
     tdist, dirs = t(b["tdist"]), t(rays["directions"])
     weights = gr.weights_from_density(dens, tdist, dirs)
-    losses = gr.geometry_losses(weights, t(lm), tdist, t(rays["viewdirs"]), gr.normals_from_raw(raw), t(b["normals"]), TERMS)
+    losses = gr.geometry_losses(weights, t(lm), tdist, t(rays["viewdirs"]), gr.normals_from_raw(raw), t(b["normals_grad"]), TERMS)
     losses.sum().backward()
     return losses.detach().numpy(), dens.grad.numpy(), raw.grad.numpy()
-
-
-def _check(got, ref64, ref32, what, rel_floor=1e-6):
-    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
-    bound = 3.0 * err32 + rel_floor * float(np.abs(ref64).max()) + 1e-12
-    assert err <= bound, (what, err, err32, bound)
 
 
 def test_kernel_against_restatement():
@@ -81,8 +45,8 @@ def test_kernel_against_restatement():
     floor), on the forward's own buffers."""
     n = 3000
     rc = common.make_rc()
-    rays, jit = _case(n)
-    lm = _lossmult(n)
+    rays, jit = lc.cache_case(n)
+    lm = lc.lossmult(n)
     _, losses = rc.geometry_backward(rays, jit, 0.4, lm, TERMS)
     torch.cuda.synchronize()
     b = _buffers(rc, n)
@@ -90,9 +54,9 @@ def test_kernel_against_restatement():
     l64, dd64, dp64 = _restated(w, b, rays, lm, torch.float64)
     l32, dd32, dp32 = _restated(w, b, rays, lm, torch.float32)
     assert all(v > 0 for v in l64), l64
-    _check(losses.cpu().numpy().astype(np.float64), l64, l32, "losses", rel_floor=1e-5)
-    _check(b["d_density"], dd64, dd32, "d_density")
-    _check(b["d_pred"], dp64, dp32, "d_pred")
+    lc.check(losses.cpu().numpy().astype(np.float64), l64, l32, "losses", rel_floor=1e-5)
+    lc.check(b["d_density"], dd64, dd32, "d_density")
+    lc.check(b["d_pred"], dp64, dp32, "d_pred")
 
 
 def test_forward_matches_the_data_and_render_buffers():
@@ -100,7 +64,7 @@ def test_forward_matches_the_data_and_render_buffers():
     launch-per-stage render's with analytic normals requested, at anneal 0.4."""
     n = 1000
     rc = common.make_rc()
-    rays, jit = _case(n, seed=11)
+    rays, jit = lc.cache_case(n, seed=11)
     rc.geometry_backward(rays, jit, 0.4, None, TERMS, grads=False)
     gt = np.full((n, 3), 0.5, np.float32)
     rc.data_backward(rays, gt, jit, 0.4, grads=False)
@@ -143,7 +107,7 @@ def test_whole_chain_against_oracle():
     pinned to h64^T d_pred and the column sums of d_pred, computed in fp64 from the call's own buffers."""
     rc = common.make_rc()
     n0 = 8192
-    rays, jit = _case(n0, seed=21)
+    rays, jit = lc.cache_case(n0, seed=21)
     rc.geometry_backward(rays, jit, 0.4, None, TERMS, grads=False)
     means = rc.workspace(f"g:means{L2}")[: 3 * n0 * S2].reshape(3, -1).T.copy()
     m = train_ref.relu_margin(common.weights_torch(dtype=torch.float64), CFG, L2, torch.from_numpy(means).double())
@@ -151,7 +115,7 @@ def test_whole_chain_against_oracle():
     assert len(keep) == 1200, len(keep)        # 38 400 samples: two chunks
     rays = {k: np.ascontiguousarray(v[keep]) for k, v in rays.items()}
     jit, n = [np.ascontiguousarray(j[keep]) for j in jit], len(keep)
-    lm = _lossmult(n, seed=23)
+    lm = lc.lossmult(n, seed=23)
     g, flats, _ = train.geometry_grads(rc, rays, jit, 1.0, lm)
     torch.cuda.synchronize()
     b = _buffers(rc, n)
@@ -169,7 +133,7 @@ def test_whole_chain_against_oracle():
         w = {k: v.clone().requires_grad_(True) for k, v in common.weights_torch(dtype=dt).items()}
         t = lambda a: torch.from_numpy(np.asarray(a)).to(dt)
         _oracle_chain(w, t(b["means"]).reshape(n, S2, 3), t(b["tdist"]), t(rays["directions"]), t(rays["viewdirs"]),
-                      t(b["normals"]), t(lm)).backward()
+                      t(b["normals_grad"]), t(lm)).backward()
         ref[dt] = {k: v.grad for k, v in w.items() if v.grad is not None}
     checked, tables = 0, 0
     for part in (f"MLP_{L2}", "Shader"):
@@ -193,24 +157,18 @@ def test_whole_chain_against_oracle():
     assert checked == len(rc.density_grad_layout(L2)[0]) + 2
 
 
-def _mlp_part(rc, flat, which):
-    layout = rc.density_grad_layout(L2)[0] if which == 0 else rc.shader_grad_layout()[0]
-    keep = [(o, int(np.prod(s))) for name, o, s in layout if "grid" not in name]
-    return torch.cat([flat[o:o + c] for o, c in keep])
-
-
 def test_semantics():
     rc = common.make_rc()
     n = 777
-    rays, jit = _case(n, seed=31)
-    lm = _lossmult(n, seed=32)
+    rays, jit = lc.cache_case(n, seed=31)
+    lm = lc.lossmult(n, seed=32)
     f1, l1 = rc.geometry_backward(rays, jit, 0.3, lm, TERMS)
     f1 = [f.clone() for f in f1]
     l1 = l1.clone()
     f2, l2 = rc.geometry_backward(rays, jit, 0.3, lm, TERMS)
     assert torch.equal(l1, l2)                                   # bitwise stable
     for i in range(2):
-        assert torch.equal(_mlp_part(rc, f1[i], i), _mlp_part(rc, f2[i], i))
+        assert torch.equal(lc.mlp_part(rc, f1[i], i), lc.mlp_part(rc, f2[i], i))
         assert float(f1[i].abs().max()) > 0
     # only pred_normals_layer of the shader layout is touched
     for name, off, shape in rc.shader_grad_layout()[0]:
@@ -219,7 +177,7 @@ def test_semantics():
     acc = [f.clone() for f in f1]                                # accumulates: a second call doubles
     rc.geometry_backward(rays, jit, 0.3, lm, TERMS, grads=acc)
     for i in range(2):
-        assert torch.equal(_mlp_part(rc, acc[i], i), 2 * _mlp_part(rc, f1[i], i))
+        assert torch.equal(lc.mlp_part(rc, acc[i], i), 2 * lc.mlp_part(rc, f1[i], i))
         ref = 2 * f1[i].cpu().numpy()
         np.testing.assert_allclose(acc[i].cpu().numpy(), ref, rtol=1e-5, atol=1e-6 * float(np.abs(ref).max()))
     fz, lz = rc.geometry_backward(rays, jit, 0.3, lm, TERMS, grads=False)   # NULL buffers: the losses only
@@ -273,7 +231,7 @@ def test_training_loop_reduces_the_loss():
     loss and the predicted-normal term fall."""
     rc = common.make_rc()
     n = 2048
-    rays, jit = _case(n, seed=41)
+    rays, jit = lc.cache_case(n, seed=41)
     target = rc_ext.RadianceCache(CFG, 0)
     target.load_weights(common.weights_np(seed=2))
     target.set_fused(False)
@@ -282,19 +240,13 @@ def test_training_loop_reduces_the_loss():
     layouts = {l: rc.density_grad_layout(l)[0] for l in range(CFG.num_levels)}
     layouts["shader"] = rc.shader_grad_layout()[0]
     names = {name for lay in layouts.values() for name, _, _ in lay}
-    params = {k: torch.from_numpy(v).cuda() for k, v in common.weights_np().items() if k in names}
-    assert len(params) == len(names)
-    opt = torch.optim.Adam(params.values(), lr=LOOP_LR)
-    total, pred = [], []
-    for step in range(LOOP_STEPS):
+
+    def grads():
         flats, losses = train.cache_stage_grads(rc, rays, gt, jit, 1.0)
-        total.append(float(sum(float(v) for v in losses.values())))
-        pred.append(float(losses["predicted_normals"]))
-        for key, lay in layouts.items():
-            for name, v in train.grads_as_dict(flats[key], lay).items():
-                params[name].grad = v.clone()
-        opt.step()
-        rc.load_weights(params)
+        record = (float(sum(float(v) for v in losses.values())), float(losses["predicted_normals"]))
+        return record, {name: v for key, lay in layouts.items() for name, v in train.grads_as_dict(flats[key], lay).items()}
+
+    total, pred = zip(*lc.adam_loop(rc, names, LOOP_LR, LOOP_STEPS, grads))
     assert min(pred[-3:]) < PRED_DROP * pred[0], (pred, total)
     assert min(total[-3:]) < LOOP_DROP * total[0], (total, pred)
 

@@ -23,6 +23,7 @@ import torch
 
 import common
 import interlevel_ref as ir
+import loss_cases as lc
 import nrc_amd
 from nrc_amd import rc_ext, train
 from nrc_amd.config import GridConfig
@@ -474,22 +475,10 @@ def test_interlevel_whole_chain_against_fp64(geom):
     S = [s for _, _, s in cfg.sampling_strategy]
     NP = cfg.num_levels - 1
     rc = handle(geom, smooth=True)
-
-    def buffers(n):
-        get = lambda name, shape: rc.workspace("i:" + name)[: int(np.prod(shape))].reshape(shape).copy()
-        sd = [get(f"sdist{l}", (n, S[l] + 1)) for l in range(NP + 1)]
-        td = [get(f"tdist{l}", (n, S[l] + 1)) for l in range(NP + 1)]
-        dens = [get(f"density{l}", (n, S[l])) for l in range(NP + 1)]
-        means = [get(f"means{l}", (3, n * S[l])).T.copy() for l in range(NP + 1)]
-        dd = [get(f"d_density{l}", (n, S[l])) for l in range(NP)]
-        return sd, td, dens, means, dd
-
     n0 = 1500
-    rays = nrc_amd.synthetic_rays(n0, seed=21).hot_fields()
-    rays = {k: v for k, v in rays.items() if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-    jit = [j.reshape(-1) for j in common.jitters(n0, seed=22)]
+    rays, jit = lc.cache_case(n0, seed=21)
     rc.interlevel_backward(rays, jit, 0.4, il.mults, il.blurs, levels=())
-    _, _, _, means, _ = buffers(n0)
+    _, _, _, means, _ = lc.interlevel_buffers(rc, n0)
     w64 = weights_t(geom, True)
     ok = np.ones(n0, bool)
     for l in range(NP):
@@ -502,7 +491,7 @@ def test_interlevel_whole_chain_against_fp64(geom):
     n = len(keep)
     g, _, losses = train.interlevel_grads(rc, rays, jit, 1.0)
     assert bool((losses > 0).all())
-    sd, td, dens, means, dd = buffers(n)
+    sd, td, dens, means, dd = lc.interlevel_buffers(rc, n)
     _, d64 = ir.interlevel_forward_backward(sd, td, dens, rays["directions"], np.ones(n), il.mults, il.blurs, torch.float64)
     for l in range(NP):
         r = d64[l].numpy()

@@ -8,6 +8,7 @@ import torch
 
 import common
 import interlevel_ref as ir
+import loss_cases as lc
 import nrc_amd
 from nrc_amd import train
 from oracle import train_ref
@@ -20,55 +21,25 @@ NP = CFG.num_levels - 1
 pytestmark = pytest.mark.gpu
 
 
-def _case(n, seed=5):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rays = {k: v for k, v in rays.items() if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-    jit = [j.reshape(-1) for j in common.jitters(n, seed=seed + 1)]
-    return rays, jit
-
-
-def _lossmult(n, seed=9):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
-    lm[::7] = 0.0
-    return lm
-
-
-def _buffers(rc, n):
-    """The sampler levels' sdist / tdist / density / means as the call left them."""
-    g = lambda name, shape: rc.workspace("i:" + name)[: int(np.prod(shape))].reshape(shape).copy()
-    sd = [g(f"sdist{l}", (n, S[l] + 1)) for l in range(NP + 1)]
-    td = [g(f"tdist{l}", (n, S[l] + 1)) for l in range(NP + 1)]
-    dens = [g(f"density{l}", (n, S[l])) for l in range(NP + 1)]
-    means = [g(f"means{l}", (3, n * S[l])).T.copy() for l in range(NP + 1)]
-    dd = [g(f"d_density{l}", (n, S[l])) for l in range(NP)]
-    return sd, td, dens, means, dd
-
-
-def _bound(got, ref64, ref32, floor):
-    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
-    return err, 3.0 * err32 + floor
-
-
 def test_kernel_against_restatement():
     """Losses and d loss / d density within 3x the fp32 restatement's distance from fp64, on the HIP forward's buffers."""
     rc = common.make_rc()
     n = 1000
-    rays, jit = _case(n)
-    lm = _lossmult(n)
+    rays, jit = lc.cache_case(n)
+    lm = lc.lossmult(n)
     _, losses = rc.interlevel_backward(rays, jit, 0.4, IL.mults, IL.blurs, lossmult=lm, levels=())
     losses = losses.cpu().numpy()
-    sd, td, dens, _, dd = _buffers(rc, n)
+    sd, td, dens, _, dd = lc.interlevel_buffers(rc, n)
     args = (sd, td, dens, rays["directions"], lm, IL.mults, IL.blurs)
     l64, g64 = ir.interlevel_forward_backward(*args, torch.float64)
     l32, g32 = ir.interlevel_forward_backward(*args, torch.float32)
     for l in range(NP):
         assert l64[l] > 0
-        err, tol = _bound(np.float64(losses[l]), l64[l], l32[l], 1e-6 * l64[l])
+        err, tol = lc.bound(np.float64(losses[l]), l64[l], l32[l], 1e-6 * l64[l])
         assert err <= tol, ("loss", l, losses[l], l64[l], l32[l])
         r64, r32 = g64[l].numpy(), g32[l].double().numpy()
         scale = float(np.abs(r64).max())
-        err, tol = _bound(dd[l].astype(np.float64), r64, r32, 1e-6 * scale)
+        err, tol = lc.bound(dd[l].astype(np.float64), r64, r32, 1e-6 * scale)
         assert err <= tol, ("d_density", l, err, tol, scale)
         assert np.all(dd[l][lm == 0.0] == 0.0)          # lossmult 0: no gradient
 
@@ -77,7 +48,7 @@ def test_forward_matches_the_render_workspace():
     """The training forward's per-level buffers are bitwise those of a launch-per-stage render at anneal 0.4, on the
     per-stage (1000 rays) and the per-ray level-kernel (>= 24 576 rays) forms of the plan."""
     for n in (1000, 24577):
-        rays, jit = _case(n, seed=11)
+        rays, jit = lc.cache_case(n, seed=11)
         rc = common.make_rc()
         rc.interlevel_backward(rays, jit, 0.4, IL.mults, IL.blurs, levels=())
         torch.cuda.synchronize()
@@ -97,9 +68,9 @@ def test_whole_chain_against_oracle():
     the fp64 restatement.  Rays whose samples sit within 3e-5 of a ReLU kink (where fp32 and fp64 may take different
     sides) are left out: each ray's forward is independent of the others, so the subset's buffers are the same bits."""
     rc = common.make_rc()
-    rays, jit = _case(1500, seed=21)
+    rays, jit = lc.cache_case(1500, seed=21)
     rc.interlevel_backward(rays, jit, 0.4, IL.mults, IL.blurs, levels=())
-    _, _, _, means, _ = _buffers(rc, 1500)
+    _, _, _, means, _ = lc.interlevel_buffers(rc, 1500)
     w64 = common.weights_torch(dtype=torch.float64)
     ok = np.ones(1500, bool)
     for l in range(NP):
@@ -111,7 +82,7 @@ def test_whole_chain_against_oracle():
     jit = [np.ascontiguousarray(j[keep]) for j in jit]
     n = len(keep)
     g, flats, _ = train.interlevel_grads(rc, rays, jit, 1.0)
-    sd, td, dens, means, dd = _buffers(rc, n)
+    sd, td, dens, means, dd = lc.interlevel_buffers(rc, n)
     _, d64 = ir.interlevel_forward_backward(sd, td, dens, rays["directions"], np.ones(n), IL.mults, IL.blurs, torch.float64)
     for l in range(NP):
         # a sample whose upstream is exactly 0 on one side (every term at and behind it truncated by max(0, .)) may carry
@@ -143,8 +114,8 @@ def _mlp_offset(rc, level):
 def test_semantics():
     rc = common.make_rc()
     n = 777
-    rays, jit = _case(n, seed=31)
-    lm = _lossmult(n, seed=32)
+    rays, jit = lc.cache_case(n, seed=31)
+    lm = lc.lossmult(n, seed=32)
     f1, l1 = rc.interlevel_backward(rays, jit, 0.3, IL.mults, IL.blurs, lossmult=lm)
     f1 = [f.clone() for f in f1]
     l1 = l1.clone()
@@ -199,7 +170,7 @@ def test_semantics():
 def test_bad_arguments():
     rc = common.make_rc()
     n = 64
-    rays, _ = _case(n)
+    rays, _ = lc.cache_case(n)
     r, held, _ = rc._rays_struct(rays)
     lib = rc.lib
     losses = torch.zeros(NP, device="cuda")
@@ -222,20 +193,14 @@ def test_training_loop_reduces_the_loss():
     """Adam on the parameters of MLP_0 / MLP_1 driven by interlevel_grads + load_weights on a fixed 4096-ray batch."""
     rc = common.make_rc()
     n = 4096
-    rays, jit = _case(n, seed=41)
+    rays, jit = lc.cache_case(n, seed=41)
     names = [name for l in range(NP) for name, _, _ in rc.density_grad_layout(l)[0]]
-    params = {k: torch.from_numpy(v).cuda() for k, v in common.weights_np().items() if k in names}
-    assert len(params) == len(names)
-    opt = torch.optim.Adam(params.values(), lr=LOOP_LR)
-    hist = []
-    for step in range(LOOP_STEPS):
+
+    def grads():
         g, _, losses = train.interlevel_grads(rc, rays, jit, 1.0)
-        hist.append(float(losses.sum()))
-        for l in range(NP):
-            for name, v in g[l].items():
-                params[name].grad = v.clone()
-        opt.step()
-        rc.load_weights(params)
+        return float(losses.sum()), {name: v for l in range(NP) for name, v in g[l].items()}
+
+    hist = lc.adam_loop(rc, names, LOOP_LR, LOOP_STEPS, grads)
     assert min(hist[-3:]) < LOOP_DROP * hist[0], hist
 
 

@@ -2,7 +2,6 @@
 and the whole chain against the fp64 torch restatement (tests/light_sampling_ref.py), call semantics, the regularizer, the
 light-layout refresh and a training loop."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -10,9 +9,9 @@ import torch
 
 import common
 import light_sampling_ref as lr
+import loss_cases as lc
 import nrc_amd
 from nrc_amd import config, rc_ext, train
-from oracle import material_ref
 
 CFG = nrc_amd.hotdog_config()
 RC_ERR_UNSUPPORTED, RC_ERR_MISSING_WEIGHT = -5, -3
@@ -21,26 +20,9 @@ FWD = ("m_pts", "m_nrm", "l_vmf", "l_vmf_logit", "sec_dirs", "sec_samples", "sec
 pytestmark = pytest.mark.gpu
 
 
-def _rc(weights=None):
-    return common.make_rc(weights=weights if weights is not None else common.weights_material_np())
-
-
-def _case(n, K=8, seed=3):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rnd = material_ref.draw_randoms(dataclasses.replace(CFG, num_secondary_samples=K), n, seed=seed + 1)
-    return rays, rnd
-
-
 def _split(K):
     Kd = int(round(K * CFG.diffuse_sample_fraction))
     return K - Kd, Kd
-
-
-def _lossmult(n, seed=9):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
-    lm[::7] = 0.0
-    return lm
 
 
 def _fwd(rc, n, K):
@@ -53,12 +35,12 @@ def _fwd(rc, n, K):
 
 @pytest.mark.parametrize("K", [8, 32])
 def test_forward_is_bitwise_render_material(K):
-    rc = _rc()
+    rc = lc.make_material_rc()
     n = 1500
-    rays, rnd = _case(n, K)
+    rays, rnd = lc.material_case(n, K)
     rc.render_material(rays, rnd, K)
     want = _fwd(rc, n, K)
-    rc.light_sampling_backward(rays, rnd, K, lossmult=_lossmult(n))
+    rc.light_sampling_backward(rays, rnd, K, lossmult=lc.lossmult(n))
     got = _fwd(rc, n, K)
     for k in FWD:
         assert np.array_equal(want[k].view(np.uint32), got[k].view(np.uint32)), k
@@ -76,34 +58,28 @@ def _restated(rc, n, K, rnd, lm, dtype):
     return float(loss), g.reshape(n, 640).numpy()
 
 
-def _check(got, ref64, ref32, what, rel_floor=1e-6):
-    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
-    bound = 3.0 * err32 + rel_floor * float(np.abs(ref64).max()) + 1e-12
-    assert err <= bound, (what, err, err32, bound)
-
-
 def test_loss_kernel_against_restatement():
     """The loss and d loss / d vmf_params on the forward's own buffers, within 3x the fp32 restatement's distance from
     fp64 (plus a 1e-6 relative floor)."""
-    rc = _rc()
+    rc = lc.make_material_rc()
     n, K = 1024, 8
-    rays, rnd = _case(n, K, seed=11)
-    lm = _lossmult(n)
+    rays, rnd = lc.material_case(n, K, seed=11)
+    lm = lc.lossmult(n)
     _, loss = rc.light_sampling_backward(rays, rnd, K, lossmult=lm)
     torch.cuda.synchronize()
     dvp = rc.workspace("ls:dvp")[: 640 * n].reshape(n, 640)
     l64, g64 = _restated(rc, n, K, rnd, lm, torch.float64)
     l32, g32 = _restated(rc, n, K, rnd, lm, torch.float32)
     assert l64 > 0 and float(np.abs(g64).max()) > 0
-    _check(np.array([float(loss[0])]), np.array([l64]), np.array([l32]), "loss")
-    _check(dvp, g64, g32, "d vmf_params")
+    lc.check(np.array([float(loss[0])]), np.array([l64]), np.array([l32]), "loss")
+    lc.check(dvp, g64, g32, "d vmf_params")
 
 
 def test_whole_chain_against_fp64_autograd():
-    rc = _rc()
+    rc = lc.make_material_rc()
     n, K = 512, 8
-    rays, rnd = _case(n, K, seed=21)
-    lm = _lossmult(n, seed=22)
+    rays, rnd = lc.material_case(n, K, seed=21)
+    lm = lc.lossmult(n, seed=22)
     flat, _ = rc.light_sampling_backward(rays, rnd, K, lossmult=lm)
     torch.cuda.synchronize()
     layout, total = rc.light_grad_layout()
@@ -127,15 +103,15 @@ def test_whole_chain_against_fp64_autograd():
         size = int(np.prod(shape))
         g64 = refs[torch.float64][name].reshape(-1)
         g32 = refs[torch.float32][name].reshape(-1)
-        _check(got[off: off + size], g64, g32, name)
+        lc.check(got[off: off + size], g64, g32, name)
     assert float(np.abs(got).max()) > 0
 
 
 def test_semantics():
-    rc = _rc()
+    rc = lc.make_material_rc()
     n, K = 777, 8
-    rays, rnd = _case(n, K, seed=31)
-    lm = _lossmult(n, seed=32)
+    rays, rnd = lc.material_case(n, K, seed=31)
+    lm = lc.lossmult(n, seed=32)
     layout, total = rc.light_grad_layout()
     dense0 = [off for name, off, _ in layout if name.endswith("layers_0/kernel")][0]
     f1, l1 = rc.light_sampling_backward(rays, rnd, K, lossmult=lm)
@@ -187,7 +163,7 @@ def test_semantics():
 
 
 def test_regularizer_against_numpy():
-    rc = _rc()
+    rc = lc.make_material_rc()
     w = common.weights_material_np()
     layout, total = rc.light_grad_layout()
     flat, loss = rc.light_regularizer(0.7)
@@ -205,31 +181,12 @@ def test_regularizer_against_numpy():
     assert float(loss[0]) == pytest.approx(0.7 * want, rel=1e-6)
 
 
-def _perturbed_light(seed=5):
-    w = dict(common.weights_material_np())
-    rng = np.random.Generator(np.random.PCG64(seed))
-    for k in list(w):
-        if "LightSampler" in k:
-            w[k] = (np.asarray(w[k]) * (1.0 + 0.05 * rng.standard_normal(np.shape(w[k])))).astype(np.float32)
-    return w
-
-
-def _material_render(rc, n=1024, K=8):
-    rays, rnd = _case(n, K, seed=51)
-    cres, mres = rc.render_material(rays, rnd, K)
-    return {**{"c_" + k: v.clone() for k, v in cres.items()}, **{"m_" + k: v.clone() for k, v in mres.items()}}
-
-
 def test_load_params_flat_light_renders_as_load_weights():
-    w2 = _perturbed_light()
-    a = _rc(w2)
-    b = _rc()
-    layout, total = b.light_grad_layout()
-    flat = torch.empty(total, dtype=torch.float32, device="cuda")
-    for name, off, shape in layout:
-        flat[off: off + int(np.prod(shape))] = torch.from_numpy(np.ascontiguousarray(w2[name], np.float32)).reshape(-1)
-    b.load_params_flat("light", flat)
-    ra, rb = _material_render(a), _material_render(b)
+    w2 = lc.perturbed(common.weights_material_np(), "LightSampler", 5)
+    a = lc.make_material_rc(w2)
+    b = lc.make_material_rc()
+    b.load_params_flat("light", lc.flat_from_layout(*b.light_grad_layout(), w2))
+    ra, rb = lc.material_render(a, 8), lc.material_render(b, 8)
     for k in ra:
         assert torch.equal(ra[k], rb[k]), k
 
@@ -238,30 +195,15 @@ START, LOOP_STEPS = 2500, 40
 
 
 def test_training_loop_lowers_the_loss_and_resumes():
-    rc = _rc()
+    rc = lc.make_material_rc()
     opt = train.LightSamplerOptimizer(rc)
     opt.init_from(common.weights_material_np(), count=START)
     n = 2048
-    rays, rnd = _case(n, 8, seed=61)
+    rays, rnd = lc.material_case(n, 8, seed=61)
     cfg = config.LightSamplingConfig()
-    totals = []
-    for i in range(LOOP_STEPS):
-        if i == LOOP_STEPS - 2:
-            sd, r_sd = opt.state_dict(), _material_render(rc)
-        losses = train.light_sampler_step(rc, opt, rays, rnd, cfg=cfg)
-        totals.append(float(losses["light_sampling"]))
-    print("light_sampler_step loop:", [round(t, 6) for t in totals])
-    assert opt.count == START + LOOP_STEPS
-    assert all(np.isfinite(totals))
-    assert min(totals[-3:]) < totals[0], totals
+    step = lambda: train.light_sampler_step(rc, opt, rays, rnd, cfg=cfg)
+    # the state two steps back is resumed: the handle renders bitwise what it rendered then, and the run goes on
+    lc.step_loop(step, lambda losses: float(losses["light_sampling"]), opt, START, LOOP_STEPS,
+                 lambda totals: min(totals[-3:]) < totals[0], "light_sampler_step loop:", lambda t: round(t, 6),
+                 render=lambda: lc.material_render(rc, 8))
     assert {train.param_group(k) for k in opt.names()} == {"LightSampler"}
-    # resume from the state two steps back: the handle renders bitwise what it rendered then, and the run goes on
-    opt.load_state_dict(sd)
-    assert opt.count == START + LOOP_STEPS - 2
-    r_again = _material_render(rc)
-    for k in r_sd:
-        assert torch.equal(r_sd[k], r_again[k]), k
-    for _ in range(2):
-        losses = train.light_sampler_step(rc, opt, rays, rnd, cfg=cfg)
-    assert opt.count == START + LOOP_STEPS
-    assert float(losses["light_sampling"]) == pytest.approx(totals[-1], rel=1e-3)

@@ -9,11 +9,11 @@ import pytest
 import torch
 
 import common
+import loss_cases as lc
 import material_data_loss_ref as md
 import material_smoothness_ref as ms
 import nrc_amd
 from nrc_amd import config, rc_ext, train
-from oracle import material_ref
 
 CFG = nrc_amd.hotdog_config()
 RC_ERR_INVALID_ARG, RC_ERR_UNSUPPORTED, RC_ERR_MISSING_WEIGHT = -1, -5, -3
@@ -21,23 +21,8 @@ RC_ERR_INVALID_ARG, RC_ERR_UNSUPPORTED, RC_ERR_MISSING_WEIGHT = -1, -5, -3
 pytestmark = pytest.mark.gpu
 
 
-def _rc(weights=None):
-    return common.make_rc(weights=weights if weights is not None else common.weights_material_np())
-
-
 def _case(n, K=8, seed=3):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rnd = material_ref.draw_randoms(dataclasses.replace(CFG, num_secondary_samples=K), n, seed=seed + 1)
-    rng = np.random.Generator(np.random.PCG64(seed + 2))
-    gt = rng.uniform(0.0, 1.0, size=(n, 3)).astype(np.float32)
-    return rays, rnd, gt
-
-
-def _lossmult(n, seed=9):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
-    lm[::7] = 0.0
-    return lm
+    return (*lc.material_case(n, K, seed), lc.uniform_gt(n, seed + 2))
 
 
 def _fwd(rc, n, K):
@@ -49,7 +34,7 @@ def _fwd(rc, n, K):
 
 @pytest.mark.parametrize("K", [8, 32])
 def test_forward_is_bitwise_render_material(K):
-    rc = _rc()
+    rc = lc.make_material_rc()
     n = 1500
     rays, rnd, gt = _case(n, K)
     cres, mres = rc.render_material(rays, rnd, num_secondary_samples=K)
@@ -58,19 +43,13 @@ def test_forward_is_bitwise_render_material(K):
     want_rgb = mres["rgb"].cpu().numpy().reshape(-1)
     want_crgb = cres["rgb"].cpu().numpy().reshape(-1)
     cfg = dataclasses.replace(config.MaterialDataLossConfig(), num_secondary_samples=K)
-    rc.material_data_backward(rays, rnd, gt, K, lossmult=_lossmult(n), cfg=cfg)
+    rc.material_data_backward(rays, rnd, gt, K, lossmult=lc.lossmult(n), cfg=cfg)
     torch.cuda.synchronize()
     got = _fwd(rc, n, K)
     for k in want:
         assert np.array_equal(want[k].view(np.uint32), got[k].view(np.uint32)), k
     assert np.array_equal(rc.workspace("md:rgb")[: 3 * n].view(np.uint32), want_rgb.view(np.uint32))
     assert np.array_equal(rc.workspace("md:cache_rgb")[: 3 * n].view(np.uint32), want_crgb.view(np.uint32))
-
-
-def _check(got, ref64, ref32, what, rel_floor=1e-6):
-    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
-    bound = 3.0 * err32 + rel_floor * float(np.abs(ref64).max()) + 1e-12
-    assert err <= bound, (what, err, err32, bound)
 
 
 def _trace_tensors(rc, n, K, dt):
@@ -87,9 +66,9 @@ def test_loss_and_every_tensor_against_fp64_autograd(n):
     """At the call's own shading points and trace: the loss and every tensor of the material layout within 3x the fp32
     restatement's distance from fp64 (plus a 1e-6 relative floor)."""
     K = 8
-    rc = _rc()
+    rc = lc.make_material_rc()
     rays, rnd, gt = _case(n, K, seed=21)
-    lm = _lossmult(n, seed=22)
+    lm = lc.lossmult(n, seed=22)
     cres, mres = rc.render_material(rays, rnd, num_secondary_samples=K)
     S = CFG.sampling_strategy[-1][2]
     acc_p = rc.workspace("weights2")[: n * S].reshape(n, S).sum(-1)
@@ -113,19 +92,19 @@ def test_loss_and_every_tensor_against_fp64_autograd(n):
         refs[dt] = {k: (np.zeros(v.shape) if g is None else g.detach().double().numpy()) for (k, v), g in zip(w.items(), gs)}
         losses[dt] = float(ls)
     assert losses[torch.float64] > 0
-    _check(np.array([float(loss[0])]), np.array([losses[torch.float64]]), np.array([losses[torch.float32]]), "loss")
+    lc.check(np.array([float(loss[0])]), np.array([losses[torch.float64]]), np.array([losses[torch.float32]]), "loss")
     for name, off, shape in layout:
         size = int(np.prod(shape))
-        _check(got[off: off + size], refs[torch.float64][name].reshape(-1), refs[torch.float32][name].reshape(-1), name)
+        lc.check(got[off: off + size], refs[torch.float64][name].reshape(-1), refs[torch.float32][name].reshape(-1), name)
     assert float(np.abs(got).max()) > 0
 
 
 def test_semantics():
     K = 8
-    rc = _rc()
+    rc = lc.make_material_rc()
     n = 777
     rays, rnd, gt = _case(n, K, seed=31)
-    lm = _lossmult(n, seed=32)
+    lm = lc.lossmult(n, seed=32)
     layout, total = rc.material_grad_layout()
     dense0 = [off for name, off, _ in layout if name.endswith("bottleneck_layer/kernel")][0]
     f1, l1 = rc.material_data_backward(rays, rnd, gt, K, lossmult=lm)
@@ -187,38 +166,20 @@ def test_semantics():
 LOOP_STEPS = 40
 
 
-def _material_render(rc, n=1024):
-    rays, rnd, _ = _case(n, 8, seed=51)
-    cres, mres = rc.render_material(rays, rnd, num_secondary_samples=8)
-    return {**{"c_" + k: v.clone() for k, v in cres.items()}, **{"m_" + k: v.clone() for k, v in mres.items()}}
-
-
 def test_material_stage_loop_lowers_the_data_loss_and_resumes():
     """material_stage_step (data + smoothness + regularizer) on a fixed batch, at the material-stage schedule of the
     MaterialShader group (OptimizerConfig(material=True))."""
-    rc = _rc()
+    rc = lc.make_material_rc()
     opt = train.MaterialOptimizer(rc, config.OptimizerConfig(material=True))
     opt.init_from(common.weights_material_np(), count=0)
     n = 2048
     rays, rnd, gt = _case(n, 8, seed=61)
-    noise = np.random.Generator(np.random.PCG64(62)).standard_normal((n, 3)).astype(np.float32)
-    totals = []
-    for i in range(LOOP_STEPS):
-        if i == LOOP_STEPS - 2:
-            sd, r_sd = opt.state_dict(), _material_render(rc)
-        losses = train.material_stage_step(rc, opt, rays, rnd, gt, noise)
+    noise = lc.normal_noise(n, 62)
+
+    def each(losses):
         assert set(losses) == {"data", "material_smoothness", "regularizer/material_grid", "material_ray_sampler"}
-        totals.append(float(losses["data"]))
-    print("material_stage_step loop (data):", [f"{t:.6e}" for t in totals])
-    assert opt.count == LOOP_STEPS
-    assert all(np.isfinite(totals))
-    assert min(totals[-3:]) < 0.9 * totals[0], totals
-    opt.load_state_dict(sd)
-    assert opt.count == LOOP_STEPS - 2
-    r_again = _material_render(rc)
-    for k in r_sd:
-        assert torch.equal(r_sd[k], r_again[k]), k
-    for _ in range(2):
-        losses = train.material_stage_step(rc, opt, rays, rnd, gt, noise)
-    assert opt.count == LOOP_STEPS
-    assert float(losses["data"]) == pytest.approx(totals[-1], rel=1e-3)
+
+    step = lambda: train.material_stage_step(rc, opt, rays, rnd, gt, noise)
+    lc.step_loop(step, lambda losses: float(losses["data"]), opt, 0, LOOP_STEPS,
+                 lambda totals: min(totals[-3:]) < 0.9 * totals[0], "material_stage_step loop (data):",
+                 lambda t: f"{t:.6e}", each=each, render=lambda: lc.material_render(rc, 8))

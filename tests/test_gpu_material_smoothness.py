@@ -8,10 +8,10 @@ import pytest
 import torch
 
 import common
+import loss_cases as lc
 import material_smoothness_ref as mr
 import nrc_amd
 from nrc_amd import config, rc_ext, train
-from oracle import material_ref
 
 CFG = nrc_amd.hotdog_config()
 RC_ERR_INVALID_ARG, RC_ERR_UNSUPPORTED, RC_ERR_MISSING_WEIGHT = -1, -5, -3
@@ -19,23 +19,8 @@ RC_ERR_INVALID_ARG, RC_ERR_UNSUPPORTED, RC_ERR_MISSING_WEIGHT = -1, -5, -3
 pytestmark = pytest.mark.gpu
 
 
-def _rc(weights=None):
-    return common.make_rc(weights=weights if weights is not None else common.weights_material_np())
-
-
 def _case(n, seed=3):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rnd = material_ref.draw_randoms(CFG, n, seed=seed + 1)
-    rng = np.random.Generator(np.random.PCG64(seed + 2))
-    noise = rng.standard_normal((n, 3)).astype(np.float32)
-    return rays, rnd, noise
-
-
-def _lossmult(n, seed=9):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    lm = rng.uniform(0.5, 2.0, size=n).astype(np.float32)
-    lm[::7] = 0.0
-    return lm
+    return (*lc.material_case(n, seed=seed), lc.normal_noise(n, seed + 2))
 
 
 def _fwd(rc, n):
@@ -44,12 +29,12 @@ def _fwd(rc, n):
 
 
 def test_forward_is_bitwise_render_material():
-    rc = _rc()
+    rc = lc.make_material_rc()
     n = 1500
     rays, rnd, noise = _case(n)
     rc.render_material(rays, rnd)
     want = _fwd(rc, n)
-    rc.material_smoothness_backward(rays, rnd, noise, lossmult=_lossmult(n))
+    rc.material_smoothness_backward(rays, rnd, noise, lossmult=lc.lossmult(n))
     got = _fwd(rc, n)
     for k in want:
         assert np.array_equal(want[k].view(np.uint32), got[k].view(np.uint32)), k
@@ -58,19 +43,13 @@ def test_forward_is_bitwise_render_material():
     assert np.array_equal(pts[1], want["m_pts"].reshape(n, 3) + noise * np.float32(0.01))
 
 
-def _check(got, ref64, ref32, what, rel_floor=1e-6):
-    err, err32 = float(np.abs(got - ref64).max()), float(np.abs(ref32 - ref64).max())
-    bound = 3.0 * err32 + rel_floor * float(np.abs(ref64).max()) + 1e-12
-    assert err <= bound, (what, err, err32, bound)
-
-
 @pytest.mark.parametrize("n", [512, 3001])
 def test_loss_and_every_tensor_against_fp64_autograd(n):
     """At the call's own shading points (m_pts, x' from "ms:pts", filt_weight): the loss and every tensor of the material
     layout within 3x the fp32 restatement's distance from fp64 (plus a 1e-6 relative floor)."""
-    rc = _rc()
+    rc = lc.make_material_rc()
     rays, rnd, noise = _case(n, seed=21)
-    lm = _lossmult(n, seed=22)
+    lm = lc.lossmult(n, seed=22)
     flat, loss = rc.material_smoothness_backward(rays, rnd, noise, lossmult=lm)
     torch.cuda.synchronize()
     layout, total = rc.material_grad_layout()
@@ -92,30 +71,30 @@ def test_loss_and_every_tensor_against_fp64_autograd(n):
             split = lambda m: (t(m[:, :3]), t(m[:, 3]), t(m[:, 4]))
             lk = float(mr.smoothness_loss(split(mats[0]), split(mats[1]), t(lm) * t(fw)))
     assert losses[torch.float64] > 0
-    _check(np.array([float(loss[0])]), np.array([losses[torch.float64]]), np.array([losses[torch.float32]]), "loss")
+    lc.check(np.array([float(loss[0])]), np.array([losses[torch.float64]]), np.array([losses[torch.float32]]), "loss")
     assert float(loss[0]) == pytest.approx(lk, rel=1e-5)
     for name, off, shape in layout:
         size = int(np.prod(shape))
         g64 = refs[torch.float64][name].reshape(-1)
         g32 = refs[torch.float32][name].reshape(-1)
-        _check(got[off: off + size], g64, g32, name)
+        lc.check(got[off: off + size], g64, g32, name)
     assert float(np.abs(got).max()) > 0
 
 
 def test_zero_noise_gives_zero_loss():
-    rc = _rc()
+    rc = lc.make_material_rc()
     n = 999
     rays, rnd, _ = _case(n, seed=25)
-    _, loss = rc.material_smoothness_backward(rays, rnd, np.zeros((n, 3), np.float32), lossmult=_lossmult(n))
+    _, loss = rc.material_smoothness_backward(rays, rnd, np.zeros((n, 3), np.float32), lossmult=lc.lossmult(n))
     assert float(loss[0]) == 0.0
     assert np.array_equal(rc.workspace("m_mat")[: 5 * n], rc.workspace("ms:mat_p")[: 5 * n])
 
 
 def test_semantics():
-    rc = _rc()
+    rc = lc.make_material_rc()
     n = 777
     rays, rnd, noise = _case(n, seed=31)
-    lm = _lossmult(n, seed=32)
+    lm = lc.lossmult(n, seed=32)
     layout, total = rc.material_grad_layout()
     dense0 = [off for name, off, _ in layout if name.endswith("bottleneck_layer/kernel")][0]
     f1, l1 = rc.material_smoothness_backward(rays, rnd, noise, lossmult=lm)
@@ -175,7 +154,7 @@ def test_semantics():
 
 
 def test_regularizer_against_numpy():
-    rc = _rc()
+    rc = lc.make_material_rc()
     w = common.weights_material_np()
     layout, total = rc.material_grad_layout()
     flat, loss = rc.material_regularizer(0.7)
@@ -193,31 +172,12 @@ def test_regularizer_against_numpy():
     assert float(loss[0]) == pytest.approx(0.7 * want, rel=1e-6)
 
 
-def _perturbed_material(seed=5):
-    w = dict(common.weights_material_np())
-    rng = np.random.Generator(np.random.PCG64(seed))
-    for k in list(w):
-        if "MaterialShader" in k:
-            w[k] = (np.asarray(w[k]) * (1.0 + 0.05 * rng.standard_normal(np.shape(w[k])))).astype(np.float32)
-    return w
-
-
-def _material_render(rc, n=1024):
-    rays, rnd, _ = _case(n, seed=51)
-    cres, mres = rc.render_material(rays, rnd)
-    return {**{"c_" + k: v.clone() for k, v in cres.items()}, **{"m_" + k: v.clone() for k, v in mres.items()}}
-
-
 def test_load_params_flat_material_renders_as_load_weights():
-    w2 = _perturbed_material()
-    a = _rc(w2)
-    b = _rc()
-    layout, total = b.material_grad_layout()
-    flat = torch.empty(total, dtype=torch.float32, device="cuda")
-    for name, off, shape in layout:
-        flat[off: off + int(np.prod(shape))] = torch.from_numpy(np.ascontiguousarray(w2[name], np.float32)).reshape(-1)
-    b.load_params_flat("material", flat)
-    ra, rb = _material_render(a), _material_render(b)
+    w2 = lc.perturbed(common.weights_material_np(), "MaterialShader", 5)
+    a = lc.make_material_rc(w2)
+    b = lc.make_material_rc()
+    b.load_params_flat("material", lc.flat_from_layout(*b.material_grad_layout(), w2))
+    ra, rb = lc.material_render(a), lc.material_render(b)
     for k in ra:
         assert torch.equal(ra[k], rb[k]), k
 
@@ -229,32 +189,20 @@ def test_training_loop_lowers_the_loss_and_resumes():
     """material_step on a fixed batch.  The learning rate is the test's choice: the material-stage schedule of the
     MaterialShader group (OptimizerConfig(material=True): 0.002, no delay), not the cache stage's 5e-4 behind a
     2 500-step delay, so that 40 steps move the loss."""
-    rc = _rc()
+    rc = lc.make_material_rc()
     opt = train.MaterialOptimizer(rc, config.OptimizerConfig(material=True))
     opt.init_from(common.weights_material_np(), count=0)
     n = 2048
     rays, rnd, noise = _case(n, seed=61)
     cfg = config.MaterialSmoothnessConfig()
-    totals = []
-    for i in range(LOOP_STEPS):
-        if i == LOOP_STEPS - 2:
-            sd, r_sd = opt.state_dict(), _material_render(rc)
-        losses = train.material_step(rc, opt, rays, rnd, noise, cfg=cfg)
+
+    def each(losses):
         assert set(losses) == {"material_smoothness", "regularizer/material_grid", "material_ray_sampler"}
         assert float(losses["material_ray_sampler"]) == 0.0
-        totals.append(float(losses["material_smoothness"]))
-    print("material_step loop:", [f"{t:.6e}" for t in totals])
-    assert opt.count == LOOP_STEPS
-    assert all(np.isfinite(totals))
-    assert min(totals[-3:]) < totals[0], totals
+
+    step = lambda: train.material_step(rc, opt, rays, rnd, noise, cfg=cfg)
+    # the state two steps back is resumed: the handle renders bitwise what it rendered then, and the run goes on
+    lc.step_loop(step, lambda losses: float(losses["material_smoothness"]), opt, 0, LOOP_STEPS,
+                 lambda totals: min(totals[-3:]) < totals[0], "material_step loop:", lambda t: f"{t:.6e}",
+                 each=each, render=lambda: lc.material_render(rc))
     assert {train.param_group(k) for k in opt.names()} == {"MaterialShader"}
-    # resume from the state two steps back: the handle renders bitwise what it rendered then, and the run goes on
-    opt.load_state_dict(sd)
-    assert opt.count == LOOP_STEPS - 2
-    r_again = _material_render(rc)
-    for k in r_sd:
-        assert torch.equal(r_sd[k], r_again[k]), k
-    for _ in range(2):
-        losses = train.material_step(rc, opt, rays, rnd, noise, cfg=cfg)
-    assert opt.count == LOOP_STEPS
-    assert float(losses["material_smoothness"]) == pytest.approx(totals[-1], rel=1e-3)

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import common
+import loss_cases as lc
 import optimizer_ref as ref
 import nrc_amd
 from nrc_amd import checkpoint, rc_ext, train
@@ -16,13 +17,6 @@ CFG = nrc_amd.hotdog_config()
 pytestmark = pytest.mark.gpu
 
 START = 2500          # past the learning-rate delay: steps of a visible size
-
-
-def _case(n, seed=5):
-    rays = nrc_amd.synthetic_rays(n, seed=seed).hot_fields()
-    rays = {k: v for k, v in rays.items() if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-    jit = [j.reshape(-1) for j in common.jitters(n, seed=seed + 1)]
-    return rays, jit
 
 
 def _groups(opt, k):
@@ -118,7 +112,8 @@ def test_norm_clip_against_fp64_and_reproducible():
         assert np.array_equal(opt.params[k].cpu().numpy().view(np.uint32), want.view(np.uint32)), k
 
 
-def _perturbed(seed=3):
+def _moved_cache_weights(seed=3):
+    """Every cache-stage parameter scaled by 1.05 plus 0.01 N(0, 1): its own draw, not loss_cases.perturbed's."""
     w = dict(common.weights_np())
     rng = np.random.default_rng(seed)
     names = set()
@@ -132,7 +127,7 @@ def _perturbed(seed=3):
 
 
 def _renders(rc, n=512):
-    rays, jit = _case(n, seed=31)
+    rays, jit = lc.cache_case(n, seed=31)
     srays, srnd = common.secondary_case(n, seed=12)
     g = np.random.default_rng(4).gumbel(size=(n, 32)).astype(np.float32)
     out = {}
@@ -154,7 +149,7 @@ def _renders(rc, n=512):
 
 
 def test_load_params_flat_renders_as_load_weights():
-    new = _perturbed()
+    new = _moved_cache_weights()
     a = common.make_rc()
     a.load_weights(new)
     want = _renders(a)
@@ -181,7 +176,7 @@ def test_load_params_flat_renders_as_load_weights():
 
 def _record_grads(weights, n=2048, seed=41):
     rc = common.make_rc(weights=weights)
-    rays, jit = _case(n, seed=seed)
+    rays, jit = lc.cache_case(n, seed=seed)
     target = rc_ext.RadianceCache(CFG, 0)
     target.load_weights(common.weights_np(seed=2))
     target.set_fused(False)
@@ -231,19 +226,15 @@ def test_step_against_torch_adam_and_load_weights():
 def test_training_loop_reduces_the_loss():
     rc, opt = _opt(count=START)
     n = 2048
-    rays, jit = _case(n, seed=41)
+    rays, jit = lc.cache_case(n, seed=41)
     target = rc_ext.RadianceCache(CFG, 0)
     target.load_weights(common.weights_np(seed=2))
     target.set_fused(False)
     gt = target.render_rays(rays, {"jitter": jit}, outputs=["rgb"])["rgb"].reshape(n, 3).contiguous()
-    total = []
-    for _ in range(LOOP_STEPS):
-        losses = train.cache_stage_step(rc, opt, rays, gt, jit)
-        total.append(float(sum(float(v) for v in losses.values())))
-    print("cache_stage_step loop totals:", [round(t, 5) for t in total])
-    assert opt.count == START + LOOP_STEPS
-    assert all(np.isfinite(total))
-    assert min(total[-3:]) < LOOP_DROP * total[0], total
+    lc.step_loop(lambda: train.cache_stage_step(rc, opt, rays, gt, jit),
+                 lambda losses: float(sum(float(v) for v in losses.values())), opt, START, LOOP_STEPS,
+                 lambda total: min(total[-3:]) < LOOP_DROP * total[0], "cache_stage_step loop totals:",
+                 lambda t: round(t, 5))
 
 
 def test_checkpoint_and_state_dict_round_trips(tmp_path):

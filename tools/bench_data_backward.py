@@ -9,18 +9,20 @@
       shader GEMMs' FLOP over k_gemm's kernel time against the fp32-MFMA peak.
 Prints one JSON line per measurement."""
 import argparse
-import csv
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import bench_common as bc
 
 FP32_MFMA_PEAK_TFS = 155.0     # measured v_mfma_f32_32x32x2_f32 peak of the MI355X (DESIGN.md)
 # dense layers of the shader side (in, out): pred_normals, bottleneck, 4 heads, integrated BRDF, SLF
 LAYERS = [(64, 3), (96, 128), (96, 1), (96, 3), (96, 3), (96, 3), (129, 64), (64, 64), (64, 1), (200, 128), (128, 128),
           (128, 128), (328, 128), (128, 3)]
+GROUPS = {"forward": ("k_sample", "k_level", "k_hashgrid", "k_density_mlp", "k_cache_shader", "k_composite"),
+          "k_data_loss_bwd": ("k_data_loss_bwd",), "reduce+copy": ("k_interlevel_reduce", "k_points_aos"),
+          "k_gemm": ("k_gemm",),
+          "shader_elementwise": ("k_sum_parts", "k_stage_feature", "k_shader_glue_fwd", "k_shader_out_bwd",
+                                 "k_shader_glue_bwd", "k_split_feature"),
+          "density_backward": ("k_density_bwd", "k_wgrad", "k_grad_reduce"), "grid_scatter": ("k_grid_scatter",)}
 
 
 def shader_flop_per_sample():
@@ -28,38 +30,18 @@ def shader_flop_per_sample():
     return 3 * 2 * sum(i * o for i, o in LAYERS)
 
 
-def split(stats_path, calls):
-    """Kernel time per call by group from a rocprofv3 kernel_stats.csv."""
-    groups = {"forward": ("k_sample", "k_level", "k_hashgrid", "k_density_mlp", "k_cache_shader", "k_composite"),
-              "k_data_loss_bwd": ("k_data_loss_bwd",), "reduce+copy": ("k_interlevel_reduce", "k_points_aos"),
-              "k_gemm": ("k_gemm",),
-              "shader_elementwise": ("k_sum_parts", "k_stage_feature", "k_shader_glue_fwd", "k_shader_out_bwd",
-                                     "k_shader_glue_bwd", "k_split_feature"),
-              "density_backward": ("k_density_bwd", "k_wgrad", "k_grad_reduce"), "grid_scatter": ("k_grid_scatter",)}
-    out = {k: 0.0 for k in groups}
-    with open(stats_path) as f:
-        for row in csv.DictReader(f):
-            name = row["Name"]
-            for g, pre in groups.items():
-                if any(p in name for p in pre):
-                    out[g] += float(row["TotalDurationNs"]) / 1e6 / calls
-                    break
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rays", type=int, nargs="+", default=[8192, 65536])
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--stats", default=None)
+    bc.add_rays(ap, [8192, 65536])
+    bc.add_loop(ap, 3, 10)
+    bc.add_stats(ap)
     a = ap.parse_args()
     import nrc_amd
     cfg = nrc_amd.hotdog_config()
     S2 = cfg.sampling_strategy[-1][2]
     if a.stats:
         n = a.rays[0]
-        ms = split(a.stats, a.warmup + a.reps)
+        ms = bc.split_groups(a.stats, GROUPS, a.warmup + a.reps)
         flop = shader_flop_per_sample() * n * S2
         t = ms["k_gemm"] * 1e-3
         tfs = flop / t / 1e12 if t > 0 else 0.0
@@ -68,32 +50,18 @@ def main():
                           "shader_floor_ms": round(floor_ms, 3), "k_gemm_TFLOPs": round(tfs, 1),
                           "k_gemm_frac_of_fp32_mfma_peak": round(tfs / FP32_MFMA_PEAK_TFS, 3)}))
         return
-    import numpy as np
     import torch
     import common
+    import loss_cases as lc
     from nrc_amd import train
     for n in a.rays:
         rc = common.make_rc()
-        rays = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in nrc_amd.synthetic_rays(n, seed=3).hot_fields().items()
-                if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-        jit = [torch.from_numpy(j.reshape(-1)).cuda() for j in common.jitters(n, seed=4)]
+        rays, jit = bc.to_device(lc.cache_case(n, seed=3))
         gt = torch.rand(n, 3, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
         flats = [torch.zeros(rc.density_grad_layout(cfg.num_levels - 1)[1], device="cuda"),
                  torch.zeros(rc.shader_grad_layout()[1], device="cuda")]
-        torch.cuda.synchronize()
-        free0 = torch.cuda.mem_get_info()[0]
-        for _ in range(a.warmup):
-            rc.data_backward(rays, gt, jit, train.anneal_at(1.0), grads=flats)
-        torch.cuda.synchronize()
-        ws_gb = (free0 - torch.cuda.mem_get_info()[0]) / 1e9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
-            rc.data_backward(rays, gt, jit, train.anneal_at(1.0), grads=flats)
-        e1.record()
-        torch.cuda.synchronize()
-        print(json.dumps({"rays": n, "ms_per_call": round(e0.elapsed_time(e1) / a.reps, 4), "workspace_GB": round(ws_gb, 2),
-                          "grad_MB": [round(f.numel() * 4 / 1e6, 1) for f in flats]}), flush=True)
+        call = lambda: rc.data_backward(rays, gt, jit, train.anneal_at(1.0), grads=flats)
+        bc.emit({"rays": n, **bc.time_whole_call(call, a.warmup, a.reps, flats)})
         rc.close()
         del flats
         torch.cuda.empty_cache()

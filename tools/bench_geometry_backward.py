@@ -10,50 +10,32 @@ pred_normals_layer) per call.
       per sample against the HBM peak.
 Prints one JSON line per measurement."""
 import argparse
-import csv
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import bench_common as bc
 
 HBM_PEAK_TBS = 8.0             # MI355X HBM3E peak (DESIGN.md)
 # k_geometry_loss_bwd's compulsory traffic per sample: weights, density, tdist, normals_pred, normals_grad (3 + 3),
 # hbuf (64), d_density and d_pred (3) written -- 4 x (1 + 1 + 1 + 6 + 64 + 1 + 3) bytes
 LOSS_BYTES_PER_SAMPLE = 4 * (1 + 1 + 1 + 6 + 64 + 1 + 3)
-
-
-def split(stats_path, calls):
-    """Kernel time per call by group from a rocprofv3 kernel_stats.csv."""
-    groups = {"forward": ("k_sample", "k_level", "k_hashgrid", "k_density_mlp"),
-              "k_geometry_loss_bwd": ("k_geometry_loss_bwd",), "reduce+copy": ("k_interlevel_reduce", "k_points_aos"),
-              "pred_layer": ("k_gemm", "k_sum_parts", "k_stage_hidden"),
-              "density_backward": ("k_density_bwd", "k_wgrad", "k_grad_reduce"), "grid_scatter": ("k_grid_scatter",)}
-    out = {k: 0.0 for k in groups}
-    with open(stats_path) as f:
-        for row in csv.DictReader(f):
-            name = row["Name"]
-            for g, pre in groups.items():
-                if any(p in name for p in pre):
-                    out[g] += float(row["TotalDurationNs"]) / 1e6 / calls
-                    break
-    return out
+GROUPS = {"forward": ("k_sample", "k_level", "k_hashgrid", "k_density_mlp"),
+          "k_geometry_loss_bwd": ("k_geometry_loss_bwd",), "reduce+copy": ("k_interlevel_reduce", "k_points_aos"),
+          "pred_layer": ("k_gemm", "k_sum_parts", "k_stage_hidden"),
+          "density_backward": ("k_density_bwd", "k_wgrad", "k_grad_reduce"), "grid_scatter": ("k_grid_scatter",)}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rays", type=int, nargs="+", default=[8192, 65536])
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--stats", default=None)
+    bc.add_rays(ap, [8192, 65536])
+    bc.add_loop(ap, 3, 10)
+    bc.add_stats(ap)
     a = ap.parse_args()
     import nrc_amd
     cfg = nrc_amd.hotdog_config()
     S2 = cfg.sampling_strategy[-1][2]
     if a.stats:
         n = a.rays[0]
-        ms = split(a.stats, a.warmup + a.reps)
+        ms = bc.split_groups(a.stats, GROUPS, a.warmup + a.reps)
         nbytes = LOSS_BYTES_PER_SAMPLE * n * S2
         t = ms["k_geometry_loss_bwd"] * 1e-3
         floor_ms = nbytes / (HBM_PEAK_TBS * 1e12) * 1e3
@@ -61,32 +43,18 @@ def main():
                           "loss_bytes_per_sample": LOSS_BYTES_PER_SAMPLE, "loss_floor_ms": round(floor_ms, 4),
                           "loss_frac_of_hbm_peak": round(nbytes / t / (HBM_PEAK_TBS * 1e12), 3) if t > 0 else 0.0}))
         return
-    import numpy as np
     import torch
     import common
+    import loss_cases as lc
     from nrc_amd import train
     for n in a.rays:
         rc = common.make_rc()
-        rays = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in nrc_amd.synthetic_rays(n, seed=3).hot_fields().items()
-                if k in ("origins", "directions", "viewdirs", "near", "far", "lights")}
-        jit = [torch.from_numpy(j.reshape(-1)).cuda() for j in common.jitters(n, seed=4)]
+        rays, jit = bc.to_device(lc.cache_case(n, seed=3))
         terms = train.geometry_terms(1.0)
         flats = [torch.zeros(rc.density_grad_layout(cfg.num_levels - 1)[1], device="cuda"),
                  torch.zeros(rc.shader_grad_layout()[1], device="cuda")]
-        torch.cuda.synchronize()
-        free0 = torch.cuda.mem_get_info()[0]
-        for _ in range(a.warmup):
-            rc.geometry_backward(rays, jit, train.anneal_at(1.0), None, terms, grads=flats)
-        torch.cuda.synchronize()
-        ws_gb = (free0 - torch.cuda.mem_get_info()[0]) / 1e9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.reps):
-            rc.geometry_backward(rays, jit, train.anneal_at(1.0), None, terms, grads=flats)
-        e1.record()
-        torch.cuda.synchronize()
-        print(json.dumps({"rays": n, "ms_per_call": round(e0.elapsed_time(e1) / a.reps, 4), "workspace_GB": round(ws_gb, 2),
-                          "grad_MB": [round(f.numel() * 4 / 1e6, 1) for f in flats]}), flush=True)
+        call = lambda: rc.geometry_backward(rays, jit, train.anneal_at(1.0), None, terms, grads=flats)
+        bc.emit({"rays": n, **bc.time_whole_call(call, a.warmup, a.reps, flats)})
         rc.close()
         del flats
         torch.cuda.empty_cache()

@@ -10,84 +10,40 @@ LightSampler gradients), the forward alone (rc_render_material at the same size)
       reported per run, not per call.
 Prints one JSON line per measurement."""
 import argparse
-import csv
 import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import bench_common as bc
 
-
-def split(stats_path):
-    """Kernel ms per group over the whole profiled run, from a rocprofv3 kernel_stats.csv."""
-    groups = {"k_light_sampling_loss_bwd": ("k_light_sampling_loss_bwd",), "gemm": ("k_gemm", "k_sum_parts"),
-              "grid_scatter": ("k_grid_scatter",), "regularizer": ("k_grid_l2",), "reduce": ("k_interlevel_reduce",)}
-    out = {k: 0.0 for k in groups}
-    out["other (material forward)"] = 0.0
-    with open(stats_path) as f:
-        for row in csv.DictReader(f):
-            name = row["Name"]
-            for g, pre in groups.items():
-                if any(p in name for p in pre):
-                    out[g] += float(row["TotalDurationNs"]) / 1e6
-                    break
-            else:
-                out["other (material forward)"] += float(row["TotalDurationNs"]) / 1e6
-    return out
+GROUPS = {"k_light_sampling_loss_bwd": ("k_light_sampling_loss_bwd",), "gemm": ("k_gemm", "k_sum_parts"),
+          "grid_scatter": ("k_grid_scatter",), "regularizer": ("k_grid_l2",), "reduce": ("k_interlevel_reduce",)}
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rays", type=int, nargs="+", default=[8192, 32768])
+    bc.add_rays(ap, [8192, 32768])
     ap.add_argument("--k", type=int, default=8)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--stats", default=None)
+    bc.add_loop(ap, 3, 10)
+    bc.add_stats(ap)
     a = ap.parse_args()
     if a.stats:
-        ms = split(a.stats)
+        ms = bc.split_groups(a.stats, GROUPS, other="other (material forward)")
         print(json.dumps({"rays": a.rays[0], "k": a.k, "calls_each": a.warmup + a.reps,
                           "kernel_ms_per_run": {k: round(v, 4) for k, v in ms.items()}}))
         return
-    import dataclasses
-
     import torch
-    import common
-    import nrc_amd
-    from oracle import material_ref
-    cfg = nrc_amd.hotdog_config()
+    import loss_cases as lc
     for n in a.rays:
-        rc = common.make_rc(weights=common.weights_material_np())
-        dev = lambda v: [dev(x) for x in v] if isinstance(v, list) else torch.from_numpy(v).cuda()
-        # inputs resident on the device: the calls' host work is argument marshalling only
-        rays = {k: dev(v) for k, v in nrc_amd.synthetic_rays(n, seed=3).hot_fields().items()}
-        rnd = {k: dev(v) for k, v in material_ref.draw_randoms(dataclasses.replace(cfg, num_secondary_samples=a.k), n,
-                                                                 seed=4).items()}
+        rc = lc.make_material_rc()
+        rays, rnd = bc.to_device(lc.material_case(n, a.k, seed=3))
         grad = torch.zeros(rc.light_grad_layout()[1], device="cuda")
         calls = {
             "backward": lambda: rc.light_sampling_backward(rays, rnd, a.k, grad=grad),
             "forward_render_material": lambda: rc.render_material(rays, rnd, a.k),
             "regularizer": lambda: rc.light_regularizer(1.0, grad),
         }
-        res = {"rays": n, "k": a.k}
-        for name, fn in calls.items():
-            for _ in range(a.warmup):
-                fn()
-            torch.cuda.synchronize()
-            # device events bracket each call on the caller's stream; the median of the repetitions
-            times = []
-            for _ in range(a.reps):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                times.append(e0.elapsed_time(e1))
-            times.sort()
-            res[name + "_ms"] = round(times[len(times) // 2], 4)
+        res = {"rays": n, "k": a.k, **bc.time_calls(calls, a.warmup, a.reps)}
         res["backward_over_forward"] = round(res["backward_ms"] / res["forward_render_material_ms"], 3)
-        print(json.dumps(res), flush=True)
+        bc.emit(res)
         rc.close()
         torch.cuda.empty_cache()
 
