@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 4
+#define RC_ABI_VERSION 5
 #define RC_MAX_LEVELS 3
 
 typedef struct rc_handle rc_handle;
@@ -287,7 +287,7 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
- * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward.
+ * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -635,7 +635,7 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
 
 /* rc_load_params_flat: rc_load_weights of every tensor of one gradient layout, from a DEVICE buffer in that layout
  * (layout = density level l: rc_density_grad_layout(l); RC_LAYOUT_SHADER: rc_shader_grad_layout; RC_LAYOUT_LIGHT:
- * rc_light_grad_layout; RC_LAYOUT_MATERIAL: rc_material_grad_layout).  The grid tables
+ * rc_light_grad_layout; RC_LAYOUT_MATERIAL: rc_material_grad_layout; RC_LAYOUT_ENVMAP: rc_envmap_grad_layout).  The grid tables
  * are copied device to device into the handle's table buffers, ordered on `stream`; the dense-layer segments go to
  * the host in ONE copy (gathered on the device first when they are not contiguous), after which the call waits for
  * `stream` (the host repack needs them).  The derived tables (cell tables, level-2 pairs, cell records) and packs are
@@ -645,6 +645,7 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
 #define RC_LAYOUT_SHADER (-1)
 #define RC_LAYOUT_LIGHT (-2)   /* rc_light_grad_layout */
 #define RC_LAYOUT_MATERIAL (-3)   /* rc_material_grad_layout */
+#define RC_LAYOUT_ENVMAP (-4)   /* rc_envmap_grad_layout */
 int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void* stream);
 
 /* ---- the light sampler's own loss -----------------------------------------------------------------
@@ -777,6 +778,34 @@ typedef struct {
 int rc_material_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, const float* lossmult, int64_t n,
                               const rc_randoms* rnd, const rc_material_randoms* mrnd, int32_t num_secondary_samples,
                               const rc_material_data_loss* cfg, float* material_grads, float* loss, void* stream);
+
+/* ---- the EnvMap's gradient of the material stage's data loss --------------------------------------
+ * rc_material_data_backward_env is rc_material_data_backward (same forward, loss, material_grads, refusals and buffers,
+ * bit for bit) and, when envmap_grads is given, the exact gradient of the same loss w.r.t. the params/Cache/EnvMap tensors
+ * that the model-level path reads (Model._handle_env_map, internal/models.py:360-421), under the same
+ * Trainer.stopgrad = True reading.  Per secondary ray k of shading point r and channel c:
+ *   env   = max(max(softplus(raw + env_rgb_bias), 0), 0)       the EnvMap's clip, then env_map_fn's jnp.maximum
+ *   ein   = nan_to_num(env (1 - acc_k))
+ *   direct = clip(ein lobe, 0, rgb_max) weight_k / max(pdf_k, 1e-5), averaged over the Ks / Kd samples of its pass
+ *   d loss / d env = env_scale g_rc w_r (1 / K_pass) weight_k / max(pdf_k, 1e-5) clip'(ein lobe) lobe (1 - acc_k) max'(.)
+ * with g_rc = d loss / d rgb of rc_material_data_backward; the lobe, acc, the directions, pdf, the MIS weight and w are
+ * constants.  env_scale: MaterialMLP.stopgrad_env_map_weight[1] (nerf_ngp_yobo.gin:420: 1), stopgrad_with_weight's
+ * factor on the gradient (the value is not scaled).  JAX rules: clip / maximum ties pass half, nan_to_num passes where
+ * finite, softplus' = sigmoid.  The MLP's backward runs at the trace's own directions ("sec_dirs"), which are stopped:
+ * pos_enc has no gradient; the alpha column of output_rgba_layer gets exact zeros; output_ambient_rgb_layer is not read
+ * on this path and is not in the layout.  Not covered: the indirect terms, the Cache, the LightSampler, path (b).
+ * The EnvMap layout: params/Cache/EnvMap/{layer_0, layer_1, layer_2, layer_bottleneck, output_rgba_layer}, kernel
+ * [in, out] then bias [out] each (hotdog: 10 segments, 175 620 floats).  rc_load_params_flat(RC_LAYOUT_ENVMAP) loads it.
+ * envmap_grads: ACCUMULATED into; dense gradients are reduced over fixed slices of rows in a fixed order (bitwise
+ * reproducible).  Either gradient pointer may be NULL.  The recompute is fp32 whatever rc_mlp_arithmetic() says of the
+ * forward.  Everything is ordered on `stream`.  Buffers: rc_material_data_backward's, "md:d_env" ([n Ks | n Kd][3], the
+ * sec_* ray order) and one chunk of rows of the EnvMap's backward ("md:e_*"). */
+int64_t rc_envmap_grad_size(rc_handle* h);
+int rc_envmap_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count);
+int rc_material_data_backward_env(rc_handle* h, const rc_rays* rays, const float* gt_rgb, const float* lossmult, int64_t n,
+                                  const rc_randoms* rnd, const rc_material_randoms* mrnd, int32_t num_secondary_samples,
+                                  const rc_material_data_loss* cfg, float env_scale, float* material_grads,
+                                  float* envmap_grads, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

@@ -292,6 +292,10 @@ class MaterialDataLossConfig:
     filter_normals_thresh: float = 1.01
     # the stage's num_secondary_samples 4 (configs/trainer.gin:327) times Trainer.sample_factor 2 (engine/trainer.py:86)
     num_secondary_samples: int = 8
+    # MaterialMLP.stopgrad_env_map_weight = (1e-2, 1) (configs/nerf_ngp_yobo.gin:420): its second entry is
+    # stopgrad_with_weight's factor on the gradient that incoming_rgb passes to the EnvMap (models.py:412-418); the value
+    # is not scaled
+    env_map_grad_weight: float = 1.0
 
     @property
     def weight(self) -> float:

@@ -107,7 +107,13 @@ struct MaterialWs { WsBuf cache_rgb, cache_acc, pts, feat, mat_p, loss_ray, loss
 // rc_material_data_backward (its forward is rc_render_material on set 0 and WS_SECONDARY): the primary pass's composite
 // ("cache_rgb" is read by the loss), the rebuilt rgb, the per-point loss sums and d loss / d material, d loss / d features,
 // the per-workgroup weight-gradient partials and loss sums.
-struct MatDataWs { WsBuf cache_rgb, cache_acc, rgb, loss_ray, dmat, dfeat, part, loss_part; };
+// rc_material_data_backward_env adds d loss / d (EnvMap radiance) per secondary ray and one row chunk of the EnvMap's
+// backward (rc_envmap_bwd.hip): the recompute's activations (xb = [layer_2's output | the encoded direction]), their
+// gradients, the weight-gradient K slices and a 1.0f.
+struct MatDataWs {
+  WsBuf cache_rgb, cache_acc, rgb, loss_ray, dmat, dfeat, part, loss_part;
+  WsBuf d_env, e_h0, e_h1, e_xb, e_hb, e_raw, e_draw, e_dhb, e_dxb, e_dh1, e_dh0, e_part, e_ones;
+};
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
@@ -116,7 +122,7 @@ struct MatDataWs { WsBuf cache_rgb, cache_acc, rgb, loss_ray, dmat, dfeat, part,
 // WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat, WS_LIGHT
 // the buffers of rc_light_sampling_backward's own (its forward runs on WS_RENDER0 + WS_SECONDARY) and rc_light_regularizer,
 // WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer,
-// WS_MATDATA those of rc_material_data_backward (its forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY).
+// WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY).
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
                WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
@@ -203,7 +209,8 @@ constexpr WsName kTable[] = {
     WS(M, cache_rgb), WS(M, cache_acc), WS(M, pts), WS(M, feat), WS(M, mat_p), WS(M, loss_ray), WS(M, loss_part), WS(M, dfeat),
     WS(M, part), WS(M, reg_part),
     WS(MD, cache_rgb), WS(MD, cache_acc), WS(MD, rgb), WS(MD, loss_ray), WS(MD, dmat), WS(MD, dfeat), WS(MD, part),
-    WS(MD, loss_part)};
+    WS(MD, loss_part), WS(MD, d_env), WS(MD, e_h0), WS(MD, e_h1), WS(MD, e_xb), WS(MD, e_hb), WS(MD, e_raw), WS(MD, e_draw),
+    WS(MD, e_dhb), WS(MD, e_dxb), WS(MD, e_dh1), WS(MD, e_dh0), WS(MD, e_part), WS(MD, e_ones)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
 static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD),
@@ -248,6 +255,8 @@ struct rc_handle {
   DevBuf data_w;                             // rc_data_backward: the shader's dense layers on the Flax layout
   uint64_t geom_gen = 0;                     // layers_gen geom_w was uploaded at
   DevBuf geom_w;                             // rc_geometry_backward: pred_normals_layer kernel [64][3] + bias [3]
+  uint64_t env_gen = 0;                      // layers_gen env_w was uploaded at
+  DevBuf env_w;                              // rc_material_data_backward_env: the EnvMap's dense layers on the Flax layout
   float* pinned = nullptr;                   // rc_load_params_flat: page-locked landing buffer of the dense segments
   size_t pinned_bytes = 0;
   bool have_envmap = false;
@@ -1077,6 +1086,7 @@ void rc_destroy(rc_handle* h) {
   if (h->ide_table.p) (void)hipFree(h->ide_table.p);
   free_buf(h->data_w);
   free_buf(h->geom_w);
+  free_buf(h->env_w);
   if (h->pinned) (void)hipHostFree(h->pinned);
   drop_graphs(h);
   for (WsSet& s : h->ws) if (s.done) (void)hipEventDestroy(s.done);

@@ -606,6 +606,21 @@ struct RcMatDataHeadArgs {
 };
 int rc_mat_data_blocks(int64_t n);
 void rc_launch_material_data_head_bwd(const RcMatDataHeadArgs& a, hipStream_t st);
+// k_material_data_env_bwd: k_material_data_bwd's recompute, then d loss / d (the EnvMap radiance of every secondary ray)
+// times env_scale into d_env [n Ks | n Kd][3] (the sec_* ray order); a's rgb / loss_ray / dmat are not written
+void rc_launch_material_data_env_bwd(const RcMatDataArgs& a, float env_scale, float* d_env, hipStream_t st);
+
+// The EnvMap's gradient of the material data loss (rc_envmap_bwd.hip)
+constexpr int kRcEnvIn = 27, kRcEnvWidth = 256, kRcEnvBott = 128;   // pos_enc(d, 0, 4) + identity, the trunk, layer_bottleneck
+constexpr int kRcEnvLdx = 288;             // row stride of [layer_2's output (256) | the encoded direction (27) | 0 (5)]
+// xb[p][256 .. 288) = [pos_enc(dirs[c0 + p], 0, 4, append_identity) | 0], k_envmap's sinf arguments; p < C
+void rc_launch_envmap_stage(const float* dirs, int64_t c0, int64_t C, float* xb, hipStream_t st);
+// d_raw[p][c] = d_env[c0 + p][c] max'(softplus(z), 0) sigmoid(z), z = raw[p][c] + rgb_bias (c < 3); d_raw[p][3] = 0
+void rc_launch_envmap_out_bwd(const float* d_env, const float* raw, float rgb_bias, int64_t c0, int64_t C, float* d_raw,
+                              hipStream_t st);
+// RcGemmArgs' product on k_gemm_tile (a 128 x 128 tile of C per workgroup, the operand panels staged through LDS):
+// kparts K slices on blockIdx.y as rc_launch_gemm.  Same results as k_gemm up to the order of the sum over k.
+void rc_launch_gemm_tile(const RcGemmArgs& a, int kparts, hipStream_t st);
 
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;

@@ -19,6 +19,8 @@
 //                             the lobes, the four means and rgb (bitwise rc_render_material's "rgb"), the loss terms of
 //                             the point, then d loss / d (albedo rgb, roughness, metalness) per lane, added over the
 //                             wave by the same butterfly: per point [5] floats written, nothing per (point, sample).
+//   k_material_data_env_bwd   the same body with the other tail: d loss / d (EnvMap radiance) of every
+//                             secondary ray, [n Ks | n Kd][3] in the trace's ray order; nothing else written.
 //   k_material_data_head_bwd  one workgroup of 128 threads takes chunks of 16 shading points: the material head's
 //                             recompute in material_head_block's order, material_head_bwd (rc_dev_material.h), d loss /
 //                             d features ([n][32], for rc_hashgrid_backward) and one weight-gradient partial per
@@ -66,7 +68,10 @@ __device__ __forceinline__ float clip_grad(float x, float hi) {
 }
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
-__global__ __launch_bounds__(256) void k_material_data_bwd(RcMatDataArgs a) {
+// The body of k_material_data_bwd; kEnv: k_material_data_env_bwd's, which leaves the point's outputs alone and writes
+// d loss / d (the EnvMap radiance of its secondary rays) instead of d loss / d material.
+template <bool kEnv>
+__device__ __forceinline__ void material_data_point(const RcMatDataArgs& a, float env_scale, float* d_env) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int64_t r = (int64_t)blockIdx.x * 4 + wave;
   const bool ok = r < a.n;
@@ -82,6 +87,8 @@ __global__ __launch_bounds__(256) void k_material_data_bwd(RcMatDataArgs a) {
   float ind[3] = {0, 0, 0}, dir[3] = {0, 0, 0};
   float rin[3] = {0, 0, 0}, ein[3] = {0, 0, 0}, lobe[3] = {0, 0, 0};
   float wd = 0.0f, D = 0.0f, G = 0.0f, n_v = 0.0f, n_l = 0.0f, n_h = 0.0f, c5 = 0.0f;
+  float dein[3] = {0, 0, 0};               // kEnv: d ein / d (the EnvMap's clipped softplus)
+  int64_t sec = 0;
   if (act) {
     const float* sm = a.samples + (r * K + lane) * RC_SMP_CH;
     const V3 wi = {sm[0], sm[1], sm[2]};
@@ -110,6 +117,12 @@ __global__ __launch_bounds__(256) void k_material_data_bwd(RcMatDataArgs a) {
       if (ri != ri) ri = 0.0f;
       ri = fmaxf(fminf(fmaxf(ri, -RC_FMAX), RC_FMAX), 0.0f);
       float ei = fmaxf(a.sec_env[3 * idx + c], 0.0f) * (1.0f - acc);
+      if (kEnv) {
+        // env_map_fn's jnp.maximum(., 0) (ties split), the product with 1 - acc, nan_to_num (passes where finite)
+        const float e0 = a.sec_env[3 * idx + c];
+        dein[c] = (ei == ei && fabsf(ei) <= RC_FMAX) ? max_grad(e0, 0.0f) * (1.0f - acc) : 0.0f;
+        sec = idx;
+      }
       if (ei != ei) ei = 0.0f;
       ei = fminf(fmaxf(ei, -RC_FMAX), RC_FMAX);
       rin[c] = ri; ein[c] = ei;
@@ -158,6 +171,16 @@ __global__ __launch_bounds__(256) void k_material_data_bwd(RcMatDataArgs a) {
     lsum += lm * (2.0f * d * d * sc);
     grgb[c] = a.coef * lm * 2.0f * d * sc * w;             // d loss / d sh_rgb[c]
   }
+  if (kEnv) {
+    // d loss / d env = d loss / d sh_rgb * (1 / K_pass) * weight / max(pdf, 1e-5) * clip'(ein lobe) * lobe * d ein / d env
+    if (act && ok) {
+      const float inv = 1.0f / (float)(spec ? Ks : Kd);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        d_env[3 * sec + c] = env_scale * (grgb[c] * inv * wd * (clip_grad(ein[c] * lobe[c], a.rgb_max) * lobe[c]) * dein[c]);
+    }
+    return;
+  }
   if (lane == 0 && ok) {
     a.rgb[3 * r] = out[0]; a.rgb[3 * r + 1] = out[1]; a.rgb[3 * r + 2] = out[2];
     a.loss_ray[r] = lsum;
@@ -204,6 +227,12 @@ __global__ __launch_bounds__(256) void k_material_data_bwd(RcMatDataArgs a) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) a.dmat[r * 5 + k] = dm[k];
   }
+}
+
+__global__ __launch_bounds__(256) void k_material_data_bwd(RcMatDataArgs a) { material_data_point<false>(a, 0.0f, nullptr); }
+
+__global__ __launch_bounds__(256) void k_material_data_env_bwd(RcMatDataArgs a, float env_scale, float* d_env) {
+  material_data_point<true>(a, env_scale, d_env);
 }
 
 __global__ __launch_bounds__(128) void k_material_data_head_bwd(RcMatDataHeadArgs a) {
@@ -312,6 +341,11 @@ int rc_mat_data_blocks(int64_t n) {
 void rc_launch_material_data_bwd(const RcMatDataArgs& a, hipStream_t st) {
   if (a.n <= 0) return;
   hipLaunchKernelGGL(k_material_data_bwd, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, st, a);
+}
+
+void rc_launch_material_data_env_bwd(const RcMatDataArgs& a, float env_scale, float* d_env, hipStream_t st) {
+  if (a.n <= 0) return;
+  hipLaunchKernelGGL(k_material_data_env_bwd, dim3((unsigned)((a.n + 3) / 4)), dim3(256), 0, st, a, env_scale, d_env);
 }
 
 void rc_launch_material_data_head_bwd(const RcMatDataHeadArgs& a, hipStream_t st) {

@@ -87,10 +87,10 @@ int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void*
   if (!h) return RC_ERR_INVALID_ARG;
   if (!params) return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: null params");
   if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_load_params_flat: not available on a time-resolved cache handle");
-  if (layout != RC_LAYOUT_SHADER && layout != RC_LAYOUT_LIGHT && layout != RC_LAYOUT_MATERIAL &&
+  if (layout != RC_LAYOUT_SHADER && layout != RC_LAYOUT_LIGHT && layout != RC_LAYOUT_MATERIAL && layout != RC_LAYOUT_ENVMAP &&
       (layout < 0 || layout >= h->cfg.num_levels))
-    return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: layout must be a density level, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT "
-                                       "or RC_LAYOUT_MATERIAL");
+    return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: layout must be a density level, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, "
+                                       "RC_LAYOUT_MATERIAL or RC_LAYOUT_ENVMAP");
   int rc;
   if ((rc = layout_check(h, layout, "rc_load_params_flat"))) return rc;
   const std::vector<GradSeg> segs = layout_segments(h, layout);

@@ -1,7 +1,7 @@
 // Host side of the training backward of one level's density field (rc_train.hip); included by rc_api.hip before the other
 // training files.  Also what those files share: the gradient-buffer layouts (GradSeg, one builder per layout,
 // layout_segments, behind every rc_*_grad_size / rc_*_grad_layout and rc_load_params_flat), the dense layers on k_gemm
-// (dense_fwd, dense_dx, dense_wgrad) and the body of the three grid-L2 regularizers.
+// (dense_fwd, dense_dx, dense_wgrad) and on k_gemm_tile (dense_*_tile) and the body of the three grid-L2 regularizers.
 
 namespace {
 
@@ -109,7 +109,22 @@ std::vector<GradSeg> material_grad_segments(rc_handle* h) {
   return v;
 }
 
-// Layout ids of the ABI: a density level >= 0, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, RC_LAYOUT_MATERIAL.  `who`'s check that
+// params/Cache/EnvMap, the layers the model-level path reads (output_ambient_rgb_layer is not one of them): layer_0,
+// layer_1, layer_2, layer_bottleneck, output_rgba_layer (kernel, bias each)
+constexpr const char* kEnvLayers[5] = {"layer_0", "layer_1", "layer_2", "layer_bottleneck", "output_rgba_layer"};
+std::vector<GradSeg> envmap_grad_segments(rc_handle* h) {
+  const auto inv = dense_inventory(h->cfg, nullptr);
+  std::vector<GradSeg> v;
+  int64_t off = 0;
+  for (const char* l : kEnvLayers) {
+    const std::string path = std::string("params/Cache/EnvMap/") + l;
+    const auto& io = inv.at(path);
+    dense_grad_segments(v, off, path, io.first, io.second);
+  }
+  return v;
+}
+
+// Layout ids of the ABI: a density level >= 0, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP.  `who`'s check that
 // the handle has the layout (a density export maps a negative level to kNoLayout, so that it names no other layout).
 constexpr int kNoLayout = INT32_MIN;
 int layout_check(rc_handle* h, int layout, const std::string& who) {
@@ -119,6 +134,8 @@ int layout_check(rc_handle* h, int layout, const std::string& who) {
     if (h->grids[kLightGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, who + ": no light grid");
   } else if (layout == RC_LAYOUT_MATERIAL) {
     if (h->grids[kMaterialGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, who + ": no material grid");
+  } else if (layout == RC_LAYOUT_ENVMAP) {
+    if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
   } else if (layout < 0 || layout >= h->cfg.num_levels) {
     return fail(h, RC_ERR_INVALID_ARG, who + ": bad level");
   }
@@ -131,6 +148,7 @@ std::vector<GradSeg> layout_segments(rc_handle* h, int layout) {
     case RC_LAYOUT_SHADER: return shader_grad_segments(h);
     case RC_LAYOUT_LIGHT: return light_grad_segments(h);
     case RC_LAYOUT_MATERIAL: return material_grad_segments(h);
+    case RC_LAYOUT_ENVMAP: return envmap_grad_segments(h);
     default: return density_grad_segments(h, layout);
   }
 }
@@ -214,6 +232,39 @@ void dense_wgrad(const Dense& L, int64_t M, const float* X, int64_t ldx, const f
   }
 }
 
+// The same three on k_gemm_tile (rc_envmap_bwd.hip), same arguments and results up to the order of the sums over k.
+void dense_fwd_tile(const Dense& L, int64_t M, const float* X, int64_t ldx, float* Y, int64_t ldy, bool relu, hipStream_t st) {
+  RcGemmArgs g{};
+  g.M = (int)M; g.N = L.out; g.K = L.in;
+  g.a = X; g.sai = ldx; g.sak = 1; g.b = L.w; g.sbk = L.out; g.sbj = 1;
+  g.c = Y; g.sci = ldy; g.scj = 1; g.bias = L.b; g.relu = relu ? 1 : 0; g.kslice = g.K;
+  rc_launch_gemm_tile(g, 1, st);
+}
+
+void dense_dx_tile(const Dense& L, int64_t M, const float* dY, int64_t ldy, float* dX, int64_t ldx, int j0, int nj,
+                   const float* mask, bool accumulate, hipStream_t st) {
+  RcGemmArgs g{};
+  g.M = (int)M; g.N = nj; g.K = L.out;
+  g.a = dY; g.sai = ldy; g.sak = 1; g.b = L.w + (int64_t)j0 * L.out; g.sbk = 1; g.sbj = L.out;
+  g.c = dX + j0; g.sci = ldx; g.scj = 1; g.mask = mask ? mask + j0 : nullptr; g.smi = ldx; g.smj = 1;
+  g.accumulate = accumulate ? 1 : 0; g.kslice = g.K;
+  rc_launch_gemm_tile(g, 1, st);
+}
+
+void dense_wgrad_tile(const Dense& L, int64_t M, const float* X, int64_t ldx, const float* dY, int64_t ldy, const float* ones,
+                      float* part, float* grads, const GradSeg* kb, hipStream_t st) {
+  const int64_t Z = (M + kDataKSlice - 1) / kDataKSlice;
+  for (int pass = 0; pass < 2; ++pass) {
+    RcGemmArgs g{};
+    g.M = pass == 0 ? L.in : 1; g.N = L.out; g.K = M;
+    g.a = pass == 0 ? X : ones; g.sai = pass == 0 ? 1 : 0; g.sak = pass == 0 ? ldx : 0;
+    g.b = dY; g.sbk = ldy; g.sbj = 1; g.c = part; g.sci = L.out; g.scj = 1;
+    g.kslice = kDataKSlice; g.spart = (int64_t)g.M * L.out;
+    rc_launch_gemm_tile(g, (int)Z, st);
+    rc_launch_sum_parts(part, (int)Z, g.spart, grads + kb[pass].offset, st);
+  }
+}
+
 // rc_{density,light,material}_regularizer after the export's own checks: mult * sum over the tables of grid `grid` of
 // 0.5 * mean(x^2) into `loss`, and mult * x / numel added into the layout `grads` (whose head is the grid's tables), on
 // the workspace set `set` (X: its extra buffers, reg_part the per-table partial sums).
@@ -284,6 +335,7 @@ int64_t rc_density_grad_size(rc_handle* h, int32_t level) {
 int64_t rc_shader_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_SHADER, "rc_shader_grad_size"); }
 int64_t rc_light_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_LIGHT, "rc_light_grad_size"); }
 int64_t rc_material_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_MATERIAL, "rc_material_grad_size"); }
+int64_t rc_envmap_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_ENVMAP, "rc_envmap_grad_size"); }
 
 int rc_density_grad_layout(rc_handle* h, int32_t level, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
   return layout_grad_layout(h, level < 0 ? kNoLayout : level, segs, capacity, count, "rc_density_grad_layout");
@@ -296,6 +348,10 @@ int rc_light_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, 
 }
 int rc_material_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
   return layout_grad_layout(h, RC_LAYOUT_MATERIAL, segs, capacity, count, "rc_material_grad_layout");
+}
+
+int rc_envmap_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  return layout_grad_layout(h, RC_LAYOUT_ENVMAP, segs, capacity, count, "rc_envmap_grad_layout");
 }
 
 int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_t n, const float* d_density,

@@ -14,7 +14,7 @@ import numpy as np
 
 from .config import GridConfig, RenderConfig
 
-RC_ABI_VERSION = 4
+RC_ABI_VERSION = 5
 RC_MAX_LEVELS = 3
 
 RC_PASS_CACHE = 0x1
@@ -155,6 +155,7 @@ RC_ADAM_MAX_GROUPS = 8
 RC_LAYOUT_SHADER = -1
 RC_LAYOUT_LIGHT = -2
 RC_LAYOUT_MATERIAL = -3
+RC_LAYOUT_ENVMAP = -4
 
 
 class rc_light_sampling_loss(C.Structure):
@@ -193,16 +194,18 @@ EXPORTS = (
     "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward", "rc_geometry_backward", "rc_density_regularizer",
     "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
     "rc_light_regularizer", "rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
-    "rc_material_regularizer", "rc_material_data_backward",
+    "rc_material_regularizer", "rc_material_data_backward", "rc_envmap_grad_size", "rc_envmap_grad_layout",
+    "rc_material_data_backward_env",
 )
 
-# Gradient layouts by key -- a density level (int), "shader", "light", "material": the C functions of its size and of its
+# Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap": the C functions of its size and of its
 # segments (a density level is their first argument) and its RC_LAYOUT_* id (rc_load_params_flat; a level is its own).
 _GRAD_LAYOUTS = {
     int: ("rc_density_grad_size", "rc_density_grad_layout", None),
     "shader": ("rc_shader_grad_size", "rc_shader_grad_layout", RC_LAYOUT_SHADER),
     "light": ("rc_light_grad_size", "rc_light_grad_layout", RC_LAYOUT_LIGHT),
     "material": ("rc_material_grad_size", "rc_material_grad_layout", RC_LAYOUT_MATERIAL),
+    "envmap": ("rc_envmap_grad_size", "rc_envmap_grad_layout", RC_LAYOUT_ENVMAP),
 }
 _LAYOUT_KEYS = {row[2]: key for key, row in _GRAD_LAYOUTS.items() if key is not int}
 
@@ -343,6 +346,15 @@ def load_library():
                                               C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_int32,
                                               C.POINTER(rc_material_data_loss), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.rc_material_data_backward.restype = C.c_int
+    lib.rc_envmap_grad_size.argtypes = [C.c_void_p]
+    lib.rc_envmap_grad_size.restype = C.c_int64
+    lib.rc_envmap_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.rc_envmap_grad_layout.restype = C.c_int
+    lib.rc_material_data_backward_env.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_int32,
+                                                  C.POINTER(rc_material_data_loss), C.c_float, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]
+    lib.rc_material_data_backward_env.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -956,7 +968,7 @@ class RadianceCache:
         self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), stream))
 
     def load_params_flat(self, layout, params, stream_handle=None):
-        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light" or "material")
+        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light", "material" or "envmap")
         from a flat
         float32 cuda buffer in that layout -- table copies ordered on the current stream, the dense layers in one copy
         to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
@@ -1097,6 +1109,11 @@ class RadianceCache:
         tables, then bottleneck_layer, pred_brdf_layer), and its size in floats."""
         return self._grad_layout("material")
 
+    def envmap_grad_layout(self):
+        """rc_envmap_grad_layout: [(tensor name, offset, shape)] of the model-level EnvMap's gradient buffer
+        (params/Cache/EnvMap: layer_0, layer_1, layer_2, layer_bottleneck, output_rgba_layer), and its size in floats."""
+        return self._grad_layout("envmap")
+
     def _shading_randoms(self, randoms, held):
         """The rc_randoms / rc_material_randoms of material_smoothness_backward: the primary pass's jitter and the shading
         point's pick (gumbel or resample_inds) of render_material's randoms; the sampler members stay NULL."""
@@ -1150,12 +1167,17 @@ class RadianceCache:
         return self._regularizer(self.lib.rc_material_regularizer, "material", (float(mult),), grad)
 
     def material_data_backward(self, rays: Dict[str, object], randoms: Dict[str, object], gt_rgb,
-                               num_secondary_samples: int = None, lossmult=None, cfg=None, grad=None, stream_handle=None):
+                               num_secondary_samples: int = None, lossmult=None, cfg=None, grad=None, stream_handle=None,
+                               env_grad=None, env_scale: float = 1.0):
         """rc_material_data_backward: render_material with the same rays / randoms / num_secondary_samples, the material
         stage's data loss against gt_rgb ([n, 3]) with the constants of cfg (config.MaterialDataLossConfig) and its
         gradient w.r.t. the MaterialShader parameters (material_grad_layout; the Trainer.stopgrad = True reading,
         DESIGN.md §4.12).  grad: flat buffer to accumulate into (allocated zeroed when None); grad=False computes the
-        loss only.  Returns (grad flat or None, loss [1] cuda tensor)."""
+        loss only.  Returns (grad flat or None, loss [1] cuda tensor).
+        env_grad: None leaves everything above as it is.  True, or a flat buffer of envmap_grad_layout to
+        accumulate into, makes the call rc_material_data_backward_env: the same loss and MaterialShader gradient, and the
+        gradient w.r.t. the params/Cache/EnvMap tensors times env_scale (MaterialMLP.stopgrad_env_map_weight[1]).
+        Returns (grad flat or None, EnvMap grad flat, loss)."""
         from .config import MaterialDataLossConfig
 
         cfg = MaterialDataLossConfig() if cfg is None else cfg
@@ -1173,12 +1195,21 @@ class RadianceCache:
                                   use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)),
                                   use_norm_rawnerf=int(bool(cfg.use_norm_rawnerf)))
         flat, loss, stream = self._loss_prologue("material", grad, stream_handle=stream_handle)
-        self._check(self.lib.rc_material_data_backward(self._h, C.byref(r), gt.data_ptr(),
-                                                       None if lm is None else lm.data_ptr(), n, C.byref(rnd), C.byref(mr),
-                                                       K, C.byref(c), None if flat is None else flat.data_ptr(),
-                                                       loss.data_ptr(), stream))
+        if env_grad is None or env_grad is False:
+            self._check(self.lib.rc_material_data_backward(self._h, C.byref(r), gt.data_ptr(),
+                                                           None if lm is None else lm.data_ptr(), n, C.byref(rnd),
+                                                           C.byref(mr), K, C.byref(c),
+                                                           None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
+            self._keep = [held]
+            return flat, loss
+        env = self._grad_buffer(None if env_grad is True else env_grad, self._grad_size("envmap"), "env_grad")
+        self._check(self.lib.rc_material_data_backward_env(self._h, C.byref(r), gt.data_ptr(),
+                                                           None if lm is None else lm.data_ptr(), n, C.byref(rnd),
+                                                           C.byref(mr), K, C.byref(c), float(env_scale),
+                                                           None if flat is None else flat.data_ptr(), env.data_ptr(),
+                                                           loss.data_ptr(), stream))
         self._keep = [held]
-        return flat, loss
+        return flat, env, loss
 
     def _material_randoms(self, randoms, n, K, held):
         """The rc_randoms / rc_material_randoms of render_material and light_sampling_backward (device copies kept in

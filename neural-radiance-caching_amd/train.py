@@ -533,16 +533,22 @@ def material_step(rc, opt: MaterialOptimizer, rays, randoms, noise, lossmult=Non
 
 
 def material_data_grads(rc, rays, randoms, gt_rgb, lossmult=None, flat=None,
-                        cfg: MaterialDataLossConfig = MaterialDataLossConfig()):
+                        cfg: MaterialDataLossConfig = MaterialDataLossConfig(), env_flat=None):
     """The material stage's data loss on a batch and its MaterialShader gradient: compute_data_loss of
     the MaterialIntegrator's rgb against gt_rgb ([n, 3]) times loss_weight, material_loss_weight_ease and data_loss_mult,
     accumulated into `flat` (layout rc.material_grad_layout(); allocated zeroed when None).  The gradient is the
     Trainer.stopgrad = True reading (path (a)); the Cache, EnvMap and LightSampler get none from this call.  randoms:
-    render_material's.  -> (flat, {"data": 0-d cuda tensor}), the key of the reference's losses_flat."""
+    render_material's.  -> (flat, {"data": 0-d cuda tensor}), the key of the reference's losses_flat.
+    env_flat: True, or a flat buffer of rc.envmap_grad_layout() to accumulate into, adds the EnvMap's
+    gradient of the same loss times cfg.env_map_grad_weight: -> (flat, env_flat, losses)."""
     if cfg.loss_type != "rawnerf_transient_unbiased" or cfg.use_loss_clip:
         raise NotImplementedError("material data loss: only the rawnerf unbiased form without loss clip")
-    flat, loss = rc.material_data_backward(rays, randoms, gt_rgb, cfg.num_secondary_samples, lossmult, cfg, flat)
-    return flat, {"data": loss[0]}
+    if env_flat is None:
+        flat, loss = rc.material_data_backward(rays, randoms, gt_rgb, cfg.num_secondary_samples, lossmult, cfg, flat)
+        return flat, {"data": loss[0]}
+    flat, env_flat, loss = rc.material_data_backward(rays, randoms, gt_rgb, cfg.num_secondary_samples, lossmult, cfg, flat,
+                                                     env_grad=env_flat, env_scale=cfg.env_map_grad_weight)
+    return flat, env_flat, {"data": loss[0]}
 
 
 def material_stage_grads(rc, rays, randoms, gt_rgb, noise, train_frac: float, lossmult=None, flat=None,
@@ -565,3 +571,43 @@ def material_stage_step(rc, opt: MaterialOptimizer, rays, randoms, gt_rgb, noise
     -> the losses dict of material_stage_grads."""
     return _train_step(opt, group, lambda tf: material_stage_grads(rc, rays, randoms, gt_rgb, noise, tf, lossmult,
                                                                    opt.grads["material"], data_cfg, smooth_cfg))
+
+
+# ---- the EnvMap ----------------------------------------------------------------------------------------------------
+
+class EnvMapOptimizer(CacheStageOptimizer):
+    """The model-level EnvMap's optimizer state on the device: flat params, mu, nu and gradients in the layout
+    rc.envmap_grad_layout() (key "envmap") and the optax count.  Every tensor is in param_group "EnvMap" (the last listed
+    prefix on "Cache/EnvMap/..." wins over none: "Cache" is no group).  clip_gradients takes its norm per top-level module
+    and Cache/EnvMap sits under Cache, whose other tensors this optimizer does not hold: with grad_max_norm > 0 that norm
+    cannot be formed here, so it is refused (hotdog has both clips off).  A step is ONE rc_adam_update over this buffer,
+    then rc_load_params_flat (RC_LAYOUT_ENVMAP).  init_from / params_dict / state_dict / load_state_dict as
+    CacheStageOptimizer."""
+
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
+        if cfg.grad_max_norm > 0:
+            raise NotImplementedError("EnvMapOptimizer: grad_max_norm needs the norm over all of params/Cache")
+        super().__init__(rc, cfg, ["envmap"])
+
+
+def material_env_stage_step(rc, opt_material: MaterialOptimizer, opt_envmap: EnvMapOptimizer, rays, randoms, gt_rgb, noise,
+                            lossmult=None, group=None, data_cfg: MaterialDataLossConfig = MaterialDataLossConfig(),
+                            smooth_cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig(), step_material: bool = True,
+                            step_envmap: bool = True):
+    """One train step of the material stage on the MaterialShader and the EnvMap: one forward, the data
+    loss into both optimizers' zeroed gradient buffers (rc_material_data_backward_env), material_smoothness_grads into the
+    material buffer, ONE pmean over both (allreduce_grads), then both optimizer steps.  train_frac is read from
+    opt_material.count; the two counts advance together.  step_material / step_envmap = False leaves that optimizer's
+    parameters, moments and count alone (its gradient buffer is zeroed).  -> the losses dict of material_stage_grads."""
+    tf = train_frac_at(opt_material.count, opt_material.cfg.scaled_steps(opt_material.cfg.max_steps))
+    gm, ge = opt_material.grads["material"], opt_envmap.grads["envmap"]
+    _, _, losses = material_data_grads(rc, rays, randoms, gt_rgb, lossmult, gm, data_cfg, env_flat=ge)
+    _, more = material_smoothness_grads(rc, rays, randoms, noise, tf, lossmult, gm, smooth_cfg)
+    losses.update(more)
+    allreduce_grads([gm, ge], group=group)
+    for opt, on, g in ((opt_material, step_material, gm), (opt_envmap, step_envmap, ge)):
+        if on:
+            opt.step()
+        else:
+            g.zero_()
+    return losses
