@@ -455,6 +455,68 @@ typedef struct rc_cast_outputs {
 int rc_cast_rays(rc_handle* h, const rc_camera* cam, const int32_t* pix_x, const int32_t* pix_y, int64_t n,
                  int32_t x0, int32_t y0, int32_t width, int32_t height, const rc_cast_outputs* out, void* stream);
 
+/* ---- rays of a batch that mixes cameras, and the training batch of one step ----------------
+ * rc_camera_set: the reference's `cameras` tuple on the device -- per-camera tables, and what all cameras share
+ * (camera_utils.cast_ray_batch reads pixtocams[cam_idx], camtoworlds[cam_idx], lights[cam_idx] per ray and ONE
+ * camtype / distortion_params / pixtocam_ndc / z_range, internal/camera_utils.py:1266-1299).  The tables are
+ * device arrays that stay valid until the call's work on `stream` is done; the shared fields mean what they mean in
+ * rc_camera. */
+typedef struct rc_camera_set {
+  int32_t count;             /* C >= 1 cameras                                                             */
+  const float* pixtocams;    /* [C, 9]  inverse intrinsics, row-major [3,3] each                           */
+  const float* camtoworlds;  /* [C, 12] extrinsics, row-major [3,4] each                                   */
+  const float* lights;       /* [C, 3]  lights[cam_idx], or NULL: the camera centre camtoworld[:3, 3]      */
+  float near, far;
+  int32_t camtype;
+  int32_t has_distortion;
+  float distortion[6];
+  int32_t has_ndc;
+  float pixtocam_ndc[9];
+  int32_t has_z_range;
+  float z_range[2];
+  const float* pix_dx;       /* rc_train_batch only: [n] sub-pixel jitter offsets or NULL, as rc_camera.pix_dx / pix_dy; */
+  const float* pix_dy;       /* rc_cast_rays_multi takes its own as arguments and does not read these      */
+} rc_camera_set;
+
+/* cast_ray_batch for pixels of several cameras in one launch; replaces a host loop of one rc_cast_rays per distinct
+ * camera (camera_utils.py:1225-1329 with the per-ray lookup of :1266-1288).
+ * cam_idx / pix_x / pix_y: int32 device arrays [n] (Pixels.cam_idx / pix_x_int / pix_y_int), all required.
+ * cam_idx[i] must lie in [0, set->count): the kernel clamps it so that no table is read out of bounds, but a clamped
+ * ray is the ray of the wrong camera -- a contract violation like a pix_x outside the image, not an error code.
+ * pix_dx / pix_dy: [n] sub-pixel jitter offsets, both or neither.  Every output of ray i is bitwise what rc_cast_rays
+ * writes for camera cam_idx[i] and that pixel.  n == 0 succeeds and launches nothing. */
+int rc_cast_rays_multi(rc_handle* h, const rc_camera_set* set, const int32_t* cam_idx, const int32_t* pix_x,
+                       const int32_t* pix_y, int64_t n, const float* pix_dx, const float* pix_dy,
+                       const rc_cast_outputs* out, void* stream);
+
+/* The batch of one train step from a PRNG key; replaces Dataset._next_train + _make_ray_batch for image-shaped data
+ * (internal/datasets.py:948-993, 850-946) + cast_ray_batch.  n = P * patch_size^2 rays, ray i = pixel i % patch_size^2
+ * (row-major in the patch, camera_utils.pixel_coordinates(p, p)) of patch i / patch_size^2.
+ * Index rule (this package's own; the reference draws from numpy's global Mersenne Twister, datasets.py:969-981):
+ * w = random_bits(key, (P, 3)) of jax's threefry2x32 (what rc_prng_fill(key, RC_PRNG_MODE_BITS, n = 3 P) holds); patch
+ * q takes  cam = (w[q][0] * C) >> 32,  x0 = border + (w[q][1] * (W - 2 border - p + 1)) >> 32,  y0 likewise with H and
+ * w[q][2], in 64-bit integers (bias <= range / 2^32).  batching RC_BATCHING_SINGLE_IMAGE: every patch takes the camera
+ * of w[0][0] (datasets.py:981).
+ * images: device [C, H, W, 3], RC_IMAGE_F32 float32 or RC_IMAGE_U8 uint8 (read as (float)u / 255.0f, an IEEE division).
+ * cam_lossmult: device [C] or NULL (datasets.py:989-990; NULL: lossmult = 1).  key: host uint32[2].
+ * Errors (nothing is launched): n != P p^2 for every P, i.e. n % p^2 != 0; count < 1; W - 2 border - p + 1 < 1 or the
+ * same with H; a NULL table, image or key; 3 P >= 2^32 - 1.  n == 0 succeeds and launches nothing.
+ * A NULL handle is an error as well, reported after the argument checks above (rc_last_error(NULL) has their text),
+ * so that a host can validate a call's shape without a device. */
+typedef enum rc_image_dtype { RC_IMAGE_F32 = 0, RC_IMAGE_U8 = 1 } rc_image_dtype;
+typedef enum rc_batching { RC_BATCHING_ALL_IMAGES = 0, RC_BATCHING_SINGLE_IMAGE = 1 } rc_batching;
+typedef struct rc_train_batch_outputs {
+  rc_cast_outputs rays;      /* the rays of the n pixels                                                    */
+  float* rgb;                /* [n,3] images[cam, y, x]                                                     */
+  float* lossmult;           /* [n]                                                                         */
+  int32_t* cam_idx;          /* [n]   the picks: camera, pixel column, pixel row                            */
+  int32_t* pix_x;
+  int32_t* pix_y;
+} rc_train_batch_outputs;    /* NULL = not wanted */
+int rc_train_batch(rc_handle* h, const rc_camera_set* set, const void* images, int32_t image_dtype, int32_t height,
+                   int32_t width, const float* cam_lossmult, const uint32_t key[2], int32_t patch_size, int32_t border,
+                   int32_t batching, int64_t n, const rc_train_batch_outputs* out_batch, void* stream);
+
 /* ---- jax.random-compatible random tensors, generated in HBM ----------------------
  * Replaces the reference's jax.random.uniform / normal / categorical(gumbel) draws on the path
  * (internal/stepfun.py:200-202 per-ray jitter, internal/models.py:240-247 resampling noise,

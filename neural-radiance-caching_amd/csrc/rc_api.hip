@@ -1987,6 +1987,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 }  // extern "C"
 
 #include "rc_transient_host.inc"
+#include "rc_batch_host.inc"
 #include "rc_train_host.inc"
 #include "rc_interlevel_host.inc"
 #include "rc_data_host.inc"

@@ -385,21 +385,58 @@ void rc_launch_transient_bins(const RcTransBinsArgs& a, hipStream_t stream);
 // ---------------------------------------------------------------------------------------------
 // On-device ray generation (rc_camera.hip)
 // ---------------------------------------------------------------------------------------------
-struct RcCastArgs {
-  int64_t n;
-  const int32_t* pix_x; const int32_t* pix_y;      // explicit pixel batch, or NULL: the rectangle below, row-major
-  int32_t x0, y0, width;
-  float pixtocam[9]; float rot[9]; float trans[3]; float light[3];
+// What every camera of a call shares (the reference's `cameras` tuple beyond the per-camera matrices)
+struct RcCastShared {
   float near_v, far_v;
   int32_t camtype;                                  // 0 perspective, 1 panoramic, 2 fisheye, 3 fisheye (equisolid)
   int32_t has_distortion; float dist[6];            // k1 k2 k3 k4 p1 p2
   int32_t has_ndc; float ndc_xmult, ndc_ymult;      // 1 / pixtocam_ndc[0][2], 1 / pixtocam_ndc[1][2]
   int32_t has_z_range; float z_lo, z_hi;            // cast_ray_batch's z_range
-  const float* pix_dx; const float* pix_dy;         // sub-pixel jitter offsets [n] or NULL
+};
+struct RcCastOut {                                  // rc_cast_outputs; NULL = not wanted
   float* origins; float* directions; float* viewdirs; float* radii; float* imageplane; float* look; float* up;
   float* lights; float* near; float* far;
 };
+struct RcCastArgs {
+  int64_t n;
+  const int32_t* pix_x; const int32_t* pix_y;      // explicit pixel batch, or NULL: the rectangle below, row-major
+  int32_t x0, y0, width;
+  float pixtocam[9]; float rot[9]; float trans[3]; float light[3];
+  RcCastShared s;
+  const float* pix_dx; const float* pix_dy;         // sub-pixel jitter offsets [n] or NULL
+  RcCastOut out;
+};
 void rc_launch_cast_rays(const RcCastArgs& a, hipStream_t stream);
+
+// Rays of a batch that mixes cameras, and the training batch built from a PRNG key (rc_batch.hip)
+struct RcCameraTables {
+  int32_t count;                                    // C >= 1
+  const float* pixtocams;                           // [C, 9]
+  const float* camtoworlds;                         // [C, 12]
+  const float* lights;                              // [C, 3] or NULL: the camera centre
+};
+struct RcCastMultiArgs {
+  int64_t n;
+  RcCameraTables cams; RcCastShared s;
+  const int32_t* cam_idx; const int32_t* pix_x; const int32_t* pix_y;
+  const float* pix_dx; const float* pix_dy;
+  RcCastOut out;
+};
+struct RcTrainBatchArgs {
+  int64_t n;                                        // P * p * p rays
+  RcCameraTables cams; RcCastShared s;
+  const void* images; int32_t image_u8;             // [C, H, W, 3] float32, or uint8 (value / 255)
+  int32_t height, width;
+  const float* cam_lossmult;                        // [C] or NULL (1)
+  uint32_t key0, key1; uint32_t n_words;            // 3 P words of random_bits(key, (P, 3))
+  int32_t patch, x_lo, x_range, y_lo, y_range;      // p; x in [x_lo, x_lo + x_range), y likewise
+  int32_t single_image;
+  const float* pix_dx; const float* pix_dy;
+  RcCastOut out;
+  float* rgb; float* lossmult; int32_t* cam_idx; int32_t* pix_x; int32_t* pix_y;
+};
+void rc_launch_cast_rays_multi(const RcCastMultiArgs& a, hipStream_t stream);
+void rc_launch_train_batch(const RcTrainBatchArgs& a, hipStream_t stream);
 
 // Training backward of one level's density field (rc_train.hip)
 struct RcDensityBwdArgs {

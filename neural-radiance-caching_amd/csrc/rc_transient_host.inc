@@ -308,6 +308,30 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   RC_CATCH(h)
 }
 
+static RcCastOut cast_out(const rc_cast_outputs* out) {
+  RcCastOut o{};
+  o.origins = out->origins; o.directions = out->directions; o.viewdirs = out->viewdirs; o.radii = out->radii;
+  o.imageplane = out->imageplane; o.look = out->look; o.up = out->up; o.lights = out->lights; o.near = out->near; o.far = out->far;
+  return o;
+}
+
+// The fields rc_camera and rc_camera_set share, into the kernels' form; -> what is wrong with them, or NULL
+template <class Cam>
+static const char* cast_shared(const Cam* cam, RcCastShared& s) {
+  if (cam->camtype < 0 || cam->camtype > 3)
+    return "camtype must be 0 (perspective), 1 (panoramic), 2 (fisheye) or 3 (fisheye, equisolid)";
+  s.near_v = cam->near; s.far_v = cam->far; s.camtype = cam->camtype;
+  s.has_distortion = cam->has_distortion != 0;
+  for (int i = 0; i < 6; ++i) s.dist[i] = cam->distortion[i];
+  s.has_ndc = cam->has_ndc != 0;
+  if (s.has_ndc) {          // convert_to_ndc: xmult = 1 / pixtocam[0, 2], ymult = 1 / pixtocam[1, 2] (camera_utils.py:97-98)
+    if (cam->pixtocam_ndc[2] == 0.0f || cam->pixtocam_ndc[5] == 0.0f) return "pixtocam_ndc[0][2] and [1][2] must be non-zero";
+    s.ndc_xmult = 1.0f / cam->pixtocam_ndc[2]; s.ndc_ymult = 1.0f / cam->pixtocam_ndc[5];
+  }
+  s.has_z_range = cam->has_z_range != 0; s.z_lo = cam->z_range[0]; s.z_hi = cam->z_range[1];
+  return nullptr;
+}
+
 int rc_cast_rays(rc_handle* h, const rc_camera* cam, const int32_t* pix_x, const int32_t* pix_y, int64_t n,
                  int32_t x0, int32_t y0, int32_t width, int32_t height, const rc_cast_outputs* out, void* stream_v) {
   RC_TRY
@@ -329,21 +353,11 @@ int rc_cast_rays(rc_handle* h, const rc_camera* cam, const int32_t* pix_x, const
     a.trans[r] = cam->camtoworld[4 * r + 3];
     a.light[r] = cam->light[r];
   }
-  if (cam->camtype < 0 || cam->camtype > 3)
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_cast_rays: camtype must be 0 (perspective), 1 (panoramic), 2 (fisheye) or 3 (fisheye, equisolid)");
-  a.near_v = cam->near; a.far_v = cam->far; a.camtype = cam->camtype;
-  a.has_distortion = cam->has_distortion != 0;
-  for (int i = 0; i < 6; ++i) a.dist[i] = cam->distortion[i];
-  a.has_ndc = cam->has_ndc != 0;
-  if (a.has_ndc) {          // convert_to_ndc: xmult = 1 / pixtocam[0, 2], ymult = 1 / pixtocam[1, 2] (camera_utils.py:97-98)
-    if (cam->pixtocam_ndc[2] == 0.0f || cam->pixtocam_ndc[5] == 0.0f) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: pixtocam_ndc[0][2] and [1][2] must be non-zero");
-    a.ndc_xmult = 1.0f / cam->pixtocam_ndc[2]; a.ndc_ymult = 1.0f / cam->pixtocam_ndc[5];
-  }
-  a.has_z_range = cam->has_z_range != 0; a.z_lo = cam->z_range[0]; a.z_hi = cam->z_range[1];
+  if (const char* bad = cast_shared(cam, a.s))
+    return fail(h, cam->camtype < 0 || cam->camtype > 3 ? RC_ERR_UNSUPPORTED : RC_ERR_INVALID_ARG, std::string("rc_cast_rays: ") + bad);
   if ((cam->pix_dx == nullptr) != (cam->pix_dy == nullptr)) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: pix_dx and pix_dy go together");
   a.pix_dx = cam->pix_dx; a.pix_dy = cam->pix_dy;
-  a.origins = out->origins; a.directions = out->directions; a.viewdirs = out->viewdirs; a.radii = out->radii;
-  a.imageplane = out->imageplane; a.look = out->look; a.up = out->up; a.lights = out->lights; a.near = out->near; a.far = out->far;
+  a.out = cast_out(out);
   rc_launch_cast_rays(a, (hipStream_t)stream_v);
   RC_HIP(h, hipGetLastError());
   return RC_OK;

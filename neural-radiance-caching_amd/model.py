@@ -420,12 +420,8 @@ def _cast_pixels(model: Model, cameras, lights, pixels: Pixels, camtype) -> Rays
     camtoworlds = _strip_device_axis(cameras[1], 3)
     lights = None if lights is None else _strip_device_axis(lights, 2)
     to_np = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    on_dev = lambda a: isinstance(a, torch.Tensor) and a.is_cuda
     sh = tuple(np.shape(pixels.near)[:-1])                      # batch shape SH; metadata fields are SH + [1]
-    cam_idx = to_np(pixels.cam_idx).reshape(-1).astype(np.int64)
-    px = to_np(pixels.pix_x_int).reshape(-1).astype(np.int32)
-    py = to_np(pixels.pix_y_int).reshape(-1).astype(np.int32)
-    if px.size != cam_idx.size:
-        raise ValueError("Pixels fields must share their batch shape")
 
     def cam(i):
         p2c = pixtocams if pixtocams.ndim == 2 else pixtocams[i]
@@ -434,20 +430,32 @@ def _cast_pixels(model: Model, cameras, lights, pixels: Pixels, camtype) -> Rays
         return Camera(pixtocam=p2c, camtoworld=c2w[:3, :4], light=light, near=0.0, far=0.0, camtype=ctype,
                       distortion_params=distortion, pixtocam_ndc=ndc, z_range=z_range)
 
-    uniq = np.unique(cam_idx)
-    if len(uniq) == 1:
-        rays = model.rc.cast_rays(cam(int(uniq[0])), px, py)
+    count = max([t.shape[0] for t in (pixtocams, camtoworlds) if t.ndim == 3], default=0)
+    dev_idx = all(on_dev(a) for a in (pixels.cam_idx, pixels.pix_x_int, pixels.pix_y_int))
+    if dev_idx:
+        cam_idx, px, py = (a.reshape(-1).to(torch.int32) for a in (pixels.cam_idx, pixels.pix_x_int, pixels.pix_y_int))
+        several = True                                          # not looked at on the host: the tables serve any mix
+        if count == 0:                                          # one camera for every pixel, whatever cam_idx says
+            count, cam_idx = 1, torch.zeros_like(cam_idx)
     else:
-        parts, order = [], []
-        for i in uniq:
-            sel = np.nonzero(cam_idx == i)[0]
-            parts.append(model.rc.cast_rays(cam(int(i)), px[sel], py[sel]))
-            order.append(sel)
-        inv = torch.from_numpy(np.argsort(np.concatenate(order), kind="stable")).to(parts[0].origins.device)
-        rays = Rays(**{k: (None if v is None else torch.cat([getattr(p, k) for p in parts])[inv])
-                       for k, v in vars(parts[0]).items()})
+        cam_idx = to_np(pixels.cam_idx).reshape(-1).astype(np.int64)
+        px = to_np(pixels.pix_x_int).reshape(-1).astype(np.int32)
+        py = to_np(pixels.pix_y_int).reshape(-1).astype(np.int32)
+        several = count > 0 and cam_idx.size > 0 and bool((cam_idx != cam_idx[0]).any())
+        if several and not (0 <= int(cam_idx.min()) and int(cam_idx.max()) < count):
+            raise IndexError(f"cam_idx outside [0, {count})")
+    if px.shape[0] != cam_idx.shape[0]:
+        raise ValueError("Pixels fields must share their batch shape")
+    if not several:
+        rays = model.rc.cast_rays(cam(int(cam_idx[0]) if count > 0 and cam_idx.shape[0] else 0), px, py)
+    else:
+        # one launch for any mix of cameras (rc_cast_rays_multi): the tables go up once per call, the indices stay
+        # where they are; each ray is bitwise the one the single-camera call yields
+        c2w = np.broadcast_to(camtoworlds, (count,) + camtoworlds.shape[-2:])
+        cams = model.rc.camera_set(pixtocams, c2w, lights, 0.0, 0.0, ctype, distortion, ndc, z_range)
+        rays = model.rc.cast_rays_multi(cams, cam_idx, px, py)
     dev = rays.origins.device
-    meta = lambda a, dt=torch.float32: torch.as_tensor(to_np(a)).to(device=dev, dtype=dt).reshape(sh + (1,))
+    meta = lambda a, dt=torch.float32: (a if on_dev(a) else torch.as_tensor(to_np(a))).to(device=dev, dtype=dt).reshape(sh + (1,))
     rays = rays.tree_map(lambda t: t.reshape(sh + (t.shape[-1],)))
     return rays.replace(lossmult=meta(pixels.lossmult), near=meta(pixels.near), far=meta(pixels.far),
                         cam_idx=meta(pixels.cam_idx, torch.int32), light_idx=meta(pixels.light_idx, torch.int32),

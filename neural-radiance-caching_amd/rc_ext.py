@@ -146,6 +146,23 @@ class rc_cast_outputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k, _ in CAST_OUTPUTS]
 
 
+class rc_camera_set(C.Structure):
+    _fields_ = [("count", C.c_int32), ("pixtocams", C.c_void_p), ("camtoworlds", C.c_void_p), ("lights", C.c_void_p),
+                ("near", C.c_float), ("far", C.c_float), ("camtype", C.c_int32),
+                ("has_distortion", C.c_int32), ("distortion", C.c_float * 6),
+                ("has_ndc", C.c_int32), ("pixtocam_ndc", C.c_float * 9),
+                ("has_z_range", C.c_int32), ("z_range", C.c_float * 2), ("pix_dx", C.c_void_p), ("pix_dy", C.c_void_p)]
+
+
+class rc_train_batch_outputs(C.Structure):
+    _fields_ = [("rays", rc_cast_outputs)] + [(k, C.c_void_p) for k in ("rgb", "lossmult", "cam_idx", "pix_x", "pix_y")]
+
+
+RC_IMAGE_F32, RC_IMAGE_U8 = 0, 1
+BATCHING = {"all_images": 0, "single_image": 1}
+CAMTYPES = {"perspective": 0, "pano": 1, "fisheye": 2, "fisheye_equisolid": 3}
+
+
 class rc_geometry_loss(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("distortion_mult", "distortion_p", "distortion_premult", "orientation_mult",
                                          "pred_normal_mult", "pred_normal_w_grad_weight", "pred_normal_reverse_mult")]
@@ -195,7 +212,7 @@ EXPORTS = (
     "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
     "rc_light_regularizer", "rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
     "rc_material_regularizer", "rc_material_data_backward", "rc_envmap_grad_size", "rc_envmap_grad_layout",
-    "rc_material_data_backward_env",
+    "rc_material_data_backward_env", "rc_cast_rays_multi", "rc_train_batch",
 )
 
 # Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap": the C functions of its size and of its
@@ -290,6 +307,12 @@ def load_library():
     lib.rc_cast_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_void_p, C.c_void_p]
     lib.rc_cast_rays.restype = C.c_int
+    lib.rc_cast_rays_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_cast_rays_multi.restype = C.c_int
+    lib.rc_train_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.rc_train_batch.restype = C.c_int
     lib.rc_prng_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]
     lib.rc_prng_fill.restype = C.c_int
     lib.rc_density_grad_size.argtypes = [C.c_void_p, C.c_int32]
@@ -432,6 +455,46 @@ class AdamTable:
             b.params, b.grads, b.mu, b.nu = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
             b.n, b.nseg = n, len(segs)
             b.seg_offset, b.seg_size, b.seg_group = off.ctypes.data, size.ctypes.data, grp.ctypes.data
+
+
+class CameraSet:
+    """rc_camera_set with its device tables (RadianceCache.camera_set): uploaded once, reused by every call."""
+
+    def __init__(self, rc, pixtocams, camtoworlds, lights=None, near=0.0, far=0.0, camtype="perspective",
+                 distortion_params=None, pixtocam_ndc=None, z_range=None):
+        torch = rc._torch
+        host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        c2w = np.asarray(host(camtoworlds), np.float32)
+        if c2w.ndim != 3 or c2w.shape[1] < 3 or c2w.shape[2] != 4:
+            raise ValueError("camtoworlds must be [C, 3, 4] or [C, 4, 4]")
+        c2w = np.array(c2w[:, :3, :4], np.float32, order="C")
+        self.count = int(c2w.shape[0])
+        p2c = np.asarray(host(pixtocams), np.float32)
+        p2c = np.array(np.broadcast_to(p2c, (self.count, 3, 3)), np.float32, order="C")      # a copy: broadcast views are read-only
+        self.pixtocams = rc._dev(p2c.reshape(self.count, 9))
+        self.camtoworlds = rc._dev(c2w.reshape(self.count, 12))
+        self.lights = None
+        if lights is not None:
+            self.lights = rc._dev(np.array(np.broadcast_to(np.asarray(host(lights), np.float32), (self.count, 3)), np.float32, order="C"))
+        self.near, self.far = float(near), float(far)
+        s = rc_camera_set()
+        s.count = self.count
+        s.pixtocams, s.camtoworlds = self.pixtocams.data_ptr(), self.camtoworlds.data_ptr()
+        s.lights = None if self.lights is None else self.lights.data_ptr()
+        s.near, s.far = self.near, self.far
+        s.camtype = CAMTYPES[getattr(camtype, "value", camtype)]
+        if distortion_params is not None:
+            s.has_distortion = 1
+            for i, k in enumerate(("k1", "k2", "k3", "k4", "p1", "p2")):
+                s.distortion[i] = float(distortion_params.get(k, 0.0))
+        if pixtocam_ndc is not None:
+            s.has_ndc = 1
+            for i, v in enumerate(np.asarray(host(pixtocam_ndc), np.float32).reshape(9)):
+                s.pixtocam_ndc[i] = float(v)
+        if z_range is not None:
+            s.has_z_range = 1
+            s.z_range[0], s.z_range[1] = float(z_range[0]), float(z_range[1])
+        self.struct = s
 
 
 class RcError(RuntimeError):
@@ -1063,6 +1126,100 @@ class RadianceCache:
                     radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
                     vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=ones, near=t["near"],
                     far=t["far"], cam_idx=zi, light_idx=zi)
+
+    def camera_set(self, pixtocams, camtoworlds, lights=None, near: float = 0.0, far: float = 0.0, camtype="perspective",
+                   distortion_params=None, pixtocam_ndc=None, z_range=None):
+        """The reference's `cameras` tuple uploaded once: -> CameraSet for cast_rays_multi / train_batch.  pixtocams
+        [C, 3, 3] (or one [3, 3] for all), camtoworlds [C, 3, 4] (or [C, 4, 4]), lights [C, 3] or None (the camera centres);
+        the other arguments as in cast_rays' camera."""
+        return CameraSet(self, pixtocams, camtoworlds, lights, near, far, camtype, distortion_params, pixtocam_ndc, z_range)
+
+    def _cast_tensors(self, shape, out):
+        torch = self._torch
+        t = {}
+        for k, width in CAST_OUTPUTS:
+            t[k] = torch.empty(tuple(shape) + (width,), dtype=torch.float32, device=f"cuda:{self.device}")
+            setattr(out, k, t[k].data_ptr())
+        return t
+
+    def cast_rays_multi(self, cameras: "CameraSet", cam_idx, pix_x_int, pix_y_int, pix_jitter=None):
+        """rc_cast_rays_multi: the rays of pixels (pix_x_int, pix_y_int) of cameras cam_idx (three int arrays of one shape;
+        cuda int32 tensors are used where they are) in ONE launch, as a Rays of cuda tensors with the pixels' batch
+        shape; every field is bitwise what cast_rays yields per camera.  cam_idx must lie in [0, cameras.count): the
+        kernel only clamps it for memory safety.  lossmult is 1, cam_idx is carried over, light_idx is 0."""
+        from .rays import Rays
+        torch = self._torch
+        as_i32 = lambda a: self._dev(a if isinstance(a, torch.Tensor) else np.ascontiguousarray(a), torch.int32)
+        ci, px, py = as_i32(cam_idx), as_i32(pix_x_int), as_i32(pix_y_int)
+        if not (ci.shape == px.shape == py.shape):
+            raise ValueError("cam_idx, pix_x_int and pix_y_int must have the same shape")
+        shape, n = tuple(px.shape), px.numel()
+        jit = [None, None]
+        if pix_jitter is not None:
+            jit = [self._dev(j if isinstance(j, torch.Tensor) else np.ascontiguousarray(j, dtype=np.float32)).reshape(-1) for j in pix_jitter]
+            if jit[0].numel() != n or jit[1].numel() != n:
+                raise ValueError("pix_jitter: two arrays with one value per pixel")
+        out = rc_cast_outputs()
+        t = self._cast_tensors(shape, out)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.rc_cast_rays_multi(self._h, C.byref(cameras.struct), ptr(ci), ptr(px), ptr(py), n, ptr(jit[0]),
+                                                ptr(jit[1]), C.byref(out), stream))
+        self._keep = [ci, px, py, jit, cameras]
+        ones = torch.ones(shape + (1,), dtype=torch.float32, device=px.device)
+        return Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
+                    radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
+                    vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=ones, near=t["near"],
+                    far=t["far"], cam_idx=ci.reshape(shape + (1,)), light_idx=torch.zeros_like(ci).reshape(shape + (1,)))
+
+    def train_batch(self, cameras: "CameraSet", images, key, n: int, patch_size: int = 1, border: int = 0,
+                    batching: str = "all_images", cam_lossmult=None, pix_jitter=None):
+        """rc_train_batch: the batch of one train step from a PRNG key in ONE launch.  images: cuda tensor [C, H, W, 3],
+        float32 or uint8 (read as u / 255); cam_lossmult: cuda float32 [C] or None; key: uint32[2].  -> (Rays of
+        [n, .] cuda tensors with lossmult, cam_idx, pix_x_int, pix_y_int filled in, rgb [n, 3]).  The index rule is
+        data.patch_indices, this package's own."""
+        from . import prng
+        from .rays import Rays
+        torch = self._torch
+        if batching not in BATCHING:
+            raise ValueError(f"unknown batching {batching!r}")
+        if not isinstance(images, torch.Tensor) or not images.is_cuda or not images.is_contiguous() or images.dim() != 4 \
+                or images.shape[-1] != 3 or images.dtype not in (torch.float32, torch.uint8):
+            raise ValueError("images must be a contiguous cuda tensor [C, H, W, 3] of float32 or uint8")
+        if images.shape[0] != cameras.count:
+            raise ValueError(f"{images.shape[0]} images for {cameras.count} cameras")
+        n = int(n)
+        dev = f"cuda:{self.device}"
+        k = (C.c_uint32 * 2)(*[int(v) for v in prng.as_key(key)])
+        cs = cameras.struct
+        jit = None
+        if pix_jitter is not None:
+            jit = [self._dev(j if isinstance(j, torch.Tensor) else np.ascontiguousarray(j, dtype=np.float32)).reshape(-1) for j in pix_jitter]
+            if jit[0].numel() != n or jit[1].numel() != n:
+                raise ValueError("pix_jitter: two arrays with one value per ray")
+            cs = rc_camera_set.from_buffer_copy(cs)
+            cs.pix_dx, cs.pix_dy = jit[0].data_ptr(), jit[1].data_ptr()
+        lm = None if cam_lossmult is None else self._dev(cam_lossmult).reshape(-1)
+        if lm is not None and lm.numel() != cameras.count:
+            raise ValueError("cam_lossmult: one value per camera")
+        out = rc_train_batch_outputs()
+        t = self._cast_tensors((max(n, 0),), out.rays)
+        rgb = torch.empty((max(n, 0), 3), dtype=torch.float32, device=dev)
+        lossmult = torch.empty((max(n, 0), 1), dtype=torch.float32, device=dev)
+        idx = torch.empty((3, max(n, 0), 1), dtype=torch.int32, device=dev)
+        out.rgb, out.lossmult = rgb.data_ptr(), lossmult.data_ptr()
+        out.cam_idx, out.pix_x, out.pix_y = idx[0].data_ptr(), idx[1].data_ptr(), idx[2].data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(self.lib.rc_train_batch(self._h, C.byref(cs), images.data_ptr(),
+                                            RC_IMAGE_U8 if images.dtype == torch.uint8 else RC_IMAGE_F32, int(images.shape[1]),
+                                            int(images.shape[2]), None if lm is None else lm.data_ptr(), k, int(patch_size),
+                                            int(border), BATCHING[batching], n, C.byref(out), stream))
+        self._keep = [jit, lm, cameras, images]
+        rays = Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
+                    radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
+                    vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=lossmult, near=t["near"],
+                    far=t["far"], cam_idx=idx[0], light_idx=torch.zeros_like(idx[0]), pix_x_int=idx[1], pix_y_int=idx[2])
+        return rays, rgb
 
     def render_transient(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]] = None,
                          outputs: Optional[Iterable[str]] = None):

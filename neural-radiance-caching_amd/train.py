@@ -72,6 +72,7 @@ from typing import Dict, Iterable, List, Optional
 
 import numpy as np
 
+from . import prng
 from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaterialDataLossConfig,
                      MaterialSmoothnessConfig, OptimizerConfig)
 
@@ -441,6 +442,29 @@ def cache_stage_step(rc, opt: CacheStageOptimizer, rays, rgb, jitters, lossmult=
     refresh).  -> the losses dict of cache_stage_grads (the local batch's values)."""
     return _train_step(opt, group, lambda tf: cache_stage_grads(rc, rays, rgb, jitters, tf, lossmult, dict(opt.grads),
                                                                 geometry_cfg, data_cfg, interlevel_cfg))
+
+
+def cache_stage_fit(rc, opt: CacheStageOptimizer, dataset, key, steps: int, group=None,
+                    geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
+                    interlevel_cfg: InterlevelConfig = InterlevelConfig()):
+    """`steps` train steps of the cache stage fed by a data.DeviceDataset, from one PRNG key.  Per step: key, rng =
+    random_split(rng); dataset.next_train (one launch: cameras, pixels, rays, colours); one more split per proposal level
+    for its per-ray jitter, drawn in HBM (rc.prng_fill); cache_stage_step.  The host handles keys and scalars only: no
+    tensor crosses PCIe inside the loop and nothing is read back.  -> the steps' loss dicts (0-d cuda tensors)."""
+    rng = prng.as_key(key)
+    n = dataset.batch_size
+    history = []
+    for _ in range(int(steps)):
+        step_key, rng = prng.random_split(rng)
+        batch_key, jitter_key = prng.random_split(step_key)
+        batch = dataset.next_train(batch_key)
+        jitters = []
+        for _ in range(rc.cfg.num_levels):
+            k, jitter_key = prng.random_split(jitter_key)
+            jitters.append(rc.prng_fill(k, (n, 1), "uniform"))
+        history.append(cache_stage_step(rc, opt, batch.rays.hot_fields(), batch.rgb, jitters, batch.rays.lossmult, group,
+                                        geometry_cfg, data_cfg, interlevel_cfg))
+    return history
 
 
 # ---- the light sampler ---------------------------------------------------------------------------------------------
