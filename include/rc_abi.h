@@ -287,7 +287,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * secondary trace of rc_render_material / the shadow rays of rc_render_transient, "t:" = rc_density_backward,
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
- * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env.
+ * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env,
+ * "td:" = rc_transient_data_backward.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -320,6 +321,16 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * loss sums, doubles), "dfeat" ([2n][32] d loss / d features), "part" (per-workgroup partials of the dense layers'
  * gradients), "reg_part" (rc_material_regularizer's per-table partial sums, doubles).  The forward's own buffers keep
  * their set-0 names ("m_pts", "m_nrm", "m_mat", "filt_weight").
+ * "td:": "rgb" ([n][700][3] the rendered histograms), "G" ([n][700][3] d loss / d rgb), "Gt" ([n][700][3] the temporal
+ * filter's transpose applied to G: d loss / d the unfiltered direct histogram), "loss_ray" ([2][n] per-ray sums of the loss
+ * terms, then of lossmult (rgb - gt)^2); of the last chunk of C <= 256 rays of the heads' backward: "dz_irr" ([32 C][2100]
+ * d loss / d transient_indirect_layer's output), "dz_slf" ([32 C][2104] d loss / d output_rgba_layer's output, the alpha
+ * column and three pad floats zero), "x_irr" ([32 C][64]), "x_slf" ([32 C][128]) (the heads' inputs, row-major in the
+ * reference's column order), "part" (weight-gradient K slices), "ones"; for all n rays, row-major per shaded sample in the
+ * reference's column order: "d_t_irr" ([32 n][64] d loss / d the irradiance trunk's output), "d_t_slf" ([32 n][128] d loss /
+ * d the surface light field trunk's output), "d_tint_ibrdf" ([32 n][3]), "d_direct" ([32 n][3] d loss / d direct_rgb),
+ * "d_weights" ([32 n] d loss / d the compositing weights).  The forward's own buffers keep their set-0 names ("t_irr",
+ * "t_slf", "tshade", "weights2").
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -697,17 +708,19 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
 
 /* rc_load_params_flat: rc_load_weights of every tensor of one gradient layout, from a DEVICE buffer in that layout
  * (layout = density level l: rc_density_grad_layout(l); RC_LAYOUT_SHADER: rc_shader_grad_layout; RC_LAYOUT_LIGHT:
- * rc_light_grad_layout; RC_LAYOUT_MATERIAL: rc_material_grad_layout; RC_LAYOUT_ENVMAP: rc_envmap_grad_layout).  The grid tables
+ * rc_light_grad_layout; RC_LAYOUT_MATERIAL: rc_material_grad_layout; RC_LAYOUT_ENVMAP: rc_envmap_grad_layout;
+ * RC_LAYOUT_TRANSIENT_HEADS: rc_transient_head_grad_layout).  The grid tables
  * are copied device to device into the handle's table buffers, ordered on `stream`; the dense-layer segments go to
  * the host in ONE copy (gathered on the device first when they are not contiguous), after which the call waits for
  * `stream` (the host repack needs them).  The derived tables (cell tables, level-2 pairs, cell records) and packs are
  * marked stale and captured graphs dropped, as rc_load_weights does: the next render or backward call on any stream
- * computes bitwise what it would after rc_load_weights of the same tensors.  The time-resolved cache handle is
- * unsupported. */
+ * computes bitwise what it would after rc_load_weights of the same tensors.  A time-resolved cache handle loads
+ * RC_LAYOUT_TRANSIENT_HEADS only (every other layout: RC_ERR_UNSUPPORTED); that layout needs such a handle. */
 #define RC_LAYOUT_SHADER (-1)
 #define RC_LAYOUT_LIGHT (-2)   /* rc_light_grad_layout */
 #define RC_LAYOUT_MATERIAL (-3)   /* rc_material_grad_layout */
 #define RC_LAYOUT_ENVMAP (-4)   /* rc_envmap_grad_layout */
+#define RC_LAYOUT_TRANSIENT_HEADS (-5)   /* rc_transient_head_grad_layout */
 int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void* stream);
 
 /* ---- the light sampler's own loss -----------------------------------------------------------------
@@ -868,6 +881,49 @@ int rc_material_data_backward_env(rc_handle* h, const rc_rays* rays, const float
                                   const rc_randoms* rnd, const rc_material_randoms* mrnd, int32_t num_secondary_samples,
                                   const rc_material_data_loss* cfg, float env_scale, float* material_grads,
                                   float* envmap_grads, float* loss, void* stream);
+
+/* ---- the time-resolved cache's data loss and its per-bin heads -------------------------------------
+ * rc_transient_data_backward: train_utils.compute_transient_data_loss (internal/train_utils.py:531-640) with loss type
+ * 'rawnerf_transient_unbiased' (:725-732) on rc_render_transient's own rgb [n][n_bins][3], and its exact gradient of the
+ * two per-bin head layers.  With d = rgb - gt, dn = sg(rgb_nocorr - gt_nocorr) (both default to rgb, gt), c =
+ * _get_rgb_clip_for_rawnerf of the pass's own rgb (the cache stage's rendering has no "cache_rgb"), s_rc = 1 / (sg(sum over
+ * the bins of c) ** exponent + eps) per ray and channel, lossmult_rc = 0 where any bin of gt exceeds thresh:
+ *   losses[0] = mult * mean_{n x 3}(lossmult s (sum_b 2 d dn + 2 (k sum_b d)(k sum_b dn) gauss_mult))     k = gauss_constant_scale
+ *   losses[1] = mult * mean_{n x 3}(lossmult sum_b d^2)                                                   (the "mses" stat)
+ * (transient_gauss_sigma_scales = []: dtof_to_gauss is its constant row; the row is divided by n_bins and added to every
+ * bin, so it counts once).  The gradient reading is the one of rc_data_backward / rc_geometry_backward: sample positions,
+ * tdist, means and with them every travel time and time shift are constants.  One call:
+ *   1. rc_render_transient itself with the same rays / cam_origins / rnd, its "rgb" to "td:rgb";
+ *   2. losses (DEVICE floats [2], written; fixed reduction order), "td:G" = d loss / d rgb, "td:Gt";
+ *   3. the adjoint of the TransientVolumeIntegrator (the direct scatter, next-ray spill included; the time shift; the
+ *      clamps with JAX's tie rule; zero_invalid_bins; indirect_scale; softplus') and of the two heads, whose outputs are
+ *      recomputed in fp32 whatever rc_mlp_arithmetic() says and never stored beyond a chunk of 256 rays: "td:d_t_irr",
+ *      "td:d_t_slf", "td:d_tint_ibrdf", "td:d_direct", "td:d_weights" (see rc_workspace_ptr) feed the backward of the rest
+ *      of the shader, which is not part of this call;
+ *   4. only when head_grads is given: the heads' gradient, ACCUMULATED into head_grads (rc_transient_head_grad_layout:
+ *      params/Cache/Shader/transient_indirect_layer/{kernel [64, 3 n_bins], bias}, then
+ *      params/Cache/Shader/SurfaceLightField/output_rgba_layer/{kernel [128, 3 n_bins + 1], bias}; the alpha column gets
+ *      exact zeros), reduced over fixed slices of rows in a fixed order: two calls on the same inputs are bitwise equal.
+ * gt, rgb_nocorr, gt_nocorr: [n][n_bins][3] device floats (the latter two may be NULL).  lossmult: [n] device or NULL (1).
+ * Needs a time-resolved handle without occlusions (RC_ERR_UNSUPPORTED otherwise).  n == 0 returns RC_OK and writes
+ * nothing.  Everything is ordered on `stream`; no allocation once the workspace has seen the batch size.
+ * rc_load_params_flat(RC_LAYOUT_TRANSIENT_HEADS) loads the layout. */
+typedef struct {
+  float mult;                  /* Config.data_loss_mult (cornell.gin:62: 1.0) */
+  float gauss_mult;            /* Config.data_loss_gauss_mult (cornell.gin:63: 0.01) */
+  float gauss_constant_scale;  /* Config.transient_gauss_constant_scale (cornell.gin:64: 0.5) */
+  float exponent;              /* Config.rawnerf_exponent (cornell.gin:55: 1) */
+  float eps;                   /* Config.rawnerf_eps (cornell.gin:58: 1e-2) */
+  float clip_val;              /* compute_unbiased_loss_rawnerf_transient's clip_val (1e4) */
+  float thresh;                /* Config.loss_thresh (configs.py:447: 1e6) */
+  int32_t use_gt_rawnerf;      /* Config.use_gt_rawnerf (configs.py:587: False) */
+  int32_t use_combined_rawnerf; /* Config.use_combined_rawnerf (configs.py:588: True) */
+} rc_transient_data_loss;
+int64_t rc_transient_head_grad_size(rc_handle* h);
+int rc_transient_head_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count);
+int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                               const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                               const rc_transient_data_loss* cfg, float* head_grads, float* losses, void* stream);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,27 @@ class DataLossConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class TransientDataLossConfig:
+    """Training-time constants of the time-resolved cache's data loss (train_utils.compute_transient_data_loss,
+    internal/train_utils.py:531-640) as configs/transient_simulation_ngp_yobo_cornell.gin resolves it."""
+    # TransientMaterialModel.cache_loss (cornell.gin:51) -> _select_transient_data_loss_function (train_utils.py:725-732)
+    loss_type: str = "rawnerf_transient_unbiased"
+    rawnerf_exponent: float = 1.0            # Config.rawnerf_exponent (cornell.gin:55)
+    rawnerf_eps: float = 1e-2                # Config.rawnerf_eps (cornell.gin:58)
+    data_loss_mult: float = 1.0              # Config.data_loss_mult (cornell.gin:62)
+    data_loss_gauss_mult: float = 0.01       # Config.data_loss_gauss_mult (cornell.gin:63)
+    transient_gauss_sigma_scales: Tuple = ()     # Config.transient_gauss_sigma_scales (cornell.gin:61): no blurred rows
+    transient_gauss_constant_scale: float = 0.5  # Config.transient_gauss_constant_scale (cornell.gin:64)
+    clip_val: float = 1e4                    # compute_unbiased_loss_rawnerf_transient's clip_val (train_utils.py:200)
+    loss_thresh: float = 1e6                 # Config.loss_thresh (internal/configs.py:447)
+    use_gt_rawnerf: bool = False             # Config.use_gt_rawnerf (internal/configs.py:587)
+    use_combined_rawnerf: bool = True        # Config.use_combined_rawnerf (internal/configs.py:588)
+    mask_lossmult: bool = False              # Config.mask_lossmult (cornell.gin:137)
+    clip_eval: bool = False                  # Config.clip_eval (internal/configs.py:730)
+    use_itof: bool = False                   # Config.use_itof (internal/configs.py:717)
+
+
+@dataclasses.dataclass(frozen=True)
 class GeometryLossConfig:
     """Training-time constants of the cache stage's geometry losses and its density-grid regularizer (hotdog)."""
     # Config.distortion_loss_mult (configs/nerf_ngp_yobo_hotdog.gin:10, over nerf_ngp_yobo.gin:66's 0.0);

@@ -114,6 +114,14 @@ struct MatDataWs {
   WsBuf cache_rgb, cache_acc, rgb, loss_ray, dmat, dfeat, part, loss_part;
   WsBuf d_env, e_h0, e_h1, e_xb, e_hb, e_raw, e_draw, e_dhb, e_dxb, e_dh1, e_dh0, e_part, e_ones;
 };
+// rc_transient_data_backward (its forward is rc_render_transient on set 0): the rendered histograms, G = d loss / d rgb and
+// the temporal filter's transpose of it, the per-ray loss and mse sums; one chunk of kRcTdChunkRays rays of the heads'
+// backward (dZ of both heads, their inputs row-major, the weight-gradient K slices, a 1.0f); the adjoints of everything
+// k_transient_shader hands to k_transient_bins, for all n rays.
+struct TransDataWs {
+  WsBuf rgb, G, Gt, loss_ray, dz_irr, dz_slf, x_irr, x_slf, part, ones;
+  WsBuf d_t_irr, d_t_slf, d_tint_ibrdf, d_direct, d_weights;
+};
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
@@ -122,15 +130,16 @@ struct MatDataWs {
 // WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat, WS_LIGHT
 // the buffers of rc_light_sampling_backward's own (its forward runs on WS_RENDER0 + WS_SECONDARY) and rc_light_regularizer,
 // WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer,
-// WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY).
+// WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY),
+// WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0).
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -150,7 +159,7 @@ struct WsName {
   WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
   WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr; WsBuf DataWs::*d = nullptr;
   WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
-  WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr;
+  WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -163,6 +172,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf LightWs::*m) : name(s), ls(m) {}
   constexpr WsName(const char* s, WsBuf MaterialWs::*m) : name(s), ms(m) {}
   constexpr WsName(const char* s, WsBuf MatDataWs::*m) : name(s), md(m) {}
+  constexpr WsName(const char* s, WsBuf TransDataWs::*m) : name(s), td(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -175,7 +185,8 @@ struct WsName {
       if (o) return one(s, o);
       if (ls) return one(s, ls);
       if (ms) return one(s, ms);
-      return md ? one(s, md) : nullptr;
+      if (md) return one(s, md);
+      return td ? one(s, td) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -185,7 +196,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -210,10 +221,12 @@ constexpr WsName kTable[] = {
     WS(M, part), WS(M, reg_part),
     WS(MD, cache_rgb), WS(MD, cache_acc), WS(MD, rgb), WS(MD, loss_ray), WS(MD, dmat), WS(MD, dfeat), WS(MD, part),
     WS(MD, loss_part), WS(MD, d_env), WS(MD, e_h0), WS(MD, e_h1), WS(MD, e_xb), WS(MD, e_hb), WS(MD, e_raw), WS(MD, e_draw),
-    WS(MD, e_dhb), WS(MD, e_dxb), WS(MD, e_dh1), WS(MD, e_dh0), WS(MD, e_part), WS(MD, e_ones)};
+    WS(MD, e_dhb), WS(MD, e_dxb), WS(MD, e_dh1), WS(MD, e_dh0), WS(MD, e_part), WS(MD, e_ones),
+    WS(TD, rgb), WS(TD, G), WS(TD, Gt), WS(TD, loss_ray), WS(TD, dz_irr), WS(TD, dz_slf), WS(TD, x_irr), WS(TD, x_slf), WS(TD, part),
+    WS(TD, ones), WS(TD, d_t_irr), WS(TD, d_t_slf), WS(TD, d_tint_ibrdf), WS(TD, d_direct), WS(TD, d_weights)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -257,6 +270,8 @@ struct rc_handle {
   DevBuf geom_w;                             // rc_geometry_backward: pred_normals_layer kernel [64][3] + bias [3]
   uint64_t env_gen = 0;                      // layers_gen env_w was uploaded at
   DevBuf env_w;                              // rc_material_data_backward_env: the EnvMap's dense layers on the Flax layout
+  uint64_t thead_gen = 0;                    // layers_gen thead_w was uploaded at
+  DevBuf thead_w;                            // rc_transient_data_backward: the two per-bin head layers on the Flax layout
   float* pinned = nullptr;                   // rc_load_params_flat: page-locked landing buffer of the dense segments
   size_t pinned_bytes = 0;
   bool have_envmap = false;
@@ -1087,6 +1102,7 @@ void rc_destroy(rc_handle* h) {
   free_buf(h->data_w);
   free_buf(h->geom_w);
   free_buf(h->env_w);
+  free_buf(h->thead_w);
   if (h->pinned) (void)hipHostFree(h->pinned);
   drop_graphs(h);
   for (WsSet& s : h->ws) if (s.done) (void)hipEventDestroy(s.done);
@@ -1995,4 +2011,5 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_light_host.inc"
 #include "rc_material_bwd_host.inc"
 #include "rc_material_data_host.inc"
+#include "rc_transient_bwd_host.inc"
 #include "rc_optim_host.inc"

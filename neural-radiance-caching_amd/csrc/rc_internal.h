@@ -659,6 +659,36 @@ void rc_launch_envmap_out_bwd(const float* d_env, const float* raw, float rgb_bi
 // kparts K slices on blockIdx.y as rc_launch_gemm.  Same results as k_gemm up to the order of the sum over k.
 void rc_launch_gemm_tile(const RcGemmArgs& a, int kparts, hipStream_t st);
 
+// The time-resolved cache's data loss and the backward of k_transient_bins (rc_transient_bwd.hip)
+constexpr int kRcTdBins = 700, kRcTdHist = 3 * kRcTdBins;      // histogram entries of a ray: entry = 3 bin + channel
+constexpr int kRcTdLdSlf = kRcTdHist + 4;                      // row stride of dZ_slf: the alpha column and 3 pad floats, zeros
+constexpr int kRcTdChunkRays = 256;                            // rays whose dZ the workspace holds at a time
+struct RcTransLossArgs {
+  int64_t n; int32_t n_taps; const float* taps;            // rays; the temporal filter of the direct part (device)
+  const float* rgb, * gt;                                  // [n][700][3]
+  const float* rgb_nocorr, * gt_nocorr;                    // [n][700][3] or nullptr (rgb, gt)
+  const float* lossmult;                                   // [n] or nullptr (1)
+  float coef;                                              // data_loss_mult / (3 n): d loss / d (per ray-and-channel term)
+  float gauss;                                             // 2 constant_scale^2 data_loss_gauss_mult
+  float exponent, eps, clip_val, thresh;
+  int32_t use_gt, use_combined;
+  float* G, * Gt;                                          // [n][700][3] d loss / d rgb and the filter's transpose of it, written
+  float* loss_ray;                                         // [2][n] per-ray sums of the loss terms and of lossmult (rgb - gt)^2
+};
+struct RcTransBinsBwdArgs {
+  int64_t n_rays, r0, C;                                   // the batch; this launch's rays [r0, r0 + C)
+  const float* slf_feat, * irr_feat, * tshade, * weights;  // the forward's buffers (RcTransBinsArgs)
+  const float* w_slf, * b_slf, * w_irr, * b_irr;           // output_rgba_layer [128][2101], [2101]; transient_indirect_layer [64][2100], [2100]
+  float exposure, shift, max_dists, irradiance_bias, slf_rgb_bias, indirect_scale, rgb_max, light_near;
+  int32_t bin_zero_threshold_light, light_zero;
+  const float* G, * Gt;                                    // [n_rays][2100]
+  float* dz_irr, * dz_slf;                                 // [C 32][2100], [C 32][kRcTdLdSlf] written (zeros outside the live tiles)
+  float* x_irr, * x_slf;                                   // [C 32][64], [C 32][128] the heads' inputs, reference column order, written
+  float* d_tib, * d_direct, * d_weights;                   // [n_rays 32][3], [n_rays 32][3], [n_rays 32] written for the chunk's rays
+};
+void rc_launch_transient_loss(const RcTransLossArgs& a, hipStream_t st);
+void rc_launch_transient_bins_bwd(const RcTransBinsBwdArgs& a, hipStream_t st);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

@@ -86,15 +86,17 @@ int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void*
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
   if (!params) return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: null params");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_load_params_flat: not available on a time-resolved cache handle");
+  // a time-resolved handle loads its per-bin heads only (the other layouts' trainers do not run on it)
+  if (h->transient && layout != RC_LAYOUT_TRANSIENT_HEADS)
+    return fail(h, RC_ERR_UNSUPPORTED, "rc_load_params_flat: not available on a time-resolved cache handle");
   if (layout != RC_LAYOUT_SHADER && layout != RC_LAYOUT_LIGHT && layout != RC_LAYOUT_MATERIAL && layout != RC_LAYOUT_ENVMAP &&
-      (layout < 0 || layout >= h->cfg.num_levels))
+      layout != RC_LAYOUT_TRANSIENT_HEADS && (layout < 0 || layout >= h->cfg.num_levels))
     return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: layout must be a density level, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, "
-                                       "RC_LAYOUT_MATERIAL or RC_LAYOUT_ENVMAP");
+                                       "RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP or RC_LAYOUT_TRANSIENT_HEADS");
   int rc;
   if ((rc = layout_check(h, layout, "rc_load_params_flat"))) return rc;
   const std::vector<GradSeg> segs = layout_segments(h, layout);
-  const auto inv = dense_inventory(h->cfg, nullptr);
+  const auto inv = dense_inventory(h->cfg, h->transient ? &h->tcfg : nullptr);
   // classify: grid table (grid, level) or dense layer (checked against the inventory)
   struct Dst { int g = -1, l = -1; };
   std::vector<Dst> dst(segs.size());

@@ -124,7 +124,22 @@ std::vector<GradSeg> envmap_grad_segments(rc_handle* h) {
   return v;
 }
 
-// Layout ids of the ABI: a density level >= 0, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP.  `who`'s check that
+// The two per-bin head layers of the time-resolved cache (rc_transient_data_backward): transient_indirect_layer
+// [64, 3 n_bins], SurfaceLightField/output_rgba_layer [128, 3 n_bins + 1] (kernel, bias each)
+std::vector<GradSeg> transient_head_segments(rc_handle* h) {
+  const auto inv = dense_inventory(h->cfg, &h->tcfg);
+  std::vector<GradSeg> v;
+  int64_t off = 0;
+  for (const char* l : {"transient_indirect_layer", "SurfaceLightField/output_rgba_layer"}) {
+    const std::string path = std::string("params/Cache/Shader/") + l;
+    const auto& io = inv.at(path);
+    dense_grad_segments(v, off, path, io.first, io.second);
+  }
+  return v;
+}
+
+// Layout ids of the ABI: a density level >= 0, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP,
+// RC_LAYOUT_TRANSIENT_HEADS.  `who`'s check that
 // the handle has the layout (a density export maps a negative level to kNoLayout, so that it names no other layout).
 constexpr int kNoLayout = INT32_MIN;
 int layout_check(rc_handle* h, int layout, const std::string& who) {
@@ -136,6 +151,8 @@ int layout_check(rc_handle* h, int layout, const std::string& who) {
     if (h->grids[kMaterialGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, who + ": no material grid");
   } else if (layout == RC_LAYOUT_ENVMAP) {
     if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
+  } else if (layout == RC_LAYOUT_TRANSIENT_HEADS) {
+    if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs a time-resolved cache handle (rc_set_transient)");
   } else if (layout < 0 || layout >= h->cfg.num_levels) {
     return fail(h, RC_ERR_INVALID_ARG, who + ": bad level");
   }
@@ -149,6 +166,7 @@ std::vector<GradSeg> layout_segments(rc_handle* h, int layout) {
     case RC_LAYOUT_LIGHT: return light_grad_segments(h);
     case RC_LAYOUT_MATERIAL: return material_grad_segments(h);
     case RC_LAYOUT_ENVMAP: return envmap_grad_segments(h);
+    case RC_LAYOUT_TRANSIENT_HEADS: return transient_head_segments(h);
     default: return density_grad_segments(h, layout);
   }
 }
@@ -336,6 +354,13 @@ int64_t rc_shader_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT
 int64_t rc_light_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_LIGHT, "rc_light_grad_size"); }
 int64_t rc_material_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_MATERIAL, "rc_material_grad_size"); }
 int64_t rc_envmap_grad_size(rc_handle* h) { return layout_grad_size(h, RC_LAYOUT_ENVMAP, "rc_envmap_grad_size"); }
+
+int64_t rc_transient_head_grad_size(rc_handle* h) {
+  return layout_grad_size(h, RC_LAYOUT_TRANSIENT_HEADS, "rc_transient_head_grad_size");
+}
+int rc_transient_head_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  return layout_grad_layout(h, RC_LAYOUT_TRANSIENT_HEADS, segs, capacity, count, "rc_transient_head_grad_layout");
+}
 
 int rc_density_grad_layout(rc_handle* h, int32_t level, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
   return layout_grad_layout(h, level < 0 ? kNoLayout : level, segs, capacity, count, "rc_density_grad_layout");

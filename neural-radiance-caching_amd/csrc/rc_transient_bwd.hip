@@ -1,0 +1,352 @@
+// The time-resolved cache's data loss and the adjoint of the TransientVolumeIntegrator with the two per-bin head layers
+// (DESIGN.md §4.15): the kernels behind rc_transient_data_backward (rc_transient_bwd_host.inc).
+//
+//   k_transient_loss      train_utils.compute_transient_data_loss (internal/train_utils.py:531-640) with loss type
+//                         'rawnerf_transient_unbiased' (:725-732): one wavefront per ray turns rgb [700][3], gt, the optional
+//                         nocorr pair and lossmult into G = d loss / d rgb, the ray's loss and mse sums, and Gt = the temporal
+//                         filter's transpose applied to G (the forward's filter is a true 'same' convolution of the direct
+//                         part, render.py:406-417: its transpose is the correlation with the same taps).  The per-ray and
+//                         per-channel sums over the bins are wave reductions; the scalars are added up by
+//                         k_interlevel_reduce in a fixed order.
+//   k_transient_bins_bwd  the adjoint of k_transient_bins (rc_transient.hip), one wavefront per ray with the ray's G row in
+//                         LDS: the gather that transposes shift_direct (render.py:436-477; a sample that spilled into the next
+//                         ray of the batch reads that ray's Gt), the two-tap gather that transposes shift_map_coordinates
+//                         (render.py:480-496), the clamp / zero_invalid_bins masks, indirect_scale, softplus' and tint * ibrdf.
+//                         The heads' pre-activations are recomputed tile by tile as X W on v_mfma_f32_32x32x2_f32 (samples in
+//                         the rows, 32 histogram entries in the columns, as the forward; the weights come row-major from L2),
+//                         fp32 whatever the forward's arithmetic.  dZ of both heads goes to the chunk's buffers, where
+//                         k_gemm_tile picks it up for dW += X^T dZ and dX = dZ W^T.
+#include <hip/hip_runtime.h>
+
+#include "rc_internal.h"
+
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int kB = kRcTdBins, kH = kRcTdHist;
+constexpr int kPerLane = (kH + 63) / 64;       // histogram entries of a lane
+constexpr int kTiles = (kH + 31) / 32;         // 66 column tiles of 32 entries
+constexpr int kWavesPerBlock = 4;
+constexpr int kBinsWaves = 1;          // rays (waves) of a k_transient_bins_bwd workgroup
+
+__device__ __forceinline__ float half_sum(float v) {      // over the 32 lanes of a half-wave, every lane gets the sum
+#pragma unroll
+  for (int d = 16; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_total(float v) { return half_sum(v) + __shfl_xor(half_sum(v), 32, 64); }
+
+__device__ __forceinline__ float clip0(float x, float hi) { return fminf(fmaxf(x, 0.0f), hi); }
+__device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
+// d jnp.clip(x, 0, hi) / dx = d minimum(maximum(x, 0), hi): each tie passes half
+__device__ __forceinline__ float clip_grad(float x, float hi) {
+  const float lo_g = x > 0.0f ? 1.0f : (x == 0.0f ? 0.5f : 0.0f);
+  const float y = fmaxf(x, 0.0f);
+  const float hi_g = y < hi ? 1.0f : (y == hi ? 0.5f : 0.0f);
+  return lo_g * hi_g;
+}
+
+__global__ __launch_bounds__(kWavesPerBlock * 64) void k_transient_loss(RcTransLossArgs a) {
+  __shared__ float sG[kWavesPerBlock][kH];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int64_t ray = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  const bool ray_ok = ray < a.n;
+  if (!ray_ok) ray = a.n - 1;
+  const float* rgb = a.rgb + ray * kH;
+  const float* gt = a.gt + ray * kH;
+  const float* rgbn = a.rgb_nocorr ? a.rgb_nocorr + ray * kH : rgb;      // train_utils.py:604-610
+  const float* gtn = a.gt_nocorr ? a.gt_nocorr + ray * kH : gt;
+  float dn[kPerLane];
+  // per channel: sum of the clipped colour, of d, of dn, of d dn, of d^2, count of gt > thresh
+  float acc[3][6];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int q = 0; q < 6; ++q) acc[c][q] = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) {
+    const int e = lane + 64 * k;
+    const bool ok = e < kH;
+    const int ec = ok ? e : 0;
+    const float r = rgb[ec], g = gt[ec];
+    const float d = r - g, dnv = rgbn[ec] - gtn[ec];
+    dn[k] = dnv;
+    // _get_rgb_clip_for_rawnerf (train_utils.py:369-393): the cache stage's rendering has no "cache_rgb": the pass's own rgb
+    float cl;
+    if (a.use_gt) cl = clip0(g, a.clip_val);
+    else {
+      cl = clip0(r, a.clip_val);
+      if (a.use_combined) cl = clip0(fmaxf(cl, g), a.clip_val);
+    }
+    const int ch = e % 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const bool m = ok && ch == c;
+      acc[c][0] += m ? cl : 0.0f;
+      acc[c][1] += m ? d : 0.0f;
+      acc[c][2] += m ? dnv : 0.0f;
+      acc[c][3] += m ? d * dnv : 0.0f;
+      acc[c][4] += m ? d * d : 0.0f;
+      acc[c][5] += (m && g > a.thresh) ? 1.0f : 0.0f;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int q = 0; q < 6; ++q) acc[c][q] = wave_total(acc[c][q]);
+  const float lm0 = a.lossmult ? a.lossmult[ray] : 1.0f;
+  float gmul[3], gadd[3], loss = 0.0f, mse = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float lm = acc[c][5] > 0.0f ? 0.0f : lm0;                       // train_utils.py:586-590
+    const float p = a.exponent == 1.0f ? acc[c][0] : powf(acc[c][0], a.exponent);
+    const float s = 1.0f / (p + a.eps);                                   // train_utils.py:217
+    // 2 d sg(dn) s per bin, and the gauss constant row (0.5 sum d)(0.5 sum dn) 2 s gauss_mult / n_bins on every bin
+    loss += lm * (s * (2.0f * acc[c][3] + a.gauss * (acc[c][1] * acc[c][2])));
+    mse += lm * acc[c][4];
+    gmul[c] = a.coef * (lm * s);
+    gadd[c] = a.gauss * acc[c][2];                // the row is divided by n_bins, then added to all n_bins bins: once
+  }
+  if (ray_ok && lane == 0) { a.loss_ray[ray] = loss; a.loss_ray[a.n + ray] = mse; }
+  float* sg = sG[wave];
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) {
+    const int e = lane + 64 * k;
+    if (e < kH) {
+      const int ch = e % 3;
+      const float gm = ch == 0 ? gmul[0] : (ch == 1 ? gmul[1] : gmul[2]);
+      const float ga = ch == 0 ? gadd[0] : (ch == 1 ? gadd[1] : gadd[2]);
+      const float v = gm * (2.0f * dn[k] + ga);
+      sg[e] = v;
+      if (ray_ok) a.G[ray * kH + e] = v;
+    }
+  }
+  __syncthreads();
+  // forward: out[b] = sum_k taps[k] in[b - (k - half)]  ->  d in[j] = sum_k taps[k] G[j + (k - half)]
+  const int half = (a.n_taps - 1) / 2;
+  for (int e = lane; e < kH; e += 64) {
+    float v;
+    if (a.n_taps > 0) {
+      v = 0.0f;
+      for (int k = 0; k < a.n_taps; ++k) {
+        const int j = e + 3 * (k - half);
+        if (j >= 0 && j < kH) v += a.taps[k] * sg[j];
+      }
+    } else {
+      v = sg[e];
+    }
+    if (ray_ok) a.Gt[ray * kH + e] = v;
+  }
+}
+
+// per-sample parameters of a ray in LDS
+enum { P_W = 0, P_DIND, P_LO, P_HI, P_TIB0, P_TIB1, P_TIB2, P_DW, P_DT0, P_DT1, P_DT2, P_COUNT };
+
+__global__ __launch_bounds__(kBinsWaves * 64) void k_transient_bins_bwd(RcTransBinsBwdArgs a) {
+  __shared__ float sG[kBinsWaves][kH];
+  __shared__ float sP[kBinsWaves][P_COUNT][32];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int fl = lane & 31, h = lane >> 5;
+  int64_t rl = (int64_t)blockIdx.x * kBinsWaves + wave;      // ray of the chunk
+  const bool ray_ok = rl < a.C;
+  if (!ray_ok) rl = a.C - 1;
+  const int64_t ray = a.r0 + rl;
+  const int64_t n = a.n_rays * 32;
+  float* sg = sG[wave];
+  float (*sp)[32] = sP[wave];
+  for (int e = lane; e < kH; e += 64) sg[e] = a.G[ray * kH + e];
+  int win_lo = kB, win_hi = -1;
+  float dir_dw = 0.0f;
+  if (lane < 32) {
+    const int64_t p = ray * 32 + lane;
+    const float ld = a.tshade[RC_TS_LDIST * n + p], w = a.weights[p], cdist = a.tshade[RC_TS_CAMDIST * n + p];
+    const float rd = a.tshade[RC_TS_RDIST * n + p];
+    sp[P_W][lane] = w;
+    sp[P_DIND][lane] = (rd + a.shift) / a.exposure;                   // k_transient_bins' P_DIND
+    sp[P_TIB0][lane] = a.tshade[(RC_TS_TIB + 0) * n + p];
+    sp[P_TIB1][lane] = a.tshade[(RC_TS_TIB + 1) * n + p];
+    sp[P_TIB2][lane] = a.tshade[(RC_TS_TIB + 2) * n + p];
+    // the window of bins zero_invalid_bins keeps, with the comparisons of k_transient_bins
+    const bool kill = a.light_zero && ld < a.light_near;
+    auto close = [&](int b) { return (float)(b + a.bin_zero_threshold_light) * a.exposure < ld; };
+    auto far = [&](int b) { return ((float)b * a.exposure + cdist) > a.max_dists; };
+    int lo = (int)ceilf(ld / a.exposure) - a.bin_zero_threshold_light;
+    lo = min(max(lo, 0), kB);
+    while (lo > 0 && !close(lo - 1)) --lo;
+    while (lo < kB && close(lo)) ++lo;
+    int hi = (int)floorf((a.max_dists - cdist) / a.exposure);
+    hi = min(max(hi, -1), kB - 1);
+    while (hi < kB - 1 && !far(hi + 1)) ++hi;
+    while (hi >= 0 && far(hi)) --hi;
+    if (kill) { lo = kB; hi = -1; }
+    sp[P_LO][lane] = __int_as_float(lo);
+    sp[P_HI][lane] = __int_as_float(hi);
+    if (lo <= hi) { win_lo = lo; win_hi = hi; }
+    // ---- the direct scatter's adjoint (shift_direct, render.py:436-477): a gather of Gt at the sample's two bins; bins
+    //      [700, 1400) are the next ray's (the flattened [n 700] histogram), dropped behind the last ray as in the forward
+    const float d = (ld + rd) / a.exposure + a.shift / a.exposure;
+    const float low = fmaxf(floorf(d), 0.0f), high = ceilf(d);
+    const float w_high = d - low, w_low = 1.0f - w_high;
+    auto gt3 = [&](float bin, float (&o)[3]) {
+      o[0] = o[1] = o[2] = 0.0f;
+      if (!(bin >= 0.0f && bin < (float)(2 * kB))) return;
+      int b = (int)bin;
+      int64_t r = ray;
+      if (b >= kB) { b -= kB; r += 1; }
+      if (r >= a.n_rays) return;
+      const float* g = a.Gt + r * kH + 3 * b;
+      o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
+    };
+    float gl[3], gh[3];
+    gt3(low, gl);
+    gt3(high, gh);
+    float dd[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float gat = w_low * gl[c] + w_high * gh[c];
+      const float direct = a.tshade[(RC_TS_DD + c) * n + p] + a.tshade[(RC_TS_DS + c) * n + p];
+      dd[c] = w * gat;
+      dir_dw += direct * gat;
+    }
+    if (ray_ok) {
+      a.d_direct[3 * p] = dd[0]; a.d_direct[3 * p + 1] = dd[1]; a.d_direct[3 * p + 2] = dd[2];
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    win_lo = min(win_lo, __shfl_xor(win_lo, d, 64));
+    win_hi = max(win_hi, __shfl_xor(win_hi, d, 64));
+  }
+  // tiles outside the bins any sample of the ray keeps: dZ is exactly zero there (the forward's tile-range skip)
+  const int T_lo = win_lo <= win_hi ? (3 * win_lo) / 32 : kTiles;
+  const int T_hi = win_lo <= win_hi ? (3 * win_hi + 2) / 32 : -1;
+  // the heads' inputs of this ray's 32 samples: MFMA A operands (k_transient_shader's accumulator order)
+  float xs[64], xi[32];
+#pragma unroll
+  for (int s = 0; s < 64; ++s) xs[s] = a.slf_feat[(ray * 64 + s) * 64 + lane];
+#pragma unroll
+  for (int s = 0; s < 32; ++s) xi[s] = a.irr_feat[(ray * 32 + s) * 64 + lane];
+  // ... and row-major in the reference's column order for the GEMMs: step s, half h holds column feat(s) + 4 h
+  if (ray_ok) {
+    float* xo = a.x_slf + (rl * 32 + fl) * 128 + 4 * h;
+#pragma unroll
+    for (int s = 0; s < 64; ++s) xo[32 * (s >> 4) + (s & 3) + 8 * ((s & 15) >> 2)] = xs[s];
+    float* io = a.x_irr + (rl * 32 + fl) * 64 + 4 * h;
+#pragma unroll
+    for (int s = 0; s < 32; ++s) io[32 * (s >> 4) + (s & 3) + 8 * ((s & 15) >> 2)] = xi[s];
+  }
+  __syncthreads();
+  float dws[16], dtib[3][16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { dws[r] = 0.0f; dtib[0][r] = 0.0f; dtib[1][r] = 0.0f; dtib[2][r] = 0.0f; }
+  float* const zi = a.dz_irr + (rl * 32 + 4 * h) * (int64_t)kH;
+  float* const zs = a.dz_slf + (rl * 32 + 4 * h) * (int64_t)kRcTdLdSlf;
+  for (int T = 0; T < kTiles; ++T) {
+    const int f = T * 32 + fl;
+    const bool fok = f < kH;
+    if (T < T_lo || T > T_hi) {
+      if (ray_ok) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = (r & 3) + 8 * (r >> 2);
+          if (fok) zi[(int64_t)i * kH + f] = 0.0f;
+          if (f < kRcTdLdSlf) zs[(int64_t)i * kRcTdLdSlf + f] = 0.0f;
+        }
+      }
+      continue;
+    }
+    const int fc = fok ? f : kH - 1;
+    // ---- X W of the tile for both heads, two accumulation chains side by side
+    f32x16 as, ai;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { as[r] = 0.0f; ai[r] = 0.0f; }
+    const float* ps = a.w_slf + (int64_t)(4 * h) * (kH + 1) + fc;
+    const float* pi = a.w_irr + (int64_t)(4 * h) * kH + fc;
+#pragma unroll
+    for (int g = 0; g < 32; ++g) {
+      const int s0 = 2 * g, s1 = 2 * g + 1;
+      const int k0 = 32 * (s0 >> 4) + (s0 & 3) + 8 * ((s0 & 15) >> 2), k1 = 32 * (s1 >> 4) + (s1 & 3) + 8 * ((s1 & 15) >> 2);
+      const int kg = 32 * (g >> 4) + (g & 3) + 8 * ((g & 15) >> 2);
+      as = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[s0], ps[(int64_t)k0 * (kH + 1)], as, 0, 0, 0);
+      ai = __builtin_amdgcn_mfma_f32_32x32x2f32(xi[g], pi[(int64_t)kg * kH], ai, 0, 0, 0);
+      as = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[s1], ps[(int64_t)k1 * (kH + 1)], as, 0, 0, 0);
+    }
+    const float bs = a.b_slf[fc] + a.slf_rgb_bias, bi = a.b_irr[fc] + a.irradiance_bias;
+    const int b = f / 3, c = f - 3 * b;
+    const float b_f = (float)b;
+    const int b_live = fok ? b : -(1 << 29);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int lo = __float_as_int(sp[P_LO][i]), hi = __float_as_int(sp[P_HI][i]);
+      const bool live = b_live >= lo && b_live <= hi;
+      float dzi = 0.0f, dzs = 0.0f;
+      if (__builtin_amdgcn_ballot_w64(live) != 0ull) {
+        const float w = sp[P_W][i], dmove = sp[P_DIND][i];
+        const float tib = sp[P_TIB0 + c][i];
+        // the time shift's transpose (shift_map_coordinates): entry b reaches the targets y0 = b + floor(d) and y0 + 1
+        // with the weights the targets compute (k_transient_bins' wa, and its wb as seen from the source)
+        const float fd = floorf(dmove);
+        const int e0 = f + 3 * (int)fminf(fmaxf(fd, -1.0e6f), 1.0e6f);
+        const float t = (b_f + fd) - dmove;
+        const bool at_b = t == b_f;
+        const float wa = at_b ? 1.0f : t - (b_f - 1.0f);
+        const float t2 = ((b_f + fd) + 1.0f) - dmove;
+        const float wb = 1.0f - (t2 - b_f);
+        const float g0 = (unsigned)e0 < (unsigned)kH ? sg[e0] : 0.0f;
+        const float g1 = (unsigned)(e0 + 3) < (unsigned)kH ? sg[e0 + 3] : 0.0f;
+        const float gsum = wa * g0 + wb * g1;
+        const float zi_ = ai[r] + bi, zs_ = as[r] + bs;
+        const float spi = softplus_f(zi_), sps = softplus_f(zs_);
+        const float ref = fmaxf(sps, 0.0f);
+        const float diff_pre = spi * a.indirect_scale, spec_pre = (tib * ref) * a.indirect_scale;
+        const float diff = live ? clip0(diff_pre, a.rgb_max) : 0.0f, spec = live ? clip0(spec_pre, a.rgb_max) : 0.0f;
+        const float g = w * gsum;
+        const float gd = live ? (g * clip_grad(diff_pre, a.rgb_max)) * a.indirect_scale : 0.0f;
+        const float gs = live ? (g * clip_grad(spec_pre, a.rgb_max)) * a.indirect_scale : 0.0f;
+        const float ref_g = sps > 0.0f ? 1.0f : (sps == 0.0f ? 0.5f : 0.0f);      // clip(softplus, 0, inf)
+        dzi = gd * sigmoid_f(zi_);
+        dzs = ((gs * tib) * ref_g) * sigmoid_f(zs_);
+        dws[r] += gsum * (diff + spec);
+        const float dt = gs * ref;
+        dtib[0][r] += c == 0 ? dt : 0.0f;
+        dtib[1][r] += c == 1 ? dt : 0.0f;
+        dtib[2][r] += c == 2 ? dt : 0.0f;
+      }
+      if (ray_ok) {
+        const int ir = (r & 3) + 8 * (r >> 2);
+        if (fok) zi[(int64_t)ir * kH + f] = dzi;
+        if (f < kRcTdLdSlf) zs[(int64_t)ir * kRcTdLdSlf + f] = fok ? dzs : 0.0f;
+      }
+    }
+  }
+  // ---- per-sample sums over the ray's entries (the 32 lanes of a half-wave), in a fixed order
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+    const float v0 = half_sum(dws[r]), v1 = half_sum(dtib[0][r]), v2 = half_sum(dtib[1][r]), v3 = half_sum(dtib[2][r]);
+    if (fl == 0) { sp[P_DW][i] = v0; sp[P_DT0][i] = v1; sp[P_DT1][i] = v2; sp[P_DT2][i] = v3; }
+  }
+  __syncthreads();
+  if (lane < 32 && ray_ok) {
+    const int64_t p = ray * 32 + lane;
+    a.d_weights[p] = dir_dw + sp[P_DW][lane];
+    a.d_tib[3 * p] = sp[P_DT0][lane]; a.d_tib[3 * p + 1] = sp[P_DT1][lane]; a.d_tib[3 * p + 2] = sp[P_DT2][lane];
+  }
+}
+
+}  // namespace
+
+void rc_launch_transient_loss(const RcTransLossArgs& a, hipStream_t st) {
+  if (a.n <= 0) return;
+  hipLaunchKernelGGL(k_transient_loss, dim3((unsigned)((a.n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * 64), 0,
+                     st, a);
+}
+
+void rc_launch_transient_bins_bwd(const RcTransBinsBwdArgs& a, hipStream_t st) {
+  if (a.C <= 0) return;
+  hipLaunchKernelGGL(k_transient_bins_bwd, dim3((unsigned)((a.C + kBinsWaves - 1) / kBinsWaves)),
+                     dim3(kBinsWaves * 64), 0, st, a);
+}

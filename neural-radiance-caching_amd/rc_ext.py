@@ -173,6 +173,7 @@ RC_LAYOUT_SHADER = -1
 RC_LAYOUT_LIGHT = -2
 RC_LAYOUT_MATERIAL = -3
 RC_LAYOUT_ENVMAP = -4
+RC_LAYOUT_TRANSIENT_HEADS = -5
 
 
 class rc_light_sampling_loss(C.Structure):
@@ -188,6 +189,12 @@ class rc_material_data_loss(C.Structure):
     _fields_ = [("mult", C.c_float), ("weight", C.c_float), ("exponent", C.c_float), ("eps", C.c_float),
                 ("clip_val", C.c_float), ("thresh", C.c_float), ("use_gt_rawnerf", C.c_int32),
                 ("use_combined_rawnerf", C.c_int32), ("use_norm_rawnerf", C.c_int32)]
+
+
+class rc_transient_data_loss(C.Structure):
+    _fields_ = [("mult", C.c_float), ("gauss_mult", C.c_float), ("gauss_constant_scale", C.c_float), ("exponent", C.c_float),
+                ("eps", C.c_float), ("clip_val", C.c_float), ("thresh", C.c_float), ("use_gt_rawnerf", C.c_int32),
+                ("use_combined_rawnerf", C.c_int32)]
 
 
 class rc_adam_buffer(C.Structure):
@@ -212,10 +219,11 @@ EXPORTS = (
     "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
     "rc_light_regularizer", "rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
     "rc_material_regularizer", "rc_material_data_backward", "rc_envmap_grad_size", "rc_envmap_grad_layout",
-    "rc_material_data_backward_env", "rc_cast_rays_multi", "rc_train_batch",
+    "rc_material_data_backward_env", "rc_cast_rays_multi", "rc_train_batch", "rc_transient_head_grad_size",
+    "rc_transient_head_grad_layout", "rc_transient_data_backward",
 )
 
-# Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap": the C functions of its size and of its
+# Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap", "transient_heads": the C functions of its size and of its
 # segments (a density level is their first argument) and its RC_LAYOUT_* id (rc_load_params_flat; a level is its own).
 _GRAD_LAYOUTS = {
     int: ("rc_density_grad_size", "rc_density_grad_layout", None),
@@ -223,6 +231,7 @@ _GRAD_LAYOUTS = {
     "light": ("rc_light_grad_size", "rc_light_grad_layout", RC_LAYOUT_LIGHT),
     "material": ("rc_material_grad_size", "rc_material_grad_layout", RC_LAYOUT_MATERIAL),
     "envmap": ("rc_envmap_grad_size", "rc_envmap_grad_layout", RC_LAYOUT_ENVMAP),
+    "transient_heads": ("rc_transient_head_grad_size", "rc_transient_head_grad_layout", RC_LAYOUT_TRANSIENT_HEADS),
 }
 _LAYOUT_KEYS = {row[2]: key for key, row in _GRAD_LAYOUTS.items() if key is not int}
 
@@ -378,6 +387,14 @@ def load_library():
                                                   C.POINTER(rc_material_data_loss), C.c_float, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p]
     lib.rc_material_data_backward_env.restype = C.c_int
+    lib.rc_transient_head_grad_size.argtypes = [C.c_void_p]
+    lib.rc_transient_head_grad_size.restype = C.c_int64
+    lib.rc_transient_head_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.rc_transient_head_grad_layout.restype = C.c_int
+    lib.rc_transient_data_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(rc_transient_data_loss), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rc_transient_data_backward.restype = C.c_int
     lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.rc_hashgrid_backward.restype = C.c_int
     lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
@@ -1031,7 +1048,8 @@ class RadianceCache:
         self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), stream))
 
     def load_params_flat(self, layout, params, stream_handle=None):
-        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light", "material" or "envmap")
+        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light", "material", "envmap"
+        or, on a time-resolved handle, "transient_heads")
         from a flat
         float32 cuda buffer in that layout -- table copies ordered on the current stream, the dense layers in one copy
         to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
@@ -1260,6 +1278,63 @@ class RadianceCache:
         self._check(self.lib.rc_render_transient(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, shadow_p, C.byref(cout), stream))
         self._keep = [held]
         return res
+
+    def transient_head_grad_layout(self):
+        """rc_transient_head_grad_layout: [(tensor name, offset, shape)] of the time-resolved cache's per-bin head layers
+        (params/Cache/Shader/transient_indirect_layer, .../SurfaceLightField/output_rgba_layer), and its size in floats."""
+        return self._grad_layout("transient_heads")
+
+    def transient_data_backward(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]], gt, rgb_nocorr=None,
+                                gt_nocorr=None, lossmult=None, cfg=None, grad=None, stream_handle=None):
+        """rc_transient_data_backward: render_transient with the same rays (lights and cam_origins included) / randoms
+        ({"jitter": [u0, u1, u2]} or None), the time-resolved data loss against gt ([n, n_bins, 3]) with the constants of
+        cfg (config.TransientDataLossConfig) and its gradient w.r.t. the two per-bin head layers
+        (transient_head_grad_layout).  rgb_nocorr / gt_nocorr: [n, n_bins, 3] or None (this render, gt).
+        grad: flat buffer to accumulate into (allocated zeroed when None); grad=False leaves the heads' gradient out (the
+        loss and the "td:" adjoints are still computed).  Returns (grad flat or None, losses [2] cuda tensor: loss, mse)."""
+        from .config import TransientDataLossConfig
+
+        torch = self._torch
+        cfg = TransientDataLossConfig() if cfg is None else cfg
+        if (cfg.loss_type != "rawnerf_transient_unbiased" or tuple(cfg.transient_gauss_sigma_scales) or cfg.mask_lossmult
+                or cfg.clip_eval or cfg.use_itof):
+            raise NotImplementedError("transient data loss: only rawnerf_transient_unbiased with the constant gauss row")
+        r, held, n = self._rays_struct(rays)
+        cam = self._dev(rays["cam_origins"]).reshape(-1, 3)
+        held["cam_origins"] = cam
+        rnd_p = None
+        if randoms is not None and randoms.get("jitter") is not None:
+            rnd_p = self._jitter_struct(randoms["jitter"], held, n)
+        lm = self._lossmult(lossmult, held, n)
+        # without a time-resolved config there is no n_bins to check against: the call itself refuses such a handle
+        count = None if self.cfg.transient is None else n * self.cfg.transient.n_bins * 3
+
+        def hist(x, what):
+            if x is None:
+                return None
+            t = self._dev(x).reshape(-1)
+            if count is not None and t.numel() != count:
+                raise ValueError(f"{what} must hold [n, n_bins, 3] values")
+            held[what] = t
+            return t.data_ptr()
+
+        gt_p, rn_p, gn_p = hist(gt, "gt"), hist(rgb_nocorr, "rgb_nocorr"), hist(gt_nocorr, "gt_nocorr")
+        if gt_p is None:
+            raise ValueError("gt is required")
+        c = rc_transient_data_loss(mult=float(cfg.data_loss_mult), gauss_mult=float(cfg.data_loss_gauss_mult),
+                                   gauss_constant_scale=float(cfg.transient_gauss_constant_scale),
+                                   exponent=float(cfg.rawnerf_exponent), eps=float(cfg.rawnerf_eps),
+                                   clip_val=float(cfg.clip_val), thresh=float(cfg.loss_thresh),
+                                   use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
+                                   use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)))
+        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("transient_heads"))
+        losses = torch.zeros(2, dtype=torch.float32, device=f"cuda:{self.device}")
+        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        self._check(self.lib.rc_transient_data_backward(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, gt_p, rn_p, gn_p,
+                                                        None if lm is None else lm.data_ptr(), C.byref(c),
+                                                        None if flat is None else flat.data_ptr(), losses.data_ptr(), stream))
+        self._keep = [held]
+        return flat, losses
 
     def material_grad_layout(self):
         """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid

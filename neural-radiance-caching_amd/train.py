@@ -64,6 +64,15 @@ The material network, second piece of that stage:
     rc_material_regularizer);
   * `MaterialOptimizer(rc, cfg)` / `material_step(...)` -> the optimizer state and step on the material layout (group
     "MaterialShader").  The material data loss's gradient (the Disney-GGX integration) is not part of these.
+
+The time-resolved cache, first piece of its training:
+
+  * `transient_data_grads(rc, rays, cam_origins, jitters, gt, ...)` -> the transient data loss
+    (train_utils.compute_transient_data_loss, 'rawnerf_transient_unbiased') of rc_render_transient's histograms and the exact
+    gradient of the two per-bin head layers (rc_transient_data_backward); the adjoints at the rest of the shader stay in
+    the handle's "td:" workspace;
+  * `TransientHeadOptimizer(rc, cfg)` / `transient_head_step(...)` -> the optimizer state and step on that layout
+    (transient_indirect_layer in group "Cache", SurfaceLightField/output_rgba_layer in group "SurfaceLightField").
 """
 from __future__ import annotations
 
@@ -74,7 +83,7 @@ import numpy as np
 
 from . import prng
 from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaterialDataLossConfig,
-                     MaterialSmoothnessConfig, OptimizerConfig)
+                     MaterialSmoothnessConfig, OptimizerConfig, TransientDataLossConfig)
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -635,3 +644,45 @@ def material_env_stage_step(rc, opt_material: MaterialOptimizer, opt_envmap: Env
         else:
             g.zero_()
     return losses
+
+
+# ---- the time-resolved cache ---------------------------------------------------------------------------------------
+
+def transient_data_grads(rc, rays, cam_origins, jitters, gt, rgb_nocorr=None, gt_nocorr=None, lossmult=None, flat=None,
+                         cfg: TransientDataLossConfig = TransientDataLossConfig()):
+    """The time-resolved cache's data loss on a batch and its gradient of the two per-bin head layers:
+    compute_transient_data_loss of rc_render_transient's rgb against gt ([n, n_bins, 3]) times data_loss_mult, accumulated
+    into `flat` (layout rc.transient_head_grad_layout(); allocated zeroed when None).  rays: render_transient's fields
+    (lights included); cam_origins: [n, 3] (replaces rays["cam_origins"] when given); jitters: per-level [n] sampler jitter
+    (None = deterministic); rgb_nocorr / gt_nocorr: the unbiased loss's second pair (None: this render, gt).
+    -> (flat, {"data": ..., "mse": ...}), 0-d cuda tensors: the reference's losses_flat key and its "mses" stat."""
+    rays = dict(rays)
+    if cam_origins is not None:
+        rays["cam_origins"] = cam_origins
+    randoms = None if jitters is None else {"jitter": list(jitters)}
+    flat, losses = rc.transient_data_backward(rays, randoms, gt, rgb_nocorr, gt_nocorr, lossmult, cfg, flat)
+    return flat, {"data": losses[0], "mse": losses[1]}
+
+
+class TransientHeadOptimizer(CacheStageOptimizer):
+    """The optimizer state of the time-resolved cache's two per-bin head layers on the device: flat params, mu, nu and
+    gradients in the layout rc.transient_head_grad_layout() (key "transient_heads") and the optax count.
+    param_group puts transient_indirect_layer in "Cache" and SurfaceLightField/output_rgba_layer in "SurfaceLightField" (the
+    last listed prefix on the path wins), as create_optimizer does.  clip_gradients takes its norm per top-level module and
+    both layers sit under Cache, whose other tensors this optimizer does not hold: with grad_max_norm > 0 that norm cannot
+    be formed here, so it is refused.  A step is ONE rc_adam_update over this buffer, then rc_load_params_flat
+    (RC_LAYOUT_TRANSIENT_HEADS).  init_from / params_dict / state_dict / load_state_dict as CacheStageOptimizer."""
+
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig()):
+        if cfg.grad_max_norm > 0:
+            raise NotImplementedError("TransientHeadOptimizer: grad_max_norm needs the norm over all of params/Cache")
+        super().__init__(rc, cfg, ["transient_heads"])
+
+
+def transient_head_step(rc, opt: TransientHeadOptimizer, rays, cam_origins, jitters, gt, rgb_nocorr=None, gt_nocorr=None,
+                        lossmult=None, group=None, cfg: TransientDataLossConfig = TransientDataLossConfig()):
+    """One train step of the per-bin heads on the transient data loss: transient_data_grads into the optimizer's zeroed
+    gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().  -> the losses dict of
+    transient_data_grads."""
+    return _train_step(opt, group, lambda tf: transient_data_grads(rc, rays, cam_origins, jitters, gt, rgb_nocorr, gt_nocorr,
+                                                                   lossmult, opt.grads["transient_heads"], cfg))
