@@ -58,19 +58,30 @@ def data_loss(rgb, gt, cache_rgb, lossmult=None, weight=0.1, mult=1.0, exponent=
     return weight * mult * (lm * (2.0 * d * d.detach() * s)).mean()
 
 
-def loop_loss(rgb, gt, cache_rgb, lossmult=None, weight=0.1, mult=1.0, exponent=1.0, eps=1e-2, clip_val=1e4, thresh=1e6):
-    """The reference's expression (use_combined_rawnerf) as plain loops over rays and channels (floats)."""
+def loop_loss(rgb, gt, cache_rgb, lossmult=None, weight=0.1, mult=1.0, exponent=1.0, eps=1e-2, clip_val=1e4, thresh=1e6,
+              use_gt=False, use_combined=True, use_norm=False):
+    """The reference's expression as plain loops over rays and channels (floats), with _get_rgb_clip_for_rawnerf's three
+    switches (train_utils.py:369-395): use_gt takes clip(gt), else clip(cache_rgb), combined with gt when use_combined;
+    use_norm replaces every channel of a ray by the norm over its three."""
     rgb, gt, c = (np.asarray(t, np.float64) for t in (rgb, gt, cache_rgb))
     n = len(rgb)
     tot = 0.0
     for i in range(n):
+        cr = [0.0, 0.0, 0.0]
+        for k in range(3):
+            if use_gt:
+                cr[k] = min(max(gt[i, k], 0.0), clip_val)
+            else:
+                cr[k] = min(max(c[i, k], 0.0), clip_val)
+                if use_combined:
+                    cr[k] = min(max(max(cr[k], gt[i, k]), 0.0), clip_val)
+        if use_norm:
+            cr = [math.sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2])] * 3
         for k in range(3):
             lm = 1.0 if lossmult is None else float(lossmult[i])
             if gt[i, k] > thresh:
                 lm = 0.0
-            cr = min(max(c[i, k], 0.0), clip_val)
-            cr = min(max(max(cr, gt[i, k]), 0.0), clip_val)
-            s = 1.0 / (cr ** exponent + eps)
+            s = 1.0 / (cr[k] ** exponent + eps)
             d = rgb[i, k] - gt[i, k]
             tot += lm * 2.0 * d * d * s
     return weight * mult * tot / (3 * n)

@@ -29,43 +29,15 @@ def _buffers(rc, n):
     return lc.buffers(rc, "d:", n, ("density", "tdist", "means", "h64", "app", "d_density"))
 
 
-def _restated(w, b, rays, gt, lm, dtype, mult=1.0):
-    t = lambda a: torch.from_numpy(np.asarray(a)).to(dtype)
-    h64 = t(b["h64"]).requires_grad_(True)
-    app = t(b["app"]).requires_grad_(True)
-    dens = t(b["density"]).requires_grad_(True)
-    taps = {}
-    loss, _ = dr.data_loss(w, CFG, h64, app, dens, t(b["tdist"]), t(rays["directions"]), t(rays["viewdirs"]), t(gt), t(lm),
-                           mult=mult, taps=taps)
-    loss.backward()
-    return float(loss.detach()), dict(d_density=dens.grad, dfeat=h64.grad, dapp=app.grad, dp3=taps["pred_raw"].grad)
-
-
 def test_kernel_against_restatement():
     """Loss, d density, d feature64, d app32 and d pred_raw within 3x the fp32 restatement's distance from fp64 (plus a
-    small floor), on the HIP forward's d: buffers, lossmult with zeros."""
+    small floor), on the HIP forward's d: buffers, lossmult with zeros (loss_cases.data_compare)."""
     rc = common.make_rc()
     n = 1000
     rays, jit, gt = _case(n)
     lm = lc.lossmult(n)
     (_, _), loss = rc.data_backward(rays, gt, jit, 0.4, lm)
-    loss = float(loss.cpu())
-    b = _buffers(rc, n)
-    np_ = n * S2
-    got = dict(d_density=b["d_density"], dfeat=rc.workspace("d:dfeat")[: np_ * 64].reshape(n, S2, 64),
-               dapp=rc.workspace("d:dapp")[: np_ * 32].reshape(n, S2, 32), dp3=rc.workspace("d:dp3")[: np_ * 3].reshape(n, S2, 3))
-    l64, g64 = _restated(common.weights_torch(dtype=torch.float64), b, rays, gt, lm, torch.float64)
-    l32, g32 = _restated(common.weights_torch(dtype=torch.float32), b, rays, gt, lm, torch.float32)
-    err, tol = lc.bound(np.float64(loss), l64, l32, 1e-6 * l64)
-    assert err <= tol, ("loss", loss, l64, l32)
-    for k in ("d_density", "dfeat", "dapp", "dp3"):
-        r64, r32 = g64[k].numpy(), g32[k].double().numpy()
-        scale = float(np.abs(r64).max())
-        assert scale > 0, k
-        err, tol = lc.bound(got[k].astype(np.float64), r64, r32, 2e-5 * scale)
-        assert err <= tol, (k, err, tol, scale)
-    assert np.all(b["d_density"][lm == 0.0] == 0.0)
-    assert np.all(got["dfeat"][lm == 0.0] == 0.0)
+    lc.data_compare(rc, n, rays, gt, lm, float(loss.cpu()))
 
 
 def test_layout_matches_the_python_mirror():

@@ -28,16 +28,7 @@ def _buffers(rc, n):
 
 
 def _restated(w, b, rays, lm, dtype):
-    t = lambda a: torch.from_numpy(np.asarray(a)).to(dtype)
-    dens = t(b["density"]).requires_grad_(True)
-    kern = t(w[f"params/Cache/Sampler/MLP_{L2}/pred_normals_layer/kernel"])
-    bias = t(w[f"params/Cache/Sampler/MLP_{L2}/pred_normals_layer/bias"])
-    raw = (t(b["h64"]) @ kern + bias).detach().requires_grad_(True)
-    tdist, dirs = t(b["tdist"]), t(rays["directions"])
-    weights = gr.weights_from_density(dens, tdist, dirs)
-    losses = gr.geometry_losses(weights, t(lm), tdist, t(rays["viewdirs"]), gr.normals_from_raw(raw), t(b["normals_grad"]), TERMS)
-    losses.sum().backward()
-    return losses.detach().numpy(), dens.grad.numpy(), raw.grad.numpy()
+    return lc.geometry_restated(w, b, rays, lm, dtype, TERMS)
 
 
 def test_kernel_against_restatement():
@@ -185,6 +176,13 @@ def test_semantics():
     empty = {k: v[:0] for k, v in rays.items()}                 # n = 0: nothing written
     fe, le = rc.geometry_backward(empty, [j[:0] for j in jit], 0.4, None, TERMS)
     assert float(le.abs().max()) == 0.0 and all(float(f.abs().max()) == 0.0 for f in fe)
+    # distortion_p of 0 and of 1 (power_ladder's log and identity forms) are refused before any launch
+    for p in (0.0, 1.0):
+        with pytest.raises(rc_ext.RcError) as e:
+            rc.geometry_backward(rays, jit, 0.3, lm, dict(TERMS, distortion_p=p), grads=False)
+        assert e.value.code == RC_ERR_UNSUPPORTED
+    _, la = rc.geometry_backward(rays, jit, 0.3, lm, TERMS, grads=False)
+    assert torch.equal(la, l1)
     # a NULL losses pointer and a time-resolved handle
     r, held, _ = rc._rays_struct(rays)
     cfg = rc_ext.rc_geometry_loss(**TERMS)

@@ -22,26 +22,14 @@ pytestmark = pytest.mark.gpu
 
 
 def test_kernel_against_restatement():
-    """Losses and d loss / d density within 3x the fp32 restatement's distance from fp64, on the HIP forward's buffers."""
+    """Losses and d loss / d density within 3x the fp32 restatement's distance from fp64, on the HIP forward's buffers
+    (loss_cases.interlevel_compare)."""
     rc = common.make_rc()
     n = 1000
     rays, jit = lc.cache_case(n)
     lm = lc.lossmult(n)
     _, losses = rc.interlevel_backward(rays, jit, 0.4, IL.mults, IL.blurs, lossmult=lm, levels=())
-    losses = losses.cpu().numpy()
-    sd, td, dens, _, dd = lc.interlevel_buffers(rc, n)
-    args = (sd, td, dens, rays["directions"], lm, IL.mults, IL.blurs)
-    l64, g64 = ir.interlevel_forward_backward(*args, torch.float64)
-    l32, g32 = ir.interlevel_forward_backward(*args, torch.float32)
-    for l in range(NP):
-        assert l64[l] > 0
-        err, tol = lc.bound(np.float64(losses[l]), l64[l], l32[l], 1e-6 * l64[l])
-        assert err <= tol, ("loss", l, losses[l], l64[l], l32[l])
-        r64, r32 = g64[l].numpy(), g32[l].double().numpy()
-        scale = float(np.abs(r64).max())
-        err, tol = lc.bound(dd[l].astype(np.float64), r64, r32, 1e-6 * scale)
-        assert err <= tol, ("d_density", l, err, tol, scale)
-        assert np.all(dd[l][lm == 0.0] == 0.0)          # lossmult 0: no gradient
+    lc.interlevel_compare(rc, n, rays, lm, losses.cpu().numpy(), IL.mults, IL.blurs)
 
 
 def test_forward_matches_the_render_workspace():

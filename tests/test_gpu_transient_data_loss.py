@@ -13,7 +13,7 @@ from nrc_amd import config, rc_ext, train
 pytestmark = pytest.mark.gpu
 
 CHUNK = 256                     # kRcTdChunkRays
-ADJOINTS = (("d_t_irr", 64), ("d_t_slf", 128), ("d_tint_ibrdf", 3), ("d_direct", 3), ("d_weights", 1))
+ADJOINTS = lc.TRANSIENT_ADJOINTS
 LOOP_STEPS = 20
 # The Adam loop's rate.  The target's head weights are loss_cases.perturbed: each element 5 % of itself away, which is an rms
 # of 0.006 - 0.009 for the two He-uniform kernels (U(+-sqrt(6/64)), U(+-sqrt(6/128))).  Adam with eps = 1e-15 moves every
@@ -37,46 +37,8 @@ def handles():
     return {False: _rc(False), True: _rc(True)}
 
 
-def _batch(n, seed, jitter_seed=None, **ray_kw):
-    rays = nrc_amd.synthetic_transient_rays(n, seed=seed, **ray_kw).hot_fields()
-    jit = None if jitter_seed is None else [j.reshape(-1) for j in common.jitters(n, seed=jitter_seed)]
-    return rays, jit
-
-
-def _target(rc, rays, jit, seed):
-    """gt = the device's own render times U(0.5, 1.5) per element: the same float32 array for the call and both chains."""
-    rnd = None if jit is None else {"jitter": jit}
-    rgb = rc.render_transient(rays, rnd, outputs=["rgb"])["rgb"].cpu().numpy()
-    u = np.random.Generator(np.random.PCG64(seed)).uniform(0.5, 1.5, size=rgb.shape)
-    return (rgb * u).astype(np.float32)
-
-
-def _compare(rc, smooth, rays, jit, gt, rgb_nocorr=None, gt_nocorr=None, lossmult=None, what=""):
-    n = len(rays["origins"])
-    w = common.weights_transient_np(smooth)
-    r64 = tref.chain(w, rays, jit, gt, rgb_nocorr, gt_nocorr, lossmult, torch.float64)
-    r32 = tref.chain(w, rays, jit, gt, rgb_nocorr, gt_nocorr, lossmult, torch.float32)
-    flat, losses = rc.transient_data_backward(rays, None if jit is None else {"jitter": jit}, gt, rgb_nocorr, gt_nocorr, lossmult)
-    losses = losses.cpu().numpy()
-    f = lambda x: np.asarray(x, np.float64)
-    print(what, "loss", losses[0], r64["loss"], r32["loss"], "mse", losses[1], r64["mse"], r32["mse"])
-    lc.check(f(losses[0:1]), f([r64["loss"]]), f([r32["loss"]]), what + " loss")
-    lc.check(f(losses[1:2]), f([r64["mse"]]), f([r32["mse"]]), what + " mse")
-    lc.check(rc.workspace("td:G")[: n * 2100].reshape(n, 700, 3), r64["G"], r32["G"], what + " G")
-    layout, total = rc.transient_head_grad_layout()
-    assert [name for name, _, _ in layout] == list(tref.HEAD_TENSORS)
-    got = {k: v.cpu().numpy() for k, v in train.grads_as_dict(flat, layout).items()}
-    for name in tref.HEAD_TENSORS:                         # every element
-        lc.check(got[name], r64["grads"][name], r32["grads"][name], f"{what} {name}")
-    assert np.all(got[tref.HEAD_SLF + "/kernel"][:, -1] == 0.0) and got[tref.HEAD_SLF + "/bias"][-1] == 0.0     # alpha
-    near = r64["near_tie"]
-    assert near.mean() <= 0.01, (what, near.mean())
-    keep = ~near
-    for name, width in ADJOINTS:
-        g = rc.workspace("td:" + name)[: n * 32 * width].reshape(n * 32, -1)
-        a, b = r64[name].reshape(n * 32, -1), r32[name].reshape(n * 32, -1)
-        lc.check(g[keep], a[keep], b[keep], f"{what} {name}")
-    return flat, losses, r64
+# shared with test_gpu_loss_settings, which runs the same comparison under a loss_cfg off the defaults
+_batch, _target, _compare = lc.transient_batch, lc.transient_target, lc.transient_compare
 
 
 @pytest.mark.parametrize("smooth", [False, True])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import loss_cases as lc
 import material_data_loss_ref as md
 import nrc_amd
 from nrc_amd import config, train
@@ -53,6 +54,23 @@ def test_restatement_equals_the_loop_form():
         got = float(md.data_loss(rgb, gt, c, lmult, weight=0.1, mult=1.0, exponent=1.0, eps=1e-2))
         want = md.loop_loss(rgb.detach().numpy(), gt.numpy(), c.numpy(), None if lmult is None else lmult.numpy())
         assert got == pytest.approx(want, rel=1e-13)
+
+
+@pytest.mark.parametrize("name", list(lc.MATERIAL_SETTINGS))
+def test_restatement_equals_the_loop_form_at_the_settings(name):
+    """data_loss against the loops at every non-default setting test_gpu_loss_settings runs on the device: the torch
+    restatement is the oracle of branches only it implements, the loops are its second opinion."""
+    rgb, gt, c, lm = _loss_case(n=7, seed=1)
+    c[3, 0] = -0.5                                   # clipped at 0
+    c[4, 1] = 0.9                                    # above clip_val = 0.5 and above gt
+    kw = lc.material_loss_kw(dataclasses.replace(config.MaterialDataLossConfig(), **lc.MATERIAL_SETTINGS[name]))
+    assert (gt > 0.8).any() and (gt > 0.5).any() and (c > gt).any() and (c < gt).any()
+    default = md.loop_loss(rgb.detach().numpy(), gt.numpy(), c.numpy(), lm.numpy())
+    for lmult in (None, lm):
+        got = float(md.data_loss(rgb, gt, c, lmult, **kw))
+        want = md.loop_loss(rgb.detach().numpy(), gt.numpy(), c.numpy(), None if lmult is None else lmult.numpy(), **kw)
+        assert got == pytest.approx(want, rel=1e-12)
+    assert want != pytest.approx(default, rel=1e-3)
 
 
 def test_gradient_is_half_the_derivative_of_the_value():

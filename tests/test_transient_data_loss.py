@@ -4,9 +4,11 @@ the TransientVolumeIntegrator's two linear maps with their transposes written as
 import dataclasses
 
 import numpy as np
+import pytest
 import torch
 
 import common
+import loss_cases as lc
 import nrc_amd
 import transient_data_loss_ref as tref
 from nrc_amd.config import TransientDataLossConfig
@@ -27,12 +29,53 @@ def test_loss_equals_the_loops():
     rn, gn = rgb + 0.01 * rng.standard_normal(rgb.shape), gt + 0.01 * rng.standard_normal(gt.shape)
     lm = np.array([1.0, 0.0, 1.7])
     gt[2, 1, 0] = 2e6                                      # over loss_thresh: channel 0 of ray 2 drops out
-    for kw in (dict(), dict(rgb_nocorr=rn, gt_nocorr=gn), dict(lossmult=lm), dict(rgb_nocorr=rn, gt_nocorr=gn, lossmult=lm)):
-        t = {k: torch.from_numpy(v) for k, v in kw.items()}
-        loss, mse = tref.data_loss(torch.from_numpy(rgb), torch.from_numpy(gt), cfg=CFG, **t)
-        l2, m2 = tref.loop_loss(rgb, gt, cfg=CFG, **kw)
-        assert abs(float(loss) - l2) <= 1e-12 * max(1.0, abs(l2)), (kw.keys(), float(loss), l2)
-        assert abs(float(mse) - m2) <= 1e-9 * max(1.0, abs(m2))
+    # the defaults, then every non-default setting test_gpu_loss_settings runs on the device (clip_val and loss_thresh from
+    # the finite part of this gt: the clip binds, the threshold drops whole channels)
+    fin = np.where(gt < 1e6, gt, 0.0)
+    cfgs = [CFG] + [lc.transient_setting(name, fin) for name in lc.TRANSIENT_SETTINGS]
+    assert cfgs[4].clip_val < fin.max() and 0.1 <= lc.transient_loss_thresh(fin)[1] <= 0.5
+    for cfg in cfgs:
+        for kw in (dict(), dict(rgb_nocorr=rn, gt_nocorr=gn), dict(lossmult=lm), dict(rgb_nocorr=rn, gt_nocorr=gn, lossmult=lm)):
+            t = {k: torch.from_numpy(v) for k, v in kw.items()}
+            loss, mse = tref.data_loss(torch.from_numpy(rgb), torch.from_numpy(gt), cfg=cfg, **t)
+            l2, m2 = tref.loop_loss(rgb, gt, cfg=cfg, **kw)
+            assert abs(float(loss) - l2) <= 1e-12 * max(1.0, abs(l2)), (cfg, kw.keys(), float(loss), l2)
+            assert abs(float(mse) - m2) <= 1e-9 * max(1.0, abs(m2))
+
+
+@pytest.fixture(scope="module")
+def settings_batch():
+    """The batch of test_gpu_loss_settings' transient cases with the fp64 restatement's render in the device's place, and
+    the restatement at the default settings."""
+    rays, jit = lc.transient_batch(8, seed=31, jitter_seed=32)
+    u = np.random.Generator(np.random.PCG64(33)).uniform(0.5, 1.5, size=(8, 700, 3))
+    d64 = tref.chain(common.weights_transient_np(False), rays, jit, lambda rgb: (rgb * u).astype(np.float32))
+    return rays, jit, (d64["rgb"] * u).astype(np.float32), d64
+
+
+@pytest.mark.parametrize("name", lc.TRANSIENT_SETTINGS)
+def test_settings_reach_the_result(settings_batch, name):
+    """Every non-default setting moves the fp64 loss or the largest head gradient by more than 100 x the tolerance the GPU
+    comparison grants (loss_cases.guard), so a device call that ignored the setting could not pass."""
+    rays, jit, gt, d64 = settings_batch
+    cfg = lc.transient_setting(name, gt)
+    extra = {}
+    if name == "combined":
+        n = len(gt)
+        rng = np.random.Generator(np.random.PCG64(34))
+        extra = dict(lossmult=lc.lossmult(n), rgb_nocorr=(gt * rng.uniform(0.5, 1.5, size=gt.shape)).astype(np.float32),
+                     gt_nocorr=(gt * rng.uniform(0.5, 1.5, size=gt.shape)).astype(np.float32))
+        d64 = lc.transient_refs(False, rays, jit, gt, **extra)[0]      # the defaults on the same extras
+    if name == "loss_thresh":
+        share = lc.transient_loss_thresh(gt)[1]
+        assert 0.1 <= share <= 0.5, share
+    if name in ("clip_val", "combined"):
+        assert cfg.clip_val < float(gt.max())
+    r64, r32 = lc.transient_refs(False, rays, jit, gt, loss_cfg=cfg, **extra)
+    lc.transient_guard(name, r64, r32, d64)
+    if name == "loss_thresh":
+        zeroed = gt.max(axis=1) > cfg.loss_thresh
+        assert np.all(r64["G"].transpose(0, 2, 1)[zeroed] == 0.0)
 
 
 def test_known_answer_two_rays_four_bins():
