@@ -72,6 +72,11 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, cons
 //     splits into a set follow the marker that retires it;
 //  3. behind a layer's last cell two flush MFMAs (16x16x32 into a 4-register sink that lives as long as the stream
 //     object and is never read) issue before the accumulators are read or the last operands are released.
+// The rules and the options of mlp_layer_split:
+//  * B pieces handed in ready (NBP: the shader's feature, split once for its three readers) live across whole layers, so
+//    rule 2 holds for them by construction; the keep markers on them are kept for uniformity and cost nothing.
+//  * a bias block (BIAS1) issues the three products of its cell that use B's hi piece, fenced like six; its B is a
+//    register constant, kept like any other piece.  Rule 3's flush follows the last cell whatever its kind.
 // (diagnostic switches: -DRC_RULE1=0 / -DRC_RULE2=0 / -DRC_RULE3=0 take a rule out; profiles/r04_split_mfma_hazard.txt, 4.)
 #ifndef RC_RULE1
 #define RC_RULE1 1
@@ -112,6 +117,16 @@ __device__ __forceinline__ void mfma_split6(const u32x4 (&a)[3], const u32x4 (&b
   acc = mfma_bf16(a[1], b[0], acc);
   acc = mfma_bf16(a[0], b[1], acc);
   acc = mfma_bf16(a[0], b[0], acc);
+  split_fence();
+}
+
+// the three products of a cell whose B has a hi piece only (a bias block, B = 1 | 0): those of mfma_split6 that use b[0], in
+// its order; the other three add +0
+__device__ __forceinline__ void mfma_split3(const u32x4 (&a)[3], const u32x4& b0, f32x16& acc) {
+  split_fence();
+  acc = mfma_bf16(a[2], b0, acc);
+  acc = mfma_bf16(a[1], b0, acc);
+  acc = mfma_bf16(a[0], b0, acc);
   split_fence();
 }
 
@@ -250,12 +265,33 @@ __device__ __forceinline__ void mlp_layer_f32(const WS& w, const float* act, f32
 
 // The split form of the same pass: blocks of 8 k-steps, cells (block, tile) of three 1-KiB pieces in stream order.  The
 // activations of the next block and the pieces of the next cell are read before the six MFMAs of the current one.
-template <int NT, int KS, int FBASE, int NF, int W, int CH, class WS>
-__device__ __forceinline__ void mlp_layer_split(const WS& w, const float* act, f32x16 (&acc)[NT]) {
+//  NBP    the B pieces of blocks [0, NBP) come already split from the caller (`pre`, split_blocks below): no LDS read and
+//         no split8 for them here; a value that several layers read as their B operand is split once.
+//  BIAS1  the last block is a bias block: its only live step holds 1 on the low half-wave and 0 on the high one, whose
+//         pieces are (0x3f80, 0, 0).  The three products with B's mid and lo piece add +0 and are not issued (the same
+//         three, in the same relative order, as mlp_bias_step); the block's B is not read from LDS at all.
+// the B pieces of blocks [0, NBP) of a lane's activation column, for the layers that take them ready (NBP above)
+template <int NBP>
+__device__ __forceinline__ void split_blocks(const float* act, u32x4 (&pre)[NBP][3]) {
+  float v[NBP][8];
+#pragma unroll
+  for (int q = 0; q < NBP; ++q)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[q][j] = act[(8 * q + j) * 64];
+#pragma unroll
+  for (int q = 0; q < NBP; ++q) split8(v[q], pre[q]);
+}
+template <int NT, int KS, int FBASE, int NF, int W, int CH, int NBP, bool BIAS1, class WS>
+__device__ __forceinline__ void mlp_layer_split(const WS& w, const float* act, f32x16 (&acc)[NT], const u32x4 (*pre)[3]) {
   static_assert(FBASE % 4 == 0, "split layers start on a 1-KiB piece");
   constexpr int NB = (KS + 7) / 8, NC = NB * NT;
+  static_assert(NBP <= NB, "no more ready blocks than blocks");
+  static_assert(!BIAS1 || KS % 8 == 1, "a bias block holds the bias step alone");
   float bv[8];
   u32x4 a[3][3], b[2][3];
+  u32x4 b1;                                                 // B of a bias block: hi piece of (1 | 0), mid = lo = 0
+  b1[0] = (BIAS1 && w.lane < 32) ? 0x00003f80u : 0u; b1[1] = 0u; b1[2] = 0u; b1[3] = 0u;
+  auto from_act = [](int q) { return q < NB && q >= NBP && !(BIAS1 && q == NB - 1); };
   auto load_b = [&](int q) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) bv[j] = (8 * q + j < KS) ? act[(8 * q + j) * 64] : 0.0f;
@@ -264,38 +300,51 @@ __device__ __forceinline__ void mlp_layer_split(const WS& w, const float* act, f
 #pragma unroll
     for (int p = 0; p < 3; ++p) a[cell % 3][p] = ws_read4<NF, W, CH>(w, FBASE + (cell * 3 + p) * 4);
   };
-  load_b(0);
+  auto keep_b = [&](int q) {
+    if (BIAS1 && q == NB - 1) split_keep(b1);
+    else if (q < NBP) split_keep3(pre[q]);
+    else split_keep3(b[q & 1]);
+  };
+  if (from_act(0)) load_b(0);
   load_a(0);
   if (NC > 1) load_a(1);
-  split8(bv, b[0]);
-  if (NB > 1) load_b(1);
+  if (from_act(0)) split8(bv, b[0]);
+  if (from_act(1)) load_b(1);
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int cell = q * NT + t;
-      mfma_split6(a[cell % 3], b[q & 1], acc[t]);
+      if (BIAS1 && q == NB - 1) mfma_split3(a[cell % 3], b1, acc[t]);
+      else if (q < NBP) mfma_split6(a[cell % 3], pre[q], acc[t]);
+      else mfma_split6(a[cell % 3], b[q & 1], acc[t]);
       // the MFMAs of this cell have issued: those of the cell before have started, its registers may go
       if (cell >= 1) split_keep3(a[(cell - 1) % 3]);
       if (cell + 2 < NC) load_a(cell + 2);
       if (t == 0) {
-        if (q >= 1) split_keep3(b[(q - 1) & 1]);
-        if (q + 1 < NB) {
-          split8(bv, b[(q + 1) & 1]);
-          if (q + 2 < NB) load_b(q + 2);
-        }
+        if (q >= 1) keep_b(q - 1);
+        if (from_act(q + 1)) split8(bv, b[(q + 1) & 1]);
+        if (from_act(q + 2)) load_b(q + 2);
       }
     }
   }
-  split_flush(w, b[(NB - 1) & 1][0]);
+  if (BIAS1) split_flush(w, b1);
+  else if (NB - 1 < NBP) split_flush(w, pre[NB - 1][0]);
+  else split_flush(w, b[(NB - 1) & 1][0]);
   split_keep3(a[(NC - 1) % 3]);
-  split_keep3(b[(NB - 1) & 1]);
+  keep_b(NB - 1);
 }
 
 template <int NT, int KS, int FBASE, int NF, int SG = (NT >= 8 ? 1 : (NT >= 4 ? 2 : (NT >= 2 ? 4 : 8))), int W = kWaves, int CH = kChunk, class WS = WStream>
 __device__ __forceinline__ void mlp_layer(const WS& w, const float* act, f32x16 (&acc)[NT]) {
-  if constexpr (kRcSplit) mlp_layer_split<NT, KS, FBASE, NF, W, CH, WS>(w, act, acc);
+  if constexpr (kRcSplit) mlp_layer_split<NT, KS, FBASE, NF, W, CH, 0, false>(w, act, acc, nullptr);
   else mlp_layer_f32<NT, KS, FBASE, NF, SG, W, CH, WS>(w, act, acc);
+}
+
+// A layer of the split build with the options of mlp_layer_split (ready B pieces, bias block).
+template <int NT, int KS, int FBASE, int NF, int NBP, bool BIAS1, int W = kWaves, int CH = kChunk, class WS = WStream>
+__device__ __forceinline__ void mlp_layer_x(const WS& w, const float* act, f32x16 (&acc)[NT], const u32x4 (*pre)[3] = nullptr) {
+  mlp_layer_split<NT, KS, FBASE, NF, W, CH, NBP, BIAS1>(w, act, acc, pre);
 }
 
 // A layer of a proposal level's density MLP: the exact fp32 MFMA chain in every build (rc_pack_host.h rc_lfr32).
@@ -532,10 +581,16 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
   RC_TSTAMP(0);
   // ---- small heads tile on the feature (the bottleneck is folded into its consumers, see kShActSteps)
   float rough, tint[3], ad[3], idf[3];
+  // split build: the pieces of the 48 feature steps, split ONCE for the three layers that read the feature as their B
+  // operand (heads, 85-step layer, first IBRDF layer).  They stay live from here to the first IBRDF layer, so rule 2
+  // holds for them by construction.
+  u32x4 fpc[6][3];
+  if constexpr (kRcSplit) split_blocks<6>(act, fpc);
   {
     f32x16 acc[1];
     acc[0] = zero16();
-    mlp_layer<1, 49, F0 + ShaderFrags::F_H, NF>(ws, act, acc);
+    if constexpr (kRcSplit) mlp_layer_x<1, 49, F0 + ShaderFrags::F_H, NF, 6, true>(ws, act, acc, fpc);
+    else mlp_layer<1, 49, F0 + ShaderFrags::F_H, NF>(ws, act, acc);
     // by accumulator register (same on both half-waves): 0 roughness, 1-3 tint, 4-6 ambient irradiance, 7-9 irradiance
     rough = softplus(acc[0][0] + k.roughness_bias);                       // nerf.py:633-634
     tint[0] = sigmoidf(acc[0][1]); tint[1] = sigmoidf(acc[0][2]); tint[2] = sigmoidf(acc[0][3]);   // :976
@@ -592,7 +647,8 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
   f32x16 s0[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t) s0[t] = zero16();
-  mlp_layer<8, 85, F0 + ShaderFrags::F_S0, NF>(ws, act, s0);
+  if constexpr (kRcSplit) mlp_layer_x<8, 85, F0 + ShaderFrags::F_S0, NF, 6, false>(ws, act, s0, fpc);      // blocks 6-10 (IDE | bias) from act
+  else mlp_layer<8, 85, F0 + ShaderFrags::F_S0, NF>(ws, act, s0);
   RC_TSTAMP(3);
   // ---- integrated BRDF: (bottleneck, n.v) 129 -> 64 -> 64 -> 1 (nerf.py:461-482), first layer on the feature
   float ibrdf;
@@ -601,12 +657,14 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     ib[0] = zero16(); ib[1] = zero16();
     // IDE is dead after s0': its first step becomes the (n.v | bias) step right behind the 48 feature steps
     act[48 * 64] = h == 0 ? dot_nv : 1.0f;
-    mlp_layer<2, 49, F0 + ShaderFrags::F_I0, NF>(ws, act, ib);
+    if constexpr (kRcSplit) mlp_layer_x<2, 49, F0 + ShaderFrags::F_I0, NF, 6, false>(ws, act, ib, fpc);      // step 48 carries n.v: no bias block
+    else mlp_layer<2, 49, F0 + ShaderFrags::F_I0, NF>(ws, act, ib);
     // steps [48, 81) are scratch for the IBRDF tail
     park<2, true>(ib, act, 48);
     act[(48 + 32) * 64] = h == 0 ? 1.0f : 0.0f;
     ib[0] = zero16(); ib[1] = zero16();
-    mlp_layer<2, 33, F0 + ShaderFrags::F_I1, NF>(ws, act + 48 * 64, ib);
+    if constexpr (kRcSplit) mlp_layer_x<2, 33, F0 + ShaderFrags::F_I1, NF, 0, true>(ws, act + 48 * 64, ib);
+    else mlp_layer<2, 33, F0 + ShaderFrags::F_I1, NF>(ws, act + 48 * 64, ib);
     float o[1], nokeep[1];
     dot_out1<2, 1, F0 + ShaderFrags::F_IO, NF>(ws, ib, o, nokeep);     // output_integrated_brdf_layer on relu(ib)
     ibrdf = sigmoidf(o[0] + 1.0986123f);        // + log(3), nerf.py:481
@@ -621,12 +679,14 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     act[64 * 64] = h == 0 ? 1.0f : 0.0f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = zero16();
-    mlp_layer<4, 65, F0 + ShaderFrags::F_S1, NF>(ws, act, acc);
+    if constexpr (kRcSplit) mlp_layer_x<4, 65, F0 + ShaderFrags::F_S1, NF, 0, true>(ws, act, acc);
+    else mlp_layer<4, 65, F0 + ShaderFrags::F_S1, NF>(ws, act, acc);
     park<4, true>(acc, act, 0);
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = zero16();
     RC_TSTAMP(5);
-    mlp_layer<4, 65, F0 + ShaderFrags::F_S2, NF>(ws, act, acc);
+    if constexpr (kRcSplit) mlp_layer_x<4, 65, F0 + ShaderFrags::F_S2, NF, 0, true>(ws, act, acc);
+    else mlp_layer<4, 65, F0 + ShaderFrags::F_S2, NF>(ws, act, acc);
     park<4, true>(acc, act, 0);
     RC_TSTAMP(6);
     mlp_layer<4, 64, F0 + ShaderFrags::F_SB, NF>(ws, act, skip);
