@@ -130,6 +130,11 @@ class rc_transient_outputs(C.Structure):
     _fields_ = [("ptr", C.c_void_p * RC_TOUT_COUNT)]
 
 
+# outputs table -> (its struct of pointers, name -> slot)
+_OUTPUT_TABLES = {OUTPUTS: (rc_outputs, OUTPUT_ID), MAT_OUTPUTS: (rc_mat_outputs, MAT_OUTPUT_ID),
+                  TRANSIENT_OUTPUTS: (rc_transient_outputs, TRANSIENT_OUTPUT_ID)}
+
+
 class rc_camera(C.Structure):
     _fields_ = [("pixtocam", C.c_float * 9), ("camtoworld", C.c_float * 12), ("light", C.c_float * 3),
                 ("near", C.c_float), ("far", C.c_float), ("camtype", C.c_int32),
@@ -209,20 +214,6 @@ class rc_adam_step(C.Structure):
                 + [("grad_max_val", C.c_float), ("grad_max_norm", C.c_float), ("zero_grads", C.c_int32)])
 
 
-EXPORTS = (
-    "rc_create", "rc_destroy", "rc_last_error", "rc_abi_version", "rc_mlp_arithmetic", "rc_load_weights", "rc_render_rays", "rc_render_chunks",
-    "rc_hashgrid_lookup", "rc_sample_intervals", "rc_workspace_ptr", "rc_set_profiling", "rc_stage_count",
-    "rc_stage_name", "rc_stage_times_ms", "rc_set_graph_mode", "rc_set_fused", "rc_render_material", "rc_set_transient", "rc_render_transient", "rc_cast_rays",
-    "rc_prng_fill", "rc_density_grad_size", "rc_density_grad_layout", "rc_density_backward",
-    "rc_hashgrid_grad_layout", "rc_hashgrid_backward", "rc_allgather_outputs", "rc_interlevel_backward",
-    "rc_shader_grad_size", "rc_shader_grad_layout", "rc_data_backward", "rc_geometry_backward", "rc_density_regularizer",
-    "rc_adam_update", "rc_load_params_flat", "rc_light_grad_size", "rc_light_grad_layout", "rc_light_sampling_backward",
-    "rc_light_regularizer", "rc_material_grad_size", "rc_material_grad_layout", "rc_material_smoothness_backward",
-    "rc_material_regularizer", "rc_material_data_backward", "rc_envmap_grad_size", "rc_envmap_grad_layout",
-    "rc_material_data_backward_env", "rc_cast_rays_multi", "rc_train_batch", "rc_transient_head_grad_size",
-    "rc_transient_head_grad_layout", "rc_transient_data_backward",
-)
-
 # Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap", "transient_heads": the C functions of its size and of its
 # segments (a density level is their first argument) and its RC_LAYOUT_* id (rc_load_params_flat; a level is its own).
 _GRAD_LAYOUTS = {
@@ -234,6 +225,66 @@ _GRAD_LAYOUTS = {
     "transient_heads": ("rc_transient_head_grad_size", "rc_transient_head_grad_layout", RC_LAYOUT_TRANSIENT_HEADS),
 }
 _LAYOUT_KEYS = {row[2]: key for key, row in _GRAD_LAYOUTS.items() if key is not int}
+
+# The prototype of every export of include/rc_abi.h: name -> (restype, [argtypes]).  The one source of load_library's
+# ctypes prototypes and of EXPORTS; tests/test_abi_exports.py compares it with the header's declarations.
+_H, _P, _I32, _I64, _F = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_float        # _H: rc_handle*, _P: any other pointer
+_RAYS, _RND, _MRND, _OUT = C.POINTER(rc_rays), C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.POINTER(rc_outputs)
+_PROTOTYPES = {
+    "rc_create": (C.c_int, [C.POINTER(rc_config), C.c_int, C.POINTER(C.c_void_p)]),
+    "rc_destroy": (None, [_H]),
+    "rc_last_error": (C.c_char_p, [_H]),
+    "rc_abi_version": (C.c_int, []),
+    "rc_mlp_arithmetic": (C.c_int, []),
+    "rc_load_weights": (C.c_int, [_H, C.POINTER(rc_tensor_desc), _I32]),
+    "rc_render_rays": (C.c_int, [_H, _RAYS, _I64, _RND, C.c_uint32, _OUT, _P]),
+    "rc_render_chunks": (C.c_int, [_H, _RAYS, _I64, _I64, C.c_uint32, _OUT, _I64, C.POINTER(C.c_void_p), _I32]),
+    "rc_render_material": (C.c_int, [_H, _RAYS, _I64, _RND, _MRND, _I32, _OUT, C.POINTER(rc_mat_outputs), _P]),
+    "rc_allgather_outputs": (C.c_int, [_H, _P, _OUT, _I64, _OUT, _P]),
+    "rc_hashgrid_lookup": (C.c_int, [_H, _I32, _P, _I64, _P, _I32, _P]),
+    "rc_sample_intervals": (C.c_int, [_H, _P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "rc_workspace_ptr": (C.c_int, [_H, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "rc_set_profiling": (C.c_int, [_H, _I32]),
+    "rc_set_graph_mode": (C.c_int, [_H, _I32]),
+    "rc_set_fused": (C.c_int, [_H, _I32]),
+    "rc_stage_count": (C.c_int, []),
+    "rc_stage_name": (C.c_char_p, [_I32]),
+    "rc_stage_times_ms": (C.c_int, [_H, C.POINTER(C.c_float), _I32]),
+    "rc_set_transient": (C.c_int, [_H, _P]),
+    "rc_render_transient": (C.c_int, [_H, _P, _P, _I64, _P, _P, _P, _P]),
+    "rc_cast_rays": (C.c_int, [_H, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P]),
+    "rc_cast_rays_multi": (C.c_int, [_H, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
+    "rc_train_batch": (C.c_int, [_H, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I64, _P, _P]),
+    "rc_prng_fill": (C.c_int, [_H, _P, _I32, _F, _F, _I64, _P, _P]),
+    "rc_density_grad_size": (C.c_int64, [_H, _I32]),
+    "rc_density_grad_layout": (C.c_int, [_H, _I32, _P, _I32, C.POINTER(C.c_int32)]),
+    "rc_density_backward": (C.c_int, [_H, _I32, _P, _I64, _P, _P, _P, _P, _P]),
+    "rc_hashgrid_grad_layout": (C.c_int, [_H, _I32, _P, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "rc_hashgrid_backward": (C.c_int, [_H, _I32, _P, _I64, _P, _P, _I32, _P]),
+    "rc_interlevel_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_void_p), _P, _P]),
+    "rc_data_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _F, _F, _F, _P, _P, _P, _P]),
+    "rc_geometry_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, C.POINTER(rc_geometry_loss), _P, _P, _P, _P]),
+    "rc_density_regularizer": (C.c_int, [_H, _I32, _F, _P, _P, _P]),
+    "rc_adam_update": (C.c_int, [_H, C.POINTER(rc_adam_buffer), _I32, C.POINTER(rc_adam_step), _P]),
+    "rc_load_params_flat": (C.c_int, [_H, _I32, _P, _P]),
+    "rc_light_sampling_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _MRND, _I32, C.POINTER(rc_light_sampling_loss),
+                                             _P, _P, _P]),
+    "rc_light_regularizer": (C.c_int, [_H, _F, _P, _P, _P]),
+    "rc_material_smoothness_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _MRND, _P,
+                                                  C.POINTER(rc_material_smoothness_loss), _P, _P, _P]),
+    "rc_material_regularizer": (C.c_int, [_H, _F, _P, _P, _P]),
+    "rc_material_data_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _MRND, _I32, C.POINTER(rc_material_data_loss),
+                                            _P, _P, _P]),
+    "rc_material_data_backward_env": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _MRND, _I32,
+                                                C.POINTER(rc_material_data_loss), _F, _P, _P, _P, _P]),
+    "rc_transient_data_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P, C.POINTER(rc_transient_data_loss),
+                                             _P, _P, _P]),
+}
+for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the five named layouts
+    _PROTOTYPES[_size] = (C.c_int64, [_H])
+    _PROTOTYPES[_layout] = (C.c_int, [_H, _P, _I32, C.POINTER(C.c_int32)])
+EXPORTS = tuple(_PROTOTYPES)
 
 _LIB = None
 _RAY_FIELDS = ("origins", "directions", "viewdirs", "near", "far", "lights", "normals")
@@ -275,136 +326,9 @@ def load_library():
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the render path.")
     lib = C.CDLL(path)
-    lib.rc_create.argtypes = [C.POINTER(rc_config), C.c_int, C.POINTER(C.c_void_p)]
-    lib.rc_create.restype = C.c_int
-    lib.rc_destroy.argtypes = [C.c_void_p]
-    lib.rc_destroy.restype = None
-    lib.rc_last_error.argtypes = [C.c_void_p]
-    lib.rc_last_error.restype = C.c_char_p
-    lib.rc_abi_version.restype = C.c_int
-    lib.rc_mlp_arithmetic.restype = C.c_int
-    lib.rc_load_weights.argtypes = [C.c_void_p, C.POINTER(rc_tensor_desc), C.c_int32]
-    lib.rc_load_weights.restype = C.c_int
-    lib.rc_render_rays.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_int64, C.POINTER(rc_randoms), C.c_uint32,
-                                   C.POINTER(rc_outputs), C.c_void_p]
-    lib.rc_render_rays.restype = C.c_int
-    lib.rc_render_chunks.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_int64, C.c_int64, C.c_uint32,
-                                     C.POINTER(rc_outputs), C.c_int64, C.POINTER(C.c_void_p), C.c_int32]
-    lib.rc_render_chunks.restype = C.c_int
-    lib.rc_render_material.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_int64, C.POINTER(rc_randoms),
-                                       C.POINTER(rc_material_randoms), C.c_int32, C.POINTER(rc_outputs),
-                                       C.POINTER(rc_mat_outputs), C.c_void_p]
-    lib.rc_render_material.restype = C.c_int
-    lib.rc_hashgrid_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.rc_hashgrid_lookup.restype = C.c_int
-    lib.rc_sample_intervals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_sample_intervals.restype = C.c_int
-    lib.rc_workspace_ptr.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    lib.rc_workspace_ptr.restype = C.c_int
-    lib.rc_set_profiling.argtypes = [C.c_void_p, C.c_int32]
-    lib.rc_set_profiling.restype = C.c_int
-    lib.rc_set_graph_mode.argtypes = [C.c_void_p, C.c_int32]
-    lib.rc_set_graph_mode.restype = C.c_int
-    lib.rc_set_fused.argtypes = [C.c_void_p, C.c_int32]
-    lib.rc_set_fused.restype = C.c_int
-    lib.rc_set_transient.argtypes = [C.c_void_p, C.c_void_p]
-    lib.rc_set_transient.restype = C.c_int
-    lib.rc_render_transient.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]
-    lib.rc_render_transient.restype = C.c_int
-    lib.rc_cast_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
-                                 C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rc_cast_rays.restype = C.c_int
-    lib.rc_cast_rays_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_cast_rays_multi.restype = C.c_int
-    lib.rc_train_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                   C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.rc_train_batch.restype = C.c_int
-    lib.rc_prng_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.rc_prng_fill.restype = C.c_int
-    lib.rc_density_grad_size.argtypes = [C.c_void_p, C.c_int32]
-    lib.rc_density_grad_size.restype = C.c_int64
-    lib.rc_density_grad_layout.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.rc_density_grad_layout.restype = C.c_int
-    lib.rc_density_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    lib.rc_density_backward.restype = C.c_int
-    lib.rc_hashgrid_grad_layout.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    lib.rc_hashgrid_grad_layout.restype = C.c_int
-    lib.rc_interlevel_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms), C.c_float,
-                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.c_void_p,
-                                           C.c_void_p]
-    lib.rc_interlevel_backward.restype = C.c_int
-    lib.rc_shader_grad_size.argtypes = [C.c_void_p]
-    lib.rc_shader_grad_size.restype = C.c_int64
-    lib.rc_shader_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.rc_shader_grad_layout.restype = C.c_int
-    lib.rc_data_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
-                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_data_backward.restype = C.c_int
-    lib.rc_geometry_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
-                                         C.c_float, C.POINTER(rc_geometry_loss), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_geometry_backward.restype = C.c_int
-    lib.rc_density_regularizer.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_density_regularizer.restype = C.c_int
-    lib.rc_adam_update.argtypes = [C.c_void_p, C.POINTER(rc_adam_buffer), C.c_int32, C.POINTER(rc_adam_step), C.c_void_p]
-    lib.rc_adam_update.restype = C.c_int
-    lib.rc_load_params_flat.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.rc_load_params_flat.restype = C.c_int
-    lib.rc_light_grad_size.argtypes = [C.c_void_p]
-    lib.rc_light_grad_size.restype = C.c_int64
-    lib.rc_light_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.rc_light_grad_layout.restype = C.c_int
-    lib.rc_light_sampling_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
-                                               C.POINTER(rc_material_randoms), C.c_int32, C.POINTER(rc_light_sampling_loss),
-                                               C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_light_sampling_backward.restype = C.c_int
-    lib.rc_light_regularizer.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_light_regularizer.restype = C.c_int
-    lib.rc_material_grad_size.argtypes = [C.c_void_p]
-    lib.rc_material_grad_size.restype = C.c_int64
-    lib.rc_material_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.rc_material_grad_layout.restype = C.c_int
-    lib.rc_material_smoothness_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64,
-                                                    C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_void_p,
-                                                    C.POINTER(rc_material_smoothness_loss), C.c_void_p, C.c_void_p,
-                                                    C.c_void_p]
-    lib.rc_material_smoothness_backward.restype = C.c_int
-    lib.rc_material_regularizer.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_material_regularizer.restype = C.c_int
-    lib.rc_material_data_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_void_p, C.c_int64,
-                                              C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_int32,
-                                              C.POINTER(rc_material_data_loss), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_material_data_backward.restype = C.c_int
-    lib.rc_envmap_grad_size.argtypes = [C.c_void_p]
-    lib.rc_envmap_grad_size.restype = C.c_int64
-    lib.rc_envmap_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.rc_envmap_grad_layout.restype = C.c_int
-    lib.rc_material_data_backward_env.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_void_p, C.c_int64,
-                                                  C.POINTER(rc_randoms), C.POINTER(rc_material_randoms), C.c_int32,
-                                                  C.POINTER(rc_material_data_loss), C.c_float, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]
-    lib.rc_material_data_backward_env.restype = C.c_int
-    lib.rc_transient_head_grad_size.argtypes = [C.c_void_p]
-    lib.rc_transient_head_grad_size.restype = C.c_int64
-    lib.rc_transient_head_grad_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    lib.rc_transient_head_grad_layout.restype = C.c_int
-    lib.rc_transient_data_backward.argtypes = [C.c_void_p, C.POINTER(rc_rays), C.c_void_p, C.c_int64, C.POINTER(rc_randoms),
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(rc_transient_data_loss), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rc_transient_data_backward.restype = C.c_int
-    lib.rc_hashgrid_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.rc_hashgrid_backward.restype = C.c_int
-    lib.rc_allgather_outputs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rc_outputs), C.c_int64, C.POINTER(rc_outputs),
-                                         C.c_void_p]
-    lib.rc_allgather_outputs.restype = C.c_int
-    lib.rc_stage_count.restype = C.c_int
-    lib.rc_stage_name.argtypes = [C.c_int32]
-    lib.rc_stage_name.restype = C.c_char_p
-    lib.rc_stage_times_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int32]
-    lib.rc_stage_times_ms.restype = C.c_int
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = lib
     return lib
 
@@ -449,6 +373,37 @@ def transient_config_to_c(t) -> rc_transient_config:
               "brdf_bias", "irradiance_bias", "slf_rgb_bias", "occ_threshold", "shadow_near", "shadow_far"):
         setattr(c, k, float(getattr(t, k)))
     return c
+
+
+def _ptr(x):
+    """Device address of a tensor, NULL for None."""
+    return None if x is None else x.data_ptr()
+
+
+def _camera_options(s, camtype="perspective", distortion_params=None, pixtocam_ndc=None, z_range=None):
+    """The optional members that rc_camera and rc_camera_set share.  distortion_params: dict of floats like the reference's
+    (k1..k4, p1, p2; missing = 0)."""
+    s.camtype = CAMTYPES[getattr(camtype, "value", camtype)]
+    if distortion_params is not None:
+        s.has_distortion = 1
+        for i, k in enumerate(("k1", "k2", "k3", "k4", "p1", "p2")):
+            s.distortion[i] = float(distortion_params.get(k, 0.0))
+    if pixtocam_ndc is not None:
+        s.has_ndc = 1
+        for i, v in enumerate(np.asarray(pixtocam_ndc, np.float32).reshape(9)):
+            s.pixtocam_ndc[i] = float(v)
+    if z_range is not None:
+        s.has_z_range = 1
+        s.z_range[0], s.z_range[1] = float(z_range[0]), float(z_range[1])
+
+
+def _rays_of_cast(t, lossmult, cam_idx, light_idx, pix_x_int=None, pix_y_int=None):
+    """The Rays of one cast: the tensors of CAST_OUTPUTS (the camera is its own virtual camera) plus the per-ray extras."""
+    from .rays import Rays
+    return Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
+                radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
+                vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=lossmult, near=t["near"],
+                far=t["far"], cam_idx=cam_idx, light_idx=light_idx, pix_x_int=pix_x_int, pix_y_int=pix_y_int)
 
 
 class AdamTable:
@@ -497,20 +452,9 @@ class CameraSet:
         s = rc_camera_set()
         s.count = self.count
         s.pixtocams, s.camtoworlds = self.pixtocams.data_ptr(), self.camtoworlds.data_ptr()
-        s.lights = None if self.lights is None else self.lights.data_ptr()
+        s.lights = _ptr(self.lights)
         s.near, s.far = self.near, self.far
-        s.camtype = CAMTYPES[getattr(camtype, "value", camtype)]
-        if distortion_params is not None:
-            s.has_distortion = 1
-            for i, k in enumerate(("k1", "k2", "k3", "k4", "p1", "p2")):
-                s.distortion[i] = float(distortion_params.get(k, 0.0))
-        if pixtocam_ndc is not None:
-            s.has_ndc = 1
-            for i, v in enumerate(np.asarray(host(pixtocam_ndc), np.float32).reshape(9)):
-                s.pixtocam_ndc[i] = float(v)
-        if z_range is not None:
-            s.has_z_range = 1
-            s.z_range[0], s.z_range[1] = float(z_range[0]), float(z_range[1])
+        _camera_options(s, camtype, distortion_params, None if pixtocam_ndc is None else host(pixtocam_ndc), z_range)
         self.struct = s
 
 
@@ -583,7 +527,7 @@ class RadianceCache:
             torch.cuda.synchronize(self.device)
         self._check(self.lib.rc_load_weights(self._h, descs, len(weights)))
 
-    # -- hot path ---------------------------------------------------------------------------
+    # -- marshalling shared by the entry points ----------------------------------------------
     def _zeros_like_many(self, shapes):
         """Zero-filled float32 cuda tensors of the given shapes as views of ONE allocation (one fill kernel instead of
         one per output; every view starts on a 256-byte boundary)."""
@@ -604,48 +548,97 @@ class RadianceCache:
             return x                    # already where and how the library wants it (the per-call path of a training loop)
         return x.to(device=f"cuda:{self.device}", dtype=dtype).contiguous()
 
+    def _stream(self, handle=None):
+        """The raw hipStream_t a call is enqueued on: `handle`, or torch's current stream of this device."""
+        return self._torch.cuda.current_stream(self.device).cuda_stream if handle is None else handle
+
+    def _fill_rays(self, rays, held, checked):
+        """rc_rays of a dict of ray fields (_RAY_FIELDS; a missing one stays NULL), every device tensor registered in
+        `held` -> (struct, ray count).  checked: the fields are viewed as [n, 3] / [n] and must agree on n.  Otherwise
+        (the lean path) a float32 cuda tensor is passed by pointer as it is and n is the size of `near`."""
+        r, n = rc_rays(), None
+        for k in _RAY_FIELDS:
+            v = rays.get(k)
+            if v is None:
+                continue
+            t = self._dev(v)
+            if checked:
+                t = t.reshape(-1, 3) if k not in ("near", "far") else t.reshape(-1)
+                n = t.shape[0] if n is None else n
+                if t.shape[0] != n:
+                    raise ValueError(f"ray field {k} has {t.shape[0]} rows, expected {n}")
+            elif k == "near":
+                n = t.numel()
+            held[k] = t
+            setattr(r, k, t.data_ptr())
+        return r, n
+
+    def _rays_struct(self, rays):
+        held = {}
+        r, n = self._fill_rays(rays, held, checked=True)
+        return r, held, n
+
+    def _randoms(self, held, jitter=None, gumbel=None, resample_inds=None, n=None, tag=""):
+        """rc_randoms of a per-level jitter list (None, or a None level, stays NULL) and optional gumbel / resample_inds.
+        The launch that reads them is asynchronous: every device copy and the struct itself are registered in `held`
+        (keys prefixed with `tag`).  n: when given, the number of values each level's jitter must hold."""
+        rnd = rc_randoms()
+        if jitter is not None:
+            for l, j in enumerate(jitter):
+                if j is not None:
+                    t = held[f"{tag}jit{l}"] = self._dev(j)
+                    if n is not None and t.numel() != n:
+                        raise ValueError(f"jitter of level {l} has {t.numel()} values, expected {n}")
+                    rnd.jitter[l] = t.data_ptr()
+        if gumbel is not None:
+            held[tag + "gumbel"] = self._dev(gumbel)
+            rnd.gumbel = held[tag + "gumbel"].data_ptr()
+        if resample_inds is not None:
+            held[tag + "inds"] = self._dev(resample_inds, self._torch.int32)
+            rnd.resample_inds = held[tag + "inds"].data_ptr()
+        held[tag + "rnd"] = rnd
+        return rnd
+
+    def _pass_randoms(self, randoms, held):
+        """rc_render_rays' `rnd` argument of a randoms dict (jitter, gumbel, resample_inds), NULL for None."""
+        if randoms is None:
+            return None
+        return C.byref(self._randoms(held, randoms.get("jitter"), randoms.get("gumbel"), randoms.get("resample_inds")))
+
+    def _jitter_struct(self, jitters, held, n):
+        return None if jitters is None else C.byref(self._randoms(held, jitters, n=n))
+
+    def _outputs(self, table, names, shape_of, out=None):
+        """The outputs `names` of `table` (OUTPUTS, MAT_OUTPUTS or TRANSIENT_OUTPUTS), shaped by shape_of(name) -> (dict
+        name -> float32 cuda tensor, outputs struct holding their pointers).  The tensors are views of ONE zero-filled
+        allocation, or the caller's buffers `out`, checked."""
+        torch = self._torch
+        struct, ids = _OUTPUT_TABLES[table]
+        if out is None:
+            out = dict(zip(names, self._zeros_like_many([shape_of(nm) for nm in names])))
+        cout, res = struct(), {}
+        for nm in names:
+            t, shape = out[nm], shape_of(nm)
+            if tuple(t.shape) != shape or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"output buffer {nm}: expected contiguous float32 cuda tensor of shape {shape}")
+            res[nm] = t
+            cout.ptr[ids[nm]] = t.data_ptr()
+        return res, cout
+
+    # -- hot path ---------------------------------------------------------------------------
     def render_rays(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]] = None,
                     pass_mask: int = RC_PASS_CACHE, outputs: Optional[Iterable[str]] = None,
                     out: Optional[Dict[str, object]] = None):
         """rays: dict with origins, directions, viewdirs [n,3], near, far [n] or [n,1], optional lights,
         normals.  Returns dict name -> torch cuda tensor ([n,3] or [n]).  Passing the dict returned by
         an earlier call as `out` reuses its buffers (same pointers -> the captured hipGraph is replayed)."""
-        torch = self._torch
         r, held, n = self._rays_struct(rays)
-        rnd_p = None
-        if randoms is not None:
-            rnd = rc_randoms()
-            jit = randoms.get("jitter")
-            if jit is not None:
-                for l, j in enumerate(jit):
-                    if j is not None:
-                        t = self._dev(j).reshape(-1)
-                        held[f"jit{l}"] = t
-                        rnd.jitter[l] = t.data_ptr()
-            if randoms.get("gumbel") is not None:
-                held["gumbel"] = self._dev(randoms["gumbel"])
-                rnd.gumbel = held["gumbel"].data_ptr()
-            if randoms.get("resample_inds") is not None:
-                held["inds"] = self._dev(randoms["resample_inds"], torch.int32).reshape(-1)
-                rnd.resample_inds = held["inds"].data_ptr()
-            rnd_p = C.byref(rnd)
+        rnd_p = self._pass_randoms(randoms, held)
         names = [nm for nm, _ in OUTPUTS] if outputs is None else list(outputs)
         if out is not None:
             names = list(out.keys())
-        cout = rc_outputs()
-        res = {}
-        dev = f"cuda:{self.device}"
-        shapes = {nm: ((n, 3) if OUTPUTS[OUTPUT_ID[nm]][1] == 3 else (n,)) for nm in names}
-        fresh = dict(zip(names, self._zeros_like_many([shapes[nm] for nm in names]))) if out is None else None
-        for nm in names:
-            shape = shapes[nm]
-            t = out[nm] if out is not None else fresh[nm]
-            if tuple(t.shape) != shape or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"output buffer {nm}: expected contiguous float32 cuda tensor of shape {shape}")
-            res[nm] = t
-            cout.ptr[OUTPUT_ID[nm]] = t.data_ptr()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_render_rays(self._h, C.byref(r), n, rnd_p, pass_mask, C.byref(cout), stream))
+        res, cout = self._outputs(OUTPUTS, names, lambda nm: (n, 3) if OUTPUTS[OUTPUT_ID[nm]][1] == 3 else (n,), out)
+        self._check(self.lib.rc_render_rays(self._h, C.byref(r), n, rnd_p, pass_mask, C.byref(cout), self._stream()))
         self._keep = [held]   # keep inputs alive until the next call (async enqueue)
         return res
 
@@ -661,53 +654,29 @@ class RadianceCache:
             total += (n * width + 63) // 64 * 64
         return max(total, 1), offs, ids
 
+    @staticmethod
+    def _plan_outputs(plan, base: int) -> rc_outputs:
+        """rc_outputs pointing into a flat float32 buffer at address `base` that `plan` (output_plan) lays out."""
+        cout = rc_outputs()
+        for oid, off in plan[2]:
+            cout.ptr[oid] = base + 4 * off
+        return cout
+
     def render_chunk(self, rays: Dict[str, object], randoms, pass_mask: int, plan, out_flat=None, stream_handle=None):
         """rc_render_rays into one fresh flat buffer laid out by `plan` (output_plan).  The hot-loop variant of
         render_rays: device-resident float32 ray fields are passed by pointer as they are (no reshape / copy), the
         outputs are not wrapped into per-key tensors.  Returns (flat tensor, n)."""
-        torch = self._torch
-        r = rc_rays()
-        held = []
-        n = None
-        for k in _RAY_FIELDS:
-            v = rays.get(k)
-            if v is None:
-                continue
-            if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype is torch.float32 and v.is_contiguous()):
-                v = self._dev(v)
-            held.append(v)
-            setattr(r, k, v.data_ptr())
-            if k == "near":
-                n = v.numel()
-        rnd_p = None
-        if randoms is not None:
-            rnd = rc_randoms()
-            jit = randoms.get("jitter")
-            if jit is not None:
-                for l, j in enumerate(jit):
-                    if j is not None:
-                        t = self._dev(j)
-                        held.append(t)
-                        rnd.jitter[l] = t.data_ptr()
-            if randoms.get("gumbel") is not None:
-                t = self._dev(randoms["gumbel"])
-                held.append(t)
-                rnd.gumbel = t.data_ptr()
-            if randoms.get("resample_inds") is not None:
-                t = self._dev(randoms["resample_inds"], torch.int32)
-                held.append(t)
-                rnd.resample_inds = t.data_ptr()
-            rnd_p = C.byref(rnd)
-        total, _, ids = plan
+        held = {}
+        r, n = self._fill_rays(rays, held, checked=False)
+        rnd_p = self._pass_randoms(randoms, held)
         # out_flat: a zero-filled float32 cuda buffer of `total` elements the caller provides (a row of its arena)
-        flat = torch.zeros(total, dtype=torch.float32, device=held[0].device) if out_flat is None else out_flat
-        base = flat.data_ptr()
-        cout = rc_outputs()
-        for oid, off in ids:
-            cout.ptr[oid] = base + 4 * off
+        flat = out_flat
+        if flat is None:
+            flat = self._torch.zeros(plan[0], dtype=self._torch.float32, device=f"cuda:{self.device}")
+        cout = self._plan_outputs(plan, flat.data_ptr())
         # stream_handle: the raw hipStream_t to enqueue on (a caller that alternates streams skips torch's context manager)
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
-        self._check(self.lib.rc_render_rays(self._h, C.byref(r), n, rnd_p, pass_mask, C.byref(cout), stream))
+        self._check(self.lib.rc_render_rays(self._h, C.byref(r), n, rnd_p, pass_mask, C.byref(cout),
+                                            self._stream(stream_handle)))
         self._keep = held          # inputs stay alive until the next call (async enqueue)
         return flat, n
 
@@ -716,45 +685,20 @@ class RadianceCache:
         n_chunks * chunk rays each (contiguous, the last chunk edge-padded by the caller); `arena`: zero-filled
         [n_chunks, total] float32 cuda tensor whose rows are laid out by `plan`; chunk i goes to
         stream_handles[i % len] (raw hipStream_t values).  One ABI call for the whole image."""
-        torch = self._torch
-        r = rc_rays()
-        held = []
-        for k in _RAY_FIELDS:
-            v = rays.get(k)
-            if v is None:
-                continue
-            assert isinstance(v, torch.Tensor) and v.is_cuda and v.dtype is torch.float32 and v.is_contiguous(), k
+        held = {}
+        r, _ = self._fill_rays(rays, held, checked=False)
+        for k, v in held.items():
+            assert v is rays[k], k          # passed as it is: a contiguous float32 tensor on this device
             assert v.numel() == n_chunks * chunk * (1 if k in ("near", "far") else 3), (k, tuple(v.shape))
-            held.append(v)
-            setattr(r, k, v.data_ptr())
-        total, _, ids = plan
+        total = plan[0]
         assert arena.is_contiguous() and tuple(arena.shape) == (n_chunks, total)
-        base = arena.data_ptr()
-        cout = rc_outputs()
-        for oid, off in ids:
-            cout.ptr[oid] = base + 4 * off
+        cout = self._plan_outputs(plan, arena.data_ptr())
         hs = (C.c_void_p * len(stream_handles))(*stream_handles)
         self._check(self.lib.rc_render_chunks(self._h, C.byref(r), chunk, n_chunks, pass_mask, C.byref(cout), total, hs,
                                               len(stream_handles)))
         self._keep = held
 
-    def _rays_struct(self, rays):
-        r = rc_rays()
-        held = {}
-        n = None
-        for k in ("origins", "directions", "viewdirs", "near", "far", "lights", "normals"):
-            v = rays.get(k)
-            if v is None:
-                continue
-            t = self._dev(v)
-            t = t.reshape(-1, 3) if k not in ("near", "far") else t.reshape(-1)
-            held[k] = t
-            setattr(r, k, t.data_ptr())
-            n = t.shape[0] if n is None else n
-            if t.shape[0] != n:
-                raise ValueError(f"ray field {k} has {t.shape[0]} rows, expected {n}")
-        return r, held, n
-
+    # -- gradient layouts and the shared head of the loss calls --------------------------------
     def _segments(self, query, args, tail=()):
         """The two calls of an rc_*_grad_layout query (count, then the segments): [(tensor name, offset, shape)]."""
         cnt = C.c_int32()
@@ -795,20 +739,29 @@ class RadianceCache:
             raise ValueError(f"{what} must be a contiguous float32 cuda tensor of {total} elements")
         return flat
 
-    def _loss_prologue(self, key, grad, stream_handle=None):
+    def _loss_prologue(self, key, grad, stream_handle=None, slots=1):
         """The head of a loss call with one gradient buffer: the buffer of layout `key` (None for grad=False; `grad`
-        checked, or allocated zeroed when None), the zeroed float32 loss tensor [1] and the stream (the current one when
-        stream_handle is None)."""
-        torch = self._torch
+        checked, or allocated zeroed when None), the zeroed float32 loss tensor [slots] (2 for the transient loss, 4 for
+        the geometry terms) and the stream (the current one when stream_handle is None)."""
         flat = None if grad is False else self._grad_buffer(grad, self._grad_size(key))
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
-        return flat, loss, stream
+        loss = self._torch.zeros(slots, dtype=self._torch.float32, device=f"cuda:{self.device}")
+        return flat, loss, self._stream(stream_handle)
+
+    def _loss_prologue_pair(self, grads, slots=1):
+        """_loss_prologue of data_backward / geometry_backward, whose gradient goes to two buffers: (density flat of the
+        last level, shader flat), either one None (allocated zeroed); grads=False gives (None, None)."""
+        flats = [None, None]
+        if grads is not False:
+            given = list(grads) if grads is not None else [None, None]
+            for i, key in enumerate((self.cfg.num_levels - 1, "shader")):
+                flats[i] = self._grad_buffer(given[i], self._grad_size(key), f"grads[{i}]")
+        _, loss, stream = self._loss_prologue(None, False, slots=slots)
+        return flats, loss, stream
 
     def _regularizer(self, fn, key, args, grad):
         """rc_{density,light,material}_regularizer: fn(handle, *args, grad flat, loss, stream) -> (grad flat or None, loss)."""
         flat, loss, stream = self._loss_prologue(key, grad)
-        self._check(fn(self._h, *args, None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
+        self._check(fn(self._h, *args, _ptr(flat), loss.data_ptr(), stream))
         return flat, loss
 
     def _lossmult(self, lossmult, held, n):
@@ -839,7 +792,6 @@ class RadianceCache:
     def hashgrid_backward(self, grid_id: int, points, d_features, grads=None, apply_contraction: bool = True):
         """rc_hashgrid_backward: scatter d L / d features [n, L*F] (the layout hashgrid_lookup returns) into the tables'
         gradient buffer (flat float32 cuda tensor of hashgrid_grad_layout(grid_id)[1] elements; accumulated into when given)."""
-        torch = self._torch
         pts = self._dev(points).reshape(-1, 3).contiguous()
         n = pts.shape[0]
         df = self._dev(d_features).reshape(n, -1).contiguous()
@@ -847,9 +799,8 @@ class RadianceCache:
         g = self.cfg_grid(grid_id)
         if df.shape[1] != g.out_dim:
             raise ValueError(f"d_features must have {g.out_dim} columns")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rc_hashgrid_backward(self._h, grid_id, pts.data_ptr(), n, df.data_ptr(), grads.data_ptr(),
-                                                  1 if apply_contraction else 0, stream))
+                                                  1 if apply_contraction else 0, self._stream()))
         self._keep = [pts, df]
         return grads
 
@@ -869,10 +820,8 @@ class RadianceCache:
             df = self._dev(d_feature).reshape(n, 64).contiguous()
         grads = self._grad_buffer(grads, self._grad_size(level))
         dens = torch.empty(n, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_density_backward(self._h, level, pts.data_ptr(), n, dd.data_ptr(),
-                                                 None if df is None else df.data_ptr(), grads.data_ptr(), dens.data_ptr(),
-                                                 stream))
+        self._check(self.lib.rc_density_backward(self._h, level, pts.data_ptr(), n, dd.data_ptr(), _ptr(df),
+                                                 grads.data_ptr(), dens.data_ptr(), self._stream()))
         self._keep = [pts, dd, df]
         return grads, dens
 
@@ -885,7 +834,6 @@ class RadianceCache:
         (density_grad_layout(level)), accumulated into; a missing one is allocated zeroed.  levels: the proposal levels
         whose backward runs (default all); the others get no gradient (None in the result).
         Returns (flat buffers, losses [num_levels - 1] cuda tensor)."""
-        torch = self._torch
         r, held, n = self._rays_struct(rays)
         nprop = self.cfg.num_levels - 1
         levels = tuple(range(nprop)) if levels is None else tuple(levels)
@@ -901,28 +849,13 @@ class RadianceCache:
                 continue
             flats[l] = self._grad_buffer(flats[l], self._grad_size(l), f"grads[{l}]")
             ptrs[l] = flats[l].data_ptr()
-        losses = torch.zeros(max(nprop, 1), dtype=torch.float32, device=f"cuda:{self.device}")
+        _, losses, stream = self._loss_prologue(None, False, slots=max(nprop, 1))
         m = (C.c_float * nprop)(*[float(v) for v in mults])
         b = (C.c_float * nprop)(*[float(v) for v in blurs])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_interlevel_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n, rnd_p,
-                                                    float(anneal), m, b, ptrs, losses.data_ptr(), stream))
+        self._check(self.lib.rc_interlevel_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), m, b, ptrs,
+                                                    losses.data_ptr(), stream))
         self._keep = [held]
         return flats, losses
-
-    def _jitter_struct(self, jitters, held, n):
-        if jitters is None:
-            return None
-        rnd = rc_randoms()
-        for l, j in enumerate(jitters):
-            if j is not None:
-                t = self._dev(j).reshape(-1)
-                if t.shape[0] != n:
-                    raise ValueError(f"jitter of level {l} has {t.shape[0]} values, expected {n}")
-                held[f"jit{l}"] = t
-                rnd.jitter[l] = t.data_ptr()
-        held["rnd"] = rnd
-        return C.byref(rnd)
 
     def data_backward(self, rays: Dict[str, object], rgb, jitters=None, anneal: float = 0.4, lossmult=None,
                       charb_padding: float = 1e-3, mult: float = 1.0, grads=None):
@@ -931,7 +864,6 @@ class RadianceCache:
         (shader_grad_layout).  jitters / anneal as interlevel_backward; lossmult: [n] or None (1).  grads: (density
         flat, shader flat) to accumulate into, either None (allocated zeroed); grads=False computes the loss only.
         Returns ((density flat, shader flat), loss [1] cuda tensor); one copy of the term (the reference adds it twice)."""
-        torch = self._torch
         r, held, n = self._rays_struct(rays)
         rnd_p = self._jitter_struct(jitters, held, n)
         gt = self._dev(rgb).reshape(-1, 3).contiguous()
@@ -939,17 +871,10 @@ class RadianceCache:
             raise ValueError("rgb must be [n, 3]")
         held["gt"] = gt
         lm = self._lossmult(lossmult, held, n)
-        flats = [None, None]
-        if grads is not False:
-            given = list(grads) if grads is not None else [None, None]
-            for i, level in enumerate((self.cfg.num_levels - 1, "shader")):
-                flats[i] = self._grad_buffer(given[i], self._grad_size(level), f"grads[{i}]")
-        loss = torch.zeros(1, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_data_backward(self._h, C.byref(r), gt.data_ptr(), None if lm is None else lm.data_ptr(), n,
-                                              rnd_p, float(anneal), float(charb_padding), float(mult),
-                                              None if flats[0] is None else flats[0].data_ptr(),
-                                              None if flats[1] is None else flats[1].data_ptr(), loss.data_ptr(), stream))
+        flats, loss, stream = self._loss_prologue_pair(grads)
+        self._check(self.lib.rc_data_backward(self._h, C.byref(r), gt.data_ptr(), _ptr(lm), n, rnd_p, float(anneal),
+                                              float(charb_padding), float(mult), _ptr(flats[0]), _ptr(flats[1]),
+                                              loss.data_ptr(), stream))
         self._keep = [held]
         return (flats[0], flats[1]), loss
 
@@ -962,7 +887,6 @@ class RadianceCache:
         -0.25 / 1e4).  jitters / anneal / lossmult as data_backward.  grads: (density flat, shader flat) to accumulate
         into, either None (allocated zeroed); grads=False computes the losses only.
         Returns ((density flat, shader flat), losses [4] cuda tensor); one copy of each term."""
-        torch = self._torch
         r, held, n = self._rays_struct(rays)
         rnd_p = self._jitter_struct(jitters, held, n)
         lm = self._lossmult(lossmult, held, n)
@@ -972,18 +896,9 @@ class RadianceCache:
         if unknown:
             raise ValueError(f"unknown geometry loss fields {sorted(unknown)}")
         cfg = rc_geometry_loss(**{k: float(v) for k, v in t.items()})
-        flats = [None, None]
-        if grads is not False:
-            given = list(grads) if grads is not None else [None, None]
-            for i, level in enumerate((self.cfg.num_levels - 1, "shader")):
-                flats[i] = self._grad_buffer(given[i], self._grad_size(level), f"grads[{i}]")
-        losses = torch.zeros(4, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_geometry_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n, rnd_p,
-                                                  float(anneal), C.byref(cfg),
-                                                  None if flats[0] is None else flats[0].data_ptr(),
-                                                  None if flats[1] is None else flats[1].data_ptr(), losses.data_ptr(),
-                                                  stream))
+        flats, losses, stream = self._loss_prologue_pair(grads, slots=4)
+        self._check(self.lib.rc_geometry_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg),
+                                                  _ptr(flats[0]), _ptr(flats[1]), losses.data_ptr(), stream))
         self._keep = [held]
         return (flats[0], flats[1]), losses
 
@@ -1011,10 +926,9 @@ class RadianceCache:
         rnd, mr = self._material_randoms(randoms, n, K, held)
         lm = self._lossmult(lossmult, held, n)
         cfg = rc_light_sampling_loss(mult=float(mult), linear_to_srgb=int(bool(linear_to_srgb)))
-        flat, loss, stream = self._loss_prologue("light", grad, stream_handle=stream_handle)
-        self._check(self.lib.rc_light_sampling_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n,
-                                                        C.byref(rnd), C.byref(mr), K, C.byref(cfg),
-                                                        None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
+        flat, loss, stream = self._loss_prologue("light", grad, stream_handle)
+        self._check(self.lib.rc_light_sampling_backward(self._h, C.byref(r), _ptr(lm), n, C.byref(rnd), C.byref(mr), K,
+                                                        C.byref(cfg), _ptr(flat), loss.data_ptr(), stream))
         self._keep = [held]
         return flat, loss
 
@@ -1044,24 +958,20 @@ class RadianceCache:
         st.grad_max_val = float(step.get("grad_max_val", 0.0))
         st.grad_max_norm = float(step.get("grad_max_norm", 0.0))
         st.zero_grads = int(bool(step.get("zero_grads", False)))
-        stream = self._torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
-        self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), stream))
+        self._check(self.lib.rc_adam_update(self._h, table.bufs, len(table.bufs), C.byref(st), self._stream(stream_handle)))
 
     def load_params_flat(self, layout, params, stream_handle=None):
-        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light", "material", "envmap"
-        or, on a time-resolved handle, "transient_heads")
-        from a flat
-        float32 cuda buffer in that layout -- table copies ordered on the current stream, the dense layers in one copy
-        to the host (the call waits for the stream there).  Renders afterwards equal those after load_weights of the
-        same tensors, bitwise."""
+        """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light", "material",
+        "envmap" or, on a time-resolved handle, "transient_heads") from a flat float32 cuda buffer in that layout -- table
+        copies ordered on the current stream, the dense layers in one copy to the host (the call waits for the stream
+        there).  Renders afterwards equal those after load_weights of the same tensors, bitwise."""
         torch = self._torch
         key = layout if isinstance(layout, str) else _LAYOUT_KEYS.get(int(layout), int(layout))
         lay = _GRAD_LAYOUTS[key][2] if isinstance(key, str) else key
         total = self._grad_size(key)
         if params.numel() != total or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous():
             raise ValueError(f"params must be a contiguous float32 cuda tensor of {total} elements")
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
-        self._check(self.lib.rc_load_params_flat(self._h, lay, params.data_ptr(), stream))
+        self._check(self.lib.rc_load_params_flat(self._h, lay, params.data_ptr(), self._stream(stream_handle)))
 
     def prng_fill(self, key, shape, mode: str = "uniform", minval: float = 0.0, maxval: float = 1.0):
         """rc_prng_fill: the tensor jax.random.{bits,uniform,normal,gumbel}(key, shape) of the reference's pinned jax
@@ -1075,9 +985,29 @@ class RadianceCache:
         shape = tuple(int(v) for v in shape)
         n = int(np.prod(shape)) if shape else 1
         out = torch.empty(shape, dtype=torch.int32 if mode == "bits" else torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_prng_fill(self._h, k, modes[mode], float(minval), float(maxval), n, out.data_ptr(), stream))
+        self._check(self.lib.rc_prng_fill(self._h, k, modes[mode], float(minval), float(maxval), n, out.data_ptr(),
+                                          self._stream()))
         return out
+
+    # -- rays from cameras ------------------------------------------------------------------------
+    def _cast_tensors(self, shape, out):
+        torch = self._torch
+        t = {}
+        for k, width in CAST_OUTPUTS:
+            t[k] = torch.empty(tuple(shape) + (width,), dtype=torch.float32, device=f"cuda:{self.device}")
+            setattr(out, k, t[k].data_ptr())
+        return t
+
+    def _pix_jitter(self, pix_jitter, n, per="pixel"):
+        """The two sub-pixel offset arrays (dx, dy) on the device, flat with n values each; None for None."""
+        if pix_jitter is None:
+            return None
+        torch = self._torch
+        jit = [self._dev(j if isinstance(j, torch.Tensor) else np.ascontiguousarray(j, dtype=np.float32)).reshape(-1)
+               for j in pix_jitter]
+        if jit[0].numel() != n or jit[1].numel() != n:
+            raise ValueError(f"pix_jitter: two arrays with one value per {per}")
+        return jit
 
     def cast_rays(self, camera, pix_x_int=None, pix_y_int=None, rect=None, pix_jitter=None):
         """rc_cast_rays: rays of `camera` (pixtocam [3,3], camtoworld [3,4], light, near, far; optional camtype,
@@ -1085,34 +1015,17 @@ class RadianceCache:
         pixel batch (two int arrays of one shape) or for rect = (x0, y0, width, height), as a Rays of cuda tensors
         with the batch shape of the pixels ([h, w, .] for a rectangle).  pix_jitter = (dx, dy): the sub-pixel offsets
         the reference draws when jitter > 0 (camera_utils.py:943-957), float32 arrays of the pixels' shape."""
-        from .rays import Rays
         torch = self._torch
         cam = rc_camera()
         p2c = np.asarray(camera.pixtocam, np.float32).reshape(9)
         c2w = np.asarray(camera.camtoworld, np.float32).reshape(12)
         light = c2w.reshape(3, 4)[:, 3] if camera.light is None else np.asarray(camera.light, np.float32).reshape(3)
-        for i in range(9):
-            cam.pixtocam[i] = float(p2c[i])
-        for i in range(12):
-            cam.camtoworld[i] = float(c2w[i])
-        for i in range(3):
-            cam.light[i] = float(light[i])
+        for dst, src in ((cam.pixtocam, p2c), (cam.camtoworld, c2w), (cam.light, light)):
+            for i, v in enumerate(src):
+                dst[i] = float(v)
         cam.near, cam.far = float(camera.near), float(camera.far)
-        cam.camtype = {"perspective": 0, "pano": 1, "fisheye": 2, "fisheye_equisolid": 3}[getattr(camera, "camtype", "perspective")]
-        dist = getattr(camera, "distortion_params", None)
-        if dist is not None:              # dict of floats like the reference's distortion_params (k1..k4, p1, p2; missing = 0)
-            cam.has_distortion = 1
-            for i, k in enumerate(("k1", "k2", "k3", "k4", "p1", "p2")):
-                cam.distortion[i] = float(dist.get(k, 0.0))
-        ndc = getattr(camera, "pixtocam_ndc", None)
-        if ndc is not None:
-            cam.has_ndc = 1
-            for i, v in enumerate(np.asarray(ndc, np.float32).reshape(9)):
-                cam.pixtocam_ndc[i] = float(v)
-        zr = getattr(camera, "z_range", None)
-        if zr is not None:
-            cam.has_z_range = 1
-            cam.z_range[0], cam.z_range[1] = float(zr[0]), float(zr[1])
+        _camera_options(cam, getattr(camera, "camtype", "perspective"), getattr(camera, "distortion_params", None),
+                        getattr(camera, "pixtocam_ndc", None), getattr(camera, "z_range", None))
         dev = f"cuda:{self.device}"
         if rect is not None:
             x0, y0, w, hgt = (int(v) for v in rect)
@@ -1123,27 +1036,16 @@ class RadianceCache:
             if px.shape != py.shape:
                 raise ValueError("pix_x_int and pix_y_int must have the same shape")
             shape, n, x0, y0, w, hgt = tuple(px.shape), px.numel(), 0, 0, 0, 0
-        jit = None
-        if pix_jitter is not None:
-            jit = [self._dev(np.ascontiguousarray(j, dtype=np.float32) if not isinstance(j, torch.Tensor) else j).reshape(-1) for j in pix_jitter]
-            if jit[0].numel() != n or jit[1].numel() != n:
-                raise ValueError("pix_jitter: two arrays with one value per pixel")
+        jit = self._pix_jitter(pix_jitter, n)
+        if jit is not None:
             cam.pix_dx, cam.pix_dy = jit[0].data_ptr(), jit[1].data_ptr()
         out = rc_cast_outputs()
-        t = {}
-        for k, width in CAST_OUTPUTS:
-            t[k] = torch.empty(shape + (width,), dtype=torch.float32, device=dev)
-            setattr(out, k, t[k].data_ptr())
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_cast_rays(self._h, C.byref(cam), px.data_ptr() if px is not None else None,
-                                          py.data_ptr() if py is not None else None, n, x0, y0, w, hgt, C.byref(out), stream))
+        t = self._cast_tensors(shape, out)
+        self._check(self.lib.rc_cast_rays(self._h, C.byref(cam), _ptr(px), _ptr(py), n, x0, y0, w, hgt, C.byref(out),
+                                          self._stream()))
         self._keep = [px, py, jit]
-        ones = torch.ones(shape + (1,), dtype=torch.float32, device=dev)
         zi = torch.zeros(shape + (1,), dtype=torch.int32, device=dev)
-        return Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
-                    radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
-                    vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=ones, near=t["near"],
-                    far=t["far"], cam_idx=zi, light_idx=zi)
+        return _rays_of_cast(t, torch.ones(shape + (1,), dtype=torch.float32, device=dev), zi, zi)
 
     def camera_set(self, pixtocams, camtoworlds, lights=None, near: float = 0.0, far: float = 0.0, camtype="perspective",
                    distortion_params=None, pixtocam_ndc=None, z_range=None):
@@ -1152,43 +1054,25 @@ class RadianceCache:
         the other arguments as in cast_rays' camera."""
         return CameraSet(self, pixtocams, camtoworlds, lights, near, far, camtype, distortion_params, pixtocam_ndc, z_range)
 
-    def _cast_tensors(self, shape, out):
-        torch = self._torch
-        t = {}
-        for k, width in CAST_OUTPUTS:
-            t[k] = torch.empty(tuple(shape) + (width,), dtype=torch.float32, device=f"cuda:{self.device}")
-            setattr(out, k, t[k].data_ptr())
-        return t
-
     def cast_rays_multi(self, cameras: "CameraSet", cam_idx, pix_x_int, pix_y_int, pix_jitter=None):
         """rc_cast_rays_multi: the rays of pixels (pix_x_int, pix_y_int) of cameras cam_idx (three int arrays of one shape;
         cuda int32 tensors are used where they are) in ONE launch, as a Rays of cuda tensors with the pixels' batch
         shape; every field is bitwise what cast_rays yields per camera.  cam_idx must lie in [0, cameras.count): the
         kernel only clamps it for memory safety.  lossmult is 1, cam_idx is carried over, light_idx is 0."""
-        from .rays import Rays
         torch = self._torch
         as_i32 = lambda a: self._dev(a if isinstance(a, torch.Tensor) else np.ascontiguousarray(a), torch.int32)
         ci, px, py = as_i32(cam_idx), as_i32(pix_x_int), as_i32(pix_y_int)
         if not (ci.shape == px.shape == py.shape):
             raise ValueError("cam_idx, pix_x_int and pix_y_int must have the same shape")
         shape, n = tuple(px.shape), px.numel()
-        jit = [None, None]
-        if pix_jitter is not None:
-            jit = [self._dev(j if isinstance(j, torch.Tensor) else np.ascontiguousarray(j, dtype=np.float32)).reshape(-1) for j in pix_jitter]
-            if jit[0].numel() != n or jit[1].numel() != n:
-                raise ValueError("pix_jitter: two arrays with one value per pixel")
+        jit = self._pix_jitter(pix_jitter, n) or [None, None]
         out = rc_cast_outputs()
         t = self._cast_tensors(shape, out)
-        ptr = lambda x: None if x is None else x.data_ptr()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_cast_rays_multi(self._h, C.byref(cameras.struct), ptr(ci), ptr(px), ptr(py), n, ptr(jit[0]),
-                                                ptr(jit[1]), C.byref(out), stream))
+        self._check(self.lib.rc_cast_rays_multi(self._h, C.byref(cameras.struct), _ptr(ci), _ptr(px), _ptr(py), n,
+                                                _ptr(jit[0]), _ptr(jit[1]), C.byref(out), self._stream()))
         self._keep = [ci, px, py, jit, cameras]
         ones = torch.ones(shape + (1,), dtype=torch.float32, device=px.device)
-        return Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
-                    radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
-                    vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=ones, near=t["near"],
-                    far=t["far"], cam_idx=ci.reshape(shape + (1,)), light_idx=torch.zeros_like(ci).reshape(shape + (1,)))
+        return _rays_of_cast(t, ones, ci.reshape(shape + (1,)), torch.zeros_like(ci).reshape(shape + (1,)))
 
     def train_batch(self, cameras: "CameraSet", images, key, n: int, patch_size: int = 1, border: int = 0,
                     batching: str = "all_images", cam_lossmult=None, pix_jitter=None):
@@ -1197,7 +1081,6 @@ class RadianceCache:
         [n, .] cuda tensors with lossmult, cam_idx, pix_x_int, pix_y_int filled in, rgb [n, 3]).  The index rule is
         data.patch_indices, this package's own."""
         from . import prng
-        from .rays import Rays
         torch = self._torch
         if batching not in BATCHING:
             raise ValueError(f"unknown batching {batching!r}")
@@ -1210,11 +1093,8 @@ class RadianceCache:
         dev = f"cuda:{self.device}"
         k = (C.c_uint32 * 2)(*[int(v) for v in prng.as_key(key)])
         cs = cameras.struct
-        jit = None
-        if pix_jitter is not None:
-            jit = [self._dev(j if isinstance(j, torch.Tensor) else np.ascontiguousarray(j, dtype=np.float32)).reshape(-1) for j in pix_jitter]
-            if jit[0].numel() != n or jit[1].numel() != n:
-                raise ValueError("pix_jitter: two arrays with one value per ray")
+        jit = self._pix_jitter(pix_jitter, n, per="ray")
+        if jit is not None:
             cs = rc_camera_set.from_buffer_copy(cs)
             cs.pix_dx, cs.pix_dy = jit[0].data_ptr(), jit[1].data_ptr()
         lm = None if cam_lossmult is None else self._dev(cam_lossmult).reshape(-1)
@@ -1227,55 +1107,38 @@ class RadianceCache:
         idx = torch.empty((3, max(n, 0), 1), dtype=torch.int32, device=dev)
         out.rgb, out.lossmult = rgb.data_ptr(), lossmult.data_ptr()
         out.cam_idx, out.pix_x, out.pix_y = idx[0].data_ptr(), idx[1].data_ptr(), idx[2].data_ptr()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rc_train_batch(self._h, C.byref(cs), images.data_ptr(),
                                             RC_IMAGE_U8 if images.dtype == torch.uint8 else RC_IMAGE_F32, int(images.shape[1]),
-                                            int(images.shape[2]), None if lm is None else lm.data_ptr(), k, int(patch_size),
-                                            int(border), BATCHING[batching], n, C.byref(out), stream))
+                                            int(images.shape[2]), _ptr(lm), k, int(patch_size), int(border),
+                                            BATCHING[batching], n, C.byref(out), self._stream()))
         self._keep = [jit, lm, cameras, images]
-        rays = Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
-                    radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=t["origins"],
-                    vcam_look=t["look"], vcam_up=t["up"], vcam_origins=t["origins"], lossmult=lossmult, near=t["near"],
-                    far=t["far"], cam_idx=idx[0], light_idx=torch.zeros_like(idx[0]), pix_x_int=idx[1], pix_y_int=idx[2])
-        return rays, rgb
+        return _rays_of_cast(t, lossmult, idx[0], torch.zeros_like(idx[0]), idx[1], idx[2]), rgb
 
+    # -- time-resolved cache ------------------------------------------------------------------------
     def render_transient(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]] = None,
                          outputs: Optional[Iterable[str]] = None):
         """Time-resolved cache (rc_render_transient).  rays needs `lights` and `cam_origins` besides the usual
         fields; randoms: {"jitter": [u0, u1, u2], "shadow_jitter": [v0, v1, v2]} or None (shadow_jitter: per-level jitter of
         the n * 32 shadow rays when the config has use_occlusions).  Returns dict name -> cuda tensor: [n, n_bins, 3] for the
         histograms, [n, 3] / [n] otherwise."""
-        torch = self._torch
         r, held, n = self._rays_struct(rays)
         cam = self._dev(rays["cam_origins"]).reshape(-1, 3)
         held["cam_origins"] = cam
-        def jitter_struct(key):
-            if randoms is None or randoms.get(key) is None:
-                return None
-            rnd = rc_randoms()
-            for l, j in enumerate(randoms[key]):
-                if j is not None:
-                    t = self._dev(j).reshape(-1)
-                    held[f"{key}{l}"] = t
-                    rnd.jitter[l] = t.data_ptr()
-            held[key + "_struct"] = rnd
-            return C.byref(rnd)
-
-        rnd_p = jitter_struct("jitter")
-        shadow_p = jitter_struct("shadow_jitter")      # [3][n * 32], use_occlusions only
+        rnd_p, shadow_p = None, None                   # shadow_jitter: [3][n * 32], use_occlusions only
+        if randoms is not None and randoms.get("jitter") is not None:
+            rnd_p = C.byref(self._randoms(held, randoms["jitter"]))
+        if randoms is not None and randoms.get("shadow_jitter") is not None:
+            shadow_p = C.byref(self._randoms(held, randoms["shadow_jitter"], tag="shadow_"))
         names = [nm for nm, _ in TRANSIENT_OUTPUTS] if outputs is None else list(outputs)
-        cout = rc_transient_outputs()
-        res = {}
-        dev = f"cuda:{self.device}"
         nb = self.cfg.transient.n_bins
+
         def tshape(nm):
             kind = TRANSIENT_OUTPUTS[TRANSIENT_OUTPUT_ID[nm]][1]
             return (n, nb, 3) if kind == "bins" else ((n, 3) if kind == 3 else (n,))
-        for nm, t in zip(names, self._zeros_like_many([tshape(nm) for nm in names])):
-            res[nm] = t
-            cout.ptr[TRANSIENT_OUTPUT_ID[nm]] = t.data_ptr()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_render_transient(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, shadow_p, C.byref(cout), stream))
+
+        res, cout = self._outputs(TRANSIENT_OUTPUTS, names, tshape)
+        self._check(self.lib.rc_render_transient(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, shadow_p, C.byref(cout),
+                                                 self._stream()))
         self._keep = [held]
         return res
 
@@ -1294,7 +1157,6 @@ class RadianceCache:
         loss and the "td:" adjoints are still computed).  Returns (grad flat or None, losses [2] cuda tensor: loss, mse)."""
         from .config import TransientDataLossConfig
 
-        torch = self._torch
         cfg = TransientDataLossConfig() if cfg is None else cfg
         if (cfg.loss_type != "rawnerf_transient_unbiased" or tuple(cfg.transient_gauss_sigma_scales) or cfg.mask_lossmult
                 or cfg.clip_eval or cfg.use_itof):
@@ -1302,9 +1164,7 @@ class RadianceCache:
         r, held, n = self._rays_struct(rays)
         cam = self._dev(rays["cam_origins"]).reshape(-1, 3)
         held["cam_origins"] = cam
-        rnd_p = None
-        if randoms is not None and randoms.get("jitter") is not None:
-            rnd_p = self._jitter_struct(randoms["jitter"], held, n)
+        rnd_p = None if randoms is None else self._jitter_struct(randoms.get("jitter"), held, n)
         lm = self._lossmult(lossmult, held, n)
         # without a time-resolved config there is no n_bins to check against: the call itself refuses such a handle
         count = None if self.cfg.transient is None else n * self.cfg.transient.n_bins * 3
@@ -1327,15 +1187,13 @@ class RadianceCache:
                                    clip_val=float(cfg.clip_val), thresh=float(cfg.loss_thresh),
                                    use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
                                    use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)))
-        flat = None if grad is False else self._grad_buffer(grad, self._grad_size("transient_heads"))
-        losses = torch.zeros(2, dtype=torch.float32, device=f"cuda:{self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream if stream_handle is None else stream_handle
+        flat, losses, stream = self._loss_prologue("transient_heads", grad, stream_handle, slots=2)
         self._check(self.lib.rc_transient_data_backward(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, gt_p, rn_p, gn_p,
-                                                        None if lm is None else lm.data_ptr(), C.byref(c),
-                                                        None if flat is None else flat.data_ptr(), losses.data_ptr(), stream))
+                                                        _ptr(lm), C.byref(c), _ptr(flat), losses.data_ptr(), stream))
         self._keep = [held]
         return flat, losses
 
+    # -- material stage -------------------------------------------------------------------------------
     def material_grad_layout(self):
         """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid
         tables, then bottleneck_layer, pred_brdf_layer), and its size in floats."""
@@ -1349,15 +1207,10 @@ class RadianceCache:
     def _shading_randoms(self, randoms, held):
         """The rc_randoms / rc_material_randoms of material_smoothness_backward: the primary pass's jitter and the shading
         point's pick (gumbel or resample_inds) of render_material's randoms; the sampler members stay NULL."""
-        torch = self._torch
-        rnd = rc_randoms()
-        if randoms.get("jitter") is not None:
-            for l, j in enumerate(randoms["jitter"]):
-                held[f"jit{l}"] = self._dev(j).reshape(-1)
-                rnd.jitter[l] = held[f"jit{l}"].data_ptr()
-        mr = rc_material_randoms()
+        rnd = self._randoms(held, randoms.get("jitter"))
+        mr = held["mrnd"] = rc_material_randoms()
         if randoms.get("resample_inds") is not None:
-            held["m_inds"] = self._dev(randoms["resample_inds"], torch.int32).reshape(-1)
+            held["m_inds"] = self._dev(randoms["resample_inds"], self._torch.int32).reshape(-1)
             mr.resample_inds = held["m_inds"].data_ptr()
         elif randoms.get("gumbel") is not None:
             held["m_gumbel"] = self._dev(randoms["gumbel"])
@@ -1383,10 +1236,9 @@ class RadianceCache:
         cfg = rc_material_smoothness_loss(mult=float(mult), weight_albedo=float(weight_albedo),
                                           weight_other=float(weight_other), noise=float(noise_scale),
                                           tensoir_albedo=int(bool(tensoir_albedo)))
-        flat, loss, stream = self._loss_prologue("material", grad, stream_handle=stream_handle)
-        self._check(self.lib.rc_material_smoothness_backward(self._h, C.byref(r), None if lm is None else lm.data_ptr(), n,
-                                                             C.byref(rnd), C.byref(mr), nz.data_ptr(), C.byref(cfg),
-                                                             None if flat is None else flat.data_ptr(), loss.data_ptr(),
+        flat, loss, stream = self._loss_prologue("material", grad, stream_handle)
+        self._check(self.lib.rc_material_smoothness_backward(self._h, C.byref(r), _ptr(lm), n, C.byref(rnd), C.byref(mr),
+                                                             nz.data_ptr(), C.byref(cfg), _ptr(flat), loss.data_ptr(),
                                                              stream))
         self._keep = [held]
         return flat, loss
@@ -1426,33 +1278,24 @@ class RadianceCache:
                                   use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
                                   use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)),
                                   use_norm_rawnerf=int(bool(cfg.use_norm_rawnerf)))
-        flat, loss, stream = self._loss_prologue("material", grad, stream_handle=stream_handle)
+        flat, loss, stream = self._loss_prologue("material", grad, stream_handle)
+        head = (self._h, C.byref(r), gt.data_ptr(), _ptr(lm), n, C.byref(rnd), C.byref(mr), K, C.byref(c))
         if env_grad is None or env_grad is False:
-            self._check(self.lib.rc_material_data_backward(self._h, C.byref(r), gt.data_ptr(),
-                                                           None if lm is None else lm.data_ptr(), n, C.byref(rnd),
-                                                           C.byref(mr), K, C.byref(c),
-                                                           None if flat is None else flat.data_ptr(), loss.data_ptr(), stream))
-            self._keep = [held]
-            return flat, loss
-        env = self._grad_buffer(None if env_grad is True else env_grad, self._grad_size("envmap"), "env_grad")
-        self._check(self.lib.rc_material_data_backward_env(self._h, C.byref(r), gt.data_ptr(),
-                                                           None if lm is None else lm.data_ptr(), n, C.byref(rnd),
-                                                           C.byref(mr), K, C.byref(c), float(env_scale),
-                                                           None if flat is None else flat.data_ptr(), env.data_ptr(),
-                                                           loss.data_ptr(), stream))
+            env = None
+            self._check(self.lib.rc_material_data_backward(*head, _ptr(flat), loss.data_ptr(), stream))
+        else:
+            env = self._grad_buffer(None if env_grad is True else env_grad, self._grad_size("envmap"), "env_grad")
+            self._check(self.lib.rc_material_data_backward_env(*head, float(env_scale), _ptr(flat), env.data_ptr(),
+                                                               loss.data_ptr(), stream))
         self._keep = [held]
-        return flat, env, loss
+        return (flat, loss) if env is None else (flat, env, loss)
 
     def _material_randoms(self, randoms, n, K, held):
         """The rc_randoms / rc_material_randoms of render_material and light_sampling_backward (device copies kept in
         `held`)."""
         torch = self._torch
-        rnd = rc_randoms()
-        if randoms.get("jitter") is not None:
-            for l, j in enumerate(randoms["jitter"]):
-                held[f"jit{l}"] = self._dev(j).reshape(-1)
-                rnd.jitter[l] = held[f"jit{l}"].data_ptr()
-        mr = rc_material_randoms()
+        rnd = self._randoms(held, randoms.get("jitter"))
+        mr = held["mrnd"] = rc_material_randoms()
         for k in ("gumbel", "vmf_noise", "spec_u1", "spec_u2", "cos_u1", "cos_u2", "vmf_v", "vmf_tmp"):
             if k == "gumbel" and randoms.get(k) is None:
                 continue                      # the primary pick is handed over as resample_inds
@@ -1499,24 +1342,19 @@ class RadianceCache:
         vmf_tmp, spec_jitter[3], spec_gumbel, diff_jitter[3], diff_gumbel) and optionally the categorical picks
         themselves (resample_inds [n]; spec_resample_inds [n*Ks] + diff_resample_inds [n*Kd]), which replace the draws.
         Returns (cache_outputs, material_outputs) as dicts of cuda tensors."""
-        torch = self._torch
         K = num_secondary_samples or self.cfg.num_secondary_samples
         r, held, n = self._rays_struct(rays)
         rnd, mr = self._material_randoms(randoms, n, K, held)
-        cout, mout = rc_outputs(), rc_mat_outputs()
-        cres, mres = {}, {}
-        c_items = [(i, nm, width) for i, (nm, width) in enumerate(OUTPUTS) if nm not in ("env_map_rgb", "rgb_no_env")]
-        m_items = [(i, nm, width) for i, (nm, width) in enumerate(MAT_OUTPUTS)]
-        bufs = self._zeros_like_many([((n, 3) if width == 3 else (n,)) for _, _, width in c_items + m_items])
-        for (i, nm, _), t in zip(c_items, bufs[: len(c_items)]):
-            cres[nm] = t
-            cout.ptr[i] = t.data_ptr()
-        for (i, nm, _), t in zip(m_items, bufs[len(c_items):]):
-            mres[nm] = t
-            mout.ptr[i] = t.data_ptr()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        c_names = [nm for nm, _ in OUTPUTS if nm not in ("env_map_rgb", "rgb_no_env")]
+        m_names = [nm for nm, _ in MAT_OUTPUTS]
+        cshape = lambda nm: (n, 3) if OUTPUTS[OUTPUT_ID[nm]][1] == 3 else (n,)
+        mshape = lambda nm: (n, 3) if MAT_OUTPUTS[MAT_OUTPUT_ID[nm]][1] == 3 else (n,)
+        # both tables' outputs in ONE zero-filled allocation
+        bufs = self._zeros_like_many([cshape(nm) for nm in c_names] + [mshape(nm) for nm in m_names])
+        cres, cout = self._outputs(OUTPUTS, c_names, cshape, dict(zip(c_names, bufs)))
+        mres, mout = self._outputs(MAT_OUTPUTS, m_names, mshape, dict(zip(m_names, bufs[len(c_names):])))
         self._check(self.lib.rc_render_material(self._h, C.byref(r), n, C.byref(rnd), C.byref(mr), K, C.byref(cout),
-                                                C.byref(mout), stream))
+                                                C.byref(mout), self._stream()))
         self._keep = [held]
         return cres, mres
 
@@ -1533,8 +1371,7 @@ class RadianceCache:
             res[nm] = torch.empty((world * n,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
             lo.ptr[OUTPUT_ID[nm]] = t.data_ptr()
             fu.ptr[OUTPUT_ID[nm]] = res[nm].data_ptr()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_allgather_outputs(self._h, C.c_void_p(nccl_comm), C.byref(lo), n, C.byref(fu), stream))
+        self._check(self.lib.rc_allgather_outputs(self._h, C.c_void_p(nccl_comm), C.byref(lo), n, C.byref(fu), self._stream()))
         self._keep = [local]
         return res
 
@@ -1548,9 +1385,8 @@ class RadianceCache:
         g = self.cfg_grid(grid_id)
         p = self._dev(points).reshape(-1, 3)
         out = torch.empty((p.shape[0], g.out_dim), dtype=torch.float32, device=p.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         self._check(self.lib.rc_hashgrid_lookup(self._h, grid_id, p.data_ptr(), p.shape[0], out.data_ptr(),
-                                                int(apply_contraction), stream))
+                                                int(apply_contraction), self._stream()))
         self._keep = [p]
         return out
 
@@ -1561,9 +1397,8 @@ class RadianceCache:
         n, P = logits.shape
         out = torch.empty((n, num_samples + 1), dtype=torch.float32, device=t.device)
         j = None if jitter is None else self._dev(jitter).reshape(-1)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._check(self.lib.rc_sample_intervals(self._h, t.data_ptr(), logits.data_ptr(), n, P, num_samples,
-                                                 None if j is None else j.data_ptr(), out.data_ptr(), stream))
+        self._check(self.lib.rc_sample_intervals(self._h, t.data_ptr(), logits.data_ptr(), n, P, num_samples, _ptr(j),
+                                                 out.data_ptr(), self._stream()))
         self._keep = [t, logits, j]
         return out
 
