@@ -85,8 +85,7 @@ def render_camera(model, camera: Camera, height: int, width: int, passes=("cache
             rays = cast_ray_batch(model.rc, camera, rect=(0, y0, width, hgt))
             randoms = None
             if rng is not None:
-                apply_key, rng = prng.random_split(rng)
-                rng, _ = prng.random_split(rng)                 # the key render_eval_fn hands back for the next chunk
+                apply_key, rng = prng.chunk_keys(rng)
                 s_key = prng.cache_keys(prng.model_cache_rng(apply_key))["sampler"]
                 jit = []
                 for _ in levels:                                # sampling.py:341 / :408

@@ -10,6 +10,8 @@ Mirrors, for the radiance-cache hot path only:
        around it, engine/trainer.py:821-832)
   * render_image(render_fn, rng, rays, config, passes, ...) -> (rendering, rng)
       models.render_image                     internal/models.py:2361-2525
+      (ONE chunk loop, one mean over repeats and one image sink, for a foreign callable -- host slices in, numpy out
+       per chunk -- and for this package's own render function, whose chunks and results stay on the device)
   * utils.shard / utils.unshard               internal/utils.py:333-343
 
 One process drives one GPU (torch.distributed rank); `n_local_devices` is therefore 1 and the
@@ -28,6 +30,7 @@ Randomness: `rng` may be
 """
 from __future__ import annotations
 
+import contextlib
 import time
 from collections.abc import Mapping
 from typing import Any, Dict, Optional, Tuple
@@ -94,7 +97,7 @@ class RenderDict(Mapping):
     """The `render` dict of one ray batch (keys of _finalize_outputs, internal/models.py:2074-2171) over ONE flat
     device allocation: the kernel writes every output slot into `flat`; a key's tensor ([n, 3], [n, 1] or [n], plus
     `lead` leading axes of size 1) is a view made when the key is read.  Aliases (`cache_<k>`, `ambient_rgb`, ...)
-    share a region, exact constants (`occ`, `vignette`, ...) share one cached tensor per batch size.  The host loop
+    share a region, exact constants (`occ`, `vignette`, ...) share one cached tensor per batch size.  The chunk loop
     of render_image never touches the views: it keeps `flat` per chunk and unpacks the whole image once."""
 
     __slots__ = ("flat", "layout", "consts", "extras", "lead", "_views")
@@ -483,9 +486,7 @@ def create_render_fn(model: Model, dataset: Any = None, mapping_fn: Any = None):
         dev_keys = isinstance(rng, np.ndarray) and rng.dtype == np.uint32 and rng.shape == (1, 2)
         key = rng[0] if dev_keys else rng
         if prng.is_key(key):
-            # render_eval_fn: one split for model.apply, one for the rng handed back (train_utils.py:3794, 3817-3818)
-            apply_key, key = prng.random_split(key)
-            next_key, _ = prng.random_split(key)
+            apply_key, next_key = prng.chunk_keys(key)
             next_rng = next_key[None] if dev_keys else next_key
         else:
             apply_key, next_rng = rng, rng
@@ -527,109 +528,149 @@ _TRANSIENT_KEEP = ("transient_direct_viz", "transient_indirect_viz")
 
 
 def _skip_key(k: str) -> bool:
-    return ("transient" in k) and (k not in _TRANSIENT_KEEP)       # models.py:2459, 2472
+    """`transient*` outputs stay out of an image, the two visualisations excepted."""
+    return ("transient" in k) and (k not in _TRANSIENT_KEEP)
+
+
+class _RepeatMean:
+    """Running (Welford) mean of one chunk's {key: array} over its repeats, numpy arrays or torch tensors alike.
+    `_STAT_KEYS` are averaged, every other key keeps the first repeat's value (a mean of unit normals is not a unit
+    normal) and the first repeat's arrays are never written to.  With `variance`, M2 is kept for `_VAR_KEYS` and comes
+    back as `<key>_variance` = M2 / (n - 1) * n.  One repeat has nothing to average: render_image does not come here
+    for it, and its sink writes the zero variance images."""
+
+    def __init__(self, variance: bool = False):
+        self.n, self.variance, self.mean, self.m2 = 0, variance, {}, {}
+
+    def add(self, cur):
+        self.n += 1
+        if self.n == 1:
+            for k, v in cur.items():
+                tensor = hasattr(v, "clone")
+                self.mean[k] = v if k not in _STAT_KEYS else v.clone() if tensor else v.copy()
+                if self.variance and k in _VAR_KEYS:
+                    self.m2[k] = v.new_zeros(v.shape) if tensor else np.zeros_like(v)
+            return
+        for k, mean in self.mean.items():
+            if k in _STAT_KEYS:
+                delta = cur[k] - mean
+                mean += delta / self.n
+                if k in self.m2:
+                    self.m2[k] += delta * (cur[k] - mean)
+
+    def result(self):
+        out = dict(self.mean)
+        for k, v in self.m2.items():
+            out[f"{k}_variance"] = (v / (self.n - 1)) * self.n if self.n > 1 else v
+        return out
 
 
 def render_image(render_fn, rng, rays: Rays, config, passes: Tuple[str, ...], verbose: bool = True,
                  resample: Any = None, num_repeats: int = 1, compute_variance: bool = False):
-    """models.render_image (internal/models.py:2361-2525): chunked host loop, edge padding,
-    Welford mean over repeats, row-major scatter into [H, W, ...] float32 numpy arrays.
+    """models.render_image: `rays` [H, W, .] are rendered in batches of `config.render_chunk_size` rays, the last one
+    edge-padded to a full chunk, and assembled row-major into {key: [H, W, ...]} numpy arrays of render_fn's dtypes.
+    `render_fn(rng, rays [1, m, .], passes, resample)` -> ({key: [1, 1, m, ...]}, rng); the rng it hands back goes into
+    the next call, the last one is returned.  With `num_repeats` > 1 every chunk is rendered that often and averaged
+    (`_RepeatMean`); `compute_variance` adds `rgb_variance` / `integrated_rgb_variance`, zeros for a single repeat.
+    `transient*` keys but the two visualisations are left out.
 
-    When `render_fn` comes from this module (`render_fn.device` names a GPU) the loop stays on the device: the rays
-    are uploaded once, every chunk is enqueued without a host synchronisation (chunks alternate between two HIP
-    streams so one chunk's gathers overlap the other's matrix work), the per-chunk results stay in HBM, and the
-    image is unpacked and copied to the host ONCE at the end.  Same chunks, same padding, same Welford update,
-    same returned arrays as the host loop (which any other callable gets); aliased keys (`cache_rgb` is `rgb`)
+    A foreign callable gets host slices of the rays, and its results are brought to numpy chunk by chunk.  When
+    `render_fn` comes from this module (`render_fn.device` names a GPU) the same loop stays on the device
+    (`_device_state`): the rays are uploaded once, every chunk is enqueued without a host synchronisation, the results
+    stay in HBM, and the image is unpacked and copied to the host ONCE at the end; aliased keys (`cache_rgb` is `rgb`)
     share one array."""
-    dev = getattr(render_fn, "device", None)
-    if dev is not None:
-        return _render_image_device(render_fn, dev, rng, rays, config, passes, verbose, resample, num_repeats,
-                                    compute_variance)
     height, width = rays.origins.shape[:2]
     num_rays = height * width
-    rays = rays.tree_map(lambda r: np.asarray(r).reshape((num_rays, -1)) if np.size(r) >= num_rays else np.asarray(r))
-    rendering = None
     chunk = config.render_chunk_size
-    idx0s = range(0, num_rays, chunk)
+    n_chunks = -(-num_rays // chunk)
+    padding = n_chunks * chunk - num_rays
+    dev = getattr(render_fn, "device", None)
+    mdl = getattr(render_fn, "model", None) if dev is not None else None
+    sink = _ImageSink(height, width, chunk, compute_variance)
+    join = row = None
+    on_stream = lambda i: contextlib.nullcontext()
     start = time.time()
-    for i_chunk, idx0 in enumerate(idx0s):
-        if verbose and i_chunk % max(1, len(idx0s) // 10) == 0:
-            print(f"Rendering chunk {i_chunk}/{len(idx0s)-1}")
-        chunk_size = min(chunk, num_rays - idx0)
-        chunk_rays = rays.tree_map(lambda r: r[idx0: idx0 + chunk_size])
-        padding = 0
-        if chunk_size % chunk != 0:
-            padding = chunk - (chunk_size % chunk)
-            chunk_rays = chunk_rays.tree_map(lambda r: np.pad(r, ((0, padding), (0, 0)), mode="edge"))
-        chunk_rays = shard(chunk_rays)
-        means: Dict[str, np.ndarray] = {}
-        m2: Dict[str, np.ndarray] = {}
-        for i_repeat in range(num_repeats):
-            cur, rng = render_fn(rng, chunk_rays, passes, resample)
-            cur = {k: np.array(unshard(v[0].cpu().numpy() if hasattr(v, "cpu") else np.asarray(v[0]), padding))
-                   for k, v in cur.items()}
-            if rendering is None:
-                rendering = {}
-                for k, v in cur.items():
-                    if _skip_key(k):
+    if dev is None:
+        flat = rays.tree_map(lambda r: np.asarray(r).reshape((num_rays, -1)) if np.size(r) >= num_rays else np.asarray(r))
+
+        def chunk_rays(i):
+            sub = flat.tree_map(lambda r: r[i * chunk: (i + 1) * chunk])
+            if padding and i == n_chunks - 1:
+                sub = sub.tree_map(lambda r: np.pad(r, ((0, padding), (0, 0)), mode="edge"))
+            return shard(sub)
+
+    def strip(v):                          # [1, 1, m, ...] -> [m, ...]; a foreign callable's results come to the host
+        v = v[0]
+        if dev is None:
+            v = np.array(v.cpu().numpy() if hasattr(v, "cpu") else v)
+        return v.reshape((-1,) + tuple(v.shape[2:]))
+
+    try:
+        if dev is not None:
+            chunk_rays, on_stream, join, row = _device_state(render_fn, mdl, dev, rng, rays, chunk, n_chunks, padding,
+                                                             passes, resample, num_repeats)
+        for i_chunk in range(n_chunks):
+            if verbose and i_chunk % max(1, n_chunks // 10) == 0:
+                print(f"Rendering chunk {i_chunk}/{n_chunks-1}")
+            if row is not None:                                        # already enqueued: only the sink is filled
+                sink.add(row(i_chunk))
+                continue
+            crays = chunk_rays(i_chunk)
+            with on_stream(i_chunk):
+                acc = _RepeatMean(compute_variance) if num_repeats > 1 else None
+                for _ in range(num_repeats):
+                    cur, rng = render_fn(rng, crays, passes, resample)
+                    if acc is None and dev is not None and isinstance(cur, RenderDict):
+                        if mdl is not None:
+                            mdl._variables_checked = True              # the variable tree: on the first chunk only
                         continue
-                    rendering[k] = np.zeros((height, width) + v.shape[1:], dtype=v.dtype)
-                    if compute_variance and k in _VAR_KEYS:
-                        rendering[f"{k}_variance"] = np.zeros_like(rendering[k])
-            for k, v in cur.items():
-                if _skip_key(k):
-                    continue
-                if k not in means:
-                    means[k] = v.copy()
-                    if compute_variance and num_repeats > 1 and k in _VAR_KEYS:
-                        m2[k] = np.zeros_like(v)
-                elif k in _STAT_KEYS:
-                    delta = v - means[k]
-                    means[k] += delta / (i_repeat + 1)
-                    if compute_variance and num_repeats > 1 and k in _VAR_KEYS:
-                        m2[k] += delta * (v - means[k])
-        ind = np.arange(chunk_size)
-        ys, xs = (idx0 + ind) // width, (idx0 + ind) % width
-        for k, v in means.items():
-            rendering[k][ys, xs] = v[:chunk_size]
-            if compute_variance and num_repeats > 1 and k in _VAR_KEYS and k in m2:
-                rendering[f"{k}_variance"][ys, xs] = ((m2[k] / (num_repeats - 1)) * num_repeats)[:chunk_size]
+                    cur = {k: strip(v) for k, v in cur.items() if not _skip_key(k)}
+                    if acc is not None:
+                        acc.add(cur)
+                sink.add(cur if acc is None else acc.result())
+    finally:
+        if mdl is not None:
+            mdl._variables_checked = False
+            mdl._out_arena = None
+    if join is not None:
+        join()
+    rendering = sink.finish(num_rays)
     if verbose:
-        print("Milliseconds per ray", (time.time() - start) * 1000 / (height * width))
+        print("Milliseconds per ray", (time.time() - start) * 1000 / num_rays)
     return rendering, rng
 
 
 class _ImageSink:
-    """Per-chunk results of the device loop -> [H, W, ...] numpy arrays with ONE device-to-host copy.
-
-    Chunks whose `render` is a RenderDict over the same layout are kept as their flat buffers only; the image is
-    assembled on the device (one gather per distinct region) into a key-major buffer that is copied to the host once;
-    aliased keys share a numpy array.  Anything else (plain dicts, Welford means) goes key by key."""
+    """Per-chunk results of render_image -> [H, W, ...] numpy arrays: chunks are contiguous and row-major, so the image
+    is their concatenation, trimmed to `num_rays` once.  RenderDicts over one layout are kept as their flat buffers
+    only; the image is assembled on the device (one gather per distinct region) into a key-major buffer that is copied
+    to the host once; aliased keys share a numpy array.  Anything else (dicts of numpy arrays or tensors, means over
+    repeats with their variances) goes key by key.  With `compute_variance`, a variance image that no chunk brought
+    (a single repeat) is zeros."""
 
     def __init__(self, height, width, chunk, compute_variance):
         self.h, self.w, self.chunk, self.var = height, width, chunk, compute_variance
         self.flats, self.layout, self.consts, self.extras = [], None, None, []
-        self.generic = []                  # per chunk {key: [chunk, ...] tensor}
-        self.keys = None
+        self.generic = []                  # per chunk {key: [chunk, ...] array}
 
-    def add_flat(self, rd: RenderDict):
-        if self.layout is None:
-            self.layout, self.consts = rd.layout, rd.consts
-        if rd.layout is not self.layout or self.generic:
-            return self.add_dict({k: rd[k][0, 0] if rd.lead == 2 else rd[k] for k in rd})
-        self.flats.append(rd.flat)
-        self.extras.append(rd.extras)
-
-    def add_dict(self, d):
-        if self.flats:                     # mixed: fall back to key-by-key for everything
+    def add(self, cur):
+        if isinstance(cur, RenderDict):
+            if self.layout is None:
+                self.layout, self.consts = cur.layout, cur.consts
+            if cur.layout is self.layout and not self.generic:
+                self.flats.append(cur.flat)
+                self.extras.append(cur.extras)
+                return
+            cur = {k: cur[k][0, 0] if cur.lead == 2 else cur[k] for k in cur if not _skip_key(k)}
+        if self.flats:
             raise RuntimeError("render_fn changed its result type between chunks")
-        self.generic.append(d)
+        self.generic.append(cur)
 
     def finish(self, num_rays):
-        import torch
         H, W = self.h, self.w
         out: Dict[str, np.ndarray] = {}
         if self.flats:
+            import torch
             A = torch.stack(self.flats)                                # [n_chunks, flat_size]
             regions, order = {}, []
             for k, ent in self.layout.items():
@@ -669,25 +710,32 @@ class _ImageSink:
             for k, ent in self.layout.items():
                 if not _skip_key(k):
                     out[k] = arrays[ent]
-            return out
-        keys = [k for k in self.generic[0] if not _skip_key(k)] if self.generic else []
-        for k in keys:
-            v = torch.cat([c[k] for c in self.generic])[:num_rays]
-            out[k] = v.cpu().numpy().reshape((H, W) + tuple(v.shape[1:]))
+        for k in (self.generic[0] if self.generic else ()):
+            parts = [c[k] for c in self.generic]
+            if isinstance(parts[0], np.ndarray):
+                v = np.concatenate(parts)[:num_rays]
+            else:
+                import torch
+                v = torch.cat(parts)[:num_rays].cpu().numpy()
+            out[k] = v.reshape((H, W) + tuple(v.shape[1:]))
+        if self.var:
+            for k in _VAR_KEYS:
+                if k in out and f"{k}_variance" not in out:
+                    out[f"{k}_variance"] = np.zeros_like(out[k])
         return out
 
 
-def _render_image_device(render_fn, dev, rng, rays, config, passes, verbose, resample, num_repeats, compute_variance):
-    """The loop of models.render_image (internal/models.py:2412-2514) with everything between the upload of the rays
-    and the final copy of the image kept on GPU `dev`."""
+def _device_state(render_fn, mdl, dev, rng, rays, chunk, n_chunks, padding, passes, resample, num_repeats):
+    """What render_image sets up once when the chunks stay on GPU `dev`: `chunk_rays(i)`, chunk i of the rays uploaded
+    once as [n_chunks, 1, chunk, .] (edge padding and utils.shard done); `on_stream(i)`, the context of the stream
+    chunk i runs on (two streams forked from the current one); `join()`, which makes the current stream wait for them;
+    `row`, None or (direct path) row(i) -> the RenderDict of chunk i after ALL chunks were enqueued here.  For one repeat
+    of this package's own model the chunks write into rows of ONE zero-filled arena made here, on the main stream the
+    pool forks from (no allocation + fill launch per chunk); it is left in `mdl._out_arena`, which the caller resets."""
     import torch
 
-    height, width = rays.origins.shape[:2]
-    num_rays = height * width
     device = torch.device("cuda", dev)
-    chunk = config.render_chunk_size
-    n_chunks = -(-num_rays // chunk)
-    padding = n_chunks * chunk - num_rays
+    num_rays = n_chunks * chunk - padding
 
     def upload(r):
         t = r if isinstance(r, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(r))
@@ -696,106 +744,49 @@ def _render_image_device(render_fn, dev, rng, rays, config, passes, verbose, res
         t = t.to(device).reshape(num_rays, -1)
         if padding:                                                    # np.pad(mode="edge") of the last chunk
             t = torch.cat([t, t[-1:].expand(padding, -1)])
-        return t.reshape(n_chunks, 1, chunk, -1)                       # [chunk index][shard = 1][m][.]: utils.shard done
+        return t.reshape(n_chunks, 1, chunk, -1)
 
-    start = time.time()
     main = torch.cuda.current_stream(device)
     drays = rays.tree_map(upload)
     names = [k for k, v in vars(drays).items() if v is not None and v.dim() == 4]
     cols = {k: getattr(drays, k).unbind(0) for k in names}
     rest = {k: v for k, v in vars(drays).items() if k not in names}
     pool = [torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)] if n_chunks > 1 else [main]
-    # Host time per chunk: the variable tree is checked for updates on the first chunk only, and the chunks write their
-    # outputs into rows of ONE zero-filled arena made here, on the main stream the pool streams fork from (no allocation
-    # + fill launch per chunk)
-    mdl = getattr(render_fn, "model", None)
     arena = None
     if (mdl is not None and num_repeats == 1 and n_chunks > 1 and "material" not in passes
             and getattr(mdl.config, "transient", None) is None and hasattr(mdl, "_plan")):
         total = mdl._plan(chunk, "is_secondary" in passes, "lossmult" in names)[0][0]
         arena = torch.zeros((n_chunks, total), dtype=torch.float32, device=device)
+        mdl._out_arena = (arena, 0)
     ready = torch.cuda.Event()
     ready.record(main)
     for s in pool:
         s.wait_event(ready)
-    sink = _ImageSink(height, width, chunk, compute_variance)
-    var_out: Dict[str, list] = {}
+
+    def join():
+        for s in pool:
+            main.wait_stream(s)
+
     # Direct path for the plain deterministic cache pass of this package's own model (rng None: nothing to thread from
-    # chunk to chunk): exactly the calls render_fn -> render_eval_pfn -> Model.apply would make for the chunk, without
-    # rebuilding a Rays / RenderDict per chunk (host time per chunk 38 -> ~15 us; the results are the same buffers).
-    direct = (arena is not None and rng is None and tuple(passes) == ("cache",) and not resample
-              and getattr(render_fn, "direct_ok", False))
-    try:
-      if arena is not None:
-          mdl._out_arena = (arena, 0)
-      if direct:
-          hot = [k for k in names if k in ("origins", "directions", "viewdirs", "near", "far", "lights", "lossmult")]
-          rc_plan, layout = mdl._plan(chunk, False, "lossmult" in names)
-          mdl._ensure_variables(getattr(render_fn, "variables", None))
-          handles = [s_.cuda_stream for s_ in pool]
-          # the loop over the chunks itself runs in the library (rc_render_chunks: chunk i on stream i % 2, outputs into
-          # row i of the arena); what is left per chunk here is the bookkeeping of the sink
-          full = {k: getattr(drays, k) for k in hot if k != "lossmult"}
-          mdl.rc.render_chunks(full, chunk, n_chunks, rc_ext.RC_PASS_CACHE, rc_plan, arena, handles)
-          for i_chunk in range(n_chunks):
-              if verbose and i_chunk % max(1, n_chunks // 10) == 0:
-                  print(f"Rendering chunk {i_chunk}/{n_chunks-1}")
-              row = arena[i_chunk]
-              extras = (cols["lossmult"][i_chunk][0].reshape(-1, 1).expand(-1, 3),) if "lossmult" in hot else ()
-              sink.add_flat(RenderDict(row, layout, mdl._consts, extras))
-      for i_chunk in range(0 if not direct else n_chunks, n_chunks):
-          if verbose and i_chunk % max(1, n_chunks // 10) == 0:
-              print(f"Rendering chunk {i_chunk}/{n_chunks-1}")
-          chunk_rays = Rays(**rest, **{k: cols[k][i_chunk] for k in names})
-          with torch.cuda.stream(pool[i_chunk % len(pool)]):
-              if num_repeats == 1:
-                  cur, rng = render_fn(rng, chunk_rays, passes, resample)
-                  if isinstance(cur, RenderDict):
-                      sink.add_flat(cur)
-                      if mdl is not None:
-                          mdl._variables_checked = True
-                  else:
-                      sink.add_dict({k: v[0].reshape((-1,) + tuple(v.shape[3:])) for k, v in cur.items()})
-                  continue
-              means: Dict[str, Any] = {}
-              m2: Dict[str, Any] = {}
-              for i_repeat in range(num_repeats):                        # Welford on the device (models.py:2483-2490)
-                  cur, rng = render_fn(rng, chunk_rays, passes, resample)
-                  for k in cur:
-                      if _skip_key(k):
-                          continue
-                      v = cur[k][0].reshape((-1,) + tuple(cur[k].shape[3:]))
-                      if k not in means:
-                          means[k] = v.clone() if k in _STAT_KEYS else v
-                          if compute_variance and k in _VAR_KEYS:
-                              m2[k] = torch.zeros_like(v)
-                      elif k in _STAT_KEYS:
-                          delta = v - means[k]
-                          means[k] += delta / (i_repeat + 1)
-                          if compute_variance and k in _VAR_KEYS:
-                              m2[k] += delta * (v - means[k])
-              sink.add_dict(means)
-              for k, v in m2.items():
-                  var_out.setdefault(k, []).append((v / (num_repeats - 1)) * num_repeats)
-    finally:
-        if mdl is not None:
-            mdl._variables_checked = False
-            mdl._out_arena = None
-    done = [torch.cuda.Event() for _ in pool]
-    for s, e in zip(pool, done):
-        e.record(s)
-        main.wait_event(e)
-    rendering = sink.finish(num_rays)
-    for k, parts in var_out.items():
-        v = torch.cat(parts)[:num_rays]
-        rendering[f"{k}_variance"] = v.cpu().numpy().reshape((height, width) + tuple(v.shape[1:]))
-    if compute_variance and num_repeats == 1:
-        for k in _VAR_KEYS:
-            if k in rendering:
-                rendering[f"{k}_variance"] = np.zeros_like(rendering[k])
-    if verbose:
-        print("Milliseconds per ray", (time.time() - start) * 1000 / (height * width))
-    return rendering, rng
+    # chunk to chunk): the calls render_fn -> render_eval_pfn -> Model.apply would make, looped over the chunks in the
+    # library (rc_render_chunks: chunk i on stream i % 2 into row i of the arena; host time per chunk 38 -> ~15 us)
+    row = None
+    if (arena is not None and rng is None and tuple(passes) == ("cache",) and not resample
+            and getattr(render_fn, "direct_ok", False)):
+        hot = [k for k in names if k in ("origins", "directions", "viewdirs", "near", "far", "lights", "lossmult")]
+        rc_plan, layout = mdl._plan(chunk, False, "lossmult" in names)
+        mdl._ensure_variables(getattr(render_fn, "variables", None))
+        full = {k: getattr(drays, k) for k in hot if k != "lossmult"}
+        mdl.rc.render_chunks(full, chunk, n_chunks, rc_ext.RC_PASS_CACHE, rc_plan, arena, [s.cuda_stream for s in pool])
+        lossmult = cols["lossmult"] if "lossmult" in hot else None
+
+        def row(i):
+            extras = (lossmult[i][0].reshape(-1, 1).expand(-1, 3),) if lossmult is not None else ()
+            return RenderDict(arena[i], layout, mdl._consts, extras)
+
+    chunk_rays = lambda i: Rays(**rest, **{k: cols[k][i] for k in names})
+    on_stream = lambda i: torch.cuda.stream(pool[i % len(pool)])
+    return chunk_rays, on_stream, join, row
 
 
 # ------------------------------------------------------------------------------------------------
@@ -814,14 +805,11 @@ def shard_bounds(num_rays: int, rank: int, world: int) -> Tuple[int, int]:
 def _advance_rng(rng, rank: int, first: bool):
     """Per-chunk random stream of a rank: the key is folded with the rank once (ranks draw different numbers, as the
     per-device keys of the reference's pmap do), then threaded from chunk to chunk like render_image threads the key
-    render_fn hands back (internal/models.py:2445; train_utils.py:3794, 3817-3818).  Returns (key for this chunk,
-    carry for the next one).  Seeds / Generators advance by themselves; dicts of explicit tensors and None pass."""
+    render_fn hands back (prng.chunk_keys).  Returns (key for this chunk, carry for the next one).  Seeds / Generators advance by themselves; dicts of explicit tensors and None pass."""
     if prng.is_key(rng):
         if first:
             rng = prng.fold_in(rng, rank)
-        apply_key, key = prng.random_split(rng)
-        next_key, _ = prng.random_split(key)
-        return apply_key, next_key
+        return prng.chunk_keys(rng)
     if first and isinstance(rng, (int, np.integer)):
         rng = np.random.Generator(np.random.PCG64([int(rng), rank]))
     return rng, rng
@@ -852,9 +840,8 @@ def render_image_distributed(model_apply, rng, rays: Rays, config, passes=("cach
     results on its device, packs the consumed keys into one [rays_per_rank, sum(widths)] buffer and
     issues ONE all_gather per image (the reference all-gathers the whole ~45-key dict per chunk per
     repeat, internal/train_utils.py:3795-3815).  With num_repeats > 1 the repeats of a chunk are averaged on the
-    device BEFORE the gather (running mean, the update of internal/models.py:2483-2490) -- for the
-    reference's stat_keys only (internal/models.py:2398-2401, `_STAT_KEYS`); every other key keeps the first repeat's
-    value, exactly as render_image / _render_image_device do (a mean of unit normals is not a unit normal).
+    device BEFORE the gather, by the `_RepeatMean` of render_image: the mean of the reference's
+    stat_keys (`_STAT_KEYS`), the first repeat of every other key.
 
     model_apply(rng, rays) -> {"render": {key: tensor[n, ...]}}; runs on "nccl" (= RCCL over xGMI)
     with the HIP model and on "gloo" with any CPU callable (tests).  `device`: where a rank with an empty shard
@@ -881,24 +868,19 @@ def render_image_distributed(model_apply, rng, rays: Rays, config, passes=("cach
     chunk = config.render_chunk_size
     buf = None
     first = True
-    stat_cols = None                   # [sum(widths)] bool: columns whose key the reference averages over repeats
     for idx0 in range(lo, hi, chunk):
         sub = flat.tree_map(lambda r: r[idx0: min(idx0 + chunk, hi)])
         m = min(idx0 + chunk, hi) - idx0
-        mean = None
-        for i_repeat in range(num_repeats):
+        acc = _RepeatMean() if num_repeats > 1 else None
+        for _ in range(num_repeats):
             key, rng = _advance_rng(rng, rank, first)
             first = False
             out = model_apply(key, sub)["render"]
-            cur = torch.cat([out[k].reshape(m, -1) for k in keys], dim=1)
-            if mean is None:
-                mean = cur.clone() if num_repeats > 1 else cur
-                continue
-            if stat_cols is None:
-                mask = np.concatenate([np.full(widths[k], k in _STAT_KEYS) for k in keys])
-                stat_cols = torch.from_numpy(mask).to(cur.device)
-            delta = cur - mean                                          # models.py:2485-2486, stat_keys only
-            mean += torch.where(stat_cols, delta / (i_repeat + 1), torch.zeros_like(delta))
+            if acc is not None:
+                acc.add({k: out[k] for k in keys})
+        if acc is not None:
+            out = acc.result()
+        mean = torch.cat([out[k].reshape(m, -1) for k in keys], dim=1)
         if buf is None:
             dev = device or mean.device
             buf = torch.zeros((per, int(cols[-1])), dtype=torch.float32, device=dev)

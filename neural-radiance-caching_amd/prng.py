@@ -103,6 +103,14 @@ def random_split(rng):
     return k[0], k[1]
 
 
+def chunk_keys(key):
+    """Key schedule of one render_image chunk (internal/models.py:2445 -> train_utils.py:3794, 3817-3818): one split
+    for model.apply, one more for the key handed on to the next chunk.  Returns (apply_key, next_key)."""
+    apply_key, key = random_split(key)
+    next_key, _ = random_split(key)
+    return apply_key, next_key
+
+
 def random_bits(key, shape) -> np.ndarray:
     shape = tuple(int(s) for s in np.atleast_1d(shape)) if not isinstance(shape, tuple) else shape
     n = int(np.prod(shape)) if len(shape) else 1

@@ -70,13 +70,19 @@ def test_render_eval_pfn_called_like_the_trainer():
 
 
 def test_device_loop_equals_host_loop():
-    """render_image keeps the chunk loop on the GPU when the render function comes from this package; a plain callable
-    gets the reference's host loop.  Same chunks, same padding, same Welford update: identical images, key by key."""
+    """render_image keeps the chunks on the GPU when the render function comes from this package; a plain callable gets
+    host slices and numpy results.  Same chunks, same padding, same mean over repeats: identical images, key by key,
+    on every branch of the loop."""
     cfg, m = _model(512)
     bound = M.bind_render_fn(M.create_render_fn(m))
-    plain = lambda rng, rays, passes, resample: bound(rng, rays, passes, resample)      # no .device: host loop
-    rays = nrc_amd.synthetic_camera_rays(37, 41)          # 1517 rays: 2 full chunks + 493
-    for repeats, key in ((1, None), (3, prng.PRNGKey(5))):
+    plain = lambda rng, rays, passes, resample: bound(rng, rays, passes, resample)      # no .device: brought to the host
+    cases = (((37, 41), 1, None),                # 1517 rays: 2 full chunks + 493; the direct path (one render_chunks call)
+             ((37, 41), 1, prng.PRNGKey(5)),     # stream pool and arena, chunk by chunk
+             ((37, 41), 3, prng.PRNGKey(5)),     # the mean over repeats
+             ((20, 20), 1, None),                # one padded chunk: no stream pool, no arena
+             ((20, 20), 3, prng.PRNGKey(5)))
+    for shape, repeats, key in cases:
+        rays = nrc_amd.synthetic_camera_rays(*shape)
         a, ra = M.render_image(bound, key, rays, cfg, ("cache",), verbose=False, num_repeats=repeats, compute_variance=True)
         b, rb = M.render_image(plain, key, rays, cfg, ("cache",), verbose=False, num_repeats=repeats, compute_variance=True)
         assert set(a) == set(b)
@@ -87,6 +93,8 @@ def test_device_loop_equals_host_loop():
             else:                                         # the running mean is computed by torch there, numpy here
                 assert np.abs(a[k] - b[k]).max() <= 1e-6, k
         assert (ra is None and rb is None) or np.array_equal(ra, rb)
+        if repeats == 1:
+            assert a["cache_rgb"] is a["rgb"]             # aliased keys share an array
 
 
 def test_pixels_branch_casts_on_the_device():

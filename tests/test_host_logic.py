@@ -101,6 +101,46 @@ def test_render_image_welford_mean_and_variance():
     assert np.allclose(out["distance_median"], rays.far[..., 0])
 
 
+def test_render_image_single_repeat_variance_is_zeros():
+    rays = nrc_amd.synthetic_camera_rays(5, 4)
+    fn, _ = _fake_render_fn([0.25])
+    out, _ = M.render_image(fn, None, rays, _FakeCfg(), ("cache",), verbose=False, num_repeats=1, compute_variance=True)
+    assert out["rgb_variance"].shape == out["rgb"].shape and out["rgb_variance"].dtype == out["rgb"].dtype
+    assert not out["rgb_variance"].any()
+    assert np.allclose(out["rgb"], rays.origins + 0.25)
+
+
+@pytest.mark.parametrize("backend", ["numpy", "torch"])
+def test_repeat_mean_on_numpy_and_torch(backend):
+    """The one running mean of render_image / render_image_distributed, on both array types it is used with."""
+    import torch
+    wrap = (lambda a: a.copy()) if backend == "numpy" else (lambda a: torch.from_numpy(a.copy()))
+    host = lambda a: np.asarray(a)
+    base = np.random.default_rng(0).normal(size=(6, 3)).astype(np.float32)
+    noise = [0.0, 0.3, -0.6, 0.9]
+    reps = [{"rgb": wrap(base + np.float32(e)), "acc": wrap(base[:, 0] * np.float32(1 + e)),
+             "normals": wrap(base * np.float32(1 + e))} for e in noise]
+    first = {k: host(v).copy() for k, v in reps[0].items()}
+    acc = M._RepeatMean(variance=True)
+    for r in reps:
+        acc.add(r)
+    out = acc.result()
+    assert set(out) == {"rgb", "acc", "normals", "rgb_variance"}             # M2 for the variance keys only
+    stack = lambda k: np.stack([host(r[k]) for r in reps]).astype(np.float64)
+    assert np.abs(host(out["rgb"]) - stack("rgb").mean(0)).max() <= 1e-6
+    assert np.abs(host(out["acc"]) - stack("acc").mean(0)).max() <= 1e-6
+    assert np.abs(host(out["rgb_variance"]) - np.var(stack("rgb"), axis=0, ddof=1) * 4).max() <= 1e-5
+    assert np.allclose(host(out["rgb_variance"]), np.var(noise, ddof=1) * 4, atol=1e-5)
+    assert np.array_equal(host(out["normals"]), first["normals"])            # not a stat key: the first repeat
+    for k, v in reps[0].items():                                             # the first repeat's inputs are untouched
+        assert np.array_equal(host(v), first[k]), k
+    assert type(out["rgb"]) is type(reps[0]["rgb"]) and out["rgb"].dtype == reps[0]["rgb"].dtype
+    plain = M._RepeatMean()                                                   # no variance asked for: none kept
+    for r in reps:
+        plain.add(r)
+    assert set(plain.result()) == {"rgb", "acc", "normals"}
+
+
 def test_model_needs_the_hip_library(monkeypatch, tmp_path):
     from nrc_amd import rc_ext
     monkeypatch.setattr(rc_ext, "_LIB", None)

@@ -105,6 +105,41 @@ def test_reference_call_order_of_the_cache_pass():
                           rnd["jitter"][0] * mj)
 
 
+def test_chunk_keys_is_the_two_split_schedule():
+    """prng.chunk_keys: one split for model.apply, one more for the key handed to the next chunk; and its three users
+    in model.py still return what the explicit sequence gives."""
+    from nrc_amd import model as m
+    for key in (prng.PRNGKey(5), prng.PRNGKey(2 ** 32 + 20200823)):
+        apply_key, rest = prng.random_split(key)
+        next_key, _ = prng.random_split(rest)
+        got = prng.chunk_keys(key)
+        assert np.array_equal(got[0], apply_key) and np.array_equal(got[1], next_key)
+        for rank in (0, 1):                                 # _advance_rng: the rank folded in once, on the first chunk
+            a, rest = prng.random_split(prng.fold_in(key, rank))
+            n, _ = prng.random_split(rest)
+            got = m._advance_rng(key, rank, True)
+            assert np.array_equal(got[0], a) and np.array_equal(got[1], n)
+            assert not np.array_equal(got[0], apply_key)
+        got = m._advance_rng(key, 1, False)
+        assert np.array_equal(got[0], apply_key) and np.array_equal(got[1], next_key)
+
+        class _Model:                                       # what create_render_fn reads of a Model
+            device = None
+
+            def apply(self, variables, rng, rays, **kw):
+                self.rng = rng
+                return {"render": {"rgb": np.zeros((4, 3), np.float32)}}
+
+        mdl = _Model()
+        pfn = m.create_render_fn(mdl)
+        _, rng_out = pfn(None, key, 1.0, None, None, None, ("cache",))
+        assert rng_out.shape == (2,) and np.array_equal(rng_out, next_key) and np.array_equal(mdl.rng, apply_key)
+        _, rng_out = pfn(None, key[None], 1.0, None, None, None, ("cache",))
+        assert rng_out.shape == (1, 2) and np.array_equal(rng_out[0], next_key) and np.array_equal(mdl.rng, apply_key)
+        out, rng_out = pfn(None, 7, 1.0, None, None, None, ("cache",))            # not a key: handed through
+        assert rng_out == 7 and mdl.rng == 7 and out["rgb"].shape == (1, 1, 4, 3)
+
+
 def test_light_vmf_noise_is_constant_per_shape():
     a = prng.light_vmf_noise((5, 1, 128, 3))
     b = prng.light_vmf_noise((5, 1, 128, 3))
