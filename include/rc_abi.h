@@ -925,6 +925,60 @@ int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* c
                                const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
                                const rc_transient_data_loss* cfg, float* head_grads, float* losses, void* stream);
 
+/* ---- evaluation of a rendered view -------------------------------------------------------------------
+ * rc_eval_image: what the reference's trainer computes per test view, on images that stay on the device.
+ *   post-process (engine/trainer.py:617-637) of pred and gt alike: with n_bins > 0 the arrays are [H][W][n_bins][3] and
+ *     x = clip(sum over the bins / img_scale, 0, 1), otherwise [H][W][3]; then linear_to_srgb(x * exposure)
+ *     (internal/image_utils.py:192-198, eps = float32's), clipped to [0, 1] only under clip_eval, times mask when given;
+ *   mse, psnr = -10 / ln 10 * ln(mse) (image_utils.py:464; the mean runs over all H W 3 values, masked ones included;
+ *     mse = 0 gives +inf) and ssim = dm_pix.ssim at its defaults (11 taps, sigma 1.5, k1 0.01, k2 0.03, max_val 1; the
+ *     mean of the map over the valid window [H - 10][W - 10][3]) of the two post-processed images;
+ *   transient_iou = sum min(pred, gt) / sum max(pred, gt) over the raw histograms (trainer.py:1633-1636), n_bins > 0 only;
+ *   l1_mean, l1_median = sum |distance - depth_gt| mask / sum mask, plain means without a mask (trainer.py:1766-1779);
+ *   mae: the angle in degrees between normalize(normals_gt + (1 - mask)) and normalize(normals + (1 - acc)), either one
+ *     zero where its norm is below 1e-5, times mask, averaged over ALL pixels (trainer.py:1810-1855).
+ * Every pointer is a device pointer to float32; mask, acc, the distances and depth_gt are [H][W], the normals [H][W][3].
+ * out: DEVICE doubles [RC_EVAL_COUNT], written; a slot whose inputs are NULL is NaN.  Every sum is taken over
+ * per-workgroup partials in a fixed order in double: two calls on the same inputs are bitwise equal.  Optional outputs:
+ * post_pred / post_gt [H][W][3] (the post-processed images), ssim_map [H - 10][W - 10][3].
+ * RC_ERR_INVALID_ARG: NULL images / pred / gt / out, height or width < 11 (no valid window), non-finite or non-positive
+ * img_scale, normals without normals_gt or acc, skip_postprocess with n_bins > 0; RC_ERR_UNSUPPORTED: clip_eval with
+ * n_bins > 0 (the reference's clip_eval post-process does not sum bins).  Everything is ordered on `stream`; no allocation once the workspace has seen the
+ * largest image.  Works on any handle; no weights are needed. */
+typedef enum {
+  RC_EVAL_MSE = 0,
+  RC_EVAL_PSNR,
+  RC_EVAL_SSIM,
+  RC_EVAL_TRANSIENT_IOU,
+  RC_EVAL_L1_MEAN,
+  RC_EVAL_L1_MEDIAN,
+  RC_EVAL_MAE,
+  RC_EVAL_COUNT
+} rc_eval_slot;
+typedef struct {
+  const float* pred;            /* [H][W][3], or [H][W][n_bins][3] with n_bins > 0 */
+  const float* gt;              /* as pred */
+  const float* mask;            /* [H][W] or NULL */
+  const float* acc;             /* [H][W]; needed with normals */
+  const float* normals;         /* [H][W][3] or NULL */
+  const float* normals_gt;      /* [H][W][3]; needed with normals */
+  const float* distance_mean;   /* [H][W] or NULL */
+  const float* distance_median; /* [H][W] or NULL */
+  const float* depth_gt;        /* [H][W] or NULL (no depth errors) */
+  float* post_pred;             /* [H][W][3] written, or NULL */
+  float* post_gt;               /* [H][W][3] written, or NULL */
+  float* ssim_map;              /* [H - 10][W - 10][3] written, or NULL */
+  int32_t height;
+  int32_t width;
+  int32_t n_bins;               /* 0: pred and gt are images */
+  float exposure;               /* Dataset.exposure (1 when the data set has none) */
+  float img_scale;              /* Config.img_scale; read with n_bins > 0 only */
+  int32_t clip_eval;            /* Config.clip_eval */
+  int32_t skip_postprocess;     /* nonzero: pred and gt are compared as they are (image.MetricHarness is called on
+                                   post-processed images); n_bins must be 0, exposure and clip_eval are not read */
+} rc_eval_images;
+int rc_eval_image(rc_handle* h, const rc_eval_images* images, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -689,6 +689,50 @@ struct RcTransBinsBwdArgs {
 void rc_launch_transient_loss(const RcTransLossArgs& a, hipStream_t st);
 void rc_launch_transient_bins_bwd(const RcTransBinsBwdArgs& a, hipStream_t st);
 
+// Evaluation of a rendered view (rc_metrics.hip).  Partial sums are doubles, one slot set per workgroup.
+struct RcEvalBinsArgs {
+  const float* pred, * gt;                                 // [n_pix][n_bins][3]
+  int64_t n_pix; int32_t n_bins;
+  int32_t vec_ok;                                          // both arrays reach a 16-byte boundary after the same number of floats
+  float* binsum_pred, * binsum_gt;                         // [n_pix][3] written
+  double* part;                                            // [rc_eval_bins_blocks(n_pix)][2]: sum of min, sum of max
+};
+struct RcEvalPixelArgs {
+  const float* pred, * gt;                                 // [n_pix][3]: the images, or the bin sums (bins != 0)
+  const float* mask;                                       // [n_pix] or nullptr
+  const float* acc, * normals, * normals_gt;               // [n_pix], [n_pix][3] x 2; all three or none
+  const float* distance_mean, * distance_median, * depth_gt;   // [n_pix] each or nullptr
+  int64_t n_pix;
+  int32_t bins, clip_eval, skip;                           // skip: no post-process, the images as they are (times mask)
+  float exposure, img_scale;
+  float* post_pred, * post_gt;                             // [n_pix][3] written
+  double* part;                                            // [rc_eval_pixel_blocks(n_pix)][rc_eval_pixel_parts()]
+};
+struct RcEvalSsimArgs {
+  const float* a, * b;                                     // [height][width][3]
+  int32_t height, width;
+  float taps[11];                                          // the normalised Gaussian window
+  float c1, c2;
+  float* map;                                              // [height - 10][width - 10][3] or nullptr
+  double* part;                                            // [3][tiles_y][tiles_x]
+};
+struct RcEvalFinishArgs {
+  const double* part_pixels, * part_ssim, * part_bins;
+  int64_t n_part_pixels, n_part_ssim, n_part_bins;         // workgroups of each kernel (0: the kernel did not run)
+  int64_t n_pix;
+  double ssim_count;                                       // (H - 10)(W - 10) 3
+  int32_t masked, have_l1_mean, have_l1_median, have_mae;
+  double* out;                                             // [RC_EVAL_COUNT] device doubles
+};
+int rc_eval_bins_blocks(int64_t n_pix);
+int rc_eval_pixel_blocks(int64_t n_pix);
+int rc_eval_pixel_parts();
+void rc_eval_ssim_tiles(int height, int width, int* ty, int* tx);
+void rc_launch_eval_bins(const RcEvalBinsArgs& a, hipStream_t stream);
+void rc_launch_eval_pixels(const RcEvalPixelArgs& a, hipStream_t stream);
+void rc_launch_eval_ssim(const RcEvalSsimArgs& a, hipStream_t stream);
+void rc_launch_eval_finish(const RcEvalFinishArgs& a, hipStream_t stream);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

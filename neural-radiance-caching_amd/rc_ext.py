@@ -202,6 +202,18 @@ class rc_transient_data_loss(C.Structure):
                 ("use_combined_rawnerf", C.c_int32)]
 
 
+# rc_eval_slot -> name; order must match include/rc_abi.h
+EVAL_SLOTS = ("mse", "psnr", "ssim", "transient_iou", "l1_mean", "l1_median", "mae")
+RC_EVAL_COUNT = len(EVAL_SLOTS)
+_EVAL_INPUTS = ("pred", "gt", "mask", "acc", "normals", "normals_gt", "distance_mean", "distance_median", "depth_gt")
+
+
+class rc_eval_images(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in _EVAL_INPUTS + ("post_pred", "post_gt", "ssim_map")]
+                + [("height", C.c_int32), ("width", C.c_int32), ("n_bins", C.c_int32), ("exposure", C.c_float),
+                   ("img_scale", C.c_float), ("clip_eval", C.c_int32), ("skip_postprocess", C.c_int32)])
+
+
 class rc_adam_buffer(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
                 ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
@@ -280,6 +292,7 @@ _PROTOTYPES = {
                                                 C.POINTER(rc_material_data_loss), _F, _P, _P, _P, _P]),
     "rc_transient_data_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P, C.POINTER(rc_transient_data_loss),
                                              _P, _P, _P]),
+    "rc_eval_image": (C.c_int, [_H, C.POINTER(rc_eval_images), _P, _P]),
 }
 for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the five named layouts
     _PROTOTYPES[_size] = (C.c_int64, [_H])
@@ -1192,6 +1205,60 @@ class RadianceCache:
                                                         _ptr(lm), C.byref(c), _ptr(flat), losses.data_ptr(), stream))
         self._keep = [held]
         return flat, losses
+
+    # -- evaluation of a rendered view ------------------------------------------------------------------
+    def eval_image(self, pred, gt, mask=None, acc=None, normals=None, normals_gt=None, distance_mean=None,
+                   distance_median=None, depth_gt=None, exposure: float = 1.0, img_scale: float = 1.0,
+                   clip_eval: bool = False, skip_postprocess: bool = False, shape=None, keep_images: bool = False, ssim_map: bool = False,
+                   stream_handle=None, sync: bool = True):
+        """rc_eval_image: the reference trainer's per-view metrics of a rendered image against its
+        ground truth, on the device.  pred, gt: [H, W, 3] images or [H, W, n_bins, 3] histograms (cuda tensors are used
+        where they are, numpy arrays are uploaded); mask, acc, distance_mean, distance_median, depth_gt: [H, W] (a
+        trailing 1 is accepted) or None; normals, normals_gt: [H, W, 3] or None.  shape: (H, W) or (H, W, n_bins) where
+        it cannot be read off pred / gt.  Returns {"mse", "psnr", "ssim", "transient_iou", "l1_mean", "l1_median",
+        "mae"} as floats (skip_postprocess: pred and gt are compared as they are, MetricHarness' call; NaN where the inputs of a slot were not given) after ONE copy of the result array to the host;
+        with sync=False the array stays on the device under "result" (float64 [RC_EVAL_COUNT] in EVAL_SLOTS' order) and
+        nothing waits.  keep_images adds "post_pred" / "post_gt" ([H, W, 3] cuda tensors, the post-processed images),
+        ssim_map "ssim_map" ([H - 10, W - 10, 3])."""
+        torch = self._torch
+        held = {k: None if v is None else self._dev(v) for k, v in
+                zip(_EVAL_INPUTS, (pred, gt, mask, acc, normals, normals_gt, distance_mean, distance_median, depth_gt))}
+        if shape is None:
+            lead = held["pred"] if held["pred"] is not None else held["gt"]
+            if lead is None or lead.dim() not in (3, 4) or lead.shape[-1] != 3:
+                raise ValueError("pred / gt must be [H, W, 3] or [H, W, n_bins, 3] (or give shape)")
+            shape = tuple(lead.shape[:-1])
+        H, W = int(shape[0]), int(shape[1])
+        nb = int(shape[2]) if len(shape) > 2 else 0
+        widths = {"pred": 3 * max(nb, 1), "gt": 3 * max(nb, 1), "normals": 3, "normals_gt": 3}
+        im = rc_eval_images(height=H, width=W, n_bins=nb, exposure=float(exposure), img_scale=float(img_scale),
+                            clip_eval=int(bool(clip_eval)), skip_postprocess=int(bool(skip_postprocess)))
+        for k, t in held.items():
+            if t is None:
+                continue
+            if t.numel() != H * W * widths.get(k, 1):
+                raise ValueError(f"{k} holds {t.numel()} values, expected {H * W * widths.get(k, 1)}")
+            setattr(im, k, t.data_ptr())
+        dev = f"cuda:{self.device}"
+        res = {}
+        if H >= 11 and W >= 11:                        # smaller images are refused by the call itself
+            if keep_images:
+                res["post_pred"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+                res["post_gt"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+                im.post_pred, im.post_gt = res["post_pred"].data_ptr(), res["post_gt"].data_ptr()
+            if ssim_map:
+                res["ssim_map"] = torch.empty((H - 10, W - 10, 3), dtype=torch.float32, device=dev)
+                im.ssim_map = res["ssim_map"].data_ptr()
+        out = torch.empty(RC_EVAL_COUNT, dtype=torch.float64, device=dev)
+        self._check(self.lib.rc_eval_image(self._h, C.byref(im), out.data_ptr(), self._stream(stream_handle)))
+        self._keep = [held]
+        if not sync:
+            res["result"] = out
+            return res
+        if stream_handle is not None:                  # a foreign stream: torch's copy below is not ordered behind it
+            torch.cuda.synchronize(self.device)
+        res.update(zip(EVAL_SLOTS, out.cpu().tolist()))                 # the one device-to-host copy
+        return res
 
     # -- material stage -------------------------------------------------------------------------------
     def material_grad_layout(self):
