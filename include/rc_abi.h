@@ -979,6 +979,60 @@ typedef struct {
 } rc_eval_images;
 int rc_eval_image(rc_handle* h, const rc_eval_images* images, double* out, void* stream);
 
+/* ---- evaluation of the albedo ------------------------------------------------------------------------
+ * rc_eval_albedo: Trainer._compute_and_log_albedo_metrics (engine/trainer.py:1499-1567) of one view, on the device.
+ *   per pixel, in fp32: in = mask > 0 (no mask: every pixel, mask value 1); valid = in && acc > 0.5; gt' = in ? gt : 1;
+ *     p = in ? albedo + (1 - acc) : 1.  The valid rows (gt'[3], p[3]) are compacted in pixel order (numpy's a[mask]).
+ *   ratio: the caller's float[3], or (NULL) this view's own per-channel median of gt' / clip(p, 1e-6, 1) over its valid
+ *     rows.  The median is exact: (sorted[(M - 1) / 2] + sorted[M / 2]) / 2 in fp32 for an even M, the middle value for
+ *     an odd one, NaN for M = 0 or when a ratio of the channel is NaN (np.median of float32).
+ *   p = valid ? clip(p ratio, 0, albedo_clip) : p; a = p^(1/2.2), g = gt'^(1/2.2) (powf; a negative base gives NaN);
+ *     mse = mean over all 3 H W values of (a m - g m)^2 with the raw mask value m; psnr = -10 / ln 10 * ln(mse).
+ *   Every clip hands a NaN on, as np.clip does.
+ * out: DEVICE doubles [RC_ALBEDO_COUNT]: mse, psnr, the ratio that was applied, this view's number of valid rows.
+ * Optional outputs: post_pred / post_gt [H][W][3] (a and g), ratio_im [H][W][3] = clip(gt' / p, 0, 1) of the uncorrected p.
+ * pairs: a caller's buffer [pairs_capacity][6] to which this view's valid rows are APPENDED from row *pairs_count on;
+ *   pairs_count is a DEVICE int64 that the call reads and advances by the view's valid rows, and the host never learns it.
+ *   A row at an index >= pairs_capacity is not written but still counted: *pairs_count > pairs_capacity afterwards means
+ *   overflow, and nothing is stored behind the buffer.  The view is scored either way.
+ * rc_albedo_ratio: Trainer._compute_albedo_ratio's ratio (trainer.py:2207-2234) over rows [0, *pairs_count) of such a
+ *   buffer -> ratio, DEVICE float[3].  use_median: the exact median as above.  Otherwise the least squares of the
+ *   reference's block-diagonal lstsq system in closed form, sums in double: with gamma
+ *   (sum p^g gt^g / sum (p^g)^2)^2.2 with g = 1/2.2, without sum p gt / sum p^2.  No rows: NaN.  *pairs_count >
+ *   pairs_capacity (overflow): NaN in all three channels, decided on the device.
+ * Both calls are ordered on `stream`, never synchronise, allocate nothing once the "ea:" workspace has seen the largest
+ * size, use no float atomics (integer counts and double sums in a fixed order: two calls are bitwise equal) and work on
+ * any handle.  RC_ERR_INVALID_ARG, with nothing launched: a NULL required pointer, height or width < 1, H W or a
+ * capacity >= 2^31, a negative capacity, a non-finite albedo_clip, pairs without pairs_count. */
+typedef enum {
+  RC_ALBEDO_MSE = 0,
+  RC_ALBEDO_PSNR,
+  RC_ALBEDO_RATIO_R,
+  RC_ALBEDO_RATIO_G,
+  RC_ALBEDO_RATIO_B,
+  RC_ALBEDO_VALID,              /* this view's valid rows */
+  RC_ALBEDO_COUNT
+} rc_albedo_slot;
+typedef struct {
+  const float* albedo;          /* [H][W][3]: the rendering's albedo_rgb / material_albedo */
+  const float* acc;             /* [H][W] */
+  const float* albedo_gt;       /* [H][W][3] */
+  const float* mask;            /* [H][W] or NULL */
+  int32_t height;
+  int32_t width;
+  float albedo_clip;            /* Trainer.albedo_clip */
+  const float* ratio;           /* DEVICE float[3], or NULL: this view's own median is used */
+  float* post_pred;             /* [H][W][3] written, or NULL */
+  float* post_gt;               /* [H][W][3] written, or NULL */
+  float* ratio_im;              /* [H][W][3] written, or NULL */
+  float* pairs;                 /* [pairs_capacity][6] appended to, or NULL */
+  int64_t pairs_capacity;       /* rows */
+  int64_t* pairs_count;         /* DEVICE int64, read and advanced; required with pairs */
+} rc_albedo_images;
+int rc_eval_albedo(rc_handle* h, const rc_albedo_images* images, double* out, void* stream);
+int rc_albedo_ratio(rc_handle* h, const float* pairs, int64_t pairs_capacity, const int64_t* pairs_count,
+                    int32_t use_median, int32_t gamma, float* ratio, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

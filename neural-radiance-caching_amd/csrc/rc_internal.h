@@ -733,6 +733,47 @@ void rc_launch_eval_pixels(const RcEvalPixelArgs& a, hipStream_t stream);
 void rc_launch_eval_ssim(const RcEvalSsimArgs& a, hipStream_t stream);
 void rc_launch_eval_finish(const RcEvalFinishArgs& a, hipStream_t stream);
 
+// Evaluation of the albedo (rc_albedo.hip).  A pair row is (gt'[3], p[3]); a selection is one order
+// statistic of one channel's ratios: selection 2 c is channel c's lower middle rank, 2 c + 1 its upper one.
+constexpr int kRcAlbedoSelections = 6, kRcAlbedoDigits = 256;
+struct RcAlbedoState {                                     // on the device, the "ea:" set's `state`
+  int64_t base;                                            // the caller's *pairs_count before this view
+  int64_t total;                                           // this view's valid rows
+  int64_t rows;                                            // rows a ratio is taken over (0 on overflow)
+  int32_t overflow;                                        // the count had passed the capacity
+  uint32_t nan[3];                                         // NaN ratios per channel
+  uint32_t prefix[kRcAlbedoSelections], rank[kRcAlbedoSelections];   // key bits fixed so far; rank among the keys that share them
+  float ratio[3];                                          // the result of the select / the least squares
+  uint32_t hist[kRcAlbedoSelections][kRcAlbedoDigits];     // zero between the passes
+};
+struct RcAlbedoPixelArgs {
+  const float* albedo, * acc, * albedo_gt, * mask;         // [n_pix][3], [n_pix], [n_pix][3], [n_pix] or nullptr
+  int64_t n_pix;
+  int32_t* wg;                                             // [blocks]: valid pixels per workgroup, then (scan) those before it
+  RcAlbedoState* state;
+  float* own;                                              // [n_pix][6] the workspace's pair buffer, from row 0, or nullptr
+  float* pairs; int64_t capacity; int64_t* count;          // the caller's pair buffer, appended to, or nullptr
+  const float* ratio;                                      // [3] applied (k_albedo_score)
+  float albedo_clip;
+  float* post_pred, * post_gt, * ratio_im;                 // [n_pix][3] or nullptr
+  double* part;                                            // [blocks]: squared errors
+  double* out;                                             // [RC_ALBEDO_COUNT]
+};
+struct RcAlbedoRatioArgs {
+  const float* pairs; int64_t capacity;
+  const int64_t* count;                                    // device; nullptr: state->total rows (the workspace's buffer)
+  RcAlbedoState* state;
+  int32_t gamma;
+  double* part;                                            // [rc_albedo_row_blocks(capacity)][6]: least squares
+  float* ratio;                                            // [3] written besides state->ratio, or nullptr
+};
+int rc_albedo_pixel_blocks(int64_t n_pix);
+int rc_albedo_row_blocks(int64_t capacity);
+void rc_launch_albedo_compact(const RcAlbedoPixelArgs& a, hipStream_t stream);   // count, scan, write
+void rc_launch_albedo_score(const RcAlbedoPixelArgs& a, hipStream_t stream);     // apply, score, finish
+void rc_launch_albedo_median(const RcAlbedoRatioArgs& a, hipStream_t stream);
+void rc_launch_albedo_lstsq(const RcAlbedoRatioArgs& a, hipStream_t stream);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

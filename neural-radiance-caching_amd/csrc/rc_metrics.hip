@@ -13,37 +13,17 @@
 // tests/eval_metrics_ref.py (-ffp-contract=off keeps multiply and add apart).
 #include <hip/hip_runtime.h>
 
+#include "rc_dev_reduce.h"
 #include "rc_internal.h"
 
 namespace {
 
-constexpr int kEvalThreads = 256;
+constexpr int kEvalThreads = kReduceThreads;
 constexpr float kF32Eps = 1.1920928955078125e-07f;      // np.finfo(np.float32).eps
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;                                 // lane 0 holds the sum
-}
 __device__ __forceinline__ float wave_sum_f(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
-}
-
-// The sums of K values over a workgroup of kEvalThreads threads, in a fixed order: wave sums (shuffles), then the four
-// waves in order by thread 0, which writes them to dst[0..K).
-template <int K>
-__device__ __forceinline__ void block_sums(double (&v)[K], double* lds /* [4][K] */, double* dst) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double s = wave_sum_d(v[k]);
-    if (lane == 0) lds[wave * K + k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) dst[k] = ((lds[k] + lds[K + k]) + lds[2 * K + k]) + lds[3 * K + k];
-  }
 }
 
 // x added to the channel c (0, 1, 2) of s, without a dynamically indexed array
@@ -234,20 +214,6 @@ __global__ void __launch_bounds__(kEvalThreads) k_eval_ssim(RcEvalSsimArgs a) {
   }
   double v[1] = {sum};
   block_sums<1>(v, lds, a.part + ((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
-}
-
-// The sum of n doubles at stride `stride`, by one workgroup in a fixed order: a strided partial per thread, a tree through LDS.
-__device__ double ordered_sum(const double* p, int64_t n, int stride, double* lds) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += kEvalThreads) s += p[i * stride];
-  __syncthreads();                          // the previous sum's lds[0] has been read
-  lds[threadIdx.x] = s;
-  __syncthreads();
-  for (int st = kEvalThreads / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) lds[threadIdx.x] += lds[threadIdx.x + st];
-    __syncthreads();
-  }
-  return lds[0];
 }
 
 __global__ void __launch_bounds__(kEvalThreads) k_eval_finish(RcEvalFinishArgs a) {

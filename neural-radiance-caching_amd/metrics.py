@@ -1,14 +1,16 @@
-"""Evaluation of a rendered view on the device (rc_eval_image).
+"""Evaluation of a rendered view on the device (rc_eval_image; rc_eval_albedo, §4.17).
 
 What the reference's trainer computes per test view -- postprocess_fn (engine/trainer.py:617-637), image.MetricHarness'
 PSNR and SSIM (internal/image_utils.py:411-489), the transient IoU (trainer.py:1633-1636), the depth L1 errors
 (:1766-1779) and the normals' mean angular error (:1810-1855) -- on images that stay in HBM: the only device-to-host
-traffic of a view is the result array.  Not built: LPIPS (a network download), the shift-invariant variants (off in the
-reference's eval config, configs.py:846) and the albedo PSNR.
+traffic of a view is the result array.  The albedo metric (_compute_and_log_albedo_metrics, trainer.py:1499-1582, with
+the test-set ratio of _compute_albedo_ratio, :2202-2240) is scored the same way: its per-channel median and least squares
+run on the device.  Not built: LPIPS (a network download) and the shift-invariant variants (off in the reference's eval
+config, configs.py:846).
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 from . import rc_ext
 
@@ -50,27 +52,80 @@ def _hw(t, n, what):
     return t
 
 
+def _slice_randoms(r, i0, i1, total):
+    """Rows [i0, i1) of every tensor / array of an explicit randoms dict that holds `total` rows (the padded image); what
+    is sized otherwise (a chunk's worth, constants) passes as it is."""
+    if isinstance(r, dict):
+        return {k: _slice_randoms(v, i0, i1, total) for k, v in r.items()}
+    if isinstance(r, (list, tuple)):
+        return type(r)(_slice_randoms(v, i0, i1, total) for v in r)
+    shape = getattr(r, "shape", None)
+    return r[i0:i1] if shape is not None and len(shape) > 0 and shape[0] == total else r
+
+
+def _render_material(model, fields, names, image, n, passes, rng):
+    """The material pass of one view into `image`, chunked as models.render_image chunks it: config.render_chunk_size
+    rays, the last chunk edge-padded to a full one, a key split per chunk by prng.chunk_keys; an explicit randoms dict
+    that covers the padded image is sliced per chunk."""
+    import torch
+
+    from . import prng
+
+    chunk = int(model.config.render_chunk_size)
+    n_chunks = -(-n // chunk)
+    total = n_chunks * chunk
+    if total > n:                                   # np.pad(mode="edge") of the last chunk
+        fields = {k: torch.cat([v, v[-1:].expand(total - n, -1)]) for k, v in fields.items()}
+    for c in range(n_chunks):
+        i0, i1 = c * chunk, (c + 1) * chunk
+        sub = {k: v[i0:i1] for k, v in fields.items()}
+        if prng.is_key(rng):
+            key, rng = prng.chunk_keys(rng)
+        else:
+            key = _slice_randoms(rng, i0, i1, total)
+        render = model.apply(None, key, sub, passes=tuple(passes))["render"]
+        m = min(i1, n) - i0
+        for nm in names:
+            image[nm][i0: i0 + m].view(m, -1).copy_(render[nm].reshape(chunk, -1)[:m])
+
+
 def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cache",), masks=None, depth=None,
                   normals=None, exposure: float = 1.0, img_scale: float = 1.0, clip_eval: bool = False, rng=None,
-                  gt=None) -> Dict[str, float]:
+                  gt=None, albedo=None, albedo_ratio=None, albedo_clip: float = 1.0, albedo_pairs=None) -> Dict[str, float]:
     """Render camera `cam_idx` of a DeviceDataset with `model` (this package's Model) and score it: the rays of
     generate_ray_batch in chunks of config.render_chunk_size that stay on the device, only the outputs the metrics need,
     then rc_eval_image against dataset.images[cam_idx] (or `gt`).  masks, depth: [H, W]; normals: [H, W, 3] ground
     truth, compared with the rendering's "normals" and "acc".  rng: as Model.apply's (None: the deterministic pass).
     On a time-resolved handle the rendering's rgb is [H, W, n_bins, 3] and `gt` of that shape must be given (the data
     set holds [C, H, W, 3] images); "transient_iou" is then filled.  Returns the metrics as floats (NaN where an input
-    was not given) plus "rays_per_sec", the render's rate by device events."""
+    was not given) plus "rays_per_sec", the render's rate by device events.
+
+    passes that contain "material" render the material stage (chunked and keyed as models.render_image does, so the
+    images equal its images for the same rng bit for bit; rng must be a key or the explicit randoms) and score its "rgb",
+    "distance_*", "normals" and "acc".  albedo: [H, W, 3] ground truth; the rendering's "albedo_rgb" (cache pass) or
+    "material_albedo" (material pass) is then scored with rc_eval_albedo and "albedo_mse", "albedo_psnr" and
+    "albedo_ratio" (the 3 floats that were applied) are added.  albedo_ratio: 3 values (tensor or array, as
+    metrics.albedo_ratio returns them) applied instead of this view's own median; albedo_clip: Trainer.albedo_clip;
+    albedo_pairs: an rc_ext.AlbedoPairs to which the view's valid rows are appended."""
     import torch
 
     from .model import _draw_randoms
 
-    if tuple(passes) != ("cache",):
-        raise NotImplementedError("evaluate_view renders the cache pass only")
+    passes = tuple(passes)
+    material = "material" in passes
+    if not material and passes != ("cache",):
+        raise NotImplementedError("evaluate_view renders the cache pass (\"cache\",) or the material pass")
+    if material and rng is None:
+        raise ValueError("the material pass needs randoms: pass rng as a uint32[2] key or as the explicit random tensors")
     rc, cfg = model.rc, model.config
     batch = dataset.generate_ray_batch(cam_idx)
     H, W = dataset.height, dataset.width
     n = H * W
     transient = cfg.transient is not None
+    if transient and material:
+        raise NotImplementedError("a time-resolved handle has no material pass")
+    if transient and albedo is not None:
+        raise NotImplementedError("the albedo metric is not defined on a time-resolved handle")
     if transient and gt is None:
         raise ValueError("a time-resolved handle renders [H, W, n_bins, 3]: pass the ground truth histograms as gt")
     fields = {k: v.reshape(n, -1) for k, v in batch.rays.hot_fields().items() if v is not None and k != "lossmult"}
@@ -81,11 +136,16 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
         names += ["distance_mean", "distance_median"]
     if normals is not None:
         names += ["normals", "acc"]
+    albedo_name = "material_albedo" if material else "albedo_rgb"
+    if albedo is not None:
+        names += [albedo_name] + (["acc"] if "acc" not in names else [])
     dev = f"cuda:{rc.device}"
     table = rc_ext.TRANSIENT_OUTPUTS if transient else rc_ext.OUTPUTS
     ids = rc_ext.TRANSIENT_OUTPUT_ID if transient else rc_ext.OUTPUT_ID
 
     def tail(nm):
+        if nm == "material_albedo":
+            return (3,)
         kind = table[ids[nm]][1]
         return (cfg.transient.n_bins, 3) if kind == "bins" else ((3,) if kind == 3 else ())
 
@@ -93,16 +153,19 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
     chunk = int(cfg.render_chunk_size)
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     start.record()
-    for i0 in range(0, n, chunk):
-        i1 = min(n, i0 + chunk)
-        sub = {k: v[i0:i1] for k, v in fields.items()}
-        randoms, rng = _draw_randoms(rng, i1 - i0, cfg, False)
-        if transient:
-            res = rc.render_transient(sub, randoms, outputs=names)
-            for nm in names:
-                image[nm][i0:i1].copy_(res[nm])
-        else:
-            rc.render_rays(sub, randoms, out={nm: image[nm][i0:i1] for nm in names})
+    if material:
+        _render_material(model, fields, names, image, n, passes, rng)
+    else:
+        for i0 in range(0, n, chunk):
+            i1 = min(n, i0 + chunk)
+            sub = {k: v[i0:i1] for k, v in fields.items()}
+            randoms, rng = _draw_randoms(rng, i1 - i0, cfg, False)
+            if transient:
+                res = rc.render_transient(sub, randoms, outputs=names)
+                for nm in names:
+                    image[nm][i0:i1].copy_(res[nm])
+            else:
+                rc.render_rays(sub, randoms, out={nm: image[nm][i0:i1] for nm in names})
     stop.record()
     truth = batch.rgb if gt is None else rc._dev(gt)
     shape = (H, W, cfg.transient.n_bins) if transient else (H, W)
@@ -114,4 +177,40 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
                         shape=shape)
     ms = start.elapsed_time(stop)               # the result copy above has synchronised
     res["rays_per_sec"] = n / (ms * 1e-3) if ms > 0 else float("inf")
+    if albedo is not None:
+        a = rc.eval_albedo(image[albedo_name], image["acc"], rc._dev(albedo), mask=dv(masks, "masks"), ratio=albedo_ratio,
+                           albedo_clip=albedo_clip, pairs=albedo_pairs, shape=(H, W))
+        res.update(albedo_mse=a["mse"], albedo_psnr=a["psnr"], albedo_ratio=a["ratio"])
     return res
+
+
+def pairs_ratio(rc, pairs, correct_median: bool = False, gamma: bool = True):
+    """rc_albedo_ratio over an AlbedoPairs -> [1, 3] cuda tensor; raises when more rows were appended than the buffer
+    holds (the device then wrote NaN).  Reading the row count for that check is the one readback."""
+    ratio = rc.albedo_ratio(pairs, use_median=correct_median, gamma=gamma)
+    count = int(pairs.count.item())
+    if count > pairs.capacity:
+        raise RuntimeError(f"albedo_ratio: {count} valid rows were appended to a buffer of {pairs.capacity}")
+    return ratio
+
+
+def albedo_ratio(model, dataset, albedos, cams: Optional[Sequence[int]] = None, passes: Tuple[str, ...] = ("cache",),
+                 masks=None, rng=None, correct_median: bool = False, gamma: bool = True):
+    """Trainer._compute_albedo_ratio (engine/trainer.py:2202-2234) on the device: the cameras `cams` (default: every
+    tenth, the reference's loop) are rendered and their valid (ground truth, prediction) albedo rows collected in one
+    AlbedoPairs of len(cams) H W rows; then ONE rc_albedo_ratio call -- the per-channel median (correct_median,
+    Trainer.albedo_correct_median) or the least squares, with Trainer.albedo_gamma.  albedos: [C, H, W, 3] ground truth,
+    masks: [C, H, W] or None, indexed by camera; rng: a key is split per camera.  Returns the [1, 3] cuda tensor that
+    evaluate_view(albedo_ratio=...) takes.  The overflow check is the function's one readback."""
+    from . import prng
+
+    n_cams = int(dataset.images.shape[0])
+    cams = list(range(0, n_cams, 10)) if cams is None else [int(c) for c in cams]
+    pairs = rc_ext.AlbedoPairs(model.rc, len(cams) * dataset.height * dataset.width)
+    for c in cams:
+        key = rng
+        if prng.is_key(rng):
+            key, rng = prng.chunk_keys(rng)
+        evaluate_view(model, dataset, c, passes=passes, masks=None if masks is None else masks[c], rng=key,
+                      albedo=albedos[c], albedo_pairs=pairs)
+    return pairs_ratio(model.rc, pairs, correct_median=correct_median, gamma=gamma)

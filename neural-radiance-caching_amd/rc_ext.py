@@ -214,6 +214,18 @@ class rc_eval_images(C.Structure):
                    ("img_scale", C.c_float), ("clip_eval", C.c_int32), ("skip_postprocess", C.c_int32)])
 
 
+# rc_albedo_slot -> name; order must match include/rc_abi.h
+ALBEDO_SLOTS = ("mse", "psnr", "ratio_r", "ratio_g", "ratio_b", "valid")
+RC_ALBEDO_COUNT = len(ALBEDO_SLOTS)
+
+
+class rc_albedo_images(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("albedo", "acc", "albedo_gt", "mask")]
+                + [("height", C.c_int32), ("width", C.c_int32), ("albedo_clip", C.c_float)]
+                + [(k, C.c_void_p) for k in ("ratio", "post_pred", "post_gt", "ratio_im", "pairs")]
+                + [("pairs_capacity", C.c_int64), ("pairs_count", C.c_void_p)])
+
+
 class rc_adam_buffer(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
                 ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
@@ -293,6 +305,8 @@ _PROTOTYPES = {
     "rc_transient_data_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P, C.POINTER(rc_transient_data_loss),
                                              _P, _P, _P]),
     "rc_eval_image": (C.c_int, [_H, C.POINTER(rc_eval_images), _P, _P]),
+    "rc_eval_albedo": (C.c_int, [_H, C.POINTER(rc_albedo_images), _P, _P]),
+    "rc_albedo_ratio": (C.c_int, [_H, _P, _I64, _P, _I32, _I32, _P, _P]),
 }
 for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the five named layouts
     _PROTOTYPES[_size] = (C.c_int64, [_H])
@@ -1260,6 +1274,66 @@ class RadianceCache:
         res.update(zip(EVAL_SLOTS, out.cpu().tolist()))                 # the one device-to-host copy
         return res
 
+    # -- evaluation of the albedo ------------------------------------------------------------------------
+    def eval_albedo(self, albedo, acc, albedo_gt, mask=None, ratio=None, albedo_clip: float = 1.0, pairs=None,
+                    keep_images: bool = False, shape=None, stream_handle=None, sync: bool = True):
+        """rc_eval_albedo: the reference trainer's albedo metric of one view, on the device.  albedo,
+        albedo_gt: [H, W, 3]; acc, mask: [H, W] (a trailing 1 is accepted; cuda tensors are used where they are, numpy
+        arrays are uploaded); shape: (H, W) where it cannot be read off albedo.  ratio: 3 floats (tensor or array) that
+        are applied, or None: this view's own per-channel median.  pairs: an AlbedoPairs to which the view's valid rows
+        are appended.  Returns {"mse", "psnr", "ratio" (3 floats), "valid"} after ONE copy of the result array to the
+        host; with sync=False the array stays on the device under "result" (float64 [RC_ALBEDO_COUNT] in ALBEDO_SLOTS'
+        order) and nothing waits.  keep_images adds "post_pred" / "post_gt" (the gamma-corrected images) and "ratio_im",
+        [H, W, 3] cuda tensors."""
+        torch = self._torch
+        held = {k: None if v is None else self._dev(v) for k, v in
+                (("albedo", albedo), ("acc", acc), ("albedo_gt", albedo_gt), ("mask", mask), ("ratio", ratio))}
+        if shape is None:
+            lead = held["albedo"] if held["albedo"] is not None else held["albedo_gt"]
+            if lead is None or lead.dim() != 3 or lead.shape[-1] != 3:
+                raise ValueError("albedo / albedo_gt must be [H, W, 3] (or give shape)")
+            shape = tuple(lead.shape[:-1])
+        H, W = int(shape[0]), int(shape[1])
+        im = rc_albedo_images(height=H, width=W, albedo_clip=float(albedo_clip))
+        for k, t in held.items():
+            if t is None:
+                continue
+            want = 3 if k == "ratio" else H * W * (3 if k in ("albedo", "albedo_gt") else 1)
+            if t.numel() != want:
+                raise ValueError(f"{k} holds {t.numel()} values, expected {want}")
+            setattr(im, k, t.data_ptr())
+        if pairs is not None:
+            im.pairs, im.pairs_capacity, im.pairs_count = pairs.buffer.data_ptr(), pairs.capacity, pairs.count.data_ptr()
+        dev = f"cuda:{self.device}"
+        res = {}
+        if keep_images and H >= 1 and W >= 1:
+            for k in ("post_pred", "post_gt", "ratio_im"):
+                res[k] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+                setattr(im, k, res[k].data_ptr())
+        out = torch.empty(RC_ALBEDO_COUNT, dtype=torch.float64, device=dev)
+        self._check(self.lib.rc_eval_albedo(self._h, C.byref(im), out.data_ptr(), self._stream(stream_handle)))
+        self._keep = [held, pairs]
+        if not sync:
+            res["result"] = out
+            return res
+        if stream_handle is not None:                  # a foreign stream: torch's copy below is not ordered behind it
+            torch.cuda.synchronize(self.device)
+        v = out.cpu().tolist()                         # the one device-to-host copy
+        res.update(mse=v[0], psnr=v[1], ratio=v[2:5], valid=int(v[5]))
+        return res
+
+    def albedo_ratio(self, pairs, use_median: bool = False, gamma: bool = True, stream_handle=None):
+        """rc_albedo_ratio: the ratio of the reference's _compute_albedo_ratio over the rows of an AlbedoPairs -- the
+        exact per-channel median, or the least squares (with or without the 1/2.2 gamma).  Returns a [1, 3] cuda tensor,
+        NaN when the pairs overflowed their buffer or hold no row; nothing is read back."""
+        torch = self._torch
+        out = torch.empty((1, 3), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_albedo_ratio(self._h, pairs.buffer.data_ptr(), pairs.capacity, pairs.count.data_ptr(),
+                                             int(bool(use_median)), int(bool(gamma)), out.data_ptr(),
+                                             self._stream(stream_handle)))
+        self._keep = [pairs]
+        return out
+
     # -- material stage -------------------------------------------------------------------------------
     def material_grad_layout(self):
         """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid
@@ -1497,6 +1571,26 @@ class RadianceCache:
         arr = (C.c_float * n)()
         self._check(self.lib.rc_stage_times_ms(self._h, arr, n))
         return {self.lib.rc_stage_name(i).decode(): float(arr[i]) for i in range(n)}
+
+
+class AlbedoPairs:
+    """The pair rows rc_eval_albedo appends to and rc_albedo_ratio reads: `buffer` [capacity, 6] float32 (gt'[3], p[3]
+    per valid pixel) and `count`, the device int64 row count that only the kernels read and advance.  It may pass the
+    capacity: rows behind the buffer are counted, never stored."""
+
+    def __init__(self, rc: "RadianceCache", capacity: int, fill=None):
+        torch = rc._torch
+        dev = f"cuda:{rc.device}"
+        self.capacity = int(capacity)
+        self.buffer = torch.empty((self.capacity, 6), dtype=torch.float32, device=dev)
+        if fill is not None:
+            self.buffer.fill_(fill)
+        self.count = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def rows(self):
+        """(rows stored [min(count, capacity), 6] as numpy, count): a readback, for tests."""
+        n = int(self.count.item())
+        return self.buffer[: max(0, min(n, self.capacity))].cpu().numpy(), n
 
 
 def _memcpy_d2h(dst: int, src: int, nbytes: int):
