@@ -1033,6 +1033,75 @@ int rc_eval_albedo(rc_handle* h, const rc_albedo_images* images, double* out, vo
 int rc_albedo_ratio(rc_handle* h, const float* pairs, int64_t pairs_capacity, const int64_t* pairs_count,
                     int32_t use_median, int32_t gamma, float* ratio, void* stream);
 
+/* ---- visualisation of a rendered view ------------------------------------------------------------------
+ * The reference's vis.visualize_suite / visualize_transient_suite (internal/vis.py:319-743) and utils.save_img_u8
+ * (internal/utils.py:394-400) on images that stay on the device.
+ *
+ * rc_weighted_percentile: vis.weighted_percentile (vis.py:50-58) of `n` values with weights, read in float64 with a STABLE
+ *   sort (ties stay in pixel order), without a sort.  weight NULL: all ones.  ps: n_ps <= 8 HOST doubles (read before
+ *   the call returns); out: DEVICE doubles [n_ps].  With C(v) the weight of the elements
+ *   <= v, W the total weight, t = p (W / 100): v1 is the smallest value with C(v1) > t, or, if there is none, the result
+ *   is the largest value; B = C(< v1); w_f the weight of the first element in pixel order that equals v1; the result is
+ *   v1 if B + w_f <= t or nothing is smaller than v1, otherwise (v1 - v0) / ((B + w_f) - B) * (t - B) + v0 with v0 the
+ *   largest value below v1 whatever its weight -- np.interp's arithmetic, in double.  NaN values sort last (one key), -0
+ *   and +0 are one key.  A negative, NaN or infinite weight: every result is NaN, decided on the device.
+ * rc_image_max: np.max of n floats -> DEVICE float; a NaN is handed on.
+ * rc_vis_images: n_items pictures of one view in one call.  Item i reads src ([H][W][channels], or
+ *   [H][W][n_bins][channels] for the two bin-summing operations) and computes per value, in fp32,
+ *     x = ((src * scale) / divide) / *divisor                  (*divisor: a device float, e.g. an rc_image_max result)
+ *     RC_VIS_SRGB              linear_to_srgb(x)                 (image.linear_to_srgb; a NaN is handed on, as jnp.maximum does)
+ *     RC_VIS_BINSUM_SRGB       the same of x taken from the sum over the bins
+ *     RC_VIS_BINSUM_CLIP_SRGB  linear_to_srgb(clip(x, 0, 1)) of that sum
+ *     RC_VIS_MATTE             (exponent != 1 ? x^exponent : x) + offset + (acc ? 1 - acc : 0)      (vis.matte; plain copies)
+ *     RC_VIS_ABS               |src| scale / divide / *divisor
+ *     RC_VIS_TURBO             vis.visualize_cmap with the depth curve c(x) = -log(x + eps): v = nan_to_num(clip((c(src) -
+ *                              min(c(lo), c(hi))) / |c(hi) - c(lo)|, 0, 1)), colour = turbo[min(trunc(256 v), 255)];
+ *                              (lo, hi) = bounds[0..1], DEVICE doubles rounded to fp32; a bound that is exactly 0 is
+ *                              replaced by auto_bounds[0] - eps / auto_bounds[1] + eps (Python's `lo or ...`) when
+ *                              auto_bounds is given.  channels must be 1.
+ *   then nan_to_num (when set), then 1 where mask is given and not > 0 (the trainer's masking of the depth pictures).
+ *   A one-channel result is broadcast to three.  out_f32 [H][W][3] and / or out_u8 [H][W][3] =
+ *   uint8(rint(clip(nan_to_num(y), 0, 1) * 255)) (round half to even) are written.
+ * rc_vis_turbo_lut: the 256 x 3 table (matplotlib's "turbo", float32) the device uses.
+ * The three device calls are ordered on `stream`, never synchronise, allocate nothing once the "vz:" workspace has seen
+ * the largest size, use no float atomics (integer max / min only; floating sums in a fixed order: two calls are bitwise
+ * equal) and work on any handle.  RC_ERR_INVALID_ARG, with nothing launched: a NULL required pointer, n < 1, height or
+ * width < 1, n or H W >= 2^31, n_ps outside [1, 8], n_items < 1, an item with no output, channels other than 1 or 3,
+ * an unknown operation, n_bins > 0 on an operation that does not sum bins (and < 1 on one that does), RC_VIS_TURBO without
+ * bounds or with three channels. */
+typedef enum {
+  RC_VIS_SRGB = 0,
+  RC_VIS_BINSUM_SRGB,
+  RC_VIS_BINSUM_CLIP_SRGB,
+  RC_VIS_MATTE,
+  RC_VIS_ABS,
+  RC_VIS_TURBO,
+  RC_VIS_OP_COUNT
+} rc_vis_op;
+typedef struct {
+  const float* src;             /* [H][W][channels] or [H][W][n_bins][channels] */
+  int32_t channels;             /* 1 or 3 */
+  int32_t n_bins;               /* > 0 exactly for the bin-summing operations */
+  int32_t op;                   /* rc_vis_op */
+  int32_t nan_to_num;           /* visualize_suite's closing nan_to_num of the float picture */
+  float scale;                  /* multiplied */
+  float divide;                 /* divided by (1: none) */
+  float offset;                 /* RC_VIS_MATTE */
+  float exponent;               /* RC_VIS_MATTE (1: none) */
+  const float* divisor;         /* DEVICE float divided by, or NULL */
+  const float* acc;             /* [H][W] or NULL: RC_VIS_MATTE adds 1 - acc */
+  const float* mask;            /* [H][W] or NULL: the picture is 1 where mask is not > 0 */
+  const double* bounds;         /* DEVICE double[2]: RC_VIS_TURBO's lo, hi */
+  const double* auto_bounds;    /* DEVICE double[2] or NULL: the drawn image's own 0.5 / 99.5 percentiles */
+  float* out_f32;               /* [H][W][3] written, or NULL */
+  uint8_t* out_u8;              /* [H][W][3] written, or NULL */
+} rc_vis_item;
+int rc_weighted_percentile(rc_handle* h, const float* value, const float* weight, int64_t n, const double* ps, int32_t n_ps,
+                           double* out, void* stream);
+int rc_image_max(rc_handle* h, const float* src, int64_t n, float* out, void* stream);
+int rc_vis_images(rc_handle* h, const rc_vis_item* items, int32_t n_items, int32_t height, int32_t width, void* stream);
+int rc_vis_turbo_lut(float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// Host-only check program for the weight packing of rc_pack_host.h: built WITHOUT HIP under
+// Host-only check program for the weight packing of rc_pack_host.h and the item plan of rc_vis_plan.h: built WITHOUT HIP under
 // -fsanitize=address,undefined (`make hostcheck`), driven by tests/test_hostcheck.py, which writes the inputs as raw
 // float32 files, runs this program and compares what it writes with numpy restatements of the same layouts.
 //
@@ -12,12 +12,14 @@
 //   fold      bottleneck [12 -> 16] folded into a consumer [16 + 5 -> 9] with 5 extra rows, row0 = 0
 //   cells     cell table of a dense N = 5 level with F = 2 features (the index rule of k_build_cells)
 //   ide       the directional-encoding coefficient table
+//   vis_plan  rc_vis_images' checks and bin-sum plan on fixed item tables (no input file; tests/test_vis_hostcheck.py)
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <string>
 
 #include "rc_pack_host.h"
+#include "rc_vis_plan.h"
 
 using namespace rcpack;
 
@@ -95,6 +97,47 @@ int main(int argc, char** argv) {
     for (int i = 0; i < RC_IDE_TERMS; ++i) v.push_back((float)tb.m[i]);
     for (int i = 0; i < RC_IDE_TERMS; ++i) v.push_back(tb.sigma[i]);
     write_f32(dir + "/out_ide.bin", v);
+  }
+  {
+    // out_vis_plan.bin: the number of bin sums and the slot of each of the 6 items of a good table, then per faulty
+    // table 1 when it was refused.  The pointers are never followed.
+    float a[4], b[4], c[4];
+    unsigned char o[4];
+    const double bounds[2] = {1.0, 2.0};
+    auto item = [&](const float* src, int channels, int n_bins, int op) {
+      rc_vis_item it{};
+      it.src = src; it.channels = channels; it.n_bins = n_bins; it.op = op; it.scale = it.divide = it.exponent = 1.0f;
+      it.out_u8 = o;
+      return it;
+    };
+    std::vector<rc_vis_item> good = {item(a, 3, 0, RC_VIS_SRGB), item(b, 3, 5, RC_VIS_BINSUM_SRGB), item(c, 3, 5, RC_VIS_BINSUM_SRGB),
+                                     item(b, 3, 5, RC_VIS_BINSUM_CLIP_SRGB), item(b, 1, 15, RC_VIS_BINSUM_SRGB), item(a, 1, 0, RC_VIS_TURBO)};
+    good[5].bounds = bounds;
+    rcvis::Plan plan;
+    std::vector<float> v;
+    if (!rcvis::plan_items(good.data(), (int32_t)good.size(), 7, 9, plan).empty()) return 4;
+    v.push_back((float)plan.sums.size());
+    for (int s : plan.slot) v.push_back((float)s);
+    auto refused = [&](std::vector<rc_vis_item> t, int32_t n, int32_t h, int32_t w) {
+      v.push_back(rcvis::plan_items(n < 0 ? nullptr : t.data(), n < 0 ? 1 : n, h, w, plan).empty() ? 0.0f : 1.0f);
+    };
+    refused(good, -1, 7, 9);                                             // null items
+    refused(good, 0, 7, 9);
+    refused(good, 6, 0, 9);
+    refused(good, 6, 7, -1);
+    refused(good, 6, 1 << 16, 1 << 15);                                  // 2^31 pixels
+    std::vector<rc_vis_item> t;
+    t = good; t[2].src = nullptr; refused(t, 6, 7, 9);
+    t = good; t[0].out_u8 = nullptr; refused(t, 6, 7, 9);                // no output
+    t = good; t[0].channels = 2; refused(t, 6, 7, 9);
+    t = good; t[3].op = RC_VIS_OP_COUNT; refused(t, 6, 7, 9);
+    t = good; t[3].op = -1; refused(t, 6, 7, 9);
+    t = good; t[0].n_bins = 5; refused(t, 6, 7, 9);                      // bins on an operation that does not sum them
+    t = good; t[1].n_bins = 0; refused(t, 6, 7, 9);
+    t = good; t[5].bounds = nullptr; refused(t, 6, 7, 9);
+    t = good; t[5].channels = 3; refused(t, 6, 7, 9);
+    t = good; t[0].out_u8 = nullptr; t[0].out_f32 = a; refused(t, 6, 7, 9);   // fine: 0
+    write_f32(dir + "/out_vis_plan.bin", v);
   }
   printf("hostcheck ok\n");
   return 0;

@@ -774,6 +774,46 @@ void rc_launch_albedo_score(const RcAlbedoPixelArgs& a, hipStream_t stream);    
 void rc_launch_albedo_median(const RcAlbedoRatioArgs& a, hipStream_t stream);
 void rc_launch_albedo_lstsq(const RcAlbedoRatioArgs& a, hipStream_t stream);
 
+// Visualisation of a view (rc_vis.hip).  A selection is one requested percentile of the weighted select.
+constexpr int kRcVisSelections = 8, kRcVisDigits = 256, kRcVisMaxBlocks = 256, kRcVisItemsPerLaunch = 24;
+struct RcVisState {                                        // on the device, the "vz:" set's `state`
+  double total;                                            // W
+  double t[kRcVisSelections];                              // p (W / 100)
+  double below[kRcVisSelections];                          // the weight of the keys under the prefix: B after the last pass
+  uint32_t prefix[kRcVisSelections];                       // key bits fixed so far: v1's key after the last pass
+  int32_t found[kRcVisSelections];                         // some value has C(v) > t
+  uint32_t lower[kRcVisSelections];                        // 1 + the largest key below v1's, 0: none (integer max)
+  uint32_t first[kRcVisSelections];                        // the first element in pixel order with v1's key (integer min)
+  uint32_t max_key;                                        // the largest key (integer max)
+  int32_t bad;                                             // a negative, NaN or infinite weight was seen
+};
+struct RcVisSelectArgs {
+  const float* value, * weight;                            // [n], [n] or nullptr: all ones
+  int64_t n;
+  int32_t n_ps;
+  double ps[kRcVisSelections];
+  RcVisState* state;
+  double* part;                                            // [blocks][n_ps][kRcVisDigits]: weight sums per workgroup
+  double* out;                                             // [n_ps]
+};
+struct RcVisMaxArgs { const float* src; int64_t n; float* part; float* out; };
+struct RcVisBinsArgs { const float* src; int64_t n_pix; int32_t n_bins, channels; float* dst; };   // dst: [n_pix][channels]
+struct RcVisDevItem {
+  const float* src, * divisor, * acc, * mask;
+  const double* bounds, * auto_bounds;
+  float* out_f32; uint8_t* out_u8;
+  int32_t channels, op, nan_to_num;
+  float scale, divide, offset, exponent;
+};
+struct RcVisItemsArgs { RcVisDevItem item[kRcVisItemsPerLaunch]; int64_t n_pix; };
+int rc_vis_select_blocks(int64_t n);
+int rc_vis_max_blocks(int64_t n);
+void rc_launch_vis_select(const RcVisSelectArgs& a, hipStream_t stream);
+void rc_launch_vis_max(const RcVisMaxArgs& a, hipStream_t stream);
+void rc_launch_vis_bins(const RcVisBinsArgs& a, hipStream_t stream);
+void rc_launch_vis_items(const RcVisItemsArgs& a, int n_items, hipStream_t stream);
+const float* rc_vis_turbo_host();
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

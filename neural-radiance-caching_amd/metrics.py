@@ -10,6 +10,7 @@ config, configs.py:846).
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, Optional, Sequence, Tuple
 
 from . import rc_ext
@@ -44,6 +45,13 @@ def postprocess(rc, x, exposure: float = 1.0, img_scale: float = 1.0, clip_eval:
                          sync=False)["post_pred"]
 
 
+# outputs of rc_render_transient that vis.visualize_transient_suite reads (under their names or their cache_ aliases)
+_TRANSIENT_VIS_KEYS = ("rgb", "direct_rgb", "indirect_rgb", "diffuse_rgb", "specular_rgb", "albedo_rgb", "occ", "indirect_occ",
+                       "irradiance_rgb", "light_radiance_rgb", "n_dot_l_rgb", "direct_diffuse_rgb", "direct_specular_rgb",
+                       "indirect_diffuse_rgb", "indirect_specular_rgb", "direct_rgb_viz", "acc", "distance_mean",
+                       "distance_median", "normals", "normals_pred")
+
+
 def _hw(t, n, what):
     if t is None:
         return None
@@ -63,10 +71,11 @@ def _slice_randoms(r, i0, i1, total):
     return r[i0:i1] if shape is not None and len(shape) > 0 and shape[0] == total else r
 
 
-def _render_material(model, fields, names, image, n, passes, rng):
+def _render_material(model, fields, names, image, n, passes, rng, every_key=False):
     """The material pass of one view into `image`, chunked as models.render_image chunks it: config.render_chunk_size
     rays, the last chunk edge-padded to a full one, a key split per chunk by prng.chunk_keys; an explicit randoms dict
-    that covers the padded image is sliced per chunk."""
+    that covers the padded image is sliced per chunk.  every_key: every per-ray tensor of the pass is kept (the
+    visualisation suite), its image made when the first chunk shows its shape."""
     import torch
 
     from . import prng
@@ -85,13 +94,19 @@ def _render_material(model, fields, names, image, n, passes, rng):
             key = _slice_randoms(rng, i0, i1, total)
         render = model.apply(None, key, sub, passes=tuple(passes))["render"]
         m = min(i1, n) - i0
+        if every_key and c == 0:
+            for nm, v in render.items():
+                if nm not in image and torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == chunk and v.dtype == torch.float32:
+                    image[nm] = torch.zeros((n,) + tuple(v.shape[1:]), dtype=torch.float32, device=v.device)
+                    names.append(nm)
         for nm in names:
             image[nm][i0: i0 + m].view(m, -1).copy_(render[nm].reshape(chunk, -1)[:m])
 
 
 def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cache",), masks=None, depth=None,
                   normals=None, exposure: float = 1.0, img_scale: float = 1.0, clip_eval: bool = False, rng=None,
-                  gt=None, albedo=None, albedo_ratio=None, albedo_clip: float = 1.0, albedo_pairs=None) -> Dict[str, float]:
+                  gt=None, albedo=None, albedo_ratio=None, albedo_clip: float = 1.0, albedo_pairs=None,
+                  visualize: bool = False) -> Dict[str, float]:
     """Render camera `cam_idx` of a DeviceDataset with `model` (this package's Model) and score it: the rays of
     generate_ray_batch in chunks of config.render_chunk_size that stay on the device, only the outputs the metrics need,
     then rc_eval_image against dataset.images[cam_idx] (or `gt`).  masks, depth: [H, W]; normals: [H, W, 3] ground
@@ -106,10 +121,16 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
     "material_albedo" (material pass) is then scored with rc_eval_albedo and "albedo_mse", "albedo_psnr" and
     "albedo_ratio" (the 3 floats that were applied) are added.  albedo_ratio: 3 values (tensor or array, as
     metrics.albedo_ratio returns them) applied instead of this view's own median; albedo_clip: Trainer.albedo_clip;
-    albedo_pairs: an rc_ext.AlbedoPairs to which the view's valid rows are appended."""
+    albedo_pairs: an rc_ext.AlbedoPairs to which the view's valid rows are appended.
+
+    visualize: the keys the reference's visualisation suite reads are rendered in the same chunk loop and "vis" is added:
+    vis.visualize_suite (visualize_transient_suite on a time-resolved handle; vis_material with the material pass) of the
+    view as uint8 [H, W, 3] cuda tensors, with `img_scale` as the suite's config.img_scale and the depth pictures masked
+    by `masks`.  The scores do not change."""
     import torch
 
-    from .model import _draw_randoms
+    from . import vis
+    from .model import _CACHE_DEVICE_KEYS, _FINAL_INTEGRATOR_KEYS, _draw_randoms
 
     passes = tuple(passes)
     material = "material" in passes
@@ -139,6 +160,9 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
     albedo_name = "material_albedo" if material else "albedo_rgb"
     if albedo is not None:
         names += [albedo_name] + (["acc"] if "acc" not in names else [])
+    if visualize and not material:
+        wanted = _TRANSIENT_VIS_KEYS if transient else _CACHE_DEVICE_KEYS
+        names += [k for k in wanted if k not in names]
     dev = f"cuda:{rc.device}"
     table = rc_ext.TRANSIENT_OUTPUTS if transient else rc_ext.OUTPUTS
     ids = rc_ext.TRANSIENT_OUTPUT_ID if transient else rc_ext.OUTPUT_ID
@@ -154,7 +178,7 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     start.record()
     if material:
-        _render_material(model, fields, names, image, n, passes, rng)
+        _render_material(model, fields, names, image, n, passes, rng, every_key=visualize)
     else:
         for i0 in range(0, n, chunk):
             i1 = min(n, i0 + chunk)
@@ -170,9 +194,12 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
     truth = batch.rgb if gt is None else rc._dev(gt)
     shape = (H, W, cfg.transient.n_bins) if transient else (H, W)
     dv = lambda x, what: None if x is None else _hw(rc._dev(x), n, what)
-    res = rc.eval_image(image["rgb"], truth, mask=dv(masks, "masks"), acc=image.get("acc"), normals=image.get("normals"),
+    scored = lambda nm, on: image[nm] if on else None          # `visualize` renders more keys than the scores read
+    res = rc.eval_image(image["rgb"], truth, mask=dv(masks, "masks"), acc=scored("acc", normals is not None),
+                        normals=scored("normals", normals is not None),
                         normals_gt=None if normals is None else rc._dev(normals),
-                        distance_mean=image.get("distance_mean"), distance_median=image.get("distance_median"),
+                        distance_mean=scored("distance_mean", depth is not None),
+                        distance_median=scored("distance_median", depth is not None),
                         depth_gt=dv(depth, "depth"), exposure=exposure, img_scale=img_scale, clip_eval=clip_eval,
                         shape=shape)
     ms = start.elapsed_time(stop)               # the result copy above has synchronised
@@ -181,6 +208,20 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
         a = rc.eval_albedo(image[albedo_name], image["acc"], rc._dev(albedo), mask=dv(masks, "masks"), ratio=albedo_ratio,
                            albedo_clip=albedo_clip, pairs=albedo_pairs, shape=(H, W))
         res.update(albedo_mse=a["mse"], albedo_psnr=a["psnr"], albedo_ratio=a["ratio"])
+    if visualize:
+        if material:
+            rendering = dict(image)
+        elif transient:
+            rendering = dict(image)
+            rendering.update({"cache_" + k: image[k] for k in _FINAL_INTEGRATOR_KEYS if k in image})
+            rendering["vignette"] = torch.ones((n, 1), dtype=torch.float32, device=dev)
+            rendering["lossmult"] = torch.ones((n, 3), dtype=torch.float32, device=dev)
+        else:
+            rendering = model._finalize(image, {})
+        rendering = {k: v.reshape((H, W) + tuple(v.shape[1:])) for k, v in rendering.items()}
+        suite = vis.visualize_transient_suite if transient else vis.visualize_suite
+        scales = SimpleNamespace(img_scale=img_scale, var_scale=getattr(cfg, "var_scale", 1.0))
+        res["vis"] = suite(rendering, scales, vis_material=material, masks=dv(masks, "masks"), u8=True, rc=rc)
     return res
 
 

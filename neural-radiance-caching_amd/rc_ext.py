@@ -226,6 +226,19 @@ class rc_albedo_images(C.Structure):
                 + [("pairs_capacity", C.c_int64), ("pairs_count", C.c_void_p)])
 
 
+# rc_vis_op -> name; order must match include/rc_abi.h
+VIS_OPS = ("srgb", "binsum_srgb", "binsum_clip_srgb", "matte", "abs", "turbo")
+VIS_OP_ID = {name: i for i, name in enumerate(VIS_OPS)}
+RC_VIS_MAX_PERCENTILES = 8
+
+
+class rc_vis_item(C.Structure):
+    _fields_ = ([("src", C.c_void_p), ("channels", C.c_int32), ("n_bins", C.c_int32), ("op", C.c_int32),
+                 ("nan_to_num", C.c_int32), ("scale", C.c_float), ("divide", C.c_float), ("offset", C.c_float),
+                 ("exponent", C.c_float)]
+                + [(k, C.c_void_p) for k in ("divisor", "acc", "mask", "bounds", "auto_bounds", "out_f32", "out_u8")])
+
+
 class rc_adam_buffer(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
                 ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
@@ -307,6 +320,10 @@ _PROTOTYPES = {
     "rc_eval_image": (C.c_int, [_H, C.POINTER(rc_eval_images), _P, _P]),
     "rc_eval_albedo": (C.c_int, [_H, C.POINTER(rc_albedo_images), _P, _P]),
     "rc_albedo_ratio": (C.c_int, [_H, _P, _I64, _P, _I32, _I32, _P, _P]),
+    "rc_weighted_percentile": (C.c_int, [_H, _P, _P, _I64, _P, _I32, _P, _P]),
+    "rc_image_max": (C.c_int, [_H, _P, _I64, _P, _P]),
+    "rc_vis_images": (C.c_int, [_H, C.POINTER(rc_vis_item), _I32, _I32, _I32, _P]),
+    "rc_vis_turbo_lut": (C.c_int, [_P]),
 }
 for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the five named layouts
     _PROTOTYPES[_size] = (C.c_int64, [_H])
@@ -1334,6 +1351,84 @@ class RadianceCache:
         self._keep = [pairs]
         return out
 
+    # -- visualisation of a rendered view ------------------------------------------------------------------
+    def weighted_percentile(self, value, weight=None, ps=(0.5, 99.5), stream_handle=None):
+        """rc_weighted_percentile: the reference's vis.weighted_percentile of all values of `value`
+        with the weights `weight` (None: all ones), read in float64 with a stable sort.  ps: at most 8 percentiles.
+        Returns a float64 cuda tensor [len(ps)]; nothing is read back.  A negative, NaN or infinite weight gives NaN."""
+        torch = self._torch
+        held = [self._dev(value), None if weight is None else self._dev(weight)]
+        n = held[0].numel()
+        if held[1] is not None and held[1].numel() != n:
+            raise ValueError(f"weight holds {held[1].numel()} values, expected {n}")
+        ps = [float(p) for p in ps]
+        arr = (C.c_double * max(len(ps), 1))(*ps)
+        out = torch.empty(len(ps), dtype=torch.float64, device=f"cuda:{self.device}")
+        ptr = lambda x: None if x is None else x.data_ptr()
+        self._check(self.lib.rc_weighted_percentile(self._h, ptr(held[0]), ptr(held[1]), n, arr, len(ps),
+                                                    out.data_ptr(), self._stream(stream_handle)))
+        self._keep = [held]
+        return out
+
+    def image_max(self, src, stream_handle=None):
+        """rc_image_max: np.max over every value of `src` as a float32 cuda tensor [1] (a NaN is handed on); nothing is
+        read back."""
+        src = self._dev(src)
+        out = self._torch.empty(1, dtype=self._torch.float32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_image_max(self._h, src.data_ptr(), src.numel(), out.data_ptr(), self._stream(stream_handle)))
+        self._keep = [src]
+        return out
+
+    def vis_images(self, items, height: int, width: int, stream_handle=None):
+        """rc_vis_images: the pictures of one [height, width] view in one call.  items: dicts with "src" ([H, W, c] or, for
+        the bin-summing operations, [H, W, n_bins, c]; c = 1 may be left out) and "op" (a name of VIS_OPS), and optionally
+        n_bins, channels (default: read off src), scale, divide, offset, exponent, divisor (cuda float tensor [1]), acc,
+        mask ([H, W]), bounds / auto_bounds (cuda float64 tensors [2]), nan_to_num, and f32 / u8 (which outputs to write;
+        default u8 only).  Returns one dict per item with "f32" and / or "u8": [H, W, 3] cuda tensors."""
+        torch = self._torch
+        H, W = int(height), int(width)
+        n_pix = H * W
+        dev = f"cuda:{self.device}"
+        table = (rc_vis_item * max(len(items), 1))()
+        held, res = [], []
+        for c_item, it in zip(table, items):
+            unknown = set(it) - {"src", "op", "n_bins", "channels", "scale", "divide", "offset", "exponent", "divisor",
+                                 "acc", "mask", "bounds", "auto_bounds", "nan_to_num", "f32", "u8"}
+            if unknown:
+                raise ValueError(f"vis_images: unknown item fields {sorted(unknown)}")
+            src = self._dev(it["src"])
+            n_bins = int(it.get("n_bins", 0))
+            per_pixel = src.numel() // max(n_pix * max(n_bins, 1), 1)
+            channels = int(it.get("channels", per_pixel))
+            if n_pix < 1 or src.numel() != n_pix * max(n_bins, 1) * channels:
+                raise ValueError(f"vis_images: src holds {src.numel()} values, expected {n_pix} x {max(n_bins, 1)} x {channels}")
+            c_item.src, c_item.channels, c_item.n_bins = src.data_ptr(), channels, n_bins
+            c_item.op, c_item.nan_to_num = VIS_OP_ID[it["op"]], int(bool(it.get("nan_to_num", False)))
+            c_item.scale, c_item.divide = float(it.get("scale", 1.0)), float(it.get("divide", 1.0))
+            c_item.offset, c_item.exponent = float(it.get("offset", 0.0)), float(it.get("exponent", 1.0))
+            keep = [src]
+            for k, dtype, want in (("divisor", torch.float32, 1), ("acc", torch.float32, n_pix), ("mask", torch.float32, n_pix),
+                                   ("bounds", torch.float64, 2), ("auto_bounds", torch.float64, 2)):
+                if it.get(k) is None:
+                    continue
+                t = self._dev(it[k], dtype)
+                if t.numel() != want:
+                    raise ValueError(f"vis_images: {k} holds {t.numel()} values, expected {want}")
+                setattr(c_item, k, t.data_ptr())
+                keep.append(t)
+            out = {}
+            if it.get("f32", False):
+                out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+                c_item.out_f32 = out["f32"].data_ptr()
+            if it.get("u8", not it.get("f32", False)):
+                out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+                c_item.out_u8 = out["u8"].data_ptr()
+            held.append(keep)
+            res.append(out)
+        self._check(self.lib.rc_vis_images(self._h, table, len(items), H, W, self._stream(stream_handle)))
+        self._keep = [held]
+        return res
+
     # -- material stage -------------------------------------------------------------------------------
     def material_grad_layout(self):
         """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid
@@ -1591,6 +1686,15 @@ class AlbedoPairs:
         """(rows stored [min(count, capacity), 6] as numpy, count): a readback, for tests."""
         n = int(self.count.item())
         return self.buffer[: max(0, min(n, self.capacity))].cpu().numpy(), n
+
+
+def vis_turbo_lut():
+    """rc_vis_turbo_lut: the [256, 3] float32 colour table of RC_VIS_TURBO (matplotlib's "turbo")."""
+    out = np.empty((256, 3), np.float32)
+    rc = load_library().rc_vis_turbo_lut(out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise RcError(rc, "rc_vis_turbo_lut")
+    return out
 
 
 def _memcpy_d2h(dst: int, src: int, nbytes: int):
