@@ -288,7 +288,7 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
  * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env,
- * "td:" = rc_transient_data_backward.
+ * "td:" = rc_transient_data_backward, "mk:" = rc_mask_backward.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -331,6 +331,9 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * d the surface light field trunk's output), "d_tint_ibrdf" ([32 n][3]), "d_direct" ([32 n][3] d loss / d direct_rgb),
  * "d_weights" ([32 n] d loss / d the compositing weights).  The forward's own buffers keep their set-0 names ("t_irr",
  * "t_slf", "tshade", "weights2").
+ * "mk:" = rc_mask_backward: the training forward's per-level "sdist", "tdist", "means", "feat", "density", "weights" (the
+ * last level's "weights" written by the loss kernel), "loss_ray" ([n] per-ray terms), "d_density" ([n S]), "points"
+ * ([n S][3]).
  * Returns RC_ERR_INVALID_ARG for an unknown name or a buffer no call has allocated yet.
  * count = number of float32 (or int32) elements of the last request. */
 int rc_workspace_ptr(rc_handle* h, const char* name, void** ptr, int64_t* count);
@@ -662,6 +665,53 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
  * ACCUMULATED into each table's segment of it (layout rc_density_grad_layout(level)); the MLP segments are untouched.
  * Ordered on `stream`; the time-resolved cache handle is unsupported. */
 int rc_density_regularizer(rc_handle* h, int32_t level, float mult, float* density_grads, float* loss, void* stream);
+
+/* Mask loss of the cache stage on the last sampler level's opacity and its exact gradient (train_utils.compute_mask_loss,
+ * internal/train_utils.py:785-836, called at :2919-2927 whenever not config.is_material), with acc = the sum of the
+ * last level's weights (render.py:202):
+ *   loss = mean over the n rays of lossmult * wt * sqrt((acc - m)^2 + charb_padding^2),
+ *   wt   = m > 0.5 ? weight_opaque : weight_empty.
+ * masks: [n] device or NULL (ones: batch.masks is None, :801-804).  The main term takes (weight_opaque, weight_empty) =
+ * (opaque_loss_weight, empty_loss_weight); the backward term (losses["mask_backwards"], :2929-2945) is the
+ * empty_loss_weight= branch (:821-826): zero_masks with weights (0, backward_mask_loss_weight) on the rays of
+ * rc_backward_mask_rays.  The mask-weight decay / ease (:897-932) and (not finetune_cache) are folded into the two
+ * weights by the caller.  sdist carries no gradient (sampling.py:354-355): the loss reaches MLP_<num_levels-1> only.
+ * One call:
+ *   1. the training forward: the sampler levels only, no shader (weights_only=True, models.py:476-486; what
+ *      rc_interlevel_backward's step 1 runs) with the caller's jitter and `anneal`, on a workspace set of its own ("mk:");
+ *   2. the loss (a DEVICE float, written; bitwise reproducible) and d loss / d density of the last level;
+ *   3. only when density_grads is given: rc_density_backward of the last level at the forward's own means, ACCUMULATED
+ *      into density_grads (layout rc_density_grad_layout(num_levels-1)).
+ * cfg: HOST struct.  lossmult: [n] device or NULL (1).  One copy of the term; the reference computes it per output key
+ * ("main" and "cache_main"), the caller scales.  Everything is ordered on `stream`.  The last level must have <= 32
+ * intervals (RC_ERR_UNSUPPORTED otherwise); the time-resolved cache handle is unsupported; charb_padding <= 0 or
+ * non-finite is RC_ERR_UNSUPPORTED before any launch (JAX's gradient is NaN there).  A NULL loss, cfg or rays, or n < 0:
+ * RC_ERR_INVALID_ARG.  n == 0 returns RC_OK and writes nothing.  Buffers: "mk:" names. */
+typedef struct {
+  float charb_padding;   /* Config.charb_padding (1e-3); must be > 0 */
+  float weight_opaque;   /* applied where mask > 0.5 (strict) */
+  float weight_empty;    /* applied elsewhere */
+  int32_t zero_masks;    /* nonzero: masks are all 0 and `masks` is not read (the backward term) */
+} rc_mask_loss;
+int rc_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, const float* lossmult, int64_t n,
+                     const rc_randoms* rnd, float anneal, const rc_mask_loss* cfg, float* density_grads, float* loss,
+                     void* stream);
+
+/* The rays of the backward mask term (train_utils._compute_backward_mask_loss, internal/train_utils.py:3348-3401: its
+ * call of render_utils.get_secondary_rays, render_utils.py:927-1056, with one sample of UniformHemisphereSampler
+ * (:395-403), no MIS and the unstratified RandomGenerator2D(1, 1, False), :322-352), one per batch ray, in fp32:
+ *   normal     = -look
+ *   origin     = (origins + look * shadow_near_max) + normal * normal_eps
+ *   direction  = local_to_global((sin t cos p, sin t sin p, cos t), get_rotation_matrix(normal))   (:145-168),
+ *                cos t = 1 - u1, sin t = sqrt((2 - u1) u1), p = 2 pi u2 - pi;   viewdirs = directions
+ *   near       = shadow_near_max (:3381-3383), far = `far` (Config.secondary_far)
+ * origins, look, u1, u2: device [n,3], [n,3], [n], [n] (u1, u2 in [0, 1): the two columns of one uniform(key, (n, 2))).
+ * out_*: device [n,3], [n,3], [n], [n], the fields rc_rays reads (out_directions serves as viewdirs as well); lossmult
+ * passes through unchanged and radii are not read on this path.  Ordered on `stream`, allocates nothing, any handle.
+ * RC_ERR_INVALID_ARG with nothing launched for a NULL pointer, n < 0 or a non-finite scalar; n == 0 launches nothing. */
+int rc_backward_mask_rays(rc_handle* h, const float* origins, const float* look, const float* u1, const float* u2, int64_t n,
+                          float shadow_near_max, float normal_eps, float far, float* out_origins, float* out_directions,
+                          float* out_near, float* out_far, void* stream);
 
 /* ---- the optimizer step of the cache stage -------------------------------------------------------
  * rc_adam_update: what train_step does with the gradients after pmean (internal/train_utils.py:3154-3161):

@@ -233,6 +233,29 @@ class GeometryLossConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class MaskLossConfig:
+    """Training-time constants of the cache stage's mask loss and its backward term (train_utils.compute_mask_loss,
+    _compute_backward_mask_loss; hotdog)."""
+    charb_padding: float = 1e-3              # Config.charb_padding (internal/configs.py:330)
+    opaque_loss_weight: float = 1.0          # Config.opaque_loss_weight (configs/nerf_ngp_yobo.gin:367)
+    empty_loss_weight: float = 1.0           # Config.empty_loss_weight (nerf_ngp_yobo.gin:368)
+    backward_mask_loss: bool = True          # Config.backward_mask_loss (nerf_ngp_yobo.gin:376)
+    backward_mask_loss_weight: float = 0.1   # Config.backward_mask_loss_weight (nerf_ngp_yobo.gin:375)
+    shadow_near_max: float = 0.2             # Config.shadow_near_max (internal/configs.py:635)
+    secondary_normal_eps: float = 1e-2       # Config.secondary_normal_eps (internal/configs.py:643)
+    secondary_far: float = 2.0               # Config.secondary_far (nerf_ngp_yobo.gin:19)
+    # the mask-weight decay (internal/configs.py:395-398) and ease (:400-403): both off
+    use_mask_weight_decay: bool = False
+    mask_weight_decay_frac: float = 0.0
+    mask_weight_decay_start: float = 0.0
+    mask_weight_decay_min: float = 0.0
+    use_mask_weight_ease: bool = False
+    mask_weight_ease_frac: float = 0.0
+    mask_weight_ease_start: float = 0.0
+    mask_weight_ease_min: float = 0.0
+
+
+@dataclasses.dataclass(frozen=True)
 class LightSamplingConfig:
     """Training-time constants of the light sampler's own loss and its grid regularizer (the material_light_from_scratch
     stage, hotdog)."""

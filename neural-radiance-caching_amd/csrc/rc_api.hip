@@ -135,6 +135,10 @@ struct AlbedoWs { WsBuf pairs, wg, state, part; };
 // (doubles), the per-workgroup maxima and the sums over the bins of the histogram images ([slots][H W][3]).
 struct VisWs { WsBuf state, part, maxpart, binsum; };
 
+// rc_mask_backward, beside its RenderWs (the training forward): the per-ray loss terms, per-sample d loss / d density and
+// the means as points [n S][3].
+struct MaskWs { WsBuf loss_ray, d_density, points; };
+
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
 // serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
@@ -144,15 +148,16 @@ struct VisWs { WsBuf state, part, maxpart, binsum; };
 // WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer,
 // WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY),
 // WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
-// rc_eval_image, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images.
+// rc_eval_image, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
+// WS_MASK rc_mask_backward.
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -174,6 +179,7 @@ struct WsName {
   WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
   WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
   WsBuf EvalWs::*ev = nullptr; WsBuf AlbedoWs::*ea = nullptr; WsBuf VisWs::*vz = nullptr;
+  WsBuf MaskWs::*mk = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -190,6 +196,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf EvalWs::*m) : name(s), ev(m) {}
   constexpr WsName(const char* s, WsBuf AlbedoWs::*m) : name(s), ea(m) {}
   constexpr WsName(const char* s, WsBuf VisWs::*m) : name(s), vz(m) {}
+  constexpr WsName(const char* s, WsBuf MaskWs::*m) : name(s), mk(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -206,7 +213,8 @@ struct WsName {
       if (td) return one(s, td);
       if (ev) return one(s, ev);
       if (ea) return one(s, ea);
-      return vz ? one(s, vz) : nullptr;
+      if (vz) return one(s, vz);
+      return mk ? one(s, mk) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -216,7 +224,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -246,10 +254,11 @@ constexpr WsName kTable[] = {
     WS(TD, ones), WS(TD, d_t_irr), WS(TD, d_t_slf), WS(TD, d_tint_ibrdf), WS(TD, d_direct), WS(TD, d_weights),
     WS(EV, binsum_pred), WS(EV, binsum_gt), WS(EV, post_pred), WS(EV, post_gt), WS(EV, part),
     WS(EA, pairs), WS(EA, wg), WS(EA, state), WS(EA, part),
-    WS(VZ, state), WS(VZ, part), WS(VZ, maxpart), WS(VZ, binsum)};
+    WS(VZ, state), WS(VZ, part), WS(VZ, maxpart), WS(VZ, binsum),
+    WS(MK, loss_ray), WS(MK, d_density), WS(MK, points)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -2031,6 +2040,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_interlevel_host.inc"
 #include "rc_data_host.inc"
 #include "rc_geometry_host.inc"
+#include "rc_mask_host.inc"
 #include "rc_light_host.inc"
 #include "rc_material_bwd_host.inc"
 #include "rc_material_data_host.inc"

@@ -1,11 +1,39 @@
 // The material head's backward, shared by the material network's losses: k_material_smoothness_bwd
-// (rc_material_bwd.hip) and k_material_data_head_bwd (rc_material_data.hip).  Device code only; include after
+// (rc_material_bwd.hip) and k_material_data_head_bwd (rc_material_data.hip), and the shading frame
+// (render_utils.get_rotation_matrix) of rc_material.hip and rc_mask.hip.  Device code only; include after
 // rc_internal.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace {
 
+// Shading frames of the material stage (rc_material.hip) and of the backward mask rays (rc_mask.hip).
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// render_utils.get_rotation_matrix (y_up=False): columns (new_x, new_y, normal)
+struct Frame { V3 x, y, z; };
+__device__ __forceinline__ Frame make_frame(V3 n) {
+  const V3 up = fabsf(n.z) < 0.9f ? V3{0.0f, 0.0f, 1.0f} : V3{0.0f, 1.0f, 0.0f};
+  V3 nx = cross(up, n);
+  float l = sqrtf(dot(nx, nx)) + 1e-10f;
+  nx = {nx.x / l, nx.y / l, nx.z / l};
+  V3 ny = cross(n, nx);
+  l = sqrtf(dot(ny, ny)) + 1e-10f;
+  ny = {ny.x / l, ny.y / l, ny.z / l};
+  return {nx, ny, n};
+}
+// global_to_local: d0 * R[0,:] + d1 * R[1,:] + d2 * R[2,:] with R[i,:] = (x_i, y_i, z_i)
+__device__ __forceinline__ V3 to_local(V3 d, const Frame& f) {
+  return {d.x * f.x.x + d.y * f.x.y + d.z * f.x.z, d.x * f.y.x + d.y * f.y.y + d.z * f.y.z,
+          d.x * f.z.x + d.y * f.z.y + d.z * f.z.z};
+}
+// local_to_global: d0 * R[:,0] + d1 * R[:,1] + d2 * R[:,2]
+__device__ __forceinline__ V3 to_global(V3 d, const Frame& f) {
+  return {d.x * f.x.x + d.y * f.y.x + d.z * f.z.x, d.x * f.x.y + d.y * f.y.y + d.z * f.z.y,
+          d.x * f.x.z + d.y * f.y.z + d.z * f.z.z};
+}
 constexpr int kMsPts = 8;                  // shading points per chunk
 constexpr int kMsE = 2 * kMsPts;           // evaluations per chunk: e = 2 q + s, s = 0 at x, 1 at x'
 constexpr int kMsHid = 128;                // bottleneck width

@@ -563,6 +563,30 @@ int rc_grid_l2_blocks();                   // partial sums per table of rc_launc
 void rc_launch_grid_l2_bwd(const float* x, int64_t count, float gscale, float* grad, double* part, hipStream_t st);
 void rc_launch_grid_l2_reduce(const double* part, const RcGridL2Reduce& r, float* loss, hipStream_t st);
 
+// Mask loss of the last level's opacity and the rays of its backward term (rc_mask.hip)
+struct RcBackwardMaskRaysArgs {
+  int64_t n;
+  const float* origins, * look;            // [n][3] the batch rays' origins and camera look vectors
+  const float* u1, * u2;                   // [n] the uniform pair of each ray, in [0, 1)
+  float shadow_near_max, normal_eps, far;
+  float* o_origins, * o_directions;        // [n][3] written
+  float* o_near, * o_far;                  // [n] written
+};
+struct RcMaskLossArgs {
+  int64_t n; int S;                        // rays, last-level intervals (<= 32)
+  const float* density, * tdist, * directions;   // the training forward's last level
+  float* weights;                          // [n S] the last level's weights, written
+  const float* masks;                      // [n], or nullptr: ones (zeros with zero_masks)
+  const float* lossmult;                   // [n] or nullptr (1)
+  float padding, weight_opaque, weight_empty;
+  int zero_masks;
+  float inv_n;                             // 1 / n: the mean over the rays
+  float* loss_ray;                         // [n] lossmult * wt * charb per ray, written
+  float* d_density;                        // [n S] written
+};
+void rc_launch_backward_mask_rays(const RcBackwardMaskRaysArgs& a, hipStream_t st);
+void rc_launch_mask_loss_bwd(const RcMaskLossArgs& a, hipStream_t st);
+
 // The light sampler's own loss (rc_light.hip)
 struct RcLightLossArgs {
   int64_t n; int Ks, Kd;                   // shading points, secondary samples per suffix

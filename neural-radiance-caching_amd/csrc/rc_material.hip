@@ -16,6 +16,7 @@
 // point, lanes = secondary samples or vMF lobes; the heavy part of the stage is the batched secondary
 // trace, which re-enters the cache kernels (rc_api.hip) on R*K rays.
 #include "rc_internal.h"
+#include "rc_dev_material.h"     // sigmoidf, V3 / Frame: get_rotation_matrix, global_to_local, local_to_global
 
 namespace {
 
@@ -32,35 +33,8 @@ __device__ __forceinline__ float wmax(float v) {
   for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
   return v;
 }
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float softplusf(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-// render_utils.get_rotation_matrix (y_up=False): columns (new_x, new_y, normal)
-struct Frame { V3 x, y, z; };
-__device__ __forceinline__ Frame make_frame(V3 n) {
-  const V3 up = fabsf(n.z) < 0.9f ? V3{0.0f, 0.0f, 1.0f} : V3{0.0f, 1.0f, 0.0f};
-  V3 nx = cross(up, n);
-  float l = sqrtf(dot(nx, nx)) + 1e-10f;
-  nx = {nx.x / l, nx.y / l, nx.z / l};
-  V3 ny = cross(n, nx);
-  l = sqrtf(dot(ny, ny)) + 1e-10f;
-  ny = {ny.x / l, ny.y / l, ny.z / l};
-  return {nx, ny, n};
-}
-// global_to_local: d0 * R[0,:] + d1 * R[1,:] + d2 * R[2,:] with R[i,:] = (x_i, y_i, z_i)
-__device__ __forceinline__ V3 to_local(V3 d, const Frame& f) {
-  return {d.x * f.x.x + d.y * f.x.y + d.z * f.x.z, d.x * f.y.x + d.y * f.y.y + d.z * f.y.z,
-          d.x * f.z.x + d.y * f.z.y + d.z * f.z.z};
-}
-// local_to_global: d0 * R[:,0] + d1 * R[:,1] + d2 * R[:,2]
-__device__ __forceinline__ V3 to_global(V3 d, const Frame& f) {
-  return {d.x * f.x.x + d.y * f.y.x + d.z * f.z.x, d.x * f.x.y + d.y * f.y.y + d.z * f.z.y,
-          d.x * f.x.z + d.y * f.y.z + d.z * f.z.z};
-}
 __device__ __forceinline__ V3 ir_normalize(V3 v) {           // inverse_render/math.normalize
   const float l = sqrtf(1e-10f + dot(v, v));
   return {v.x / l, v.y / l, v.z / l};

@@ -44,8 +44,6 @@ __device__ __forceinline__ float wsum(float v) {
   for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
   return v;
 }
-struct V3 { float x, y, z; };
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ V3 ir_normalize(V3 v) {
   const float l = sqrtf(1e-10f + dot(v, v));
   return {v.x / l, v.y / l, v.z / l};

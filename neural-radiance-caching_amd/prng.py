@@ -372,3 +372,30 @@ def material_smoothness_noise(loss_key, n_points: int) -> np.ndarray:
     _, key = random_split(key)      # :2541
     rng, _ = random_split(key)      # :2566
     return normal(rng, (int(n_points), 3))
+
+
+def backward_mask_keys(cur_key):
+    """The two keys _compute_backward_mask_loss (internal/train_utils.py:3348-3401) takes from the key per_output_loss_fn
+    hands it: (key of the uniform pair, rng of the weights-only model.apply on the backward rays).  :3363 random.split ->
+    get_secondary_rays' random_split (render_utils.py:965) -> importance_sample_rays' split for its one sampler (:767)
+    -> RandomGenerator2D.sample's split (:324); then :3385 random.split for model.apply.  Like every key path of this
+    module the call order is restated from the source and is not pinned against a jax run (no jax here)."""
+    k = split(as_key(cur_key))            # train_utils.py:3363
+    rng, cur = k[0], k[1]
+    key, _ = random_split(rng)            # render_utils.py:965
+    ka, _ = random_split(key)             # :767
+    ku, _ = random_split(ka)              # :324
+    k_apply = split(cur)[0]               # train_utils.py:3385
+    return ku, k_apply
+
+
+def backward_mask_randoms(cur_key, n_rays: int, num_samples: Sequence[int], rc=None) -> Dict[str, object]:
+    """The draws of the backward mask term for n_rays batch rays: "u1", "u2" = the two columns of uniform(key, (n, 2))
+    (RandomGenerator2D(1, 1, False) is not stratified: uh, uw of render_utils.py:325-327) and "jitter" = the per-level
+    sampler jitter of the weights-only pass on the backward rays (cache_pass_randoms of its model rng).  With `rc` the
+    pair is generated on the device by one rc_prng_fill (bit-equal to the host's); otherwise on the host.  Unpinned
+    against jax, as backward_mask_keys says."""
+    ku, k_apply = backward_mask_keys(cur_key)
+    u = rc.prng_fill(ku, (int(n_rays), 2)) if rc is not None else uniform(ku, (int(n_rays), 2))
+    u1, u2 = (u[:, 0].contiguous(), u[:, 1].contiguous()) if rc is not None else (np.ascontiguousarray(u[:, 0]), np.ascontiguousarray(u[:, 1]))
+    return {"u1": u1, "u2": u2, "jitter": cache_pass_randoms(k_apply, n_rays, num_samples)["jitter"]}

@@ -173,6 +173,11 @@ class rc_geometry_loss(C.Structure):
                                          "pred_normal_mult", "pred_normal_w_grad_weight", "pred_normal_reverse_mult")]
 
 
+class rc_mask_loss(C.Structure):
+    _fields_ = [("charb_padding", C.c_float), ("weight_opaque", C.c_float), ("weight_empty", C.c_float),
+                ("zero_masks", C.c_int32)]
+
+
 RC_ADAM_MAX_GROUPS = 8
 RC_LAYOUT_SHADER = -1
 RC_LAYOUT_LIGHT = -2
@@ -303,6 +308,8 @@ _PROTOTYPES = {
     "rc_data_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _F, _F, _F, _P, _P, _P, _P]),
     "rc_geometry_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, C.POINTER(rc_geometry_loss), _P, _P, _P, _P]),
     "rc_density_regularizer": (C.c_int, [_H, _I32, _F, _P, _P, _P]),
+    "rc_mask_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _F, C.POINTER(rc_mask_loss), _P, _P, _P]),
+    "rc_backward_mask_rays": (C.c_int, [_H, _P, _P, _P, _P, _I64, _F, _F, _F, _P, _P, _P, _P, _P]),
     "rc_adam_update": (C.c_int, [_H, C.POINTER(rc_adam_buffer), _I32, C.POINTER(rc_adam_step), _P]),
     "rc_load_params_flat": (C.c_int, [_H, _I32, _P, _P]),
     "rc_light_sampling_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _MRND, _I32, C.POINTER(rc_light_sampling_loss),
@@ -952,6 +959,60 @@ class RadianceCache:
         mult * x / numel into (allocated zeroed when None); grad=False computes the loss only.
         Returns (grad flat or None, loss [1] cuda tensor)."""
         return self._regularizer(self.lib.rc_density_regularizer, level, (int(level), float(mult)), grad)
+
+    def backward_mask_rays(self, origins, look, u1, u2, shadow_near_max: float = 0.2, normal_eps: float = 1e-2,
+                           far: float = 2.0):
+        """rc_backward_mask_rays: the rays of the backward mask term (train_utils._compute_backward_mask_loss), one per
+        batch ray from origins [n, 3] and the camera look vectors look [n, 3]; u1, u2: [n] uniforms in [0, 1) (the two
+        columns of prng.backward_mask_randoms' draw).  Returns the ray dict mask_backward takes: origins, directions, viewdirs
+        (the directions' own tensor), near, far -- cuda tensors, written on the current stream."""
+        torch = self._torch
+        o = self._dev(origins).reshape(-1, 3).contiguous()
+        n = o.shape[0]
+        lk = self._dev(look).reshape(-1, 3).contiguous()
+        a, b = self._dev(u1).reshape(-1).contiguous(), self._dev(u2).reshape(-1).contiguous()
+        if lk.shape[0] != n or a.shape[0] != n or b.shape[0] != n:
+            raise ValueError("origins, look, u1 and u2 must have one row per ray")
+        dev = f"cuda:{self.device}"
+        out = {"origins": torch.empty(n, 3, dtype=torch.float32, device=dev),
+               "directions": torch.empty(n, 3, dtype=torch.float32, device=dev),
+               "near": torch.empty(n, dtype=torch.float32, device=dev), "far": torch.empty(n, dtype=torch.float32, device=dev)}
+        self._check(self.lib.rc_backward_mask_rays(self._h, o.data_ptr(), lk.data_ptr(), a.data_ptr(), b.data_ptr(), n,
+                                                   float(shadow_near_max), float(normal_eps), float(far),
+                                                   out["origins"].data_ptr(), out["directions"].data_ptr(),
+                                                   out["near"].data_ptr(), out["far"].data_ptr(), self._stream()))
+        self._keep = [o, lk, a, b]
+        out["viewdirs"] = out["directions"]
+        return out
+
+    def mask_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, masks=None, lossmult=None,
+                      terms=None, grads=None):
+        """rc_mask_backward: the mask loss of the last sampler level's opacity (train_utils.compute_mask_loss) and its
+        gradient w.r.t. the last density level (density_grad_layout(num_levels - 1)).  masks: [n] or None (ones);
+        terms: {rc_mask_loss field: value} (weights with the ease / decay applied; charb_padding defaults to 1e-3, the
+        weights to 1, zero_masks to 0).  jitters / anneal / lossmult as data_backward.  grads: the density flat to
+        accumulate into, None (allocated zeroed) or False (the loss only).
+        Returns (density flat or None, loss [1] cuda tensor); one copy of the term."""
+        r, held, n = self._rays_struct(rays)
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
+        mk = None
+        if masks is not None:
+            mk = self._dev(masks).reshape(-1)
+            if mk.shape[0] != n:
+                raise ValueError("masks must have one value per ray")
+            held["masks"] = mk
+        t = {"charb_padding": 1e-3, "weight_opaque": 1.0, "weight_empty": 1.0, "zero_masks": 0}
+        t.update(terms or {})
+        unknown = set(t) - {k for k, _ in rc_mask_loss._fields_}
+        if unknown:
+            raise ValueError(f"unknown mask loss fields {sorted(unknown)}")
+        cfg = rc_mask_loss(float(t["charb_padding"]), float(t["weight_opaque"]), float(t["weight_empty"]), int(bool(t["zero_masks"])))
+        flat, loss, stream = self._loss_prologue(self.cfg.num_levels - 1, grads)
+        self._check(self.lib.rc_mask_backward(self._h, C.byref(r), _ptr(mk), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg),
+                                              _ptr(flat), loss.data_ptr(), stream))
+        self._keep = [held]
+        return flat, loss
 
     def light_grad_layout(self):
         """rc_light_grad_layout: [(tensor name, offset, shape)] of the LightSampler gradient buffer (the light_grid tables,

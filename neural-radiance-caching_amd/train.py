@@ -24,10 +24,15 @@ model followed by `jax.lax.pmean(grad, "batch")` across devices and the optimize
     predicted-normal losses of the last sampler level (loss_utils.py:108-201) and their exact gradients of MLP_2 and
     pred_normals_layer, in one device call (rc_geometry_backward: training forward, per-ray loss backward, density
     backward); `normal_weight_ease(train_frac)` -> the ease the predicted-normal terms are scaled by;
+  * `mask_grads(rc, rays, jitters, train_frac, masks, ...)` -> the mask loss of the last level's opacity
+    (train_utils.compute_mask_loss) and, given the cameras' look vectors and the backward rays' draws, its backward term
+    (train_utils._compute_backward_mask_loss: rc_backward_mask_rays, then the same loss with zero masks), with their
+    exact gradients of MLP_2 (rc_mask_backward: sampler-only training forward, per-ray loss backward, density
+    backward); `mask_terms(train_frac)` -> the weights with the mask-weight decay / ease folded in;
   * `cache_stage_grads(rc, rays, rgb, jitters, train_frac)` -> the cache-stage loss: interlevel, data and geometry
     terms counted for "main" and "cache_main", the density-grid regularizer once, with the per-level and shader
     gradients and a loss dict keyed like the reference's losses_flat (the light / material grid regularizer keys left
-    out, see its docstring).
+    out, see its docstring); with mask_cfg the two mask terms as well.
 
 These terms are all first order here (the analytic normals are stop-gradiented where they appear).  The
 predicted-normal terms follow that first-order reading; whether it matches the reference is not settled (DESIGN.md,
@@ -82,8 +87,8 @@ from typing import Dict, Iterable, List, Optional
 import numpy as np
 
 from . import prng
-from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaterialDataLossConfig,
-                     MaterialSmoothnessConfig, OptimizerConfig, TransientDataLossConfig)
+from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaskLossConfig,
+                     MaterialDataLossConfig, MaterialSmoothnessConfig, OptimizerConfig, TransientDataLossConfig)
 
 
 def grads_as_dict(flat, layout) -> Dict[str, object]:
@@ -198,15 +203,9 @@ def data_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, flats=N
 
 
 def normal_weight_ease(train_frac: float, cfg: GeometryLossConfig = GeometryLossConfig()) -> float:
-    """train_utils.compute_weight_ease_in (internal/train_utils.py:839-867) with the normal-weight settings: 1 when the
-    schedule is off; min (1 - w) + w, w = clip((train_frac - start) / frac, 0, 1), for frac > 0; else the step
-    float(train_frac >= start)."""
-    if not cfg.use_normal_weight_ease:
-        return 1.0
-    if cfg.normal_weight_ease_frac > 0:
-        w = min(max((float(train_frac) - cfg.normal_weight_ease_start) / cfg.normal_weight_ease_frac, 0.0), 1.0)
-        return cfg.normal_weight_ease_min * (1.0 - w) + w
-    return float(float(train_frac) >= cfg.normal_weight_ease_start)
+    """weight_ease_in (train_utils.compute_weight_ease_in) with the normal-weight settings."""
+    return weight_ease_in(train_frac, cfg.use_normal_weight_ease, cfg.normal_weight_ease_start, cfg.normal_weight_ease_frac,
+                          cfg.normal_weight_ease_min)
 
 
 def geometry_terms(train_frac: float, cfg: GeometryLossConfig = GeometryLossConfig(), scale: float = 1.0):
@@ -238,21 +237,93 @@ def geometry_grads(rc, rays, jitters, train_frac: float, lossmult=None, flats=No
     return grads, list(flats), losses
 
 
+def weight_ease_in(train_frac: float, use: bool, start: float, frac: float, min_value: float = 0.0) -> float:
+    """train_utils.compute_weight_ease_in (internal/train_utils.py:839-867): 1 when the schedule is off;
+    min (1 - w) + w, w = clip((train_frac - start) / frac, 0, 1), for frac > 0; else the step float(train_frac >= start)."""
+    if not use:
+        return 1.0
+    if frac > 0:
+        w = min(max((float(train_frac) - start) / frac, 0.0), 1.0)
+        return min_value * (1.0 - w) + w
+    return float(float(train_frac) >= start)
+
+
+def weight_decay(train_frac: float, use: bool, start: float, frac: float, min_value: float = 0.0) -> float:
+    """train_utils.compute_weight_decay (internal/train_utils.py:870-894): 1 when the schedule is off; else
+    min w + (1 - w), w = clip((train_frac - start) / frac, 0, 1) (frac = 0 divides by zero there as well)."""
+    if not use:
+        return 1.0
+    w = min(max((float(train_frac) - start) / frac, 0.0), 1.0)
+    return min_value * w + (1.0 - w)
+
+
+def mask_terms(train_frac: float, cfg: MaskLossConfig = MaskLossConfig(), scale: float = 1.0):
+    """The rc_mask_loss fields of one copy of the two mask terms at train_frac: {"mask": ..., "mask_backwards": ...}.
+    _compute_mask_weight_decay and _compute_mask_weight_ease (train_utils.py:897-932) multiply the Charbonnier value
+    before the weights do (:815-832), so they are folded into the weights; the backward term is the empty_loss_weight=
+    branch (:821-826): (0, backward_mask_loss_weight) on zero masks.  scale multiplies every weight."""
+    sched = (weight_decay(train_frac, cfg.use_mask_weight_decay, cfg.mask_weight_decay_start, cfg.mask_weight_decay_frac,
+                          cfg.mask_weight_decay_min)
+             * weight_ease_in(train_frac, cfg.use_mask_weight_ease, cfg.mask_weight_ease_start, cfg.mask_weight_ease_frac,
+                              cfg.mask_weight_ease_min)) * scale
+    return {"mask": dict(charb_padding=cfg.charb_padding, weight_opaque=cfg.opaque_loss_weight * sched,
+                         weight_empty=cfg.empty_loss_weight * sched, zero_masks=0),
+            "mask_backwards": dict(charb_padding=cfg.charb_padding, weight_opaque=0.0,
+                                   weight_empty=cfg.backward_mask_loss_weight * sched, zero_masks=1)}
+
+
+MASK_KEYS = ("mask", "mask_backwards")
+
+
+def mask_grads(rc, rays, jitters, train_frac: float, masks=None, lossmult=None, flat=None, look=None, backward_randoms=None,
+               cfg: MaskLossConfig = MaskLossConfig(), anneal_cfg: InterlevelConfig = InterlevelConfig(), scale: float = 1.0):
+    """The mask loss of a batch, its backward term and their gradients (rc_mask_backward, rc_backward_mask_rays).
+    jitters / train_frac / lossmult as data_grads; masks: [n] or None (ones); flat: the last level's density flat to
+    accumulate into (allocated zeroed when None).  The backward term runs when cfg.backward_mask_loss is set and both
+    look ([n, 3] camera look vectors) and backward_randoms ({"u1", "u2": [n], "jitter": per-level [n]} of the backward
+    rays, prng.backward_mask_randoms) are given: its rays start shadow_near_max in front of the camera, carry the batch
+    rays' lossmult and zero masks.  scale multiplies both terms (cache_stage_grads passes 2).
+    -> ({"MLP_<last>": {name: view}}, flat, {"mask": 0-d tensor, "mask_backwards": 0-d tensor}); a term that did not
+    run is left out of the dict."""
+    terms = mask_terms(train_frac, cfg, scale)
+    anneal = anneal_at(train_frac, anneal_cfg)
+    flat, loss = rc.mask_backward(rays, jitters, anneal, masks, lossmult, terms["mask"], flat)
+    losses = {"mask": loss[0]}
+    if cfg.backward_mask_loss and look is not None and backward_randoms is not None:
+        back = rc.backward_mask_rays(rays["origins"], look, backward_randoms["u1"], backward_randoms["u2"],
+                                     cfg.shadow_near_max, cfg.secondary_normal_eps, cfg.secondary_far)
+        flat, loss = rc.mask_backward(back, backward_randoms.get("jitter"), anneal, None, lossmult, terms["mask_backwards"], flat)
+        losses["mask_backwards"] = loss[0]
+    last = rc.cfg.num_levels - 1
+    return {f"MLP_{last}": grads_as_dict(flat, rc.density_grad_layout(last)[0])}, flat, losses
+
+
 def cache_stage_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, flats=None,
                       geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
-                      interlevel_cfg: InterlevelConfig = InterlevelConfig()):
-    """The hotdog cache stage's whole loss on a batch and its gradients (train_utils.py:3000-3098).  The interlevel,
+                      interlevel_cfg: InterlevelConfig = InterlevelConfig(), mask_cfg: Optional[MaskLossConfig] = None,
+                      masks=None, look=None, backward_randoms=None):
+    """The hotdog cache stage's loss on a batch and its gradients (train_utils.py:3000-3098).  The interlevel,
     data and geometry terms are computed for "main" and "cache_main" on the same model results, so each counts twice
     (the device calls run once with their mults doubled; the dict reports each copy); the density-grid regularizer
     (param_regularizer_loss) counts once, over the three proposal grids.
     flats: {level: density flat, "shader": shader flat} to accumulate into (allocated zeroed when None).
     -> (flats, losses): losses maps the reference's losses_flat keys (interlevel_<l>, distortion, orientation,
     predicted_normals, predicted_normals_reverse, data, their cache_main_* copies, regularizer/density_grid) to
-    0-d cuda tensors.  The reference's losses_flat also carries regularizer/light_grid and regularizer/material_grid
-    (param_regularizer_loss starts its dict with every prefix of Config.param_regularizers, train_utils.py:1183): they
-    regularize parameters outside the cache stage's density and shader layouts and are not computed here, so the sum
-    of these values is stats["loss"] without those two keys.  The predicted-normal terms follow the first-order
-    reading of the module docstring."""
+    0-d cuda tensors.
+    mask_cfg (None: the mask terms are left out and the result is what it was without them): the mask loss on `masks`
+    ([n] or None: ones) and, with look and backward_randoms (mask_grads), its backward term, added to flats[last] and to
+    the dict as mask, mask_backwards and their cache_main_* copies.  per_output_loss_fn computes both whenever not
+    config.is_material (train_utils.py:2919-2945), and the cache stage's loop over the output keys (:2998-3024:
+    model.use_material is False) leaves is_material False for "main" and for "cache_main"; "mask" is in the exclude_list
+    (:3058-3060), so neither copy is scaled by loss_weight.  They therefore count twice like the other terms: the device
+    calls run once with doubled weights.  For the backward term that is a reading, not an identity: the reference draws
+    the backward rays of each output key from that key's own rng (:3036), so its two copies are two samples of the same
+    expectation, where this function counts one sample twice.
+    What the sum of the dict is: with the mask terms, the reference's stats["loss"] (:3098) except for
+    regularizer/light_grid and regularizer/material_grid (param_regularizer_loss starts its dict with every prefix of
+    Config.param_regularizers, :1183; they regularize parameters outside the cache stage's layouts and are not computed
+    here) and up to that one-sample reading; without mask_cfg it also lacks the four mask keys.  The predicted-normal
+    terms follow the first-order reading of the module docstring."""
     nl = rc.cfg.num_levels
     flats = dict(flats or {})
     il_cfg = dataclasses.replace(interlevel_cfg, mults=tuple(2.0 * m for m in interlevel_cfg.mults))
@@ -280,6 +351,12 @@ def cache_stage_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, 
     losses = dict(main)
     losses.update({f"cache_main_{k}": v for k, v in main.items()})
     losses["regularizer/density_grid"] = reg[0]
+    if mask_cfg is not None:
+        _, flats[nl - 1], m_losses = mask_grads(rc, rays, jitters, train_frac, masks, lossmult, flats[nl - 1], look,
+                                                backward_randoms, mask_cfg, interlevel_cfg, scale=2.0)
+        for k in MASK_KEYS:
+            if k in m_losses:
+                losses[k] = losses[f"cache_main_{k}"] = m_losses[k] / 2
     return flats, losses
 
 
@@ -444,22 +521,29 @@ def _train_step(opt: CacheStageOptimizer, group, grads):
 
 def cache_stage_step(rc, opt: CacheStageOptimizer, rays, rgb, jitters, lossmult=None, group=None,
                      geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
-                     interlevel_cfg: InterlevelConfig = InterlevelConfig()):
+                     interlevel_cfg: InterlevelConfig = InterlevelConfig(), mask_cfg: Optional[MaskLossConfig] = None,
+                     masks=None, look=None, backward_randoms=None):
     """One train step of the cache stage (train_utils.py:3128-3161): train_frac from opt.count
     (trainer.py:2116-2126), cache_stage_grads into the optimizer's zeroed gradient buffers, the pmean over `group`
     when torch.distributed runs (allreduce_grads), then opt.step() (nan_to_num, clip_gradients, the Adams, the handle's
-    refresh).  -> the losses dict of cache_stage_grads (the local batch's values)."""
+    refresh).  mask_cfg / masks / look / backward_randoms: the mask terms, as cache_stage_grads takes them.
+    -> the losses dict of cache_stage_grads (the local batch's values)."""
     return _train_step(opt, group, lambda tf: cache_stage_grads(rc, rays, rgb, jitters, tf, lossmult, dict(opt.grads),
-                                                                geometry_cfg, data_cfg, interlevel_cfg))
+                                                                geometry_cfg, data_cfg, interlevel_cfg, mask_cfg, masks,
+                                                                look, backward_randoms))
 
 
 def cache_stage_fit(rc, opt: CacheStageOptimizer, dataset, key, steps: int, group=None,
                     geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
-                    interlevel_cfg: InterlevelConfig = InterlevelConfig()):
+                    interlevel_cfg: InterlevelConfig = InterlevelConfig(), mask_cfg: Optional[MaskLossConfig] = None,
+                    masks_of=None):
     """`steps` train steps of the cache stage fed by a data.DeviceDataset, from one PRNG key.  Per step: key, rng =
     random_split(rng); dataset.next_train (one launch: cameras, pixels, rays, colours); one more split per proposal level
-    for its per-ray jitter, drawn in HBM (rc.prng_fill); cache_stage_step.  The host handles keys and scalars only: no
-    tensor crosses PCIe inside the loop and nothing is read back.  -> the steps' loss dicts (0-d cuda tensors)."""
+    for its per-ray jitter, drawn in HBM (rc.prng_fill); cache_stage_step.  With mask_cfg the mask terms run as well:
+    the batch's masks are the caller's (masks_of(batch) -> [n] cuda tensor or None for ones; the batch kernel does not
+    write masks), the backward rays start from the batch's look vectors, and their uniform pair and per-level jitter
+    are drawn in HBM from further splits of the step's jitter key.  The host handles keys and scalars only: no tensor
+    crosses PCIe inside the loop and nothing is read back.  -> the steps' loss dicts (0-d cuda tensors)."""
     rng = prng.as_key(key)
     n = dataset.batch_size
     history = []
@@ -471,8 +555,19 @@ def cache_stage_fit(rc, opt: CacheStageOptimizer, dataset, key, steps: int, grou
         for _ in range(rc.cfg.num_levels):
             k, jitter_key = prng.random_split(jitter_key)
             jitters.append(rc.prng_fill(k, (n, 1), "uniform"))
+        masks = look = back = None
+        if mask_cfg is not None:
+            masks = masks_of(batch) if masks_of is not None else None
+            if mask_cfg.backward_mask_loss:
+                look = batch.rays.look
+                k, jitter_key = prng.random_split(jitter_key)
+                u = rc.prng_fill(k, (n, 2), "uniform")
+                back = {"u1": u[:, 0].contiguous(), "u2": u[:, 1].contiguous(), "jitter": []}
+                for _ in range(rc.cfg.num_levels):
+                    k, jitter_key = prng.random_split(jitter_key)
+                    back["jitter"].append(rc.prng_fill(k, (n, 1), "uniform"))
         history.append(cache_stage_step(rc, opt, batch.rays.hot_fields(), batch.rgb, jitters, batch.rays.lossmult, group,
-                                        geometry_cfg, data_cfg, interlevel_cfg))
+                                        geometry_cfg, data_cfg, interlevel_cfg, mask_cfg, masks, look, back))
     return history
 
 
