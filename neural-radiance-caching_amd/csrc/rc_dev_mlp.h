@@ -215,13 +215,42 @@ __device__ __forceinline__ float ws_read(const WDirect& w, int f) { return w.g[(
 template <int NF, int W = kWaves, int CH = kChunk>
 __device__ __forceinline__ u32x4 ws_read4(const WDirect& w, int f) { return *reinterpret_cast<const u32x4*>(w.g + (size_t)f * 64 + w.lane * 4); }
 
+// Where a layer's B operand comes from: bf(s) is this lane's value of k-step s, s a compile-time constant once the
+// layer's loops are unrolled.
+//  BAct   the lane's activation column in LDS (act[s * 64] is step s): values that cross lanes on their way to the
+//         layer -- grid features, IDE terms, the (n.v | 1) step -- and the level-2 hidden feature.
+//  BHand  the accumulators of the layer before, handed over in registers.  The K-permutation of the packed weights
+//         makes the parked layout the accumulator layout: step 16 t + r of lane L is relu(acc[t][r]) of the SAME lane,
+//         so a layer-to-layer hand-off through LDS is a spill and a fill of a register the lane already holds.
+//         BIAS: step 16 NT is the bias step (1 on the low half-wave, 0 on the high one).
+struct BAct {
+  const float* act;
+  __device__ __forceinline__ float operator()(int s) const { return act[s * 64]; }
+};
+template <int NT, bool BIAS>
+struct BHand {
+  float v[NT * 16];
+  float one;
+  __device__ __forceinline__ float operator()(int s) const { return s < NT * 16 ? v[s < NT * 16 ? s : 0] : one; }
+};
+// PT point-tiles: tile p's column starts at act + p * tile_stride / tile p's hand-over is hand[p]
+struct BActPt {
+  const float* act; int tile_stride;
+  __device__ __forceinline__ float operator()(int p, int s) const { return act[p * tile_stride + s * 64]; }
+};
+template <int PT, int NT, bool BIAS>
+struct BHandPt {
+  BHand<NT, BIAS> hand[PT];
+  __device__ __forceinline__ float operator()(int p, int s) const { return hand[p](s); }
+};
+
 // One pass over KS k-steps for NT output tiles; the layer's fragments are [FBASE, FBASE + KS*NT)
-// of the stream.  act: this lane's activation column (act[s * 64] is step s).
+// of the stream.  bf: the B operand's source (above).
 // Software pipelined in groups of SG k-steps: the LDS reads (A fragments + B activations) of group
 // g+1 are issued before the MFMAs of group g, with scheduling fences so they stay there; the MFMA
 // pipe then runs back to back while the next operands are in flight.
-template <int NT, int KS, int FBASE, int NF, int SG, int W, int CH, class WS>
-__device__ __forceinline__ void mlp_layer_f32(const WS& w, const float* act, f32x16 (&acc)[NT]) {
+template <int NT, int KS, int FBASE, int NF, int SG, int W, int CH, class WS, class BF>
+__device__ __forceinline__ void mlp_layer_f32(const WS& w, const BF& bf, f32x16 (&acc)[NT]) {
   constexpr int NG = (KS + SG - 1) / SG;
   float a[3][SG][NT], b[3][SG];
   auto load = [&](int g, int buf) {
@@ -229,7 +258,7 @@ __device__ __forceinline__ void mlp_layer_f32(const WS& w, const float* act, f32
     for (int d = 0; d < SG; ++d) {
       const int s = g * SG + d;
       if (s < KS) {
-        b[buf][d] = act[s * 64];
+        b[buf][d] = bf(s);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int f = FBASE + s * NT + t;            // compile-time after unrolling
@@ -281,8 +310,10 @@ __device__ __forceinline__ void split_blocks(const float* act, u32x4 (&pre)[NBP]
 #pragma unroll
   for (int q = 0; q < NBP; ++q) split8(v[q], pre[q]);
 }
-template <int NT, int KS, int FBASE, int NF, int W, int CH, int NBP, bool BIAS1, class WS>
-__device__ __forceinline__ void mlp_layer_split(const WS& w, const float* act, f32x16 (&acc)[NT], const u32x4 (*pre)[3]) {
+// Blocks that are neither ready nor the bias block take their 8 values from bf (BAct: an LDS read; BHand: registers,
+// the split then being all that is left of the hand-off), at the same places in the cell loop either way.
+template <int NT, int KS, int FBASE, int NF, int W, int CH, int NBP, bool BIAS1, class WS, class BF>
+__device__ __forceinline__ void mlp_layer_split(const WS& w, const BF& bf, f32x16 (&acc)[NT], const u32x4 (*pre)[3]) {
   static_assert(FBASE % 4 == 0, "split layers start on a 1-KiB piece");
   constexpr int NB = (KS + 7) / 8, NC = NB * NT;
   static_assert(NBP <= NB, "no more ready blocks than blocks");
@@ -294,7 +325,7 @@ __device__ __forceinline__ void mlp_layer_split(const WS& w, const float* act, f
   auto from_act = [](int q) { return q < NB && q >= NBP && !(BIAS1 && q == NB - 1); };
   auto load_b = [&](int q) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) bv[j] = (8 * q + j < KS) ? act[(8 * q + j) * 64] : 0.0f;
+    for (int j = 0; j < 8; ++j) bv[j] = (8 * q + j < KS) ? bf(8 * q + j) : 0.0f;
   };
   auto load_a = [&](int cell) {
 #pragma unroll
@@ -337,20 +368,20 @@ __device__ __forceinline__ void mlp_layer_split(const WS& w, const float* act, f
 
 template <int NT, int KS, int FBASE, int NF, int SG = (NT >= 8 ? 1 : (NT >= 4 ? 2 : (NT >= 2 ? 4 : 8))), int W = kWaves, int CH = kChunk, class WS = WStream>
 __device__ __forceinline__ void mlp_layer(const WS& w, const float* act, f32x16 (&acc)[NT]) {
-  if constexpr (kRcSplit) mlp_layer_split<NT, KS, FBASE, NF, W, CH, 0, false>(w, act, acc, nullptr);
-  else mlp_layer_f32<NT, KS, FBASE, NF, SG, W, CH, WS>(w, act, acc);
+  if constexpr (kRcSplit) mlp_layer_split<NT, KS, FBASE, NF, W, CH, 0, false>(w, BAct{act}, acc, nullptr);
+  else mlp_layer_f32<NT, KS, FBASE, NF, SG, W, CH, WS>(w, BAct{act}, acc);
 }
 
 // A layer of the split build with the options of mlp_layer_split (ready B pieces, bias block).
 template <int NT, int KS, int FBASE, int NF, int NBP, bool BIAS1, int W = kWaves, int CH = kChunk, class WS = WStream>
 __device__ __forceinline__ void mlp_layer_x(const WS& w, const float* act, f32x16 (&acc)[NT], const u32x4 (*pre)[3] = nullptr) {
-  mlp_layer_split<NT, KS, FBASE, NF, W, CH, NBP, BIAS1>(w, act, acc, pre);
+  mlp_layer_split<NT, KS, FBASE, NF, W, CH, NBP, BIAS1>(w, BAct{act}, acc, pre);
 }
 
 // A layer of a proposal level's density MLP: the exact fp32 MFMA chain in every build (rc_pack_host.h rc_lfr32).
 template <int NT, int KS, int FBASE, int NF, int SG = (NT >= 8 ? 1 : (NT >= 4 ? 2 : (NT >= 2 ? 4 : 8))), int W = kWaves, int CH = kChunk, class WS = WStream>
 __device__ __forceinline__ void mlp_layer_d(const WS& w, const float* act, f32x16 (&acc)[NT]) {
-  mlp_layer_f32<NT, KS, FBASE, NF, SG, W, CH, WS>(w, act, acc);
+  mlp_layer_f32<NT, KS, FBASE, NF, SG, W, CH, WS>(w, BAct{act}, acc);
 }
 
 // The bias k-step of a layer (fragments [FBASE, FBASE + NT): the bias row of each tile) with its B operand -- 1 on the
@@ -392,8 +423,8 @@ __device__ __forceinline__ void mlp_bias_step(const WS& w, f32x16 (&acc)[NT]) {
 
 // Same as mlp_layer_d (density MLPs: fp32 MFMA in every build) for PT point-tiles per wave (64 points): every A fragment
 // read from the ring feeds PT MFMAs.  Tile p's activation column starts at act + p * tile_stride.
-template <int PT, int NT, int KS, int FBASE, int NF, int SG = (NT * PT >= 8 ? 1 : (NT * PT >= 4 ? 2 : 4)), int W = kWaves, class WS = WStream>
-__device__ __forceinline__ void mlp_layer_pt(const WS& w, const float* act, int tile_stride, f32x16 (&acc)[PT][NT]) {
+template <int PT, int NT, int KS, int FBASE, int NF, int SG, int W, class WS, class BF>
+__device__ __forceinline__ void mlp_layer_pt_b(const WS& w, const BF& bf, f32x16 (&acc)[PT][NT]) {
   constexpr int NG = (KS + SG - 1) / SG;
   float a[3][SG][NT], b[3][SG][PT];
   auto load = [&](int g, int buf) {
@@ -402,7 +433,7 @@ __device__ __forceinline__ void mlp_layer_pt(const WS& w, const float* act, int 
       const int s = g * SG + d;
       if (s < KS) {
 #pragma unroll
-        for (int p = 0; p < PT; ++p) b[buf][d][p] = act[p * tile_stride + s * 64];
+        for (int p = 0; p < PT; ++p) b[buf][d][p] = bf(p, s);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int f = FBASE + s * NT + t;
@@ -434,6 +465,11 @@ __device__ __forceinline__ void mlp_layer_pt(const WS& w, const float* act, int 
   }
 }
 
+template <int PT, int NT, int KS, int FBASE, int NF, int SG = (NT * PT >= 8 ? 1 : (NT * PT >= 4 ? 2 : 4)), int W = kWaves, class WS = WStream>
+__device__ __forceinline__ void mlp_layer_pt(const WS& w, const float* act, int tile_stride, f32x16 (&acc)[PT][NT]) {
+  mlp_layer_pt_b<PT, NT, KS, FBASE, NF, SG, W, WS>(w, BActPt{act, tile_stride}, acc);
+}
+
 // max(x, 0) as ONE instruction.  fmaxf() on a value the compiler cannot prove canonical -- an MFMA result -- is preceded
 // by a canonicalising `v_max_f32 x, x, x`: two instructions per activation, 64 per 32-point tile of a proposal MLP.
 // Split form: the inline-asm read of an accumulator right behind a v_mfma_f32_32x32x16_bf16 was NOT covered by the
@@ -460,6 +496,35 @@ __device__ __forceinline__ void park(const f32x16 (&acc)[NT], float* act, int ba
       const float v = acc[t][r];
       act[(base + t * 16 + r) * 64] = RELU ? relu0(v) : v;
     }
+}
+
+// Hand NT accumulator tiles to the next layer in registers (BHand): what park() leaves in LDS, without the trip.  The
+// ReLU is applied once per value here, as park applies it.
+template <int NT, bool BIAS, bool RELU = true>
+__device__ __forceinline__ void hand_off(const f32x16 (&acc)[NT], int lane, BHand<NT, BIAS>& hb) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) hb.v[t * 16 + r] = RELU ? relu0(acc[t][r]) : acc[t][r];
+  hb.one = lane < 32 ? 1.0f : 0.0f;
+}
+// The layer behind a hand-over of NTP tiles: KS = 16 NTP (+ 1 with the bias step).  Same fragments, same MFMAs in the
+// same order per accumulator as the layer on the parked column: mlp_layer_h follows the build's arithmetic (the split
+// form's bias step is its bias block), mlp_layer_dh is the density MLPs' fp32 chain, mlp_layer_pth its PT-tile form.
+template <int NT, int NTP, bool BIAS, int FBASE, int NF, int W = kWaves, int CH = kChunk, class WS = WStream>
+__device__ __forceinline__ void mlp_layer_dh(const WS& w, const BHand<NTP, BIAS>& hb, f32x16 (&acc)[NT]) {
+  constexpr int SG = NT >= 8 ? 1 : (NT >= 4 ? 2 : (NT >= 2 ? 4 : 8));
+  mlp_layer_f32<NT, 16 * NTP + (BIAS ? 1 : 0), FBASE, NF, SG, W, CH, WS>(w, hb, acc);
+}
+template <int NT, int NTP, bool BIAS, int FBASE, int NF, int W = kWaves, int CH = kChunk, class WS = WStream>
+__device__ __forceinline__ void mlp_layer_h(const WS& w, const BHand<NTP, BIAS>& hb, f32x16 (&acc)[NT]) {
+  if constexpr (kRcSplit) mlp_layer_split<NT, 16 * NTP + (BIAS ? 1 : 0), FBASE, NF, W, CH, 0, BIAS>(w, hb, acc, nullptr);
+  else mlp_layer_dh<NT, NTP, BIAS, FBASE, NF, W, CH, WS>(w, hb, acc);
+}
+template <int PT, int NT, int NTP, bool BIAS, int FBASE, int NF, int W = kWaves, class WS = WStream>
+__device__ __forceinline__ void mlp_layer_pth(const WS& w, const BHandPt<PT, NTP, BIAS>& hb, f32x16 (&acc)[PT][NT]) {
+  constexpr int SG = NT * PT >= 8 ? 1 : (NT * PT >= 4 ? 2 : 4);
+  mlp_layer_pt_b<PT, NT, 16 * NTP + (BIAS ? 1 : 0), FBASE, NF, SG, W, WS>(w, hb, acc);
 }
 
 // Output layers with a handful of rows (density + predicted normals, integrated BRDF, ambient rgb): in-register dot
@@ -545,7 +610,11 @@ __host__ __device__ constexpr int ide_m(int i) { return i < 2 ? i : (i < 5 ? i -
 
 
 // activation slice of the shader (steps): [0,48) feature (hidden 32 | appearance 16) | [48,84) IDE | 84 bias(1|0) |
-// (the (n.v | 1) step of the integrated BRDF reuses step 48 once the IDE is dead).  The 128-wide shader bottleneck
+// (the (n.v | 1) step of the integrated BRDF reuses step 48 once the IDE is dead).  That is ALL the slice holds: values
+// that cross lanes on their way to a layer.  What one layer hands the next -- IBRDF layer 0 -> 1, SLF layer_0 -> layer_1
+// -> layer_2 -> layer_bottleneck, with their bias steps -- is relu(acc) of the lane's own accumulators and goes in
+// registers (BHand / hand_off / mlp_layer_h above); the slice's size stays kShActSteps, the density MLPs of the fused
+// kernel stage their grid features, Jacobian rows and the waiting appearance features in it.  The 128-wide shader bottleneck
 // (Dense(96 -> 128) WITHOUT activation, nerf.py:394-396) only feeds
 // linear layers -- SLF layer_0, the input part of SLF layer_bottleneck, integrated_brdf_layers_0 -- so the host
 // folds it into those (W' = W_b W[:128], b' = b + b_b W[:128], products in fp64): the layer itself and 16 k-steps of
@@ -659,12 +728,11 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     act[48 * 64] = h == 0 ? dot_nv : 1.0f;
     if constexpr (kRcSplit) mlp_layer_x<2, 49, F0 + ShaderFrags::F_I0, NF, 6, false>(ws, act, ib, fpc);      // step 48 carries n.v: no bias block
     else mlp_layer<2, 49, F0 + ShaderFrags::F_I0, NF>(ws, act, ib);
-    // steps [48, 81) are scratch for the IBRDF tail
-    park<2, true>(ib, act, 48);
-    act[(48 + 32) * 64] = h == 0 ? 1.0f : 0.0f;
+    // the IBRDF tail takes relu(ib) and its bias step in registers
+    BHand<2, true> hi;
+    hand_off<2, true>(ib, lane, hi);
     ib[0] = zero16(); ib[1] = zero16();
-    if constexpr (kRcSplit) mlp_layer_x<2, 33, F0 + ShaderFrags::F_I1, NF, 0, true>(ws, act + 48 * 64, ib);
-    else mlp_layer<2, 33, F0 + ShaderFrags::F_I1, NF>(ws, act + 48 * 64, ib);
+    mlp_layer_h<2, 2, true, F0 + ShaderFrags::F_I1, NF>(ws, hi, ib);
     float o[1], nokeep[1];
     dot_out1<2, 1, F0 + ShaderFrags::F_IO, NF>(ws, ib, o, nokeep);     // output_integrated_brdf_layer on relu(ib)
     ibrdf = sigmoidf(o[0] + 1.0986123f);        // + log(3), nerf.py:481
@@ -675,21 +743,21 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
   {
     f32x16 acc[4] = {s0[0], s0[1], s0[2], s0[3]};
     f32x16 skip[4] = {s0[4], s0[5], s0[6], s0[7]};
-    park<4, true>(acc, act, 0);
-    act[64 * 64] = h == 0 ? 1.0f : 0.0f;
+    // every trunk layer hands relu(acc) to the next in registers; nothing of the trunk goes through LDS
+    BHand<4, true> hs;
+    hand_off<4, true>(acc, lane, hs);
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = zero16();
-    if constexpr (kRcSplit) mlp_layer_x<4, 65, F0 + ShaderFrags::F_S1, NF, 0, true>(ws, act, acc);
-    else mlp_layer<4, 65, F0 + ShaderFrags::F_S1, NF>(ws, act, acc);
-    park<4, true>(acc, act, 0);
+    mlp_layer_h<4, 4, true, F0 + ShaderFrags::F_S1, NF>(ws, hs, acc);
+    hand_off<4, true>(acc, lane, hs);
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = zero16();
     RC_TSTAMP(5);
-    if constexpr (kRcSplit) mlp_layer_x<4, 65, F0 + ShaderFrags::F_S2, NF, 0, true>(ws, act, acc);
-    else mlp_layer<4, 65, F0 + ShaderFrags::F_S2, NF>(ws, act, acc);
-    park<4, true>(acc, act, 0);
+    mlp_layer_h<4, 4, true, F0 + ShaderFrags::F_S2, NF>(ws, hs, acc);
+    BHand<4, false> hb;
+    hand_off<4, false>(acc, lane, hb);
     RC_TSTAMP(6);
-    mlp_layer<4, 64, F0 + ShaderFrags::F_SB, NF>(ws, act, skip);
+    mlp_layer_h<4, 4, false, F0 + ShaderFrags::F_SB, NF>(ws, hb, skip);
     RC_TSTAMP(7);
     float o[3], nokeep[1];
     dot_out1<4, 3, F0 + ShaderFrags::F_SO, NF>(ws, skip, o, nokeep);   // output_ambient_rgb_layer on relu(layer_bottleneck)

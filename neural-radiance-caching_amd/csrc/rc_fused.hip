@@ -43,11 +43,13 @@ __device__ __forceinline__ float density_level64(const WS& ws, float* act_wave, 
 #pragma unroll
   for (int p = 0; p < 2; ++p) { acc[p][0] = zero16(); acc[p][1] = zero16(); }
   mlp_layer_pt<2, 2, KS0, FB + FR::D0, NF>(ws, act, kTileStride, acc);
+  // D0 -> D1 in registers (rc_dev_mlp.h BHand): relu(acc) and the bias step of both point-tiles
+  BHandPt<2, 2, true> hd;
 #pragma unroll
-  for (int p = 0; p < 2; ++p) { park<2, true>(acc[p], act + p * kTileStride, 0); act[p * kTileStride + 32 * 64] = h == 0 ? 1.0f : 0.0f; }
+  for (int p = 0; p < 2; ++p) hand_off<2, true>(acc[p], lane, hd.hand[p]);
 #pragma unroll
   for (int p = 0; p < 2; ++p) { acc[p][0] = zero16(); acc[p][1] = zero16(); }
-  mlp_layer_pt<2, 2, 33, FB + FR::D1, NF>(ws, act, kTileStride, acc);
+  mlp_layer_pth<2, 2, 2, true, FB + FR::D1, NF>(ws, hd, acc);
   float out[2][1], nokeep[1];
   dot_out<2, 2, 1, FB + FR::DO, NF>(ws, acc, out, nokeep);       // output_density_layer on relu(acc), both point-tiles
   // the dot product is complete on both half-waves: sample `lane` = (tile = lane >> 5, point lane & 31)
@@ -299,10 +301,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) m0 |= (acc[t][r] > 0.0f ? 1u : 0u) << (t * 16 + r);
     }
-    park<2, true>(acc, act, 0);
-    act[32 * 64] = h == 0 ? 1.0f : 0.0f;
-    acc[0] = zero16(); acc[1] = zero16();
-    mlp_layer_d<2, 33, F_L2 + FR::D1, NF>(ws, act, acc);
+    {
+      BHand<2, true> hd;                        // D0 -> D1 in registers
+      hand_off<2, true>(acc, lane, hd);
+      acc[0] = zero16(); acc[1] = zero16();
+      mlp_layer_dh<2, 2, true, F_L2 + FR::D1, NF>(ws, hd, acc);
+    }
     if constexpr (GRAD) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -316,23 +320,22 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
     npx = out[1]; npy = out[2]; npz = out[3];
     neg_normalize(npx, npy, npz);
     if constexpr (GRAD) {
-      // the backward pass borrows [0, 32): the hidden feature waits in registers meanwhile
-      float hid[32];
+      // the backward pass's B operands are the lane's own registers (masked output weights, masked gradient): the
+      // hidden feature at [0, 32) is never displaced
+      BHand<2, false> bw;
+      bw.one = 0.0f;
 #pragma unroll
-      for (int s = 0; s < 32; ++s) hid[s] = act[s * 64];
-      float* bw = act;
-#pragma unroll
-      for (int s = 0; s < 32; ++s) bw[s * 64] = ((m1 >> s) & 1u) ? wout[s] : 0.0f;
+      for (int s = 0; s < 32; ++s) bw.v[s] = ((m1 >> s) & 1u) ? wout[s] : 0.0f;
       f32x16 g[2];
       g[0] = zero16(); g[1] = zero16();
-      mlp_layer_d<2, 32, F_L2 + FR::B1, NF>(ws, bw, g);
+      mlp_layer_dh<2, 2, false, F_L2 + FR::B1, NF>(ws, bw, g);
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) bw[(t * 16 + r) * 64] = ((m0 >> (t * 16 + r)) & 1u) ? g[t][r] : 0.0f;
+        for (int r = 0; r < 16; ++r) bw.v[t * 16 + r] = ((m0 >> (t * 16 + r)) & 1u) ? g[t][r] : 0.0f;
       f32x16 gf[1];
       gf[0] = zero16();
-      mlp_layer_d<1, 32, F_L2 + FR::B0, NF>(ws, bw, gf);
+      mlp_layer_dh<1, 2, false, F_L2 + FR::B0, NF>(ws, bw, gf);
       // d raw / d feature i = acc_feat(0, r, h) sits on lane (j, h): each half-wave contracts ITS 16 features with the
       // Jacobian rows parked in LDS, the two partial sums are added last (the order k_density_mlp uses)
       float gp[3] = {0.0f, 0.0f, 0.0f};
@@ -348,8 +351,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
         const float oth = __shfl_xor(gp[ax], 32, 64);
         gw[ax] = h == 0 ? gp[ax] + oth : oth + gp[ax];        // half 0's partial first on both halves
       }
-#pragma unroll
-      for (int s = 0; s < 32; ++s) act[s * 64] = hid[s];
       const float msq = zx * zx + zy * zy + zz * zz;
       float gzx = gw[0], gzy = gw[1], gzz = gw[2];
       if (msq > 1.0f) {
