@@ -128,6 +128,9 @@ typedef struct {
 #define RC_PASS_SECONDARY  0x2u   /* is_secondary=True: far clamp, power-ladder distances, bg 0, resample, EnvMap */
 #define RC_PASS_RESAMPLE   0x4u   /* force categorical resampling to num_resample samples (models.py:193-292) */
 #define RC_PASS_NO_ENVMAP  0x8u   /* use_env_map=False for secondary rays (material.py:2191-2217) */
+#define RC_PASS_ENV_IMAGE  0x10u  /* with RC_PASS_SECONDARY: the composite's EnvMap is the image bound by rc_set_env_image, looked up at
+                                     rays->viewdirs (Model._handle_env_map with env_map=, models.py:382-393); no image bound:
+                                     RC_ERR_INVALID_ARG.  Ignored with RC_PASS_NO_ENVMAP (use_env_map=False wins) */
 
 /* Output slots: keys of the reference's `render` dict (integrator results,
  * internal/render.py:172-247, internal/integration.py:199-231, internal/models.py:2087-2158).
@@ -1151,6 +1154,65 @@ int rc_weighted_percentile(rc_handle* h, const float* value, const float* weight
 int rc_image_max(rc_handle* h, const float* src, int64_t n, float* out, void* stream);
 int rc_vis_images(rc_handle* h, const rc_vis_item* items, int32_t n_items, int32_t height, int32_t width, void* stream);
 int rc_vis_turbo_lut(float* out);
+
+/* ---- relighting under an explicit HDR environment image -------------------------------------------------
+ * The reference's relighting path: render_eval_fn hands dataset.env_map / env_map_pmf / env_map_pdf / env_map_dirs and
+ * albedo_ratio to model.apply (internal/train_utils.py:3796-3812); Model._handle_env_map reads the image through
+ * render_utils.get_environment_color instead of the EnvMap MLP (internal/models.py:382-393); under
+ * Config.compute_relight_metrics both importance-sampler sets are EnvironmentSampler (render_utils.py:191-252).  Single
+ * illumination only (L = 1).
+ *
+ * rc_set_env_image: binds an image rgb [H][W][3] (DEVICE floats) and, optionally, its sampling tables pmf [H W], pdf [H W],
+ *   dirs [H W][3] (all three or none) to the handle.  The handle COPIES what it is given into allocations of its own on
+ *   `stream` (the image as a zero-padded RGBA copy, the tables, and safe_log(pmf)), so the caller may free its buffers once
+ *   the stream has passed the call.  rgb = NULL unbinds (height, width ignored).  A bind of the size already bound
+ *   allocates nothing.  Calls that read the bound image on ANOTHER stream are the caller's to order behind the bind.
+ * rc_env_tables: the tables of the reference's dataset loader (internal/datasets.py:2113-2154) from rgb * scale:
+ *   pmf = I sin(theta_row) / sum, I = r + g + b, sin(theta_row) = sin(linspace(0.5 / H, pi - 0.5 / H, H)) (the loader's
+ *   h_interval is 1 / H; kept), pdf = pmf H W / (2 pi^2 sin(theta_row)), dirs = (cos lng cos lat, sin lng cos lat, sin lat)
+ *   on the loader's grid.  The normaliser is summed in double in a fixed order: two calls on one image are bitwise equal.
+ * rc_env_lookup: get_environment_color (render_utils.py:1552-1598) of n directions on the bound image -> out_rgb [n][3]:
+ *   (x, y, z) <- (d.x, d.z, -d.y), s = sqrt(x^2 + y^2 + 1e-8), phi = atan2(y / (s + 1e-8), x / (s + 1e-8)), theta = atan2(s, z),
+ *   row = theta / pi H, col = (-phi + pi) / (2 pi) W, bilinear with zero padding and pixel centres at integer coordinates
+ *   (grid_utils.jax_resample_2d, CONSTANT_OUTSIDE).  Texel row i therefore sits at polar angle i pi / H, the last row fades
+ *   into the padding, and there is a dark seam at phi = +-pi: the image does not wrap.  A non-finite direction gives a NaN
+ *   colour and never a read outside the image.
+ * rc_env_pick: jax.random.categorical(key, safe_log(pmf), axis=-2, shape=(1, T, 1)) over the bound pmf -> picks [T] (DEVICE
+ *   int32): per pick the argmax over the H W texels of safe_log(pmf) + gumbel, the Gumbel noise of flat element k H W + t of
+ *   jax.random.gumbel(key, (1, T, H W, 1)) computed in registers, ties to the lowest texel.  T H W < 2^32, T <= 65535.
+ * rc_render_relight: rc_render_material under the bound image.  Same rays, randoms, workspaces, trace and outputs; `args`:
+ *   RC_RELIGHT_BRDF  the stage's own importance samplers; only the EnvMap along the secondary rays is replaced by the image
+ *                    lookup.  The EnvMap weights are not needed.
+ *   RC_RELIGHT_ENV   EnvironmentSampler in both sampler sets (compute_relight_metrics): sample (b, k) of a leg with K samples
+ *                    per point takes texel picks[(b K + k) % T], direction dirs[pick] (global, brought into the shading frame
+ *                    and back), pdf max(pdf[pick], 0), weight 1, 0 below the horizon.  T must be 256 when (n K) % 256 == 0 and
+ *                    n K otherwise, per leg (K = Ks for picks_spec, Kd for picks_diff); the tables must be bound.  The BRDF
+ *                    and vMF members of rc_material_randoms and the LightSampler weights are not read.
+ *   albedo_ratio     DEVICE float[3] or NULL: albedo <- clip(albedo ratio, 0, 1) at the shading point and in the
+ *                    material-only composite (material.py:2106-2116).
+ * RC_PASS_ENV_IMAGE (rc_render_rays) composites the bound image on secondary rays the same way.
+ * Every call is ordered on `stream`, never synchronises, allocates nothing once the sizes have been seen ("rl:" workspace),
+ * uses no float atomics (rc_env_pick: one integer max per wave and pick, order-free) and is refused on a time-resolved
+ * handle (RC_ERR_UNSUPPORTED).  n == 0 / T == 0 return RC_OK and write nothing.  RC_ERR_INVALID_ARG: a NULL required pointer,
+ * height or width < 1, H W >= 2^31, tables given in part, no image (or no tables) bound where one is read, a non-finite
+ * scale, an unknown mode, a T that breaks the rule above (the message names the expected T). */
+int rc_set_env_image(rc_handle* h, const float* rgb, const float* pmf, const float* pdf, const float* dirs, int32_t height,
+                     int32_t width, void* stream);
+int rc_env_tables(rc_handle* h, const float* rgb, int32_t height, int32_t width, float scale, float* pmf, float* pdf,
+                  float* dirs, void* stream);
+int rc_env_lookup(rc_handle* h, const float* viewdirs, int64_t n, float* out_rgb, void* stream);
+int rc_env_pick(rc_handle* h, const uint32_t key[2], int32_t T, int32_t* picks, void* stream);
+typedef enum { RC_RELIGHT_BRDF = 0, RC_RELIGHT_ENV = 1 } rc_relight_mode;
+typedef struct {
+  uint32_t mode;                 /* rc_relight_mode */
+  const int32_t* picks_spec;     /* DEVICE [T_spec] texel indices of the specular leg (RC_RELIGHT_ENV) */
+  const int32_t* picks_diff;     /* DEVICE [T_diff] texel indices of the diffuse leg (RC_RELIGHT_ENV) */
+  int32_t T_spec, T_diff;
+  const float* albedo_ratio;     /* DEVICE [3] or NULL */
+} rc_relight_args;
+int rc_render_relight(rc_handle* h, const rc_rays* rays, int64_t n_rays, const rc_randoms* rnd,
+                      const rc_material_randoms* mr, int32_t num_secondary_samples, const rc_relight_args* args,
+                      const rc_outputs* cache_out, const rc_mat_outputs* mat_out, void* stream);
 
 #ifdef __cplusplus
 }

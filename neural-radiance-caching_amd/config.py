@@ -146,6 +146,8 @@ class RenderConfig:
     default_F_0: float = 0.04
     num_vmf: int = 128                # LightMLP.num_components
     vmf_scale: float = 20.0
+    # relighting: EnvironmentSampler in both importance-sampler sets of the material stage (material.py:658, 1228-1247)
+    compute_relight_metrics: bool = False   # configs.py:496
     # --- host chunking (internal/models.py:2409) ---------------------------------
     render_chunk_size: int = 1024     # README quick-start operating point
     # --- time-resolved cache (None for the steady-state models) ------------------

@@ -139,6 +139,10 @@ struct VisWs { WsBuf state, part, maxpart, binsum; };
 // the means as points [n S][3].
 struct MaskWs { WsBuf loss_ray, d_density, points; };
 
+// rc_env_tables / rc_env_pick: the per-workgroup sums of the tables' normaliser (doubles) and the per-pick (score, texel)
+// maxima (64-bit integers).
+struct RelightWs { WsBuf part, best; };
+
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
 // serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
@@ -149,15 +153,15 @@ struct MaskWs { WsBuf loss_ray, d_density, points; };
 // WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY),
 // WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
 // rc_eval_image, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
-// WS_MASK rc_mask_backward.
+// WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick.
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -179,7 +183,7 @@ struct WsName {
   WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
   WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
   WsBuf EvalWs::*ev = nullptr; WsBuf AlbedoWs::*ea = nullptr; WsBuf VisWs::*vz = nullptr;
-  WsBuf MaskWs::*mk = nullptr;
+  WsBuf MaskWs::*mk = nullptr; WsBuf RelightWs::*rl = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -197,6 +201,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf AlbedoWs::*m) : name(s), ea(m) {}
   constexpr WsName(const char* s, WsBuf VisWs::*m) : name(s), vz(m) {}
   constexpr WsName(const char* s, WsBuf MaskWs::*m) : name(s), mk(m) {}
+  constexpr WsName(const char* s, WsBuf RelightWs::*m) : name(s), rl(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -214,7 +219,8 @@ struct WsName {
       if (ev) return one(s, ev);
       if (ea) return one(s, ea);
       if (vz) return one(s, vz);
-      return mk ? one(s, mk) : nullptr;
+      if (mk) return one(s, mk);
+      return rl ? one(s, rl) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -224,7 +230,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -255,10 +261,11 @@ constexpr WsName kTable[] = {
     WS(EV, binsum_pred), WS(EV, binsum_gt), WS(EV, post_pred), WS(EV, post_gt), WS(EV, part),
     WS(EA, pairs), WS(EA, wg), WS(EA, state), WS(EA, part),
     WS(VZ, state), WS(VZ, part), WS(VZ, maxpart), WS(VZ, binsum),
-    WS(MK, loss_ray), WS(MK, d_density), WS(MK, points)};
+    WS(MK, loss_ray), WS(MK, d_density), WS(MK, points),
+    WS(RL, part), WS(RL, best)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -350,6 +357,11 @@ struct rc_handle {
   // events: fork, join)
   hipStream_t train_stream = nullptr;
   hipEvent_t ev_train[2] = {nullptr, nullptr};
+  // rc_set_env_image: the handle's own copies of the bound image (zero-padded RGBA, RcEnvImage) and of its tables
+  // (pmf, pdf, dirs and safe_log(pmf)); env_img_h == 0: nothing bound
+  DevBuf env_padded, env_pmf, env_pdf, env_dirs, env_logp;
+  int32_t env_img_h = 0, env_img_w = 0;
+  bool env_tables = false;
   std::vector<GraphEntry> graphs;
   RenderKey last_key{};
   bool have_last_key = false;
@@ -1135,6 +1147,7 @@ void rc_destroy(rc_handle* h) {
   free_buf(h->geom_w);
   free_buf(h->env_w);
   free_buf(h->thead_w);
+  free_buf(h->env_padded); free_buf(h->env_pmf); free_buf(h->env_pdf); free_buf(h->env_dirs); free_buf(h->env_logp);
   if (h->pinned) (void)hipHostFree(h->pinned);
   drop_graphs(h);
   for (WsSet& s : h->ws) if (s.done) (void)hipEventDestroy(s.done);
@@ -1569,7 +1582,10 @@ void enqueue_all(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st)
   }
   if (secondary) {
     const bool use_env = !(A.mask & RC_PASS_NO_ENVMAP);
-    if (use_env) {
+    if (use_env && (A.mask & RC_PASS_ENV_IMAGE)) {
+      // an explicit image instead of the EnvMap MLP (Model._handle_env_map, models.py:382-393)
+      rc_launch_env_lookup(RcEnvLookupArgs{RcEnvImage{h->env_padded.p, h->env_img_h, h->env_img_w}, rays->viewdirs, n, w.env_rgb.p}, st);
+    } else if (use_env) {
       RcEnvMapArgs ea{};
       ea.n = n; ea.viewdirs = rays->viewdirs; ea.wstream = h->packs.envmap.p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = w.env_rgb.p;
       rc_launch_envmap(ea, st);
@@ -1603,7 +1619,10 @@ int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_random
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
-  if (secondary && !(pass_mask & RC_PASS_NO_ENVMAP) && !h->have_envmap)
+  const bool env_image = secondary && (pass_mask & RC_PASS_ENV_IMAGE) && !(pass_mask & RC_PASS_NO_ENVMAP);
+  if (env_image && h->env_img_h == 0)
+    return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: RC_PASS_ENV_IMAGE without a bound image (rc_set_env_image)");
+  if (secondary && !(pass_mask & RC_PASS_NO_ENVMAP) && !env_image && !h->have_envmap)
     return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/* (secondary rays composite the model-level EnvMap)");
   const bool fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && pass_mask == RC_PASS_CACHE;
   // one workspace set per caller stream (up to 4): calls on different streams do not share buffers.  The fused kernel
@@ -1768,7 +1787,8 @@ namespace {
 // what rc_render_material launched before, in the same order.
 struct MatSplit { int Ks, Kd, Kc; };
 
-int material_check(rc_handle* h, const rc_rays* rays, const rc_material_randoms* mr, int32_t K, const char* who, MatSplit& sp) {
+int material_check(rc_handle* h, const rc_rays* rays, const rc_material_randoms* mr, int32_t K, const char* who, MatSplit& sp,
+                   bool own_samplers = true) {
   int rc;
   const std::string w = who;
   if ((rc = check_rays(h, rays, who))) return rc;
@@ -1780,6 +1800,8 @@ int material_check(rc_handle* h, const rc_rays* rays, const rc_material_randoms*
   if (K < 2 || Ks < 1 || Kd < 2 || Kc < 1 || Kd - Kc < 1 || Ks + Kd > 64)
     return fail(h, RC_ERR_UNSUPPORTED, w + ": num_secondary_samples must give 1 <= Ks, 2 <= Kd, Ks + Kd <= 64");
   if (c.num_vmf != 128) return fail(h, RC_ERR_UNSUPPORTED, w + ": num_vmf must be 128");
+  // (own_samplers = false: rc_render_relight's RC_RELIGHT_ENV, which reads neither the BRDF nor the vMF members)
+  if (own_samplers)
   if (!mr->vmf_noise || !mr->spec_u1 || !mr->spec_u2 || !mr->cos_u1 || !mr->cos_u2 || !mr->vmf_v || !mr->vmf_tmp ||
       !(mr->vmf_lobe || mr->vmf_lobe_gumbel))
     return fail(h, RC_ERR_INVALID_ARG, w + ": every sampler member of rc_material_randoms is required "
@@ -1896,30 +1918,32 @@ int material_trace_args(rc_handle* h, const rc_material_randoms* mr, int64_t nse
   return RC_OK;
 }
 
-}  // namespace
+int relight_check(rc_handle* h, const rc_relight_args* rl, int64_t n, const MatSplit& sp);      // rc_relight_host.inc
 
-extern "C" {
-
-int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd,
-                       const rc_material_randoms* mr, int32_t K, const rc_outputs* cache_out,
-                       const rc_mat_outputs* mat_out, void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  RoctxScope roctx_call("rc_render_material");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_material: this handle renders the time-resolved cache (rc_render_transient)");
-  if (!rays || !mr || !cache_out || !mat_out) return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: null argument");
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_material: negative n_rays");
+// The material stage: rc_render_material (rl == nullptr) and rc_render_relight (rc_relight_host.inc), which replaces the
+// EnvMap along the secondary rays by the bound image's lookup, in RC_RELIGHT_ENV the light head and the BRDF sampler by the
+// environment sampler, and scales the albedo; every other launch is the same code in the same order.
+int material_render(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd, const rc_material_randoms* mr, int32_t K,
+                    const rc_relight_args* rl, const rc_outputs* cache_out, const rc_mat_outputs* mat_out, void* stream_v,
+                    const char* who_c) {
+  const std::string who = who_c;
+  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": this handle renders the time-resolved cache (rc_render_transient)");
+  if (!rays || !mr || !cache_out || !mat_out) return fail(h, RC_ERR_INVALID_ARG, who + ": null argument");
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n_rays");
   if (n == 0) return RC_OK;
   int rc;
   MatSplit sp;
-  if ((rc = material_check(h, rays, mr, K, "rc_render_material", sp))) return rc;
+  const bool env_mode = rl && rl->mode == RC_RELIGHT_ENV;
+  if ((rc = material_check(h, rays, mr, K, who_c, sp, !env_mode))) return rc;
+  if (rl && (rc = relight_check(h, rl, n, sp))) return rc;
+  const float* ratio = rl ? rl->albedo_ratio : nullptr;
   const rc_config& c = h->cfg;
   const int Ks = sp.Ks, Kd = sp.Kd;
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
   if (!h->have_material) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/MaterialShader/* or params/LightSampler/*");
-  if (!h->have_envmap) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/*");
+  if (!rl && !h->have_envmap) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/*");
   const int NL = c.num_levels;
   const int S2 = c.num_samples[NL - 1];
   const int64_t np2 = n * S2, nsec = n * (Ks + Kd);
@@ -1953,9 +1977,36 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
     }
   } side_join{h, st, side, false};
   // 3a. material head and 4. light sampler (128 vMF lobes) at the shading point
-  material_heads(h, n, mr, x, st);
+  if (env_mode) {
+    // _handle_light_sampling_pass hands the image's tables on: the LightSampler is not evaluated
+    RcMatHeadArgs ma{};
+    ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
+    ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
+    ma.min_roughness = c.min_roughness;
+    roctx_stage("material: head");
+    rc_launch_hashgrid(h->grids[4].dev, x.m_pts.p, 0, n, x.m_feat.p, 0, 32, c.contract_radius, nullptr, st);
+    ma.n = n; ma.feat = x.m_feat.p; ma.mat = x.m_mat.p;
+    rc_launch_material_head(ma, st);
+  } else {
+    material_heads(h, n, mr, x, st);
+  }
+  // albedo <- clip(albedo ratio, 0, 1) (_predict_material_and_feature, material.py:2106-2116)
+  if (ratio) rc_launch_albedo_ratio(x.m_mat.p, n, ratio, st);
   // 5. BRDF importance sampling -> secondary rays
-  material_brdf_sample(h, rays, n, mr, sp, x, st);
+  if (env_mode) {
+    roctx_stage("material: environment sample");
+    RcEnvSampleArgs sa{};
+    sa.n = n; sa.Ks = Ks; sa.Kd = Kd;
+    sa.pts = x.m_pts.p; sa.nrm = x.m_nrm.p; sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
+    sa.pdf = h->env_pdf.p; sa.dirs = h->env_dirs.p; sa.hw = (int64_t)h->env_img_h * h->env_img_w;
+    sa.picks_spec = rl->picks_spec; sa.picks_diff = rl->picks_diff; sa.T_spec = rl->T_spec; sa.T_diff = rl->T_diff;
+    sa.normal_eps = c.secondary_normal_eps; sa.near = c.secondary_near; sa.far = c.secondary_far;
+    sa.sec_origins = x.sec_origins.p; sa.sec_dirs = x.sec_dirs.p; sa.sec_near = x.sec_near.p; sa.sec_far = x.sec_far.p;
+    sa.sec_lights = x.sec_lights.p; sa.samples = x.sec_samples.p; sa.local_view = x.m_local_view.p;
+    rc_launch_env_sample(sa, st);
+  } else {
+    material_brdf_sample(h, rays, n, mr, sp, x, st);
+  }
   // 3b. side stream: the material head on ALL samples and the material-only composite (outputs only).  Forked HERE, behind
   // the BRDF sampler: beside the small latency-bound kernels above they doubled those kernels' times (heads 18 -> 35 us,
   // sampler 19 -> 33 us); beside the first level of the trace they fit into what its workgroups leave of a CU (no LDS /
@@ -1971,6 +2022,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
     rc_launch_hashgrid(h->grids[4].dev, w.means[NL - 1].p, 1, np2, x.m_feat_all.p, 0, 32, c.contract_radius, nullptr, side);
     ma.n = np2; ma.feat = x.m_feat_all.p; ma.mat = x.m_mat_all.p;
     rc_launch_material_head(ma, side);
+    if (ratio) rc_launch_albedo_ratio(x.m_mat_all.p, np2, ratio, side);
     rc_launch_material_composite_all(n, S2, w.weights[NL - 1].p, x.m_mat_all.p, mat_out->ptr[RC_MOUT_MATERIAL_ALBEDO],
                                      mat_out->ptr[RC_MOUT_MATERIAL_ROUGHNESS], mat_out->ptr[RC_MOUT_MATERIAL_METALNESS],
                                      mat_out->ptr[RC_MOUT_MATERIAL_F_0], c.default_F_0, side);
@@ -1991,7 +2043,9 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
     // (split-MFMA build: the EnvMap takes 0.7 of the time on the bf16 pipe and an eighth of the CUs is enough -- 16 ... 40 of
     // 256 measure 1.315-1.33 ms per step, 64: 1.36, 80: 1.38)
     static const int env_reserve = getenv("RC_ENV_RESERVE") ? atoi(getenv("RC_ENV_RESERVE")) : rc_device_cus() / (kRcSplit ? 8 : 4);
-    const bool beside_last = env_reserve > 0 && nsec >= 24576 && (h->fused_mode == 1 || h->fused_mode == 3);
+    // (rc_render_relight: the image lookup is memory-bound and short; it never takes that spot)
+    const RcEnvLookupArgs la{RcEnvImage{h->env_padded.p, h->env_img_h, h->env_img_w}, x.sec_dirs.p, nsec, x.sec_env.p};
+    const bool beside_last = !rl && env_reserve > 0 && nsec >= 24576 && (h->fused_mode == 1 || h->fused_mode == 3);
     bool env_released = false;
     if (beside_last) {
       B.env = &ea; B.env_side = side; B.env_ready = h->ev_side[1]; B.env_done = h->ev_side[2]; B.env_reserve = env_reserve;
@@ -1999,7 +2053,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
     } else {
       RC_HIP(h, hipEventRecord(h->ev_side[1], st));               // secondary rays are in place
       RC_HIP(h, hipStreamWaitEvent(side, h->ev_side[1], 0));
-      rc_launch_envmap(ea, side);
+      if (rl) rc_launch_env_lookup(la, side); else rc_launch_envmap(ea, side);
       RC_HIP(h, hipEventRecord(h->ev_side[2], side));
       env_released = true;
     }
@@ -2029,6 +2083,19 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
   }
   RC_HIP(h, hipGetLastError());
   return RC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd,
+                       const rc_material_randoms* mr, int32_t K, const rc_outputs* cache_out,
+                       const rc_mat_outputs* mat_out, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  RoctxScope roctx_call("rc_render_material");
+  return material_render(h, rays, n, rnd, mr, K, nullptr, cache_out, mat_out, stream_v, "rc_render_material");
   RC_CATCH(h)
 }
 
@@ -2049,3 +2116,4 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_metrics_host.inc"
 #include "rc_albedo_host.inc"
 #include "rc_vis_host.inc"
+#include "rc_relight_host.inc"

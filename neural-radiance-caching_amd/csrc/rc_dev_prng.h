@@ -1,5 +1,6 @@
 // Threefry-2x32 (20 rounds) and jax 0.4.16's counter layout, shared by the kernels that draw random bits: the fill
-// (rc_prng.hip) and the training batch that maps such bits to indices itself (rc_batch.hip).  Host twin: ../prng.py.
+// (rc_prng.hip), the training batch that maps such bits to indices itself (rc_batch.hip) and the categorical draw over an
+// environment image's texels (rc_relight.hip); and the map from bits to a uniform and a Gumbel value.  Host twin: ../prng.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,3 +34,12 @@ __device__ __forceinline__ uint32_t prng_bits_at(uint32_t k0, uint32_t k1, uint3
   threefry2x32(k0, k1, x0, x1);
   return e < half ? x0 : x1;
 }
+
+// jax.random.uniform's float of 32 random bits: the top 23 as the mantissa of a value in [1, 2), minus 1; then
+// max(lo, u (hi - lo) + lo)
+__device__ __forceinline__ float prng_unit_float(uint32_t bits) { return __uint_as_float((bits >> 9) | 0x3F800000u) - 1.0f; }
+__device__ __forceinline__ float prng_uniform(uint32_t bits, float lo, float hi) { return fmaxf(lo, prng_unit_float(bits) * (hi - lo) + lo); }
+// jax.random.gumbel: -log(-log(u)) of a uniform in (tiny, 1)
+constexpr float kPrngTiny = 1.17549435e-38f;
+__device__ __forceinline__ float prng_gumbel_of(float u) { return -logf(-logf(u)); }
+__device__ __forceinline__ float prng_gumbel(uint32_t bits) { return prng_gumbel_of(prng_uniform(bits, kPrngTiny, 1.0f)); }

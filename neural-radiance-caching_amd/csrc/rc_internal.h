@@ -868,6 +868,38 @@ struct RcPrngArgs {
 };
 void rc_launch_prng_fill(const RcPrngArgs& a, hipStream_t stream);
 
+// Relighting under an explicit environment image (rc_relight.hip; the lookup itself: rc_dev_relight.h)
+struct RcEnvImage { const float* padded; int32_t H, W; };   // [(H + 2)][(W + 2)][4]: zero border, 4th channel zero
+struct RcEnvLookupArgs { RcEnvImage im; const float* viewdirs; int64_t n; float* out; };   // [n,3] -> [n,3]
+struct RcEnvTablesArgs {
+  const float* rgb; int32_t H, W; float scale;     // [H][W][3], read as rgb * scale
+  float* pmf; float* pdf; float* dirs;             // [H W], [H W], [H W][3]
+  double* part;                                    // [rc_env_tables_blocks(H W)] per-workgroup sums
+};
+struct RcEnvPickArgs {
+  const float* logp; int64_t hw;                   // safe_log(pmf) [hw]
+  uint32_t key0, key1; int32_t T;
+  unsigned long long* best;                        // [T] (score, texel) maxima, zeroed by the launcher
+  int32_t* picks;                                  // [T]
+};
+struct RcEnvSampleArgs {
+  int64_t n; int32_t Ks, Kd;
+  const float* pts; const float* nrm; const float* viewdirs; const float* lights;
+  const float* pdf; const float* dirs; int64_t hw;             // the bound tables
+  const int32_t* picks_spec; const int32_t* picks_diff; int32_t T_spec, T_diff;
+  float normal_eps, near, far;
+  float* sec_origins; float* sec_dirs; float* sec_near; float* sec_far; float* sec_lights;   // as RcBrdfSampleArgs
+  float* samples; float* local_view;
+};
+void rc_launch_env_pad(const float* rgb, int H, int W, float* padded, hipStream_t st);
+void rc_launch_env_lookup(const RcEnvLookupArgs& a, hipStream_t st);
+int rc_env_tables_blocks(int64_t hw);
+void rc_launch_env_tables(const RcEnvTablesArgs& a, hipStream_t st);
+void rc_launch_env_logp(const float* pmf, int64_t hw, float* logp, hipStream_t st);
+void rc_launch_env_pick(const RcEnvPickArgs& a, hipStream_t st);
+void rc_launch_env_sample(const RcEnvSampleArgs& a, hipStream_t st);
+void rc_launch_albedo_ratio(float* mat, int64_t n, const float* ratio, hipStream_t st);   // rows of RC_MAT_CH
+
 
 // Kernel attributes (dynamic-LDS limit) are per device: true the first time the calling thread's current device
 // shows up for this `mask` (one mask per kernel), so a process driving several GPUs sets them on each.

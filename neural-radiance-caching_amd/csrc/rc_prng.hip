@@ -42,14 +42,12 @@ __device__ __forceinline__ float erfinv32(float x) {
   return p * x;
 }
 
-__device__ __forceinline__ float unit_float(uint32_t bits) { return __uint_as_float((bits >> 9) | 0x3F800000u) - 1.0f; }
-
 __device__ __forceinline__ uint32_t shape_value(uint32_t bits, int mode, float lo, float hi) {
   if (mode == RC_PRNG_BITS) return bits;
-  const float u = fmaxf(lo, unit_float(bits) * (hi - lo) + lo);
+  const float u = prng_uniform(bits, lo, hi);
   float v = u;
   if (mode == RC_PRNG_NORMAL) v = 1.41421356237309515f * erfinv32(u);
-  if (mode == RC_PRNG_GUMBEL) v = -logf(-logf(u));
+  if (mode == RC_PRNG_GUMBEL) v = prng_gumbel_of(u);
   return __float_as_uint(v);
 }
 

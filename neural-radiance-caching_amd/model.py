@@ -241,8 +241,17 @@ class Model:
             raise NotImplementedError("only the render-time path (train=False, train_frac=1.0) is accelerated")
         if sampling_strategy is not None and tuple(sampling_strategy) != tuple(self.config.sampling_strategy):
             raise NotImplementedError("sampling_strategy is fixed when the handle is created")
+        env_map = unused_render_kwargs.get("env_map")
         if "material" in passes:
-            return self._apply_material(variables, rng, rays)
+            if env_map is None:
+                return self._apply_material(variables, rng, rays)
+            # relighting: dataset.env_map and its tables handed on by render_eval_fn (train_utils.py:3796-3812);
+            # EnvironmentSampler in both sampler sets under compute_relight_metrics (material.py:658, 1228-1247)
+            from . import relight
+            env = relight.as_env_image(self.rc, env_map, unused_render_kwargs)
+            mode = "env" if getattr(self.config, "compute_relight_metrics", False) else "brdf"
+            return self._apply_material(variables, rng, rays, env=env, mode=mode,
+                                        albedo_ratio=unused_render_kwargs.get("albedo_ratio"))
         if self.config.transient is not None:
             return self._apply_transient(variables, rng, rays, is_secondary or "is_secondary" in passes, resample)
         self._ensure_variables(variables)
@@ -259,6 +268,11 @@ class Model:
         secondary = bool(mask & rc_ext.RC_PASS_SECONDARY)
         if secondary and unused_render_kwargs.get("use_env_map") is False:
             mask |= rc_ext.RC_PASS_NO_ENVMAP
+        if secondary and env_map is not None:
+            # Model._handle_env_map with an explicit image (models.py:382-393): the lookup instead of the EnvMap MLP
+            from . import relight
+            relight.as_env_image(self.rc, env_map, unused_render_kwargs)._ensure_bound()
+            mask |= rc_ext.RC_PASS_ENV_IMAGE
         lossmult = fields.get("lossmult")
         rc_plan, layout = self._plan(n, secondary, lossmult is not None)
         out_flat = None
@@ -310,7 +324,7 @@ class Model:
         r["lossmult"] = lm * torch.ones_like(r["integrated_rgb"])
         return {"render": r, "main": {"integrator": r}, "cache_main": {"integrator": r}}
 
-    def _apply_material(self, variables, rng, rays):
+    def _apply_material(self, variables, rng, rays, env=None, mode="brdf", albedo_ratio=None):
         """passes ("cache", "light", "material") with use_material / use_light_sampler /
         MaterialModel.resample_render (stage material_light_from_scratch_resample; internal/models.py:1144-1254,
         1398-1694).  `rng`: the dict of explicit random tensors (see rc_material_randoms in include/rc_abi.h;
@@ -320,10 +334,24 @@ class Model:
         NOT parity-verified: the threefry primitives are pinned by published known answers, but the ~30 split sites
         material_pass_randoms restates by hand have never been compared with a jax run (none is possible in this
         pipeline): a mis-ordered split would yield a different, equally valid-looking stream.  Parity claims of the
-        material stage are made on explicit random tensors only."""
+        material stage are made on explicit random tensors only.
+
+        env (a relight.EnvImage): the stage is relit under it (rc_render_relight): the image in place of the EnvMap and,
+        in mode "env", the environment sampler in place of the stage's own (relight.relight_inputs says what `rng` holds
+        then); albedo_ratio scales the albedo (material.py:2106-2116).  The output keys are the same."""
         import torch
 
         n_rays = int(np.prod(np.shape(rays.origins if isinstance(rays, Rays) else rays["origins"])[:-1]))
+        if env is not None:
+            from . import relight
+            rng, picks_spec, picks_diff = relight.relight_inputs(env, rng, n_rays, self.config, mode)
+            env._ensure_bound()
+            self._ensure_variables(variables)
+            fields = rays.hot_fields() if isinstance(rays, Rays) else dict(rays)
+            cres, mres = self.rc.render_relight(fields, rng, mode, picks_spec, picks_diff, albedo_ratio)
+            return self._material_outputs(cres, mres, fields)
+        if albedo_ratio is not None:
+            raise NotImplementedError("albedo_ratio is applied on the relighting path (env_map=)")
         if prng.is_key(rng):
             rng = prng.material_pass_randoms(rng, n_rays, self.config)
         if not isinstance(rng, dict):
@@ -335,6 +363,12 @@ class Model:
         self._ensure_variables(variables)
         fields = rays.hot_fields() if isinstance(rays, Rays) else dict(rays)
         cres, mres = self.rc.render_material(fields, rng)
+        return self._material_outputs(cres, mres, fields)
+
+    def _material_outputs(self, cres, mres, fields):
+        """The material stage's output dict from the two device tables (cache and material side)."""
+        import torch
+
         cache = self._finalize(cres, fields)
         r = dict(mres)
         zeros3 = torch.zeros_like(r["rgb"])
@@ -474,11 +508,21 @@ def create_render_fn(model: Model, dataset: Any = None, mapping_fn: Any = None):
     docstring), `rays` is sharded [1, m, .] (or a `Pixels` batch, cast on the device), and every value of the result
     carries the [n_dev = 1, n_dev = 1, m, ...] leading axes of pmap + all_gather so `unshard(v[0], padding)` applies
     unchanged.  `mapping_fn` (jax.pmap / jax.vmap in the reference) has nothing to map here and is ignored.
-    `dataset` supplies `camtype` for the Pixels branch; its env_map / mesh inputs must be unset (the BASELINE
-    configs render without them)."""
+    `dataset` supplies `camtype` for the Pixels branch; a dataset whose `env_map` is set (an EnvImage, or the reference's arrays
+    env_map / env_map_w / _h / _pmf / _pdf / _dirs) relights: the image and `albedo_ratio` go to every model.apply call as
+    the reference's render_eval_fn hands them on.  `dataset.mesh` must be unset."""
     camtype = getattr(dataset, "camtype", None) if dataset is not None else None
+    if dataset is not None and getattr(dataset, "mesh", None) is not None:
+        raise NotImplementedError("dataset.mesh is not part of the accelerated path")
+    # dataset.env_map and its tables: handed to model.apply with every call (train_utils.py:3796-3812), uploaded and bound
+    # once here
+    env_kwargs = {}
     if dataset is not None and getattr(dataset, "env_map", None) is not None:
-        raise NotImplementedError("dataset.env_map is not part of the accelerated path")
+        from . import relight
+        env_kwargs["env_map"] = relight.as_env_image(model.rc, dataset.env_map, {
+            k: getattr(dataset, k, None) for k in ("env_map_w", "env_map_h", "env_map_pmf", "env_map_pdf", "env_map_dirs")})
+        if getattr(dataset, "albedo_ratio", None) is not None:
+            env_kwargs["albedo_ratio"] = dataset.albedo_ratio
 
     def render_eval_pfn(variables, rng, train_frac, cameras, lights, rays, passes, resample=None):
         if isinstance(rays, Pixels):
@@ -491,7 +535,7 @@ def create_render_fn(model: Model, dataset: Any = None, mapping_fn: Any = None):
         else:
             apply_key, next_rng = rng, rng
         out = model.apply(variables, apply_key, rays, train_frac=train_frac, train=False, passes=tuple(passes),
-                          resample=resample, compute_extras=True)
+                          resample=resample, compute_extras=True, **env_kwargs)
         render = out["render"]
         if isinstance(render, RenderDict):
             render = render.with_lead(2)

@@ -270,6 +270,26 @@ def material_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
                                             (sampling.py:170-179) -- the specular and the diffuse trace therefore draw the
                                             SAME per-level jitter
     The call order is restated from the source and cannot be checked against a jax run here (no jax in the image)."""
+    return _material_stage_randoms(model_rng, n_rays, cfg, env_sampler=False)
+
+
+def relight_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
+    """The random inputs of ONE relit material-stage forward under Config.compute_relight_metrics (EnvironmentSampler in
+    both sampler sets; relight.relight(mode="env")): the tensors material_pass_randoms gives for the parts both modes
+    share (the primary rays' jitter, the shading sample's gumbel, the secondary traces' jitter and gumbel) and the two
+    categorical keys of the texel draws, "picks_key_spec" and "picks_key_diff", at their split sites:
+
+      get_outgoing_radiance                 material.py:1383 (indirect specular), 1416 (indirect diffuse); 1513, 1540 reuse
+                                            the rays of these two legs for the direct (env-map) passes
+      importance_sample_rays                render_utils.py:767 (uh, uw: drawn, not used by this sampler), 784 (the
+                                            sampler's rng); ONE sampler per set, with the leg's whole count
+      EnvironmentSampler.sample_directions  render_utils.py:215 (key, rng = split(rng); categorical(key, ...))
+    The secondary cache calls' keys do not depend on the sampler set, so the traces draw what material_pass_randoms
+    draws.  Like that function the call order is restated from the source and not pinned to a jax run."""
+    return _material_stage_randoms(model_rng, n_rays, cfg, env_sampler=True)
+
+
+def _material_stage_randoms(model_rng, n_rays: int, cfg, env_sampler: bool) -> Dict[str, object]:
     K = int(cfg.num_secondary_samples)
     Kd = int(round(K * cfg.diffuse_sample_fraction))
     Ks = int(round(K * (1.0 - cfg.diffuse_sample_fraction)))
@@ -322,6 +342,17 @@ def material_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
         jit = sampler_randoms(PRNGKey(0), n_rays * Kp, levels)
         return jit, gumbel(kg2, (n_rays, Kp, S, 1))[..., 0].reshape(n_rays * Kp, S)
 
+    if env_sampler:
+        (_, _, kb_spec), = one_pass(k_spec, [Ks])[0]
+        _, kc_spec = one_pass(k_spec, [Ks])
+        (_, _, kb_diff), = one_pass(k_diff, [Kd])[0]
+        _, kc_diff = one_pass(k_diff, [Kd])
+        out["picks_key_spec"], _ = random_split(kb_spec)      # render_utils.py:215
+        out["picks_key_diff"], _ = random_split(kb_diff)
+        out["spec_jitter"], out["spec_gumbel"] = trace_randoms(kc_spec, Ks)
+        out["diff_jitter"], out["diff_gumbel"] = trace_randoms(kc_diff, Kd)
+        del out["vmf_noise"]                  # the LightSampler is not evaluated
+        return out
     (su1, su2, _), = one_pass(k_spec, [Ks])[0]
     _, kc_spec = one_pass(k_spec, [Ks])
     out["spec_u1"], out["spec_u2"] = su1, su2

@@ -21,6 +21,10 @@ RC_PASS_CACHE = 0x1
 RC_PASS_SECONDARY = 0x2
 RC_PASS_RESAMPLE = 0x4
 RC_PASS_NO_ENVMAP = 0x8
+RC_PASS_ENV_IMAGE = 0x10
+
+RC_RELIGHT_BRDF = 0
+RC_RELIGHT_ENV = 1
 
 # rc_output_id -> (name, width); order must match include/rc_abi.h
 OUTPUTS = (
@@ -99,6 +103,11 @@ class rc_material_randoms(C.Structure):
 
 class rc_mat_outputs(C.Structure):
     _fields_ = [("ptr", C.c_void_p * RC_MOUT_COUNT)]
+
+
+class rc_relight_args(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("picks_spec", C.c_void_p), ("picks_diff", C.c_void_p), ("T_spec", C.c_int32),
+                ("T_diff", C.c_int32), ("albedo_ratio", C.c_void_p)]
 
 
 class rc_transient_config(C.Structure):
@@ -331,6 +340,12 @@ _PROTOTYPES = {
     "rc_image_max": (C.c_int, [_H, _P, _I64, _P, _P]),
     "rc_vis_images": (C.c_int, [_H, C.POINTER(rc_vis_item), _I32, _I32, _I32, _P]),
     "rc_vis_turbo_lut": (C.c_int, [_P]),
+    "rc_set_env_image": (C.c_int, [_H, _P, _P, _P, _P, _I32, _I32, _P]),
+    "rc_env_tables": (C.c_int, [_H, _P, _I32, _I32, _F, _P, _P, _P, _P]),
+    "rc_env_lookup": (C.c_int, [_H, _P, _I64, _P, _P]),
+    "rc_env_pick": (C.c_int, [_H, _P, _I32, _P, _P]),
+    "rc_render_relight": (C.c_int, [_H, _RAYS, _I64, _RND, _MRND, _I32, C.POINTER(rc_relight_args), _OUT,
+                                    C.POINTER(rc_mat_outputs), _P]),
 }
 for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the five named layouts
     _PROTOTYPES[_size] = (C.c_int64, [_H])
@@ -1587,21 +1602,23 @@ class RadianceCache:
         self._keep = [held]
         return (flat, loss) if env is None else (flat, env, loss)
 
-    def _material_randoms(self, randoms, n, K, held):
+    def _material_randoms(self, randoms, n, K, held, own_samplers=True):
         """The rc_randoms / rc_material_randoms of render_material and light_sampling_backward (device copies kept in
-        `held`)."""
+        `held`).  own_samplers=False (render_relight's "env" mode): the BRDF and vMF members stay NULL."""
         torch = self._torch
         rnd = self._randoms(held, randoms.get("jitter"))
         mr = held["mrnd"] = rc_material_randoms()
         for k in ("gumbel", "vmf_noise", "spec_u1", "spec_u2", "cos_u1", "cos_u2", "vmf_v", "vmf_tmp"):
             if k == "gumbel" and randoms.get(k) is None:
                 continue                      # the primary pick is handed over as resample_inds
+            if k != "gumbel" and not own_samplers:
+                continue
             held["m_" + k] = self._dev(randoms[k])
             setattr(mr, k, held["m_" + k].data_ptr())
-        if randoms.get("vmf_lobe") is not None:
+        if own_samplers and randoms.get("vmf_lobe") is not None:
             held["m_lobe"] = self._dev(randoms["vmf_lobe"], torch.int32).reshape(-1)
             mr.vmf_lobe = held["m_lobe"].data_ptr()
-        else:                                 # the lobe is drawn on the device: argmax(logits + Gumbel noise)
+        elif own_samplers:                    # the lobe is drawn on the device: argmax(logits + Gumbel noise)
             held["m_lobe_g"] = self._dev(randoms["vmf_lobe_gumbel"]).reshape(n, -1)
             mr.vmf_lobe_gumbel = held["m_lobe_g"].data_ptr()
         # secondary trace randoms: [specular block | diffuse block]
@@ -1652,6 +1669,94 @@ class RadianceCache:
         mres, mout = self._outputs(MAT_OUTPUTS, m_names, mshape, dict(zip(m_names, bufs[len(c_names):])))
         self._check(self.lib.rc_render_material(self._h, C.byref(r), n, C.byref(rnd), C.byref(mr), K, C.byref(cout),
                                                 C.byref(mout), self._stream()))
+        self._keep = [held]
+        return cres, mres
+
+    # -- relighting under an explicit environment image (include/rc_abi.h) ---------------
+    def set_env_image(self, rgb, pmf=None, pdf=None, dirs=None):
+        """rc_set_env_image: bind rgb [H, W, 3] and, optionally, its tables pmf / pdf [H W] and dirs [H W, 3] (all three or
+        none); the handle keeps copies of its own.  rgb=None unbinds."""
+        if rgb is None:
+            self._check(self.lib.rc_set_env_image(self._h, None, None, None, None, 0, 0, self._stream()))
+            return
+        img = self._dev(rgb)
+        if img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError("rgb must be [H, W, 3]")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        tabs = [None if t is None else self._dev(t).reshape(-1) for t in (pmf, pdf, dirs)]
+        for t, cnt, nm in zip(tabs, (H * W, H * W, 3 * H * W), ("pmf", "pdf", "dirs")):
+            if t is not None and t.numel() != cnt:
+                raise ValueError(f"{nm}: expected {cnt} values")
+        self._check(self.lib.rc_set_env_image(self._h, img.data_ptr(), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), H, W,
+                                              self._stream()))
+        self._keep = [img, tabs]
+
+    def env_tables(self, rgb, scale: float = 1.0):
+        """rc_env_tables: (pmf [H W], pdf [H W], dirs [H W, 3]) of rgb * scale as float32 cuda tensors."""
+        torch = self._torch
+        img = self._dev(rgb)
+        if img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError("rgb must be [H, W, 3]")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        dev = f"cuda:{self.device}"
+        pmf, pdf = (torch.empty(H * W, dtype=torch.float32, device=dev) for _ in range(2))
+        dirs = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
+        self._check(self.lib.rc_env_tables(self._h, img.data_ptr(), H, W, float(scale), pmf.data_ptr(), pdf.data_ptr(),
+                                           dirs.data_ptr(), self._stream()))
+        self._keep = [img]
+        return pmf, pdf, dirs
+
+    def env_lookup(self, viewdirs):
+        """rc_env_lookup: the bound image's colour [n, 3] at directions [n, 3]."""
+        d = self._dev(viewdirs).reshape(-1, 3)
+        out = self._torch.empty_like(d)
+        self._check(self.lib.rc_env_lookup(self._h, d.data_ptr(), d.shape[0], out.data_ptr(), self._stream()))
+        self._keep = [d]
+        return out
+
+    def env_pick(self, key, T: int):
+        """rc_env_pick: jax.random.categorical(key, safe_log(pmf), axis=-2, shape=(1, T, 1)) over the bound pmf as an
+        int32 cuda tensor [T]."""
+        from . import prng
+        k = (C.c_uint32 * 2)(*[int(v) for v in prng.as_key(key)])
+        out = self._torch.empty(int(T), dtype=self._torch.int32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_env_pick(self._h, k, int(T), out.data_ptr(), self._stream()))
+        return out
+
+    def render_relight(self, rays: Dict[str, object], randoms: Dict[str, object], mode: str = "brdf", picks_spec=None,
+                       picks_diff=None, albedo_ratio=None, num_secondary_samples: int = None):
+        """rc_render_relight: render_material under the bound image.  mode "brdf": the stage's own samplers, the image in
+        place of the EnvMap; "env": the environment sampler on the texel picks picks_spec [T_spec] / picks_diff [T_diff]
+        (int32), whose sampler tensors may be missing from `randoms`.  albedo_ratio: three floats or None.  Returns
+        (cache_outputs, material_outputs) as render_material does."""
+        torch = self._torch
+        if mode not in ("brdf", "env"):
+            raise ValueError(f"unknown relight mode {mode!r}")
+        K = num_secondary_samples or self.cfg.num_secondary_samples
+        r, held, n = self._rays_struct(rays)
+        rnd, mr = self._material_randoms(randoms, n, K, held, own_samplers=mode == "brdf")
+        a = held["rl_args"] = rc_relight_args()
+        a.mode = RC_RELIGHT_ENV if mode == "env" else RC_RELIGHT_BRDF
+        if mode == "env":
+            if picks_spec is None or picks_diff is None:
+                raise ValueError("mode 'env' needs picks_spec and picks_diff")
+            ps = held["rl_ps"] = self._dev(picks_spec, torch.int32).reshape(-1)
+            pd = held["rl_pd"] = self._dev(picks_diff, torch.int32).reshape(-1)
+            a.picks_spec, a.picks_diff, a.T_spec, a.T_diff = ps.data_ptr(), pd.data_ptr(), ps.numel(), pd.numel()
+        if albedo_ratio is not None:
+            ar = held["rl_ratio"] = self._dev(albedo_ratio).reshape(-1)
+            if ar.numel() != 3:
+                raise ValueError("albedo_ratio must hold three values")
+            a.albedo_ratio = ar.data_ptr()
+        c_names = [nm for nm, _ in OUTPUTS if nm not in ("env_map_rgb", "rgb_no_env")]
+        m_names = [nm for nm, _ in MAT_OUTPUTS]
+        cshape = lambda nm: (n, 3) if OUTPUTS[OUTPUT_ID[nm]][1] == 3 else (n,)
+        mshape = lambda nm: (n, 3) if MAT_OUTPUTS[MAT_OUTPUT_ID[nm]][1] == 3 else (n,)
+        bufs = self._zeros_like_many([cshape(nm) for nm in c_names] + [mshape(nm) for nm in m_names])
+        cres, cout = self._outputs(OUTPUTS, c_names, cshape, dict(zip(c_names, bufs)))
+        mres, mout = self._outputs(MAT_OUTPUTS, m_names, mshape, dict(zip(m_names, bufs[len(c_names):])))
+        self._check(self.lib.rc_render_relight(self._h, C.byref(r), n, C.byref(rnd), C.byref(mr), K, C.byref(a),
+                                               C.byref(cout), C.byref(mout), self._stream()))
         self._keep = [held]
         return cres, mres
 
