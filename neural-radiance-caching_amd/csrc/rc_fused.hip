@@ -150,12 +150,16 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
 #if defined(RC_ABL) && RC_ABL == 11
       for (int l = 0; l < 6; ++l) f[l] = ux * (float)l + uy - uz;
 #else
-      Corners<1> C[6];          // all 48 corner loads in flight before the first combine
+      // 6 cell-table loads of 16 bytes (dense levels) + 24 corner loads (hashed levels) in flight before the first combine.
+      // The kind of level l is the compile-time l < kFusedDense (fused_geometry_ok), never the run-time L.dense: as two arms
+      // of a branch that fill the same C[l], the hashed arm is a fall-through successor of the dense one for the compiler's
+      // wait-count pass and opened with s_waitcnt vmcnt(0) -- one memory round trip per hashed level instead of one in all
+      Corners<1> C[6];
       RC_FSTAMP(12);
 #pragma unroll
       for (int l = 0; l < 6; ++l) {
         const RcGridLevel& L = a.grid[0].lvl[l];
-        if (L.dense) grid_fetch_cell(a.cell_table[0][l], L.size, ux, uy, uz, C[l]);
+        if (l < kFusedDense) grid_fetch_cell(a.cell_table[0][l], L.size, ux, uy, uz, C[l]);
         else grid_fetch<1, true>(L.table, L.size, L.mask, 0u, false, ux, uy, uz, C[l]);
       }
       RC_FSTAMP_NOWAIT(13);
@@ -193,11 +197,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
 #if defined(RC_ABL) && RC_ABL == 11
       for (int l = 0; l < 7; ++l) f[l] = ux * (float)l + uy - uz;
 #else
-      Corners<1> C[7];          // all 56 corner loads in flight before the first combine
+      Corners<1> C[7];          // 6 + 32 loads in flight before the first combine (level kinds at compile time, as above)
 #pragma unroll
       for (int l = 0; l < 7; ++l) {
         const RcGridLevel& L = a.grid[1].lvl[l];
-        if (L.dense) grid_fetch_cell(a.cell_table[1][l], L.size, ux, uy, uz, C[l]);
+        if (l < kFusedDense) grid_fetch_cell(a.cell_table[1][l], L.size, ux, uy, uz, C[l]);
         else grid_fetch<1, true>(L.table, L.size, L.mask, 0u, false, ux, uy, uz, C[l]);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -253,14 +257,14 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
         // a copy of the two tables interleaved entry by entry ([density 16 B | appearance 16 B]), so the two half-waves
         // of a point read the two halves of ONE 32-byte pair -- half the cache-line requests and sector traffic
         const RcGridLevel& L = a.grid[2].lvl[l];
-        grid_fetch<4, true, 2, true>(a.pair_table[l] + 4 * h, L.size, L.mask, 0u, L.dense != 0, ux, uy, uz, C[q]);
+        grid_fetch<4, true, 2, true>(a.pair_table[l] + 4 * h, L.size, L.mask, 0u, l < kFusedDense, ux, uy, uz, C[q]);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int l = half * 4 + q;
         const int size = a.grid[2].lvl[l].size;
-        const bool dense = a.grid[2].lvl[l].dense != 0;
+        const bool dense = l < kFusedDense;       // compile-time, as in the fetch
         float v[4], jd[GRAD ? 12 : 1];
         grid_combine<4, GRAD>(C[q], v, jd);
 #pragma unroll

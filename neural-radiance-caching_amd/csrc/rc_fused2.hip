@@ -467,7 +467,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
       for (int k = 0; k < 4; ++k) {
         const int l = 4 * qq + k;
         const RcGridLevel& L = a.grid[2].lvl[l];
-        grid_fetch<4, true, 2, true>(a.pair_table[l] + 4 * h, L.size, L.mask, 0u, L.dense != 0, ux, uy, uz, C[k]);
+        grid_fetch<4, true, 2, true>(a.pair_table[l] + 4 * h, L.size, L.mask, 0u, l < kFusedDense, ux, uy, uz, C[k]);   // kind at compile time (rc_fused.hip, level 0)
       }
       __builtin_amdgcn_sched_barrier(0);
       const int base = h == 0 ? 0 : kAppTmp;
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
       for (int k = 0; k < 4; ++k) {
         const int l = 4 * qq + k;
         const int size = a.grid[2].lvl[l].size;
-        const bool dense = a.grid[2].lvl[l].dense != 0;
+        const bool dense = l < kFusedDense;
         float v[4], jd[GRAD ? 12 : 1];
         grid_combine<4, GRAD>(C[k], v, jd);
         // feature kf = 4 l + c of point j -> step base + kf / 2, lane j + 32 (kf & 1)
