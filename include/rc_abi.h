@@ -978,6 +978,54 @@ int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* c
                                const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
                                const rc_transient_data_loss* cfg, float* head_grads, float* losses, void* stream);
 
+/* rc_transient_data_backward_kind: the same call under every loss type of _select_transient_data_loss_function
+ * (internal/train_utils.py:686-750) that the transient gins use, with or without Config.use_itof.  Notation as above, and
+ *   I_r(x) = sum_b W_r[b] x_b per channel, the rows of render_utils.dtof_to_itof (inverse_render/render_utils.py:1648-1676):
+ *   per (frequency, phase_shift) pair a cos row W[b] = cos(2 pi f t_b + phi) + 1 and a sin row sin(..) + 1, then one constant
+ *   row W[b] = 1/2; Nr = 2 n_pairs + 1; t_b = b exposure_time / 299792458 with the handle's own exposure_time.  The table is
+ *   evaluated on the host in double and rounded once to float32.
+ * data_loss per type (rows = bins for the first four, the Nr iToF rows for the last four), summed over its rows:
+ *   RAWNERF_TRANSIENT_UNBIASED       s (sum_b 2 d dn + 2 (k sum d)(k sum dn) gauss_mult)          (the entry above)
+ *   RAWNERF_TRANSIENT                s (sum_b d^2 + (k sum d)^2 gauss_mult)                       (:717-724, :329-347)
+ *   MSE / MSE_UNBIASED               sum_b d^2 / sum_b 2 d dn
+ *   MSE_ITOF / MSE_ITOF_UNBIASED     sum_r I_r(d)^2 / sum_r 2 I_r(d) I_r(dn)
+ *   RAWNERF_TRANSIENT_ITOF / .._UNBIASED   the same two times s
+ * With use_itof the data loss is divided by its number of rows (n_bins or Nr; :622-623) and losses[1], the "mses" stat,
+ * becomes mult * mean_{n x 3}(lossmult sum_r I_r(d)^2 / Nr) (:595-601).  losses[0] = mult * mean_{n x 3}(lossmult data_loss).
+ * s and dn carry no gradient.  transient_gauss_sigma_scales stays [] (base.gauss_* is read by the two per-bin rawnerf types
+ * only).  Ordering, allocation, n == 0, the handle it needs and the accumulation into head_grads are those of
+ * rc_transient_data_backward; steps 1, 3 and 4 are the same code.  loss_type 0 without use_itof runs that entry's own
+ * kernel: losses, "td:G" and the gradient are bitwise its.  Refused on the host, nothing launched (RC_ERR_INVALID_ARG): a
+ * null cfg, loss_type outside [0, RC_TLOSS_COUNT), n_pairs outside [0, RC_ITOF_MAX_PAIRS], a non-finite frequency or phase.
+ * rc_dtof_to_itof: dtof [n][n_bins][3] -> itof [n][2 n_pairs + 1][3] (device floats) with the same table and the same
+ * reduction, on any time-resolved handle: an iToF or steady-state measurement of a rendered or ground-truth histogram. */
+#define RC_ITOF_MAX_PAIRS 8
+typedef enum {
+  RC_TLOSS_RAWNERF_TRANSIENT_UNBIASED = 0,
+  RC_TLOSS_RAWNERF_TRANSIENT,
+  RC_TLOSS_MSE,
+  RC_TLOSS_MSE_UNBIASED,
+  RC_TLOSS_MSE_ITOF,
+  RC_TLOSS_MSE_ITOF_UNBIASED,
+  RC_TLOSS_RAWNERF_TRANSIENT_ITOF,
+  RC_TLOSS_RAWNERF_TRANSIENT_ITOF_UNBIASED,
+  RC_TLOSS_COUNT
+} rc_transient_loss_type;
+typedef struct {
+  rc_transient_data_loss base;
+  int32_t loss_type;           /* rc_transient_loss_type: TransientMaterialModel.cache_loss (cornell_itof.gin:6, ngp_yobo.gin:280) */
+  int32_t use_itof;            /* Config.use_itof (cornell_itof.gin:5; configs.py:717: False) */
+  int32_t n_pairs;             /* len(Config.itof_frequency_phase_shifts) (cornell_itof.gin:4: 4; *_steady_state.gin: 0) */
+  int32_t pad;
+  double frequency[RC_ITOF_MAX_PAIRS];    /* Hz */
+  double phase_shift[RC_ITOF_MAX_PAIRS];  /* radians */
+} rc_transient_data_loss_kind;
+int rc_transient_data_backward_kind(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                                    const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                                    const rc_transient_data_loss_kind* cfg, float* head_grads, float* losses, void* stream);
+int rc_dtof_to_itof(rc_handle* h, const float* dtof, int64_t n, int32_t n_pairs, const double* frequency,
+                    const double* phase_shift, float* itof, void* stream);
+
 /* ---- evaluation of a rendered view -------------------------------------------------------------------
  * rc_eval_image: what the reference's trainer computes per test view, on images that stay on the device.
  *   post-process (engine/trainer.py:617-637) of pred and gt alike: with n_bins > 0 the arrays are [H][W][n_bins][3] and

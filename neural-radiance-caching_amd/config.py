@@ -203,6 +203,51 @@ class TransientDataLossConfig:
     mask_lossmult: bool = False              # Config.mask_lossmult (cornell.gin:137)
     clip_eval: bool = False                  # Config.clip_eval (internal/configs.py:730)
     use_itof: bool = False                   # Config.use_itof (internal/configs.py:717)
+    # Config.itof_frequency_phase_shifts (configs/ngp_yobo.gin:459: []): (frequency in Hz, phase in radians) pairs of
+    # render_utils.dtof_to_itof; read by the *_itof loss types and under use_itof
+    itof_frequency_phase_shifts: Tuple = ()
+
+
+def _itof_pairs(f_lo: float, f_hi: float) -> Tuple:
+    """The four pairs of the *_itof gins: two frequencies at the phases 0 and 3.14159265359 (the gins' literal)."""
+    return ((f_lo, 0.0), (f_lo, 3.14159265359), (f_hi, 0.0), (f_hi, 3.14159265359))
+
+
+# name -> the fields of TransientDataLossConfig a family of transient gins sets off the cornell reading.  exposure_time is
+# no field here: it is the handle's (TransientConfig.exposure_time).
+_TRANSIENT_DATA_LOSS_PRESETS = {
+    # configs/transient_simulation_ngp_yobo_cornell.gin:51-64: the defaults
+    "cornell": {},
+    # transient_simulation_ngp_yobo_cornell_itof.gin:4-6 (over cornell.gin): 75 / 425 MHz, use_itof, cache_loss
+    "cornell_itof": dict(loss_type="rawnerf_transient_itof", use_itof=True,
+                         itof_frequency_phase_shifts=_itof_pairs(75000000.0, 425000000.0)),
+    # transient_simulation_ngp_yobo_pots_itof.gin:4-6 (over pots.gin:56-69, cornell's constants)
+    "pots_itof": dict(loss_type="rawnerf_transient_itof", use_itof=True,
+                      itof_frequency_phase_shifts=_itof_pairs(75000000.0, 425000000.0)),
+    # transient_simulation_ngp_yobo_peppers_itof.gin:3-5, :11 (over peppers.gin:100-109): 30 / 170 MHz, data_loss_mult 0.1
+    "peppers_itof": dict(loss_type="rawnerf_transient_itof", use_itof=True, data_loss_mult=0.1,
+                         itof_frequency_phase_shifts=_itof_pairs(30000000.0, 170000000.0)),
+    # transient_simulation_ngp_yobo_house_itof.gin:3-5, :8 (over house.gin:178-198: rawnerf_eps 1e-1): data_loss_mult 0.1
+    "house_itof": dict(loss_type="rawnerf_transient_itof", use_itof=True, data_loss_mult=0.1, rawnerf_eps=1e-1,
+                       itof_frequency_phase_shifts=_itof_pairs(30000000.0, 170000000.0)),
+    # transient_simulation_ngp_yobo_kitchen_itof.gin:4-6 (over kitchen.gin:151-160)
+    "kitchen_itof": dict(loss_type="rawnerf_transient_itof", use_itof=True,
+                         itof_frequency_phase_shifts=_itof_pairs(30000000.0, 170000000.0)),
+    # transient_simulation_ngp_yobo_cornell_steady_state.gin:4-6: no pairs, so dtof_to_itof is its constant row -- an
+    # intensity image
+    "steady_state": dict(loss_type="rawnerf_transient_itof", use_itof=True, itof_frequency_phase_shifts=()),
+    # transient_simulation_ngp_yobo.gin:280 (TransientMaterialModel.cache_loss = 'mse'), use_itof False (configs.py:717)
+    "mse": dict(loss_type="mse"),
+}
+TRANSIENT_DATA_LOSS_PRESETS = tuple(_TRANSIENT_DATA_LOSS_PRESETS)
+
+
+def transient_data_loss_preset(name: str) -> TransientDataLossConfig:
+    """The cache stage's transient data loss as a family of the reference's gins resolves it
+    (TRANSIENT_DATA_LOSS_PRESETS)."""
+    if name not in _TRANSIENT_DATA_LOSS_PRESETS:
+        raise KeyError(f"unknown transient data loss preset {name!r}: one of {TRANSIENT_DATA_LOSS_PRESETS}")
+    return dataclasses.replace(TransientDataLossConfig(), **_TRANSIENT_DATA_LOSS_PRESETS[name])
 
 
 @dataclasses.dataclass(frozen=True)

@@ -19,6 +19,7 @@
 
 #include "rc_internal.h"
 #include "rc_pack_host.h"
+#include "rc_itof_host.h"
 
 void rc_launch_hashgrid_src(const RcGridDev& g, const float* points, int soa_in, const int32_t* src, int64_t n_src,
                             int64_t n, float* out, int feature_major, int64_t ldo, float contract_radius,
@@ -311,6 +312,8 @@ struct rc_handle {
   DevBuf env_w;                              // rc_material_data_backward_env: the EnvMap's dense layers on the Flax layout
   uint64_t thead_gen = 0;                    // layers_gen thead_w was uploaded at
   DevBuf thead_w;                            // rc_transient_data_backward: the two per-bin head layers on the Flax layout
+  DevBuf itof_w;                             // rc_transient_data_backward_kind, rc_dtof_to_itof: the modulation table (rc_itof_host.h)
+  std::vector<double> itof_key;              // what itof_w was built from: exposure_time, then the (frequency, phase) pairs
   float* pinned = nullptr;                   // rc_load_params_flat: page-locked landing buffer of the dense segments
   size_t pinned_bytes = 0;
   bool have_envmap = false;
@@ -1147,6 +1150,7 @@ void rc_destroy(rc_handle* h) {
   free_buf(h->geom_w);
   free_buf(h->env_w);
   free_buf(h->thead_w);
+  free_buf(h->itof_w);
   free_buf(h->env_padded); free_buf(h->env_pmf); free_buf(h->env_pdf); free_buf(h->env_dirs); free_buf(h->env_logp);
   if (h->pinned) (void)hipHostFree(h->pinned);
   drop_graphs(h);

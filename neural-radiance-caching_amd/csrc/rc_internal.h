@@ -710,7 +710,24 @@ struct RcTransBinsBwdArgs {
   float* x_irr, * x_slf;                                   // [C 32][64], [C 32][128] the heads' inputs, reference column order, written
   float* d_tib, * d_direct, * d_weights;                   // [n_rays 32][3], [n_rays 32][3], [n_rays 32] written for the chunk's rays
 };
+// k_transient_loss_kinds: the same outputs under any rc_transient_loss_type, with or without use_itof
+struct RcTransLossKindArgs {
+  RcTransLossArgs base;                                    // as k_transient_loss reads it
+  int32_t kind;                                            // rc_transient_loss_type
+  int32_t use_itof;                                        // Config.use_itof: data_loss / rows, the mse stat in its iToF form
+  int32_t n_rows;                                          // 2 n_pairs + 1 rows of W (read by the iToF types and under use_itof)
+  float q;                                                 // 1 / rows under use_itof (n_rows or 700), else 1
+  const float* W;                                          // [n_rows][700] the modulation table (rc_itof_host.h, device)
+};
+struct RcDtofToItofArgs {
+  int64_t n; int32_t n_rows;
+  const float* W;                                          // [n_rows][700]
+  const float* x;                                          // [n][700][3]
+  float* out;                                              // [n][n_rows][3] written
+};
 void rc_launch_transient_loss(const RcTransLossArgs& a, hipStream_t st);
+void rc_launch_transient_loss_kinds(const RcTransLossKindArgs& a, hipStream_t st);
+void rc_launch_dtof_to_itof(const RcDtofToItofArgs& a, hipStream_t st);
 void rc_launch_transient_bins_bwd(const RcTransBinsBwdArgs& a, hipStream_t st);
 
 // Evaluation of a rendered view (rc_metrics.hip).  Partial sums are doubles, one slot set per workgroup.

@@ -8,6 +8,13 @@
 //                         part, render.py:406-417: its transpose is the correlation with the same taps).  The per-ray and
 //                         per-channel sums over the bins are wave reductions; the scalars are added up by
 //                         k_interlevel_reduce in a fixed order.
+//   k_transient_loss_kinds  the same plan and outputs under every rc_transient_loss_type (_select_transient_data_loss_function,
+//                         :686-750: mse, mse_unbiased, rawnerf_transient, the four iToF types) and under Config.use_itof
+//                         (:595-597, :622-623).  The modulation table W [2 P + 1][700] of render_utils.dtof_to_itof
+//                         (rc_itof_host.h) is staged in LDS once per workgroup; the 2 x 3 row sums I_r(d), I_r(dn) of a row
+//                         are wave reductions, one row at a time, and sum_r 2 I_r W_r[b] is accumulated per entry in
+//                         registers.  No atomics: two calls on the same inputs are bitwise equal.
+//   k_dtof_to_itof        render_utils.dtof_to_itof itself on [n][700][3], with the same table and row reduction.
 //   k_transient_bins_bwd  the adjoint of k_transient_bins (rc_transient.hip), one wavefront per ray with the ray's G row in
 //                         LDS: the gather that transposes shift_direct (render.py:436-477; a sample that spilled into the next
 //                         ray of the batch reads that ray's Gt), the two-tap gather that transposes shift_map_coordinates
@@ -337,7 +344,244 @@ __global__ __launch_bounds__(kBinsWaves * 64) void k_transient_bins_bwd(RcTransB
   }
 }
 
+// ---- the loss family (rc_transient_loss_type) and render_utils.dtof_to_itof ------------------------------------------
+// A lane holds the entries e = lane + 64 k of its ray, k < kPerLane.  With lane = 3 b0 + l3 and slot j = k % 3 (known at
+// compile time once the k loop is unrolled), entry k is channel (l3 + j) % 3 of bin a[j] + 21 k + k / 3: three per-lane
+// values a[j] = b0 + carry(l3 + j) and an immediate.  Sums over the entries are kept per slot and turned by l3 at the end.
+struct LaneMap { int l3, a[3]; };
+
+__device__ __forceinline__ LaneMap lane_map(int lane) {
+  LaneMap m;
+  m.l3 = lane % 3;
+  const int b0 = lane / 3;
+  m.a[0] = b0; m.a[1] = b0 + (m.l3 == 2 ? 1 : 0); m.a[2] = b0 + (m.l3 >= 1 ? 1 : 0);
+  return m;
+}
+// the bin of entry k; the last k runs past the histogram in the lanes >= kH - 64 (kPerLane - 1): clamped, its value is 0
+__device__ __forceinline__ int lane_bin(const LaneMap& m, int k) {
+  const int b = m.a[k % 3] + 21 * k + k / 3;
+  return k == kPerLane - 1 ? min(b, kB - 1) : b;
+}
+__device__ __forceinline__ bool lane_entry_ok(int lane, int k) { return lane + 64 * k < kH; }
+// per-slot values -> the value of channel c, and per-channel values -> the value of slot j (the three candidates are read
+// into values first: a conditional between array elements would index the array by a run-time value and put it in scratch)
+__device__ __forceinline__ float pick3(int l3, float v0, float v1, float v2) { return l3 == 0 ? v0 : (l3 == 1 ? v1 : v2); }
+__device__ __forceinline__ float slot_to_channel(const float (&t)[3], int l3, int c) {
+  return pick3(l3, t[c], t[(c + 2) % 3], t[(c + 1) % 3]);
+}
+__device__ __forceinline__ float channel_to_slot(const float (&v)[3], int l3, int j) {
+  return pick3(l3, v[j], v[(j + 1) % 3], v[(j + 2) % 3]);
+}
+
+// I_r(x) of the wave's ray, per channel: sum_b W_r[b] x_b.  w: the row in LDS; x: the lane's entries, 0 past the histogram.
+// Per lane the entries of a slot are added in the order of k, then the lanes by wave_total: a fixed order.
+__device__ __forceinline__ void itof_row(const float* w, const LaneMap& m, const float (&x)[kPerLane], float (&I)[3]) {
+  float t[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) t[k % 3] += w[lane_bin(m, k)] * x[k];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) I[c] = wave_total(slot_to_channel(t, m.l3, c));
+}
+
+// the table to LDS, once per workgroup
+__device__ __forceinline__ void stage_itof_table(float* sW, const float* W, int n_rows) {
+  for (int i = threadIdx.x; i < n_rows * kB; i += blockDim.x) sW[i] = W[i];
+  __syncthreads();
+}
+
+// k_transient_loss under every rc_transient_loss_type, with or without use_itof: the same plan and the same outputs.
+__global__ __launch_bounds__(kWavesPerBlock * 64) void k_transient_loss_kinds(RcTransLossKindArgs ka) {
+  extern __shared__ __attribute__((aligned(16))) float sW[];      // [n_rows][kB]
+  __shared__ float sG[kWavesPerBlock][kH];
+  const RcTransLossArgs& a = ka.base;
+  const int kind = ka.kind;
+  const bool itof_kind = kind >= RC_TLOSS_MSE_ITOF;
+  const bool unbiased = kind == RC_TLOSS_RAWNERF_TRANSIENT_UNBIASED || kind == RC_TLOSS_MSE_UNBIASED ||
+                        kind == RC_TLOSS_MSE_ITOF_UNBIASED || kind == RC_TLOSS_RAWNERF_TRANSIENT_ITOF_UNBIASED;
+  const bool rawnerf = kind == RC_TLOSS_RAWNERF_TRANSIENT_UNBIASED || kind == RC_TLOSS_RAWNERF_TRANSIENT ||
+                       kind == RC_TLOSS_RAWNERF_TRANSIENT_ITOF || kind == RC_TLOSS_RAWNERF_TRANSIENT_ITOF_UNBIASED;
+  const bool gauss_row = kind == RC_TLOSS_RAWNERF_TRANSIENT_UNBIASED || kind == RC_TLOSS_RAWNERF_TRANSIENT;
+  const bool rows_used = itof_kind || ka.use_itof != 0;
+  if (rows_used) stage_itof_table(sW, ka.W, ka.n_rows);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const LaneMap m = lane_map(lane);
+  int64_t ray = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  const bool ray_ok = ray < a.n;
+  if (!ray_ok) ray = a.n - 1;
+  const float* rgb = a.rgb + ray * kH;
+  const float* gt = a.gt + ray * kH;
+  const float* rgbn = a.rgb_nocorr ? a.rgb_nocorr + ray * kH : rgb;      // train_utils.py:604-610
+  const float* gtn = a.gt_nocorr ? a.gt_nocorr + ray * kH : gt;
+  float d[kPerLane], dn[kPerLane];
+  // per slot: sum of the clipped colour, of d, of dn, of d dn, of d^2, count of gt > thresh
+  float acc[6][3];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) acc[q][0] = acc[q][1] = acc[q][2] = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) {
+    const bool ok = lane_entry_ok(lane, k);
+    const int ec = ok ? lane + 64 * k : 0;
+    const float r = rgb[ec], g = gt[ec];
+    const float dv = ok ? r - g : 0.0f, dnv = ok ? rgbn[ec] - gtn[ec] : 0.0f;
+    d[k] = dv; dn[k] = dnv;
+    float cl;                                     // _get_rgb_clip_for_rawnerf, as k_transient_loss
+    if (a.use_gt) cl = clip0(g, a.clip_val);
+    else {
+      cl = clip0(r, a.clip_val);
+      if (a.use_combined) cl = clip0(fmaxf(cl, g), a.clip_val);
+    }
+    const int j = k % 3;
+    acc[0][j] += ok ? cl : 0.0f;
+    acc[1][j] += dv;
+    acc[2][j] += dnv;
+    acc[3][j] += dv * dnv;
+    acc[4][j] += dv * dv;
+    acc[5][j] += (ok && g > a.thresh) ? 1.0f : 0.0f;
+  }
+  float tot[6][3];
+#pragma unroll
+  for (int q = 0; q < 6; ++q)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tot[q][c] = wave_total(slot_to_channel(acc[q], m.l3, c));
+  // ---- the rows: I_r(d) for the mse stat under use_itof; for the iToF types the loss and sum_r 2 I_r(x) W_r[b]
+  float g[kPerLane];
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) g[k] = 0.0f;
+  float rows_loss[3] = {0.0f, 0.0f, 0.0f}, rows_mse[3] = {0.0f, 0.0f, 0.0f};
+  if (rows_used) {
+#pragma unroll 1
+    for (int r = 0; r < ka.n_rows; ++r) {
+      const float* w = sW + r * kB;
+      float Id[3], Ix[3];
+      itof_row(w, m, d, Id);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rows_mse[c] += Id[c] * Id[c];
+      if (itof_kind) {
+        if (unbiased) {
+          itof_row(w, m, dn, Ix);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) rows_loss[c] += 2.0f * (Id[c] * Ix[c]);
+        } else {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) { Ix[c] = Id[c]; rows_loss[c] += Id[c] * Id[c]; }
+        }
+        float A[3], As[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) A[c] = 2.0f * Ix[c];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) As[j] = channel_to_slot(A, m.l3, j);
+#pragma unroll
+        for (int k = 0; k < kPerLane; ++k) g[k] += As[k % 3] * w[lane_bin(m, k)];
+      }
+    }
+  }
+  const float lm0 = a.lossmult ? a.lossmult[ray] : 1.0f;
+  float gmul[3], gadd[3], loss = 0.0f, mse = 0.0f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float lm = tot[5][c] > 0.0f ? 0.0f : lm0;                       // train_utils.py:586-590
+    float s = 1.0f;
+    if (rawnerf) {
+      const float p = a.exponent == 1.0f ? tot[0][c] : powf(tot[0][c], a.exponent);
+      s = 1.0f / (p + a.eps);                                             // train_utils.py:217
+    }
+    // the gauss constant row of the two per-bin rawnerf types: on every bin gauss sum x (x = dn or d), counted once
+    const float sum_x = unbiased ? tot[2][c] : tot[1][c];
+    gadd[c] = gauss_row ? a.gauss * sum_x : 0.0f;
+    float L;
+    if (itof_kind) L = rows_loss[c];
+    else if (unbiased) L = 2.0f * tot[3][c] + gadd[c] * tot[1][c];
+    else L = tot[4][c] + 0.5f * (gadd[c] * tot[1][c]);
+    loss += (lm * (s * L)) * ka.q;
+    mse += lm * (ka.use_itof ? rows_mse[c] / (float)ka.n_rows : tot[4][c]);
+    gmul[c] = (a.coef * (lm * s)) * ka.q;
+  }
+  if (ray_ok && lane == 0) { a.loss_ray[ray] = loss; a.loss_ray[a.n + ray] = mse; }
+  float gms[3], gas[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { gms[j] = channel_to_slot(gmul, m.l3, j); gas[j] = channel_to_slot(gadd, m.l3, j); }
+  float* sg = sG[wave];
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) {
+    const int e = lane + 64 * k;
+    if (e < kH) {
+      const float x = unbiased ? dn[k] : d[k];
+      const float v = gms[k % 3] * (itof_kind ? g[k] : 2.0f * x + gas[k % 3]);
+      sg[e] = v;
+      if (ray_ok) a.G[ray * kH + e] = v;
+    }
+  }
+  __syncthreads();
+  // the temporal filter's transpose, as k_transient_loss
+  const int half = (a.n_taps - 1) / 2;
+  for (int e = lane; e < kH; e += 64) {
+    float v;
+    if (a.n_taps > 0) {
+      v = 0.0f;
+      for (int k = 0; k < a.n_taps; ++k) {
+        const int j = e + 3 * (k - half);
+        if (j >= 0 && j < kH) v += a.taps[k] * sg[j];
+      }
+    } else {
+      v = sg[e];
+    }
+    if (ray_ok) a.Gt[ray * kH + e] = v;
+  }
+}
+
+// render_utils.dtof_to_itof: x [n][kB][3] -> out [n][n_rows][3], one wavefront per ray
+__global__ __launch_bounds__(kWavesPerBlock * 64) void k_dtof_to_itof(RcDtofToItofArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sW[];      // [n_rows][kB]
+  stage_itof_table(sW, a.W, a.n_rows);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const LaneMap m = lane_map(lane);
+  int64_t ray = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  const bool ray_ok = ray < a.n;
+  if (!ray_ok) ray = a.n - 1;
+  const float* x = a.x + ray * kH;
+  float v[kPerLane];
+#pragma unroll
+  for (int k = 0; k < kPerLane; ++k) {
+    const bool ok = lane_entry_ok(lane, k);
+    const float t = x[ok ? lane + 64 * k : 0];
+    v[k] = ok ? t : 0.0f;
+  }
+#pragma unroll 1
+  for (int r = 0; r < a.n_rows; ++r) {
+    float I[3];
+    itof_row(sW + r * kB, m, v, I);
+    if (ray_ok && lane == 0) {
+      float* o = a.out + (ray * a.n_rows + r) * 3;
+      o[0] = I[0]; o[1] = I[1]; o[2] = I[2];
+    }
+  }
+}
+
+constexpr int kItofLdsBytes = (2 * RC_ITOF_MAX_PAIRS + 1) * kB * (int)sizeof(float);
+
 }  // namespace
+
+void rc_launch_transient_loss_kinds(const RcTransLossKindArgs& a, hipStream_t st) {
+  if (a.base.n <= 0) return;
+  static std::atomic<uint64_t> prepared{0};
+  if (rc_first_use_on_device(prepared))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transient_loss_kinds), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              kItofLdsBytes);
+  const bool rows_used = a.kind >= RC_TLOSS_MSE_ITOF || a.use_itof != 0;
+  const int lds = rows_used ? a.n_rows * kB * (int)sizeof(float) : 0;
+  hipLaunchKernelGGL(k_transient_loss_kinds, dim3((unsigned)((a.base.n + kWavesPerBlock - 1) / kWavesPerBlock)),
+                     dim3(kWavesPerBlock * 64), lds, st, a);
+}
+
+void rc_launch_dtof_to_itof(const RcDtofToItofArgs& a, hipStream_t st) {
+  if (a.n <= 0) return;
+  static std::atomic<uint64_t> prepared{0};
+  if (rc_first_use_on_device(prepared))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dtof_to_itof), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              kItofLdsBytes);
+  hipLaunchKernelGGL(k_dtof_to_itof, dim3((unsigned)((a.n + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kWavesPerBlock * 64),
+                     a.n_rows * kB * (int)sizeof(float), st, a);
+}
 
 void rc_launch_transient_loss(const RcTransLossArgs& a, hipStream_t st) {
   if (a.n <= 0) return;

@@ -1,6 +1,6 @@
-// Host side of rc_transient_data_backward (rc_transient_bwd.hip); included by rc_api.hip.
+// Host side of rc_transient_data_backward, rc_transient_data_backward_kind and rc_dtof_to_itof (rc_transient_bwd.hip); included by rc_api.hip.
 //
-// One call = rc_render_transient itself (its "rgb" histograms to "td:rgb") -> k_transient_loss (G, the filter's transpose
+// One call = rc_render_transient itself (its "rgb" histograms to "td:rgb") -> k_transient_loss[_kinds] (G, the filter's transpose
 // Gt, the per-ray loss and mse sums) -> k_interlevel_reduce (the two scalars, fixed order) -> per chunk of kRcTdChunkRays
 // rays: k_transient_bins_bwd (the integrator's adjoint, the heads' recompute, dZ of both heads into the chunk's buffers,
 // the per-sample adjoints) and, on k_gemm_tile, dX = dZ W^T of both heads into "td:d_t_irr" / "td:d_t_slf" and, with a
@@ -27,14 +27,13 @@ int upload_transient_heads(rc_handle* h, const std::vector<GradSeg>& segs) {
   return upload(h, h->thead_w, v);
 }
 
-}  // namespace
+int check_transient_loss_kind(rc_handle* h, const std::string& who, const rc_transient_data_loss_kind* kind);
+int launch_transient_loss(rc_handle* h, const rc_transient_data_loss_kind* kind, const RcTransLossArgs& la, hipStream_t st);   // below
 
-int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
-                               const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
-                               const rc_transient_data_loss* cfg, float* head_grads, float* losses, void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  const std::string who = "rc_transient_data_backward";
+// Both entries: `kind` is null for rc_transient_data_backward.  Steps 1 and 3 do not depend on it.
+int transient_data_backward_impl(rc_handle* h, const std::string& who, const rc_rays* rays, const float* cam_origins, int64_t n,
+                                 const rc_randoms* rnd, const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                                 const rc_transient_data_loss* cfg, const rc_transient_data_loss_kind* kind, float* head_grads, float* losses, void* stream_v) {
   if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs a time-resolved cache handle (rc_set_transient)");
   if (h->tcfg.use_occlusions) return fail(h, RC_ERR_UNSUPPORTED, who + ": the occlusion variant is not offered (a vis_only feature)");
   if (!rays || !cfg) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/cfg");
@@ -42,6 +41,7 @@ int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* c
   if (!std::isfinite(cfg->mult) || !std::isfinite(cfg->gauss_mult) || !std::isfinite(cfg->gauss_constant_scale) ||
       !std::isfinite(cfg->exponent) || !std::isfinite(cfg->eps) || !std::isfinite(cfg->clip_val) || !(cfg->thresh == cfg->thresh))
     return fail(h, RC_ERR_INVALID_ARG, who + ": the loss constants must be finite, thresh not NaN");
+  if (int rc = check_transient_loss_kind(h, who, kind)) return rc;
   if (n == 0) return RC_OK;
   if (!gt || !losses) return fail(h, RC_ERR_INVALID_ARG, who + ": null gt/losses");
   const rc_transient_config& t = h->tcfg;
@@ -51,7 +51,7 @@ int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* c
   if (t.n_bins != kRcTdBins || segs[0].shape[0] != 64 || segs[0].shape[1] != kRcTdHist || segs[2].shape[0] != 128 ||
       segs[2].shape[1] != kRcTdHist + 1)
     return fail(h, RC_ERR_UNSUPPORTED, who + ": unexpected head widths");
-  RoctxScope roctx_call("rc_transient_data_backward");
+  RoctxScope roctx_call(who.c_str());
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   int rc;
@@ -82,7 +82,7 @@ int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* c
   la.exponent = cfg->exponent; la.eps = cfg->eps; la.clip_val = cfg->clip_val; la.thresh = cfg->thresh;
   la.use_gt = cfg->use_gt_rawnerf != 0; la.use_combined = cfg->use_combined_rawnerf != 0;
   la.G = y.G.p; la.Gt = y.Gt.p; la.loss_ray = y.loss_ray.p;
-  rc_launch_transient_loss(la, st);
+  if ((rc = launch_transient_loss(h, kind, la, st))) return rc;      // k_transient_loss or k_transient_loss_kinds
   RcInterlevelReduce rr{};
   rr.mult[0] = rr.mult[1] = cfg->mult; rr.count[0] = rr.count[1] = 3.0 * (double)n;
   rc_launch_interlevel_reduce(y.loss_ray.p, n, 2, rr, losses, st);
@@ -126,6 +126,103 @@ int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* c
     }
     RC_HIP(h, hipGetLastError());
   }
+  return RC_OK;
+}
+
+// The modulation table of (n_pairs, frequency, phase_shift) at the handle's exposure_time in h->itof_w: built and uploaded
+// when the pairs or the exposure_time differ from the cached ones.  The calls that read the previous table are waited for.
+int ensure_itof_table(rc_handle* h, int n_pairs, const double* frequency, const double* phase_shift, hipStream_t st) {
+  std::vector<double> key{(double)h->tcfg.exposure_time};
+  for (int p = 0; p < n_pairs; ++p) { key.push_back(frequency[p]); key.push_back(phase_shift[p]); }
+  if (h->itof_w.p && key == h->itof_key) return RC_OK;
+  RC_HIP(h, hipStreamSynchronize(st));
+  h->itof_key.clear();
+  if (int rc = upload(h, h->itof_w, rc_itof_table(kRcTdBins, (double)h->tcfg.exposure_time, n_pairs, frequency, phase_shift)))
+    return rc;
+  h->itof_key = key;
+  return RC_OK;
+}
+
+int check_itof_pairs(rc_handle* h, const std::string& who, int n_pairs, const double* frequency, const double* phase_shift) {
+  if (n_pairs < 0 || n_pairs > RC_ITOF_MAX_PAIRS)
+    return fail(h, RC_ERR_INVALID_ARG, who + ": n_pairs outside [0, RC_ITOF_MAX_PAIRS]");
+  if (n_pairs > 0 && (!frequency || !phase_shift)) return fail(h, RC_ERR_INVALID_ARG, who + ": null frequency/phase_shift");
+  for (int p = 0; p < n_pairs; ++p)
+    if (!std::isfinite(frequency[p]) || !std::isfinite(phase_shift[p]))
+      return fail(h, RC_ERR_INVALID_ARG, who + ": the frequencies and phase shifts must be finite");
+  return RC_OK;
+}
+
+// The refusals of rc_transient_data_backward_kind's own fields (nothing is launched); no kind, nothing to refuse.
+int check_transient_loss_kind(rc_handle* h, const std::string& who, const rc_transient_data_loss_kind* kind) {
+  if (!kind) return RC_OK;
+  if (kind->loss_type < 0 || kind->loss_type >= RC_TLOSS_COUNT) return fail(h, RC_ERR_INVALID_ARG, who + ": unknown loss_type");
+  return check_itof_pairs(h, who, kind->n_pairs, kind->frequency, kind->phase_shift);
+}
+
+// Step 2's kernel: the default reading goes to k_transient_loss whichever entry asks for it (bitwise the same results),
+// every other one to k_transient_loss_kinds with the modulation table where it is read.
+int launch_transient_loss(rc_handle* h, const rc_transient_data_loss_kind* kind, const RcTransLossArgs& la, hipStream_t st) {
+  if (!kind || (kind->loss_type == RC_TLOSS_RAWNERF_TRANSIENT_UNBIASED && !kind->use_itof)) {
+    rc_launch_transient_loss(la, st);
+    return RC_OK;
+  }
+  RcTransLossKindArgs ka{};
+  ka.base = la; ka.kind = kind->loss_type; ka.use_itof = kind->use_itof != 0;
+  ka.n_rows = 2 * kind->n_pairs + 1;
+  const bool itof_kind = kind->loss_type >= RC_TLOSS_MSE_ITOF;
+  ka.q = kind->use_itof ? (float)(1.0 / (double)(itof_kind ? ka.n_rows : kRcTdBins)) : 1.0f;      // train_utils.py:622-623
+  if (itof_kind || kind->use_itof) {
+    if (int rc = ensure_itof_table(h, kind->n_pairs, kind->frequency, kind->phase_shift, st)) return rc;
+    ka.W = h->itof_w.p;
+  }
+  rc_launch_transient_loss_kinds(ka, st);
+  return RC_OK;
+}
+
+}  // namespace
+
+int rc_transient_data_backward(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                               const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                               const rc_transient_data_loss* cfg, float* head_grads, float* losses, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  return transient_data_backward_impl(h, "rc_transient_data_backward", rays, cam_origins, n, rnd, gt, rgb_nocorr, gt_nocorr,
+                                      lossmult, cfg, nullptr, head_grads, losses, stream_v);
+  RC_CATCH(h)
+}
+
+int rc_transient_data_backward_kind(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                                    const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                                    const rc_transient_data_loss_kind* cfg, float* head_grads, float* losses, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_transient_data_backward_kind";
+  // a null cfg: the handle's refusals first, as the other entry orders them
+  if (!cfg && h->transient && !h->tcfg.use_occlusions) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/cfg");
+  return transient_data_backward_impl(h, who, rays, cam_origins, n, rnd, gt, rgb_nocorr, gt_nocorr, lossmult,
+                                      cfg ? &cfg->base : nullptr, cfg, head_grads, losses, stream_v);
+  RC_CATCH(h)
+}
+
+int rc_dtof_to_itof(rc_handle* h, const float* dtof, int64_t n, int32_t n_pairs, const double* frequency,
+                    const double* phase_shift, float* itof, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_dtof_to_itof";
+  if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs a time-resolved cache handle (rc_set_transient)");
+  if (h->tcfg.n_bins != kRcTdBins) return fail(h, RC_ERR_UNSUPPORTED, who + ": unexpected n_bins");
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n");
+  if (int rc = check_itof_pairs(h, who, n_pairs, frequency, phase_shift)) return rc;
+  if (n == 0) return RC_OK;
+  if (!dtof || !itof) return fail(h, RC_ERR_INVALID_ARG, who + ": null dtof/itof");
+  RC_HIP(h, hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream_v;
+  if (int rc = ensure_itof_table(h, n_pairs, frequency, phase_shift, st)) return rc;
+  RcDtofToItofArgs a{};
+  a.n = n; a.n_rows = 2 * n_pairs + 1; a.W = h->itof_w.p; a.x = dtof; a.out = itof;
+  rc_launch_dtof_to_itof(a, st);
+  RC_HIP(h, hipGetLastError());
   return RC_OK;
   RC_CATCH(h)
 }

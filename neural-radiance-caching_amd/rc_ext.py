@@ -216,6 +216,47 @@ class rc_transient_data_loss(C.Structure):
                 ("use_combined_rawnerf", C.c_int32)]
 
 
+# rc_transient_loss_type -> name; order must match include/rc_abi.h
+TRANSIENT_LOSS_TYPES = ("rawnerf_transient_unbiased", "rawnerf_transient", "mse", "mse_unbiased", "mse_itof", "mse_itof_unbiased",
+                        "rawnerf_transient_itof", "rawnerf_transient_itof_unbiased")
+RC_TLOSS_COUNT = len(TRANSIENT_LOSS_TYPES)
+RC_ITOF_MAX_PAIRS = 8
+
+
+class rc_transient_data_loss_kind(C.Structure):
+    _fields_ = [("base", rc_transient_data_loss), ("loss_type", C.c_int32), ("use_itof", C.c_int32), ("n_pairs", C.c_int32),
+                ("pad", C.c_int32), ("frequency", C.c_double * RC_ITOF_MAX_PAIRS), ("phase_shift", C.c_double * RC_ITOF_MAX_PAIRS)]
+
+
+def _itof_pairs(pairs):
+    """[(frequency, phase)] floats of Config.itof_frequency_phase_shifts; more than RC_ITOF_MAX_PAIRS is refused here,
+    where the C struct could not hold them."""
+    pairs = [(float(f), float(ph)) for f, ph in pairs]
+    if len(pairs) > RC_ITOF_MAX_PAIRS:
+        raise ValueError(f"at most {RC_ITOF_MAX_PAIRS} (frequency, phase) pairs")
+    return pairs
+
+
+def transient_data_loss_c(cfg) -> rc_transient_data_loss:
+    """The constants of a config.TransientDataLossConfig that every loss type shares."""
+    return rc_transient_data_loss(mult=float(cfg.data_loss_mult), gauss_mult=float(cfg.data_loss_gauss_mult),
+                                  gauss_constant_scale=float(cfg.transient_gauss_constant_scale),
+                                  exponent=float(cfg.rawnerf_exponent), eps=float(cfg.rawnerf_eps),
+                                  clip_val=float(cfg.clip_val), thresh=float(cfg.loss_thresh),
+                                  use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
+                                  use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)))
+
+
+def transient_data_loss_kind_c(cfg) -> rc_transient_data_loss_kind:
+    """rc_transient_data_backward_kind's struct of a config.TransientDataLossConfig."""
+    pairs = _itof_pairs(cfg.itof_frequency_phase_shifts)
+    ck = rc_transient_data_loss_kind(base=transient_data_loss_c(cfg), loss_type=TRANSIENT_LOSS_TYPES.index(cfg.loss_type),
+                                     use_itof=int(bool(cfg.use_itof)), n_pairs=len(pairs))
+    for i, (f, ph) in enumerate(pairs):
+        ck.frequency[i], ck.phase_shift[i] = f, ph
+    return ck
+
+
 # rc_eval_slot -> name; order must match include/rc_abi.h
 EVAL_SLOTS = ("mse", "psnr", "ssim", "transient_iou", "l1_mean", "l1_median", "mae")
 RC_EVAL_COUNT = len(EVAL_SLOTS)
@@ -333,6 +374,9 @@ _PROTOTYPES = {
                                                 C.POINTER(rc_material_data_loss), _F, _P, _P, _P, _P]),
     "rc_transient_data_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P, C.POINTER(rc_transient_data_loss),
                                              _P, _P, _P]),
+    "rc_transient_data_backward_kind": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P,
+                                                  C.POINTER(rc_transient_data_loss_kind), _P, _P, _P]),
+    "rc_dtof_to_itof": (C.c_int, [_H, _P, _I64, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),
     "rc_eval_image": (C.c_int, [_H, C.POINTER(rc_eval_images), _P, _P]),
     "rc_eval_albedo": (C.c_int, [_H, C.POINTER(rc_albedo_images), _P, _P]),
     "rc_albedo_ratio": (C.c_int, [_H, _P, _I64, _P, _I32, _I32, _P, _P]),
@@ -1269,18 +1313,24 @@ class RadianceCache:
 
     def transient_data_backward(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]], gt, rgb_nocorr=None,
                                 gt_nocorr=None, lossmult=None, cfg=None, grad=None, stream_handle=None):
-        """rc_transient_data_backward: render_transient with the same rays (lights and cam_origins included) / randoms
-        ({"jitter": [u0, u1, u2]} or None), the time-resolved data loss against gt ([n, n_bins, 3]) with the constants of
-        cfg (config.TransientDataLossConfig) and its gradient w.r.t. the two per-bin head layers
-        (transient_head_grad_layout).  rgb_nocorr / gt_nocorr: [n, n_bins, 3] or None (this render, gt).
-        grad: flat buffer to accumulate into (allocated zeroed when None); grad=False leaves the heads' gradient out (the
-        loss and the "td:" adjoints are still computed).  Returns (grad flat or None, losses [2] cuda tensor: loss, mse)."""
+        """rc_transient_data_backward / rc_transient_data_backward_kind: render_transient with the same rays (lights and
+        cam_origins included) / randoms ({"jitter": [u0, u1, u2]} or None), the time-resolved data loss against gt
+        ([n, n_bins, 3]) with the constants of cfg (config.TransientDataLossConfig; config.transient_data_loss_preset names
+        the gins' readings) and its gradient w.r.t. the two per-bin head layers (transient_head_grad_layout; DESIGN.md
+        §4.15).  cfg.loss_type is one of TRANSIENT_LOSS_TYPES; cfg.use_itof and cfg.itof_frequency_phase_shifts
+        ((frequency, phase) pairs, at most RC_ITOF_MAX_PAIRS) as the reference's Config.  The default reading goes through
+        the first export, every other one through the second.  rgb_nocorr / gt_nocorr: [n, n_bins, 3] or None (this render,
+        gt).  grad: flat buffer to accumulate into (allocated zeroed when None); grad=False leaves the heads' gradient out
+        (the loss and the "td:" adjoints are still computed).  Returns (grad flat or None, losses [2] cuda tensor: loss,
+        mse)."""
         from .config import TransientDataLossConfig
 
         cfg = TransientDataLossConfig() if cfg is None else cfg
-        if (cfg.loss_type != "rawnerf_transient_unbiased" or tuple(cfg.transient_gauss_sigma_scales) or cfg.mask_lossmult
-                or cfg.clip_eval or cfg.use_itof):
-            raise NotImplementedError("transient data loss: only rawnerf_transient_unbiased with the constant gauss row")
+        if (cfg.loss_type not in TRANSIENT_LOSS_TYPES or tuple(cfg.transient_gauss_sigma_scales) or cfg.mask_lossmult
+                or cfg.clip_eval):
+            raise NotImplementedError(f"transient data loss: loss_type is one of {TRANSIENT_LOSS_TYPES}, with the constant gauss "
+                                      "row only (no sigma scales), without mask_lossmult and clip_eval")
+        plain = cfg.loss_type == TRANSIENT_LOSS_TYPES[0] and not cfg.use_itof
         r, held, n = self._rays_struct(rays)
         cam = self._dev(rays["cam_origins"]).reshape(-1, 3)
         held["cam_origins"] = cam
@@ -1301,17 +1351,37 @@ class RadianceCache:
         gt_p, rn_p, gn_p = hist(gt, "gt"), hist(rgb_nocorr, "rgb_nocorr"), hist(gt_nocorr, "gt_nocorr")
         if gt_p is None:
             raise ValueError("gt is required")
-        c = rc_transient_data_loss(mult=float(cfg.data_loss_mult), gauss_mult=float(cfg.data_loss_gauss_mult),
-                                   gauss_constant_scale=float(cfg.transient_gauss_constant_scale),
-                                   exponent=float(cfg.rawnerf_exponent), eps=float(cfg.rawnerf_eps),
-                                   clip_val=float(cfg.clip_val), thresh=float(cfg.loss_thresh),
-                                   use_gt_rawnerf=int(bool(cfg.use_gt_rawnerf)),
-                                   use_combined_rawnerf=int(bool(cfg.use_combined_rawnerf)))
+        c = transient_data_loss_c(cfg)
         flat, losses, stream = self._loss_prologue("transient_heads", grad, stream_handle, slots=2)
-        self._check(self.lib.rc_transient_data_backward(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, gt_p, rn_p, gn_p,
-                                                        _ptr(lm), C.byref(c), _ptr(flat), losses.data_ptr(), stream))
+        if plain:
+            self._check(self.lib.rc_transient_data_backward(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, gt_p, rn_p, gn_p,
+                                                            _ptr(lm), C.byref(c), _ptr(flat), losses.data_ptr(), stream))
+        else:
+            ck = transient_data_loss_kind_c(cfg)
+            self._check(self.lib.rc_transient_data_backward_kind(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, gt_p, rn_p,
+                                                                 gn_p, _ptr(lm), C.byref(ck), _ptr(flat), losses.data_ptr(),
+                                                                 stream))
         self._keep = [held]
         return flat, losses
+
+    def dtof_to_itof(self, x, pairs, stream_handle=None):
+        """rc_dtof_to_itof (render_utils.dtof_to_itof): x [n, n_bins, 3] histograms (a cuda tensor is used where it is) ->
+        cuda tensor [n, 2 P + 1, 3]: per (frequency, phase) pair of `pairs` the cos row and the sin row, then the constant
+        row (half the bin sum: the steady-state image), with the handle's exposure_time."""
+        torch = self._torch
+        pairs = _itof_pairs(pairs)
+        t = self._dev(x)
+        if self.cfg.transient is not None and (t.dim() != 3 or tuple(t.shape[1:]) != (self.cfg.transient.n_bins, 3)):
+            raise ValueError("x must be [n, n_bins, 3]")
+        t = t.contiguous()
+        n, P = int(t.shape[0]), len(pairs)
+        out = torch.empty((n, 2 * P + 1, 3), dtype=torch.float32, device=t.device)
+        f = (C.c_double * max(P, 1))(*[p[0] for p in pairs])
+        ph = (C.c_double * max(P, 1))(*[p[1] for p in pairs])
+        stream = self._stream(stream_handle)
+        self._check(self.lib.rc_dtof_to_itof(self._h, t.data_ptr(), n, P, f, ph, out.data_ptr(), stream))
+        self._keep = [t]
+        return out
 
     # -- evaluation of a rendered view ------------------------------------------------------------------
     def eval_image(self, pred, gt, mask=None, acc=None, normals=None, normals_gt=None, distance_mean=None,

@@ -73,9 +73,12 @@ The material network, second piece of that stage:
 The time-resolved cache, first piece of its training:
 
   * `transient_data_grads(rc, rays, cam_origins, jitters, gt, ...)` -> the transient data loss
-    (train_utils.compute_transient_data_loss, 'rawnerf_transient_unbiased') of rc_render_transient's histograms and the exact
-    gradient of the two per-bin head layers (rc_transient_data_backward); the adjoints at the rest of the shader stay in
-    the handle's "td:" workspace;
+    (train_utils.compute_transient_data_loss) of rc_render_transient's histograms and the exact gradient of the two per-bin
+    head layers; the adjoints at the rest of the shader stay in the handle's "td:" workspace.  cfg picks the reading:
+    'rawnerf_transient_unbiased' by default (rc_transient_data_backward), or through rc_transient_data_backward_kind the
+    per-bin types 'rawnerf_transient', 'mse', 'mse_unbiased' and the iToF types 'mse_itof', 'rawnerf_transient_itof' and
+    their unbiased forms, with or without use_itof -- config.transient_data_loss_preset("cornell_itof"), "steady_state",
+    "mse", ... name the gins' readings;
   * `TransientHeadOptimizer(rc, cfg)` / `transient_head_step(...)` -> the optimizer state and step on that layout
     (transient_indirect_layer in group "Cache", SurfaceLightField/output_rgba_layer in group "SurfaceLightField").
 """
@@ -746,8 +749,9 @@ def material_env_stage_step(rc, opt_material: MaterialOptimizer, opt_envmap: Env
 def transient_data_grads(rc, rays, cam_origins, jitters, gt, rgb_nocorr=None, gt_nocorr=None, lossmult=None, flat=None,
                          cfg: TransientDataLossConfig = TransientDataLossConfig()):
     """The time-resolved cache's data loss on a batch and its gradient of the two per-bin head layers:
-    compute_transient_data_loss of rc_render_transient's rgb against gt ([n, n_bins, 3]) times data_loss_mult, accumulated
-    into `flat` (layout rc.transient_head_grad_layout(); allocated zeroed when None).  rays: render_transient's fields
+    compute_transient_data_loss of rc_render_transient's rgb against gt ([n, n_bins, 3]) times data_loss_mult, under the loss
+    type, use_itof and (frequency, phase) pairs of cfg (config.transient_data_loss_preset; an iToF or steady-state reading
+    compares dtof_to_itof of the histograms, gt stays a histogram), accumulated into `flat` (layout rc.transient_head_grad_layout(); allocated zeroed when None).  rays: render_transient's fields
     (lights included); cam_origins: [n, 3] (replaces rays["cam_origins"] when given); jitters: per-level [n] sampler jitter
     (None = deterministic); rgb_nocorr / gt_nocorr: the unbiased loss's second pair (None: this render, gt).
     -> (flat, {"data": ..., "mse": ...}), 0-d cuda tensors: the reference's losses_flat key and its "mses" stat."""
@@ -777,7 +781,8 @@ class TransientHeadOptimizer(CacheStageOptimizer):
 def transient_head_step(rc, opt: TransientHeadOptimizer, rays, cam_origins, jitters, gt, rgb_nocorr=None, gt_nocorr=None,
                         lossmult=None, group=None, cfg: TransientDataLossConfig = TransientDataLossConfig()):
     """One train step of the per-bin heads on the transient data loss: transient_data_grads into the optimizer's zeroed
-    gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().  -> the losses dict of
+    gradient buffer, the pmean over `group` when torch.distributed runs, then opt.step().  cfg: the loss reading, as
+    transient_data_grads takes it (any of config.transient_data_loss_preset's).  -> the losses dict of
     transient_data_grads."""
     return _train_step(opt, group, lambda tf: transient_data_grads(rc, rays, cam_origins, jitters, gt, rgb_nocorr, gt_nocorr,
                                                                    lossmult, opt.grads["transient_heads"], cfg))
