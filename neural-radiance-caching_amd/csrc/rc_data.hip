@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(256) k_shader_glue_fwd(RcShaderBwdArgs a) {
     if (m < mcur) { cre = 1.0f; cim = 0.0f; mcur = 0; }
     while (mcur < m) { const float nr = cre * o.rx - cim * o.ry; cim = cre * o.ry + cim * o.rx; cre = nr; ++mcur; }
     float poly = 0.0f, zp = 1.0f;
-    for (int k = 0; k < RC_IDE_ZPOW; ++k) { poly += a.ide->coef[i][k] * zp; zp *= o.rz; }
+    for (int k = 0; k < RC_IDE_ZPOW; ++k) { poly += kRcIdeCoef[i][k] * zp; zp *= o.rz; }
     const float att = expf(-a.ide->sigma[i] * o.rough);
     ide[i] = cre * poly * att;
     ide[RC_IDE_TERMS + i] = cim * poly * att;

@@ -146,11 +146,28 @@ typedef __attribute__((address_space(3))) void* lds_void_ptr;
 struct WStream {
   const float* g;    // packed fragment stream (padded to a whole number of chunks)
   float* ring;       // LDS ring [2 * kChunk][64]
-  int lane, wave;
+  int lane, wave;    // wave: a scalar register (readfirstlane in the constructor)
+  uint32_t voff;     // bytes from the start of a group of W pieces to this lane's 16 bytes of the wave's piece
+  float* ringw;      // the wave's piece of the ring's first group (scalar)
   mutable f32x4 sink = {0.0f, 0.0f, 0.0f, 0.0f};     // split form: destination of the flush MFMAs (see INSTABILITY above), never read
   __device__ WStream() = default;
-  __device__ WStream(const float* g_, float* ring_, int lane_, int wave_) : g(g_), ring(ring_), lane(lane_), wave(wave_) {}
+  __device__ WStream(const float* g_, float* ring_, int lane_, int wave_)
+      : g(g_), ring(ring_), lane(lane_), wave(__builtin_amdgcn_readfirstlane(wave_)), voff((uint32_t)(wave * 256 + lane_ * 4) * 4u), ringw(ring_ + wave * 256) {}
 };
+
+// The LDS-DMA of this wave's 1-KiB piece of the group of W pieces that starts at fragment `frag` of the stream and at
+// fragment `slot` of the ring.  The address setup is what a piece costs besides the load itself, so it is kept to two
+// instructions: the source is the stream's scalar base plus ONE 32-bit vector offset (the per-lane part w.voff, set up
+// once, plus the group's offset: a stream is far below 4 GiB), the destination (M0) scalar arithmetic on the wave index.
+// No 64-bit vector add and no readfirstlane per piece.
+// A group is issued whole or not at all (the callers test its first fragment against the kernel's fragment count, at
+// compile time): what lies behind the last fragment is the zero padding of the stream (whole chunks, rc_api.hip
+// pad_stream), which lands in ring slots that nobody reads.
+__device__ __forceinline__ void ws_issue_piece(const WStream& w, int frag, int slot) {
+  const char* src = reinterpret_cast<const char*>(w.g) + (w.voff + (uint32_t)frag * 256u);
+  float* dst = w.ringw + slot * 64;
+  __builtin_amdgcn_global_load_lds((const void*)src, (lds_void_ptr)dst, 16, 0, 0);
+}
 
 // Issue the LDS-DMA of chunk c (this wave's quarter: 4 x 1 KiB).
 // CH: fragments per chunk of this kernel's ring (kChunk by default; the EnvMap kernel runs a 2 x 8 KiB ring).
@@ -159,13 +176,8 @@ __device__ __forceinline__ void ws_issue(const WStream& w, int c) {
   static_assert(CH % (4 * W) == 0, "whole 1-KiB pieces per wave");
 #pragma unroll
   for (int k = 0; k < CH / 4 / W; ++k) {
-    const int i = w.wave + W * k;                  // 1-KiB piece inside the chunk
-    const int frag0 = c * CH + 4 * i;
-    if (frag0 < NF) {
-      const float* src = w.g + (size_t)frag0 * 64 + w.lane * 4;
-      float* dst = w.ring + ((c & 1) * CH + 4 * i) * 64;
-      __builtin_amdgcn_global_load_lds((const void*)src, (lds_void_ptr)dst, 16, 0, 0);
-    }
+    const int g0 = 4 * W * k;                      // group of W 1-KiB pieces inside the chunk, piece w.wave of it is ours
+    if (c * CH + g0 < NF) ws_issue_piece(w, c * CH + g0, (c & 1) * CH + g0);
   }
 }
 
@@ -174,7 +186,10 @@ __device__ __forceinline__ void ws_begin(const WStream& w) {
   ws_issue<NF, W, CH>(w, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+  // the pieces go out as one burst: the kernel's own first loads and their address arithmetic stay behind them
+  __builtin_amdgcn_sched_barrier(0);
   if (CH < NF) ws_issue<NF, W, CH>(w, 1);
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 // Entering chunk c: it has landed (issued one chunk ago), everybody is done with chunk c-1.
@@ -645,7 +660,7 @@ struct ShadeOut { float rgb[3], ad[3], idf[3], is[3], tint[3]; };
 #endif
 template <int F0, int NF, class WS = WStream>
 __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int lane, int h, float nx, float ny, float nz,
-                                                float vx, float vy, float vz, const RcIdeTable* tb, const ShaderConsts& k,
+                                                float vx, float vy, float vz, const ShaderConsts& k,
                                                 unsigned long long* st = nullptr) {
   RC_TSTAMP(0);
   // ---- small heads tile on the feature (the bottleneck is folded into its consumers, see kShActSteps)
@@ -703,8 +718,8 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
       float poly = 0.0f;
 #pragma unroll
       for (int k = 0; k < RC_IDE_ZPOW; ++k) {
-        // structurally non-zero coefficients only: k <= l - m and (l - m - k) even
-        if (k <= l - m && ((l - m - k) & 1) == 0) poly = poly + zp[k] * tb->coef[i][k];
+        // structurally non-zero coefficients only: k <= l - m and (l - m - k) even; immediates (rc_ide_coef.h)
+        if (k <= l - m && ((l - m - k) & 1) == 0) poly = poly + zp[k] * kRcIdeCoef[i][k];
       }
       const float att = expf(-(0.5f * (float)(l * (l + 1))) * rough);
       act[(kStepIde + i) * 64] = (cpw[m] * poly) * att;

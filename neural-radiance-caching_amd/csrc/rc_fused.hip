@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   float* s_out = scr + 6 * 68;
   typename std::conditional<DIRECT, WDirect, WStream>::type ws;
   if constexpr (DIRECT) { ws.g = a.wstream; ws.lane = lane; }
-  else { ws.g = a.wstream; ws.ring = ring; ws.lane = lane; ws.wave = wave; }
+  else ws = WStream(a.wstream, ring, lane, wave);
 #ifdef RC_STAMPS
   unsigned long long stamps[16];
   const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   for (int c = 0; c < 3; ++c) { so.rgb[c] = act[c * 64]; so.ad[c] = npx; so.idf[c] = npy; so.is[c] = npz; so.tint[c] = density; }
 #else
   const ShadeOut so = shader_tile<F_SH, NF>(ws, act, lane, h, npx, npy, npz, a.viewdirs[3 * ray], a.viewdirs[3 * ray + 1],
-                                            a.viewdirs[3 * ray + 2], reinterpret_cast<const RcIdeTable*>(a.ide_coef), a.sh);
+                                            a.viewdirs[3 * ray + 2], a.sh);
 #endif
 
   RC_FSTAMP(10);

@@ -323,8 +323,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   float* s_out = scr + 6 * 68;
   float* x_dens = scr + 7 * 68;                      // [64] densities of a proposal level, from both waves to wave 0
   float* x_misc = scr + 8 * 68;                      // [32] roughness of the shaded samples, from wave 0 to wave 1
-  WStream ws;
-  ws.g = a.wstream; ws.ring = ring; ws.lane = lane; ws.wave = wave;
+  WStream ws(a.wstream, ring, lane, wave);
 #ifdef RC_STAMPS
   unsigned long long stamps[16];
   unsigned long long tb_wait = 0, tb_count = 0;
@@ -606,7 +605,6 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   // ------------------------------------------------------------------ shader on the 32 samples (rc_dev_mlp.h shader_tile)
   constexpr int F0 = F_SH;
   const float vx = a.viewdirs[3 * ray], vy = a.viewdirs[3 * ray + 1], vz = a.viewdirs[3 * ray + 2];
-  const RcIdeTable* tb = reinterpret_cast<const RcIdeTable*>(a.ide_coef);
   const ShaderConsts& k = a.sh;
   // appearance features to their place behind the hidden feature: [0, 32) hidden | [32, 48) appearance | 48 bias
   if (q == 0) {
@@ -659,7 +657,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
       float poly = 0.0f;
 #pragma unroll
       for (int p = 0; p < RC_IDE_ZPOW; ++p)
-        if (p <= l - m && ((l - m - p) & 1) == 0) poly = poly + zp[p] * tb->coef[i][p];
+        if (p <= l - m && ((l - m - p) & 1) == 0) poly = poly + zp[p] * kRcIdeCoef[i][p];
       ide_v[i] = cpw[m] * poly;
     }
     tw_skip<F0 + ShaderFrags::F_H, rc_lfr(49, 1)>(ws);          // the seams wave 0 crosses inside the heads layer

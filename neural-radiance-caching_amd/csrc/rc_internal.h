@@ -219,6 +219,7 @@ void rc_launch_envmap(const RcEnvMapArgs& a, hipStream_t stream);
 // IDE table layout (built on the host, see rc_api.hip): for deg_view 5 there are 36 (l,m)
 // terms; term i has polynomial coefficients in z of degree <= 16 and an xy power m.
 #include "rc_pack_host.h"      // RC_IDE_TERMS, RC_IDE_ZPOW, RcIdeTable, rc_cell_corner (host-only header)
+#include "rc_ide_coef.h"       // kRcIdeCoef: the table's coefficients as compile-time constants of the kernels
 
 // ---------------------------------------------------------------------------------------------
 // Material stage (rc_material.hip)

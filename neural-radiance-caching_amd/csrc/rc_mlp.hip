@@ -216,7 +216,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_shader(RcShaderArgs a) {
   const ShaderConsts kc{a.roughness_bias, a.irradiance_bias, a.ambient_bias, a.rgb_max, a.slf_ambient_bias};
   const ShadeOut so = shader_tile<0, NF>(ws, act, lane, h, a.normals_pred[q], a.normals_pred[a.n_src + q],
                                         a.normals_pred[2 * a.n_src + q], a.viewdirs[3 * ray], a.viewdirs[3 * ray + 1],
-                                        a.viewdirs[3 * ray + 2], reinterpret_cast<const RcIdeTable*>(a.ide_coef), kc
+                                        a.viewdirs[3 * ray + 2], kc
 #ifdef RC_STAMPS
                                         , stamps + 2
 #endif

@@ -172,7 +172,6 @@ __global__ __launch_bounds__(kWaves * 64) void k_transient_shader(RcTransShaderA
   {
     // IDE of reflect(-v, n) (ref_utils.py:25-42, 155-190), as in shader_tile
     const float rx = 2.0f * dotp * nx - (-vx), ry = 2.0f * dotp * ny - (-vy), rz = 2.0f * dotp * nz - (-vz);
-    const RcIdeTable* tb = reinterpret_cast<const RcIdeTable*>(a.ide_coef);
     float zp[RC_IDE_ZPOW];
     zp[0] = 1.0f;
 #pragma unroll
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_transient_shader(RcTransShaderA
       float poly = 0.0f;
 #pragma unroll
       for (int k = 0; k < RC_IDE_ZPOW; ++k)
-        if (k <= l - m && ((l - m - k) & 1) == 0) poly = poly + zp[k] * tb->coef[i][k];
+        if (k <= l - m && ((l - m - k) & 1) == 0) poly = poly + zp[k] * kRcIdeCoef[i][k];
       const float att = expf(-(0.5f * (float)(l * (l + 1))) * rough);
       act[(T_IDE + i) * 64] = (cpw[m] * poly) * att;
     }
@@ -345,13 +344,8 @@ __device__ __forceinline__ float softplus_hw(float x) {
 __device__ __forceinline__ void ws_issue_rt(const WStream& w, int c, int nf) {
 #pragma unroll
   for (int k = 0; k < kChunk / 4 / kWaves; ++k) {
-    const int i = w.wave + kWaves * k;
-    const int frag0 = c * kChunk + 4 * i;
-    if (frag0 < nf) {
-      const float* src = w.g + (size_t)frag0 * 64 + w.lane * 4;
-      float* dst = w.ring + ((c & 1) * kChunk + 4 * i) * 64;
-      __builtin_amdgcn_global_load_lds((const void*)src, (lds_void_ptr)dst, 16, 0, 0);
-    }
+    const int g0 = 4 * kWaves * k;
+    if (c * kChunk + g0 < nf) ws_issue_piece(w, c * kChunk + g0, (c & 1) * kChunk + g0);
   }
 }
 // fragment J of column tile T of the stream.  T is a run-time value, J a constant once the callers' loops are
