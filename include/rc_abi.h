@@ -549,6 +549,70 @@ typedef enum rc_prng_mode { RC_PRNG_MODE_BITS = 0, RC_PRNG_MODE_UNIFORM = 1, RC_
 int rc_prng_fill(rc_handle* h, const uint32_t key[2], int32_t mode, float minval, float maxval, int64_t n, void* out,
                  void* stream);
 
+/* ---- every random tensor of one material-stage forward from one key, in one launch ------------------------
+ * rc_material_randoms_plan walks the reference's random_split sites of BaseMaterialModel.__call__ on the host (the tree
+ * prng.material_stage_plan restates in Python; csrc/rc_prng_host.h is its C twin) and returns one rc_prng_segment per
+ * jax.random draw: the key, the distribution, the element count and where the tensor lies in ONE arena of 32-bit words.
+ * rc_prng_fill_segments fills the arena in one launch; every value is the rc_prng_fill of the same key, mode and count.
+ * Needs no GPU and no handle.  Like every key path of the package the ORDER of the splits is restated from the source
+ * and is not pinned against a jax run.
+ *
+ * The arena holds the members of rc_randoms / rc_material_randoms in the layout those structs take: sec_jitter[l] is one
+ * block [n Ks | n Kd] (the specular and the diffuse trace's segments are adjacent), sec_gumbel one [n (Ks + Kd), S_last].
+ * The two [m, 2] uniform draws of RandomGenerator2D.sample are split into their columns: even elements go to `offset`
+ * (spec_u1 / cos_u1), odd ones to `offset2` (spec_u2 / cos_u2); everywhere else offset2 is -1.  Members start at
+ * multiples of 64 words.  Sizes: Ks = round(K (1 - f)), Kd = round(K f), Kc = round(Kd / 2), Kl = Kd - Kc with Python's
+ * round (half to even), the host twin's; a K with Ks + Kd != K is RC_ERR_UNSUPPORTED.  A member of zero elements (Kc = 0
+ * at K = 2) keeps its segment, with n = 0.  The two RC_PRNG_MEMBER_PICKS_KEY_* rows of RC_PRNG_PLAN_ENV_SAMPLER carry a
+ * key only (n = 0): the texel draws of rc_render_relight take keys, not tensors. */
+typedef enum rc_prng_member {
+  RC_PRNG_MEMBER_JITTER = 0,          /* + level: rc_randoms.jitter[level] [n]                                       */
+  RC_PRNG_MEMBER_GUMBEL = 8,          /* rc_material_randoms.gumbel [n, S_last]                                      */
+  RC_PRNG_MEMBER_VMF_NOISE = 9,       /* vmf_noise [n, num_vmf, 3]: the PRNGKey(1) constant, RC_PRNG_PLAN_VMF_NOISE  */
+  RC_PRNG_MEMBER_SPEC_U = 10,         /* spec_u1 | spec_u2 [n, Ks] each (two planes)                                 */
+  RC_PRNG_MEMBER_COS_U = 11,          /* cos_u1 | cos_u2 [n, Kc] each (two planes)                                   */
+  RC_PRNG_MEMBER_VMF_LOBE_GUMBEL = 12,/* vmf_lobe_gumbel [n, num_vmf]                                                */
+  RC_PRNG_MEMBER_VMF_V = 13,          /* vmf_v [n, Kl, 2], interleaved                                               */
+  RC_PRNG_MEMBER_VMF_TMP = 14,        /* vmf_tmp [n, Kl]                                                             */
+  RC_PRNG_MEMBER_SPEC_GUMBEL = 15,    /* sec_gumbel rows [0, n Ks)                                                   */
+  RC_PRNG_MEMBER_DIFF_GUMBEL = 16,    /* sec_gumbel rows [n Ks, n (Ks + Kd))                                         */
+  RC_PRNG_MEMBER_NOISE = 17,          /* rc_material_smoothness_backward's noise [n, 3] (loss_key given)             */
+  RC_PRNG_MEMBER_PICKS_KEY_SPEC = 18, /* key of the specular leg's texel draw (n = 0)                                */
+  RC_PRNG_MEMBER_PICKS_KEY_DIFF = 19,
+  RC_PRNG_MEMBER_SPEC_JITTER = 24,    /* + level: sec_jitter[level] elements [0, n Ks)                               */
+  RC_PRNG_MEMBER_DIFF_JITTER = 32     /* + level: sec_jitter[level] elements [n Ks, n (Ks + Kd))                     */
+} rc_prng_member;
+
+typedef struct {
+  uint32_t key[2];
+  int32_t mode;      /* rc_prng_mode */
+  int32_t id;        /* rc_prng_member */
+  float lo, hi;      /* RC_PRNG_MODE_UNIFORM's range (the other modes fix their own) */
+  int64_t n;         /* elements of the tensor jax draws: the counters are cut at half = (n + 1) / 2, as in rc_prng_fill */
+  int64_t offset;    /* word offset in the arena of element 0; two planes: of the even elements */
+  int64_t offset2;   /* -1; two planes: word offset of the odd elements (element i lands at plane[i & 1][i >> 1]) */
+} rc_prng_segment;
+
+#define RC_PRNG_MAX_SEGMENTS 32
+#define RC_PRNG_PLAN_TRAIN        0x1u   /* the secondary traces' sampler jitter from each trace's own key (train=True);
+                                            otherwise from PRNGKey(0), internal/sampling.py:170-179 */
+#define RC_PRNG_PLAN_ENV_SAMPLER  0x2u   /* EnvironmentSampler in both sampler sets (prng.relight_pass_randoms) */
+#define RC_PRNG_PLAN_VMF_NOISE    0x4u   /* add the vmf_noise constant (depends on n alone: callers cache it) */
+
+/* model_key: the rng of the model's __call__; loss_key: the key material_smoothness receives, or NULL (no noise row).
+ * level_samples[n_levels]: samples per sampler level (the last one is S_last).  Writes at most `capacity` rows to segs,
+ * the number of rows to *count and the arena's size in words to *arena_words.  RC_ERR_INVALID_ARG for a NULL pointer,
+ * n_rays < 1, K < 2, a capacity too small or a tensor of 2^32 - 1 elements or more; no rc_last_error (no handle). */
+int rc_material_randoms_plan(const uint32_t model_key[2], const uint32_t* loss_key, int64_t n_rays, int32_t K,
+                             float diffuse_fraction, int32_t num_vmf, const int32_t* level_samples, int32_t n_levels,
+                             uint32_t flags, rc_prng_segment* segs, int32_t capacity, int32_t* count, int64_t* arena_words);
+
+/* Fills every segment of segs[n_segs] into arena (arena_words 32-bit words on the device) in ONE launch on `stream`.
+ * RC_ERR_INVALID_ARG, with nothing launched, for n_segs > RC_PRNG_MAX_SEGMENTS, an unknown mode, a segment of
+ * 2^32 - 1 elements or more, a destination outside [0, arena_words) or two destinations that overlap. */
+int rc_prng_fill_segments(rc_handle* h, const rc_prng_segment* segs, int32_t n_segs, void* arena, int64_t arena_words,
+                          void* stream);
+
 /* ---- training backward of one proposal level's density field ----------------------
  * Replaces, for the parameters of Cache/Sampler/MLP_<level>, the gradients jax.value_and_grad(loss_fn) yields in
  * train_step (internal/train_utils.py:3128-3131) for the sub-graph HashEncoding.__call__

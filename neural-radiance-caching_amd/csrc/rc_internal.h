@@ -885,6 +885,22 @@ struct RcPrngArgs {
   uint32_t* out;
 };
 void rc_launch_prng_fill(const RcPrngArgs& a, hipStream_t stream);
+// Several fills in one launch (k_prng_fill_segments): the table travels in the kernel arguments.  Workgroups
+// [wg_end[s - 1], wg_end[s]) belong to row s; a row of n elements takes ceil(ceil(n / 2) / 256) of them.
+struct RcPrngSegRow {
+  uint32_t key0, key1;
+  int32_t mode;
+  float lo, hi;
+  uint32_t n;
+  int64_t off, off2;             // word offsets in the arena; off2 < 0: one plane
+};
+struct RcPrngSegArgs {
+  RcPrngSegRow seg[RC_PRNG_MAX_SEGMENTS];
+  uint32_t wg_end[RC_PRNG_MAX_SEGMENTS];
+  int32_t n_segs;
+  uint32_t* arena;
+};
+void rc_launch_prng_fill_segments(const RcPrngSegArgs& a, hipStream_t stream);
 
 // Relighting under an explicit environment image (rc_relight.hip; the lookup itself: rc_dev_relight.h)
 struct RcEnvImage { const float* padded; int32_t H, W; };   // [(H + 2)][(W + 2)][4]: zero border, 4th channel zero

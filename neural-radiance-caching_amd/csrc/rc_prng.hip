@@ -62,7 +62,37 @@ __global__ __launch_bounds__(256) void k_prng_fill(RcPrngArgs a) {
   }
 }
 
+// Several fills in one launch: a workgroup finds its row of the table from blockIdx.x alone, so key, mode, range and
+// offsets are wave-uniform; the lane's block is the one k_prng_fill computes for the same key and element count, and its
+// two words go through the same shape_value.  Two planes: element e lands at plane[e & 1][e >> 1].
+__global__ __launch_bounds__(256) void k_prng_fill_segments(RcPrngSegArgs a) {
+  const uint32_t wg = blockIdx.x;
+  int s = 0;
+  while (s < a.n_segs - 1 && wg >= a.wg_end[s]) ++s;
+  const RcPrngSegRow& r = a.seg[s];
+  const uint32_t n = r.n, half = (n >> 1) + (n & 1u);
+  const uint32_t i = (wg - (s ? a.wg_end[s - 1] : 0u)) * 256u + threadIdx.x;
+  if (i >= half) return;
+  const uint32_t e1 = i + half;                                  // < 2^32 - 1: no wrap
+  uint32_t x0 = i;
+  uint32_t x1 = e1 < n ? e1 : 0u;                                // odd n: zero pad
+  threefry2x32(r.key0, r.key1, x0, x1);
+  const uint32_t v0 = shape_value(x0, r.mode, r.lo, r.hi), v1 = shape_value(x1, r.mode, r.lo, r.hi);
+  if (r.off2 < 0) {
+    a.arena[r.off + i] = v0;
+    if (e1 < n) a.arena[r.off + e1] = v1;
+  } else {
+    a.arena[((i & 1u) ? r.off2 : r.off) + (i >> 1)] = v0;
+    if (e1 < n) a.arena[((e1 & 1u) ? r.off2 : r.off) + (e1 >> 1)] = v1;
+  }
+}
+
 }  // namespace
+
+void rc_launch_prng_fill_segments(const RcPrngSegArgs& a, hipStream_t stream) {
+  const uint32_t blocks = a.n_segs > 0 ? a.wg_end[a.n_segs - 1] : 0u;
+  if (blocks) hipLaunchKernelGGL(k_prng_fill_segments, dim3(blocks), dim3(256), 0, stream, a);
+}
 
 void rc_launch_prng_fill(const RcPrngArgs& a, hipStream_t stream) {
   const int64_t half = (a.n + 1) >> 1;

@@ -329,7 +329,8 @@ class Model:
         MaterialModel.resample_render (stage material_light_from_scratch_resample; internal/models.py:1144-1254,
         1398-1694).  `rng`: the dict of explicit random tensors (see rc_material_randoms in include/rc_abi.h;
         oracle-compatible generator: oracle.material_ref.draw_randoms), or a uint32[2] key, from which the tensors are
-        derived at the reference's split sites (prng.material_pass_randoms).
+        derived at the reference's split sites (prng.material_pass_randoms) on the device: bits and uniforms are those
+        of the host twin bit for bit, normal and Gumbel values agree to a few ulp (rc.material_randoms).
 
         NOT parity-verified: the threefry primitives are pinned by published known answers, but the ~30 split sites
         material_pass_randoms restates by hand have never been compared with a jax run (none is possible in this
@@ -352,8 +353,9 @@ class Model:
             return self._material_outputs(cres, mres, fields)
         if albedo_ratio is not None:
             raise NotImplementedError("albedo_ratio is applied on the relighting path (env_map=)")
-        if prng.is_key(rng):
-            rng = prng.material_pass_randoms(rng, n_rays, self.config)
+        if prng.is_key(rng):              # drawn in HBM by one launch; on the host for a handle
+            # without the call (a stand-in that records calls)
+            rng = prng.material_pass_randoms(rng, n_rays, self.config, rc=self.rc if hasattr(self.rc, "material_randoms") else None)
         if not isinstance(rng, dict):
             raise ValueError("the material stage needs a uint32[2] key or explicit random tensors: pass rng as the dict "
                              "described by rc_material_randoms")

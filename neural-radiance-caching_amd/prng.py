@@ -28,7 +28,7 @@ The device twin is rc_prng_fill (csrc/rc_prng.hip, include/rc_abi.h): same count
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -185,13 +185,7 @@ def sampler_randoms(sampler_rng, n_rays: int, num_samples: Sequence[int]):
     one uniform [n_rays, 1] per level (stepfun.py:196-202).  Returned as the UNIT uniform the C ABI takes
     (rc_randoms.jitter): jax's uniform(maxval=max_jitter) is float32(unit * max_jitter), the product the sampling
     kernel forms itself."""
-    rng = as_key(sampler_rng)
-    out = []
-    for _ in num_samples:
-        key, rng = random_split(rng)
-        out.append(uniform(key, (n_rays, 1)))
-        _, rng = random_split(rng)
-    return out
+    return [uniform(d.key, d.shape) for d in _sampler_plan(sampler_rng, "jitter", n_rays, len(num_samples))]
 
 
 def cache_keys(cache_rng) -> Dict[str, np.ndarray]:
@@ -252,7 +246,7 @@ def light_vmf_noise(shape, seed: int = 1) -> np.ndarray:
     return normal(key, tuple(shape))
 
 
-def material_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
+def material_pass_randoms(model_rng, n_rays: int, cfg, rc=None, train: bool = False) -> Dict[str, object]:
     """Explicit random tensors of ONE material-stage forward (the dict rc_material_randoms / Model.apply(passes=
     ("cache", "light", "material")) take) derived from the model's rng at the reference's split sites:
 
@@ -269,7 +263,13 @@ def material_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
                                             their sampler runs on the constant PRNGKey(0) at render time
                                             (sampling.py:170-179) -- the specular and the diffuse trace therefore draw the
                                             SAME per-level jitter
-    The call order is restated from the source and cannot be checked against a jax run here (no jax in the image)."""
+    The call order is restated from the source and cannot be checked against a jax run here (no jax in the image).
+    With `rc` (a RadianceCache) the same tensors are drawn in HBM by one launch (rc.material_randoms: cuda views of one
+    arena, sec_jitter / sec_gumbel in the ABI's layout instead of the spec_* / diff_* pairs); train: material_stage_plan."""
+    if rc is not None:
+        return rc.material_randoms(model_rng, n_rays, cfg.num_secondary_samples, train=train)
+    if train:
+        return plan_randoms(material_stage_plan(model_rng, n_rays, cfg, train=True, vmf_noise=True))
     return _material_stage_randoms(model_rng, n_rays, cfg, env_sampler=False)
 
 
@@ -290,15 +290,74 @@ def relight_pass_randoms(model_rng, n_rays: int, cfg) -> Dict[str, object]:
 
 
 def _material_stage_randoms(model_rng, n_rays: int, cfg, env_sampler: bool) -> Dict[str, object]:
-    K = int(cfg.num_secondary_samples)
+    return plan_randoms(material_stage_plan(model_rng, n_rays, cfg, env_sampler=env_sampler, vmf_noise=True))
+
+
+class Draw(NamedTuple):
+    """One jax.random draw of a plan.  name: the member of the randoms dict ("jitter[1]": element 1 of the list "jitter");
+    key: uint32[2]; mode: MODE_*; shape: the shape jax draws (its element count fixes the counter layout); layout: "flat"
+    (the member is the tensor), "planes" (the last axis of 2 is split: <name>1 = [..., 0], <name>2 = [..., 1]) or "key" (no
+    tensor: the member is the key itself)."""
+    name: str
+    key: np.ndarray
+    mode: int
+    shape: Tuple[int, ...]
+    layout: str
+
+
+# member ids of the C twin (include/rc_abi.h rc_prng_member); "<name>[l]" is id + l
+MEMBER_IDS = {"jitter": 0, "gumbel": 8, "vmf_noise": 9, "spec_u": 10, "cos_u": 11, "vmf_lobe_gumbel": 12, "vmf_v": 13,
+              "vmf_tmp": 14, "spec_gumbel": 15, "diff_gumbel": 16, "noise": 17, "picks_key_spec": 18, "picks_key_diff": 19,
+              "spec_jitter": 24, "diff_jitter": 32}
+
+
+def member_id(name: str) -> int:
+    base, _, idx = name.partition("[")
+    return MEMBER_IDS[base] + (int(idx[:-1]) if idx else 0)
+
+
+def material_split(cfg, K: Optional[int] = None) -> Tuple[int, int, int, int]:
+    """(Ks, Kd, Kc, Kl) of K secondary samples: GGX, diffuse = cosine + light sampler (Python's round: half to even)."""
+    K = int(cfg.num_secondary_samples if K is None else K)
     Kd = int(round(K * cfg.diffuse_sample_fraction))
     Ks = int(round(K * (1.0 - cfg.diffuse_sample_fraction)))
     Kc = int(round(0.5 * Kd))
-    Kl = Kd - Kc
-    levels = [lvl[2] for lvl in cfg.sampling_strategy]
-    S = int(levels[-1])
+    return Ks, Kd, Kc, Kd - Kc
+
+
+def _sampler_plan(sampler_rng, name: str, n_rays: int, num_levels: int):
+    """sampler_randoms as draws: per level one random_split for the jitter, one more for the density MLP."""
+    rng, out = as_key(sampler_rng), []
+    for l in range(num_levels):
+        key, rng = random_split(rng)
+        out.append(Draw(f"{name}[{l}]", key, MODE_UNIFORM, (n_rays, 1), "flat"))
+        _, rng = random_split(rng)
+    return out
+
+
+def material_stage_plan(model_rng, n_rays: int, cfg, train: bool = False, env_sampler: bool = False, loss_key=None,
+                        vmf_noise: bool = False) -> list:
+    """The random_split tree of ONE material-stage forward as an ordered list of Draw rows: the split sites that
+    material_pass_randoms / relight_pass_randoms cite, and no tensor.  plan_randoms realises it on the host;
+    rc_material_randoms_plan (csrc/rc_prng_host.h) is the same tree in C, row for row, and rc_prng_fill_segments fills it
+    in HBM in one launch (RadianceCache.material_randoms).
+
+      train        True: the sampler of each secondary trace runs on its own key, cache_keys(kc)["sampler"] with kc the key
+                   of material.py:2190 -- internal/sampling.py:170-179 replaces the rng by PRNGKey(0) only when
+                   `deterministic or (not train and is_secondary)`.  False: PRNGKey(0) for both traces (render time).
+      env_sampler  EnvironmentSampler in both sampler sets (relight_pass_randoms): the two texel-draw keys as "key" rows.
+      loss_key     the key material_smoothness receives (extra_loss_keys): the plan ends with its noise [n, 3]
+                   (material_smoothness_noise).
+      vmf_noise    add light_vmf_noise's PRNGKey(1) constant [n, num_vmf, 3]; it depends on n alone, so callers cache it.
+
+    Like every key path of this module the call order is restated from the source and is NOT pinned against a jax run (no
+    jax here); that holds for the train=True reading and for the place of the noise as well."""
+    n = int(n_rays)
+    Ks, Kd, Kc, Kl = material_split(cfg)
+    levels = [int(lvl[2]) for lvl in cfg.sampling_strategy]
+    S, NL, V = levels[-1], len(levels), int(cfg.num_vmf)
     rng = as_key(model_rng)
-    out = dict(cache_pass_randoms(rng, n_rays, levels, resample=False))           # primary rays' jitter
+    plan = _sampler_plan(cache_keys(model_cache_rng(rng))["sampler"], "jitter", n, NL)      # primary rays' jitter
     _, rng = random_split(rng)                # :1156
     _, rng = random_split(rng)                # :1177
     k_samples, rng = random_split(rng)        # :1195
@@ -308,8 +367,9 @@ def _material_stage_randoms(model_rng, n_rays: int, cfg, env_sampler: bool) -> D
     _, r = random_split(k_samples)            # :1417
     k2, r = random_split(r)                   # :1431
     kg, _ = random_split(k2)                  # :241
-    out["gumbel"] = gumbel(kg, (n_rays, S, 1))[..., 0]
-    out["vmf_noise"] = light_vmf_noise((n_rays, 1, int(cfg.num_vmf), 3))[:, 0]
+    plan.append(Draw("gumbel", kg, MODE_GUMBEL, (n, S), "flat"))
+    if vmf_noise and not env_sampler:         # (the LightSampler is not evaluated under the EnvironmentSampler)
+        plan.append(Draw("vmf_noise", random_split(PRNGKey(1))[0], MODE_NORMAL, (n, V, 3), "flat"))
     # -- material shader
     k_sh, _ = random_split(k_mat)             # models.py:1548
     k_pa, _ = random_split(k_sh)              # shading.py:289
@@ -320,55 +380,81 @@ def _material_stage_randoms(model_rng, n_rays: int, cfg, env_sampler: bool) -> D
     k_spec, r = random_split(k_out)           # :1383 indirect specular
     k_diff, r = random_split(r)               # :1416 indirect diffuse (the env-map passes reuse these rays)
 
-    def one_pass(k_pass, counts):
-        """counts: samples per sampler, in sampler order.  Returns ([(uh, uw, sampler_rng)], key of the cache call)."""
+    def one_pass(k_pass, n_samplers):
+        """-> ([(key of the [m, 2] uniform, sampler rng)] per sampler, key of the cache call)."""
         kh, _ = random_split(k_pass)          # :1642
         kh1, r2 = random_split(kh)            # :1721 get_secondary_rays
         kh2, _ = random_split(r2)             # :1780 radiance_cache_fn
         ki, _ = random_split(kh1)             # render_utils.py:962
-        draws, r3 = [], ki
-        for cnt in counts:
+        keys, r3 = [], ki
+        for _ in range(n_samplers):
             ka, r3 = random_split(r3)         # :767
             ku, _ = random_split(ka)          # :324
-            u = uniform(ku, (n_rays * cnt, 2))
             kb, r3 = random_split(r3)         # :784
-            draws.append((u[:, 0].reshape(n_rays, cnt), u[:, 1].reshape(n_rays, cnt), kb))
+            keys.append((ku, kb))
         kc, _ = random_split(kh2)             # material.py:2190
-        return draws, kc
+        return keys, kc
 
-    def trace_randoms(kc, Kp):
-        ck = cache_keys(kc)                   # models.py:712 (sampler: replaced by PRNGKey(0)), 727, 748
+    def trace_plan(kc, Kp, name):
+        ck = cache_keys(kc)                   # models.py:712 (sampler: PRNGKey(0) unless train), 727, 748
         kg2, _ = random_split(ck["resample"])  # :241
-        jit = sampler_randoms(PRNGKey(0), n_rays * Kp, levels)
-        return jit, gumbel(kg2, (n_rays, Kp, S, 1))[..., 0].reshape(n_rays * Kp, S)
+        return (_sampler_plan(ck["sampler"] if train else PRNGKey(0), f"{name}_jitter", n * Kp, NL)
+                + [Draw(f"{name}_gumbel", kg2, MODE_GUMBEL, (n * Kp, S), "flat")])
 
+    keys_s, kc_spec = one_pass(k_spec, 1)
+    keys_d, kc_diff = one_pass(k_diff, 1 if env_sampler else 2)
     if env_sampler:
-        (_, _, kb_spec), = one_pass(k_spec, [Ks])[0]
-        _, kc_spec = one_pass(k_spec, [Ks])
-        (_, _, kb_diff), = one_pass(k_diff, [Kd])[0]
-        _, kc_diff = one_pass(k_diff, [Kd])
-        out["picks_key_spec"], _ = random_split(kb_spec)      # render_utils.py:215
-        out["picks_key_diff"], _ = random_split(kb_diff)
-        out["spec_jitter"], out["spec_gumbel"] = trace_randoms(kc_spec, Ks)
-        out["diff_jitter"], out["diff_gumbel"] = trace_randoms(kc_diff, Kd)
-        del out["vmf_noise"]                  # the LightSampler is not evaluated
-        return out
-    (su1, su2, _), = one_pass(k_spec, [Ks])[0]
-    _, kc_spec = one_pass(k_spec, [Ks])
-    out["spec_u1"], out["spec_u2"] = su1, su2
-    out["spec_jitter"], out["spec_gumbel"] = trace_randoms(kc_spec, Ks)
-    draws, kc_diff = one_pass(k_diff, [Kc, Kl])
-    out["cos_u1"], out["cos_u2"] = draws[0][0], draws[0][1]
-    k_light = draws[1][2]
-    ks, _ = random_split(k_light)             # LightSampler.sample_directions (render_utils.py:1450)
-    kv1, r5 = random_split(ks)                # sample_vmf :1407
-    kl, _ = random_split(kv1)                 # sample_vmf_vars :1358
-    out["vmf_lobe_gumbel"] = gumbel(kl, (n_rays, int(cfg.num_vmf)))
-    kn, r5 = random_split(r5)                 # :1409
-    out["vmf_v"] = normal(kn, (n_rays, Kl, 2))
-    kt, _ = random_split(r5)                  # :1413
-    out["vmf_tmp"] = uniform(kt, (n_rays, Kl))
-    out["diff_jitter"], out["diff_gumbel"] = trace_randoms(kc_diff, Kd)
+        plan.append(Draw("picks_key_spec", random_split(keys_s[0][1])[0], MODE_BITS, (0,), "key"))    # render_utils.py:215
+    else:
+        plan.append(Draw("spec_u", keys_s[0][0], MODE_UNIFORM, (n, Ks, 2), "planes"))
+    plan += trace_plan(kc_spec, Ks, "spec")
+    if env_sampler:
+        plan.append(Draw("picks_key_diff", random_split(keys_d[0][1])[0], MODE_BITS, (0,), "key"))
+    else:
+        plan.append(Draw("cos_u", keys_d[0][0], MODE_UNIFORM, (n, Kc, 2), "planes"))
+        ks, _ = random_split(keys_d[1][1])    # LightSampler.sample_directions (render_utils.py:1450)
+        kv1, r5 = random_split(ks)            # sample_vmf :1407
+        kl, _ = random_split(kv1)             # sample_vmf_vars :1358
+        plan.append(Draw("vmf_lobe_gumbel", kl, MODE_GUMBEL, (n, V), "flat"))
+        kn, r5 = random_split(r5)             # :1409
+        plan.append(Draw("vmf_v", kn, MODE_NORMAL, (n, Kl, 2), "flat"))
+        kt, _ = random_split(r5)              # :1413
+        plan.append(Draw("vmf_tmp", kt, MODE_UNIFORM, (n, Kl), "flat"))
+    plan += trace_plan(kc_diff, Kd, "diff")
+    if loss_key is not None:
+        key = as_key(loss_key)
+        _, key = random_split(key)            # train_utils.py:2530
+        _, key = random_split(key)            # :2541
+        kn2, _ = random_split(key)            # :2566
+        plan.append(Draw("noise", kn2, MODE_NORMAL, (n, 3), "flat"))
+    return plan
+
+
+_DRAW_FN = {MODE_BITS: lambda k, s: random_bits(k, s), MODE_UNIFORM: lambda k, s: uniform(k, s),
+            MODE_NORMAL: lambda k, s: normal(k, s), MODE_GUMBEL: lambda k, s: gumbel(k, s)}
+
+
+def put_member(out: Dict[str, object], name: str, value) -> None:
+    """Store one plan member under its name; "<base>[l]" appends to the list out[base] (levels come in order)."""
+    base, _, idx = name.partition("[")
+    if idx:
+        out.setdefault(base, []).append(value)
+    else:
+        out[name] = value
+
+
+def plan_randoms(plan) -> Dict[str, object]:
+    """Host realisation of a material_stage_plan: the randoms dict with numpy arrays."""
+    out: Dict[str, object] = {}
+    for d in plan:
+        if d.layout == "key":
+            out[d.name] = d.key
+            continue
+        x = _DRAW_FN[d.mode](d.key, tuple(d.shape))
+        if d.layout == "planes":
+            out[d.name + "1"], out[d.name + "2"] = x[..., 0], x[..., 1]
+        else:
+            put_member(out, d.name, x)
     return out
 
 

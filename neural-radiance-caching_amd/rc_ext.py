@@ -101,6 +101,15 @@ class rc_material_randoms(C.Structure):
                 ("resample_inds", C.c_void_p), ("sec_resample_inds", C.c_void_p), ("vmf_lobe_gumbel", C.c_void_p)]
 
 
+class rc_prng_segment(C.Structure):
+    _fields_ = [("key", C.c_uint32 * 2), ("mode", C.c_int32), ("id", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("n", C.c_int64), ("offset", C.c_int64), ("offset2", C.c_int64)]
+
+
+RC_PRNG_MAX_SEGMENTS = 32
+RC_PRNG_PLAN_TRAIN, RC_PRNG_PLAN_ENV_SAMPLER, RC_PRNG_PLAN_VMF_NOISE = 0x1, 0x2, 0x4
+
+
 class rc_mat_outputs(C.Structure):
     _fields_ = [("ptr", C.c_void_p * RC_MOUT_COUNT)]
 
@@ -348,6 +357,8 @@ _PROTOTYPES = {
     "rc_cast_rays_multi": (C.c_int, [_H, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "rc_train_batch": (C.c_int, [_H, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I64, _P, _P]),
     "rc_prng_fill": (C.c_int, [_H, _P, _I32, _F, _F, _I64, _P, _P]),
+    "rc_material_randoms_plan": (C.c_int, [_P, _P, _I64, _I32, _F, _I32, _P, _I32, C.c_uint32, _P, _I32, _P, _P]),
+    "rc_prng_fill_segments": (C.c_int, [_H, _P, _I32, _P, _I64, _P]),
     "rc_density_grad_size": (C.c_int64, [_H, _I32]),
     "rc_density_grad_layout": (C.c_int, [_H, _I32, _P, _I32, C.POINTER(C.c_int32)]),
     "rc_density_backward": (C.c_int, [_H, _I32, _P, _I64, _P, _P, _P, _P, _P]),
@@ -590,6 +601,7 @@ class RadianceCache:
         if rc != 0:
             raise RcError(rc, (self.lib.rc_last_error(None) or b"").decode())
         self._keep = []
+        self._vmf_noise_cache = {}          # n -> the PRNGKey(1) constant [n, num_vmf, 3] (material_randoms)
         if cfg.transient is not None:
             self._check(self.lib.rc_set_transient(self._h, C.byref(transient_config_to_c(cfg.transient))))
 
@@ -1151,6 +1163,67 @@ class RadianceCache:
         out = torch.empty(shape, dtype=torch.int32 if mode == "bits" else torch.float32, device=f"cuda:{self.device}")
         self._check(self.lib.rc_prng_fill(self._h, k, modes[mode], float(minval), float(maxval), n, out.data_ptr(),
                                           self._stream()))
+        return out
+
+    def prng_fill_segments(self, segs, arena):
+        """rc_prng_fill_segments: every segment of `segs` (a ctypes array or a list of rc_prng_segment) into `arena`, a
+        32-bit cuda tensor, in one launch."""
+        if not isinstance(segs, C.Array):
+            segs = (rc_prng_segment * len(segs))(*segs)
+        if not (arena.is_cuda and arena.is_contiguous() and arena.element_size() == 4):
+            raise ValueError("arena must be a contiguous cuda tensor of 32-bit words")
+        self._check(self.lib.rc_prng_fill_segments(self._h, segs, len(segs), arena.data_ptr(), arena.numel(), self._stream()))
+
+    def material_randoms(self, key, n: int, K: int = None, train: bool = False, env_sampler: bool = False, loss_key=None,
+                         vmf_noise_in_arena: bool = False):
+        """Every random tensor of one material-stage forward from the model's rng `key`, drawn in HBM: the plan in C
+        (rc_material_randoms_plan, the tree of prng.material_stage_plan), ONE arena allocation, ONE launch
+        (rc_prng_fill_segments).  Returns the randoms dict render_material / the *_backward calls / render_relight take:
+        jitter[levels], gumbel, spec_u1/u2, cos_u1/u2, vmf_lobe_gumbel, vmf_v, vmf_tmp, sec_jitter[levels] and sec_gumbel in
+        the ABI's [spec | diff] layout, `noise` [n, 3] when loss_key (the key material_smoothness receives) is given, and
+        with env_sampler the two host keys picks_key_spec / picks_key_diff instead of the sampler members.  Every tensor is
+        a cuda view of the one arena, except vmf_noise: the PRNGKey(1) constant depends on n alone and comes from a per-n
+        cache of the handle (vmf_noise_in_arena=True draws it with the plan instead).  train: prng.material_stage_plan."""
+        from . import prng
+        torch = self._torch
+        cfg = self.cfg
+        n, K = int(n), int(K or cfg.num_secondary_samples)
+        flags = ((RC_PRNG_PLAN_TRAIN if train else 0) | (RC_PRNG_PLAN_ENV_SAMPLER if env_sampler else 0)
+                 | (RC_PRNG_PLAN_VMF_NOISE if vmf_noise_in_arena else 0))
+        segs, count, words = material_randoms_plan(key, n, K, cfg.diffuse_sample_fraction, cfg.num_vmf,
+                                                   [lvl[2] for lvl in cfg.sampling_strategy], flags, loss_key)
+        arena = torch.empty(words, dtype=torch.float32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_prng_fill_segments(self._h, segs, count, arena.data_ptr(), words, self._stream()))
+        Ks, Kd, Kc, Kl = prng.material_split(cfg, K)
+        S, V = int(cfg.sampling_strategy[-1][2]), int(cfg.num_vmf)
+        by_id = {segs[i].id: segs[i] for i in range(count)}
+        view = lambda off, shape: arena[off:off + int(np.prod(shape))].view(shape)
+        out = {}
+        ids = prng.MEMBER_IDS
+        NL = len(cfg.sampling_strategy)
+        out["jitter"] = [view(by_id[ids["jitter"] + l].offset, (n, 1)) for l in range(NL)]
+        out["gumbel"] = view(by_id[ids["gumbel"]].offset, (n, S))
+        if not env_sampler:
+            if vmf_noise_in_arena:
+                out["vmf_noise"] = view(by_id[ids["vmf_noise"]].offset, (n, V, 3))
+            else:
+                cache = self._vmf_noise_cache
+                if n not in cache:
+                    cache[n] = self.prng_fill(prng.random_split(prng.PRNGKey(1))[0], (n, V, 3), "normal")
+                out["vmf_noise"] = cache[n]
+            for name, cnt in (("spec_u", Ks), ("cos_u", Kc)):
+                g = by_id[ids[name]]
+                out[name + "1"], out[name + "2"] = view(g.offset, (n, cnt)), view(g.offset2, (n, cnt))
+            out["vmf_lobe_gumbel"] = view(by_id[ids["vmf_lobe_gumbel"]].offset, (n, V))
+            out["vmf_v"] = view(by_id[ids["vmf_v"]].offset, (n, Kl, 2))
+            out["vmf_tmp"] = view(by_id[ids["vmf_tmp"]].offset, (n, Kl))
+        else:
+            for name in ("picks_key_spec", "picks_key_diff"):
+                out[name] = np.array(list(by_id[ids[name]].key), dtype=np.uint32)
+        out["sec_jitter"] = [view(by_id[ids["spec_jitter"] + l].offset, (n * K, 1)) for l in range(NL)]
+        out["sec_gumbel"] = view(by_id[ids["spec_gumbel"]].offset, (n * K, S))
+        if loss_key is not None:
+            out["noise"] = view(by_id[ids["noise"]].offset, (n, 3))
         return out
 
     # -- rays from cameras ------------------------------------------------------------------------
@@ -1922,6 +1995,25 @@ class AlbedoPairs:
         """(rows stored [min(count, capacity), 6] as numpy, count): a readback, for tests."""
         n = int(self.count.item())
         return self.buffer[: max(0, min(n, self.capacity))].cpu().numpy(), n
+
+
+def material_randoms_plan(key, n: int, K: int, diffuse_fraction: float, num_vmf: int, level_samples, flags: int = 0,
+                          loss_key=None, capacity: int = RC_PRNG_MAX_SEGMENTS):
+    """rc_material_randoms_plan (needs no GPU and no handle): the segment table of one material-stage forward's random
+    tensors -> (ctypes array of rc_prng_segment, number of rows, arena size in 32-bit words)."""
+    from . import prng
+
+    k = (C.c_uint32 * 2)(*[int(v) for v in prng.as_key(key)])
+    lk = None if loss_key is None else (C.c_uint32 * 2)(*[int(v) for v in prng.as_key(loss_key)])
+    levels = (C.c_int32 * len(level_samples))(*[int(v) for v in level_samples])
+    segs = (rc_prng_segment * max(1, int(capacity)))()
+    count, words = C.c_int32(0), C.c_int64(0)
+    rc = load_library().rc_material_randoms_plan(k, lk, int(n), int(K), float(diffuse_fraction), int(num_vmf), levels,
+                                                 len(level_samples), int(flags), segs, int(capacity), C.byref(count),
+                                                 C.byref(words))
+    if rc != 0:
+        raise RcError(rc, f"rc_material_randoms_plan(n={n}, K={K}): refused (rounded sample counts, sizes or capacity)")
+    return segs, count.value, words.value
 
 
 def vis_turbo_lut():

@@ -744,6 +744,44 @@ def material_env_stage_step(rc, opt_material: MaterialOptimizer, opt_envmap: Env
     return losses
 
 
+def material_stage_fit(rc, opt_material: MaterialOptimizer, opt_envmap: EnvMapOptimizer, dataset, key, steps: int,
+                       opt_light: Optional[LightSamplerOptimizer] = None, group=None,
+                       data_cfg: MaterialDataLossConfig = MaterialDataLossConfig(),
+                       smooth_cfg: MaterialSmoothnessConfig = MaterialSmoothnessConfig(),
+                       light_cfg: LightSamplingConfig = LightSamplingConfig()):
+    """`steps` train steps of the material stage fed by a data.DeviceDataset, from one PRNG key.  Per
+    step: step_key, rng = random_split(rng); batch_key, k = random_split(step_key); model_key, loss_key = random_split(k);
+    dataset.next_train(batch_key) (one launch); rc.material_randoms(model_key, n, data_cfg.num_secondary_samples,
+    train=True, loss_key=extra_loss_keys(loss_key)["material_smoothness"]) -- every random tensor of the forward and the
+    smoothness noise in one launch, in HBM; material_env_stage_step; with opt_light also light_sampler_step on the same rays
+    and randoms (light_cfg.num_secondary_samples must be the data loss's).  The host handles keys and scalars only: no
+    tensor is made on the host or crosses PCIe inside the loop and nothing is read back.  The way the step's three keys
+    come from `key` is this package's convention, as cache_stage_fit's is; neither it nor the tree behind material_randoms
+    is pinned against a jax run.  -> the steps' loss dicts (0-d cuda tensors): "data", "material_smoothness",
+    "regularizer/material_grid", "material_ray_sampler", and with opt_light "light_sampling", "regularizer/light_grid"."""
+    K = int(data_cfg.num_secondary_samples)
+    if opt_light is not None and int(light_cfg.num_secondary_samples) != K:
+        raise ValueError("material_stage_fit: light_cfg.num_secondary_samples must equal data_cfg.num_secondary_samples "
+                         "(both steps read the same randoms)")
+    rng = prng.as_key(key)
+    n = dataset.batch_size
+    history = []
+    for _ in range(int(steps)):
+        step_key, rng = prng.random_split(rng)
+        batch_key, k = prng.random_split(step_key)
+        model_key, loss_key = prng.random_split(k)
+        batch = dataset.next_train(batch_key)
+        randoms = rc.material_randoms(model_key, n, K, train=True,
+                                      loss_key=prng.extra_loss_keys(loss_key)["material_smoothness"])
+        rays = batch.rays.hot_fields()
+        losses = material_env_stage_step(rc, opt_material, opt_envmap, rays, randoms, batch.rgb, randoms["noise"],
+                                         batch.rays.lossmult, group, data_cfg, smooth_cfg)
+        if opt_light is not None:
+            losses.update(light_sampler_step(rc, opt_light, rays, randoms, batch.rays.lossmult, group, light_cfg))
+        history.append(losses)
+    return history
+
+
 # ---- the time-resolved cache ---------------------------------------------------------------------------------------
 
 def transient_data_grads(rc, rays, cam_origins, jitters, gt, rgb_nocorr=None, gt_nocorr=None, lossmult=None, flat=None,
