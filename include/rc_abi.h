@@ -1144,6 +1144,54 @@ typedef struct {
 } rc_eval_images;
 int rc_eval_image(rc_handle* h, const rc_eval_images* images, double* out, void* stream);
 
+/* ---- shift-invariant PSNR and SSIM ------------------------------------------------------------------
+ * rc_eval_shift_invariant: image_utils.shift_invariant_mse / shift_invariant_ssim (internal/image_utils.py:74-189) of two
+ * post-processed images, compared as they are; pred is the reference's im0 (the image that is shifted), gt its im1.
+ *   for di = -radius_i .. radius_i (outer), dj = -radius_j .. radius_j (inner):
+ *     shifted[y][x] = pred[R_H(y + di)][R_W(x + dj)], R_n(i) = -i below 0 and 2 (n - 1) - i above n - 1 (numpy "reflect");
+ *     metric [H][W]: mse: ((d_0^2 + d_1^2) + d_2^2) / 3 of d = shifted - gt; ssim: both images reflect-padded by 5,
+ *       dm_pix.ssim's map at its defaults (rc_eval_image's arithmetic) on the [H + 10][W + 10] pair, ((s_0 + s_1) + s_2) / 3;
+ *     pooled = the sum of metric over the (2 hw + 1)^2 window, zeros outside the image, along H then along W, taps in
+ *       increasing order, divided once by (2 hw + 1)^2;
+ *     the first shift is taken; a later one replaces the best at a pixel where pooled >= best (ssim) / pooled <= best
+ *       (mse): an exact tie goes to the LATER shift.  A comparison with NaN is false: the earlier shift stays (inputs are
+ *       finite by contract).
+ *   mse = mean over [H][W] of the chosen shifts' unpooled metric, psnr = -10 / ln 10 * ln(mse) (mse = 0 gives +inf),
+ *   ssim = mean of the chosen shifts' unpooled metric over [5, H - 5) x [5, W - 5).
+ * out: DEVICE doubles [RC_EVAL_SI_COUNT], written; the SSIM slot is NaN without want_ssim.  Optional DEVICE outputs, each
+ * [H][W] or NULL: mse_map / ssim_map (float32, the chosen shifts' unpooled metric), mse_di / mse_dj / ssim_di / ssim_dj
+ * (int32, the chosen shift); the ssim ones are not written without want_ssim.  Every sum is taken over per-workgroup
+ * partials in a fixed order in double: two calls on the same inputs are bitwise equal, maps and picks included.
+ * RC_ERR_INVALID_ARG: NULL images / pred / gt / out, height or width < 11, a negative radius or halfwidth, radius_i >=
+ * height or radius_j >= width (one reflection must do); RC_ERR_UNSUPPORTED: a radius above RC_EVAL_SI_MAX_RADIUS or a
+ * halfwidth above RC_EVAL_SI_MAX_HALFWIDTH.  Everything is ordered on `stream`; no allocation once the workspace has seen
+ * the largest case.  Works on any handle; no weights are needed. */
+#define RC_EVAL_SI_MAX_RADIUS 8
+#define RC_EVAL_SI_MAX_HALFWIDTH 16
+typedef enum {
+  RC_EVAL_SI_MSE = 0,
+  RC_EVAL_SI_PSNR,
+  RC_EVAL_SI_SSIM,
+  RC_EVAL_SI_COUNT
+} rc_eval_si_slot;
+typedef struct {
+  const float* pred;            /* [H][W][3] */
+  const float* gt;              /* [H][W][3] */
+  float* mse_map;               /* [H][W] written, or NULL */
+  float* ssim_map;              /* [H][W] written, or NULL */
+  int32_t* mse_di;              /* [H][W] written, or NULL */
+  int32_t* mse_dj;
+  int32_t* ssim_di;
+  int32_t* ssim_dj;
+  int32_t height;
+  int32_t width;
+  int32_t radius_i;             /* search_radii[0], along H */
+  int32_t radius_j;             /* search_radii[1], along W */
+  int32_t window_halfwidth;
+  int32_t want_ssim;            /* 0: only the mse search runs */
+} rc_eval_si_images;
+int rc_eval_shift_invariant(rc_handle* h, const rc_eval_si_images* images, double* out, void* stream);
+
 /* ---- evaluation of the albedo ------------------------------------------------------------------------
  * rc_eval_albedo: Trainer._compute_and_log_albedo_metrics (engine/trainer.py:1499-1567) of one view, on the device.
  *   per pixel, in fp32: in = mask > 0 (no mask: every pixel, mask value 1); valid = in && acc > 0.5; gt' = in ? gt : 1;

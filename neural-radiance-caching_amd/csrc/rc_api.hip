@@ -125,8 +125,10 @@ struct TransDataWs {
 };
 
 // rc_eval_image: the bin sums of both histograms (n_bins > 0), the post-processed images where the caller gives no buffer
-// of its own, and the per-workgroup partial sums of the three kernels (doubles).
-struct EvalWs { WsBuf binsum_pred, binsum_gt, post_pred, post_gt, part; };
+// of its own, and the per-workgroup partial sums of the three kernels (doubles).  rc_eval_shift_invariant: the metric maps
+// of one di row of shifts, the search state ([4][H][W]: best pooled, best metric, di, dj) and the per-workgroup partial
+// sums of both searches (doubles).
+struct EvalWs { WsBuf binsum_pred, binsum_gt, post_pred, post_gt, part, si_metric, si_state, si_part; };
 
 // rc_eval_albedo / rc_albedo_ratio: the view's own pair rows (no ratio handed in), the valid pixels per workgroup (int32),
 // the select's state (RcAlbedoState) and the per-workgroup partial sums (doubles).
@@ -153,7 +155,7 @@ struct RelightWs { WsBuf part, best; };
 // WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer,
 // WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY),
 // WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
-// rc_eval_image, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
+// rc_eval_image and rc_eval_shift_invariant, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
 // WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick.
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
                WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_COUNT };
@@ -260,6 +262,7 @@ constexpr WsName kTable[] = {
     WS(TD, rgb), WS(TD, G), WS(TD, Gt), WS(TD, loss_ray), WS(TD, dz_irr), WS(TD, dz_slf), WS(TD, x_irr), WS(TD, x_slf), WS(TD, part),
     WS(TD, ones), WS(TD, d_t_irr), WS(TD, d_t_slf), WS(TD, d_tint_ibrdf), WS(TD, d_direct), WS(TD, d_weights),
     WS(EV, binsum_pred), WS(EV, binsum_gt), WS(EV, post_pred), WS(EV, post_gt), WS(EV, part),
+    WS(EV, si_metric), WS(EV, si_state), WS(EV, si_part),
     WS(EA, pairs), WS(EA, wg), WS(EA, state), WS(EA, part),
     WS(VZ, state), WS(VZ, part), WS(VZ, maxpart), WS(VZ, binsum),
     WS(MK, loss_ray), WS(MK, d_density), WS(MK, points),
@@ -2118,6 +2121,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_transient_bwd_host.inc"
 #include "rc_optim_host.inc"
 #include "rc_metrics_host.inc"
+#include "rc_metrics_si_host.inc"
 #include "rc_albedo_host.inc"
 #include "rc_vis_host.inc"
 #include "rc_relight_host.inc"

@@ -775,6 +775,40 @@ void rc_launch_eval_pixels(const RcEvalPixelArgs& a, hipStream_t stream);
 void rc_launch_eval_ssim(const RcEvalSsimArgs& a, hipStream_t stream);
 void rc_launch_eval_finish(const RcEvalFinishArgs& a, hipStream_t stream);
 
+// Shift-invariant PSNR / SSIM (rc_metrics.hip).  The shifts are processed one di row at a time: a group
+// is the 2 radius_j + 1 shifts (di, -radius_j .. radius_j); the search state is carried between groups in [H][W] arrays.
+enum RcSiKind { RC_SI_MSE = 0, RC_SI_SSIM = 1 };
+struct RcSiMetricArgs {
+  const float* pred, * gt;                                 // [height][width][3]
+  int32_t height, width;
+  int32_t di, radius_j;                                    // the group: dj = -radius_j .. radius_j
+  float taps[11];                                          // ssim: the normalised Gaussian window
+  float c1, c2;
+  float* metric;                                           // [2 radius_j + 1][height][width] written
+};
+struct RcSiSelectArgs {
+  const float* metric;                                     // [2 radius_j + 1][height][width]
+  int32_t height, width;
+  int32_t di, radius_j, halfwidth;
+  int32_t first, last;                                     // the search's first group (no state yet) / its last one
+  int32_t crop;                                            // the partial sums cover [crop, height - crop) x [crop, width - crop)
+  float* best_pooled, * best_metric;                       // [height][width] the state, read (first == 0) and written
+  int32_t* best_di, * best_dj;
+  float* out_map;                                          // last only: [height][width] or nullptr
+  int32_t* out_di, * out_dj;
+  double* part;                                            // last only: one per workgroup
+};
+struct RcSiFinishArgs {
+  const double* part_mse, * part_ssim;                     // part_ssim nullptr: no ssim search ran
+  int64_t n_part;
+  double n_mse, n_ssim;                                    // H W, (H - 10)(W - 10)
+  double* out;                                             // [RC_EVAL_SI_COUNT] device doubles
+};
+void rc_si_tiles(int height, int width, int* ty, int* tx);
+void rc_launch_si_metric(int kind, const RcSiMetricArgs& a, hipStream_t stream);
+void rc_launch_si_select(int kind, const RcSiSelectArgs& a, hipStream_t stream);
+void rc_launch_si_finish(const RcSiFinishArgs& a, hipStream_t stream);
+
 // Evaluation of the albedo (rc_albedo.hip).  A pair row is (gt'[3], p[3]); a selection is one order
 // statistic of one channel's ratios: selection 2 c is channel c's lower middle rank, 2 c + 1 its upper one.
 constexpr int kRcAlbedoSelections = 6, kRcAlbedoDigits = 256;

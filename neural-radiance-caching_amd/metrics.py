@@ -5,8 +5,8 @@ PSNR and SSIM (internal/image_utils.py:411-489), the transient IoU (trainer.py:1
 (:1766-1779) and the normals' mean angular error (:1810-1855) -- on images that stay in HBM: the only device-to-host
 traffic of a view is the result array.  The albedo metric (_compute_and_log_albedo_metrics, trainer.py:1499-1582, with
 the test-set ratio of _compute_albedo_ratio, :2202-2240) is scored the same way: its per-channel median and least squares
-run on the device.  Not built: LPIPS (a network download) and the shift-invariant variants (off in the reference's eval
-config, configs.py:846).
+run on the device.  The shift-invariant psnr_si / ssim_si (image_utils.py:74-189, rc_eval_shift_invariant, §4.16.1) are
+SearchInvariantHarness' and evaluate_view(search_invariant=...)'s.  Not built: LPIPS (a network download).
 """
 from __future__ import annotations
 
@@ -25,7 +25,7 @@ class MetricHarness:
         if not disable_lpips:
             raise NotImplementedError("LPIPS is not built (its network is a download): pass disable_lpips=True")
         if not disable_search_invariant:
-            raise NotImplementedError("the shift-invariant metrics (psnr_si, ssim_si) are not built: pass "
+            raise NotImplementedError("the shift-invariant metrics (psnr_si, ssim_si) are SearchInvariantHarness': pass "
                                       "disable_search_invariant=True")
         self.rc = rc
         self.disable_ssim = bool(disable_ssim)
@@ -36,6 +36,52 @@ class MetricHarness:
         r = self.rc.eval_image(rgb_pred, rgb_gt, skip_postprocess=True)
         keys = ("psnr",) if self.disable_ssim else ("psnr", "ssim")
         return {name_fn(k): float(r[k]) for k in keys}
+
+
+def si_suffix(search_radii, window_halfwidth) -> str:
+    """image_utils.MetricHarness' suffix of the shift-invariant keys: "_(4,_4)_8" at the defaults.  search_radii is
+    rendered as a tuple, as the reference's default is one."""
+    return f" {tuple(rc_ext.search_radii_pair(search_radii))} {window_halfwidth}".replace(" ", "_")
+
+
+def shift_invariant_mse(rc, img0, img1, search_radii=(4, 4), window_halfwidth: int = 8):
+    """image_utils.shift_invariant_mse on a RadianceCache -> (score, opt_di, opt_dj): the float, and the chosen shifts
+    as int32 [H, W] cuda tensors.  img0 is the image that is shifted."""
+    r = rc.eval_shift_invariant(img0, img1, search_radii, window_halfwidth, ssim=False, keep_maps=True)
+    return r["mse"], r["mse_di"], r["mse_dj"]
+
+
+def shift_invariant_ssim(rc, img0, img1, search_radii=(4, 4), window_halfwidth: int = 8):
+    """image_utils.shift_invariant_ssim on a RadianceCache -> (score, opt_di, opt_dj)."""
+    r = rc.eval_shift_invariant(img0, img1, search_radii, window_halfwidth, ssim=True, keep_maps=True)
+    return r["ssim"], r["ssim_di"], r["ssim_dj"]
+
+
+class SearchInvariantHarness:
+    """image_utils.MetricHarness as the reference constructs it (disable_search_invariant=False, LPIPS off) on a
+    RadianceCache: `harness(rgb_pred, rgb_gt, name_fn)` -> {"psnr", "ssim", "psnr_si_(4,_4)_8", "ssim_si_(4,_4)_8"} of two
+    post-processed [H, W, 3] images, compared as they are; under disable_ssim only "psnr" and "psnr_si...", as there."""
+
+    def __init__(self, rc, disable_ssim: bool = False, search_radii=(4, 4), window_halfwidth: int = 8):
+        if rc is None:
+            raise ValueError("SearchInvariantHarness needs the RadianceCache it runs on: SearchInvariantHarness(rc)")
+        self.rc = rc
+        self.disable_ssim = bool(disable_ssim)
+        self.search_radii = rc_ext.search_radii_pair(search_radii)
+        self.window_halfwidth = int(window_halfwidth)
+        self.si_suffix = si_suffix(search_radii, window_halfwidth)
+
+    def __call__(self, rgb_pred, rgb_gt, name_fn=lambda s: s) -> Dict[str, float]:
+        pred, gt = self.rc._dev(rgb_pred), self.rc._dev(rgb_gt)
+        plain = self.rc.eval_image(pred, gt, skip_postprocess=True)
+        si = self.rc.eval_shift_invariant(pred, gt, self.search_radii, self.window_halfwidth, ssim=not self.disable_ssim)
+        out = {"psnr": plain["psnr"]}
+        if not self.disable_ssim:
+            out["ssim"] = plain["ssim"]
+        out["psnr_si" + self.si_suffix] = si["psnr"]
+        if not self.disable_ssim:
+            out["ssim_si" + self.si_suffix] = si["ssim"]
+        return {name_fn(k): float(v) for k, v in out.items()}
 
 
 def postprocess(rc, x, exposure: float = 1.0, img_scale: float = 1.0, clip_eval: bool = False):
@@ -106,7 +152,7 @@ def _render_material(model, fields, names, image, n, passes, rng, every_key=Fals
 def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cache",), masks=None, depth=None,
                   normals=None, exposure: float = 1.0, img_scale: float = 1.0, clip_eval: bool = False, rng=None,
                   gt=None, albedo=None, albedo_ratio=None, albedo_clip: float = 1.0, albedo_pairs=None,
-                  visualize: bool = False) -> Dict[str, float]:
+                  visualize: bool = False, search_invariant=None) -> Dict[str, float]:
     """Render camera `cam_idx` of a DeviceDataset with `model` (this package's Model) and score it: the rays of
     generate_ray_batch in chunks of config.render_chunk_size that stay on the device, only the outputs the metrics need,
     then rc_eval_image against dataset.images[cam_idx] (or `gt`).  masks, depth: [H, W]; normals: [H, W, 3] ground
@@ -126,7 +172,11 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
     visualize: the keys the reference's visualisation suite reads are rendered in the same chunk loop and "vis" is added:
     vis.visualize_suite (visualize_transient_suite on a time-resolved handle; vis_material with the material pass) of the
     view as uint8 [H, W, 3] cuda tensors, with `img_scale` as the suite's config.img_scale and the depth pictures masked
-    by `masks`.  The scores do not change."""
+    by `masks`.  The scores do not change.
+
+    search_invariant: None, or (search_radii, window_halfwidth): "psnr_si<suffix>" and "ssim_si<suffix>" (si_suffix) of
+    the post-processed, masked images that rc_eval_image leaves on the device are added (rc_eval_shift_invariant,
+    DESIGN.md §4.16.1); every other key is what None returns."""
     import torch
 
     from . import vis
@@ -201,9 +251,14 @@ def evaluate_view(model, dataset, cam_idx: int, passes: Tuple[str, ...] = ("cach
                         distance_mean=scored("distance_mean", depth is not None),
                         distance_median=scored("distance_median", depth is not None),
                         depth_gt=dv(depth, "depth"), exposure=exposure, img_scale=img_scale, clip_eval=clip_eval,
-                        shape=shape)
+                        shape=shape, keep_images=search_invariant is not None)
     ms = start.elapsed_time(stop)               # the result copy above has synchronised
     res["rays_per_sec"] = n / (ms * 1e-3) if ms > 0 else float("inf")
+    if search_invariant is not None:
+        radii, halfwidth = search_invariant
+        si = rc.eval_shift_invariant(res.pop("post_pred"), res.pop("post_gt"), radii, halfwidth)
+        res["psnr_si" + si_suffix(radii, halfwidth)] = si["psnr"]
+        res["ssim_si" + si_suffix(radii, halfwidth)] = si["ssim"]
     if albedo is not None:
         a = rc.eval_albedo(image[albedo_name], image["acc"], rc._dev(albedo), mask=dv(masks, "masks"), ratio=albedo_ratio,
                            albedo_clip=albedo_clip, pairs=albedo_pairs, shape=(H, W))

@@ -278,6 +278,31 @@ class rc_eval_images(C.Structure):
                    ("img_scale", C.c_float), ("clip_eval", C.c_int32), ("skip_postprocess", C.c_int32)])
 
 
+# rc_eval_si_slot -> name; order must match include/rc_abi.h
+EVAL_SI_SLOTS = ("mse", "psnr", "ssim")
+RC_EVAL_SI_COUNT = len(EVAL_SI_SLOTS)
+RC_EVAL_SI_MAX_RADIUS = 8
+RC_EVAL_SI_MAX_HALFWIDTH = 16
+_EVAL_SI_MAPS = ("mse_map", "ssim_map", "mse_di", "mse_dj", "ssim_di", "ssim_dj")
+
+
+class rc_eval_si_images(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("pred", "gt") + _EVAL_SI_MAPS]
+                + [(k, C.c_int32) for k in ("height", "width", "radius_i", "radius_j", "window_halfwidth", "want_ssim")])
+
+
+def search_radii_pair(search_radii):
+    """(ri, rj) of the reference's `search_radii`: two integers."""
+    try:
+        ri, rj = search_radii
+        ok = int(ri) == ri and int(rj) == rj
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"search_radii must be a pair of integers (i, j), not {search_radii!r}")
+    return int(ri), int(rj)
+
+
 # rc_albedo_slot -> name; order must match include/rc_abi.h
 ALBEDO_SLOTS = ("mse", "psnr", "ratio_r", "ratio_g", "ratio_b", "valid")
 RC_ALBEDO_COUNT = len(ALBEDO_SLOTS)
@@ -389,6 +414,7 @@ _PROTOTYPES = {
                                                   C.POINTER(rc_transient_data_loss_kind), _P, _P, _P]),
     "rc_dtof_to_itof": (C.c_int, [_H, _P, _I64, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),
     "rc_eval_image": (C.c_int, [_H, C.POINTER(rc_eval_images), _P, _P]),
+    "rc_eval_shift_invariant": (C.c_int, [_H, C.POINTER(rc_eval_si_images), _P, _P]),
     "rc_eval_albedo": (C.c_int, [_H, C.POINTER(rc_albedo_images), _P, _P]),
     "rc_albedo_ratio": (C.c_int, [_H, _P, _I64, _P, _I32, _I32, _P, _P]),
     "rc_weighted_percentile": (C.c_int, [_H, _P, _P, _I64, _P, _I32, _P, _P]),
@@ -1508,6 +1534,46 @@ class RadianceCache:
         if stream_handle is not None:                  # a foreign stream: torch's copy below is not ordered behind it
             torch.cuda.synchronize(self.device)
         res.update(zip(EVAL_SLOTS, out.cpu().tolist()))                 # the one device-to-host copy
+        return res
+
+    def eval_shift_invariant(self, pred, gt, search_radii=(4, 4), window_halfwidth: int = 8, ssim: bool = True,
+                             keep_maps: bool = False, stream_handle=None, sync: bool = True):
+        """rc_eval_shift_invariant: image_utils.shift_invariant_mse / shift_invariant_ssim of two
+        post-processed [H, W, 3] images, compared as they are (cuda tensors are used where they are, numpy arrays are
+        uploaded); pred is the image that is shifted.  Returns {"mse", "psnr", "ssim"} as floats ("ssim" is NaN with
+        ssim=False) after ONE copy of the result array to the host; with sync=False the array stays on the device under
+        "result" (float64 [RC_EVAL_SI_COUNT] in EVAL_SI_SLOTS' order) and nothing waits.  keep_maps adds "mse_map"
+        (float32 [H, W], the chosen shifts' unpooled metric), "mse_di" and "mse_dj" (int32 [H, W], the chosen shifts), and
+        with ssim the three "ssim_" ones."""
+        torch = self._torch
+        ri, rj = search_radii_pair(search_radii)
+        if int(window_halfwidth) != window_halfwidth:
+            raise ValueError(f"window_halfwidth must be an integer, not {window_halfwidth!r}")
+        held = {"pred": self._dev(pred), "gt": self._dev(gt)}
+        lead = held["pred"]
+        if lead.dim() != 3 or lead.shape[-1] != 3:
+            raise ValueError("pred / gt must be [H, W, 3]")
+        if held["gt"].shape != lead.shape:
+            raise ValueError(f"gt is {tuple(held['gt'].shape)}, pred {tuple(lead.shape)}")
+        H, W = int(lead.shape[0]), int(lead.shape[1])
+        im = rc_eval_si_images(pred=lead.data_ptr(), gt=held["gt"].data_ptr(), height=H, width=W, radius_i=ri, radius_j=rj,
+                               window_halfwidth=int(window_halfwidth), want_ssim=int(bool(ssim)))
+        dev = f"cuda:{self.device}"
+        res = {}
+        if keep_maps:
+            for k in _EVAL_SI_MAPS:
+                if ssim or not k.startswith("ssim"):
+                    res[k] = torch.empty((H, W), dtype=torch.float32 if k.endswith("map") else torch.int32, device=dev)
+                    setattr(im, k, res[k].data_ptr())
+        out = torch.empty(RC_EVAL_SI_COUNT, dtype=torch.float64, device=dev)
+        self._check(self.lib.rc_eval_shift_invariant(self._h, C.byref(im), out.data_ptr(), self._stream(stream_handle)))
+        self._keep = [held]
+        if not sync:
+            res["result"] = out
+            return res
+        if stream_handle is not None:                  # a foreign stream: torch's copy below is not ordered behind it
+            torch.cuda.synchronize(self.device)
+        res.update(zip(EVAL_SI_SLOTS, out.cpu().tolist()))              # the one device-to-host copy
         return res
 
     # -- evaluation of the albedo ------------------------------------------------------------------------
