@@ -1374,6 +1374,55 @@ int rc_render_relight(rc_handle* h, const rc_rays* rays, int64_t n_rays, const r
                       const rc_material_randoms* mr, int32_t num_secondary_samples, const rc_relight_args* args,
                       const rc_outputs* cache_out, const rc_mat_outputs* mat_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The probe of a surface point: the `vis_secondary` block of the reference's evaluation loop
+ * (engine/trainer.py:848-1069) for P <= RC_PROBE_MAX selected pixels of a rendered view in one launch each.
+ *
+ * rc_probe_rays: the rays of P latitude-longitude panoramas of height x width pixels, probe-major (ray
+ *   (p height + row) width + col), cast from the hit points of the view's rows pixel[0 .. P):
+ *     position = origins + directions * distance_median + normal_offset * normals      (trainer.py:863-871; the
+ *                reference's offset is 4e-1);  origins = position, near / far as given;
+ *     radii    = those of camera_utils.cast_spherical_rays around `position` with the identity rotation (the reference
+ *                overwrites its rotation matrix with np.eye(3), :874-882): bitwise what rc_cast_rays writes for camtype 1,
+ *                pixtocam = diag(2 pi / width, pi / height, 1).  They belong to the panoramic direction of the pixel, not
+ *                to the direction the ray carries: the reference's mismatch, kept;
+ *     directions = viewdirs = utils.get_sphere_directions(height, width, flip) (internal/utils.py:55-83;
+ *                _update_secondary_rays, :934-942);
+ *     lights, imageplane, look, up = row 0 of the view's arrays (:944-1012); for a NULL member of rc_probe_view the
+ *                panoramic cast's own value stays: its image plane, look (0, 0, -1), up (0, 1, 0), and `position` as the
+ *                light (the camera centre, as rc_camera_set's NULL lights).
+ *   `pixel` is a HOST array of P rows of the view; `out` members may be NULL (not wanted), `positions` too.
+ * rc_vmf_panorama: render_vmf (:1026-1069) of P mixtures of V <= RC_PROBE_MAX_LOBES lobes over the same panorama:
+ *     mean_j = means_j / max(|means_j|, 1e-5),  w_j = safe_exp(logits_j) / sum_j safe_exp(logits_j)  (math.safe_exp, the
+ *     clip at 70),  L = sum_j w_j eval_vmf(xyz, mean_j, kappas_j)  (render_utils.py:1335-1346: 1 / 4 pi for kappa <=
+ *     FLT_EPSILON, its own safe_exp = exp(min(x, 80))), summed over j ascending in fp32;
+ *     out_linear = L, out_srgb = image.linear_to_srgb(L) in three channels, out_u8 = utils.save_img_u8's 8-bit form of
+ *     out_srgb.  Each output may be NULL, not all of them; one requested alone is bitwise what it is with the others.
+ * Both calls work on any handle, are ordered on `stream`, never synchronise, allocate nothing and use no atomics.
+ * RC_ERR_INVALID_ARG, with nothing launched: P < 1 or P > RC_PROBE_MAX, a pixel outside [0, n_view), height or width < 1,
+ * P height width >= 2^31, V < 1 or V > RC_PROBE_MAX_LOBES, a NULL required pointer (view, its first four members, pixel,
+ * out; means, kappas, logits), no output requested.
+ * ------------------------------------------------------------------------------------------------ */
+#define RC_PROBE_MAX 16
+#define RC_PROBE_MAX_LOBES 128
+typedef struct rc_probe_view {        /* DEVICE arrays of the rendered view, or of any subset of its pixels */
+  const float* origins;               /* [n_view,3] primary rays                                            */
+  const float* directions;            /* [n_view,3]                                                         */
+  const float* distance_median;       /* [n_view]   rendering["distance_median"]                            */
+  const float* normals;               /* [n_view,3] rendering["normals_to_use"]                             */
+  const float* lights;                /* [>= 1,3] or NULL                                                   */
+  const float* imageplane;            /* [>= 1,2] or NULL                                                   */
+  const float* look;                  /* [>= 1,3] or NULL                                                   */
+  const float* up;                    /* [>= 1,3] or NULL                                                   */
+  int64_t n_view;
+} rc_probe_view;
+int rc_probe_rays(rc_handle* h, const rc_probe_view* view, const int64_t* pixel, int32_t P, int32_t height, int32_t width,
+                  float near, float far, float normal_offset, int32_t flip, const rc_cast_outputs* out, float* positions,
+                  void* stream);
+int rc_vmf_panorama(rc_handle* h, const float* means, const float* kappas, const float* logits, int32_t P, int32_t V,
+                    int32_t height, int32_t width, int32_t flip, float* out_linear, float* out_srgb, uint8_t* out_u8,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2126,3 +2126,4 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 #include "rc_vis_host.inc"
 #include "rc_relight_host.inc"
 #include "rc_prng_host.inc"
+#include "rc_probe_host.inc"

@@ -890,6 +890,30 @@ void rc_launch_vis_bins(const RcVisBinsArgs& a, hipStream_t stream);
 void rc_launch_vis_items(const RcVisItemsArgs& a, int n_items, hipStream_t stream);
 const float* rc_vis_turbo_host();
 
+// The probe of a surface point (rc_probe.hip): the panorama of secondary rays cast from the hit points
+// of P pixels of a rendered view, and the panorama of each pixel's vMF mixture.
+constexpr int kRcProbeMax = RC_PROBE_MAX, kRcProbeMaxLobes = RC_PROBE_MAX_LOBES;
+struct RcProbeRaysArgs {
+  const float* origins, * directions, * distance_median, * normals;     // the view's rows
+  const float* lights, * imageplane, * look, * up;                       // row 0 goes to every ray; nullptr: the cast's own
+  int64_t pixel[kRcProbeMax];                                            // the row of each probe
+  int32_t P, height, width, flip;
+  int64_t n;                                                             // P * height * width
+  float normal_offset, phi_offset, theta_offset;                         // pi / W and pi / (2 H), rounded from double
+  float pixtocam[9], rot[9];                                             // diag(2 pi / W, pi / H, 1), the identity
+  RcCastShared s;                                                        // camtype 1, near, far
+  RcCastOut out;
+  float* positions;                                                      // [P,3] or nullptr
+};
+struct RcVmfPanoramaArgs {
+  const float* means, * kappas, * logits;                                // [P,V,3], [P,V], [P,V]
+  int32_t V, height, width, flip;
+  float phi_offset, theta_offset;
+  float* out_linear, * out_srgb; uint8_t* out_u8;                        // [P,H,W], [P,H,W,3], [P,H,W,3]; nullptr: not wanted
+};
+void rc_launch_probe_rays(const RcProbeRaysArgs& a, hipStream_t stream);
+void rc_launch_vmf_panorama(const RcVmfPanoramaArgs& a, int P, hipStream_t stream);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rc_dev_reduce.h"
+#include "rc_dev_vis.h"
 #include "rc_internal.h"
 
 namespace {
@@ -28,8 +29,6 @@ constexpr int kThreads = kReduceThreads;
 constexpr int kPasses = 4, kDigitBits = 8;                // 4 x 8 bits of the 32-bit key
 constexpr int kSel = kRcVisSelections;
 static_assert((1 << kDigitBits) == kRcVisDigits && kRcVisDigits == kThreads, "one thread per digit");
-constexpr float kF32Eps = 1.1920928955078125e-07f;        // np.finfo(np.float32).eps
-constexpr float kF32Max = 3.4028234663852886e+38f;
 
 __constant__ float kTurbo[256 * 3] = {
 #include "rc_turbo_lut.inc"
@@ -40,9 +39,6 @@ const float kTurboHost[256 * 3] = {
 
 __device__ __forceinline__ float nan_f() { return __uint_as_float(0x7fc00000u); }
 __device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// np.clip / jnp.clip: a NaN stays a NaN (fminf / fmaxf would drop it)
-__device__ __forceinline__ float clip(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
 
 // Unsigned keys in the order of numpy's sort: negative values with every bit flipped, the others with the sign bit set;
 // -0 and +0 share a key, and every NaN has the largest one.
@@ -350,18 +346,7 @@ __global__ void __launch_bounds__(kThreads) k_vis_bins(RcVisBinsArgs a) {
   }
 }
 
-// image.linear_to_srgb (internal/image.py:192-200) with eps = float32's under jnp: jnp.maximum hands a NaN on
-__device__ __forceinline__ float linear_to_srgb(float x) {
-  if (x != x) return x;
-  const float srgb0 = (float)(323.0 / 25.0) * x;
-  const float srgb1 = ((211.0f * powf(fmaxf(kF32Eps, x), (float)(5.0 / 12.0))) - 11.0f) / 200.0f;
-  return x <= 0.0031308f ? srgb0 : srgb1;
-}
-
-__device__ __forceinline__ float nan_to_num(float x) {
-  if (x != x) return 0.0f;
-  return fminf(fmaxf(x, -kF32Max), kF32Max);
-}
+// clip, linear_to_srgb, nan_to_num and save_u8 (utils.save_img_u8) are rc_dev_vis.h's
 
 // the depth curve of the suites: -log(x + eps)
 __device__ __forceinline__ float depth_curve(float x) { return -logf(x + kF32Eps); }
@@ -427,9 +412,9 @@ __global__ void __launch_bounds__(kThreads) k_vis_items(RcVisItemsArgs a) {
     it.out_f32[3 * i + 2] = y2;
   }
   if (it.out_u8) {                                         // save_img_u8: round half to even
-    it.out_u8[3 * i] = (uint8_t)rintf(clip(nan_to_num(y0), 0.0f, 1.0f) * 255.0f);
-    it.out_u8[3 * i + 1] = (uint8_t)rintf(clip(nan_to_num(y1), 0.0f, 1.0f) * 255.0f);
-    it.out_u8[3 * i + 2] = (uint8_t)rintf(clip(nan_to_num(y2), 0.0f, 1.0f) * 255.0f);
+    it.out_u8[3 * i] = save_u8(y0);
+    it.out_u8[3 * i + 1] = save_u8(y1);
+    it.out_u8[3 * i + 2] = save_u8(y2);
   }
 }
 

@@ -16,6 +16,7 @@ from .config import GridConfig, RenderConfig
 
 RC_ABI_VERSION = 5
 RC_MAX_LEVELS = 3
+RC_ERR_MISSING_WEIGHT = -3          # the rc_status code probe.light_lobes tells apart (RcError.code)
 
 RC_PASS_CACHE = 0x1
 RC_PASS_SECONDARY = 0x2
@@ -328,6 +329,16 @@ class rc_vis_item(C.Structure):
                 + [(k, C.c_void_p) for k in ("divisor", "acc", "mask", "bounds", "auto_bounds", "out_f32", "out_u8")])
 
 
+RC_PROBE_MAX, RC_PROBE_MAX_LOBES = 16, 128
+_PROBE_VIEW_REQUIRED = ("origins", "directions", "distance_median", "normals")
+_PROBE_VIEW_BROADCAST = (("lights", 3), ("imageplane", 2), ("look", 3), ("up", 3))
+
+
+class rc_probe_view(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in _PROBE_VIEW_REQUIRED] + [(k, C.c_void_p) for k, _ in _PROBE_VIEW_BROADCAST]
+                + [("n_view", C.c_int64)])
+
+
 class rc_adam_buffer(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
                 ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
@@ -421,6 +432,9 @@ _PROTOTYPES = {
     "rc_image_max": (C.c_int, [_H, _P, _I64, _P, _P]),
     "rc_vis_images": (C.c_int, [_H, C.POINTER(rc_vis_item), _I32, _I32, _I32, _P]),
     "rc_vis_turbo_lut": (C.c_int, [_P]),
+    "rc_probe_rays": (C.c_int, [_H, C.POINTER(rc_probe_view), _P, _I32, _I32, _I32, _F, _F, _F, _I32,
+                                C.POINTER(rc_cast_outputs), _P, _P]),
+    "rc_vmf_panorama": (C.c_int, [_H, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "rc_set_env_image": (C.c_int, [_H, _P, _P, _P, _P, _I32, _I32, _P]),
     "rc_env_tables": (C.c_int, [_H, _P, _I32, _I32, _F, _P, _P, _P, _P]),
     "rc_env_lookup": (C.c_int, [_H, _P, _I64, _P, _P]),
@@ -1714,6 +1728,98 @@ class RadianceCache:
         self._keep = [held]
         return res
 
+    # -- the probe of a surface point ---------------------------------------------------
+    def probe_rays(self, view, pixels, height: int, width: int, near: float, far: float, normal_offset: float = 0.4,
+                   flip: bool = False, stream_handle=None):
+        """rc_probe_rays: the [height, width] panoramas of secondary rays cast from the hit points of rows `pixels` (host
+        integers, at most RC_PROBE_MAX) of `view`: a dict of "origins", "directions", "normals" ([n_view, 3]) and
+        "distance_median" ([n_view]), and optionally "lights", "imageplane", "look", "up", whose row 0 every ray takes (a
+        missing one keeps the panoramic cast's own value).  cuda tensors are used where they are.  Returns (Rays of
+        [P, height, width, .] cuda tensors, positions [P, 3]); cam_origins and the vcam_* fields are None (only the
+        time-resolved cache reads them)."""
+        torch = self._torch
+        from .rays import Rays
+        pix = np.ascontiguousarray(np.asarray(pixels).reshape(-1), dtype=np.int64)
+        P, H, W = int(pix.size), int(height), int(width)
+        v, held = rc_probe_view(), {}
+        for k in _PROBE_VIEW_REQUIRED:
+            t = held[k] = self._dev(view[k]).reshape(-1) if k == "distance_median" else self._dev(view[k]).reshape(-1, 3)
+            setattr(v, k, t.data_ptr())
+        v.n_view = n_view = held["origins"].shape[0]
+        for k in _PROBE_VIEW_REQUIRED:
+            if held[k].shape[0] != n_view:
+                raise ValueError(f"probe_rays: view[{k!r}] has {held[k].shape[0]} rows, expected {n_view}")
+        for k, width_k in _PROBE_VIEW_BROADCAST:
+            if view.get(k) is not None:
+                t = held[k] = self._dev(view[k]).reshape(-1, width_k)
+                if t.shape[0] < 1:
+                    raise ValueError(f"probe_rays: view[{k!r}] is empty")
+                setattr(v, k, t.data_ptr())
+        if not (1 <= P <= RC_PROBE_MAX and H >= 1 and W >= 1 and P * H * W < 2 ** 31):
+            raise ValueError(f"probe_rays: {P} probes of {H} x {W} rays (1..{RC_PROBE_MAX} probes, below 2^31 rays in all)")
+        out = rc_cast_outputs()
+        t = self._cast_tensors((P, H, W), out)
+        dev = f"cuda:{self.device}"
+        positions = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        self._check(self.lib.rc_probe_rays(self._h, C.byref(v), pix.ctypes.data_as(C.c_void_p), P, H, W, float(near), float(far),
+                                           float(normal_offset), int(bool(flip)), C.byref(out), positions.data_ptr(),
+                                           self._stream(stream_handle)))
+        self._keep = [held]
+        zi = torch.zeros((P, H, W, 1), dtype=torch.int32, device=dev)
+        rays = Rays(origins=t["origins"], lights=t["lights"], directions=t["directions"], viewdirs=t["viewdirs"],
+                    radii=t["radii"], imageplane=t["imageplane"], look=t["look"], up=t["up"], cam_origins=None,
+                    vcam_look=None, vcam_up=None, vcam_origins=None,
+                    lossmult=torch.ones((P, H, W, 1), dtype=torch.float32, device=dev), near=t["near"], far=t["far"],
+                    cam_idx=zi, light_idx=zi)
+        return rays, positions
+
+    def vmf_panorama(self, means, kappas, logits, height: int, width: int, flip: bool = False, linear: bool = False,
+                     srgb: bool = True, u8: bool = False, stream_handle=None):
+        """rc_vmf_panorama: the reference's render_vmf of P mixtures over the [height, width] panorama.  means [P, V, 3]
+        (raw: they are normalised with max(|m|, 1e-5)), kappas [P, V], logits [P, V] (a single mixture may leave P out).
+        Returns the requested of "linear" ([P, H, W] float32, the mixture's density), "srgb" ([P, H, W, 3] float32) and "u8"
+        ([P, H, W, 3] uint8, save_img_u8's form of "srgb") as cuda tensors."""
+        torch = self._torch
+        m, k, l = self._dev(means), self._dev(kappas), self._dev(logits)
+        if m.dim() == 2:
+            m, k, l = m[None], k[None], l[None]
+        if m.dim() != 3 or m.shape[-1] != 3 or tuple(k.shape) != tuple(m.shape[:2]) or tuple(l.shape) != tuple(m.shape[:2]):
+            raise ValueError(f"vmf_panorama: means {tuple(m.shape)}, kappas {tuple(k.shape)}, logits {tuple(l.shape)}: "
+                             "expected [P, V, 3], [P, V], [P, V]")
+        P, V, H, W = int(m.shape[0]), int(m.shape[1]), int(height), int(width)
+        if not (1 <= P <= RC_PROBE_MAX and 1 <= V <= RC_PROBE_MAX_LOBES and H >= 1 and W >= 1 and P * H * W < 2 ** 31):
+            raise ValueError(f"vmf_panorama: {P} mixtures of {V} lobes over {H} x {W} pixels (1..{RC_PROBE_MAX} mixtures, "
+                             f"1..{RC_PROBE_MAX_LOBES} lobes, below 2^31 pixels in all)")
+        if not (linear or srgb or u8):
+            raise ValueError("vmf_panorama: no output requested")
+        dev = f"cuda:{self.device}"
+        res = {}
+        if linear:
+            res["linear"] = torch.empty((P, H, W), dtype=torch.float32, device=dev)
+        if srgb:
+            res["srgb"] = torch.empty((P, H, W, 3), dtype=torch.float32, device=dev)
+        if u8:
+            res["u8"] = torch.empty((P, H, W, 3), dtype=torch.uint8, device=dev)
+        self._check(self.lib.rc_vmf_panorama(self._h, m.data_ptr(), k.data_ptr(), l.data_ptr(), P, V, H, W, int(bool(flip)),
+                                             _ptr(res.get("linear")), _ptr(res.get("srgb")), _ptr(res.get("u8")),
+                                             self._stream(stream_handle)))
+        self._keep = [m, k, l]
+        return res
+
+    def workspace_tensor(self, name: str, count: int = None):
+        """The first `count` floats (default: all) of an internal buffer of the last call as a cuda tensor: a copy made on
+        torch's current stream, behind the call that filled the buffer; nothing waits and nothing reaches the host."""
+        torch = self._torch
+        ptr, cnt = C.c_void_p(), C.c_int64()
+        self._check(self.lib.rc_workspace_ptr(self._h, name.encode(), C.byref(ptr), C.byref(cnt)))
+        count = cnt.value if count is None else int(count)
+        if not 0 <= count <= cnt.value:
+            raise ValueError(f"workspace {name!r} holds {cnt.value} floats, {count} were asked for")
+        out = torch.empty(count, dtype=torch.float32, device=f"cuda:{self.device}")
+        if count:
+            _memcpy_d2d_async(out.data_ptr(), ptr.value, count * 4, self._stream())
+        return out
+
     # -- material stage -------------------------------------------------------------------------------
     def material_grad_layout(self):
         """rc_material_grad_layout: [(tensor name, offset, shape)] of the MaterialShader gradient buffer (the material_grid
@@ -2099,3 +2205,13 @@ def _memcpy_d2h(dst: int, src: int, nbytes: int):
     rc = hip.hipMemcpy(dst, src, nbytes, 2)  # hipMemcpyDeviceToHost
     if rc != 0:
         raise RuntimeError(f"hipMemcpy failed: {rc}")
+
+
+def _memcpy_d2d_async(dst: int, src: int, nbytes: int, stream):
+    """hipMemcpyAsync device->device on `stream` through the HIP runtime torch already loaded."""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMemcpyAsync.restype = C.c_int
+    rc = hip.hipMemcpyAsync(dst, src, nbytes, 3, stream)  # hipMemcpyDeviceToDevice
+    if rc != 0:
+        raise RuntimeError(f"hipMemcpyAsync failed: {rc}")
