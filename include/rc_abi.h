@@ -167,7 +167,9 @@ typedef struct {
 
 /* ---- material stage (config 3): BaseMaterialModel.__call__ with use_material / use_light_sampler
  * (internal/models.py:1144-1254, 1398-1694).  Explicit random inputs for everything the reference
- * draws with jax.random on that path; Ks = round(K (1 - diffuse_fraction)), Kd = K - Ks, Kc = Kd / 2. */
+ * draws with jax.random on that path.  Member sizes: Ks = round(K (1 - diffuse_fraction)), Kd = round(K diffuse_fraction),
+ * Kc = round(Kd / 2), Kl = Kd - Kc, every round() Python's (half to even: K = 10 at 0.5 gives Kd = 5, Kc = 2, Kl = 3), as
+ * rc_material_randoms_plan sizes them.  A K whose Ks + Kd != K (K = 5 at 0.5) is refused with RC_ERR_UNSUPPORTED. */
 typedef struct {
   const float* gumbel;            /* [n, S_last]  categorical pick of the shading sample (models.py:1418-1438) */
   const float* vmf_noise;         /* [n, 128, 3]  N(0,1): LightMLP.get_vmfs means_random (light_sampler.py:142-144) */

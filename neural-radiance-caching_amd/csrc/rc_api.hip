@@ -20,6 +20,7 @@
 #include "rc_internal.h"
 #include "rc_pack_host.h"
 #include "rc_itof_host.h"
+#include "rc_prng_host.h"     // rc_round_half_even: the split of K, as the randoms plan sizes its members
 
 void rc_launch_hashgrid_src(const RcGridDev& g, const float* points, int soa_in, const int32_t* src, int64_t n_src,
                             int64_t n, float* out, int feature_major, int64_t ldo, float contract_radius,
@@ -1800,10 +1801,13 @@ int material_check(rc_handle* h, const rc_rays* rays, const rc_material_randoms*
   const std::string w = who;
   if ((rc = check_rays(h, rays, who))) return rc;
   const rc_config& c = h->cfg;
-  sp.Ks = (int)lround(K * (1.0 - (double)c.diffuse_sample_fraction));
-  sp.Kd = (int)lround(K * (double)c.diffuse_sample_fraction);
-  sp.Kc = (int)lround(0.5 * sp.Kd);
+  // Python's round (half to even), as importance_sample_rays and everything that sizes the random tensors
+  sp.Ks = rc_round_half_even(K * (1.0 - (double)c.diffuse_sample_fraction));
+  sp.Kd = rc_round_half_even(K * (double)c.diffuse_sample_fraction);
+  sp.Kc = rc_round_half_even(0.5 * sp.Kd);
   const int Ks = sp.Ks, Kd = sp.Kd, Kc = sp.Kc;
+  if (Ks + Kd != K)
+    return fail(h, RC_ERR_UNSUPPORTED, w + ": num_secondary_samples does not split into Ks + Kd (round half to even)");
   if (K < 2 || Ks < 1 || Kd < 2 || Kc < 1 || Kd - Kc < 1 || Ks + Kd > 64)
     return fail(h, RC_ERR_UNSUPPORTED, w + ": num_secondary_samples must give 1 <= Ks, 2 <= Kd, Ks + Kd <= 64");
   if (c.num_vmf != 128) return fail(h, RC_ERR_UNSUPPORTED, w + ": num_vmf must be 128");

@@ -41,6 +41,7 @@ Tolerances (u = 2^-24, every bound is on |device - fp64 reference|; S samples, a
                  order, so the device has to equal the float32 restatement bit for bit
 No case and no element is excused."""
 import os
+import sys
 
 import numpy as np
 
@@ -121,7 +122,11 @@ def out_shape(kernel, slot, i):
 
 
 class Cases:
-    def __init__(self):
+    """`spec`: the module that describes the kernels of a case table -- KERNELS, SLOTS, INT_SLOTS, out_shape, reference, the
+    two file magics -- this one unless another driver's table (tests/matstage_ref.py) brings its own."""
+
+    def __init__(self, spec=None):
+        self.spec = spec or sys.modules[__name__]
         self.bufs, self.stored, self.launches, self.producer = [], [], [], {}
         self._chain, self._floors = {}, None
 
@@ -140,13 +145,13 @@ class Cases:
     def launch(self, kernel, name, family, ints=None, flts=None, outs=(), **bufs):
         """`bufs`: slot -> buffer number (inputs); `outs`: the output slots to allocate.  Every other slot is a null pointer."""
         ints, flts = dict(ints or {}), {k: float(np.float32(v)) for k, v in (flts or {}).items()}
-        si, sf, sb, so = SLOTS[kernel]
+        si, sf, sb, so = self.spec.SLOTS[kernel]
         assert set(ints) == set(si) and set(flts) == set(sf) and set(bufs) <= set(sb) and set(outs) <= set(so), (kernel, name)
         b = {s: -1 for s in sb}
         b.update(bufs)
         li = len(self.launches)
         for s in outs:
-            b[s] = self.out(out_shape(kernel, s, ints))
+            b[s] = self.out(self.spec.out_shape(kernel, s, ints))
             self.producer[b[s]] = (li, s)
         self.launches.append({"kernel": kernel, "name": name, "family": family, "ints": ints, "flts": flts, "bufs": b})
         return li
@@ -177,8 +182,8 @@ class Cases:
             return dev[idx][GUARD:-GUARD]
         if idx not in self._chain:
             li, slot = self.producer[idx]
-            v = reference(self, li, np.float32)[slot]
-            self._chain[idx] = (v.astype(np.int32).view(np.float32) if slot in INT_SLOTS else v.astype(np.float32)).ravel()
+            v = self.spec.reference(self, li, np.float32)[slot]
+            self._chain[idx] = (v.astype(np.int32).view(np.float32) if slot in self.spec.INT_SLOTS else v.astype(np.float32)).ravel()
         return self._chain[idx]
 
 
@@ -640,7 +645,7 @@ def render(cs, li, ref, mut=None):
     """The output buffers a device that computed `ref` in float32 would leave: {buffer: floats with guards}."""
     L = cs.launches[li]
     out = {}
-    for slot in SLOTS[L["kernel"]][3]:
+    for slot in cs.spec.SLOTS[L["kernel"]][3]:
         idx = L["bufs"][slot]
         if idx < 0:
             continue
@@ -648,7 +653,7 @@ def render(cs, li, ref, mut=None):
             out[idx] = cs.bufs[idx].copy()
             continue
         v = ref[slot]
-        v = v.astype(np.int32).view(np.float32) if slot in INT_SLOTS else v.astype(np.float32)
+        v = v.astype(np.int32).view(np.float32) if slot in cs.spec.INT_SLOTS else v.astype(np.float32)
         buf = cs.bufs[idx].copy()
         buf[GUARD:GUARD + v.size] = v.ravel()
         n = L["ints"].get("n", 0)
@@ -664,11 +669,11 @@ def check(cs, li, got, ref, tol):
     """`got`: {buffer: floats with guards}.  Returns (failures [(slot, what, figure)], {slot: max error / tolerance})."""
     L = cs.launches[li]
     bad, ratio = [], {}
-    for slot in SLOTS[L["kernel"]][3]:
+    for slot in cs.spec.SLOTS[L["kernel"]][3]:
         idx = L["bufs"][slot]
         if idx < 0:
             continue
-        shape = out_shape(L["kernel"], slot, L["ints"])
+        shape = cs.spec.out_shape(L["kernel"], slot, L["ints"])
         size = int(np.prod(shape))
         buf = got[idx]
         if not (is_canary(buf[:GUARD]).all() and is_canary(buf[GUARD + size:]).all()):
@@ -679,7 +684,7 @@ def check(cs, li, got, ref, tol):
                 bad.append((slot, "written", int((~is_canary(g)).sum())))
             continue
         want = np.asarray(ref[slot])
-        if slot in INT_SLOTS:
+        if slot in cs.spec.INT_SLOTS:
             if not np.array_equal(g.view(np.int32).astype(np.int64), want.ravel()):
                 bad.append((slot, "index", g.view(np.int32).tolist()))
             continue
@@ -719,8 +724,8 @@ def write_case_file(path, cs):
         at += buf.size if stored else 0
     rec = np.full((len(cs.launches), nf), -1, np.int64)
     for n, L in enumerate(cs.launches):
-        si, sf, sb, _ = SLOTS[L["kernel"]]
-        rec[n, 0] = KERNELS.index(L["kernel"])
+        si, sf, sb, _ = cs.spec.SLOTS[L["kernel"]]
+        rec[n, 0] = cs.spec.KERNELS.index(L["kernel"])
         rec[n, 1:1 + N_INT] = 0
         rec[n, 1 + N_INT:1 + N_INT + N_FLT] = 0
         for j, s in enumerate(si):
@@ -730,7 +735,7 @@ def write_case_file(path, cs):
         for j, s in enumerate(sb):
             rec[n, 1 + N_INT + N_FLT + j] = L["bufs"][s]
     with open(path, "wb") as fh:
-        np.array([MAGIC_CASES, len(cs.bufs), len(cs.launches), nf], np.int64).tofile(fh)
+        np.array([cs.spec.MAGIC_CASES, len(cs.bufs), len(cs.launches), nf], np.int64).tofile(fh)
         np.array(table, np.int64).reshape(-1, 2).tofile(fh)
         rec.tofile(fh)
         for buf, stored in zip(cs.bufs, cs.stored):
@@ -742,7 +747,7 @@ def read_results(path, cs):
     """{buffer: floats with guards} of every output buffer, and the driver's wall time in seconds."""
     head = np.fromfile(path, np.int64, 4)
     outs = [n for n, s in enumerate(cs.stored) if not s]
-    assert head[0] == MAGIC_RESULTS and head[1] == len(outs) and head[2] == len(cs.launches), head
+    assert head[0] == cs.spec.MAGIC_RESULTS and head[1] == len(outs) and head[2] == len(cs.launches), head
     data = np.fromfile(path, np.float32, offset=32)
     assert data.size == sum(cs.bufs[n].size for n in outs), data.size
     got, at = {}, 0

@@ -734,6 +734,72 @@ def test_material_stage_golden_fp64(rc_smooth):
     assert np.abs(cres["rgb"].cpu().numpy() - g["render_cache_rgb"]).max() <= 1e-5
 
 
+def _smooth_rc_at(K):
+    from nrc_amd import rc_ext
+    cfg = nrc_amd.hotdog_config(num_secondary_samples=K)
+    rc = rc_ext.RadianceCache(cfg, 0)
+    rc.load_weights(common.weights_material_np(smooth=True))
+    return cfg, rc
+
+
+def test_material_stage_k10_rounds_half_to_even_like_the_randoms():
+    """K = 10 at diffuse_sample_fraction 0.5: Kd = 5 and Kc = round(2.5) = 2 with Python's round, which sizes cos_u1/u2
+    [n, 2] and vmf_v [n, 3, 2] (oracle.material_ref.draw_randoms, prng.material_split).  material_check used lround
+    (Kc = 3): cos_u1 read past its end, vmf_v / vmf_tmp at the wrong stride.  Picks handed over, smooth weights: every
+    material key within the 1e-4 of test_material_stage_smooth_field_holds_1e4."""
+    from oracle import material_ref
+    cfg, rc = _smooth_rc_at(10)
+    n = 5
+    rays = nrc_amd.synthetic_rays(n, seed=77)
+    rnd = material_ref.draw_randoms(cfg, n, seed=3)
+    assert rnd["spec_u1"].shape == (n, 5) and rnd["cos_u1"].shape == (n, 2) and rnd["vmf_v"].shape == (n, 3, 2)
+    ref = material_ref.material_forward(common.to_torch(common.weights_material_np(True)), cfg, common.rays_torch(rays), rnd)
+    picks = dict(inds=ref["inds"][:, 0].numpy(), spec_inds=ref["debug"]["specular"]["inds"].numpy(),
+                 diff_inds=ref["debug"]["diffuse"]["inds"].numpy())
+    cres, mres = _material_with_picks(rc, rays, rnd, picks)
+    assert np.array_equal(rc.workspace("inds", np.int32)[:n], picks["inds"])
+    r = ref["render"]
+    for k in MAT_ALL_KEYS:
+        a = mres[k].cpu().numpy()
+        d = np.abs(a - r[k].numpy().reshape(a.shape)).max()
+        print(f"K=10 {k}: {d:.3e}")
+        assert d <= RGB_TOL, (k, d)
+    smp = rc.workspace("sec_samples")[:n * 10 * 5].reshape(n, 10, 5)
+    for blk, name in ((slice(0, 5), "specular"), (slice(5, 10), "diffuse")):
+        assert np.abs(smp[:, blk, :3] - ref["debug"][name]["local_lightdirs"].numpy()).max() <= RGB_TOL, name
+
+
+def test_material_stage_k5_is_refused_with_the_outputs_untouched():
+    """K = 5 at 0.5: round(2.5) + round(2.5) = 4, not 5 -- refused with RC_ERR_UNSUPPORTED as rc_material_randoms_plan
+    refuses it, before anything is launched: every float of both output tables keeps the value it had."""
+    import ctypes as C
+    from nrc_amd import rc_ext
+    from oracle import material_ref
+    cfg, rc = _smooth_rc_at(5)
+    n = 5
+    rays = nrc_amd.synthetic_rays(n, seed=77)
+    rnd = material_ref.draw_randoms(cfg, n, seed=3)
+    r, held, n_ = rc._rays_struct(rays.hot_fields())
+    crnd, mr = rc._material_randoms(rnd, n, 5, held)
+    c_names = [nm for nm, _ in rc_ext.OUTPUTS if nm not in ("env_map_rgb", "rgb_no_env")]
+    m_names = [nm for nm, _ in rc_ext.MAT_OUTPUTS]
+    cshape = lambda nm: (n, 3) if rc_ext.OUTPUTS[rc_ext.OUTPUT_ID[nm]][1] == 3 else (n,)
+    mshape = lambda nm: (n, 3) if rc_ext.MAT_OUTPUTS[rc_ext.MAT_OUTPUT_ID[nm]][1] == 3 else (n,)
+    fill = lambda shape: torch.full(shape, 0.625, dtype=torch.float32, device="cuda:0")
+    cres, cout = rc._outputs(rc_ext.OUTPUTS, c_names, cshape, {nm: fill(cshape(nm)) for nm in c_names})
+    mres, mout = rc._outputs(rc_ext.MAT_OUTPUTS, m_names, mshape, {nm: fill(mshape(nm)) for nm in m_names})
+    code = rc.lib.rc_render_material(rc._h, C.byref(r), n, C.byref(crnd), C.byref(mr), 5, C.byref(cout), C.byref(mout),
+                                     rc._stream())
+    torch.cuda.synchronize()
+    assert code == -5, code                                             # RC_ERR_UNSUPPORTED
+    assert b"Ks + Kd" in (rc.lib.rc_last_error(rc._h) or b"")
+    for nm, t in list(cres.items()) + list(mres.items()):
+        assert bool((t == 0.625).all()), nm
+    with pytest.raises(rc_ext.RcError) as e:
+        rc.render_material(rays.hot_fields(), rnd)
+    assert e.value.code == -5
+
+
 def test_material_stage_white_noise_with_picks(rc_smooth):
     """White-noise tables with the picks handed over: every ray is compared (no `same` mask).  One-ulp differences of the
     secondary sample positions are amplified by the 2048-cell random tables (the fp32 and fp64 oracles differ by 1e-3
