@@ -432,6 +432,24 @@ typedef struct rc_transient_outputs { float* ptr[RC_TOUT_COUNT]; } rc_transient_
 int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
                         const rc_randoms* shadow_rnd, const rc_transient_outputs* out, void* stream);
 
+/* Time slices of the histograms (the trainer's light-in-flight frames, engine/trainer.py:1693-1726) without the
+ * histograms: for every ray and every time t the value  w * v[ceil t] + (1 - w) * v[floor t],  w = t - floor t,  of
+ * v = rgb / the filtered direct part / the indirect part, computed from the bins that reach floor t and ceil t only
+ * (DESIGN.md section 4.22).  Same contract as rc_render_transient: same rays (lights and cam_origins required), same
+ * randoms, same workspace set, use_occlusions handles included; the direct part spills into the next ray of the batch in
+ * the same way.  `extra` (nullable) may ask for the outputs of the steady-state composite -- RC_TOUT_ACC, the four
+ * RC_TOUT_DISTANCE_*, MEANS, NORMALS, NORMALS_PRED, RAY_DISTS, LIGHT_DISTS; any other non-NULL pointer of it needs every
+ * bin and returns RC_ERR_UNSUPPORTED.  Each call repeats the whole trace up to the per-bin heads. */
+#define RC_TSLICE_MAX 8
+typedef struct rc_transient_slices {
+  int32_t count;                 /* 1 .. RC_TSLICE_MAX */
+  float t[RC_TSLICE_MAX];        /* fractional bin index, 0 <= t <= n_bins - 1 */
+  float* rgb; float* direct; float* indirect;   /* device, [n][count][3]; NULL = not wanted, at least one set */
+} rc_transient_slices;
+int rc_render_transient_slices(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                               const rc_randoms* shadow_rnd, const rc_transient_slices* s,
+                               const rc_transient_outputs* extra /* nullable */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * On-device ray generation: camera_utils.pixels_to_rays + cast_ray_batch
  * (internal/camera_utils.py:896-1072, 1225-1329) for one camera: ProjectionType.PERSPECTIVE / FISHEYE /

@@ -53,6 +53,28 @@ def cast_ray_batch(rc, camera: Camera, pix_x_int=None, pix_y_int=None, rect=None
     return rc.cast_rays(camera, pix_x_int, pix_y_int, rect, pix_jitter)
 
 
+def chunk_rows(model, width: int, rows_per_chunk: Optional[int] = None) -> int:
+    """Rows of pixels of one chunk of render_camera's loop: rows_per_chunk, or whole rows covering >= 16 384 rays."""
+    return rows_per_chunk or max(1, max(model.config.render_chunk_size, 16384) // width)
+
+
+def chunk_randoms(model, rng, n: int):
+    """The sampler jitter of one chunk of n rays, generated in HBM from the keys the reference's render_image ->
+    render_eval_fn -> model chain would derive for it (models.py:2445, train_utils.py:3794-3818; prng.py) -> (randoms,
+    the key of the next chunk); (None, None) for rng None (deterministic sampling branch)."""
+    from . import prng
+    if rng is None:
+        return None, None
+    apply_key, rng = prng.chunk_keys(rng)
+    s_key = prng.cache_keys(prng.model_cache_rng(apply_key))["sampler"]
+    jit = []
+    for _ in model.config.sampling_strategy:                # sampling.py:341 / :408
+        k, s_key = prng.random_split(s_key)
+        jit.append(model.rc.prng_fill(k, (n,), "uniform"))
+        _, s_key = prng.random_split(s_key)
+    return {"jitter": jit}, rng
+
+
 def render_camera(model, camera: Camera, height: int, width: int, passes=("cache",), rows_per_chunk: Optional[int] = None,
                   keys=("rgb", "acc", "distance_median"), streams: int = 1, to_host: bool = True, rng=None):
     """Image of one camera without a host-side ray batch: rows of pixels are cast on the device and rendered
@@ -67,10 +89,7 @@ def render_camera(model, camera: Camera, height: int, width: int, passes=("cache
     from . import prng
     if rng is not None:
         rng = prng.as_key(rng)
-    levels = [lvl[2] for lvl in model.config.sampling_strategy]
-
-    chunk = model.config.render_chunk_size
-    rows = rows_per_chunk or max(1, max(chunk, 16384) // width)
+    rows = chunk_rows(model, width, rows_per_chunk)
     dev = torch.device(f"cuda:{model.device}")
     pool = [torch.cuda.Stream(device=dev) for _ in range(max(1, streams))] if streams > 1 else [torch.cuda.current_stream(dev)]
     start = torch.cuda.Event()
@@ -83,16 +102,7 @@ def render_camera(model, camera: Camera, height: int, width: int, passes=("cache
             st.wait_event(start)
         with torch.cuda.stream(st):
             rays = cast_ray_batch(model.rc, camera, rect=(0, y0, width, hgt))
-            randoms = None
-            if rng is not None:
-                apply_key, rng = prng.chunk_keys(rng)
-                s_key = prng.cache_keys(prng.model_cache_rng(apply_key))["sampler"]
-                jit = []
-                for _ in levels:                                # sampling.py:341 / :408
-                    k, s_key = prng.random_split(s_key)
-                    jit.append(model.rc.prng_fill(k, (hgt * width,), "uniform"))
-                    _, s_key = prng.random_split(s_key)
-                randoms = {"jitter": jit}
+            randoms, rng = chunk_randoms(model, rng, hgt * width)
             r = model.apply(None, randoms, rays, passes=passes)["render"]
             for k in keys:
                 v = r[k]

@@ -55,6 +55,7 @@ const char* const kRawPaths[RAW_COUNT] = {"params/MaterialShader/bottleneck_laye
 struct Packs {
   DevBuf dens[RC_MAX_LEVELS], train[RC_MAX_LEVELS];
   DevBuf shader, fused, fused_front, envmap, t_shader, t_bins, t_taps;
+  DevBuf t_slice_slf, t_slice_irr;       // k_transient_slice: the two per-bin heads as plain columns (repack_transient)
   DevBuf pair[RC_MAX_GRID_LEVELS];       // level-2 density + appearance tables interleaved (cell tables on dense levels)
   DevBuf cell[2][RC_MAX_GRID_LEVELS];    // dense levels of proposal grids 0 / 1 as cell tables
   DevBuf rec[3][RC_MAX_GRID_LEVELS];     // hashed levels of grids 0-2 as cell records (kLevelHRec)
@@ -535,7 +536,8 @@ int upload(rc_handle* h, DevBuf& b, const std::vector<float>& v) {
 }
 template <class Buf> void free_buf(Buf& b) { if (b.p) (void)hipFree(b.p); b = Buf{}; }
 void free_packs(Packs& P) {
-  for (DevBuf* b : {&P.shader, &P.fused, &P.fused_front, &P.envmap, &P.t_shader, &P.t_bins, &P.t_taps}) free_buf(*b);
+  for (DevBuf* b : {&P.shader, &P.fused, &P.fused_front, &P.envmap, &P.t_shader, &P.t_bins, &P.t_taps, &P.t_slice_slf,
+                    &P.t_slice_irr}) free_buf(*b);
   for (int l = 0; l < RC_MAX_LEVELS; ++l) { free_buf(P.dens[l]); free_buf(P.train[l]); }
   for (int l = 0; l < RC_MAX_GRID_LEVELS; ++l) {
     free_buf(P.pair[l]);
@@ -1358,6 +1360,7 @@ struct RenderArgs {
   rc_rays rays; rc_randoms rnd; bool have_rnd; int64_t n; uint32_t mask; rc_outputs out; int slot; bool fused;
   const rc_transient_outputs* tout = nullptr; const float* cam_origins = nullptr;
   const rc_randoms* shadow_rnd = nullptr; bool weights_only = false; bool force_grad = false;
+  const rc_transient_slices* tslices = nullptr;   // rc_render_transient_slices: k_transient_slice in place of k_transient_bins
   // rc_interlevel_backward's training forward: the sampler levels only (sdist / tdist / means / density / weights of every
   // level in the workspace, nothing behind them), resampling at `anneal` (< 0: the config's render-time value)
   bool sampler_only = false; float anneal = -1.0f;
@@ -2113,6 +2116,7 @@ int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_ra
 }  // extern "C"
 
 #include "rc_transient_host.inc"
+#include "rc_transient_slice_host.inc"
 #include "rc_batch_host.inc"
 #include "rc_train_host.inc"
 #include "rc_interlevel_host.inc"

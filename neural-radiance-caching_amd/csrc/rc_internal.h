@@ -382,6 +382,26 @@ int rc_transient_bins_frags();
 void rc_launch_transient_shader(const RcTransShaderArgs& a, hipStream_t stream);
 void rc_launch_transient_bins(const RcTransBinsArgs& a, hipStream_t stream);
 
+// Time slices of the histograms without the histograms (rc_transient_slice.hip): launched in place of
+// k_transient_bins.  The two per-bin heads as plain columns: column f = 3 bin + channel of a head is kRcSliceStride*
+// consecutive floats, value j = 2 step + half of the activation order k_transient_shader stores (the steps_acc tables),
+// then the bias.
+constexpr int kRcSliceMax = RC_TSLICE_MAX;
+constexpr int kRcSliceStrideSlf = 132;     // 128 rows + bias, padded to whole float4
+constexpr int kRcSliceStrideIrr = 68;      // 64 rows + bias, padded
+struct RcTransSliceArgs {
+  int64_t n_rays;
+  const float* w_slf; const float* w_irr;  // [2100][kRcSliceStrideSlf], [2100][kRcSliceStrideIrr]
+  const float* slf_feat; const float* irr_feat; const float* tshade; const float* weights;   // as RcTransBinsArgs
+  float exposure, shift, max_dists, irradiance_bias, slf_rgb_bias, indirect_scale, rgb_max, light_near;
+  int32_t bin_zero_threshold_light, light_zero, n_taps;
+  const float* taps;
+  int32_t count;                           // 1 .. kRcSliceMax
+  float t[kRcSliceMax];                    // fractional bin index, 0 <= t <= 699
+  float* out_rgb; float* out_direct; float* out_indirect;                // [n_rays][count][3], NULL = not wanted
+};
+void rc_launch_transient_slice(const RcTransSliceArgs& a, hipStream_t stream);
+
 
 // ---------------------------------------------------------------------------------------------
 // On-device ray generation (rc_camera.hip)

@@ -130,6 +130,27 @@ int repack_transient(rc_handle* h) {
     if (rc) return rc;
   }
   {
+    // k_transient_slice (rc_transient_slice.hip): the same two heads as plain columns.  The activations k_transient_shader
+    // stores are in MFMA operand order -- value 2 k + h of a sample is half h of step k -- so the columns are built from
+    // the same step tables: row j of a column is the weight that meets value j, then the bias.
+    std::vector<Step> s4, s2;
+    steps_acc(s4, 4, 0); step_bias(s4);
+    steps_acc(s2, 2, 0); step_bias(s2);
+    const int cols = 3 * h->tcfg.n_bins;
+    auto plain = [&](const HostLayer* L, const std::vector<Step>& st, int stride) {
+      std::vector<float> v((size_t)cols * stride, 0.0f);
+      for (int col = 0; col < cols; ++col)
+        for (size_t k = 0; k < st.size(); ++k)
+          for (int hh = 0; hh < 2; ++hh)
+            if ((int)(2 * k + hh) < stride) v[(size_t)col * stride + 2 * k + hh] = pack_value(st[k], hh, Col{L, col, 0, true});
+      return v;
+    };
+    static_assert(kRcSliceStrideSlf >= 2 * 64 + 1 && kRcSliceStrideIrr >= 2 * 32 + 1, "a column holds every row and the bias");
+    int rc = upload(h, h->packs.t_slice_slf, plain(lo, s4, kRcSliceStrideSlf));
+    if (rc) return rc;
+    if ((rc = upload(h, h->packs.t_slice_irr, plain(ro, s2, kRcSliceStrideIrr)))) return rc;
+  }
+  {
     // temporal filter (render.py:411-413): taps -round(4 sigma) .. round(4 sigma), exp(-k^2 / 2 sigma^2) - exp(-8), normalised
     std::vector<float> taps;
     const float sigma = h->tcfg.tfilter_sigma;
@@ -154,6 +175,8 @@ int repack_transient(rc_handle* h) {
   h->packed_dirty = false;
   return RC_OK;
 }
+
+void enqueue_transient_slice(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st);      // rc_transient_slice_host.inc
 
 // After the proposal sampler and the appearance-grid lookup: shader, per-bin heads + compositing, scalar composites.
 // `w` is workspace set 0 (the shadow rays use its extras and the secondary set).
@@ -214,7 +237,9 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipS
     s.irr_feat = w.t_irr.p; s.slf_feat = w.t_slf.p; s.tshade = w.tshade.p;
     rc_launch_transient_shader(s, st);
   }
-  {
+  if (A.tslices) {
+    enqueue_transient_slice(h, A, w, st);       // rc_render_transient_slices: the bins that reach the asked times only
+  } else {
     RcTransBinsArgs b{};
     b.n_rays = n; b.wstream = h->packs.t_bins.p;
     b.slf_feat = w.t_slf.p; b.irr_feat = w.t_irr.p; b.tshade = w.tshade.p; b.weights = w.weights[NL - 1].p;
@@ -256,18 +281,19 @@ int rc_set_transient(rc_handle* h, const rc_transient_config* t) {
   RC_CATCH(h)
 }
 
-int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
-                        const rc_randoms* shadow_rnd, const rc_transient_outputs* out, void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  RoctxScope roctx_call("rc_render_transient");
-  if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_transient: call rc_set_transient first");
-  if (!rays || !out) return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: null rays/outputs");
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: negative n_rays");
+namespace {
+
+// rc_render_transient and rc_render_transient_slices (`slices` non-NULL: k_transient_slice in place of k_transient_bins;
+// `out` then holds the composite outputs asked for besides): checks of the rays, workspace, launch sequence
+int render_transient_impl(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                          const rc_randoms* shadow_rnd, const rc_transient_outputs* out, const rc_transient_slices* slices,
+                          void* stream_v, const std::string& who) {
+  if (!rays || !out) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/outputs");
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n_rays");
   if (n == 0) return RC_OK;
   int rc;
-  if ((rc = check_rays(h, rays, "rc_render_transient"))) return rc;
-  if (!rays->lights || !cam_origins) return fail(h, RC_ERR_INVALID_ARG, "rc_render_transient: lights and cam_origins are required");
+  if ((rc = check_rays(h, rays, who.c_str()))) return rc;
+  if (!rays->lights || !cam_origins) return fail(h, RC_ERR_INVALID_ARG, who + ": lights and cam_origins are required");
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
@@ -289,7 +315,7 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   A.have_rnd = rnd != nullptr;
   if (rnd) A.rnd = *rnd;
   A.n = n; A.mask = RC_PASS_CACHE; A.fused = false; A.slot = -1;
-  A.tout = out; A.cam_origins = cam_origins; A.shadow_rnd = shadow_rnd; A.force_grad = h->tcfg.use_occlusions != 0;
+  A.tout = out; A.tslices = slices; A.cam_origins = cam_origins; A.shadow_rnd = shadow_rnd; A.force_grad = h->tcfg.use_occlusions != 0;
   // outputs shared with the steady-state compositing kernel
   memset(&A.out, 0, sizeof(A.out));
   A.out.ptr[RC_OUT_ACC] = out->ptr[RC_TOUT_ACC];
@@ -305,6 +331,17 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   enqueue_all(h, A, w, st);
   RC_HIP(h, hipGetLastError());
   return RC_OK;
+}
+
+}  // namespace
+
+int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                        const rc_randoms* shadow_rnd, const rc_transient_outputs* out, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  RoctxScope roctx_call("rc_render_transient");
+  if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_transient: call rc_set_transient first");
+  return render_transient_impl(h, rays, cam_origins, n, rnd, shadow_rnd, out, nullptr, stream_v, "rc_render_transient");
   RC_CATCH(h)
 }
 

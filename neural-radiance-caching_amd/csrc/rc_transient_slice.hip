@@ -1,0 +1,269 @@
+// Time slices of the time-resolved cache without the histograms (rc_render_transient_slices): the
+// trainer's light-in-flight frame (engine/trainer.py:1693-1726, _save_path_evaluation)
+//     cache_time_slice = w * cache_rgb[..., ceil t, :] + (1 - w) * cache_rgb[..., floor t, :],   w = t - floor t
+// from the bins that reach floor t and ceil t only.
+//
+//   k_transient_slice   launched in place of k_transient_bins (rc_transient.hip) behind the unchanged k_transient_shader,
+//                       one wavefront per ray, up to RC_TSLICE_MAX times per launch.
+//
+// Indirect part at target bin y (shift_map_coordinates, render.py:480-507, the arithmetic of k_transient_bins' tile
+// epilogue): sample s with time shift d reaches y from the source bins i0 = floor(y - d) and i0 + 1.  The two targets of
+// a time share a source, so a sample needs at most 3 source bins x 3 channels of each head: a lane takes ONE (time,
+// sample, source bin, channel), evaluates the two head values as plain fp32 dot products of the sample's stored
+// activations (LDS, one row per sample) with one weight column (global, contiguous), and leaves weight * value in LDS;
+// a second pass adds the 32 samples of each (time, target, channel) in sample order.
+// Direct part: the floor / ceil scatter of this ray's and the previous ray's samples into the ray's LDS histogram and the
+// temporal filter, both as k_transient_bins does them, the filter for the 2 x 3 entries of each time only.
+// Nothing is reduced across lanes and every sum has a fixed order: two launches are bitwise equal, and a time's result
+// does not depend on the other times of the launch.
+#include "rc_internal.h"
+#include "rc_dev_sample.h"
+
+using namespace rcdev;
+
+namespace {
+
+constexpr int kBins = 700;
+constexpr int kHist = kBins * 3;
+constexpr int kMaxTaps = 32;                     // temporal filter taps handled by the unrolled window
+constexpr int kPadD = 3 * (kMaxTaps / 2);        // zeros on both sides of the direct histogram
+constexpr int kSliceWaves = 4;                   // rays of a workgroup (the waves share nothing)
+constexpr int kItems = 32 * 9;                   // (sample, source bin slot, channel) of one time
+constexpr int kHistD = kHist + 2 * kPadD;
+constexpr int kRegion = kRcSliceMax * kItems > kHistD ? kRcSliceMax * kItems : kHistD;   // direct histogram, then the items' values
+constexpr int kSP = 7;
+constexpr int kSliceWaveLds = 32 * kRcSliceStrideSlf + 32 * kRcSliceStrideIrr + kRegion + kSP * 32;   // floats
+static_assert(kSliceWaves * kSliceWaveLds * 4 <= 160 * 1024, "a workgroup's rays fit the LDS of a compute unit");
+static_assert(kRcSliceMax * 6 <= 64, "one lane per (time, target, channel)");
+
+// k_transient_bins' softplus (rc_transient.hip softplus_bins), the same three lines
+__device__ __forceinline__ float softplus_bins(float x) {
+  const float e = __builtin_amdgcn_exp2f(-fabsf(x) * 1.44269504088896341f);
+  return fmaxf(x, 0.0f) + __builtin_amdgcn_logf(1.0f + e) * 0.693147180559945309f;
+}
+
+// floor(y - d) as a bin index; far outside the histogram it is held at -8 / 708 (every bin next to it is outside too)
+__device__ __forceinline__ int src_bin(float y, float d) { return (int)fminf(fmaxf(floorf(y - d), -8.0f), (float)(kBins + 8)); }
+
+__global__ __launch_bounds__(kSliceWaves * 64) void k_transient_slice(RcTransSliceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int fl = lane & 31, h = lane >> 5;
+  const int64_t ray = (int64_t)blockIdx.x * kSliceWaves + wave;
+  if (ray >= a.n_rays) return;                     // no workgroup barrier below: the waves share nothing
+  const int64_t n = a.n_rays * 32;                 // samples
+  float* xs = lds_dyn + wave * kSliceWaveLds;      // [32 samples][kRcSliceStrideSlf]: value j = 2 step + half
+  float* xi = xs + 32 * kRcSliceStrideSlf;         // [32 samples][kRcSliceStrideIrr]
+  float* region = xi + 32 * kRcSliceStrideIrr;
+  float* hist_d = region + kPadD;                  // direct histogram (before the temporal filter), zero padded
+  float* vals = region;                            // afterwards: [time][sample][slot][channel] weight * value
+  float* sp = region + kRegion;                    // [kSP][32] per-sample parameters
+  enum { P_W = 0, P_TIB0, P_TIB1, P_TIB2, P_DIND, P_LO, P_HI };
+  const bool want_direct = a.out_rgb || a.out_direct, want_indirect = a.out_rgb || a.out_indirect;
+
+  for (int e = lane; e < kHistD; e += 64) region[e] = 0.0f;
+  if (lane < 32) {
+    const int64_t p = ray * 32 + lane;
+    const float ld = a.tshade[RC_TS_LDIST * n + p], in_w = a.weights[p], cdist = a.tshade[RC_TS_CAMDIST * n + p];
+    const float in_t0 = a.tshade[(RC_TS_TIB + 0) * n + p], in_t1 = a.tshade[(RC_TS_TIB + 1) * n + p],
+                in_t2 = a.tshade[(RC_TS_TIB + 2) * n + p], in_rd = a.tshade[RC_TS_RDIST * n + p];
+    sp[P_W * 32 + lane] = in_w;
+    sp[P_TIB0 * 32 + lane] = in_t0;
+    sp[P_TIB1 * 32 + lane] = in_t1;
+    sp[P_TIB2 * 32 + lane] = in_t2;
+    sp[P_DIND * 32 + lane] = (in_rd + a.shift) / a.exposure;          // k_transient_bins' P_DIND
+    // the window of bins zero_invalid_bins keeps (render_utils.py:1699-1767), with the comparisons of k_transient_bins
+    const bool kill = a.light_zero && ld < a.light_near;
+    auto close = [&](int b) { return (float)(b + a.bin_zero_threshold_light) * a.exposure < ld; };
+    auto far = [&](int b) { return ((float)b * a.exposure + cdist) > a.max_dists; };
+    int lo = (int)ceilf(ld / a.exposure) - a.bin_zero_threshold_light;
+    lo = min(max(lo, 0), kBins);
+    while (lo > 0 && !close(lo - 1)) --lo;
+    while (lo < kBins && close(lo)) ++lo;
+    int hi = (int)floorf((a.max_dists - cdist) / a.exposure);
+    hi = min(max(hi, -1), kBins - 1);
+    while (hi < kBins - 1 && !far(hi + 1)) ++hi;
+    while (hi >= 0 && far(hi)) --hi;
+    if (kill) { lo = kBins; hi = -1; }
+    sp[P_LO * 32 + lane] = __int_as_float(lo);
+    sp[P_HI * 32 + lane] = __int_as_float(hi);
+  }
+  if (want_indirect) {
+    // this ray's activations of the two head layers, one row per sample (lane & 31 = sample, lane >> 5 = which of the
+    // step's two values)
+#pragma unroll 8
+    for (int s = 0; s < 64; ++s) xs[fl * kRcSliceStrideSlf + 2 * s + h] = a.slf_feat[(ray * 64 + s) * 64 + lane];
+#pragma unroll 8
+    for (int s = 0; s < 32; ++s) xi[fl * kRcSliceStrideIrr + 2 * s + h] = a.irr_feat[(ray * 32 + s) * 64 + lane];
+  }
+  lds_sync<false>();
+
+  // this lane's (time, target, channel): lanes 6 ti + 2 c + g, g = 0 the floor bin, g = 1 the ceil bin
+  const int o_ti = lane / 6, o_c = (lane - 6 * o_ti) >> 1, o_g = lane & 1;
+  const bool o_ok = o_ti < a.count;
+  float o_t = a.t[0];
+#pragma unroll
+  for (int k = 1; k < kRcSliceMax; ++k) o_t = k == o_ti ? a.t[k] : o_t;
+  const int o_y0 = (int)floorf(o_t), o_y1 = (int)ceilf(o_t);
+  const int o_y = o_g ? o_y1 : o_y0;
+
+  float dv = 0.0f;
+  if (want_direct) {
+    // ---- direct light: k_transient_bins' scatter (render.py:436-477); bins >= 700 of the previous ray of the batch land
+    //      at the start of this ray's histogram
+    {
+      const int64_t sr = ray - 1 + h;
+      int il = -1, ih = -1;
+      float vl[3] = {0.0f, 0.0f, 0.0f}, vh[3] = {0.0f, 0.0f, 0.0f};
+      if (sr >= 0) {
+        const int64_t p = sr * 32 + fl;
+        const float d = (a.tshade[RC_TS_LDIST * n + p] + a.tshade[RC_TS_RDIST * n + p]) / a.exposure + a.shift / a.exposure;
+        const float low = fmaxf(floorf(d), 0.0f), high = ceilf(d);
+        const float w_high = d - low, w_low = 1.0f - w_high;
+        const int off = h == 0 ? kBins : 0;
+        // (held inside the int range first: a bin far outside the histogram is dropped either way)
+        il = (int)fminf(low, 4.0f * kBins) - off; ih = (int)fminf(fmaxf(high, -1.0f), 4.0f * kBins) - off;
+        if (il < 0 || il >= kBins) il = -1;
+        if (ih < 0 || ih >= kBins) ih = -1;
+        const float w = a.weights[p];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float val = w * (a.tshade[(RC_TS_DD + c) * n + p] + a.tshade[(RC_TS_DS + c) * n + p]);
+          vl[c] = val * w_low; vh[c] = val * w_high;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (il >= 0) atomicAdd(&hist_d[il * 3 + c], vl[c]);
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        if (ih >= 0) atomicAdd(&hist_d[ih * 3 + c], vh[c]);
+    }
+    lds_sync<false>();
+    // ---- temporal filter (render.py:406-417) of this lane's entry, k_transient_bins' three forms
+    float tp[kMaxTaps];
+#pragma unroll
+    for (int k = 0; k < kMaxTaps; ++k) tp[k] = k < a.n_taps ? a.taps[k] : 0.0f;
+    const int half_taps = (a.n_taps - 1) / 2;
+    if (o_ok) {
+      const int e = o_y * 3 + o_c;
+      if (a.n_taps > kMaxTaps) {
+        for (int k = 0; k < a.n_taps; ++k) {
+          const int yb = o_y - (k - half_taps);
+          if (yb >= 0 && yb < kBins) dv += a.taps[k] * hist_d[yb * 3 + o_c];
+        }
+      } else if (a.n_taps > 0) {
+        const float* win = hist_d + e + 3 * half_taps;        // tap k reads bin y - (k - half)
+        if (a.n_taps == 25) {
+#pragma unroll
+          for (int k = 0; k < 25; ++k) dv += tp[k] * win[-3 * k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < kMaxTaps; ++k)
+            if (k < a.n_taps) dv += tp[k] * win[-3 * k];
+        }
+      } else {
+        dv = hist_d[e];
+      }
+    }
+    lds_sync<false>();                             // the histogram is read: its LDS now takes the items' values
+  }
+
+  float iv = 0.0f;
+  if (want_indirect) {
+    // ---- one (time, sample, source bin slot, channel) per lane: weight * value of source bin floor(y0 - d) + slot
+    const int total = a.count * kItems;
+    for (int it0 = 0; it0 < total; it0 += 64) {
+      const int it = it0 + lane;
+      const bool valid = it < total;
+      const int ti = it / kItems, rem = it - ti * kItems;
+      const int s = rem / 9, q = rem - 9 * s, j = q / 3, c = q - 3 * j;
+      float tsel = a.t[0];
+#pragma unroll
+      for (int k = 1; k < kRcSliceMax; ++k) tsel = k == ti ? a.t[k] : tsel;
+      const float y0 = floorf(tsel), y1 = ceilf(tsel);
+      const float d = sp[P_DIND * 32 + s], w = sp[P_W * 32 + s];
+      const int lo = __float_as_int(sp[P_LO * 32 + s]), hi = __float_as_int(sp[P_HI * 32 + s]);
+      const int ia = src_bin(y0, d), ib = src_bin(y1, d);
+      const int b = ia + j;
+      // a pair outside the histogram, outside the sample's window, read by neither target or with weight 0 is an exact zero
+      const bool need = valid && w != 0.0f && b >= 0 && b < kBins && b >= lo && b <= hi &&
+                        (b == ia || b == ia + 1 || b == ib || b == ib + 1);
+      float val = 0.0f;
+      if (need) {
+        const int col = 3 * b + c;
+        const float* ws = a.w_slf + (size_t)col * kRcSliceStrideSlf;
+        const float* wi = a.w_irr + (size_t)col * kRcSliceStrideIrr;
+        const float4* ws4 = reinterpret_cast<const float4*>(ws);
+        const float4* wi4 = reinterpret_cast<const float4*>(wi);
+        const float4* xs4 = reinterpret_cast<const float4*>(xs + s * kRcSliceStrideSlf);
+        const float4* xi4 = reinterpret_cast<const float4*>(xi + s * kRcSliceStrideIrr);
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll 8
+        for (int g = 0; g < 32; ++g) {
+          const float4 wv = ws4[g], xv = xs4[g];
+          s0 = __builtin_fmaf(xv.x, wv.x, s0); s1 = __builtin_fmaf(xv.y, wv.y, s1);
+          s2 = __builtin_fmaf(xv.z, wv.z, s2); s3 = __builtin_fmaf(xv.w, wv.w, s3);
+        }
+        const float as = ((s0 + s1) + (s2 + s3)) + ws[128];
+        float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+#pragma unroll 8
+        for (int g = 0; g < 16; ++g) {
+          const float4 wv = wi4[g], xv = xi4[g];
+          r0 = __builtin_fmaf(xv.x, wv.x, r0); r1 = __builtin_fmaf(xv.y, wv.y, r1);
+          r2 = __builtin_fmaf(xv.z, wv.z, r2); r3 = __builtin_fmaf(xv.w, wv.w, r3);
+        }
+        const float ai = ((r0 + r1) + (r2 + r3)) + wi[64];
+        const float tib = sp[(P_TIB0 + c) * 32 + s];
+        // nerf.py:1795-1797, :1712-1719 and surface_light_field.py:1037-1058, nerf.py:1721-1723, as k_transient_bins
+        float diff = softplus_bins(ai + a.irradiance_bias) * a.indirect_scale;
+        const float ref = fmaxf(softplus_bins(1.0f * as + a.slf_rgb_bias), 0.0f);
+        float spec = (tib * ref) * a.indirect_scale;
+        diff = __builtin_amdgcn_fmed3f(diff, 0.0f, a.rgb_max);
+        spec = __builtin_amdgcn_fmed3f(spec, 0.0f, a.rgb_max);
+        val = w * (diff + spec);
+      }
+      if (valid) vals[it] = val;
+    }
+    lds_sync<false>();
+    // ---- this lane's target: the 32 samples in order, each with the weights the target computes (coordinate y - d,
+    //      i0 = floor, fw = y - d - i0: 1 - fw to source bin i0, fw to i0 + 1)
+    if (o_ok) {
+      const float yf = (float)o_y, y0f = (float)o_y0;
+      const float* v = vals + o_ti * kItems + o_c;
+      for (int s = 0; s < 32; ++s) {
+        const float d = sp[P_DIND * 32 + s];
+        const float t = yf - d;
+        const float fw = t - floorf(t);
+        const int jj = src_bin(yf, d) - src_bin(y0f, d);      // slot of i0; 1 or 2 for the ceil bin (2 only with fw == 0)
+        const float v0 = v[s * 9 + 3 * min(max(jj, 0), 2)], v1 = v[s * 9 + 3 * min(max(jj + 1, 0), 2)];
+        const float lo_v = (jj >= 0 && jj <= 2) ? v0 : 0.0f, hi_v = (jj + 1 >= 0 && jj + 1 <= 2) ? v1 : 0.0f;
+        iv += hi_v * fw + lo_v * (1.0f - fw);
+      }
+    }
+  }
+
+  // ---- w * v[ceil t] + (1 - w) * v[floor t]: the ceil bin sits on the next lane
+  const float rgb = dv + iv;
+  const float rgb_hi = __shfl_xor(rgb, 1, 64), dv_hi = __shfl_xor(dv, 1, 64), iv_hi = __shfl_xor(iv, 1, 64);
+  if (o_ok && o_g == 0) {
+    const float w = o_t - floorf(o_t);
+    const int64_t at = (ray * a.count + o_ti) * 3 + o_c;
+    if (a.out_rgb) a.out_rgb[at] = w * rgb_hi + (1.0f - w) * rgb;
+    if (a.out_direct) a.out_direct[at] = w * dv_hi + (1.0f - w) * dv;
+    if (a.out_indirect) a.out_indirect[at] = w * iv_hi + (1.0f - w) * iv;
+  }
+}
+
+}  // namespace
+
+void rc_launch_transient_slice(const RcTransSliceArgs& a, hipStream_t stream) {
+  if (a.n_rays <= 0) return;
+  static std::atomic<uint64_t> prepared{0};
+  const int lds = kSliceWaves * kSliceWaveLds * (int)sizeof(float);
+  if (rc_first_use_on_device(prepared)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_transient_slice), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  }
+  hipLaunchKernelGGL(k_transient_slice, dim3((unsigned)((a.n_rays + kSliceWaves - 1) / kSliceWaves)), dim3(kSliceWaves * 64), lds,
+                     stream, a);
+}

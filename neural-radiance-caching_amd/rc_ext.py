@@ -149,6 +149,18 @@ class rc_transient_outputs(C.Structure):
     _fields_ = [("ptr", C.c_void_p * RC_TOUT_COUNT)]
 
 
+RC_TSLICE_MAX = 8
+# rc_render_transient_slices: the slice outputs (fields of rc_transient_slices) and the outputs `extra` may ask for
+TRANSIENT_SLICE_OUTPUTS = ("rgb", "direct", "indirect")
+TRANSIENT_SLICE_EXTRAS = ("acc", "distance_mean", "distance_median", "distance_percentile_5", "distance_percentile_95",
+                          "means", "normals", "normals_pred", "ray_dists", "light_dists")
+
+
+class rc_transient_slices(C.Structure):
+    _fields_ = [("count", C.c_int32), ("t", C.c_float * RC_TSLICE_MAX), ("rgb", C.c_void_p), ("direct", C.c_void_p),
+                ("indirect", C.c_void_p)]
+
+
 # outputs table -> (its struct of pointers, name -> slot)
 _OUTPUT_TABLES = {OUTPUTS: (rc_outputs, OUTPUT_ID), MAT_OUTPUTS: (rc_mat_outputs, MAT_OUTPUT_ID),
                   TRANSIENT_OUTPUTS: (rc_transient_outputs, TRANSIENT_OUTPUT_ID)}
@@ -389,6 +401,8 @@ _PROTOTYPES = {
     "rc_stage_times_ms": (C.c_int, [_H, C.POINTER(C.c_float), _I32]),
     "rc_set_transient": (C.c_int, [_H, _P]),
     "rc_render_transient": (C.c_int, [_H, _P, _P, _I64, _P, _P, _P, _P]),
+    "rc_render_transient_slices": (C.c_int, [_H, _RAYS, _P, _I64, _P, _P, C.POINTER(rc_transient_slices),
+                                             C.POINTER(rc_transient_outputs), _P]),
     "rc_cast_rays": (C.c_int, [_H, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _P]),
     "rc_cast_rays_multi": (C.c_int, [_H, _P, _P, _P, _P, _I64, _P, _P, _P, _P]),
     "rc_train_batch": (C.c_int, [_H, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _I64, _P, _P]),
@@ -1418,6 +1432,54 @@ class RadianceCache:
                                                  self._stream()))
         self._keep = [held]
         return res
+
+    def render_transient_slices(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]], times,
+                                outputs: Iterable[str] = ("rgb",), extra: Optional[Iterable[str]] = None):
+        """rc_render_transient_slices: the time slices  w * v[ceil t] + (1 - w) * v[floor t],  w = t - floor t,  of the
+        histograms render_transient would give for the same rays / randoms, without the histograms.
+        times: fractional bin indices in [0, n_bins - 1]; outputs: of TRANSIENT_SLICE_OUTPUTS ("rgb", the filtered
+        "direct" part, the "indirect" part); extra: of TRANSIENT_SLICE_EXTRAS, the outputs of the steady-state composite.
+        Returns {output: [n, len(times), 3] cuda tensor} plus the extras ([n, 3] / [n]).  A call serves RC_TSLICE_MAX times;
+        more are served by several calls, and EACH CALL REPEATS THE TRACE up to the per-bin heads -- ask for the times of
+        a view together."""
+        torch = self._torch
+        times = [float(t) for t in np.asarray(times, dtype=np.float64).reshape(-1)]
+        outputs, extra = list(outputs), list(extra or ())
+        bad = [k for k in outputs if k not in TRANSIENT_SLICE_OUTPUTS] + [k for k in extra if k not in TRANSIENT_SLICE_EXTRAS]
+        if bad or not outputs:
+            raise ValueError(f"render_transient_slices: outputs of {TRANSIENT_SLICE_OUTPUTS} (at least one), extra of "
+                             f"{TRANSIENT_SLICE_EXTRAS}; got {bad or outputs}")
+        if not times:
+            raise ValueError("render_transient_slices: no times")
+        r, held, n = self._rays_struct(rays)
+        cam = self._dev(rays["cam_origins"]).reshape(-1, 3)
+        held["cam_origins"] = cam
+        rnd_p, shadow_p = None, None
+        if randoms is not None and randoms.get("jitter") is not None:
+            rnd_p = C.byref(self._randoms(held, randoms["jitter"]))
+        if randoms is not None and randoms.get("shadow_jitter") is not None:
+            shadow_p = C.byref(self._randoms(held, randoms["shadow_jitter"], tag="shadow_"))
+        xres, xout = self._outputs(TRANSIENT_OUTPUTS, extra,
+                                   lambda nm: (n, 3) if TRANSIENT_OUTPUTS[TRANSIENT_OUTPUT_ID[nm]][1] == 3 else (n,))
+        res = {}
+        groups = [times[i: i + RC_TSLICE_MAX] for i in range(0, len(times), RC_TSLICE_MAX)]
+        for gi, group in enumerate(groups):
+            bufs = dict(zip(outputs, self._zeros_like_many([(n, len(group), 3)] * len(outputs))))
+            s = rc_transient_slices(count=len(group))
+            for i, t in enumerate(group):
+                s.t[i] = t
+            for k in outputs:
+                setattr(s, k, bufs[k].data_ptr())
+            if n > 0:                      # (an empty tensor has no address to hand over, and there is nothing to write)
+                self._check(self.lib.rc_render_transient_slices(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, shadow_p,
+                                                                C.byref(s), C.byref(xout) if extra and gi == 0 else None,
+                                                                self._stream()))
+            for k in outputs:
+                res.setdefault(k, []).append(bufs[k])
+        self._keep = [held]
+        out = {k: v[0] if len(v) == 1 else torch.cat(v, dim=1) for k, v in res.items()}
+        out.update(xres)
+        return out
 
     def transient_head_grad_layout(self):
         """rc_transient_head_grad_layout: [(tensor name, offset, shape)] of the time-resolved cache's per-bin head layers
