@@ -1,9 +1,9 @@
 // C-ABI host of the radiance-cache renderer (see include/rc_abi.h).
 //
-// Owns: device copies of the hash/dense tables, the MFMA-fragment-packed MLP weights, the
-// per-batch workspace and the launch sequence that replaces BaseNeRFModel.__call__
-// (internal/models.py:657-774): 3 x [resample -> grid lookup -> density MLP] -> (categorical
-// resample) -> appearance grid -> cache shader -> volume compositing.
+// Owns: the handle, device copies of the hash/dense tables, the MFMA-fragment-packed MLP weights,
+// the per-batch workspace and the small entry points.  The launch sequence that replaces
+// BaseNeRFModel.__call__ is rc_render_host.inc, the material stage rc_material_host.inc; like
+// every other *_host.inc they are included at the end of this file.
 #include <dlfcn.h>
 #include <math.h>
 #include <stdlib.h>
@@ -344,13 +344,7 @@ struct rc_handle {
   // fused per-ray kernel for the plain cache pass (fused_mode: 0 never, 1 whenever eligible)
   int fused_mode = 1;
   RcFusedLaunch fused_tmpl{};      // launch descriptor of the fused plan, resolved at repack (build_fused_template)
-  int fused_stagger = getenv("RC_FUSED_STAGGER") ? atoi(getenv("RC_FUSED_STAGGER")) : 0;   // experiment (rc_fused2.hip)
   int fused_prio = getenv("RC_FUSED_PRIO") ? atoi(getenv("RC_FUSED_PRIO")) : 1;             // rc_fused2.hip: 1 = the younger workgroup of a CU leads through the lookups
-#ifdef RC_FUSED_DIRECT_EXPERIMENT
-  int fused_direct = getenv("RC_FUSED_DIRECT") ? atoi(getenv("RC_FUSED_DIRECT")) : 0;   // experiment switch (see rc_fused.hip, DIRECT)
-#else
-  int fused_direct = 0;
-#endif
   bool fused_ok = false;
   bool fused_front_ok = false;               // transient handles: the FRONT variant of the fused kernel is usable
   // hipGraph replay of the launch sequence (graph_mode: 0 off, 1 capture when a call repeats, 2 always)
@@ -1067,22 +1061,6 @@ int ensure_packed(rc_handle* h) {
   return repack(h);
 }
 
-// Secondary rays: rgb += env * (1 - acc) (Model._composite_env_map, internal/models.py:423-460).
-__global__ void k_env_combine(int64_t n, const float* rgb_noenv, const float* acc, const float* env, float* rgb_out,
-                              float* acc_out, float* env_out, float* noenv_out) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const float a = acc[r];
-  if (acc_out) acc_out[r] = a;
-  for (int c = 0; c < 3; ++c) {
-    const float base = rgb_noenv[3 * r + c];
-    const float e = env ? env[3 * r + c] : 0.0f;
-    if (rgb_out) rgb_out[3 * r + c] = env ? base + e * (1.0f - a) : base;
-    if (env_out) env_out[3 * r + c] = e;
-    if (noenv_out) noenv_out[3 * r + c] = base;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -1355,366 +1333,6 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
 }
 
 namespace {
-
-struct RenderArgs {
-  rc_rays rays; rc_randoms rnd; bool have_rnd; int64_t n; uint32_t mask; rc_outputs out; int slot; bool fused;
-  const rc_transient_outputs* tout = nullptr; const float* cam_origins = nullptr;
-  const rc_randoms* shadow_rnd = nullptr; bool weights_only = false; bool force_grad = false;
-  const rc_transient_slices* tslices = nullptr;   // rc_render_transient_slices: k_transient_slice in place of k_transient_bins
-  // rc_interlevel_backward's training forward: the sampler levels only (sdist / tdist / means / density / weights of every
-  // level in the workspace, nothing behind them), resampling at `anneal` (< 0: the config's render-time value)
-  bool sampler_only = false; float anneal = -1.0f;
-  // rc_geometry_backward's training forward: the sampler levels with the last level's hidden vector, predicted and
-  // analytic normals (force_grad), nothing behind them
-  bool levels_only = false;
-  bool export_samples = false;     // fused plan: leave tdist / density / means / normals_pred of the last level in the workspace
-  const float* s_bounds = nullptr; // secondary rays with ONE (near, far): power-ladder bounds computed once (RcSampleArgs)
-  // material stage: the EnvMap of the trace's directions is released on `env_side` when the LAST proposal level is
-  // launched, which leaves `env_reserve` CUs to it (both kernels keep a CU's LDS to themselves; see rc_render_material)
-  const RcEnvMapArgs* env = nullptr; hipStream_t env_side = nullptr; hipEvent_t env_ready = nullptr, env_done = nullptr;
-  int env_reserve = 0;
-  bool* env_released = nullptr;    // set when the launch plan taken had the spot (the caller releases the EnvMap itself otherwise)
-};
-
-void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st);
-
-// Enqueue the whole launch sequence on `st` (also used under stream capture) with workspace set `w`.
-void enqueue_all(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st) {
-  const rc_config& c = h->cfg;
-  const int NL = c.num_levels;
-  const int64_t n = A.n;
-  const rc_rays* rays = &A.rays;
-  const rc_randoms* rnd = A.have_rnd ? &A.rnd : nullptr;
-  const bool secondary = (A.mask & RC_PASS_SECONDARY) != 0;
-  const bool resample = secondary || (A.mask & RC_PASS_RESAMPLE);
-  // lean: no per-sample consumer of the last level's hidden feature / predicted normals besides the shader
-  const bool lean = resample && !A.tout && !A.weights_only && !A.force_grad && !A.out.ptr[RC_OUT_NORMALS_PRED] &&
-                    !A.out.ptr[RC_OUT_NORMALS];
-  const int slot = A.slot;
-  if (A.fused) {
-    // everything of the launch that only changes when weights are (re)packed was resolved then (build_fused_template)
-    RcFusedLaunch F = h->fused_tmpl;
-    F.rays = A.rays; F.n = n;
-    for (int l = 0; l < 3; ++l) F.jitter[l] = rnd ? rnd->jitter[l] : nullptr;
-    F.out = A.out;
-    F.direct = h->fused_direct;
-    // mode 3: the one-wavefront-per-ray form.  Builds with the split-MFMA shader (RC_SPLIT_MFMA) run it for mode 1 as well:
-    // the two-wave kernel was unstable with the split form in every layer (rc_dev_mlp.h INSTABILITY; cause not found)
-    // (a split build compiles the two-wave kernel only under -DRC_TEAM_SPLIT_DIAG, for diagnosis: rc_pack_host.h RC_TEAM_KERNEL)
-    F.team = (h->fused_mode == 1 && RC_TEAM_KERNEL) ? 1 : 0;
-    F.stagger_cycles = h->fused_stagger;
-    F.prio_mode = h->fused_prio;
-    if (A.export_samples) {
-      F.export_samples = 1;
-      F.f_tdist = w.tdist[NL - 1].p; F.f_density = w.density[NL - 1].p; F.f_means = w.means[NL - 1].p; F.f_normals_pred = w.normals_pred.p;
-    }
-    // profiling: the single launch is reported as the "shader" stage, every other stage as 0
-    for (int i = 0; i <= ST_SHADER; ++i) stage_mark(h, slot, i, st);
-    roctx_stage(F.team ? "k_cache_fused_team" : "k_cache_fused");
-    rc_launch_fused(F, st);
-    for (int i = ST_SHADER + 1; i <= ST_COUNT; ++i) stage_mark(h, slot, i, st);
-    return;
-  }
-  if (A.tout && h->fused_front_ok && h->fused_mode != 0 && !secondary && !resample && !A.weights_only) {
-    // time-resolved cache on primary rays: the whole proposal sampler + appearance lookup as ONE launch (the FRONT
-    // variant of the fused kernel), results in the workspace buffers the stages behind it read
-    RcFusedLaunch F = fused_front_end(h);
-    F.rays = A.rays; F.n = n;
-    for (int l = 0; l < 3; ++l) F.jitter[l] = rnd ? rnd->jitter[l] : nullptr;
-    F.wstream = h->packs.fused_front.p;
-    F.front = 1;
-    F.want_grad = (A.out.ptr[RC_OUT_NORMALS] != nullptr || A.force_grad) ? 1 : 0;
-    F.use_raydist = 1; F.raydist_p = c.raydist_p; F.raydist_premult = c.raydist_premult;   // TransientNeRFModel (see below)
-    F.f_tdist = w.tdist[NL - 1].p; F.f_density = w.density[NL - 1].p; F.f_means = w.means[NL - 1].p;
-    F.f_normals_pred = w.normals_pred.p; F.f_normals_grad = w.normals_grad.p; F.f_hbuf = w.hbuf.p; F.f_app = w.app.p;
-    rc_launch_fused(F, st);
-    enqueue_transient_tail(h, A, w, st);
-    return;
-  }
-  for (int l = 0; l < NL; ++l) {
-    const int S = c.num_samples[l];
-    const int64_t np = n * S;
-    RcSampleArgs sa{};
-    sa.origins = rays->origins; sa.directions = rays->directions; sa.viewdirs = rays->viewdirs;
-    sa.near = rays->near; sa.far = rays->far; sa.normals = rays->normals; sa.n_rays = n;
-    if (l > 0) {
-      sa.prev_sdist = w.sdist[l - 1].p; sa.prev_tdist = w.tdist[l - 1].p; sa.prev_density = w.density[l - 1].p;
-      sa.P = c.num_samples[l - 1]; sa.prev_weights = w.weights[l - 1].p;
-    } else {
-      sa.P = 1;
-    }
-    sa.S = S;
-    sa.jitter = rnd ? rnd->jitter[l] : nullptr;
-    sa.sdist = w.sdist[l].p; sa.tdist = w.tdist[l].p; sa.means = w.means[l].p;
-    sa.anneal = A.anneal >= 0.0f ? A.anneal : c.anneal; sa.padding = c.resample_padding;
-    sa.secondary = secondary ? 1 : 0;
-    sa.use_raydist = (secondary || h->transient) ? 1 : 0;     // TransientNeRFModel: use_raydist_for_secondary_only = False
-    sa.raydist_p = c.raydist_p; sa.raydist_premult = c.raydist_premult;
-    sa.eps_dot_min = c.shadow_normal_eps_dot_min; sa.far_clamp = c.env_map_distance;
-    sa.s_bounds = (secondary && !rays->normals) ? A.s_bounds : nullptr;
-    const bool want_grad = (l == NL - 1) && (A.out.ptr[RC_OUT_NORMALS] != nullptr || A.force_grad);
-    // only the density of this level's samples is consumed behind it (proposal levels; the last level on the lean
-    // resampling pass): grid lookup + density MLP as ONE launch, weights resident in LDS (rc_level.hip) -- and on the
-    // default plan (rc_set_fused 1) the level's sampling in front of it in the same launch, one ray per wave
-    const bool level_kernel = h->fused_mode != 0 && !h->profiling && rc_level_supported(h->grids[l].dev) && !want_grad &&
-                              (l < NL - 1 || (lean && !A.tout));
-    RcLevelArgs la{};
-    la.grid = &h->grids[l].dev; la.means = w.means[l].p; la.n = np; la.wstream = h->packs.dens[l].p;
-    la.density_bias = c.density_bias; la.contract_radius = c.contract_radius; la.density = w.density[l].p;
-    // (one ray per wave pays from ~100 rays per CU on: measured break-even of the whole pass near 32 k rays, +27 us at 1-4 k)
-    if (level_kernel && (h->fused_mode == 1 || h->fused_mode == 3) && n >= 24576 && rc_level_ray_supported(h->grids[l].dev, S)) {
-      roctx_stage(l == 0 ? "level0 (sample+grid+mlp)" : (l == 1 ? "level1 (sample+grid+mlp)" : "level2 (sample+grid+mlp)"));
-      if (A.env && l == NL - 1) {
-        (void)hipEventRecord(A.env_ready, st);
-        (void)hipStreamWaitEvent(A.env_side, A.env_ready, 0);
-        rc_launch_envmap(*A.env, A.env_side);
-        (void)hipEventRecord(A.env_done, A.env_side);
-        la.cu_reserve = A.env_reserve;
-        if (A.env_released) *A.env_released = true;
-      }
-      rc_launch_level_ray(la, sa, st);
-      continue;
-    }
-    stage_mark(h, slot, ST_SAMPLE0 + 3 * l, st);
-    rc_launch_sample(sa, st);
-
-    stage_mark(h, slot, ST_GRID0 + 3 * l, st);
-    if (level_kernel) {
-      stage_mark(h, slot, ST_MLP0 + 3 * l, st);
-      rc_launch_level(la, st);
-      continue;
-    }
-    rc_launch_hashgrid(h->grids[l].dev, w.means[l].p, 1, np, w.feat[l].p, 1, np, c.contract_radius, want_grad ? w.jac.p : nullptr, st);
-
-    RcDensityMlpArgs da{};
-    da.feat = w.feat[l].p; da.n = np; da.ld = np;
-    da.K = h->grids[l].dev.num_levels * h->grids[l].dev.num_features;
-    da.wstream = h->packs.dens[l].p; da.means = w.means[l].p;
-    da.density_bias = c.density_bias; da.contract_radius = c.contract_radius; da.bbox = h->grids[l].cfg.bbox;
-    da.last = (l == NL - 1) ? 1 : 0; da.density = w.density[l].p;
-    // lean resampling pass: the hidden feature / predicted normals are only needed at the ONE sample per ray picked
-    // below, so they are not written for all of them here (256 + 12 bytes per sample) but recomputed for the picks
-    da.hbuf = (da.last && !lean && !A.sampler_only) ? w.hbuf.p : nullptr;
-    da.normals_pred = (da.last && !lean && !A.sampler_only) ? w.normals_pred.p : nullptr;
-    da.jac = want_grad ? w.jac.p : nullptr; da.normals_grad = want_grad ? w.normals_grad.p : nullptr;
-    stage_mark(h, slot, ST_MLP0 + 3 * l, st);
-    rc_launch_density_mlp(da, st);
-  }
-  if (A.sampler_only || A.levels_only) return;
-  const int S2 = c.num_samples[NL - 1];
-  const int64_t np2 = n * S2;
-  if (A.weights_only) {
-    // weights_only=True (models.py:944-982): no shader; only acc = sum of the last level's weights is consumed
-    RcCompositeArgs ca{};
-    ca.directions = rays->directions; ca.origins = rays->origins; ca.lights = rays->lights; ca.n_rays = n; ca.S = S2;
-    ca.tdist = w.tdist[NL - 1].p; ca.density = w.density[NL - 1].p; ca.means = w.means[NL - 1].p;
-    ca.normals_pred = w.normals_pred.p; ca.normals_grad = nullptr;
-    ca.shade = w.shade.p; ca.Sf = S2; ca.weights = w.weights[NL - 1].p;
-    ca.bg = 0.0f;
-    ca.pct[0] = c.percentiles[0]; ca.pct[1] = c.percentiles[1]; ca.pct[2] = c.percentiles[2];
-    ca.out = A.out;
-    rc_launch_composite(ca, st);
-    return;
-  }
-  stage_mark(h, slot, ST_RESAMPLE, st);
-  const int32_t* src = nullptr;
-  if (resample) {
-    RcResampleArgs ra{};
-    ra.n_rays = n; ra.S = S2; ra.tdist = w.tdist[NL - 1].p; ra.density = w.density[NL - 1].p;
-    ra.directions = rays->directions; ra.gumbel = rnd->gumbel; ra.inds_in = rnd->resample_inds;
-    ra.inds_out = (int32_t*)w.inds.p; ra.filt_weight = w.filt_weight.p; ra.weights = w.weights[NL - 1].p;
-    ra.acc_out = w.acc_sel.p; ra.src_out = (int32_t*)w.src_idx.p;
-    rc_launch_resample(ra, st);
-    src = (const int32_t*)w.src_idx.p;
-  }
-  const int64_t nsh = resample ? n : np2;
-  bool pair_lookup = false;
-  if (lean) {
-    // density MLP of the last level once more, on the picked samples only (same kernel, same per-point arithmetic:
-    // bitwise the values the full pass would have stored), compact outputs
-    const int l2 = NL - 1;
-    const int K2 = h->grids[l2].dev.num_levels * h->grids[l2].dev.num_features;
-    // with the fused plan's interleaved tables at hand: this lookup and the appearance lookup below in one pass
-    pair_lookup = h->fused_ok && l2 == 2 && nsh == n && h->fused_mode != 0;
-    if (pair_lookup) {
-      RcPairTables pt{};
-      for (int l = 0; l < h->grids[2].dev.num_levels; ++l) pt.t[l] = h->fused_tmpl.pair_table[l];
-      rc_launch_hashgrid_pair(h->grids[2].dev, pt, w.means[NL - 1].p, src, np2, n, w.feat_sel.p, w.app.p, n, c.contract_radius, st);
-    } else {
-      rc_launch_hashgrid_src(h->grids[l2].dev, w.means[NL - 1].p, 1, src, np2, n, w.feat_sel.p, 1, n, c.contract_radius, nullptr, st);
-    }
-    RcDensityMlpArgs ds{};
-    ds.feat = w.feat_sel.p; ds.n = n; ds.ld = n; ds.K = K2; ds.wstream = h->packs.dens[NL - 1].p;
-    ds.means = w.means[NL - 1].p; ds.src = src; ds.n_src = np2;
-    ds.density_bias = c.density_bias; ds.contract_radius = c.contract_radius; ds.bbox = h->grids[l2].cfg.bbox;
-    ds.last = 1; ds.density = w.density_sel.p; ds.hbuf = w.hbuf_sel.p; ds.normals_pred = w.normals_sel.p;
-    rc_launch_density_mlp(ds, st);
-  }
-  stage_mark(h, slot, ST_GRID_APP, st);
-  if (!pair_lookup)
-    rc_launch_hashgrid_src(h->grids[3].dev, w.means[NL - 1].p, 1, src, np2, nsh, w.app.p, 1, nsh, c.contract_radius, nullptr, st);
-  if (A.tout) {
-    enqueue_transient_tail(h, A, w, st);
-    return;
-  }
-  stage_mark(h, slot, ST_SHADER, st);
-  {
-    RcShaderArgs s{};
-    s.n = nsh; s.n_src = lean ? n : np2; s.src = lean ? nullptr : src; s.samples_per_ray = resample ? 1 : S2;
-    s.hbuf = (lean ? w.hbuf_sel : w.hbuf).p; s.app = w.app.p;
-    s.normals_pred = (lean ? w.normals_sel : w.normals_pred).p; s.viewdirs = rays->viewdirs;
-    s.wstream = h->packs.shader.p; s.ide_coef = h->ide_table.p;
-    s.roughness_bias = c.roughness_bias; s.irradiance_bias = c.irradiance_bias; s.ambient_bias = c.ambient_irradiance_bias;
-    s.rgb_max = c.rgb_max; s.slf_ambient_bias = c.slf_ambient_bias;
-    s.shade = w.shade.p; s.debug = w.debug.p;
-    rc_launch_shader(s, st);
-  }
-  stage_mark(h, slot, ST_COMPOSITE, st);
-  {
-    RcCompositeArgs ca{};
-    ca.directions = rays->directions; ca.origins = rays->origins; ca.lights = rays->lights; ca.n_rays = n; ca.S = S2;
-    ca.tdist = w.tdist[NL - 1].p; ca.density = w.density[NL - 1].p; ca.means = w.means[NL - 1].p;
-    ca.normals_pred = lean ? nullptr : w.normals_pred.p;
-    ca.normals_grad = A.out.ptr[RC_OUT_NORMALS] ? w.normals_grad.p : nullptr;
-    ca.shade = w.shade.p; ca.Sf = resample ? 1 : S2;
-    ca.inds = resample ? (const int32_t*)w.inds.p : nullptr; ca.filt_weight = resample ? w.filt_weight.p : nullptr;
-    ca.weights = w.weights[NL - 1].p;
-    ca.bg = secondary ? 0.0f : c.bg_intensity;
-    ca.pct[0] = c.percentiles[0]; ca.pct[1] = c.percentiles[1]; ca.pct[2] = c.percentiles[2];
-    ca.out = A.out;
-    if (secondary) { ca.out.ptr[RC_OUT_RGB] = w.rgb_noenv.p; ca.out.ptr[RC_OUT_ACC] = w.acc_ws.p; }
-    // one resampled sample per ray and nothing but rgb / acc wanted (the batched secondary trace): the weights and their
-    // sum are k_resample's, one thread per ray finishes (17 -> 3 us for 32 768 rays; same bits)
-    bool pick_only = resample;
-    for (int id = 0; id < RC_OUT_COUNT && pick_only; ++id)
-      if (ca.out.ptr[id] && id != RC_OUT_RGB && id != RC_OUT_ACC) pick_only = false;
-    if (pick_only) rc_launch_composite_pick(n, w.shade.p, w.filt_weight.p, w.acc_sel.p, ca.bg, ca.out.ptr[RC_OUT_RGB], ca.out.ptr[RC_OUT_ACC], st);
-    else rc_launch_composite(ca, st);
-  }
-  if (secondary) {
-    const bool use_env = !(A.mask & RC_PASS_NO_ENVMAP);
-    if (use_env && (A.mask & RC_PASS_ENV_IMAGE)) {
-      // an explicit image instead of the EnvMap MLP (Model._handle_env_map, models.py:382-393)
-      rc_launch_env_lookup(RcEnvLookupArgs{RcEnvImage{h->env_padded.p, h->env_img_h, h->env_img_w}, rays->viewdirs, n, w.env_rgb.p}, st);
-    } else if (use_env) {
-      RcEnvMapArgs ea{};
-      ea.n = n; ea.viewdirs = rays->viewdirs; ea.wstream = h->packs.envmap.p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = w.env_rgb.p;
-      rc_launch_envmap(ea, st);
-    }
-    hipLaunchKernelGGL(k_env_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
-                       (const float*)w.rgb_noenv.p, (const float*)w.acc_ws.p, use_env ? (const float*)w.env_rgb.p : (const float*)nullptr,
-                       A.out.ptr[RC_OUT_RGB], A.out.ptr[RC_OUT_ACC], A.out.ptr[RC_OUT_ENV_MAP_RGB], A.out.ptr[RC_OUT_RGB_NO_ENV]);
-  }
-  stage_mark(h, slot, ST_COUNT, st);
-}
-
-}  // namespace
-
-int rc_render_rays(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd, uint32_t pass_mask,
-                   const rc_outputs* out, void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (!rays || !out) return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: null rays/outputs");
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: negative n_rays");
-  if (n == 0) return RC_OK;
-  int rc;
-  if ((rc = check_rays(h, rays, "rc_render_rays"))) return rc;
-  RoctxScope roctx_call("rc_render_rays");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_rays: this handle renders the time-resolved cache (rc_render_transient)");
-  if (!(pass_mask & RC_PASS_CACHE)) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_rays: pass_mask must include RC_PASS_CACHE");
-  const bool secondary = (pass_mask & RC_PASS_SECONDARY) != 0;
-  const bool resample = secondary || (pass_mask & RC_PASS_RESAMPLE);
-  if (resample && h->cfg.num_resample != 1) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_rays: num_resample must be 1");
-  if (resample && !(rnd && (rnd->gumbel || rnd->resample_inds)))
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: resampling needs rc_randoms.gumbel or .resample_inds");
-  RC_HIP(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream_v;
-  if ((rc = ensure_packed(h))) return rc;
-  const bool env_image = secondary && (pass_mask & RC_PASS_ENV_IMAGE) && !(pass_mask & RC_PASS_NO_ENVMAP);
-  if (env_image && h->env_img_h == 0)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_rays: RC_PASS_ENV_IMAGE without a bound image (rc_set_env_image)");
-  if (secondary && !(pass_mask & RC_PASS_NO_ENVMAP) && !env_image && !h->have_envmap)
-    return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/* (secondary rays composite the model-level EnvMap)");
-  const bool fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && pass_mask == RC_PASS_CACHE;
-  // one workspace set per caller stream (up to 4): calls on different streams do not share buffers.  The fused kernel
-  // keeps every intermediate on chip: no workspace, no set.
-  const int ws_slot = fused ? WS_RENDER0 : ws_pick(h, st);
-  RenderWs& w = h->ws[ws_slot].r;
-  WsUse use(h, ws_slot, st, !fused);
-  if ((rc = use.rc)) return rc;
-  if (!fused && (rc = ensure_workspace(h, w, n))) return rc;      // a reallocation drops the captured graphs (ws_alloc)
-  rc_shader_prepare();
-
-  RenderArgs A{};
-  A.rays = *rays;
-  A.have_rnd = rnd != nullptr;
-  if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = pass_mask; A.out = *out;
-  A.fused = fused;
-  A.slot = -1;
-  if (h->profiling) {
-    // mode 3: events around the dominant kernel of every 8th call only (an event record costs ~1.3 us of stream time)
-    const int64_t call = h->prof_calls++;
-    if (h->profiling != 3 || call % 8 == 0) {
-      A.slot = (int)((h->profiling == 3 ? call / 8 : call) % kEvSlots);
-      h->ev_used[A.slot] = true;
-    }
-  }
-
-  // event records are not replayable graph nodes: profile eagerly.  The fused plan is ONE launch: a plain launch
-  // queues back to back with the previous one (gap < 1 us), the replay of a one-node graph leaves ~5 us between them.
-  if (h->graph_mode == 0 || h->profiling || fused) {
-    enqueue_all(h, A, w, st);
-    RC_HIP(h, hipGetLastError());
-    return RC_OK;
-  }
-  RenderKey key;
-  memset(&key, 0, sizeof(key));
-  key.n = n; key.mask = pass_mask; key.slot = A.slot; key.ws_slot = ws_slot;
-  const void* rp[7] = {rays->origins, rays->directions, rays->viewdirs, rays->near, rays->far, rays->lights, rays->normals};
-  memcpy(key.rays, rp, sizeof(rp));
-  if (rnd) {
-    for (int l = 0; l < RC_MAX_LEVELS; ++l) key.rnd[l] = rnd->jitter[l];
-    key.rnd[RC_MAX_LEVELS] = rnd->gumbel; key.rnd[RC_MAX_LEVELS + 1] = rnd->resample_inds;
-  }
-  for (int i = 0; i < RC_OUT_COUNT; ++i) key.out[i] = out->ptr[i];
-  for (auto& g : h->graphs)
-    if (g.key == key) {
-      RC_HIP(h, hipGraphLaunch(g.exec, st));
-      return RC_OK;
-    }
-  const bool capture = h->graph_mode == 2 || (h->have_last_key && h->last_key == key);
-  h->last_key = key;
-  h->have_last_key = true;
-  if (!capture) {
-    enqueue_all(h, A, w, st);
-    RC_HIP(h, hipGetLastError());
-    return RC_OK;
-  }
-  // capture on a private stream (the caller's may be the legacy default stream), replay on the caller's
-  if (!h->cap_stream) RC_HIP(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-  if (h->graphs.size() >= 64) drop_graphs(h);
-  GraphEntry e;
-  e.key = key;
-  RC_HIP(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-  enqueue_all(h, A, w, h->cap_stream);
-  hipError_t ce = hipStreamEndCapture(h->cap_stream, &e.graph);
-  if (ce != hipSuccess || !e.graph) {
-    // capture unsupported for this sequence: fall back to eager launches for good
-    (void)hipGetLastError();
-    h->graph_mode = 0;
-    enqueue_all(h, A, w, st);
-    RC_HIP(h, hipGetLastError());
-    return RC_OK;
-  }
-  RC_HIP(h, hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
-  h->graphs.push_back(e);
-  RC_HIP(h, hipGraphLaunch(e.exec, st));
-  return RC_OK;
-  RC_CATCH(h)
-}
-
-namespace {
 // RCCL entry points, resolved from the instance the process already has (torch ships its own librccl.so: linking a
 // second copy into this library would split the communicator state between two instances).
 struct RcclApi {
@@ -1765,356 +1383,10 @@ int rc_allgather_outputs(rc_handle* h, void* nccl_comm, const rc_outputs* local,
   RC_CATCH(h)
 }
 
-// The chunk loop of render_image in native code: n_chunks x rc_render_rays on alternating streams (include/rc_abi.h).
-int rc_render_chunks(rc_handle* h, const rc_rays* rays, int64_t chunk, int64_t n_chunks, uint32_t pass_mask,
-                     const rc_outputs* out0, int64_t out_stride, void* const* streams, int32_t n_streams) {
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (!rays || !out0 || !streams) return fail(h, RC_ERR_INVALID_ARG, "rc_render_chunks: null rays/outputs/streams");
-  if (chunk <= 0 || n_chunks < 0 || n_streams <= 0 || out_stride < 0)
-    return fail(h, RC_ERR_INVALID_ARG, "rc_render_chunks: chunk, n_chunks, n_streams, out_stride out of range");
-  if ((pass_mask & RC_PASS_SECONDARY) || (pass_mask & RC_PASS_RESAMPLE))
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_render_chunks: passes that draw random numbers go through rc_render_rays per chunk");
-  for (int64_t i = 0; i < n_chunks; ++i) {
-    rc_rays r = *rays;
-    const int64_t o = i * chunk;
-    auto adv = [&](const float*& p, int w) { if (p) p += o * w; };
-    adv(r.origins, 3); adv(r.directions, 3); adv(r.viewdirs, 3); adv(r.near, 1); adv(r.far, 1); adv(r.lights, 3); adv(r.normals, 3);
-    rc_outputs out = *out0;
-    for (int k = 0; k < RC_OUT_COUNT; ++k)
-      if (out.ptr[k]) out.ptr[k] += i * out_stride;
-    const int rc = rc_render_rays(h, &r, chunk, nullptr, pass_mask, &out, streams[i % n_streams]);
-    if (rc) return rc;
-  }
-  return RC_OK;
-}
-
 }  // extern "C"
 
-namespace {
-
-// rc_render_material's forward, shared with rc_light_sampling_backward (rc_light_host.inc): the argument checks behind
-// the entry point's own, the workspace, and steps 1-2 (the primary cache pass, the shading point), 3a-4 (the shading
-// heads), 5 (BRDF importance sampling) and the arguments of step 6 (the batched secondary trace).  Each step launches
-// what rc_render_material launched before, in the same order.
-struct MatSplit { int Ks, Kd, Kc; };
-
-int material_check(rc_handle* h, const rc_rays* rays, const rc_material_randoms* mr, int32_t K, const char* who, MatSplit& sp,
-                   bool own_samplers = true) {
-  int rc;
-  const std::string w = who;
-  if ((rc = check_rays(h, rays, who))) return rc;
-  const rc_config& c = h->cfg;
-  // Python's round (half to even), as importance_sample_rays and everything that sizes the random tensors
-  sp.Ks = rc_round_half_even(K * (1.0 - (double)c.diffuse_sample_fraction));
-  sp.Kd = rc_round_half_even(K * (double)c.diffuse_sample_fraction);
-  sp.Kc = rc_round_half_even(0.5 * sp.Kd);
-  const int Ks = sp.Ks, Kd = sp.Kd, Kc = sp.Kc;
-  if (Ks + Kd != K)
-    return fail(h, RC_ERR_UNSUPPORTED, w + ": num_secondary_samples does not split into Ks + Kd (round half to even)");
-  if (K < 2 || Ks < 1 || Kd < 2 || Kc < 1 || Kd - Kc < 1 || Ks + Kd > 64)
-    return fail(h, RC_ERR_UNSUPPORTED, w + ": num_secondary_samples must give 1 <= Ks, 2 <= Kd, Ks + Kd <= 64");
-  if (c.num_vmf != 128) return fail(h, RC_ERR_UNSUPPORTED, w + ": num_vmf must be 128");
-  // (own_samplers = false: rc_render_relight's RC_RELIGHT_ENV, which reads neither the BRDF nor the vMF members)
-  if (own_samplers)
-  if (!mr->vmf_noise || !mr->spec_u1 || !mr->spec_u2 || !mr->cos_u1 || !mr->cos_u2 || !mr->vmf_v || !mr->vmf_tmp ||
-      !(mr->vmf_lobe || mr->vmf_lobe_gumbel))
-    return fail(h, RC_ERR_INVALID_ARG, w + ": every sampler member of rc_material_randoms is required "
-                                           "(vmf_lobe or vmf_lobe_gumbel)");
-  if (!(mr->gumbel || mr->resample_inds) || !(mr->sec_gumbel || mr->sec_resample_inds))
-    return fail(h, RC_ERR_INVALID_ARG, w + ": the categorical picks need gumbel or resample_inds (primary) and "
-                                           "sec_gumbel or sec_resample_inds (secondary trace)");
-  return RC_OK;
-}
-
-int material_workspace(rc_handle* h, RenderWs& w, ExtraWs& x, RenderWs& ws_sec, int64_t n, const MatSplit& sp) {
-  const rc_config& c = h->cfg;
-  const int64_t np2 = n * c.num_samples[c.num_levels - 1], nsec = n * (sp.Ks + sp.Kd);
-  int rc;
-  if ((rc = ensure_workspace(h, w, n))) return rc;
-  if ((rc = ws_alloc(h, {{x.m_pts, 3 * n}, {x.m_nrm, 3 * n}, {x.m_feat, 32 * n}, {x.m_mat, RC_MAT_CH * n}, {x.m_feat_all, 32 * np2},
-                         {x.m_mat_all, RC_MAT_CH * np2}, {x.l_feat, 32 * n}, {x.l_vmf, (int64_t)128 * RC_VMF_CH * n},
-                         {x.l_vmf_logit, (int64_t)128 * n}, {x.sec_origins, 3 * nsec}, {x.sec_dirs, 3 * nsec}, {x.sec_near, nsec},
-                         {x.sec_far, nsec}, {x.sec_lights, 3 * nsec}, {x.sec_samples, RC_SMP_CH * nsec}, {x.m_local_view, 3 * n},
-                         {x.sec_rgb, 3 * nsec}, {x.sec_acc, nsec}, {x.sec_env, 3 * nsec}})) ||
-      (rc = ensure_workspace(h, ws_sec, nsec)))
-    return rc;
-  return RC_OK;
-}
-
-// 1. cache pass on the primary rays (all samples shaded) -> cache_out; 2. one shading sample per ray
-void material_primary(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd, const rc_material_randoms* mr,
-                      const rc_outputs* cache_out, RenderWs& w, ExtraWs& x, hipStream_t st) {
-  const rc_config& c = h->cfg;
-  const int NL = c.num_levels;
-  const int S2 = c.num_samples[NL - 1];
-  RenderArgs A{};
-  A.rays = *rays; A.have_rnd = rnd != nullptr; if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = RC_PASS_CACHE; A.out = *cache_out; A.slot = -1;
-  // the fused kernel when the handle runs it (rc_set_fused mode 1): one launch, its per-sample results exported for
-  // steps 2-3 below; bitwise the launch-per-stage pass (tests/test_gpu_parity.py)
-  A.fused = (h->fused_mode == 1 || h->fused_mode == 3) && h->fused_ok && !h->profiling && c.num_samples[NL - 1] == 32;
-  A.export_samples = A.fused;
-  enqueue_all(h, A, w, st);
-
-  // 2. one shading sample per ray (MaterialModel.resample_render, models.py:1430-1439)
-  RcResampleArgs ra{};
-  ra.n_rays = n; ra.S = S2; ra.tdist = w.tdist[NL - 1].p; ra.density = w.density[NL - 1].p;
-  ra.directions = rays->directions; ra.gumbel = mr->gumbel; ra.inds_in = mr->resample_inds;
-  ra.inds_out = (int32_t*)w.inds.p; ra.filt_weight = w.filt_weight.p; ra.weights = w.weights[NL - 1].p; ra.src_out = (int32_t*)w.src_idx.p;
-  // position and predicted normal of the picked sample = the shading point
-  ra.means = w.means[NL - 1].p; ra.normals = w.normals_pred.p; ra.pts_out = x.m_pts.p; ra.nrm_out = x.m_nrm.p;
-  rc_launch_resample(ra, st);
-}
-
-// 3a. material head and 4. light sampler (128 vMF lobes) at the shading point: one lookup launch + one head launch on the
-// caller's stream
-void material_heads(rc_handle* h, int64_t n, const rc_material_randoms* mr, ExtraWs& x, hipStream_t st) {
-  const rc_config& c = h->cfg;
-  const auto& raw = h->packs.raw;
-  roctx_stage("material: heads + light sampler");
-  RcMatHeadArgs ma{};
-  ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
-  ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
-  ma.min_roughness = c.min_roughness;
-  RcLightHeadArgs la{};
-  la.n = n; la.feat = x.l_feat.p;
-  la.w0 = raw[RAW_LIGHT_0].kernel.p; la.b0 = raw[RAW_LIGHT_0].bias.p;
-  la.w1 = raw[RAW_LIGHT_1].kernel.p; la.b1 = raw[RAW_LIGHT_1].bias.p;
-  la.w2 = raw[RAW_LIGHT_OUT].kernel.p; la.b2 = raw[RAW_LIGHT_OUT].bias.p;
-  la.pts = x.m_pts.p; la.noise = mr->vmf_noise; la.vmf_scale = c.vmf_scale; la.vmf = x.l_vmf.p; la.vmf_logit = x.l_vmf_logit.p;
-  // caller's stream, the critical path: both grids at the shading points in one launch, both heads in one launch (as
-  // four launches on two streams the BRDF sampler waited ~12 us for the event behind the light head)
-  rc_launch_hashgrid_two(h->grids[4].dev, h->grids[5].dev, x.m_pts.p, n, x.m_feat.p, x.l_feat.p, c.contract_radius, st);
-  ma.n = n; ma.feat = x.m_feat.p; ma.mat = x.m_mat.p;
-  rc_launch_shading_heads(ma, la, st);
-}
-
-// 5. BRDF importance sampling -> secondary rays
-void material_brdf_sample(rc_handle* h, const rc_rays* rays, int64_t n, const rc_material_randoms* mr, const MatSplit& sp,
-                          ExtraWs& x, hipStream_t st) {
-  const rc_config& c = h->cfg;
-  roctx_stage("material: brdf sample");
-  RcBrdfSampleArgs sa{};
-  sa.n = n; sa.Ks = sp.Ks; sa.Kd = sp.Kd; sa.Kc = sp.Kc;
-  sa.pts = x.m_pts.p; sa.nrm = x.m_nrm.p; sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
-  sa.mat = x.m_mat.p; sa.vmf = x.l_vmf.p; sa.vmf_logit = x.l_vmf_logit.p;
-  sa.spec_u1 = mr->spec_u1; sa.spec_u2 = mr->spec_u2; sa.cos_u1 = mr->cos_u1; sa.cos_u2 = mr->cos_u2;
-  sa.vmf_lobe = mr->vmf_lobe; sa.vmf_v = mr->vmf_v; sa.vmf_tmp = mr->vmf_tmp; sa.vmf_lobe_gumbel = mr->vmf_lobe_gumbel;
-  sa.normal_eps = c.secondary_normal_eps; sa.near = c.secondary_near; sa.far = c.secondary_far;
-  sa.sec_origins = x.sec_origins.p; sa.sec_dirs = x.sec_dirs.p; sa.sec_near = x.sec_near.p; sa.sec_far = x.sec_far.p;
-  sa.sec_lights = x.sec_lights.p; sa.samples = x.sec_samples.p; sa.local_view = x.m_local_view.p;
-  rc_launch_brdf_sample(sa, st);
-}
-
-// 6. the arguments of the ONE batched secondary trace through the cache (is_secondary, resample, use_env_map=False;
-//    ref_rays.normals = None since MaterialMLP.shadow_eps_indirect = False) -> sec_rgb, sec_acc
-int material_trace_args(rc_handle* h, const rc_material_randoms* mr, int64_t nsec, ExtraWs& x, hipStream_t st, RenderArgs& B) {
-  const rc_config& c = h->cfg;
-  B = RenderArgs{};
-  B.rays.origins = x.sec_origins.p; B.rays.directions = x.sec_dirs.p; B.rays.viewdirs = x.sec_dirs.p;
-  B.rays.near = x.sec_near.p; B.rays.far = x.sec_far.p; B.rays.lights = x.sec_lights.p; B.rays.normals = nullptr;
-  B.have_rnd = true;
-  for (int l = 0; l < RC_MAX_LEVELS; ++l) B.rnd.jitter[l] = mr->sec_jitter[l];
-  B.rnd.gumbel = mr->sec_gumbel; B.rnd.resample_inds = mr->sec_resample_inds;
-  B.n = nsec; B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY | RC_PASS_NO_ENVMAP; B.slot = -1;
-  // every secondary ray of this trace has the same (near, far) (k_brdf_sample writes the two constants): the
-  // power-ladder image of the pair is computed once instead of by each of the 3 x 32 768 sampler waves
-  // ... and once per handle: the five inputs are constants of the configuration (same device function, a buffer of
-  // the handle's own; 5 us + a 6 us gap in every step before)
-  if (!h->sec_sbounds) {
-    RC_HIP(h, hipMalloc((void**)&h->sec_sbounds, 2 * sizeof(float)));
-    rc_launch_ladder_bounds(c.secondary_near, c.secondary_far, c.env_map_distance, c.raydist_p, c.raydist_premult, h->sec_sbounds, st);
-    RC_HIP(h, hipStreamSynchronize(st));       // later calls may come on other streams
-  }
-  B.s_bounds = h->sec_sbounds;
-  memset(&B.out, 0, sizeof(B.out));
-  B.out.ptr[RC_OUT_RGB] = x.sec_rgb.p; B.out.ptr[RC_OUT_ACC] = x.sec_acc.p;
-  return RC_OK;
-}
-
-int relight_check(rc_handle* h, const rc_relight_args* rl, int64_t n, const MatSplit& sp);      // rc_relight_host.inc
-
-// The material stage: rc_render_material (rl == nullptr) and rc_render_relight (rc_relight_host.inc), which replaces the
-// EnvMap along the secondary rays by the bound image's lookup, in RC_RELIGHT_ENV the light head and the BRDF sampler by the
-// environment sampler, and scales the albedo; every other launch is the same code in the same order.
-int material_render(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd, const rc_material_randoms* mr, int32_t K,
-                    const rc_relight_args* rl, const rc_outputs* cache_out, const rc_mat_outputs* mat_out, void* stream_v,
-                    const char* who_c) {
-  const std::string who = who_c;
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": this handle renders the time-resolved cache (rc_render_transient)");
-  if (!rays || !mr || !cache_out || !mat_out) return fail(h, RC_ERR_INVALID_ARG, who + ": null argument");
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n_rays");
-  if (n == 0) return RC_OK;
-  int rc;
-  MatSplit sp;
-  const bool env_mode = rl && rl->mode == RC_RELIGHT_ENV;
-  if ((rc = material_check(h, rays, mr, K, who_c, sp, !env_mode))) return rc;
-  if (rl && (rc = relight_check(h, rl, n, sp))) return rc;
-  const float* ratio = rl ? rl->albedo_ratio : nullptr;
-  const rc_config& c = h->cfg;
-  const int Ks = sp.Ks, Kd = sp.Kd;
-  RC_HIP(h, hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream_v;
-  if ((rc = ensure_packed(h))) return rc;
-  if (!h->have_material) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/MaterialShader/* or params/LightSampler/*");
-  if (!rl && !h->have_envmap) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: params/Cache/EnvMap/*");
-  const int NL = c.num_levels;
-  const int S2 = c.num_samples[NL - 1];
-  const int64_t np2 = n * S2, nsec = n * (Ks + Kd);
-  WsUse use(h, WS_RENDER0, st);          // shares set 0 (and the secondary set) with the other entry points
-  if ((rc = use.rc)) return rc;
-  RenderWs& w = use.s.r;
-  ExtraWs& x = ws_extra<ExtraWs>(use.s);
-  RenderWs& ws_sec = h->ws[WS_SECONDARY].r;
-  if ((rc = material_workspace(h, w, x, ws_sec, n, sp))) return rc;
-  rc_shader_prepare();
-
-  // 1. cache pass on the primary rays (all samples shaded) -> cache_out; 2. one shading sample per ray
-  material_primary(h, rays, n, rnd, mr, cache_out, w, x, st);
-  const auto& raw = h->packs.raw;
-  // Side stream: the material-only composite over all samples (step 3b) and the EnvMap along the secondary rays (step 6b)
-  // feed only the outputs / the final integration, so they leave the critical path sampler -> trace -> integrate and
-  // fill the gaps of its latency-bound kernels.  Forked from and joined to the caller's stream with events: to the
-  // caller the call is still ordered on `st` alone.
-  { int rcs = ensure_side_stream(h); if (rcs) return rcs; }
-  hipStream_t side = h->side_stream;
-  // Whatever way this function is left once work has been forked onto the side stream, the caller's stream is joined
-  // to it again BEFORE the workspace set is released (declared after `use`: destroyed first): an early error
-  // return must not leave side-stream kernels writing mat_out / sec_env behind a caller that believes `st` orders
-  // everything of the call.
-  struct SideJoin {
-    rc_handle* h; hipStream_t st, side; bool forked;
-    ~SideJoin() {
-      if (!forked) return;
-      if (hipEventRecord(h->ev_side[2], side) != hipSuccess || hipStreamWaitEvent(st, h->ev_side[2], 0) != hipSuccess)
-        (void)hipStreamSynchronize(side);
-    }
-  } side_join{h, st, side, false};
-  // 3a. material head and 4. light sampler (128 vMF lobes) at the shading point
-  if (env_mode) {
-    // _handle_light_sampling_pass hands the image's tables on: the LightSampler is not evaluated
-    RcMatHeadArgs ma{};
-    ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
-    ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
-    ma.min_roughness = c.min_roughness;
-    roctx_stage("material: head");
-    rc_launch_hashgrid(h->grids[4].dev, x.m_pts.p, 0, n, x.m_feat.p, 0, 32, c.contract_radius, nullptr, st);
-    ma.n = n; ma.feat = x.m_feat.p; ma.mat = x.m_mat.p;
-    rc_launch_material_head(ma, st);
-  } else {
-    material_heads(h, n, mr, x, st);
-  }
-  // albedo <- clip(albedo ratio, 0, 1) (_predict_material_and_feature, material.py:2106-2116)
-  if (ratio) rc_launch_albedo_ratio(x.m_mat.p, n, ratio, st);
-  // 5. BRDF importance sampling -> secondary rays
-  if (env_mode) {
-    roctx_stage("material: environment sample");
-    RcEnvSampleArgs sa{};
-    sa.n = n; sa.Ks = Ks; sa.Kd = Kd;
-    sa.pts = x.m_pts.p; sa.nrm = x.m_nrm.p; sa.viewdirs = rays->viewdirs; sa.lights = rays->lights;
-    sa.pdf = h->env_pdf.p; sa.dirs = h->env_dirs.p; sa.hw = (int64_t)h->env_img_h * h->env_img_w;
-    sa.picks_spec = rl->picks_spec; sa.picks_diff = rl->picks_diff; sa.T_spec = rl->T_spec; sa.T_diff = rl->T_diff;
-    sa.normal_eps = c.secondary_normal_eps; sa.near = c.secondary_near; sa.far = c.secondary_far;
-    sa.sec_origins = x.sec_origins.p; sa.sec_dirs = x.sec_dirs.p; sa.sec_near = x.sec_near.p; sa.sec_far = x.sec_far.p;
-    sa.sec_lights = x.sec_lights.p; sa.samples = x.sec_samples.p; sa.local_view = x.m_local_view.p;
-    rc_launch_env_sample(sa, st);
-  } else {
-    material_brdf_sample(h, rays, n, mr, sp, x, st);
-  }
-  // 3b. side stream: the material head on ALL samples and the material-only composite (outputs only).  Forked HERE, behind
-  // the BRDF sampler: beside the small latency-bound kernels above they doubled those kernels' times (heads 18 -> 35 us,
-  // sampler 19 -> 33 us); beside the first level of the trace they fit into what its workgroups leave of a CU (no LDS /
-  // 11 KB) and cost it little.
-  {
-    RC_HIP(h, hipEventRecord(h->ev_side[0], st));
-    RC_HIP(h, hipStreamWaitEvent(side, h->ev_side[0], 0));
-    side_join.forked = true;
-    RcMatHeadArgs ma{};
-    ma.w0 = raw[RAW_MAT_BOTTLENECK].kernel.p; ma.b0 = raw[RAW_MAT_BOTTLENECK].bias.p;
-    ma.w1 = raw[RAW_MAT_BRDF].kernel.p; ma.b1 = raw[RAW_MAT_BRDF].bias.p;
-    ma.min_roughness = c.min_roughness;
-    rc_launch_hashgrid(h->grids[4].dev, w.means[NL - 1].p, 1, np2, x.m_feat_all.p, 0, 32, c.contract_radius, nullptr, side);
-    ma.n = np2; ma.feat = x.m_feat_all.p; ma.mat = x.m_mat_all.p;
-    rc_launch_material_head(ma, side);
-    if (ratio) rc_launch_albedo_ratio(x.m_mat_all.p, np2, ratio, side);
-    rc_launch_material_composite_all(n, S2, w.weights[NL - 1].p, x.m_mat_all.p, mat_out->ptr[RC_MOUT_MATERIAL_ALBEDO],
-                                     mat_out->ptr[RC_MOUT_MATERIAL_ROUGHNESS], mat_out->ptr[RC_MOUT_MATERIAL_METALNESS],
-                                     mat_out->ptr[RC_MOUT_MATERIAL_F_0], c.default_F_0, side);
-  }
-  // 6. ONE batched secondary trace through the cache (is_secondary, resample, use_env_map=False;
-  //    ref_rays.normals = None since MaterialMLP.shadow_eps_indirect = False) + EnvMap along the same rays
-  {
-    RenderArgs B;
-    if ((rc = material_trace_args(h, mr, nsec, x, st, B))) return rc;
-    RcEnvMapArgs ea{};
-    ea.n = nsec; ea.viewdirs = x.sec_dirs.p; ea.wstream = h->packs.envmap.p; ea.rgb_bias = c.env_rgb_bias; ea.env_rgb = x.sec_env.p;
-    // 6b. EnvMap of the secondary directions, on the side stream.  It is MFMA-bound and keeps a CU's LDS to itself, as the
-    // level kernels of the trace do: next to a level kernel it only gets the CUs that kernel's persistent workgroups
-    // leave.  Beside the first two levels (F = 1: bound by their own instruction issue) every CU it takes is a CU they
-    // miss; the LAST level (F = 4) is bound by the fabric's random-sector rate, not by CUs.  So the EnvMap is released when
-    // that level is launched, and that launch leaves it a quarter of the CUs (RC_ENV_RESERVE overrides; 0 = beside the
-    // first level as before): 1.48 -> 1.45 ms per step (reserve 32 / 64 / 96 of 256: 1.463 / 1.447-1.456 / 1.508).
-    // (split-MFMA build: the EnvMap takes 0.7 of the time on the bf16 pipe and an eighth of the CUs is enough -- 16 ... 40 of
-    // 256 measure 1.315-1.33 ms per step, 64: 1.36, 80: 1.38)
-    static const int env_reserve = getenv("RC_ENV_RESERVE") ? atoi(getenv("RC_ENV_RESERVE")) : rc_device_cus() / (kRcSplit ? 8 : 4);
-    // (rc_render_relight: the image lookup is memory-bound and short; it never takes that spot)
-    const RcEnvLookupArgs la{RcEnvImage{h->env_padded.p, h->env_img_h, h->env_img_w}, x.sec_dirs.p, nsec, x.sec_env.p};
-    const bool beside_last = !rl && env_reserve > 0 && nsec >= 24576 && (h->fused_mode == 1 || h->fused_mode == 3);
-    bool env_released = false;
-    if (beside_last) {
-      B.env = &ea; B.env_side = side; B.env_ready = h->ev_side[1]; B.env_done = h->ev_side[2]; B.env_reserve = env_reserve;
-      B.env_released = &env_released;
-    } else {
-      RC_HIP(h, hipEventRecord(h->ev_side[1], st));               // secondary rays are in place
-      RC_HIP(h, hipStreamWaitEvent(side, h->ev_side[1], 0));
-      if (rl) rc_launch_env_lookup(la, side); else rc_launch_envmap(ea, side);
-      RC_HIP(h, hipEventRecord(h->ev_side[2], side));
-      env_released = true;
-    }
-    enqueue_all(h, B, ws_sec, st);
-    if (!env_released) {
-      // the trace took a launch plan without that spot (per-stage profiling on, a grid layout the level kernels do not
-      // cover): the EnvMap behind the trace
-      RC_HIP(h, hipEventRecord(h->ev_side[1], st));
-      RC_HIP(h, hipStreamWaitEvent(side, h->ev_side[1], 0));
-      rc_launch_envmap(ea, side);
-      RC_HIP(h, hipEventRecord(h->ev_side[2], side));
-    }
-    RC_HIP(h, hipStreamWaitEvent(st, h->ev_side[2], 0));          // join: everything of this call is ordered on st again
-    side_join.forked = false;
-  }
-  // 7. Monte-Carlo BRDF integration + MaterialIntegrator composite
-  roctx_stage("material: integrate");
-  {
-    RcMatIntegrateArgs ia{};
-    ia.n = n; ia.Ks = Ks; ia.Kd = Kd; ia.S = S2;
-    ia.mat = x.m_mat.p; ia.samples = x.sec_samples.p; ia.local_view = x.m_local_view.p; ia.sec_rgb = x.sec_rgb.p;
-    ia.sec_acc = x.sec_acc.p; ia.sec_env = x.sec_env.p; ia.weights = w.weights[NL - 1].p; ia.filt_weight = w.filt_weight.p;
-    ia.pts = x.m_pts.p; ia.nrm = x.m_nrm.p; ia.origins = rays->origins; ia.lights = rays->lights;
-    ia.f0 = c.default_F_0; ia.rgb_max = c.rgb_max; ia.bg = c.bg_intensity;
-    ia.out = *mat_out;
-    rc_launch_material_integrate(ia, st);
-  }
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rc_render_material(rc_handle* h, const rc_rays* rays, int64_t n, const rc_randoms* rnd,
-                       const rc_material_randoms* mr, int32_t K, const rc_outputs* cache_out,
-                       const rc_mat_outputs* mat_out, void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  RoctxScope roctx_call("rc_render_material");
-  return material_render(h, rays, n, rnd, mr, K, nullptr, cache_out, mat_out, stream_v, "rc_render_material");
-  RC_CATCH(h)
-}
-
-}  // extern "C"
-
+#include "rc_render_host.inc"
+#include "rc_material_host.inc"
 #include "rc_transient_host.inc"
 #include "rc_transient_slice_host.inc"
 #include "rc_batch_host.inc"

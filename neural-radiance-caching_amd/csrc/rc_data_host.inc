@@ -64,11 +64,8 @@ int rc_data_backward(rc_handle* h, const rc_rays* rays, const float* gt_rgb, con
     return rc;
 
   // 1. the training forward: rc_render_rays' launch-per-stage cache pass, no analytic normals
-  RenderArgs A{};
-  A.rays = *rays;
-  A.have_rnd = rnd != nullptr;
-  if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = RC_PASS_CACHE; A.slot = -1; A.fused = false; A.anneal = anneal;
+  RenderArgs A = cache_pass(rays, rnd, n);
+  A.anneal = anneal;
   A.out.ptr[RC_OUT_RGB] = x.rgb.p;
   enqueue_all(h, A, w, st);
 

@@ -216,20 +216,6 @@ __device__ __forceinline__ u32x4 ws_read4(const WStream& w, int f) {
   return lds_piece(w.ring + (f % (2 * CH)) * 64 + w.lane * 4);
 }
 
-// The same fragment stream read straight from global memory (L2-resident: one kernel's stream is <= 0.7 MB), one
-// coalesced 256-byte load per fragment and wave, no LDS ring and therefore NO workgroup barriers: the waves of a
-// workgroup are free to drift apart.  Which stream type a kernel uses is a property of the kernel; the arithmetic
-// (fragment order, MFMA order) is identical.
-struct WDirect {
-  const float* g;
-  int lane;
-  mutable f32x4 sink = {0.0f, 0.0f, 0.0f, 0.0f};
-};
-template <int NF, int W = kWaves, int CH = kChunk>
-__device__ __forceinline__ float ws_read(const WDirect& w, int f) { return w.g[(size_t)f * 64 + w.lane]; }
-template <int NF, int W = kWaves, int CH = kChunk>
-__device__ __forceinline__ u32x4 ws_read4(const WDirect& w, int f) { return *reinterpret_cast<const u32x4*>(w.g + (size_t)f * 64 + w.lane * 4); }
-
 // Where a layer's B operand comes from: bf(s) is this lane's value of k-step s, s a compile-time constant once the
 // layer's loops are unrolled.
 //  BAct   the lane's activation column in LDS (act[s * 64] is step s): values that cross lanes on their way to the

@@ -58,16 +58,10 @@ __device__ __forceinline__ float density_level64(const WS& ws, float* act_wave, 
 
 // FRONT: stop behind the last proposal level (density MLP + appearance lookup) and hand the per-sample results to the
 // stages of the time-resolved cache; the stream then ends at F_SH.
-// DIRECT (experiment, -DRC_FUSED_DIRECT_EXPERIMENT + RC_FUSED_DIRECT=1): the weight fragments come straight from global
-// memory (WDirect: L2-resident, one coalesced 256-byte load per fragment) instead of through the workgroup's LDS ring:
-// no ring, no workgroup barrier anywhere in the kernel, so the four rays of a workgroup drift apart and their gather
-// phases stop queueing behind each other in the CU's memory pipe.  Bitwise equal results; measured 145 us per 1024 rays
-// against 132 us through the ring: 2165 extra vector loads per ray and their L2 latency cost more than the 40 barriers
-// and the lockstep.  Kept as a template parameter, not instantiated in the product build.
 // EXPORT: the full kernel that also leaves the last level's per-sample results (fence posts, density, sample means,
 // predicted normals) in the workspace buffers of the launch-per-stage plan, for a caller that goes on working per sample
 // behind the cache pass (the material stage: its shading-point pick and the material-only composite).
-template <bool GRAD, bool FRONT = false, bool DIRECT = false, bool EXPORT = false>
+template <bool GRAD, bool FRONT = false, bool EXPORT = false>
 __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   split_exclusive_simd();
   constexpr int NF = FRONT ? F_SH : NF_FUSED;
@@ -82,15 +76,13 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   float* s_sd[2] = {scr, scr + 68};
   float* s_td = scr + 2 * 68; float* s_cw = scr + 3 * 68; float* s_c = scr + 4 * 68; float* s_v = scr + 5 * 68;
   float* s_out = scr + 6 * 68;
-  typename std::conditional<DIRECT, WDirect, WStream>::type ws;
-  if constexpr (DIRECT) { ws.g = a.wstream; ws.lane = lane; }
-  else ws = WStream(a.wstream, ring, lane, wave);
+  WStream ws(a.wstream, ring, lane, wave);
 #ifdef RC_STAMPS
   unsigned long long stamps[16];
   const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
   RC_FSTAMP(0);
-  if constexpr (!DIRECT) ws_begin<NF>(ws);
+  ws_begin<NF>(ws);
 
   const float ox = a.origins[3 * ray], oy = a.origins[3 * ray + 1], oz = a.origins[3 * ray + 2];
   const float dx = a.directions[3 * ray], dy = a.directions[3 * ray + 1], dz = a.directions[3 * ray + 2];
@@ -368,7 +360,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
       }
       ngx = rc_div(gzx, a.contract_radius); ngy = rc_div(gzy, a.contract_radius); ngz = rc_div(gzz, a.contract_radius);
       neg_normalize(ngx, ngy, ngz);
-    } else if constexpr (!FRONT && !DIRECT) {
+    } else if constexpr (!FRONT) {
       // the stream is consumed strictly in order: step the ring over the unused backward fragments
 #pragma unroll
       for (int f = F_L2 + FR::B1; f < F_SH; ++f)
@@ -540,12 +532,8 @@ void rc_launch_fused(const RcFusedLaunch& L, hipStream_t stream) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-#ifdef RC_FUSED_DIRECT_EXPERIMENT
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-#endif
   }
   RcFusedArgs a{};
   a.origins = L.rays.origins; a.directions = L.rays.directions; a.viewdirs = L.rays.viewdirs; a.near = L.rays.near;
@@ -583,20 +571,12 @@ void rc_launch_fused(const RcFusedLaunch& L, hipStream_t stream) {
     a.f_tdist = L.f_tdist; a.f_density = L.f_density; a.f_means = L.f_means; a.f_normals_pred = L.f_normals_pred;
   } else if (L.export_samples) {
     a.f_tdist = L.f_tdist; a.f_density = L.f_density; a.f_means = L.f_means; a.f_normals_pred = L.f_normals_pred;
-    if (L.out.ptr[RC_OUT_NORMALS]) hipLaunchKernelGGL((k_cache_fused<true, false, false, true>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((k_cache_fused<false, false, false, true>), grid, block, lds, stream, a);
-    return;
-  }
-#ifdef RC_FUSED_DIRECT_EXPERIMENT      // measured 145.3 us against 132.2 us through the ring (same box, bitwise equal results): not built by default
-  if (L.direct) {
     if (L.out.ptr[RC_OUT_NORMALS]) hipLaunchKernelGGL((k_cache_fused<true, false, true>), grid, block, lds, stream, a);
     else hipLaunchKernelGGL((k_cache_fused<false, false, true>), grid, block, lds, stream, a);
     return;
   }
-#endif
 #if RC_TEAM_KERNEL
   if (L.team) {
-    a.stagger_cycles = L.stagger_cycles;
     a.prio_mode = L.prio_mode;
     rc_launch_fused_team(a, L.out.ptr[RC_OUT_NORMALS] != nullptr, stream);
     return;

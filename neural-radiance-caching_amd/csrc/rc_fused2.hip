@@ -329,28 +329,6 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   unsigned long long tb_wait = 0, tb_count = 0;
   const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  // Stagger (see rc_launch_fused_team): the workgroups that share a CU run the same phases at the same time -- all of
-  // them in the lookups (bound by the memory system's random-sector rate, SIMDs idle), then all of them in the matrix
-  // phases.  Every second workgroup to ARRIVE on a physical CU starts `stagger_cycles` late, so one half of the batch
-  // gathers while the other half multiplies.  Which workgroups share a CU is the dispatcher's business: the arrival
-  // counter is indexed by the hardware's own CU identity.
-  if (a.stagger_cycles > 0) {
-    int late = 0;
-    if (threadIdx.x == 0) {
-      const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);          // HW_REG_HW_ID: CU_ID 11:8, SH_ID 12, SE_ID 15:13
-      const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);         // HW_REG_XCC_ID 3:0
-      const uint32_t key = ((xcc & 15u) << 8) | ((hw >> 8) & 255u);
-      late = atomicAdd(&a.cu_slots[key], 1) & 1;
-      lds_dyn[0] = __int_as_float(late);
-    }
-    __syncthreads();
-    late = __float_as_int(lds_dyn[0]);
-    __syncthreads();
-    if (late) {
-      const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-      while (__builtin_amdgcn_s_memtime() - t_start < (unsigned long long)a.stagger_cycles) __builtin_amdgcn_s_sleep(16);
-    }
-  }
   // Priorities.  The workgroup dispatched second onto a CU loses every issue arbitration to the older one (age): it
   // falls 25 us behind in the proposal levels and then runs the tail of its shader alone, its stalls exposed.  Mode 1
   // (default): the younger workgroup -- the second half of the grid, the dispatcher deals the first half one per CU --
@@ -857,16 +835,6 @@ void rc_launch_fused_team(const RcFusedArgs& a, bool grad, hipStream_t stream) {
   // resident at once (two workgroups per CU); beyond that workgroups start as others finish and the scheme costs
   // 2.4 % (16 384 rays: 1790 -> 1833 us), so it is switched off
   if ((int64_t)grid.x > 2 * (int64_t)rc_device_cus() || kRays != 2) b.prio_mode = 0;
-  if (b.stagger_cycles > 0) {
-    static std::atomic<int32_t*> slots{nullptr};       // one process drives one GPU (one handle per device)
-    int32_t* p = slots.load();
-    if (!p) {
-      if (hipMalloc((void**)&p, 4096 * sizeof(int32_t)) != hipSuccess || hipMemset(p, 0, 4096 * sizeof(int32_t)) != hipSuccess) p = nullptr;
-      slots.store(p);
-    }
-    b.cu_slots = p;
-    if (!p) b.stagger_cycles = 0;
-  }
   if (grad) hipLaunchKernelGGL(k_cache_fused_team<true>, grid, block, lds, stream, b);
   else hipLaunchKernelGGL(k_cache_fused_team<false>, grid, block, lds, stream, b);
 }

@@ -63,12 +63,8 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
   if (grads && (rc = ws_alloc(h, {{x.d_density, np}, {x.d_pred, 3 * np}}))) return rc;
 
   // 1. the training forward: the sampler levels, the last with hbuf, normals_pred and the analytic normals
-  RenderArgs A{};
-  A.rays = *rays;
-  A.have_rnd = rnd != nullptr;
-  if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = RC_PASS_CACHE; A.slot = -1; A.fused = false; A.anneal = anneal;
-  A.levels_only = true; A.force_grad = true;
+  RenderArgs A = cache_pass(rays, rnd, n);
+  A.anneal = anneal; A.stop = RENDER_LEVELS; A.force_grad = true;
   enqueue_all(h, A, w, st);
 
   // 2. the four terms, d loss / d density and d loss / d pred_raw

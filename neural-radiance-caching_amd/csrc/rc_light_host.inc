@@ -1,7 +1,7 @@
 // Host side of rc_light_sampling_backward and rc_light_regularizer (rc_light.hip); included by rc_api.hip.
 //
 // One rc_light_sampling_backward call = rc_render_material's forward up to the batched secondary trace (material_* in
-// rc_api.hip, on set 0 and WS_SECONDARY) -> the light head's recompute on k_gemm (h0, h1, vmf_params; "ls:" buffers) ->
+// rc_material_host.inc, on set 0 and WS_SECONDARY) -> the light head's recompute on k_gemm (h0, h1, vmf_params; "ls:" buffers) ->
 // k_light_sampling_loss_bwd (per-point loss sums, d loss / d vmf_params) -> k_interlevel_reduce (the loss, fixed order) ->
 // with a gradient buffer: the three dense layers' backward on k_gemm (input gradients masked by ReLU', weight gradients
 // over fixed K slices of points, added up by k_sum_parts in slice order) and rc_hashgrid_backward of the light grid.

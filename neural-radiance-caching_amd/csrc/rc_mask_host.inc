@@ -65,12 +65,8 @@ int rc_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, cons
 
   // 1. the training forward: the sampler levels only (weights_only=True, models.py:476-486), stopped behind the last
   //    level's density
-  RenderArgs A{};
-  A.rays = *rays;
-  A.have_rnd = rnd != nullptr;
-  if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = RC_PASS_CACHE; A.slot = -1; A.fused = false;
-  A.sampler_only = true; A.anneal = anneal;
+  RenderArgs A = cache_pass(rays, rnd, n);
+  A.stop = RENDER_SAMPLER; A.anneal = anneal;
   enqueue_all(h, A, w, st);
 
   // 2. the loss and d loss / d density of the last level

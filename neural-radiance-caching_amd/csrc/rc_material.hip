@@ -14,7 +14,7 @@
 //
 // These are small element-wise / per-point kernels (a few MFLOP per batch): one wavefront per shading
 // point, lanes = secondary samples or vMF lobes; the heavy part of the stage is the batched secondary
-// trace, which re-enters the cache kernels (rc_api.hip) on R*K rays.
+// trace, which re-enters the cache kernels (rc_render_host.inc) on R*K rays.
 #include "rc_internal.h"
 #include "rc_dev_material.h"     // sigmoidf, V3 / Frame: get_rotation_matrix, global_to_local, local_to_global
 

@@ -1,6 +1,6 @@
 // Host side of rc_material_smoothness_backward and rc_material_regularizer (rc_material_bwd.hip); included by rc_api.hip.
 //
-// One rc_material_smoothness_backward call = rc_render_material's steps 1-2 (material_primary in rc_api.hip, on set 0) ->
+// One rc_material_smoothness_backward call = rc_render_material's steps 1-2 (material_primary in rc_material_host.inc, on set 0) ->
 // k_material_smoothness_points (x, x' = x + noise_scale nu; "ms:pts") -> one material-grid lookup over the 2n points
 // ("ms:feat"; the same device function as rc_render_material's k_hashgrid_two) -> k_material_smoothness_bwd (both heads,
 // m(x) into m_mat, the loss terms and per-workgroup loss sums, with a gradient buffer the head's backward, d loss /

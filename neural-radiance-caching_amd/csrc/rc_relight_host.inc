@@ -3,7 +3,7 @@
 //
 // rc_set_env_image = pad kernel + three device-to-device copies + safe_log(pmf), all into the handle's own allocations.
 // rc_env_tables = per-workgroup sums -> tables.  rc_env_pick = zero the maxima -> draw -> finish.  rc_render_relight =
-// material_render (rc_api.hip) with the relight arguments.  Nothing here reads device memory.
+// material_render (rc_material_host.inc) with the relight arguments.  Nothing here reads device memory.
 
 namespace {
 

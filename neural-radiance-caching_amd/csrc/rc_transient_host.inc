@@ -191,15 +191,7 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipS
   {
     // acc, distances and the geometry composites are those of the steady-state integrator (render.py:283-330);
     // this kernel also leaves the alpha-compositing weights of the last level in the workspace for the bins kernel
-    RcCompositeArgs ca{};
-    ca.directions = A.rays.directions; ca.origins = A.rays.origins; ca.lights = A.rays.lights; ca.n_rays = n; ca.S = S2;
-    ca.tdist = w.tdist[NL - 1].p; ca.density = w.density[NL - 1].p; ca.means = w.means[NL - 1].p; ca.normals_pred = w.normals_pred.p;
-    ca.normals_grad = A.out.ptr[RC_OUT_NORMALS] ? w.normals_grad.p : nullptr;
-    ca.shade = w.shade.p; ca.Sf = S2; ca.inds = nullptr; ca.filt_weight = nullptr; ca.weights = w.weights[NL - 1].p;
-    ca.bg = 0.0f;
-    ca.pct[0] = c.percentiles[0]; ca.pct[1] = c.percentiles[1]; ca.pct[2] = c.percentiles[2];
-    ca.out = A.out;
-    rc_launch_composite(ca, st);
+    rc_launch_composite(composite_args(h, A, w, false, true, 0.0f), st);
   }
   const float* occ = nullptr;
   if (t.use_occlusions) {
@@ -212,13 +204,11 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipS
     sr.origins = x.sh_origins.p; sr.dirs = x.sh_dirs.p; sr.near = x.sh_near.p; sr.far = x.sh_far.p;
     sr.out_normals = x.sh_normals.p; sr.out_lights = x.sh_lights.p;
     rc_launch_shadow_rays(sr, st);
-    RenderArgs B{};
-    B.rays.origins = sr.origins; B.rays.directions = sr.dirs; B.rays.viewdirs = sr.dirs; B.rays.near = sr.near; B.rays.far = sr.far;
-    B.rays.lights = sr.out_lights; B.rays.normals = sr.out_normals;
-    B.have_rnd = A.shadow_rnd != nullptr;
-    if (A.shadow_rnd) B.rnd = *A.shadow_rnd;
-    B.n = nsec; B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY; B.slot = -1; B.fused = false; B.weights_only = true;
-    memset(&B.out, 0, sizeof(B.out));
+    rc_rays shadow{};
+    shadow.origins = sr.origins; shadow.directions = sr.dirs; shadow.viewdirs = sr.dirs; shadow.near = sr.near; shadow.far = sr.far;
+    shadow.lights = sr.out_lights; shadow.normals = sr.out_normals;
+    RenderArgs B = cache_pass(&shadow, A.shadow_rnd, nsec);
+    B.mask = RC_PASS_CACHE | RC_PASS_SECONDARY; B.stop = RENDER_WEIGHTS;
     B.out.ptr[RC_OUT_ACC] = x.sh_acc.p;
     enqueue_all(h, B, h->ws[WS_SECONDARY].r, st);
     occ = x.sh_acc.p;
@@ -310,14 +300,9 @@ int render_transient_impl(rc_handle* h, const rc_rays* rays, const float* cam_or
       return rc;
   }
   rc_shader_prepare();
-  RenderArgs A{};
-  A.rays = *rays;
-  A.have_rnd = rnd != nullptr;
-  if (rnd) A.rnd = *rnd;
-  A.n = n; A.mask = RC_PASS_CACHE; A.fused = false; A.slot = -1;
+  RenderArgs A = cache_pass(rays, rnd, n);
   A.tout = out; A.tslices = slices; A.cam_origins = cam_origins; A.shadow_rnd = shadow_rnd; A.force_grad = h->tcfg.use_occlusions != 0;
   // outputs shared with the steady-state compositing kernel
-  memset(&A.out, 0, sizeof(A.out));
   A.out.ptr[RC_OUT_ACC] = out->ptr[RC_TOUT_ACC];
   A.out.ptr[RC_OUT_DISTANCE_MEAN] = out->ptr[RC_TOUT_DISTANCE_MEAN];
   A.out.ptr[RC_OUT_DISTANCE_MEDIAN] = out->ptr[RC_TOUT_DISTANCE_MEDIAN];

@@ -305,33 +305,33 @@ class Cases:
 _D, _G, _L, _M, _T = HOST_FILES
 PRODUCTION = [
     # rc_data_host.inc: the recompute
-    (_D, 125, ("fwd", 96, 1, 96, 0, 10, 0, 0)), (_D, 126, ("fwd", 96, 3, 96, 0, 10, 1, 0)),
-    (_D, 127, ("fwd", 96, 3, 96, 0, 10, 4, 0)), (_D, 128, ("fwd", 96, 3, 96, 0, 10, 7, 0)),
-    (_D, 129, ("fwd", 64, 3, 96, 0, 3, 0, 0)), (_D, 130, ("fwd", 96, 128, 96, 0, 328, 128, 0)),
-    (_D, 131, ("fwd", 96, 128, 96, 0, 129, 0, 0)), (_D, 133, ("fwd", 129, 64, 129, 0, 64, 0, 1)),
-    (_D, 134, ("fwd", 64, 64, 64, 0, 64, 0, 1)), (_D, 135, ("fwd", 64, 1, 64, 0, 1, 0, 0)),
-    (_D, 136, ("fwd", 200, 128, 328, 128, 128, 0, 1)), (_D, 137, ("fwd", 128, 128, 128, 0, 128, 0, 1)),
-    (_D, 138, ("fwd", 128, 128, 128, 0, 328, 0, 1)), (_D, 139, ("fwd", 328, 128, 328, 0, 128, 0, 1)),
-    (_D, 140, ("fwd", 128, 3, 128, 0, 3, 0, 0)),
+    (_D, 122, ("fwd", 96, 1, 96, 0, 10, 0, 0)), (_D, 123, ("fwd", 96, 3, 96, 0, 10, 1, 0)),
+    (_D, 124, ("fwd", 96, 3, 96, 0, 10, 4, 0)), (_D, 125, ("fwd", 96, 3, 96, 0, 10, 7, 0)),
+    (_D, 126, ("fwd", 64, 3, 96, 0, 3, 0, 0)), (_D, 127, ("fwd", 96, 128, 96, 0, 328, 128, 0)),
+    (_D, 128, ("fwd", 96, 128, 96, 0, 129, 0, 0)), (_D, 130, ("fwd", 129, 64, 129, 0, 64, 0, 1)),
+    (_D, 131, ("fwd", 64, 64, 64, 0, 64, 0, 1)), (_D, 132, ("fwd", 64, 1, 64, 0, 1, 0, 0)),
+    (_D, 133, ("fwd", 200, 128, 328, 128, 128, 0, 1)), (_D, 134, ("fwd", 128, 128, 128, 0, 128, 0, 1)),
+    (_D, 135, ("fwd", 128, 128, 128, 0, 328, 0, 1)), (_D, 136, ("fwd", 328, 128, 328, 0, 128, 0, 1)),
+    (_D, 137, ("fwd", 128, 3, 128, 0, 3, 0, 0)),
     # the input gradients
-    (_D, 143, ("dx", 128, 3, 3, 0, 128, 0, 0, 128, 128, 0)), (_D, 144, ("dx", 328, 128, 128, 0, 328, 0, 0, 128, 328, 0)),
-    (_D, 145, ("dx", 328, 128, 128, 0, 328, 0, 128, 200, None, 0)), (_D, 146, ("dx", 128, 128, 328, 0, 128, 0, 0, 128, 128, 0)),
-    (_D, 147, ("dx", 128, 128, 128, 0, 128, 0, 0, 128, 128, 0)), (_D, 148, ("dx", 200, 128, 128, 0, 328, 128, 0, 200, None, 1)),
-    (_D, 149, ("dx", 64, 1, 1, 0, 64, 0, 0, 64, 64, 0)), (_D, 150, ("dx", 64, 64, 64, 0, 64, 0, 0, 64, 64, 0)),
-    (_D, 151, ("dx", 129, 64, 64, 0, 129, 0, 0, 129, None, 0)), (_D, 153, ("dx", 96, 128, 128, 0, 96, 0, 0, 96, None, 0)),
-    (_D, 154, ("dx", 96, 1, 10, 0, 96, 0, 0, 96, None, 1)), (_D, 155, ("dx", 96, 3, 10, 1, 96, 0, 0, 96, None, 1)),
-    (_D, 156, ("dx", 96, 3, 10, 4, 96, 0, 0, 96, None, 1)), (_D, 157, ("dx", 96, 3, 10, 7, 96, 0, 0, 96, None, 1)),
-    (_D, 158, ("dx", 64, 3, 3, 0, 96, 0, 0, 64, None, 1)),
-    # the weight gradients (the lambda of line 163 at each of its calls)
-    (_D, 165, ("wgrad", 64, 3, 96, 0, 3, 0)), (_D, 166, ("wgrad", 96, 128, 96, 0, 128, 0)),
-    (_D, 167, ("wgrad", 96, 1, 96, 0, 10, 0)), (_D, 168, ("wgrad", 96, 3, 96, 0, 10, 1)),
-    (_D, 169, ("wgrad", 96, 3, 96, 0, 10, 4)), (_D, 170, ("wgrad", 96, 3, 96, 0, 10, 7)),
-    (_D, 171, ("wgrad", 129, 64, 129, 0, 64, 0)), (_D, 172, ("wgrad", 64, 64, 64, 0, 64, 0)),
-    (_D, 173, ("wgrad", 64, 1, 64, 0, 1, 0)), (_D, 174, ("wgrad", 200, 128, 328, 128, 128, 0)),
-    (_D, 175, ("wgrad", 128, 128, 128, 0, 128, 0)), (_D, 176, ("wgrad", 128, 128, 128, 0, 328, 0)),
-    (_D, 177, ("wgrad", 328, 128, 328, 0, 128, 0)), (_D, 178, ("wgrad", 128, 3, 128, 0, 3, 0)),
+    (_D, 140, ("dx", 128, 3, 3, 0, 128, 0, 0, 128, 128, 0)), (_D, 141, ("dx", 328, 128, 128, 0, 328, 0, 0, 128, 328, 0)),
+    (_D, 142, ("dx", 328, 128, 128, 0, 328, 0, 128, 200, None, 0)), (_D, 143, ("dx", 128, 128, 328, 0, 128, 0, 0, 128, 128, 0)),
+    (_D, 144, ("dx", 128, 128, 128, 0, 128, 0, 0, 128, 128, 0)), (_D, 145, ("dx", 200, 128, 128, 0, 328, 128, 0, 200, None, 1)),
+    (_D, 146, ("dx", 64, 1, 1, 0, 64, 0, 0, 64, 64, 0)), (_D, 147, ("dx", 64, 64, 64, 0, 64, 0, 0, 64, 64, 0)),
+    (_D, 148, ("dx", 129, 64, 64, 0, 129, 0, 0, 129, None, 0)), (_D, 150, ("dx", 96, 128, 128, 0, 96, 0, 0, 96, None, 0)),
+    (_D, 151, ("dx", 96, 1, 10, 0, 96, 0, 0, 96, None, 1)), (_D, 152, ("dx", 96, 3, 10, 1, 96, 0, 0, 96, None, 1)),
+    (_D, 153, ("dx", 96, 3, 10, 4, 96, 0, 0, 96, None, 1)), (_D, 154, ("dx", 96, 3, 10, 7, 96, 0, 0, 96, None, 1)),
+    (_D, 155, ("dx", 64, 3, 3, 0, 96, 0, 0, 64, None, 1)),
+    # the weight gradients (the lambda of line 160 at each of its calls)
+    (_D, 162, ("wgrad", 64, 3, 96, 0, 3, 0)), (_D, 163, ("wgrad", 96, 128, 96, 0, 128, 0)),
+    (_D, 164, ("wgrad", 96, 1, 96, 0, 10, 0)), (_D, 165, ("wgrad", 96, 3, 96, 0, 10, 1)),
+    (_D, 166, ("wgrad", 96, 3, 96, 0, 10, 4)), (_D, 167, ("wgrad", 96, 3, 96, 0, 10, 7)),
+    (_D, 168, ("wgrad", 129, 64, 129, 0, 64, 0)), (_D, 169, ("wgrad", 64, 64, 64, 0, 64, 0)),
+    (_D, 170, ("wgrad", 64, 1, 64, 0, 1, 0)), (_D, 171, ("wgrad", 200, 128, 328, 128, 128, 0)),
+    (_D, 172, ("wgrad", 128, 128, 128, 0, 128, 0)), (_D, 173, ("wgrad", 128, 128, 128, 0, 328, 0)),
+    (_D, 174, ("wgrad", 328, 128, 328, 0, 128, 0)), (_D, 175, ("wgrad", 128, 3, 128, 0, 3, 0)),
     # rc_geometry_host.inc: pred_normals_layer (no bias in the forward; d_pred offset by 3 c0)
-    (_G, 114, ("wgrad", 64, 3, 64, 0, 3, 3)), (_G, 116, ("dx", 64, 3, 3, 3, 64, 0, 0, 64, None, 0)),
+    (_G, 110, ("wgrad", 64, 3, 64, 0, 3, 3)), (_G, 112, ("dx", 64, 3, 3, 3, 64, 0, 0, 64, None, 0)),
     # rc_light_host.inc: the three layers of each loop
     (_L, 73, ("fwd", 32, 64, 32, 0, 64, 0, 1)), (_L, 73, ("fwd", 64, 64, 64, 0, 64, 0, 1)), (_L, 73, ("fwd", 64, 640, 64, 0, 640, 0, 0)),
     (_L, 99, ("wgrad", 32, 64, 32, 0, 64, 0)), (_L, 99, ("wgrad", 64, 64, 64, 0, 64, 0)), (_L, 99, ("wgrad", 64, 640, 64, 0, 640, 0)),
@@ -352,7 +352,7 @@ PRODUCTION = [
 ]
 # lines that hold a dense_* name without being a call site of their own: the two wgrad lambdas and the launch of the
 # hand-built descriptor (listed above under the line that starts it)
-NOT_CALL_SITES = {(_D, 162), (_D, 163), (_M, 76), (_M, 80), (_M, 81)}
+NOT_CALL_SITES = {(_D, 159), (_D, 160), (_M, 76), (_M, 80), (_M, 81)}
 _CALL = re.compile(r"\b(dense_(?:fwd|dx|wgrad)(?:_tile)?|wgrad|RcGemmArgs|rc_launch_gemm(?:_tile)?)\b")
 
 

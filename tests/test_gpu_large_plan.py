@@ -1,7 +1,7 @@
 """Oracle contact for the launch plans the LARGE batches run.
 
 From 24 576 rays on, the launch-per-stage plan runs a proposal level with its sampling in front as ONE launch
-(k_level_ray, csrc/rc_level.hip; the switch is in rc_api.hip enqueue_all) -- the plan the material stage's 32 768-ray
+(k_level_ray, csrc/rc_level.hip; the switch is in rc_render_host.inc stage_levels) -- the plan the material stage's 32 768-ray
 secondary trace and its bench line run.  The other GPU tests reach that plan only transitively (bitwise equal to the
 separate kernels, which equal the oracle at n <= 512).  Here the oracle itself is run on a strided subset of a batch
 large enough to take that plan (rays are independent: the oracle of a subset with the subset's random inputs is the

@@ -1,7 +1,6 @@
 """The two forms of the fused cache kernel side by side: rc_set_fused 1 (two wavefronts per ray, rc_fused2.hip) against
 3 (one wavefront per ray, rc_fused.hip) and 2 (launch-per-stage): bitwise comparison of every output on a few batch
-sizes, then the time per 1024-ray launch (64 distinct batches, HIP events).  RC_FUSED_STAGGER=<cycles> starts the second
-half of the team kernel's grid late (experiment)."""
+sizes, then the time per 1024-ray launch (64 distinct batches, HIP events)."""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R)
 import numpy as np, torch
@@ -49,4 +48,4 @@ for mode in (3, 1, 3, 1):
     for i in range(reps): rc.render_rays(B[i % 64], None, out=out)
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / reps * 1e3
-    print(f"mode {mode} ({'team, 2 waves/ray' if mode == 1 else 'one wave/ray'}): {us:8.2f} us/launch  ({n / us:.2f} M rays/s)  stagger={os.environ.get('RC_FUSED_STAGGER', '0')}", flush=True)
+    print(f"mode {mode} ({'team, 2 waves/ray' if mode == 1 else 'one wave/ray'}): {us:8.2f} us/launch  ({n / us:.2f} M rays/s)", flush=True)
