@@ -1,4 +1,4 @@
-// What the case-file drivers of the GPU tests share (tests/sample_check.hip, tests/matstage_check.hip; formats:
+// What the case-file drivers of the GPU tests share (tests/sample_check.hip, tests/matstage_check.hip, tests/transient_check.hip; formats:
 // tests/sample_ref.py).  It lives beside the Makefile so that a driver's target depends on nothing under tests/ but the
 // driver's own file.  The case file, one launch's checked view of it, and the main loop.  Every buffer is device memory of
 // its own with guard zones, canaries where the case file stores nothing.  The launches run in order on the null stream,
@@ -88,6 +88,15 @@ struct Launch {
     return dev[b] + kGuard;
   }
   const int32_t* Pi(int j, int64_t need, bool required = false) const { return reinterpret_cast<const int32_t*>(P(j, need, required)); }
+  // the same floats of slot j as the case file stores them, on the host (what a driver packs or copies into an argument
+  // struct before the launch); the slot has to be a stored buffer
+  const float* H(int j, int64_t need, bool required = false) const {
+    if (!P(j, need, required)) return nullptr;
+    const int64_t b = rec[1 + kInts + kFlts + j];
+    if (fl.buf(b)[0] < 0) die("a buffer read on the host is not stored in the case file");
+    return fl.data.data() + fl.buf(b)[0] + kGuard;
+  }
+  int64_t B(int j) const { return rec[1 + kInts + kFlts + j]; }
 };
 
 int driver_main(int argc, char** argv, int64_t magic_cases, int64_t magic_results, int64_t n_kernels, void (*run)(const Launch&)) {

@@ -211,6 +211,74 @@ inline std::vector<float> pack(const std::vector<Step>& steps, const std::vector
 }
 
 
+// ---------------------------------------------------------------------------------------------
+// The two per-bin heads of the time-resolved cache (rc_transient.hip k_transient_bins, rc_transient_slice.hip): `slf` is
+// output_rgba_layer [128 -> cols + 1], `irr` transient_indirect_layer [64 -> cols], cols = 3 n_bins histogram entries.
+// rc_transient_host.inc packs the library's weights with these; tests/transient_check.hip a case file's.
+// ---------------------------------------------------------------------------------------------
+// k_transient_bins' stream: per column tile of 32 entries [slf (128 + bias) | irr (64 + bias)], every tile padded with zeros
+// to `frags_per_tile` fragments (whole chunks of the kernel's LDS ring).  Split form (tile_xw2_split): the pieces of the SLF
+// head's 9 blocks, then of the irradiance head's 5.  fp32 form (tile_xw2's consumption order): 16 groups of [SLF head 4
+// steps | irradiance head 2 steps], then the two bias steps.
+inline std::vector<float> pack_bins_stream(const HostLayer& slf, const HostLayer& irr, int cols, int frags_per_tile,
+                                           bool split = kRcSplit) {
+  std::vector<float> stream;
+  std::vector<Step> s4, s2;
+  steps_acc(s4, 4, 0); step_bias(s4);
+  steps_acc(s2, 2, 0); step_bias(s2);
+  const int tiles = (cols + 31) / 32;
+  const size_t tile_floats = (size_t)frags_per_tile * 64;
+  auto append = [&](const std::vector<float>& b) { stream.insert(stream.end(), b.begin(), b.end()); };
+  for (int t = 0; t < tiles; ++t) {
+    if (split) {
+      append(pack_split(s4, {tile_full(&slf, t)}));
+      append(pack_split(s2, {tile_full(&irr, t)}));
+    } else {
+      const std::vector<float> pa = pack_f32(s4, {tile_full(&slf, t)}), pb = pack_f32(s2, {tile_full(&irr, t)});
+      auto frag = [&](const std::vector<float>& p, int i) { stream.insert(stream.end(), p.begin() + (size_t)i * 64, p.begin() + (size_t)(i + 1) * 64); };
+      for (int g = 0; g < 16; ++g) {
+        for (int q = 0; q < 4; ++q) frag(pa, 4 * g + q);
+        for (int q = 0; q < 2; ++q) frag(pb, 2 * g + q);
+      }
+      frag(pa, 64); frag(pb, 32);
+    }
+    stream.resize((size_t)(t + 1) * tile_floats, 0.0f);
+  }
+  return stream;
+}
+
+// k_transient_slice's plain columns of one head (`ntiles` accumulator tiles of inputs: 4 for slf, 2 for irr).  The
+// activations k_transient_shader stores are in MFMA operand order -- value 2 k + h of a sample is half h of step k -- so the
+// columns are built from the same step tables: row j of a column is the weight that meets value j, then the bias.
+inline std::vector<float> pack_slice_columns(const HostLayer& L, int ntiles, int cols, int stride) {
+  std::vector<Step> st;
+  steps_acc(st, ntiles, 0); step_bias(st);
+  std::vector<float> v((size_t)cols * stride, 0.0f);
+  for (int col = 0; col < cols; ++col)
+    for (size_t k = 0; k < st.size(); ++k)
+      for (int hh = 0; hh < 2; ++hh)
+        if ((int)(2 * k + hh) < stride) v[(size_t)col * stride + 2 * k + hh] = pack_value(st[k], hh, Col{&L, col, 0, true});
+  return v;
+}
+
+// temporal filter of the direct part (render.py:411-413): taps -round(4 sigma) .. round(4 sigma), exp(-k^2 / 2 sigma^2) -
+// exp(-8), normalised; none for sigma = 0
+inline std::vector<float> temporal_taps(float sigma) {
+  std::vector<float> taps;
+  if (sigma != 0.0f) {
+    const int half = (int)lround(4.0 * sigma);
+    float sum = 0.0f;
+    for (int k = -half; k <= half; ++k) {
+      const float kk = (float)k;
+      const float v = expf(-(kk * kk) / (2.0f * sigma * sigma)) - (float)exp(-8.0);
+      taps.push_back(v);
+      sum += v;
+    }
+    for (float& v : taps) v = v / sum;
+  }
+  return taps;
+}
+
 // A linear layer `b` (no activation) folded into the layer L that consumes it: rows [row0, row0 + b.out) of L take b's
 // output, the following `extra_rows` rows are kept as they are.  W' = W_b W[rows], b' = b_b W[rows] (fp64 products,
 // rounded once); L's own bias is added where the result is packed.

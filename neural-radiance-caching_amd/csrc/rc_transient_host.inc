@@ -98,73 +98,26 @@ int repack_transient(rc_handle* h) {
     if (rc) return rc;
   }
   {
-    // k_transient_bins: per column tile of 32 histogram entries [output_rgba_layer (128 + bias) | transient_indirect_layer (64 + bias)]
-    std::vector<float> stream;
-    std::vector<Step> s4, s2;
-    steps_acc(s4, 4, 0); step_bias(s4);
-    steps_acc(s2, 2, 0); step_bias(s2);
-    const int tiles = (3 * h->tcfg.n_bins + 31) / 32;
-    // every tile is padded to whole chunks of the kernel's LDS ring (two; three in the split form: its seams then sit at fixed fragments of a tile)
-    const size_t tile_floats = (size_t)rc_transient_bins_frags() / tiles * 64;
-    for (int t = 0; t < tiles; ++t) {
-      // consumption order of tile_xw2 (rc_transient.hip): 16 groups of [SLF head 4 steps | irradiance head 2 steps],
-      // then the two bias steps
-      if (kRcSplit) {
-        // split form (tile_xw2_split): the pieces of the SLF head's 9 blocks, then of the irradiance head's 5
-        append(stream, pack_split(s4, {tile_full(lo, t)}));
-        append(stream, pack_split(s2, {tile_full(ro, t)}));
-      } else {
-        const std::vector<float> pa = pack_f32(s4, {tile_full(lo, t)}), pb = pack_f32(s2, {tile_full(ro, t)});
-        auto frag = [&](const std::vector<float>& p, int i) { stream.insert(stream.end(), p.begin() + (size_t)i * 64, p.begin() + (size_t)(i + 1) * 64); };
-        for (int g = 0; g < 16; ++g) {
-          for (int q = 0; q < 4; ++q) frag(pa, 4 * g + q);
-          for (int q = 0; q < 2; ++q) frag(pb, 2 * g + q);
-        }
-        frag(pa, 64); frag(pb, 32);
-      }
-      stream.resize((size_t)(t + 1) * tile_floats, 0.0f);
-    }
+    // k_transient_bins: per column tile of 32 histogram entries [output_rgba_layer (128 + bias) | transient_indirect_layer (64 + bias)],
+    // every tile padded to whole chunks of the kernel's LDS ring (rc_pack_host.h pack_bins_stream)
+    const int cols = 3 * h->tcfg.n_bins, tiles = (cols + 31) / 32;
+    const std::vector<float> stream = pack_bins_stream(*lo, *ro, cols, rc_transient_bins_frags() / tiles);
     if ((int)(stream.size() / 64) != rc_transient_bins_frags())
       return fail(h, RC_ERR_INVALID_ARG, "internal: transient bins stream length mismatch");
     int rc = upload(h, h->packs.t_bins, pad_stream(stream));
     if (rc) return rc;
   }
   {
-    // k_transient_slice (rc_transient_slice.hip): the same two heads as plain columns.  The activations k_transient_shader
-    // stores are in MFMA operand order -- value 2 k + h of a sample is half h of step k -- so the columns are built from
-    // the same step tables: row j of a column is the weight that meets value j, then the bias.
-    std::vector<Step> s4, s2;
-    steps_acc(s4, 4, 0); step_bias(s4);
-    steps_acc(s2, 2, 0); step_bias(s2);
+    // k_transient_slice (rc_transient_slice.hip): the same two heads as plain columns (rc_pack_host.h pack_slice_columns)
     const int cols = 3 * h->tcfg.n_bins;
-    auto plain = [&](const HostLayer* L, const std::vector<Step>& st, int stride) {
-      std::vector<float> v((size_t)cols * stride, 0.0f);
-      for (int col = 0; col < cols; ++col)
-        for (size_t k = 0; k < st.size(); ++k)
-          for (int hh = 0; hh < 2; ++hh)
-            if ((int)(2 * k + hh) < stride) v[(size_t)col * stride + 2 * k + hh] = pack_value(st[k], hh, Col{L, col, 0, true});
-      return v;
-    };
     static_assert(kRcSliceStrideSlf >= 2 * 64 + 1 && kRcSliceStrideIrr >= 2 * 32 + 1, "a column holds every row and the bias");
-    int rc = upload(h, h->packs.t_slice_slf, plain(lo, s4, kRcSliceStrideSlf));
+    int rc = upload(h, h->packs.t_slice_slf, pack_slice_columns(*lo, 4, cols, kRcSliceStrideSlf));
     if (rc) return rc;
-    if ((rc = upload(h, h->packs.t_slice_irr, plain(ro, s2, kRcSliceStrideIrr)))) return rc;
+    if ((rc = upload(h, h->packs.t_slice_irr, pack_slice_columns(*ro, 2, cols, kRcSliceStrideIrr)))) return rc;
   }
   {
-    // temporal filter (render.py:411-413): taps -round(4 sigma) .. round(4 sigma), exp(-k^2 / 2 sigma^2) - exp(-8), normalised
-    std::vector<float> taps;
-    const float sigma = h->tcfg.tfilter_sigma;
-    if (sigma != 0.0f) {
-      const int half = (int)lround(4.0 * sigma);
-      float sum = 0.0f;
-      for (int k = -half; k <= half; ++k) {
-        const float kk = (float)k;
-        const float v = expf(-(kk * kk) / (2.0f * sigma * sigma)) - (float)exp(-8.0);
-        taps.push_back(v);
-        sum += v;
-      }
-      for (float& v : taps) v = v / sum;
-    }
+    // temporal filter (render.py:411-413, rc_pack_host.h temporal_taps)
+    const std::vector<float> taps = temporal_taps(h->tcfg.tfilter_sigma);
     h->n_taps = (int)taps.size();
     if (h->n_taps) {
       int rc = upload(h, h->packs.t_taps, taps);

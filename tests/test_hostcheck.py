@@ -89,6 +89,26 @@ def hostcheck(tmp_path_factory):
     return d, layers, grid
 
 
+@pytest.fixture(scope="module")
+def tbins(tmp_path_factory):
+    """`hostcheck --tbins`: the two per-bin head layers of the time-resolved cache through the three packing functions."""
+    r = subprocess.run(["make", "-C", CSRC, "hostcheck"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    d = tmp_path_factory.mktemp("hostcheck_tbins")
+    rng = np.random.default_rng(12)
+    layers = {}
+    for name, (i, o) in dict(slf=(128, 71), irr=(64, 70)).items():
+        k = rng.normal(size=(i, o)).astype(np.float32)
+        b = rng.normal(size=(o,)).astype(np.float32)
+        k.tofile(d / f"in_{name}_kernel.bin")
+        b.tofile(d / f"in_{name}_bias.bin")
+        layers[name] = (k, b)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([os.path.join(CSRC, "hostcheck"), "--tbins", str(d)], capture_output=True, text=True, env=env)
+    assert r.returncode == 0 and "hostcheck tbins ok" in r.stdout, r.stdout + r.stderr       # non-zero: a sanitizer report
+    return d, layers
+
+
 def _out(d, name):
     return np.fromfile(d / f"out_{name}.bin", dtype=np.float32)
 
@@ -108,6 +128,85 @@ def test_fragment_packing_matches_numpy(hostcheck):
             tile[i] = ("c", r, True)
     want = np_pack(natural(9) + [(-2, -1)], [tile], layers)
     assert np.array_equal(unsplit(_out(d, "by_reg"), 6, 1), want)
+
+
+def _head_tiles(layers, t):
+    """[step][lane] float32 of column tile t of the two per-bin heads: slf over 4 accumulator tiles + bias, irr over 2."""
+    s4 = [(acc_feat(q, r, 0), acc_feat(q, r, 1)) for q in range(4) for r in range(16)] + [(-2, -1)]
+    s2 = [(acc_feat(q, r, 0), acc_feat(q, r, 1)) for q in range(2) for r in range(16)] + [(-2, -1)]
+    pa = np_pack(s4, [full_tile("slf", t, 71)], layers).reshape(65, 64)
+    pb = np_pack(s2, [full_tile("irr", t, 70)], layers).reshape(33, 64)
+    return pa, pb
+
+
+def test_transient_bins_stream_matches_numpy(tbins):
+    """rc_pack_host.h pack_bins_stream, what repack_transient uploads for k_transient_bins, in both forms: per column tile
+    [slf | irr], zero fragments up to the tile's whole chunks.  cols = 70 is no multiple of 32: the last tile's entries
+    71..95 are zero columns; entry 70 holds slf's column 70 (the alpha of output_rgba_layer, entry 2100 of the library's
+    stream, which k_transient_bins never stores) and a zero irr column."""
+    d, layers = tbins
+    split = _out(d, "tbins_split").reshape(3, 192 * 64)
+    f32 = _out(d, "tbins_f32").reshape(3, 128, 64)
+    for t in range(3):
+        pa, pb = _head_tiles(layers, t)
+        # split form: 9 blocks of the slf head (108 fragments), 5 of the irr head (60), zeros behind
+        assert np.array_equal(unsplit(split[t, :108 * 64], 65, 1).reshape(65, 64), pa)
+        assert np.array_equal(unsplit(split[t, 108 * 64:168 * 64], 33, 1).reshape(33, 64), pb)
+        assert not split[t, 168 * 64:].view(np.uint32).any()
+        # fp32 form: 16 groups of [slf 4 g .. 4 g + 3 | irr 2 g, 2 g + 1], then [slf 64 | irr 32], zeros behind
+        want = []
+        for g in range(16):
+            want += [pa[4 * g + q] for q in range(4)] + [pb[2 * g + q] for q in range(2)]
+        want += [pa[64], pb[32]]
+        assert np.array_equal(f32[t, :98].view(np.uint32), np.asarray(want, np.float32).view(np.uint32))
+        assert not f32[t, 98:].view(np.uint32).any()
+    pa, pb = _head_tiles(layers, 2)
+    assert not pa[:, [l for l in range(64) if (l & 31) >= 7]].any() and pa[:, :7].all()
+    assert not pb[:, [l for l in range(64) if (l & 31) >= 6]].any() and pb[:, :6].all()
+
+
+def test_transient_slice_columns_match_numpy(tbins):
+    """pack_slice_columns: column f of a head is `stride` floats, value j = 2 step + half of the accumulator-order steps
+    (feature acc_feat(j // 32, (j // 2) % 16, j & 1)), the bias at 2 x steps, zeros behind."""
+    d, layers = tbins
+    for name, ntiles, stride in (("slf", 4, 132), ("irr", 2, 68)):
+        k, b = layers[name]
+        got = _out(d, "tslice_" + name).reshape(70, stride)
+        K = 32 * ntiles
+        rows = [acc_feat(j // 32, (j // 2) % 16, j & 1) for j in range(K)]
+        assert sorted(rows) == list(range(K))
+        want = np.zeros((70, stride), np.float32)
+        want[:, :K] = k[rows, :70].T
+        want[:, K] = b[:70]
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_temporal_taps_match_numpy(tbins):
+    """temporal_taps (render.py:406-408): float32 arithmetic step by step, the sum in tap order; bit for bit."""
+    d, _ = tbins
+    v = _out(d, "ttaps")
+    at = 0
+    for sigma, count in ((3.0, 25), (4.0, 33), (0.7, 7), (0.0, 0)):
+        assert int(v[at]) == count
+        got = v[at + 1:at + 1 + count]
+        at += 1 + count
+        if not count:
+            continue
+        half = (count - 1) // 2
+        assert half == int(np.floor(4.0 * sigma + 0.5))
+        kk = np.arange(-half, half + 1).astype(np.float32)
+        sg = np.float32(sigma)
+        arg = -(kk * kk) / (np.float32(2.0) * sg * sg)
+        e64 = np.exp(arg.astype(np.float64))
+        raw = e64.astype(np.float32) - np.float32(np.exp(-8.0))
+        tot = np.float32(0.0)
+        for x in raw:
+            tot = np.float32(tot + x)
+        want = raw / tot
+        # (expf returns the float nearest to the exact value at these 33 arguments: the fp64 exp, rounded once)
+        assert np.array_equal(got.view(np.uint32), want.astype(np.float32).view(np.uint32))
+        assert np.array_equal(got, got[::-1]) and abs(float(got.astype(np.float64).sum()) - 1.0) < count * 2.0 ** -24
+    assert at == v.size
 
 
 def test_dot_fragments_match_numpy(hostcheck):
