@@ -1,12 +1,37 @@
 // ---------------------------------------------------------------------------------------------------------
-// rc_cast_rays_multi / rc_train_batch: rays of mixed cameras and the training batch of one step (rc_batch.hip)
+// rc_cast_rays / rc_cast_rays_multi / rc_train_batch: rays of one camera (rc_camera.hip), of mixed cameras and the
+// training batch of one step (rc_batch.hip)
 // ---------------------------------------------------------------------------------------------------------
-// Argument errors of these two calls are reported before the handle is looked at, into the handle's message or, without
+// Argument errors of rc_cast_rays_multi and rc_train_batch are reported before the handle is looked at, into the handle's message or, without
 // one, into the message rc_last_error(NULL) returns: a host can check a call's shape on a machine without a GPU.
 static int batch_fail(rc_handle* h, const std::string& msg) {
   if (h) return fail(h, RC_ERR_INVALID_ARG, msg);
   g_create_error = msg;
   return RC_ERR_INVALID_ARG;
+}
+
+static RcCastOut cast_out(const rc_cast_outputs* out) {
+  RcCastOut o{};
+  o.origins = out->origins; o.directions = out->directions; o.viewdirs = out->viewdirs; o.radii = out->radii;
+  o.imageplane = out->imageplane; o.look = out->look; o.up = out->up; o.lights = out->lights; o.near = out->near; o.far = out->far;
+  return o;
+}
+
+// The fields rc_camera and rc_camera_set share, into the kernels' form; -> what is wrong with them, or NULL
+template <class Cam>
+static const char* cast_shared(const Cam* cam, RcCastShared& s) {
+  if (cam->camtype < 0 || cam->camtype > 3)
+    return "camtype must be 0 (perspective), 1 (panoramic), 2 (fisheye) or 3 (fisheye, equisolid)";
+  s.near_v = cam->near; s.far_v = cam->far; s.camtype = cam->camtype;
+  s.has_distortion = cam->has_distortion != 0;
+  for (int i = 0; i < 6; ++i) s.dist[i] = cam->distortion[i];
+  s.has_ndc = cam->has_ndc != 0;
+  if (s.has_ndc) {          // convert_to_ndc: xmult = 1 / pixtocam[0, 2], ymult = 1 / pixtocam[1, 2] (camera_utils.py:97-98)
+    if (cam->pixtocam_ndc[2] == 0.0f || cam->pixtocam_ndc[5] == 0.0f) return "pixtocam_ndc[0][2] and [1][2] must be non-zero";
+    s.ndc_xmult = 1.0f / cam->pixtocam_ndc[2]; s.ndc_ymult = 1.0f / cam->pixtocam_ndc[5];
+  }
+  s.has_z_range = cam->has_z_range != 0; s.z_lo = cam->z_range[0]; s.z_hi = cam->z_range[1];
+  return nullptr;
 }
 
 static const char* camera_tables(const rc_camera_set* set, RcCameraTables& t, RcCastShared& s) {
@@ -70,6 +95,38 @@ int rc_train_batch(rc_handle* h, const rc_camera_set* set, const void* images, i
   a.out = cast_out(&out->rays);
   a.rgb = out->rgb; a.lossmult = out->lossmult; a.cam_idx = out->cam_idx; a.pix_x = out->pix_x; a.pix_y = out->pix_y;
   rc_launch_train_batch(a, (hipStream_t)stream_v);
+  RC_HIP(h, hipGetLastError());
+  return RC_OK;
+  RC_CATCH(h)
+}
+
+int rc_cast_rays(rc_handle* h, const rc_camera* cam, const int32_t* pix_x, const int32_t* pix_y, int64_t n,
+                 int32_t x0, int32_t y0, int32_t width, int32_t height, const rc_cast_outputs* out, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  if (!cam || !out) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: null camera/outputs");
+  if ((pix_x == nullptr) != (pix_y == nullptr)) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: pix_x and pix_y go together");
+  if (!pix_x) {
+    if (width <= 0 || height <= 0) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: empty pixel rectangle");
+    if (n != (int64_t)width * height) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: n must equal width * height");
+  }
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: negative n");
+  if (n == 0) return RC_OK;
+  RC_HIP(h, hipSetDevice(h->device));
+  RcCastArgs a{};
+  a.n = n; a.pix_x = pix_x; a.pix_y = pix_y; a.x0 = x0; a.y0 = y0; a.width = width > 0 ? width : 1;
+  for (int i = 0; i < 9; ++i) a.pixtocam[i] = cam->pixtocam[i];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.rot[3 * r + c] = cam->camtoworld[4 * r + c];
+    a.trans[r] = cam->camtoworld[4 * r + 3];
+    a.light[r] = cam->light[r];
+  }
+  if (const char* bad = cast_shared(cam, a.s))
+    return fail(h, cam->camtype < 0 || cam->camtype > 3 ? RC_ERR_UNSUPPORTED : RC_ERR_INVALID_ARG, std::string("rc_cast_rays: ") + bad);
+  if ((cam->pix_dx == nullptr) != (cam->pix_dy == nullptr)) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: pix_dx and pix_dy go together");
+  a.pix_dx = cam->pix_dx; a.pix_dy = cam->pix_dy;
+  a.out = cast_out(out);
+  rc_launch_cast_rays(a, (hipStream_t)stream_v);
   RC_HIP(h, hipGetLastError());
   return RC_OK;
   RC_CATCH(h)

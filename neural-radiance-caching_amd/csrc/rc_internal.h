@@ -337,6 +337,22 @@ void rc_launch_build_cells(const float* src, int N, int F, float* dst, int dst_s
 // per-sample channels written by k_transient_shader ([RC_TS_COUNT][n], channel-major)
 enum { RC_TS_DD = 0, RC_TS_DS = 3, RC_TS_ALBEDO = 6, RC_TS_TIB = 9, RC_TS_ROUGH = 12, RC_TS_NDOTL = 13, RC_TS_IRRAD = 14,
        RC_TS_OCC = 15, RC_TS_LDIST = 16, RC_TS_RDIST = 17, RC_TS_CAMDIST = 18, RC_TS_COUNT = 19 };
+constexpr int kRcTdBins = 700, kRcTdHist = 3 * kRcTdBins;      // histogram entries of a ray: entry = 3 bin + channel
+
+// What the integrator's kernels (k_transient_bins, k_transient_slice, k_transient_bins_bwd) read alike: the shader's
+// per-sample buffers and the integrator's settings (rc_dev_transient.h; filled by transient_in, rc_transient_host.inc).
+// The kernels' argument structs take it, and RcTransTaps, as a base: the fields keep their names in every struct.
+struct RcTransIn {
+  int64_t n_rays;
+  const float* slf_feat; const float* irr_feat; const float* tshade; const float* weights;   // weights [n_rays][32]
+  float exposure, shift, max_dists, irradiance_bias, slf_rgb_bias, indirect_scale, rgb_max, light_near;
+  int32_t bin_zero_threshold_light, light_zero;
+};
+// the temporal filter of the direct part
+struct RcTransTaps {
+  int32_t n_taps;
+  const float* taps;                       // device, n_taps entries
+};
 
 struct RcTransShaderArgs {
   int64_t n; int32_t samples_per_ray;
@@ -352,14 +368,9 @@ struct RcTransShaderArgs {
   float* tshade;                           // [RC_TS_COUNT][n]
 };
 
-struct RcTransBinsArgs {
-  int64_t n_rays;
+struct RcTransBinsArgs : RcTransIn, RcTransTaps {
   unsigned long long* stamps;              // diagnostic builds (-DRC_STAMPS) only
   const float* wstream;                    // per column tile: 65 SLF output fragments | 33 transient_indirect fragments
-  const float* slf_feat; const float* irr_feat; const float* tshade; const float* weights;   // weights [n_rays][32]
-  float exposure, shift, max_dists, irradiance_bias, slf_rgb_bias, indirect_scale, rgb_max, light_near;
-  int32_t bin_zero_threshold_light, light_zero, n_taps;
-  const float* taps;                       // temporal filter (device), n_taps entries
   float* out_rgb; float* out_direct; float* out_indirect;               // [n_rays][700][3]
   float* out_ti_diffuse; float* out_ti_specular;                         // unshifted composites [n_rays][700][3]
   float* out_direct_rgb; float* out_indirect_rgb; float* out_integrated_rgb;
@@ -387,13 +398,8 @@ void rc_launch_transient_bins(const RcTransBinsArgs& a, hipStream_t stream);
 constexpr int kRcSliceMax = RC_TSLICE_MAX;
 constexpr int kRcSliceStrideSlf = 132;     // 128 rows + bias, padded to whole float4
 constexpr int kRcSliceStrideIrr = 68;      // 64 rows + bias, padded
-struct RcTransSliceArgs {
-  int64_t n_rays;
+struct RcTransSliceArgs : RcTransIn, RcTransTaps {
   const float* w_slf; const float* w_irr;  // [2100][kRcSliceStrideSlf], [2100][kRcSliceStrideIrr]
-  const float* slf_feat; const float* irr_feat; const float* tshade; const float* weights;   // as RcTransBinsArgs
-  float exposure, shift, max_dists, irradiance_bias, slf_rgb_bias, indirect_scale, rgb_max, light_near;
-  int32_t bin_zero_threshold_light, light_zero, n_taps;
-  const float* taps;
   int32_t count;                           // 1 .. kRcSliceMax
   float t[kRcSliceMax];                    // fractional bin index, 0 <= t <= 699
   float* out_rgb; float* out_direct; float* out_indirect;                // [n_rays][count][3], NULL = not wanted
@@ -703,11 +709,10 @@ void rc_launch_envmap_out_bwd(const float* d_env, const float* raw, float rgb_bi
 void rc_launch_gemm_tile(const RcGemmArgs& a, int kparts, hipStream_t st);
 
 // The time-resolved cache's data loss and the backward of k_transient_bins (rc_transient_bwd.hip)
-constexpr int kRcTdBins = 700, kRcTdHist = 3 * kRcTdBins;      // histogram entries of a ray: entry = 3 bin + channel
 constexpr int kRcTdLdSlf = kRcTdHist + 4;                      // row stride of dZ_slf: the alpha column and 3 pad floats, zeros
 constexpr int kRcTdChunkRays = 256;                            // rays whose dZ the workspace holds at a time
-struct RcTransLossArgs {
-  int64_t n; int32_t n_taps; const float* taps;            // rays; the temporal filter of the direct part (device)
+struct RcTransLossArgs : RcTransTaps {
+  int64_t n;                                               // rays
   const float* rgb, * gt;                                  // [n][700][3]
   const float* rgb_nocorr, * gt_nocorr;                    // [n][700][3] or nullptr (rgb, gt)
   const float* lossmult;                                   // [n] or nullptr (1)
@@ -718,12 +723,9 @@ struct RcTransLossArgs {
   float* G, * Gt;                                          // [n][700][3] d loss / d rgb and the filter's transpose of it, written
   float* loss_ray;                                         // [2][n] per-ray sums of the loss terms and of lossmult (rgb - gt)^2
 };
-struct RcTransBinsBwdArgs {
-  int64_t n_rays, r0, C;                                   // the batch; this launch's rays [r0, r0 + C)
-  const float* slf_feat, * irr_feat, * tshade, * weights;  // the forward's buffers (RcTransBinsArgs)
+struct RcTransBinsBwdArgs : RcTransIn {                   // the batch: the forward's buffers and settings
+  int64_t r0, C;                                           // this launch's rays [r0, r0 + C)
   const float* w_slf, * b_slf, * w_irr, * b_irr;           // output_rgba_layer [128][2101], [2101]; transient_indirect_layer [64][2100], [2100]
-  float exposure, shift, max_dists, irradiance_bias, slf_rgb_bias, indirect_scale, rgb_max, light_near;
-  int32_t bin_zero_threshold_light, light_zero;
   const float* G, * Gt;                                    // [n_rays][2100]
   float* dz_irr, * dz_slf;                                 // [C 32][2100], [C 32][kRcTdLdSlf] written (zeros outside the live tiles)
   float* x_irr, * x_slf;                                   // [C 32][64], [C 32][128] the heads' inputs, reference column order, written

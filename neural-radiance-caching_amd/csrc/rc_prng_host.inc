@@ -55,3 +55,26 @@ int rc_prng_fill_segments(rc_handle* h, const rc_prng_segment* segs, int32_t n_s
   return RC_OK;
   RC_CATCH(h)
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// rc_prng_fill: jax.random-compatible random tensors generated in HBM (../prng.py is the host twin)
+// ---------------------------------------------------------------------------------------------------------
+int rc_prng_fill(rc_handle* h, const uint32_t key[2], int32_t mode, float minval, float maxval, int64_t n, void* out,
+                 void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  if (!key || (!out && n > 0)) return fail(h, RC_ERR_INVALID_ARG, "rc_prng_fill: null key/output");
+  if (mode < RC_PRNG_BITS || mode > RC_PRNG_GUMBEL) return fail(h, RC_ERR_INVALID_ARG, "rc_prng_fill: unknown mode");
+  if (n < 0 || n >= 0xFFFFFFFFll) return fail(h, RC_ERR_INVALID_ARG, "rc_prng_fill: n must be in [0, 2^32 - 1)");
+  if (n == 0) return RC_OK;
+  RC_HIP(h, hipSetDevice(h->device));
+  RcPrngArgs a{};
+  a.key0 = key[0]; a.key1 = key[1]; a.mode = mode; a.n = n; a.out = (uint32_t*)out;
+  // jax.random.normal / gumbel fix their own range: (nextafter(-1, 0), 1) and (tiny, 1)
+  a.lo = mode == RC_PRNG_NORMAL ? -0.99999994f : (mode == RC_PRNG_GUMBEL ? 1.17549435e-38f : minval);
+  a.hi = (mode == RC_PRNG_NORMAL || mode == RC_PRNG_GUMBEL) ? 1.0f : maxval;
+  rc_launch_prng_fill(a, (hipStream_t)stream_v);
+  RC_HIP(h, hipGetLastError());
+  return RC_OK;
+  RC_CATCH(h)
+}

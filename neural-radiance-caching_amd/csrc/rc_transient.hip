@@ -17,6 +17,7 @@
 // histogram in LDS and into the unshifted per-bin composites.
 #include "rc_dev_mlp.h"
 #include "rc_dev_sample.h"
+#include "rc_dev_transient.h"
 
 using namespace rcdev;
 
@@ -305,8 +306,6 @@ __global__ void k_shadow_rays(RcShadowRayArgs a) {
 // ---------------------------------------------------------------------------------------------
 // per-bin heads + compositing: one wavefront per ray
 // ---------------------------------------------------------------------------------------------
-constexpr int kBins = 700;
-constexpr int kHist = kBins * 3;                 // 2100 histogram entries per ray, entry = bin * 3 + channel
 constexpr int kTilesB = (kHist + 31) / 32;       // 66 column tiles
 constexpr int kTileFrags = 65 + 33;              // SLF output layer (128 + bias) | transient_indirect_layer (64 + bias)
 // split form (rc_pack_host.h): 9 + 5 blocks of 8 k-steps x 3 pieces x 4 fragments = 168 fragments per tile
@@ -319,20 +318,8 @@ static_assert(kTileFrags <= kFragsPerTile, "a tile's fragments fit its two chunk
 constexpr int kBinFrags = kTilesB * kFragsPerTile;
 constexpr int kSP = 10;                          // per-sample parameters kept in LDS
 constexpr int kHistPad = kHist + 32;             // + one dummy slot per lane (out-of-range targets read-add-write there)
-constexpr int kMaxTaps = 32;                     // temporal filter taps handled by the unrolled window
-constexpr int kPadD = 3 * (kMaxTaps / 2);        // zeros on both sides of the direct histogram: the filter window needs no range test
 constexpr int kWaveLds = 2 * kHistPad + (kHist + 2 * kPadD) + kSP * 32 + 6 * 32;   // floats: indirect hist (one per half-wave), padded direct hist, params, bin sums
 
-// softplus on the hardware transcendentals (v_exp_f32 / v_log_f32, about 1 ulp each): the per-bin heads evaluate
-// 2 x 2100 of them per sample, which is what bounds k_transient_bins.  log1p(e) for small e by its series.
-// The per-bin heads' form: max(x, 0) + log(1 + exp(-|x|)) on the two hardware transcendentals, WITHOUT the series branch
-// for tiny exp(-|x|).  1 + e rounds e away below 6e-8 and carries an absolute error of <= 6e-8 below 1e-3: 4e-8 on a
-// softplus that is then scaled by indirect_scale (0.05) into per-bin radiance compared at 2e-6 -- three orders of
-// magnitude inside the budget, for 4 vector instructions less per evaluation (2 x 16 x 2100 evaluations per ray).
-__device__ __forceinline__ float softplus_bins(float x) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(x) * 1.44269504088896341f);
-  return fmaxf(x, 0.0f) + __builtin_amdgcn_logf(1.0f + e) * 0.693147180559945309f;
-}
 __device__ __forceinline__ float softplus_hw(float x) {
   // straight-line: v_exp_f32 / v_log_f32 are base 2; both forms of log1p are evaluated and selected
   const float e = __builtin_amdgcn_exp2f(-fabsf(x) * 1.44269504088896341f);
@@ -461,40 +448,20 @@ __global__ __launch_bounds__(kWaves * 64) void k_transient_bins(RcTransBinsArgs 
   int win_lo = kBins, win_hi = -1;
   if (lane < 32) {
     const int64_t p = ray * 32 + lane;
-    // the eight per-sample inputs in one batch of loads (as "LDS slot = load" they were eight dependent round trips: the
-    // loads were not moved over the LDS stores between them)
-    const float ld = a.tshade[RC_TS_LDIST * n + p], in_w = a.weights[p], in_cam = a.tshade[RC_TS_CAMDIST * n + p];
-    const float in_t0 = a.tshade[(RC_TS_TIB + 0) * n + p], in_t1 = a.tshade[(RC_TS_TIB + 1) * n + p],
-                in_t2 = a.tshade[(RC_TS_TIB + 2) * n + p], in_rd = a.tshade[RC_TS_RDIST * n + p];
-    sp[P_W * 32 + lane] = in_w;
-    sp[P_LDIST * 32 + lane] = ld;
-    sp[P_CAMDIST * 32 + lane] = in_cam;
-    sp[P_TIB0 * 32 + lane] = in_t0;
-    sp[P_TIB1 * 32 + lane] = in_t1;
-    sp[P_TIB2 * 32 + lane] = in_t2;
-    // bins_move / exposure_time (render.py:483): ray_dist + shift, divided by the exposure
-    sp[P_DIND * 32 + lane] = (in_rd + a.shift) / a.exposure;
-    const bool kill = a.light_zero && ld < a.light_near;                               // render_utils.py:1750-1760
-    sp[P_KILL * 32 + lane] = kill ? 1.0f : 0.0f;
-    // Window of bins that survive zero_invalid_bins (render_utils.py:1699-1767), once per sample (lane = sample).
-    // Both travel-time tests are monotone in the bin index, so each is a bound: bins >= lo pass
-    // "(b + thr) * e < light_dist" (too close), bins <= hi pass "b * e + cam_dist > max_dists" (too far); the bounds
-    // are settled with the very comparisons of the reference.
-    const float cdist = in_cam;
-    auto close = [&](int b) { return (float)(b + a.bin_zero_threshold_light) * a.exposure < ld; };
-    auto far = [&](int b) { return ((float)b * a.exposure + cdist) > a.max_dists; };
-    int lo = (int)ceilf(ld / a.exposure) - a.bin_zero_threshold_light;
-    lo = min(max(lo, 0), kBins);
-    while (lo > 0 && !close(lo - 1)) --lo;
-    while (lo < kBins && close(lo)) ++lo;
-    int hi = (int)floorf((a.max_dists - cdist) / a.exposure);
-    hi = min(max(hi, -1), kBins - 1);
-    while (hi < kBins - 1 && !far(hi + 1)) ++hi;
-    while (hi >= 0 && far(hi)) --hi;
-    if (kill) { lo = kBins; hi = -1; }
-    sp[P_LO * 32 + lane] = __int_as_float(lo);
-    sp[P_HI * 32 + lane] = __int_as_float(hi);
-    if (lo <= hi) { win_lo = lo; win_hi = hi; }
+    const TdSample in = td_sample(a, n, p);
+    sp[P_W * 32 + lane] = in.w;
+    sp[P_LDIST * 32 + lane] = in.ld;
+    sp[P_CAMDIST * 32 + lane] = in.cdist;
+    sp[P_TIB0 * 32 + lane] = in.tib[0];
+    sp[P_TIB1 * 32 + lane] = in.tib[1];
+    sp[P_TIB2 * 32 + lane] = in.tib[2];
+    sp[P_DIND * 32 + lane] = in.d_ind;
+    // the window of bins zero_invalid_bins keeps, once per sample (lane = sample)
+    const TdWindow win = td_window(a, in.ld, in.cdist);
+    sp[P_KILL * 32 + lane] = win.kill ? 1.0f : 0.0f;
+    sp[P_LO * 32 + lane] = __int_as_float(win.lo);
+    sp[P_HI * 32 + lane] = __int_as_float(win.hi);
+    if (win.lo <= win.hi) { win_lo = win.lo; win_hi = win.hi; }
   }
   // Column tiles outside [first, last] bin that ANY sample of the workgroup's rays keeps hold exact zeros on every lane
   // (diff = spec = 0 there): their 98 MFMAs and their epilogue are not run, the weight stream starts at the first tile
@@ -627,24 +594,20 @@ __global__ __launch_bounds__(kWaves * 64) void k_transient_bins(RcTransBinsArgs 
         const float old = *slot;
 #endif
         const float tib = sp[tib_off + (r & 3) + 8 * (r >> 2)];
-        // nerf.py:1795-1797 and :1712-1719: softplus(. + irradiance_bias) * indirect_scale;
-        // surface_light_field.py:1037-1058 and nerf.py:1721-1723: tint * ibrdf * clip(softplus(. + rgb_bias), 0) * scale
 #if defined(RC_ABL) && RC_ABL == 3
         float diff = (ai[r] + a.irradiance_bias) * a.indirect_scale;       // ablation: no transcendentals
-        const float ref = fmaxf(1.0f * as[r] + a.slf_rgb_bias, 0.0f);
+        float spec = (tib * fmaxf(1.0f * as[r] + a.slf_rgb_bias, 0.0f)) * a.indirect_scale;
+        diff = __builtin_amdgcn_fmed3f(diff, 0.0f, a.rgb_max);
+        spec = __builtin_amdgcn_fmed3f(spec, 0.0f, a.rgb_max);
 #else
-        float diff = softplus_bins(ai[r] + a.irradiance_bias) * a.indirect_scale;
-        const float ref = fmaxf(softplus_bins(1.0f * as[r] + a.slf_rgb_bias), 0.0f);
+        float diff, spec;
+        td_head_value(a, ai[r], as[r], tib, diff, spec);
         // keep the value in front of the `live` select below: the optimizer otherwise sinks this chain into a divergent
         // branch on `live` (s_and_saveexec / s_cbranch / s_or exec per iteration) where one v_cndmask does
         asm volatile("" : "+v"(diff));
 #endif
-        float spec = (tib * ref) * a.indirect_scale;
-        // jnp.clip(x, 0, rgb_max) (nerf.py:1757-1758) as ONE v_med3_f32: the median of (x, 0, rgb_max) is the clamp for
-        // 0 <= rgb_max and an ordered x (softplus >= 0 is never NaN here); fmaxf + fminf were two instructions plus a
-        // canonicalising v_max of the scalar bound each
-        diff = live ? __builtin_amdgcn_fmed3f(diff, 0.0f, a.rgb_max) : 0.0f;
-        spec = live ? __builtin_amdgcn_fmed3f(spec, 0.0f, a.rgb_max) : 0.0f;
+        diff = live ? diff : 0.0f;
+        spec = live ? spec : 0.0f;
         sdu[r] += diff; ssu[r] += spec;
         cd += w * diff; cs += w * spec;
         const float val = w * (diff + spec);
@@ -734,86 +697,21 @@ __global__ __launch_bounds__(kWaves * 64) void k_transient_bins(RcTransBinsArgs 
   unsigned long long st_t1, st_t2;
   RC_BSTAMP(st_t1);
 #endif
-  // ---- direct light: scatter at (ray_dist + light_dist) / exposure with floor / ceil weights (render.py:436-477).
-  //      The reference indexes the flattened [rays * bins] array: bins >= 700 of the previous ray of the batch
-  //      land at the start of this ray's histogram.
-  {
-    // lanes 0-31 take the samples of the previous ray (their bins >= 700), lanes 32-63 those of this ray
-    const int64_t sr = ray - 1 + h;
-    int il = -1, ih = -1;
-    float vl[3] = {0.0f, 0.0f, 0.0f}, vh[3] = {0.0f, 0.0f, 0.0f};
-    if (sr >= 0) {
-      const int64_t p = sr * 32 + fl;
-      const float d = (a.tshade[RC_TS_LDIST * n + p] + a.tshade[RC_TS_RDIST * n + p]) / a.exposure + a.shift / a.exposure;
-      const float low = fmaxf(floorf(d), 0.0f), high = ceilf(d);
-      const float w_high = d - low, w_low = 1.0f - w_high;
-      const int off = h == 0 ? kBins : 0;
-      il = (int)low - off; ih = (int)high - off;
-      if (il < 0 || il >= kBins) il = -1;
-      if (ih < 0 || ih >= kBins) ih = -1;
-      const float w = a.weights[p];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float val = w * (a.tshade[(RC_TS_DD + c) * n + p] + a.tshade[(RC_TS_DS + c) * n + p]);
-        vl[c] = val * w_low; vh[c] = val * w_high;
-      }
-    }
-    // One LDS float add per (target kind, channel) for all 64 samples at once: lane = sample, all the low targets first,
-    // then all the high ones -- the order of the reference's two scatter-adds (render.py:453-477: `.at[indices_low].add`,
-    // then `.at[indices_high].add`).  Lanes that hit one address are served one after the other by the LDS.  (Rounds 1-3
-    // walked the 64 samples in order, eight v_readlane broadcasts and two three-lane adds each: 512 + 128 instructions.)
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (il >= 0) atomicAdd(&hist_d[il * 3 + c], vl[c]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (ih >= 0) atomicAdd(&hist_d[ih * 3 + c], vh[c]);
-  }
+  // ---- direct light: lanes 0-31 take the samples of the previous ray (their bins >= 700), lanes 32-63 those of this ray
+  td_direct_scatter(a, n, ray - 1 + h, fl, h == 0 ? kBins : 0, hist_d);
   lds_sync<false>();
 #ifdef RC_STAMPS
   RC_BSTAMP(st_t2);
 #endif
   // ---- temporal filter on the direct part (render.py:406-417), outputs, sums over bins
   float sum_d[3] = {0.0f, 0.0f, 0.0f}, sum_i[3] = {0.0f, 0.0f, 0.0f};
-  // the taps in registers (wave-uniform loads); the window of an entry is n_taps LDS reads 3 floats apart around it,
-  // the zero padding of hist_d stands in for the bins outside [0, 700) (adding tap * 0 leaves the sum unchanged)
   float tp[kMaxTaps];
-#pragma unroll
-  for (int k = 0; k < kMaxTaps; ++k) tp[k] = k < a.n_taps ? a.taps[k] : 0.0f;
-  const int half_taps = (a.n_taps - 1) / 2;
+  td_load_taps(a, tp);
   for (int e = lane; e < kHist; e += 64) {
     const int b = e / 3, c = e - 3 * b;
-    float dv;
-    if (a.n_taps > kMaxTaps) {
-      dv = 0.0f;
-      for (int k = 0; k < a.n_taps; ++k) {
-        const int yb = b - (k - half_taps);
-        if (yb >= 0 && yb < kBins) dv += a.taps[k] * hist_d[yb * 3 + c];
-      }
-#if defined(RC_ABL) && RC_ABL == 6
-    } else if (a.n_taps < 0) {                   // ablation: no filter
-#else
-    } else if (a.n_taps > 0) {
-#endif
-      dv = 0.0f;
-      const float* win = hist_d + e + 3 * half_taps;        // tap k reads bin b - (k - half)
-      if (a.n_taps == 25) {
-#pragma unroll
-        for (int k = 0; k < 25; ++k) dv += tp[k] * win[-3 * k];
-      } else {
-#pragma unroll
-        for (int k = 0; k < kMaxTaps; ++k)
-          if (k < a.n_taps) dv += tp[k] * win[-3 * k];
-      }
-    } else {
-      dv = hist_d[e];
-    }
+    const float dv = td_filter_entry(a, tp, hist_d, b, c);
     const float iv = hist_i[e] + hist_i[kHistPad + e];
-#if defined(RC_ABL) && RC_ABL == 5
-    if (ray_ok && dv + iv == 12345.678f) {       // ablation: no output stores
-#else
     if (ray_ok) {
-#endif
       if (a.out_rgb) a.out_rgb[ray * kHist + e] = dv + iv;
       if (a.out_direct) a.out_direct[ray * kHist + e] = dv;
       if (a.out_indirect) a.out_indirect[ray * kHist + e] = iv;

@@ -26,12 +26,15 @@
 #include <hip/hip_runtime.h>
 
 #include "rc_internal.h"
+#include "rc_dev_transient.h"
+
+using namespace rcdev;
 
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-constexpr int kB = kRcTdBins, kH = kRcTdHist;
+constexpr int kB = kBins, kH = kHist;
 constexpr int kPerLane = (kH + 63) / 64;       // histogram entries of a lane
 constexpr int kTiles = (kH + 31) / 32;         // 66 column tiles of 32 entries
 constexpr int kWavesPerBlock = 4;
@@ -44,7 +47,6 @@ __device__ __forceinline__ float half_sum(float v) {      // over the 32 lanes o
 }
 __device__ __forceinline__ float wave_total(float v) { return half_sum(v) + __shfl_xor(half_sum(v), 32, 64); }
 
-__device__ __forceinline__ float clip0(float x, float hi) { return fminf(fmaxf(x, 0.0f), hi); }
 __device__ __forceinline__ float softplus_f(float x) { return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x))); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 // d jnp.clip(x, 0, hi) / dx = d minimum(maximum(x, 0), hi): each tie passes half
@@ -80,13 +82,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_transient_loss(RcTransL
     const float r = rgb[ec], g = gt[ec];
     const float d = r - g, dnv = rgbn[ec] - gtn[ec];
     dn[k] = dnv;
-    // _get_rgb_clip_for_rawnerf (train_utils.py:369-393): the cache stage's rendering has no "cache_rgb": the pass's own rgb
-    float cl;
-    if (a.use_gt) cl = clip0(g, a.clip_val);
-    else {
-      cl = clip0(r, a.clip_val);
-      if (a.use_combined) cl = clip0(fmaxf(cl, g), a.clip_val);
-    }
+    const float cl = td_rawnerf_clip(a, r, g);
     const int ch = e % 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -131,21 +127,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_transient_loss(RcTransL
     }
   }
   __syncthreads();
-  // forward: out[b] = sum_k taps[k] in[b - (k - half)]  ->  d in[j] = sum_k taps[k] G[j + (k - half)]
-  const int half = (a.n_taps - 1) / 2;
-  for (int e = lane; e < kH; e += 64) {
-    float v;
-    if (a.n_taps > 0) {
-      v = 0.0f;
-      for (int k = 0; k < a.n_taps; ++k) {
-        const int j = e + 3 * (k - half);
-        if (j >= 0 && j < kH) v += a.taps[k] * sg[j];
-      }
-    } else {
-      v = sg[e];
-    }
-    if (ray_ok) a.Gt[ray * kH + e] = v;
-  }
+  td_filter_transpose_row(a, sg, lane, ray_ok ? a.Gt + ray * kH : nullptr);
 }
 
 // per-sample parameters of a ray in LDS
@@ -168,53 +150,36 @@ __global__ __launch_bounds__(kBinsWaves * 64) void k_transient_bins_bwd(RcTransB
   float dir_dw = 0.0f;
   if (lane < 32) {
     const int64_t p = ray * 32 + lane;
-    const float ld = a.tshade[RC_TS_LDIST * n + p], w = a.weights[p], cdist = a.tshade[RC_TS_CAMDIST * n + p];
-    const float rd = a.tshade[RC_TS_RDIST * n + p];
-    sp[P_W][lane] = w;
-    sp[P_DIND][lane] = (rd + a.shift) / a.exposure;                   // k_transient_bins' P_DIND
-    sp[P_TIB0][lane] = a.tshade[(RC_TS_TIB + 0) * n + p];
-    sp[P_TIB1][lane] = a.tshade[(RC_TS_TIB + 1) * n + p];
-    sp[P_TIB2][lane] = a.tshade[(RC_TS_TIB + 2) * n + p];
-    // the window of bins zero_invalid_bins keeps, with the comparisons of k_transient_bins
-    const bool kill = a.light_zero && ld < a.light_near;
-    auto close = [&](int b) { return (float)(b + a.bin_zero_threshold_light) * a.exposure < ld; };
-    auto far = [&](int b) { return ((float)b * a.exposure + cdist) > a.max_dists; };
-    int lo = (int)ceilf(ld / a.exposure) - a.bin_zero_threshold_light;
-    lo = min(max(lo, 0), kB);
-    while (lo > 0 && !close(lo - 1)) --lo;
-    while (lo < kB && close(lo)) ++lo;
-    int hi = (int)floorf((a.max_dists - cdist) / a.exposure);
-    hi = min(max(hi, -1), kB - 1);
-    while (hi < kB - 1 && !far(hi + 1)) ++hi;
-    while (hi >= 0 && far(hi)) --hi;
-    if (kill) { lo = kB; hi = -1; }
-    sp[P_LO][lane] = __int_as_float(lo);
-    sp[P_HI][lane] = __int_as_float(hi);
-    if (lo <= hi) { win_lo = lo; win_hi = hi; }
-    // ---- the direct scatter's adjoint (shift_direct, render.py:436-477): a gather of Gt at the sample's two bins; bins
-    //      [700, 1400) are the next ray's (the flattened [n 700] histogram), dropped behind the last ray as in the forward
-    const float d = (ld + rd) / a.exposure + a.shift / a.exposure;
-    const float low = fmaxf(floorf(d), 0.0f), high = ceilf(d);
-    const float w_high = d - low, w_low = 1.0f - w_high;
-    auto gt3 = [&](float bin, float (&o)[3]) {
+    const TdSample in = td_sample(a, n, p);
+    sp[P_W][lane] = in.w;
+    sp[P_DIND][lane] = in.d_ind;
+    sp[P_TIB0][lane] = in.tib[0];
+    sp[P_TIB1][lane] = in.tib[1];
+    sp[P_TIB2][lane] = in.tib[2];
+    const TdWindow win = td_window(a, in.ld, in.cdist);
+    sp[P_LO][lane] = __int_as_float(win.lo);
+    sp[P_HI][lane] = __int_as_float(win.hi);
+    if (win.lo <= win.hi) { win_lo = win.lo; win_hi = win.hi; }
+    // ---- the direct scatter's adjoint (shift_direct, render.py:436-477): a gather of Gt at the sample's two bins, in this
+    //      ray's row or the next ray's (the flattened [n 700] histogram), dropped behind the last ray as in the forward
+    const TdDirect own = td_direct(a, in.ld, in.rd, 0), next = td_direct(a, in.ld, in.rd, kB);
+    auto gt3 = [&](int b_own, int b_next, float (&o)[3]) {
       o[0] = o[1] = o[2] = 0.0f;
-      if (!(bin >= 0.0f && bin < (float)(2 * kB))) return;
-      int b = (int)bin;
-      int64_t r = ray;
-      if (b >= kB) { b -= kB; r += 1; }
-      if (r >= a.n_rays) return;
+      const int b = b_own >= 0 ? b_own : b_next;
+      const int64_t r = b_own >= 0 ? ray : ray + 1;
+      if (b < 0 || r >= a.n_rays) return;
       const float* g = a.Gt + r * kH + 3 * b;
       o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
     };
     float gl[3], gh[3];
-    gt3(low, gl);
-    gt3(high, gh);
+    gt3(own.il, next.il, gl);
+    gt3(own.ih, next.ih, gh);
     float dd[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float gat = w_low * gl[c] + w_high * gh[c];
+      const float gat = own.w_low * gl[c] + own.w_high * gh[c];
       const float direct = a.tshade[(RC_TS_DD + c) * n + p] + a.tshade[(RC_TS_DS + c) * n + p];
-      dd[c] = w * gat;
+      dd[c] = in.w * gat;
       dir_dw += direct * gat;
     }
     if (ray_ok) {
@@ -424,12 +389,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_transient_loss_kinds(Rc
     const float r = rgb[ec], g = gt[ec];
     const float dv = ok ? r - g : 0.0f, dnv = ok ? rgbn[ec] - gtn[ec] : 0.0f;
     d[k] = dv; dn[k] = dnv;
-    float cl;                                     // _get_rgb_clip_for_rawnerf, as k_transient_loss
-    if (a.use_gt) cl = clip0(g, a.clip_val);
-    else {
-      cl = clip0(r, a.clip_val);
-      if (a.use_combined) cl = clip0(fmaxf(cl, g), a.clip_val);
-    }
+    const float cl = td_rawnerf_clip(a, r, g);
     const int j = k % 3;
     acc[0][j] += ok ? cl : 0.0f;
     acc[1][j] += dv;
@@ -512,21 +472,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void k_transient_loss_kinds(Rc
     }
   }
   __syncthreads();
-  // the temporal filter's transpose, as k_transient_loss
-  const int half = (a.n_taps - 1) / 2;
-  for (int e = lane; e < kH; e += 64) {
-    float v;
-    if (a.n_taps > 0) {
-      v = 0.0f;
-      for (int k = 0; k < a.n_taps; ++k) {
-        const int j = e + 3 * (k - half);
-        if (j >= 0 && j < kH) v += a.taps[k] * sg[j];
-      }
-    } else {
-      v = sg[e];
-    }
-    if (ray_ok) a.Gt[ray * kH + e] = v;
-  }
+  td_filter_transpose_row(a, sg, lane, ray_ok ? a.Gt + ray * kH : nullptr);
 }
 
 // render_utils.dtof_to_itof: x [n][kB][3] -> out [n][n_rows][3], one wavefront per ray

@@ -45,7 +45,6 @@ int transient_data_backward_impl(rc_handle* h, const std::string& who, const rc_
   if (n == 0) return RC_OK;
   if (!gt || !losses) return fail(h, RC_ERR_INVALID_ARG, who + ": null gt/losses");
   const rc_transient_config& t = h->tcfg;
-  const int NL = h->cfg.num_levels;
   const int64_t np = n * 32;
   const std::vector<GradSeg> segs = transient_head_segments(h);
   if (t.n_bins != kRcTdBins || segs[0].shape[0] != 64 || segs[0].shape[1] != kRcTdHist || segs[2].shape[0] != 128 ||
@@ -75,7 +74,7 @@ int transient_data_backward_impl(rc_handle* h, const std::string& who, const rc_
   // 2. the loss, G and the filter's transpose of it
   roctx_stage("transient data loss");
   RcTransLossArgs la{};
-  la.n = n; la.n_taps = h->n_taps; la.taps = h->n_taps ? h->packs.t_taps.p : nullptr;
+  la.n = n; transient_taps(h, la);
   la.rgb = y.rgb.p; la.gt = gt; la.rgb_nocorr = rgb_nocorr; la.gt_nocorr = gt_nocorr; la.lossmult = lossmult;
   la.coef = (float)((double)cfg->mult / (3.0 * (double)n));
   la.gauss = (float)(2.0 * (double)cfg->gauss_constant_scale * (double)cfg->gauss_constant_scale * (double)cfg->gauss_mult);
@@ -101,14 +100,8 @@ int transient_data_backward_impl(rc_handle* h, const std::string& who, const rc_
     L[l] = Dense{(int)segs[2 * l].shape[0], (int)segs[2 * l].shape[1], h->thead_w.p + segs[2 * l].offset, h->thead_w.p + segs[2 * l + 1].offset};
   RC_HIP(h, hipMemsetD32Async((hipDeviceptr_t)y.ones.p, 0x3f800000, 1, st));     // 1.0f: the A operand of a bias gradient
   RcTransBinsBwdArgs b{};
-  b.n_rays = n;
-  b.slf_feat = w.t_slf.p; b.irr_feat = w.t_irr.p; b.tshade = w.tshade.p; b.weights = w.weights[NL - 1].p;
+  transient_in(h, w, n, b);
   b.w_irr = L[TH_IRR].w; b.b_irr = L[TH_IRR].b; b.w_slf = L[TH_SLF].w; b.b_slf = L[TH_SLF].b;
-  b.exposure = t.exposure_time; b.shift = t.transient_shift;
-  b.max_dists = (float)((double)(t.n_bins - 1) * (double)t.exposure_time);
-  b.irradiance_bias = t.irradiance_bias; b.slf_rgb_bias = t.slf_rgb_bias; b.indirect_scale = t.indirect_scale;
-  b.rgb_max = t.rgb_max; b.light_near = t.light_near;
-  b.bin_zero_threshold_light = t.bin_zero_threshold_light; b.light_zero = t.light_zero;
   b.G = y.G.p; b.Gt = y.Gt.p;
   b.dz_irr = y.dz_irr.p; b.dz_slf = y.dz_slf.p; b.x_irr = y.x_irr.p; b.x_slf = y.x_slf.p;
   b.d_tib = y.d_tint_ibrdf.p; b.d_direct = y.d_direct.p; b.d_weights = y.d_weights.p;

@@ -131,6 +131,19 @@ int repack_transient(rc_handle* h) {
 
 void enqueue_transient_slice(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st);      // rc_transient_slice_host.inc
 
+// What the integrator's kernels read alike, from the handle's settings: the shader's buffers of n rays in workspace set `w`
+void transient_in(const rc_handle* h, const RenderWs& w, int64_t n, RcTransIn& b) {
+  const rc_transient_config& t = h->tcfg;
+  b.n_rays = n;
+  b.slf_feat = w.t_slf.p; b.irr_feat = w.t_irr.p; b.tshade = w.tshade.p; b.weights = w.weights[h->cfg.num_levels - 1].p;
+  b.exposure = t.exposure_time; b.shift = t.transient_shift;
+  b.max_dists = (float)((double)(t.n_bins - 1) * (double)t.exposure_time);       // render_utils.py:1730
+  b.irradiance_bias = t.irradiance_bias; b.slf_rgb_bias = t.slf_rgb_bias; b.indirect_scale = t.indirect_scale;
+  b.rgb_max = t.rgb_max; b.light_near = t.light_near;
+  b.bin_zero_threshold_light = t.bin_zero_threshold_light; b.light_zero = t.light_zero;
+}
+void transient_taps(const rc_handle* h, RcTransTaps& f) { f.n_taps = h->n_taps; f.taps = h->n_taps ? h->packs.t_taps.p : nullptr; }
+
 // After the proposal sampler and the appearance-grid lookup: shader, per-bin heads + compositing, scalar composites.
 // `w` is workspace set 0 (the shadow rays use its extras and the secondary set).
 void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st) {
@@ -184,14 +197,7 @@ void enqueue_transient_tail(rc_handle* h, const RenderArgs& A, RenderWs& w, hipS
     enqueue_transient_slice(h, A, w, st);       // rc_render_transient_slices: the bins that reach the asked times only
   } else {
     RcTransBinsArgs b{};
-    b.n_rays = n; b.wstream = h->packs.t_bins.p;
-    b.slf_feat = w.t_slf.p; b.irr_feat = w.t_irr.p; b.tshade = w.tshade.p; b.weights = w.weights[NL - 1].p;
-    b.exposure = t.exposure_time; b.shift = t.transient_shift;
-    b.max_dists = (float)((double)(t.n_bins - 1) * (double)t.exposure_time);       // render_utils.py:1730
-    b.irradiance_bias = t.irradiance_bias; b.slf_rgb_bias = t.slf_rgb_bias; b.indirect_scale = t.indirect_scale;
-    b.rgb_max = t.rgb_max; b.light_near = t.light_near;
-    b.bin_zero_threshold_light = t.bin_zero_threshold_light; b.light_zero = t.light_zero;
-    b.n_taps = h->n_taps; b.taps = h->n_taps ? h->packs.t_taps.p : nullptr;
+    transient_in(h, w, n, b); transient_taps(h, b); b.wstream = h->packs.t_bins.p;
     b.out_rgb = o.ptr[RC_TOUT_RGB]; b.out_direct = o.ptr[RC_TOUT_TRANSIENT_DIRECT_VIZ]; b.out_indirect = o.ptr[RC_TOUT_TRANSIENT_INDIRECT_VIZ];
     b.out_ti_diffuse = o.ptr[RC_TOUT_TRANSIENT_INDIRECT_DIFFUSE]; b.out_ti_specular = o.ptr[RC_TOUT_TRANSIENT_INDIRECT_SPECULAR];
     b.out_direct_rgb = o.ptr[RC_TOUT_DIRECT_RGB]; b.out_indirect_rgb = o.ptr[RC_TOUT_INDIRECT_RGB];
@@ -280,84 +286,5 @@ int rc_render_transient(rc_handle* h, const rc_rays* rays, const float* cam_orig
   RoctxScope roctx_call("rc_render_transient");
   if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_render_transient: call rc_set_transient first");
   return render_transient_impl(h, rays, cam_origins, n, rnd, shadow_rnd, out, nullptr, stream_v, "rc_render_transient");
-  RC_CATCH(h)
-}
-
-static RcCastOut cast_out(const rc_cast_outputs* out) {
-  RcCastOut o{};
-  o.origins = out->origins; o.directions = out->directions; o.viewdirs = out->viewdirs; o.radii = out->radii;
-  o.imageplane = out->imageplane; o.look = out->look; o.up = out->up; o.lights = out->lights; o.near = out->near; o.far = out->far;
-  return o;
-}
-
-// The fields rc_camera and rc_camera_set share, into the kernels' form; -> what is wrong with them, or NULL
-template <class Cam>
-static const char* cast_shared(const Cam* cam, RcCastShared& s) {
-  if (cam->camtype < 0 || cam->camtype > 3)
-    return "camtype must be 0 (perspective), 1 (panoramic), 2 (fisheye) or 3 (fisheye, equisolid)";
-  s.near_v = cam->near; s.far_v = cam->far; s.camtype = cam->camtype;
-  s.has_distortion = cam->has_distortion != 0;
-  for (int i = 0; i < 6; ++i) s.dist[i] = cam->distortion[i];
-  s.has_ndc = cam->has_ndc != 0;
-  if (s.has_ndc) {          // convert_to_ndc: xmult = 1 / pixtocam[0, 2], ymult = 1 / pixtocam[1, 2] (camera_utils.py:97-98)
-    if (cam->pixtocam_ndc[2] == 0.0f || cam->pixtocam_ndc[5] == 0.0f) return "pixtocam_ndc[0][2] and [1][2] must be non-zero";
-    s.ndc_xmult = 1.0f / cam->pixtocam_ndc[2]; s.ndc_ymult = 1.0f / cam->pixtocam_ndc[5];
-  }
-  s.has_z_range = cam->has_z_range != 0; s.z_lo = cam->z_range[0]; s.z_hi = cam->z_range[1];
-  return nullptr;
-}
-
-int rc_cast_rays(rc_handle* h, const rc_camera* cam, const int32_t* pix_x, const int32_t* pix_y, int64_t n,
-                 int32_t x0, int32_t y0, int32_t width, int32_t height, const rc_cast_outputs* out, void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (!cam || !out) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: null camera/outputs");
-  if ((pix_x == nullptr) != (pix_y == nullptr)) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: pix_x and pix_y go together");
-  if (!pix_x) {
-    if (width <= 0 || height <= 0) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: empty pixel rectangle");
-    if (n != (int64_t)width * height) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: n must equal width * height");
-  }
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: negative n");
-  if (n == 0) return RC_OK;
-  RC_HIP(h, hipSetDevice(h->device));
-  RcCastArgs a{};
-  a.n = n; a.pix_x = pix_x; a.pix_y = pix_y; a.x0 = x0; a.y0 = y0; a.width = width > 0 ? width : 1;
-  for (int i = 0; i < 9; ++i) a.pixtocam[i] = cam->pixtocam[i];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) a.rot[3 * r + c] = cam->camtoworld[4 * r + c];
-    a.trans[r] = cam->camtoworld[4 * r + 3];
-    a.light[r] = cam->light[r];
-  }
-  if (const char* bad = cast_shared(cam, a.s))
-    return fail(h, cam->camtype < 0 || cam->camtype > 3 ? RC_ERR_UNSUPPORTED : RC_ERR_INVALID_ARG, std::string("rc_cast_rays: ") + bad);
-  if ((cam->pix_dx == nullptr) != (cam->pix_dy == nullptr)) return fail(h, RC_ERR_INVALID_ARG, "rc_cast_rays: pix_dx and pix_dy go together");
-  a.pix_dx = cam->pix_dx; a.pix_dy = cam->pix_dy;
-  a.out = cast_out(out);
-  rc_launch_cast_rays(a, (hipStream_t)stream_v);
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
-  RC_CATCH(h)
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// rc_prng_fill: jax.random-compatible random tensors generated in HBM (../prng.py is the host twin)
-// ---------------------------------------------------------------------------------------------------------
-int rc_prng_fill(rc_handle* h, const uint32_t key[2], int32_t mode, float minval, float maxval, int64_t n, void* out,
-                 void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
-  if (!key || (!out && n > 0)) return fail(h, RC_ERR_INVALID_ARG, "rc_prng_fill: null key/output");
-  if (mode < RC_PRNG_BITS || mode > RC_PRNG_GUMBEL) return fail(h, RC_ERR_INVALID_ARG, "rc_prng_fill: unknown mode");
-  if (n < 0 || n >= 0xFFFFFFFFll) return fail(h, RC_ERR_INVALID_ARG, "rc_prng_fill: n must be in [0, 2^32 - 1)");
-  if (n == 0) return RC_OK;
-  RC_HIP(h, hipSetDevice(h->device));
-  RcPrngArgs a{};
-  a.key0 = key[0]; a.key1 = key[1]; a.mode = mode; a.n = n; a.out = (uint32_t*)out;
-  // jax.random.normal / gumbel fix their own range: (nextafter(-1, 0), 1) and (tiny, 1)
-  a.lo = mode == RC_PRNG_NORMAL ? -0.99999994f : (mode == RC_PRNG_GUMBEL ? 1.17549435e-38f : minval);
-  a.hi = (mode == RC_PRNG_NORMAL || mode == RC_PRNG_GUMBEL) ? 1.0f : maxval;
-  rc_launch_prng_fill(a, (hipStream_t)stream_v);
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
   RC_CATCH(h)
 }

@@ -13,20 +13,17 @@
 // activations (LDS, one row per sample) with one weight column (global, contiguous), and leaves weight * value in LDS;
 // a second pass adds the 32 samples of each (time, target, channel) in sample order.
 // Direct part: the floor / ceil scatter of this ray's and the previous ray's samples into the ray's LDS histogram and the
-// temporal filter, both as k_transient_bins does them, the filter for the 2 x 3 entries of each time only.
+// temporal filter of k_transient_bins (rc_dev_transient.h), the filter for the 2 x 3 entries of each time only.
 // Nothing is reduced across lanes and every sum has a fixed order: two launches are bitwise equal, and a time's result
 // does not depend on the other times of the launch.
 #include "rc_internal.h"
 #include "rc_dev_sample.h"
+#include "rc_dev_transient.h"
 
 using namespace rcdev;
 
 namespace {
 
-constexpr int kBins = 700;
-constexpr int kHist = kBins * 3;
-constexpr int kMaxTaps = 32;                     // temporal filter taps handled by the unrolled window
-constexpr int kPadD = 3 * (kMaxTaps / 2);        // zeros on both sides of the direct histogram
 constexpr int kSliceWaves = 4;                   // rays of a workgroup (the waves share nothing)
 constexpr int kItems = 32 * 9;                   // (sample, source bin slot, channel) of one time
 constexpr int kHistD = kHist + 2 * kPadD;
@@ -35,12 +32,6 @@ constexpr int kSP = 7;
 constexpr int kSliceWaveLds = 32 * kRcSliceStrideSlf + 32 * kRcSliceStrideIrr + kRegion + kSP * 32;   // floats
 static_assert(kSliceWaves * kSliceWaveLds * 4 <= 160 * 1024, "a workgroup's rays fit the LDS of a compute unit");
 static_assert(kRcSliceMax * 6 <= 64, "one lane per (time, target, channel)");
-
-// k_transient_bins' softplus (rc_transient.hip softplus_bins), the same three lines
-__device__ __forceinline__ float softplus_bins(float x) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(x) * 1.44269504088896341f);
-  return fmaxf(x, 0.0f) + __builtin_amdgcn_logf(1.0f + e) * 0.693147180559945309f;
-}
 
 // floor(y - d) as a bin index; far outside the histogram it is held at -8 / 708 (every bin next to it is outside too)
 __device__ __forceinline__ int src_bin(float y, float d) { return (int)fminf(fmaxf(floorf(y - d), -8.0f), (float)(kBins + 8)); }
@@ -64,29 +55,15 @@ __global__ __launch_bounds__(kSliceWaves * 64) void k_transient_slice(RcTransSli
   for (int e = lane; e < kHistD; e += 64) region[e] = 0.0f;
   if (lane < 32) {
     const int64_t p = ray * 32 + lane;
-    const float ld = a.tshade[RC_TS_LDIST * n + p], in_w = a.weights[p], cdist = a.tshade[RC_TS_CAMDIST * n + p];
-    const float in_t0 = a.tshade[(RC_TS_TIB + 0) * n + p], in_t1 = a.tshade[(RC_TS_TIB + 1) * n + p],
-                in_t2 = a.tshade[(RC_TS_TIB + 2) * n + p], in_rd = a.tshade[RC_TS_RDIST * n + p];
-    sp[P_W * 32 + lane] = in_w;
-    sp[P_TIB0 * 32 + lane] = in_t0;
-    sp[P_TIB1 * 32 + lane] = in_t1;
-    sp[P_TIB2 * 32 + lane] = in_t2;
-    sp[P_DIND * 32 + lane] = (in_rd + a.shift) / a.exposure;          // k_transient_bins' P_DIND
-    // the window of bins zero_invalid_bins keeps (render_utils.py:1699-1767), with the comparisons of k_transient_bins
-    const bool kill = a.light_zero && ld < a.light_near;
-    auto close = [&](int b) { return (float)(b + a.bin_zero_threshold_light) * a.exposure < ld; };
-    auto far = [&](int b) { return ((float)b * a.exposure + cdist) > a.max_dists; };
-    int lo = (int)ceilf(ld / a.exposure) - a.bin_zero_threshold_light;
-    lo = min(max(lo, 0), kBins);
-    while (lo > 0 && !close(lo - 1)) --lo;
-    while (lo < kBins && close(lo)) ++lo;
-    int hi = (int)floorf((a.max_dists - cdist) / a.exposure);
-    hi = min(max(hi, -1), kBins - 1);
-    while (hi < kBins - 1 && !far(hi + 1)) ++hi;
-    while (hi >= 0 && far(hi)) --hi;
-    if (kill) { lo = kBins; hi = -1; }
-    sp[P_LO * 32 + lane] = __int_as_float(lo);
-    sp[P_HI * 32 + lane] = __int_as_float(hi);
+    const TdSample in = td_sample(a, n, p);
+    sp[P_W * 32 + lane] = in.w;
+    sp[P_TIB0 * 32 + lane] = in.tib[0];
+    sp[P_TIB1 * 32 + lane] = in.tib[1];
+    sp[P_TIB2 * 32 + lane] = in.tib[2];
+    sp[P_DIND * 32 + lane] = in.d_ind;
+    const TdWindow win = td_window(a, in.ld, in.cdist);
+    sp[P_LO * 32 + lane] = __int_as_float(win.lo);
+    sp[P_HI * 32 + lane] = __int_as_float(win.hi);
   }
   if (want_indirect) {
     // this ray's activations of the two head layers, one row per sample (lane & 31 = sample, lane >> 5 = which of the
@@ -109,63 +86,13 @@ __global__ __launch_bounds__(kSliceWaves * 64) void k_transient_slice(RcTransSli
 
   float dv = 0.0f;
   if (want_direct) {
-    // ---- direct light: k_transient_bins' scatter (render.py:436-477); bins >= 700 of the previous ray of the batch land
-    //      at the start of this ray's histogram
-    {
-      const int64_t sr = ray - 1 + h;
-      int il = -1, ih = -1;
-      float vl[3] = {0.0f, 0.0f, 0.0f}, vh[3] = {0.0f, 0.0f, 0.0f};
-      if (sr >= 0) {
-        const int64_t p = sr * 32 + fl;
-        const float d = (a.tshade[RC_TS_LDIST * n + p] + a.tshade[RC_TS_RDIST * n + p]) / a.exposure + a.shift / a.exposure;
-        const float low = fmaxf(floorf(d), 0.0f), high = ceilf(d);
-        const float w_high = d - low, w_low = 1.0f - w_high;
-        const int off = h == 0 ? kBins : 0;
-        // (held inside the int range first: a bin far outside the histogram is dropped either way)
-        il = (int)fminf(low, 4.0f * kBins) - off; ih = (int)fminf(fmaxf(high, -1.0f), 4.0f * kBins) - off;
-        if (il < 0 || il >= kBins) il = -1;
-        if (ih < 0 || ih >= kBins) ih = -1;
-        const float w = a.weights[p];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float val = w * (a.tshade[(RC_TS_DD + c) * n + p] + a.tshade[(RC_TS_DS + c) * n + p]);
-          vl[c] = val * w_low; vh[c] = val * w_high;
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        if (il >= 0) atomicAdd(&hist_d[il * 3 + c], vl[c]);
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        if (ih >= 0) atomicAdd(&hist_d[ih * 3 + c], vh[c]);
-    }
+    // ---- direct light: lanes 0-31 take the samples of the previous ray (their bins >= 700), lanes 32-63 those of this ray
+    td_direct_scatter(a, n, ray - 1 + h, fl, h == 0 ? kBins : 0, hist_d);
     lds_sync<false>();
-    // ---- temporal filter (render.py:406-417) of this lane's entry, k_transient_bins' three forms
+    // ---- temporal filter of this lane's entry
     float tp[kMaxTaps];
-#pragma unroll
-    for (int k = 0; k < kMaxTaps; ++k) tp[k] = k < a.n_taps ? a.taps[k] : 0.0f;
-    const int half_taps = (a.n_taps - 1) / 2;
-    if (o_ok) {
-      const int e = o_y * 3 + o_c;
-      if (a.n_taps > kMaxTaps) {
-        for (int k = 0; k < a.n_taps; ++k) {
-          const int yb = o_y - (k - half_taps);
-          if (yb >= 0 && yb < kBins) dv += a.taps[k] * hist_d[yb * 3 + o_c];
-        }
-      } else if (a.n_taps > 0) {
-        const float* win = hist_d + e + 3 * half_taps;        // tap k reads bin y - (k - half)
-        if (a.n_taps == 25) {
-#pragma unroll
-          for (int k = 0; k < 25; ++k) dv += tp[k] * win[-3 * k];
-        } else {
-#pragma unroll
-          for (int k = 0; k < kMaxTaps; ++k)
-            if (k < a.n_taps) dv += tp[k] * win[-3 * k];
-        }
-      } else {
-        dv = hist_d[e];
-      }
-    }
+    td_load_taps(a, tp);
+    if (o_ok) dv = td_filter_entry(a, tp, hist_d, o_y, o_c);
     lds_sync<false>();                             // the histogram is read: its LDS now takes the items' values
   }
 
@@ -215,12 +142,8 @@ __global__ __launch_bounds__(kSliceWaves * 64) void k_transient_slice(RcTransSli
         }
         const float ai = ((r0 + r1) + (r2 + r3)) + wi[64];
         const float tib = sp[(P_TIB0 + c) * 32 + s];
-        // nerf.py:1795-1797, :1712-1719 and surface_light_field.py:1037-1058, nerf.py:1721-1723, as k_transient_bins
-        float diff = softplus_bins(ai + a.irradiance_bias) * a.indirect_scale;
-        const float ref = fmaxf(softplus_bins(1.0f * as + a.slf_rgb_bias), 0.0f);
-        float spec = (tib * ref) * a.indirect_scale;
-        diff = __builtin_amdgcn_fmed3f(diff, 0.0f, a.rgb_max);
-        spec = __builtin_amdgcn_fmed3f(spec, 0.0f, a.rgb_max);
+        float diff, spec;
+        td_head_value(a, ai, as, tib, diff, spec);
         val = w * (diff + spec);
       }
       if (valid) vals[it] = val;

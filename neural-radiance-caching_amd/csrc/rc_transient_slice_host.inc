@@ -4,17 +4,10 @@
 namespace {
 
 void enqueue_transient_slice(rc_handle* h, const RenderArgs& A, RenderWs& w, hipStream_t st) {
-  const rc_transient_config& t = h->tcfg;
   const rc_transient_slices& sl = *A.tslices;
   RcTransSliceArgs b{};
-  b.n_rays = A.n; b.w_slf = h->packs.t_slice_slf.p; b.w_irr = h->packs.t_slice_irr.p;
-  b.slf_feat = w.t_slf.p; b.irr_feat = w.t_irr.p; b.tshade = w.tshade.p; b.weights = w.weights[h->cfg.num_levels - 1].p;
-  b.exposure = t.exposure_time; b.shift = t.transient_shift;
-  b.max_dists = (float)((double)(t.n_bins - 1) * (double)t.exposure_time);       // render_utils.py:1730
-  b.irradiance_bias = t.irradiance_bias; b.slf_rgb_bias = t.slf_rgb_bias; b.indirect_scale = t.indirect_scale;
-  b.rgb_max = t.rgb_max; b.light_near = t.light_near;
-  b.bin_zero_threshold_light = t.bin_zero_threshold_light; b.light_zero = t.light_zero;
-  b.n_taps = h->n_taps; b.taps = h->n_taps ? h->packs.t_taps.p : nullptr;
+  transient_in(h, w, A.n, b); transient_taps(h, b);
+  b.w_slf = h->packs.t_slice_slf.p; b.w_irr = h->packs.t_slice_irr.p;
   b.count = sl.count;
   for (int i = 0; i < kRcSliceMax; ++i) b.t[i] = i < sl.count ? sl.t[i] : 0.0f;
   b.out_rgb = sl.rgb; b.out_direct = sl.direct; b.out_indirect = sl.indirect;

@@ -347,8 +347,8 @@ PRODUCTION = [
     (_M, 85, ("wgrad", 256, 256, 256, 0, 256, 0)), (_M, 86, ("wgrad", 256, 256, 256, 0, 256, 0)),
     (_M, 87, ("wgrad", 27, 256, 288, 256, 256, 0)),
     # rc_transient_bwd_host.inc: the per-bin heads (dX at chunk r0 = 1: 32 rows of 64 / 128 in)
-    (_T, 121, ("dx", 64, 2100, 2100, 0, 64, 2048, 0, 64, None, 0)), (_T, 122, ("dx", 128, 2101, 2104, 0, 128, 4096, 0, 128, None, 0)),
-    (_T, 124, ("wgrad", 64, 2100, 64, 0, 2100, 0)), (_T, 125, ("wgrad", 128, 2101, 128, 0, 2104, 0)),
+    (_T, 114, ("dx", 64, 2100, 2100, 0, 64, 2048, 0, 64, None, 0)), (_T, 115, ("dx", 128, 2101, 2104, 0, 128, 4096, 0, 128, None, 0)),
+    (_T, 117, ("wgrad", 64, 2100, 64, 0, 2100, 0)), (_T, 118, ("wgrad", 128, 2101, 128, 0, 2104, 0)),
 ]
 # lines that hold a dense_* name without being a call site of their own: the two wgrad lambdas and the launch of the
 # hand-built descriptor (listed above under the line that starts it)

@@ -144,9 +144,11 @@ def test_windows_are_exact_zeros_outside(runs, target):
 def test_slice_equals_interpolated_histograms(runs, target):
     """k_transient_slice against k_transient_bins on the same buffers: w v[ceil t] + (1 - w) v[floor t] of the histograms the
     bins kernel wrote, to the 4e-5 of test_slices_vs_full_render_and_extras_bitwise (there on histograms below 1; here
-    relative to the largest of the entries read where that exceeds 1)."""
+    relative to the largest of the entries read where that exceeds 1).  The direct part is held to equality as well: the
+    expression in float32, in that order, from the twin's out_direct ("the direct slice is bitwise the full
+    render's", here on asymmetric taps and every form of the filter)."""
     run = runs[target]
-    worst, seen = 0.0, 0
+    worst, seen, exact_seen = 0.0, 0, 0
     for li, L in enumerate(run.cs.launches):
         if L["kernel"] != "slice" or L.get("twin") is None:
             continue
@@ -154,6 +156,13 @@ def test_slice_equals_interpolated_histograms(runs, target):
             s, h = run.logical(li, slot), run.logical(L["twin"], slot)
             if s is None or h is None:
                 continue
+            if slot == "out_direct":
+                # the two kernels share the scatter and the filter (rc_dev_transient.h): float32, in the kernel's order
+                tf = np.asarray(L["t"], np.float32)
+                w = (tf - np.floor(tf))[None, :, None]
+                exact = w * h[:, np.ceil(tf).astype(int)] + (np.float32(1.0) - w) * h[:, np.floor(tf).astype(int)]
+                assert exact.dtype == np.float32 and np.array_equal(s.view(np.uint32), exact.view(np.uint32)), (L["name"], slot)
+                exact_seen += 1
             h = h.astype(np.float64)
             t = np.asarray(L["t"], np.float32).astype(np.float64)
             mag = np.maximum(np.abs(h[:, np.floor(t).astype(int)]), np.abs(h[:, np.ceil(t).astype(int)]))
@@ -162,7 +171,7 @@ def test_slice_equals_interpolated_histograms(runs, target):
             assert d.max() <= 4e-5, (L["name"], slot, float(d.max()))
             seen += 1
     print(f"{target}: max |slice - interpolated histogram| = {worst:.3e} (bound 4e-5) over {seen} outputs")
-    assert seen >= 3 * 55
+    assert seen >= 3 * 55 and exact_seen >= 55
 
 
 @pytest.mark.parametrize("target", list(TARGETS))

@@ -68,9 +68,8 @@ const Packed& packed(const Launch& L) {
   return g_packs.back();
 }
 
-// the fields RcTransBinsArgs, RcTransSliceArgs and RcTransBinsBwdArgs share: floats 0-7 in the structs' order
-template <class A>
-void shared_fields(const Launch& L, A& a, int64_t n, int64_t thr, int64_t light_zero) {
+// the block RcTransBinsArgs, RcTransSliceArgs and RcTransBinsBwdArgs share: floats 0-7 in the struct's order
+void shared_fields(const Launch& L, RcTransIn& a, int64_t n, int64_t thr, int64_t light_zero) {
   if (thr < -(1 << 20) || thr > (1 << 20)) die("bad bin threshold");
   a.n_rays = n;
   a.slf_feat = L.P(S_SLF, n * 64 * 64, true); a.irr_feat = L.P(S_IRR, n * 32 * 64, true);
