@@ -293,7 +293,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "i:" = rc_interlevel_backward, "d:" = rc_data_backward, "g:" = rc_geometry_backward / rc_density_regularizer,
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
  * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env,
- * "td:" = rc_transient_data_backward, "mk:" = rc_mask_backward.
+ * "td:" = rc_transient_data_backward, "mk:" = rc_mask_backward, "nb:" = rc_normals_backward,
+ * "gs:" = rc_geometry_smoothness_backward.
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -752,6 +753,48 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
  * ACCUMULATED into each table's segment of it (layout rc_density_grad_layout(level)); the MLP segments are untouched.
  * Ordered on `stream`; the time-resolved cache handle is unsupported. */
 int rc_density_regularizer(rc_handle* h, int32_t level, float mult, float* density_grads, float* loss, void* stream);
+
+/* Gradient THROUGH the analytic normals of the last sampler level (second order in the density field): for
+ * n(x) = nan_to_num(-l2_normalize(d raw / d x)) (geometry.py:421-460, no stop-gradient) the gradient of
+ * sum(d_normals * n(points)) with respect to the last level's tables and the kernels of density_layers_0,
+ * density_layers_1 and output_density_layer, ACCUMULATED into `grads` (layout rc_density_grad_layout(num_levels-1)).
+ * The three bias gradients are exact zeros (the ReLU network is piecewise linear): the bias segments are not touched.
+ * points: [n,3] world-space, d_normals: [n,3], normals_out: [n,3] or NULL (the normals themselves), all device.
+ * l2_normalize's override gradient (the backward divides by sqrt(max(float32 eps, |g|^2))) and nan_to_num's rule (the
+ * gradient passes where the value is finite) are the reference's.  The weight gradients have a fixed reduction order
+ * (bitwise reproducible); the table gradients are float atomics (order-dependent in the last bits).
+ * Any handle whose last level has 32 grid features (RC_ERR_UNSUPPORTED otherwise), the time-resolved one included.
+ * RC_ERR_INVALID_ARG for n < 0, NULL grads, NULL points / d_normals with n > 0; n == 0 returns RC_OK and launches nothing.
+ * Ordered on `stream`.  Buffers: "nb:" names ("feat", "jac", "gf", "ghat", "u", "t0", "a0", "t1", "a2", "ones", "partial",
+ * "normals"). */
+int rc_normals_backward(rc_handle* h, const float* points, int64_t n, const float* d_normals, float* grads, float* normals_out,
+                        void* stream);
+
+/* geometry_smoothness_loss of the cache stage (train_utils.py:2703-2812; added to "main" at trainer.py:316-320 when
+ * Config.use_geometry_smoothness is set and the stage has no material) and its exact gradient.  On the last sampler
+ * level (S intervals), with x the training forward's sample means (no gradient), x' = x + noise * cfg->noise (fp32, product
+ * and sum rounded separately; noise: DEVICE [n, S, 3] standard normals, prng.geometry_smoothness_noise) and
+ * c = lossmult * stop_gradient(weights * S):
+ *   loss = weight_normals * mean over [n, S, 3] of |n(x) - n(x')| c + weight_density * mean over [n, S] of |d(x) - d(x')| c,
+ * n the analytic normals (differentiable at both point sets), d the converted density with its bounding-box mask,
+ * nan_to_num on the perturbed results, lax.abs' derivative (+1 at 0).  One call:
+ *   1. the training forward of the sampler levels with the analytic normals (as rc_geometry_backward) on a workspace set
+ *      of its own ("gs:"), the perturbed points, the last level once more at x';
+ *   2. the loss (ONE DEVICE float, written; fixed reduction order, bitwise reproducible), d loss / d normals at x and
+ *      (negated) at x', d loss / d density at both when weight_density != 0;
+ *   3. only when density_grads is given, per chunk of 32 768 samples: rc_normals_backward at x and at x', and
+ *      rc_density_backward at both when weight_density != 0, all ACCUMULATED into density_grads (layout
+ *      rc_density_grad_layout(num_levels-1)).
+ * cfg: HOST struct; the weights already carry the caller's mult.  weight_normals_pred != 0 is RC_ERR_UNSUPPORTED before
+ * any launch (no config uses it), and so is a time-resolved cache handle, a last level of more than 32 intervals or of
+ * other than 32 grid features.  RC_ERR_INVALID_ARG for NULL rays / cfg / loss, NULL noise with n > 0, a non-finite setting
+ * or anneal.  n == 0 returns RC_OK and writes nothing.  Ordered on `stream`.  Buffers: "gs:" names (the training forward's,
+ * and "means_p" SoA [3][n S], "feat_p", "jac_p", "density_p", "normals_p" SoA, "points", "points_p" [n S][3], "d_normals",
+ * "d_normals_p" [n S][3], "d_density", "d_density_p", "loss_ray"). */
+typedef struct { float noise, weight_normals, weight_normals_pred, weight_density; } rc_geometry_smoothness;
+int rc_geometry_smoothness_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                                    float anneal, const float* noise, const rc_geometry_smoothness* cfg, float* density_grads,
+                                    float* loss, void* stream);
 
 /* Mask loss of the cache stage on the last sampler level's opacity and its exact gradient (train_utils.compute_mask_loss,
  * internal/train_utils.py:785-836, called at :2919-2927 whenever not config.is_material), with acc = the sum of the

@@ -319,6 +319,20 @@ class LightSamplingConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class GeometrySmoothnessConfig:
+    """Training-time constants of the geometry smoothness loss of a stage without a material (every transient scene config
+    and nero_ngp_yobo_luyu.gin set Config.use_geometry_smoothness)."""
+    # the geometry_smoothness extra loss of the stage: "main" mult 1.0, start_frac 0.0 (engine/trainer.py:316-320)
+    mult: float = 1.0
+    start_frac: float = 0.0
+    # Config.geometry_smoothness_* (configs/transient_simulation_ngp_yobo_pots.gin:151-155)
+    noise: float = 0.1                     # :152
+    weight_normals: float = 0.001          # :153
+    weight_normals_pred: float = 0.0       # :154
+    weight_density: float = 0.0            # :155
+
+
+@dataclasses.dataclass(frozen=True)
 class MaterialSmoothnessConfig:
     """Training-time constants of the material network's smoothness loss, its grid regularizer and the stage's other
     extra loss (the material_light_from_scratch stage, hotdog)."""

@@ -54,6 +54,7 @@ const char* const kRawPaths[RAW_COUNT] = {"params/MaterialShader/bottleneck_laye
                                           "params/LightSampler/output_layer"};
 struct Packs {
   DevBuf dens[RC_MAX_LEVELS], train[RC_MAX_LEVELS];
+  DevBuf nbwd;                           // rc_normals_backward: the last level's training stream + the two replayed forward layers
   DevBuf shader, fused, fused_front, envmap, t_shader, t_bins, t_taps;
   DevBuf t_slice_slf, t_slice_irr;       // k_transient_slice: the two per-bin heads as plain columns (repack_transient)
   DevBuf pair[RC_MAX_GRID_LEVELS];       // level-2 density + appearance tables interleaved (cell tables on dense levels)
@@ -148,6 +149,15 @@ struct MaskWs { WsBuf loss_ray, d_density, points; };
 // maxima (64-bit integers).
 struct RelightWs { WsBuf part, best; };
 
+// rc_normals_backward: the last level's grid features and their Jacobian, d raw / d feature (feature-major) and G^ = d L /
+// d (the Jacobian-chained gradient) for the scatter, the point-major operands of the weight-gradient contraction
+// (u [n][32]; t0, a0, t1, a2 [n][64]; a column of ones), its per-workgroup partials, and the normals when the caller wants none.
+struct NormalsWs { WsBuf feat, jac, gf, ghat, u, t0, a0, t1, a2, ones, partial, normals; };
+// rc_geometry_smoothness_backward, beside its RenderWs (the training forward): the perturbed means (SoA, as the density MLP
+// reads them) with their features, Jacobian, density and analytic normals; the means and perturbed means as points [n S][3];
+// d loss / d normals and d loss / d density at both point sets; the per-ray loss values.
+struct GSmoothWs { WsBuf means_p, feat_p, jac_p, density_p, normals_p, points, points_p, d_normals, d_normals_p, d_density, d_density_p, loss_ray; };
+
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
 // serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
@@ -158,15 +168,16 @@ struct RelightWs { WsBuf part, best; };
 // WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY),
 // WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
 // rc_eval_image and rc_eval_shift_invariant, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
-// WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick.
+// WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick, WS_NORMALS rc_normals_backward, WS_GSMOOTH
+// rc_geometry_smoothness_backward.
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_NORMALS, WS_GSMOOTH, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:", "nb:", "gs:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs, NormalsWs, GSmoothWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -188,7 +199,7 @@ struct WsName {
   WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
   WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
   WsBuf EvalWs::*ev = nullptr; WsBuf AlbedoWs::*ea = nullptr; WsBuf VisWs::*vz = nullptr;
-  WsBuf MaskWs::*mk = nullptr; WsBuf RelightWs::*rl = nullptr;
+  WsBuf MaskWs::*mk = nullptr; WsBuf RelightWs::*rl = nullptr; WsBuf NormalsWs::*nb = nullptr; WsBuf GSmoothWs::*gs = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -207,6 +218,8 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf VisWs::*m) : name(s), vz(m) {}
   constexpr WsName(const char* s, WsBuf MaskWs::*m) : name(s), mk(m) {}
   constexpr WsName(const char* s, WsBuf RelightWs::*m) : name(s), rl(m) {}
+  constexpr WsName(const char* s, WsBuf NormalsWs::*m) : name(s), nb(m) {}
+  constexpr WsName(const char* s, WsBuf GSmoothWs::*m) : name(s), gs(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -225,7 +238,9 @@ struct WsName {
       if (ea) return one(s, ea);
       if (vz) return one(s, vz);
       if (mk) return one(s, mk);
-      return rl ? one(s, rl) : nullptr;
+      if (rl) return one(s, rl);
+      if (nb) return one(s, nb);
+      return gs ? one(s, gs) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -235,7 +250,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs; using NB = NormalsWs; using GS = GSmoothWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -268,10 +283,14 @@ constexpr WsName kTable[] = {
     WS(EA, pairs), WS(EA, wg), WS(EA, state), WS(EA, part),
     WS(VZ, state), WS(VZ, part), WS(VZ, maxpart), WS(VZ, binsum),
     WS(MK, loss_ray), WS(MK, d_density), WS(MK, points),
-    WS(RL, part), WS(RL, best)};
+    WS(RL, part), WS(RL, best),
+    WS(NB, feat), WS(NB, jac), WS(NB, gf), WS(NB, ghat), WS(NB, u), WS(NB, t0), WS(NB, a0), WS(NB, t1), WS(NB, a2), WS(NB, ones),
+    WS(NB, partial), WS(NB, normals),
+    WS(GS, means_p), WS(GS, feat_p), WS(GS, jac_p), WS(GS, density_p), WS(GS, normals_p), WS(GS, points), WS(GS, points_p),
+    WS(GS, d_normals), WS(GS, d_normals_p), WS(GS, d_density), WS(GS, d_density_p), WS(GS, loss_ray)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL) + sizeof(NB) + sizeof(GS),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -311,6 +330,7 @@ struct rc_handle {
   uint64_t train_gen[RC_MAX_LEVELS] = {};    // layers_gen the training stream of a level was packed at
   uint64_t data_gen = 0;                     // layers_gen data_w was uploaded at
   DevBuf data_w;                             // rc_data_backward: the shader's dense layers on the Flax layout
+  uint64_t nbwd_gen = 0;                     // layers_gen packs.nbwd was packed at
   uint64_t geom_gen = 0;                     // layers_gen geom_w was uploaded at
   DevBuf geom_w;                             // rc_geometry_backward: pred_normals_layer kernel [64][3] + bias [3]
   uint64_t env_gen = 0;                      // layers_gen env_w was uploaded at
@@ -533,6 +553,7 @@ void free_packs(Packs& P) {
   for (DevBuf* b : {&P.shader, &P.fused, &P.fused_front, &P.envmap, &P.t_shader, &P.t_bins, &P.t_taps, &P.t_slice_slf,
                     &P.t_slice_irr}) free_buf(*b);
   for (int l = 0; l < RC_MAX_LEVELS; ++l) { free_buf(P.dens[l]); free_buf(P.train[l]); }
+  free_buf(P.nbwd);
   for (int l = 0; l < RC_MAX_GRID_LEVELS; ++l) {
     free_buf(P.pair[l]);
     for (int g = 0; g < 2; ++g) free_buf(P.cell[g][l]);
@@ -1394,6 +1415,7 @@ int rc_allgather_outputs(rc_handle* h, void* nccl_comm, const rc_outputs* local,
 #include "rc_interlevel_host.inc"
 #include "rc_data_host.inc"
 #include "rc_geometry_host.inc"
+#include "rc_normals_bwd_host.inc"
 #include "rc_mask_host.inc"
 #include "rc_light_host.inc"
 #include "rc_material_bwd_host.inc"

@@ -488,7 +488,8 @@ struct RcWgradArgs {
 int rc_wgrad_waves(int64_t n);
 int rc_wgrad_partial_floats(int nwaves);
 // grads: [W0 K x 64 | b0 64 | W1 64 x 64 | b1 64 | Wout 64 | bout 1], accumulated into
-void rc_launch_wgrad(RcWgradArgs a, int K, float* grads, hipStream_t stream);
+// no_bias: the three bias segments are left as they are (rc_normals_backward: their gradient is an exact zero)
+void rc_launch_wgrad(RcWgradArgs a, int K, float* grads, hipStream_t stream, bool no_bias = false);
 struct RcGridScatterArgs {
   RcGridDev grid;             // geometry of the forward tables
   float* gtable[RC_MAX_GRID_LEVELS];   // gradient tables, same layout as the forward tables
@@ -502,6 +503,44 @@ struct RcGridScatterArgs {
 };
 void rc_launch_grid_scatter(const RcGridScatterArgs& a, hipStream_t stream);
 bool rc_train_prepare();     // LDS opt-in of the scatter kernels (call once outside any stream capture)
+
+// Gradient THROUGH the analytic normals of the last level and the geometry smoothness loss (rc_normals_bwd.hip)
+struct RcNormalsBwdArgs {
+  const float* feat;          // grid features, feature-major [32][ld] (k_hashgrid_fwd)
+  const float* jac;           // [3][32][ld] d feature / d contracted coordinate (k_hashgrid_fwd<F, true>)
+  int64_t n; int64_t ld;
+  const float* wstream;       // [d0 | d1 | out | W1^T | W0^T | d0 | d1] fragments
+  const float* points;        // world-space [n,3]
+  float contract_radius;
+  const float* d_normals;     // [n,3] upstream
+  float* normals;             // [n,3] the analytic normals, or nullptr
+  float* u;                   // point-major [n,32] d L / d (d raw / d feature)
+  float* t0; float* a0; float* t1; float* a2;   // point-major [n,64]
+  float* ones;                // [n] written: 1
+  float* gf;                  // feature-major [32][ld] d raw / d grid feature
+  float* ghat;                // [n,3] d L / d (sum_i J[i][.] gf[i]), contracted axes (x, y, z)
+};
+void rc_launch_normals_bwd(const RcNormalsBwdArgs& a, hipStream_t stream);
+// the table gradients of the trilinear Jacobian: s's dfeat is gf (feature-major), every corner takes
+// precondition gf s_l sum_ax ghat[ax] d w_c / d loc_ax
+void rc_launch_grid_scatter_jac(const RcGridScatterArgs& s, const float* ghat, hipStream_t stream);
+struct RcGSmoothLossArgs {
+  int64_t n; int S;                        // rays, last-level intervals (<= 32)
+  const float* density, * tdist, * directions;   // the training forward's last level
+  const float* normals;                    // SoA [3][n S] analytic normals at the means
+  const float* density_p, * normals_p;     // the same at the perturbed means
+  const float* lossmult;                   // [n] or nullptr (1)
+  float wn3, wd;                           // weight_normals / 3, weight_density: the per-sample loss sum
+  float gn, gd;                            // weight_normals / (3 n S), weight_density / (n S): d loss / d |term|
+  float* weights;                          // [n S] the last level's weights, written
+  float* loss_ray;                         // [n] written
+  float* d_normals, * d_normals_p;         // [n S][3] written, or nullptr (loss only)
+  float* d_density, * d_density_p;         // [n S] written when wd != 0 and d_normals is given
+};
+// means_p (SoA [3][np]) = fl(means + fl(noise * scale)); points / points_p: both as [np][3]
+void rc_launch_gsmooth_points(const float* means, const float* noise, float scale, int64_t np, float* means_p, float* points,
+                              float* points_p, hipStream_t st);
+void rc_launch_gsmooth_loss(const RcGSmoothLossArgs& a, hipStream_t st);
 
 // Spline interlevel loss and d loss / d density of the proposal levels (rc_interlevel.hip)
 struct RcInterlevelArgs {

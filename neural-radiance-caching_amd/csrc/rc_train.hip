@@ -254,7 +254,8 @@ __global__ __launch_bounds__(256) void k_wgrad(RcWgradArgs a) {
 // grads[.] += sum over the workgroup partials in a fixed order.  Output layout: [W0 K x 64 | b0 64 | W1 64 x 64 | b1 64 | Wout 64 | bout 1].
 // A workgroup owns 16 consecutive values; thread (v = tid & 15, s = tid >> 4) adds the partials of waves
 // s, s + 16, ... of the workgroup partials (64-byte row pieces, many loads in flight), the 16 slices are then added in slice order.
-__global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ partial, int nparts, int K, float* __restrict__ grads) {
+// no_bias: the bias values b0, b1, bout are not added (rc_normals_backward leaves those segments untouched).
+__global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ partial, int nparts, int K, float* __restrict__ grads, int no_bias) {
   __shared__ float part[16][17];
   const int v = threadIdx.x & 15, sl = threadIdx.x >> 4;
   const int i = blockIdx.x * 16 + v;
@@ -264,6 +265,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ p
   part[sl][v] = s;
   __syncthreads();
   if (sl != 0 || i > kPartBO) return;
+  if (no_bias && ((i >= kPartB0 && i < kPartW1) || (i >= kPartB1 && i < kPartWO) || i == kPartBO)) return;
   int o;
   if (i < kPartB0) {
     if (i >= K * 64) return;       // rows of the padded 32-row input tile beyond the level's K features
@@ -499,14 +501,14 @@ int rc_wgrad_waves(int64_t n) {
   return (int)((w + 3) / 4 * 4);
 }
 
-void rc_launch_wgrad(RcWgradArgs a, int K, float* grads, hipStream_t stream) {
+void rc_launch_wgrad(RcWgradArgs a, int K, float* grads, hipStream_t stream, bool no_bias) {
   if (a.n <= 0) return;
   const int nwaves = rc_wgrad_waves(a.n);
   const int64_t nsteps = (a.n + 1) / 2;
   a.steps_per_wave = (nsteps + nwaves - 1) / nwaves;
   a.K = K;
   hipLaunchKernelGGL(k_wgrad, dim3(nwaves / 4), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL(k_grad_reduce, dim3((kPartBO + 16) / 16), dim3(256), 0, stream, a.partial, nwaves / 4, K, grads);
+  hipLaunchKernelGGL(k_grad_reduce, dim3((kPartBO + 16) / 16), dim3(256), 0, stream, a.partial, nwaves / 4, K, grads, no_bias ? 1 : 0);
 }
 
 // LDS opt-in of the scatter kernels beyond 64 KiB, once per device (not from inside a stream capture: rc_density_backward

@@ -320,8 +320,9 @@ int grid_l2_regularizer(rc_handle* h, int grid, int set, float mult, float* grad
   return RC_OK;
 }
 
-// Stream of k_density_bwd: the forward fragments of every level followed by W1^T, W0^T.
-int pack_train_stream(rc_handle* h, int level) {
+// Stream of k_density_bwd: the forward fragments of every level followed by W1^T, W0^T.  `replay`: the floats of the two
+// forward layers, appended once more by the caller that runs them again (rc_normals_backward).
+int build_train_stream(rc_handle* h, int level, std::vector<float>& stream, size_t* replay = nullptr) {
   std::string missing;
   const std::string base = "params/Cache/Sampler/MLP_" + std::to_string(level);
   const HostLayer* d0 = need(h, base + "/density_layers_0", missing);
@@ -330,9 +331,10 @@ int pack_train_stream(rc_handle* h, int level) {
   if (!missing.empty()) return fail(h, RC_ERR_MISSING_WEIGHT, "missing weight: " + missing);
   std::vector<Step> s;
   steps_natural(s, d0->in, 0); step_bias(s);
-  std::vector<float> stream = pack_f32(s, {tile_full(d0, 0), tile_full(d0, 1)});
+  stream = pack_f32(s, {tile_full(d0, 0), tile_full(d0, 1)});
   s.clear(); steps_acc(s, 2, 0); step_bias(s);
   append(stream, pack_f32(s, {tile_full(d1, 0), tile_full(d1, 1)}));
+  if (replay) *replay = stream.size();
   append(stream, pack_dot({Col{dout, 0}}, 2, false));
   HostLayer w1t, w0t;
   w1t.in = d1->out; w1t.out = d1->in; w1t.kernel.resize(d1->kernel.size()); w1t.bias.assign(w1t.out, 0.0f);
@@ -342,6 +344,12 @@ int pack_train_stream(rc_handle* h, int level) {
   std::vector<Step> sb; steps_acc(sb, 2, 0);
   append(stream, pack_f32(sb, {tile_full(&w1t, 0, 0, false), tile_full(&w1t, 1, 0, false)}));
   append(stream, pack_f32(sb, {tile_full(&w0t, 0, 0, false)}));
+  return RC_OK;
+}
+
+int pack_train_stream(rc_handle* h, int level) {
+  std::vector<float> stream;
+  if (int rc = build_train_stream(h, level, stream)) return rc;
   return upload(h, h->packs.train[level], pad_stream(stream));
 }
 

@@ -491,6 +491,18 @@ def material_smoothness_noise(loss_key, n_points: int) -> np.ndarray:
     return normal(rng, (int(n_points), 3))
 
 
+def geometry_smoothness_noise(loss_key, n_rays: int, S: int, rc=None):
+    """The noise of geometry_smoothness_loss (train_utils.py:2728-2743) from the key the loss receives: two
+    jax.random.split (:2728, :2741; plain splits, not utils.random_split), the second `rng` being the normal's key, then
+    normal(rng, [n, S, 3]) (:2743; the shape of the last level's means).  With `rc` it is drawn on the device by one
+    rc_prng_fill in normal mode (the same bits and counters; the values an ulp or two from the host twin's, as every
+    normal of rc_prng_fill); otherwise on the host.  The order against a jax run is unverified (no jax here)."""
+    key = split(as_key(loss_key))[1]      # :2728  rng, cur_key = random.split(cur_key)
+    rng = split(key)[0]                   # :2741  rng, cur_key = random.split(cur_key)
+    shape = (int(n_rays), int(S), 3)
+    return rc.prng_fill(rng, shape, mode="normal") if rc is not None else normal(rng, shape)
+
+
 def backward_mask_keys(cur_key):
     """The two keys _compute_backward_mask_loss (internal/train_utils.py:3348-3401) takes from the key per_output_loss_fn
     hands it: (key of the uniform pair, rng of the weights-only model.apply on the backward rays).  :3363 random.split ->

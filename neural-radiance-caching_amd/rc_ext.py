@@ -204,6 +204,10 @@ class rc_geometry_loss(C.Structure):
                                          "pred_normal_mult", "pred_normal_w_grad_weight", "pred_normal_reverse_mult")]
 
 
+class rc_geometry_smoothness(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("noise", "weight_normals", "weight_normals_pred", "weight_density")]
+
+
 class rc_mask_loss(C.Structure):
     _fields_ = [("charb_padding", C.c_float), ("weight_opaque", C.c_float), ("weight_empty", C.c_float),
                 ("zero_masks", C.c_int32)]
@@ -419,6 +423,9 @@ _PROTOTYPES = {
     "rc_data_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _F, _F, _F, _P, _P, _P, _P]),
     "rc_geometry_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, C.POINTER(rc_geometry_loss), _P, _P, _P, _P]),
     "rc_density_regularizer": (C.c_int, [_H, _I32, _F, _P, _P, _P]),
+    "rc_normals_backward": (C.c_int, [_H, _P, _I64, _P, _P, _P, _P]),
+    "rc_geometry_smoothness_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, _P, C.POINTER(rc_geometry_smoothness), _P,
+                                                  _P, _P]),
     "rc_mask_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _F, C.POINTER(rc_mask_loss), _P, _P, _P]),
     "rc_backward_mask_rays": (C.c_int, [_H, _P, _P, _P, _P, _I64, _F, _F, _F, _P, _P, _P, _P, _P]),
     "rc_adam_update": (C.c_int, [_H, C.POINTER(rc_adam_buffer), _I32, C.POINTER(rc_adam_step), _P]),
@@ -1084,6 +1091,54 @@ class RadianceCache:
         mult * x / numel into (allocated zeroed when None); grad=False computes the loss only.
         Returns (grad flat or None, loss [1] cuda tensor)."""
         return self._regularizer(self.lib.rc_density_regularizer, level, (int(level), float(mult)), grad)
+
+    def normals_backward(self, points, d_normals, grads=None):
+        """rc_normals_backward: the gradient THROUGH the analytic normals of the last sampler level: of
+        sum(d_normals * n(points)), n = nan_to_num(-l2_normalize(d raw / d x)), w.r.t. the last level's hash-grid tables
+        and the kernels of its density MLP (the bias segments are left as they are: their gradient is an exact zero).
+        points, d_normals: [n, 3].  Returns (grads, normals): `grads` is the flat float32 cuda buffer of
+        density_grad_layout(num_levels - 1), accumulated into when passed in (zeroed and allocated otherwise)."""
+        torch = self._torch
+        pts = self._dev(points).reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        dn = self._dev(d_normals).reshape(-1, 3).contiguous()
+        if dn.shape[0] != n:
+            raise ValueError("d_normals must have one row per point")
+        grads = self._grad_buffer(grads, self._grad_size(self.cfg.num_levels - 1))
+        normals = torch.empty(n, 3, dtype=torch.float32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_normals_backward(self._h, pts.data_ptr(), n, dn.data_ptr(), grads.data_ptr(),
+                                                 normals.data_ptr(), self._stream()))
+        self._keep = [pts, dn]
+        return grads, normals
+
+    def geometry_smoothness_backward(self, rays: Dict[str, object], jitters, anneal: float, noise, lossmult=None, terms=None,
+                                     grads=None):
+        """rc_geometry_smoothness_backward: train_utils.geometry_smoothness_loss on the last sampler level and its
+        gradient w.r.t. the last density level (density_grad_layout(num_levels - 1)), the analytic normals differentiable
+        at the sample means and at the perturbed means.  noise: [n, S, 3] standard normals
+        (prng.geometry_smoothness_noise); terms: {rc_geometry_smoothness field: value} (weights with the caller's mult
+        applied; noise defaults to 0.1, weight_normals to 0.001, the other two weights to 0).  jitters / anneal /
+        lossmult as data_backward.  grads: the density flat to accumulate into, None (allocated zeroed) or False (the
+        loss only).  Returns (density flat or None, loss [1] cuda tensor); one copy of the term."""
+        r, held, n = self._rays_struct(rays)
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
+        S = self.cfg.sampling_strategy[-1][2]
+        nz = self._dev(noise).reshape(-1).contiguous()
+        if nz.shape[0] != n * S * 3:
+            raise ValueError(f"noise must be [n, {S}, 3]")
+        held["noise"] = nz
+        t = {"noise": 0.1, "weight_normals": 0.001, "weight_normals_pred": 0.0, "weight_density": 0.0}
+        t.update(terms or {})
+        unknown = set(t) - {k for k, _ in rc_geometry_smoothness._fields_}
+        if unknown:
+            raise ValueError(f"unknown geometry smoothness fields {sorted(unknown)}")
+        cfg = rc_geometry_smoothness(**{k: float(v) for k, v in t.items()})
+        flat, loss, stream = self._loss_prologue(self.cfg.num_levels - 1, grads)
+        self._check(self.lib.rc_geometry_smoothness_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal),
+                                                             _ptr(nz), C.byref(cfg), _ptr(flat), loss.data_ptr(), stream))
+        self._keep = [held]
+        return flat, loss
 
     def backward_mask_rays(self, origins, look, u1, u2, shadow_near_max: float = 0.2, normal_eps: float = 1e-2,
                            far: float = 2.0):

@@ -32,9 +32,13 @@ model followed by `jax.lax.pmean(grad, "batch")` across devices and the optimize
   * `cache_stage_grads(rc, rays, rgb, jitters, train_frac)` -> the cache-stage loss: interlevel, data and geometry
     terms counted for "main" and "cache_main", the density-grid regularizer once, with the per-level and shader
     gradients and a loss dict keyed like the reference's losses_flat (the light / material grid regularizer keys left
-    out, see its docstring); with mask_cfg the two mask terms as well.
+    out, see its docstring); with mask_cfg the two mask terms as well; with smoothness_cfg the geometry smoothness term;
+  * `geometry_smoothness_grads(rc, rays, jitters, noise, train_frac)` -> the geometry_smoothness extra loss of the stages
+    without a material and its exact gradient of MLP_2 THROUGH the analytic normals at the sample means and at the
+    perturbed means (rc_geometry_smoothness_backward on rc_normals_backward, DESIGN.md §4.23: second order in the density
+    field); `geometry_smoothness_terms(train_frac)` -> the weights with the extra loss's mult folded in.
 
-These terms are all first order here (the analytic normals are stop-gradiented where they appear).  The
+The terms above geometry_smoothness_grads are all first order here (the analytic normals are stop-gradiented where they appear).  The
 predicted-normal terms follow that first-order reading; whether it matches the reference is not settled (DESIGN.md,
 Oddities: train_utils.py:1060-1070 passes gt="normals_pred", pred="normals" to the forward term, and
 nerf_ngp_yobo.gin:57 disables the analytic normals).
@@ -90,7 +94,7 @@ from typing import Dict, Iterable, List, Optional
 import numpy as np
 
 from . import prng
-from .config import (DataLossConfig, GeometryLossConfig, InterlevelConfig, LightSamplingConfig, MaskLossConfig,
+from .config import (DataLossConfig, GeometryLossConfig, GeometrySmoothnessConfig, InterlevelConfig, LightSamplingConfig, MaskLossConfig,
                      MaterialDataLossConfig, MaterialSmoothnessConfig, OptimizerConfig, TransientDataLossConfig)
 
 
@@ -301,10 +305,33 @@ def mask_grads(rc, rays, jitters, train_frac: float, masks=None, lossmult=None, 
     return {f"MLP_{last}": grads_as_dict(flat, rc.density_grad_layout(last)[0])}, flat, losses
 
 
+def geometry_smoothness_terms(train_frac: float, cfg: GeometrySmoothnessConfig = GeometrySmoothnessConfig(), scale: float = 1.0):
+    """The rc_geometry_smoothness fields of the term at train_frac: the three weights times the extra loss's mult (0
+    before cfg.start_frac of training, as material_smoothness_grads gates its term) and scale; the noise magnitude as it is."""
+    mult = (cfg.mult if train_frac >= cfg.start_frac else 0.0) * scale
+    return dict(noise=cfg.noise, weight_normals=cfg.weight_normals * mult, weight_normals_pred=cfg.weight_normals_pred * mult,
+                weight_density=cfg.weight_density * mult)
+
+
+def geometry_smoothness_grads(rc, rays, jitters, noise, train_frac: float, lossmult=None, flat=None,
+                              cfg: GeometrySmoothnessConfig = GeometrySmoothnessConfig(),
+                              anneal_cfg: InterlevelConfig = InterlevelConfig(), scale: float = 1.0):
+    """The geometry smoothness loss of a batch and its gradient through the analytic normals (and the density, when its
+    weight is set) of the last level (rc_geometry_smoothness_backward).  jitters / train_frac / lossmult as
+    data_grads; noise: [n, S, 3] N(0, 1) (prng.geometry_smoothness_noise); flat: the last level's density flat to
+    accumulate into (allocated zeroed when None).
+    -> ({"MLP_<last>": {name: view}}, flat, loss [1])."""
+    flat, loss = rc.geometry_smoothness_backward(rays, jitters, anneal_at(train_frac, anneal_cfg), noise, lossmult,
+                                                 geometry_smoothness_terms(train_frac, cfg, scale), flat)
+    last = rc.cfg.num_levels - 1
+    return {f"MLP_{last}": grads_as_dict(flat, rc.density_grad_layout(last)[0])}, flat, loss
+
+
 def cache_stage_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, flats=None,
                       geometry_cfg: GeometryLossConfig = GeometryLossConfig(), data_cfg: DataLossConfig = DataLossConfig(),
                       interlevel_cfg: InterlevelConfig = InterlevelConfig(), mask_cfg: Optional[MaskLossConfig] = None,
-                      masks=None, look=None, backward_randoms=None):
+                      masks=None, look=None, backward_randoms=None,
+                      smoothness_cfg: Optional[GeometrySmoothnessConfig] = None, smoothness_noise=None):
     """The hotdog cache stage's loss on a batch and its gradients (train_utils.py:3000-3098).  The interlevel,
     data and geometry terms are computed for "main" and "cache_main" on the same model results, so each counts twice
     (the device calls run once with their mults doubled; the dict reports each copy); the density-grid regularizer
@@ -322,6 +349,10 @@ def cache_stage_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, 
     calls run once with doubled weights.  For the backward term that is a reading, not an identity: the reference draws
     the backward rays of each output key from that key's own rng (:3036), so its two copies are two samples of the same
     expectation, where this function counts one sample twice.
+    smoothness_cfg with smoothness_noise (None: left out, the result is what it is without them): the geometry_smoothness
+    extra loss (geometry_smoothness_grads), added to flats[last] and to the dict as geometry_smoothness.  It counts ONCE: the
+    trainer registers it under "main" only (engine/trainer.py:318-320), and it is in the exclude_list (:3058-3060), so it
+    is not scaled by loss_weight.
     What the sum of the dict is: with the mask terms, the reference's stats["loss"] (:3098) except for
     regularizer/light_grid and regularizer/material_grid (param_regularizer_loss starts its dict with every prefix of
     Config.param_regularizers, :1183; they regularize parameters outside the cache stage's layouts and are not computed
@@ -360,6 +391,12 @@ def cache_stage_grads(rc, rays, rgb, jitters, train_frac: float, lossmult=None, 
         for k in MASK_KEYS:
             if k in m_losses:
                 losses[k] = losses[f"cache_main_{k}"] = m_losses[k] / 2
+    if smoothness_cfg is not None:
+        if smoothness_noise is None:
+            raise ValueError("smoothness_cfg needs smoothness_noise (prng.geometry_smoothness_noise)")
+        _, flats[nl - 1], s_loss = geometry_smoothness_grads(rc, rays, jitters, smoothness_noise, train_frac, lossmult,
+                                                             flats[nl - 1], smoothness_cfg, interlevel_cfg)
+        losses["geometry_smoothness"] = s_loss[0]
     return flats, losses
 
 
