@@ -320,12 +320,6 @@ __device__ __forceinline__ void pair_fetch(const float* __restrict__ tab_a, int 
   }
 }
 
-// v_permlane32_swap: lanes 32-63 of the first operand <-> lanes 0-31 of the second; returns {first, second} afterwards
-__device__ __forceinline__ void swap_halves(float& first, float& second) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(first), __float_as_uint(second), false, false);
-  first = __uint_as_float(r[0]); second = __uint_as_float(r[1]);
-}
-
 // after the loads: the eight corners of this half-wave's level (A on the lower, B on the upper half) in combine order.
 // Lower half: own A corners 0-3 | A corners 4-7 from lane + 32; upper half: B corners 0-3 from lane - 32 | own B corners 4-7.
 template <bool HAS_B>

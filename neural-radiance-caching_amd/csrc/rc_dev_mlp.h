@@ -30,17 +30,21 @@ __device__ __forceinline__ uint32_t pack_top16(float a1, float a0) {
   return __builtin_amdgcn_perm(__float_as_uint(a1), __float_as_uint(a0), 0x07060302u);
 }
 __device__ __forceinline__ float top16(float a) { return __uint_as_float(__float_as_uint(a) & 0xffff0000u); }
-// v[j] == hi[j] + mid[j] + lo[j] exactly (each residual is exact: the top shares its leading bits)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 top16(f32x2 a) { return f32x2{top16(a[0]), top16(a[1])}; }
+// v[j] == hi[j] + mid[j] + lo[j] exactly (each residual is exact: the top shares its leading bits).  The two residual
+// subtractions of a pair are independent: on a 2-vector each pair is one v_pk_add_f32 (full rate, the same IEEE
+// subtraction per element) instead of two v_sub_f32.
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&b)[3]) {
   u32x4 &hi = b[0], &mid = b[1], &lo = b[2];
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
-    const float a0 = v[2 * p], a1 = v[2 * p + 1];
-    hi[p] = pack_top16(a1, a0);
-    const float r0 = a0 - top16(a0), r1 = a1 - top16(a1);
-    mid[p] = pack_top16(r1, r0);
-    const float l0 = r0 - top16(r0), l1 = r1 - top16(r1);
-    lo[p] = pack_top16(l1, l0);
+    const f32x2 a = {v[2 * p], v[2 * p + 1]};
+    hi[p] = pack_top16(a[1], a[0]);
+    const f32x2 r = a - top16(a);
+    mid[p] = pack_top16(r[1], r[0]);
+    const f32x2 l = r - top16(r);
+    lo[p] = pack_top16(l[1], l[0]);
   }
 }
 __device__ __forceinline__ f32x16 mfma_bf16(const u32x4& a, const u32x4& b, const f32x16& c) {
@@ -579,6 +583,21 @@ __device__ __forceinline__ float softplus(float x) {
   return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
 }
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
+// Two values that both half-waves hold alike (xa, xb identical on lanes j and j + 32), each evaluated ONCE: the lower
+// half-wave evaluates xa while the upper one evaluates xb, one v_permlane32_swap hands both results to both halves.
+// Every value goes through exactly the operations of the plain function, so ya == f(xa), yb == f(xb) bit for bit.
+template <class F>
+__device__ __forceinline__ void eval_pair(F f, int h, float xa, float xb, float& ya, float& yb) {
+  const float y = f(h ? xb : xa);
+  ya = y; yb = y;
+  swap_halves(ya, yb);        // ya: lanes 32-63 take f(xa) of lanes 0-31; yb: lanes 0-31 take f(xb) of lanes 32-63
+}
+__device__ __forceinline__ void softplus_pair(int h, float xa, float xb, float& ya, float& yb) {
+  eval_pair([](float x) { return softplus(x); }, h, xa, xb, ya, yb);
+}
+__device__ __forceinline__ void sigmoid_pair(int h, float xa, float xb, float& ya, float& yb) {
+  eval_pair([](float x) { return sigmoidf(x); }, h, xa, xb, ya, yb);
+}
 
 #ifndef RC_DEV_CONTRACT3
 #define RC_DEV_CONTRACT3
@@ -651,6 +670,7 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
   RC_TSTAMP(0);
   // ---- small heads tile on the feature (the bottleneck is folded into its consumers, see kShActSteps)
   float rough, tint[3], ad[3], idf[3];
+  float tint2_raw, idf2_raw;     // the two heads whose transcendental waits for a partner (IBRDF tail, SLF tail)
   // split build: the pieces of the 48 feature steps, split ONCE for the three layers that read the feature as their B
   // operand (heads, 85-step layer, first IBRDF layer).  They stay live from here to the first IBRDF layer, so rule 2
   // holds for them by construction.
@@ -662,15 +682,20 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     if constexpr (kRcSplit) mlp_layer_x<1, 49, F0 + ShaderFrags::F_H, NF, 6, true>(ws, act, acc, fpc);
     else mlp_layer<1, 49, F0 + ShaderFrags::F_H, NF>(ws, act, acc);
     // by accumulator register (same on both half-waves): 0 roughness, 1-3 tint, 4-6 ambient irradiance, 7-9 irradiance
-    rough = softplus(acc[0][0] + k.roughness_bias);                       // nerf.py:633-634
-    tint[0] = sigmoidf(acc[0][1]); tint[1] = sigmoidf(acc[0][2]); tint[2] = sigmoidf(acc[0][3]);   // :976
-    const float ar[3] = {acc[0][4], acc[0][5], acc[0][6]};
-    const float ir[3] = {acc[0][7], acc[0][8], acc[0][9]};
+    // Lanes j and j + 32 hold the same sample, so each transcendental is evaluated once, in pairs (softplus_pair):
+    // (rough, ad0) (ad1, ad2) (idf0, idf1) here, (idf2, amb0) (amb1, amb2) behind the SLF tail, (tint0, tint1) here and
+    // (tint2, ibrdf) behind the IBRDF tail.  Bias adds and clamps stay per value.
+    float sp_ad[3], sp_idf[2];
+    softplus_pair(h, acc[0][0] + k.roughness_bias, acc[0][4] + k.ambient_bias, rough, sp_ad[0]);     // nerf.py:633-634
+    softplus_pair(h, acc[0][5] + k.ambient_bias, acc[0][6] + k.ambient_bias, sp_ad[1], sp_ad[2]);
+    softplus_pair(h, acc[0][7] + k.irradiance_bias, acc[0][8] + k.irradiance_bias, sp_idf[0], sp_idf[1]);
+    sigmoid_pair(h, acc[0][1], acc[0][2], tint[0], tint[1]);                                         // :976
+    tint2_raw = acc[0][3];
+    idf2_raw = acc[0][9] + k.irradiance_bias;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      ad[c] = fminf(fmaxf(softplus(ar[c] + k.ambient_bias), 0.0f), k.rgb_max);      // nerf.py:965-969
-      idf[c] = fminf(fmaxf(softplus(ir[c] + k.irradiance_bias), 0.0f), k.rgb_max);  // nerf.py:1008-1012
-    }
+    for (int c = 0; c < 3; ++c) ad[c] = fminf(fmaxf(sp_ad[c], 0.0f), k.rgb_max);                     // nerf.py:965-969
+#pragma unroll
+    for (int c = 0; c < 2; ++c) idf[c] = fminf(fmaxf(sp_idf[c], 0.0f), k.rgb_max);                   // nerf.py:1008-1012
   }
   RC_TSTAMP(1);
   // ---- normals, n.(-v), reflection direction, IDE
@@ -736,7 +761,7 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     mlp_layer_h<2, 2, true, F0 + ShaderFrags::F_I1, NF>(ws, hi, ib);
     float o[1], nokeep[1];
     dot_out1<2, 1, F0 + ShaderFrags::F_IO, NF>(ws, ib, o, nokeep);     // output_integrated_brdf_layer on relu(ib)
-    ibrdf = sigmoidf(o[0] + 1.0986123f);        // + log(3), nerf.py:481
+    sigmoid_pair(h, tint2_raw, o[0] + 1.0986123f, tint[2], ibrdf);        // + log(3), nerf.py:481
   }
   RC_TSTAMP(4);
   // ---- SLF trunk: layer_1, layer_2, layer_bottleneck (x part accumulates onto the input part)
@@ -762,8 +787,12 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     RC_TSTAMP(7);
     float o[3], nokeep[1];
     dot_out1<4, 3, F0 + ShaderFrags::F_SO, NF>(ws, skip, o, nokeep);   // output_ambient_rgb_layer on relu(layer_bottleneck)
+    float sp_idf2, sp_amb[3];
+    softplus_pair(h, idf2_raw, o[0] + k.slf_ambient_bias, sp_idf2, sp_amb[0]);
+    softplus_pair(h, o[1] + k.slf_ambient_bias, o[2] + k.slf_ambient_bias, sp_amb[1], sp_amb[2]);
+    idf[2] = fminf(fmaxf(sp_idf2, 0.0f), k.rgb_max);                                            // nerf.py:1008-1012
 #pragma unroll
-    for (int c = 0; c < 3; ++c) amb[c] = fmaxf(softplus(o[c] + k.slf_ambient_bias), 0.0f);      // slf.py:1053-1059
+    for (int c = 0; c < 3; ++c) amb[c] = fmaxf(sp_amb[c], 0.0f);                                // slf.py:1053-1059
   }
   RC_TSTAMP(8);
   ShadeOut o;

@@ -81,6 +81,24 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
 #pragma unroll
   for (int k = 0; k < N; ++k) v[k] = lane63(v[k]);
 }
+// 2 N sums over 32 lanes each in N registers: v[k] holds channel 2 k on lanes 0-31 and channel 2 k + 1 on lanes 32-63;
+// tot[c] is the sum of channel c, broadcast.  Steps 0-4 of wave_sum_step add the two 16-lane rows of each half-wave in
+// the order wave_sum adds rows 0 and 1 (step 4, row_bcast:15 into rows 1 and 3: r1 + r0 and r3 + r2); the totals are
+// read from lanes 31 and 63.  Against wave_sum_n on registers whose lanes 32-63 are zeros only the trailing (0 + 0) + sum
+// of step 5 is missing, which can do no more than turn a -0 total into +0.
+template <int N>
+__device__ __forceinline__ void wave_sum32_pairs(float (&v)[N], float (&tot)[2 * N]) {
+#pragma unroll
+  for (int st = 0; st < 5; ++st) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = wave_sum_step(v[k], st);
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    tot[2 * k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[k]), 31));
+    tot[2 * k + 1] = lane63(v[k]);
+  }
+}
 __device__ __forceinline__ float wave_max(float v) {
   return lane63(wave_scan_op(v, -INFINITY, [](float a, float b) { return fmaxf(a, b); }));
 }

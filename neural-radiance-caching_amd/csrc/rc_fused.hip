@@ -423,31 +423,38 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   // every weighted sum of the ray in one batched butterfly
   enum { V_ACC = 0, V_RGB = 1, V_AD = 4, V_IDF = 7, V_IS = 10, V_TINT = 13, V_DIF = 16, V_IND = 19, V_MEAN = 22, V_RD = 25,
          V_LD = 26, V_NP = 27, V_NG = 30, V_LOGT = 33, V_COUNT = 34 };
-  float v[V_COUNT];
-  v[V_ACC] = wnf;
+  // The 32 samples sit on lanes 0-31 and every factor below is the same on lanes j and j + 32, so two channels share a
+  // register: channel 2 k on the lower half-wave, 2 k + 1 on the upper one, both weighted with the lower half's wnf
+  // (wave_sum32_pairs: 17 registers and 5 steps instead of 34 and 6, each sum in k_composite's order).
+  static_assert(V_COUNT % 2 == 0, "channels are reduced in pairs");
+  float x[V_COUNT];
+  x[V_ACC] = 1.0f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float v_rgb = act_s ? so.rgb[c] : 0.0f, v_ad = act_s ? so.ad[c] : 0.0f, v_id = act_s ? so.idf[c] : 0.0f;
-    const float v_is = act_s ? so.is[c] : 0.0f, v_t = act_s ? so.tint[c] : 0.0f;
-    v[V_RGB + c] = wnf * v_rgb;
-    v[V_AD + c] = wnf * v_ad;
-    v[V_IDF + c] = wnf * v_id;
-    v[V_IS + c] = wnf * v_is;
-    v[V_TINT + c] = wnf * v_t;
-    v[V_DIF + c] = wnf * (v_ad + v_id);
-    v[V_IND + c] = wnf * (v_id + v_is);
+    x[V_RGB + c] = so.rgb[c];
+    x[V_AD + c] = so.ad[c];
+    x[V_IDF + c] = so.idf[c];
+    x[V_IS + c] = so.is[c];
+    x[V_TINT + c] = so.tint[c];
+    x[V_DIF + c] = so.ad[c] + so.idf[c];
+    x[V_IND + c] = so.idf[c] + so.is[c];
   }
-  v[V_MEAN] = wnf * mx; v[V_MEAN + 1] = wnf * my; v[V_MEAN + 2] = wnf * mz;
-  v[V_RD] = wnf * sqrtf((ox - mx) * (ox - mx) + (oy - my) * (oy - my) + (oz - mz) * (oz - mz));
-  v[V_LD] = 0.0f;
+  x[V_MEAN] = mx; x[V_MEAN + 1] = my; x[V_MEAN + 2] = mz;
+  x[V_RD] = sqrtf((ox - mx) * (ox - mx) + (oy - my) * (oy - my) + (oz - mz) * (oz - mz));
+  x[V_LD] = 0.0f;
   if (a.lights) {
     const float lx = a.lights[3 * ray], ly = a.lights[3 * ray + 1], lz = a.lights[3 * ray + 2];
-    v[V_LD] = wnf * sqrtf((lx - mx) * (lx - mx) + (ly - my) * (ly - my) + (lz - mz) * (lz - mz));
+    x[V_LD] = sqrtf((lx - mx) * (lx - mx) + (ly - my) * (ly - my) + (lz - mz) * (lz - mz));
   }
-  v[V_NP] = wnf * npx; v[V_NP + 1] = wnf * npy; v[V_NP + 2] = wnf * npz;
-  v[V_NG] = wnf * ngx; v[V_NG + 1] = wnf * ngy; v[V_NG + 2] = wnf * ngz;
-  v[V_LOGT] = act_s ? wnf * logf(0.5f * (t0 + t1)) : 0.0f;
-  wave_sum_n<V_COUNT>(v);
+  x[V_NP] = npx; x[V_NP + 1] = npy; x[V_NP + 2] = npz;
+  x[V_NG] = ngx; x[V_NG + 1] = ngy; x[V_NG + 2] = ngz;
+  x[V_LOGT] = logf(0.5f * (t0 + t1));
+  float wnf2 = wnf, wnf_hi = wnf;
+  swap_halves(wnf2, wnf_hi);                    // wnf2: lanes 32-63 take the weights of lanes 0-31
+  float vp[V_COUNT / 2], v[V_COUNT];
+#pragma unroll
+  for (int k = 0; k < V_COUNT / 2; ++k) vp[k] = wnf2 * (h ? x[2 * k + 1] : x[2 * k]);
+  wave_sum32_pairs<V_COUNT / 2>(vp, v);
   const float accw = v[V_ACC];
   const float bgw = fmaxf(0.0f, 1.0f - accw) * a.bg;
   store3(RC_OUT_RGB, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);

@@ -30,6 +30,12 @@ __device__ __forceinline__ float rc_safe_exp(float x) {
   return expf(x > 70.0f ? 70.0f : (x < -RC_FMAX ? -RC_FMAX : x));
 }
 
+// v_permlane32_swap: lanes 32-63 of the first operand <-> lanes 0-31 of the second; returns {first, second} afterwards
+__device__ __forceinline__ void swap_halves(float& first, float& second) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(first), __float_as_uint(second), false, false);
+  first = __uint_as_float(r[0]); second = __uint_as_float(r[1]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Hash grid
 // ---------------------------------------------------------------------------------------------
