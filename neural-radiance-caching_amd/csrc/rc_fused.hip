@@ -24,6 +24,10 @@ using namespace rcfused;
 
 namespace {
 
+// act steps [32, 48) of the one-wave kernel: the appearance features, where shader_tile reads them (the two-wave kernel
+// still parks them at kAppTmp: its density MLP runs on another layout)
+constexpr int kAppSteps = 32;
+
 // Density MLP of a proposal level on 64 samples (two point-tiles); returns the raw density of
 // sample `lane`.  K grid features of this lane's sample are in f[].
 template <int K, int FB, int NF, class WS>
@@ -274,9 +278,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
         }
       }
     }
-    // feature k of point j -> step base + k/2, lane j + 32 (k & 1): density features feed D0 at [0,16),
-    // appearance features wait at [kAppTmp, kAppTmp + 16) until the density MLP is through
-    const int base = h == 0 ? 0 : kAppTmp;
+    // feature k of point j -> step base + k/2, lane j + 32 (k & 1): density features feed D0 at [0,16), appearance
+    // features go straight to the shader's steps [kAppSteps, kAppSteps + 16): the level-2 density MLP reads [0, 17),
+    // hands D0 -> D1 over in registers and parks its hidden feature at [0, 32) (the fp32 chain in both arithmetics), the
+    // backward pass reads the Jacobian at kJac and up -- nothing touches [32, 48) before the shader does
+    const int base = h == 0 ? 0 : kAppSteps;
 #pragma unroll
     for (int k = 0; k < 32; ++k) act_wave[(base + (k >> 1)) * 64 + j + 32 * (k & 1)] = f[k];
     act[16 * 64] = h == 0 ? 1.0f : 0.0f;
@@ -370,6 +376,9 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   RC_FSTAMP(9);
   if constexpr (FRONT) {
     // hand-over to the stages behind the sampler, in the layouts of the launch-per-stage front end
+    // (the buffer pointers as one batch of scalar loads in front of the first store, as in the compositing tail below)
+    asm volatile("" :: "s"(a.f_tdist), "s"(a.f_density), "s"(a.f_means), "s"(a.f_normals_pred), "s"(a.f_normals_grad),
+                 "s"(a.f_hbuf), "s"(a.f_app), "s"(a.n));
     if (ray_ok) {
       const int64_t np = a.n * 32, p = ray * 32 + j;
       for (int e2 = lane; e2 <= 32; e2 += 64) a.f_tdist[ray * 33 + e2] = s_td[e2];
@@ -385,25 +394,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
 #pragma unroll
       for (int s = 0; s < 32; ++s) hb[s * 64] = act[s * 64];                 // hidden feature, accumulator layout
 #pragma unroll
-      for (int s = 0; s < 16; ++s) a.f_app[(int64_t)(2 * s + h) * np + p] = act[(kAppTmp + s) * 64];   // feature 2 s + h of point j
+      for (int s = 0; s < 16; ++s) a.f_app[(int64_t)(2 * s + h) * np + p] = act[(kAppSteps + s) * 64];   // feature 2 s + h of point j
     }
     return;
   }
-  if constexpr (EXPORT) {
-    if (ray_ok) {
-      const int64_t np = a.n * 32, p = ray * 32 + j;
-      for (int e2 = lane; e2 <= 32; e2 += 64) a.f_tdist[ray * 33 + e2] = s_td[e2];
-      if (h == 0) {
-        a.f_density[p] = density;
-        a.f_means[p] = mx; a.f_means[np + p] = my; a.f_means[2 * np + p] = mz;
-        a.f_normals_pred[p] = npx; a.f_normals_pred[np + p] = npy; a.f_normals_pred[2 * np + p] = npz;
-      }
-    }
-  }
   // ------------------------------------------------------------------ shader on the 32 samples
-#pragma unroll
-  for (int s = 0; s < 16; ++s) act[(32 + s) * 64] = act[(kAppTmp + s) * 64];
-  act[48 * 64] = h == 0 ? 1.0f : 0.0f;
+  act[48 * 64] = h == 0 ? 1.0f : 0.0f;      // the appearance features are at [32, 48) since the level-2 scatter
 #if defined(RC_ABL) && RC_ABL == 12
   ShadeOut so;
   for (int c = 0; c < 3; ++c) { so.rgb[c] = act[c * 64]; so.ad[c] = npx; so.idf[c] = npy; so.is[c] = npz; so.tint[c] = density; }
@@ -416,10 +412,39 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   // ------------------------------------------------------------------ volume compositing (k_composite)
   const bool act_s = lane < 32;
   const float wnf = alpha_weight(density, t0, t1, dnorm, act_s, lane);
+  // The output pointers the tail stores through, fetched as ONE batch of scalar loads in front of the sums: read where
+  // they are used, each store opened with its own s_load, a wait for it and a branch -- a scalar-cache round trip per
+  // output on the ray's chain.  The loads go out here (fence below), the values are pinned in scalar registers by the
+  // empty asm behind the butterfly, whose vector work covers their latency; the stores then find them there.
+  constexpr int kOutPtrs = RC_OUT_LIGHT_DISTS + 1;     // every output of the primary-ray pass: ids [0, kOutPtrs)
+  float* op[kOutPtrs];
+#pragma unroll
+  for (int i = 0; i < kOutPtrs; ++i) op[i] = a.out.ptr[i];
+  if constexpr (EXPORT) {
+    // its stores open a block of their own, behind which the loads above would sink: pinned in front of it, with the
+    // workspace pointers
+    asm volatile("" :: "s"(a.f_tdist), "s"(a.f_density), "s"(a.f_means), "s"(a.f_normals_pred), "s"(a.n), "s"(op[0]), "s"(op[1]),
+                 "s"(op[2]), "s"(op[3]), "s"(op[4]), "s"(op[5]), "s"(op[6]), "s"(op[7]), "s"(op[8]), "s"(op[9]), "s"(op[10]), "s"(op[11]),
+                 "s"(op[12]), "s"(op[13]), "s"(op[14]), "s"(op[15]), "s"(op[16]), "s"(op[17]), "s"(op[18]));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // (EXPORT) the last level's per-sample results, behind the shader: every value is still live for the compositing, and
+  // no scalar load of the shader then falls between the kernel's first and last store
+  if constexpr (EXPORT) {
+    if (ray_ok) {
+      const int64_t np = a.n * 32, p = ray * 32 + j;
+      for (int e2 = lane; e2 <= 32; e2 += 64) a.f_tdist[ray * 33 + e2] = s_td[e2];
+      if (h == 0) {
+        a.f_density[p] = density;
+        a.f_means[p] = mx; a.f_means[np + p] = my; a.f_means[2 * np + p] = mz;
+        a.f_normals_pred[p] = npx; a.f_normals_pred[np + p] = npy; a.f_normals_pred[2 * np + p] = npz;
+      }
+    }
+  }
   auto store3 = [&](int id, float x, float y, float z) {
-    if (lane == 0 && ray_ok && a.out.ptr[id]) { a.out.ptr[id][3 * ray] = x; a.out.ptr[id][3 * ray + 1] = y; a.out.ptr[id][3 * ray + 2] = z; }
+    if (lane == 0 && ray_ok && op[id]) { op[id][3 * ray] = x; op[id][3 * ray + 1] = y; op[id][3 * ray + 2] = z; }
   };
-  auto store1 = [&](int id, float x) { if (lane == 0 && ray_ok && a.out.ptr[id]) a.out.ptr[id][ray] = x; };
+  auto store1 = [&](int id, float x) { if (lane == 0 && ray_ok && op[id]) op[id][ray] = x; };
   // every weighted sum of the ray in one batched butterfly
   enum { V_ACC = 0, V_RGB = 1, V_AD = 4, V_IDF = 7, V_IS = 10, V_TINT = 13, V_DIF = 16, V_IND = 19, V_MEAN = 22, V_RD = 25,
          V_LD = 26, V_NP = 27, V_NG = 30, V_LOGT = 33, V_COUNT = 34 };
@@ -455,6 +480,12 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
 #pragma unroll
   for (int k = 0; k < V_COUNT / 2; ++k) vp[k] = wnf2 * (h ? x[2 * k + 1] : x[2 * k]);
   wave_sum32_pairs<V_COUNT / 2>(vp, v);
+  // all pointers are in scalar registers here: one wait for the batch, and the stores below use these values
+  static_assert(kOutPtrs == 19, "the pin below names every pointer");
+  asm volatile("" :: "s"(op[0]), "s"(op[1]), "s"(op[2]), "s"(op[3]), "s"(op[4]), "s"(op[5]), "s"(op[6]), "s"(op[7]), "s"(op[8]),
+               "s"(op[9]), "s"(op[10]), "s"(op[11]), "s"(op[12]), "s"(op[13]), "s"(op[14]), "s"(op[15]), "s"(op[16]), "s"(op[17]),
+               "s"(op[18]));
+  __builtin_amdgcn_sched_barrier(0);
   const float accw = v[V_ACC];
   const float bgw = fmaxf(0.0f, 1.0f - accw) * a.bg;
   store3(RC_OUT_RGB, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
@@ -488,8 +519,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
     if (lane < 3 && ray_ok) {
       const float ps = a.pct[lane] / 100.0f;
       const float v = interp1(ps, s_cw, s_td, 33);
-      const int id = lane == 0 ? RC_OUT_DISTANCE_PERCENTILE_5 : (lane == 1 ? RC_OUT_DISTANCE_MEDIAN : RC_OUT_DISTANCE_PERCENTILE_95);
-      if (a.out.ptr[id]) a.out.ptr[id][ray] = v;
+      float* const dst = lane == 0 ? op[RC_OUT_DISTANCE_PERCENTILE_5] : (lane == 1 ? op[RC_OUT_DISTANCE_MEDIAN] : op[RC_OUT_DISTANCE_PERCENTILE_95]);
+      if (dst) dst[ray] = v;
     }
   }
   RC_FSTAMP(11);
