@@ -13,7 +13,9 @@
 // weight fragment feeds two MFMAs there.
 //
 // Same arithmetic, in the same order, as the stand-alone kernels (rc_sample.hip, rc_hashgrid.hip,
-// rc_mlp.hip), whose reference citations apply; this file only changes where the data lives.
+// rc_mlp.hip), whose reference citations apply; this file only changes where the data lives.  Proposal levels 0 and 1
+// are two calls of proposal_level; resample, mean_of, density_of, level2_combine, export_samples and the phases shared
+// with the two-wave kernel (analytic_normal, the distance statistics, store3 / store1) are rc_fused_common.h's.
 // Used for the cache pass on primary rays without resampling (BASELINE configs 1, 2, 4); secondary
 // rays, resampling and the material stage use the stand-alone kernels.
 #include "rc_fused_common.h"
@@ -27,6 +29,13 @@ namespace {
 // act steps [32, 48) of the one-wave kernel: the appearance features, where shader_tile reads them (the two-wave kernel
 // still parks them at kAppTmp: its density MLP runs on another layout)
 constexpr int kAppSteps = 32;
+
+// Operands of the empty asm statements that pin pointers in scalar registers (one asm statement holding all operands of
+// a pin: that is what makes all of them live together): the compositing tail's copies op[] of a.out.ptr[0 .. 18], and the workspace pointers of
+// export_samples with the ray count
+#define RC_OUT_PINS "s"(op[0]), "s"(op[1]), "s"(op[2]), "s"(op[3]), "s"(op[4]), "s"(op[5]), "s"(op[6]), "s"(op[7]), "s"(op[8]), "s"(op[9]), \
+                    "s"(op[10]), "s"(op[11]), "s"(op[12]), "s"(op[13]), "s"(op[14]), "s"(op[15]), "s"(op[16]), "s"(op[17]), "s"(op[18])
+#define RC_EXPORT_PINS "s"(a.f_tdist), "s"(a.f_density), "s"(a.f_means), "s"(a.f_normals_pred), "s"(a.n)
 
 // Density MLP of a proposal level on 64 samples (two point-tiles); returns the raw density of
 // sample `lane`.  K grid features of this lane's sample are in f[].
@@ -60,6 +69,54 @@ __device__ __forceinline__ float density_level64(const WS& ws, float* act_wave, 
   return tile == 0 ? out[0][0] : out[1][0];
 }
 
+// Proposal level LEVEL (0, 1) on the 64 intervals in s_td, K grid levels, density MLP at fragment FB: sample mean ->
+// contract -> lookup -> density MLP -> the alpha weight of sample `lane`
+template <int LEVEL, int K, int FB, int NF, class WS>
+__device__ __forceinline__ float proposal_level(const RcFusedArgs& a, const WS& ws, float* act_wave, const Ray& r, const float* s_td, int lane,
+                                                unsigned long long* stamps) {
+  float mx, my, mz, t0, t1;
+  mean_of(r, s_td, lane, mx, my, mz, t0, t1);
+  float cx = mx, cy = my, cz = mz;
+  contract3(cx, cy, cz, a.contract_radius);
+  const RcGridDev& g = a.grid[LEVEL];
+  float f[K];
+  {
+    const float ux = unit_box(g.bbox, cx), uy = unit_box(g.bbox, cy), uz = unit_box(g.bbox, cz);
+#if defined(RC_ABL) && RC_ABL == 11
+    for (int l = 0; l < K; ++l) f[l] = ux * (float)l + uy - uz;
+#else
+    // the cell-table loads of 16 bytes (dense levels) + the corner loads (hashed levels) in flight before the first
+    // combine: 6 + 24 on level 0, 6 + 32 on level 1.
+    // The kind of level l is the compile-time l < kFusedDense (fused_geometry_ok), never the run-time L.dense: as two arms
+    // of a branch that fill the same C[l], the hashed arm is a fall-through successor of the dense one for the compiler's
+    // wait-count pass and opened with s_waitcnt vmcnt(0) -- one memory round trip per hashed level instead of one in all
+    Corners<1> C[K];
+    if constexpr (LEVEL == 0) RC_FSTAMP(12);
+#pragma unroll
+    for (int l = 0; l < K; ++l) {
+      const RcGridLevel& L = g.lvl[l];
+      if (l < kFusedDense) grid_fetch_cell(a.cell_table[LEVEL][l], L.size, ux, uy, uz, C[l]);
+      else grid_fetch<1, true>(L.table, L.size, L.mask, 0u, false, ux, uy, uz, C[l]);
+    }
+    if constexpr (LEVEL == 0) RC_FSTAMP_NOWAIT(13);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int l = 0; l < K; ++l) {
+      float v[1], jd[1];
+      grid_combine<1, false>(C[l], v, jd);
+      f[l] = v[0] * g.precondition;
+    }
+#endif
+  }
+  RC_FSTAMP(LEVEL == 0 ? 2 : 5);
+#if defined(RC_ABL) && RC_ABL == 13
+  const float raw = f[0] + f[K - 1];
+#else
+  const float raw = density_level64<K, FB, NF>(ws, act_wave, lane, f);
+#endif
+  return alpha_weight(density_of(a, raw, cx, cy, cz, g.bbox), t0, t1, r.dnorm, true, lane);
+}
+
 // FRONT: stop behind the last proposal level (density MLP + appearance lookup) and hand the per-sample results to the
 // stages of the time-resolved cache; the stream then ends at F_SH.
 // EXPORT: the full kernel that also leaves the last level's per-sample results (fence posts, density, sample means,
@@ -76,10 +133,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   if (!ray_ok) ray = a.n - 1;                      // keep the wave in the workgroup's lockstep
   float* ring = lds_dyn;
   float* act_wave = lds_dyn + kRingFloats + wave * (kShActSteps * 64);
-  float* scr = lds_dyn + kRingFloats + kWaves * (kShActSteps * 64) + wave * kScratch;
-  float* s_sd[2] = {scr, scr + 68};
-  float* s_td = scr + 2 * 68; float* s_cw = scr + 3 * 68; float* s_c = scr + 4 * 68; float* s_v = scr + 5 * 68;
-  float* s_out = scr + 6 * 68;
+  const Scratch s = carve_scratch(lds_dyn + kRingFloats + kWaves * (kShActSteps * 64) + wave * kScratch);
   WStream ws(a.wstream, ring, lane, wave);
 #ifdef RC_STAMPS
   unsigned long long stamps[16];
@@ -88,151 +142,34 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   RC_FSTAMP(0);
   ws_begin<NF>(ws);
 
-  const float ox = a.origins[3 * ray], oy = a.origins[3 * ray + 1], oz = a.origins[3 * ray + 2];
-  const float dx = a.directions[3 * ray], dy = a.directions[3 * ray + 1], dz = a.directions[3 * ray + 2];
-  const float near = a.near[ray], far = a.far[ray];
-  const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-
-  // resample S intervals from (prev sdist in s_prev [P+1], logit per bin), produce tdist in s_td and
-  // the sample mean of interval `idx` (all lanes)
-  auto resample = [&](int level, int P, int S, float logit, const float* s_prev) {
-    const bool hasj = a.jitter[level] != nullptr;
-    const float jit = hasj ? a.jitter[level][ray] : 0.0f;
-#if defined(RC_ABL) && RC_ABL == 14
-    for (int e2 = lane; e2 <= S; e2 += 64) s_out[e2] = (float)e2 / (float)S + 1e-9f * logit;
-    lds_sync<false>();
-#else
-    sample_intervals_wave<false>(logit, P, S, a.us[level], hasj, jit, s_prev, s_cw, s_c, s_v, s_out, lane);
-#endif
-    if constexpr (FRONT) {
-      if (a.use_raydist) {      // TransientNeRFModel samples its primary rays in power-ladder distance (models.py:122, 183-191)
-        const float s_near = power_ladder(near, a.raydist_p, a.raydist_premult), s_far = power_ladder(far, a.raydist_p, a.raydist_premult);
-        for (int e2 = lane; e2 <= S; e2 += 64)
-          s_td[e2] = inv_power_ladder(s_out[e2] * s_far + (1.0f - s_out[e2]) * s_near, a.raydist_p, a.raydist_premult, a.y_max);
-        lds_sync<false>();
-        return;
-      }
-    }
-    for (int e2 = lane; e2 <= S; e2 += 64) s_td[e2] = s_out[e2] * far + (1.0f - s_out[e2]) * near;   // coord.py:259-260
-    lds_sync<false>();
-  };
-  auto mean_of = [&](int idx, float& mx, float& my, float& mz, float& t0, float& t1) {
-    t0 = s_td[idx]; t1 = s_td[idx + 1];
-    const float sm = t0 + t1, d = t1 - t0;
-    const float ratio = (d * d) / fmaxf(RC_EPS * RC_EPS, 3.0f * (sm * sm) + d * d);
-    const float tm = sm * (0.5f + ratio);
-    mx = dx * tm + ox; my = dy * tm + oy; mz = dz * tm + oz;
-  };
-  auto density_of = [&](float raw, float cx, float cy, float cz, float bbox) {
-    const bool inside = (cx > -bbox) & (cx < bbox) & (cy > -bbox) & (cy < bbox) & (cz > -bbox) & (cz < bbox);
-    const float d = rc_safe_exp(raw + a.density_bias);
-    return inside ? d : 0.0f;
-  };
+  const Ray r = load_ray(a, ray);
 
   // ------------------------------------------------------------------ level 0 (P = 1, S = 64)
-  if (lane == 0) { s_sd[0][0] = 0.0f; s_sd[0][1] = 1.0f; }
+  if (lane == 0) { s.sd[0][0] = 0.0f; s.sd[0][1] = 1.0f; }
   lds_sync<false>();
-  resample(0, 1, 64, a.anneal * safe_log(1.0f + a.padding), s_sd[0]);
+  resample<FRONT>(a, r, ray, s, lane, 0, 1, 64, a.anneal * safe_log(1.0f + a.padding), s.sd[0]);
   RC_FSTAMP(1);
-  float w;
-  {
-    float mx, my, mz, t0, t1;
-    mean_of(lane, mx, my, mz, t0, t1);
-    float cx = mx, cy = my, cz = mz;
-    contract3(cx, cy, cz, a.contract_radius);
-    float f[6];
-    {
-      const float ux = unit_box(a.grid[0].bbox, cx), uy = unit_box(a.grid[0].bbox, cy), uz = unit_box(a.grid[0].bbox, cz);
-#if defined(RC_ABL) && RC_ABL == 11
-      for (int l = 0; l < 6; ++l) f[l] = ux * (float)l + uy - uz;
-#else
-      // 6 cell-table loads of 16 bytes (dense levels) + 24 corner loads (hashed levels) in flight before the first combine.
-      // The kind of level l is the compile-time l < kFusedDense (fused_geometry_ok), never the run-time L.dense: as two arms
-      // of a branch that fill the same C[l], the hashed arm is a fall-through successor of the dense one for the compiler's
-      // wait-count pass and opened with s_waitcnt vmcnt(0) -- one memory round trip per hashed level instead of one in all
-      Corners<1> C[6];
-      RC_FSTAMP(12);
-#pragma unroll
-      for (int l = 0; l < 6; ++l) {
-        const RcGridLevel& L = a.grid[0].lvl[l];
-        if (l < kFusedDense) grid_fetch_cell(a.cell_table[0][l], L.size, ux, uy, uz, C[l]);
-        else grid_fetch<1, true>(L.table, L.size, L.mask, 0u, false, ux, uy, uz, C[l]);
-      }
-      RC_FSTAMP_NOWAIT(13);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int l = 0; l < 6; ++l) {
-        float v[1], jd[1];
-        grid_combine<1, false>(C[l], v, jd);
-        f[l] = v[0] * a.grid[0].precondition;
-      }
-#endif
-    }
-    RC_FSTAMP(2);
-#if defined(RC_ABL) && RC_ABL == 13
-    const float raw = f[0] + f[5];
-#else
-    const float raw = density_level64<6, F_L0, NF>(ws, act_wave, lane, f);
-#endif
-    w = alpha_weight(density_of(raw, cx, cy, cz, a.grid[0].bbox), t0, t1, dnorm, true, lane);
-  }
+  float w = proposal_level<0, 6, F_L0, NF>(a, ws, act_wave, r, s.td, lane, RC_FSTAMP_BUF);
   RC_FSTAMP(3);
-  for (int e2 = lane; e2 <= 64; e2 += 64) s_sd[1][e2] = s_out[e2];
+  for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[1][e2] = s.out[e2];
   lds_sync<false>();
   // ------------------------------------------------------------------ level 1 (P = 64, S = 64)
-  resample(1, 64, 64, a.anneal * safe_log(w + a.padding), s_sd[1]);
+  resample<FRONT>(a, r, ray, s, lane, 1, 64, 64, a.anneal * safe_log(w + a.padding), s.sd[1]);
   RC_FSTAMP(4);
-  {
-    float mx, my, mz, t0, t1;
-    mean_of(lane, mx, my, mz, t0, t1);
-    float cx = mx, cy = my, cz = mz;
-    contract3(cx, cy, cz, a.contract_radius);
-    float f[7];
-    {
-      const float ux = unit_box(a.grid[1].bbox, cx), uy = unit_box(a.grid[1].bbox, cy), uz = unit_box(a.grid[1].bbox, cz);
-#if defined(RC_ABL) && RC_ABL == 11
-      for (int l = 0; l < 7; ++l) f[l] = ux * (float)l + uy - uz;
-#else
-      Corners<1> C[7];          // 6 + 32 loads in flight before the first combine (level kinds at compile time, as above)
-#pragma unroll
-      for (int l = 0; l < 7; ++l) {
-        const RcGridLevel& L = a.grid[1].lvl[l];
-        if (l < kFusedDense) grid_fetch_cell(a.cell_table[1][l], L.size, ux, uy, uz, C[l]);
-        else grid_fetch<1, true>(L.table, L.size, L.mask, 0u, false, ux, uy, uz, C[l]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int l = 0; l < 7; ++l) {
-        float v[1], jd[1];
-        grid_combine<1, false>(C[l], v, jd);
-        f[l] = v[0] * a.grid[1].precondition;
-      }
-#endif
-    }
-    RC_FSTAMP(5);
-#if defined(RC_ABL) && RC_ABL == 13
-    const float raw = f[0] + f[6];
-#else
-    const float raw = density_level64<7, F_L1, NF>(ws, act_wave, lane, f);
-#endif
-    w = alpha_weight(density_of(raw, cx, cy, cz, a.grid[1].bbox), t0, t1, dnorm, true, lane);
-  }
+  w = proposal_level<1, 7, F_L1, NF>(a, ws, act_wave, r, s.td, lane, RC_FSTAMP_BUF);
   RC_FSTAMP(6);
-  for (int e2 = lane; e2 <= 64; e2 += 64) s_sd[0][e2] = s_out[e2];
+  for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[0][e2] = s.out[e2];
   lds_sync<false>();
   // ------------------------------------------------------------------ level 2 (P = 64, S = 32)
-  resample(2, 64, 32, a.anneal * safe_log(w + a.padding), s_sd[0]);
+  resample<FRONT>(a, r, ray, s, lane, 2, 64, 32, a.anneal * safe_log(w + a.padding), s.sd[0]);
   RC_FSTAMP(7);
   const int j = lane & 31, h = lane >> 5;
   float mx, my, mz, t0, t1;
-  mean_of(j, mx, my, mz, t0, t1);
+  mean_of(r, s.td, j, mx, my, mz, t0, t1);
   float cx = mx, cy = my, cz = mz;
   const float zx = rc_div(mx, a.contract_radius), zy = rc_div(my, a.contract_radius), zz = rc_div(mz, a.contract_radius);
   contract3(cx, cy, cz, a.contract_radius);
   float* act = act_wave + lane;
-  // (GRAD) d feature / d contracted coordinate of the density grid, 96 values per point, goes to LDS: element e of
-  // point j at step kJac + e / 2, lane j + 32 (e & 1); written and read back by the lane (j, 0) that owns the point
-  auto jac_at = [&](int e) -> float& { return act_wave[(kJac + (e >> 1)) * 64 + j + 32 * (e & 1)]; };
   {
     // half-wave 0 looks up the level-2 density grid, half-wave 1 the appearance grid (same level sizes)
     const RcGridDev& g = a.grid[2];      // bbox / precondition: same for both grids (checked on the host)
@@ -259,23 +196,11 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int l = half * 4 + q;
-        const int size = a.grid[2].lvl[l].size;
-        const bool dense = l < kFusedDense;       // compile-time, as in the fetch
         float v[4], jd[GRAD ? 12 : 1];
-        grid_combine<4, GRAD>(C[q], v, jd);
+        level2_combine<GRAD>(g, C[q], v, jd);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) f[4 * l + c] = v[c] * g.precondition;
-        if constexpr (GRAD) {
-          const float s = g.precondition * (float)size / (2.0f * g.bbox);
-          if (h == 0) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              jac_at(0 * 32 + 4 * l + c) = (dense ? jd[2 * 4 + c] : jd[0 * 4 + c]) * s;
-              jac_at(1 * 32 + 4 * l + c) = jd[1 * 4 + c] * s;
-              jac_at(2 * 32 + 4 * l + c) = (dense ? jd[0 * 4 + c] : jd[2 * 4 + c]) * s;
-            }
-          }
-        }
+        for (int c = 0; c < 4; ++c) f[4 * l + c] = v[c];
+        if constexpr (GRAD) level2_jacobian(g, l, jd, act_wave, j, h);
       }
     }
     // feature k of point j -> step base + k/2, lane j + 32 (k & 1): density features feed D0 at [0,16), appearance
@@ -318,7 +243,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
     park<2, true>(acc, act, 0);               // hidden feature: stays at [0,32) for the shader
     float out[4], wout[GRAD ? 32 : 1];
     dot_out1<2, 4, F_L2 + FR::DO, NF, GRAD>(ws, acc, out, wout);      // density + predicted normals on relu(acc)
-    density = density_of(out[0], cx, cy, cz, a.grid[2].bbox);
+    density = density_of(a, out[0], cx, cy, cz, a.grid[2].bbox);
     npx = out[1]; npy = out[2]; npz = out[3];
     neg_normalize(npx, npy, npz);
     if constexpr (GRAD) {
@@ -338,34 +263,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
       f32x16 gf[1];
       gf[0] = zero16();
       mlp_layer_dh<1, 2, false, F_L2 + FR::B0, NF>(ws, bw, gf);
-      // d raw / d feature i = acc_feat(0, r, h) sits on lane (j, h): each half-wave contracts ITS 16 features with the
-      // Jacobian rows parked in LDS, the two partial sums are added last (the order k_density_mlp uses)
-      float gp[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) gp[ax] += gf[0][r] * jac_at(ax * 32 + i);
-      }
-      float gw[3];
-#pragma unroll
-      for (int ax = 0; ax < 3; ++ax) {
-        const float oth = __shfl_xor(gp[ax], 32, 64);
-        gw[ax] = h == 0 ? gp[ax] + oth : oth + gp[ax];        // half 0's partial first on both halves
-      }
-      const float msq = zx * zx + zy * zy + zz * zz;
-      float gzx = gw[0], gzy = gw[1], gzz = gw[2];
-      if (msq > 1.0f) {
-        const float rt = sqrtf(msq);
-        const float s = (2.0f * rt - 1.0f) / msq;
-        const float ds = (1.0f - rt) / (msq * msq);
-        const float gz_dot = gw[0] * zx + gw[1] * zy + gw[2] * zz;
-        gzx = s * gw[0] + 2.0f * ds * gz_dot * zx;
-        gzy = s * gw[1] + 2.0f * ds * gz_dot * zy;
-        gzz = s * gw[2] + 2.0f * ds * gz_dot * zz;
-      }
-      ngx = rc_div(gzx, a.contract_radius); ngy = rc_div(gzy, a.contract_radius); ngz = rc_div(gzz, a.contract_radius);
-      neg_normalize(ngx, ngy, ngz);
+      analytic_normal(gf[0], act_wave, j, h, zx, zy, zz, a.contract_radius, ngx, ngy, ngz);
     } else if constexpr (!FRONT) {
       // the stream is consumed strictly in order: step the ring over the unused backward fragments
 #pragma unroll
@@ -377,24 +275,15 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   if constexpr (FRONT) {
     // hand-over to the stages behind the sampler, in the layouts of the launch-per-stage front end
     // (the buffer pointers as one batch of scalar loads in front of the first store, as in the compositing tail below)
-    asm volatile("" :: "s"(a.f_tdist), "s"(a.f_density), "s"(a.f_means), "s"(a.f_normals_pred), "s"(a.f_normals_grad),
-                 "s"(a.f_hbuf), "s"(a.f_app), "s"(a.n));
+    asm volatile("" :: RC_EXPORT_PINS, "s"(a.f_normals_grad), "s"(a.f_hbuf), "s"(a.f_app));
     if (ray_ok) {
       const int64_t np = a.n * 32, p = ray * 32 + j;
-      for (int e2 = lane; e2 <= 32; e2 += 64) a.f_tdist[ray * 33 + e2] = s_td[e2];
-      if (h == 0) {
-        a.f_density[p] = density;
-        a.f_means[p] = mx; a.f_means[np + p] = my; a.f_means[2 * np + p] = mz;
-        a.f_normals_pred[p] = npx; a.f_normals_pred[np + p] = npy; a.f_normals_pred[2 * np + p] = npz;
-        if constexpr (GRAD) {
-          if (a.f_normals_grad) { a.f_normals_grad[p] = ngx; a.f_normals_grad[np + p] = ngy; a.f_normals_grad[2 * np + p] = ngz; }
-        }
-      }
+      export_samples<GRAD>(a, ray, lane, s.td, density, mx, my, mz, npx, npy, npz, ngx, ngy, ngz);
       float* hb = a.f_hbuf + ray * (32 * 64) + lane;
 #pragma unroll
-      for (int s = 0; s < 32; ++s) hb[s * 64] = act[s * 64];                 // hidden feature, accumulator layout
+      for (int k = 0; k < 32; ++k) hb[k * 64] = act[k * 64];                 // hidden feature, accumulator layout
 #pragma unroll
-      for (int s = 0; s < 16; ++s) a.f_app[(int64_t)(2 * s + h) * np + p] = act[(kAppSteps + s) * 64];   // feature 2 s + h of point j
+      for (int k = 0; k < 16; ++k) a.f_app[(int64_t)(2 * k + h) * np + p] = act[(kAppSteps + k) * 64];   // feature 2 k + h of point j
     }
     return;
   }
@@ -411,7 +300,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   RC_FSTAMP(10);
   // ------------------------------------------------------------------ volume compositing (k_composite)
   const bool act_s = lane < 32;
-  const float wnf = alpha_weight(density, t0, t1, dnorm, act_s, lane);
+  const float wnf = alpha_weight(density, t0, t1, r.dnorm, act_s, lane);
   // The output pointers the tail stores through, fetched as ONE batch of scalar loads in front of the sums: read where
   // they are used, each store opened with its own s_load, a wait for it and a branch -- a scalar-cache round trip per
   // output on the ray's chain.  The loads go out here (fence below), the values are pinned in scalar registers by the
@@ -423,28 +312,15 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   if constexpr (EXPORT) {
     // its stores open a block of their own, behind which the loads above would sink: pinned in front of it, with the
     // workspace pointers
-    asm volatile("" :: "s"(a.f_tdist), "s"(a.f_density), "s"(a.f_means), "s"(a.f_normals_pred), "s"(a.n), "s"(op[0]), "s"(op[1]),
-                 "s"(op[2]), "s"(op[3]), "s"(op[4]), "s"(op[5]), "s"(op[6]), "s"(op[7]), "s"(op[8]), "s"(op[9]), "s"(op[10]), "s"(op[11]),
-                 "s"(op[12]), "s"(op[13]), "s"(op[14]), "s"(op[15]), "s"(op[16]), "s"(op[17]), "s"(op[18]));
+    asm volatile("" :: RC_EXPORT_PINS, RC_OUT_PINS);
   }
   __builtin_amdgcn_sched_barrier(0);
   // (EXPORT) the last level's per-sample results, behind the shader: every value is still live for the compositing, and
   // no scalar load of the shader then falls between the kernel's first and last store
   if constexpr (EXPORT) {
-    if (ray_ok) {
-      const int64_t np = a.n * 32, p = ray * 32 + j;
-      for (int e2 = lane; e2 <= 32; e2 += 64) a.f_tdist[ray * 33 + e2] = s_td[e2];
-      if (h == 0) {
-        a.f_density[p] = density;
-        a.f_means[p] = mx; a.f_means[np + p] = my; a.f_means[2 * np + p] = mz;
-        a.f_normals_pred[p] = npx; a.f_normals_pred[np + p] = npy; a.f_normals_pred[2 * np + p] = npz;
-      }
-    }
+    if (ray_ok) export_samples<false>(a, ray, lane, s.td, density, mx, my, mz, npx, npy, npz, ngx, ngy, ngz);
   }
-  auto store3 = [&](int id, float x, float y, float z) {
-    if (lane == 0 && ray_ok && op[id]) { op[id][3 * ray] = x; op[id][3 * ray + 1] = y; op[id][3 * ray + 2] = z; }
-  };
-  auto store1 = [&](int id, float x) { if (lane == 0 && ray_ok && op[id]) op[id][ray] = x; };
+  const bool st = lane == 0 && ray_ok;      // store3 / store1 of the ray's outputs
   // every weighted sum of the ray in one batched butterfly
   enum { V_ACC = 0, V_RGB = 1, V_AD = 4, V_IDF = 7, V_IS = 10, V_TINT = 13, V_DIF = 16, V_IND = 19, V_MEAN = 22, V_RD = 25,
          V_LD = 26, V_NP = 27, V_NG = 30, V_LOGT = 33, V_COUNT = 34 };
@@ -465,7 +341,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
     x[V_IND + c] = so.idf[c] + so.is[c];
   }
   x[V_MEAN] = mx; x[V_MEAN + 1] = my; x[V_MEAN + 2] = mz;
-  x[V_RD] = sqrtf((ox - mx) * (ox - mx) + (oy - my) * (oy - my) + (oz - mz) * (oz - mz));
+  x[V_RD] = sqrtf((r.ox - mx) * (r.ox - mx) + (r.oy - my) * (r.oy - my) + (r.oz - mz) * (r.oz - mz));
   x[V_LD] = 0.0f;
   if (a.lights) {
     const float lx = a.lights[3 * ray], ly = a.lights[3 * ray + 1], lz = a.lights[3 * ray + 2];
@@ -481,48 +357,29 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   for (int k = 0; k < V_COUNT / 2; ++k) vp[k] = wnf2 * (h ? x[2 * k + 1] : x[2 * k]);
   wave_sum32_pairs<V_COUNT / 2>(vp, v);
   // all pointers are in scalar registers here: one wait for the batch, and the stores below use these values
-  static_assert(kOutPtrs == 19, "the pin below names every pointer");
-  asm volatile("" :: "s"(op[0]), "s"(op[1]), "s"(op[2]), "s"(op[3]), "s"(op[4]), "s"(op[5]), "s"(op[6]), "s"(op[7]), "s"(op[8]),
-               "s"(op[9]), "s"(op[10]), "s"(op[11]), "s"(op[12]), "s"(op[13]), "s"(op[14]), "s"(op[15]), "s"(op[16]), "s"(op[17]),
-               "s"(op[18]));
+  static_assert(kOutPtrs == 19, "RC_OUT_PINS names every pointer");
+  asm volatile("" :: RC_OUT_PINS);
   __builtin_amdgcn_sched_barrier(0);
   const float accw = v[V_ACC];
   const float bgw = fmaxf(0.0f, 1.0f - accw) * a.bg;
-  store3(RC_OUT_RGB, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
-  store3(RC_OUT_DIRECT_RGB, v[V_AD], v[V_AD + 1], v[V_AD + 2]);
-  store3(RC_OUT_INDIRECT_DIFFUSE_RGB, v[V_IDF], v[V_IDF + 1], v[V_IDF + 2]);
-  store3(RC_OUT_INDIRECT_SPECULAR_RGB, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
-  store3(RC_OUT_SPECULAR_RGB, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
-  store3(RC_OUT_ALBEDO_RGB, v[V_TINT], v[V_TINT + 1], v[V_TINT + 2]);
-  store3(RC_OUT_DIFFUSE_RGB, v[V_DIF], v[V_DIF + 1], v[V_DIF + 2]);
-  store3(RC_OUT_INDIRECT_RGB, v[V_IND], v[V_IND + 1], v[V_IND + 2]);
-  store3(RC_OUT_INDIRECT_OCC, accw, accw, accw);
-  store1(RC_OUT_ACC, accw);
-  store3(RC_OUT_MEANS, v[V_MEAN], v[V_MEAN + 1], v[V_MEAN + 2]);
-  store1(RC_OUT_RAY_DISTS, v[V_RD]);
-  if (a.lights) store1(RC_OUT_LIGHT_DISTS, v[V_LD]);
-  store3(RC_OUT_NORMALS_PRED, v[V_NP], v[V_NP + 1], v[V_NP + 2]);
-  if constexpr (GRAD) store3(RC_OUT_NORMALS, v[V_NG], v[V_NG + 1], v[V_NG + 2]);
-  {
-    const float e = v[V_LOGT] / fmaxf(RC_EPS, accw);
-    float dm = expf(e);
-    if (dm != dm) dm = 0.0f;                     // nan_to_num(x, copy=inf): nan -> 0.0 (rc_sample.hip, k_composite)
-    dm = fminf(dm, RC_FMAX);
-    dm = fminf(fmaxf(dm, s_td[0]), s_td[32]);
-    store1(RC_OUT_DISTANCE_MEAN, dm);
-    const float wn = wnf / fmaxf(RC_EPS, accw);
-    const float incl = wave_scan_incl(wn, lane);
-    if (lane == 0) s_cw[0] = 0.0f;
-    if (lane < 31) s_cw[lane + 1] = fminf(1.0f, incl);
-    if (lane == 0) s_cw[32] = 1.0f;
-    lds_sync<false>();
-    if (lane < 3 && ray_ok) {
-      const float ps = a.pct[lane] / 100.0f;
-      const float v = interp1(ps, s_cw, s_td, 33);
-      float* const dst = lane == 0 ? op[RC_OUT_DISTANCE_PERCENTILE_5] : (lane == 1 ? op[RC_OUT_DISTANCE_MEDIAN] : op[RC_OUT_DISTANCE_PERCENTILE_95]);
-      if (dst) dst[ray] = v;
-    }
-  }
+  store3(op[RC_OUT_RGB], st, ray, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
+  store3(op[RC_OUT_DIRECT_RGB], st, ray, v[V_AD], v[V_AD + 1], v[V_AD + 2]);
+  store3(op[RC_OUT_INDIRECT_DIFFUSE_RGB], st, ray, v[V_IDF], v[V_IDF + 1], v[V_IDF + 2]);
+  store3(op[RC_OUT_INDIRECT_SPECULAR_RGB], st, ray, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
+  store3(op[RC_OUT_SPECULAR_RGB], st, ray, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
+  store3(op[RC_OUT_ALBEDO_RGB], st, ray, v[V_TINT], v[V_TINT + 1], v[V_TINT + 2]);
+  store3(op[RC_OUT_DIFFUSE_RGB], st, ray, v[V_DIF], v[V_DIF + 1], v[V_DIF + 2]);
+  store3(op[RC_OUT_INDIRECT_RGB], st, ray, v[V_IND], v[V_IND + 1], v[V_IND + 2]);
+  store3(op[RC_OUT_INDIRECT_OCC], st, ray, accw, accw, accw);
+  store1(op[RC_OUT_ACC], st, ray, accw);
+  store3(op[RC_OUT_MEANS], st, ray, v[V_MEAN], v[V_MEAN + 1], v[V_MEAN + 2]);
+  store1(op[RC_OUT_RAY_DISTS], st, ray, v[V_RD]);
+  if (a.lights) store1(op[RC_OUT_LIGHT_DISTS], st, ray, v[V_LD]);
+  store3(op[RC_OUT_NORMALS_PRED], st, ray, v[V_NP], v[V_NP + 1], v[V_NP + 2]);
+  if constexpr (GRAD) store3(op[RC_OUT_NORMALS], st, ray, v[V_NG], v[V_NG + 1], v[V_NG + 2]);
+  store1(op[RC_OUT_DISTANCE_MEAN], st, ray, distance_mean(v[V_LOGT], accw, s.td));
+  distance_percentiles(a, ray, ray_ok, lane, wnf, accw, s.td, s.cw, op[RC_OUT_DISTANCE_PERCENTILE_5], op[RC_OUT_DISTANCE_MEDIAN],
+                       op[RC_OUT_DISTANCE_PERCENTILE_95]);
   RC_FSTAMP(11);
 #ifdef RC_STAMPS
   if (lane == 0 && a.stamps && ray_ok) {
@@ -565,13 +422,16 @@ void rc_launch_fused(const RcFusedLaunch& L, hipStream_t stream) {
   if (L.n <= 0) return;
   static std::atomic<uint64_t> prepared{0};
   const int lds = (kRingFloats + kWaves * (kShActSteps * 64 + kScratch)) * (int)sizeof(float);
+  // the six instantiations, by [GRAD][form]
+  enum { kPlain = 0, kFront = 1, kExport = 2 };
+  using Kernel = void (*)(RcFusedArgs);
+  static const Kernel kernels[2][3] = {
+      {k_cache_fused<false>, k_cache_fused<false, true>, k_cache_fused<false, false, true>},
+      {k_cache_fused<true>, k_cache_fused<true, true>, k_cache_fused<true, false, true>}};
   if (rc_first_use_on_device(prepared)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cache_fused<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    for (int g = 0; g < 2; ++g)
+      for (int f = 0; f < 3; ++f)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[g][f]), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   }
   RcFusedArgs a{};
   a.origins = L.rays.origins; a.directions = L.rays.directions; a.viewdirs = L.rays.viewdirs; a.near = L.rays.near;
@@ -596,30 +456,22 @@ void rc_launch_fused(const RcFusedLaunch& L, hipStream_t stream) {
   }
 #endif
   dim3 grid((unsigned)((L.n + kWaves - 1) / kWaves)), block(kWaves * 64);
+  if (L.front || L.export_samples) {
+    a.f_tdist = L.f_tdist; a.f_density = L.f_density; a.f_means = L.f_means; a.f_normals_pred = L.f_normals_pred;
+  }
   if (L.front) {
     a.use_raydist = L.use_raydist; a.raydist_p = L.raydist_p; a.raydist_premult = L.raydist_premult;
     a.y_max = L.raydist_p < 0.0f ? nextafterf((L.raydist_p - 1.0f) / L.raydist_p, -INFINITY) : 0.0f;       // as rc_launch_sample
-    a.f_tdist = L.f_tdist; a.f_density = L.f_density; a.f_means = L.f_means; a.f_normals_pred = L.f_normals_pred;
     a.f_normals_grad = L.want_grad ? L.f_normals_grad : nullptr; a.f_hbuf = L.f_hbuf; a.f_app = L.f_app;
-    if (L.want_grad) hipLaunchKernelGGL((k_cache_fused<true, true>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((k_cache_fused<false, true>), grid, block, lds, stream, a);
-    return;
   }
-  if (L.export_samples && L.team) {
-    a.f_tdist = L.f_tdist; a.f_density = L.f_density; a.f_means = L.f_means; a.f_normals_pred = L.f_normals_pred;
-  } else if (L.export_samples) {
-    a.f_tdist = L.f_tdist; a.f_density = L.f_density; a.f_means = L.f_means; a.f_normals_pred = L.f_normals_pred;
-    if (L.out.ptr[RC_OUT_NORMALS]) hipLaunchKernelGGL((k_cache_fused<true, false, true>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((k_cache_fused<false, false, true>), grid, block, lds, stream, a);
-    return;
-  }
+  const bool grad = L.front ? L.want_grad != 0 : L.out.ptr[RC_OUT_NORMALS] != nullptr;
 #if RC_TEAM_KERNEL
-  if (L.team) {
+  if (!L.front && L.team) {        // the two-wave kernel exports by itself where a.f_density is set
     a.prio_mode = L.prio_mode;
-    rc_launch_fused_team(a, L.out.ptr[RC_OUT_NORMALS] != nullptr, stream);
+    rc_launch_fused_team(a, grad, stream);
     return;
   }
 #endif
-  if (L.out.ptr[RC_OUT_NORMALS]) hipLaunchKernelGGL(k_cache_fused<true>, grid, block, lds, stream, a);
-  else hipLaunchKernelGGL(k_cache_fused<false>, grid, block, lds, stream, a);
+  const int form = L.front ? kFront : (L.export_samples && !L.team ? kExport : kPlain);
+  hipLaunchKernelGGL(kernels[grad][form], grid, block, lds, stream, a);
 }

@@ -21,6 +21,10 @@
 //     in the ray's LDS slice both waves read); one-tile layers (heads, the last backward layer) run on wave 0 while
 //     wave 1 evaluates the directional-encoding polynomials;
 //   the per-ray scans (alpha weights, step-function resampling, compositing) run on wave 0.
+// The ray record, the scratch slices, analytic_normal, the distance statistics and store3 / store1 are
+// rc_fused_common.h's, shared with rc_fused.hip.  resample, mean_of, density_of, the level-2 combine with its Jacobian
+// scatter and the sample export stay this kernel's own copies: calling the shared ones costs the instantiation without
+// GRAD 0.7 us in 112.6 (profiles/r11_fused_shared_phases_ab.txt, section 2).
 // Hand-offs between the two waves go through LDS and a workgroup barrier (4 waves); every wave of the workgroup executes
 // the same sequence of barriers (ring seams included: a wave that does not read a fragment range still walks its seams).
 #include "rc_fused_common.h"
@@ -48,7 +52,7 @@ constexpr int kTW = 2 * kRays;                // waves per workgroup: kRays rays
 #endif
 constexpr int kTCH = RC_TCH;                  // fragments per ring chunk (48: 12 KiB, the ring is 24 KiB)
 constexpr int kTRing = 2 * kTCH * 64;         // floats
-constexpr int kTScratch = 9 * 68;             // per ray: the 7 step-function arrays + density exchange + small hand-offs
+constexpr int kTScratch = kScratch + 2 * 68;  // per ray: the 7 step-function arrays + density exchange + small hand-offs
 constexpr int kNF = NF_FUSED;
 
 // Hand-off barrier between the two waves of a ray (all four waves of the workgroup take it).  Its release fence also
@@ -318,11 +322,9 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   float* ring = lds_dyn;
   float* act_ray = lds_dyn + kTRing + rs * (kShActSteps * 64);
   float* scr = lds_dyn + kTRing + kRays * (kShActSteps * 64) + rs * kTScratch;
-  float* s_sd[2] = {scr, scr + 68};
-  float* s_td = scr + 2 * 68; float* s_cw = scr + 3 * 68; float* s_c = scr + 4 * 68; float* s_v = scr + 5 * 68;
-  float* s_out = scr + 6 * 68;
-  float* x_dens = scr + 7 * 68;                      // [64] densities of a proposal level, from both waves to wave 0
-  float* x_misc = scr + 8 * 68;                      // [32] roughness of the shaded samples, from wave 0 to wave 1
+  const Scratch s = carve_scratch(scr);
+  float* x_dens = scr + kScratch;                    // [64] densities of a proposal level, from both waves to wave 0
+  float* x_misc = scr + kScratch + 68;               // [32] roughness of the shaded samples, from wave 0 to wave 1
   WStream ws(a.wstream, ring, lane, wave);
 #ifdef RC_STAMPS
   unsigned long long stamps[16];
@@ -342,11 +344,10 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   RC_FSTAMP(0);
   ws_begin<kNF, kTW, kTCH>(ws);
 
-  const float ox = a.origins[3 * ray], oy = a.origins[3 * ray + 1], oz = a.origins[3 * ray + 2];
-  const float dx = a.directions[3 * ray], dy = a.directions[3 * ray + 1], dz = a.directions[3 * ray + 2];
-  const float near = a.near[ray], far = a.far[ray];
-  const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
-
+  const Ray r = load_ray(a, ray);
+  // this kernel's own resample / mean_of / density_of (see the head of the file) on the names they were written with
+  float* s_td = s.td; float* s_cw = s.cw; float* s_c = s.c; float* s_v = s.v; float* s_out = s.out;
+  const float ox = r.ox, oy = r.oy, oz = r.oz, dx = r.dx, dy = r.dy, dz = r.dz, near = r.near, far = r.far;
   // (wave 0) resample S intervals from (prev sdist in s_prev [P+1], logit per bin): sdist -> s_out, tdist -> s_td
   auto resample = [&](int level, int P, int S, float logit, const float* s_prev) {
     const bool hasj = a.jitter[level] != nullptr;
@@ -369,11 +370,11 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   };
   const int j = lane & 31, h = lane >> 5;
 
-  // ------------------------------------------------------------------ level 0 (P = 1, S = 64)
+  // ------------------------------------------------------------------ level 0 (P = 1, S = 64); the resampling on wave 0
   if (q == 0) {
-    if (lane == 0) { s_sd[0][0] = 0.0f; s_sd[0][1] = 1.0f; }
+    if (lane == 0) { s.sd[0][0] = 0.0f; s.sd[0][1] = 1.0f; }
     lds_sync<false>();
-    resample(0, 1, 64, a.anneal * safe_log(1.0f + a.padding), s_sd[0]);
+    resample(0, 1, 64, a.anneal * safe_log(1.0f + a.padding), s.sd[0]);
   }
   TB();
   RC_FSTAMP(1);
@@ -393,10 +394,10 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   RC_FSTAMP(3);
   // ------------------------------------------------------------------ level 1 (P = 64, S = 64)
   if (q == 0) {
-    const float w = alpha_weight(x_dens[lane], s_td[lane], s_td[lane + 1], dnorm, true, lane);
-    for (int e2 = lane; e2 <= 64; e2 += 64) s_sd[1][e2] = s_out[e2];
+    const float w = alpha_weight(x_dens[lane], s.td[lane], s.td[lane + 1], r.dnorm, true, lane);
+    for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[1][e2] = s.out[e2];
     lds_sync<false>();
-    resample(1, 64, 64, a.anneal * safe_log(w + a.padding), s_sd[1]);
+    resample(1, 64, 64, a.anneal * safe_log(w + a.padding), s.sd[1]);
   }
   TB();
   RC_FSTAMP(4);
@@ -416,10 +417,10 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   RC_FSTAMP(6);
   // ------------------------------------------------------------------ level 2 (P = 64, S = 32)
   if (q == 0) {
-    const float w = alpha_weight(x_dens[lane], s_td[lane], s_td[lane + 1], dnorm, true, lane);
-    for (int e2 = lane; e2 <= 64; e2 += 64) s_sd[0][e2] = s_out[e2];
+    const float w = alpha_weight(x_dens[lane], s.td[lane], s.td[lane + 1], r.dnorm, true, lane);
+    for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[0][e2] = s.out[e2];
     lds_sync<false>();
-    resample(2, 64, 32, a.anneal * safe_log(w + a.padding), s_sd[0]);
+    resample(2, 64, 32, a.anneal * safe_log(w + a.padding), s.sd[0]);
   }
   TB();
   RC_FSTAMP(7);
@@ -429,7 +430,6 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   const float zx = rc_div(mx, a.contract_radius), zy = rc_div(my, a.contract_radius), zz = rc_div(mz, a.contract_radius);
   contract3(cx, cy, cz, a.contract_radius);
   float* act = act_ray + lane;
-  auto jac_at = [&](int e) -> float& { return act_ray[(kJac + (e >> 1)) * 64 + j + 32 * (e & 1)]; };
   {
     // half-wave 0 looks up the level-2 density grid, half-wave 1 the appearance grid (interleaved pair tables);
     // wave q takes grid levels 4 q .. 4 q + 3: 32 corner loads of 16 bytes in flight per lane.  The body is expanded
@@ -463,9 +463,9 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
           if (h == 0) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-              jac_at(0 * 32 + 4 * l + c) = (dense ? jd[2 * 4 + c] : jd[0 * 4 + c]) * s;
-              jac_at(1 * 32 + 4 * l + c) = jd[1 * 4 + c] * s;
-              jac_at(2 * 32 + 4 * l + c) = (dense ? jd[0 * 4 + c] : jd[2 * 4 + c]) * s;
+              jac_at(act_ray, j, 0 * 32 + 4 * l + c) = (dense ? jd[2 * 4 + c] : jd[0 * 4 + c]) * s;
+              jac_at(act_ray, j, 1 * 32 + 4 * l + c) = jd[1 * 4 + c] * s;
+              jac_at(act_ray, j, 2 * 32 + 4 * l + c) = (dense ? jd[0 * 4 + c] : jd[2 * 4 + c]) * s;
             }
           }
         }
@@ -541,32 +541,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
         f32x16 gf[1];
         gf[0] = zero16();
         mlp_layer_d<1, 32, F_L2 + FR::B0, kNF, 8, kTW, kTCH>(ws, act, gf);
-        float gp[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax) gp[ax] += gf[0][r] * jac_at(ax * 32 + i);
-        }
-        float gw[3];
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-          const float oth = __shfl_xor(gp[ax], 32, 64);
-          gw[ax] = h == 0 ? gp[ax] + oth : oth + gp[ax];        // half 0's partial first on both halves
-        }
-        const float msq = zx * zx + zy * zy + zz * zz;
-        float gzx = gw[0], gzy = gw[1], gzz = gw[2];
-        if (msq > 1.0f) {
-          const float rt = sqrtf(msq);
-          const float s = (2.0f * rt - 1.0f) / msq;
-          const float ds = (1.0f - rt) / (msq * msq);
-          const float gz_dot = gw[0] * zx + gw[1] * zy + gw[2] * zz;
-          gzx = s * gw[0] + 2.0f * ds * gz_dot * zx;
-          gzy = s * gw[1] + 2.0f * ds * gz_dot * zy;
-          gzz = s * gw[2] + 2.0f * ds * gz_dot * zz;
-        }
-        ngx = rc_div(gzx, a.contract_radius); ngy = rc_div(gzy, a.contract_radius); ngz = rc_div(gzz, a.contract_radius);
-        neg_normalize(ngx, ngy, ngz);
+        analytic_normal(gf[0], act_ray, j, h, zx, zy, zz, a.contract_radius, ngx, ngy, ngz);
       } else {
         tw_skip<F_L2 + FR::B0, rc_lfr32(32, 1)>(ws);
       }
@@ -715,11 +690,8 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   // weighted sums are split: wave 0 the colours (it has the heads) and the analytic normals, wave 1 the geometry
   // (means, distances, predicted normals) and the distance percentiles.  Same sums in the same order as one wave.
   const bool act_s = lane < 32;
-  const float wnf = alpha_weight(density, t0, t1, dnorm, act_s, lane);
-  auto store3 = [&](int id, float x, float y, float z) {
-    if (lane == 0 && ray_ok && a.out.ptr[id]) { a.out.ptr[id][3 * ray] = x; a.out.ptr[id][3 * ray + 1] = y; a.out.ptr[id][3 * ray + 2] = z; }
-  };
-  auto store1 = [&](int id, float x) { if (lane == 0 && ray_ok && a.out.ptr[id]) a.out.ptr[id][ray] = x; };
+  const float wnf = alpha_weight(density, t0, t1, r.dnorm, act_s, lane);
+  const bool st = lane == 0 && ray_ok;      // store3 / store1 of the ray's outputs
   if (q == 0) {
     ShadeOut so;
 #pragma unroll
@@ -749,23 +721,23 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     wave_sum_n<V_COUNT>(v);
     const float accw = v[V_ACC];
     const float bgw = fmaxf(0.0f, 1.0f - accw) * a.bg;
-    store3(RC_OUT_RGB, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
-    store3(RC_OUT_DIRECT_RGB, v[V_AD], v[V_AD + 1], v[V_AD + 2]);
-    store3(RC_OUT_INDIRECT_DIFFUSE_RGB, v[V_IDF], v[V_IDF + 1], v[V_IDF + 2]);
-    store3(RC_OUT_INDIRECT_SPECULAR_RGB, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
-    store3(RC_OUT_SPECULAR_RGB, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
-    store3(RC_OUT_ALBEDO_RGB, v[V_TINT], v[V_TINT + 1], v[V_TINT + 2]);
-    store3(RC_OUT_DIFFUSE_RGB, v[V_DIF], v[V_DIF + 1], v[V_DIF + 2]);
-    store3(RC_OUT_INDIRECT_RGB, v[V_IND], v[V_IND + 1], v[V_IND + 2]);
-    store3(RC_OUT_INDIRECT_OCC, accw, accw, accw);
-    store1(RC_OUT_ACC, accw);
-    if constexpr (GRAD) store3(RC_OUT_NORMALS, v[V_NG], v[V_NG + 1], v[V_NG + 2]);
+    store3(a.out.ptr[RC_OUT_RGB], st, ray, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
+    store3(a.out.ptr[RC_OUT_DIRECT_RGB], st, ray, v[V_AD], v[V_AD + 1], v[V_AD + 2]);
+    store3(a.out.ptr[RC_OUT_INDIRECT_DIFFUSE_RGB], st, ray, v[V_IDF], v[V_IDF + 1], v[V_IDF + 2]);
+    store3(a.out.ptr[RC_OUT_INDIRECT_SPECULAR_RGB], st, ray, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
+    store3(a.out.ptr[RC_OUT_SPECULAR_RGB], st, ray, v[V_IS], v[V_IS + 1], v[V_IS + 2]);
+    store3(a.out.ptr[RC_OUT_ALBEDO_RGB], st, ray, v[V_TINT], v[V_TINT + 1], v[V_TINT + 2]);
+    store3(a.out.ptr[RC_OUT_DIFFUSE_RGB], st, ray, v[V_DIF], v[V_DIF + 1], v[V_DIF + 2]);
+    store3(a.out.ptr[RC_OUT_INDIRECT_RGB], st, ray, v[V_IND], v[V_IND + 1], v[V_IND + 2]);
+    store3(a.out.ptr[RC_OUT_INDIRECT_OCC], st, ray, accw, accw, accw);
+    store1(a.out.ptr[RC_OUT_ACC], st, ray, accw);
+    if constexpr (GRAD) store3(a.out.ptr[RC_OUT_NORMALS], st, ray, v[V_NG], v[V_NG + 1], v[V_NG + 2]);
   } else {
     enum { V_ACC = 0, V_MEAN = 1, V_RD = 4, V_LD = 5, V_NP = 6, V_LOGT = 9, V_COUNT = 10 };
     float v[V_COUNT];
     v[V_ACC] = wnf;
     v[V_MEAN] = wnf * mx; v[V_MEAN + 1] = wnf * my; v[V_MEAN + 2] = wnf * mz;
-    v[V_RD] = wnf * sqrtf((ox - mx) * (ox - mx) + (oy - my) * (oy - my) + (oz - mz) * (oz - mz));
+    v[V_RD] = wnf * sqrtf((r.ox - mx) * (r.ox - mx) + (r.oy - my) * (r.oy - my) + (r.oz - mz) * (r.oz - mz));
     v[V_LD] = 0.0f;
     if (a.lights) {
       const float lx = a.lights[3 * ray], ly = a.lights[3 * ray + 1], lz = a.lights[3 * ray + 2];
@@ -775,28 +747,13 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     v[V_LOGT] = act_s ? wnf * logf(0.5f * (t0 + t1)) : 0.0f;
     wave_sum_n<V_COUNT>(v);
     const float accw = v[V_ACC];
-    store3(RC_OUT_MEANS, v[V_MEAN], v[V_MEAN + 1], v[V_MEAN + 2]);
-    store1(RC_OUT_RAY_DISTS, v[V_RD]);
-    if (a.lights) store1(RC_OUT_LIGHT_DISTS, v[V_LD]);
-    store3(RC_OUT_NORMALS_PRED, v[V_NP], v[V_NP + 1], v[V_NP + 2]);
-    const float e = v[V_LOGT] / fmaxf(RC_EPS, accw);
-    float dm = expf(e);
-    if (dm != dm) dm = 0.0f;                     // nan_to_num(x, copy=inf): nan -> 0.0 (rc_sample.hip, k_composite)
-    dm = fminf(dm, RC_FMAX);
-    dm = fminf(fmaxf(dm, s_td[0]), s_td[32]);
-    store1(RC_OUT_DISTANCE_MEAN, dm);
-    const float wn = wnf / fmaxf(RC_EPS, accw);
-    const float incl = wave_scan_incl(wn, lane);
-    if (lane == 0) s_cw[0] = 0.0f;
-    if (lane < 31) s_cw[lane + 1] = fminf(1.0f, incl);
-    if (lane == 0) s_cw[32] = 1.0f;
-    lds_sync<false>();
-    if (lane < 3 && ray_ok) {
-      const float ps = a.pct[lane] / 100.0f;
-      const float pv = interp1(ps, s_cw, s_td, 33);
-      const int id = lane == 0 ? RC_OUT_DISTANCE_PERCENTILE_5 : (lane == 1 ? RC_OUT_DISTANCE_MEDIAN : RC_OUT_DISTANCE_PERCENTILE_95);
-      if (a.out.ptr[id]) a.out.ptr[id][ray] = pv;
-    }
+    store3(a.out.ptr[RC_OUT_MEANS], st, ray, v[V_MEAN], v[V_MEAN + 1], v[V_MEAN + 2]);
+    store1(a.out.ptr[RC_OUT_RAY_DISTS], st, ray, v[V_RD]);
+    if (a.lights) store1(a.out.ptr[RC_OUT_LIGHT_DISTS], st, ray, v[V_LD]);
+    store3(a.out.ptr[RC_OUT_NORMALS_PRED], st, ray, v[V_NP], v[V_NP + 1], v[V_NP + 2]);
+    store1(a.out.ptr[RC_OUT_DISTANCE_MEAN], st, ray, distance_mean(v[V_LOGT], accw, s.td));
+    distance_percentiles(a, ray, ray_ok, lane, wnf, accw, s.td, s.cw, a.out.ptr[RC_OUT_DISTANCE_PERCENTILE_5],
+                         a.out.ptr[RC_OUT_DISTANCE_MEDIAN], a.out.ptr[RC_OUT_DISTANCE_PERCENTILE_95]);
 #ifdef RC_STAMPS
     RC_FSTAMP(11);
     if (lane == 0 && a.stamps && ray_ok) {          // wave 1 of a ray: second half of the stamp buffer

@@ -259,6 +259,42 @@ def test_two_wave_fused_kernel_equals_the_one_wave_kernel(rc, n, jitter_seed):
             assert bool(torch.isfinite(res[1][k]).all()), k
 
 
+def test_two_wave_fused_kernel_exports_the_samples_of_the_one_wave_kernel(rc_smooth):
+    """The material stage's primary pass under rc_set_fused 1 (RC_SPLIT_MFMA=0: k_cache_fused_team with its sample
+    export) against rc_set_fused 3 (k_cache_fused's EXPORT instantiation): the four exported buffers themselves (fence
+    posts, densities, means, predicted normals of the last level, read back from the workspace) and every array
+    render_material returns are bitwise equal; 5 rays (a workgroup with one live ray), fixed picks (the shading point
+    then takes the exported mean and normal at the given index).  In the split build both modes run the one-wave kernel,
+    as above."""
+    from oracle import material_ref
+    n = 5
+    cfg = nrc_amd.hotdog_config()
+    rays = nrc_amd.synthetic_rays(n, seed=905)
+    rnd = material_ref.draw_randoms(cfg, n, seed=5)
+    ks, kd = rnd["spec_u1"].shape[1], rnd["diff_jitter"][0].size // n
+    rnd = dict(rnd, gumbel=None, spec_gumbel=None, diff_gumbel=None,
+               resample_inds=np.array([3, 11, 16, 20, 29], np.int32),
+               spec_resample_inds=((np.arange(n * ks) * 7 + 3) % 32).astype(np.int32),
+               diff_resample_inds=((np.arange(n * kd) * 5 + 1) % 32).astype(np.int32))
+    res = {}
+    for mode in (1, 3):
+        rc_smooth.set_fused(mode)
+        try:
+            cres, mres = rc_smooth.render_material(rays.hot_fields(), rnd)
+            torch.cuda.synchronize()
+        finally:
+            rc_smooth.set_fused(True)
+        res[mode] = {**{"cache:" + k: v.clone() for k, v in cres.items()}, **{"material:" + k: v.clone() for k, v in mres.items()}}
+        for name, count in (("tdist2", n * 33), ("density2", n * 32), ("means2", 3 * n * 32), ("normals_pred", 3 * n * 32)):
+            w = rc_smooth.workspace(name)
+            assert w.size >= count, (name, w.size)
+            res[mode]["export:" + name] = torch.from_numpy(w[:count].copy())
+    assert res[1].keys() == res[3].keys() and len(res[1]) > 0
+    for k in res[1]:
+        assert torch.equal(res[1][k], res[3][k]), k
+        assert bool(torch.isfinite(res[1][k]).all()), k
+
+
 def test_empty_batch_is_a_noop(rc):
     rays = nrc_amd.synthetic_rays(4)
     f = {k: np.asarray(v)[:0] for k, v in rays.hot_fields().items()}
