@@ -335,8 +335,9 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * reference's column order), "part" (weight-gradient K slices), "ones"; for all n rays, row-major per shaded sample in the
  * reference's column order: "d_t_irr" ([32 n][64] d loss / d the irradiance trunk's output), "d_t_slf" ([32 n][128] d loss /
  * d the surface light field trunk's output), "d_tint_ibrdf" ([32 n][3]), "d_direct" ([32 n][3] d loss / d direct_rgb),
- * "d_weights" ([32 n] d loss / d the compositing weights).  The forward's own buffers keep their set-0 names ("t_irr",
- * "t_slf", "tshade", "weights2").
+ * "d_weights" ([32 n] d loss / d the compositing weights); after rc_transient_data_backward_sampler with sampler_grads also
+ * "d_density" ([32 n] d loss / d the last level's density through those weights) and "points" ([32 n][3] the sample means).
+ * The forward's own buffers keep their set-0 names ("t_irr", "t_slf", "tshade", "weights2").
  * "mk:" = rc_mask_backward: the training forward's per-level "sdist", "tdist", "means", "feat", "density", "weights" (the
  * last level's "weights" written by the loss kernel), "loss_ray" ([n] per-ray terms), "d_density" ([n S]), "points"
  * ([n S][3]).
@@ -895,12 +896,14 @@ int rc_adam_update(rc_handle* h, const rc_adam_buffer* bufs, int32_t nbuf, const
  * `stream` (the host repack needs them).  The derived tables (cell tables, level-2 pairs, cell records) and packs are
  * marked stale and captured graphs dropped, as rc_load_weights does: the next render or backward call on any stream
  * computes bitwise what it would after rc_load_weights of the same tensors.  A time-resolved cache handle loads
- * RC_LAYOUT_TRANSIENT_HEADS only (every other layout: RC_ERR_UNSUPPORTED); that layout needs such a handle. */
+ * RC_LAYOUT_TRANSIENT_HEADS and RC_LAYOUT_TRANSIENT_SAMPLER only (every other layout: RC_ERR_UNSUPPORTED); those two
+ * layouts need such a handle. */
 #define RC_LAYOUT_SHADER (-1)
 #define RC_LAYOUT_LIGHT (-2)   /* rc_light_grad_layout */
 #define RC_LAYOUT_MATERIAL (-3)   /* rc_material_grad_layout */
 #define RC_LAYOUT_ENVMAP (-4)   /* rc_envmap_grad_layout */
 #define RC_LAYOUT_TRANSIENT_HEADS (-5)   /* rc_transient_head_grad_layout */
+#define RC_LAYOUT_TRANSIENT_SAMPLER (-6)   /* rc_transient_sampler_grad_layout */
 int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void* stream);
 
 /* ---- the light sampler's own loss -----------------------------------------------------------------
@@ -1152,6 +1155,52 @@ int rc_transient_data_backward_kind(rc_handle* h, const rc_rays* rays, const flo
                                     const rc_transient_data_loss_kind* cfg, float* head_grads, float* losses, void* stream);
 int rc_dtof_to_itof(rc_handle* h, const float* dtof, int64_t n, int32_t n_pairs, const double* frequency,
                     const double* phase_shift, float* itof, void* stream);
+
+/* ---- the time-resolved cache's density fields and proposal samplers -------------------------------
+ * The sampler side of a time-resolved handle: the three density fields (grid tables and density MLP of every level) and
+ * MLP_<last>/pred_normals_layer in ONE flat buffer, RC_LAYOUT_TRANSIENT_SAMPLER = the segments of rc_density_grad_layout(0),
+ * then level 1, then level 2, each in its own order, then params/Cache/Sampler/MLP_<last>/pred_normals_layer/{kernel
+ * [64, 3], bias [3]}.  rc_transient_sampler_grad_size / _layout describe it, rc_load_params_flat loads it; a steady-state
+ * handle has no such layout (RC_ERR_UNSUPPORTED).
+ *
+ * rc_transient_interlevel_backward, rc_transient_geometry_backward, rc_transient_mask_backward and
+ * rc_transient_density_regularizer are rc_interlevel_backward, rc_geometry_backward, rc_mask_backward and
+ * rc_density_regularizer on a time-resolved handle: the same host code, kernels, workspace sets ("i:", "g:", "mk:"),
+ * reduction order, argument checks and loss slots.  What differs:
+ *   - the training forward is this handle's own sampler (power-ladder distances on every ray, its contract radius and
+ *     grids), with the caller's jitter and anneal;
+ *   - every gradient is ACCUMULATED into `sampler_grads` (RC_LAYOUT_TRANSIENT_SAMPLER; NULL: the losses only): a level's
+ *     density gradient into that level's segments, pred_normals_layer's into the tail.  rc_transient_geometry_backward
+ *     with a buffer always computes both of its gradients;
+ *   - a handle without rc_set_transient and a use_occlusions handle are refused (RC_ERR_UNSUPPORTED), before any other
+ *     check of the handle's state; the argument checks in front of that are the counterpart's.
+ * The rays of the backward mask term (rc_backward_mask_rays) are passed to rc_transient_mask_backward like any others:
+ * on this handle the primary and the secondary sampler differ only by the clamp of `far` at env_map_distance, which is
+ * NOT applied (the same rays as long as far <= env_map_distance; the cornell gin's secondary_far is 1).
+ *
+ * rc_transient_data_backward_sampler: rc_transient_data_backward_kind (the same code: losses, "td:G", the "td:" adjoints
+ * and head_grads are bitwise its), then, with `sampler_grads`, the data loss's gradient of MLP_<last> THROUGH THE
+ * COMPOSITING WEIGHTS: "td:d_density" = alpha_weights_bwd("td:d_weights") |delta| with the forward's density, tdist and
+ * weights of the last level (delta = (t1 - t0) |direction|, the forward compositing's own), and rc_density_backward of the
+ * last level at the forward's sample means, accumulated into the level's segments of sampler_grads.  This is the weights
+ * path ONLY: the paths through the geometry feature and the predicted normals into the shader need the shader's backward
+ * and are not part of the call (the gin weighs them with stopgrad_geometry_feature_weight =
+ * stopgrad_geometry_normals_weight = 1.0).  sampler_grads == NULL: nothing beyond rc_transient_data_backward_kind runs. */
+int64_t rc_transient_sampler_grad_size(rc_handle* h);
+int rc_transient_sampler_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count);
+int rc_transient_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                                     float anneal, const float* mults, const float* blurs, float* sampler_grads, float* losses,
+                                     void* stream);
+int rc_transient_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                                   float anneal, const rc_geometry_loss* cfg, float* sampler_grads, float* losses, void* stream);
+int rc_transient_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, const float* lossmult, int64_t n,
+                               const rc_randoms* rnd, float anneal, const rc_mask_loss* cfg, float* sampler_grads, float* loss,
+                               void* stream);
+int rc_transient_density_regularizer(rc_handle* h, int32_t level, float mult, float* sampler_grads, float* loss, void* stream);
+int rc_transient_data_backward_sampler(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                                       const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                                       const rc_transient_data_loss_kind* cfg, float* head_grads, float* sampler_grads,
+                                       float* losses, void* stream);
 
 /* ---- evaluation of a rendered view -------------------------------------------------------------------
  * rc_eval_image: what the reference's trainer computes per test view, on images that stay on the device.

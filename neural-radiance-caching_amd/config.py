@@ -511,3 +511,49 @@ def cornell_transient_config(**overrides) -> RenderConfig:
         transient=dataclasses.replace(TransientConfig(), **t_over),
     )
     return dataclasses.replace(base, **overrides)
+
+
+# The cache stage's sampler-side losses as configs/transient_simulation_ngp_yobo_cornell.gin resolves them through its
+# chain (cornell.gin -> transient_simulation_ngp_yobo.gin [tsny] -> transient_ngp_yobo.gin [tny] -> trainer.gin ->
+# internal/configs.py).  Every field is read there; the line that holds the winning value is beside it.
+
+def cornell_transient_interlevel_config(**overrides) -> InterlevelConfig:
+    return dataclasses.replace(InterlevelConfig(
+        mults=(0.01, 0.01),      # Config.interlevel_loss_mults, cornell.gin:139 (use_spline_interlevel_loss: tny.gin:256)
+        blurs=(0.03, 0.003),     # Config.interlevel_loss_blurs, tsny.gin:69
+        anneal_slope=10.0,       # ProposalVolumeSampler.anneal_slope, cornell.gin:107
+        anneal_end=1.0,          # ProposalVolumeSampler.anneal_end, cornell.gin:109
+        anneal_clip=0.4,         # ProposalVolumeSampler.anneal_clip, cornell.gin:108
+    ), **overrides)
+
+
+def cornell_transient_geometry_config(**overrides) -> GeometryLossConfig:
+    return dataclasses.replace(GeometryLossConfig(
+        distortion_mult=0.0001,              # Config.distortion_loss_mult, cornell.gin:128
+        distortion_p=-0.25,                  # Config.distortion_loss_curve_fn = power_ladder(p, premult), tny.gin:263-264;
+        distortion_premult=10000.0,          # target 'tdist' (tny.gin:261), normalize_distortion_loss False (configs.py:341)
+        orientation_mult=0.0002,             # Config.orientation_loss_mult, cornell.gin:129; target 'normals_pred' (tsny.gin:71)
+        pred_normal_mult=0.0005,             # Config.predicted_normal_loss_mult, cornell.gin:130
+        pred_normal_reverse_mult=0.0025,     # Config.predicted_normal_reverse_loss_mult, cornell.gin:131
+        pred_normal_w_grad_weight=1.0,       # Config.predicted_normal_loss_stopgrad_weight, tsny.gin:65
+        use_normal_weight_ease=False,        # Config.use_normal_weight_ease, tsny.gin:73
+        use_normal_weight_ease_backward=False,   # Config.use_normal_weight_ease_backward, tsny.gin:74
+        normal_weight_ease_frac=0.0,         # tsny.gin:76
+        normal_weight_ease_start=0.0,        # tsny.gin:77
+        normal_weight_ease_min=0.01,         # tsny.gin:78 (not read while the ease is off)
+        density_grid_mult=0.01,              # Config.param_regularizers 'density_grid': (0.01, jnp.mean, 2, 1), cornell.gin:140-141
+    ), **overrides)
+
+
+def cornell_transient_mask_config(**overrides) -> MaskLossConfig:
+    return dataclasses.replace(MaskLossConfig(
+        charb_padding=1e-3,                  # Config.charb_padding, internal/configs.py:330
+        opaque_loss_weight=0.1,              # Config.opaque_loss_weight, cornell.gin:133
+        empty_loss_weight=0.1,               # Config.empty_loss_weight, cornell.gin:134 (over tny.gin:445's 1.0)
+        backward_mask_loss=True,             # Config.backward_mask_loss, cornell.gin:136
+        backward_mask_loss_weight=0.1,       # Config.backward_mask_loss_weight, cornell.gin:135
+        shadow_near_max=0.1,                 # Config.shadow_near_max, cornell.gin:172 (over tsny.gin:18's 5e-2)
+        secondary_normal_eps=0.0,            # Config.secondary_normal_eps, cornell.gin:189
+        secondary_far=1.0,                   # Config.secondary_far, cornell.gin:30
+        # the mask-weight decay and ease: no gin of the chain sets them (internal/configs.py:395-403, both off)
+    ), **overrides)

@@ -125,6 +125,7 @@ struct MatDataWs {
 struct TransDataWs {
   WsBuf rgb, G, Gt, loss_ray, dz_irr, dz_slf, x_irr, x_slf, part, ones;
   WsBuf d_t_irr, d_t_slf, d_tint_ibrdf, d_direct, d_weights;
+  WsBuf d_density, points;      // rc_transient_data_backward_sampler: d loss / d density through the weights, the means [n S][3]
 };
 
 // rc_eval_image: the bin sums of both histograms (n_bins > 0), the post-processed images where the caller gives no buffer
@@ -278,6 +279,7 @@ constexpr WsName kTable[] = {
     WS(MD, e_dhb), WS(MD, e_dxb), WS(MD, e_dh1), WS(MD, e_dh0), WS(MD, e_part), WS(MD, e_ones),
     WS(TD, rgb), WS(TD, G), WS(TD, Gt), WS(TD, loss_ray), WS(TD, dz_irr), WS(TD, dz_slf), WS(TD, x_irr), WS(TD, x_slf), WS(TD, part),
     WS(TD, ones), WS(TD, d_t_irr), WS(TD, d_t_slf), WS(TD, d_tint_ibrdf), WS(TD, d_direct), WS(TD, d_weights),
+    WS(TD, d_density), WS(TD, points),
     WS(EV, binsum_pred), WS(EV, binsum_gt), WS(EV, post_pred), WS(EV, post_gt), WS(EV, part),
     WS(EV, si_metric), WS(EV, si_state), WS(EV, si_part),
     WS(EA, pairs), WS(EA, wg), WS(EA, state), WS(EA, part),

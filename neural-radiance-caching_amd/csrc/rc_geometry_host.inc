@@ -6,6 +6,9 @@
 // (the four losses, fixed order) -> with a gradient buffer, per chunk of kDataChunk samples: h64 staged in the reference's
 // column order, pred_normals_layer's weight gradient on k_gemm (K = the chunk's samples, fixed slices), d feature64 =
 // d pred_raw W_n^T, and rc_density_backward of the last level.
+// rc_transient_geometry_backward and rc_transient_density_regularizer are the same bodies on a time-resolved handle, their
+// gradients at offsets of the one sampler buffer (RC_LAYOUT_TRANSIENT_SAMPLER, DESIGN.md §4.15b).
+// (tests/gemm_ref.py lists the dense_* call sites of this file by line.)
 
 namespace {
 
@@ -20,36 +23,35 @@ int upload_geometry_weights(rc_handle* h) {
   return upload(h, h->geom_w, v);
 }
 
-}  // namespace
-
-int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
-                         float anneal, const rc_geometry_loss* cfg, float* density_grads, float* shader_grads, float* losses,
-                         void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
+// The body of rc_geometry_backward and rc_transient_geometry_backward.  density_grads: the last level's density layout
+// (null: none); pn_grads + pn_seg[0 / 1].offset: where pred_normals_layer's kernel / bias gradient goes (pn_grads null:
+// none); allow_transient: a time-resolved handle runs (its own sampler's forward).
+int geometry_backward_impl(rc_handle* h, const std::string& who, bool allow_transient, const rc_rays* rays, const float* lossmult,
+                           int64_t n, const rc_randoms* rnd, float anneal, const rc_geometry_loss* cfg, float* density_grads,
+                           float* pn_grads, const GradSeg* pn_seg, float* losses, void* stream_v) {
   const rc_config& c = h->cfg;
   const int NL = c.num_levels;
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_geometry_backward: negative n_rays");
-  if (!rays || !cfg) return fail(h, RC_ERR_INVALID_ARG, "rc_geometry_backward: null rays/cfg");
-  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, "rc_geometry_backward: anneal must be finite and >= 0");
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n_rays");
+  if (!rays || !cfg) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/cfg");
+  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, who + ": anneal must be finite and >= 0");
   const float f[] = {cfg->distortion_mult, cfg->distortion_p, cfg->distortion_premult, cfg->orientation_mult,
                      cfg->pred_normal_mult, cfg->pred_normal_w_grad_weight, cfg->pred_normal_reverse_mult};
   for (float v : f)
-    if (!std::isfinite(v)) return fail(h, RC_ERR_INVALID_ARG, "rc_geometry_backward: the loss settings must be finite");
+    if (!std::isfinite(v)) return fail(h, RC_ERR_INVALID_ARG, who + ": the loss settings must be finite");
   if (cfg->distortion_p == 0.0f || cfg->distortion_p == 1.0f)
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_geometry_backward: distortion_p must not be 0 or 1");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_geometry_backward: not available on a time-resolved cache handle");
+    return fail(h, RC_ERR_UNSUPPORTED, who + ": distortion_p must not be 0 or 1");
+  if (h->transient && !allow_transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
   if (n == 0) return RC_OK;
-  if (!losses) return fail(h, RC_ERR_INVALID_ARG, "rc_geometry_backward: null losses");
+  if (!losses) return fail(h, RC_ERR_INVALID_ARG, who + ": null losses");
   int rc;
-  if ((rc = check_rays(h, rays, "rc_geometry_backward"))) return rc;
+  if ((rc = check_rays(h, rays, who.c_str()))) return rc;
   const int S2 = c.num_samples[NL - 1];
-  if (S2 < 1 || S2 > 32) return fail(h, RC_ERR_UNSUPPORTED, "rc_geometry_backward: needs <= 32 samples on the last level");
-  RoctxScope roctx_call("rc_geometry_backward");
+  if (S2 < 1 || S2 > 32) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs <= 32 samples on the last level");
+  RoctxScope roctx_call(who.c_str());
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
-  const bool grads = density_grads || shader_grads;
+  const bool grads = density_grads || pn_grads;
   if (grads && h->geom_gen != h->layers_gen) {
     if ((rc = upload_geometry_weights(h))) return rc;
     h->geom_gen = h->layers_gen;
@@ -100,14 +102,12 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
     return rc;
   RC_HIP(h, hipMemsetD32Async((hipDeviceptr_t)x.ones.p, 0x3f800000, 1, st));     // 1.0f: the A operand of a bias gradient
   rc_launch_points_aos(w.means[NL - 1].p, np, x.points.p, st);
-  int kseg[DL_COUNT];
-  const std::vector<GradSeg> segs = shader_grad_segments(h, kseg);
   const Dense Wn{64, 3, h->geom_w.p, nullptr};
   for (int64_t c0 = 0; c0 < np; c0 += CH) {
     const int64_t C = np - c0 < CH ? np - c0 : CH;
     const float* dp = x.d_pred.p + 3 * c0;
     rc_launch_stage_hidden(w.hbuf.p, c0, C, x.h64.p, st);
-    if (shader_grads) dense_wgrad(Wn, C, x.h64.p, 64, dp, 3, x.ones.p, x.part.p, shader_grads, &segs[kseg[DL_PRED]], st);
+    if (pn_grads) dense_wgrad(Wn, C, x.h64.p, 64, dp, 3, x.ones.p, x.part.p, pn_grads, pn_seg, st);
     if (density_grads) {
       dense_dx(Wn, C, dp, 3, x.dfeat.p, 64, 0, 64, nullptr, false, st);     // d feature64 = d pred_raw W_n^T
       RC_HIP(h, hipGetLastError());
@@ -117,6 +117,35 @@ int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmul
   }
   RC_HIP(h, hipGetLastError());
   return RC_OK;
+}
+
+}  // namespace
+
+int rc_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                         float anneal, const rc_geometry_loss* cfg, float* density_grads, float* shader_grads, float* losses,
+                         void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  int kseg[DL_COUNT];
+  std::vector<GradSeg> segs;
+  if (shader_grads && !h->transient) segs = shader_grad_segments(h, kseg);
+  return geometry_backward_impl(h, "rc_geometry_backward", false, rays, lossmult, n, rnd, anneal, cfg, density_grads, shader_grads,
+                                segs.empty() ? nullptr : &segs[kseg[DL_PRED]], losses, stream_v);
+  RC_CATCH(h)
+}
+
+int rc_transient_geometry_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                                   float anneal, const rc_geometry_loss* cfg, float* sampler_grads, float* losses, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_transient_geometry_backward";
+  if (int rc = transient_sampler_handle(h, who)) return rc;
+  int64_t off[RC_MAX_LEVELS] = {};
+  int pred = 0;
+  const std::vector<GradSeg> segs = transient_sampler_segments(h, off, &pred);
+  return geometry_backward_impl(h, who, true, rays, lossmult, n, rnd, anneal, cfg,
+                                sampler_grads ? sampler_grads + off[h->cfg.num_levels - 1] : nullptr, sampler_grads, &segs[pred], losses,
+                                stream_v);
   RC_CATCH(h)
 }
 
@@ -125,5 +154,18 @@ int rc_density_regularizer(rc_handle* h, int32_t level, float mult, float* densi
   if (!h) return RC_ERR_INVALID_ARG;
   if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, "rc_density_regularizer: bad level");
   return grid_l2_regularizer<GeometryWs>(h, level, WS_GEOMETRY, mult, density_grads, loss, stream_v, "rc_density_regularizer");
+  RC_CATCH(h)
+}
+
+int rc_transient_density_regularizer(rc_handle* h, int32_t level, float mult, float* sampler_grads, float* loss, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_transient_density_regularizer";
+  if (int rc = transient_sampler_handle(h, who)) return rc;
+  if (level < 0 || level >= h->cfg.num_levels) return fail(h, RC_ERR_INVALID_ARG, who + ": bad level");
+  int64_t off[RC_MAX_LEVELS] = {};
+  (void)transient_sampler_segments(h, off);
+  return grid_l2_regularizer<GeometryWs>(h, level, WS_GEOMETRY, mult, sampler_grads ? sampler_grads + off[level] : nullptr, loss,
+                                         stream_v, who, true);
   RC_CATCH(h)
 }

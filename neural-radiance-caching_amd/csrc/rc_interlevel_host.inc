@@ -5,30 +5,33 @@
 // k_interlevel_reduce (the losses, fixed order) -> per proposal level with a gradient buffer: the means copied from the
 // workspace's SoA [3][n S] into the AoS [n S][3] rc_density_backward takes (an exact copy: the backward evaluates the
 // forward's points; 24 bytes per sample moved, against the ~2 KB per sample the density backward itself moves), then
-// rc_density_backward of that level.
+// rc_density_backward of that level.  rc_transient_interlevel_backward is the same body on a time-resolved handle (its own
+// sampler's forward), the levels' gradients at their offsets of the one sampler buffer (DESIGN.md §4.15b).
 
-int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
-                           float anneal, const float* mults, const float* blurs, float* const* grads, float* losses,
-                           void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
+namespace {
+
+// The body of rc_interlevel_backward and rc_transient_interlevel_backward.  grads: per proposal level where its density
+// gradient goes (null, or a null entry: none); allow_transient: a time-resolved handle runs (its own sampler's forward).
+int interlevel_backward_impl(rc_handle* h, const std::string& who, bool allow_transient, const rc_rays* rays, const float* lossmult,
+                             int64_t n, const rc_randoms* rnd, float anneal, const float* mults, const float* blurs,
+                             float* const* grads, float* losses, void* stream_v) {
   const rc_config& c = h->cfg;
   const int NL = c.num_levels;
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: negative n_rays");
-  if (!rays || !mults || !blurs) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: null rays/mults/blurs");
-  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: anneal must be finite and >= 0");
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n_rays");
+  if (!rays || !mults || !blurs) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/mults/blurs");
+  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, who + ": anneal must be finite and >= 0");
   for (int l = 0; l < NL - 1; ++l) {
-    if (!std::isfinite(mults[l])) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: mults must be finite");
-    if (!(blurs[l] >= 0.0f) || !std::isfinite(blurs[l])) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: blurs must be finite and >= 0");
+    if (!std::isfinite(mults[l])) return fail(h, RC_ERR_INVALID_ARG, who + ": mults must be finite");
+    if (!(blurs[l] >= 0.0f) || !std::isfinite(blurs[l])) return fail(h, RC_ERR_INVALID_ARG, who + ": blurs must be finite and >= 0");
   }
   if (n == 0) return RC_OK;
-  if (!losses) return fail(h, RC_ERR_INVALID_ARG, "rc_interlevel_backward: null losses");
+  if (!losses) return fail(h, RC_ERR_INVALID_ARG, who + ": null losses");
   int rc;
-  if ((rc = check_rays(h, rays, "rc_interlevel_backward"))) return rc;
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_interlevel_backward: not available on a time-resolved cache handle");
+  if ((rc = check_rays(h, rays, who.c_str()))) return rc;
+  if (h->transient && !allow_transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
   if (!rc_interlevel_supported(NL, c.num_samples))
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_interlevel_backward: needs >= 2 levels, <= 64 samples per proposal level, <= 32 on the last");
-  RoctxScope roctx_call("rc_interlevel_backward");
+    return fail(h, RC_ERR_UNSUPPORTED, who + ": needs >= 2 levels, <= 64 samples per proposal level, <= 32 on the last");
+  RoctxScope roctx_call(who.c_str());
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
@@ -79,5 +82,38 @@ int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossm
   }
   RC_HIP(h, hipGetLastError());
   return RC_OK;
+}
+
+// rc_transient_*: the handle's kind, checked in front of the shared body's own checks of the handle's state
+int transient_sampler_handle(rc_handle* h, const std::string& who) {
+  if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs a time-resolved cache handle (rc_set_transient)");
+  if (h->tcfg.use_occlusions) return fail(h, RC_ERR_UNSUPPORTED, who + ": the occlusion variant is not offered (a vis_only feature)");
+  return RC_OK;
+}
+
+}  // namespace
+
+int rc_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                           float anneal, const float* mults, const float* blurs, float* const* grads, float* losses,
+                           void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  return interlevel_backward_impl(h, "rc_interlevel_backward", false, rays, lossmult, n, rnd, anneal, mults, blurs, grads, losses,
+                                  stream_v);
+  RC_CATCH(h)
+}
+
+int rc_transient_interlevel_backward(rc_handle* h, const rc_rays* rays, const float* lossmult, int64_t n, const rc_randoms* rnd,
+                                     float anneal, const float* mults, const float* blurs, float* sampler_grads, float* losses,
+                                     void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_transient_interlevel_backward";
+  if (int rc = transient_sampler_handle(h, who)) return rc;
+  int64_t off[RC_MAX_LEVELS] = {};
+  (void)transient_sampler_segments(h, off);
+  float* grads[RC_MAX_LEVELS] = {};
+  for (int l = 0; l < h->cfg.num_levels - 1; ++l) grads[l] = sampler_grads ? sampler_grads + off[l] : nullptr;
+  return interlevel_backward_impl(h, who, true, rays, lossmult, n, rnd, anneal, mults, blurs, grads, losses, stream_v);
   RC_CATCH(h)
 }

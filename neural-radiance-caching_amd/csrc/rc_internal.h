@@ -796,6 +796,17 @@ void rc_launch_transient_loss_kinds(const RcTransLossKindArgs& a, hipStream_t st
 void rc_launch_dtof_to_itof(const RcDtofToItofArgs& a, hipStream_t st);
 void rc_launch_transient_bins_bwd(const RcTransBinsBwdArgs& a, hipStream_t st);
 
+// The data loss's gradient through the compositing weights of the last level (rc_transient_sampler.hip)
+struct RcTransWeightsBwdArgs {
+  int64_t n; int32_t S;                                    // rays, samples per ray (<= 32)
+  const float* d_weights;                                  // [n S] d loss / d weights ("td:d_weights")
+  const float* weights, * density;                         // [n S] the forward's compositing weights and density of the last level
+  const float* tdist;                                      // [n][S + 1]
+  const float* directions;                                 // [n][3]
+  float* d_density;                                        // [n S] written
+};
+void rc_launch_transient_weights_bwd(const RcTransWeightsBwdArgs& a, hipStream_t st);
+
 // Evaluation of a rendered view (rc_metrics.hip).  Partial sums are doubles, one slot set per workgroup.
 struct RcEvalBinsArgs {
   const float* pred, * gt;                                 // [n_pix][n_bins][3]

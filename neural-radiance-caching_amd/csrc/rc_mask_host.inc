@@ -5,7 +5,8 @@
 // caller's jitter and anneal; rc_interlevel_backward's step 1: nothing behind the last level's density) ->
 // k_mask_loss_bwd (the last level's weights, the per-ray terms, d loss / d density) -> k_interlevel_reduce (the loss,
 // fixed order) -> with a gradient buffer, per chunk of kDataChunk samples: rc_density_backward of the last level at the
-// forward's own means.
+// forward's own means.  rc_transient_mask_backward is the same body on a time-resolved handle, the gradient at the last
+// level's offset of the one sampler buffer (DESIGN.md §4.15b).
 
 int rc_backward_mask_rays(rc_handle* h, const float* origins, const float* look, const float* u1, const float* u2, int64_t n,
                           float shadow_near_max, float normal_eps, float far, float* out_origins, float* out_directions,
@@ -29,28 +30,30 @@ int rc_backward_mask_rays(rc_handle* h, const float* origins, const float* look,
   RC_CATCH(h)
 }
 
-int rc_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, const float* lossmult, int64_t n,
-                     const rc_randoms* rnd, float anneal, const rc_mask_loss* cfg, float* density_grads, float* loss,
-                     void* stream_v) {
-  RC_TRY
-  if (!h) return RC_ERR_INVALID_ARG;
+namespace {
+
+// The body of rc_mask_backward and rc_transient_mask_backward.  density_grads: the last level's density layout (null:
+// the loss only); allow_transient: a time-resolved handle runs (its own sampler's forward).
+int mask_backward_impl(rc_handle* h, const std::string& who, bool allow_transient, const rc_rays* rays, const float* masks,
+                       const float* lossmult, int64_t n, const rc_randoms* rnd, float anneal, const rc_mask_loss* cfg,
+                       float* density_grads, float* loss, void* stream_v) {
   const rc_config& c = h->cfg;
   const int NL = c.num_levels;
-  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, "rc_mask_backward: negative n_rays");
-  if (!rays || !cfg || !loss) return fail(h, RC_ERR_INVALID_ARG, "rc_mask_backward: null rays/cfg/loss");
-  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, "rc_mask_backward: anneal must be finite and >= 0");
+  if (n < 0) return fail(h, RC_ERR_INVALID_ARG, who + ": negative n_rays");
+  if (!rays || !cfg || !loss) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/cfg/loss");
+  if (!(anneal >= 0.0f) || !std::isfinite(anneal)) return fail(h, RC_ERR_INVALID_ARG, who + ": anneal must be finite and >= 0");
   if (!std::isfinite(cfg->weight_opaque) || !std::isfinite(cfg->weight_empty))
-    return fail(h, RC_ERR_INVALID_ARG, "rc_mask_backward: the weights must be finite");
+    return fail(h, RC_ERR_INVALID_ARG, who + ": the weights must be finite");
   // d sqrt(x^2 + pad^2) / d x at pad = 0 and x = 0 is NaN in JAX: not restated
   if (!(cfg->charb_padding > 0.0f) || !std::isfinite(cfg->charb_padding))
-    return fail(h, RC_ERR_UNSUPPORTED, "rc_mask_backward: charb_padding must be finite and > 0");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, "rc_mask_backward: not available on a time-resolved cache handle");
+    return fail(h, RC_ERR_UNSUPPORTED, who + ": charb_padding must be finite and > 0");
+  if (h->transient && !allow_transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
   if (n == 0) return RC_OK;
   int rc;
-  if ((rc = check_rays(h, rays, "rc_mask_backward"))) return rc;
+  if ((rc = check_rays(h, rays, who.c_str()))) return rc;
   const int S2 = c.num_samples[NL - 1];
-  if (S2 < 1 || S2 > 32) return fail(h, RC_ERR_UNSUPPORTED, "rc_mask_backward: needs <= 32 samples on the last level");
-  RoctxScope roctx_call("rc_mask_backward");
+  if (S2 < 1 || S2 > 32) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs <= 32 samples on the last level");
+  RoctxScope roctx_call(who.c_str());
   RC_HIP(h, hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream_v;
   if ((rc = ensure_packed(h))) return rc;
@@ -97,5 +100,29 @@ int rc_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, cons
   }
   RC_HIP(h, hipGetLastError());
   return RC_OK;
+}
+
+}  // namespace
+
+int rc_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, const float* lossmult, int64_t n,
+                     const rc_randoms* rnd, float anneal, const rc_mask_loss* cfg, float* density_grads, float* loss,
+                     void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  return mask_backward_impl(h, "rc_mask_backward", false, rays, masks, lossmult, n, rnd, anneal, cfg, density_grads, loss, stream_v);
+  RC_CATCH(h)
+}
+
+int rc_transient_mask_backward(rc_handle* h, const rc_rays* rays, const float* masks, const float* lossmult, int64_t n,
+                               const rc_randoms* rnd, float anneal, const rc_mask_loss* cfg, float* sampler_grads, float* loss,
+                               void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_transient_mask_backward";
+  if (int rc = transient_sampler_handle(h, who)) return rc;
+  int64_t off[RC_MAX_LEVELS] = {};
+  (void)transient_sampler_segments(h, off);
+  return mask_backward_impl(h, who, true, rays, masks, lossmult, n, rnd, anneal, cfg,
+                            sampler_grads ? sampler_grads + off[h->cfg.num_levels - 1] : nullptr, loss, stream_v);
   RC_CATCH(h)
 }

@@ -86,13 +86,13 @@ int rc_load_params_flat(rc_handle* h, int32_t layout, const float* params, void*
   RC_TRY
   if (!h) return RC_ERR_INVALID_ARG;
   if (!params) return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: null params");
-  // a time-resolved handle loads its per-bin heads only (the other layouts' trainers do not run on it)
-  if (h->transient && layout != RC_LAYOUT_TRANSIENT_HEADS)
+  // a time-resolved handle loads its per-bin heads and its sampler side only (the other layouts' trainers do not run on it)
+  if (h->transient && layout != RC_LAYOUT_TRANSIENT_HEADS && layout != RC_LAYOUT_TRANSIENT_SAMPLER)
     return fail(h, RC_ERR_UNSUPPORTED, "rc_load_params_flat: not available on a time-resolved cache handle");
   if (layout != RC_LAYOUT_SHADER && layout != RC_LAYOUT_LIGHT && layout != RC_LAYOUT_MATERIAL && layout != RC_LAYOUT_ENVMAP &&
-      layout != RC_LAYOUT_TRANSIENT_HEADS && (layout < 0 || layout >= h->cfg.num_levels))
+      layout != RC_LAYOUT_TRANSIENT_HEADS && layout != RC_LAYOUT_TRANSIENT_SAMPLER && (layout < 0 || layout >= h->cfg.num_levels))
     return fail(h, RC_ERR_INVALID_ARG, "rc_load_params_flat: layout must be a density level, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, "
-                                       "RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP or RC_LAYOUT_TRANSIENT_HEADS");
+                                       "RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP, RC_LAYOUT_TRANSIENT_HEADS or RC_LAYOUT_TRANSIENT_SAMPLER");
   int rc;
   if ((rc = layout_check(h, layout, "rc_load_params_flat"))) return rc;
   const std::vector<GradSeg> segs = layout_segments(h, layout);

@@ -138,8 +138,25 @@ std::vector<GradSeg> transient_head_segments(rc_handle* h) {
   return v;
 }
 
+// The sampler side of the time-resolved cache in one buffer (rc_transient_*_backward): the segments of
+// density_grad_segments(0), (1), ... in their order, then MLP_<last>/pred_normals_layer [64, 3] (kernel, bias).
+// level_off[l]: where level l's segments start; *pred_seg: the index of pred_normals_layer's kernel segment.
+std::vector<GradSeg> transient_sampler_segments(rc_handle* h, int64_t* level_off = nullptr, int* pred_seg = nullptr) {
+  std::vector<GradSeg> v;
+  int64_t off = 0;
+  for (int l = 0; l < h->cfg.num_levels; ++l) {
+    if (level_off) level_off[l] = off;
+    const std::vector<GradSeg> lv = density_grad_segments(h, l);
+    for (GradSeg g : lv) { g.offset += off; v.push_back(g); }
+    off += grad_size(lv);
+  }
+  if (pred_seg) *pred_seg = (int)v.size();
+  dense_grad_segments(v, off, data_layer_path(h, DL_PRED), kDataLayers[DL_PRED].in, kDataLayers[DL_PRED].out);
+  return v;
+}
+
 // Layout ids of the ABI: a density level >= 0, RC_LAYOUT_SHADER, RC_LAYOUT_LIGHT, RC_LAYOUT_MATERIAL, RC_LAYOUT_ENVMAP,
-// RC_LAYOUT_TRANSIENT_HEADS.  `who`'s check that
+// RC_LAYOUT_TRANSIENT_HEADS, RC_LAYOUT_TRANSIENT_SAMPLER.  `who`'s check that
 // the handle has the layout (a density export maps a negative level to kNoLayout, so that it names no other layout).
 constexpr int kNoLayout = INT32_MIN;
 int layout_check(rc_handle* h, int layout, const std::string& who) {
@@ -151,7 +168,7 @@ int layout_check(rc_handle* h, int layout, const std::string& who) {
     if (h->grids[kMaterialGrid].sizes.empty()) return fail(h, RC_ERR_UNSUPPORTED, who + ": no material grid");
   } else if (layout == RC_LAYOUT_ENVMAP) {
     if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
-  } else if (layout == RC_LAYOUT_TRANSIENT_HEADS) {
+  } else if (layout == RC_LAYOUT_TRANSIENT_HEADS || layout == RC_LAYOUT_TRANSIENT_SAMPLER) {
     if (!h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": needs a time-resolved cache handle (rc_set_transient)");
   } else if (layout < 0 || layout >= h->cfg.num_levels) {
     return fail(h, RC_ERR_INVALID_ARG, who + ": bad level");
@@ -167,6 +184,7 @@ std::vector<GradSeg> layout_segments(rc_handle* h, int layout) {
     case RC_LAYOUT_MATERIAL: return material_grad_segments(h);
     case RC_LAYOUT_ENVMAP: return envmap_grad_segments(h);
     case RC_LAYOUT_TRANSIENT_HEADS: return transient_head_segments(h);
+    case RC_LAYOUT_TRANSIENT_SAMPLER: return transient_sampler_segments(h);
     default: return density_grad_segments(h, layout);
   }
 }
@@ -286,11 +304,13 @@ void dense_wgrad_tile(const Dense& L, int64_t M, const float* X, int64_t ldx, co
 // rc_{density,light,material}_regularizer after the export's own checks: mult * sum over the tables of grid `grid` of
 // 0.5 * mean(x^2) into `loss`, and mult * x / numel added into the layout `grads` (whose head is the grid's tables), on
 // the workspace set `set` (X: its extra buffers, reg_part the per-table partial sums).
+// `allow_transient`: rc_transient_density_regularizer (every other caller refuses a time-resolved handle).
 template <class X>
-int grid_l2_regularizer(rc_handle* h, int grid, int set, float mult, float* grads, float* loss, void* stream_v, const std::string& who) {
+int grid_l2_regularizer(rc_handle* h, int grid, int set, float mult, float* grads, float* loss, void* stream_v, const std::string& who,
+                        bool allow_transient = false) {
   if (!std::isfinite(mult)) return fail(h, RC_ERR_INVALID_ARG, who + ": mult must be finite");
   if (!loss) return fail(h, RC_ERR_INVALID_ARG, who + ": null loss");
-  if (h->transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
+  if (h->transient && !allow_transient) return fail(h, RC_ERR_UNSUPPORTED, who + ": not available on a time-resolved cache handle");
   const GridState& gs = h->grids[grid];
   const int T = (int)gs.sizes.size();
   if (T < 1 || T > RC_MAX_GRID_LEVELS) return fail(h, RC_ERR_UNSUPPORTED, who + ": unexpected grid levels");
@@ -368,6 +388,12 @@ int64_t rc_transient_head_grad_size(rc_handle* h) {
 }
 int rc_transient_head_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
   return layout_grad_layout(h, RC_LAYOUT_TRANSIENT_HEADS, segs, capacity, count, "rc_transient_head_grad_layout");
+}
+int64_t rc_transient_sampler_grad_size(rc_handle* h) {
+  return layout_grad_size(h, RC_LAYOUT_TRANSIENT_SAMPLER, "rc_transient_sampler_grad_size");
+}
+int rc_transient_sampler_grad_layout(rc_handle* h, rc_grad_segment* segs, int32_t capacity, int32_t* count) {
+  return layout_grad_layout(h, RC_LAYOUT_TRANSIENT_SAMPLER, segs, capacity, count, "rc_transient_sampler_grad_layout");
 }
 
 int rc_density_grad_layout(rc_handle* h, int32_t level, rc_grad_segment* segs, int32_t capacity, int32_t* count) {

@@ -1,4 +1,4 @@
-// Host side of rc_transient_data_backward, rc_transient_data_backward_kind and rc_dtof_to_itof (rc_transient_bwd.hip); included by rc_api.hip.
+// Host side of rc_transient_data_backward, _kind, _sampler (rc_transient_sampler.hip) and rc_dtof_to_itof (rc_transient_bwd.hip); included by rc_api.hip.
 //
 // One call = rc_render_transient itself (its "rgb" histograms to "td:rgb") -> k_transient_loss[_kinds] (G, the filter's transpose
 // Gt, the per-ray loss and mse sums) -> k_interlevel_reduce (the two scalars, fixed order) -> per chunk of kRcTdChunkRays
@@ -195,6 +195,52 @@ int rc_transient_data_backward_kind(rc_handle* h, const rc_rays* rays, const flo
   if (!cfg && h->transient && !h->tcfg.use_occlusions) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/cfg");
   return transient_data_backward_impl(h, who, rays, cam_origins, n, rnd, gt, rgb_nocorr, gt_nocorr, lossmult,
                                       cfg ? &cfg->base : nullptr, cfg, head_grads, losses, stream_v);
+  RC_CATCH(h)
+}
+
+// rc_transient_data_backward_kind, then the weights path of its gradient into the last level's segments of the sampler
+// layout: k_transient_weights_bwd ("td:d_weights" -> "td:d_density" on the forward's density, tdist and weights of set 0)
+// and rc_density_backward of the last level at the forward's means, in chunks of kDataChunk samples.
+int rc_transient_data_backward_sampler(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
+                                       const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
+                                       const rc_transient_data_loss_kind* cfg, float* head_grads, float* sampler_grads,
+                                       float* losses, void* stream_v) {
+  RC_TRY
+  if (!h) return RC_ERR_INVALID_ARG;
+  const std::string who = "rc_transient_data_backward_sampler";
+  if (!cfg && h->transient && !h->tcfg.use_occlusions) return fail(h, RC_ERR_INVALID_ARG, who + ": null rays/cfg");
+  int rc;
+  if ((rc = transient_data_backward_impl(h, who, rays, cam_origins, n, rnd, gt, rgb_nocorr, gt_nocorr, lossmult,
+                                         cfg ? &cfg->base : nullptr, cfg, head_grads, losses, stream_v)))
+    return rc;
+  if (n == 0 || !sampler_grads) return RC_OK;
+  const int NL = h->cfg.num_levels;
+  const int S2 = h->cfg.num_samples[NL - 1];               // 32 (rc_set_transient)
+  const int64_t np = n * S2;
+  hipStream_t st = (hipStream_t)stream_v;
+  int64_t off[RC_MAX_LEVELS] = {};
+  (void)transient_sampler_segments(h, off);
+  WsUse use_d(h, WS_TRANSDATA, st);
+  if ((rc = use_d.rc)) return rc;
+  TransDataWs& y = ws_extra<TransDataWs>(use_d.s);
+  if ((rc = ws_alloc(h, {{y.d_density, np}, {y.points, 3 * np}}))) return rc;
+  WsUse use(h, WS_RENDER0, st);          // the forward's buffers, as step 3 of the shared body reads them
+  if ((rc = use.rc)) return rc;
+  RenderWs& w = use.s.r;
+  RcTransWeightsBwdArgs a{};
+  a.n = n; a.S = S2; a.d_weights = y.d_weights.p; a.weights = w.weights[NL - 1].p; a.density = w.density[NL - 1].p;
+  a.tdist = w.tdist[NL - 1].p; a.directions = rays->directions; a.d_density = y.d_density.p;
+  rc_launch_transient_weights_bwd(a, st);
+  rc_launch_points_aos(w.means[NL - 1].p, np, y.points.p, st);
+  RC_HIP(h, hipGetLastError());
+  for (int64_t c0 = 0; c0 < np; c0 += kDataChunk) {
+    const int64_t C = np - c0 < kDataChunk ? np - c0 : kDataChunk;
+    if ((rc = rc_density_backward(h, NL - 1, y.points.p + 3 * c0, C, y.d_density.p + c0, nullptr, sampler_grads + off[NL - 1], nullptr,
+                                  stream_v)))
+      return rc;
+  }
+  RC_HIP(h, hipGetLastError());
+  return RC_OK;
   RC_CATCH(h)
 }
 

@@ -219,6 +219,7 @@ RC_LAYOUT_LIGHT = -2
 RC_LAYOUT_MATERIAL = -3
 RC_LAYOUT_ENVMAP = -4
 RC_LAYOUT_TRANSIENT_HEADS = -5
+RC_LAYOUT_TRANSIENT_SAMPLER = -6
 
 
 class rc_light_sampling_loss(C.Structure):
@@ -367,7 +368,7 @@ class rc_adam_step(C.Structure):
                 + [("grad_max_val", C.c_float), ("grad_max_norm", C.c_float), ("zero_grads", C.c_int32)])
 
 
-# Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap", "transient_heads": the C functions of its size and of its
+# Gradient layouts by key -- a density level (int), "shader", "light", "material", "envmap", "transient_heads", "transient_sampler": the C functions of its size and of its
 # segments (a density level is their first argument) and its RC_LAYOUT_* id (rc_load_params_flat; a level is its own).
 _GRAD_LAYOUTS = {
     int: ("rc_density_grad_size", "rc_density_grad_layout", None),
@@ -376,6 +377,7 @@ _GRAD_LAYOUTS = {
     "material": ("rc_material_grad_size", "rc_material_grad_layout", RC_LAYOUT_MATERIAL),
     "envmap": ("rc_envmap_grad_size", "rc_envmap_grad_layout", RC_LAYOUT_ENVMAP),
     "transient_heads": ("rc_transient_head_grad_size", "rc_transient_head_grad_layout", RC_LAYOUT_TRANSIENT_HEADS),
+    "transient_sampler": ("rc_transient_sampler_grad_size", "rc_transient_sampler_grad_layout", RC_LAYOUT_TRANSIENT_SAMPLER),
 }
 _LAYOUT_KEYS = {row[2]: key for key, row in _GRAD_LAYOUTS.items() if key is not int}
 
@@ -444,6 +446,13 @@ _PROTOTYPES = {
                                              _P, _P, _P]),
     "rc_transient_data_backward_kind": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P,
                                                   C.POINTER(rc_transient_data_loss_kind), _P, _P, _P]),
+    "rc_transient_data_backward_sampler": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _P, _P, _P, _P,
+                                                     C.POINTER(rc_transient_data_loss_kind), _P, _P, _P, _P]),
+    "rc_transient_interlevel_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                   _P, _P, _P]),
+    "rc_transient_geometry_backward": (C.c_int, [_H, _RAYS, _P, _I64, _RND, _F, C.POINTER(rc_geometry_loss), _P, _P, _P]),
+    "rc_transient_mask_backward": (C.c_int, [_H, _RAYS, _P, _P, _I64, _RND, _F, C.POINTER(rc_mask_loss), _P, _P, _P]),
+    "rc_transient_density_regularizer": (C.c_int, [_H, _I32, _F, _P, _P, _P]),
     "rc_dtof_to_itof": (C.c_int, [_H, _P, _I64, _I32, C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P]),
     "rc_eval_image": (C.c_int, [_H, C.POINTER(rc_eval_images), _P, _P]),
     "rc_eval_shift_invariant": (C.c_int, [_H, C.POINTER(rc_eval_si_images), _P, _P]),
@@ -463,7 +472,7 @@ _PROTOTYPES = {
     "rc_render_relight": (C.c_int, [_H, _RAYS, _I64, _RND, _MRND, _I32, C.POINTER(rc_relight_args), _OUT,
                                     C.POINTER(rc_mat_outputs), _P]),
 }
-for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the five named layouts
+for _size, _layout, _ in (row for key, row in _GRAD_LAYOUTS.items() if key is not int):        # the named layouts
     _PROTOTYPES[_size] = (C.c_int64, [_H])
     _PROTOTYPES[_layout] = (C.c_int, [_H, _P, _I32, C.POINTER(C.c_int32)])
 EXPORTS = tuple(_PROTOTYPES)
@@ -1247,7 +1256,7 @@ class RadianceCache:
 
     def load_params_flat(self, layout, params, stream_handle=None):
         """rc_load_params_flat: load every tensor of one gradient layout (a density level, "shader", "light", "material",
-        "envmap" or, on a time-resolved handle, "transient_heads") from a flat float32 cuda buffer in that layout -- table
+        "envmap" or, on a time-resolved handle, "transient_heads" / "transient_sampler") from a flat float32 cuda buffer in that layout -- table
         copies ordered on the current stream, the dense layers in one copy to the host (the call waits for the stream
         there).  Renders afterwards equal those after load_weights of the same tensors, bitwise."""
         torch = self._torch
@@ -1541,18 +1550,10 @@ class RadianceCache:
         (params/Cache/Shader/transient_indirect_layer, .../SurfaceLightField/output_rgba_layer), and its size in floats."""
         return self._grad_layout("transient_heads")
 
-    def transient_data_backward(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]], gt, rgb_nocorr=None,
-                                gt_nocorr=None, lossmult=None, cfg=None, grad=None, stream_handle=None):
-        """rc_transient_data_backward / rc_transient_data_backward_kind: render_transient with the same rays (lights and
-        cam_origins included) / randoms ({"jitter": [u0, u1, u2]} or None), the time-resolved data loss against gt
-        ([n, n_bins, 3]) with the constants of cfg (config.TransientDataLossConfig; config.transient_data_loss_preset names
-        the gins' readings) and its gradient w.r.t. the two per-bin head layers (transient_head_grad_layout; DESIGN.md
-        §4.15).  cfg.loss_type is one of TRANSIENT_LOSS_TYPES; cfg.use_itof and cfg.itof_frequency_phase_shifts
-        ((frequency, phase) pairs, at most RC_ITOF_MAX_PAIRS) as the reference's Config.  The default reading goes through
-        the first export, every other one through the second.  rgb_nocorr / gt_nocorr: [n, n_bins, 3] or None (this render,
-        gt).  grad: flat buffer to accumulate into (allocated zeroed when None); grad=False leaves the heads' gradient out
-        (the loss and the "td:" adjoints are still computed).  Returns (grad flat or None, losses [2] cuda tensor: loss,
-        mse)."""
+    def _transient_data_args(self, rays, randoms, gt, rgb_nocorr, gt_nocorr, lossmult, cfg):
+        """What transient_data_backward and transient_data_backward_sampler hand to their exports: (cfg, whether it is the
+        default reading, rc_rays, the tensors kept alive, n, cam_origins, rc_randoms or None, lossmult, the three histogram
+        pointers)."""
         from .config import TransientDataLossConfig
 
         cfg = TransientDataLossConfig() if cfg is None else cfg
@@ -1581,6 +1582,22 @@ class RadianceCache:
         gt_p, rn_p, gn_p = hist(gt, "gt"), hist(rgb_nocorr, "rgb_nocorr"), hist(gt_nocorr, "gt_nocorr")
         if gt_p is None:
             raise ValueError("gt is required")
+        return cfg, plain, r, held, n, cam, rnd_p, lm, gt_p, rn_p, gn_p
+
+    def transient_data_backward(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]], gt, rgb_nocorr=None,
+                                gt_nocorr=None, lossmult=None, cfg=None, grad=None, stream_handle=None):
+        """rc_transient_data_backward / rc_transient_data_backward_kind: render_transient with the same rays (lights and
+        cam_origins included) / randoms ({"jitter": [u0, u1, u2]} or None), the time-resolved data loss against gt
+        ([n, n_bins, 3]) with the constants of cfg (config.TransientDataLossConfig; config.transient_data_loss_preset names
+        the gins' readings) and its gradient w.r.t. the two per-bin head layers (transient_head_grad_layout; DESIGN.md
+        §4.15).  cfg.loss_type is one of TRANSIENT_LOSS_TYPES; cfg.use_itof and cfg.itof_frequency_phase_shifts
+        ((frequency, phase) pairs, at most RC_ITOF_MAX_PAIRS) as the reference's Config.  The default reading goes through
+        the first export, every other one through the second.  rgb_nocorr / gt_nocorr: [n, n_bins, 3] or None (this render,
+        gt).  grad: flat buffer to accumulate into (allocated zeroed when None); grad=False leaves the heads' gradient out
+        (the loss and the "td:" adjoints are still computed).  Returns (grad flat or None, losses [2] cuda tensor: loss,
+        mse)."""
+        cfg, plain, r, held, n, cam, rnd_p, lm, gt_p, rn_p, gn_p = self._transient_data_args(rays, randoms, gt, rgb_nocorr,
+                                                                                             gt_nocorr, lossmult, cfg)
         c = transient_data_loss_c(cfg)
         flat, losses, stream = self._loss_prologue("transient_heads", grad, stream_handle, slots=2)
         if plain:
@@ -1593,6 +1610,103 @@ class RadianceCache:
                                                                  stream))
         self._keep = [held]
         return flat, losses
+
+    # -- the time-resolved cache's density fields and proposal samplers -----------------
+    def transient_sampler_grad_layout(self):
+        """rc_transient_sampler_grad_layout: [(tensor name, offset, shape)] of the time-resolved cache's sampler side in one
+        buffer (density_grad_layout(0), (1), (2) in turn, then MLP_<last>/pred_normals_layer), and its size in floats."""
+        return self._grad_layout("transient_sampler")
+
+    def transient_data_backward_sampler(self, rays: Dict[str, object], randoms: Optional[Dict[str, object]], gt, rgb_nocorr=None,
+                                        gt_nocorr=None, lossmult=None, cfg=None, grad=None, sampler_grad=None,
+                                        stream_handle=None):
+        """rc_transient_data_backward_sampler: transient_data_backward (same arguments, same losses, adjoints and head
+        gradient, bitwise) plus the data loss's gradient of MLP_<last> through the compositing weights -- the weights path
+        only, see DESIGN.md §4.15b -- accumulated into sampler_grad (transient_sampler_grad_layout; allocated zeroed when
+        None; False: left out, nothing beyond transient_data_backward runs).  "td:d_density" holds d loss / d density.
+        Returns (head flat or None, sampler flat or None, losses [2])."""
+        cfg, _, r, held, n, cam, rnd_p, lm, gt_p, rn_p, gn_p = self._transient_data_args(rays, randoms, gt, rgb_nocorr,
+                                                                                         gt_nocorr, lossmult, cfg)
+        ck = transient_data_loss_kind_c(cfg)
+        flat, losses, stream = self._loss_prologue("transient_heads", grad, stream_handle, slots=2)
+        sflat = None if sampler_grad is False else self._grad_buffer(sampler_grad, self._grad_size("transient_sampler"),
+                                                                     "sampler_grad")
+        self._check(self.lib.rc_transient_data_backward_sampler(self._h, C.byref(r), cam.data_ptr(), n, rnd_p, gt_p, rn_p, gn_p,
+                                                                _ptr(lm), C.byref(ck), _ptr(flat), _ptr(sflat),
+                                                                losses.data_ptr(), stream))
+        self._keep = [held]
+        return flat, sflat, losses
+
+    def transient_interlevel_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, mults=(0.01, 0.01),
+                                      blurs=(0.03, 0.003), lossmult=None, grad=None):
+        """rc_transient_interlevel_backward: interlevel_backward on a time-resolved handle (its own sampler's forward).
+        grad: the flat buffer of transient_sampler_grad_layout to accumulate into (allocated zeroed when None; False: the
+        losses only).  Returns (sampler flat or None, losses [num_levels - 1] cuda tensor)."""
+        r, held, n = self._rays_struct(rays)
+        nprop = self.cfg.num_levels - 1
+        if len(mults) != nprop or len(blurs) != nprop:
+            raise ValueError(f"mults and blurs need {nprop} values")
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
+        flat, losses, stream = self._loss_prologue("transient_sampler", grad, slots=max(nprop, 1))
+        m = (C.c_float * nprop)(*[float(v) for v in mults])
+        b = (C.c_float * nprop)(*[float(v) for v in blurs])
+        self._check(self.lib.rc_transient_interlevel_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), m, b,
+                                                              _ptr(flat), losses.data_ptr(), stream))
+        self._keep = [held]
+        return flat, losses
+
+    def transient_geometry_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, lossmult=None, terms=None,
+                                    grad=None):
+        """rc_transient_geometry_backward: geometry_backward on a time-resolved handle; the density gradient goes to the
+        last level's segments of the sampler flat, pred_normals_layer's to its tail.  terms as geometry_backward (the
+        distortion curve defaults to the gins' -0.25 / 1e4).  grad as transient_interlevel_backward.
+        Returns (sampler flat or None, losses [4] cuda tensor)."""
+        r, held, n = self._rays_struct(rays)
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
+        t = {"distortion_p": -0.25, "distortion_premult": 1e4}
+        t.update(terms or {})
+        unknown = set(t) - {k for k, _ in rc_geometry_loss._fields_}
+        if unknown:
+            raise ValueError(f"unknown geometry loss fields {sorted(unknown)}")
+        cfg = rc_geometry_loss(**{k: float(v) for k, v in t.items()})
+        flat, losses, stream = self._loss_prologue("transient_sampler", grad, slots=4)
+        self._check(self.lib.rc_transient_geometry_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg),
+                                                            _ptr(flat), losses.data_ptr(), stream))
+        self._keep = [held]
+        return flat, losses
+
+    def transient_mask_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, masks=None, lossmult=None,
+                                terms=None, grad=None):
+        """rc_transient_mask_backward: mask_backward on a time-resolved handle (rays of backward_mask_rays included); the
+        gradient goes to the last level's segments of the sampler flat.  grad as transient_interlevel_backward.
+        Returns (sampler flat or None, loss [1] cuda tensor)."""
+        r, held, n = self._rays_struct(rays)
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
+        mk = None
+        if masks is not None:
+            mk = self._dev(masks).reshape(-1)
+            if mk.shape[0] != n:
+                raise ValueError("masks must have one value per ray")
+            held["masks"] = mk
+        t = {"charb_padding": 1e-3, "weight_opaque": 1.0, "weight_empty": 1.0, "zero_masks": 0}
+        t.update(terms or {})
+        unknown = set(t) - {k for k, _ in rc_mask_loss._fields_}
+        if unknown:
+            raise ValueError(f"unknown mask loss fields {sorted(unknown)}")
+        cfg = rc_mask_loss(float(t["charb_padding"]), float(t["weight_opaque"]), float(t["weight_empty"]), int(bool(t["zero_masks"])))
+        flat, loss, stream = self._loss_prologue("transient_sampler", grad)
+        self._check(self.lib.rc_transient_mask_backward(self._h, C.byref(r), _ptr(mk), _ptr(lm), n, rnd_p, float(anneal),
+                                                        C.byref(cfg), _ptr(flat), loss.data_ptr(), stream))
+        self._keep = [held]
+        return flat, loss
+
+    def transient_density_regularizer(self, level: int, mult: float, grad=None):
+        """rc_transient_density_regularizer: density_regularizer of grid `level` on a time-resolved handle, the gradient
+        into that level's table segments of the sampler flat.  Returns (sampler flat or None, loss [1] cuda tensor)."""
+        return self._regularizer(self.lib.rc_transient_density_regularizer, "transient_sampler", (int(level), float(mult)), grad)
 
     def dtof_to_itof(self, x, pairs, stream_handle=None):
         """rc_dtof_to_itof (render_utils.dtof_to_itof): x [n, n_bins, 3] histograms (a cuda tensor is used where it is) ->

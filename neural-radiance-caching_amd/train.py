@@ -861,3 +861,110 @@ def transient_head_step(rc, opt: TransientHeadOptimizer, rays, cam_origins, jitt
     transient_data_grads."""
     return _train_step(opt, group, lambda tf: transient_data_grads(rc, rays, cam_origins, jitters, gt, rgb_nocorr, gt_nocorr,
                                                                    lossmult, opt.grads["transient_heads"], cfg))
+
+
+# ---- the time-resolved cache's density fields and proposal samplers (DESIGN.md §4.15b) ---------------------------------
+
+def transient_sampler_layout(cfg):
+    """Python mirror of rc_transient_sampler_grad_layout: ([(name, offset, shape)], total floats).  Per level the density
+    grid's tables in level order and the three density layers (kernel, bias each) -- weights.param_shapes lists them in
+    this order --, then MLP_<last>/pred_normals_layer."""
+    from .weights import param_shapes
+
+    shapes = param_shapes(cfg)
+    pred = f"params/Cache/Sampler/MLP_{cfg.num_levels - 1}/pred_normals_layer/"
+    names = [k for l in range(cfg.num_levels) for k in shapes
+             if k.startswith(f"params/Cache/Sampler/MLP_{l}/") and not k.startswith(pred)]
+    names += [pred + "kernel", pred + "bias"]
+    out, off = [], 0
+    for k in names:
+        out.append((k, off, tuple(shapes[k])))
+        off += int(np.prod(shapes[k]))
+    return out, off
+
+
+def transient_sampler_grads(rc, rays, cam_origins, jitters, gt, train_frac: float, rgb_nocorr=None, gt_nocorr=None,
+                            lossmult=None, flats=None, data_cfg: TransientDataLossConfig = TransientDataLossConfig(),
+                            interlevel_cfg: Optional[InterlevelConfig] = None, geometry_cfg: Optional[GeometryLossConfig] = None,
+                            mask_cfg: Optional[MaskLossConfig] = None, masks=None, look=None, backward_randoms=None,
+                            scale: float = 1.0):
+    """The time-resolved cache stage's losses on a batch and their gradients of the per-bin heads and of the sampler side
+    (the three density fields and pred_normals_layer): the transient data loss with its weights path into MLP_<last>
+    (rc_transient_data_backward_sampler), the spline interlevel loss, the four geometry terms, the mask loss and -- with
+    look and backward_randoms, as mask_grads takes them -- its backward term, and the density-grid regularizer of every
+    level.  The configs default to the cornell gin's (config.cornell_transient_*_config); train_frac sets the anneal.
+    flats: {"transient_heads": flat, "transient_sampler": flat} to accumulate into (allocated zeroed when missing).
+    scale multiplies the interlevel, geometry and mask terms (one copy of each is computed; the data loss and the
+    regularizer count once).  The shader trunk and the appearance grid get no gradient, and the data loss reaches MLP_<last>
+    through the compositing weights only.
+    -> (flats, losses): data, mse, interlevel_<l>, the GEOMETRY_KEYS, mask[, mask_backwards], regularizer/density_grid."""
+    from . import config as _config
+
+    il = _config.cornell_transient_interlevel_config() if interlevel_cfg is None else interlevel_cfg
+    ge = _config.cornell_transient_geometry_config() if geometry_cfg is None else geometry_cfg
+    mk = _config.cornell_transient_mask_config() if mask_cfg is None else mask_cfg
+    flats = dict(flats or {})
+    rays = dict(rays)
+    if cam_origins is not None:
+        rays["cam_origins"] = cam_origins
+    randoms = None if jitters is None else {"jitter": list(jitters)}
+    anneal = anneal_at(train_frac, il)
+    heads, sampler, d_losses = rc.transient_data_backward_sampler(rays, randoms, gt, rgb_nocorr, gt_nocorr, lossmult, data_cfg,
+                                                                  flats.get("transient_heads"), flats.get("transient_sampler"))
+    losses = {"data": d_losses[0], "mse": d_losses[1]}
+    sampler, il_losses = rc.transient_interlevel_backward(rays, jitters, anneal, tuple(scale * m for m in il.mults), il.blurs,
+                                                          lossmult, sampler)
+    for l in range(rc.cfg.num_levels - 1):
+        losses[f"interlevel_{l}"] = il_losses[l]
+    sampler, g_losses = rc.transient_geometry_backward(rays, jitters, anneal, lossmult, geometry_terms(train_frac, ge, scale),
+                                                       sampler)
+    for k, key in enumerate(GEOMETRY_KEYS):
+        losses[key] = g_losses[k]
+    terms = mask_terms(train_frac, mk, scale)
+    sampler, m_loss = rc.transient_mask_backward(rays, jitters, anneal, masks, lossmult, terms["mask"], sampler)
+    losses["mask"] = m_loss[0]
+    if mk.backward_mask_loss and look is not None and backward_randoms is not None:
+        back = rc.backward_mask_rays(rays["origins"], look, backward_randoms["u1"], backward_randoms["u2"], mk.shadow_near_max,
+                                     mk.secondary_normal_eps, mk.secondary_far)
+        sampler, m_loss = rc.transient_mask_backward(back, backward_randoms.get("jitter"), anneal, None, lossmult,
+                                                     terms["mask_backwards"], sampler)
+        losses["mask_backwards"] = m_loss[0]
+    reg = None
+    for l in range(rc.cfg.num_levels):
+        sampler, r = rc.transient_density_regularizer(l, ge.density_grid_mult, sampler)
+        reg = r if reg is None else reg + r
+    losses["regularizer/density_grid"] = reg[0]
+    flats["transient_heads"], flats["transient_sampler"] = heads, sampler
+    return flats, losses
+
+
+class TransientSamplerOptimizer(CacheStageOptimizer):
+    """The optimizer state of the time-resolved cache stage on the device: the sampler side in ONE flat buffer (key
+    "transient_sampler": rc.transient_sampler_grad_layout()) and, with heads=True, the two per-bin head layers beside it (key
+    "transient_heads"); params, mu, nu, gradients and the optax count.  param_group puts every sampler tensor in "Cache", as
+    create_optimizer folds the prefixes (TransientHeadOptimizer names the heads' groups).  grad_max_norm > 0 is refused for
+    TransientHeadOptimizer's reason: the norm is per top-level module, and params/Cache holds the shader trunk and the
+    appearance grid, which this optimizer does not.  A step is ONE rc_adam_update over its buffers, then rc_load_params_flat
+    per layout."""
+
+    def __init__(self, rc, cfg: OptimizerConfig = OptimizerConfig(), heads: bool = True):
+        if cfg.grad_max_norm > 0:
+            raise NotImplementedError("TransientSamplerOptimizer: grad_max_norm needs the norm over all of params/Cache")
+        super().__init__(rc, cfg, (["transient_heads"] if heads else []) + ["transient_sampler"])
+
+
+def transient_cache_stage_step(rc, opt: TransientSamplerOptimizer, rays, cam_origins, jitters, gt, rgb_nocorr=None,
+                               gt_nocorr=None, lossmult=None, group=None,
+                               data_cfg: TransientDataLossConfig = TransientDataLossConfig(),
+                               interlevel_cfg: Optional[InterlevelConfig] = None,
+                               geometry_cfg: Optional[GeometryLossConfig] = None, mask_cfg: Optional[MaskLossConfig] = None,
+                               masks=None, look=None, backward_randoms=None, scale: float = 1.0):
+    """One train step of the time-resolved cache stage, heads and sampler side together: transient_sampler_grads into the
+    optimizer's zeroed gradient buffers, the pmean over `group` when torch.distributed runs, then opt.step() (ONE
+    rc_adam_update, the handle's refresh).  opt: a TransientSamplerOptimizer with heads=True.
+    -> the losses dict of transient_sampler_grads."""
+    if "transient_heads" not in opt.keys:
+        raise ValueError("transient_cache_stage_step needs TransientSamplerOptimizer(heads=True)")
+    return _train_step(opt, group, lambda tf: transient_sampler_grads(
+        rc, rays, cam_origins, jitters, gt, tf, rgb_nocorr, gt_nocorr, lossmult, dict(opt.grads), data_cfg, interlevel_cfg,
+        geometry_cfg, mask_cfg, masks, look, backward_randoms, scale))
