@@ -294,7 +294,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
  * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env,
  * "td:" = rc_transient_data_backward, "mk:" = rc_mask_backward, "nb:" = rc_normals_backward,
- * "gs:" = rc_geometry_smoothness_backward.
+ * "gs:" = rc_geometry_smoothness_backward, "q:" = rc_query_points / rc_density_lattice, "iso:" = rc_isosurface (their
+ * buffers are listed at those calls).
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -1534,6 +1535,51 @@ int rc_probe_rays(rc_handle* h, const rc_probe_view* view, const int64_t* pixel,
 int rc_vmf_panorama(rc_handle* h, const float* means, const float* kappas, const float* logits, int32_t P, int32_t V,
                     int32_t height, int32_t width, int32_t flip, float* out_linear, float* out_srgb, uint8_t* out_u8,
                     void* stream);
+
+/* -- surface export: the handle's fields at arbitrary points, the density on a lattice, and the
+ * isosurface of any device lattice as a triangle mesh.
+ *
+ * rc_query_points: points [n,3] world coordinates on the device; every output is nullable.
+ *   density [n]         predict_density of sampler level `level` (level < 0: the last): the grid lookup with the
+ *                       contraction, density_layers_*, output_density_layer, safe_exp(raw + density_bias), gated to 0 outside
+ *                       the contracted box -- what the launch-per-stage level path computes for its sample means
+ *   normals_pred [n,3]  nan_to_num(-l2_normalize(pred_normals_layer(h))), last level only
+ *   normals [n,3]       the analytic normals nan_to_num(-l2_normalize(d raw / d x)), last level only; neither is rectified
+ *                       (there is no view direction)
+ *   material [n,5]      albedo rgb, roughness, metalness of the material head on the material grid's features
+ * The existing forward kernels run on chunks of 131 072 points, so the workspace ("q:" names of rc_workspace_ptr: "means"
+ * (SoA [3][C] of the last chunk), "feat", "jac", "density", "normals_pred", "normals_grad", "m_feat") is bounded whatever n is.
+ * RC_ERR_INVALID_ARG: n < 0, NULL points with n > 0, level >= num_levels.  RC_ERR_UNSUPPORTED: normals_pred / normals on
+ * another level than the last, material on a time-resolved handle (which is accepted for the other three outputs).
+ * RC_ERR_MISSING_WEIGHT: material without the material weights, a missing grid table.  n == 0 returns RC_OK and launches
+ * nothing.  Everything is ordered on `stream`.
+ *
+ * rc_density_lattice: field [nx,ny,nz] on the device, row-major with iz fastest (the `ij` meshgrid of the reference's
+ * mesh script); lo / hi: HOST float[3].  Point i of axis a sits at lo[a] + (float)i * ((hi[a] - lo[a]) / (float)(n_a - 1)),
+ * evaluated in fp32 in exactly this form (linspace up to its last bits; torch.linspace's two-sided formula differs there, on
+ * purpose).  The value is rc_query_points' density with nan_to_num applied; the points are generated on the device slab by
+ * slab ("q:" workspace, it does not grow with the lattice).  RC_ERR_INVALID_ARG: a dimension outside 2 .. 1024,
+ * hi[a] <= lo[a], level >= num_levels, NULL field.
+ *
+ * rc_isosurface: marching tetrahedra on the Kuhn decomposition of every lattice cell (csrc/rc_iso_table.h states the
+ * rule).  field: ANY device lattice in the layout above.  A point is inside when f >= iso (a NaN is outside).  One vertex per
+ * lattice edge, face diagonal or body diagonal of the decomposition whose ends differ, numbered by (lower end's linear index,
+ * direction number); position by linear interpolation with the parameter clamped to [0, 1]; normals (nullable, [V,3]) =
+ * -normalize of the lattice's central-difference gradient (one-sided at the border) interpolated the same way, (0,0,0) for a
+ * zero gradient.  Triangles [T,3] int32 in cell order, oriented so that their normals point towards lower field values.
+ * counts: device int64[2] = {V, T}, always written.  vertices / normals / triangles are written only if V <= v_capacity and
+ * T <= t_capacity; otherwise only counts is written and the call still returns RC_OK -- call with capacities 0, read
+ * counts, allocate, call again.  No atomics: two calls on one lattice give bitwise the same arrays.
+ * RC_ERR_INVALID_ARG: a dimension outside 2 .. 1024, hi[a] <= lo[a], NULL field / counts, a NaN iso, a negative capacity,
+ * v_capacity > INT32_MAX, a NULL array with a non-zero capacity.  Workspace: "iso:" names "mask", "tcount" (bytes per lattice
+ * point), "vbase" (int32 per point), "tile_v", "tile_t", "group_v", "group_t", "group_off", "state". */
+int rc_query_points(rc_handle* h, const float* points, int64_t n, int32_t level, float* density, float* normals_pred,
+                    float* normals, float* material, void* stream);
+int rc_density_lattice(rc_handle* h, const float* lo, const float* hi, int32_t nx, int32_t ny, int32_t nz, int32_t level,
+                       float* field, void* stream);
+int rc_isosurface(rc_handle* h, const float* field, int32_t nx, int32_t ny, int32_t nz, float iso, const float* lo,
+                  const float* hi, float* vertices, float* normals, int64_t v_capacity, int32_t* triangles,
+                  int64_t t_capacity, int64_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

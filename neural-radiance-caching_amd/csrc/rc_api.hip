@@ -158,6 +158,13 @@ struct NormalsWs { WsBuf feat, jac, gf, ghat, u, t0, a0, t1, a2, ones, partial, 
 // reads them) with their features, Jacobian, density and analytic normals; the means and perturbed means as points [n S][3];
 // d loss / d normals and d loss / d density at both point sets; the per-ray loss values.
 struct GSmoothWs { WsBuf means_p, feat_p, jac_p, density_p, normals_p, points, points_p, d_normals, d_normals_p, d_density, d_density_p, loss_ray; };
+// rc_query_points / rc_density_lattice, one chunk of points: the points as SoA [3][C], the grid features (feature-major)
+// and their Jacobian, the density where the caller wants none, both kinds of normals as SoA, the material grid's features.
+struct QueryWs { WsBuf means, feat, jac, density, normals_pred, normals_grad, m_feat; };
+// rc_isosurface (RcIsoArgs): per lattice point the mask of crossing owned edges and the cell's triangle count (bytes) and
+// the index of its first vertex (int32), per tile and per group the sums / offsets of both scans (int32; int64 pairs), the
+// RcIsoState.
+struct IsoWs { WsBuf mask, tcount, tile_v, tile_t, group_v, group_t, group_off, vbase, state; };
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
@@ -170,15 +177,15 @@ struct GSmoothWs { WsBuf means_p, feat_p, jac_p, density_p, normals_p, points, p
 // WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
 // rc_eval_image and rc_eval_shift_invariant, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
 // WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick, WS_NORMALS rc_normals_backward, WS_GSMOOTH
-// rc_geometry_smoothness_backward.
+// rc_geometry_smoothness_backward, WS_QUERY rc_query_points and rc_density_lattice, WS_ISO rc_isosurface.
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_NORMALS, WS_GSMOOTH, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_NORMALS, WS_GSMOOTH, WS_QUERY, WS_ISO, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:", "nb:", "gs:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:", "nb:", "gs:", "q:", "iso:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs, NormalsWs, GSmoothWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs, NormalsWs, GSmoothWs, QueryWs, IsoWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -201,6 +208,7 @@ struct WsName {
   WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
   WsBuf EvalWs::*ev = nullptr; WsBuf AlbedoWs::*ea = nullptr; WsBuf VisWs::*vz = nullptr;
   WsBuf MaskWs::*mk = nullptr; WsBuf RelightWs::*rl = nullptr; WsBuf NormalsWs::*nb = nullptr; WsBuf GSmoothWs::*gs = nullptr;
+  WsBuf QueryWs::*q = nullptr; WsBuf IsoWs::*iso = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -221,6 +229,8 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf RelightWs::*m) : name(s), rl(m) {}
   constexpr WsName(const char* s, WsBuf NormalsWs::*m) : name(s), nb(m) {}
   constexpr WsName(const char* s, WsBuf GSmoothWs::*m) : name(s), gs(m) {}
+  constexpr WsName(const char* s, WsBuf QueryWs::*m) : name(s), q(m) {}
+  constexpr WsName(const char* s, WsBuf IsoWs::*m) : name(s), iso(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -241,7 +251,9 @@ struct WsName {
       if (mk) return one(s, mk);
       if (rl) return one(s, rl);
       if (nb) return one(s, nb);
-      return gs ? one(s, gs) : nullptr;
+      if (gs) return one(s, gs);
+      if (q) return one(s, q);
+      return iso ? one(s, iso) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -251,7 +263,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs; using NB = NormalsWs; using GS = GSmoothWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs; using NB = NormalsWs; using GS = GSmoothWs; using Q = QueryWs; using ISO = IsoWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -289,10 +301,13 @@ constexpr WsName kTable[] = {
     WS(NB, feat), WS(NB, jac), WS(NB, gf), WS(NB, ghat), WS(NB, u), WS(NB, t0), WS(NB, a0), WS(NB, t1), WS(NB, a2), WS(NB, ones),
     WS(NB, partial), WS(NB, normals),
     WS(GS, means_p), WS(GS, feat_p), WS(GS, jac_p), WS(GS, density_p), WS(GS, normals_p), WS(GS, points), WS(GS, points_p),
-    WS(GS, d_normals), WS(GS, d_normals_p), WS(GS, d_density), WS(GS, d_density_p), WS(GS, loss_ray)};
+    WS(GS, d_normals), WS(GS, d_normals_p), WS(GS, d_density), WS(GS, d_density_p), WS(GS, loss_ray),
+    WS(Q, means), WS(Q, feat), WS(Q, jac), WS(Q, density), WS(Q, normals_pred), WS(Q, normals_grad), WS(Q, m_feat),
+    WS(ISO, mask), WS(ISO, tcount), WS(ISO, tile_v), WS(ISO, tile_t), WS(ISO, group_v), WS(ISO, group_t), WS(ISO, group_off),
+    WS(ISO, vbase), WS(ISO, state)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL) + sizeof(NB) + sizeof(GS),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL) + sizeof(NB) + sizeof(GS) + sizeof(Q) + sizeof(ISO),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -1431,3 +1446,4 @@ int rc_allgather_outputs(rc_handle* h, void* nccl_comm, const rc_outputs* local,
 #include "rc_relight_host.inc"
 #include "rc_prng_host.inc"
 #include "rc_probe_host.inc"
+#include "rc_mesh_host.inc"

@@ -990,6 +990,35 @@ struct RcVmfPanoramaArgs {
 void rc_launch_probe_rays(const RcProbeRaysArgs& a, hipStream_t stream);
 void rc_launch_vmf_panorama(const RcVmfPanoramaArgs& a, int P, hipStream_t stream);
 
+// Surface export (rc_mesh.hip): the plumbing of rc_query_points / rc_density_lattice around the forward
+// kernels, and the marching tetrahedra of rc_isosurface.
+// rows [n][3] -> SoA [3][n] and back (the density MLP reads and writes SoA)
+void rc_launch_rows_to_soa(const float* rows, int64_t n, float* soa, hipStream_t stream);
+void rc_launch_soa_to_rows(const float* soa, int64_t n, float* rows, hipStream_t stream);
+// Lattice points first .. first + n of an [nx, ny, nz] lattice (iz fastest) as SoA [3][n]: axis a's point i sits at
+// lo[a] + (float)i * step[a]
+struct RcLatticeArgs { float lo[3], step[3]; int32_t nx, ny, nz; };
+void rc_launch_lattice_points(const RcLatticeArgs& a, int64_t first, int64_t n, float* soa, hipStream_t stream);
+void rc_launch_nan_to_num(float* x, int64_t n, hipStream_t stream);      // in place, jnp.nan_to_num's defaults
+// rc_isosurface.  A tile is kRcIsoTile consecutive lattice points (one workgroup), a group kRcIsoGroup consecutive tiles.
+constexpr int kRcIsoTile = 1024, kRcIsoGroup = 256;
+struct RcIsoState { int32_t emit; };      // 1: both capacities suffice, the emission kernels write
+struct RcIsoArgs {
+  const float* field; RcLatticeArgs lat; float iso;
+  uint32_t n;                              // nx ny nz <= 2^30
+  uint32_t tiles, groups;
+  uint8_t* mask;                           // [tiles kRcIsoTile] the 7 owned edges of each point that cross the surface
+  uint8_t* tcount;                         // [tiles kRcIsoTile] triangles of the cell whose lowest corner the point is
+  int32_t* tile_v, * tile_t;               // [tiles] vertices / triangles of a tile, then of the tiles before it in its group
+  int32_t* group_v, * group_t;             // [groups] vertices / triangles of a group
+  int64_t* group_off;                      // [groups][2] vertices / triangles of the groups before
+  int32_t* vbase;                          // [n] index of a point's first vertex (written where mask != 0)
+  RcIsoState* state;
+  int64_t v_capacity, t_capacity;
+  float* vertices, * normals; int32_t* triangles; int64_t* counts;
+};
+void rc_launch_isosurface(const RcIsoArgs& a, hipStream_t stream);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

@@ -465,6 +465,10 @@ _PROTOTYPES = {
     "rc_probe_rays": (C.c_int, [_H, C.POINTER(rc_probe_view), _P, _I32, _I32, _I32, _F, _F, _F, _I32,
                                 C.POINTER(rc_cast_outputs), _P, _P]),
     "rc_vmf_panorama": (C.c_int, [_H, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "rc_query_points": (C.c_int, [_H, _P, _I64, _I32, _P, _P, _P, _P, _P]),
+    "rc_density_lattice": (C.c_int, [_H, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _I32, _I32, _I32, _P, _P]),
+    "rc_isosurface": (C.c_int, [_H, _P, _I32, _I32, _I32, _F, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _I64, _P,
+                                _I64, _P, _P]),
     "rc_set_env_image": (C.c_int, [_H, _P, _P, _P, _P, _I32, _I32, _P]),
     "rc_env_tables": (C.c_int, [_H, _P, _I32, _I32, _F, _P, _P, _P, _P]),
     "rc_env_lookup": (C.c_int, [_H, _P, _I64, _P, _P]),
@@ -2337,6 +2341,68 @@ class RadianceCache:
                                                 int(apply_contraction), self._stream()))
         self._keep = [p]
         return out
+
+    # -- surface export (mesh.py) ---------------------------------------------------------------
+    QUERY_OUTPUTS = (("density", 1), ("normals_pred", 3), ("normals", 3), ("material", 5))
+
+    def query_points(self, points, outputs=("density",), level=None):
+        """rc_query_points: the handle's fields at points [n, 3] (world coordinates) -> {name: cuda tensor} for the names
+        of `outputs` among "density" [n] (sampler level `level`, None: the last), "normals_pred" [n, 3], "normals" [n, 3]
+        (the analytic normals; both of the last level, unrectified) and "material" [n, 5] (albedo rgb, roughness,
+        metalness)."""
+        torch = self._torch
+        widths = dict(self.QUERY_OUTPUTS)
+        unknown = [k for k in outputs if k not in widths]
+        if unknown:
+            raise ValueError(f"query_points: unknown outputs {unknown}")
+        p = self._dev(points).reshape(-1, 3)
+        n = p.shape[0]
+        out = {k: torch.empty((n,) if widths[k] == 1 else (n, widths[k]), dtype=torch.float32, device=p.device) for k in outputs}
+        self._check(self.lib.rc_query_points(self._h, p.data_ptr(), n, -1 if level is None else int(level),
+                                             *[_ptr(out.get(k)) for k, _ in self.QUERY_OUTPUTS], self._stream()))
+        self._keep = [p]
+        return out
+
+    def density_lattice(self, lo, hi, dims, level=None):
+        """rc_density_lattice: the density of sampler level `level` (None: the last), nan_to_num applied, on the
+        [nx, ny, nz] lattice whose axis a has point i at lo[a] + float32(i) * ((hi[a] - lo[a]) / float32(n_a - 1))."""
+        torch = self._torch
+        nx, ny, nz = (int(d) for d in dims)
+        field = torch.empty((max(nx, 0), max(ny, 0), max(nz, 0)), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_density_lattice(self._h, (C.c_float * 3)(*[float(v) for v in lo]),
+                                                (C.c_float * 3)(*[float(v) for v in hi]), nx, ny, nz,
+                                                -1 if level is None else int(level), field.data_ptr(), self._stream()))
+        return field
+
+    def isosurface_into(self, field, iso, lo, hi, vertices, normals, triangles, counts):
+        """rc_isosurface, one call: field [nx, ny, nz] float32 cuda; vertices / normals [cap_v, 3] float32, triangles
+        [cap_t, 3] int32 (None: capacity 0; normals may be None on its own); counts: int64 [2] cuda, always written."""
+        nx, ny, nz = (int(d) for d in field.shape)
+        self._check(self.lib.rc_isosurface(self._h, field.data_ptr(), nx, ny, nz, float(iso),
+                                           (C.c_float * 3)(*[float(v) for v in lo]), (C.c_float * 3)(*[float(v) for v in hi]),
+                                           _ptr(vertices), _ptr(normals), 0 if vertices is None else vertices.shape[0],
+                                           _ptr(triangles), 0 if triangles is None else triangles.shape[0],
+                                           counts.data_ptr(), self._stream()))
+        self._keep = [field]
+
+    def isosurface(self, field, iso, lo, hi, normals=True):
+        """The two passes of rc_isosurface on a [nx, ny, nz] lattice (any float32 cuda tensor in rc_density_lattice's
+        layout): count, read {V, T} (the one host synchronisation), allocate, extract ->
+        (vertices [V, 3], normals [V, 3] or None, triangles [T, 3] int32)."""
+        torch = self._torch
+        field = self._dev(field)
+        if field.dim() != 3:
+            raise ValueError("isosurface: field must be [nx, ny, nz]")
+        dev = field.device
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.isosurface_into(field, iso, lo, hi, None, None, None, counts)
+        V, T = (int(c) for c in counts.tolist())
+        vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        vnormals = torch.empty((V, 3), dtype=torch.float32, device=dev) if normals else None
+        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        if V > 0:
+            self.isosurface_into(field, iso, lo, hi, vertices, vnormals, triangles, counts)
+        return vertices, vnormals, triangles
 
     def sample_intervals(self, t, logits, num_samples: int, jitter=None):
         torch = self._torch
