@@ -24,8 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "neural-radiance-caching_amd", "csrc")
 VARIANT = os.path.join(ROOT, "build", "f32", "librc_hip.so")
 CHILD_MODULES = ("tests/test_gpu_parity.py", "tests/test_gpu_abi_robustness.py", "tests/test_gpu_large_plan.py",
-                 "tests/test_gpu_boundary.py", "tests/test_gpu_mlp_floor.py")
-MIN_PASSED = 108     # 113 GPU tests in the child's modules
+                 "tests/test_gpu_boundary.py", "tests/test_gpu_mlp_floor.py", "tests/test_gpu_render_settings.py")
+MIN_PASSED = 154     # 108 + the 46 tests of test_gpu_render_settings.py; 162 GPU tests in the child's modules
 K = 3.0
 _SUITE = {}          # how the suite child ended: a fault there starts no further child on that library
 

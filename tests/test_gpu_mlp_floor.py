@@ -13,6 +13,7 @@ test also shows its own power: numpy's emulation of the nearest plausible wrong 
 the three leading products (hi.hi, mid.hi, hi.mid, accumulated in fp32) -- must exceed the bound by POWER x.
 """
 import contextlib
+import dataclasses
 
 import numpy as np
 import pytest
@@ -75,10 +76,18 @@ def floor_stats(hip, b32, b64, emu):
     return (np.abs(hip - b64).max(0), np.abs(b32 - b64).max(0), np.abs(emu - b64).max(0), np.abs(b64).max(0))
 
 
-def floor_check(name, hip, b32, b64, emu, power=True, eps=EPS):
-    """The bound above per channel, and (power) the emulation POWER x beyond it."""
+def floor_check(name, hip, b32, b64, emu, power=True, eps=EPS, cfg=None):
+    """The bound above per channel, and (power) the emulation POWER x beyond it.  cfg: the config of a case that is not at
+    the hotdog defaults; its figures are printed (HIP / floor, HIP / bound, emulation / bound per channel) and a failure
+    names the fields that are off their defaults."""
     err, floor, wrong, scale = floor_stats(hip, b32, b64, emu)
     bound = K * floor + eps * scale
+    if cfg is not None:
+        base = nrc_amd.hotdog_config()
+        name = (name, {f.name: getattr(cfg, f.name) for f in dataclasses.fields(cfg) if getattr(cfg, f.name) != getattr(base, f.name)})
+        with np.errstate(divide="ignore", invalid="ignore"):
+            print(name[0], "HIP / floor", np.round(err / floor, 2), "HIP / bound", np.round(err / bound, 2),
+                  "emulation / bound", np.round(wrong / bound, 1))
     assert (err <= bound).all(), (name, "HIP", err, "floor", floor, "bound", bound)
     if power:
         assert (wrong >= POWER * bound).all(), (name, "3-product emulation", wrong, "bound", bound)
@@ -118,17 +127,19 @@ def rc_smooth():
     return h
 
 
-def envmap_case(rc, n):
+def envmap_case(rc, n, cfg=None, weights_np=None):
+    """cfg, weights_np: the config the handle was made with and the weights it holds (None: the hotdog defaults,
+    common.weights_np())."""
     from nrc_amd import rc_ext
     from oracle import cache_ref
-    cfg = nrc_amd.hotdog_config()
+    cfg = nrc_amd.hotdog_config() if cfg is None else cfg
     rays, rnd = common.secondary_case(n, seed=11)
     d = adversarial_dirs(n, seed=n)
     rays["directions"] = rays["viewdirs"] = d
     out = rc.render_rays(rays, rnd, rc_ext.RC_PASS_CACHE | rc_ext.RC_PASS_SECONDARY, outputs=["env_map_rgb"])
     torch.cuda.synchronize()
     hip = out["env_map_rgb"].cpu().numpy()
-    w = common.weights_np()
+    w = common.weights_np() if weights_np is None else weights_np
     vd = torch.from_numpy(d)
     with torch.no_grad():
         b64 = cache_ref.model_env_map_rgb(common.to_torch(w, torch.float64), cfg, vd.double()).numpy()
@@ -156,9 +167,11 @@ def acc_order():
     return 32 * (s // 16) + (s % 4) + 8 * ((s % 16) // 4) + 4 * h           # [32, 2]
 
 
-def shader_inputs(rc, n, S=32):
+def shader_inputs(rc, n, S=None, cfg=None):
     """The shader's inputs as the HIP path computed them: hidden density feature [n, S, 64] (hbuf: [tile][step][half,
-    point]), appearance features [n, S, 32] (app: feature-major), normals_pred [n, S, 3] (SoA), means [n, S, 3]."""
+    point]), appearance features [n, S, 32] (app: feature-major), normals_pred [n, S, 3] (SoA), means [n, S, 3].
+    S: the last level's sample count, taken from cfg (None: the hotdog defaults) where it is not given."""
+    S = (nrc_amd.hotdog_config() if cfg is None else cfg).sampling_strategy[-1][2] if S is None else S
     np_ = n * S
     tiles = (np_ + 31) // 32
     hb = rc.workspace("hbuf")[: tiles * 32 * 64].reshape(tiles, 32, 2, 32)          # [tile, step, half, point]
@@ -176,9 +189,10 @@ SHADE_KEYS = (("rgb", 0), ("direct_diffuse_rgb", 3), ("indirect_diffuse_rgb", 6)
               ("albedo_rgb", 12))       # rc_internal.h RC_SH_RGB / AD / ID / IS / TINT
 
 
-def cache_shader_case(rc, weights_np, n=64):
+def cache_shader_case(rc, weights_np, n=64, cfg=None):
+    """cfg: the config the handle was made with (None: the hotdog defaults)."""
     from oracle import cache_ref
-    cfg = nrc_amd.hotdog_config()
+    cfg = nrc_amd.hotdog_config() if cfg is None else cfg
     rays = nrc_amd.synthetic_rays(n, seed=31)
     rc.set_fused(False)
     try:
@@ -186,7 +200,7 @@ def cache_shader_case(rc, weights_np, n=64):
         torch.cuda.synchronize()
     finally:
         rc.set_fused(True)
-    hidden, app, nrm, means, shade = shader_inputs(rc, n)
+    hidden, app, nrm, means, shade = shader_inputs(rc, n, cfg=cfg)
     rt = common.rays_torch(rays)
 
     def run(dtype, patched=False):

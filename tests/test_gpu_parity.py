@@ -411,10 +411,11 @@ def test_render_image_matches_oracle_on_small_image():
 # secondary rays (is_secondary=True): far clamp, near replacement, power-ladder distances,
 # categorical resampling to one sample, bg = 0, model-level EnvMap composite
 # ---------------------------------------------------------------------------------------------
-def _oracle_secondary(rays, rnd, **kw):
+def _oracle_secondary(rays, rnd, cfg=None, **kw):
     from oracle import cache_ref
     jit = [torch.from_numpy(j)[:, None] for j in rnd["jitter"]]
-    return cache_ref.cache_forward(common.weights_torch(), nrc_amd.hotdog_config(), common.rays_dict_torch(rays), jit,
+    cfg = nrc_amd.hotdog_config() if cfg is None else cfg
+    return cache_ref.cache_forward(common.weights_torch(), cfg, common.rays_dict_torch(rays), jit,
                                    is_secondary=True, gumbel=torch.from_numpy(rnd["gumbel"]),
                                    want_grad_normals=False, **kw)
 
