@@ -294,8 +294,8 @@ int rc_sample_intervals(rc_handle* h, const float* t, const float* logits, int64
  * "o:" = rc_adam_update / rc_load_params_flat, "ls:" = rc_light_sampling_backward / rc_light_regularizer,
  * "ms:" = rc_material_smoothness_backward / rc_material_regularizer, "md:" = rc_material_data_backward / rc_material_data_backward_env,
  * "td:" = rc_transient_data_backward, "mk:" = rc_mask_backward, "nb:" = rc_normals_backward,
- * "gs:" = rc_geometry_smoothness_backward, "q:" = rc_query_points / rc_density_lattice, "iso:" = rc_isosurface (their
- * buffers are listed at those calls).
+ * "gs:" = rc_geometry_smoothness_backward, "q:" = rc_query_points / rc_density_lattice, "iso:" = rc_isosurface,
+ * "atlas:" = rc_query_cache_diffuse / rc_bake_atlas (their buffers are listed at those calls).
  * Buffers of the render sets (no prefix, "p1:" .. "p3:", "s:"): per level, with the level 0 .. num_levels-1 appended,
  * "sdist", "tdist", "means", "feat", "density", "weights" (e.g. "sdist0", "weights2"); "hbuf", "normals_pred",
  * "normals_grad", "jac", "app", "shade", "debug", "env_rgb", "rgb_noenv", "acc_ws", "inds", "src_idx", "filt_weight",
@@ -1580,6 +1580,55 @@ int rc_density_lattice(rc_handle* h, const float* lo, const float* hi, int32_t n
 int rc_isosurface(rc_handle* h, const float* field, int32_t nx, int32_t ny, int32_t nz, float iso, const float* lo,
                   const float* hi, float* vertices, float* normals, int64_t v_capacity, int32_t* triangles,
                   int64_t t_capacity, int64_t* counts, void* stream);
+
+/* -- textured export: a per-triangle texture atlas of a device mesh, baked from the handle's fields.
+ *
+ * The layout, for T >= 1 triangles and a cell of r x r texels, 4 <= r <= 64.  Two triangles share one square cell:
+ * ncells = ceil(T / 2), cols = the smallest integer with cols^2 >= ncells, rows = ceil(ncells / cols), W = cols r,
+ * H = rows r (both at most 16384).  Texel (x, y), x from the left and y from the top, is image element [y, x] and linear
+ * index y W + x.  cx = x / r, cy = y / r, cell = cy cols + cx, i = x - cx r, j = y - cy r, half = (i + j >= r),
+ * t = 2 cell + half; the texel is empty when cell >= ncells or t >= T.  Barycentrics of the texel centre: half 0
+ * b1 = i / (r - 2), b2 = j / (r - 2); half 1 b1 = (r - 1 - i) / (r - 3), b2 = (r - 1 - j) / (r - 3) (one fp32 division
+ * each); its world point p = V0 + b1 (V1 - V0) + b2 (V2 - V0) in fp32 in this form.  Corners in local texel units (a
+ * texel's centre at (i + 0.5, j + 0.5)): half 0 (0.5, 0.5), (r - 1.5, 0.5), (0.5, r - 1.5); half 1 (r - 0.5, r - 0.5),
+ * (2.5, r - 0.5), (r - 0.5, 2.5).  Every bilinear tap of non-zero weight at a uv inside a triangle's uv triangle falls
+ * on a texel that triangle owns, so nearest and bilinear sampling never mix two triangles (mip-mapping would).
+ *
+ * rc_atlas_layout: host only; dims = {cols, rows, W, H}.  RC_ERR_INVALID_ARG: NULL dims, T < 1, r outside 4 .. 64;
+ *   RC_ERR_UNSUPPORTED: W or H above 16384.  The other calls refuse the same way.
+ * rc_atlas_uvs: uvs [T,3,2] on the device, the normalised (u, v) = (X / W, 1 - Y / H) of each triangle's corners at
+ *   global texel coordinates (X, Y) -- the `vt` lines of an OBJ file.
+ * rc_atlas_points: the texels with linear index first .. first + count - 1: points [count,3] (nullable) and owner [count]
+ *   (nullable): the triangle index, -1 for an empty texel, -2 where the triangle has a vertex index outside 0 .. V - 1
+ *   (such a triangle is never dereferenced); the point of a texel without an owner is (0, 0, 0).  vertices [V,3] float,
+ *   triangles [T,3] int32 on the device.  RC_ERR_INVALID_ARG: a NULL mesh array, V < 1, first < 0, count < 0,
+ *   first + count > W H.  count == 0 returns RC_OK and launches nothing.
+ * rc_query_cache_diffuse: diffuse [n,6] = ambient_diffuse rgb, indirect_diffuse rgb of the cache's shader at points [n,3]:
+ *   clip(softplus(Dense(96 -> 3)(feature) + bias), 0, rgb_max) of ambient_irradiance_layer / irradiance_layer on the feature
+ *   [the last sampler level's hidden vector (64) | the appearance grid's features at the contracted point (32)] -- what the
+ *   launch-per-stage plan's shader computes as ambient_diffuse_rgb / indirect_diffuse_rgb for a sample with that mean.  No
+ *   gate: like that shader, a point beyond the contracted box gets the heads' value on the features looked up at its
+ *   contracted position (only the density is gated there).  RC_ERR_UNSUPPORTED on a time-resolved handle.
+ * rc_bake_atlas: every non-NULL plane of `out` for the whole atlas, chunk by chunk of rc_query_points' chunk size: the
+ *   texels' points, the launches of rc_query_points / rc_query_cache_diffuse on them, zeros where a texel has no owner.  A
+ *   baked texel equals rc_query_points (rc_query_cache_diffuse) at that texel's point bit for bit.  `level` as in
+ *   rc_query_points.  Workspace: the "q:" names and "atlas:" names "points", "owner", "hidden", "app_feat", none of which grows
+ *   with the atlas.  No atomics; everything is ordered on `stream`, nothing waits for the device. */
+typedef struct {
+  float* density;          /* [H,W] */
+  float* normals_pred;     /* [H,W,3] */
+  float* normals;          /* [H,W,3] */
+  float* material;         /* [H,W,5] */
+  float* diffuse;          /* [H,W,6] */
+  uint8_t* coverage;       /* [H,W]: 1 where a triangle owns the texel */
+} rc_atlas_outputs;
+int rc_atlas_layout(int64_t T, int32_t r, int32_t dims[4]);
+int rc_atlas_uvs(rc_handle* h, int64_t T, int32_t r, float* uvs, void* stream);
+int rc_atlas_points(rc_handle* h, const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int32_t r,
+                    int64_t first, int64_t count, float* points, int32_t* owner, void* stream);
+int rc_query_cache_diffuse(rc_handle* h, const float* points, int64_t n, float* diffuse, void* stream);
+int rc_bake_atlas(rc_handle* h, const float* vertices, int64_t V, const int32_t* triangles, int64_t T, int32_t r,
+                  int32_t level, const rc_atlas_outputs* out, void* stream);
 
 #ifdef __cplusplus
 }

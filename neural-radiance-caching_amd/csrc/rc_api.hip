@@ -165,6 +165,10 @@ struct QueryWs { WsBuf means, feat, jac, density, normals_pred, normals_grad, m_
 // the index of its first vertex (int32), per tile and per group the sums / offsets of both scans (int32; int64 pairs), the
 // RcIsoState.
 struct IsoWs { WsBuf mask, tcount, tile_v, tile_t, group_v, group_t, group_off, vbase, state; };
+// rc_bake_atlas / rc_query_cache_diffuse, beside the QueryWs of WS_QUERY, one chunk: the texels' points as rows [C][3] and
+// their owners (int32); the last level's hidden vectors (k_density_mlp's accumulator layout) and the appearance grid's
+// features (feature-major).
+struct AtlasWs { WsBuf points, owner, hidden, app_feat; };
 
 // Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
 // different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
@@ -177,15 +181,16 @@ struct IsoWs { WsBuf mask, tcount, tile_v, tile_t, group_v, group_t, group_off, 
 // WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
 // rc_eval_image and rc_eval_shift_invariant, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
 // WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick, WS_NORMALS rc_normals_backward, WS_GSMOOTH
-// rc_geometry_smoothness_backward, WS_QUERY rc_query_points and rc_density_lattice, WS_ISO rc_isosurface.
+// rc_geometry_smoothness_backward, WS_QUERY rc_query_points and rc_density_lattice, WS_ISO rc_isosurface,
+// WS_ATLAS the buffers of rc_bake_atlas and rc_query_cache_diffuse's own (their query launches run on WS_QUERY).
 enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_NORMALS, WS_GSMOOTH, WS_QUERY, WS_ISO, WS_COUNT };
+               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_NORMALS, WS_GSMOOTH, WS_QUERY, WS_ISO, WS_ATLAS, WS_COUNT };
 // rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:", "nb:", "gs:", "q:", "iso:"};
+const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:", "nb:", "gs:", "q:", "iso:", "atlas:"};
 
 struct WsSet {
   RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs, NormalsWs, GSmoothWs, QueryWs, IsoWs> x;   // the set's extra buffers (ws_extra)
+  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs, NormalsWs, GSmoothWs, QueryWs, IsoWs, AtlasWs> x;   // the set's extra buffers (ws_extra)
   // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
   // (event), so two streams never run on one set at the same time (WsUse)
   hipStream_t stream = nullptr;
@@ -208,7 +213,7 @@ struct WsName {
   WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
   WsBuf EvalWs::*ev = nullptr; WsBuf AlbedoWs::*ea = nullptr; WsBuf VisWs::*vz = nullptr;
   WsBuf MaskWs::*mk = nullptr; WsBuf RelightWs::*rl = nullptr; WsBuf NormalsWs::*nb = nullptr; WsBuf GSmoothWs::*gs = nullptr;
-  WsBuf QueryWs::*q = nullptr; WsBuf IsoWs::*iso = nullptr;
+  WsBuf QueryWs::*q = nullptr; WsBuf IsoWs::*iso = nullptr; WsBuf AtlasWs::*at = nullptr;
   constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
   constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
   constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
@@ -231,6 +236,7 @@ struct WsName {
   constexpr WsName(const char* s, WsBuf GSmoothWs::*m) : name(s), gs(m) {}
   constexpr WsName(const char* s, WsBuf QueryWs::*m) : name(s), q(m) {}
   constexpr WsName(const char* s, WsBuf IsoWs::*m) : name(s), iso(m) {}
+  constexpr WsName(const char* s, WsBuf AtlasWs::*m) : name(s), at(m) {}
   // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
   WsBuf* in(WsSet& s, int l) const {
     if (l < 0) {
@@ -253,7 +259,8 @@ struct WsName {
       if (nb) return one(s, nb);
       if (gs) return one(s, gs);
       if (q) return one(s, q);
-      return iso ? one(s, iso) : nullptr;
+      if (iso) return one(s, iso);
+      return at ? one(s, at) : nullptr;
     }
     if (lv) return &(s.r.*lv)[l];
     InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
@@ -263,7 +270,7 @@ struct WsName {
 };
 namespace wsn {
 using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs; using NB = NormalsWs; using GS = GSmoothWs; using Q = QueryWs; using ISO = IsoWs;
+using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs; using NB = NormalsWs; using GS = GSmoothWs; using Q = QueryWs; using ISO = IsoWs; using AT = AtlasWs;
 #define WS(S, m) WsName(#m, &S::m)
 constexpr WsName kTable[] = {
     WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
@@ -304,10 +311,11 @@ constexpr WsName kTable[] = {
     WS(GS, d_normals), WS(GS, d_normals_p), WS(GS, d_density), WS(GS, d_density_p), WS(GS, loss_ray),
     WS(Q, means), WS(Q, feat), WS(Q, jac), WS(Q, density), WS(Q, normals_pred), WS(Q, normals_grad), WS(Q, m_feat),
     WS(ISO, mask), WS(ISO, tcount), WS(ISO, tile_v), WS(ISO, tile_t), WS(ISO, group_v), WS(ISO, group_t), WS(ISO, group_off),
-    WS(ISO, vbase), WS(ISO, state)};
+    WS(ISO, vbase), WS(ISO, state),
+    WS(AT, points), WS(AT, owner), WS(AT, hidden), WS(AT, app_feat)};
 #undef WS
 constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL) + sizeof(NB) + sizeof(GS) + sizeof(Q) + sizeof(ISO),
+static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL) + sizeof(NB) + sizeof(GS) + sizeof(Q) + sizeof(ISO) + sizeof(AT),
               "the table lists every workspace buffer");
 }  // namespace wsn
 
@@ -350,6 +358,8 @@ struct rc_handle {
   uint64_t nbwd_gen = 0;                     // layers_gen packs.nbwd was packed at
   uint64_t geom_gen = 0;                     // layers_gen geom_w was uploaded at
   DevBuf geom_w;                             // rc_geometry_backward: pred_normals_layer kernel [64][3] + bias [3]
+  uint64_t diffuse_gen = 0;                  // layers_gen diffuse_w was uploaded at
+  DevBuf diffuse_w;                          // rc_query_cache_diffuse: ambient_irradiance_layer and irradiance_layer on the Flax layout
   uint64_t env_gen = 0;                      // layers_gen env_w was uploaded at
   DevBuf env_w;                              // rc_material_data_backward_env: the EnvMap's dense layers on the Flax layout
   uint64_t thead_gen = 0;                    // layers_gen thead_w was uploaded at
@@ -1170,6 +1180,7 @@ void rc_destroy(rc_handle* h) {
   if (h->ide_table.p) (void)hipFree(h->ide_table.p);
   free_buf(h->data_w);
   free_buf(h->geom_w);
+  free_buf(h->diffuse_w);
   free_buf(h->env_w);
   free_buf(h->thead_w);
   free_buf(h->itof_w);
@@ -1447,3 +1458,4 @@ int rc_allgather_outputs(rc_handle* h, void* nccl_comm, const rc_outputs* local,
 #include "rc_prng_host.inc"
 #include "rc_probe_host.inc"
 #include "rc_mesh_host.inc"
+#include "rc_atlas_host.inc"

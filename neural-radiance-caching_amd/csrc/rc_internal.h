@@ -1019,6 +1019,37 @@ struct RcIsoArgs {
 };
 void rc_launch_isosurface(const RcIsoArgs& a, hipStream_t stream);
 
+// Texture atlas (rc_atlas.hip; include/rc_abi.h states the layout rule).
+struct RcAtlasLayout { int32_t cols, rows, W, H, r; int64_t T, ncells; };
+// The rule's host side: RC_OK, or RC_ERR_INVALID_ARG (T < 1, r outside 4 .. 64) / RC_ERR_UNSUPPORTED (W or H above 16384)
+int rc_atlas_layout_of(int64_t T, int32_t r, RcAtlasLayout& L);
+void rc_launch_atlas_uvs(const RcAtlasLayout& L, float* uvs, hipStream_t stream);      // uvs [T][3][2]
+struct RcAtlasPointsArgs {
+  RcAtlasLayout L;
+  const float* vertices; int64_t V;          // [V][3]
+  const int32_t* triangles;                  // [T][3]
+  int64_t first, n;                          // the texels with linear index first .. first + n
+  float* rows;                               // [n][3] or nullptr
+  float* soa;                                // SoA [3][n] (what the density MLP reads) or nullptr
+  int32_t* owner;                            // [n] or nullptr: triangle, -1 empty, -2 a vertex index outside 0 .. V-1
+};
+void rc_launch_atlas_points(const RcAtlasPointsArgs& a, hipStream_t stream);
+// Texels c0 .. c0 + n of the planes (already offset by the caller): zeros where owner < 0, coverage = owner >= 0
+struct RcAtlasStoreArgs {
+  const int32_t* owner; int64_t n;
+  float* density, * normals_pred, * normals, * material, * diffuse; uint8_t* coverage;     // nullptr: not wanted
+};
+void rc_launch_atlas_store(const RcAtlasStoreArgs& a, hipStream_t stream);
+// ambient_diffuse / indirect_diffuse of the cache shader at n points: hbuf in k_density_mlp's accumulator layout, app
+// feature-major [32][ld], w = ambient_irradiance_layer kernel [96][3], bias [3], irradiance_layer kernel [96][3], bias [3]
+constexpr int kRcDiffuseWeights = 2 * (96 * 3 + 3);
+struct RcDiffuseArgs {
+  int64_t n, ld; const float* hbuf, * app, * w;
+  float ambient_bias, irradiance_bias, rgb_max;
+  float* out;                                // [n][6]
+};
+void rc_launch_shader_diffuse_points(const RcDiffuseArgs& a, hipStream_t stream);
+
 // The optimizer step on flat buffers (rc_optim.hip).  A run: consecutive elements of one buffer in one group.
 constexpr int kRcAdamMaxBufs = 8, kRcAdamMaxRuns = 32, kRcAdamMaxGroups = 8;
 struct RcAdamBuf { float* params, * grads, * mu, * nu; int64_t n, block0; int run0, nruns; };

@@ -35,8 +35,10 @@ int query_alloc(rc_handle* h, QueryWs& q, int level, int64_t C, bool density, bo
 }
 
 // predict_density of level `level` at the C points of q.means: the lookup (contraction included), the density MLP with
-// the gate of the contracted box; on the last level the predicted and (with the Jacobian) the analytic normals as SoA
-void query_density_chunk(rc_handle* h, QueryWs& q, int level, int64_t C, float* density, bool pred, bool grad, hipStream_t st) {
+// the gate of the contracted box; on the last level the predicted and (with the Jacobian) the analytic normals as SoA, and
+// with `hbuf` the hidden vector as the shader reads it (rc_atlas_host.inc)
+void query_density_chunk(rc_handle* h, QueryWs& q, int level, int64_t C, float* density, bool pred, bool grad, hipStream_t st,
+                         float* hbuf = nullptr) {
   const rc_config& c = h->cfg;
   const GridState& gs = h->grids[level];
   rc_launch_hashgrid(gs.dev, q.means.p, 1, C, q.feat.p, 1, C, c.contract_radius, grad ? q.jac.p : nullptr, st);
@@ -46,7 +48,7 @@ void query_density_chunk(rc_handle* h, QueryWs& q, int level, int64_t C, float* 
   da.density_bias = c.density_bias; da.contract_radius = c.contract_radius; da.bbox = gs.cfg.bbox;
   da.last = level == c.num_levels - 1 ? 1 : 0;
   da.density = density ? density : q.density.p;
-  da.normals_pred = pred ? q.normals_pred.p : nullptr;
+  da.normals_pred = pred ? q.normals_pred.p : nullptr; da.hbuf = hbuf;
   da.jac = grad ? q.jac.p : nullptr; da.normals_grad = grad ? q.normals_grad.p : nullptr;
   rc_launch_density_mlp(da, st);
 }

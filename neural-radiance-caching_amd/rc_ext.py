@@ -356,6 +356,13 @@ class rc_probe_view(C.Structure):
                 + [("n_view", C.c_int64)])
 
 
+ATLAS_OUTPUTS = (("density", 1), ("normals_pred", 3), ("normals", 3), ("material", 5), ("diffuse", 6), ("coverage", 1))
+
+
+class rc_atlas_outputs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k, _ in ATLAS_OUTPUTS]
+
+
 class rc_adam_buffer(C.Structure):
     _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("mu", C.c_void_p), ("nu", C.c_void_p), ("n", C.c_int64),
                 ("nseg", C.c_int32), ("seg_offset", C.c_void_p), ("seg_size", C.c_void_p), ("seg_group", C.c_void_p)]
@@ -469,6 +476,11 @@ _PROTOTYPES = {
     "rc_density_lattice": (C.c_int, [_H, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _I32, _I32, _I32, _P, _P]),
     "rc_isosurface": (C.c_int, [_H, _P, _I32, _I32, _I32, _F, C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _I64, _P,
                                 _I64, _P, _P]),
+    "rc_atlas_layout": (C.c_int, [_I64, _I32, C.POINTER(C.c_int32)]),
+    "rc_atlas_uvs": (C.c_int, [_H, _I64, _I32, _P, _P]),
+    "rc_atlas_points": (C.c_int, [_H, _P, _I64, _P, _I64, _I32, _I64, _I64, _P, _P, _P]),
+    "rc_query_cache_diffuse": (C.c_int, [_H, _P, _I64, _P, _P]),
+    "rc_bake_atlas": (C.c_int, [_H, _P, _I64, _P, _I64, _I32, _I32, C.POINTER(rc_atlas_outputs), _P]),
     "rc_set_env_image": (C.c_int, [_H, _P, _P, _P, _P, _I32, _I32, _P]),
     "rc_env_tables": (C.c_int, [_H, _P, _I32, _I32, _F, _P, _P, _P, _P]),
     "rc_env_lookup": (C.c_int, [_H, _P, _I64, _P, _P]),
@@ -2404,6 +2416,65 @@ class RadianceCache:
             self.isosurface_into(field, iso, lo, hi, vertices, vnormals, triangles, counts)
         return vertices, vnormals, triangles
 
+    # -- textured export (mesh.py) ----------------------------------------------------------------
+    def query_cache_diffuse(self, points):
+        """rc_query_cache_diffuse: [n, 6] = ambient_diffuse rgb, indirect_diffuse rgb of the cache's shader at points
+        [n, 3] -- its two heads that need no view direction."""
+        torch = self._torch
+        p = self._dev(points).reshape(-1, 3)
+        out = torch.empty((p.shape[0], 6), dtype=torch.float32, device=p.device)
+        self._check(self.lib.rc_query_cache_diffuse(self._h, p.data_ptr(), p.shape[0], out.data_ptr(), self._stream()))
+        self._keep = [p]
+        return out
+
+    def _mesh_arrays(self, vertices, triangles):
+        torch = self._torch
+        v = self._dev(vertices).reshape(-1, 3)
+        t = self._dev(triangles, torch.int32).reshape(-1, 3)
+        return v, t
+
+    def atlas_uvs(self, T: int, r: int):
+        """rc_atlas_uvs: the normalised uv of every triangle corner, [T, 3, 2] float32."""
+        torch = self._torch
+        atlas_layout(T, r)                               # refuses before anything is allocated
+        uvs = torch.empty((int(T), 3, 2), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._check(self.lib.rc_atlas_uvs(self._h, int(T), int(r), uvs.data_ptr(), self._stream()))
+        return uvs
+
+    def atlas_points(self, vertices, triangles, r: int, first: int = 0, count: Optional[int] = None):
+        """rc_atlas_points: (points [count, 3] float32, owner [count] int32) of the texels with linear index y W + x in
+        first .. first + count - 1 (count None: to the end of the atlas)."""
+        torch = self._torch
+        v, t = self._mesh_arrays(vertices, triangles)
+        W, H = atlas_layout(t.shape[0], r)[2:]
+        count = W * H - int(first) if count is None else int(count)
+        points = torch.empty((max(count, 0), 3), dtype=torch.float32, device=v.device)
+        owner = torch.empty((max(count, 0),), dtype=torch.int32, device=v.device)
+        self._check(self.lib.rc_atlas_points(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0], int(r), int(first),
+                                             count, points.data_ptr(), owner.data_ptr(), self._stream()))
+        self._keep = [v, t]
+        return points, owner
+
+    def bake_atlas(self, vertices, triangles, r: int, outputs=("material",), level=None):
+        """rc_bake_atlas: the planes named in `outputs` (ATLAS_OUTPUTS) of the atlas of a mesh -> {name: [H, W] or
+        [H, W, channels] cuda tensor}, float32 but for "coverage" (uint8)."""
+        torch = self._torch
+        widths = dict(ATLAS_OUTPUTS)
+        unknown = [k for k in outputs if k not in widths]
+        if unknown:
+            raise ValueError(f"bake_atlas: unknown outputs {unknown}")
+        v, t = self._mesh_arrays(vertices, triangles)
+        W, H = atlas_layout(t.shape[0], r)[2:]
+        out, a = {}, rc_atlas_outputs()
+        for k in outputs:
+            out[k] = torch.empty((H, W) if widths[k] == 1 else (H, W, widths[k]), device=v.device,
+                                 dtype=torch.uint8 if k == "coverage" else torch.float32)
+            setattr(a, k, out[k].data_ptr())
+        self._check(self.lib.rc_bake_atlas(self._h, v.data_ptr(), v.shape[0], t.data_ptr(), t.shape[0], int(r),
+                                           -1 if level is None else int(level), C.byref(a), self._stream()))
+        self._keep = [v, t]
+        return out
+
     def sample_intervals(self, t, logits, num_samples: int, jitter=None):
         torch = self._torch
         t = self._dev(t)
@@ -2492,6 +2563,16 @@ def vis_turbo_lut():
     if rc != 0:
         raise RcError(rc, "rc_vis_turbo_lut")
     return out
+
+
+def atlas_layout(T: int, r: int):
+    """rc_atlas_layout: (cols, rows, W, H) of the per-triangle atlas of T triangles with cells of r x r texels
+    (include/rc_abi.h states the rule); RcError where the library refuses (T < 1, r outside 4 .. 64, a side above 16384)."""
+    dims = (C.c_int32 * 4)()
+    rc = load_library().rc_atlas_layout(int(T), int(r), dims)
+    if rc != 0:
+        raise RcError(rc, f"rc_atlas_layout: T = {T}, r = {r} is outside the supported range")
+    return tuple(int(d) for d in dims)
 
 
 def _memcpy_d2h(dst: int, src: int, nbytes: int):
