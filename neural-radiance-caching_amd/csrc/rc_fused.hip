@@ -16,6 +16,21 @@
 // rc_mlp.hip), whose reference citations apply; this file only changes where the data lives.  Proposal levels 0 and 1
 // are two calls of proposal_level; resample, mean_of, density_of, level2_combine, export_samples and the phases shared
 // with the two-wave kernel (analytic_normal, the distance statistics, store3 / store1) are rc_fused_common.h's.
+//
+// Scalar batches.  One wave per SIMD issues in order, so a scalar load that is waited for right behind its issue is a
+// scalar-cache round trip on the ray's chain.  The arguments are therefore laid out by phase (rc_fused_common.h:
+// RcResampleRec, RcLookupRec, RcShadeRec -- what ONE phase reads, side by side) and every record is read as a few wide
+// s_loads one phase ahead of its use, then named by one empty asm behind the work that covers the loads; the phase uses
+// those registers and reads no argument itself:
+//   resampling 0 + lookup 0         read at kernel entry, named behind ws_begin's wait and barrier
+//   resampling 1 + lookup 1         read behind the last table load of lookup 0, named behind the level-0 density MLP
+//   resampling 2 + lookup 2         read behind the last table load of lookup 1, named behind the level-1 density MLP
+//   shader and compositing scalars  read in front of lookup 2, named behind the level-2 density MLP's output layer
+//   output pointers                 read in front of the compositing's butterfly, named behind it (RC_OUT_PINS)
+// (behind the table loads and not in front of the MLP: the first LDS wait of the MLP would close the scalar loads too, the
+// two share a counter.)  No scalar load lies between the table loads of a lookup
+// (tests/test_fused_scalar_batches_code_objects.py).
+//
 // Used for the cache pass on primary rays without resampling (BASELINE configs 1, 2, 4); secondary
 // rays, resampling and the material stage use the stand-alone kernels.
 #include "rc_fused_common.h"
@@ -36,6 +51,38 @@ constexpr int kAppSteps = 32;
 #define RC_OUT_PINS "s"(op[0]), "s"(op[1]), "s"(op[2]), "s"(op[3]), "s"(op[4]), "s"(op[5]), "s"(op[6]), "s"(op[7]), "s"(op[8]), "s"(op[9]), \
                     "s"(op[10]), "s"(op[11]), "s"(op[12]), "s"(op[13]), "s"(op[14]), "s"(op[15]), "s"(op[16]), "s"(op[17]), "s"(op[18])
 #define RC_EXPORT_PINS "s"(a.f_tdist), "s"(a.f_density), "s"(a.f_means), "s"(a.f_normals_pred), "s"(a.n)
+
+// A lookup's record (RcLookupRec) in registers: the K levels' tables and sizes, the hashed levels' masks (a dense level's
+// stays the constant 0: its lookup takes none) and the scalars of the proposal level around the lookup.  fetch_lookup
+// reads, pin_lookup is the one empty asm that names every value read (K is 6, 7 or 8).
+template <int K> struct LookupRegs { const float* table[K]; int32_t size[K]; uint32_t mask[K]; float bbox, precondition, contract_radius, density_bias; };
+template <int K>
+__device__ __forceinline__ LookupRegs<K> fetch_lookup(const RcLookupRec& q) {
+  LookupRegs<K> g;
+#pragma unroll
+  for (int l = 0; l < K; ++l) { g.table[l] = q.table[l]; g.size[l] = q.size[l]; g.mask[l] = l < kFusedDense ? 0u : q.mask[l]; }
+  g.bbox = q.bbox; g.precondition = q.precondition; g.contract_radius = q.contract_radius; g.density_bias = q.density_bias;
+  return g;
+}
+#define RC_LOOKUP_PINS6(g) "s"(g.table[0]), "s"(g.table[1]), "s"(g.table[2]), "s"(g.table[3]), "s"(g.table[4]), "s"(g.table[5]),      \
+                           "s"(g.size[0]), "s"(g.size[1]), "s"(g.size[2]), "s"(g.size[3]), "s"(g.size[4]), "s"(g.size[5]),              \
+                           "s"(g.mask[3]), "s"(g.mask[4]), "s"(g.mask[5]), "s"(g.bbox), "s"(g.precondition), "s"(g.contract_radius), \
+                           "s"(g.density_bias)
+static_assert(kFusedDense == 3, "the pins name the masks of levels 3 and up");
+template <int K>
+__device__ __forceinline__ void pin_lookup(const LookupRegs<K>& g) {
+  static_assert(K >= 6 && K <= 8, "RC_LOOKUP_PINS6 and the levels behind it");
+  if constexpr (K == 6) asm volatile("" :: RC_LOOKUP_PINS6(g));
+  else if constexpr (K == 7) asm volatile("" :: RC_LOOKUP_PINS6(g), "s"(g.table[6]), "s"(g.size[6]), "s"(g.mask[6]));
+  else asm volatile("" :: RC_LOOKUP_PINS6(g), "s"(g.table[6]), "s"(g.size[6]), "s"(g.mask[6]), "s"(g.table[7]), "s"(g.size[7]), "s"(g.mask[7]));
+}
+// the shader's and the tail's record (RcShadeRec) in registers
+struct ShadeRegs { ShaderConsts sh; float bg; const float* lights; const float* viewdirs; float pct0, pct1, pct2; };
+__device__ __forceinline__ ShadeRegs fetch_shade(const RcShadeRec& q) {
+  return ShadeRegs{q.sh, q.bg, q.lights, q.viewdirs, q.pct[0], q.pct[1], q.pct[2]};
+}
+#define RC_SHADE_PINS(k) "s"(k.sh.roughness_bias), "s"(k.sh.irradiance_bias), "s"(k.sh.ambient_bias), "s"(k.sh.rgb_max), "s"(k.sh.slf_ambient_bias), \
+                         "s"(k.bg), "s"(k.lights), "s"(k.viewdirs), "s"(k.pct0), "s"(k.pct1), "s"(k.pct2)
 
 // Density MLP of a proposal level on 64 samples (two point-tiles); returns the raw density of
 // sample `lane`.  K grid features of this lane's sample are in f[].
@@ -70,20 +117,22 @@ __device__ __forceinline__ float density_level64(const WS& ws, float* act_wave, 
 }
 
 // Proposal level LEVEL (0, 1) on the 64 intervals in s_td, K grid levels, density MLP at fragment FB: sample mean ->
-// contract -> lookup -> density MLP -> the alpha weight of sample `lane`
-template <int LEVEL, int K, int FB, int NF, class WS>
-__device__ __forceinline__ float proposal_level(const RcFusedArgs& a, const WS& ws, float* act_wave, const Ray& r, const float* s_td, int lane,
-                                                unsigned long long* stamps) {
+// contract -> lookup -> density MLP -> the alpha weight of sample `lane`.  Every scalar it reads is in g (fetched one phase
+// earlier); fetch_next() issues the scalar loads of the next phase's records behind the lookup's table loads, pin_next()
+// names them behind the density MLP.
+template <int LEVEL, int K, int FB, int NF, class WS, class FETCH, class PIN>
+__device__ __forceinline__ float proposal_level(const LookupRegs<K>& g, const WS& ws, float* act_wave, const Ray& r, const float* s_td, int lane,
+                                                unsigned long long* stamps, const FETCH& fetch_next, const PIN& pin_next) {
   float mx, my, mz, t0, t1;
   mean_of(r, s_td, lane, mx, my, mz, t0, t1);
   float cx = mx, cy = my, cz = mz;
-  contract3(cx, cy, cz, a.contract_radius);
-  const RcGridDev& g = a.grid[LEVEL];
+  contract3(cx, cy, cz, g.contract_radius);
   float f[K];
   {
     const float ux = unit_box(g.bbox, cx), uy = unit_box(g.bbox, cy), uz = unit_box(g.bbox, cz);
 #if defined(RC_ABL) && RC_ABL == 11
     for (int l = 0; l < K; ++l) f[l] = ux * (float)l + uy - uz;
+    fetch_next();
 #else
     // the cell-table loads of 16 bytes (dense levels) + the corner loads (hashed levels) in flight before the first
     // combine: 6 + 24 on level 0, 6 + 32 on level 1.
@@ -94,11 +143,13 @@ __device__ __forceinline__ float proposal_level(const RcFusedArgs& a, const WS& 
     if constexpr (LEVEL == 0) RC_FSTAMP(12);
 #pragma unroll
     for (int l = 0; l < K; ++l) {
-      const RcGridLevel& L = g.lvl[l];
-      if (l < kFusedDense) grid_fetch_cell(a.cell_table[LEVEL][l], L.size, ux, uy, uz, C[l]);
-      else grid_fetch<1, true>(L.table, L.size, L.mask, 0u, false, ux, uy, uz, C[l]);
+      if (l < kFusedDense) grid_fetch_cell(g.table[l], g.size[l], ux, uy, uz, C[l]);
+      else grid_fetch<1, true>(g.table[l], g.size[l], g.mask[l], 0u, false, ux, uy, uz, C[l]);
     }
     if constexpr (LEVEL == 0) RC_FSTAMP_NOWAIT(13);
+    // the next phase's records behind the last table load: their round trip runs beside the tables' (a wait on LDS in
+    // front of the MLP closes scalar loads too -- the two share a counter -- so in front of the MLP they would wait there)
+    fetch_next();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int l = 0; l < K; ++l) {
@@ -114,7 +165,8 @@ __device__ __forceinline__ float proposal_level(const RcFusedArgs& a, const WS& 
 #else
   const float raw = density_level64<K, FB, NF>(ws, act_wave, lane, f);
 #endif
-  return alpha_weight(density_of(a, raw, cx, cy, cz, g.bbox), t0, t1, r.dnorm, true, lane);
+  pin_next();
+  return alpha_weight(density_of(g.density_bias, raw, cx, cy, cz, g.bbox), t0, t1, r.dnorm, true, lane);
 }
 
 // FRONT: stop behind the last proposal level (density MLP + appearance lookup) and hand the per-sample results to the
@@ -140,41 +192,61 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
   RC_FSTAMP(0);
+  // the records of the first resampling and the first lookup: their scalar loads go out here, the wait and the barrier of
+  // ws_begin cover them
+  const ResampleRegs rs0 = fetch_resample(a.rs[0]);
+  const LookupRegs<6> g0 = fetch_lookup<6>(a.look[0]);
+  __builtin_amdgcn_sched_barrier(0);
   ws_begin<NF>(ws);
+  asm volatile("" :: RC_RESAMPLE_PINS(rs0));
+  pin_lookup(g0);
 
   const Ray r = load_ray(a, ray);
 
   // ------------------------------------------------------------------ level 0 (P = 1, S = 64)
   if (lane == 0) { s.sd[0][0] = 0.0f; s.sd[0][1] = 1.0f; }
   lds_sync<false>();
-  resample<FRONT>(a, r, ray, s, lane, 0, 1, 64, a.anneal * safe_log(1.0f + a.padding), s.sd[0]);
+  resample<FRONT>(a, rs0, r, ray, s, lane, 1, 64, rs0.anneal * safe_log(1.0f + rs0.padding), s.sd[0]);
   RC_FSTAMP(1);
-  float w = proposal_level<0, 6, F_L0, NF>(a, ws, act_wave, r, s.td, lane, RC_FSTAMP_BUF);
+  // the records of level 1 behind the level-0 density MLP, those of level 2 behind the level-1 one
+  ResampleRegs rs1, rs2;
+  LookupRegs<7> g1;
+  LookupRegs<8> g2;
+  float w = proposal_level<0, 6, F_L0, NF>(g0, ws, act_wave, r, s.td, lane, RC_FSTAMP_BUF,
+                                           [&] { rs1 = fetch_resample(a.rs[1]); g1 = fetch_lookup<7>(a.look[1]); },
+                                           [&] { asm volatile("" :: RC_RESAMPLE_PINS(rs1)); pin_lookup(g1); });
   RC_FSTAMP(3);
   for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[1][e2] = s.out[e2];
   lds_sync<false>();
   // ------------------------------------------------------------------ level 1 (P = 64, S = 64)
-  resample<FRONT>(a, r, ray, s, lane, 1, 64, 64, a.anneal * safe_log(w + a.padding), s.sd[1]);
+  resample<FRONT>(a, rs1, r, ray, s, lane, 64, 64, rs1.anneal * safe_log(w + rs1.padding), s.sd[1]);
   RC_FSTAMP(4);
-  w = proposal_level<1, 7, F_L1, NF>(a, ws, act_wave, r, s.td, lane, RC_FSTAMP_BUF);
+  w = proposal_level<1, 7, F_L1, NF>(g1, ws, act_wave, r, s.td, lane, RC_FSTAMP_BUF,
+                                     [&] { rs2 = fetch_resample(a.rs[2]); g2 = fetch_lookup<8>(a.look[2]); },
+                                     [&] { asm volatile("" :: RC_RESAMPLE_PINS(rs2)); pin_lookup(g2); });
   RC_FSTAMP(6);
   for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[0][e2] = s.out[e2];
   lds_sync<false>();
   // ------------------------------------------------------------------ level 2 (P = 64, S = 32)
-  resample<FRONT>(a, r, ray, s, lane, 2, 64, 32, a.anneal * safe_log(w + a.padding), s.sd[0]);
+  resample<FRONT>(a, rs2, r, ray, s, lane, 64, 32, rs2.anneal * safe_log(w + rs2.padding), s.sd[0]);
   RC_FSTAMP(7);
   const int j = lane & 31, h = lane >> 5;
   float mx, my, mz, t0, t1;
   mean_of(r, s.td, j, mx, my, mz, t0, t1);
   float cx = mx, cy = my, cz = mz;
-  const float zx = rc_div(mx, a.contract_radius), zy = rc_div(my, a.contract_radius), zz = rc_div(mz, a.contract_radius);
-  contract3(cx, cy, cz, a.contract_radius);
+  const float zx = rc_div(mx, g2.contract_radius), zy = rc_div(my, g2.contract_radius), zz = rc_div(mz, g2.contract_radius);
+  contract3(cx, cy, cz, g2.contract_radius);
   float* act = act_wave + lane;
+  // the shader's and the tail's record: in front of the level-2 lookup, whose memory time and the density MLP behind it
+  // cover its loads
+  ShadeRegs k{};
+  if constexpr (!FRONT) k = fetch_shade(a.shade);
+  __builtin_amdgcn_sched_barrier(0);
   {
-    // half-wave 0 looks up the level-2 density grid, half-wave 1 the appearance grid (same level sizes)
-    const RcGridDev& g = a.grid[2];      // bbox / precondition: same for both grids (checked on the host)
+    // half-wave 0 looks up the level-2 density grid, half-wave 1 the appearance grid (same level sizes; bbox /
+    // precondition: same for both grids, checked on the host)
     float f[32];
-    const float ux = unit_box(g.bbox, cx), uy = unit_box(g.bbox, cy), uz = unit_box(g.bbox, cz);
+    const float ux = unit_box(g2.bbox, cx), uy = unit_box(g2.bbox, cy), uz = unit_box(g2.bbox, cz);
     // two rounds of four levels: 32 corner loads of 16 bytes in flight per lane
 #if defined(RC_ABL) && RC_ABL == 11
     for (int k = 0; k < 32; ++k) f[k] = ux * (float)k + uy - uz;
@@ -189,18 +261,17 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
         // level geometry is identical for the two grids (checked on the host) and so is the entry index: the host keeps
         // a copy of the two tables interleaved entry by entry ([density 16 B | appearance 16 B]), so the two half-waves
         // of a point read the two halves of ONE 32-byte pair -- half the cache-line requests and sector traffic
-        const RcGridLevel& L = a.grid[2].lvl[l];
-        grid_fetch<4, true, 2, true>(a.pair_table[l] + 4 * h, L.size, L.mask, 0u, l < kFusedDense, ux, uy, uz, C[q]);
+        grid_fetch<4, true, 2, true>(g2.table[l] + 4 * h, g2.size[l], g2.mask[l], 0u, l < kFusedDense, ux, uy, uz, C[q]);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int l = half * 4 + q;
         float v[4], jd[GRAD ? 12 : 1];
-        level2_combine<GRAD>(g, C[q], v, jd);
+        level2_combine<GRAD>(g2.precondition, C[q], v, jd);
 #pragma unroll
         for (int c = 0; c < 4; ++c) f[4 * l + c] = v[c];
-        if constexpr (GRAD) level2_jacobian(g, l, jd, act_wave, j, h);
+        if constexpr (GRAD) level2_jacobian(g2.precondition, g2.size[l], g2.bbox, l, jd, act_wave, j, h);
       }
     }
     // feature k of point j -> step base + k/2, lane j + 32 (k & 1): density features feed D0 at [0,16), appearance
@@ -243,7 +314,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
     park<2, true>(acc, act, 0);               // hidden feature: stays at [0,32) for the shader
     float out[4], wout[GRAD ? 32 : 1];
     dot_out1<2, 4, F_L2 + FR::DO, NF, GRAD>(ws, acc, out, wout);      // density + predicted normals on relu(acc)
-    density = density_of(a, out[0], cx, cy, cz, a.grid[2].bbox);
+    if constexpr (!FRONT) asm volatile("" :: RC_SHADE_PINS(k));
+    density = density_of(g2.density_bias, out[0], cx, cy, cz, g2.bbox);
     npx = out[1]; npy = out[2]; npz = out[3];
     neg_normalize(npx, npy, npz);
     if constexpr (GRAD) {
@@ -263,7 +335,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
       f32x16 gf[1];
       gf[0] = zero16();
       mlp_layer_dh<1, 2, false, F_L2 + FR::B0, NF>(ws, bw, gf);
-      analytic_normal(gf[0], act_wave, j, h, zx, zy, zz, a.contract_radius, ngx, ngy, ngz);
+      analytic_normal(gf[0], act_wave, j, h, zx, zy, zz, g2.contract_radius, ngx, ngy, ngz);
     } else if constexpr (!FRONT) {
       // the stream is consumed strictly in order: step the ring over the unused backward fragments
 #pragma unroll
@@ -293,8 +365,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   ShadeOut so;
   for (int c = 0; c < 3; ++c) { so.rgb[c] = act[c * 64]; so.ad[c] = npx; so.idf[c] = npy; so.is[c] = npz; so.tint[c] = density; }
 #else
-  const ShadeOut so = shader_tile<F_SH, NF>(ws, act, lane, h, npx, npy, npz, a.viewdirs[3 * ray], a.viewdirs[3 * ray + 1],
-                                            a.viewdirs[3 * ray + 2], a.sh);
+  const ShadeOut so = shader_tile<F_SH, NF>(ws, act, lane, h, npx, npy, npz, k.viewdirs[3 * ray], k.viewdirs[3 * ray + 1],
+                                            k.viewdirs[3 * ray + 2], k.sh);
 #endif
 
   RC_FSTAMP(10);
@@ -343,8 +415,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   x[V_MEAN] = mx; x[V_MEAN + 1] = my; x[V_MEAN + 2] = mz;
   x[V_RD] = sqrtf((r.ox - mx) * (r.ox - mx) + (r.oy - my) * (r.oy - my) + (r.oz - mz) * (r.oz - mz));
   x[V_LD] = 0.0f;
-  if (a.lights) {
-    const float lx = a.lights[3 * ray], ly = a.lights[3 * ray + 1], lz = a.lights[3 * ray + 2];
+  if (k.lights) {
+    const float lx = k.lights[3 * ray], ly = k.lights[3 * ray + 1], lz = k.lights[3 * ray + 2];
     x[V_LD] = sqrtf((lx - mx) * (lx - mx) + (ly - my) * (ly - my) + (lz - mz) * (lz - mz));
   }
   x[V_NP] = npx; x[V_NP + 1] = npy; x[V_NP + 2] = npz;
@@ -361,7 +433,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   asm volatile("" :: RC_OUT_PINS);
   __builtin_amdgcn_sched_barrier(0);
   const float accw = v[V_ACC];
-  const float bgw = fmaxf(0.0f, 1.0f - accw) * a.bg;
+  const float bgw = fmaxf(0.0f, 1.0f - accw) * k.bg;
   store3(op[RC_OUT_RGB], st, ray, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
   store3(op[RC_OUT_DIRECT_RGB], st, ray, v[V_AD], v[V_AD + 1], v[V_AD + 2]);
   store3(op[RC_OUT_INDIRECT_DIFFUSE_RGB], st, ray, v[V_IDF], v[V_IDF + 1], v[V_IDF + 2]);
@@ -374,11 +446,13 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   store1(op[RC_OUT_ACC], st, ray, accw);
   store3(op[RC_OUT_MEANS], st, ray, v[V_MEAN], v[V_MEAN + 1], v[V_MEAN + 2]);
   store1(op[RC_OUT_RAY_DISTS], st, ray, v[V_RD]);
-  if (a.lights) store1(op[RC_OUT_LIGHT_DISTS], st, ray, v[V_LD]);
+  if (k.lights) store1(op[RC_OUT_LIGHT_DISTS], st, ray, v[V_LD]);
   store3(op[RC_OUT_NORMALS_PRED], st, ray, v[V_NP], v[V_NP + 1], v[V_NP + 2]);
   if constexpr (GRAD) store3(op[RC_OUT_NORMALS], st, ray, v[V_NG], v[V_NG + 1], v[V_NG + 2]);
   store1(op[RC_OUT_DISTANCE_MEAN], st, ray, distance_mean(v[V_LOGT], accw, s.td));
-  distance_percentiles(a, ray, ray_ok, lane, wnf, accw, s.td, s.cw, op[RC_OUT_DISTANCE_PERCENTILE_5], op[RC_OUT_DISTANCE_MEDIAN],
+  // (by value: a conditional on the members themselves selects their address and loads per lane, rc_dev_grid.h pick_half)
+  const float pct0 = k.pct0, pct1 = k.pct1, pct2 = k.pct2;
+  distance_percentiles([=](int i) { return pick_half(i, pct0, pick_half(i - 1, pct1, pct2)); }, ray, ray_ok, lane, wnf, accw, s.td, s.cw, op[RC_OUT_DISTANCE_PERCENTILE_5], op[RC_OUT_DISTANCE_MEDIAN],
                        op[RC_OUT_DISTANCE_PERCENTILE_95]);
   RC_FSTAMP(11);
 #ifdef RC_STAMPS
@@ -434,18 +508,28 @@ void rc_launch_fused(const RcFusedLaunch& L, hipStream_t stream) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[g][f]), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   }
   RcFusedArgs a{};
-  a.origins = L.rays.origins; a.directions = L.rays.directions; a.viewdirs = L.rays.viewdirs; a.near = L.rays.near;
-  a.far = L.rays.far; a.lights = L.rays.lights; a.n = L.n;
-  for (int l = 0; l < 3; ++l) { a.jitter[l] = L.jitter[l]; a.us[l] = make_uspec(L.num_samples[l], L.jitter[l] != nullptr); }
+  a.origins = L.rays.origins; a.directions = L.rays.directions; a.near = L.rays.near; a.far = L.rays.far; a.n = L.n;
+  // the per-phase records (rc_fused_common.h), from the same fields as the arrays behind them
+  for (int l = 0; l < 3; ++l) a.rs[l] = RcResampleRec{L.jitter[l], make_uspec(L.num_samples[l], L.jitter[l] != nullptr), L.anneal, L.padding};
+  for (int g = 0; g < 3; ++g) {
+    RcLookupRec& q = a.look[g];
+    for (int l = 0; l < RC_MAX_GRID_LEVELS; ++l) {
+      const RcGridLevel& lv = L.grid[g]->lvl[l];
+      q.table[l] = g == 2 ? L.pair_table[l] : (l < kFusedDense ? L.cell_table[g][l] : lv.table);
+      q.size[l] = lv.size; q.mask[l] = lv.mask;
+    }
+    q.bbox = L.grid[g]->bbox; q.precondition = L.grid[g]->precondition; q.contract_radius = L.contract_radius; q.density_bias = L.density_bias;
+  }
+  a.shade.sh = ShaderConsts{L.roughness_bias, L.irradiance_bias, L.ambient_bias, L.rgb_max, L.slf_ambient_bias};
+  a.shade.bg = L.bg; a.shade.density_bias = L.density_bias; a.shade.contract_radius = L.contract_radius;
+  a.shade.lights = L.rays.lights; a.shade.viewdirs = L.rays.viewdirs;
+  for (int i = 0; i < 3; ++i) a.shade.pct[i] = L.pct[i];
   for (int g = 0; g < 4; ++g) a.grid[g] = *L.grid[g];
   for (int l = 0; l < RC_MAX_GRID_LEVELS; ++l) {
     a.pair_table[l] = L.pair_table[l];
     a.cell_table[0][l] = L.cell_table[0][l]; a.cell_table[1][l] = L.cell_table[1][l];
   }
   a.wstream = L.wstream; a.ide_coef = L.ide_coef;
-  a.anneal = L.anneal; a.padding = L.padding; a.density_bias = L.density_bias; a.contract_radius = L.contract_radius; a.bg = L.bg;
-  for (int i = 0; i < 3; ++i) a.pct[i] = L.pct[i];
-  a.sh = ShaderConsts{L.roughness_bias, L.irradiance_bias, L.ambient_bias, L.rgb_max, L.slf_ambient_bias};
   a.out = L.out;
 #ifdef RC_STAMPS
   {

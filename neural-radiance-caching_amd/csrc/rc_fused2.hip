@@ -350,9 +350,9 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   const float ox = r.ox, oy = r.oy, oz = r.oz, dx = r.dx, dy = r.dy, dz = r.dz, near = r.near, far = r.far;
   // (wave 0) resample S intervals from (prev sdist in s_prev [P+1], logit per bin): sdist -> s_out, tdist -> s_td
   auto resample = [&](int level, int P, int S, float logit, const float* s_prev) {
-    const bool hasj = a.jitter[level] != nullptr;
-    const float jit = hasj ? a.jitter[level][ray] : 0.0f;
-    sample_intervals_wave<false>(logit, P, S, a.us[level], hasj, jit, s_prev, s_cw, s_c, s_v, s_out, lane);
+    const bool hasj = a.rs[level].jitter != nullptr;
+    const float jit = hasj ? a.rs[level].jitter[ray] : 0.0f;
+    sample_intervals_wave<false>(logit, P, S, a.rs[level].us, hasj, jit, s_prev, s_cw, s_c, s_v, s_out, lane);
     for (int e2 = lane; e2 <= S; e2 += 64) s_td[e2] = s_out[e2] * far + (1.0f - s_out[e2]) * near;   // coord.py:259-260
     lds_sync<false>();
   };
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   };
   auto density_of = [&](float raw, float cx, float cy, float cz, float bbox) {
     const bool inside = (cx > -bbox) & (cx < bbox) & (cy > -bbox) & (cy < bbox) & (cz > -bbox) & (cz < bbox);
-    const float d = rc_safe_exp(raw + a.density_bias);
+    const float d = rc_safe_exp(raw + a.shade.density_bias);
     return inside ? d : 0.0f;
   };
   const int j = lane & 31, h = lane >> 5;
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   if (q == 0) {
     if (lane == 0) { s.sd[0][0] = 0.0f; s.sd[0][1] = 1.0f; }
     lds_sync<false>();
-    resample(0, 1, 64, a.anneal * safe_log(1.0f + a.padding), s.sd[0]);
+    resample(0, 1, 64, a.rs[0].anneal * safe_log(1.0f + a.rs[0].padding), s.sd[0]);
   }
   TB();
   RC_FSTAMP(1);
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     float mx, my, mz, t0, t1;
     mean_of(32 * q + j, mx, my, mz, t0, t1);
     float cx = mx, cy = my, cz = mz;
-    contract3(cx, cy, cz, a.contract_radius);
+    contract3(cx, cy, cz, a.shade.contract_radius);
     const float raw = level_tile<6, F_L0, 0>(a, ws, act_ray + q * kTileStride, lane, cx, cy, cz
 #ifdef RC_STAMPS
                                             , &stamps[2]
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     const float w = alpha_weight(x_dens[lane], s.td[lane], s.td[lane + 1], r.dnorm, true, lane);
     for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[1][e2] = s.out[e2];
     lds_sync<false>();
-    resample(1, 64, 64, a.anneal * safe_log(w + a.padding), s.sd[1]);
+    resample(1, 64, 64, a.rs[1].anneal * safe_log(w + a.rs[1].padding), s.sd[1]);
   }
   TB();
   RC_FSTAMP(4);
@@ -405,7 +405,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     float mx, my, mz, t0, t1;
     mean_of(32 * q + j, mx, my, mz, t0, t1);
     float cx = mx, cy = my, cz = mz;
-    contract3(cx, cy, cz, a.contract_radius);
+    contract3(cx, cy, cz, a.shade.contract_radius);
     const float raw = level_tile<7, F_L1, 1>(a, ws, act_ray + q * kTileStride, lane, cx, cy, cz
 #ifdef RC_STAMPS
                                             , &stamps[5]
@@ -420,15 +420,15 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     const float w = alpha_weight(x_dens[lane], s.td[lane], s.td[lane + 1], r.dnorm, true, lane);
     for (int e2 = lane; e2 <= 64; e2 += 64) s.sd[0][e2] = s.out[e2];
     lds_sync<false>();
-    resample(2, 64, 32, a.anneal * safe_log(w + a.padding), s.sd[0]);
+    resample(2, 64, 32, a.rs[2].anneal * safe_log(w + a.rs[2].padding), s.sd[0]);
   }
   TB();
   RC_FSTAMP(7);
   float mx, my, mz, t0, t1;
   mean_of(j, mx, my, mz, t0, t1);
   float cx = mx, cy = my, cz = mz;
-  const float zx = rc_div(mx, a.contract_radius), zy = rc_div(my, a.contract_radius), zz = rc_div(mz, a.contract_radius);
-  contract3(cx, cy, cz, a.contract_radius);
+  const float zx = rc_div(mx, a.shade.contract_radius), zy = rc_div(my, a.shade.contract_radius), zz = rc_div(mz, a.shade.contract_radius);
+  contract3(cx, cy, cz, a.shade.contract_radius);
   float* act = act_ray + lane;
   {
     // half-wave 0 looks up the level-2 density grid, half-wave 1 the appearance grid (interleaved pair tables);
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
         f32x16 gf[1];
         gf[0] = zero16();
         mlp_layer_d<1, 32, F_L2 + FR::B0, kNF, 8, kTW, kTCH>(ws, act, gf);
-        analytic_normal(gf[0], act_ray, j, h, zx, zy, zz, a.contract_radius, ngx, ngy, ngz);
+        analytic_normal(gf[0], act_ray, j, h, zx, zy, zz, a.shade.contract_radius, ngx, ngy, ngz);
       } else {
         tw_skip<F_L2 + FR::B0, rc_lfr32(32, 1)>(ws);
       }
@@ -557,8 +557,8 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
   if (young && pm == 3) __builtin_amdgcn_s_setprio(1);
   // ------------------------------------------------------------------ shader on the 32 samples (rc_dev_mlp.h shader_tile)
   constexpr int F0 = F_SH;
-  const float vx = a.viewdirs[3 * ray], vy = a.viewdirs[3 * ray + 1], vz = a.viewdirs[3 * ray + 2];
-  const ShaderConsts& k = a.sh;
+  const float vx = a.shade.viewdirs[3 * ray], vy = a.shade.viewdirs[3 * ray + 1], vz = a.shade.viewdirs[3 * ray + 2];
+  const ShaderConsts& k = a.shade.sh;
   // appearance features to their place behind the hidden feature: [0, 32) hidden | [32, 48) appearance | 48 bias
   if (q == 0) {
 #pragma unroll
@@ -720,7 +720,7 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     v[V_NG] = wnf * ngx; v[V_NG + 1] = wnf * ngy; v[V_NG + 2] = wnf * ngz;
     wave_sum_n<V_COUNT>(v);
     const float accw = v[V_ACC];
-    const float bgw = fmaxf(0.0f, 1.0f - accw) * a.bg;
+    const float bgw = fmaxf(0.0f, 1.0f - accw) * a.shade.bg;
     store3(a.out.ptr[RC_OUT_RGB], st, ray, v[V_RGB] + bgw, v[V_RGB + 1] + bgw, v[V_RGB + 2] + bgw);
     store3(a.out.ptr[RC_OUT_DIRECT_RGB], st, ray, v[V_AD], v[V_AD + 1], v[V_AD + 2]);
     store3(a.out.ptr[RC_OUT_INDIRECT_DIFFUSE_RGB], st, ray, v[V_IDF], v[V_IDF + 1], v[V_IDF + 2]);
@@ -739,8 +739,8 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     v[V_MEAN] = wnf * mx; v[V_MEAN + 1] = wnf * my; v[V_MEAN + 2] = wnf * mz;
     v[V_RD] = wnf * sqrtf((r.ox - mx) * (r.ox - mx) + (r.oy - my) * (r.oy - my) + (r.oz - mz) * (r.oz - mz));
     v[V_LD] = 0.0f;
-    if (a.lights) {
-      const float lx = a.lights[3 * ray], ly = a.lights[3 * ray + 1], lz = a.lights[3 * ray + 2];
+    if (a.shade.lights) {
+      const float lx = a.shade.lights[3 * ray], ly = a.shade.lights[3 * ray + 1], lz = a.shade.lights[3 * ray + 2];
       v[V_LD] = wnf * sqrtf((lx - mx) * (lx - mx) + (ly - my) * (ly - my) + (lz - mz) * (lz - mz));
     }
     v[V_NP] = wnf * npx; v[V_NP + 1] = wnf * npy; v[V_NP + 2] = wnf * npz;
@@ -749,10 +749,10 @@ __global__ __launch_bounds__(kTW * 64, kRays == 2 ? 2 : 1) void k_cache_fused_te
     const float accw = v[V_ACC];
     store3(a.out.ptr[RC_OUT_MEANS], st, ray, v[V_MEAN], v[V_MEAN + 1], v[V_MEAN + 2]);
     store1(a.out.ptr[RC_OUT_RAY_DISTS], st, ray, v[V_RD]);
-    if (a.lights) store1(a.out.ptr[RC_OUT_LIGHT_DISTS], st, ray, v[V_LD]);
+    if (a.shade.lights) store1(a.out.ptr[RC_OUT_LIGHT_DISTS], st, ray, v[V_LD]);
     store3(a.out.ptr[RC_OUT_NORMALS_PRED], st, ray, v[V_NP], v[V_NP + 1], v[V_NP + 2]);
     store1(a.out.ptr[RC_OUT_DISTANCE_MEAN], st, ray, distance_mean(v[V_LOGT], accw, s.td));
-    distance_percentiles(a, ray, ray_ok, lane, wnf, accw, s.td, s.cw, a.out.ptr[RC_OUT_DISTANCE_PERCENTILE_5],
+    distance_percentiles([&](int i) { return a.shade.pct[i]; }, ray, ray_ok, lane, wnf, accw, s.td, s.cw, a.out.ptr[RC_OUT_DISTANCE_PERCENTILE_5],
                          a.out.ptr[RC_OUT_DISTANCE_MEDIAN], a.out.ptr[RC_OUT_DISTANCE_PERCENTILE_95]);
 #ifdef RC_STAMPS
     RC_FSTAMP(11);

@@ -45,19 +45,37 @@ constexpr int NF_FUSED = F_SH + ShaderFrags::COUNT;
 #else
 #define RC_FSTAMP_BUF nullptr
 #endif
+// ---- per-phase argument records of the one-wave kernel: what ONE phase of the ray's chain reads of the arguments, side by
+// side and 64-byte aligned, so that the phase's scalars arrive in two or three wide s_loads that the kernel issues one
+// phase ahead of their use (rc_fused.hip, head).  rc_launch_fused fills them; the two-wave kernel reads the same fields.
+// a lookup: the tables, sizes and masks of the grid's levels, with the scalars the proposal level needs around it
+struct alignas(64) RcLookupRec {
+  const float* table[RC_MAX_GRID_LEVELS];   // proposal grids 0 / 1: the cell table of a dense level, the hash table of a hashed one;
+                                            // level 2: the interleaved [density | appearance] tables (RcFusedLaunch::pair_table)
+  int32_t size[RC_MAX_GRID_LEVELS];
+  uint32_t mask[RC_MAX_GRID_LEVELS];
+  float bbox, precondition, contract_radius, density_bias;
+};
+// a resampling
+struct alignas(32) RcResampleRec { const float* jitter; USpec us; float anneal, padding; };
+// the shader and the compositing tail
+struct alignas(64) RcShadeRec {
+  ShaderConsts sh; float bg, density_bias, contract_radius;
+  const float* lights; const float* viewdirs;
+  float pct[3];
+};
+
 struct RcFusedArgs {
-  const float* origins; const float* directions; const float* viewdirs; const float* near; const float* far;
-  const float* lights;
+  const float* origins; const float* directions; const float* near; const float* far;
   int64_t n;
-  const float* jitter[3];
+  RcResampleRec rs[3];
+  RcLookupRec look[3];
+  RcShadeRec shade;
+  // the grids as every other kernel takes them: the two-wave kernel's lookups (level kinds, cell records) read these
   RcGridDev grid[4];
   const float* pair_table[RC_MAX_GRID_LEVELS];
   const float* cell_table[2][RC_MAX_GRID_LEVELS];
   const float* wstream; const float* ide_coef;
-  USpec us[3];
-  float anneal, padding, density_bias, contract_radius, bg;
-  float pct[3];
-  ShaderConsts sh;
   rc_outputs out;
   unsigned long long* stamps;
   int32_t prio_mode;        // rc_fused2.hip: wave priorities of the workgroup that arrived second on its CU (see the kernel)
@@ -92,19 +110,24 @@ __device__ __forceinline__ Scratch carve_scratch(float* scr) {
   return Scratch{{scr, scr + 68}, scr + 2 * 68, scr + 3 * 68, scr + 4 * 68, scr + 5 * 68, scr + 6 * 68};
 }
 
+// a resampling's record in registers (the one-wave kernel reads it one phase ahead, rc_fused.hip)
+struct ResampleRegs { const float* jitter; USpec us; float anneal, padding; };
+__device__ __forceinline__ ResampleRegs fetch_resample(const RcResampleRec& q) { return ResampleRegs{q.jitter, q.us, q.anneal, q.padding}; }
+#define RC_RESAMPLE_PINS(rs) "s"(rs.jitter), "s"(rs.us.start), "s"(rs.us.stop), "s"(rs.us.max_jitter), "s"(rs.anneal), "s"(rs.padding)
+
 // resample S intervals from (prev sdist in s_prev [P+1], logit per bin): sdist -> s.out, tdist -> s.td
 // (the ray index by reference, as the kernels' lambdas had it: by value the EXPORT instantiation without GRAD gets four
 // more s_waitcnt in its level-2 resampling, profiles/r11_fused_shared_phases_ab.txt)
 template <bool FRONT>
-__device__ __forceinline__ void resample(const RcFusedArgs& a, const Ray& r, const int64_t& ray, const Scratch& s, int lane, int level, int P, int S,
-                                         float logit, const float* s_prev) {
-  const bool hasj = a.jitter[level] != nullptr;
-  const float jit = hasj ? a.jitter[level][ray] : 0.0f;
+__device__ __forceinline__ void resample(const RcFusedArgs& a, const ResampleRegs& rs, const Ray& r, const int64_t& ray, const Scratch& s, int lane,
+                                         int P, int S, float logit, const float* s_prev) {
+  const bool hasj = rs.jitter != nullptr;
+  const float jit = hasj ? rs.jitter[ray] : 0.0f;
 #if defined(RC_ABL) && RC_ABL == 14
   for (int e2 = lane; e2 <= S; e2 += 64) s.out[e2] = (float)e2 / (float)S + 1e-9f * logit;
   lds_sync<false>();
 #else
-  sample_intervals_wave<false>(logit, P, S, a.us[level], hasj, jit, s_prev, s.cw, s.c, s.v, s.out, lane);
+  sample_intervals_wave<false>(logit, P, S, rs.us, hasj, jit, s_prev, s.cw, s.c, s.v, s.out, lane);
 #endif
   if constexpr (FRONT) {
     if (a.use_raydist) {      // TransientNeRFModel samples its primary rays in power-ladder distance (models.py:122, 183-191)
@@ -128,9 +151,9 @@ __device__ __forceinline__ void mean_of(const Ray& r, const float* s_td, int idx
   mx = r.dx * tm + r.ox; my = r.dy * tm + r.oy; mz = r.dz * tm + r.oz;
 }
 
-__device__ __forceinline__ float density_of(const RcFusedArgs& a, float raw, float cx, float cy, float cz, float bbox) {
+__device__ __forceinline__ float density_of(float density_bias, float raw, float cx, float cy, float cz, float bbox) {
   const bool inside = (cx > -bbox) & (cx < bbox) & (cy > -bbox) & (cy < bbox) & (cz > -bbox) & (cz < bbox);
-  const float d = rc_safe_exp(raw + a.density_bias);
+  const float d = rc_safe_exp(raw + density_bias);
   return inside ? d : 0.0f;
 }
 
@@ -141,17 +164,17 @@ __device__ __forceinline__ float& jac_at(float* act_ray, int j, int e) { return 
 // level-2 combine of a grid level from its fetched corners: the four preconditioned features, and (GRAD) the raw
 // derivatives level2_jacobian takes
 template <bool GRAD>
-__device__ __forceinline__ void level2_combine(const RcGridDev& g, const Corners<4>& C, float (&f)[4], float (&jd)[GRAD ? 12 : 1]) {
+__device__ __forceinline__ void level2_combine(float precondition, const Corners<4>& C, float (&f)[4], float (&jd)[GRAD ? 12 : 1]) {
   float v[4];
   grid_combine<4, GRAD>(C, v, jd);
 #pragma unroll
-  for (int c = 0; c < 4; ++c) f[c] = v[c] * g.precondition;
+  for (int c = 0; c < 4; ++c) f[c] = v[c] * precondition;
 }
 // half-wave 0 (the density grid) parks the three Jacobian rows of grid level l (a constant where it is called), a dense
 // level's axes swapped; behind the caller's use of the features, as both kernels have it
-__device__ __forceinline__ void level2_jacobian(const RcGridDev& g, int l, const float (&jd)[12], float* act_ray, int j, int h) {
+__device__ __forceinline__ void level2_jacobian(float precondition, int size, float bbox, int l, const float (&jd)[12], float* act_ray, int j, int h) {
   const bool dense = l < kFusedDense;       // compile-time, as in the fetch
-  const float s = g.precondition * (float)g.lvl[l].size / (2.0f * g.bbox);
+  const float s = precondition * (float)size / (2.0f * bbox);
   if (h == 0) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -229,7 +252,9 @@ __device__ __forceinline__ float distance_mean(float logt, float accw, const flo
 }
 
 // the three distance percentiles: inclusive scan of the normalised weights into s_cw, lanes 0-2 interpolate one each
-__device__ __forceinline__ void distance_percentiles(const RcFusedArgs& a, int64_t ray, bool ray_ok, int lane, float wnf, float accw,
+// (pct_of(lane): the percentile of lane 0, 1, 2)
+template <class PCT>
+__device__ __forceinline__ void distance_percentiles(const PCT& pct_of, int64_t ray, bool ray_ok, int lane, float wnf, float accw,
                                                      const float* s_td, float* s_cw, float* p5, float* median, float* p95) {
   const float wn = wnf / fmaxf(RC_EPS, accw);
   const float incl = wave_scan_incl(wn, lane);
@@ -238,7 +263,7 @@ __device__ __forceinline__ void distance_percentiles(const RcFusedArgs& a, int64
   if (lane == 0) s_cw[32] = 1.0f;
   lds_sync<false>();
   if (lane < 3 && ray_ok) {
-    const float ps = a.pct[lane] / 100.0f;
+    const float ps = pct_of(lane) / 100.0f;
     const float v = interp1(ps, s_cw, s_td, 33);
     float* const dst = lane == 0 ? p5 : (lane == 1 ? median : p95);
     if (dst) dst[ray] = v;
