@@ -1,7 +1,7 @@
 // C-ABI host of the radiance-cache renderer (see include/rc_abi.h).
 //
 // Owns: the handle, device copies of the hash/dense tables, the MFMA-fragment-packed MLP weights,
-// the per-batch workspace and the small entry points.  The launch sequence that replaces
+// the per-batch workspace (its sets and buffer names: rc_ws.h) and the small entry points.  The launch sequence that replaces
 // BaseNeRFModel.__call__ is rc_render_host.inc, the material stage rc_material_host.inc; like
 // every other *_host.inc they are included at the end of this file.
 #include <dlfcn.h>
@@ -20,6 +20,7 @@
 #include "rc_internal.h"
 #include "rc_pack_host.h"
 #include "rc_itof_host.h"
+#include "rc_ws.h"
 #include "rc_prng_host.h"     // rc_round_half_even: the split of K, as the randoms plan sizes its members
 
 void rc_launch_hashgrid_src(const RcGridDev& g, const float* points, int soa_in, const int32_t* src, int64_t n_src,
@@ -63,136 +64,10 @@ struct Packs {
   struct { DevBuf kernel, bias; } raw[RAW_COUNT];   // material / light-sampler layers on the Flax layout
 };
 
-// Workspace buffer: device pointer, capacity in bytes, element count of the last request (rc_workspace_ptr).
-struct WsBuf { float* p = nullptr; size_t bytes = 0; int64_t count = 0; };
-// One set of rc_render_rays' launch-per-stage buffers (ensure_workspace).
-struct RenderWs {
-  WsBuf sdist[RC_MAX_LEVELS], tdist[RC_MAX_LEVELS], means[RC_MAX_LEVELS], feat[RC_MAX_LEVELS], density[RC_MAX_LEVELS],
-      weights[RC_MAX_LEVELS];
-  WsBuf hbuf, normals_pred, normals_grad, jac, app, shade, debug, env_rgb, rgb_noenv, acc_ws, inds, src_idx, filt_weight, acc_sel;
-  WsBuf feat_sel, hbuf_sel, normals_sel, density_sel;   // lean resampling pass: the picked samples only
-  WsBuf t_irr, t_slf, tshade;                          // time-resolved cache: set 0 only
-};
-// Set 0 only: rc_render_material's buffers and the shadow rays of rc_render_transient.
-struct ExtraWs {
-  WsBuf m_pts, m_nrm, m_feat, m_mat, m_feat_all, m_mat_all, l_feat, l_vmf, l_vmf_logit, sec_origins, sec_dirs, sec_near,
-      sec_far, sec_lights, sec_samples, m_local_view, sec_rgb, sec_acc, sec_env;
-  WsBuf sh_origins, sh_dirs, sh_near, sh_far, sh_normals, sh_lights, sh_acc;
-};
-// rc_density_backward.
-struct TrainWs { WsBuf feat, dfeat, a1, a2, d1, d2, fe, graw, density, partial; };
-// rc_interlevel_backward, beside its RenderWs (the training forward): per proposal level d loss / d density and the
-// sample means as points [n S][3]; the per-ray loss sums.
-struct InterlevelWs { WsBuf d_density[RC_MAX_LEVELS], points[RC_MAX_LEVELS]; WsBuf loss_ray; };
-// rc_data_backward, beside its RenderWs (the training forward): the ray rgb, per-ray loss sums, per-sample d loss / d
-// density and d loss / d rgb_s, the means as points [n S][3]; then one sample chunk of the shader backward
-// (rc_data_host.inc; rc_train_host.inc's dense-layer helpers: recompute activations, their gradients, the weight-gradient
-// K-slices and a column of ones).
-struct DataWs {
-  WsBuf rgb, loss_ray, d_density, d_rgbs, points;
-  WsBuf f96, heads, p3, ib_in, x328, s0, s1, sb, i1, i2, io, so;
-  WsBuf dheads, dio, dso, dsb, dx328, ds1, ds0, di2, di1, dib_in, db128, dp3, df96, dfeat, dapp, part, ones;
-};
-// rc_geometry_backward, beside its RenderWs (the training forward): per-ray values of the four terms, per-sample d loss /
-// d density and d loss / d pred_raw, the means as points [n S][3]; one sample chunk of the hidden vectors h64 and
-// d feature64, the weight-gradient K-slices and a column of ones; rc_density_regularizer's per-table partial sums.
-struct GeometryWs { WsBuf loss_ray, d_density, d_pred, points, h64, dfeat, part, ones, reg_part; };
-// rc_adam_update: the per-tile sums of g^2 (doubles), the norm and the clip multiplier; rc_load_params_flat: the dense
-// segments of a layout gathered for the one copy to the host.
-struct OptimWs { WsBuf part, norm, mult, stage; };
-// rc_light_sampling_backward (its forward on set 0 and WS_SECONDARY): the primary pass's composite (not read), the light
-// head's recompute and its gradients, the per-point loss sums, the weight-gradient K slices and a column of ones;
-// rc_light_regularizer's per-table partial sums.
-struct LightWs { WsBuf cache_rgb, cache_acc, h0, h1, vp, dvp, dh1, dh0, dfeat, loss_ray, part, ones, reg_part; };
-// rc_material_smoothness_backward (its forward on set 0): the primary pass's composite (not read), the lookup points and
-// features of both evaluations, the materials at x', the per-point and per-workgroup loss sums, d loss / d features, the
-// per-workgroup weight-gradient partials; rc_material_regularizer's per-table partial sums.
-struct MaterialWs { WsBuf cache_rgb, cache_acc, pts, feat, mat_p, loss_ray, loss_part, dfeat, part, reg_part; };
-// rc_material_data_backward (its forward is rc_render_material on set 0 and WS_SECONDARY): the primary pass's composite
-// ("cache_rgb" is read by the loss), the rebuilt rgb, the per-point loss sums and d loss / d material, d loss / d features,
-// the per-workgroup weight-gradient partials and loss sums.
-// rc_material_data_backward_env adds d loss / d (EnvMap radiance) per secondary ray and one row chunk of the EnvMap's
-// backward (rc_envmap_bwd.hip): the recompute's activations (xb = [layer_2's output | the encoded direction]), their
-// gradients, the weight-gradient K slices and a 1.0f.
-struct MatDataWs {
-  WsBuf cache_rgb, cache_acc, rgb, loss_ray, dmat, dfeat, part, loss_part;
-  WsBuf d_env, e_h0, e_h1, e_xb, e_hb, e_raw, e_draw, e_dhb, e_dxb, e_dh1, e_dh0, e_part, e_ones;
-};
-// rc_transient_data_backward (its forward is rc_render_transient on set 0): the rendered histograms, G = d loss / d rgb and
-// the temporal filter's transpose of it, the per-ray loss and mse sums; one chunk of kRcTdChunkRays rays of the heads'
-// backward (dZ of both heads, their inputs row-major, the weight-gradient K slices, a 1.0f); the adjoints of everything
-// k_transient_shader hands to k_transient_bins, for all n rays.
-struct TransDataWs {
-  WsBuf rgb, G, Gt, loss_ray, dz_irr, dz_slf, x_irr, x_slf, part, ones;
-  WsBuf d_t_irr, d_t_slf, d_tint_ibrdf, d_direct, d_weights;
-  WsBuf d_density, points;      // rc_transient_data_backward_sampler: d loss / d density through the weights, the means [n S][3]
-};
-
-// rc_eval_image: the bin sums of both histograms (n_bins > 0), the post-processed images where the caller gives no buffer
-// of its own, and the per-workgroup partial sums of the three kernels (doubles).  rc_eval_shift_invariant: the metric maps
-// of one di row of shifts, the search state ([4][H][W]: best pooled, best metric, di, dj) and the per-workgroup partial
-// sums of both searches (doubles).
-struct EvalWs { WsBuf binsum_pred, binsum_gt, post_pred, post_gt, part, si_metric, si_state, si_part; };
-
-// rc_eval_albedo / rc_albedo_ratio: the view's own pair rows (no ratio handed in), the valid pixels per workgroup (int32),
-// the select's state (RcAlbedoState) and the per-workgroup partial sums (doubles).
-struct AlbedoWs { WsBuf pairs, wg, state, part; };
-
-// rc_weighted_percentile / rc_image_max / rc_vis_images: the select's state (RcVisState), its per-workgroup weight sums
-// (doubles), the per-workgroup maxima and the sums over the bins of the histogram images ([slots][H W][3]).
-struct VisWs { WsBuf state, part, maxpart, binsum; };
-
-// rc_mask_backward, beside its RenderWs (the training forward): the per-ray loss terms, per-sample d loss / d density and
-// the means as points [n S][3].
-struct MaskWs { WsBuf loss_ray, d_density, points; };
-
-// rc_env_tables / rc_env_pick: the per-workgroup sums of the tables' normaliser (doubles) and the per-pick (score, texel)
-// maxima (64-bit integers).
-struct RelightWs { WsBuf part, best; };
-
-// rc_normals_backward: the last level's grid features and their Jacobian, d raw / d feature (feature-major) and G^ = d L /
-// d (the Jacobian-chained gradient) for the scatter, the point-major operands of the weight-gradient contraction
-// (u [n][32]; t0, a0, t1, a2 [n][64]; a column of ones), its per-workgroup partials, and the normals when the caller wants none.
-struct NormalsWs { WsBuf feat, jac, gf, ghat, u, t0, a0, t1, a2, ones, partial, normals; };
-// rc_geometry_smoothness_backward, beside its RenderWs (the training forward): the perturbed means (SoA, as the density MLP
-// reads them) with their features, Jacobian, density and analytic normals; the means and perturbed means as points [n S][3];
-// d loss / d normals and d loss / d density at both point sets; the per-ray loss values.
-struct GSmoothWs { WsBuf means_p, feat_p, jac_p, density_p, normals_p, points, points_p, d_normals, d_normals_p, d_density, d_density_p, loss_ray; };
-// rc_query_points / rc_density_lattice, one chunk of points: the points as SoA [3][C], the grid features (feature-major)
-// and their Jacobian, the density where the caller wants none, both kinds of normals as SoA, the material grid's features.
-struct QueryWs { WsBuf means, feat, jac, density, normals_pred, normals_grad, m_feat; };
-// rc_isosurface (RcIsoArgs): per lattice point the mask of crossing owned edges and the cell's triangle count (bytes) and
-// the index of its first vertex (int32), per tile and per group the sums / offsets of both scans (int32; int64 pairs), the
-// RcIsoState.
-struct IsoWs { WsBuf mask, tcount, tile_v, tile_t, group_v, group_t, group_off, vbase, state; };
-// rc_bake_atlas / rc_query_cache_diffuse, beside the QueryWs of WS_QUERY, one chunk: the texels' points as rows [C][3] and
-// their owners (int32); the last level's hidden vectors (k_density_mlp's accumulator layout) and the appearance grid's
-// features (feature-major).
-struct AtlasWs { WsBuf points, owner, hidden, app_feat; };
-
-// Workspace sets.  WS_RENDER0-3 serve rc_render_rays, one per caller stream, so that independent batches enqueued on
-// different streams overlap (the least recently used one is taken over when a fifth stream shows up); WS_RENDER0 also
-// serves rc_render_material / rc_render_transient (with ExtraWs), whose batched secondary trace runs on WS_SECONDARY.
-// WS_TRAIN serves rc_density_backward (TrainWs only), WS_INTERLEVEL rc_interlevel_backward, WS_DATA rc_data_backward,
-// WS_GEOMETRY rc_geometry_backward and rc_density_regularizer, WS_OPTIM rc_adam_update and rc_load_params_flat, WS_LIGHT
-// the buffers of rc_light_sampling_backward's own (its forward runs on WS_RENDER0 + WS_SECONDARY) and rc_light_regularizer,
-// WS_MATERIAL those of rc_material_smoothness_backward (its forward runs on WS_RENDER0) and rc_material_regularizer,
-// WS_MATDATA those of rc_material_data_backward / rc_material_data_backward_env (their forward is rc_render_material's, on WS_RENDER0 + WS_SECONDARY),
-// WS_TRANSDATA those of rc_transient_data_backward (its forward is rc_render_transient's, on WS_RENDER0), WS_EVAL
-// rc_eval_image and rc_eval_shift_invariant, WS_ALBEDO rc_eval_albedo and rc_albedo_ratio, WS_VIS rc_weighted_percentile, rc_image_max and rc_vis_images,
-// WS_MASK rc_mask_backward, WS_RELIGHT rc_env_tables and rc_env_pick, WS_NORMALS rc_normals_backward, WS_GSMOOTH
-// rc_geometry_smoothness_backward, WS_QUERY rc_query_points and rc_density_lattice, WS_ISO rc_isosurface,
-// WS_ATLAS the buffers of rc_bake_atlas and rc_query_cache_diffuse's own (their query launches run on WS_QUERY).
-enum WsSetId { WS_RENDER0, WS_RENDER1, WS_RENDER2, WS_RENDER3, WS_SECONDARY, WS_TRAIN, WS_INTERLEVEL, WS_DATA, WS_GEOMETRY, WS_OPTIM,
-               WS_LIGHT, WS_MATERIAL, WS_MATDATA, WS_TRANSDATA, WS_EVAL, WS_ALBEDO, WS_VIS, WS_MASK, WS_RELIGHT, WS_NORMALS, WS_GSMOOTH, WS_QUERY, WS_ISO, WS_ATLAS, WS_COUNT };
-// rc_workspace_ptr's "<prefix><name>" for each set
-const char* const kWsPrefix[WS_COUNT] = {"", "p1:", "p2:", "p3:", "s:", "t:", "i:", "d:", "g:", "o:", "ls:", "ms:", "md:", "td:", "ev:", "ea:", "vz:", "mk:", "rl:", "nb:", "gs:", "q:", "iso:", "atlas:"};
-
-struct WsSet {
-  RenderWs r;
-  std::variant<std::monostate, ExtraWs, TrainWs, InterlevelWs, DataWs, GeometryWs, OptimWs, LightWs, MaterialWs, MatDataWs, TransDataWs, EvalWs, AlbedoWs, VisWs, MaskWs, RelightWs, NormalsWs, GSmoothWs, QueryWs, IsoWs, AtlasWs> x;   // the set's extra buffers (ws_extra)
-  // who used the set last: a call whose stream differs from the previous user's first waits for that user's last call
-  // (event), so two streams never run on one set at the same time (WsUse)
+// A workspace set (rc_ws.h: its buffers, the registry of their names) and who used it last: a call whose stream differs
+// from the previous user's first waits for that user's last call (event), so two streams never run on one set at the same
+// time (WsUse).
+struct WsSet : WsBufs {
   hipStream_t stream = nullptr;
   bool used = false;
   hipEvent_t done = nullptr;
@@ -203,121 +78,6 @@ template <class X> X& ws_extra(WsSet& s) {
   if (X* p = std::get_if<X>(&s.x)) return *p;
   return s.x.template emplace<X>();
 }
-
-// Every workspace buffer by name, for rc_workspace_ptr ("<name>", per-level buffers "<name><level>") and rc_destroy.
-struct WsName {
-  const char* name;
-  WsBuf RenderWs::*r = nullptr; WsBuf (RenderWs::*lv)[RC_MAX_LEVELS] = nullptr; WsBuf ExtraWs::*x = nullptr; WsBuf TrainWs::*t = nullptr;
-  WsBuf InterlevelWs::*i = nullptr; WsBuf (InterlevelWs::*ilv)[RC_MAX_LEVELS] = nullptr; WsBuf DataWs::*d = nullptr;
-  WsBuf GeometryWs::*g = nullptr; WsBuf OptimWs::*o = nullptr; WsBuf LightWs::*ls = nullptr;
-  WsBuf MaterialWs::*ms = nullptr; WsBuf MatDataWs::*md = nullptr; WsBuf TransDataWs::*td = nullptr;
-  WsBuf EvalWs::*ev = nullptr; WsBuf AlbedoWs::*ea = nullptr; WsBuf VisWs::*vz = nullptr;
-  WsBuf MaskWs::*mk = nullptr; WsBuf RelightWs::*rl = nullptr; WsBuf NormalsWs::*nb = nullptr; WsBuf GSmoothWs::*gs = nullptr;
-  WsBuf QueryWs::*q = nullptr; WsBuf IsoWs::*iso = nullptr; WsBuf AtlasWs::*at = nullptr;
-  constexpr WsName(const char* s, WsBuf RenderWs::*m) : name(s), r(m) {}
-  constexpr WsName(const char* s, WsBuf (RenderWs::*m)[RC_MAX_LEVELS]) : name(s), lv(m) {}
-  constexpr WsName(const char* s, WsBuf ExtraWs::*m) : name(s), x(m) {}
-  constexpr WsName(const char* s, WsBuf TrainWs::*m) : name(s), t(m) {}
-  constexpr WsName(const char* s, WsBuf InterlevelWs::*m) : name(s), i(m) {}
-  constexpr WsName(const char* s, WsBuf (InterlevelWs::*m)[RC_MAX_LEVELS]) : name(s), ilv(m) {}
-  constexpr WsName(const char* s, WsBuf DataWs::*m) : name(s), d(m) {}
-  constexpr WsName(const char* s, WsBuf GeometryWs::*m) : name(s), g(m) {}
-  constexpr WsName(const char* s, WsBuf OptimWs::*m) : name(s), o(m) {}
-  constexpr WsName(const char* s, WsBuf LightWs::*m) : name(s), ls(m) {}
-  constexpr WsName(const char* s, WsBuf MaterialWs::*m) : name(s), ms(m) {}
-  constexpr WsName(const char* s, WsBuf MatDataWs::*m) : name(s), md(m) {}
-  constexpr WsName(const char* s, WsBuf TransDataWs::*m) : name(s), td(m) {}
-  constexpr WsName(const char* s, WsBuf EvalWs::*m) : name(s), ev(m) {}
-  constexpr WsName(const char* s, WsBuf AlbedoWs::*m) : name(s), ea(m) {}
-  constexpr WsName(const char* s, WsBuf VisWs::*m) : name(s), vz(m) {}
-  constexpr WsName(const char* s, WsBuf MaskWs::*m) : name(s), mk(m) {}
-  constexpr WsName(const char* s, WsBuf RelightWs::*m) : name(s), rl(m) {}
-  constexpr WsName(const char* s, WsBuf NormalsWs::*m) : name(s), nb(m) {}
-  constexpr WsName(const char* s, WsBuf GSmoothWs::*m) : name(s), gs(m) {}
-  constexpr WsName(const char* s, WsBuf QueryWs::*m) : name(s), q(m) {}
-  constexpr WsName(const char* s, WsBuf IsoWs::*m) : name(s), iso(m) {}
-  constexpr WsName(const char* s, WsBuf AtlasWs::*m) : name(s), at(m) {}
-  // the buffer in set `s` (level `l` of a per-level buffer, l < 0 for the others); nullptr when the set has none
-  WsBuf* in(WsSet& s, int l) const {
-    if (l < 0) {
-      if (r) return &(s.r.*r);
-      if (x) return one(s, x);
-      if (t) return one(s, t);
-      if (i) return one(s, i);
-      if (d) return one(s, d);
-      if (g) return one(s, g);
-      if (o) return one(s, o);
-      if (ls) return one(s, ls);
-      if (ms) return one(s, ms);
-      if (md) return one(s, md);
-      if (td) return one(s, td);
-      if (ev) return one(s, ev);
-      if (ea) return one(s, ea);
-      if (vz) return one(s, vz);
-      if (mk) return one(s, mk);
-      if (rl) return one(s, rl);
-      if (nb) return one(s, nb);
-      if (gs) return one(s, gs);
-      if (q) return one(s, q);
-      if (iso) return one(s, iso);
-      return at ? one(s, at) : nullptr;
-    }
-    if (lv) return &(s.r.*lv)[l];
-    InterlevelWs* p = ilv ? std::get_if<InterlevelWs>(&s.x) : nullptr;
-    return p ? &(p->*ilv)[l] : nullptr;
-  }
-  template <class X> static WsBuf* one(WsSet& s, WsBuf X::*m) { X* p = std::get_if<X>(&s.x); return p ? &(p->*m) : nullptr; }
-};
-namespace wsn {
-using R = RenderWs; using X = ExtraWs; using T = TrainWs; using I = InterlevelWs; using D = DataWs; using G = GeometryWs; using O = OptimWs;
-using L = LightWs; using M = MaterialWs; using MD = MatDataWs; using TD = TransDataWs; using EV = EvalWs; using EA = AlbedoWs; using VZ = VisWs; using MK = MaskWs; using RL = RelightWs; using NB = NormalsWs; using GS = GSmoothWs; using Q = QueryWs; using ISO = IsoWs; using AT = AtlasWs;
-#define WS(S, m) WsName(#m, &S::m)
-constexpr WsName kTable[] = {
-    WS(R, sdist), WS(R, tdist), WS(R, means), WS(R, feat), WS(R, density), WS(R, weights), WS(R, hbuf), WS(R, normals_pred),
-    WS(R, normals_grad), WS(R, jac), WS(R, app), WS(R, shade), WS(R, debug), WS(R, env_rgb), WS(R, rgb_noenv), WS(R, acc_ws),
-    WS(R, inds), WS(R, src_idx), WS(R, filt_weight), WS(R, acc_sel), WS(R, feat_sel), WS(R, hbuf_sel), WS(R, normals_sel),
-    WS(R, density_sel), WS(R, t_irr), WS(R, t_slf), WS(R, tshade),
-    WS(X, m_pts), WS(X, m_nrm), WS(X, m_feat), WS(X, m_mat), WS(X, m_feat_all), WS(X, m_mat_all), WS(X, l_feat), WS(X, l_vmf),
-    WS(X, l_vmf_logit), WS(X, sec_origins), WS(X, sec_dirs), WS(X, sec_near), WS(X, sec_far), WS(X, sec_lights),
-    WS(X, sec_samples), WS(X, m_local_view), WS(X, sec_rgb), WS(X, sec_acc), WS(X, sec_env), WS(X, sh_origins), WS(X, sh_dirs),
-    WS(X, sh_near), WS(X, sh_far), WS(X, sh_normals), WS(X, sh_lights), WS(X, sh_acc),
-    WS(T, feat), WS(T, dfeat), WS(T, a1), WS(T, a2), WS(T, d1), WS(T, d2), WS(T, fe), WS(T, graw), WS(T, density), WS(T, partial),
-    WS(I, d_density), WS(I, points), WS(I, loss_ray),
-    WS(D, rgb), WS(D, loss_ray), WS(D, d_density), WS(D, d_rgbs), WS(D, points), WS(D, f96), WS(D, heads), WS(D, p3),
-    WS(D, ib_in), WS(D, x328), WS(D, s0), WS(D, s1), WS(D, sb), WS(D, i1), WS(D, i2), WS(D, io), WS(D, so), WS(D, dheads),
-    WS(D, dio), WS(D, dso), WS(D, dsb), WS(D, dx328), WS(D, ds1), WS(D, ds0), WS(D, di2), WS(D, di1), WS(D, dib_in),
-    WS(D, db128), WS(D, dp3), WS(D, df96), WS(D, dfeat), WS(D, dapp), WS(D, part), WS(D, ones),
-    WS(G, loss_ray), WS(G, d_density), WS(G, d_pred), WS(G, points), WS(G, h64), WS(G, dfeat), WS(G, part), WS(G, ones),
-    WS(G, reg_part), WS(O, part), WS(O, norm), WS(O, mult), WS(O, stage),
-    WS(L, cache_rgb), WS(L, cache_acc), WS(L, h0), WS(L, h1), WS(L, vp), WS(L, dvp), WS(L, dh1), WS(L, dh0), WS(L, dfeat),
-    WS(L, loss_ray), WS(L, part), WS(L, ones), WS(L, reg_part),
-    WS(M, cache_rgb), WS(M, cache_acc), WS(M, pts), WS(M, feat), WS(M, mat_p), WS(M, loss_ray), WS(M, loss_part), WS(M, dfeat),
-    WS(M, part), WS(M, reg_part),
-    WS(MD, cache_rgb), WS(MD, cache_acc), WS(MD, rgb), WS(MD, loss_ray), WS(MD, dmat), WS(MD, dfeat), WS(MD, part),
-    WS(MD, loss_part), WS(MD, d_env), WS(MD, e_h0), WS(MD, e_h1), WS(MD, e_xb), WS(MD, e_hb), WS(MD, e_raw), WS(MD, e_draw),
-    WS(MD, e_dhb), WS(MD, e_dxb), WS(MD, e_dh1), WS(MD, e_dh0), WS(MD, e_part), WS(MD, e_ones),
-    WS(TD, rgb), WS(TD, G), WS(TD, Gt), WS(TD, loss_ray), WS(TD, dz_irr), WS(TD, dz_slf), WS(TD, x_irr), WS(TD, x_slf), WS(TD, part),
-    WS(TD, ones), WS(TD, d_t_irr), WS(TD, d_t_slf), WS(TD, d_tint_ibrdf), WS(TD, d_direct), WS(TD, d_weights),
-    WS(TD, d_density), WS(TD, points),
-    WS(EV, binsum_pred), WS(EV, binsum_gt), WS(EV, post_pred), WS(EV, post_gt), WS(EV, part),
-    WS(EV, si_metric), WS(EV, si_state), WS(EV, si_part),
-    WS(EA, pairs), WS(EA, wg), WS(EA, state), WS(EA, part),
-    WS(VZ, state), WS(VZ, part), WS(VZ, maxpart), WS(VZ, binsum),
-    WS(MK, loss_ray), WS(MK, d_density), WS(MK, points),
-    WS(RL, part), WS(RL, best),
-    WS(NB, feat), WS(NB, jac), WS(NB, gf), WS(NB, ghat), WS(NB, u), WS(NB, t0), WS(NB, a0), WS(NB, t1), WS(NB, a2), WS(NB, ones),
-    WS(NB, partial), WS(NB, normals),
-    WS(GS, means_p), WS(GS, feat_p), WS(GS, jac_p), WS(GS, density_p), WS(GS, normals_p), WS(GS, points), WS(GS, points_p),
-    WS(GS, d_normals), WS(GS, d_normals_p), WS(GS, d_density), WS(GS, d_density_p), WS(GS, loss_ray),
-    WS(Q, means), WS(Q, feat), WS(Q, jac), WS(Q, density), WS(Q, normals_pred), WS(Q, normals_grad), WS(Q, m_feat),
-    WS(ISO, mask), WS(ISO, tcount), WS(ISO, tile_v), WS(ISO, tile_t), WS(ISO, group_v), WS(ISO, group_t), WS(ISO, group_off),
-    WS(ISO, vbase), WS(ISO, state),
-    WS(AT, points), WS(AT, owner), WS(AT, hidden), WS(AT, app_feat)};
-#undef WS
-constexpr size_t listed() { size_t n = 0; for (const WsName& e : kTable) n += (e.lv || e.ilv) ? RC_MAX_LEVELS : 1; return n; }
-static_assert(listed() * sizeof(WsBuf) == sizeof(R) + sizeof(X) + sizeof(T) + sizeof(I) + sizeof(D) + sizeof(G) + sizeof(O) + sizeof(L) + sizeof(M) + sizeof(MD) + sizeof(TD) + sizeof(EV) + sizeof(EA) + sizeof(VZ) + sizeof(MK) + sizeof(RL) + sizeof(NB) + sizeof(GS) + sizeof(Q) + sizeof(ISO) + sizeof(AT),
-              "the table lists every workspace buffer");
-}  // namespace wsn
 
 constexpr int kEvSlots = 16;
 
@@ -992,29 +752,14 @@ int ensure_workspace(rc_handle* h, RenderWs& w, int64_t n) {
 }
 
 void free_workspace(rc_handle* h) {
-  for (WsSet& s : h->ws)
-    for (const WsName& e : wsn::kTable)
-      for (int l = -1; l < RC_MAX_LEVELS; ++l)
-        if (WsBuf* b = e.in(s, l)) free_buf(*b);
+  for (WsSet& s : h->ws) ws_for_each(s, [](WsBuf& b) { free_buf(b); });
 }
 
 // rc_workspace_ptr: "<set prefix><name>[level]" -> the buffer (nullptr for an unknown name)
 WsBuf* ws_find(rc_handle* h, const char* name) {
-  const char* colon = strchr(name, ':');
-  const std::string pre = colon ? std::string(name, colon + 1) : "", leaf = colon ? colon + 1 : name;
-  int set = 0;
-  while (set < WS_COUNT && pre != kWsPrefix[set]) ++set;
-  if (set == WS_COUNT) return nullptr;
-  WsSet& s = h->ws[set];
-  for (const WsName& e : wsn::kTable) {
-    const size_t k = strlen(e.name);
-    if (leaf.compare(0, k, e.name) != 0) continue;
-    WsBuf* b = nullptr;
-    if (leaf.size() == k) b = e.in(s, -1);
-    else if (leaf.size() == k + 1 && leaf[k] >= '0' && leaf[k] < '0' + h->cfg.num_levels - (e.ilv ? 1 : 0)) b = e.in(s, leaf[k] - '0');
-    if (b) return b;
-  }
-  return nullptr;
+  std::string leaf;
+  const int set = ws_split(name, leaf);
+  return set < 0 ? nullptr : ws_lookup(h->ws[set], leaf, h->cfg.num_levels);
 }
 
 // roctx ranges around the stages (tracing), for `rocprofv3 --marker-trace`.  The marker library is resolved at run

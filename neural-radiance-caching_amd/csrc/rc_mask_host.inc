@@ -4,8 +4,8 @@
 // One rc_mask_backward call = the training forward (enqueue_all's sampler levels on the workspace set WS_MASK, the
 // caller's jitter and anneal; rc_interlevel_backward's step 1: nothing behind the last level's density) ->
 // k_mask_loss_bwd (the last level's weights, the per-ray terms, d loss / d density) -> k_interlevel_reduce (the loss,
-// fixed order) -> with a gradient buffer, per chunk of kDataChunk samples: rc_density_backward of the last level at the
-// forward's own means.  rc_transient_mask_backward is the same body on a time-resolved handle, the gradient at the last
+// fixed order) -> with a gradient buffer: rc_density_backward of the last level at the forward's own means
+// (density_backward_chunks).  rc_transient_mask_backward is the same body on a time-resolved handle, the gradient at the last
 // level's offset of the one sampler buffer (DESIGN.md §4.15b).
 
 int rc_backward_mask_rays(rc_handle* h, const float* origins, const float* look, const float* u1, const float* u2, int64_t n,
@@ -89,17 +89,8 @@ int mask_backward_impl(rc_handle* h, const std::string& who, bool allow_transien
   RC_HIP(h, hipGetLastError());
   if (!density_grads) return RC_OK;
 
-  // 3. the density backward of the last level at the forward's sample means, in chunks of kDataChunk samples
-  if ((rc = ws_alloc(h, x.points, 3 * np))) return rc;
-  rc_launch_points_aos(w.means[NL - 1].p, np, x.points.p, st);
-  RC_HIP(h, hipGetLastError());
-  for (int64_t c0 = 0; c0 < np; c0 += kDataChunk) {
-    const int64_t C = np - c0 < kDataChunk ? np - c0 : kDataChunk;
-    if ((rc = rc_density_backward(h, NL - 1, x.points.p + 3 * c0, C, x.d_density.p + c0, nullptr, density_grads, nullptr, stream_v)))
-      return rc;
-  }
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
+  // 3. the density backward of the last level at the forward's sample means
+  return density_backward_chunks(h, NL - 1, w.means[NL - 1].p, np, x.points, x.d_density.p, nullptr, density_grads, st);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // Host side of the training backward of one level's density field (rc_train.hip); included by rc_api.hip before the other
 // training files.  Also what those files share: the gradient-buffer layouts (GradSeg, one builder per layout,
 // layout_segments, behind every rc_*_grad_size / rc_*_grad_layout and rc_load_params_flat), the dense layers on k_gemm
-// (dense_fwd, dense_dx, dense_wgrad) and on k_gemm_tile (dense_*_tile) and the body of the three grid-L2 regularizers.
+// (dense_fwd, dense_dx, dense_wgrad) and on k_gemm_tile (dense_*_tile), the body of the three grid-L2 regularizers and,
+// behind rc_density_backward, the chunked tail of the losses that end in it (density_backward_chunks).
 
 namespace {
 
@@ -499,6 +500,28 @@ int rc_density_backward(rc_handle* h, int32_t level, const float* points, int64_
   return RC_OK;
   RC_CATCH(h)
 }
+
+namespace {
+
+// The tail of a per-ray loss whose gradient reaches level `level` through d loss / d density alone (and d loss / d feature64
+// where d_feature is given): the forward's sample means (SoA [3][np]) copied into `points` as rows [np][3], then
+// rc_density_backward at them in chunks of kDataChunk samples.
+int density_backward_chunks(rc_handle* h, int level, const float* means_soa, int64_t np, WsBuf& points, const float* d_density,
+                            const float* d_feature, float* grads, hipStream_t st) {
+  if (int rc = ws_alloc(h, points, 3 * np)) return rc;
+  rc_launch_points_aos(means_soa, np, points.p, st);
+  RC_HIP(h, hipGetLastError());
+  for (int64_t c0 = 0; c0 < np; c0 += kDataChunk) {
+    const int64_t C = np - c0 < kDataChunk ? np - c0 : kDataChunk;
+    if (int rc = rc_density_backward(h, level, points.p + 3 * c0, C, d_density + c0, d_feature ? d_feature + 64 * c0 : nullptr, grads,
+                                     nullptr, st))
+      return rc;
+  }
+  RC_HIP(h, hipGetLastError());
+  return RC_OK;
+}
+
+}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
 // rc_hashgrid_backward: the transpose of rc_hashgrid_lookup for any of the handle's grids

@@ -200,7 +200,9 @@ int rc_transient_data_backward_kind(rc_handle* h, const rc_rays* rays, const flo
 
 // rc_transient_data_backward_kind, then the weights path of its gradient into the last level's segments of the sampler
 // layout: k_transient_weights_bwd ("td:d_weights" -> "td:d_density" on the forward's density, tdist and weights of set 0)
-// and rc_density_backward of the last level at the forward's means, in chunks of kDataChunk samples.
+// and rc_density_backward of the last level at the forward's means (density_backward_chunks).
+// The launch order is the one it always had; "td:points" is requested inside density_backward_chunks, behind the launch of
+// k_transient_weights_bwd (a buffer that has to grow is reallocated there, as in the mask loss).
 int rc_transient_data_backward_sampler(rc_handle* h, const rc_rays* rays, const float* cam_origins, int64_t n, const rc_randoms* rnd,
                                        const float* gt, const float* rgb_nocorr, const float* gt_nocorr, const float* lossmult,
                                        const rc_transient_data_loss_kind* cfg, float* head_grads, float* sampler_grads,
@@ -223,7 +225,7 @@ int rc_transient_data_backward_sampler(rc_handle* h, const rc_rays* rays, const 
   WsUse use_d(h, WS_TRANSDATA, st);
   if ((rc = use_d.rc)) return rc;
   TransDataWs& y = ws_extra<TransDataWs>(use_d.s);
-  if ((rc = ws_alloc(h, {{y.d_density, np}, {y.points, 3 * np}}))) return rc;
+  if ((rc = ws_alloc(h, y.d_density, np))) return rc;
   WsUse use(h, WS_RENDER0, st);          // the forward's buffers, as step 3 of the shared body reads them
   if ((rc = use.rc)) return rc;
   RenderWs& w = use.s.r;
@@ -231,16 +233,7 @@ int rc_transient_data_backward_sampler(rc_handle* h, const rc_rays* rays, const 
   a.n = n; a.S = S2; a.d_weights = y.d_weights.p; a.weights = w.weights[NL - 1].p; a.density = w.density[NL - 1].p;
   a.tdist = w.tdist[NL - 1].p; a.directions = rays->directions; a.d_density = y.d_density.p;
   rc_launch_transient_weights_bwd(a, st);
-  rc_launch_points_aos(w.means[NL - 1].p, np, y.points.p, st);
-  RC_HIP(h, hipGetLastError());
-  for (int64_t c0 = 0; c0 < np; c0 += kDataChunk) {
-    const int64_t C = np - c0 < kDataChunk ? np - c0 : kDataChunk;
-    if ((rc = rc_density_backward(h, NL - 1, y.points.p + 3 * c0, C, y.d_density.p + c0, nullptr, sampler_grads + off[NL - 1], nullptr,
-                                  stream_v)))
-      return rc;
-  }
-  RC_HIP(h, hipGetLastError());
-  return RC_OK;
+  return density_backward_chunks(h, NL - 1, w.means[NL - 1].p, np, y.points, y.d_density.p, nullptr, sampler_grads + off[NL - 1], st);
   RC_CATCH(h)
 }
 

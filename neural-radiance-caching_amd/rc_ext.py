@@ -982,6 +982,88 @@ class RadianceCache:
         held["lossmult"] = lm
         return lm
 
+    def _cache_loss_head(self, rays, jitters, lossmult):
+        """What every per-ray cache loss marshals first: (rc_rays, the tensors kept alive, n, rc_randoms of the per-level
+        jitters or None, lossmult [n] or None)."""
+        r, held, n = self._rays_struct(rays)
+        return r, held, n, self._jitter_struct(jitters, held, n), self._lossmult(lossmult, held, n)
+
+    @staticmethod
+    def _terms_struct(ctype, what, defaults, terms):
+        """The ctypes struct of a loss's `terms` dict laid over `defaults`; a key that is no field of the struct is refused."""
+        t = dict(defaults)
+        t.update(terms or {})
+        unknown = set(t) - {k for k, _ in ctype._fields_}
+        if unknown:
+            raise ValueError(f"unknown {what} fields {sorted(unknown)}")
+        return ctype(**{k: float(t[k]) if typ is C.c_float else int(bool(t[k])) for k, typ in ctype._fields_ if k in t})
+
+    def _interlevel(self, transient, rays, jitters, anneal, mults, blurs, lossmult, grads, levels=None):
+        """interlevel_backward (grads: per proposal level a flat or None, `levels` those whose backward runs) and
+        transient_interlevel_backward (grads: the one sampler flat, None or False)."""
+        r, held, n = self._rays_struct(rays)
+        nprop = self.cfg.num_levels - 1
+        if len(mults) != nprop or len(blurs) != nprop:
+            raise ValueError(f"mults and blurs need {nprop} values")
+        rnd_p = self._jitter_struct(jitters, held, n)
+        lm = self._lossmult(lossmult, held, n)
+        if transient:
+            fn = self.lib.rc_transient_interlevel_backward
+            flats, losses, stream = self._loss_prologue("transient_sampler", grads, slots=max(nprop, 1))
+            where = _ptr(flats)
+        else:
+            fn = self.lib.rc_interlevel_backward
+            levels = tuple(range(nprop)) if levels is None else tuple(levels)
+            flats = list(grads) if grads is not None else [None] * nprop
+            where = (C.c_void_p * nprop)()
+            for l in range(nprop):
+                if l not in levels:
+                    flats[l] = None
+                    continue
+                flats[l] = self._grad_buffer(flats[l], self._grad_size(l), f"grads[{l}]")
+                where[l] = flats[l].data_ptr()
+            _, losses, stream = self._loss_prologue(None, False, slots=max(nprop, 1))
+        m = (C.c_float * nprop)(*[float(v) for v in mults])
+        b = (C.c_float * nprop)(*[float(v) for v in blurs])
+        self._check(fn(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), m, b, where, losses.data_ptr(), stream))
+        self._keep = [held]
+        return flats, losses
+
+    def _geometry(self, transient, rays, jitters, anneal, lossmult, terms, grads):
+        """geometry_backward (grads: (density flat, shader flat), None or False) and transient_geometry_backward (grads: the
+        one sampler flat, None or False)."""
+        r, held, n, rnd_p, lm = self._cache_loss_head(rays, jitters, lossmult)
+        cfg = self._terms_struct(rc_geometry_loss, "geometry loss", {"distortion_p": -0.25, "distortion_premult": 1e4}, terms)
+        if transient:
+            fn = self.lib.rc_transient_geometry_backward
+            flats, losses, stream = self._loss_prologue("transient_sampler", grads, slots=4)
+            where = (_ptr(flats),)
+        else:
+            fn = self.lib.rc_geometry_backward
+            flats, losses, stream = self._loss_prologue_pair(grads, slots=4)
+            where, flats = (_ptr(flats[0]), _ptr(flats[1])), (flats[0], flats[1])
+        self._check(fn(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg), *where, losses.data_ptr(), stream))
+        self._keep = [held]
+        return flats, losses
+
+    def _mask(self, transient, rays, jitters, anneal, masks, lossmult, terms, grads):
+        """mask_backward (grads: the last level's density flat) and transient_mask_backward (grads: the sampler flat)."""
+        r, held, n, rnd_p, lm = self._cache_loss_head(rays, jitters, lossmult)
+        mk = None
+        if masks is not None:
+            mk = self._dev(masks).reshape(-1)
+            if mk.shape[0] != n:
+                raise ValueError("masks must have one value per ray")
+            held["masks"] = mk
+        cfg = self._terms_struct(rc_mask_loss, "mask loss", {"charb_padding": 1e-3, "weight_opaque": 1.0, "weight_empty": 1.0,
+                                                             "zero_masks": 0}, terms)
+        fn = self.lib.rc_transient_mask_backward if transient else self.lib.rc_mask_backward
+        flat, loss, stream = self._loss_prologue("transient_sampler" if transient else self.cfg.num_levels - 1, grads)
+        self._check(fn(self._h, C.byref(r), _ptr(mk), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg), _ptr(flat), loss.data_ptr(),
+                       stream))
+        self._keep = [held]
+        return flat, loss
+
     def density_grad_layout(self, level: int):
         """rc_density_grad_layout: [(tensor name, offset, shape)] of the gradient buffer of proposal level `level`
         (the reference's parameter-tree names), and its total size in floats."""
@@ -1042,28 +1124,7 @@ class RadianceCache:
         (density_grad_layout(level)), accumulated into; a missing one is allocated zeroed.  levels: the proposal levels
         whose backward runs (default all); the others get no gradient (None in the result).
         Returns (flat buffers, losses [num_levels - 1] cuda tensor)."""
-        r, held, n = self._rays_struct(rays)
-        nprop = self.cfg.num_levels - 1
-        levels = tuple(range(nprop)) if levels is None else tuple(levels)
-        if len(mults) != nprop or len(blurs) != nprop:
-            raise ValueError(f"mults and blurs need {nprop} values")
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
-        flats = list(grads) if grads is not None else [None] * nprop
-        ptrs = (C.c_void_p * nprop)()
-        for l in range(nprop):
-            if l not in levels:
-                flats[l] = None
-                continue
-            flats[l] = self._grad_buffer(flats[l], self._grad_size(l), f"grads[{l}]")
-            ptrs[l] = flats[l].data_ptr()
-        _, losses, stream = self._loss_prologue(None, False, slots=max(nprop, 1))
-        m = (C.c_float * nprop)(*[float(v) for v in mults])
-        b = (C.c_float * nprop)(*[float(v) for v in blurs])
-        self._check(self.lib.rc_interlevel_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), m, b, ptrs,
-                                                    losses.data_ptr(), stream))
-        self._keep = [held]
-        return flats, losses
+        return self._interlevel(False, rays, jitters, anneal, mults, blurs, lossmult, grads, levels)
 
     def data_backward(self, rays: Dict[str, object], rgb, jitters=None, anneal: float = 0.4, lossmult=None,
                       charb_padding: float = 1e-3, mult: float = 1.0, grads=None):
@@ -1095,20 +1156,7 @@ class RadianceCache:
         -0.25 / 1e4).  jitters / anneal / lossmult as data_backward.  grads: (density flat, shader flat) to accumulate
         into, either None (allocated zeroed); grads=False computes the losses only.
         Returns ((density flat, shader flat), losses [4] cuda tensor); one copy of each term."""
-        r, held, n = self._rays_struct(rays)
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
-        t = {"distortion_p": -0.25, "distortion_premult": 1e4}
-        t.update(terms or {})
-        unknown = set(t) - {k for k, _ in rc_geometry_loss._fields_}
-        if unknown:
-            raise ValueError(f"unknown geometry loss fields {sorted(unknown)}")
-        cfg = rc_geometry_loss(**{k: float(v) for k, v in t.items()})
-        flats, losses, stream = self._loss_prologue_pair(grads, slots=4)
-        self._check(self.lib.rc_geometry_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg),
-                                                  _ptr(flats[0]), _ptr(flats[1]), losses.data_ptr(), stream))
-        self._keep = [held]
-        return (flats[0], flats[1]), losses
+        return self._geometry(False, rays, jitters, anneal, lossmult, terms, grads)
 
     def density_regularizer(self, level: int, mult: float, grad=None):
         """rc_density_regularizer: mult * sum over the tables of density grid `level` of 0.5 * mean(x^2)
@@ -1145,20 +1193,14 @@ class RadianceCache:
         applied; noise defaults to 0.1, weight_normals to 0.001, the other two weights to 0).  jitters / anneal /
         lossmult as data_backward.  grads: the density flat to accumulate into, None (allocated zeroed) or False (the
         loss only).  Returns (density flat or None, loss [1] cuda tensor); one copy of the term."""
-        r, held, n = self._rays_struct(rays)
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
+        r, held, n, rnd_p, lm = self._cache_loss_head(rays, jitters, lossmult)
         S = self.cfg.sampling_strategy[-1][2]
         nz = self._dev(noise).reshape(-1).contiguous()
         if nz.shape[0] != n * S * 3:
             raise ValueError(f"noise must be [n, {S}, 3]")
         held["noise"] = nz
-        t = {"noise": 0.1, "weight_normals": 0.001, "weight_normals_pred": 0.0, "weight_density": 0.0}
-        t.update(terms or {})
-        unknown = set(t) - {k for k, _ in rc_geometry_smoothness._fields_}
-        if unknown:
-            raise ValueError(f"unknown geometry smoothness fields {sorted(unknown)}")
-        cfg = rc_geometry_smoothness(**{k: float(v) for k, v in t.items()})
+        cfg = self._terms_struct(rc_geometry_smoothness, "geometry smoothness",
+                                 {"noise": 0.1, "weight_normals": 0.001, "weight_normals_pred": 0.0, "weight_density": 0.0}, terms)
         flat, loss, stream = self._loss_prologue(self.cfg.num_levels - 1, grads)
         self._check(self.lib.rc_geometry_smoothness_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal),
                                                              _ptr(nz), C.byref(cfg), _ptr(flat), loss.data_ptr(), stream))
@@ -1198,26 +1240,7 @@ class RadianceCache:
         weights to 1, zero_masks to 0).  jitters / anneal / lossmult as data_backward.  grads: the density flat to
         accumulate into, None (allocated zeroed) or False (the loss only).
         Returns (density flat or None, loss [1] cuda tensor); one copy of the term."""
-        r, held, n = self._rays_struct(rays)
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
-        mk = None
-        if masks is not None:
-            mk = self._dev(masks).reshape(-1)
-            if mk.shape[0] != n:
-                raise ValueError("masks must have one value per ray")
-            held["masks"] = mk
-        t = {"charb_padding": 1e-3, "weight_opaque": 1.0, "weight_empty": 1.0, "zero_masks": 0}
-        t.update(terms or {})
-        unknown = set(t) - {k for k, _ in rc_mask_loss._fields_}
-        if unknown:
-            raise ValueError(f"unknown mask loss fields {sorted(unknown)}")
-        cfg = rc_mask_loss(float(t["charb_padding"]), float(t["weight_opaque"]), float(t["weight_empty"]), int(bool(t["zero_masks"])))
-        flat, loss, stream = self._loss_prologue(self.cfg.num_levels - 1, grads)
-        self._check(self.lib.rc_mask_backward(self._h, C.byref(r), _ptr(mk), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg),
-                                              _ptr(flat), loss.data_ptr(), stream))
-        self._keep = [held]
-        return flat, loss
+        return self._mask(False, rays, jitters, anneal, masks, lossmult, terms, grads)
 
     def light_grad_layout(self):
         """rc_light_grad_layout: [(tensor name, offset, shape)] of the LightSampler gradient buffer (the light_grid tables,
@@ -1658,19 +1681,7 @@ class RadianceCache:
         """rc_transient_interlevel_backward: interlevel_backward on a time-resolved handle (its own sampler's forward).
         grad: the flat buffer of transient_sampler_grad_layout to accumulate into (allocated zeroed when None; False: the
         losses only).  Returns (sampler flat or None, losses [num_levels - 1] cuda tensor)."""
-        r, held, n = self._rays_struct(rays)
-        nprop = self.cfg.num_levels - 1
-        if len(mults) != nprop or len(blurs) != nprop:
-            raise ValueError(f"mults and blurs need {nprop} values")
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
-        flat, losses, stream = self._loss_prologue("transient_sampler", grad, slots=max(nprop, 1))
-        m = (C.c_float * nprop)(*[float(v) for v in mults])
-        b = (C.c_float * nprop)(*[float(v) for v in blurs])
-        self._check(self.lib.rc_transient_interlevel_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), m, b,
-                                                              _ptr(flat), losses.data_ptr(), stream))
-        self._keep = [held]
-        return flat, losses
+        return self._interlevel(True, rays, jitters, anneal, mults, blurs, lossmult, grad)
 
     def transient_geometry_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, lossmult=None, terms=None,
                                     grad=None):
@@ -1678,46 +1689,14 @@ class RadianceCache:
         last level's segments of the sampler flat, pred_normals_layer's to its tail.  terms as geometry_backward (the
         distortion curve defaults to the gins' -0.25 / 1e4).  grad as transient_interlevel_backward.
         Returns (sampler flat or None, losses [4] cuda tensor)."""
-        r, held, n = self._rays_struct(rays)
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
-        t = {"distortion_p": -0.25, "distortion_premult": 1e4}
-        t.update(terms or {})
-        unknown = set(t) - {k for k, _ in rc_geometry_loss._fields_}
-        if unknown:
-            raise ValueError(f"unknown geometry loss fields {sorted(unknown)}")
-        cfg = rc_geometry_loss(**{k: float(v) for k, v in t.items()})
-        flat, losses, stream = self._loss_prologue("transient_sampler", grad, slots=4)
-        self._check(self.lib.rc_transient_geometry_backward(self._h, C.byref(r), _ptr(lm), n, rnd_p, float(anneal), C.byref(cfg),
-                                                            _ptr(flat), losses.data_ptr(), stream))
-        self._keep = [held]
-        return flat, losses
+        return self._geometry(True, rays, jitters, anneal, lossmult, terms, grad)
 
     def transient_mask_backward(self, rays: Dict[str, object], jitters=None, anneal: float = 0.4, masks=None, lossmult=None,
                                 terms=None, grad=None):
         """rc_transient_mask_backward: mask_backward on a time-resolved handle (rays of backward_mask_rays included); the
         gradient goes to the last level's segments of the sampler flat.  grad as transient_interlevel_backward.
         Returns (sampler flat or None, loss [1] cuda tensor)."""
-        r, held, n = self._rays_struct(rays)
-        rnd_p = self._jitter_struct(jitters, held, n)
-        lm = self._lossmult(lossmult, held, n)
-        mk = None
-        if masks is not None:
-            mk = self._dev(masks).reshape(-1)
-            if mk.shape[0] != n:
-                raise ValueError("masks must have one value per ray")
-            held["masks"] = mk
-        t = {"charb_padding": 1e-3, "weight_opaque": 1.0, "weight_empty": 1.0, "zero_masks": 0}
-        t.update(terms or {})
-        unknown = set(t) - {k for k, _ in rc_mask_loss._fields_}
-        if unknown:
-            raise ValueError(f"unknown mask loss fields {sorted(unknown)}")
-        cfg = rc_mask_loss(float(t["charb_padding"]), float(t["weight_opaque"]), float(t["weight_empty"]), int(bool(t["zero_masks"])))
-        flat, loss, stream = self._loss_prologue("transient_sampler", grad)
-        self._check(self.lib.rc_transient_mask_backward(self._h, C.byref(r), _ptr(mk), _ptr(lm), n, rnd_p, float(anneal),
-                                                        C.byref(cfg), _ptr(flat), loss.data_ptr(), stream))
-        self._keep = [held]
-        return flat, loss
+        return self._mask(True, rays, jitters, anneal, masks, lossmult, terms, grad)
 
     def transient_density_regularizer(self, level: int, mult: float, grad=None):
         """rc_transient_density_regularizer: density_regularizer of grid `level` on a time-resolved handle, the gradient

@@ -267,3 +267,114 @@ def test_ide_table_matches_the_oracle(hostcheck):
     assert np.allclose(sigma, 0.5 * l * (l + 1))
     assert np.allclose(coef[:, : mat.shape[0]], mat.T.astype(np.float32), rtol=1e-6, atol=0)
     assert not coef[:, mat.shape[0]:].any()
+
+
+# ---- the workspace registry (csrc/rc_ws.h) ---------------------------------------------------------------------------
+# The table as it stood before the registry moved into its own header: the 21 structs in the order of the set's variant
+# (RenderWs first: every set has one), the prefix of the set that holds each, and their buffers.  "name#" is a per-level
+# buffer ("name0" ..).
+WS_STRUCTS = [
+    ("RenderWs", "", "sdist# tdist# means# feat# density# weights# hbuf normals_pred normals_grad jac app shade debug env_rgb "
+                     "rgb_noenv acc_ws inds src_idx filt_weight acc_sel feat_sel hbuf_sel normals_sel density_sel t_irr t_slf tshade"),
+    ("ExtraWs", "", "m_pts m_nrm m_feat m_mat m_feat_all m_mat_all l_feat l_vmf l_vmf_logit sec_origins sec_dirs sec_near sec_far "
+                    "sec_lights sec_samples m_local_view sec_rgb sec_acc sec_env sh_origins sh_dirs sh_near sh_far sh_normals "
+                    "sh_lights sh_acc"),
+    ("TrainWs", "t:", "feat dfeat a1 a2 d1 d2 fe graw density partial"),
+    ("InterlevelWs", "i:", "d_density# points# loss_ray"),
+    ("DataWs", "d:", "rgb loss_ray d_density d_rgbs points f96 heads p3 ib_in x328 s0 s1 sb i1 i2 io so dheads dio dso dsb dx328 "
+                     "ds1 ds0 di2 di1 dib_in db128 dp3 df96 dfeat dapp part ones"),
+    ("GeometryWs", "g:", "loss_ray d_density d_pred points h64 dfeat part ones reg_part"),
+    ("OptimWs", "o:", "part norm mult stage"),
+    ("LightWs", "ls:", "cache_rgb cache_acc h0 h1 vp dvp dh1 dh0 dfeat loss_ray part ones reg_part"),
+    ("MaterialWs", "ms:", "cache_rgb cache_acc pts feat mat_p loss_ray loss_part dfeat part reg_part"),
+    ("MatDataWs", "md:", "cache_rgb cache_acc rgb loss_ray dmat dfeat part loss_part d_env e_h0 e_h1 e_xb e_hb e_raw e_draw e_dhb "
+                         "e_dxb e_dh1 e_dh0 e_part e_ones"),
+    ("TransDataWs", "td:", "rgb G Gt loss_ray dz_irr dz_slf x_irr x_slf part ones d_t_irr d_t_slf d_tint_ibrdf d_direct d_weights "
+                           "d_density points"),
+    ("EvalWs", "ev:", "binsum_pred binsum_gt post_pred post_gt part si_metric si_state si_part"),
+    ("AlbedoWs", "ea:", "pairs wg state part"),
+    ("VisWs", "vz:", "state part maxpart binsum"),
+    ("MaskWs", "mk:", "loss_ray d_density points"),
+    ("RelightWs", "rl:", "part best"),
+    ("NormalsWs", "nb:", "feat jac gf ghat u t0 a0 t1 a2 ones partial normals"),
+    ("GSmoothWs", "gs:", "means_p feat_p jac_p density_p normals_p points points_p d_normals d_normals_p d_density d_density_p "
+                         "loss_ray"),
+    ("QueryWs", "q:", "means feat jac density normals_pred normals_grad m_feat"),
+    ("IsoWs", "iso:", "mask tcount tile_v tile_t group_v group_t group_off vbase state"),
+    ("AtlasWs", "atlas:", "points owner hidden app_feat"),
+]
+WS_BARE_PREFIXES = ("p1:", "p2:", "p3:", "s:")          # WS_RENDER1-3 and WS_SECONDARY: a RenderWs and nothing else
+WS_MAX_LEVELS = 3                                      # RC_MAX_LEVELS
+WS_PROBES = ("bogus:feat", "x:hbuf", "zz", "i:nothing", "hbuf9", "hbuf0", "sdist", "sdist3", "i:points", "i:d_density2", "d:f97",
+             "T:feat", "atlas", ":hbuf", "q:", "td:g")
+
+
+def _ws_fields(k):
+    """{leaf: per-level?} of struct k of WS_STRUCTS"""
+    return {f.rstrip("#"): f.endswith("#") for f in WS_STRUCTS[k][2].split()}
+
+
+def _ws_expected(kind, leaf, digit, num_levels):
+    """(struct index, field, level) that "<leaf><digit>" reaches in a set holding struct `kind` (0: none beside its RenderWs),
+    or None: RenderWs first, then the held struct; a per-level buffer takes the digits 0 .. num_levels - 1, InterlevelWs' only
+    0 .. num_levels - 2, any other buffer no digit."""
+    for k in ([0, kind] if kind else [0]):
+        per_level = _ws_fields(k).get(leaf)
+        if per_level is None:
+            continue
+        if not per_level and digit is None:
+            return k, leaf, -1
+        if per_level and digit is not None and digit < num_levels - (1 if WS_STRUCTS[k][0] == "InterlevelWs" else 0):
+            return k, leaf, digit
+    return None
+
+
+@pytest.mark.parametrize("num_levels", [3, 2])
+def test_workspace_registry_resolves_the_table(num_levels):
+    """`hostcheck --ws`: every set holds the struct of its kind and is asked for every name of the whole table under its own
+    prefix, bare and with the digits 0 .. RC_MAX_LEVELS.  What resolves, and to which buffer, is what the literal table
+    above and the lookup rule say; nothing else resolves; the sanitizers report nothing."""
+    r = subprocess.run(["make", "-C", CSRC, "hostcheck"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([os.path.join(CSRC, "hostcheck"), "--ws", str(num_levels), *WS_PROBES], capture_output=True, text=True, env=env)
+    assert r.returncode == 0 and r.stdout.endswith("hostcheck ws ok\n") and not r.stderr, r.stdout[-2000:] + r.stderr
+    lines = r.stdout.splitlines()
+    hits = {}
+    for ln in lines:
+        if ln.startswith("hit "):
+            _, full, kind, field, level, off = ln.split()
+            assert hits.setdefault(full, (int(kind), field, int(level), int(off))) == (int(kind), field, int(level), int(off))
+    assert len(WS_STRUCTS) == 21 and len({s[0] for s in WS_STRUCTS}) == 21
+    sets = [(prefix, k) for k, (_, prefix, _) in enumerate(WS_STRUCTS) if k] + [(p, 0) for p in WS_BARE_PREFIXES]
+    assert len({p for p, _ in sets}) == 24
+    leaves = sorted({leaf for k in range(len(WS_STRUCTS)) for leaf in _ws_fields(k)})
+    want, lookups = {}, 0
+    for prefix, kind in sets:
+        for leaf in leaves:
+            for digit in [None] + list(range(WS_MAX_LEVELS + 1)):
+                e = _ws_expected(kind, leaf, digit, num_levels)
+                if e is not None:
+                    want[prefix + leaf + ("" if digit is None else str(digit))] = e
+    assert {k: v[:3] for k, v in hits.items()} == want
+    # the program asked for every row of the table, 5 spellings each, in each of the 24 sets, then for the probes
+    rows = sum(len(_ws_fields(k)) for k in range(len(WS_STRUCTS)))
+    assert lines[-2].split() == ["lookups", str(24 * rows * (WS_MAX_LEVELS + 2) + len(WS_PROBES)), "buffers",
+                                 str(sum((WS_MAX_LEVELS if lv else 1) for p, k in sets for kk in {0, k} for lv in _ws_fields(kk).values()))]
+    # every name of a struct resolves under its set's prefix (a name RenderWs has too reaches RenderWs), to distinct buffers
+    for prefix, kind in sets:
+        for k in {0, kind}:
+            offs = []
+            for leaf, per_level in _ws_fields(k).items():
+                top = num_levels - (1 if WS_STRUCTS[k][0] == "InterlevelWs" else 0)
+                for name in ([f"{leaf}{d}" for d in range(top)] if per_level else [leaf]):
+                    got = hits[prefix + name]
+                    assert got[0] in (0, k) and got[1] == leaf, (prefix, name, got)
+                    if got[0] == k:
+                        offs.append(got[3])
+            assert len(set(offs)) == len(offs), (prefix, k)
+    probes = {ln.split()[1]: ln.split()[2:] for ln in lines if ln.startswith("probe ")}
+    assert set(probes) == set(WS_PROBES)
+    for name, (set_id, off) in probes.items():
+        assert off == "-", name
+        assert (set_id == "-1") == (":" in name and name.split(":")[0] + ":" not in {p for p, _ in sets}), name
