@@ -494,10 +494,51 @@ int ensure_side_stream(rc_handle* h) {
 
 int repack_transient(rc_handle* h);
 
+// What the fused streams (packs.fused, packs.fused_front) are put together from.  They are packed on their own: where the
+// one-wave kernel reads its output rows as tables (rc_pack_host.h kRcFusedRows) the five output blocks take pack_dot_rows
+// and the offsets of FusedDens / FusedShader; every other stream of the library keeps pack_dot's fragments.
+struct FusedParts {
+  std::vector<float> head[3], tail[3];       // a density MLP's layers in front of its output block, and behind it (backward fragments)
+  std::vector<Col> rows[3];                  // its output rows
+  std::vector<float> sh_head, sh_trunk;      // the shader's layers in front of the IBRDF's output block, and between the two blocks
+  std::vector<Col> io, so;                   // the two output blocks of the shader
+};
+// `v` at fragment `at` of the stream; a gap in front of it (at most max_gap fragments: the padding to a piece or of a row
+// table, rc_rows_at) is zeros
+bool put_at(std::vector<float>& stream, int at, const std::vector<float>& v, int max_gap) {
+  const int have = (int)(stream.size() / 64);
+  if (stream.size() % 64 != 0 || have > at || at - have > max_gap) return false;
+  stream.resize((size_t)at * 64, 0.0f);
+  append(stream, v);
+  return true;
+}
+std::vector<float> fused_dot(const std::vector<Col>& outs, int ntiles, bool pad_to_piece) {
+  return kRcFusedRows ? pack_dot_rows(outs, ntiles, pad_to_piece) : pack_dot(outs, ntiles, pad_to_piece);
+}
+// [density MLP 0 | 1 | 2 (+ backward)] up to F_SH, then (with_shader) the shader: false if a part misses its offset
+bool build_fused_stream(const FusedParts& P, bool with_shader, std::vector<float>& stream) {
+  using namespace rcfused;
+  const int row_gap = kRcFusedRows ? kRcChunkFrags - 1 : 0;
+  bool ok = true;
+  auto level = [&](int l, int fb, int d_o, int b1) {
+    ok = ok && put_at(stream, fb, P.head[l], 0) && put_at(stream, fb + d_o, fused_dot(P.rows[l], 2, false), row_gap) &&
+         put_at(stream, fb + b1, P.tail[l], 0);
+  };
+  level(0, F_L0, FusedDens<4, F_L0>::DO, FusedDens<4, F_L0>::B1);
+  level(1, F_L1, FusedDens<5, F_L1>::DO, FusedDens<5, F_L1>::B1);
+  level(2, F_L2, FusedDens<17, F_L2>::DO, FusedDens<17, F_L2>::B1);
+  ok = ok && put_at(stream, F_SH, {}, 3);                    // split layers start on a whole piece
+  if (!with_shader) return ok;
+  using SF = FusedShader;
+  ok = ok && put_at(stream, F_SH + SF::F_H, P.sh_head, 0) && put_at(stream, F_SH + SF::F_IO, fused_dot(P.io, 2, kRcSplit), row_gap) &&
+       put_at(stream, F_SH + SF::F_S1, P.sh_trunk, 0) && put_at(stream, F_SH + SF::F_SO, fused_dot(P.so, 4, kRcSplit), row_gap);
+  return ok && (int)(stream.size() / 64) == NF_FUSED;
+}
+
 int repack(rc_handle* h) {
   std::string missing;
   const rc_config& c = h->cfg;
-  std::vector<float> fused_parts[4];
+  FusedParts fused_parts;
   if (!h->ide_table.p) {      // directional-encoding coefficients of the cache shaders (both kinds of handle)
     RcIdeTable tb;
     build_ide_table(tb);
@@ -526,7 +567,9 @@ int repack(rc_handle* h) {
     append(stream, pack_f32(s, {tile_full(d1, 0), tile_full(d1, 1)}));
     std::vector<Col> regs = {Col{dout, 0}};
     if (dn) { regs.push_back(Col{dn, 0}); regs.push_back(Col{dn, 1}); regs.push_back(Col{dn, 2}); }
+    if (l < 3) { fused_parts.head[l] = stream; fused_parts.rows[l] = regs; }
     append(stream, pack_dot(regs, 2, false));
+    const size_t tail_at = stream.size();
     if (dn) {
       // backward fragments for the analytic normals (last level): W1^T, W0^T (w_out is kept from the forward dot)
       HostLayer w1t, w0t;
@@ -538,7 +581,7 @@ int repack(rc_handle* h) {
       append(stream, pack_f32(sb, {tile_full(&w1t, 0, 0, false), tile_full(&w1t, 1, 0, false)}));
       append(stream, pack_f32(sb, {tile_full(&w0t, 0, 0, false)}));
     }
-    if (l < 3) fused_parts[l] = stream;
+    if (l < 3) fused_parts.tail[l].assign(stream.begin() + tail_at, stream.end());
     int rc = upload(h, h->packs.dens[l], pad_stream(stream));
     if (rc) return rc;
   }
@@ -546,14 +589,8 @@ int repack(rc_handle* h) {
     // front end of the time-resolved cache through the fused kernel's FRONT variant: [dens 0 | dens 1 | dens 2 (+ bwd)]
     int off[4];
     rc_fused_stream_offsets(&off[0], &off[1], &off[2], &off[3]);
-    bool ok = fused_geometry_ok(h);
     std::vector<float> stream;
-    for (int p = 0; p < 3 && ok; ++p) {
-      ok = (int)(stream.size() / 64) == off[p];
-      append(stream, fused_parts[p]);
-    }
-    if (ok && (int)(stream.size() / 64) < off[3] && off[3] - (int)(stream.size() / 64) < 4) stream.resize((size_t)off[3] * 64, 0.0f);
-    ok = ok && (int)(stream.size() / 64) == off[3];
+    const bool ok = fused_geometry_ok(h) && off[3] == rcfused::F_SH && build_fused_stream(fused_parts, false, stream);
     h->fused_front_ok = ok;
     if (ok) {
       int rc = upload(h, h->packs.fused_front, pad_stream(stream));
@@ -605,7 +642,10 @@ int repack(rc_handle* h) {
     append(stream, pack(s, {tile_full(&i0f, 0), tile_full(&i0f, 1)}));
     s.clear(); steps_acc(s, 2, 0); step_bias(s);
     append(stream, pack(s, {tile_full(i1, 0), tile_full(i1, 1)}));
-    append(stream, pack_dot({Col{io, 0}}, 2));
+    fused_parts.sh_head = stream;
+    fused_parts.io = {Col{io, 0}};
+    append(stream, pack_dot(fused_parts.io, 2));
+    const size_t trunk_at = stream.size();
     // SLF trunk
     s.clear(); steps_acc(s, 4, 0); step_bias(s);
     append(stream, pack(s, {tile_full(l1, 0), tile_full(l1, 1), tile_full(l1, 2), tile_full(l1, 3)}));
@@ -613,8 +653,9 @@ int repack(rc_handle* h) {
     std::vector<Step> sb; steps_acc(sb, 4, 0);
     append(stream, pack(sb, {tile_full(lb, 0, 0, false), tile_full(lb, 1, 0, false), tile_full(lb, 2, 0, false),
                              tile_full(lb, 3, 0, false)}));
-    append(stream, pack_dot({Col{la, 0}, Col{la, 1}, Col{la, 2}}, 4));
-    fused_parts[3] = stream;
+    fused_parts.sh_trunk.assign(stream.begin() + trunk_at, stream.end());
+    fused_parts.so = {Col{la, 0}, Col{la, 1}, Col{la, 2}};
+    append(stream, pack_dot(fused_parts.so, 4));
     int rc = upload(h, h->packs.shader, pad_stream(stream));
     if (rc) return rc;
   }
@@ -623,14 +664,8 @@ int repack(rc_handle* h) {
     // hotdog layout only (3 levels of 64/64/32 samples, 6/7/32 density features, 32 appearance features)
     int off[4];
     const int nf = rc_fused_stream_offsets(&off[0], &off[1], &off[2], &off[3]);
-    bool ok = fused_geometry_ok(h);
     std::vector<float> stream;
-    for (int p = 0; p < 4 && ok; ++p) {
-      if (p == 3 && (int)(stream.size() / 64) < off[p] && off[p] - (int)(stream.size() / 64) < 4) stream.resize((size_t)off[p] * 64, 0.0f);   // split layers start on a whole piece (F_SH)
-      ok = (int)(stream.size() / 64) == off[p];
-      append(stream, fused_parts[p]);
-    }
-    ok = ok && (int)(stream.size() / 64) == nf;
+    const bool ok = fused_geometry_ok(h) && nf == rcfused::NF_FUSED && build_fused_stream(fused_parts, true, stream);
     h->fused_ok = ok;
     if (ok) {
       int rc = upload(h, h->packs.fused, pad_stream(stream));

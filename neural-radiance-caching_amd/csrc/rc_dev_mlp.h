@@ -578,6 +578,68 @@ __device__ __forceinline__ void dot_out1(const WS& w, const f32x16 (&hid)[NT], f
   dot_out<1, NT, NO, FBASE, NF, KEEP, W, NOB, CH, WS>(w, h1, o1, keep);
 }
 
+// dot_out on a block packed as a row table (rc_pack_host.h pack_dot_rows: [half-wave][output][tile][register], then the
+// biases; NOB outputs, fragments [FBASE, FBASE + rc_rfr(NOB, NT))).  A lane reads the row of ITS half-wave, four registers
+// per ds_read_b128: lanes 0-31 share one address and lanes 32-63 another, a broadcast of each.  The values are the ones
+// dot_out's fragments hold on the lane and every FMA, partial sum and add is dot_out's, in its order: same bits.
+// The block lies in ONE chunk of the ring (rc_rows_at), so the only seam it can meet is in front of its first fragment --
+// the same ws_advance, at a compile-time place, as any other read of the stream.
+template <int PT, int NT, int NO, int FBASE, int NF, bool KEEP = false, int W = kWaves, int NOB = NO, int CH = kChunk, class WS = WStream>
+__device__ __forceinline__ void dot_rows(const WS& w, const f32x16 (&hid)[PT][NT], float (&out)[PT][NO],
+                                         float (&keep)[KEEP ? NT * 16 : 1]) {
+  constexpr int N = NOB * NT * 16, S = rc_rows_stride(NOB, NT), NFR = rc_rfr(NOB, NT, false);
+  static_assert(CH == kRcChunkFrags, "rc_rows_at places the block by the ring's chunk");
+  static_assert(FBASE / CH == (FBASE + NFR - 1) / CH, "a row table lies in one chunk of the ring");
+  static_assert(FBASE + NFR <= NF, "inside the stream");
+  if (FBASE > 0 && FBASE % CH == 0) ws_advance<NF, W, CH>(w, FBASE / CH);
+  const float* row = w.ring + (FBASE % (2 * CH)) * 64 + (w.lane >> 5) * S;      // this half-wave's row
+  const float* bias = w.ring + (FBASE % (2 * CH)) * 64 + S + N;
+  float part[PT][NO][2];
+#pragma unroll
+  for (int p = 0; p < PT; ++p)
+#pragma unroll
+    for (int o = 0; o < NO; ++o) { part[p][o][0] = 0.0f; part[p][o][1] = 0.0f; }
+#pragma unroll
+  for (int o = 0; o < NO; ++o)
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const f32x4 wv4 = *reinterpret_cast<const f32x4*>(row + (o * NT + t) * 16 + 4 * r4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = 4 * r4 + i;
+          const float wv = wv4[i];
+          if constexpr (KEEP) { if (o == 0) keep[t * 16 + r] = wv; }
+#pragma unroll
+          for (int p = 0; p < PT; ++p) part[p][o][r & 1] = __builtin_fmaf(relu0(hid[p][t][r]), wv, part[p][o][r & 1]);
+        }
+      }
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    const float b = bias[o];
+#pragma unroll
+    for (int p = 0; p < PT; ++p) {
+      float sum = part[p][o][0] + part[p][o][1];
+      sum = sum + __shfl_xor(sum, 32, 64);
+      out[p][o] = sum + b;
+    }
+  }
+}
+template <int NT, int NO, int FBASE, int NF, bool KEEP = false, int W = kWaves, int NOB = NO, int CH = kChunk, class WS = WStream>
+__device__ __forceinline__ void dot_rows1(const WS& w, const f32x16 (&hid)[NT], float (&out)[NO],
+                                          float (&keep)[KEEP ? NT * 16 : 1]) {
+  const f32x16 (&h1)[1][NT] = reinterpret_cast<const f32x16 (&)[1][NT]>(hid);
+  float (&o1)[1][NO] = reinterpret_cast<float (&)[1][NO]>(out);
+  dot_rows<1, NT, NO, FBASE, NF, KEEP, W, NOB, CH, WS>(w, h1, o1, keep);
+}
+// an output block of the shader in the layout SF names (ShaderFragsL::kRows)
+template <class SF, int NT, int NO, int FBASE, int NF, class WS>
+__device__ __forceinline__ void dot_out_sf(const WS& w, const f32x16 (&hid)[NT], float (&out)[NO], float (&keep)[1]) {
+  if constexpr (SF::kRows) dot_rows1<NT, NO, FBASE, NF, false, kWaves, NO, kChunk, WS>(w, hid, out, keep);
+  else dot_out1<NT, NO, FBASE, NF, false, kWaves, NO, kChunk, WS>(w, hid, out, keep);
+}
+
 __device__ __forceinline__ float softplus(float x) {
   // jax.nn.softplus = logaddexp(x, 0) = max(x, 0) + log1p(exp(-|x|))
   return fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));
@@ -643,12 +705,7 @@ constexpr int kShActSteps = 102;
 constexpr int kStepIde = 48;
 constexpr int kStepBias = 84;
 
-// fragment offsets of the shader's layers inside its weight stream (host: rc_api.hip, same order)
-struct ShaderFrags {
-  static constexpr int F_H = 0, F_S0 = F_H + rc_lfr(49, 1), F_I0 = F_S0 + rc_lfr(85, 8), F_I1 = F_I0 + rc_lfr(49, 2), F_IO = F_I1 + rc_lfr(33, 2),
-                       F_S1 = F_IO + rc_dfr(1, 2), F_S2 = F_S1 + rc_lfr(65, 4), F_SB = F_S2 + rc_lfr(65, 4), F_SO = F_SB + rc_lfr(64, 4),
-                       COUNT = F_SO + rc_dfr(3, 4);
-};
+// fragment offsets of the shader's layers inside its weight stream: ShaderFrags / ShaderFragsL<ROWS, F0> (rc_pack_host.h)
 
 struct ShaderConsts { float roughness_bias, irradiance_bias, ambient_bias, rgb_max, slf_ambient_bias; };
 struct ShadeOut { float rgb[3], ad[3], idf[3], is[3], tint[3]; };
@@ -663,7 +720,7 @@ struct ShadeOut { float rgb[3], ad[3], idf[3], is[3], tint[3]; };
 #else
 #define RC_TSTAMP(i) do { } while (0)
 #endif
-template <int F0, int NF, class WS = WStream>
+template <int F0, int NF, class WS = WStream, class SF = ShaderFrags>
 __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int lane, int h, float nx, float ny, float nz,
                                                 float vx, float vy, float vz, const ShaderConsts& k,
                                                 unsigned long long* st = nullptr) {
@@ -679,8 +736,8 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
   {
     f32x16 acc[1];
     acc[0] = zero16();
-    if constexpr (kRcSplit) mlp_layer_x<1, 49, F0 + ShaderFrags::F_H, NF, 6, true>(ws, act, acc, fpc);
-    else mlp_layer<1, 49, F0 + ShaderFrags::F_H, NF>(ws, act, acc);
+    if constexpr (kRcSplit) mlp_layer_x<1, 49, F0 + SF::F_H, NF, 6, true>(ws, act, acc, fpc);
+    else mlp_layer<1, 49, F0 + SF::F_H, NF>(ws, act, acc);
     // by accumulator register (same on both half-waves): 0 roughness, 1-3 tint, 4-6 ambient irradiance, 7-9 irradiance
     // Lanes j and j + 32 hold the same sample, so each transcendental is evaluated once, in pairs (softplus_pair):
     // (rough, ad0) (ad1, ad2) (idf0, idf1) here, (idf2, amb0) (amb1, amb2) behind the SLF tail, (tint0, tint1) here and
@@ -742,8 +799,8 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
   f32x16 s0[8];
 #pragma unroll
   for (int t = 0; t < 8; ++t) s0[t] = zero16();
-  if constexpr (kRcSplit) mlp_layer_x<8, 85, F0 + ShaderFrags::F_S0, NF, 6, false>(ws, act, s0, fpc);      // blocks 6-10 (IDE | bias) from act
-  else mlp_layer<8, 85, F0 + ShaderFrags::F_S0, NF>(ws, act, s0);
+  if constexpr (kRcSplit) mlp_layer_x<8, 85, F0 + SF::F_S0, NF, 6, false>(ws, act, s0, fpc);      // blocks 6-10 (IDE | bias) from act
+  else mlp_layer<8, 85, F0 + SF::F_S0, NF>(ws, act, s0);
   RC_TSTAMP(3);
   // ---- integrated BRDF: (bottleneck, n.v) 129 -> 64 -> 64 -> 1 (nerf.py:461-482), first layer on the feature
   float ibrdf;
@@ -752,15 +809,15 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     ib[0] = zero16(); ib[1] = zero16();
     // IDE is dead after s0': its first step becomes the (n.v | bias) step right behind the 48 feature steps
     act[48 * 64] = h == 0 ? dot_nv : 1.0f;
-    if constexpr (kRcSplit) mlp_layer_x<2, 49, F0 + ShaderFrags::F_I0, NF, 6, false>(ws, act, ib, fpc);      // step 48 carries n.v: no bias block
-    else mlp_layer<2, 49, F0 + ShaderFrags::F_I0, NF>(ws, act, ib);
+    if constexpr (kRcSplit) mlp_layer_x<2, 49, F0 + SF::F_I0, NF, 6, false>(ws, act, ib, fpc);      // step 48 carries n.v: no bias block
+    else mlp_layer<2, 49, F0 + SF::F_I0, NF>(ws, act, ib);
     // the IBRDF tail takes relu(ib) and its bias step in registers
     BHand<2, true> hi;
     hand_off<2, true>(ib, lane, hi);
     ib[0] = zero16(); ib[1] = zero16();
-    mlp_layer_h<2, 2, true, F0 + ShaderFrags::F_I1, NF>(ws, hi, ib);
+    mlp_layer_h<2, 2, true, F0 + SF::F_I1, NF>(ws, hi, ib);
     float o[1], nokeep[1];
-    dot_out1<2, 1, F0 + ShaderFrags::F_IO, NF>(ws, ib, o, nokeep);     // output_integrated_brdf_layer on relu(ib)
+    dot_out_sf<SF, 2, 1, F0 + SF::F_IO, NF>(ws, ib, o, nokeep);     // output_integrated_brdf_layer on relu(ib)
     sigmoid_pair(h, tint2_raw, o[0] + 1.0986123f, tint[2], ibrdf);        // + log(3), nerf.py:481
   }
   RC_TSTAMP(4);
@@ -774,19 +831,19 @@ __device__ __forceinline__ ShadeOut shader_tile(const WS& ws, float* act, int la
     hand_off<4, true>(acc, lane, hs);
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = zero16();
-    mlp_layer_h<4, 4, true, F0 + ShaderFrags::F_S1, NF>(ws, hs, acc);
+    mlp_layer_h<4, 4, true, F0 + SF::F_S1, NF>(ws, hs, acc);
     hand_off<4, true>(acc, lane, hs);
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = zero16();
     RC_TSTAMP(5);
-    mlp_layer_h<4, 4, true, F0 + ShaderFrags::F_S2, NF>(ws, hs, acc);
+    mlp_layer_h<4, 4, true, F0 + SF::F_S2, NF>(ws, hs, acc);
     BHand<4, false> hb;
     hand_off<4, false>(acc, lane, hb);
     RC_TSTAMP(6);
-    mlp_layer_h<4, 4, false, F0 + ShaderFrags::F_SB, NF>(ws, hb, skip);
+    mlp_layer_h<4, 4, false, F0 + SF::F_SB, NF>(ws, hb, skip);
     RC_TSTAMP(7);
     float o[3], nokeep[1];
-    dot_out1<4, 3, F0 + ShaderFrags::F_SO, NF>(ws, skip, o, nokeep);   // output_ambient_rgb_layer on relu(layer_bottleneck)
+    dot_out_sf<SF, 4, 3, F0 + SF::F_SO, NF>(ws, skip, o, nokeep);   // output_ambient_rgb_layer on relu(layer_bottleneck)
     float sp_idf2, sp_amb[3];
     softplus_pair(h, idf2_raw, o[0] + k.slf_ambient_bias, sp_idf2, sp_amb[0]);
     softplus_pair(h, o[1] + k.slf_ambient_bias, o[2] + k.slf_ambient_bias, sp_amb[1], sp_amb[2]);

@@ -89,7 +89,7 @@ __device__ __forceinline__ ShadeRegs fetch_shade(const RcShadeRec& q) {
 template <int K, int FB, int NF, class WS>
 __device__ __forceinline__ float density_level64(const WS& ws, float* act_wave, int lane, const float (&f)[K]) {
   constexpr int KS0 = (K + 1) / 2 + 1;
-  using FR = DensFrags<KS0>;
+  using FR = FusedDens<KS0, FB>;
   const int tile = lane >> 5, j = lane & 31, h = lane >> 5;
   // scatter the features into B-operand slots: feature k of point (tile, j) -> step k/2, lane j + 32 (k & 1)
 #pragma unroll
@@ -111,7 +111,8 @@ __device__ __forceinline__ float density_level64(const WS& ws, float* act_wave, 
   for (int p = 0; p < 2; ++p) { acc[p][0] = zero16(); acc[p][1] = zero16(); }
   mlp_layer_pth<2, 2, 2, true, FB + FR::D1, NF>(ws, hd, acc);
   float out[2][1], nokeep[1];
-  dot_out<2, 2, 1, FB + FR::DO, NF>(ws, acc, out, nokeep);       // output_density_layer on relu(acc), both point-tiles
+  if constexpr (kRcFusedRows) dot_rows<2, 2, 1, FB + FR::DO, NF>(ws, acc, out, nokeep);
+  else dot_out<2, 2, 1, FB + FR::DO, NF>(ws, acc, out, nokeep);       // output_density_layer on relu(acc), both point-tiles
   // the dot product is complete on both half-waves: sample `lane` = (tile = lane >> 5, point lane & 31)
   return tile == 0 ? out[0][0] : out[1][0];
 }
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   }
   RC_FSTAMP(8);
   // density MLP of the last level on one tile (same code as k_density_mlp<17, GRAD>)
-  using FR = DensFrags<17>;
+  using FR = FusedDens<17, F_L2>;
   float density, npx, npy, npz, ngx = 0.0f, ngy = 0.0f, ngz = 0.0f;
   {
     f32x16 acc[2];
@@ -313,7 +314,8 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
     }
     park<2, true>(acc, act, 0);               // hidden feature: stays at [0,32) for the shader
     float out[4], wout[GRAD ? 32 : 1];
-    dot_out1<2, 4, F_L2 + FR::DO, NF, GRAD>(ws, acc, out, wout);      // density + predicted normals on relu(acc)
+    if constexpr (kRcFusedRows) dot_rows1<2, 4, F_L2 + FR::DO, NF, GRAD>(ws, acc, out, wout);
+    else dot_out1<2, 4, F_L2 + FR::DO, NF, GRAD>(ws, acc, out, wout);      // density + predicted normals on relu(acc)
     if constexpr (!FRONT) asm volatile("" :: RC_SHADE_PINS(k));
     density = density_of(g2.density_bias, out[0], cx, cy, cz, g2.bbox);
     npx = out[1]; npy = out[2]; npz = out[3];
@@ -365,7 +367,9 @@ __global__ __launch_bounds__(kWaves * 64) void k_cache_fused(RcFusedArgs a) {
   ShadeOut so;
   for (int c = 0; c < 3; ++c) { so.rgb[c] = act[c * 64]; so.ad[c] = npx; so.idf[c] = npy; so.is[c] = npz; so.tint[c] = density; }
 #else
-  const ShadeOut so = shader_tile<F_SH, NF>(ws, act, lane, h, npx, npy, npz, k.viewdirs[3 * ray], k.viewdirs[3 * ray + 1],
+  // (NF_FUSED, which is NF here: FRONT has returned above, and its instantiation of what follows -- never reached -- must not
+  // name a stream that ends in front of the shader's row tables, whose reader asserts that its block lies inside the stream)
+  const ShadeOut so = shader_tile<F_SH, NF_FUSED, WStream, FusedShader>(ws, act, lane, h, npx, npy, npz, k.viewdirs[3 * ray], k.viewdirs[3 * ray + 1],
                                             k.viewdirs[3 * ray + 2], k.sh);
 #endif
 

@@ -17,16 +17,10 @@ constexpr int kAppTmp = 33;                   // act steps [33, 49): appearance 
 constexpr int kFusedDense = kRcFusedDenseLevels;               // grid levels [0, 3) of every grid are dense (16, 32, 64 cells a side), the rest hashed: fused_geometry_ok
 constexpr int kJac = 49;                      // act steps [49, 97): d feature / d position of the level-2 density grid
 
-// fragments of the fused weight stream
-template <int KS0> struct DensFrags {
-  static constexpr int NO = KS0 == 17 ? 4 : 1;       // output rows: density (+ 3 predicted normals on the last level)
-  static constexpr int D0 = 0, D1 = rc_lfr32(KS0, 2), DO = D1 + rc_lfr32(33, 2), B1 = DO + rc_dfr32(NO, 2), B0 = B1 + rc_lfr32(32, 2), END = B0 + rc_lfr32(32, 1);
-};
-constexpr int F_L0 = 0;                              // K = 6: KS0 = 4
-constexpr int F_L1 = F_L0 + DensFrags<4>::B1;        // K = 7: KS0 = 5
-constexpr int F_L2 = F_L1 + DensFrags<5>::B1;        // K = 32: KS0 = 17, with the 96 backward fragments
-constexpr int F_SH = rc_align_piece(F_L2 + DensFrags<17>::END);      // the shader's split layers start on a whole piece
-constexpr int NF_FUSED = F_SH + ShaderFrags::COUNT;
+// fragments of the fused weight stream: DensFrags, F_L0 .. F_SH, NF_FUSED, FusedDens and FusedShader are rc_pack_host.h's
+// (host-only, so that hostcheck prints them); the one-wave kernel of a split build reads the output rows as tables
+// (kRcFusedRows), every other kernel the fragment form
+static_assert(kChunk == kRcChunkFrags, "rc_rows_at places the row tables by the ring's chunk");
 
 #ifdef RC_STAMPS
 #define RC_FSTAMP(i) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); stamps[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)

@@ -84,6 +84,67 @@ constexpr int rc_lfr32(int ks, int nt) { return ks * nt; }
 constexpr int rc_dfr32(int no, int nt) { return no * (nt * 16 + 1); }
 constexpr int rc_align_piece(int f) { return kRcSplit ? (f + 3) / 4 * 4 : f; }
 
+// ---------------------------------------------------------------------------------------------
+// Output rows as a table (the fused streams of the one-wave kernel only: kRcFusedRows).  A dot_out fragment holds two
+// distinct floats (one per half-wave; a bias fragment one), so a block of NO outputs over NT tiles ships NO (16 NT + 1)
+// fragments for 2 NO 16 NT + NO values.  The table form of the same block, in floats from the block's first fragment:
+//   [0, n)            half-wave 0: [output][tile][register]      n = NO * NT * 16
+//   [S, S + n)        half-wave 1, S = rc_rows_stride: n, or n + 32 where n is a multiple of 64 -- the two rows then lie
+//                     128 bytes apart modulo the 256 bytes of a bank row, and the two addresses of a read (lanes 0-31 one,
+//                     lanes 32-63 the other) never meet on a bank
+//   [S + n, S + n + NO)  the biases
+// padded with zeros to whole fragments (to whole 1-KiB pieces where a split layer follows).  dot_rows (rc_dev_mlp.h) reads
+// it; a block never straddles a chunk of the ring (rc_rows_at moves it to the next chunk's start if it would): a lane's
+// address depends on its half-wave, so both rows must be resident together.
+// ---------------------------------------------------------------------------------------------
+constexpr int kRcChunkFrags = 64;                  // fragments per chunk of the weight ring (rc_dev_mlp.h kChunk)
+constexpr bool kRcFusedRows = kRcSplit && !RC_TEAM_KERNEL;
+constexpr int rc_rows_stride(int no, int nt) { return (no * nt * 16 + 31) / 32 * 32 + (((no * nt * 16 + 31) / 32) % 2 == 0 ? 32 : 0); }
+constexpr int rc_rows_floats(int no, int nt) { return rc_rows_stride(no, nt) + no * nt * 16 + no; }
+constexpr int rc_rfr(int no, int nt, bool piece) { return piece ? (rc_rows_floats(no, nt) + 255) / 256 * 4 : (rc_rows_floats(no, nt) + 63) / 64; }
+constexpr int rc_rows_at(int f, int nfr) {
+  return f / kRcChunkFrags != (f + nfr - 1) / kRcChunkFrags ? (f + kRcChunkFrags - 1) / kRcChunkFrags * kRcChunkFrags : f;
+}
+
+// fragment offsets of the shader's layers inside its weight stream (host: rc_api.hip, same order).  ROWS: the two output
+// blocks as row tables, the stream starting at fragment F0 of its kernel's stream (the fused streams); the fragment form
+// (k_cache_shader, the texture atlas, the material stage, the two-wave kernel) does not depend on F0.
+namespace rcdev {
+template <bool ROWS, int F0 = 0>
+struct ShaderFragsL {
+  static constexpr bool kRows = ROWS;
+  static constexpr int F_H = 0, F_S0 = F_H + rc_lfr(49, 1), F_I0 = F_S0 + rc_lfr(85, 8), F_I1 = F_I0 + rc_lfr(49, 2),
+                       F_IO = ROWS ? rc_rows_at(F0 + F_I1 + rc_lfr(33, 2), rc_rfr(1, 2, kRcSplit)) - F0 : F_I1 + rc_lfr(33, 2),
+                       F_S1 = F_IO + (ROWS ? rc_rfr(1, 2, kRcSplit) : rc_dfr(1, 2)), F_S2 = F_S1 + rc_lfr(65, 4), F_SB = F_S2 + rc_lfr(65, 4),
+                       F_SO = ROWS ? rc_rows_at(F0 + F_SB + rc_lfr(64, 4), rc_rfr(3, 4, kRcSplit)) - F0 : F_SB + rc_lfr(64, 4),
+                       COUNT = F_SO + (ROWS ? rc_rfr(3, 4, kRcSplit) : rc_dfr(3, 4));
+  static_assert((F0 + F_S1) % 4 == 0 || !kRcSplit, "the layer behind a row table starts on a whole piece");
+};
+using ShaderFrags = ShaderFragsL<false>;
+}  // namespace rcdev
+
+// fragments of the fused weight stream [density MLP 0 | 1 | 2 (+ backward fragments) | shader]
+namespace rcfused {
+template <int KS0, bool ROWS = false, int FB = 0> struct DensFrags {
+  static constexpr int NO = KS0 == 17 ? 4 : 1;       // output rows: density (+ 3 predicted normals on the last level)
+  static constexpr int D0 = 0, D1 = rc_lfr32(KS0, 2),
+                       DO = ROWS ? rc_rows_at(FB + D1 + rc_lfr32(33, 2), rc_rfr(NO, 2, false)) - FB : D1 + rc_lfr32(33, 2),
+                       B1 = DO + (ROWS ? rc_rfr(NO, 2, false) : rc_dfr32(NO, 2)), B0 = B1 + rc_lfr32(32, 2), END = B0 + rc_lfr32(32, 1);
+};
+template <bool ROWS> struct FusedFrags {
+  static constexpr int L0 = 0;                                          // K = 6: KS0 = 4
+  static constexpr int L1 = L0 + DensFrags<4, ROWS, L0>::B1;            // K = 7: KS0 = 5
+  static constexpr int L2 = L1 + DensFrags<5, ROWS, L1>::B1;            // K = 32: KS0 = 17, with the 96 backward fragments
+  static constexpr int SH = rc_align_piece(L2 + DensFrags<17, ROWS, L2>::END);      // the shader's split layers start on a whole piece
+  static constexpr int NF = SH + rcdev::ShaderFragsL<ROWS, SH>::COUNT;
+  static_assert(SH % 4 == 0 || !kRcSplit, "F_SH: the shader's split layers start on a whole 1-KiB piece");
+};
+constexpr int F_L0 = FusedFrags<kRcFusedRows>::L0, F_L1 = FusedFrags<kRcFusedRows>::L1, F_L2 = FusedFrags<kRcFusedRows>::L2,
+              F_SH = FusedFrags<kRcFusedRows>::SH, NF_FUSED = FusedFrags<kRcFusedRows>::NF;
+template <int KS0, int FB> using FusedDens = DensFrags<KS0, kRcFusedRows, FB>;       // a density MLP of the fused stream at fragment FB
+using FusedShader = rcdev::ShaderFragsL<kRcFusedRows, F_SH>;
+}  // namespace rcfused
+
 namespace rcpack {
 
 struct HostLayer {
@@ -147,6 +208,23 @@ inline std::vector<float> pack_dot(const std::vector<Col>& outs, int ntiles, boo
   for (const Col& c : outs)
     for (int lane = 0; lane < 64; ++lane) v.push_back(c.L ? c.L->bias[c.col] : 0.0f);
   if (pad_to_piece) v.resize((size_t)rc_dfr((int)outs.size(), ntiles) * 64, 0.0f);
+  return v;
+}
+
+// The same block as a row table (rc_rows_stride above, dot_rows in rc_dev_mlp.h): the two distinct floats of every weight
+// fragment of pack_dot -- what lanes 0 and 32 hold -- and the one of every bias fragment.
+inline std::vector<float> pack_dot_rows(const std::vector<Col>& outs, int ntiles, bool pad_to_piece = kRcSplit) {
+  const int no = (int)outs.size(), n = no * ntiles * 16, stride = rc_rows_stride(no, ntiles);
+  std::vector<float> v((size_t)rc_rfr(no, ntiles, pad_to_piece) * 64, 0.0f);
+  for (int h = 0; h < 2; ++h)
+    for (int o = 0; o < no; ++o)
+      for (int t = 0; t < ntiles; ++t)
+        for (int r = 0; r < 16; ++r) {
+          const Col& c = outs[o];
+          const int row = acc_feat(t, r, h) + c.row_off;
+          v[(size_t)h * stride + (o * ntiles + t) * 16 + r] = (c.L && row < c.L->in) ? c.L->kernel[(size_t)row * c.L->out + c.col] : 0.0f;
+        }
+  for (int o = 0; o < no; ++o) v[(size_t)stride + n + o] = outs[o].L ? outs[o].L->bias[outs[o].col] : 0.0f;
   return v;
 }
 
